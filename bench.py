@@ -16,7 +16,10 @@ not set and --gpus N > 1, from THIS script: the parent — before anything touch
 starts N fresh child processes of itself with those variables set, relays rank 0's JSON line
 and exits non-zero if any child did.
 
-Prints ONE JSON line on rank 0 (contract in the round prompt).
+A plain run sets up, warms up, times --steps outer iterations, writes the last step's mesh with --dump-outputs DIR and
+prints ONE JSON line on rank 0.  Everything else it can measure (roofline, the reference's own call, fresh-process calls,
+other schedules, solvers and tolerances, the copy ceiling, per-collective times, the CPU baseline and its parity) runs
+with --full only.
 """
 from __future__ import annotations
 
@@ -44,8 +47,14 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", type=int, default=3, help="scene config (multiviewstitch_amd/scene.py); 3 = metric workload")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: roofline (HIP-event sampling inside the timed region + a pass of its own), the reference's "
+                         "call on fresh handles and in fresh processes, single-solve schedule, tolerance headroom, copy ceiling, "
+                         "alternative solver, per-collective times (N > 1), CPU baseline + parity; the --no-* options trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the mesh the last step left (vertices, normals, rotations; float64) as DIR/<name>.npy")
     ap.add_argument("--phases", action="store_true", help="extra instrumented pass: per-phase HIP-event times to stderr")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and its parity check")
     ap.add_argument("--no-alt-solver", action="store_true", help="skip the comparison run with the one-kernel-per-iteration CG (profiles of the default solver alone)")
     ap.add_argument("--no-single-solve", action="store_true", help="skip the run with one global solve per outer iteration (kernel-trace profiles: launches per outer iteration then count the metric's schedule only)")
     ap.add_argument("--no-tolerance-headroom", action="store_true", help="skip the runs at cg_tol 1e-7 / 1e-6 reported beside the headline")
@@ -58,7 +67,10 @@ def parse_args(argv=None):
                                                       "the N > 1 code path with several ranks sharing one GPU)")
     ap.add_argument("--dry-run", action="store_true", help="launcher rehearsal without a GPU: every rank joins the process group "
                                                            "(use --backend gloo), one all-reduce, rank 0 prints a JSON line")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def dry_run(args) -> int:
@@ -167,6 +179,15 @@ def cpu_model():
     return "unknown"
 
 
+def dump_outputs(out_dir, d):
+    """What a caller of the timed path receives after its last step: the deformed mesh (float64, ~6.5 MB at config 3)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"vertices": d.vertices(), "normals": d.normals(), "rotations": d.rotations()}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    log(f"[bench] outputs of the last timed step -> {out_dir}: " + ", ".join(f"{n} {a.shape}" for n, a in arrays.items()))
+
+
 def main():
     args = parse_args()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -231,7 +252,7 @@ def main():
             worst["status"] = max(worst["status"], st["status"])
         return st
 
-    exchange = None
+    exchange = shard = bufs = None
     if world > 1:
         shard = mdist.EngineShard(d, device)
         bufs = shard.buffers(K, world)
@@ -309,8 +330,9 @@ def main():
         log(f"[bench r{rank}] warmup done: solver iterations={st['cg_iters']} arap_iters_run={st['arap_iters_run']} "
             f"n_valid={st['n_valid']} worst rel residual of the warm-up batch={st['worst_rel_residual_in_batch']:.2e}")
     worst.update(rel=0.0, missed=0, solves=0, status=0)
-    d.enable_timing(3)                      # HIP events around the planned sweeps of the solves of every 8th pass (around every
-    fence()                                 # solve they cost 5 % of the step: scripts/timing_overhead.py)
+    if args.full:                           # HIP events around the planned sweeps of the solves of every 8th pass (around every
+        d.enable_timing(3)                  # solve they cost 5 % of the step: scripts/timing_overhead.py), for the roofline
+    fence()
     tb = time.perf_counter()
     st = run(args.steps)
     fence()
@@ -320,6 +342,75 @@ def main():
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    ms_per_step = 1e3 * elapsed / args.steps
+    value = args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, d)
+    timed = dict(worst)
+    log(f"[bench r{rank}] timed batch: worst true relative residual {timed['rel']:.2e} over {timed['solves']} solves, "
+        f"{timed['missed']} above cg_tol, status {timed['status']}")
+    V = len(sc.verts)
+    info = d.solver_info()
+    extras = {}
+    if args.full:
+        extras = measure_full(args, d=d, sc=sc, tp=tp, tn=tn, device=device, dev_id=dev_id, run=run, fence=fence, st=st, K=K, V=V,
+                              info=info, world=world, rank=rank, P_local=P_local, P_total=P_total, ms_per_step=ms_per_step,
+                              shard=shard, bufs=bufs, exchange=exchange)
+
+    if args.phases:
+        d.enable_timing(1)
+        run(args.steps)
+        fence()
+        tot = 0.0
+        for name in ("assoc", "graph", "smooth", "weights", "rhs", "cg", "tail", "local", "finalize"):
+            ms, n = d.kernel_time(name)
+            tot += ms
+            log(f"[phases r{rank}] {name:9s} {ms/args.steps:9.4f} ms/step  {n/args.steps:7.1f} launches/step")
+        log(f"[phases r{rank}] sum       {tot/args.steps:9.4f} ms/step")
+        d.enable_timing(0)
+
+    if rank == 0:
+        out = {
+            "metric": "nonrigid_outer_iterations_per_sec", "value": round(value, 3), "unit": "iter/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
+            "dtype_note": "fp64 geometry, right-hand sides, residuals and solution; the inexact LOCAL correction inside a patch sweep "
+                          "runs in f32 with bf16 neighbour directions (the fp64 true residual decides convergence)",
+            "data": "synthetic",
+            "config": {"workload": f"config{args.config}: {cfg['n_views']} views {cfg['w']}x{cfg['h']} inverse depth, "
+                                   f"P={P_total} target points, K={K} nodes, V={V} template vertices; step = associate + "
+                                   f"9-NN graph + 2 smoothing sweeps + ARAP(5, 1e-4) + geometry update",
+                       "points": P_total, "nodes": int(K), "vertices": V, "views_per_gpu": len(my_views),
+                       "global_solver": info["kind"], "solver_launches_per_step": int(st["cg_launches"]),
+                       "local_iters_per_step": int(st["cg_iters"]), "valid_nodes": int(st["n_valid"]),
+                       "parallelism": f"views sharded x{world}, template replicated"},
+            "regime": {"timed": f"outer iterations {args.warmup}..{args.warmup + args.steps - 1} of a fresh fit from the template pose",
+                       "first_outer_iteration_ms": round(first_ms, 3),
+                       "event_sampling_in_timed_region": bool(args.full),      # --full: the roofline's HIP events (every 8th pass)
+                       "note": "fewer than half of the nodes hold a correspondence in this regime (the reference rejects nodes whose "
+                               "mean direction is nearly tangential, |cos| < 0.1); past ~170 outer iterations of a fit (which the reference "
+                               "never runs: counter = 1) one sliver triangle stalls the sweeps and the solver switches to Anderson-mixed "
+                               "sweeps: 0.63-0.68 ms per step (profiles/r03/soak_400_outer.log, DESIGN.md §5)"},
+            "solver": {"worst_rel_residual_timed": timed["rel"], "solves_timed": timed["solves"],
+                       "unconverged_solves_timed": timed["missed"], "status": timed["status"], "cg_tol": d.params.cg_tol},
+        }
+        out.update(extras)
+        if world > 1:
+            out["ranks"] = dist.get_world_size()
+            out["backend"] = dist.get_backend()
+            out["gpus_visible"] = n_dev
+        print(json.dumps(out), flush=True)
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def measure_full(args, *, d, sc, tp, tn, device, dev_id, run, fence, st, K, V, info, world, rank, P_local, P_total, ms_per_step,
+                 shard, bufs, exchange):
+    """--full: every figure beside the headline, measured after the timed region on the same handle and inputs.  Returns the
+    result-line fields it fills (the headline's own fields stay as the plain run computed them)."""
+    import torch
+    import torch.distributed as dist
+    from multiviewstitch_amd import deformation
     # (sampled passes bracket the planned sweeps of each solve; the idle flags those very launches left are read back: "cg_idle"
     #  counts them, and every bracket is filed under its composition "cg:a<active>:i<idle>")
     cg_ms, cg_launches = d.kernel_time("cg")
@@ -338,17 +429,9 @@ def main():
         fence()
         tail_ms, tail_launches = d.kernel_time("tail")
         d.enable_timing(0)
-    timed = dict(worst)
-    log(f"[bench r{rank}] timed batch: worst true relative residual {timed['rel']:.2e} over {timed['solves']} solves, "
-        f"{timed['missed']} above cg_tol, status {timed['status']}")
-
-    ms_per_step = 1e3 * elapsed / args.steps
-    value = args.steps / elapsed
 
     # ---------------------------------------------------------------- roofline ----
     # Dominant kernel = the global-solve kernel (the "cg" phase timer brackets exactly its launches).
-    V = len(sc.verts)
-    info = d.solver_info()
     deg = np.bincount(sc.faces.reshape(-1), minlength=V)          # closed manifold: degree == facet count
     if info["kind"] == "patch":
         # k_ras_sweep (schwarz.hip): one launch = one overlapping-patch sweep over all V rows, 3 rhs fused.
@@ -599,18 +682,6 @@ def main():
         else:
             collectives["bytes_all_gather_in_per_rank"] = int(K) * 392 * world
 
-    if args.phases:
-        d.enable_timing(1)
-        run(args.steps)
-        fence()
-        tot = 0.0
-        for name in ("assoc", "graph", "smooth", "weights", "rhs", "cg", "tail", "local", "finalize"):
-            ms, n = d.kernel_time(name)
-            tot += ms
-            log(f"[phases r{rank}] {name:9s} {ms/args.steps:9.4f} ms/step  {n/args.steps:7.1f} launches/step")
-        log(f"[phases r{rank}] sum       {tot/args.steps:9.4f} ms/step")
-        d.enable_timing(0)
-
     # ------------------------------------------------- CPU baseline + parity of this very workload ----
     cpu_baseline = None
     parity = None
@@ -700,49 +771,20 @@ def main():
                                             "sample": f"the next {n2} outer iterations"}
         log(f"[bench] cpu_baseline: {n_it} it in {t_cpu:.2f}s single thread, {n2} it in {t2:.2f}s on {threads} threads ({cpu_model()})")
 
-    if rank == 0:
-        out = {
-            "metric": "nonrigid_outer_iterations_per_sec", "value": round(value, 3), "unit": "iter/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
-            "dtype_note": "fp64 geometry, right-hand sides, residuals and solution; the inexact LOCAL correction inside a patch sweep "
-                          "runs in f32 with bf16 neighbour directions (the fp64 true residual decides convergence)",
-            "data": "synthetic",
-            "config": {"workload": f"config{args.config}: {cfg['n_views']} views {cfg['w']}x{cfg['h']} inverse depth, "
-                                   f"P={P_total} target points, K={K} nodes, V={V} template vertices; step = associate + "
-                                   f"9-NN graph + 2 smoothing sweeps + ARAP(5, 1e-4) + geometry update",
-                       "points": P_total, "nodes": int(K), "vertices": V, "views_per_gpu": len(my_views),
-                       "global_solver": info["kind"], "solver_launches_per_step": int(st["cg_launches"]),
-                       "local_iters_per_step": int(st["cg_iters"]), "valid_nodes": int(st["n_valid"]),
-                       "parallelism": f"views sharded x{world}, template replicated"},
-            "regime": {"timed": f"outer iterations {args.warmup}..{args.warmup + args.steps - 1} of a fresh fit from the template pose",
-                       "first_outer_iteration_ms": round(first_ms, 3),
-                       "note": "fewer than half of the nodes hold a correspondence in this regime (the reference rejects nodes whose "
-                               "mean direction is nearly tangential, |cos| < 0.1); past ~170 outer iterations of a fit (which the reference "
-                               "never runs: counter = 1) one sliver triangle stalls the sweeps and the solver switches to Anderson-mixed "
-                               "sweeps: 0.63-0.68 ms per step (profiles/r03/soak_400_outer.log, DESIGN.md §5)"},
-            "solver": {"worst_rel_residual_timed": timed["rel"], "solves_timed": timed["solves"],
-                       "unconverged_solves_timed": timed["missed"], "status": timed["status"], "cg_tol": d.params.cg_tol},
-            "roofline": roofline, "cpu_baseline": cpu_baseline, "parity": parity,
-        }
-        if world > 1:
-            out["ranks"] = dist.get_world_size()
-            out["backend"] = dist.get_backend()
-            out["gpus_visible"] = n_dev
-            out["collectives"] = collectives
-        if ref_sched is not None:
-            out["reference_schedule"] = ref_sched        # the call the reference makes: fresh Deformation + UniformSampling + one Deform
-        if headroom:
-            out["tolerance_headroom"] = {"rows": headroom, "headline_cg_tol": d.params.cg_tol,
-                                         "note": "the same window at looser solve tolerances, beside the headline (which is measured at the default 1e-8); integers = n_valid and "
-                                                 "arap_iters_run of every compared iteration; 25-iteration tables for configs 1-4: profiles/r04/tolerance_headroom.md"}
-        if single is not None:
-            out["single_solve_schedule"] = single       # one ARAP global+local pass per outer iteration
-        if alt is not None:
-            out["alt_solver"] = alt
-        print(json.dumps(out), flush=True)
+    extras = {"roofline": roofline, "cpu_baseline": cpu_baseline, "parity": parity}
     if world > 1:
-        dist.destroy_process_group()
+        extras["collectives"] = collectives
+    if ref_sched is not None:
+        extras["reference_schedule"] = ref_sched        # the call the reference makes: fresh Deformation + UniformSampling + one Deform
+    if headroom:
+        extras["tolerance_headroom"] = {"rows": headroom, "headline_cg_tol": d.params.cg_tol,
+                                        "note": "the same window at looser solve tolerances, beside the headline (which is measured at the default 1e-8); integers = n_valid and "
+                                                "arap_iters_run of every compared iteration; 25-iteration tables for configs 1-4: profiles/r04/tolerance_headroom.md"}
+    if single is not None:
+        extras["single_solve_schedule"] = single       # one ARAP global+local pass per outer iteration
+    if alt is not None:
+        extras["alt_solver"] = alt
+    return extras
 
 
 if __name__ == "__main__":

@@ -2,7 +2,7 @@
 # per-dispatch durations AND the idle gap in front of every kernel for a few outer iterations of the default bench (rocprofv3 kernel trace):
 # where the step's time goes that no kernel accounts for
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-rm -rf /tmp/kt && rocprofv3 --kernel-trace --output-format csv -d /tmp/kt -- python3 bench.py --no-cpu-baseline > /dev/null 2> /tmp/kt.err || { tail -5 /tmp/kt.err; exit 1; }
+rm -rf /tmp/kt && rocprofv3 --kernel-trace --output-format csv -d /tmp/kt -- python3 bench.py --full --no-cpu-baseline > /dev/null 2> /tmp/kt.err || { tail -5 /tmp/kt.err; exit 1; }
 python3 - <<'PY'
 import csv, glob, collections
 f = glob.glob('/tmp/kt/*/*_kernel_trace.csv')[0]

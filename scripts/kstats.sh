@@ -1,7 +1,7 @@
 #!/bin/bash
 # quick per-kernel durations of the default bench under rocprofv3 (engine kernels only)
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-rm -rf /tmp/ks && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks -- python3 bench.py --no-cpu-baseline ${KS_ARGS} > /dev/null 2> /tmp/ks.err || { tail -5 /tmp/ks.err; exit 1; }
+rm -rf /tmp/ks && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks -- python3 bench.py --full --no-cpu-baseline ${KS_ARGS} > /dev/null 2> /tmp/ks.err || { tail -5 /tmp/ks.err; exit 1; }
 python3 - <<'PY'
 import csv, glob
 f = glob.glob('/tmp/ks/*/*_kernel_stats.csv')[0]

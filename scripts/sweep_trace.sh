@@ -1,7 +1,7 @@
 #!/bin/bash
 # per-dispatch durations of k_ras_sweep of the last outer iteration of the default bench (rocprofv3 kernel trace)
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-rm -rf /tmp/kt && rocprofv3 --kernel-trace --output-format csv -d /tmp/kt -- python3 bench.py --no-cpu-baseline > /dev/null 2> /tmp/kt.err || { tail -5 /tmp/kt.err; exit 1; }
+rm -rf /tmp/kt && rocprofv3 --kernel-trace --output-format csv -d /tmp/kt -- python3 bench.py --full --no-cpu-baseline > /dev/null 2> /tmp/kt.err || { tail -5 /tmp/kt.err; exit 1; }
 python3 - <<'PY'
 import csv, glob
 f = glob.glob('/tmp/kt/*/*_kernel_trace.csv')[0]

@@ -1,4 +1,4 @@
-"""Cost of the HIP-event instrumentation bench.py keeps on inside its timed region (enable_timing(2): two events per solve)."""
+"""Cost of the HIP-event instrumentation bench.py --full keeps on inside its timed region (enable_timing(2): two events per solve)."""
 import sys, time
 sys.path.insert(0, ".")
 import torch

@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define MVS_ABI_VERSION 4   /* 3: tracing hook, mvs_comm_set_exchange, view-sharded RemoveGround / LocalAlignmentCore; 4: mvs_deform_group_*, mvs_align_dev, mvs_retain_connect_region_dev / mvs_remove_ground_dev / mvs_part_recog_dev, mvs_trim (additive); mvs_local_alignment_core_sharded takes the rank */
+#define MVS_ABI_VERSION 4   /* 3: tracing hook, mvs_comm_set_exchange, view-sharded RemoveGround / LocalAlignmentCore; 4: mvs_deform_group_*, mvs_align_dev, mvs_retain_connect_region_dev / mvs_remove_ground_dev / mvs_part_recog_dev, mvs_trim (additive); mvs_local_alignment_core_sharded takes the rank; still 4, additive: mvs_visibility_cull(_dev), mvs_mesh_vertex_normals(_dev), mvs_processor_stitch_points / _cull_model (mvs_io.h) */
 
 enum mvs_status {
     MVS_OK            =  0,
@@ -245,6 +245,40 @@ int mvs_srt_apply(const double* pts, const double* normals, int64_t P,
 int mvs_srt_apply_dev(const double* pts_dev, const double* normals_dev, int64_t P,
                       double s, const double* R, const double* t, int inverse,
                       double* out_pts_dev, double* out_normals_dev, void* hip_stream);
+
+/* ------------------------------------------------- stitch tail (f1) -- */
+/* The visibility cull of Processor::AlignmentSeq: a point stays iff, for every sequence k0 and every camera c of k0, the point
+ * mapped into k0's frame projects inside c's image (Camera::GetImgCoordFromWorld, R/Camera/Camera.cpp:45-48,68-72, then
+ * CheckRange, R/Common/Utils.h:20-22).
+ *   MVS_CULL_SEQUENCES (:966-1004, before Poisson): segment k holds the points of sequence k (n_seg == n_seq); for k0 != k the
+ *     point is mapped by mvs_srt_relative(k0, k) forward (s R p + t, :979-982), for k0 == k it is not mapped at all (:973).
+ *   MVS_CULL_ALL_SEQ (:1064-1083, AllSeqProj on the Poisson model): every k0, its own sequence included, maps by the inverse
+ *     (1/s_k0) R_k0^T (p - t_k0); segments are independent point ranges (usually one).
+ * seg_off: host, n_seg + 1 ascending offsets from 0 into points; scales[n_seq], R[n_seq*9] (row-major), t[n_seq*3]: the SRT
+ * chain as AlignmentSeq holds it; cam_off: host, n_seq + 1 ascending offsets from 0 into cams (sequences may differ in camera
+ * count and image size).  keep[P] = 1 / 0, n_keep[n_seg] = kept points per segment.  Every test is exact fp64 (true divides). */
+enum mvs_cull_mode {
+    MVS_CULL_SEQUENCES = 0,
+    MVS_CULL_ALL_SEQ   = 1
+};
+int mvs_visibility_cull(const double* points, const int64_t* seg_off, int32_t n_seg, int32_t n_seq,
+                        const double* scales, const double* R, const double* t,
+                        const int32_t* cam_off, const mvs_camera* cams, int32_t mode,
+                        uint8_t* keep, int64_t* n_keep);
+/* Same with the points and the mask in HBM, enqueued on hip_stream (NULL = legacy default stream); returns once n_keep (host) is
+ * known, i.e. with the stream's work up to the cull complete. */
+int mvs_visibility_cull_dev(const double* points_dev, const int64_t* seg_off, int32_t n_seg, int32_t n_seq,
+                            const double* scales, const double* R, const double* t,
+                            const int32_t* cam_off, const mvs_camera* cams, int32_t mode,
+                            uint8_t* keep_dev, int64_t* n_keep, void* hip_stream);
+
+/* Mesh::CalculateVertexNormals for a general triangle list (R/PlyObj/PlyObj.cpp:139-185, what ReadObj computes for a file without
+ * `vn` lines, :3-16): the unit normal of every facet (the 1e-6 rescue of a short edge, n/|n| — a zero-area facet gives NaN) summed
+ * per vertex in ascending facet order (a facet listing a vertex twice counts twice), / count, normalised; a vertex of no facet
+ * gives NaN.  No manifold test: every mesh ReadObj accepts is accepted.  A facet index outside [0, V) is MVS_E_BAD_MESH. */
+int mvs_mesh_vertex_normals(int64_t V, const double* points, int64_t F, const int32_t* faces, double* out_normals);
+int mvs_mesh_vertex_normals_dev(int64_t V, const double* points_dev, int64_t F, const int32_t* faces_dev,
+                                double* out_normals_dev, void* hip_stream);
 
 /* ---------------------------------------------------- Alignment (a10-a15) -- */
 /* Template -> scan coarse alignment, class Alignment (R/Alignment/Alignment.h:21-36) and its helpers.

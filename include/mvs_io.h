@@ -60,6 +60,28 @@ int mvs_parts_read(const char* path, int64_t n_vertices, int32_t* labels /*n_ver
 int mvs_processor_deform(const char* model_obj, const char* template_obj, const char* parts_path, const double cam_R[9],
                          double dist_thres, const mvs_deform_params* params, const char* out_obj, mvs_deform_stats* stats);
 
+/* The tail of Processor::AlignmentSeq before Poisson (R/Processor/Processor.cpp:952-1040): for each sequence k, read
+ * npts_paths[k] (mvs_npts_read: float32 like `ifs >> float`, :958-963), cull it (mvs_visibility_cull, MVS_CULL_SEQUENCES,
+ * :966-1004), compact it and map it forward (s_k R_k p + t_k, R_k n, :1021-1027), then write out_dir/PSR%d.obj (points and
+ * normals, no facets, :1029-1030) and out_dir/PSR.npts (every sequence in order, :1033-1040).  The reference compacts in place and
+ * never resizes (:969-1003, :1022), so by default sequence k writes all P_k points: the kept ones in order, then the originals at
+ * [n_keep, P_k) as they were; flags MVS_STITCH_TRUNCATE writes the kept points only.  scales / R / t are the doubles AlignmentSeq
+ * holds in memory (mvs_srt_txt_read would pass them through float32, :1145-1165); cam_off / cams as mvs_visibility_cull.
+ * n_keep (n_seq, may be NULL) receives the kept counts. */
+#define MVS_STITCH_TRUNCATE 1u
+int mvs_processor_stitch_points(int32_t n_seq, const char* const* npts_paths, const double* scales, const double* R,
+                                const double* t, const int32_t* cam_off, const mvs_camera* cams, uint32_t flags,
+                                const char* out_dir, int64_t* n_keep);
+
+/* The trim of the Poisson model after GeometryRec (R/Processor/Processor.cpp:1057-1105): ReadObj(model_obj) — normals from the
+ * `vn` lines, computed as mvs_mesh_vertex_normals when the file has none (R/PlyObj/PlyObj.cpp:3-16) —, then with all_seq_proj
+ * (ParamParser::isAllSeqProj) the cull MVS_CULL_ALL_SEQ and the facet remap (a facet stays iff its three vertices do,
+ * :1064-1100), then Alignment::RetainConnectRegion (:1102-1103), then WriteObj(out_obj) (:1104).  V_out / F_out (may be NULL)
+ * receive the sizes written.  The SRT and cameras are validated as for mvs_visibility_cull even when all_seq_proj is 0. */
+int mvs_processor_cull_model(const char* model_obj, int32_t n_seq, const double* scales, const double* R, const double* t,
+                             const int32_t* cam_off, const mvs_camera* cams, int32_t all_seq_proj, const char* out_obj,
+                             int64_t* V_out, int64_t* F_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -100,6 +100,10 @@ _SIGS = {
     "mvs_srt_relative": (C.c_int, [_D, _VP, _VP, _D, _VP, _VP, _VP, _VP, _VP]),
     "mvs_srt_apply": (C.c_int, [_VP, _VP, _I64, _D, _VP, _VP, _I32, _VP, _VP]),
     "mvs_srt_apply_dev": (C.c_int, [_VP, _VP, _I64, _D, _VP, _VP, _I32, _VP, _VP, _VP]),
+    "mvs_visibility_cull": (C.c_int, [_VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _VP]),
+    "mvs_visibility_cull_dev": (C.c_int, [_VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP]),
+    "mvs_mesh_vertex_normals": (C.c_int, [_I64, _VP, _I64, _VP, _VP]),
+    "mvs_mesh_vertex_normals_dev": (C.c_int, [_I64, _VP, _I64, _VP, _VP, _VP]),
     "mvs_pca": (C.c_int, [_VP, _I64, _VP, _U32, _VP, _VP, _VP, _VP]),
     "mvs_retain_connect_region": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
     "mvs_retain_connect_region_dev": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
@@ -168,6 +172,8 @@ _SIGS = {
     "mvs_depth_raw_write": (C.c_int, [C.c_char_p, _I64, _VP]),
     "mvs_parts_read": (C.c_int, [C.c_char_p, _I64, _VP]),
     "mvs_processor_deform": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, _VP, _D, _VP, C.c_char_p, _VP]),
+    "mvs_processor_stitch_points": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP, _U32, C.c_char_p, _VP]),
+    "mvs_processor_cull_model": (C.c_int, [C.c_char_p, _I32, _VP, _VP, _VP, _VP, _VP, _I32, C.c_char_p, _VP, _VP]),
     # include/mvs_test.h (test hooks: per handle, not part of the drop-in ABI)
     "mvs_test_preload_wait": (C.c_int, []),
     "mvs_test_ctl": (C.c_int, [_VP, _VP, _I32]),
@@ -210,6 +216,26 @@ def check(rc):
     if rc < 0:
         raise MvsError(rc, lib().mvs_last_error().decode(errors="replace"))
     return rc
+
+
+CULL_SEQUENCES, CULL_ALL_SEQ = 0, 1          # enum mvs_cull_mode
+STITCH_TRUNCATE = 1                         # MVS_STITCH_TRUNCATE (include/mvs_io.h)
+
+
+def seq_tables(scales, Rs, ts, cameras):
+    """The SRT chain and the per-sequence camera lists of AlignmentSeq as C arrays:
+    (n_seq, scales[n], R[n,3,3] row-major, t[n,3], cam_off int32[n+1], mvs_camera[]).  ``cameras[k]`` lists sequence k's cameras."""
+    s = arr(scales, np.float64).reshape(-1)
+    n = len(s)
+    R = arr(Rs, np.float64).reshape(n, 3, 3)
+    t = arr(ts, np.float64).reshape(n, 3)
+    if len(cameras) != n:
+        raise MvsError(-1, f"{len(cameras)} camera lists for {n} sequences")
+    off = np.zeros(n + 1, np.int32)
+    off[1:] = np.cumsum([len(c) for c in cameras])
+    flat = [CCamera.of(c) for seq in cameras for c in seq]
+    cams = (CCamera * max(1, len(flat)))(*flat)
+    return n, s, R, t, off, cams
 
 
 def device_count():

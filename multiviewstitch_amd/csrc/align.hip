@@ -922,6 +922,14 @@ template <class T> int down(T* h, const Dev& d, size_t n) {
 
 }  // namespace
 
+// the trim of the Poisson model, Processor::AlignmentSeq (R/Processor/Processor.cpp:1064-1104): the AllSeqProj compaction with
+// its facet remap (a facet stays iff its three vertices do) when keep is given, then RetainConnectRegion (mvs_processor_cull_model)
+int cull_retain_dev(double* pts, double* nrm, int64_t* V, int32_t* faces, int64_t* F, const int32_t* keep) {
+    int rc;
+    if (keep && *V > 0 && (rc = compact_dev(pts, nrm, V, faces, F, keep))) return rc;
+    return retain_dev(pts, nrm, V, faces, F);
+}
+
 extern "C" {
 
 int mvs_pca(const double* pts, int64_t n, const int32_t* labels, uint32_t mask, double* bary, double* bbox, double* axes, double* evals) {

@@ -1,0 +1,231 @@
+// api_stitch.cpp — C-ABI of the tail of Processor::AlignmentSeq (R/Processor/Processor.cpp:952-1105): mvs_visibility_cull(_dev),
+// mvs_mesh_vertex_normals(_dev) (include/mvs.h) and the two file-level steps mvs_processor_stitch_points / _cull_model
+// (include/mvs_io.h).  The point work is stitch.hip / align.hip; the host reads and writes the files and builds the small tables.
+#include "engine.h"
+#include "trace.h"
+#include "stitch.h"
+#include "../../include/mvs_io.h"
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+int mvs_current_device();
+
+namespace {
+
+int need_device() {
+    if (mvs_device_count() == 0) { mvs_set_error("no HIP device: the MI355X engine has no CPU fallback"); return MVS_E_NO_DEVICE; }
+    return mvs_check_hip(hipSetDevice(mvs_current_device()), "hipSetDevice");
+}
+
+struct DevBuf {               // RAII device scratch from the pool (scratch.cpp)
+    void* p = nullptr;
+    int alloc(size_t bytes, hipStream_t s = nullptr) { return mvs_scratch_alloc(&p, bytes ? bytes : 1, s); }
+    ~DevBuf() { mvs_scratch_free(p); }
+    template <class T> T* as() { return (T*)p; }
+};
+
+int bad(const char* fn, const char* what) { mvs_set_error("%s: %s", fn, what); return MVS_E_INVALID_ARG; }
+
+// the SRT chain and the cameras of every sequence (host arrays): n_seq >= 1, cam_off ascending from 0, cameras of positive size
+int check_seqs(const char* fn, int32_t n_seq, const double* scales, const double* R, const double* t, const int32_t* cam_off,
+               const mvs_camera* cams) {
+    if (n_seq < 1) return bad(fn, "n_seq must be >= 1");
+    if (!scales || !R || !t || !cam_off) return bad(fn, "scales, R, t and cam_off must not be NULL");
+    if (cam_off[0] != 0) return bad(fn, "cam_off must start at 0");
+    for (int k = 0; k < n_seq; ++k)
+        if (cam_off[k + 1] < cam_off[k]) return bad(fn, "cam_off must ascend");
+    if (cam_off[n_seq] > 0 && !cams) return bad(fn, "cams is NULL");
+    for (int c = 0; c < cam_off[n_seq]; ++c)
+        if (cams[c].w <= 0 || cams[c].h <= 0) return bad(fn, "every camera needs w, h > 0");
+    return MVS_OK;
+}
+
+int check_cull(const char* fn, const int64_t* seg_off, int32_t n_seg, int32_t n_seq, const double* scales, const double* R,
+               const double* t, const int32_t* cam_off, const mvs_camera* cams, int32_t mode, const void* points, const void* keep,
+               const int64_t* n_keep) {
+    int rc = check_seqs(fn, n_seq, scales, R, t, cam_off, cams);
+    if (rc) return rc;
+    if (n_seg < 1 || !seg_off || !n_keep) return bad(fn, "need n_seg >= 1, seg_off and n_keep");
+    if (mode != MVS_CULL_SEQUENCES && mode != MVS_CULL_ALL_SEQ) return bad(fn, "mode must be MVS_CULL_SEQUENCES or MVS_CULL_ALL_SEQ");
+    if (mode == MVS_CULL_SEQUENCES && n_seg != n_seq) return bad(fn, "MVS_CULL_SEQUENCES takes one segment per sequence");
+    if (seg_off[0] != 0) return bad(fn, "seg_off must start at 0");
+    for (int g = 0; g < n_seg; ++g)
+        if (seg_off[g + 1] < seg_off[g]) return bad(fn, "seg_off must ascend");
+    if (seg_off[n_seg] >= 0x7fffffffLL) return bad(fn, "more than 2^31 - 1 points");
+    if (seg_off[n_seg] > 0 && (!points || !keep)) return bad(fn, "points / keep is NULL");
+    return MVS_OK;
+}
+
+std::string join(const char* dir, const char* name) {
+    std::string s(dir);
+    if (!s.empty() && s.back() != '/') s += '/';
+    return s + name;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mvs_visibility_cull_dev(const double* points_dev, const int64_t* seg_off, int32_t n_seg, int32_t n_seq, const double* scales,
+                            const double* R, const double* t, const int32_t* cam_off, const mvs_camera* cams, int32_t mode,
+                            uint8_t* keep_dev, int64_t* n_keep, void* hip_stream) {
+    MVS_TRACE();
+    int rc = check_cull(__func__, seg_off, n_seg, n_seq, scales, R, t, cam_off, cams, mode, points_dev, keep_dev, n_keep);
+    if (rc) return rc;
+    if ((rc = need_device())) return rc;
+    return vis_cull_dev(points_dev, seg_off, n_seg, n_seq, scales, R, t, cam_off, cams, mode, keep_dev, nullptr, n_keep,
+                        (hipStream_t)hip_stream);
+}
+
+int mvs_visibility_cull(const double* points, const int64_t* seg_off, int32_t n_seg, int32_t n_seq, const double* scales,
+                        const double* R, const double* t, const int32_t* cam_off, const mvs_camera* cams, int32_t mode, uint8_t* keep,
+                        int64_t* n_keep) {
+    MVS_TRACE();
+    int rc = check_cull(__func__, seg_off, n_seg, n_seq, scales, R, t, cam_off, cams, mode, points, keep, n_keep);
+    if (rc) return rc;
+    if ((rc = need_device())) return rc;
+    const int64_t P = seg_off[n_seg];
+    DevBuf dp, dk;
+    if ((rc = dp.alloc((size_t)P * 24)) || (rc = dk.alloc((size_t)P))) return rc;
+    if (P) HIPCHK(hipMemcpy(dp.p, points, (size_t)P * 24, hipMemcpyHostToDevice));
+    if ((rc = vis_cull_dev(dp.as<double>(), seg_off, n_seg, n_seq, scales, R, t, cam_off, cams, mode, dk.as<uint8_t>(), nullptr, n_keep,
+                           nullptr))) return rc;
+    if (P) HIPCHK(hipMemcpy(keep, dk.p, (size_t)P, hipMemcpyDeviceToHost));
+    return MVS_OK;
+}
+
+int mvs_mesh_vertex_normals_dev(int64_t V, const double* points_dev, int64_t F, const int32_t* faces_dev, double* out_normals_dev,
+                                void* hip_stream) {
+    MVS_TRACE();
+    if (V < 0 || F < 0 || V >= 0x7fffffffLL || F >= 0x7fffffffLL / 3 || (V > 0 && (!points_dev || !out_normals_dev)) || (F > 0 && !faces_dev))
+        return bad(__func__, "bad arguments");
+    int rc = need_device();
+    if (rc) return rc;
+    return mesh_vertex_normals_dev(points_dev, V, faces_dev, F, out_normals_dev, (hipStream_t)hip_stream);
+}
+
+int mvs_mesh_vertex_normals(int64_t V, const double* points, int64_t F, const int32_t* faces, double* out_normals) {
+    MVS_TRACE();
+    if (V < 0 || F < 0 || V >= 0x7fffffffLL || F >= 0x7fffffffLL / 3 || (V > 0 && (!points || !out_normals)) || (F > 0 && !faces))
+        return bad(__func__, "bad arguments");
+    int rc = need_device();
+    if (rc) return rc;
+    if (V == 0) return MVS_OK;
+    DevBuf dp, df, dn;
+    if ((rc = dp.alloc((size_t)V * 24)) || (rc = df.alloc((size_t)F * 12)) || (rc = dn.alloc((size_t)V * 24))) return rc;
+    HIPCHK(hipMemcpy(dp.p, points, (size_t)V * 24, hipMemcpyHostToDevice));
+    if (F) HIPCHK(hipMemcpy(df.p, faces, (size_t)F * 12, hipMemcpyHostToDevice));
+    if ((rc = mesh_vertex_normals_dev(dp.as<double>(), V, df.as<int32_t>(), F, dn.as<double>(), nullptr))) return rc;
+    HIPCHK(hipMemcpy(out_normals, dn.p, (size_t)V * 24, hipMemcpyDeviceToHost));
+    return MVS_OK;
+}
+
+int mvs_processor_stitch_points(int32_t n_seq, const char* const* npts_paths, const double* scales, const double* R, const double* t,
+                                const int32_t* cam_off, const mvs_camera* cams, uint32_t flags, const char* out_dir, int64_t* n_keep) {
+    MVS_TRACE();
+    int rc = check_seqs(__func__, n_seq, scales, R, t, cam_off, cams);
+    if (rc) return rc;
+    if (!npts_paths || !out_dir) return bad(__func__, "npts_paths / out_dir is NULL");
+    for (int k = 0; k < n_seq; ++k)
+        if (!npts_paths[k]) return bad(__func__, "a path of npts_paths is NULL");
+    if (flags & ~MVS_STITCH_TRUNCATE) return bad(__func__, "unknown flag");
+    if ((rc = need_device())) return rc;
+    // :958-963, every sequence into one array (segment k = sequence k)
+    std::vector<int64_t> off(n_seq + 1, 0);
+    for (int k = 0; k < n_seq; ++k) {
+        int64_t n = 0;
+        if ((rc = mvs_npts_read(npts_paths[k], &n, nullptr, nullptr))) return rc;
+        off[k + 1] = off[k] + n;
+    }
+    const int64_t P = off[n_seq];
+    if (P >= 0x7fffffffLL) return bad(__func__, "more than 2^31 - 1 points");
+    std::vector<double> hp((size_t)P * 3), hn((size_t)P * 3);
+    for (int k = 0; k < n_seq; ++k) {
+        int64_t n = off[k + 1] - off[k];
+        if ((rc = mvs_npts_read(npts_paths[k], &n, hp.data() + 3 * off[k], hn.data() + 3 * off[k]))) return rc;
+        if (n != off[k + 1] - off[k]) { mvs_set_error("%s changed while it was read", npts_paths[k]); return MVS_E_IO; }
+    }
+    const int truncate = (flags & MVS_STITCH_TRUNCATE) ? 1 : 0;
+    DevBuf dp, dn, dk, op, on;
+    if ((rc = dp.alloc((size_t)P * 24)) || (rc = dn.alloc((size_t)P * 24)) || (rc = dk.alloc((size_t)P * 4 + 4)) ||
+        (rc = op.alloc((size_t)P * 24)) || (rc = on.alloc((size_t)P * 24))) return rc;
+    if (P) {
+        HIPCHK(hipMemcpy(dp.p, hp.data(), (size_t)P * 24, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(dn.p, hn.data(), (size_t)P * 24, hipMemcpyHostToDevice));
+    }
+    std::vector<int64_t> nk(n_seq), oo(n_seq + 1);
+    if ((rc = vis_cull_dev(dp.as<double>(), off.data(), n_seq, n_seq, scales, R, t, cam_off, cams, MVS_CULL_SEQUENCES, nullptr,
+                           dk.as<int32_t>(), nk.data(), nullptr))) return rc;
+    if ((rc = stitch_compact_dev(dp.as<double>(), dn.as<double>(), dk.as<int32_t>(), off.data(), n_seq, nk.data(), truncate, scales, R, t,
+                                 op.as<double>(), on.as<double>(), oo.data(), nullptr))) return rc;
+    const int64_t Q = oo[n_seq];
+    if (Q) {
+        HIPCHK(hipMemcpy(hp.data(), op.p, (size_t)Q * 24, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(hn.data(), on.p, (size_t)Q * 24, hipMemcpyDeviceToHost));
+    }
+    for (int k = 0; k < n_seq; ++k) {                                     // :1029-1030
+        char name[32];
+        std::snprintf(name, sizeof name, "PSR%d.obj", k);
+        if ((rc = mvs_obj_write(join(out_dir, name).c_str(), oo[k + 1] - oo[k], hp.data() + 3 * oo[k], hn.data() + 3 * oo[k], 0, nullptr)))
+            return rc;
+    }
+    if ((rc = mvs_npts_write(join(out_dir, "PSR.npts").c_str(), Q, hp.data(), hn.data()))) return rc;   // :1033-1040
+    if (n_keep) std::memcpy(n_keep, nk.data(), sizeof(int64_t) * n_seq);
+    return MVS_OK;
+}
+
+int mvs_processor_cull_model(const char* model_obj, int32_t n_seq, const double* scales, const double* R, const double* t,
+                             const int32_t* cam_off, const mvs_camera* cams, int32_t all_seq_proj, const char* out_obj, int64_t* V_out,
+                             int64_t* F_out) {
+    MVS_TRACE();
+    int rc = check_seqs(__func__, n_seq, scales, R, t, cam_off, cams);
+    if (rc) return rc;
+    if (!model_obj || !out_obj) return bad(__func__, "model_obj / out_obj is NULL");
+    if ((rc = need_device())) return rc;
+    int64_t V = 0, N = 0, F = 0;                                          // ReadObj, :1062
+    if ((rc = mvs_obj_read(model_obj, &V, &N, &F, nullptr, nullptr, nullptr))) return rc;
+    if (N != 0 && N != V) {
+        mvs_set_error("%s: %lld normals for %lld vertices (the reference indexes one per vertex)", model_obj, (long long)N, (long long)V);
+        return MVS_E_BAD_MESH;
+    }
+    if (V >= 0x7fffffffLL || F >= 0x7fffffffLL / 3) return bad(__func__, "mesh too large");
+    std::vector<double> hp((size_t)V * 3), hn((size_t)V * 3);
+    std::vector<int32_t> hf((size_t)F * 3);
+    if ((rc = mvs_obj_read(model_obj, &V, &N, &F, hp.data(), hn.data(), hf.data()))) return rc;
+    for (int64_t i = 0; i < F * 3; ++i)
+        if (hf[i] < 0 || hf[i] >= V) { mvs_set_error("%s: facet index %d outside [1, %lld]", model_obj, hf[i] + 1, (long long)V); return MVS_E_BAD_MESH; }
+    DevBuf dp, dn, df, dk;
+    if ((rc = dp.alloc((size_t)V * 24)) || (rc = dn.alloc((size_t)V * 24)) || (rc = df.alloc((size_t)F * 12)) ||
+        (rc = dk.alloc((size_t)V * 4 + 4))) return rc;
+    if (V) HIPCHK(hipMemcpy(dp.p, hp.data(), (size_t)V * 24, hipMemcpyHostToDevice));
+    if (F) HIPCHK(hipMemcpy(df.p, hf.data(), (size_t)F * 12, hipMemcpyHostToDevice));
+    if (N == 0) {                                                         // no `vn` lines: CalculateVertexNormals, PlyObj.cpp:11-14
+        if ((rc = mesh_vertex_normals_dev(dp.as<double>(), V, df.as<int32_t>(), F, dn.as<double>(), nullptr))) return rc;
+    } else if (V) {
+        HIPCHK(hipMemcpy(dn.p, hn.data(), (size_t)V * 24, hipMemcpyHostToDevice));
+    }
+    int32_t* keep = nullptr;
+    if (all_seq_proj && V > 0) {                                          // :1064-1100
+        const int64_t seg[2] = {0, V};
+        int64_t nk = 0;
+        HIPCHK(hipMemset(dk.p, 0, (size_t)V * 4 + 4));
+        if ((rc = vis_cull_dev(dp.as<double>(), seg, 1, n_seq, scales, R, t, cam_off, cams, MVS_CULL_ALL_SEQ, nullptr, dk.as<int32_t>(), &nk,
+                               nullptr))) return rc;
+        keep = dk.as<int32_t>();
+    }
+    if ((rc = cull_retain_dev(dp.as<double>(), dn.as<double>(), &V, df.as<int32_t>(), &F, keep))) return rc;   // :1102-1103
+    HIPCHK(hipDeviceSynchronize());
+    if (V) {
+        HIPCHK(hipMemcpy(hp.data(), dp.p, (size_t)V * 24, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(hn.data(), dn.p, (size_t)V * 24, hipMemcpyDeviceToHost));
+    }
+    if (F) HIPCHK(hipMemcpy(hf.data(), df.p, (size_t)F * 12, hipMemcpyDeviceToHost));
+    if ((rc = mvs_obj_write(out_obj, V, hp.data(), hn.data(), F, hf.data()))) return rc;                       // :1104
+    if (V_out) *V_out = V;
+    if (F_out) *F_out = F;
+    return MVS_OK;
+}
+
+}  // extern "C"

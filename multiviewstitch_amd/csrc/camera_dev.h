@@ -22,4 +22,9 @@ __device__ inline void img_from_world(const CamDev& c, d3 pw, int32_t* u, int32_
     *u = cvt_i32(c.fx * p.x / p.z + c.cx + 0.5);
     *v = cvt_i32(c.fy * p.y / p.z + c.cy + 0.5);
 }
+// the point half of the similarity map (geom.hip k_srt_apply, stitch.hip k_vis_cull)
+__device__ inline d3 map34_point(const Map34& m, d3 p) {
+    const d3 tt = mk3(m.t[0], m.t[1], m.t[2]);
+    return m.inverse ? mulMv(m.M, p - tt) : mulMv(m.M, p) + tt;
+}
 #endif

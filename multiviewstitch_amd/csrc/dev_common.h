@@ -39,6 +39,16 @@ __host__ __device__ inline double det3(const double* M) {
            M[2] * (M[3] * M[7] - M[4] * M[6]);
 }
 
+// Mesh::CalculateTriangleNormal (R/PlyObj/PlyObj.cpp:172-185): the 1e-6 rescue of a short edge, then n / |n| — a zero-area
+// facet gives NaN (geom.hip's depth normals and stitch.hip's general-mesh normals)
+__host__ __device__ inline d3 tri_normal_plyobj(d3 p0, d3 p1, d3 p2) {
+    d3 v1 = p1 - p0, v2 = p2 - p1;
+    if (norm3(v1) <= 1e-6) v1 = 1e+9 * p1 - 1e+9 * p0;
+    if (norm3(v2) <= 1e-6) v2 = 1e+9 * p2 - 1e+9 * p1;
+    const d3 n = cross3(v1, v2);
+    return n / norm3(n);
+}
+
 // float32 squared distance with FLANN's accumulation order
 __host__ __device__ inline float d2f(float qx, float qy, float qz, float px, float py, float pz) {
     const float dx = qx - px, dy = qy - py, dz = qz - pz;

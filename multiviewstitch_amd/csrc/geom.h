@@ -11,6 +11,11 @@ struct CamDev {
 };
 CamDev make_camdev(const mvs_camera* c);
 
+// the similarity point map of mvs_srt_apply (v = M p + t, or M (p - t) when inverse; normals n' = Rn n), built on the host:
+// forward M = s R (Processor.cpp:1025), inverse M = (1/s) R^T (:1183); applied by map34_point (camera_dev.h)
+struct Map34 { double M[9], Rn[9], t[3]; int inverse; };
+Map34 make_map34(double sc, const double* R, const double* t, int inverse);
+
 int  depth_to_model_dev(const float* dsp_dev, const mvs_camera* cam, double mn, double mx, double smooth,
                         int64_t* n_points, int64_t* n_faces, double* out_pts, double* out_nrm, int32_t* out_tex,
                         int32_t* out_faces, hipStream_t s);

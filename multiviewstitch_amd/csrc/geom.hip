@@ -47,14 +47,6 @@ __global__ void k_quad_count(const float* __restrict__ dsp, int w, int h, double
     cnt[i] = (q.a ? 1 : 0) + (q.b ? 1 : 0);
 }
 
-__device__ inline d3 tri_normal_plyobj(d3 p0, d3 p1, d3 p2) {            // PlyObj.cpp:172-185
-    d3 v1 = p1 - p0, v2 = p2 - p1;
-    if (norm3(v1) <= 1e-6) v1 = 1e+9 * p1 - 1e+9 * p0;
-    if (norm3(v2) <= 1e-6) v2 = 1e+9 * p2 - 1e+9 * p1;
-    const d3 n = cross3(v1, v2);
-    return n / norm3(n);
-}
-
 __global__ void k_depth_emit(const float* __restrict__ dsp, CamDev cam, double mn, double mx, double thr,
                              const int32_t* __restrict__ vstart, const int32_t* __restrict__ fstart,
                              double* __restrict__ out_pts, double* __restrict__ out_nrm, int32_t* __restrict__ out_tex,
@@ -116,20 +108,29 @@ __global__ void k_depth_unproject(const float* __restrict__ dsp, CamDev cam, dou
     }
 }
 
-struct Map34 { double M[9], Rn[9], t[3]; int inverse; };
-
 __global__ void k_srt_apply(const double* __restrict__ pts, const double* __restrict__ nrm, int64_t P, Map34 m,
                             double* __restrict__ out_pts, double* __restrict__ out_nrm) {
-    const d3 tt = mk3(m.t[0], m.t[1], m.t[2]);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (int64_t)gridDim.x * blockDim.x) {
-        const d3 p = ld3(pts + 3 * i);
-        const d3 q = m.inverse ? mulMv(m.M, p - tt) : mulMv(m.M, p) + tt;
-        st3(out_pts + 3 * i, q);
+        st3(out_pts + 3 * i, map34_point(m, ld3(pts + 3 * i)));
         if (nrm) st3(out_nrm + 3 * i, mulMv(m.Rn, ld3(nrm + 3 * i)));
     }
 }
 
 }  // namespace
+
+Map34 make_map34(double sc, const double* R, const double* t, int inverse) {
+    Map34 m;
+    m.inverse = inverse;
+    const double Rt[9] = {R[0], R[3], R[6], R[1], R[4], R[7], R[2], R[5], R[8]};
+    if (!inverse) {
+        for (int i = 0; i < 9; ++i) { m.M[i] = sc * R[i]; m.Rn[i] = R[i]; }          // scales[k] * Rs[k], Processor.cpp:1025
+    } else {
+        const double inv = 1.0 / sc;                                                  // 1.0 / scales[k] * Rs[k]^T, :1183
+        for (int i = 0; i < 9; ++i) { m.M[i] = inv * Rt[i]; m.Rn[i] = Rt[i]; }
+    }
+    for (int i = 0; i < 3; ++i) m.t[i] = t[i];
+    return m;
+}
 
 CamDev make_camdev(const mvs_camera* c) {
     CamDev d;
@@ -181,16 +182,7 @@ void launch_depth_unproject(const float* dsp_dev, const mvs_camera* cam, double 
 void launch_srt_apply(const double* pts, const double* nrm, int64_t P, double sc, const double* R, const double* t,
                       int inverse, double* out_pts, double* out_nrm, hipStream_t s) {
     if (P <= 0) return;
-    Map34 m;
-    m.inverse = inverse;
-    const double Rt[9] = {R[0], R[3], R[6], R[1], R[4], R[7], R[2], R[5], R[8]};
-    if (!inverse) {
-        for (int i = 0; i < 9; ++i) { m.M[i] = sc * R[i]; m.Rn[i] = R[i]; }          // scales[k] * Rs[k], Processor.cpp:1025
-    } else {
-        const double inv = 1.0 / sc;                                                  // 1.0 / scales[k] * Rs[k]^T, :1183
-        for (int i = 0; i < 9; ++i) { m.M[i] = inv * Rt[i]; m.Rn[i] = Rt[i]; }
-    }
-    for (int i = 0; i < 3; ++i) m.t[i] = t[i];
+    const Map34 m = make_map34(sc, R, t, inverse);
     const int64_t blocks = std::min<int64_t>((P + TPB - 1) / TPB, 256 * 16);
     k_srt_apply<<<dim3((unsigned)blocks), dim3(TPB), 0, s>>>(pts, nrm, P, m, out_pts, out_nrm);
 }

@@ -1,0 +1,21 @@
+// stitch.h — launchers of stitch.hip (the tail of Processor::AlignmentSeq and general-mesh vertex normals); see stitch.hip.
+#ifndef MVS_STITCH_H_
+#define MVS_STITCH_H_
+#include "engine.h"
+
+// visibility cull of the points of n_seg segments (seg_off: host, n_seg + 1, from 0); mode = enum mvs_cull_mode; the keep mask goes
+// to keep_u8 or, when it is not NULL, keep_i32 (device, P entries); n_keep (host, n_seg) receives the kept counts.  Synchronises s.
+int vis_cull_dev(const double* pts_dev, const int64_t* seg_off, int n_seg, int n_seq, const double* scales, const double* R,
+                 const double* t, const int32_t* cam_off, const mvs_camera* cams, int mode, uint8_t* keep_u8, int32_t* keep_i32,
+                 int64_t* n_keep, hipStream_t s);
+// compaction of every segment by its int32 keep mask (reference layout, or the kept points only when truncate) followed by the
+// forward map of sequence g (s R p + t, R n).  out_off (host, n_seg + 1) receives the output offsets.  Synchronises s.
+int stitch_compact_dev(const double* pts, const double* nrm, const int32_t* keep, const int64_t* seg_off, int n_seg, const int64_t* n_keep,
+                       int truncate, const double* scales, const double* R, const double* t, double* out_pts, double* out_nrm,
+                       int64_t* out_off, hipStream_t s);
+// PlyObj vertex normals of a triangle list (device arrays); MVS_E_BAD_MESH for a facet index outside [0, V).  Synchronises s.
+int mesh_vertex_normals_dev(const double* pts, int64_t V, const int32_t* faces, int64_t F, double* out, hipStream_t s);
+// Poisson model trim on device arrays (align.hip): compaction by keep (int32, V + 1, or NULL: none) with the facet remap, then
+// RetainConnectRegion.  V, F in/out.
+int cull_retain_dev(double* pts, double* nrm, int64_t* V, int32_t* faces, int64_t* F, const int32_t* keep);
+#endif

@@ -1,4 +1,5 @@
-"""``Processor::Deform`` (R/Processor/Processor.cpp:1111-1138) on files, through ``mvs_processor_deform``."""
+"""``Processor::Deform`` (R/Processor/Processor.cpp:1111-1138) on files, through ``mvs_processor_deform``; the tail of
+``Processor::AlignmentSeq`` (:952-1105) through ``mvs_processor_stitch_points`` / ``mvs_processor_cull_model``."""
 from __future__ import annotations
 
 import ctypes as C
@@ -19,6 +20,31 @@ def Deform(model_obj, template_obj, parts_path, cam_R, dist_thres: float, out_ob
     rc = L.check(L.lib().mvs_processor_deform(os.fsencode(model_obj), os.fsencode(template_obj), os.fsencode(parts_path), L.ptr(R),
                                               float(dist_thres), C.byref(prm), os.fsencode(out_obj), C.byref(st)))
     return _stats(st, rc)
+
+
+def StitchPointSets(npts_paths, scales, Rs, ts, cameras, out_dir, truncate: bool = False) -> np.ndarray:
+    """The tail of Processor::AlignmentSeq before Poisson (R/Processor/Processor.cpp:952-1040): each sequence's ``.npts`` culled,
+    compacted and mapped forward, written to ``out_dir``/PSR%d.obj and ``out_dir``/PSR.npts.  ``cameras[k]`` lists sequence k's
+    cameras.  By default sequence k keeps the reference's P_k points (the kept ones, then the untouched tail); ``truncate`` writes
+    the kept points only.  -> kept counts per sequence."""
+    n, s, R, t, coff, cams = L.seq_tables(scales, Rs, ts, cameras)
+    if len(npts_paths) != n:
+        raise L.MvsError(-1, f"{len(npts_paths)} paths for {n} sequences")
+    paths = (C.c_char_p * n)(*[os.fsencode(p) for p in npts_paths])
+    nk = np.empty(n, np.int64)
+    L.check(L.lib().mvs_processor_stitch_points(n, paths, L.ptr(s), L.ptr(R), L.ptr(t), L.ptr(coff), cams,
+                                                L.STITCH_TRUNCATE if truncate else 0, os.fsencode(out_dir), L.ptr(nk)))
+    return nk
+
+
+def CullPoissonModel(model_obj, scales, Rs, ts, cameras, out_obj, all_seq_proj: bool = True):
+    """The trim of the Poisson model (R/Processor/Processor.cpp:1057-1105): ReadObj (normals computed when the file has no `vn`),
+    the AllSeqProj cull with its facet remap, RetainConnectRegion, WriteObj.  -> (V, F) written."""
+    n, s, R, t, coff, cams = L.seq_tables(scales, Rs, ts, cameras)
+    V, F = C.c_int64(), C.c_int64()
+    L.check(L.lib().mvs_processor_cull_model(os.fsencode(model_obj), n, L.ptr(s), L.ptr(R), L.ptr(t), L.ptr(coff), cams,
+                                             int(bool(all_seq_proj)), os.fsencode(out_obj), C.byref(V), C.byref(F)))
+    return V.value, F.value
 
 
 def CheckConsistencyCore(curcam, refcams, depth, refdepths, min_dsp: float, max_dsp: float, reproj_err: int) -> np.ndarray:

@@ -369,3 +369,31 @@ def make_sequence(n_frames: int = 5, w: int = 320, h: int = 240, dyaw_deg: float
         cams.append(Camera(fx, fy, cx, cy, Rc.copy(), tc.copy(), w, h))
         depths.append(d)
     return cams, np.stack(depths)
+
+
+def make_stitch_sequences(cams_per_seq, sizes, f, seed: int = 11, dist: float = 5.0, s_range=(0.8, 1.25)):
+    """Cameras and SRT chain of the stitch tail of Processor::AlignmentSeq (R/Processor/Processor.cpp:952-1105): sequence k has
+    ``cams_per_seq[k]`` cameras of size ``sizes[k]`` = (w, h) and focal factor ``f[k]`` (fx = f w) on the ring around the origin
+    (every camera of every sequence at its own yaw, elevations alternating), expressed in sequence k's frame, which relates to the
+    world by a random similarity world = s R local + t with s in ``s_range``.  -> (scales[n], Rs[n,3,3], ts[n,3], cameras)."""
+    rng = np.random.default_rng(seed)
+    n = len(cams_per_seq)
+    total = int(sum(cams_per_seq))
+    scales, Rs, ts, cameras = [], [], [], []
+    j = 0
+    for k in range(n):
+        s = float(rng.uniform(*s_range))
+        R = _rot_axis(rng.normal(size=3), float(rng.uniform(-math.pi, math.pi)))
+        t = rng.uniform(-0.3, 0.3, 3)
+        w, h = sizes[k]
+        fx = fy = f[k] * w
+        cams = []
+        for _ in range(cams_per_seq[k]):
+            yaw = 2 * math.pi * j / total
+            el = math.radians(10.0 if j % 2 == 0 else -5.0)
+            eye = dist * np.array([math.cos(el) * math.cos(yaw), math.cos(el) * math.sin(yaw), math.sin(el)])
+            Rc, tc = _look_at(eye)
+            cams.append(Camera(fx, fy, w / 2 - 0.5, h / 2 - 0.5, (Rc @ R).copy(), ((Rc @ t + tc) / s).copy(), w, h))
+            j += 1
+        scales.append(s); Rs.append(R); ts.append(t); cameras.append(cams)
+    return np.array(scales), np.array(Rs), np.array(ts), cameras

@@ -188,3 +188,50 @@ def depth_unproject(inv_depth, cam, min_dsp, max_dsp):
     valid = np.empty(c.h * c.w, np.uint8)
     L.check(L.lib().mvs_depth_unproject(L.ptr(d), C.byref(c), min_dsp, max_dsp, L.ptr(pts), L.ptr(valid)))
     return pts, valid
+
+
+# ----------------------------------------------------------- stitch tail ----
+def _segments(seg_off, P):
+    off = L.arr([0, P] if seg_off is None else seg_off, np.int64).reshape(-1)
+    return off, len(off) - 1
+
+
+def visibility_cull(points, scales, Rs, ts, cameras, mode: int = L.CULL_SEQUENCES, seg_off=None):
+    """The visibility cull of Processor::AlignmentSeq (R/Processor/Processor.cpp:966-1004 with ``mode=CULL_SEQUENCES``: segment
+    k = the points of sequence k; :1064-1083 with ``mode=CULL_ALL_SEQ``, AllSeqProj on the Poisson model).  ``cameras[k]`` lists
+    sequence k's cameras; ``seg_off`` (n_seg + 1 offsets from 0) defaults to one segment.  -> (keep uint8[P], n_keep int64[n_seg])."""
+    pts = L.arr(points, np.float64).reshape(-1, 3)
+    off, n_seg = _segments(seg_off, len(pts))
+    n, s, R, t, coff, cams = L.seq_tables(scales, Rs, ts, cameras)
+    keep = np.empty(len(pts), np.uint8)
+    nk = np.empty(n_seg, np.int64)
+    L.check(L.lib().mvs_visibility_cull(L.ptr(pts), L.ptr(off), n_seg, n, L.ptr(s), L.ptr(R), L.ptr(t), L.ptr(coff), cams, int(mode),
+                                        L.ptr(keep), L.ptr(nk)))
+    return keep, nk
+
+
+def visibility_cull_dev(points_dev: int, seg_off, scales, Rs, ts, cameras, keep_dev: int, mode: int = L.CULL_SEQUENCES,
+                        stream: int | None = None):
+    """Device-resident variant: ``points_dev`` (P*3 float64) and ``keep_dev`` (P uint8) are device addresses, ``seg_off`` a host
+    sequence of n_seg + 1 offsets.  Returns n_keep once the cull is complete."""
+    off = L.arr(seg_off, np.int64).reshape(-1)
+    n, s, R, t, coff, cams = L.seq_tables(scales, Rs, ts, cameras)
+    nk = np.empty(len(off) - 1, np.int64)
+    L.check(L.lib().mvs_visibility_cull_dev(L.ptr(int(points_dev)), L.ptr(off), len(off) - 1, n, L.ptr(s), L.ptr(R), L.ptr(t), L.ptr(coff),
+                                            cams, int(mode), L.ptr(int(keep_dev)), L.ptr(nk), C.c_void_p(stream) if stream else None))
+    return nk
+
+
+def mesh_vertex_normals(points, faces):
+    """Mesh::CalculateVertexNormals of a general triangle list (R/PlyObj/PlyObj.cpp:139-185): NaN for a vertex of no facet."""
+    pts = L.arr(points, np.float64).reshape(-1, 3)
+    fac = L.arr(faces, np.int32).reshape(-1, 3)
+    out = np.empty_like(pts)
+    L.check(L.lib().mvs_mesh_vertex_normals(len(pts), L.ptr(pts), len(fac), L.ptr(fac), L.ptr(out)))
+    return out
+
+
+def mesh_vertex_normals_dev(points_dev: int, V: int, faces_dev: int, F: int, out_dev: int, stream: int | None = None):
+    """Device-resident variant (addresses of V*3 float64 points, F*3 int32 facets, V*3 float64 output)."""
+    L.check(L.lib().mvs_mesh_vertex_normals_dev(int(V), L.ptr(int(points_dev)), int(F), L.ptr(int(faces_dev)) if F else None,
+                                                L.ptr(int(out_dev)), C.c_void_p(stream) if stream else None))

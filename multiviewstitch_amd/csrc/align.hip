@@ -22,7 +22,6 @@
 #include <cstring>
 #include <vector>
 
-int mvs_current_device();
 void knn_grid_build(const double* pts, int n, void* ws, hipStream_t s);
 size_t label_grid_ws_bytes(int V);
 void launch_label_nn(const double* tmpl, int V, const int32_t* tmpl_labels, void* ws, const double* pts, int64_t P,
@@ -396,12 +395,7 @@ __global__ void k_apply_masked(double* __restrict__ pts, double* __restrict__ nr
 }
 
 // ------------------------------------------------------------------------------------ host side ----
-struct Dev {                 // RAII scratch from the pool (scratch.cpp): every launch of this file is on the legacy default stream
-    void* p = nullptr;
-    int alloc(size_t b) { return mvs_scratch_alloc(&p, b ? b : 1); }
-    ~Dev() { mvs_scratch_free(p); }
-    template <class T> T* as() const { return (T*)p; }
-};
+// (scratch: Scratch blocks of the pool, engine.h; every launch of this file is on the legacy default stream)
 inline dim3 blocks(int64_t n) { return dim3((unsigned)std::max<int64_t>(1, (n + TPB - 1) / TPB)); }
 inline double nrm3(const double* a) { return std::sqrt((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]); }
 inline double dotp(const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
@@ -449,7 +443,7 @@ void mv3(const double* M, const double* v, double* o) {
 
 struct Pca { double bary[3], lo[3], hi[3], axis[3][3], eval[3]; double cnt; uint32_t present; };
 struct Work {                 // per-call reduction scratch (device + pinned-size host mirror)
-    Dev part;
+    Scratch part;
     // SLOTS reductions can be in flight before ONE copy brings their partial sums (a blocking copy is ~20 us whatever its size:
     // Alignment::Align made ~80 of them for 1.3 ms of kernels)
     static constexpr int SLOTS = 8;
@@ -621,7 +615,7 @@ int range_batch(const RangeItem* it, int n, Work& w) {
 
 // keep[] (int32 0/1 on the device) -> compact points / normals / faces in place; updates n, F
 int compact_dev(double* pts, double* nrm, int64_t* n, int32_t* faces, int64_t* F, const int32_t* keep /* n+1 */) {
-    Dev vpos, fkeep, fpos, tp, tn, tf;
+    Scratch vpos, fkeep, fpos, tp, tn, tf;
     int rc;
     if ((rc = vpos.alloc(sizeof(int32_t) * (*n + 1)))) return rc;
     if ((rc = scan_exclusive_i32(keep, *n, vpos.as<int32_t>(), nullptr))) return rc;
@@ -653,7 +647,7 @@ int compact_dev(double* pts, double* nrm, int64_t* n, int32_t* faces, int64_t* F
 // part and are removed by the same compaction (RemoveGround hands its removal over instead of compacting twice); overwritten.
 int retain_dev(double* pts, double* nrm, int64_t* n, int32_t* faces, int64_t* F, const Reducer& red = Reducer(), int rank = 0, int32_t* live = nullptr) {
     if (*n <= 0 && !red.fn) return MVS_OK;
-    Dev parent, size, keep_own, part;
+    Scratch parent, size, keep_own, part;
     int rc;
     const int64_t n1 = std::max<int64_t>(*n, 1);
     LOCAL(parent.alloc(sizeof(int32_t) * n1));
@@ -706,7 +700,7 @@ int remove_ground_dev(double* pts, double* nrm, int64_t* n, int32_t* faces, int6
     int rc = pca_dev(pts, *n, nullptr, 0, w, &p, red);
     if (rc) return rc;
     const double* pivot = p.axis[0];
-    Dev t, side, dist, keep;
+    Scratch t, side, dist, keep;
     const int64_t n1 = std::max<int64_t>(*n, 1);
     LOCAL(t.alloc(sizeof(double) * n1));
     LOCAL(side.alloc((size_t)n1));
@@ -900,24 +894,11 @@ int apply_masked_dev(double* pts, double* nrm, int64_t n, const int32_t* labels,
 }
 
 int part_recog_dev(const double* tmpl, const int32_t* tmpl_labels, int64_t V, const double* pts, int64_t P, int32_t* out) {
-    Dev ws, far;
+    Scratch ws, far;
     int rc;
     if ((rc = ws.alloc(label_grid_ws_bytes((int)V))) || (rc = far.alloc(sizeof(int32_t) * (size_t)(P + 1)))) return rc;
     launch_label_nn(tmpl, (int)V, tmpl_labels, ws.p, pts, P, out, far.as<int32_t>(), nullptr);
     return mvs_check_hip(hipGetLastError(), "part_recog");       // (no wait: what follows is ordered behind it on the stream, the scratch goes back to the pool in that order)
-}
-
-int need_device() {
-    if (mvs_device_count() == 0) { mvs_set_error("no HIP device: the MI355X engine has no CPU fallback"); return MVS_E_NO_DEVICE; }
-    return mvs_check_hip(hipSetDevice(mvs_current_device()), "hipSetDevice");
-}
-template <class T> int up(Dev& d, const T* h, size_t n, size_t cap = 0) {
-    int rc = d.alloc(sizeof(T) * std::max(n, cap));
-    if (rc || !n) return rc;
-    return mvs_check_hip(hipMemcpy(d.p, h, sizeof(T) * n, hipMemcpyHostToDevice), "upload");
-}
-template <class T> int down(T* h, const Dev& d, size_t n) {
-    return n ? mvs_check_hip(hipMemcpy(h, d.p, sizeof(T) * n, hipMemcpyDeviceToHost), "download") : MVS_OK;
 }
 
 }  // namespace
@@ -937,7 +918,7 @@ int mvs_pca(const double* pts, int64_t n, const int32_t* labels, uint32_t mask, 
     if (!pts || n < 2 || !bary || !bbox || !axes || !evals) { mvs_set_error("bad arguments"); return MVS_E_INVALID_ARG; }
     int rc = need_device();
     if (rc) return rc;
-    Dev dp, dl; Work w; Pca p;
+    Scratch dp, dl; Work w; Pca p;
     if ((rc = up(dp, pts, (size_t)n * 3)) || (labels && (rc = up(dl, labels, (size_t)n))) || (rc = w.init())) return rc;
     if ((rc = pca_dev(dp.as<double>(), n, labels ? dl.as<int32_t>() : nullptr, mask, w, &p))) return rc;
     std::memcpy(bary, p.bary, 24); std::memcpy(bbox, p.lo, 24); std::memcpy(bbox + 3, p.hi, 24);
@@ -950,7 +931,7 @@ int mvs_retain_connect_region(int64_t* V, double* pts, double* normals, int64_t*
     if (!V || !F || !pts || *V < 0 || *F < 0 || (*F > 0 && !faces)) { mvs_set_error("bad arguments"); return MVS_E_INVALID_ARG; }
     int rc = need_device();
     if (rc) return rc;
-    Dev dp, dn, df;
+    Scratch dp, dn, df;
     if ((rc = up(dp, pts, (size_t)*V * 3)) || (normals && (rc = up(dn, normals, (size_t)*V * 3))) || (rc = up(df, faces, (size_t)*F * 3))) return rc;
     int64_t n = *V, f = *F;
     if ((rc = retain_dev(dp.as<double>(), normals ? dn.as<double>() : nullptr, &n, df.as<int32_t>(), &f))) return rc;
@@ -964,7 +945,7 @@ int mvs_remove_ground(int64_t* V, double* pts, double* normals, int64_t* F, int3
     if (!V || !F || !pts || !ground_ray || *V < 2 || *F < 0 || (*F > 0 && !faces)) { mvs_set_error("bad arguments"); return MVS_E_INVALID_ARG; }
     int rc = need_device();
     if (rc) return rc;
-    Dev dp, dn, df; Work w;
+    Scratch dp, dn, df; Work w;
     if ((rc = up(dp, pts, (size_t)*V * 3)) || (normals && (rc = up(dn, normals, (size_t)*V * 3))) || (rc = up(df, faces, (size_t)*F * 3)) || (rc = w.init())) return rc;
     int64_t n = *V, f = *F;
     if ((rc = remove_ground_dev(dp.as<double>(), normals ? dn.as<double>() : nullptr, &n, df.as<int32_t>(), &f, dist_thres, ground_ray, w))) return rc;
@@ -1020,7 +1001,7 @@ int mvs_init_alignment(const double* src, int64_t ns, const double* tgt, int64_t
     if (!src || !tgt || ns < 2 || nt < 2 || !ground_ray || !view_ray || !R || !t || !scale) { mvs_set_error("bad arguments"); return MVS_E_INVALID_ARG; }
     int rc = need_device();
     if (rc) return rc;
-    Dev ds, dt; Work w;
+    Scratch ds, dt; Work w;
     if ((rc = up(ds, src, (size_t)ns * 3)) || (rc = up(dt, tgt, (size_t)nt * 3)) || (rc = w.init())) return rc;
     return init_alignment_dev(ds.as<double>(), ns, dt.as<double>(), nt, ground_ray, view_ray, w, R, t, scale);
 }
@@ -1037,7 +1018,7 @@ int mvs_init_alignment_sharded(const double* src, int64_t ns, const double* tgt_
     };
     LOCAL(args_ok());
     LOCAL(need_device());
-    Dev ds, dt; Work w;
+    Scratch ds, dt; Work w;
     LOCAL(up(ds, src, (size_t)ns * 3));
     LOCAL(up(dt, tgt_local, (size_t)nt_local * 3, 3));
     LOCAL(w.init());
@@ -1050,7 +1031,7 @@ int mvs_part_recog(const double* tmpl_pts, const int32_t* tmpl_labels, int64_t V
     int rc = need_device();
     if (rc) return rc;
     if (P == 0) return MVS_OK;
-    Dev dt, dl, dp, dout;
+    Scratch dt, dl, dp, dout;
     if ((rc = up(dt, tmpl_pts, (size_t)V * 3)) || (rc = up(dl, tmpl_labels, (size_t)V)) || (rc = up(dp, pts, (size_t)P * 3)) || (rc = dout.alloc(sizeof(int32_t) * P))) return rc;
     if ((rc = part_recog_dev(dt.as<double>(), dl.as<int32_t>(), V, dp.as<double>(), P, dout.as<int32_t>()))) return rc;
     return down(out_labels, dout, (size_t)P);
@@ -1062,7 +1043,7 @@ int mvs_remove_ground_sharded(int64_t* V, double* pts, double* normals, int64_t*
     if (!reduce || !V || !F || !ground_ray) { mvs_set_error("bad arguments"); return MVS_E_INVALID_ARG; }
     Reducer red; red.fn = reduce; red.ctx = reduce_ctx;
     int rc;
-    Dev dp, dn, df; Work w;
+    Scratch dp, dn, df; Work w;
     auto args_ok = [&]() {
         if (*V >= 0 && *F >= 0 && (*V == 0 || pts) && (*F == 0 || faces) && rank >= 0) return (int)MVS_OK;
         mvs_set_error("bad arguments"); return (int)MVS_E_INVALID_ARG;
@@ -1089,7 +1070,7 @@ int mvs_local_alignment_core_sharded(const double* src, const int32_t* s_labels,
     MVS_TRACE();
     if (!reduce) { mvs_set_error("bad arguments"); return MVS_E_INVALID_ARG; }
     Reducer red; red.fn = reduce; red.ctx = reduce_ctx;
-    Dev ds, dsl, dt, dtl; Work w;
+    Scratch ds, dsl, dt, dtl; Work w;
     auto args_ok = [&]() {
         if (src && s_labels && ns >= 2 && nt_local >= 0 && (nt_local == 0 || (tgt_local && t_labels_local)) && rank >= 0 && R && t && scale) return (int)MVS_OK;
         mvs_set_error("bad arguments"); return (int)MVS_E_INVALID_ARG;
@@ -1110,7 +1091,7 @@ int mvs_local_alignment_core(const double* src, const int32_t* s_labels, int64_t
     if (!src || !tgt || !s_labels || !t_labels || ns < 2 || nt < 2 || !R || !t || !scale) { mvs_set_error("bad arguments"); return MVS_E_INVALID_ARG; }
     int rc = need_device();
     if (rc) return rc;
-    Dev ds, dsl, dt, dtl; Work w;
+    Scratch ds, dsl, dt, dtl; Work w;
     if ((rc = up(ds, src, (size_t)ns * 3)) || (rc = up(dsl, s_labels, (size_t)ns)) || (rc = up(dt, tgt, (size_t)nt * 3)) || (rc = up(dtl, t_labels, (size_t)nt)) || (rc = w.init())) return rc;
     return local_core_dev(ds.as<double>(), dsl.as<int32_t>(), ns, dt.as<double>(), dtl.as<int32_t>(), nt, group_mask, label, w, R, t, scale);
 }
@@ -1176,7 +1157,7 @@ int mvs_align(double* src, double* s_normals, int64_t ns, const int32_t* s_label
     for (int64_t i = 0; i < ns; ++i) if (s_labels[i] < 0 || s_labels[i] > 31) { mvs_set_error("labels must be 0..31"); return MVS_E_INVALID_ARG; }
     int rc = need_device();
     if (rc) return rc;
-    Dev ds, dsn, dsl, dt, dtn, dtf, dtl; Work w;
+    Scratch ds, dsn, dsl, dt, dtn, dtf, dtl; Work w;
     if ((rc = up(ds, src, (size_t)ns * 3)) || (rc = up(dsn, s_normals, (size_t)ns * 3)) || (rc = up(dsl, s_labels, (size_t)ns)) ||
         (rc = up(dt, tgt, (size_t)*nt * 3)) || (rc = up(dtn, t_normals, (size_t)*nt * 3)) || (rc = up(dtf, t_faces, (size_t)*nf * 3)) ||
         (rc = dtl.alloc(sizeof(int32_t) * *nt)) || (rc = w.init())) return rc;
@@ -1201,7 +1182,7 @@ int mvs_align_dev(double* src, double* s_normals, int64_t ns, const int32_t* s_l
     int rc = need_device();
     if (rc) return rc;
     HIPCHK(hipDeviceSynchronize());                        // (the caller's arrays come from some other stream)
-    Dev ds, dsn, dsl; Work w;
+    Scratch ds, dsn, dsl; Work w;
     if ((rc = up(ds, src, (size_t)ns * 3)) || (rc = up(dsn, s_normals, (size_t)ns * 3)) || (rc = up(dsl, s_labels, (size_t)ns)) || (rc = w.init())) return rc;
     int64_t n = *nt, f = *nf;
     if ((rc = align_core_dev(ds.as<double>(), dsn.as<double>(), dsl.as<int32_t>(), ns, tgt_dev, t_normals_dev, &n, t_faces_dev, &f, t_labels_dev, view_ray,
@@ -1213,6 +1194,6 @@ int mvs_align_dev(double* src, double* s_normals, int64_t ns, const int32_t* s_l
 
 }  // extern "C"
 
-// one kernel of this translation unit, for the code-object preload of api_deform.cpp (mvs_set_device): asking the runtime for its
+// one kernel of this translation unit, for the code-object preload of runtime.cpp (mvs_set_device): asking the runtime for its
 // attributes loads the unit's code object without launching anything
 const void* mvs_tu_probe_align() { return (const void*)k_cc_init; }

@@ -7,148 +7,14 @@
 #include "../../include/mvs_test.h"
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <chrono>
 #include <cstring>
 #include <cstdlib>
 #include <tuple>
-#include <mutex>
-#include <condition_variable>
-#include <thread>
 #include <sched.h>
-#include <dlfcn.h>
-
-// ------------------------------------------------------------------ errors ----
-static thread_local char g_err[512] = "";
-static int g_device = 0;
-
-void mvs_set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-}
-int mvs_check_hip(hipError_t e, const char* what) {
-    if (e == hipSuccess) return MVS_OK;
-    mvs_set_error("HIP error %d (%s) at %s", (int)e, hipGetErrorString(e), what);
-    return e == hipErrorOutOfMemory ? MVS_E_OOM : MVS_E_HIP;
-}
-int mvs_current_device() { return g_device; }
-void mvs_preload(int device);
-void mvs_preload_join(int device);
-int mvs_debug_level() {
-    static const int level = [] { const char* e = getenv("MVS_DEBUG_CG"); return (e && *e) ? (e[0] == '2' ? 2 : 1) : 0; }();
-    return level;
-}
-
-// ---- cold start ----
-// The reference's process calls Processor::Deform ONCE (R/main.cpp:24-25): what a drop-in caller sees is the COLD call.  Two
-// things a first call pays that later ones do not: the runtime loads each translation unit's code object at the first use of one
-// of its kernels (twelve units), and the first stream of a process is a new hardware queue (hipStreamCreate: 5.7 ms, measured).
-// Both need nothing from the caller: a helper thread does them — once per device — as soon as the device is known
-// (mvs_set_device, or the first entry that needs a device), while the host reads its files; the thread is detached and
-// touches only the runtime and the stream pool (mutex).  mvs_preload_wait (mvs_test.h) joins the work, for measurements.
-const void* const* mvs_tu_kernels_grid(int*); const void* const* mvs_tu_kernels_assoc(int*); const void* const* mvs_tu_kernels_knn(int*);
-const void* const* mvs_tu_kernels_arap(int*); const void* const* mvs_tu_kernels_schwarz(int*); const void* const* mvs_tu_kernels_meshbuild(int*);
-const void* const* mvs_tu_kernels_geom(int*);
-const void* mvs_tu_probe_srt(); const void* mvs_tu_probe_align(); const void* mvs_tu_probe_consist(); const void* mvs_tu_probe_render(); const void* mvs_tu_probe_matchfilter();
-const void* mvs_tu_probe_stitch();
-void stream_pool_prime(int device);
-// (never destroyed: the helper thread is detached and may outlive the static destructors of an exiting process)
-static std::mutex& g_preload_mu = *new std::mutex;
-static std::condition_variable& g_preload_cv = *new std::condition_variable;
-static std::vector<int>& g_preload_started = *new std::vector<int>;
-static std::vector<int>& g_preload_done = *new std::vector<int>;
-void mvs_preload(int device) {
-    {
-        std::lock_guard<std::mutex> lk(g_preload_mu);
-        for (int d : g_preload_started) if (d == device) return;
-        g_preload_started.push_back(device);
-    }
-    std::thread([device] {
-        if (hipSetDevice(device) == hipSuccess) {
-            // the deformation path first, every kernel of it (a kernel's first launch otherwise pays its own resolution: the first
-            // outer iteration of a fresh process took 5.6-7.5 ms against 0.8 ms warm with only the code objects loaded), in the
-            // order a fit meets the units; then one kernel of each remaining unit
-            stream_pool_prime(device);
-            for (auto unit : {mvs_tu_kernels_meshbuild, mvs_tu_kernels_knn, mvs_tu_kernels_grid, mvs_tu_kernels_assoc, mvs_tu_kernels_arap, mvs_tu_kernels_schwarz,
-                              mvs_tu_kernels_geom}) {
-                int n = 0;
-                const void* const* ks = unit(&n);
-                for (int i = 0; i < n; ++i) { hipFuncAttributes a; if (hipFuncGetAttributes(&a, ks[i]) != hipSuccess) (void)hipGetLastError(); }
-            }
-            for (const void* k : {mvs_tu_probe_srt(), mvs_tu_probe_align(), mvs_tu_probe_consist(), mvs_tu_probe_render(), mvs_tu_probe_matchfilter(),
-                                  mvs_tu_probe_stitch()}) {
-                hipFuncAttributes a;
-                if (hipFuncGetAttributes(&a, k) != hipSuccess) (void)hipGetLastError();
-            }
-        }
-        std::lock_guard<std::mutex> lk(g_preload_mu);
-        g_preload_done.push_back(device);
-        g_preload_cv.notify_all();
-    }).detach();
-}
-void mvs_preload_join(int device) {
-    std::unique_lock<std::mutex> lk(g_preload_mu);
-    bool started = false;
-    for (int d : g_preload_started) started = started || d == device;
-    if (!started) return;
-    g_preload_cv.wait(lk, [&] { for (int d : g_preload_done) if (d == device) return true; return false; });
-}
-
-// ---- tracing (trace.h) ----
-static mvs_trace_fn g_trace_fn = nullptr;
-static void* g_trace_ctx = nullptr;
-static int (*g_roctx_push)(const char*) = nullptr;
-static int (*g_roctx_pop)() = nullptr;
-static bool g_roctx_on = false;
-bool mvs_trace_on() { return g_trace_fn != nullptr || g_roctx_on; }
-void mvs_trace_enter(const char* entry) {
-    if (g_roctx_on && g_roctx_push) (void)g_roctx_push(entry);
-    if (g_trace_fn) g_trace_fn(g_trace_ctx, entry, 0, 0.0);
-}
-void mvs_trace_leave(const char* entry, double host_ms) {
-    if (g_trace_fn) g_trace_fn(g_trace_ctx, entry, 1, host_ms);
-    if (g_roctx_on && g_roctx_pop) (void)g_roctx_pop();
-}
 
 extern "C" {
-
-int mvs_set_trace(mvs_trace_fn fn, void* ctx) { g_trace_ctx = ctx; g_trace_fn = fn; return MVS_OK; }
-int mvs_set_trace_roctx(int on) {
-    if (on && !g_roctx_push) {
-        void* lib = nullptr;
-        for (const char* name : {"libroctx64.so.4", "libroctx64.so", "/opt/rocm/lib/libroctx64.so", "librocprofiler-sdk-roctx.so"}) { lib = dlopen(name, RTLD_NOW | RTLD_GLOBAL); if (lib) break; }
-        if (lib) { g_roctx_push = (int (*)(const char*))dlsym(lib, "roctxRangePushA"); g_roctx_pop = (int (*)())dlsym(lib, "roctxRangePop"); }
-        if (!g_roctx_push || !g_roctx_pop) { g_roctx_push = nullptr; g_roctx_pop = nullptr; mvs_set_error("roctx is not available on this host"); return MVS_E_STATE; }
-    }
-    g_roctx_on = on != 0;
-    return MVS_OK;
-}
-
-const char* mvs_last_error(void) { return g_err; }
-int mvs_abi_version(void) { return MVS_ABI_VERSION; }
-int mvs_device_count(void) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) { (void)hipGetLastError(); return 0; }
-    return n;
-}
-int mvs_set_device(int device) {
-    if (device < 0 || device >= mvs_device_count()) { mvs_set_error("no such device %d", device); return MVS_E_NO_DEVICE; }
-    HIPCHK(hipSetDevice(device));
-    g_device = device;
-    mvs_preload(device);
-    return MVS_OK;
-}
-int mvs_device_name(char* buf, int buflen) {
-    if (!buf || buflen <= 0) return MVS_E_INVALID_ARG;
-    if (mvs_device_count() == 0) { mvs_set_error("no HIP device"); return MVS_E_NO_DEVICE; }
-    hipDeviceProp_t pr;
-    HIPCHK(hipGetDeviceProperties(&pr, g_device));
-    snprintf(buf, buflen, "%s (%s)", pr.name, pr.gcnArchName);
-    return MVS_OK;
-}
 
 void mvs_deform_default_params(mvs_deform_params* p) {
     if (!p) return;
@@ -170,107 +36,6 @@ template <class T> int dmalloc(T** p, size_t n) {
     return mvs_check_hip(hipMalloc((void**)p, n * sizeof(T)), "hipMalloc");
 }
 template <class T> void dfree(T*& p) { if (p) { (void)hipFree(p); p = nullptr; } }
-
-// Streams of destroyed handles are kept for the next handle: hipStreamCreate is the most expensive call of a cold
-// mvs_deform_create on this runtime (5.7 ms for a new hardware queue, measured; the whole device-side mesh build is < 1 ms).
-// A released stream has been synchronised by mvs_deform_destroy.  At most 64 idle streams are kept per process.
-struct PooledStream { int device; hipStream_t s; };
-std::mutex g_pool_mutex;
-std::vector<PooledStream> g_pool;
-int stream_acquire(int device, hipStream_t* out) {
-    {
-        std::lock_guard<std::mutex> lk(g_pool_mutex);
-        for (size_t i = 0; i < g_pool.size(); ++i)
-            if (g_pool[i].device == device) { *out = g_pool[i].s; g_pool.erase(g_pool.begin() + i); return MVS_OK; }
-    }
-    return mvs_check_hip(hipStreamCreateWithFlags(out, hipStreamNonBlocking), "hipStreamCreate");
-}
-}  // namespace
-// (cold start: one stream in the pool before the first handle asks for it)
-void stream_pool_prime(int device) {
-    {
-        std::lock_guard<std::mutex> lk(g_pool_mutex);
-        for (const PooledStream& p : g_pool) if (p.device == device) return;
-    }
-    hipStream_t s = nullptr;
-    if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); return; }
-    // the runtime's own fill / copy kernels and staging paths are loaded at their first use too (hipMemsetAsync, device-to-device
-    // and strided device-to-host copies: what a pass and its harvest enqueue): one use of each on a scratch buffer
-    {
-        void *d = nullptr, *hp = nullptr;
-        if (hipMalloc(&d, 1 << 16) == hipSuccess && hipHostMalloc(&hp, 1 << 12, hipHostMallocDefault) == hipSuccess) {
-            (void)hipMemsetAsync(d, 0, 1 << 16, s);
-            (void)hipMemsetAsync((char*)d + 4, 0, 4, s);
-            (void)hipMemcpyAsync((char*)d + (1 << 15), d, 1 << 14, hipMemcpyDeviceToDevice, s);
-            (void)hipMemcpy2DAsync(hp, 64, d, 1024, 64, 32, hipMemcpyDeviceToHost, s);
-            (void)hipMemcpyAsync(hp, d, 256, hipMemcpyDeviceToHost, s);
-            (void)hipMemcpyAsync(d, hp, 256, hipMemcpyHostToDevice, s);
-            char pageable[256] = {0};
-            (void)hipMemcpyAsync(pageable, d, sizeof pageable, hipMemcpyDeviceToHost, s);
-            (void)hipStreamSynchronize(s);
-            (void)hipMemcpyAsync(d, pageable, sizeof pageable, hipMemcpyHostToDevice, s);
-            (void)hipStreamSynchronize(s);
-        }
-        if (d) (void)hipFree(d);
-        if (hp) (void)hipHostFree(hp);
-        (void)hipGetLastError();
-    }
-    // ... and a second stream: a process that holds two handles at once (bench.py's reference-schedule leg beside its main handle)
-    // otherwise meets the 5.7 ms of a new hardware queue at the second handle's creation
-    hipStream_t s2 = nullptr;
-    if (hipStreamCreateWithFlags(&s2, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); s2 = nullptr; }
-    std::lock_guard<std::mutex> lk(g_pool_mutex);
-    g_pool.push_back({device, s});
-    if (s2) g_pool.push_back({device, s2});
-}
-namespace {
-void stream_release(int device, hipStream_t s) {
-    {
-        std::lock_guard<std::mutex> lk(g_pool_mutex);
-        if (g_pool.size() < 64) { g_pool.push_back({device, s}); return; }
-    }
-    (void)hipStreamDestroy(s);
-}
-
-// Set-up scratch of the same kind: the kNN table of mvs_deform_sample_nodes (device side) and its pinned landing zone.  hipFree of
-// the 3.5 MB table was 0.25 ms of a 1.1 ms call and the download into pageable memory another 0.15; a fresh Deformation per
-// Deform call (the reference's pattern) asks for the same sizes again and again.  One idle buffer of each kind per device.
-struct PooledBuf { int device; void* p; size_t bytes; bool pinned; };
-std::vector<PooledBuf> g_bufs;
-int scratch_acquire(int device, size_t bytes, bool pinned, void** out) {
-    {
-        std::lock_guard<std::mutex> lk(g_pool_mutex);
-        for (size_t i = 0; i < g_bufs.size(); ++i)
-            if (g_bufs[i].device == device && g_bufs[i].pinned == pinned && g_bufs[i].bytes >= bytes) { *out = g_bufs[i].p; const PooledBuf b = g_bufs[i]; g_bufs.erase(g_bufs.begin() + i); (void)b; return (int)MVS_OK; }
-    }
-    if (!pinned) return mvs_check_hip(hipMalloc(out, bytes), "hipMalloc");
-    // ordinary (CPU-cached, pageable) memory: the greedy pass READS the table on the host — from hipHostMalloc memory that pass
-    // took 1.7 ms instead of 0.5 (and registering malloc'ed memory did not help); "pinned" here only names the host-side pool
-    *out = std::malloc(bytes);
-    if (!*out) { mvs_set_error("out of host memory"); return MVS_E_OOM; }
-    return MVS_OK;
-}
-// (the caller has synchronised with everything that used the buffer)
-void scratch_release(int device, void* p, size_t bytes, bool pinned) {
-    if (!p) return;
-    PooledBuf old{0, nullptr, 0, false};
-    {
-        std::lock_guard<std::mutex> lk(g_pool_mutex);
-        size_t slot = g_bufs.size();
-        for (size_t i = 0; i < g_bufs.size(); ++i) if (g_bufs[i].device == device && g_bufs[i].pinned == pinned) slot = i;
-        if (slot == g_bufs.size()) { g_bufs.push_back({device, p, bytes, pinned}); return; }
-        if (g_bufs[slot].bytes >= bytes) old = PooledBuf{device, p, bytes, pinned};        // keep the larger one
-        else { old = g_bufs[slot]; g_bufs[slot] = PooledBuf{device, p, bytes, pinned}; }
-    }
-    if (old.p) { if (old.pinned) { std::free(old.p); } else (void)hipFree(old.p); }
-}
-
-int need_device() {
-    if (mvs_device_count() == 0) { mvs_set_error("no HIP device: the MI355X engine has no CPU fallback"); return MVS_E_NO_DEVICE; }
-    int rc = mvs_check_hip(hipSetDevice(g_device), "hipSetDevice");
-    if (!rc) mvs_preload(g_device);
-    return rc;
-}
 
 int check_params(const mvs_deform_params* p) {
     if (!p) { mvs_set_error("params is NULL"); return MVS_E_INVALID_ARG; }
@@ -1041,11 +806,13 @@ int mvs_deform_create(int64_t V, const double* points, const double* normals, in
     auto lap = [&](const char* what) { if (mvs_debug_level()) fprintf(stderr, "[mvs] create (api): %s at %.2f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_c0).count()); };
     int rc = need_device();
     if (rc) return rc;
+    const int dev = mvs_current_device();
+    mvs_preload(dev);
     lap("device");
     mvs_deform_s* h = new mvs_deform_s;
-    h->device = g_device; h->V = V; h->F = F;
+    h->device = dev; h->V = V; h->F = F;
 #define TRY(x) do { rc = (x); if (rc) { mvs_deform_destroy(h); return rc; } } while (0)
-    TRY(stream_acquire(g_device, &h->own_stream));
+    TRY(stream_acquire(dev, &h->own_stream));
     h->stream = h->own_stream;
     lap("stream");
     {   // pinned, host-coherent mirror of the control block: the last kernel of every pass writes it, the host reads it
@@ -1174,24 +941,24 @@ int mvs_deform_sample_nodes(mvs_deform_t h, int knn, int64_t* K) {
     auto lap = [&](const char* what) {
         if (mvs_debug_level()) fprintf(stderr, "[mvs] sample_nodes: %s at %.3f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     };
-    // one allocation: the table, then the search grid's workspace (from the process's scratch pool, as its pinned landing zone)
+    // one block of the scratch pool: the table, then the search grid's workspace; the host table is runtime.cpp's one-slot cache
     const size_t tab_bytes = (sizeof(int32_t) * (size_t)V * knn + 255) & ~(size_t)255;
     const size_t ws_bytes = V >= 1024 ? knn_grid_ws_bytes((int)V) : 0;
-    const size_t dev_bytes = tab_bytes + ws_bytes + 256;
-    char* d_mem = nullptr;
     int32_t* tab = nullptr;
-    int rc = scratch_acquire(h->device, dev_bytes, false, (void**)&d_mem);
-    if (!rc) rc = scratch_acquire(h->device, tab_bytes, true, (void**)&tab);
-    if (rc) { scratch_release(h->device, d_mem, dev_bytes, false); return rc; }
-    int32_t* d_tab = (int32_t*)d_mem;
-    lap("allocation");
-    if (ws_bytes) launch_knn_grid(h->d_pts, (int)V, knn, d_tab, d_mem + tab_bytes, h->stream);
-    else launch_knn(h->d_pts, (int)V, knn, d_tab, h->stream);
-    rc = mvs_check_hip(hipMemcpyAsync(tab, d_tab, sizeof(int32_t) * V * knn, hipMemcpyDeviceToHost, h->stream), "download");
-    if (!rc) rc = mvs_check_hip(hipStreamSynchronize(h->stream), "sync");
-    lap("kNN table on the host");
-    scratch_release(h->device, d_mem, dev_bytes, false);
-    if (rc) { scratch_release(h->device, tab, tab_bytes, true); return rc; }
+    int rc;
+    {
+        Scratch d_mem;
+        if ((rc = d_mem.alloc(tab_bytes + ws_bytes + 256, h->stream))) return rc;
+        if ((rc = host_table_acquire(tab_bytes, (void**)&tab))) return rc;
+        int32_t* d_tab = d_mem.as<int32_t>();
+        lap("allocation");
+        if (ws_bytes) launch_knn_grid(h->d_pts, (int)V, knn, d_tab, d_mem.as<char>() + tab_bytes, h->stream);
+        else launch_knn(h->d_pts, (int)V, knn, d_tab, h->stream);
+        rc = mvs_check_hip(hipMemcpyAsync(tab, d_tab, sizeof(int32_t) * V * knn, hipMemcpyDeviceToHost, h->stream), "download");
+        if (!rc) rc = mvs_check_hip(hipStreamSynchronize(h->stream), "sync");
+        lap("kNN table on the host");
+    }
+    if (rc) { host_table_release(tab, tab_bytes); return rc; }
     // greedy suppression in vertex order.  The rows of the table come straight from a DMA write (none of them in a CPU cache):
     // every row is requested a few vertices ahead — the loop's branch ("removed?") is predicted well enough for the core to run
     // ahead, a formulation without it (next zero bit of a bitmap) made every row fetch a serial DRAM round trip: 0.9 ms against 0.5
@@ -1208,7 +975,7 @@ int mvs_deform_sample_nodes(mvs_deform_t h, int knn, int64_t* K) {
             if (nb >= 0 && nb != i) removed[nb] = 1;        // :98-102
         }
     }
-    scratch_release(h->device, tab, tab_bytes, true);
+    host_table_release(tab, tab_bytes);
     lap("greedy suppression");
     rc = install_nodes(h, samp.data(), (int64_t)samp.size());   // (distinct and in range by construction)
     if (rc) return rc;
@@ -1517,6 +1284,7 @@ int mvs_knn_points(const double* pts, int64_t n, int k, int32_t* out_idx) {
     if (!pts || !out_idx || n <= 0 || k < 1 || k > 64 || n > 0x7ffffff0LL) { mvs_set_error("bad arguments (k 1..64)"); return MVS_E_INVALID_ARG; }
     int rc = need_device();
     if (rc) return rc;
+    mvs_preload(mvs_current_device());
     double* d = nullptr; int32_t* o = nullptr;
     rc = dmalloc(&d, (size_t)n * 3);
     if (!rc) rc = dmalloc(&o, (size_t)n * k);
@@ -1558,7 +1326,7 @@ int mvs_test_ctl(mvs_deform_t h, double* out, int n) {
 }
 
 // waits until the cold-start helper thread of the current device has loaded the code objects and primed the stream pool
-int mvs_test_preload_wait(void) { mvs_preload_join(g_device); return MVS_OK; }
+int mvs_test_preload_wait(void) { mvs_preload_join(mvs_current_device()); return MVS_OK; }
 
 // maxspin = polls a workgroup waits at the tail loop's device-wide barrier before it abandons the solve (<= 0: default);
 // plan_cap = at most this many launches per solve, the remaining sweeps run inside the last one (0: no cap); skip_wg = the

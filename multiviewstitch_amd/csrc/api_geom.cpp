@@ -8,22 +8,9 @@
 #include <cstring>
 #include <vector>
 
-int mvs_current_device();
-
 namespace {
 
-int need_device() {
-    if (mvs_device_count() == 0) { mvs_set_error("no HIP device: the MI355X engine has no CPU fallback"); return MVS_E_NO_DEVICE; }
-    return mvs_check_hip(hipSetDevice(mvs_current_device()), "hipSetDevice");
-}
 bool cam_ok(const mvs_camera* c) { return c && c->w > 0 && c->h > 0 && (int64_t)c->w * c->h < 0x7ffffff0LL; }
-
-struct DevBuf {               // RAII device scratch from the pool (scratch.cpp; these entries launch on the legacy default stream and end in a blocking copy)
-    void* p = nullptr;
-    int alloc(size_t bytes) { return mvs_scratch_alloc(&p, bytes ? bytes : 1); }
-    ~DevBuf() { mvs_scratch_free(p); }
-    template <class T> T* as() { return (T*)p; }
-};
 
 inline int msvc_rand(uint32_t* st) {          // MSVC rand(): SURVEY Appendix A.3
     *st = *st * 214013u + 2531011u;
@@ -54,9 +41,8 @@ int mvs_depth_to_model(const float* inv_depth, const mvs_camera* cam, double min
     int rc = need_device();
     if (rc) return rc;
     const size_t n = (size_t)cam->w * cam->h;
-    DevBuf dsp, pts, nrm, tex, fcs;
-    if ((rc = dsp.alloc(n * sizeof(float)))) return rc;
-    HIPCHK(hipMemcpy(dsp.p, inv_depth, n * sizeof(float), hipMemcpyHostToDevice));
+    Scratch dsp, pts, nrm, tex, fcs;                    // (these entries launch on the legacy default stream and end in a blocking copy)
+    if ((rc = up(dsp, inv_depth, n))) return rc;
     int64_t np = 0, nf = 0;
     rc = depth_to_model_dev(dsp.as<float>(), cam, min_dsp, max_dsp, smooth, &np, &nf, nullptr, nullptr, nullptr, nullptr, nullptr);
     if (rc) return rc;
@@ -69,10 +55,8 @@ int mvs_depth_to_model(const float* inv_depth, const mvs_camera* cam, double min
     rc = depth_to_model_dev(dsp.as<float>(), cam, min_dsp, max_dsp, smooth, &np, &nf, pts.as<double>(), nrm.as<double>(),
                             tex.as<int32_t>(), fcs.as<int32_t>(), nullptr);
     if (rc) return rc;
-    if (out_points && np) HIPCHK(hipMemcpy(out_points, pts.p, (size_t)np * 24, hipMemcpyDeviceToHost));
-    if (out_normals && np) HIPCHK(hipMemcpy(out_normals, nrm.p, (size_t)np * 24, hipMemcpyDeviceToHost));
-    if (out_tex_index && np) HIPCHK(hipMemcpy(out_tex_index, tex.p, (size_t)np * 4, hipMemcpyDeviceToHost));
-    if (out_faces && nf) HIPCHK(hipMemcpy(out_faces, fcs.p, (size_t)nf * 12, hipMemcpyDeviceToHost));
+    if ((out_points && (rc = down(out_points, pts, (size_t)np * 3))) || (out_normals && (rc = down(out_normals, nrm, (size_t)np * 3))) ||
+        (out_tex_index && (rc = down(out_tex_index, tex, (size_t)np))) || (out_faces && (rc = down(out_faces, fcs, (size_t)nf * 3)))) return rc;
     return MVS_OK;
 }
 
@@ -83,13 +67,11 @@ int mvs_depth_unproject(const float* inv_depth, const mvs_camera* cam, double mi
     int rc = need_device();
     if (rc) return rc;
     const size_t n = (size_t)cam->w * cam->h;
-    DevBuf dsp, pts, val;
-    if ((rc = dsp.alloc(n * 4)) || (rc = pts.alloc(n * 24)) || (rc = val.alloc(n))) return rc;
-    HIPCHK(hipMemcpy(dsp.p, inv_depth, n * 4, hipMemcpyHostToDevice));
+    Scratch dsp, pts, val;
+    if ((rc = up(dsp, inv_depth, n)) || (rc = pts.alloc(n * 24)) || (rc = val.alloc(n))) return rc;
     launch_depth_unproject(dsp.as<float>(), cam, min_dsp, max_dsp, pts.as<double>(), val.as<uint8_t>(), nullptr);
     HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out_points, pts.p, n * 24, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out_valid, val.p, n, hipMemcpyDeviceToHost));
+    if ((rc = down(out_points, pts, n * 3)) || (rc = down(out_valid, val, n))) return rc;
     return MVS_OK;
 }
 
@@ -132,18 +114,14 @@ int mvs_srt_fit(const double* matches, int64_t n, const mvs_camera* cam1, const 
         for (int64_t i = 0; i < (int64_t)iters * 3; ++i)
             if (triples[i] < 0 || triples[i] >= n) { mvs_set_error("triple index out of range"); return MVS_E_INVALID_ARG; }
     }
-    DevBuf dm, dt, dout;
-    if ((rc = dm.alloc((size_t)n * 48)) || (rc = dout.alloc(14 * 8))) return rc;
-    HIPCHK(hipMemcpy(dm.p, matches, (size_t)n * 48, hipMemcpyHostToDevice));
+    Scratch dm, dt, dout;
+    if ((rc = up(dm, matches, (size_t)n * 6)) || (rc = dout.alloc(14 * 8))) return rc;
     HIPCHK(hipMemset(dout.p, 0, 14 * 8));
-    if (mode == MVS_SRT_RANSAC) {
-        if ((rc = dt.alloc((size_t)iters * 12))) return rc;
-        HIPCHK(hipMemcpy(dt.p, triples, (size_t)iters * 12, hipMemcpyHostToDevice));
-    }
+    if (mode == MVS_SRT_RANSAC && (rc = up(dt, triples, (size_t)iters * 3))) return rc;
     rc = srt_fit_dev(dm.as<double>(), n, cam1, cam2, mode, dt.as<int32_t>(), iters, dout.as<double>(), nullptr);
     if (rc) return rc;
     double out[14];
-    HIPCHK(hipMemcpy(out, dout.p, sizeof out, hipMemcpyDeviceToHost));
+    if ((rc = down(out, dout, 14))) return rc;
     *scale = out[0];
     std::memcpy(R, out + 1, 9 * sizeof(double));
     std::memcpy(t, out + 10, 3 * sizeof(double));
@@ -157,16 +135,14 @@ int mvs_srt_residual(const double* matches, int64_t n, const mvs_camera* cam1, c
     if (!matches || !cam1 || !cam2 || !R || !t || n < 1 || (!mean_err && !per_match)) { mvs_set_error("bad arguments"); return MVS_E_INVALID_ARG; }
     int rc = need_device();
     if (rc) return rc;
-    DevBuf dm, drt, dpm;
-    if ((rc = dm.alloc((size_t)n * 48)) || (rc = drt.alloc(12 * 8)) || (rc = dpm.alloc((size_t)n * 16))) return rc;
     double Rt[12];
     std::memcpy(Rt, R, 72); std::memcpy(Rt + 9, t, 24);
-    HIPCHK(hipMemcpy(dm.p, matches, (size_t)n * 48, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(drt.p, Rt, sizeof Rt, hipMemcpyHostToDevice));
+    Scratch dm, drt, dpm;
+    if ((rc = up(dm, matches, (size_t)n * 6)) || (rc = up(drt, Rt, 12)) || (rc = dpm.alloc((size_t)n * 16))) return rc;
     launch_srt_residual(dm.as<double>(), n, make_camdev(cam1), make_camdev(cam2), scale, drt.as<double>(), dpm.as<double>(), nullptr);
     HIPCHK(hipDeviceSynchronize());
     std::vector<double> pm((size_t)n * 2);
-    HIPCHK(hipMemcpy(pm.data(), dpm.p, (size_t)n * 16, hipMemcpyDeviceToHost));
+    if ((rc = down(pm.data(), dpm, pm.size()))) return rc;
     if (per_match) std::memcpy(per_match, pm.data(), (size_t)n * 16);
     if (mean_err) {
         double err = 0.0;                                       // summed in match order, SRTSolver.cpp:25-27
@@ -303,22 +279,16 @@ int mvs_select_keyframe_pair(int32_t n1, int32_t n2, const mvs_camera* cams1, co
             uint32_t st = advance(start, ((int64_t)3 * act[a] + r) * per_round);       // (assumes 3 rounds for every earlier pair)
             if ((rc = mvs_srt_make_triples(p.size, iters, &st, tri.data() + (size_t)a * iters * 3))) return rc;
         }
-        DevBuf dm, doff, dset, dc1, dc2, dtri, dstats, dhyp, dout, dpm;
-        if ((rc = dm.alloc(m_all.size() * 8)) || (rc = doff.alloc(off.size() * 8)) || (rc = dset.alloc(set_of.size() * 4)) ||
-            (rc = dc1.alloc(c1.size() * sizeof(CamDev))) || (rc = dc2.alloc(c2.size() * sizeof(CamDev))) || (rc = dtri.alloc(tri.size() * 4)) ||
+        Scratch dm, doff, dset, dc1, dc2, dtri, dstats, dhyp, dout, dpm;
+        if ((rc = up(dm, m_all.data(), m_all.size())) || (rc = up(doff, off.data(), off.size())) || (rc = up(dset, set_of.data(), set_of.size())) ||
+            (rc = up(dc1, c1.data(), c1.size())) || (rc = up(dc2, c2.data(), c2.size())) || (rc = up(dtri, tri.data(), tri.size())) ||
             (rc = dstats.alloc(act.size() * 16 * 8)) || (rc = dhyp.alloc(act.size() * (size_t)iters * 13 * 8)) || (rc = dout.alloc(act.size() * 13 * 8)) ||
             (rc = dpm.alloc((size_t)tot * 16))) return rc;
-        HIPCHK(hipMemcpy(dm.p, m_all.data(), m_all.size() * 8, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(doff.p, off.data(), off.size() * 8, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dset.p, set_of.data(), set_of.size() * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dc1.p, c1.data(), c1.size() * sizeof(CamDev), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dc2.p, c2.data(), c2.size() * sizeof(CamDev), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dtri.p, tri.data(), tri.size() * 4, hipMemcpyHostToDevice));
         if ((rc = srt_ransac_round_batched(dm.as<double>(), doff.as<int64_t>(), (int)act.size(), tot, dset.as<int32_t>(), dc1.as<CamDev>(), dc2.as<CamDev>(),
                                            dtri.as<int32_t>(), iters, dstats.as<double>(), dhyp.as<double>(), dout.as<double>(), dpm.as<double>(), nullptr))) return rc;
         HIPCHK(hipDeviceSynchronize());
         std::vector<double> pm((size_t)tot * 2);
-        HIPCHK(hipMemcpy(pm.data(), dpm.p, pm.size() * 8, hipMemcpyDeviceToHost));
+        if ((rc = down(pm.data(), dpm, pm.size()))) return rc;
         for (size_t a = 0; a < act.size(); ++a) filter(el[act[a]], pm.data() + 2 * off[a]);
     }
     for (int e = 0; e < (int)el.size(); ++e) if (el[e].rounds < 3) { first_short = e; break; }
@@ -422,18 +392,13 @@ int mvs_srt_apply(const double* pts, const double* normals, int64_t P, double s,
     int rc = need_device();
     if (rc) return rc;
     if (P == 0) return MVS_OK;
-    DevBuf dp, dn, op, on;
-    if ((rc = dp.alloc((size_t)P * 24)) || (rc = op.alloc((size_t)P * 24))) return rc;
-    HIPCHK(hipMemcpy(dp.p, pts, (size_t)P * 24, hipMemcpyHostToDevice));
-    if (normals) {
-        if ((rc = dn.alloc((size_t)P * 24)) || (rc = on.alloc((size_t)P * 24))) return rc;
-        HIPCHK(hipMemcpy(dn.p, normals, (size_t)P * 24, hipMemcpyHostToDevice));
-    }
+    Scratch dp, dn, op, on;
+    if ((rc = up(dp, pts, (size_t)P * 3)) || (rc = op.alloc((size_t)P * 24))) return rc;
+    if (normals && ((rc = up(dn, normals, (size_t)P * 3)) || (rc = on.alloc((size_t)P * 24)))) return rc;
     launch_srt_apply(dp.as<double>(), normals ? dn.as<double>() : nullptr, P, s, R, t, inverse, op.as<double>(),
                      normals ? on.as<double>() : nullptr, nullptr);
     HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out_pts, op.p, (size_t)P * 24, hipMemcpyDeviceToHost));
-    if (normals) HIPCHK(hipMemcpy(out_normals, on.p, (size_t)P * 24, hipMemcpyDeviceToHost));
+    if ((rc = down(out_pts, op, (size_t)P * 3)) || (normals && (rc = down(out_normals, on, (size_t)P * 3)))) return rc;
     return MVS_OK;
 }
 

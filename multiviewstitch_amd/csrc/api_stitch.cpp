@@ -10,21 +10,7 @@
 #include <string>
 #include <vector>
 
-int mvs_current_device();
-
 namespace {
-
-int need_device() {
-    if (mvs_device_count() == 0) { mvs_set_error("no HIP device: the MI355X engine has no CPU fallback"); return MVS_E_NO_DEVICE; }
-    return mvs_check_hip(hipSetDevice(mvs_current_device()), "hipSetDevice");
-}
-
-struct DevBuf {               // RAII device scratch from the pool (scratch.cpp)
-    void* p = nullptr;
-    int alloc(size_t bytes, hipStream_t s = nullptr) { return mvs_scratch_alloc(&p, bytes ? bytes : 1, s); }
-    ~DevBuf() { mvs_scratch_free(p); }
-    template <class T> T* as() { return (T*)p; }
-};
 
 int bad(const char* fn, const char* what) { mvs_set_error("%s: %s", fn, what); return MVS_E_INVALID_ARG; }
 
@@ -87,13 +73,11 @@ int mvs_visibility_cull(const double* points, const int64_t* seg_off, int32_t n_
     if (rc) return rc;
     if ((rc = need_device())) return rc;
     const int64_t P = seg_off[n_seg];
-    DevBuf dp, dk;
-    if ((rc = dp.alloc((size_t)P * 24)) || (rc = dk.alloc((size_t)P))) return rc;
-    if (P) HIPCHK(hipMemcpy(dp.p, points, (size_t)P * 24, hipMemcpyHostToDevice));
+    Scratch dp, dk;
+    if ((rc = up(dp, points, (size_t)P * 3)) || (rc = dk.alloc((size_t)P))) return rc;
     if ((rc = vis_cull_dev(dp.as<double>(), seg_off, n_seg, n_seq, scales, R, t, cam_off, cams, mode, dk.as<uint8_t>(), nullptr, n_keep,
                            nullptr))) return rc;
-    if (P) HIPCHK(hipMemcpy(keep, dk.p, (size_t)P, hipMemcpyDeviceToHost));
-    return MVS_OK;
+    return down(keep, dk, (size_t)P);
 }
 
 int mvs_mesh_vertex_normals_dev(int64_t V, const double* points_dev, int64_t F, const int32_t* faces_dev, double* out_normals_dev,
@@ -113,13 +97,10 @@ int mvs_mesh_vertex_normals(int64_t V, const double* points, int64_t F, const in
     int rc = need_device();
     if (rc) return rc;
     if (V == 0) return MVS_OK;
-    DevBuf dp, df, dn;
-    if ((rc = dp.alloc((size_t)V * 24)) || (rc = df.alloc((size_t)F * 12)) || (rc = dn.alloc((size_t)V * 24))) return rc;
-    HIPCHK(hipMemcpy(dp.p, points, (size_t)V * 24, hipMemcpyHostToDevice));
-    if (F) HIPCHK(hipMemcpy(df.p, faces, (size_t)F * 12, hipMemcpyHostToDevice));
+    Scratch dp, df, dn;
+    if ((rc = up(dp, points, (size_t)V * 3)) || (rc = up(df, faces, (size_t)F * 3)) || (rc = dn.alloc((size_t)V * 24))) return rc;
     if ((rc = mesh_vertex_normals_dev(dp.as<double>(), V, df.as<int32_t>(), F, dn.as<double>(), nullptr))) return rc;
-    HIPCHK(hipMemcpy(out_normals, dn.p, (size_t)V * 24, hipMemcpyDeviceToHost));
-    return MVS_OK;
+    return down(out_normals, dn, (size_t)V * 3);
 }
 
 int mvs_processor_stitch_points(int32_t n_seq, const char* const* npts_paths, const double* scales, const double* R, const double* t,
@@ -148,23 +129,16 @@ int mvs_processor_stitch_points(int32_t n_seq, const char* const* npts_paths, co
         if (n != off[k + 1] - off[k]) { mvs_set_error("%s changed while it was read", npts_paths[k]); return MVS_E_IO; }
     }
     const int truncate = (flags & MVS_STITCH_TRUNCATE) ? 1 : 0;
-    DevBuf dp, dn, dk, op, on;
-    if ((rc = dp.alloc((size_t)P * 24)) || (rc = dn.alloc((size_t)P * 24)) || (rc = dk.alloc((size_t)P * 4 + 4)) ||
+    Scratch dp, dn, dk, op, on;
+    if ((rc = up(dp, hp.data(), (size_t)P * 3)) || (rc = up(dn, hn.data(), (size_t)P * 3)) || (rc = dk.alloc((size_t)P * 4 + 4)) ||
         (rc = op.alloc((size_t)P * 24)) || (rc = on.alloc((size_t)P * 24))) return rc;
-    if (P) {
-        HIPCHK(hipMemcpy(dp.p, hp.data(), (size_t)P * 24, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dn.p, hn.data(), (size_t)P * 24, hipMemcpyHostToDevice));
-    }
     std::vector<int64_t> nk(n_seq), oo(n_seq + 1);
     if ((rc = vis_cull_dev(dp.as<double>(), off.data(), n_seq, n_seq, scales, R, t, cam_off, cams, MVS_CULL_SEQUENCES, nullptr,
                            dk.as<int32_t>(), nk.data(), nullptr))) return rc;
     if ((rc = stitch_compact_dev(dp.as<double>(), dn.as<double>(), dk.as<int32_t>(), off.data(), n_seq, nk.data(), truncate, scales, R, t,
                                  op.as<double>(), on.as<double>(), oo.data(), nullptr))) return rc;
     const int64_t Q = oo[n_seq];
-    if (Q) {
-        HIPCHK(hipMemcpy(hp.data(), op.p, (size_t)Q * 24, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(hn.data(), on.p, (size_t)Q * 24, hipMemcpyDeviceToHost));
-    }
+    if ((rc = down(hp.data(), op, (size_t)Q * 3)) || (rc = down(hn.data(), on, (size_t)Q * 3))) return rc;
     for (int k = 0; k < n_seq; ++k) {                                     // :1029-1030
         char name[32];
         std::snprintf(name, sizeof name, "PSR%d.obj", k);
@@ -196,16 +170,11 @@ int mvs_processor_cull_model(const char* model_obj, int32_t n_seq, const double*
     if ((rc = mvs_obj_read(model_obj, &V, &N, &F, hp.data(), hn.data(), hf.data()))) return rc;
     for (int64_t i = 0; i < F * 3; ++i)
         if (hf[i] < 0 || hf[i] >= V) { mvs_set_error("%s: facet index %d outside [1, %lld]", model_obj, hf[i] + 1, (long long)V); return MVS_E_BAD_MESH; }
-    DevBuf dp, dn, df, dk;
-    if ((rc = dp.alloc((size_t)V * 24)) || (rc = dn.alloc((size_t)V * 24)) || (rc = df.alloc((size_t)F * 12)) ||
-        (rc = dk.alloc((size_t)V * 4 + 4))) return rc;
-    if (V) HIPCHK(hipMemcpy(dp.p, hp.data(), (size_t)V * 24, hipMemcpyHostToDevice));
-    if (F) HIPCHK(hipMemcpy(df.p, hf.data(), (size_t)F * 12, hipMemcpyHostToDevice));
-    if (N == 0) {                                                         // no `vn` lines: CalculateVertexNormals, PlyObj.cpp:11-14
-        if ((rc = mesh_vertex_normals_dev(dp.as<double>(), V, df.as<int32_t>(), F, dn.as<double>(), nullptr))) return rc;
-    } else if (V) {
-        HIPCHK(hipMemcpy(dn.p, hn.data(), (size_t)V * 24, hipMemcpyHostToDevice));
-    }
+    Scratch dp, dn, df, dk;
+    if ((rc = up(dp, hp.data(), (size_t)V * 3)) || (rc = up(dn, hn.data(), N ? (size_t)V * 3 : 0, (size_t)V * 3)) ||
+        (rc = up(df, hf.data(), (size_t)F * 3)) || (rc = dk.alloc((size_t)V * 4 + 4))) return rc;
+    // no `vn` lines: CalculateVertexNormals, PlyObj.cpp:11-14
+    if (N == 0 && (rc = mesh_vertex_normals_dev(dp.as<double>(), V, df.as<int32_t>(), F, dn.as<double>(), nullptr))) return rc;
     int32_t* keep = nullptr;
     if (all_seq_proj && V > 0) {                                          // :1064-1100
         const int64_t seg[2] = {0, V};
@@ -217,11 +186,7 @@ int mvs_processor_cull_model(const char* model_obj, int32_t n_seq, const double*
     }
     if ((rc = cull_retain_dev(dp.as<double>(), dn.as<double>(), &V, df.as<int32_t>(), &F, keep))) return rc;   // :1102-1103
     HIPCHK(hipDeviceSynchronize());
-    if (V) {
-        HIPCHK(hipMemcpy(hp.data(), dp.p, (size_t)V * 24, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(hn.data(), dn.p, (size_t)V * 24, hipMemcpyDeviceToHost));
-    }
-    if (F) HIPCHK(hipMemcpy(hf.data(), df.p, (size_t)F * 12, hipMemcpyDeviceToHost));
+    if ((rc = down(hp.data(), dp, (size_t)V * 3)) || (rc = down(hn.data(), dn, (size_t)V * 3)) || (rc = down(hf.data(), df, (size_t)F * 3))) return rc;
     if ((rc = mvs_obj_write(out_obj, V, hp.data(), hn.data(), F, hf.data()))) return rc;                       // :1104
     if (V_out) *V_out = V;
     if (F_out) *F_out = F;

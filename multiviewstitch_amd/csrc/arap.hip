@@ -785,11 +785,11 @@ void launch_vertex_normals(const double* pts, const int32_t* faces, const int32_
     k_vertex_normals<<<dim3((V + 255) / 256), dim3(256), 0, s>>>(pts, faces, vf_ptr, vf, V, out);
 }
 
-// one kernel of this translation unit, for the code-object preload of api_deform.cpp (mvs_set_device): asking the runtime for its
+// one kernel of this translation unit, for the code-object preload of runtime.cpp (mvs_set_device): asking the runtime for its
 // attributes loads the unit's code object without launching anything
 const void* mvs_tu_probe_arap() { return (const void*)k_smooth; }
 
-// every kernel of this translation unit, for the cold-start preload of api_deform.cpp (mvs_set_device): asking the runtime for a
+// every kernel of this translation unit, for the cold-start preload of runtime.cpp (mvs_set_device): asking the runtime for a
 // kernel's attributes loads the unit's code object and resolves the kernel without launching anything
 const void* const* mvs_tu_kernels_arap(int* n) {
     static const void* const ks[] = {

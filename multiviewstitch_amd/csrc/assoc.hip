@@ -2027,11 +2027,11 @@ void launch_assoc_all(const GridDev& g, const double* node_pts, const double* no
                                                                               (const float4*)sorted, nbr, mesh ? *mesh : SellDev{}, mesh_pts, nb);
 }
 
-// one kernel of this translation unit, for the code-object preload of api_deform.cpp (mvs_set_device): asking the runtime for its
+// one kernel of this translation unit, for the code-object preload of runtime.cpp (mvs_set_device): asking the runtime for its
 // attributes loads the unit's code object without launching anything
 const void* mvs_tu_probe_assoc() { return (const void*)k_assoc_prep; }
 
-// every kernel of this translation unit, for the cold-start preload of api_deform.cpp (mvs_set_device): asking the runtime for a
+// every kernel of this translation unit, for the cold-start preload of runtime.cpp (mvs_set_device): asking the runtime for a
 // kernel's attributes loads the unit's code object and resolves the kernel without launching anything
 const void* const* mvs_tu_kernels_assoc(int* n) {
     static const void* const ks[] = {

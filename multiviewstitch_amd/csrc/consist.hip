@@ -77,22 +77,6 @@ __global__ __launch_bounds__(TPB) void k_check_seq(const float* __restrict__ dsp
     out[o] = ok ? dpf : 0.0f;
 }
 
-struct Buf {
-    void* p = nullptr;
-    ~Buf() { mvs_scratch_free(p); }            // (pool of scratch.cpp: every user below ends in a synchronisation)
-    int alloc(size_t n, hipStream_t user = nullptr) {
-        if (mvs_scratch_alloc(&p, n ? n : 1, user) != MVS_OK) { mvs_set_error("hipMalloc(%zu) failed", n); return MVS_E_OOM; }
-        return MVS_OK;
-    }
-    template <class T> T* as() { return (T*)p; }
-};
-
-int have_device() {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { mvs_set_error("no HIP device"); return MVS_E_NO_DEVICE; }
-    return MVS_OK;
-}
-
 bool cam_fine(const mvs_camera* c) { return c && c->w > 0 && c->h > 0 && c->fx != 0.0 && c->fy != 0.0; }
 
 }  // namespace
@@ -107,18 +91,18 @@ int mvs_check_consistency_seq_dev(int32_t n_frames, const float* depths_dev, con
         if (!cam_fine(cams + f) || cams[f].w != cams[0].w || cams[f].h != cams[0].h) {
             mvs_set_error("mvs_check_consistency_seq: frames must share one raster size"); return MVS_E_INVALID_ARG;
         }
-    int rc = have_device();
+    int rc = need_device();
     if (rc) return rc;
     hipStream_t s = (hipStream_t)hip_stream;
     std::vector<CamDev> hc((size_t)n_frames);
     for (int f = 0; f < n_frames; ++f) hc[f] = make_camdev(cams + f);
-    Buf dc;
+    Scratch dc;
     if ((rc = dc.alloc(sizeof(CamDev) * hc.size(), s))) return rc;
     HIPCHK(hipMemcpyAsync(dc.p, hc.data(), sizeof(CamDev) * hc.size(), hipMemcpyHostToDevice, s));
     const int npx = cams[0].w * cams[0].h;
     k_check_seq<<<dim3((npx + TPB - 1) / TPB, n_frames), dim3(TPB), 0, s>>>(depths_dev, dc.as<CamDev>(), n_frames, min_dsp, max_dsp, reproj_err, out_dev);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(s));            // the camera table is freed on return
+    HIPCHK(hipStreamSynchronize(s));
     return MVS_OK;
 }
 
@@ -126,15 +110,13 @@ int mvs_check_consistency_seq(int32_t n_frames, const float* depths, const mvs_c
                               int32_t reproj_err, float* out) {
     MVS_TRACE();
     if (n_frames <= 0 || !depths || !cams || !out || !cam_fine(cams)) { mvs_set_error("mvs_check_consistency_seq: bad arguments"); return MVS_E_INVALID_ARG; }
-    int rc = have_device();
+    int rc = need_device();
     if (rc) return rc;
-    const size_t bytes = (size_t)n_frames * cams[0].w * cams[0].h * sizeof(float);
-    Buf din, dout;
-    if ((rc = din.alloc(bytes)) || (rc = dout.alloc(bytes))) return rc;
-    HIPCHK(hipMemcpy(din.p, depths, bytes, hipMemcpyHostToDevice));
+    const size_t n = (size_t)n_frames * cams[0].w * cams[0].h;
+    Scratch din, dout;
+    if ((rc = up(din, depths, n)) || (rc = dout.alloc(sizeof(float) * n))) return rc;
     if ((rc = mvs_check_consistency_seq_dev(n_frames, din.as<float>(), cams, min_dsp, max_dsp, reproj_err, dout.as<float>(), nullptr))) return rc;
-    HIPCHK(hipMemcpy(out, dout.p, bytes, hipMemcpyDeviceToHost));
-    return MVS_OK;
+    return down(out, dout, n);
 }
 
 int mvs_check_consistency(const float* depth, const mvs_camera* cur, int32_t n_ref, const float* const* ref_depths,
@@ -147,18 +129,16 @@ int mvs_check_consistency(const float* depth, const mvs_camera* cur, int32_t n_r
         if (!ref_depths[k] || !cam_fine(ref_cams + k) || ref_cams[k].w != cur->w || ref_cams[k].h != cur->h) {
             mvs_set_error("mvs_check_consistency: reference frames must have the raster size of the current frame"); return MVS_E_INVALID_ARG;
         }
-    int rc = have_device();
+    int rc = need_device();
     if (rc) return rc;
-    const size_t bytes = (size_t)cur->w * cur->h * sizeof(float);
-    Buf din, dout, dref[MAXREF];
-    if ((rc = din.alloc(bytes)) || (rc = dout.alloc(bytes))) return rc;
-    HIPCHK(hipMemcpy(din.p, depth, bytes, hipMemcpyHostToDevice));
+    const size_t n = (size_t)cur->w * cur->h;
+    Scratch din, dout, dref[MAXREF];
+    if ((rc = up(din, depth, n)) || (rc = dout.alloc(sizeof(float) * n))) return rc;
     RefSet rs;
     rs.n = n_ref;
     for (int k = 0; k < MAXREF; ++k) { rs.dsp[k] = nullptr; rs.cam[k] = make_camdev(cur); }
     for (int k = 0; k < n_ref; ++k) {
-        if ((rc = dref[k].alloc(bytes))) return rc;
-        HIPCHK(hipMemcpy(dref[k].p, ref_depths[k], bytes, hipMemcpyHostToDevice));
+        if ((rc = up(dref[k], ref_depths[k], n))) return rc;
         rs.dsp[k] = dref[k].as<float>();
         rs.cam[k] = make_camdev(ref_cams + k);
     }
@@ -166,12 +146,11 @@ int mvs_check_consistency(const float* depth, const mvs_camera* cur, int32_t n_r
     k_check_core<<<dim3((npx + TPB - 1) / TPB), dim3(TPB), 0, nullptr>>>(din.as<float>(), make_camdev(cur), rs, min_dsp, max_dsp, reproj_err, dout.as<float>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out, dout.p, bytes, hipMemcpyDeviceToHost));
-    return MVS_OK;
+    return down(out, dout, n);
 }
 
 }  // extern "C"
 
-// one kernel of this translation unit, for the code-object preload of api_deform.cpp (mvs_set_device): asking the runtime for its
+// one kernel of this translation unit, for the code-object preload of runtime.cpp (mvs_set_device): asking the runtime for its
 // attributes loads the unit's code object without launching anything
 const void* mvs_tu_probe_consist() { return (const void*)k_check_core; }

@@ -373,9 +373,41 @@ bool ras_can_fuse_local(const mvs_deform_s* h);   // patches <= MVS_NBMAX and wo
 int  ras_local_parts(const mvs_deform_s* h);      // partial sums per reduction the local step leaves (what its consumers fold)
 int  mvs_device_cus(int device);                  // compute units of a device (mutex-guarded table, one entry per device)
 #define MVS_MAX_DEVICES 64
-// scratch pool of the host-driven entries (scratch.cpp: blocks are kept for the next call; users launch on the legacy default stream)
+// scratch pool of the host-driven entries (runtime.cpp: blocks are kept for the next call)
 int  mvs_scratch_alloc(void** p, size_t bytes, hipStream_t user = nullptr);   // user: the stream the block will be used on, when it is not the legacy default stream
-void mvs_scratch_free(void* p);
+void mvs_scratch_free(void* p, hipStream_t user = nullptr);                   // user != null: synchronised before the block goes back
+
+// The one RAII block of the pool: handed back behind the stream it was allocated for, so an early return cannot give the pool a
+// block that queued work still touches.
+struct Scratch {
+    void* p = nullptr;
+    hipStream_t s = nullptr;
+    Scratch() = default;
+    Scratch(const Scratch&) = delete;
+    Scratch& operator=(const Scratch&) = delete;
+    ~Scratch() { mvs_scratch_free(p, s); }
+    int alloc(size_t bytes, hipStream_t stream = nullptr) { s = stream; return mvs_scratch_alloc(&p, bytes ? bytes : 1, stream); }
+    template <class T> T* as() const { return (T*)p; }
+};
+// blocking upload of n elements into a fresh block of max(n, cap) elements; blocking download of n elements
+template <class T> int up(Scratch& d, const T* h, size_t n, size_t cap = 0) {
+    int rc = d.alloc(sizeof(T) * (n > cap ? n : cap));
+    if (rc || !n) return rc;
+    return mvs_check_hip(hipMemcpy(d.p, h, sizeof(T) * n, hipMemcpyHostToDevice), "upload");
+}
+template <class T> int down(T* h, const Scratch& d, size_t n) {
+    return n ? mvs_check_hip(hipMemcpy(h, d.p, sizeof(T) * n, hipMemcpyDeviceToHost), "download") : MVS_OK;
+}
+// the rest of the process-wide state (runtime.cpp)
+int  mvs_current_device();
+int  need_device();                                   // MVS_E_NO_DEVICE without a HIP device, else selects mvs_current_device() on this thread
+void mvs_preload(int device);                         // cold start: code objects and the stream pool, on a helper thread, once per device
+void mvs_preload_join(int device);
+int  stream_acquire(int device, hipStream_t* out);    // stream pool of the deformation handles
+void stream_release(int device, hipStream_t s);       // (s has been synchronised)
+void stream_pool_prime(int device);
+int  host_table_acquire(size_t bytes, void** out);   // host half of sample_nodes' kNN table: one idle block kept
+void host_table_release(void* p, size_t bytes);
 void launch_vertex_normals(const double* pts, const int32_t* faces, const int32_t* vf_ptr, const int32_t* vf,
                            int V, double* out, hipStream_t s);
 

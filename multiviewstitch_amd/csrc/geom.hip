@@ -147,11 +147,11 @@ int depth_to_model_dev(const float* dsp_dev, const mvs_camera* cam, double mn, d
     const int w = cam->w, h = cam->h, n = w * h;
     const double thr = (double)(float)(smooth * (mx - mn) / 100);        // `float threshold`, Depth2Model.cpp:45
     int32_t *flag = nullptr, *vstart = nullptr, *fcnt = nullptr, *fstart = nullptr;
-    int32_t* four = nullptr;                                             // one block of the scratch pool (scratch.cpp) for the four tables
+    Scratch four;                                                        // one block of the scratch pool for the four tables
     const size_t stride = ((size_t)n + 1 + 63) / 64 * 64;
-    int rc = mvs_scratch_alloc((void**)&four, sizeof(int32_t) * 4 * stride, s);
+    int rc = four.alloc(sizeof(int32_t) * 4 * stride, s);
     if (rc) return rc;
-    flag = four; vstart = four + stride; fcnt = four + 2 * stride; fstart = four + 3 * stride;
+    flag = four.as<int32_t>(); vstart = flag + stride; fcnt = flag + 2 * stride; fstart = flag + 3 * stride;
     const dim3 g((n + TPB - 1) / TPB), b(TPB);
     k_depth_valid<<<g, b, 0, s>>>(dsp_dev, n, mn, mx, flag);
     k_quad_count<<<g, b, 0, s>>>(dsp_dev, w, h, mn, mx, thr, fcnt);
@@ -168,8 +168,6 @@ int depth_to_model_dev(const float* dsp_dev, const mvs_camera* cam, double mn, d
             rc = mvs_check_hip(hipStreamSynchronize(s), "depth_emit");
         }
     }
-    if (rc) (void)hipStreamSynchronize(s);                               // (the block goes back behind the stream's work)
-    mvs_scratch_free(four);
     return rc;
 }
 
@@ -187,11 +185,11 @@ void launch_srt_apply(const double* pts, const double* nrm, int64_t P, double sc
     k_srt_apply<<<dim3((unsigned)blocks), dim3(TPB), 0, s>>>(pts, nrm, P, m, out_pts, out_nrm);
 }
 
-// one kernel of this translation unit, for the code-object preload of api_deform.cpp (mvs_set_device): asking the runtime for its
+// one kernel of this translation unit, for the code-object preload of runtime.cpp (mvs_set_device): asking the runtime for its
 // attributes loads the unit's code object without launching anything
 const void* mvs_tu_probe_geom() { return (const void*)k_srt_apply; }
 
-// every kernel of this translation unit, for the cold-start preload of api_deform.cpp (mvs_set_device): asking the runtime for a
+// every kernel of this translation unit, for the cold-start preload of runtime.cpp (mvs_set_device): asking the runtime for a
 // kernel's attributes loads the unit's code object and resolves the kernel without launching anything
 const void* const* mvs_tu_kernels_geom(int* n) {
     static const void* const ks[] = {

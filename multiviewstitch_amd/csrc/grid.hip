@@ -171,13 +171,10 @@ void scan_exclusive_i32_async(const int32_t* in, int64_t n, int32_t* out, int32_
 // allocating, synchronising form (set-up paths of geom.hip / align.hip)
 int scan_exclusive_i32(const int32_t* in, int64_t n, int32_t* out, hipStream_t s) {
     const int64_t nb = (n + 1 + SCAN_ELEMS - 1) / SCAN_ELEMS;
-    int32_t* bsum = nullptr;
-    int rc = mvs_scratch_alloc((void**)&bsum, sizeof(int32_t) * nb, s);          // (pool of scratch.cpp; handed back behind the synchronisation)
-    if (rc) return rc;
-    scan_exclusive_i32_async(in, n, out, bsum, s);
-    rc = mvs_check_hip(hipStreamSynchronize(s), "scan");
-    mvs_scratch_free(bsum);
-    return rc;
+    Scratch bsum;
+    if (int rc = bsum.alloc(sizeof(int32_t) * nb, s)) return rc;
+    scan_exclusive_i32_async(in, n, out, bsum.as<int32_t>(), s);
+    return mvs_check_hip(hipStreamSynchronize(s), "scan");
 }
 
 namespace {
@@ -303,11 +300,11 @@ int grid_build(mvs_deform_s* h, int64_t P, const double* pts_dev, const double* 
     return mvs_check_hip(hipGetLastError(), "grid_build");
 }
 
-// one kernel of this translation unit, for the code-object preload of api_deform.cpp (mvs_set_device): asking the runtime for its
+// one kernel of this translation unit, for the code-object preload of runtime.cpp (mvs_set_device): asking the runtime for its
 // attributes loads the unit's code object without launching anything
 const void* mvs_tu_probe_grid() { return (const void*)k_bbox; }
 
-// every kernel of this translation unit, for the cold-start preload of api_deform.cpp (mvs_set_device): asking the runtime for a
+// every kernel of this translation unit, for the cold-start preload of runtime.cpp (mvs_set_device): asking the runtime for a
 // kernel's attributes loads the unit's code object and resolves the kernel without launching anything
 const void* const* mvs_tu_kernels_grid(int* n) {
     static const void* const ks[] = {

@@ -23,7 +23,7 @@ inline double mvs_knob_env(const char* name, double dflt, double lo, double hi) 
 #endif
 
 // trace level of the host side: MVS_DEBUG_CG=1 (plans, verdicts, set-up laps) or 2 (+ residual histories) in the
-// environment when the library is loaded; read once (api_deform.cpp), 0 otherwise.  It changes no result.
+// environment when the library is loaded; read once (runtime.cpp), 0 otherwise.  It changes no result.
 int mvs_debug_level();
 
 #endif

@@ -43,16 +43,6 @@ __global__ void k_ssd(const int32_t* __restrict__ m, int n, const uint8_t* __res
     err[i] = e;
 }
 
-struct Buf {
-    void* p = nullptr;
-    ~Buf() { mvs_scratch_free(p); }            // (pool of scratch.cpp: every user below ends in a synchronisation)
-    int alloc(size_t n) {
-        if (mvs_scratch_alloc(&p, n ? n : 1) != MVS_OK) { mvs_set_error("hipMalloc(%zu) failed", n); return MVS_E_OOM; }
-        return MVS_OK;
-    }
-    template <class T> T* as() { return (T*)p; }
-};
-
 }  // namespace
 
 extern "C" int mvs_match_filter(const int32_t* raw, int64_t n, const int32_t* tex1, const uint8_t* valid1, const int32_t* tex2,
@@ -78,20 +68,16 @@ extern "C" int mvs_match_filter(const int32_t* raw, int64_t n, const int32_t* te
     for (const auto& q : uniq) m.insert(m.end(), q.begin(), q.end());
     const int n1 = (int)uniq.size();
     // 2. SSD window (:683-707) on the GPU
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) { mvs_set_error("no HIP device"); return MVS_E_NO_DEVICE; }
+    if (int rc = need_device()) return rc;
     std::vector<double> err((size_t)n1);
     if (n1 > 0) {
-        Buf dm, d1, d2, de;
+        Scratch dm, d1, d2, de;
         int rc;
-        if ((rc = dm.alloc(sizeof(int32_t) * 4 * (size_t)n1)) || (rc = d1.alloc((size_t)npx * 3)) || (rc = d2.alloc((size_t)npx * 3)) ||
+        if ((rc = up(dm, m.data(), 4 * (size_t)n1)) || (rc = up(d1, img1, (size_t)npx * 3)) || (rc = up(d2, img2, (size_t)npx * 3)) ||
             (rc = de.alloc(sizeof(double) * (size_t)n1))) return rc;
-        HIPCHK(hipMemcpy(dm.p, m.data(), sizeof(int32_t) * 4 * (size_t)n1, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(d1.p, img1, (size_t)npx * 3, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(d2.p, img2, (size_t)npx * 3, hipMemcpyHostToDevice));
         k_ssd<<<dim3((n1 + 127) / 128), dim3(128)>>>(dm.as<int32_t>(), n1, d1.as<uint8_t>(), d2.as<uint8_t>(), w, h, p->ssd_win, de.as<double>());
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpy(err.data(), de.p, sizeof(double) * (size_t)n1, hipMemcpyDeviceToHost));
+        if ((rc = down(err.data(), de, (size_t)n1))) return rc;
     }
     std::vector<int32_t> m2;
     for (int k = 0; k < n1; ++k)
@@ -114,6 +100,6 @@ extern "C" int mvs_match_filter(const int32_t* raw, int64_t n, const int32_t* te
     return MVS_OK;
 }
 
-// one kernel of this translation unit, for the code-object preload of api_deform.cpp (mvs_set_device): asking the runtime for its
+// one kernel of this translation unit, for the code-object preload of runtime.cpp (mvs_set_device): asking the runtime for its
 // attributes loads the unit's code object without launching anything
 const void* mvs_tu_probe_matchfilter() { return (const void*)k_ssd; }

@@ -821,11 +821,11 @@ int mesh_build(mvs_deform_s* h, const double* points, const double* normals, con
     return MVS_OK;
 }
 
-// one kernel of this translation unit, for the code-object preload of api_deform.cpp (mvs_set_device): asking the runtime for its
+// one kernel of this translation unit, for the code-object preload of runtime.cpp (mvs_set_device): asking the runtime for its
 // attributes loads the unit's code object without launching anything
 const void* mvs_tu_probe_meshbuild() { return (const void*)k_iota; }
 
-// every kernel of this translation unit, for the cold-start preload of api_deform.cpp (mvs_set_device): asking the runtime for a
+// every kernel of this translation unit, for the cold-start preload of runtime.cpp (mvs_set_device): asking the runtime for a
 // kernel's attributes loads the unit's code object and resolves the kernel without launching anything
 const void* const* mvs_tu_kernels_meshbuild(int* n) {
     static const void* const ks[] = {

@@ -117,16 +117,6 @@ __global__ void k_rd_convert(const uint32_t* __restrict__ zbuf, int w, int h, do
     out[idx] = r;
 }
 
-struct Buf {
-    void* p = nullptr;
-    ~Buf() { mvs_scratch_free(p); }            // (pool of scratch.cpp: every user below ends in a synchronisation)
-    int alloc(size_t n, hipStream_t user = nullptr) {
-        if (mvs_scratch_alloc(&p, n ? n : 1, user) != MVS_OK) { mvs_set_error("hipMalloc(%zu) failed", n); return MVS_E_OOM; }
-        return MVS_OK;
-    }
-    template <class T> T* as() { return (T*)p; }
-};
-
 }  // namespace
 
 extern "C" {
@@ -136,20 +126,19 @@ int mvs_render_depth_dev(const double* pts_dev, int64_t V, const int32_t* faces_
     MVS_TRACE();
     if (!pts_dev || V <= 0 || F < 0 || (F && !faces_dev) || !cam || cam->w <= 0 || cam->h <= 0 || !(znear > 0) || !(zfar > znear) ||
         !out_dev || cam->cx == 0.0 || cam->cy == 0.0) { mvs_set_error("mvs_render_depth: bad arguments"); return MVS_E_INVALID_ARG; }
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { mvs_set_error("no HIP device"); return MVS_E_NO_DEVICE; }
+    int rc = need_device();
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)hip_stream;
     const GlCam g = make_glcam(cam, znear, zfar);
     const int npx = cam->w * cam->h;
-    Buf win, zb;
-    int rc;
+    Scratch win, zb;
     if ((rc = win.alloc(sizeof(float4) * (size_t)V, s)) || (rc = zb.alloc(sizeof(uint32_t) * (size_t)npx, s))) return rc;
     HIPCHK(hipMemsetD32Async((hipDeviceptr_t)zb.p, 0x3f800000, (size_t)npx, s));           // glClearDepth(1.0f)
     k_rd_project<<<dim3((unsigned)((V + TPB - 1) / TPB)), dim3(TPB), 0, s>>>(pts_dev, V, g, win.as<float4>());
     if (F) k_rd_raster<<<dim3((unsigned)((F + TPB - 1) / TPB)), dim3(TPB), 0, s>>>(win.as<float4>(), faces_dev, F, cam->w, cam->h, zb.as<uint32_t>());
     k_rd_convert<<<dim3((npx + TPB - 1) / TPB), dim3(TPB), 0, s>>>(zb.as<uint32_t>(), cam->w, cam->h, g.znear, g.zfar, out_dev);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(s));            // scratch buffers are freed on return
+    HIPCHK(hipStreamSynchronize(s));
     return MVS_OK;
 }
 
@@ -159,21 +148,17 @@ int mvs_render_depth(const double* pts, int64_t V, const int32_t* faces, int64_t
     if (!pts || V <= 0 || F < 0 || (F && !faces) || !cam || !out) { mvs_set_error("mvs_render_depth: bad arguments"); return MVS_E_INVALID_ARG; }
     for (int64_t k = 0; k < 3 * F; ++k)
         if (faces[k] < 0 || faces[k] >= V) { mvs_set_error("mvs_render_depth: facet index out of range"); return MVS_E_BAD_MESH; }
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { mvs_set_error("no HIP device"); return MVS_E_NO_DEVICE; }
-    Buf dp, df, dout;
-    int rc;
+    int rc = need_device();
+    if (rc) return rc;
+    Scratch dp, df, dout;
     const size_t npx = (size_t)std::max(cam->w, 0) * (size_t)std::max(cam->h, 0);
-    if ((rc = dp.alloc(sizeof(double) * 3 * (size_t)V)) || (rc = df.alloc(sizeof(int32_t) * 3 * (size_t)F)) || (rc = dout.alloc(sizeof(float) * npx))) return rc;
-    HIPCHK(hipMemcpy(dp.p, pts, sizeof(double) * 3 * (size_t)V, hipMemcpyHostToDevice));
-    if (F) HIPCHK(hipMemcpy(df.p, faces, sizeof(int32_t) * 3 * (size_t)F, hipMemcpyHostToDevice));
+    if ((rc = up(dp, pts, 3 * (size_t)V)) || (rc = up(df, faces, 3 * (size_t)F)) || (rc = dout.alloc(sizeof(float) * npx))) return rc;
     if ((rc = mvs_render_depth_dev(dp.as<double>(), V, df.as<int32_t>(), F, cam, znear, zfar, dout.as<float>(), nullptr))) return rc;
-    HIPCHK(hipMemcpy(out, dout.p, sizeof(float) * npx, hipMemcpyDeviceToHost));
-    return MVS_OK;
+    return down(out, dout, npx);
 }
 
 }  // extern "C"
 
-// one kernel of this translation unit, for the code-object preload of api_deform.cpp (mvs_set_device): asking the runtime for its
+// one kernel of this translation unit, for the code-object preload of runtime.cpp (mvs_set_device): asking the runtime for its
 // attributes loads the unit's code object without launching anything
 const void* mvs_tu_probe_render() { return (const void*)k_rd_project; }

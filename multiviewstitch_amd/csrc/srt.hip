@@ -292,23 +292,22 @@ int srt_ransac_round_batched(const double* m_all, const int64_t* off, int sets, 
 
 int srt_fit_dev(const double* matches_dev, int64_t n, const mvs_camera* c1, const mvs_camera* c2, int mode,
                 const int32_t* triples_dev, int iters, double* out_dev, hipStream_t s) {
-    double *stats = nullptr, *hyp = nullptr;
-    int rc0 = mvs_scratch_alloc((void**)&stats, sizeof(double) * 16, s);            // (pool of scratch.cpp: the stream is waited for before the blocks go back)
-    if (rc0) return rc0;
+    Scratch sstats, shyp;
+    int rc = sstats.alloc(sizeof(double) * 16, s);
+    if (rc) return rc;
+    double* stats = sstats.as<double>();
     k_srt_stats<<<dim3(1), dim3(256), 0, s>>>(matches_dev, n, stats);
     if (mode == MVS_SRT_CLOSED_FORM) {
         k_srt_closed<<<dim3(1), dim3(64), 0, s>>>(stats, out_dev);
     } else {
-        if ((rc0 = mvs_scratch_alloc((void**)&hyp, sizeof(double) * 13 * (size_t)iters, s))) { (void)hipStreamSynchronize(s); mvs_scratch_free(stats); return rc0; }
+        if ((rc = shyp.alloc(sizeof(double) * 13 * (size_t)iters, s))) return rc;
+        double* hyp = shyp.as<double>();
         k_srt_ransac<<<dim3(iters), dim3(64), 0, s>>>(matches_dev, n, make_camdev(c1), make_camdev(c2), stats,
                                                                  triples_dev, iters, hyp);
         k_srt_pick<<<dim3(1), dim3(64), 0, s>>>(hyp, iters, stats, out_dev);
     }
     if (c1 && c2) k_srt_residual_out<<<dim3(1), dim3(64), 0, s>>>(matches_dev, n, make_camdev(c1), make_camdev(c2), out_dev);
-    int rc = mvs_check_hip(hipStreamSynchronize(s), "srt_fit");
-    mvs_scratch_free(stats);
-    mvs_scratch_free(hyp);
-    return rc;
+    return mvs_check_hip(hipStreamSynchronize(s), "srt_fit");
 }
 
 void launch_srt_residual(const double* matches_dev, int64_t n, const CamDev& c1, const CamDev& c2, double scale,
@@ -317,6 +316,6 @@ void launch_srt_residual(const double* matches_dev, int64_t n, const CamDev& c1,
     k_srt_residual<<<dim3((unsigned)((n + 127) / 128)), dim3(128), 0, s>>>(matches_dev, n, c1, c2, scale, Rt_dev, per_match_dev);
 }
 
-// one kernel of this translation unit, for the code-object preload of api_deform.cpp (mvs_set_device): asking the runtime for its
+// one kernel of this translation unit, for the code-object preload of runtime.cpp (mvs_set_device): asking the runtime for its
 // attributes loads the unit's code object without launching anything
 const void* mvs_tu_probe_srt() { return (const void*)k_srt_closed; }

@@ -167,13 +167,6 @@ __global__ void k_vn_vertex(const int32_t* __restrict__ start, int32_t* __restri
 
 inline dim3 blocks_of(int64_t n) { return dim3((unsigned)std::max<int64_t>(1, (n + TPB - 1) / TPB)); }
 
-struct SBuf {                 // RAII block of the scratch pool (scratch.cpp), used on stream s
-    void* p = nullptr;
-    int alloc(size_t b, hipStream_t s) { return mvs_scratch_alloc(&p, b ? b : 1, s); }
-    ~SBuf() { mvs_scratch_free(p); }
-    template <class T> T* as() const { return (T*)p; }
-};
-
 }  // namespace
 
 // ------------------------------------------------------------------ launchers ----
@@ -198,7 +191,7 @@ int vis_cull_dev(const double* pts_dev, const int64_t* seg_off, int n_seg, int n
         }
     std::vector<CamDev> cd((size_t)std::max(n_cams, 1));
     for (int c = 0; c < n_cams; ++c) cd[c] = make_camdev(&cams[c]);
-    SBuf dseg, dmaps, doff, dcams, dcnt;
+    Scratch dseg, dmaps, doff, dcams, dcnt;
     int rc;
     if ((rc = dseg.alloc(sizeof(int64_t) * (n_seg + 1), s)) || (rc = dmaps.alloc(sizeof(CullMap) * maps.size(), s)) ||
         (rc = doff.alloc(sizeof(int32_t) * (n_seq + 1), s)) || (rc = dcams.alloc(sizeof(CamDev) * cd.size(), s)) ||
@@ -222,7 +215,7 @@ int vis_cull_dev(const double* pts_dev, const int64_t* seg_off, int n_seg, int n
     }
     std::vector<unsigned long long> cnt(n_seg);
     HIPCHK(hipMemcpyAsync(cnt.data(), dcnt.p, sizeof(unsigned long long) * n_seg, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));                                      // (the tables go back to the pool behind the launch)
+    HIPCHK(hipStreamSynchronize(s));
     for (int g = 0; g < n_seg; ++g) n_keep[g] = (int64_t)cnt[g];
     return MVS_OK;
 }
@@ -231,7 +224,7 @@ int stitch_compact_dev(const double* pts, const double* nrm, const int32_t* keep
                        int truncate, const double* scales, const double* R, const double* t, double* out_pts, double* out_nrm,
                        int64_t* out_off, hipStream_t s) {
     const int64_t P = seg_off[n_seg];
-    SBuf pos, tp, tn;
+    Scratch pos, tp, tn;
     int rc;
     if ((rc = pos.alloc(sizeof(int32_t) * (P + 1), s))) return rc;
     if ((rc = scan_exclusive_i32(keep, P, pos.as<int32_t>(), s))) return rc;
@@ -257,7 +250,7 @@ int stitch_compact_dev(const double* pts, const double* nrm, const int32_t* keep
 
 int mesh_vertex_normals_dev(const double* pts, int64_t V, const int32_t* faces, int64_t F, double* out, hipStream_t s) {
     if (V <= 0) return MVS_OK;
-    SBuf cnt, start, fill, list, fn, bad;
+    Scratch cnt, start, fill, list, fn, bad;
     int rc;
     const int64_t F1 = std::max<int64_t>(F, 1);
     if ((rc = cnt.alloc(sizeof(int32_t) * V, s)) || (rc = start.alloc(sizeof(int32_t) * (V + 1), s)) ||
@@ -279,6 +272,6 @@ int mesh_vertex_normals_dev(const double* pts, int64_t V, const int32_t* faces, 
     return MVS_OK;
 }
 
-// one kernel of this translation unit, for the code-object preload of api_deform.cpp (mvs_set_device): asking the runtime for its
+// one kernel of this translation unit, for the code-object preload of runtime.cpp (mvs_set_device): asking the runtime for its
 // attributes loads the unit's code object without launching anything
 const void* mvs_tu_probe_stitch() { return (const void*)k_vis_cull<uint8_t>; }

@@ -1,5 +1,5 @@
 """EXPERIMENT (needs `make -C multiviewstitch_amd/csrc clean && make EXPERIMENTS=1`): pass A of the point-streaming association VERDICT
-round 3 proposed (csrc/stream_exp.hip) on config 3, against the engine's own next association.
+round 3 proposed (tools/stream_exp.hip) on config 3, against the engine's own next association.
   1. six outer iterations (the search is bounded from the third association on);
   2. mvs_experiment_stream_dmin: bin the nodes into coarse tiles by their temporal bound, stream every tile's points against its
      nodes, packed-key atomicMin -> nearest distance and point per node; kernel times by HIP events;

@@ -229,7 +229,7 @@ def test_gpu_align_on_device_arrays_gives_the_bits_of_the_host_entry(al, sizes):
 
 @pytest.mark.gpu
 def test_scratch_pool_reuse_and_trim(al):
-    """The host-driven entries keep their device scratch for the next call (csrc/scratch.cpp; include/mvs.h: mvs_trim): the same
+    """The host-driven entries keep their device scratch for the next call (csrc/runtime.cpp; include/mvs.h: mvs_trim): the same
     call three times — fresh blocks, reused blocks, blocks allocated again after mvs_trim — gives the same bits, and a smaller
     request in between is served from (and does not corrupt) the kept blocks."""
     from multiviewstitch_amd import _lib

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from multiviewstitch_amd import scene as S
-from tests.util import rms
+from tests.util import check_batch, check_pass, check_state, counts_match, oracle_threads, rms, stop_ratios
 
 pytestmark = pytest.mark.gpu
 
@@ -95,6 +95,35 @@ def test_config4_prealign_chain_and_refine_match_oracle(oracle):
     assert st["n_valid"] == so["n_valid"] and st["arap_iters_run"] == so["arap_iters_run"] and st["converged"]
     assert rms(d.vertices(), o.vertices()) <= 1e-6
     assert rms(d.rotations().reshape(-1, 9), o.rotations().reshape(-1, 9)) <= 1e-6
+    # 5. on to 16 outer iterations: iterate(1), then ONE iterate(14) — a single batch past RAS_YOUNG_PASSES (schwarz.hip), with
+    #    calibrated plans, bounded associations and, at 512 patches, the MODE 4 sweeps of the solves
+    assert d.solver_info()["patches"] == 512
+    p = oracle.Params.default()
+    done = 1
+    oracle_threads(oracle)
+    try:
+        for n in (1, 14):
+            st, so = d.iterate(n), stop_ratios(o.iterate(p, n))
+            done += n
+            de = check_pass(st, so, f"iterate({n}) -> outer {done}", 1e-5)
+            check_batch(st, d.params.cg_tol, n)
+            dv, dr = check_state(d, o.vertices(), o.rotations(), f"iterate({n}) -> outer {done}")
+            print(f"[measured] config 4 outer {done}: rel energy diff {de:.2e}, vertex RMS {dv:.2e}, rotation RMS {dr:.2e}")
+        # 6. the 17th association, all K nodes, against the oracle's at the engine's node positions
+        v, nrm, nodes = d.vertices(), d.normals(), d.nodes()
+        assert d.iterate(1)["status"] == 0
+        got = d.node_targets(smoothed=False)
+        ref = oracle.Target(tp.cpu().numpy(), tn.cpu().numpy()).associate(v[nodes], nrm[nodes], p)
+        graph = oracle.knn_points(v[nodes], p.graph_k + 1)
+    finally:
+        oracle.set_threads(1)
+    assert np.array_equal(got["d2min"], ref["d2min"])
+    assert counts_match(got["counts"], ref["counts"])
+    assert np.array_equal(got["top_idx"], ref["top_idx"])
+    assert np.array_equal(got["valid"], ref["valid"])
+    assert np.abs(got["controls"] - ref["controls"]).max() <= 1e-12
+    assert np.array_equal(d.node_graph(), graph)
+    d.close()
 
 
 def test_config5_sixteen_part_graphs_match_oracle(oracle):
@@ -124,19 +153,41 @@ def test_config5_sixteen_part_graphs_match_oracle(oracle):
     #  RAS_YOUNG_PASSES; profiles/r04/soak_config5.log)
     tol = pd.live[0][1].params.cg_tol
     assert all(s_["unconverged_solves"] == 0 and s_["worst_rel_residual_in_batch"] <= tol for s_ in st2), st2
+    # then the group launches (mvs_deform_group_*: every part stepped twice on its own), two groups of eight parts: 3 and 10
+    # outer iterations, each call one batch per group
+    st3 = pd.iterate(3)
+    got3 = pd.vertices()
+    st4 = pd.iterate(10)
+    got4 = pd.vertices()
+    assert pd._group is not None and len(pd._group) == 2 and pd.group_passes == 13, pd.group_declined
+    calls = ((1, st, None), (1, st2, got), (3, st3, got3), (10, st4, got4))
+    for step, (_, s, _) in enumerate(calls):
+        assert all(s_["unconverged_solves"] == 0 and s_["worst_rel_residual_in_batch"] <= tol for s_ in s), (step, s)
     p = oracle.Params.default()
     k_or = 0
-    for k, part in enumerate(pd.parts):
-        vid = part["vid"]
-        o = oracle.Deform(sc.verts[vid], sc.normals[vid], part["faces"])
-        k_or += o.sample_nodes(16)
-        assert np.array_equal(o.nodes(), pd.handles[k].nodes()), f"part {k}"
-        sel = np.flatnonzero(tl == k)
-        o.set_target(tp[sel], tn[sel])
-        for step, s_ in enumerate((st, st2)):
-            so = o.iterate(p, 1)
-            assert so["n_valid"] == s_[k]["n_valid"] and so["arap_iters_run"] == s_[k]["arap_iters_run"], f"part {k} outer {step}"
-            assert s_[k]["converged"], f"part {k} outer {step}"
-        assert rms(got[vid], o.vertices()) <= 1e-6, f"part {k}"
+    worst = 0.0
+    oracle_threads(oracle)
+    try:
+        for k, part in enumerate(pd.parts):
+            vid = part["vid"]
+            o = oracle.Deform(sc.verts[vid], sc.normals[vid], part["faces"])
+            k_or += o.sample_nodes(16)
+            assert np.array_equal(o.nodes(), pd.handles[k].nodes()), f"part {k}"
+            sel = np.flatnonzero(tl == k)
+            o.set_target(tp[sel], tn[sel])
+            done = 0
+            for step, (n, s_, g) in enumerate(calls):
+                so = stop_ratios(o.iterate(p, n))
+                done += n
+                check_pass(s_[k], so, f"part {k} call {step} -> outer {done}")
+                if step < 2:
+                    assert s_[k]["converged"], f"part {k} outer {step}"
+                if g is not None:                              # after outer iterations 2, 5 and 15
+                    dv = rms(g[vid], o.vertices())
+                    assert dv <= 1e-6, (f"part {k} outer {done}", dv)
+                    worst = max(worst, dv)
+    finally:
+        oracle.set_threads(1)
+    print(f"[measured] config 5: group passes {pd.group_passes}, part vertex RMS up to {worst:.2e}")
     assert K == k_or
     pd.close()

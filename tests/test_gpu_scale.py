@@ -1,11 +1,14 @@
 """Full-size (BASELINE config 3: ~2 M points, ~8 K nodes) properties of the HIP path that need no CPU reference
 run of the same size: run-to-run determinism, the sharded phases on one GPU reproducing the fused path exactly,
-monotone ARAP energy, converged global solves — plus a sampled oracle check of the association."""
+monotone ARAP energy, converged global solves — plus a sampled oracle check of the association, and the oracle's own
+25-outer-iteration trajectory of the workload against the per-call, the batched (bench.py's calls) and the enqueue-only path."""
+import os
+
 import numpy as np
 import pytest
 
 from multiviewstitch_amd import scene as S
-from tests.util import counts_match
+from tests.util import check_batch, check_pass, check_state, counts_match, oracle_threads, stop_ratios
 
 pytestmark = pytest.mark.gpu
 
@@ -66,7 +69,8 @@ def test_full_size_iteration_properties(big, oracle):
     assert np.array_equal(got["top_idx"][pick], ref["top_idx"])
     assert np.array_equal(got["valid"][pick], ref["valid"])
     assert np.abs(got["controls"][pick] - ref["controls"]).max() <= 1e-12
-    # run-to-run determinism of the whole iteration (no atomics anywhere on the path)
+    # run-to-run determinism of the whole iteration (the only atomics on the path, in the grid build, add integer counts:
+    # order-free)
     d2, _, _ = make(big)
     d2.iterate(1)
     assert np.array_equal(d.vertices(), d2.vertices())
@@ -131,28 +135,117 @@ def test_engine_shard_orders_with_the_collectives_stream(big):
     assert d.stream() == own
 
 
-def test_config3_matches_oracle_at_vertex_level(big, oracle):
-    """The workload bench.py times (BASELINE config 3: 2.04 M points, 8 142 nodes, 54 762 vertices, 256 patches), compared
-    with the oracle's Deformation::Deform (R/Deformation/Deformation.cpp:232-402) outer iteration by outer iteration:
-    node set, valid-node count, ARAP iterations run (integers: equal), vertices and per-vertex rotations (<= 1e-6 RMS;
-    the north-star bound is 1e-4)."""
-    from tests.util import rms
+SNAPS = (1, 2, 3, 5, 13, 25)          # outer iterations after which the oracle trajectory keeps vertices, rotations, targets
+LATE_CTRL = 0.0                       # smoothed node targets from outer iteration 4 on (see test_config3_matches_oracle_at_vertex_level)
+
+
+@pytest.fixture(scope="module")
+def traj(big, oracle):
+    """The oracle's Deformation::Deform on the workload bench.py times, 25 outer iterations from the template pose on the
+    node set of make(big), each its own call: per iteration the integers, the energies and the stop-rule ratios
+    |E(t-1)-E(t)|/E(t) of the ARAP iterations (R/Deformation/Deformation.cpp: the inner loop stops below arap_tol); the
+    vertices, rotations and smoothed node targets after the outer iterations of SNAPS."""
     d, tp, tn = make(big)
+    d.close()
     sc = big["sc"]
-    assert d.solver_info()["kind"] == "patch" and d.solver_info()["patches"] == 256
+    tp, tn = tp.cpu().numpy(), tn.cpu().numpy()
     o = oracle.Deform(sc.verts, sc.normals, sc.faces)
-    assert o.sample_nodes(16) == d.K and np.array_equal(o.nodes(), d.nodes())
-    o.set_target(tp.cpu().numpy(), tn.cpu().numpy())
+    K = o.sample_nodes(16)
+    o.set_target(tp, tn)
     p = oracle.Params.default()
-    for it in range(3):
-        st, so = d.iterate(1), o.iterate(p, 1)
-        assert st["n_valid"] == so["n_valid"] and st["arap_iters_run"] == so["arap_iters_run"], f"outer {it}"
+    steps, snaps = [], {}
+    oracle_threads(oracle)
+    try:
+        for it in range(1, SNAPS[-1] + 1):
+            steps.append(stop_ratios(o.iterate(p, 1)))
+            if it in SNAPS:
+                snaps[it] = dict(v=o.vertices(), R=o.rotations().reshape(-1, 9), ctrl=o.node_targets(smoothed=True)[0])
+    finally:
+        oracle.set_threads(1)
+    return dict(K=K, onodes=o.nodes(), steps=steps, snaps=snaps, tp=tp, tn=tn, p=p)
+
+
+def test_config3_matches_oracle_at_vertex_level(big, oracle, traj):
+    """The workload bench.py times (BASELINE config 3: 2.04 M points, 8 142 nodes, 54 762 vertices, 256 patches), compared
+    with the oracle's Deformation::Deform (R/Deformation/Deformation.cpp:232-402) outer iteration by outer iteration, 25 of
+    them, one iterate(1) call each: node set, valid-node count, ARAP iterations run (integers: equal at every iteration),
+    energies (rtol 1e-6 for the first three iterations, 1e-5 after: 2.4e-6 has been met), vertices and per-vertex rotations
+    (<= 1e-6 RMS after the iterations of SNAPS; the north-star bound is 1e-4), smoothed node targets (<= 1e-10 for the
+    first three iterations, LATE_CTRL after).  LATE_CTRL is 10x the largest difference measured on the MI355X at outer
+    iterations 5, 13 and 25, which was 0: every node is a Dirichlet vertex of the global step (arap.hip, is_ctrl) and takes
+    its smoothed target exactly, so from the template pose on the association and the smoothing see the oracle's node
+    positions bit for bit — only the free vertices carry the solve's error."""
+    d, _, _ = make(big)
+    assert d.solver_info()["kind"] == "patch" and d.solver_info()["patches"] == 256
+    assert traj["K"] == d.K and np.array_equal(traj["onodes"], d.nodes())
+    worst = dict(e=0.0, v=0.0, R=0.0, ctrl0=0.0, ctrl=0.0)
+    for it in range(SNAPS[-1]):
+        st = d.iterate(1)
+        worst["e"] = max(worst["e"], check_pass(st, traj["steps"][it], f"outer {it}", 1e-6 if it < 3 else 1e-5))
         assert st["converged"] and st["worst_rel_residual_in_batch"] <= 1.5 * d.params.cg_tol
-        assert np.allclose(st["energy"][:5], so["energy"][:5], rtol=1e-6, atol=1e-12)
-        gs, os_ = d.node_targets(smoothed=True)["controls"], o.node_targets(smoothed=True)[0]
-        assert np.abs(gs - os_).max() <= 1e-10, f"outer {it}"
-        assert rms(d.vertices(), o.vertices()) <= 1e-6, f"outer {it}"
-        assert rms(d.rotations().reshape(-1, 9), o.rotations().reshape(-1, 9)) <= 1e-6, f"outer {it}"
+        snap = traj["snaps"].get(it + 1)
+        if snap is None:
+            continue
+        dc = float(np.abs(d.node_targets(smoothed=True)["controls"] - snap["ctrl"]).max())
+        assert dc <= (1e-10 if it < 3 else LATE_CTRL), f"outer {it}: {dc}"
+        dv, dr = check_state(d, snap["v"], snap["R"], f"outer {it}")
+        worst.update(v=max(worst["v"], dv), R=max(worst["R"], dr))
+        key = "ctrl" if it >= 3 else "ctrl0"
+        worst[key] = max(worst[key], dc)
+    print(f"[measured] config 3 per call: max rel energy diff {worst['e']:.2e}, vertex RMS {worst['v']:.2e}, "
+          f"rotation RMS {worst['R']:.2e}, smoothed targets {worst['ctrl0']:.2e} (outer 1-3), {worst['ctrl']:.2e} (from outer 4 on)")
+    d.close()
+
+
+def test_config3_bench_batches_match_oracle(big, oracle, traj):
+    """bench.py's calls (--warmup 5 --steps 20: iterate(1), iterate(4), iterate(20)) on a fresh handle: the 20 timed passes are
+    ONE batch (MAX_BATCH 32, api_deform.cpp), in which the host follows the device through the residual ring, lengthens short
+    plans, lowers plans and runs the fused tail sweeps; from pass 13 on the first solve of a pass predicts its stop with the
+    full margin (RAS_YOUNG_PASSES); from the third association on the search is bounded by the previous pass.  After each call
+    the last pass against the oracle trajectory; then the 26th association, all K nodes, against the oracle's at the
+    engine's node positions (the bars of test_bounded_association_and_graph_match_oracle)."""
+    d, _, _ = make(big)
+    tol = d.params.cg_tol
+    done = 0
+    for n in (1, 4, 20):
+        st = d.iterate(n)
+        done += n
+        de = check_pass(st, traj["steps"][done - 1], f"iterate({n}) -> outer {done}", 1e-6 if done <= 3 else 1e-5)
+        check_batch(st, tol, n)
+        dv, dr = check_state(d, traj["snaps"][done]["v"], traj["snaps"][done]["R"], f"iterate({n}) -> outer {done}")
+        print(f"[measured] config 3 bench calls, outer {done}: rel energy diff {de:.2e}, vertex RMS {dv:.2e}, rotation RMS {dr:.2e}")
+    v, nrm, nodes = d.vertices(), d.normals(), d.nodes()
+    assert d.iterate(1)["status"] == 0
+    got = d.node_targets(smoothed=False)
+    p = traj["p"]
+    oracle_threads(oracle)
+    try:
+        ref = oracle.Target(traj["tp"], traj["tn"]).associate(v[nodes], nrm[nodes], p)
+        graph = oracle.knn_points(v[nodes], p.graph_k + 1)
+    finally:
+        oracle.set_threads(1)
+    assert np.array_equal(got["d2min"], ref["d2min"])
+    assert counts_match(got["counts"], ref["counts"])
+    assert np.array_equal(got["top_idx"], ref["top_idx"])
+    assert np.array_equal(got["valid"], ref["valid"])
+    assert np.abs(got["controls"] - ref["controls"]).max() <= 1e-12
+    assert np.array_equal(d.node_graph(), graph)
+    d.close()
+
+
+def test_config3_enqueue_only_passes_match_oracle(big, traj):
+    """The path partwise takes when the group launches decline: iterate(1), iterate(1), then 23 passes enqueued without a
+    host synchronisation (no throttle; a solve that misses cg_tol raises the device-side escalation) and collected once."""
+    d, _, _ = make(big)
+    d.iterate(1)
+    d.iterate(1)
+    d.enqueue(23)
+    st = d.collect()
+    de = check_pass(st, traj["steps"][24], "enqueue(23) -> outer 25", 1e-5)
+    check_batch(st, d.params.cg_tol)
+    dv, dr = check_state(d, traj["snaps"][25]["v"], traj["snaps"][25]["R"], "enqueue(23) -> outer 25")
+    print(f"[measured] config 3 enqueue only, outer 25: rel energy diff {de:.2e}, vertex RMS {dv:.2e}, rotation RMS {dr:.2e}")
+    d.close()
 
 
 def test_library_owned_rccl_communicator_drives_the_sharded_passes(big):

@@ -1,5 +1,7 @@
-"""Shared helpers of the test-suite: scenes -> target point sets through the ORACLE (checker side)."""
+"""Shared helpers of the test-suite: scenes -> target point sets through the ORACLE (checker side); checks of engine
+statistics and state against an oracle trajectory."""
 import functools
+import os
 
 import numpy as np
 
@@ -74,3 +76,42 @@ def counts_match(got, ref, max_result=10000):
     got, ref = np.asarray(got), np.asarray(ref)
     full = ref[:, 0] >= max_result
     return bool(np.array_equal(got[~full], ref[~full]) and (got[full, 0] >= max_result).all())
+
+
+def oracle_threads(oracle):
+    """the oracle's OpenMP threads for a long run (results are bit-identical on any count); pair with set_threads(1)"""
+    oracle.set_threads(min(16, len(os.sched_getaffinity(0))))
+
+
+def check_pass(st, so, tag, rtol=None):
+    """the engine's last pass of a call (``st``) == the oracle's pass (``so`` of Deform.iterate, plus ``ratio``, its stop-rule
+    ratios |E(t-1)-E(t)|/E(t)): integers equal, energies to ``rtol`` (None: not compared).  On a mismatch the message shows the ratios (against
+    arap_tol) and GPU - oracle energies: a stop decided on a knife-edge reads differently from a wrong result.
+    -> the largest relative energy difference."""
+    why = (f"{tag}: GPU n_valid {st['n_valid']} arap_iters_run {st['arap_iters_run']}, oracle {so['n_valid']} "
+           f"{so['arap_iters_run']}; oracle stop-rule ratios {so['ratio'].tolist()}; GPU - oracle energy "
+           f"{(st['energy'][:5] - so['energy'][:5]).tolist()} (oracle {so['energy'][:5].tolist()})")
+    assert st["n_valid"] == so["n_valid"] and st["arap_iters_run"] == so["arap_iters_run"], why
+    if rtol is not None:
+        assert np.allclose(st["energy"][:5], so["energy"][:5], rtol=rtol, atol=1e-12), why
+    return float((np.abs(st["energy"][:5] - so["energy"][:5]) / np.maximum(np.abs(so["energy"][:5]), 1e-300)).max())
+
+
+def stop_ratios(so):
+    """``so`` (oracle Deform.iterate) with its stop-rule ratios |E(t-1)-E(t)|/E(t) added as ``ratio``"""
+    e = so["energy"][:so["arap_iters_run"]]
+    so["ratio"] = np.abs(np.diff(e)) / e[1:]
+    return so
+
+
+def check_batch(st, tol, n=None):
+    """health of a batch: every solve judged on the device, none above cg_tol, ``n`` outer iterations done"""
+    assert st["status"] == 0 and st["unconverged_solves"] == 0 and st["worst_rel_residual_in_batch"] <= tol, st
+    assert n is None or st["outer_done"] == n, st
+
+
+def check_state(d, v_ref, rot_ref, tag):
+    """vertices and per-vertex rotations of handle ``d`` within 1e-6 RMS of the oracle's -> (vertex RMS, rotation RMS)"""
+    dv, dr = rms(d.vertices(), v_ref), rms(d.rotations().reshape(-1, 9), np.reshape(rot_ref, (-1, 9)))
+    assert dv <= 1e-6 and dr <= 1e-6, (tag, dv, dr)
+    return dv, dr

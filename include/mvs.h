@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define MVS_ABI_VERSION 4   /* 3: tracing hook, mvs_comm_set_exchange, view-sharded RemoveGround / LocalAlignmentCore; 4: mvs_deform_group_*, mvs_align_dev, mvs_retain_connect_region_dev / mvs_remove_ground_dev / mvs_part_recog_dev, mvs_trim (additive); mvs_local_alignment_core_sharded takes the rank; still 4, additive: mvs_visibility_cull(_dev), mvs_mesh_vertex_normals(_dev), mvs_processor_stitch_points / _cull_model (mvs_io.h) */
+#define MVS_ABI_VERSION 4   /* 3: tracing hook, mvs_comm_set_exchange, view-sharded RemoveGround / LocalAlignmentCore; 4: mvs_deform_group_*, mvs_align_dev, mvs_retain_connect_region_dev / mvs_remove_ground_dev / mvs_part_recog_dev, mvs_trim (additive); mvs_local_alignment_core_sharded takes the rank; still 4, additive: mvs_visibility_cull(_dev), mvs_mesh_vertex_normals(_dev), mvs_processor_stitch_points / _cull_model (mvs_io.h), mvs_render_depth_views(_dev), mvs_processor_render (mvs_io.h) */
 
 enum mvs_status {
     MVS_OK            =  0,
@@ -150,6 +150,26 @@ int mvs_render_depth(const double* points, int64_t V, const int32_t* faces, int6
 /* mesh and raster in HBM; hip_stream may be NULL */
 int mvs_render_depth_dev(const double* points_dev, int64_t V, const int32_t* faces_dev, int64_t F, const mvs_camera* cam,
                          float znear, float zfar, float* out_dev, void* hip_stream);
+
+/* Model2Depth::SetInput + Run (R/Model2Depth/Model2Depth.h SetInput, Model2Depth.cpp:58-190) as Processor::Render calls it
+ * (R/Processor/Processor.cpp:1183-1191): every camera of every sequence, sequence by sequence and camera by camera, in one call.
+ * Sequence k renders the mesh mapped into its frame, p' = 1/s_k R_k^T (p - t_k) in fp64 exactly as mvs_srt_apply(inverse = 1),
+ * then narrowed to float32 as SetInput does; scales = R = t = NULL renders the points as given (the world frame).  cam_off
+ * (n_seq + 1, ascending from 0) and cams as mvs_visibility_cull; at least one camera, and cams[0] belongs to sequence 0.
+ * One viewport for all views: the window, glViewport and glReadPixels are cams[0]'s w0 x h0 (SetInput, Reshape), while each
+ * camera keeps its own frustum (w, h, cx, cy, fx, fy; Camera.cpp:15-38), so a camera of another size is rendered with its own
+ * frustum into a w0 x h0 raster.  Every other rule is mvs_render_depth's, and a view whose camera has the size w0 x h0 equals
+ * mvs_render_depth of the mapped points bit for bit.  out: cam_off[n_seq] rasters of w0 x h0 floats in camera order.
+ * The host form rejects a facet index outside [0, V) with MVS_E_BAD_MESH; the device form draws nothing for such a facet.
+ * MVS_RENDER_CHUNK_VIEWS (environment, read at every call) bounds the views rendered per chunk (0 or unset: sized from a
+ * 256 MiB budget); the results do not depend on it. */
+int mvs_render_depth_views(const double* points, int64_t V, const int32_t* faces, int64_t F, int32_t n_seq,
+                           const double* scales, const double* R, const double* t, const int32_t* cam_off,
+                           const mvs_camera* cams, float znear, float zfar, float* out /*N*h0*w0*/);
+/* mesh and rasters in HBM (the tables stay host arrays); hip_stream may be NULL; returns with the work complete */
+int mvs_render_depth_views_dev(const double* points_dev, int64_t V, const int32_t* faces_dev, int64_t F, int32_t n_seq,
+                               const double* scales, const double* R, const double* t, const int32_t* cam_off,
+                               const mvs_camera* cams, float znear, float zfar, float* out_dev, void* hip_stream);
 
 /* Processor::CheckConsistencyCore (R/Processor/Processor.cpp:72-126): depth-consistency filter of one frame against
  * n_ref (<= 4) reference frames, applied in the given order.  A pixel keeps its inverse depth iff it is inside

@@ -82,6 +82,19 @@ int mvs_processor_cull_model(const char* model_obj, int32_t n_seq, const double*
                              const int32_t* cam_off, const mvs_camera* cams, int32_t all_seq_proj, const char* out_obj,
                              int64_t* V_out, int64_t* F_out);
 
+/* Processor::Render (R/Processor/Processor.cpp:1140-1192), the second half of `main -a 0`: read srt_txt for n_seq sequences through
+ * float32 (mvs_srt_txt_read, :1145-1165) and ReadObj(deform_obj) (:1170; normals from the `vn` lines, or computed as
+ * mvs_mesh_vertex_normals when the file has none); for each sequence k map the mesh into k's frame, p' = 1/s_k R_k^T (p - t_k),
+ * n' = R_k^T n (:1176-1185, mvs_srt_apply with inverse = 1) and write result_dir/render%d.obj (WriteObj, :1186-1188); then
+ * Model2Depth::SetInput + Run (mvs_render_depth_views): each camera i of sequence k writes seq_dirs[k]/DATA/Render/_depth<i>.raw
+ * (SaveDepth of RenderDepth's raster, Model2Depth.cpp:119-153; w0 x h0 floats of cams[0]'s size), creating the directories as
+ * CreateDir does (a '/' is inserted after seq_dirs[k] when it lacks one).  A sequence without cameras renders nothing; its
+ * render%d.obj is still written.  The reference uses znear = 0.01f, zfar = 2000.0f.  Not written: the _depth%d.jpg previews
+ * (RenderDepthMap, an image encode).  cam_off / cams as mvs_render_depth_views.  A missing or bad input file is reported before
+ * any file is written.  n_views_out (may be NULL) receives cam_off[n_seq]. */
+int mvs_processor_render(const char* deform_obj, const char* srt_txt, int32_t n_seq, const int32_t* cam_off, const mvs_camera* cams,
+                         const char* result_dir, const char* const* seq_dirs, float znear, float zfar, int64_t* n_views_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -88,6 +88,8 @@ _SIGS = {
     "mvs_match_filter": (C.c_int, [_VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mvs_render_depth": (C.c_int, [_VP, _I64, _VP, _I64, _VP, C.c_float, C.c_float, _VP]),
     "mvs_render_depth_dev": (C.c_int, [_VP, _I64, _VP, _I64, _VP, C.c_float, C.c_float, _VP, _VP]),
+    "mvs_render_depth_views": (C.c_int, [_VP, _I64, _VP, _I64, _I32, _VP, _VP, _VP, _VP, _VP, C.c_float, C.c_float, _VP]),
+    "mvs_render_depth_views_dev": (C.c_int, [_VP, _I64, _VP, _I64, _I32, _VP, _VP, _VP, _VP, _VP, C.c_float, C.c_float, _VP, _VP]),
     "mvs_check_consistency": (C.c_int, [_VP, _VP, _I32, _VP, _VP, _D, _D, _I32, _VP]),
     "mvs_check_consistency_seq": (C.c_int, [_I32, _VP, _VP, _D, _D, _I32, _VP]),
     "mvs_check_consistency_seq_dev": (C.c_int, [_I32, _VP, _VP, _D, _D, _I32, _VP, _VP]),
@@ -174,6 +176,7 @@ _SIGS = {
     "mvs_processor_deform": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, _VP, _D, _VP, C.c_char_p, _VP]),
     "mvs_processor_stitch_points": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP, _U32, C.c_char_p, _VP]),
     "mvs_processor_cull_model": (C.c_int, [C.c_char_p, _I32, _VP, _VP, _VP, _VP, _VP, _I32, C.c_char_p, _VP, _VP]),
+    "mvs_processor_render": (C.c_int, [C.c_char_p, C.c_char_p, _I32, _VP, _VP, C.c_char_p, _VP, C.c_float, C.c_float, _VP]),
     # include/mvs_test.h (test hooks: per handle, not part of the drop-in ABI)
     "mvs_test_preload_wait": (C.c_int, []),
     "mvs_test_ctl": (C.c_int, [_VP, _VP, _I32]),

@@ -1,12 +1,17 @@
 // api_stitch.cpp — C-ABI of the tail of Processor::AlignmentSeq (R/Processor/Processor.cpp:952-1105): mvs_visibility_cull(_dev),
 // mvs_mesh_vertex_normals(_dev) (include/mvs.h) and the two file-level steps mvs_processor_stitch_points / _cull_model
-// (include/mvs_io.h).  The point work is stitch.hip / align.hip; the host reads and writes the files and builds the small tables.
+// (include/mvs_io.h); and of Processor::Render (:1140-1192): mvs_render_depth_views(_dev) (include/mvs.h) and the file-level
+// mvs_processor_render (include/mvs_io.h).  The point work is stitch.hip / align.hip / render_views.hip; the host reads and writes
+// the files and builds the small tables.
 #include "engine.h"
 #include "trace.h"
 #include "stitch.h"
+#include "geom.h"
 #include "../../include/mvs_io.h"
+#include <cerrno>
 #include <cstdio>
 #include <cstring>
+#include <sys/stat.h>
 #include <string>
 #include <vector>
 
@@ -48,6 +53,43 @@ std::string join(const char* dir, const char* name) {
     std::string s(dir);
     if (!s.empty() && s.back() != '/') s += '/';
     return s + name;
+}
+
+// the views of Processor::Render: n_seq >= 1, cam_off ascending from 0, at least one camera and cams[0] in sequence 0 (its size is
+// the shared viewport), cameras of positive size with cx, cy != 0 (the frustum divides by them), the SRT all given or all NULL,
+// 0 < znear < zfar
+int check_views(const char* fn, int32_t n_seq, const double* scales, const double* R, const double* t, const int32_t* cam_off,
+                const mvs_camera* cams, float znear, float zfar) {
+    if (n_seq < 1) return bad(fn, "n_seq must be >= 1");
+    if (!cam_off) return bad(fn, "cam_off is NULL");
+    if (cam_off[0] != 0) return bad(fn, "cam_off must start at 0");
+    for (int k = 0; k < n_seq; ++k)
+        if (cam_off[k + 1] < cam_off[k]) return bad(fn, "cam_off must ascend");
+    if (cam_off[n_seq] < 1) return bad(fn, "no cameras");
+    if (cam_off[1] < 1) return bad(fn, "cams[0] must belong to sequence 0 (its size is the viewport of every view)");
+    if (!cams) return bad(fn, "cams is NULL");
+    for (int c = 0; c < cam_off[n_seq]; ++c)
+        if (cams[c].w <= 0 || cams[c].h <= 0 || cams[c].cx == 0.0 || cams[c].cy == 0.0) return bad(fn, "every camera needs w, h > 0 and cx, cy != 0");
+    if (!((scales && R && t) || (!scales && !R && !t))) return bad(fn, "scales, R and t must all be given or all be NULL");
+    if (!(znear > 0) || !(zfar > znear)) return bad(fn, "need 0 < znear < zfar");
+    return MVS_OK;
+}
+
+int check_render_mesh(const char* fn, const void* pts, int64_t V, const void* faces, int64_t F, const void* out) {
+    if (!pts || V <= 0 || V >= 0x7fffffffLL) return bad(fn, "need points and 0 < V < 2^31 - 1");
+    if (F < 0 || F >= 0x7fffffffLL / 3 || (F > 0 && !faces)) return bad(fn, "need faces and 0 <= F < (2^31 - 1) / 3");
+    if (!out) return bad(fn, "out is NULL");
+    return MVS_OK;
+}
+
+// CreateDir (R/Common/Utils.h:84-100): every prefix of the path that ends at a '/'
+int make_dirs(const std::string& dir) {
+    for (size_t i = 1; i < dir.size(); ++i)
+        if (dir[i] == '/') {
+            const std::string d = dir.substr(0, i);
+            if (mkdir(d.c_str(), 0777) != 0 && errno != EEXIST) { mvs_set_error("%s: cannot create the directory (%s)", d.c_str(), std::strerror(errno)); return MVS_E_IO; }
+        }
+    return MVS_OK;
 }
 
 }  // namespace
@@ -190,6 +232,94 @@ int mvs_processor_cull_model(const char* model_obj, int32_t n_seq, const double*
     if ((rc = mvs_obj_write(out_obj, V, hp.data(), hn.data(), F, hf.data()))) return rc;                       // :1104
     if (V_out) *V_out = V;
     if (F_out) *F_out = F;
+    return MVS_OK;
+}
+
+int mvs_render_depth_views_dev(const double* points_dev, int64_t V, const int32_t* faces_dev, int64_t F, int32_t n_seq, const double* scales,
+                               const double* R, const double* t, const int32_t* cam_off, const mvs_camera* cams, float znear, float zfar,
+                               float* out_dev, void* hip_stream) {
+    MVS_TRACE();
+    int rc = check_views(__func__, n_seq, scales, R, t, cam_off, cams, znear, zfar);
+    if (rc || (rc = check_render_mesh(__func__, points_dev, V, faces_dev, F, out_dev))) return rc;
+    if ((rc = need_device())) return rc;
+    return render_views_dev(points_dev, V, faces_dev, F, n_seq, scales, R, t, cam_off, cams, znear, zfar, out_dev, (hipStream_t)hip_stream);
+}
+
+int mvs_render_depth_views(const double* points, int64_t V, const int32_t* faces, int64_t F, int32_t n_seq, const double* scales,
+                           const double* R, const double* t, const int32_t* cam_off, const mvs_camera* cams, float znear, float zfar,
+                           float* out) {
+    MVS_TRACE();
+    int rc = check_views(__func__, n_seq, scales, R, t, cam_off, cams, znear, zfar);
+    if (rc || (rc = check_render_mesh(__func__, points, V, faces, F, out))) return rc;
+    for (int64_t k = 0; k < 3 * F; ++k)
+        if (faces[k] < 0 || faces[k] >= V) { mvs_set_error("%s: facet index out of range", __func__); return MVS_E_BAD_MESH; }
+    if ((rc = need_device())) return rc;
+    const size_t n_out = (size_t)cam_off[n_seq] * (size_t)cams[0].w * (size_t)cams[0].h;
+    Scratch dp, df, dout;
+    if ((rc = up(dp, points, 3 * (size_t)V)) || (rc = up(df, faces, 3 * (size_t)F)) || (rc = dout.alloc(sizeof(float) * n_out))) return rc;
+    if ((rc = render_views_dev(dp.as<double>(), V, df.as<int32_t>(), F, n_seq, scales, R, t, cam_off, cams, znear, zfar, dout.as<float>(),
+                               nullptr))) return rc;
+    return down(out, dout, n_out);
+}
+
+int mvs_processor_render(const char* deform_obj, const char* srt_txt, int32_t n_seq, const int32_t* cam_off, const mvs_camera* cams,
+                         const char* result_dir, const char* const* seq_dirs, float znear, float zfar, int64_t* n_views_out) {
+    MVS_TRACE();
+    int rc = check_views(__func__, n_seq, nullptr, nullptr, nullptr, cam_off, cams, znear, zfar);
+    if (rc) return rc;
+    if (!deform_obj || !srt_txt || !result_dir || !seq_dirs) return bad(__func__, "deform_obj, srt_txt, result_dir and seq_dirs must not be NULL");
+    for (int k = 0; k < n_seq; ++k)
+        if (!seq_dirs[k]) return bad(__func__, "a path of seq_dirs is NULL");
+    if ((rc = need_device())) return rc;
+    std::vector<double> sc(n_seq), R((size_t)n_seq * 9), t((size_t)n_seq * 3);
+    if ((rc = mvs_srt_txt_read(srt_txt, n_seq, sc.data(), R.data(), t.data()))) return rc;          // :1145-1165, through float32
+    int64_t V = 0, N = 0, F = 0;                                                                   // ReadObj, :1170
+    if ((rc = mvs_obj_read(deform_obj, &V, &N, &F, nullptr, nullptr, nullptr))) return rc;
+    if (N != 0 && N != V) {
+        mvs_set_error("%s: %lld normals for %lld vertices (the reference indexes one per vertex)", deform_obj, (long long)N, (long long)V);
+        return MVS_E_BAD_MESH;
+    }
+    if (V <= 0 || V >= 0x7fffffffLL || F >= 0x7fffffffLL / 3) { mvs_set_error("%s: no vertices, or mesh too large", deform_obj); return MVS_E_BAD_MESH; }
+    std::vector<double> hp((size_t)V * 3), hn((size_t)V * 3);
+    std::vector<int32_t> hf((size_t)F * 3);
+    if ((rc = mvs_obj_read(deform_obj, &V, &N, &F, hp.data(), hn.data(), hf.data()))) return rc;
+    for (int64_t i = 0; i < F * 3; ++i)
+        if (hf[i] < 0 || hf[i] >= V) { mvs_set_error("%s: facet index %d outside [1, %lld]", deform_obj, hf[i] + 1, (long long)V); return MVS_E_BAD_MESH; }
+    const int n_views = cam_off[n_seq];
+    const size_t npx = (size_t)cams[0].w * (size_t)cams[0].h;
+    Scratch dp, dn, df, mp, mn, dout;
+    if ((rc = up(dp, hp.data(), (size_t)V * 3)) || (rc = up(dn, hn.data(), N ? (size_t)V * 3 : 0, (size_t)V * 3)) ||
+        (rc = up(df, hf.data(), (size_t)F * 3)) || (rc = mp.alloc((size_t)V * 24)) || (rc = mn.alloc((size_t)V * 24)) ||
+        (rc = dout.alloc(sizeof(float) * npx * n_views))) return rc;
+    // no `vn` lines: CalculateVertexNormals, PlyObj.cpp:11-14
+    if (N == 0 && (rc = mesh_vertex_normals_dev(dp.as<double>(), V, df.as<int32_t>(), F, dn.as<double>(), nullptr))) return rc;
+    std::vector<double> op((size_t)V * 3), on((size_t)V * 3);
+    for (int k = 0; k < n_seq; ++k) {                                                              // :1176-1189
+        launch_srt_apply(dp.as<double>(), dn.as<double>(), V, sc[k], R.data() + 9 * k, t.data() + 3 * k, 1, mp.as<double>(), mn.as<double>(), nullptr);
+        HIPCHK(hipGetLastError());
+        if ((rc = down(op.data(), mp, (size_t)V * 3)) || (rc = down(on.data(), mn, (size_t)V * 3))) return rc;
+        char name[32];
+        std::snprintf(name, sizeof name, "render%d.obj", k);
+        if ((rc = mvs_obj_write(join(result_dir, name).c_str(), V, op.data(), on.data(), F, hf.data()))) return rc;
+    }
+    // Model2Depth::SetInput + Run (Model2Depth.h, Model2Depth.cpp:58-190): every camera of every sequence, in order
+    if ((rc = render_views_dev(dp.as<double>(), V, df.as<int32_t>(), F, n_seq, sc.data(), R.data(), t.data(), cam_off, cams, znear, zfar,
+                               dout.as<float>(), nullptr))) return rc;
+    std::vector<float> hr(npx * n_views);
+    if ((rc = down(hr.data(), dout, hr.size()))) return rc;
+    std::vector<double> raw(npx);
+    for (int k = 0; k < n_seq; ++k) {
+        if (cam_off[k + 1] == cam_off[k]) continue;                                               // a sequence without cameras renders nothing
+        const std::string dir = join(seq_dirs[k], "DATA/Render/");                                // RenderDepth, :145
+        if ((rc = make_dirs(dir))) return rc;
+        for (int c = cam_off[k]; c < cam_off[k + 1]; ++c) {
+            for (size_t i = 0; i < npx; ++i) raw[i] = hr[(size_t)c * npx + i];
+            char name[32];
+            std::snprintf(name, sizeof name, "_depth%d.raw", c - cam_off[k]);
+            if ((rc = mvs_depth_raw_write((dir + name).c_str(), (int64_t)npx, raw.data()))) return rc;   // SaveDepth, :151-153
+        }
+    }
+    if (n_views_out) *n_views_out = n_views;
     return MVS_OK;
 }
 

@@ -50,7 +50,7 @@ const void* const* mvs_tu_kernels_grid(int*); const void* const* mvs_tu_kernels_
 const void* const* mvs_tu_kernels_arap(int*); const void* const* mvs_tu_kernels_schwarz(int*); const void* const* mvs_tu_kernels_meshbuild(int*);
 const void* const* mvs_tu_kernels_geom(int*);
 const void* mvs_tu_probe_srt(); const void* mvs_tu_probe_align(); const void* mvs_tu_probe_consist(); const void* mvs_tu_probe_render(); const void* mvs_tu_probe_matchfilter();
-const void* mvs_tu_probe_stitch();
+const void* mvs_tu_probe_stitch(); const void* mvs_tu_probe_render_views();
 // (never destroyed: the helper thread is detached and may outlive the static destructors of an exiting process)
 static std::mutex& g_preload_mu = *new std::mutex;
 static std::condition_variable& g_preload_cv = *new std::condition_variable;
@@ -75,7 +75,7 @@ void mvs_preload(int device) {
                 for (int i = 0; i < n; ++i) { hipFuncAttributes a; if (hipFuncGetAttributes(&a, ks[i]) != hipSuccess) (void)hipGetLastError(); }
             }
             for (const void* k : {mvs_tu_probe_srt(), mvs_tu_probe_align(), mvs_tu_probe_consist(), mvs_tu_probe_render(), mvs_tu_probe_matchfilter(),
-                                  mvs_tu_probe_stitch()}) {
+                                  mvs_tu_probe_stitch(), mvs_tu_probe_render_views()}) {
                 hipFuncAttributes a;
                 if (hipFuncGetAttributes(&a, k) != hipSuccess) (void)hipGetLastError();
             }
@@ -317,6 +317,13 @@ int mvs_scratch_alloc(void** p, size_t bytes, hipStream_t user) {
     std::lock_guard<std::mutex> g(P.m);
     P.out[*p] = {need, dev};
     return MVS_OK;
+}
+
+// read at every call, so that a test can bound the chunks of one call (the results do not depend on them)
+int mvs_render_chunk_views() {
+    const char* e = std::getenv("MVS_RENDER_CHUNK_VIEWS");
+    const int n = (e && *e) ? std::atoi(e) : 0;
+    return n > 0 ? n : 0;
 }
 
 void mvs_scratch_free(void* p, hipStream_t user) {

@@ -18,4 +18,9 @@ int mesh_vertex_normals_dev(const double* pts, int64_t V, const int32_t* faces, 
 // Poisson model trim on device arrays (align.hip): compaction by keep (int32, V + 1, or NULL: none) with the facet remap, then
 // RetainConnectRegion.  V, F in/out.
 int cull_retain_dev(double* pts, double* nrm, int64_t* V, int32_t* faces, int64_t* F, const int32_t* keep);
+// Model2Depth::Run over every camera of every sequence (render_views.hip), arguments validated by the caller: mesh (device) in the
+// world frame, mapped into sequence k's frame by the inverse SRT of k (scales == NULL: not mapped); out (device) = cam_off[n_seq]
+// rasters of cams[0].w x cams[0].h floats in camera order.  Views are rendered in chunks of mvs_render_chunk_views().  Synchronises s.
+int render_views_dev(const double* pts, int64_t V, const int32_t* faces, int64_t F, int n_seq, const double* scales, const double* R,
+                     const double* t, const int32_t* cam_off, const mvs_camera* cams, float znear, float zfar, float* out, hipStream_t s);
 #endif

@@ -1,5 +1,6 @@
 """``Processor::Deform`` (R/Processor/Processor.cpp:1111-1138) on files, through ``mvs_processor_deform``; the tail of
-``Processor::AlignmentSeq`` (:952-1105) through ``mvs_processor_stitch_points`` / ``mvs_processor_cull_model``."""
+``Processor::AlignmentSeq`` (:952-1105) through ``mvs_processor_stitch_points`` / ``mvs_processor_cull_model``;
+``Processor::Render`` (:1140-1192) through ``mvs_processor_render`` and its batched render ``mvs_render_depth_views``."""
 from __future__ import annotations
 
 import ctypes as C
@@ -45,6 +46,55 @@ def CullPoissonModel(model_obj, scales, Rs, ts, cameras, out_obj, all_seq_proj: 
     L.check(L.lib().mvs_processor_cull_model(os.fsencode(model_obj), n, L.ptr(s), L.ptr(R), L.ptr(t), L.ptr(coff), cams,
                                              int(bool(all_seq_proj)), os.fsencode(out_obj), C.byref(V), C.byref(F)))
     return V.value, F.value
+
+
+def _view_tables(cameras, scales, Rs, ts):
+    """seq_tables for Render / RenderViews: the SRT may be absent (None for all three: the world frame, NULL pointers)."""
+    n = len(cameras)
+    if scales is None and Rs is None and ts is None:
+        _, _, _, _, coff, cams = L.seq_tables(np.ones(n), np.tile(np.eye(3), (n, 1, 1)), np.zeros((n, 3)), cameras)
+        return n, None, None, None, coff, cams
+    if scales is None or Rs is None or ts is None:
+        raise L.MvsError(-1, "scales, Rs and ts must all be given or all be None")
+    return L.seq_tables(scales, Rs, ts, cameras)
+
+
+def Render(deform_obj, srt_txt, cameras, result_dir, seq_dirs, znear: float = 0.01, zfar: float = 2000.0) -> int:
+    """The second half of `main -a 0` (R/Processor/Processor.cpp:1140-1192): SRT.txt and deform.obj read through float32, the mesh
+    mapped into every sequence's frame and written to ``result_dir``/render%d.obj, then every camera i of sequence k rendered to
+    ``seq_dirs[k]``DATA/Render/_depth<i>.raw (cameras[0][0]'s size for every raster).  ``cameras[k]`` lists sequence k's cameras.
+    -> views rendered."""
+    n, _, _, _, coff, cams = _view_tables(cameras, None, None, None)
+    if len(seq_dirs) != n:
+        raise L.MvsError(-1, f"{len(seq_dirs)} sequence dirs for {n} sequences")
+    dirs = (C.c_char_p * n)(*[os.fsencode(d) for d in seq_dirs])
+    nv = C.c_int64()
+    L.check(L.lib().mvs_processor_render(os.fsencode(deform_obj), os.fsencode(srt_txt), n, L.ptr(coff), cams, os.fsencode(result_dir), dirs,
+                                         float(znear), float(zfar), C.byref(nv)))
+    return nv.value
+
+
+def RenderViews(points, facets, cameras, scales=None, Rs=None, ts=None, znear: float = 0.01, zfar: float = 2000.0,
+                out_dev: int | None = None, stream: int | None = None):
+    """Model2Depth::SetInput + Run (R/Model2Depth/Model2Depth.cpp:58-190): every camera of every sequence in one call.  Sequence k
+    renders the points mapped by its inverse SRT (1/s_k R_k^T (p - t_k)); without an SRT the points as given.  ``cameras[k]`` lists
+    sequence k's cameras; cameras[0][0]'s size (w0, h0) is the viewport of every view.  -> float32 [N, h0, w0] of inverse depths in
+    camera order.  With ``out_dev`` (device address of N*h0*w0 floats) the mesh arguments are device addresses, (address, count)
+    tuples as for RenderDepth, and nothing is returned."""
+    n, s, R, t, coff, cams = _view_tables(cameras, scales, Rs, ts)
+    if out_dev is not None:
+        (pp, V), (fp, F) = points, facets
+        L.check(L.lib().mvs_render_depth_views_dev(L.ptr(int(pp)), int(V), L.ptr(int(fp)), int(F), n, L.ptr(s), L.ptr(R), L.ptr(t),
+                                                   L.ptr(coff), cams, float(znear), float(zfar), L.ptr(int(out_dev)), L.ptr(stream)))
+        return None
+    pts = L.arr(points, np.float64).reshape(-1, 3)
+    fac = L.arr(facets, np.int32).reshape(-1, 3)
+    N = int(coff[-1])
+    w0, h0 = (int(cameras[0][0].w), int(cameras[0][0].h)) if N and len(cameras[0]) else (0, 0)
+    out = np.empty((N, h0, w0), np.float32)
+    L.check(L.lib().mvs_render_depth_views(L.ptr(pts), len(pts), L.ptr(fac), len(fac), n, L.ptr(s), L.ptr(R), L.ptr(t), L.ptr(coff), cams,
+                                           float(znear), float(zfar), L.ptr(out)))
+    return out
 
 
 def CheckConsistencyCore(curcam, refcams, depth, refdepths, min_dsp: float, max_dsp: float, reproj_err: int) -> np.ndarray:

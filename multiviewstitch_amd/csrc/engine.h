@@ -95,7 +95,7 @@ struct RasDev {                // patches of the restricted additive Schwarz sol
                                                           (a workgroup's bounded wait at the device-wide barrier expired): such a solve counts as a miss */
 #define MVS_CTL_SIZE   (MVS_CTL_GAVEUP + 8)
 
-// One part of a GROUP of handles (api_deform.cpp, mvs_deform_group_*): everything a bounded pass of that part's handle reads,
+// One part of a GROUP of handles (deform_group.cpp, mvs_deform_group_*): everything a bounded pass of that part's handle reads,
 // as one record in device memory.  The kernels of a pass are launched ONCE for all parts of a group — grid (x, part): a
 // workgroup takes its part's record and runs the same body a handle's own launch runs (blockIdx.x / gridDim.x are the x
 // dimension, common to the parts; a part that needs fewer workgroups lets the surplus ones return).  Every part keeps its own
@@ -233,23 +233,25 @@ struct mvs_deform_s {
     uint64_t seq_peeked = 0;        // ... whose ring row the host has already looked at
     uint64_t seq_harvested = 0;     // ... covered by the last harvest
     uint64_t bump_seq[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // first pass enqueued with the last in-batch correction of solve `it`
-    // timing
-    int timing = 0;                 // 0 off, 1 all phases, 2 "cg" groups only
-    std::map<std::string, PhaseTimer> timers;
-    std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> pending;
-    std::vector<hipEvent_t> event_pool;
-    std::map<std::string, int64_t> pending_launches;
-    // timing mode 3: the idle flags of the sweep launches the sampled event pairs bracket (every sweep leaves "found the solve
-    // finished" in its slot, schwarz.hip) are copied out behind each sampled pass — which of the TIMED launches did work is
-    // then counted from the device's own record, not inferred from another pass
-    struct SweepSample { int first, n_a, n_b; };      // slots [first, first + n_a) = the launches of one "cg" bracket
-    std::vector<SweepSample> samples;                 // one per sampled solve, in the order of the brackets
-    std::vector<size_t> sample_off;                   // where each sampled pass's flags start in h_sample (doubles)
-    std::vector<int> sample_pass_first;               // index into `samples` of each sampled pass's first solve
-    double* h_sample = nullptr;                       // pinned: [8] scalars per sweep slot of the sampled passes
-    size_t sample_cap = 0, sample_used = 0;           // doubles
+    // timing (deform_timing.cpp)
+    struct Timing {
+        int mode = 0;               // 0 off, 1 all phases, 2 "cg" groups only
+        std::map<std::string, PhaseTimer> timers;
+        std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> pending;
+        std::vector<hipEvent_t> event_pool;
+        std::map<std::string, int64_t> pending_launches;
+        // timing mode 3: the idle flags of the sweep launches the sampled event pairs bracket (every sweep leaves "found the solve
+        // finished" in its slot, schwarz.hip) are copied out behind each sampled pass — which of the TIMED launches did work is
+        // then counted from the device's own record, not inferred from another pass
+        struct SweepSample { int first, n_a, n_b; };      // slots [first, first + n_a) = the launches of one "cg" bracket
+        std::vector<SweepSample> samples;                 // one per sampled solve, in the order of the brackets
+        std::vector<size_t> sample_off;                   // where each sampled pass's flags start in h_sample (doubles)
+        std::vector<int> sample_pass_first;               // index into `samples` of each sampled pass's first solve
+        double* h_sample = nullptr;                       // pinned: [8] scalars per sweep slot of the sampled passes
+        size_t sample_cap = 0, sample_used = 0;           // doubles
+    } timing;
     mvs_deform_stats last{};
-    // device memory: one allocation per lifetime (meshbuild.hip, api_deform.cpp, grid.hip); every d_* pointer above points
+    // device memory: one allocation per lifetime (meshbuild.hip, deform_handle.cpp, grid.hip); every d_* pointer above points
     // into one of these, nothing is freed piecewise
     void* arena_mesh = nullptr;     // sized from V, F alone: vectors, control blocks, the build's workspace
     void* arena_tab = nullptr;      // sized after the device build reported ne, LS, W: ELL-8 tables, patch tables, sweep slots
@@ -260,11 +262,13 @@ struct mvs_deform_s {
     size_t arena_probe_bytes = 0;
     bool saw_abandon = false;       // a tail loop of this handle was abandoned at its barrier: keep a local-step launch behind every solve
     double gaveup_seen[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    // test hooks (include/mvs_test.h, mvs_test_tail): per handle, never process-wide
-    int dbg_maxspin = 0;            // polls a workgroup waits at the tail loop's barrier before it abandons the solve (0: default)
-    int dbg_plan_cap = 0;           // at most this many launches per solve, the rest of its sweeps run inside the last one (0: no cap)
-    int dbg_skip_wg = -1;           // the workgroup that never arrives at the tail loop's barrier (-1: none)
-    int dbg_group_leave = 0;        // mvs_test_group_leave: the handle stops qualifying for group launches after this many harvests in a group (0: never)
+    // test hooks (include/mvs_test.h, deform_test.cpp): per handle, never process-wide
+    struct TestHooks {
+        int maxspin = 0;            // polls a workgroup waits at the tail loop's barrier before it abandons the solve (0: default)
+        int plan_cap = 0;           // at most this many launches per solve, the rest of its sweeps run inside the last one (0: no cap)
+        int skip_wg = -1;           // the workgroup that never arrives at the tail loop's barrier (-1: none)
+        int group_leave = 0;        // mvs_test_group_leave: the handle stops qualifying for group launches after this many harvests in a group (0: never)
+    } dbg;
     int group_batches = 0;          // harvests of this handle inside group calls
     ChebCoef* d_cheb = nullptr;     // [2] the planned and the strong coefficient set of the sweeps, as last uploaded (launch_ras_sweep)
     ChebCoef h_cheb[2];             // ... their host side (the source of the asynchronous upload)

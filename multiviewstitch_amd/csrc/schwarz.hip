@@ -923,7 +923,7 @@ void launch_ras_sweep(const mvs_deform_s* h, const double* b, double* xin, doubl
     const ChebCoef *cc = h->d_cheb, *cc2 = h->d_cheb + 1;
     const int cheb_m = h->cheb_m_dev, m2 = h->cheb_m2_dev;
     const dim3 grid(R.NP), blk(h->ras_block);     // as many waves as the largest patch has rows (idle waves only add barrier cost)
-    RasTail tail{h->d_bar, tail_slots, RAS_TAIL_MAX, h->dbg_maxspin > 0 ? h->dbg_maxspin : RAS_TAIL_MAXSPIN, h->dbg_skip_wg};
+    RasTail tail{h->d_bar, tail_slots, RAS_TAIL_MAX, h->dbg.maxspin > 0 ? h->dbg.maxspin : RAS_TAIL_MAXSPIN, h->dbg.skip_wg};
     const RasLocal loc{h->sell, h->d_pts, h->d_rot, h->d_bpure, ras_local_parts(h)};
     // mixing_solve: every planned sweep of this solve is the mixing instantiation (a solve is all lean or all mixing: the state in
     // the sweep slots is only kept by the latter, and cap = 0 tells every launch of a lean solve not to look at it)

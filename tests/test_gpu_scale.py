@@ -199,7 +199,7 @@ def test_config3_matches_oracle_at_vertex_level(big, oracle, traj):
 
 def test_config3_bench_batches_match_oracle(big, oracle, traj):
     """bench.py's calls (--warmup 5 --steps 20: iterate(1), iterate(4), iterate(20)) on a fresh handle: the 20 timed passes are
-    ONE batch (MAX_BATCH 32, api_deform.cpp), in which the host follows the device through the residual ring, lengthens short
+    ONE batch (MAX_BATCH 32, deform_host.h), in which the host follows the device through the residual ring, lengthens short
     plans, lowers plans and runs the fused tail sweeps; from pass 13 on the first solve of a pass predicts its stop with the
     full margin (RAS_YOUNG_PASSES); from the third association on the search is bounded by the previous pass.  After each call
     the last pass against the oracle trajectory; then the 26th association, all K nodes, against the oracle's at the

@@ -71,6 +71,11 @@ def _meshes(oracle):
     fan = np.concatenate([[[0.0, 0.0, 0.1]], np.stack([np.cos(ang), np.sin(ang), np.zeros(n)], 1)])
     ff = np.array([[0, 1 + k, 1 + (k + 1) % n] for k in range(n)], np.int32)
     yield "fan, hub of degree 200", fan, np.tile([0.0, 0.0, 1.0], (n + 1, 1)), ff
+    # hubs of valence 9 .. 17 (tests/mesh_valence.py): patch tables of width 12 and 16, closed and with boundary hubs; above 16 no patches
+    from tests import mesh_valence as MV
+    for case in ("d12", "d16", "d12_open", "d16_open", "d17"):
+        m = MV.case(case)
+        yield f"hubbed sphere {case}", m.pts, m.normals, m.faces
     # the smallest closed mesh
     tet = np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0], [0, 0, 1]], float)
     yield "tetrahedron", tet, tet / np.maximum(np.linalg.norm(tet, axis=1, keepdims=True), 1), np.array([[0, 2, 1], [0, 1, 3], [0, 3, 2], [1, 2, 3]], np.int32)
@@ -108,8 +113,8 @@ def test_device_built_tables_match_a_numpy_rebuild(oracle):
         assert vfp[0] == 0 and vfp[-1] == 3 * len(faces)
         for i in range(0, V, max(1, V // 4000)):
             assert list(vf[vfp[i]:vfp[i + 1]]) == sorted(vf_ref[i]), (name, i)
-        # ---- patches (meshes of 2048 vertices and more, degree <= 16)
-        if V < 2048:
+        # ---- patches: meshes of 2048 vertices and more whose largest degree is <= 16, and no others
+        if not (V >= 2048 and deg.max() <= 16):
             assert has == 0, name
             d.close()
             continue

@@ -264,3 +264,50 @@ def test_group_call_hands_over_when_a_part_stops_qualifying():
     assert out[False][1] == out[True][1]
     d = rms(out[False][0], out[True][0])
     assert d <= 1e-7, d
+
+
+@pytest.mark.gpu
+def test_parts_of_different_patch_width_fitted_as_one_group(oracle):
+    """Two parts cut from a hubbed template (tests/mesh_valence.py, halves_d12: every hub in the half y > 0): part 0 has valence
+    <= 6 — patch tables of width 6 — and part 1 valence 12: width 12.  mvs_deform_group_iterate launches every kernel once for all
+    parts with ONE width (deform_group.cpp: GroupDims.W = the first part's), so once every part qualifies on its own
+    (group_member_ok) it checks that the parts' tables agree in width and otherwise declines with MVS_E_STATE before anything is
+    enqueued; PartwiseDeformation then steps the parts as separate launch chains.  The nodes are sampled densely (UniformSampling(3):
+    ~1 200 per part) because a part qualifies only from 1 024 nodes on, where its node graph is searched on a grid; with fewer the
+    group is declined for that reason and the widths are never looked at.  What happens here: the group is DECLINED on every call
+    because of the widths (group_declined says so, group_passes stays 0), and each part's vertices are the part-by-part oracle's."""
+    from multiviewstitch_amd import _lib
+    from tests import mesh_valence as MV
+    if _lib.device_count() == 0:
+        pytest.fail("no HIP device: GPU tests must run on the MI355X box")
+    m = MV.case("halves_d12")
+    dirs, faces = S.geodesic_sphere(24)
+    tp = MV.surface(dirs) * (1.02 + 0.02 * np.sin(3 * dirs[:, 2:3]))
+    tn = S.vertex_normals_plyobj(tp, faces)
+    labels = PW.sector_labels(m.pts, 2)
+    tl = oracle.part_recog(m.pts, labels, tp)
+    pd = PW.PartwiseDeformation(m.pts, m.normals, m.faces, labels, 2)
+    info = [h.solver_info() for _, h in pd.live]
+    assert [i["kind"] for i in info] == ["patch", "patch"] and [i["width"] for i in info] == [6, 12], info
+    pd.UniformSampling(3)
+    assert all(h.K >= 1024 for _, h in pd.live), [h.K for _, h in pd.live]
+    pd.set_target(tp, tn, tl)
+    hist = [pd.iterate(1), pd.iterate(1), pd.iterate(2)]            # two passes alone (a group needs them), then the call a group could take
+    print(f"[measured] group_passes {pd.group_passes}, group_declined: {pd.group_declined!r}")
+    assert pd.group_passes == 0 and "differ in width" in pd.group_declined, "a group of widths 6 and 12 must be declined because of the widths"
+    got = pd.vertices()
+    p = oracle.Params.default()
+    for k, part in enumerate(pd.parts):
+        vid = part["vid"]
+        o = oracle.Deform(m.pts[vid], m.normals[vid], part["faces"])
+        assert o.sample_nodes(3) == pd.live[k][1].K
+        sel = np.flatnonzero(tl == k)
+        o.set_target(tp[sel], tn[sel])
+        for n, st in zip((1, 1, 2), hist):
+            so = o.iterate(p, n)
+            assert so["n_valid"] == st[k]["n_valid"] > 0 and so["arap_iters_run"] == st[k]["arap_iters_run"], (k, n)
+            assert st[k]["status"] == 0
+        dv = rms(got[vid], o.vertices())
+        print(f"[measured] part {k} (width {info[k]['width']}): vertex RMS against the oracle {dv:.2e}")
+        assert dv <= 1e-6, f"part {k}"
+    pd.close()

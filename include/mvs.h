@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define MVS_ABI_VERSION 4   /* 3: tracing hook, mvs_comm_set_exchange, view-sharded RemoveGround / LocalAlignmentCore; 4: mvs_deform_group_*, mvs_align_dev, mvs_retain_connect_region_dev / mvs_remove_ground_dev / mvs_part_recog_dev, mvs_trim (additive); mvs_local_alignment_core_sharded takes the rank; still 4, additive: mvs_visibility_cull(_dev), mvs_mesh_vertex_normals(_dev), mvs_processor_stitch_points / _cull_model (mvs_io.h), mvs_render_depth_views(_dev), mvs_processor_render (mvs_io.h) */
+#define MVS_ABI_VERSION 4   /* 3: tracing hook, mvs_comm_set_exchange, view-sharded RemoveGround / LocalAlignmentCore; 4: mvs_deform_group_*, mvs_align_dev, mvs_retain_connect_region_dev / mvs_remove_ground_dev / mvs_part_recog_dev, mvs_trim (additive); mvs_local_alignment_core_sharded takes the rank; still 4, additive: mvs_visibility_cull(_dev), mvs_mesh_vertex_normals(_dev), mvs_processor_stitch_points / _cull_model (mvs_io.h), mvs_render_depth_views(_dev), mvs_processor_render (mvs_io.h), mvs_match_filter_pairs(_dev), mvs_sequence_pair_srt */
 
 enum mvs_status {
     MVS_OK            =  0,
@@ -247,6 +247,55 @@ int mvs_select_keyframe_pair(int32_t n1, int32_t n2, const mvs_camera* cams1, co
 /* Fill triples with the reference's generator: MSVC rand() LCG driving
  * Shuffle(idx, n, 3) (R/Common/Utils.h:25-34).  state in/out. */
 int mvs_srt_make_triples(int64_t n, int iters, uint32_t* state, int32_t* triples);
+
+/* The match-filter cascade of mvs_match_filter for ALL n1 x n2 frame pairs of two adjacent sequences in one launch set — the three
+ * loops of Processor::CalcSimilarityTransformationSeq, R/Processor/Processor.cpp:645-735.  Frame i of the first sequence has its own
+ * texIndex stack tex1[i][view_count][w*h], valid mask valid1[i][w*h] and base image imgs1[i][h][w][3]; frame j of the second one
+ * tex2[j], valid2[j], imgs2[j]; each stack is uploaded once.  Pair k = i*n2 + j owns the raw matches
+ * [raw_offsets[k], raw_offsets[k+1]) of raw[total][6] = (view1,u1,v1,view2,u2,v2); raw_offsets (n1*n2 + 1) ascends from 0.
+ * out (capacity total x 4) receives the survivors (u1,v1,u2,v2) of every pair back to back, pair k at
+ * [out_offsets[k], out_offsets[k+1]); stage_counts (optional, n1*n2 x 3) the sizes after the three stages.  Pair k's slice and its
+ * row of stage_counts equal what mvs_match_filter returns for that pair's inputs, bit for bit.  w and h must not exceed 65535 (a
+ * match is handled as one 64-bit key), n1*n2 <= 1000000; a view index outside [0, view_count) gives MVS_E_INVALID_ARG.
+ * A pair's keys are sorted in LDS; a pair with more stage-1 input than fits takes the same kernel on a global-memory workspace.
+ * MVS_MATCH_PAIRS_LDS_CAP (environment, read at every call) lowers that capacity; the results do not depend on it. */
+int mvs_match_filter_pairs(int32_t n1, int32_t n2, const int64_t* raw_offsets /*n1*n2+1*/, const int32_t* raw /*total x 6*/,
+                           const int32_t* tex1 /*n1 x views x w*h*/, const uint8_t* valid1 /*n1 x w*h*/,
+                           const int32_t* tex2 /*n2 x views x w*h*/, const uint8_t* valid2 /*n2 x w*h*/,
+                           const uint8_t* imgs1 /*n1 x h x w x 3*/, const uint8_t* imgs2 /*n2 x h x w x 3*/,
+                           const mvs_match_filter_params* p, int32_t* out /*capacity total x 4*/, int64_t* out_offsets /*n1*n2+1*/,
+                           int64_t* stage_counts /*n1*n2 x 3 or NULL*/);
+/* the six stacks in HBM, read in the order of hip_stream (may be NULL); raw, raw_offsets and every output stay host arrays;
+ * returns with the work complete */
+int mvs_match_filter_pairs_dev(int32_t n1, int32_t n2, const int64_t* raw_offsets, const int32_t* raw, const int32_t* tex1_dev,
+                               const uint8_t* valid1_dev, const int32_t* tex2_dev, const uint8_t* valid2_dev,
+                               const uint8_t* imgs1_dev, const uint8_t* imgs2_dev, const mvs_match_filter_params* p, int32_t* out,
+                               int64_t* out_offsets, int64_t* stage_counts, void* hip_stream);
+
+/* One turn of the loop over adjacent sequences of Processor::CalcSimilarityTransformationSeq (R/Processor/Processor.cpp:629-826,
+ * without the match JPEGs of :767-793; SIFT matching, :634, is the caller's: its output is `raw`):
+ *   the valid masks of both sequences from their float32 inverse-depth rasters (valid iff inside [min_dsp, max_dsp], Image3D.cpp:98-101),
+ *   the cascade of mvs_match_filter_pairs (:645-735), every survivor lifted to {GetPoint(u1,v1) of frame i, GetPoint(u2,v2) of frame j}
+ *   with the arithmetic of mvs_depth_unproject ((0,0,0) for a pixel outside [min_dsp, max_dsp]), mvs_select_keyframe_pair on the lifted
+ *   lists (:746-765; rand_state in / out, MVS_E_DEGENERATE when no pair qualifies, :794-800), then the closed-form fit
+ *   (MVS_SRT_CLOSED_FORM, :814-817) over the selected pair's matches that survived RemoveOutliers, in list order, with the pair's two
+ *   cameras; residual = ResidualError of the result (:818).
+ * cams1[n1] / cams2[n2] must have the size w x h of p->filter; depths1 [n1][w*h], depths2 [n2][w*h]; raw_offsets / raw / tex / imgs as
+ * mvs_match_filter_pairs.  Optional outputs (NULL to skip): residual, stage_counts (n1*n2 x 3), n_keep and pair_err (n1*n2, as
+ * mvs_select_keyframe_pair), n_sel and sel_matches (the fitted 3-D matches {p.xyz, q.xyz}; capacity: the largest raw bucket x 6). */
+typedef struct mvs_seq_pair_params {
+    mvs_match_filter_params filter;      /* w, h, view_count, ssd_win, ssd_err, sample_interval */
+    double  min_dsp, max_dsp;            /* ParamParser::m_fMinDsp / m_fMaxDsp: validity and lift */
+    int32_t min_match_count;             /* ParamParser::min_match_count */
+    int32_t ransac_iters;                /* 200, Processor.cpp:202 */
+    double  pixel_err, adapt_ratio;      /* RemoveOutliers */
+} mvs_seq_pair_params;
+int mvs_sequence_pair_srt(int32_t n1, int32_t n2, const mvs_camera* cams1, const mvs_camera* cams2,
+                          const float* depths1 /*n1 x w*h*/, const float* depths2 /*n2 x w*h*/,
+                          const int64_t* raw_offsets, const int32_t* raw, const int32_t* tex1, const int32_t* tex2,
+                          const uint8_t* imgs1, const uint8_t* imgs2, const mvs_seq_pair_params* p, uint32_t* rand_state,
+                          int32_t* frm_idx1, int32_t* frm_idx2, double* scale, double* R /*9*/, double* t /*3*/, double* residual,
+                          int64_t* stage_counts, int64_t* n_keep, double* pair_err, int64_t* n_sel, double* sel_matches);
 
 /* Chain composition, Processor.cpp:819-823: (s0,R0,t0) <- (sk,Rk,tk) o (s0,R0,t0). */
 int mvs_srt_compose(double sk, const double* Rk, const double* tk,

@@ -58,6 +58,12 @@ class CMatchFilterParams(C.Structure):
                 ("sample_interval", C.c_int32), ("reserved", C.c_int32)]
 
 
+class CSeqPairParams(C.Structure):
+    """struct mvs_seq_pair_params."""
+    _fields_ = [("filter", CMatchFilterParams), ("min_dsp", C.c_double), ("max_dsp", C.c_double), ("min_match_count", C.c_int32),
+                ("ransac_iters", C.c_int32), ("pixel_err", C.c_double), ("adapt_ratio", C.c_double)]
+
+
 class CStats(C.Structure):
     """struct mvs_deform_stats."""
     _fields_ = [("outer_done", C.c_int32), ("arap_iters_run", C.c_int32), ("cg_iters", C.c_int32),
@@ -86,6 +92,10 @@ _SIGS = {
     "mvs_depth_to_model_dev": (C.c_int, [_VP, _VP, _D, _D, _D, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mvs_depth_unproject": (C.c_int, [_VP, _VP, _D, _D, _VP, _VP]),
     "mvs_match_filter": (C.c_int, [_VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "mvs_match_filter_pairs": (C.c_int, [_I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "mvs_match_filter_pairs_dev": (C.c_int, [_I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "mvs_sequence_pair_srt": (C.c_int, [_I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                        _VP, _VP, _VP, _VP, _VP]),
     "mvs_render_depth": (C.c_int, [_VP, _I64, _VP, _I64, _VP, C.c_float, C.c_float, _VP]),
     "mvs_render_depth_dev": (C.c_int, [_VP, _I64, _VP, _I64, _VP, C.c_float, C.c_float, _VP, _VP]),
     "mvs_render_depth_views": (C.c_int, [_VP, _I64, _VP, _I64, _I32, _VP, _VP, _VP, _VP, _VP, C.c_float, C.c_float, _VP]),

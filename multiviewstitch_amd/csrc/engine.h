@@ -381,6 +381,7 @@ int  mvs_device_cus(int device);                  // compute units of a device (
 int  mvs_scratch_alloc(void** p, size_t bytes, hipStream_t user = nullptr);   // user: the stream the block will be used on, when it is not the legacy default stream
 void mvs_scratch_free(void* p, hipStream_t user = nullptr);                   // user != null: synchronised before the block goes back
 int  mvs_render_chunk_views();                    // MVS_RENDER_CHUNK_VIEWS: views per chunk of render_views_dev (0: sized from its byte budget)
+int  mvs_match_pairs_lds_cap();                   // keys of one frame pair that matchpairs.hip sorts in LDS: MVS_MATCH_PAIRS_LDS_KEYS (knobs.h), lowered by MVS_MATCH_PAIRS_LDS_CAP
 
 // The one RAII block of the pool: handed back behind the stream it was allocated for, so an early return cannot give the pool a
 // block that queued work still touches.

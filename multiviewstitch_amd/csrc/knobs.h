@@ -22,6 +22,12 @@ inline double mvs_knob_env(const char* name, double dflt, double lo, double hi) 
 #define MVS_KNOB(name, dflt, lo, hi) (static_cast<double>(dflt))
 #endif
 
+// matchpairs.hip: 64-bit match keys of ONE frame pair that its cascade kernel holds in LDS (a power of two: the bitonic sort pads to
+// one).  4096 keys = 32 KiB of the CU's 160 KB, so four workgroups (one per SIMD's worth of waves at 256 threads) stay resident on
+// a CU, and SIFT leaves a few thousand raw matches per frame pair at most; a larger bucket sorts in a global-memory workspace.  Not
+// an experiment knob: MVS_MATCH_PAIRS_LDS_CAP (environment, read at every call) can only lower it and never changes a result.
+#define MVS_MATCH_PAIRS_LDS_KEYS 4096
+
 // trace level of the host side: MVS_DEBUG_CG=1 (plans, verdicts, set-up laps) or 2 (+ residual histories) in the
 // environment when the library is loaded; read once (runtime.cpp), 0 otherwise.  It changes no result.
 int mvs_debug_level();

@@ -50,7 +50,7 @@ const void* const* mvs_tu_kernels_grid(int*); const void* const* mvs_tu_kernels_
 const void* const* mvs_tu_kernels_arap(int*); const void* const* mvs_tu_kernels_schwarz(int*); const void* const* mvs_tu_kernels_meshbuild(int*);
 const void* const* mvs_tu_kernels_geom(int*);
 const void* mvs_tu_probe_srt(); const void* mvs_tu_probe_align(); const void* mvs_tu_probe_consist(); const void* mvs_tu_probe_render(); const void* mvs_tu_probe_matchfilter();
-const void* mvs_tu_probe_stitch(); const void* mvs_tu_probe_render_views();
+const void* mvs_tu_probe_stitch(); const void* mvs_tu_probe_render_views(); const void* mvs_tu_probe_matchpairs();
 // (never destroyed: the helper thread is detached and may outlive the static destructors of an exiting process)
 static std::mutex& g_preload_mu = *new std::mutex;
 static std::condition_variable& g_preload_cv = *new std::condition_variable;
@@ -75,7 +75,7 @@ void mvs_preload(int device) {
                 for (int i = 0; i < n; ++i) { hipFuncAttributes a; if (hipFuncGetAttributes(&a, ks[i]) != hipSuccess) (void)hipGetLastError(); }
             }
             for (const void* k : {mvs_tu_probe_srt(), mvs_tu_probe_align(), mvs_tu_probe_consist(), mvs_tu_probe_render(), mvs_tu_probe_matchfilter(),
-                                  mvs_tu_probe_stitch(), mvs_tu_probe_render_views()}) {
+                                  mvs_tu_probe_stitch(), mvs_tu_probe_render_views(), mvs_tu_probe_matchpairs()}) {
                 hipFuncAttributes a;
                 if (hipFuncGetAttributes(&a, k) != hipSuccess) (void)hipGetLastError();
             }
@@ -324,6 +324,14 @@ int mvs_render_chunk_views() {
     const char* e = std::getenv("MVS_RENDER_CHUNK_VIEWS");
     const int n = (e && *e) ? std::atoi(e) : 0;
     return n > 0 ? n : 0;
+}
+
+// read at every call, like MVS_RENDER_CHUNK_VIEWS: a test can send small buckets through the workspace path of matchpairs.hip (the
+// variable only LOWERS the capacity; the results do not depend on it)
+int mvs_match_pairs_lds_cap() {
+    const char* e = std::getenv("MVS_MATCH_PAIRS_LDS_CAP");
+    const int n = (e && *e) ? std::atoi(e) : 0;
+    return (n > 0 && n < MVS_MATCH_PAIRS_LDS_KEYS) ? n : MVS_MATCH_PAIRS_LDS_KEYS;
 }
 
 void mvs_scratch_free(void* p, hipStream_t user) {

@@ -1,6 +1,7 @@
 """``Processor::Deform`` (R/Processor/Processor.cpp:1111-1138) on files, through ``mvs_processor_deform``; the tail of
 ``Processor::AlignmentSeq`` (:952-1105) through ``mvs_processor_stitch_points`` / ``mvs_processor_cull_model``;
-``Processor::Render`` (:1140-1192) through ``mvs_processor_render`` and its batched render ``mvs_render_depth_views``."""
+``Processor::Render`` (:1140-1192) through ``mvs_processor_render`` and its batched render ``mvs_render_depth_views``; the loop
+over adjacent sequences of ``Processor::CalcSimilarityTransformationSeq`` (:629-826) through ``mvs_sequence_pair_srt``."""
 from __future__ import annotations
 
 import ctypes as C
@@ -9,6 +10,8 @@ import os
 import numpy as np
 
 from . import _lib as L
+from . import io as _io
+from . import srt as _srt
 from .deformation import _stats, default_params
 
 
@@ -157,3 +160,108 @@ def MatchFilter(raw, tex1, valid1, tex2, valid2, img1, img2, ssd_win: int, ssd_e
     L.check(L.lib().mvs_match_filter(L.ptr(raw), len(raw), L.ptr(tex1), L.ptr(valid1), L.ptr(tex2), L.ptr(valid2), L.ptr(img1), L.ptr(img2),
                                      C.byref(prm), L.ptr(out), C.byref(n_out), L.ptr(cnt)))
     return out[:n_out.value].copy(), cnt
+
+
+def _raw_table(raw, n1, n2):
+    """raw[i][j] = (n_ij, 6) int32 -> (offsets int64[n1*n2 + 1], all rows back to back), pair k = i*n2 + j."""
+    flat = [L.arr(raw[i][j], np.int32).reshape(-1, 6) for i in range(n1) for j in range(n2)]
+    off = np.zeros(n1 * n2 + 1, np.int64)
+    off[1:] = np.cumsum([len(m) for m in flat])
+    allr = np.ascontiguousarray(np.concatenate(flat)) if off[-1] else np.zeros((0, 6), np.int32)
+    return off, allr
+
+
+def MatchFilterPairs(raw, tex1, valid1, tex2, valid2, imgs1, imgs2, ssd_win: int, ssd_err: float, sample_interval: int, stream: int | None = None):
+    """The cascade of ``MatchFilter`` for every frame pair of two adjacent sequences in one call (R/Processor/Processor.cpp:645-735).
+    raw[i][j] = (n_ij, 6) raw matches between frame i of the first sequence and frame j of the second; tex [frames, views, h*w] int32,
+    valid [frames, h*w] uint8, imgs [frames, h, w, 3] uint8 — numpy arrays, or all six contiguous torch tensors on the GPU (the device
+    form; ``stream`` is then the HIP stream that produced them).  -> (matches[i][j] = (m_ij, 4) int32 (u1, v1, u2, v2),
+    sizes after the three stages int64 [n1, n2, 3])."""
+    dev = hasattr(tex1, "data_ptr")
+    stacks = (tex1, valid1, tex2, valid2, imgs1, imgs2)
+    if dev:
+        if not all(hasattr(a, "data_ptr") and a.is_contiguous() for a in stacks):
+            raise L.MvsError(-1, "the device form takes six contiguous tensors")
+        want = ("int32", "uint8", "int32", "uint8", "uint8", "uint8")
+        if any(str(a.dtype).split(".")[-1] != d for a, d in zip(stacks, want)):
+            raise L.MvsError(-1, "tex must be int32, valid and imgs uint8")
+        ptrs = [L.ptr(int(a.data_ptr())) for a in stacks]
+    else:
+        stacks = tuple(L.arr(a, dt) for a, dt in zip(stacks, (np.int32, np.uint8, np.int32, np.uint8, np.uint8, np.uint8)))
+        ptrs = [L.ptr(a) for a in stacks]
+    n1, n2 = int(stacks[4].shape[0]), int(stacks[5].shape[0])
+    h, w = int(stacks[4].shape[1]), int(stacks[4].shape[2])
+    off, allr = _raw_table(raw, n1, n2)
+    prm = L.CMatchFilterParams(w, h, int(stacks[0].shape[1]), int(ssd_win), float(ssd_err), int(sample_interval), 0)
+    out = np.empty((max(1, len(allr)), 4), np.int32)
+    ooff = np.zeros(n1 * n2 + 1, np.int64)
+    cnt = np.zeros((n1, n2, 3), np.int64)
+    if dev:
+        L.check(L.lib().mvs_match_filter_pairs_dev(n1, n2, L.ptr(off), L.ptr(allr), *ptrs, C.byref(prm), L.ptr(out), L.ptr(ooff), L.ptr(cnt),
+                                                   L.ptr(stream)))
+    else:
+        L.check(L.lib().mvs_match_filter_pairs(n1, n2, L.ptr(off), L.ptr(allr), *ptrs, C.byref(prm), L.ptr(out), L.ptr(ooff), L.ptr(cnt)))
+    return [[out[ooff[i * n2 + j]:ooff[i * n2 + j + 1]].copy() for j in range(n2)] for i in range(n1)], cnt
+
+
+def SequencePairSRT(cams1, cams2, depths1, depths2, raw, tex1, tex2, imgs1, imgs2, ssd_win: int, ssd_err: float, sample_interval: int,
+                    min_dsp: float, max_dsp: float, min_match_count: int = 7, ransac_iters: int = 200, pixel_err: float = 60.0,
+                    adapt_ratio: float = 0.75, state: int = 1) -> dict:
+    """One turn of the loop over adjacent sequences (R/Processor/Processor.cpp:629-826, SIFT matching and the match JPEGs left out):
+    valid masks from the rasters, the match-filter cascade of every frame pair, the survivors lifted to 3-D, the key-frame pair
+    selection and the closed-form fit on the selected pair.  depths [frames, h, w] float32; raw, tex, imgs as ``MatchFilterPairs``.
+    -> dict(frm_idx1, frm_idx2, err, n_keep, pair_err, state) as ``srt.select_keyframe_pair``, plus scale, R, t, residual,
+    stage_counts [n1, n2, 3] and matches = the fitted 3-D matches (n_sel, 6); raises MvsError (MVS_E_DEGENERATE) when no pair
+    qualifies, as the reference exits."""
+    n1, n2 = len(cams1), len(cams2)
+    d1, d2 = L.arr(depths1, np.float32), L.arr(depths2, np.float32)
+    tex1, tex2 = L.arr(tex1, np.int32), L.arr(tex2, np.int32)
+    imgs1, imgs2 = L.arr(imgs1, np.uint8), L.arr(imgs2, np.uint8)
+    if len(d1) != n1 or len(d2) != n2 or len(tex1) != n1 or len(tex2) != n2 or len(imgs1) != n1 or len(imgs2) != n2:
+        raise L.MvsError(-1, "one raster, tex stack and image per camera")
+    h, w = imgs1.shape[1:3]
+    off, allr = _raw_table(raw, n1, n2)
+    prm = L.CSeqPairParams(L.CMatchFilterParams(w, h, tex1.shape[1], int(ssd_win), float(ssd_err), int(sample_interval), 0), float(min_dsp),
+                           float(max_dsp), int(min_match_count), int(ransac_iters), float(pixel_err), float(adapt_ratio))
+    c1 = (L.CCamera * n1)(*[L.CCamera.of(c) for c in cams1])
+    c2 = (L.CCamera * n2)(*[L.CCamera.of(c) for c in cams2])
+    st, f1, f2, s, res, ns = C.c_uint32(state), C.c_int32(), C.c_int32(), C.c_double(), C.c_double(), C.c_int64()
+    R, t = np.empty((3, 3)), np.empty(3)
+    cnt = np.zeros((n1, n2, 3), np.int64)
+    nk, perr = np.zeros((n1, n2), np.int64), np.zeros((n1, n2))
+    sel = np.empty((max(1, int(np.diff(off).max())), 6))
+    vp = lambda x: C.cast(C.byref(x), C.c_void_p)
+    L.check(L.lib().mvs_sequence_pair_srt(n1, n2, C.cast(c1, C.c_void_p), C.cast(c2, C.c_void_p), L.ptr(d1), L.ptr(d2), L.ptr(off), L.ptr(allr),
+                                          L.ptr(tex1), L.ptr(tex2), L.ptr(imgs1), L.ptr(imgs2), vp(prm), vp(st), vp(f1), vp(f2), vp(s), L.ptr(R),
+                                          L.ptr(t), vp(res), L.ptr(cnt), L.ptr(nk), L.ptr(perr), vp(ns), L.ptr(sel)))
+    return dict(frm_idx1=f1.value, frm_idx2=f2.value, err=float(perr[f1.value, f2.value]), n_keep=nk, pair_err=perr, state=st.value,
+                scale=s.value, R=R, t=t, residual=res.value, stage_counts=cnt, matches=sel[:ns.value].copy())
+
+
+def CalcSimilarityTransformationSeq(sequences, params: dict, state, srt_txt=None):
+    """The loop over adjacent sequences of Processor::CalcSimilarityTransformationSeq (R/Processor/Processor.cpp:629-826) and the chain
+    AlignmentSeq makes of it (:851-871).  ``sequences[k]`` = dict(cameras, depths, tex, imgs) of sequence k, plus ``raw`` (raw[i][j],
+    the matches towards sequence k + 1) for every sequence but the last; ``params`` = the keyword arguments of ``SequencePairSRT``
+    (ssd_win, ssd_err, sample_interval, min_dsp, max_dsp, ...).  One ``SequencePairSRT`` per adjacent pair with ONE rand() stream
+    through all of them: ``state`` is the srand seed — an int, or a one-element uint32 numpy array that receives the advanced state.
+    After pair k every earlier entry is composed with it (:819-823); identity is appended for the last sequence (:851-853);
+    ``srt_txt`` (a path) writes the chain as SRT.txt (:855-871).
+    -> (scales [n], Rs [n, 3, 3], ts [n, 3], select_frames [(frm_idx1, frm_idx2)] per pair): the input of ``StitchPointSets``."""
+    st = int(np.asarray(state).reshape(-1)[0])
+    scales, Rs, ts, select = [], [], [], []
+    for k in range(len(sequences) - 1):
+        a, b = sequences[k], sequences[k + 1]
+        r = SequencePairSRT(a["cameras"], b["cameras"], a["depths"], b["depths"], a["raw"], a["tex"], b["tex"], a["imgs"], b["imgs"],
+                            state=st, **params)
+        st = r["state"]
+        select.append((r["frm_idx1"], r["frm_idx2"]))
+        for k0 in range(k):
+            scales[k0], Rs[k0], ts[k0] = _srt.compose(r["scale"], r["R"], r["t"], scales[k0], Rs[k0], ts[k0])
+        scales.append(r["scale"]); Rs.append(r["R"]); ts.append(r["t"])
+    scales.append(1.0); Rs.append(np.eye(3)); ts.append(np.zeros(3))
+    if isinstance(state, np.ndarray):
+        state.reshape(-1)[0] = st
+    scales, Rs, ts = np.array(scales), np.array(Rs).reshape(-1, 3, 3), np.array(ts).reshape(-1, 3)
+    if srt_txt is not None:
+        _io.write_srt_txt(srt_txt, scales, Rs, ts)
+    return scales, Rs, ts, select

@@ -297,6 +297,67 @@ int mvs_sequence_pair_srt(int32_t n1, int32_t n2, const mvs_camera* cams1, const
                           int32_t* frm_idx1, int32_t* frm_idx2, double* scale, double* R /*9*/, double* t /*3*/, double* residual,
                           int64_t* stage_counts, int64_t* n_keep, double* pair_err, int64_t* n_sel, double* sel_matches);
 
+/* Image3D::GenNewViews (R/Image3D/Image3D.cpp:109-222) for all n_frames frames of one sequence in one launch set: view_count rotated
+ * homography views of every base image and the texIndex table of each view (generated-view pixel -> base-view pixel, -1 = unmapped).
+ * cams[n_frames] share one size w x h (<= 65535 each); imgs [n][h][w][3] uint8 as mvs_match_filter_pairs takes them; view_count >= 1,
+ * axis in 0..2 and rot_angle in degrees are ParamParser::view_count / axis / rot_angle.  views [n][view_count][h][w][3] uint8;
+ * tex [n][view_count][w*h] int32, exactly the tex1 / tex2 of mvs_match_filter_pairs.  The rules, literally those of :113-217:
+ *   angles      : -rot*i for i = view_count/2 .. 1, then rot*i for i = 0 .. view_count/2; the first view_count entries are used (an even
+ *                 view_count never uses its largest positive angle) (:131-133);
+ *   homography  : axis = row `axis` of the camera's R, R_ = RotationMatrix (R/Common/Utils.h:124-138), K_ the hand-written inverse of
+ *                 :123-125, H = K (R_ K_), every 3 x 3 product a0*b0 + a1*b1 + a2*b2 left to right; computed on the host in double (the
+ *                 only sin / cos), so the device evaluates no transcendental function;
+ *   source      : w2 = int(w*2.0) by h2 = int(h*2.0) pixels i; u = (int)(i % w2 - w2*0.25), v = (int)(i / w2 - h2*0.25), wf, uf, vf as
+ *                 :153-155; CheckRange takes ints, so its double arguments are converted first (uf = -0.5 is in range);
+ *   double->int : every conversion is one helper (camera_dev.h cvt_i32): a finite x with |x| < 2^31 truncates toward zero, anything else
+ *                 (NaN, +-inf, out of range) gives INT_MIN, as the reference's x64 build, which CheckRange always rejects;
+ *   pass A      : the bounding box of :146-167 over the source pixels whose (uf, vf) is in range, as an exact integer min / max
+ *                 reduction; start values +-1e9 as the reference, so a view with no pixel in range gets the reference's offsets;
+ *   pass B      : the paint of :170-216.  The reference scatters in ascending i and a later i overwrites an earlier one; the
+ *                 destination (int)(i % w2 - offsetx + 0.5) truncates toward zero, so two source columns (rows) can land on destination
+ *                 column (row) 0 and up to four source pixels write one destination pixel.  Here every destination pixel gathers: its
+ *                 sources in descending i, the first that passes the three CheckRange tests of :178 paints it.  Same result, no race;
+ *   colour      : the four branches of :179-211 (both equal, u11 == u22, v11 == v22, bilinear) with the reference's expressions and
+ *                 summation order, (uchar) of the double; tex = v11*w + u11 for the both-equal branch, else int(vf+0.5)*w + int(uf+0.5).
+ * Deviations: a destination pixel nothing paints is uninitialised cv::Mat memory in the reference; here it is (0,0,0), tex = -1.  The
+ * reference writes the views as JPEG and SIFT reads them back; this library has no image codec: the entry returns the rasters, and
+ * what SIFT sees after the JPEG round trip is not pinned.
+ * MVS_E_INVALID_ARG: view_count < 1, axis outside 0..2, n_frames < 1, cameras of differing sizes, a NULL pointer, w or h > 65535. */
+int mvs_gen_new_views(int32_t n_frames, const mvs_camera* cams, const uint8_t* imgs /*n x h x w x 3*/, int32_t view_count, int32_t axis,
+                      double rot_angle, uint8_t* views /*n x views x h x w x 3*/, int32_t* tex /*n x views x w*h*/);
+/* images and both outputs in HBM, in the order of hip_stream (may be NULL); returns with the work complete */
+int mvs_gen_new_views_dev(int32_t n_frames, const mvs_camera* cams, const uint8_t* imgs_dev, int32_t view_count, int32_t axis,
+                          double rot_angle, uint8_t* views_dev, int32_t* tex_dev, void* hip_stream);
+
+/* The background cull of the SIFT key points (R/Processor/Processor.cpp:567-600) for every list of one sequence in one launch set.
+ * List i (of n_frames*view_count) belongs to frame i / view_count and view i % view_count, the reference's order, and owns the keys
+ * [key_offsets[i], key_offsets[i+1]) (ascending from 0) of keys[total][4] float32 = SiftGPU::SiftKeypoint {x, y, s, o}; descs
+ * [total][128] float32 or NULL.  tex [n][view_count][w*h] as mvs_gen_new_views writes it, depths [n][w*h] the float32 inverse-depth
+ * rasters, mask [n][w*h] uint8 or NULL (NULL: ParamParser::isSegment off; non-zero = inside, Image3D::InMask).  Per key:
+ *   1. x = (int)key.x, y = (int)key.y, the implicit float -> int of GetTexIndex's parameters (the conversion rule above);
+ *   2. idx = tex[frame][view][y*w + x]; the key is dropped when idx == -1, when depths[frame][idx] is outside [min_dsp, max_dsp]
+ *      (Image3D.cpp:98-101) or when mask[frame][idx] == 0 (:576);
+ *   3. p3d = the world point of pixel idx with the arithmetic of mvs_depth_unproject (:578);
+ *   4. for every OTHER frame of the sequence GetImgCoordFromWorld with that frame's camera (integer rounding, no z test): outside the
+ *      image -> removed (:579-589).
+ * Survivors keep their order within their list; a key and its 128 floats move together.  keep (optional) [total] uint8; out_offsets
+ * [n_frames*view_count + 1]; out_keys / out_descs (capacity total rows; out_descs only with descs) hold the compacted lists back to
+ * back, list i at [out_offsets[i], out_offsets[i+1]).  Outputs must not alias inputs.
+ * Deviation: a key outside [0,w) x [0,h) (after step 1) is dropped, and so is one whose tex entry is outside [-1, w*h); the
+ * reference would read out of bounds.
+ * MVS_E_INVALID_ARG: n_frames or view_count < 1, cameras of differing sizes, w or h > 65535, key_offsets not ascending from 0, a
+ * required pointer NULL. */
+int mvs_keypoint_cull(int32_t n_frames, int32_t view_count, const mvs_camera* cams, const int64_t* key_offsets, const float* keys,
+                      const float* descs /*or NULL*/, const int32_t* tex, const float* depths, double min_dsp, double max_dsp,
+                      const uint8_t* mask /*or NULL*/, uint8_t* keep /*or NULL*/, int64_t* out_offsets, float* out_keys,
+                      float* out_descs /*NULL without descs*/);
+/* keys, descs, tex, depths, mask, keep and both compacted outputs in HBM, in the order of hip_stream (may be NULL); key_offsets and
+ * out_offsets stay host arrays; returns with the work complete */
+int mvs_keypoint_cull_dev(int32_t n_frames, int32_t view_count, const mvs_camera* cams, const int64_t* key_offsets, const float* keys_dev,
+                          const float* descs_dev, const int32_t* tex_dev, const float* depths_dev, double min_dsp, double max_dsp,
+                          const uint8_t* mask_dev, uint8_t* keep_dev, int64_t* out_offsets, float* out_keys_dev, float* out_descs_dev,
+                          void* hip_stream);
+
 /* Chain composition, Processor.cpp:819-823: (s0,R0,t0) <- (sk,Rk,tk) o (s0,R0,t0). */
 int mvs_srt_compose(double sk, const double* Rk, const double* tk,
                     double* s0, double* R0, double* t0);

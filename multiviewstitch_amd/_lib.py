@@ -96,6 +96,10 @@ _SIGS = {
     "mvs_match_filter_pairs_dev": (C.c_int, [_I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mvs_sequence_pair_srt": (C.c_int, [_I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
                                         _VP, _VP, _VP, _VP, _VP]),
+    "mvs_gen_new_views": (C.c_int, [_I32, _VP, _VP, _I32, _I32, _D, _VP, _VP]),
+    "mvs_gen_new_views_dev": (C.c_int, [_I32, _VP, _VP, _I32, _I32, _D, _VP, _VP, _VP]),
+    "mvs_keypoint_cull": (C.c_int, [_I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _D, _D, _VP, _VP, _VP, _VP, _VP]),
+    "mvs_keypoint_cull_dev": (C.c_int, [_I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _D, _D, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mvs_render_depth": (C.c_int, [_VP, _I64, _VP, _I64, _VP, C.c_float, C.c_float, _VP]),
     "mvs_render_depth_dev": (C.c_int, [_VP, _I64, _VP, _I64, _VP, C.c_float, C.c_float, _VP, _VP]),
     "mvs_render_depth_views": (C.c_int, [_VP, _I64, _VP, _I64, _I32, _VP, _VP, _VP, _VP, _VP, C.c_float, C.c_float, _VP]),

@@ -214,13 +214,6 @@ __global__ void k_mp_valid(const float* __restrict__ dsp, int64_t n, double mn, 
     valid[i] = (d < mn || d > mx) ? 0 : 1;
 }
 
-// Image3D::GetPoint: what k_depth_unproject writes for the pixel ((0,0,0) outside [mn, mx])
-__device__ inline d3 mp_point(const float* __restrict__ dsp, const CamDev& c, int u, int v, double mn, double mx) {
-    const double d = (double)dsp[(int64_t)v * c.w + u];
-    if (d < mn || d > mx) return mk3(0, 0, 0);
-    return world_from_img(c, u, v, 1.0 / d);
-}
-
 __global__ void k_mp_lift(const int32_t* __restrict__ m, int64_t total, const int64_t* __restrict__ off, int npairs, int n2,
                           const float* __restrict__ dsp1, const float* __restrict__ dsp2, const CamDev* __restrict__ c1,
                           const CamDev* __restrict__ c2, double mn, double mx, double* __restrict__ out) {
@@ -229,8 +222,8 @@ __global__ void k_mp_lift(const int32_t* __restrict__ m, int64_t total, const in
     const int k = mp_segment(off, npairs, r), i = k / n2, j = k % n2;
     const CamDev a = c1[i], b = c2[j];
     const int32_t* q = m + 4 * r;                                           // inside both images: the SSD stage kept it
-    st3(out + 6 * r, mp_point(dsp1 + (int64_t)i * a.w * a.h, a, q[0], q[1], mn, mx));
-    st3(out + 6 * r + 3, mp_point(dsp2 + (int64_t)j * b.w * b.h, b, q[2], q[3], mn, mx));
+    st3(out + 6 * r, point_from_raster(dsp1 + (int64_t)i * a.w * a.h, a, q[0], q[1], mn, mx));
+    st3(out + 6 * r + 3, point_from_raster(dsp2 + (int64_t)j * b.w * b.h, b, q[2], q[3], mn, mx));
 }
 
 int bad(const char* fn, const char* what) { mvs_set_error("%s: %s", fn, what); return MVS_E_INVALID_ARG; }

@@ -1,7 +1,8 @@
 """``Processor::Deform`` (R/Processor/Processor.cpp:1111-1138) on files, through ``mvs_processor_deform``; the tail of
 ``Processor::AlignmentSeq`` (:952-1105) through ``mvs_processor_stitch_points`` / ``mvs_processor_cull_model``;
 ``Processor::Render`` (:1140-1192) through ``mvs_processor_render`` and its batched render ``mvs_render_depth_views``; the loop
-over adjacent sequences of ``Processor::CalcSimilarityTransformationSeq`` (:629-826) through ``mvs_sequence_pair_srt``."""
+over adjacent sequences of ``Processor::CalcSimilarityTransformationSeq`` (:629-826) through ``mvs_sequence_pair_srt``; its head (:524-600)
+through ``mvs_gen_new_views`` (Image3D::GenNewViews) and ``mvs_keypoint_cull`` (the background cull of the key points)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -142,6 +143,124 @@ def RenderDepth(points, facets, camera, znear: float = 0.01, zfar: float = 2000.
     out = np.empty((camera.h, camera.w), np.float32)
     L.check(L.lib().mvs_render_depth(L.ptr(pts), len(pts), L.ptr(fac), len(fac), C.byref(cc), float(znear), float(zfar), L.ptr(out)))
     return out
+
+
+def _cam_array(cameras):
+    return (L.CCamera * max(1, len(cameras)))(*[L.CCamera.of(c) for c in cameras])
+
+
+def _is_dev(a):
+    return hasattr(a, "data_ptr")
+
+
+def _dev_ptr(a, dtype, what):
+    """device address of a contiguous torch tensor of the given dtype; None -> NULL"""
+    if a is None:
+        return None
+    if not _is_dev(a) or not a.is_contiguous() or str(a.dtype).split(".")[-1] != dtype:
+        raise L.MvsError(-1, f"the device form takes {what} as a contiguous {dtype} tensor")
+    return L.ptr(int(a.data_ptr()))
+
+
+def GenNewViews(cameras, imgs, view_count: int, axis: int, rot_angle: float, stream: int | None = None):
+    """Image3D::GenNewViews (R/Image3D/Image3D.cpp:109-222) for every frame of one sequence in one call: ``view_count`` rotated
+    homography views of each base image (rotation about row ``axis`` of the camera's R, ``rot_angle`` degrees apart) and each view's
+    texIndex table.  imgs [frames, h, w, 3] uint8 — a numpy array, or a contiguous torch tensor on the GPU (the device form;
+    ``stream`` is then the HIP stream that produced it, and the results are tensors on the same device).
+    -> (views [frames, view_count, h, w, 3] uint8, tex [frames, view_count, h*w] int32: the ``tex`` of ``MatchFilterPairs``).
+    A pixel nothing paints is (0, 0, 0) with tex = -1; the views are rasters, the reference's JPEG round trip is not reproduced."""
+    n = len(cameras)
+    cams = _cam_array(cameras)
+    w, h = (int(cameras[0].w), int(cameras[0].h)) if n else (0, 0)
+    vc = max(0, int(view_count))
+    if tuple(imgs.shape) != (n, h, w, 3):
+        raise L.MvsError(-1, f"imgs must be [frames = {n}, h = {h}, w = {w}, 3]")
+    if _is_dev(imgs):
+        import torch
+        views = torch.empty((n, vc, h, w, 3), dtype=torch.uint8, device=imgs.device)
+        tex = torch.empty((n, vc, h * w), dtype=torch.int32, device=imgs.device)
+        L.check(L.lib().mvs_gen_new_views_dev(n, cams, _dev_ptr(imgs, "uint8", "imgs"), int(view_count), int(axis), float(rot_angle),
+                                              L.ptr(int(views.data_ptr())), L.ptr(int(tex.data_ptr())), L.ptr(stream)))
+        return views, tex
+    img = L.arr(imgs, np.uint8)
+    views = np.empty((n, vc, h, w, 3), np.uint8)
+    tex = np.empty((n, vc, h * w), np.int32)
+    L.check(L.lib().mvs_gen_new_views(n, cams, L.ptr(img), int(view_count), int(axis), float(rot_angle), L.ptr(views), L.ptr(tex)))
+    return views, tex
+
+
+def KeypointCull(cameras, view_count: int, key_offsets, keys, descs, tex, depths, min_dsp: float, max_dsp: float, masks=None,
+                 stream: int | None = None) -> dict:
+    """``mvs_keypoint_cull`` on flat arrays (R/Processor/Processor.cpp:567-600): key_offsets int64 [frames*view_count + 1], keys
+    [total, 4] float32 {x, y, s, o}, descs [total, 128] float32 or None, tex [frames, view_count, h*w] int32, depths [frames, h*w]
+    float32, masks [frames, h*w] uint8 or None — numpy arrays, or all of them (but key_offsets) contiguous torch tensors on the GPU
+    (the device form, ``stream`` = the HIP stream that produced them).
+    -> dict(keep [total] uint8, out_offsets int64, keys [kept, 4], descs [kept, 128] or None), list i at out_offsets[i]:out_offsets[i+1]."""
+    n = len(cameras)
+    cams = _cam_array(cameras)
+    off = L.arr(key_offsets, np.int64).reshape(-1)
+    if len(off) != n * int(view_count) + 1:
+        raise L.MvsError(-1, "key_offsets must hold frames * view_count + 1 entries")
+    total = int(off[-1])
+    ooff = np.zeros(len(off), np.int64)
+    if _is_dev(keys):
+        import torch
+        keep = torch.empty(max(1, total), dtype=torch.uint8, device=keys.device)
+        ok = torch.empty((max(1, total), 4), dtype=torch.float32, device=keys.device)
+        od = torch.empty((max(1, total), 128), dtype=torch.float32, device=keys.device) if descs is not None else None
+        L.check(L.lib().mvs_keypoint_cull_dev(n, int(view_count), cams, L.ptr(off), _dev_ptr(keys, "float32", "keys"), _dev_ptr(descs, "float32", "descs"),
+                                              _dev_ptr(tex, "int32", "tex"), _dev_ptr(depths, "float32", "depths"), float(min_dsp), float(max_dsp),
+                                              _dev_ptr(masks, "uint8", "masks"), L.ptr(int(keep.data_ptr())), L.ptr(ooff), L.ptr(int(ok.data_ptr())),
+                                              L.ptr(int(od.data_ptr())) if od is not None else None, L.ptr(stream)))
+    else:
+        keys = L.arr(keys, np.float32).reshape(-1, 4)
+        descs = L.arr(descs, np.float32).reshape(-1, 128) if descs is not None else None
+        tex, depths = L.arr(tex, np.int32), L.arr(depths, np.float32)
+        masks = L.arr(masks, np.uint8) if masks is not None else None
+        npx = int(cameras[0].w) * int(cameras[0].h) if n else 0
+        if len(keys) != total or (descs is not None and len(descs) != total) or tex.size != n * int(view_count) * npx or depths.size != n * npx or \
+                (masks is not None and masks.size != n * npx):
+            raise L.MvsError(-1, "keys / descs must hold key_offsets[-1] rows; tex, depths and masks one raster per view / frame")
+        keep = np.zeros(max(1, total), np.uint8)
+        ok = np.empty((max(1, total), 4), np.float32)
+        od = np.empty((max(1, total), 128), np.float32) if descs is not None else None
+        L.check(L.lib().mvs_keypoint_cull(n, int(view_count), cams, L.ptr(off), L.ptr(keys), L.ptr(descs), L.ptr(tex), L.ptr(depths), float(min_dsp),
+                                          float(max_dsp), L.ptr(masks), L.ptr(keep), L.ptr(ooff), L.ptr(ok), L.ptr(od)))
+    kept = int(ooff[-1])
+    return dict(keep=keep[:total], out_offsets=ooff, keys=ok[:kept], descs=od[:kept] if od is not None else None)
+
+
+def CullKeypoints(cameras, depths, tex, keys, descs, min_dsp: float, max_dsp: float, masks=None):
+    """The background cull of the SIFT key points (R/Processor/Processor.cpp:567-600) for one sequence: keys[i] = [k_i, 4] float32
+    {x, y, s, o} of generated view i % view_count of frame i // view_count, descs[i] = [k_i, 128] float32 (or ``descs`` None); depths
+    [frames, h, w] float32, tex [frames, view_count, h*w] int32 (``GenNewViews``), masks [frames, h, w] uint8 or None (isSegment off).
+    A key survives when its base pixel is mapped, valid and inside the mask, and its world point projects inside every other frame.
+    -> (keys[i], descs[i] or None) with the survivors of every list in their order."""
+    n = len(cameras)
+    vc = int(np.asarray(tex).shape[1])
+    if len(keys) != n * vc or (descs is not None and len(descs) != len(keys)):
+        raise L.MvsError(-1, "one key list (and descriptor list) per frame and view")
+    lists = [L.arr(k, np.float32).reshape(-1, 4) for k in keys]
+    off = np.zeros(len(lists) + 1, np.int64)
+    off[1:] = np.cumsum([len(k) for k in lists])
+    flat = np.concatenate(lists) if len(lists) else np.zeros((0, 4), np.float32)
+    dflat = np.concatenate([L.arr(d, np.float32).reshape(-1, 128) for d in descs]) if descs is not None else None
+    r = KeypointCull(cameras, vc, off, flat, dflat, tex, depths, min_dsp, max_dsp, masks)
+    o = r["out_offsets"]
+    out_keys = [r["keys"][o[i]:o[i + 1]].copy() for i in range(len(lists))]
+    return out_keys, ([r["descs"][o[i]:o[i + 1]].copy() for i in range(len(lists))] if descs is not None else None)
+
+
+def LoadSequenceModels(cameras, imgs, depths, view_count: int, axis: int, rot_angle: float) -> dict:
+    """The model loop of Processor::CalcSimilarityTransformationSeq for one sequence (R/Processor/Processor.cpp:524-547, LoadModel's
+    GenNewViews): -> dict(cameras, depths, tex, imgs, views), the ``sequences[k]`` entry of ``CalcSimilarityTransformationSeq`` minus
+    ``raw``, which stays the caller's SIFT matching on ``views``."""
+    img = L.arr(imgs, np.uint8)
+    d = L.arr(depths, np.float32)
+    if len(d) != len(cameras):
+        raise L.MvsError(-1, "one raster per camera")
+    views, tex = GenNewViews(cameras, img, view_count, axis, rot_angle)
+    return dict(cameras=list(cameras), depths=d, tex=tex, imgs=img, views=views)
 
 
 def MatchFilter(raw, tex1, valid1, tex2, valid2, img1, img2, ssd_win: int, ssd_err: float, sample_interval: int):

@@ -125,7 +125,11 @@ int mvs_depth_unproject(const float* inv_depth, const mvs_camera* cam,
  * (u1,v1,u2,v2)); stage 2 keeps matches whose (2 ssd_win + 1)^2 grey windows differ by an RMS <= ssd_err (SSD(),
  * R/Common/Utils.h:221-241; windows touching the border are dropped); stage 3 is the greedy gap filter (a match
  * survives unless it is within sample_interval pixels of a kept one in either image).  out: capacity n x 4
- * (u1,v1,u2,v2); stage_counts (optional) = sizes after the three stages. */
+ * (u1,v1,u2,v2); stage_counts (optional) = sizes after the three stages.
+ * The entry is the 1 x 1 case of mvs_match_filter_pairs (matchpairs.hip): the stage-1 rule runs on the host over tex / valid, which
+ * are not uploaded; the keys and the two images go to the GPU, which sorts, filters and packs them.  A view index outside
+ * [0, view_count) gives MVS_E_INVALID_ARG, before a device is needed.  w or h above 65535 gives MVS_E_INVALID_ARG: a match is
+ * handled as one 64-bit key, as in mvs_match_filter_pairs. */
 typedef struct mvs_match_filter_params {
     int32_t w, h, view_count;
     int32_t ssd_win;           /* ParamParser::ssd_win          */

@@ -215,7 +215,7 @@ int mvs_select_keyframe_pair(int32_t n1, int32_t n2, const mvs_camera* cams1, co
         (int64_t)n1 * n2 > 1000000) { mvs_set_error("bad arguments"); return MVS_E_INVALID_ARG; }
     const int np = n1 * n2;
     const int64_t total = match_offsets[np];
-    for (int k = 0; k < np; ++k) if (match_offsets[k + 1] < match_offsets[k] || match_offsets[0] != 0) { mvs_set_error("match_offsets must ascend from 0"); return MVS_E_INVALID_ARG; }
+    if (int rc = check_offsets(__func__, "match_offsets", match_offsets, np)) return rc;
     if (total > 0 && !matches) { mvs_set_error("matches is NULL"); return MVS_E_INVALID_ARG; }
     int rc = need_device();
     if (rc) return rc;

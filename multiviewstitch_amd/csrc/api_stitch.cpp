@@ -17,16 +17,12 @@
 
 namespace {
 
-int bad(const char* fn, const char* what) { mvs_set_error("%s: %s", fn, what); return MVS_E_INVALID_ARG; }
-
 // the SRT chain and the cameras of every sequence (host arrays): n_seq >= 1, cam_off ascending from 0, cameras of positive size
 int check_seqs(const char* fn, int32_t n_seq, const double* scales, const double* R, const double* t, const int32_t* cam_off,
                const mvs_camera* cams) {
     if (n_seq < 1) return bad(fn, "n_seq must be >= 1");
     if (!scales || !R || !t || !cam_off) return bad(fn, "scales, R, t and cam_off must not be NULL");
-    if (cam_off[0] != 0) return bad(fn, "cam_off must start at 0");
-    for (int k = 0; k < n_seq; ++k)
-        if (cam_off[k + 1] < cam_off[k]) return bad(fn, "cam_off must ascend");
+    if (int rc = check_offsets(fn, "cam_off", cam_off, n_seq)) return rc;
     if (cam_off[n_seq] > 0 && !cams) return bad(fn, "cams is NULL");
     for (int c = 0; c < cam_off[n_seq]; ++c)
         if (cams[c].w <= 0 || cams[c].h <= 0) return bad(fn, "every camera needs w, h > 0");
@@ -41,10 +37,7 @@ int check_cull(const char* fn, const int64_t* seg_off, int32_t n_seg, int32_t n_
     if (n_seg < 1 || !seg_off || !n_keep) return bad(fn, "need n_seg >= 1, seg_off and n_keep");
     if (mode != MVS_CULL_SEQUENCES && mode != MVS_CULL_ALL_SEQ) return bad(fn, "mode must be MVS_CULL_SEQUENCES or MVS_CULL_ALL_SEQ");
     if (mode == MVS_CULL_SEQUENCES && n_seg != n_seq) return bad(fn, "MVS_CULL_SEQUENCES takes one segment per sequence");
-    if (seg_off[0] != 0) return bad(fn, "seg_off must start at 0");
-    for (int g = 0; g < n_seg; ++g)
-        if (seg_off[g + 1] < seg_off[g]) return bad(fn, "seg_off must ascend");
-    if (seg_off[n_seg] >= 0x7fffffffLL) return bad(fn, "more than 2^31 - 1 points");
+    if ((rc = check_offsets(fn, "seg_off", seg_off, n_seg, 0x7fffffffLL))) return rc;
     if (seg_off[n_seg] > 0 && (!points || !keep)) return bad(fn, "points / keep is NULL");
     return MVS_OK;
 }
@@ -62,9 +55,7 @@ int check_views(const char* fn, int32_t n_seq, const double* scales, const doubl
                 const mvs_camera* cams, float znear, float zfar) {
     if (n_seq < 1) return bad(fn, "n_seq must be >= 1");
     if (!cam_off) return bad(fn, "cam_off is NULL");
-    if (cam_off[0] != 0) return bad(fn, "cam_off must start at 0");
-    for (int k = 0; k < n_seq; ++k)
-        if (cam_off[k + 1] < cam_off[k]) return bad(fn, "cam_off must ascend");
+    if (int rc = check_offsets(fn, "cam_off", cam_off, n_seq)) return rc;
     if (cam_off[n_seq] < 1) return bad(fn, "no cameras");
     if (cam_off[1] < 1) return bad(fn, "cams[0] must belong to sequence 0 (its size is the viewport of every view)");
     if (!cams) return bad(fn, "cams is NULL");

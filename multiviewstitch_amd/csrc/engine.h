@@ -404,6 +404,19 @@ template <class T> int up(Scratch& d, const T* h, size_t n, size_t cap = 0) {
 template <class T> int down(T* h, const Scratch& d, size_t n) {
     return n ? mvs_check_hip(hipMemcpy(h, d.p, sizeof(T) * n, hipMemcpyDeviceToHost), "download") : MVS_OK;
 }
+// the argument checks of the host entries: every one reports through bad(); check_offsets is the test of the n + 1 offsets of n
+// back-to-back lists (int64_t or int32_t): off[0] == 0, ascending and, with a limit, off[n] below it
+inline int bad(const char* fn, const char* what) { mvs_set_error("%s: %s", fn, what); return MVS_E_INVALID_ARG; }
+template <class T> int check_offsets(const char* fn, const char* name, const T* off, int64_t n, int64_t limit = 0) {
+    const char* what = nullptr;
+    if (off[0] != 0) what = "must start at 0";
+    for (int64_t k = 0; k < n && !what; ++k)
+        if (off[k + 1] < off[k]) what = "must ascend";
+    if (!what && limit > 0 && (int64_t)off[n] >= limit) what = "holds too many items (2^31 - 1 and above)";
+    if (!what) return MVS_OK;
+    mvs_set_error("%s: %s %s", fn, name, what);
+    return MVS_E_INVALID_ARG;
+}
 // the rest of the process-wide state (runtime.cpp)
 int  mvs_current_device();
 int  need_device();                                   // MVS_E_NO_DEVICE without a HIP device, else selects mvs_current_device() on this thread

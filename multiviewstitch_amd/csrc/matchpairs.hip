@@ -1,9 +1,8 @@
 // matchpairs.hip — one turn of the sequence-pair loop of Processor::CalcSimilarityTransformationSeq (R/Processor/Processor.cpp:629-826,
 // without the match JPEGs of :767-793) for ALL n1 x n2 frame pairs of two adjacent sequences at once:
 //
-//   k_mp_map      : one thread per raw match (view1,u1,v1,view2,u2,v2): range test, texIndex look-up in the frame's own stack, -1 test,
-//                   valid read at the GENERATED-view pixel (:658-662, the rules of matchfilter.hip) -> one 64-bit key (u1,v1,u2,v2 in
-//                   16 bits each, u1 on top: integer order = the std::set order of Vector.h:57-63) or MP_NONE
+//   k_mp_map      : one thread per raw match (view1,u1,v1,view2,u2,v2): the stage-1 rule (mp_stage1, frontend_dev.h; :658-662) -> one
+//                   64-bit key or MP_NONE
 //   k_mp_cascade  : one workgroup per frame pair, the pair's keys in LDS: bitonic sort + unique (:650-680), SSD window (:683-707,
 //                   Utils.h:221-241), ordered compaction, greedy gap filter in list order (:713-735)
 //   k_mp_pack     : the survivors of every pair back to back (the layout of mvs_match_filter's `out`, pair after pair)
@@ -13,12 +12,16 @@
 // same kernel body on a slice of a global-memory workspace: the body takes a flat pointer.  Every loop with a barrier in it has a
 // trip count that depends only on per-pair sizes every thread of the workgroup reads from the same place; no workgroup waits on
 // another one.
+//
+// mvs_match_filter, the ONE-pair entry (:644-735), is a client of the same cascade: the stage-1 rule runs on the host over the caller's
+// arrays (the tex stacks and masks are never uploaded), the keys and the two base images go up and k_mp_cascade runs as the 1 x 1 case.
 #include "engine.h"
 #include "trace.h"
 #include "knobs.h"
 #include "dev_common.h"
 #include "geom.h"
 #include "camera_dev.h"
+#include "frontend_dev.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -28,30 +31,12 @@ namespace {
 
 constexpr int MP_TPB = 256;
 constexpr int MP_WAVES = MP_TPB / 64;
-constexpr unsigned long long MP_NONE = ~0ull;          // never a key: u1 = 65535 would need w > 65535
 static_assert((MVS_MATCH_PAIRS_LDS_KEYS & (MVS_MATCH_PAIRS_LDS_KEYS - 1)) == 0, "the bitonic sort pads to a power of two");
 
-// cv::cvtColor(COLOR_RGB2GRAY) for 8-bit data, as matchfilter.hip states it
-__device__ inline int mp_grey8(const uint8_t* px) { return (4899 * px[0] + 9617 * px[1] + 1868 * px[2] + 8192) >> 14; }
-
-__device__ inline unsigned long long mp_key(int u1, int v1, int u2, int v2) {
-    return ((unsigned long long)(u1 & 0xffff) << 48) | ((unsigned long long)(v1 & 0xffff) << 32) | ((unsigned long long)(u2 & 0xffff) << 16) |
-           (unsigned long long)(v2 & 0xffff);
-}
 struct MpMatch { int u1, v1, u2, v2; };
 __device__ inline MpMatch mp_unkey(unsigned long long k) {
     MpMatch m = {(int)(k >> 48), (int)((k >> 32) & 0xffff), (int)((k >> 16) & 0xffff), (int)(k & 0xffff)};
     return m;
-}
-
-// the segment of item r: the last k with off[k] <= r (off ascends from 0, off[n] > r; empty segments are skipped)
-__device__ inline int mp_segment(const int64_t* __restrict__ off, int n, int64_t r) {
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (off[mid] <= r) lo = mid; else hi = mid;
-    }
-    return lo;
 }
 
 __global__ void k_mp_map(const int32_t* __restrict__ raw, int64_t total, const int64_t* __restrict__ raw_off, int npairs, int n2,
@@ -60,18 +45,12 @@ __global__ void k_mp_map(const int32_t* __restrict__ raw, int64_t total, const i
                          int32_t* __restrict__ bad_view) {
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= total) return;
-    const int k = mp_segment(raw_off, npairs, r);
+    const int k = segment_of(raw_off, npairs, r);
     const int64_t i = k / n2, j = k % n2, npx = (int64_t)w * h;
-    const int32_t* q = raw + 6 * r;
-    const int a1 = q[0], u1 = q[1], v1 = q[2], a2 = q[3], u2 = q[4], v2 = q[5];
-    unsigned long long key = MP_NONE;
-    if (a1 < 0 || a1 >= views || a2 < 0 || a2 >= views) {
-        *bad_view = 1;                                                     // the call returns MVS_E_INVALID_ARG, as mvs_match_filter does
-    } else if (u1 >= 0 && u1 < w && v1 >= 0 && v1 < h && u2 >= 0 && u2 < w && v2 >= 0 && v2 < h) {
-        const int64_t px1 = (int64_t)v1 * w + u1, px2 = (int64_t)v2 * w + u2;
-        const int idx1 = tex1[(i * views + a1) * npx + px1], idx2 = tex2[(j * views + a2) * npx + px2];
-        if (idx1 != -1 && idx2 != -1 && valid1[i * npx + px1] && valid2[j * npx + px2])     // valid at the generated-view pixel (:661)
-            key = mp_key(idx1 % w, idx1 / w, idx2 % w, idx2 / w);
+    unsigned long long key = mp_stage1(raw + 6 * r, tex1 + i * views * npx, valid1 + i * npx, tex2 + j * views * npx, valid2 + j * npx, w, h, views);
+    if (key == MP_BAD_VIEW) {
+        *bad_view = 1;                                                     // the call returns MVS_E_INVALID_ARG
+        key = MP_NONE;
     }
     keys[r] = key;
 }
@@ -80,7 +59,7 @@ __global__ void k_mp_map(const int32_t* __restrict__ raw, int64_t total, const i
 // element travels in *s_last, because the chunk before it has already been compacted over.  n is workgroup-uniform.
 template <class F>
 __device__ inline int mp_compact(unsigned long long* buf, int n, F keep, int* s_wsum, unsigned long long* s_last) {
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     int base = 0;
     for (int c0 = 0; c0 < n; c0 += MP_TPB) {
         const int i = c0 + tid;
@@ -91,17 +70,11 @@ __device__ inline int mp_compact(unsigned long long* buf, int n, F keep, int* s_
             const unsigned long long prev = tid > 0 ? buf[i - 1] : (c0 > 0 ? *s_last : MP_NONE);
             f = keep(i, key, prev);
         }
-        const unsigned long long bal = __ballot(f);
-        const int pre = __popcll(bal & ((1ull << lane) - 1ull));
-        __syncthreads();                                                    // every read of this chunk (and of *s_last) is done
-        if (lane == 0) s_wsum[wv] = __popcll(bal);
+        __syncthreads();                                                    // every read of this chunk (and of *s_last, s_wsum) is done
         if (tid == MP_TPB - 1) *s_last = key;
-        __syncthreads();
-        int off = base, tot = 0;
-#pragma unroll
-        for (int q = 0; q < MP_WAVES; ++q) { if (q < wv) off += s_wsum[q]; tot += s_wsum[q]; }
-        if (f) buf[off + pre] = key;                                        // off + pre <= i, inside chunks already read
-        base += tot;
+        const WgRank k = wg_rank<MP_WAVES>(f, s_wsum);                      // (its barrier: the writes of the chunk start behind it)
+        if (f) buf[base + k.rank] = key;                                    // base + k.rank <= i, inside chunks already read
+        base += k.total;
     }
     __syncthreads();
     return base;
@@ -142,7 +115,7 @@ __global__ __launch_bounds__(MP_TPB) void k_mp_cascade(const unsigned long long*
     }
     for (int i = m + tid; i < P; i += MP_TPB) buf[i] = MP_NONE;
     __syncthreads();
-    // 1. the std::set: bitonic sort (ascending), then unique
+    // 1. the ordered set of :650-680: bitonic sort (ascending), then unique
     for (int kk = 2; kk <= P; kk <<= 1)
         for (int j = kk >> 1; j > 0; j >>= 1) {
             for (int t = tid; t < (P >> 1); t += MP_TPB) {
@@ -153,7 +126,7 @@ __global__ __launch_bounds__(MP_TPB) void k_mp_cascade(const unsigned long long*
             __syncthreads();
         }
     const int c1 = mp_compact(buf, m, [](int i, unsigned long long key, unsigned long long prev) { return i == 0 || key != prev; }, s_wsum, &s_last);
-    // 2. SSD window: the window-inside-image rule of k_ssd, the sum of squared integer differences (exact), the test in double
+    // 2. SSD window (Utils.h:221-241): the sum of squared integer grey differences (exact), the root mean square tested in double
     const int64_t npx = (int64_t)w * h;
     const uint8_t* img1 = imgs1 + 3 * npx * (k / n2);
     const uint8_t* img2 = imgs2 + 3 * npx * (k % n2);
@@ -167,7 +140,7 @@ __global__ __launch_bounds__(MP_TPB) void k_mp_cascade(const unsigned long long*
             const uint8_t* p1 = img1 + 3 * ((int64_t)(q.v1 - win + a) * w + (q.u1 - win));
             const uint8_t* p2 = img2 + 3 * ((int64_t)(q.v2 - win + a) * w + (q.u2 - win));
             for (int b = 0; b < len; ++b) {
-                const int d = mp_grey8(p1 + 3 * b) - mp_grey8(p2 + 3 * b);
+                const int d = grey8(p1 + 3 * b) - grey8(p2 + 3 * b);
                 sum += (unsigned long long)(d * d);
             }
         }
@@ -219,26 +192,20 @@ __global__ void k_mp_lift(const int32_t* __restrict__ m, int64_t total, const in
                           const CamDev* __restrict__ c2, double mn, double mx, double* __restrict__ out) {
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= total) return;
-    const int k = mp_segment(off, npairs, r), i = k / n2, j = k % n2;
+    const int k = segment_of(off, npairs, r), i = k / n2, j = k % n2;
     const CamDev a = c1[i], b = c2[j];
     const int32_t* q = m + 4 * r;                                           // inside both images: the SSD stage kept it
     st3(out + 6 * r, point_from_raster(dsp1 + (int64_t)i * a.w * a.h, a, q[0], q[1], mn, mx));
     st3(out + 6 * r + 3, point_from_raster(dsp2 + (int64_t)j * b.w * b.h, b, q[2], q[3], mn, mx));
 }
 
-int bad(const char* fn, const char* what) { mvs_set_error("%s: %s", fn, what); return MVS_E_INVALID_ARG; }
-
 int check_pairs(const char* fn, int32_t n1, int32_t n2, const int64_t* raw_off, const int32_t* raw, const mvs_match_filter_params* p) {
     if (n1 <= 0 || n2 <= 0 || (int64_t)n1 * n2 > 1000000) return bad(fn, "need n1, n2 >= 1 and n1 * n2 <= 1000000");
     if (!raw_off || !p) return bad(fn, "raw_offsets / params is NULL");
     if (p->w <= 0 || p->h <= 0 || p->view_count <= 0 || p->ssd_win < 0) return bad(fn, "need w, h, view_count > 0 and ssd_win >= 0");
     if (p->w > 65535 || p->h > 65535) return bad(fn, "w and h must not exceed 65535 (a match is one 64-bit key)");
-    if (raw_off[0] != 0) return bad(fn, "raw_offsets must start at 0");
-    const int np = n1 * n2;
-    for (int k = 0; k < np; ++k)
-        if (raw_off[k + 1] < raw_off[k]) return bad(fn, "raw_offsets must ascend");
-    if (raw_off[np] >= 0x7fffffffLL) return bad(fn, "more than 2^31 - 1 raw matches");
-    if (raw_off[np] > 0 && !raw) return bad(fn, "raw is NULL");
+    if (int rc = check_offsets(fn, "raw_offsets", raw_off, n1 * n2, 0x7fffffffLL)) return rc;
+    if (raw_off[n1 * n2] > 0 && !raw) return bad(fn, "raw is NULL");
     return MVS_OK;
 }
 
@@ -249,10 +216,42 @@ struct PairsOut {
     std::vector<int32_t> counts;       // np x 3
 };
 
-// the cascade over every pair; all image / table stacks in HBM, raw and raw_off on the host.  Returns with s synchronised.
-int pairs_core(int n1, int n2, const int64_t* raw_off, const int32_t* raw, const int32_t* tex1, const uint8_t* valid1, const int32_t* tex2,
-               const uint8_t* valid2, const uint8_t* imgs1, const uint8_t* imgs2, const mvs_match_filter_params* p, hipStream_t s,
-               PairsOut& o) {
+// what the two halves of the cascade share in HBM; the blocks go back when the call is over
+struct PairsDev {
+    Scratch raw, off, keys, cnt;       // raw matches (map only); raw_off [np + 1]; one key per raw match; stage sizes [np][3], then the
+                                       // bad-view flag of the map
+};
+
+// off uploaded, keys allocated, the stage sizes and the flag cleared (counts of empty pairs are never written by the cascade)
+int pairs_begin(PairsDev& d, int np, const int64_t* raw_off, hipStream_t s) {
+    int rc;
+    if ((rc = d.off.alloc(sizeof(int64_t) * ((size_t)np + 1), s)) || (rc = d.keys.alloc(sizeof(unsigned long long) * (size_t)raw_off[np], s)) ||
+        (rc = d.cnt.alloc(sizeof(int32_t) * (3 * (size_t)np + 1), s))) return rc;
+    HIPCHK(hipMemcpyAsync(d.off.p, raw_off, sizeof(int64_t) * ((size_t)np + 1), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(d.cnt.p, 0, sizeof(int32_t) * (3 * (size_t)np + 1), s));
+    return MVS_OK;
+}
+
+// stage 1 of every pair: tex / valid stacks in HBM, raw and raw_off on the host; enqueues on s
+int pairs_map(int n1, int n2, const int64_t* raw_off, const int32_t* raw, const int32_t* tex1, const uint8_t* valid1, const int32_t* tex2,
+              const uint8_t* valid2, const mvs_match_filter_params* p, hipStream_t s, PairsDev& d) {
+    const int np = n1 * n2;
+    const int64_t total = raw_off[np];
+    if (total == 0) return MVS_OK;
+    int rc;
+    if ((rc = d.raw.alloc(sizeof(int32_t) * 6 * (size_t)total, s)) || (rc = pairs_begin(d, np, raw_off, s))) return rc;
+    HIPCHK(hipMemcpyAsync(d.raw.p, raw, sizeof(int32_t) * 6 * (size_t)total, hipMemcpyHostToDevice, s));
+    k_mp_map<<<dim3((unsigned)((total + MP_TPB - 1) / MP_TPB)), dim3(MP_TPB), 0, s>>>(d.raw.as<int32_t>(), total, d.off.as<int64_t>(), np, n2, tex1, valid1,
+                                                                                     tex2, valid2, p->w, p->h, p->view_count,
+                                                                                     d.keys.as<unsigned long long>(), d.cnt.as<int32_t>() + 3 * (size_t)np);
+    HIPCHK(hipGetLastError());
+    return MVS_OK;
+}
+
+// stages 1 (sort, unique) to 3 of every pair from the keys in d (pairs_begin, then pairs_map or an upload); images in HBM.  Returns
+// with s synchronised.
+int pairs_cascade(int n1, int n2, const int64_t* raw_off, const PairsDev& d, const uint8_t* imgs1, const uint8_t* imgs2,
+                  const mvs_match_filter_params* p, hipStream_t s, PairsOut& o) {
     const int np = n1 * n2;
     const int64_t total = raw_off[np];
     o.off.assign((size_t)np + 1, 0);
@@ -261,7 +260,7 @@ int pairs_core(int n1, int n2, const int64_t* raw_off, const int32_t* raw, const
     const int cap = mvs_match_pairs_lds_cap();
     std::vector<int64_t> ws_off((size_t)np, 0);
     int64_t ws_total = 0;
-    for (int k = 0; k < np; ++k) {                                          // a pair with more raw matches than cap MAY need the workspace
+    for (int k = 0; k < np; ++k) {                                          // a pair with more keys than cap MAY need the workspace
         const int64_t n = raw_off[k + 1] - raw_off[k];
         if (n <= cap) continue;
         int64_t P = 1;
@@ -269,27 +268,18 @@ int pairs_core(int n1, int n2, const int64_t* raw_off, const int32_t* raw, const
         ws_off[k] = ws_total;
         ws_total += P;
     }
-    Scratch draw, doff, dwsoff, dkeys, dws, dout, dcnt;
+    Scratch dwsoff, dws, dout;
     int rc;
-    if ((rc = draw.alloc(sizeof(int32_t) * 6 * (size_t)total, s)) || (rc = doff.alloc(sizeof(int64_t) * ((size_t)np + 1), s)) ||
-        (rc = dwsoff.alloc(sizeof(int64_t) * (size_t)np, s)) || (rc = dkeys.alloc(sizeof(unsigned long long) * (size_t)total, s)) ||
-        (rc = dws.alloc(sizeof(unsigned long long) * (size_t)ws_total, s)) || (rc = dout.alloc(sizeof(int32_t) * 4 * (size_t)total, s)) ||
-        (rc = dcnt.alloc(sizeof(int32_t) * (3 * (size_t)np + 1), s))) return rc;
-    HIPCHK(hipMemcpyAsync(draw.p, raw, sizeof(int32_t) * 6 * (size_t)total, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(doff.p, raw_off, sizeof(int64_t) * ((size_t)np + 1), hipMemcpyHostToDevice, s));
+    if ((rc = dwsoff.alloc(sizeof(int64_t) * (size_t)np, s)) || (rc = dws.alloc(sizeof(unsigned long long) * (size_t)ws_total, s)) ||
+        (rc = dout.alloc(sizeof(int32_t) * 4 * (size_t)total, s))) return rc;
     HIPCHK(hipMemcpyAsync(dwsoff.p, ws_off.data(), sizeof(int64_t) * (size_t)np, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(dcnt.p, 0, sizeof(int32_t) * (3 * (size_t)np + 1), s));       // stage sizes, then the bad-view flag
-    int32_t* flag = dcnt.as<int32_t>() + 3 * (size_t)np;
-    k_mp_map<<<dim3((unsigned)((total + MP_TPB - 1) / MP_TPB)), dim3(MP_TPB), 0, s>>>(draw.as<int32_t>(), total, doff.as<int64_t>(), np, n2, tex1, valid1,
-                                                                                     tex2, valid2, p->w, p->h, p->view_count,
-                                                                                     dkeys.as<unsigned long long>(), flag);
     const double gap = (double)p->sample_interval * (double)p->sample_interval;         // :713
-    k_mp_cascade<<<dim3((unsigned)np), dim3(MP_TPB), 0, s>>>(dkeys.as<unsigned long long>(), doff.as<int64_t>(), n2, cap, dws.as<unsigned long long>(),
+    k_mp_cascade<<<dim3((unsigned)np), dim3(MP_TPB), 0, s>>>(d.keys.as<unsigned long long>(), d.off.as<int64_t>(), n2, cap, dws.as<unsigned long long>(),
                                                             dwsoff.as<int64_t>(), imgs1, imgs2, p->w, p->h, p->ssd_win, p->ssd_err, gap,
-                                                            dout.as<int32_t>(), dcnt.as<int32_t>());
+                                                            dout.as<int32_t>(), d.cnt.as<int32_t>());
     HIPCHK(hipGetLastError());
     std::vector<int32_t> hc(3 * (size_t)np + 1);
-    HIPCHK(hipMemcpyAsync(hc.data(), dcnt.p, sizeof(int32_t) * hc.size(), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(hc.data(), d.cnt.p, sizeof(int32_t) * hc.size(), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if (hc.back()) { mvs_set_error("match filter: view index out of range"); return MVS_E_INVALID_ARG; }
     hc.pop_back();
@@ -300,10 +290,19 @@ int pairs_core(int n1, int n2, const int64_t* raw_off, const int32_t* raw, const
     Scratch dooff;
     if ((rc = o.packed.alloc(sizeof(int32_t) * 4 * (size_t)kept, s)) || (rc = dooff.alloc(sizeof(int64_t) * ((size_t)np + 1), s))) return rc;
     HIPCHK(hipMemcpyAsync(dooff.p, o.off.data(), sizeof(int64_t) * ((size_t)np + 1), hipMemcpyHostToDevice, s));
-    k_mp_pack<<<dim3((unsigned)np), dim3(MP_TPB), 0, s>>>(dout.as<int32_t>(), doff.as<int64_t>(), dooff.as<int64_t>(), o.packed.as<int32_t>());
+    k_mp_pack<<<dim3((unsigned)np), dim3(MP_TPB), 0, s>>>(dout.as<int32_t>(), d.off.as<int64_t>(), dooff.as<int64_t>(), o.packed.as<int32_t>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
     return MVS_OK;
+}
+
+// the cascade over every pair; all image / table stacks in HBM, raw and raw_off on the host.  Returns with s synchronised.
+int pairs_core(int n1, int n2, const int64_t* raw_off, const int32_t* raw, const int32_t* tex1, const uint8_t* valid1, const int32_t* tex2,
+               const uint8_t* valid2, const uint8_t* imgs1, const uint8_t* imgs2, const mvs_match_filter_params* p, hipStream_t s,
+               PairsOut& o) {
+    PairsDev d;
+    int rc = pairs_map(n1, n2, raw_off, raw, tex1, valid1, tex2, valid2, p, s, d);
+    return rc ? rc : pairs_cascade(n1, n2, raw_off, d, imgs1, imgs2, p, s, o);
 }
 
 void copy_counts(const PairsOut& o, int64_t* stage_counts) {
@@ -314,6 +313,37 @@ void copy_counts(const PairsOut& o, int64_t* stage_counts) {
 }  // namespace
 
 extern "C" {
+
+int mvs_match_filter(const int32_t* raw, int64_t n, const int32_t* tex1, const uint8_t* valid1, const int32_t* tex2, const uint8_t* valid2,
+                     const uint8_t* img1, const uint8_t* img2, const mvs_match_filter_params* p, int32_t* out, int64_t* n_out,
+                     int64_t* stage_counts) {
+    if (n < 0 || (n && !raw) || !tex1 || !valid1 || !tex2 || !valid2 || !img1 || !img2 || !p || !out || !n_out || p->w <= 0 || p->h <= 0 ||
+        p->view_count <= 0 || p->ssd_win < 0) return bad(__func__, "bad arguments");
+    if (p->w > 65535 || p->h > 65535) return bad(__func__, "w and h must not exceed 65535 (a match is one 64-bit key)");
+    std::vector<unsigned long long> keys;                                   // stage 1 on the host: the stacks and masks stay where they are
+    for (int64_t k = 0; k < n; ++k) {
+        const unsigned long long key = mp_stage1(raw + 6 * k, tex1, valid1, tex2, valid2, p->w, p->h, p->view_count);
+        if (key == MP_BAD_VIEW) return bad(__func__, "view index out of range");
+        if (key != MP_NONE) keys.push_back(key);
+    }
+    if (keys.size() >= 0x7fffffffULL) return bad(__func__, "more than 2^31 - 1 matches");
+    int rc = need_device();
+    if (rc) return rc;
+    const int64_t off[2] = {0, (int64_t)keys.size()};
+    const size_t npx = (size_t)p->w * p->h;
+    PairsDev d;
+    Scratch i1, i2;
+    if (off[1] > 0) {
+        if ((rc = pairs_begin(d, 1, off, nullptr)) || (rc = up(i1, img1, npx * 3)) || (rc = up(i2, img2, npx * 3))) return rc;
+        HIPCHK(hipMemcpyAsync(d.keys.p, keys.data(), sizeof(unsigned long long) * keys.size(), hipMemcpyHostToDevice, nullptr));
+    }
+    PairsOut o;
+    if ((rc = pairs_cascade(1, 1, off, d, i1.as<uint8_t>(), i2.as<uint8_t>(), p, nullptr, o))) return rc;
+    if ((rc = down(out, o.packed, 4 * (size_t)o.off[1]))) return rc;
+    *n_out = o.off[1];
+    copy_counts(o, stage_counts);
+    return MVS_OK;
+}
 
 int mvs_match_filter_pairs_dev(int32_t n1, int32_t n2, const int64_t* raw_offsets, const int32_t* raw, const int32_t* tex1_dev,
                                const uint8_t* valid1_dev, const int32_t* tex2_dev, const uint8_t* valid2_dev, const uint8_t* imgs1_dev,

@@ -15,6 +15,7 @@
 #include "dev_common.h"
 #include "geom.h"
 #include "camera_dev.h"
+#include "frontend_dev.h"
 #include "stitch.h"
 #include <algorithm>
 
@@ -24,10 +25,6 @@ constexpr int TPB = 256;
 
 // the map of (segment, k0): identity (a sequence's own points before Poisson, p3d_ = p3d at :973-983), else the similarity map
 struct CullMap { Map34 m; int32_t identity; int32_t pad; };
-
-__device__ inline bool check_range(int32_t u, int32_t v, int32_t w, int32_t h) {   // CheckRange, R/Common/Utils.h:20-22
-    return u >= 0 && u < w && v >= 0 && v < h;
-}
 
 // a wave-uniform read of a table the kernel never writes, through the constant address space: the backend then always selects
 // scalar loads (through the generic pointer it chose vector loads inside the camera loop)
@@ -66,7 +63,7 @@ __global__ __launch_bounds__(TPB) void k_vis_cull(const double* __restrict__ pts
                 const CamDev cam = load_uniform(cams + c);
                 int32_t u, v;
                 img_from_world(cam, q, &u, &v);                           // GetImgCoordFromWorld, Camera.cpp:45-48,68-72
-                in = in && check_range(u, v, cam.w, cam.h);
+                in = in && in_range(u, v, cam.w, cam.h);
             }
         }
         if (active) keep[i] = (T)(in ? 1 : 0);

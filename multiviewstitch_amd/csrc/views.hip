@@ -20,6 +20,7 @@
 #include "dev_common.h"
 #include "geom.h"
 #include "camera_dev.h"
+#include "frontend_dev.h"
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -31,8 +32,6 @@ constexpr int VW_WAVES = VW_TPB / 64;
 constexpr int32_t GV_NONE = 0x7f7f7f7f;                  // what hipMemset(0x7f) leaves: no source pixel was in range
 constexpr int KC_CAMS = 64;                               // cameras staged in LDS at a time
 static_assert(sizeof(CamDev) % 8 == 0, "the cameras are staged as 8-byte words");
-
-__device__ inline bool in_range(int u, int v, int w, int h) { return u >= 0 && u < w && v >= 0 && v < h; }   // CheckRange, Utils.h:20-22
 
 // :151-155 for the source pixel (x, y) = (i % w2, i / w2); qx = w2 * 0.25, qy = h2 * 0.25
 __device__ inline void gv_source(const double* H, int x, int y, double qx, double qy, double* uf, double* vf) {
@@ -165,8 +164,6 @@ void gv_homography(const mvs_camera& c, int axis, double angle_deg, double* H) {
     mul33(K, T, H);
 }
 
-int bad(const char* fn, const char* what) { mvs_set_error("%s: %s", fn, what); return MVS_E_INVALID_ARG; }
-
 int check_cams(const char* fn, int32_t n_frames, const mvs_camera* cams) {
     if (n_frames < 1) return bad(fn, "need n_frames >= 1");
     if (!cams) return bad(fn, "cams is NULL");
@@ -218,16 +215,6 @@ int views_core(int n, const mvs_camera* cams, const uint8_t* imgs, int view_coun
 }
 
 // ------------------------------------------------------------------ key-point cull ----
-// the list of key r: the last l with off[l] <= r (off ascends from 0, off[n] > r; empty lists are skipped)
-__device__ inline int kc_list(const int64_t* __restrict__ off, int n, int64_t r) {
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (off[mid] <= r) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(VW_TPB) void k_kc_decide(const float* __restrict__ keys, int64_t total, const int64_t* __restrict__ off, int nlists,
                                                       int view_count, int n_frames, const CamDev* __restrict__ cams,
                                                       const int32_t* __restrict__ tex, const float* __restrict__ dsp,
@@ -243,7 +230,7 @@ __global__ __launch_bounds__(VW_TPB) void k_kc_decide(const float* __restrict__ 
     int frame = -1;
     d3 p = mk3(0, 0, 0);
     if (r < total) {
-        const int l = kc_list(off, nlists, r);
+        const int l = segment_of(off, nlists, r);                       // the list of key r
         frame = l / view_count;
         const int x = cvt_i32((double)keys[4 * r]), y = cvt_i32((double)keys[4 * r + 1]);          // GetTexIndex's int parameters (:575)
         if (in_range(x, y, w, h)) {
@@ -272,14 +259,8 @@ __global__ __launch_bounds__(VW_TPB) void k_kc_decide(const float* __restrict__ 
             }
     }
     if (r < total) keep[r] = ok ? 1 : 0;
-    const unsigned long long bal = __ballot(ok);
-    if ((tid & 63) == 0) s_wsum[tid >> 6] = __popcll(bal);
-    __syncthreads();
-    if (tid == 0) {
-        int sum = 0;
-        for (int q = 0; q < VW_WAVES; ++q) sum += s_wsum[q];
-        cnt[blockIdx.x] = sum;
-    }
+    const WgRank k = wg_rank<VW_WAVES>(ok, s_wsum);
+    if (tid == 0) cnt[blockIdx.x] = k.total;
 }
 
 // base[b] = survivors in the blocks before b, base[nb] = all survivors; one workgroup
@@ -329,11 +310,7 @@ __global__ __launch_bounds__(VW_TPB) void k_kc_scatter(const float* __restrict__
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int64_t r0 = (int64_t)blockIdx.x * VW_TPB, r = r0 + tid;
     const bool f = r < total && keep[r];
-    const unsigned long long bal = __ballot(f);
-    if (lane == 0) s_wsum[wv] = __popcll(bal);
-    __syncthreads();
-    int pos = base[blockIdx.x] + __popcll(bal & ((1ull << lane) - 1ull));
-    for (int q = 0; q < wv; ++q) pos += s_wsum[q];
+    const int pos = base[blockIdx.x] + wg_rank<VW_WAVES>(f, s_wsum).rank;
     s_pos[tid] = f ? pos : -1;
     if (f) {
         const float* a = keys + 4 * r;
@@ -360,11 +337,8 @@ int check_cull(const char* fn, int32_t n_frames, int32_t view_count, const mvs_c
     if ((int64_t)n_frames * view_count > 0x7ffffffeLL) return bad(fn, "too many lists");
     if (!off || !out_off) return bad(fn, "key_offsets / out_offsets is NULL");
     if (!tex || !depths) return bad(fn, "tex or depths is NULL");
-    if (off[0] != 0) return bad(fn, "key_offsets must start at 0");
     const int nl = n_frames * view_count;
-    for (int l = 0; l < nl; ++l)
-        if (off[l + 1] < off[l]) return bad(fn, "key_offsets must ascend");
-    if (off[nl] >= 0x7fffffffLL) return bad(fn, "more than 2^31 - 1 key points");
+    if ((rc = check_offsets(fn, "key_offsets", off, nl, 0x7fffffffLL))) return rc;
     if (off[nl] > 0 && (!keys || !out_keys)) return bad(fn, "keys / out_keys is NULL");
     if (descs && !out_descs) return bad(fn, "descs given without out_descs");
     return MVS_OK;

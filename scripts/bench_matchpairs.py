@@ -1,8 +1,8 @@
 """Times the match-filter cascade of one sequence pair at the shape of `main -a 1` (16 x 16 frame pairs of 640 x 480 images, 5
 generated views per frame, about 3 000 raw matches per pair):
 
-  (a) the loop that existed before: mvs_match_filter once per frame pair (stages 1 and 3 on the host, both base images uploaded
-      and the stream synchronised at every call);
+  (a) the loop that existed before: mvs_match_filter once per frame pair (the stage-1 rule on the host, then the cascade kernel of
+      (b) as its 1 x 1 case; the keys and both base images uploaded and the stream synchronised at every call);
   (b) mvs_match_filter_pairs: all 256 pairs in one call (matchpairs.hip; every stack uploaded once);
   (c) mvs_match_filter_pairs_dev: the same with the stacks already in HBM.
 

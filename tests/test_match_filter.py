@@ -81,3 +81,33 @@ def test_gpu_cascade_matches_oracle(oracle):
             assert np.array_equal(gc, oc) and np.array_equal(g, o)
     g, gc = processor.MatchFilter(np.empty((0, 6), np.int32), *scene()[1:], WIN, 6.0, 5)
     assert len(g) == 0 and not gc.any()
+
+
+@pytest.mark.gpu
+def test_gpu_one_pair_entry_on_the_special_buckets(oracle, monkeypatch):
+    """mvs_match_filter runs the batched cascade as its 1 x 1 case: the buckets of tests/test_gpu_match_pairs.py that the batched
+    entry is tested on go through the one-pair entry, each bit for bit (matches and the three stage sizes) against the oracle."""
+    from multiviewstitch_amd import _lib, processor
+    from tests import test_gpu_match_pairs as P
+    raw, tex1, valid1, tex2, valid2, imgs1, imgs2 = P.cascade_inputs()
+
+    def one(k, win, ssd_err, interval):
+        i, j = divmod(k, P.N2)
+        got, cnt = processor.MatchFilter(raw[i][j], tex1[i], valid1[i], tex2[j], valid2[j], imgs1[i], imgs2[j], win, ssd_err, interval)
+        want, wcnt = P.cascade_expected(win, ssd_err, interval)[i][j]
+        print("bucket", k, "win", win, "raw", len(raw[i][j]), "stage sizes", tuple(cnt), "oracle", tuple(wcnt))
+        assert np.array_equal(cnt, wcnt) and np.array_equal(got, want), (k, win)
+        return wcnt
+
+    for k in (P.EMPTY, P.OUTSIDE, P.REPEATED):
+        one(k, WIN, 6.0, 5)
+    assert one(P.LARGE, WIN, 6.0, 5)[0] > 4096                      # more keys than the LDS holds: sorted in the global workspace
+    assert one(P.PLAIN[0], 0, 6.0, 5)[1] > 10                       # ssd_win = 0: one-pixel windows, nothing touches a border
+    monkeypatch.setenv("MVS_MATCH_PAIRS_LDS_CAP", "256")            # a plain 1 000-match bucket through the workspace path too
+    assert one(P.PLAIN[0], WIN, 6.0, 5)[0] > 256
+    monkeypatch.delenv("MVS_MATCH_PAIRS_LDS_CAP")
+    bad = raw[0][0].copy()
+    bad[7, 0] = VIEWS                                                # view1 = view_count
+    with pytest.raises(_lib.MvsError) as e:
+        processor.MatchFilter(bad, tex1[0], valid1[0], tex2[0], valid2[0], imgs1[0], imgs2[0], WIN, 6.0, 5)
+    assert e.value.code == -1

@@ -1,15 +1,18 @@
-"""Host side of the sequence-pair entries (include/mvs.h mvs_match_filter_pairs(_dev), mvs_sequence_pair_srt): the symbols, the
-layout of mvs_seq_pair_params, and the argument checks, which run before any device is needed."""
+"""Host side of the sequence-pair entries (include/mvs.h mvs_match_filter(_pairs(_dev)), mvs_sequence_pair_srt): the symbols, the
+layout of mvs_seq_pair_params, the argument checks, which run before any device is needed, and the host code the entries share
+(csrc/frontend_dev.h mp_stage1, csrc/engine.h check_offsets) as a stand-alone program under the address and undefined-behaviour
+sanitizers."""
 import ctypes as C
 import os
 import re
+import subprocess
 
 import numpy as np
 
 from multiviewstitch_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-E_INVALID = -1
+E_INVALID, E_NO_DEVICE = -1, -4
 W, H, VIEWS, N1, N2 = 8, 6, 2, 2, 1
 
 
@@ -105,3 +108,44 @@ def test_sequence_pair_srt_rejects_bad_arguments_without_a_device():
         assert _srt_call(**kw) == E_INVALID, kw
         assert _lib.lib().mvs_last_error()
     assert _srt_call() != E_INVALID                                  # every optional output NULL
+
+
+def _one_pair_call(**kw):
+    npx = W * H
+    a = dict(raw=np.zeros((3, 6), np.int32), tex1=np.zeros((VIEWS, npx), np.int32), valid1=np.ones(npx, np.uint8),
+             tex2=np.zeros((VIEWS, npx), np.int32), valid2=np.ones(npx, np.uint8), img1=np.zeros((H, W, 3), np.uint8),
+             img2=np.zeros((H, W, 3), np.uint8), prm=_lib.CMatchFilterParams(W, H, VIEWS, 1, 6.0, 2, 0), out=np.zeros((3, 4), np.int32),
+             n_out=C.c_int64(-7), cnt=np.zeros(3, np.int64))
+    a.update(kw)
+    P = _lib.ptr
+    rc = _lib.lib().mvs_match_filter(P(a["raw"]), len(a["raw"]), P(a["tex1"]), P(a["valid1"]), P(a["tex2"]), P(a["valid2"]), P(a["img1"]),
+                                     P(a["img2"]), C.byref(a["prm"]), P(a["out"]), C.byref(a["n_out"]), P(a["cnt"]))
+    return rc, a["n_out"].value
+
+
+def test_match_filter_checks_arguments_then_view_indices_then_the_device():
+    """the order mvs_match_filter keeps: bad arguments, then a view index out of range, then the missing device"""
+    for kw in [dict(tex1=None), dict(valid1=None), dict(tex2=None), dict(valid2=None), dict(img1=None), dict(img2=None), dict(out=None),
+               dict(prm=_lib.CMatchFilterParams(65536, H, VIEWS, 1, 6.0, 2, 0)), dict(prm=_lib.CMatchFilterParams(W, 65536, VIEWS, 1, 6.0, 2, 0))]:
+        assert _one_pair_call(**kw) == (E_INVALID, -7), kw
+        assert _lib.lib().mvs_last_error()
+    bad_view = np.zeros((3, 6), np.int32)
+    bad_view[2, 0] = VIEWS                                           # view1 = view_count, everything else valid
+    assert _one_pair_call(raw=bad_view) == (E_INVALID, -7)
+    assert b"view index out of range" in _lib.lib().mvs_last_error()
+    if _lib.device_count() == 0:
+        assert _one_pair_call() == (E_NO_DEVICE, -7)
+    else:                                                            # (the suite on a GPU machine: the three matches are one key, at a border)
+        assert _one_pair_call() == (0, 0)
+
+
+def test_the_shared_host_rules_under_the_sanitizers(tmp_path):
+    """tests/frontend_rules.cpp: mp_stage1 at the edge pixels and at tex = -1, check_offsets on an empty list, a descending pair and
+    the limit value — host code, compiled without the device pass and run as a program of its own"""
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    exe = str(tmp_path / "frontend_rules")
+    subprocess.check_call([hipcc, "-x", "hip", "--offload-host-only", "-no-hip-rt", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-Xarch_host",
+                           "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all", "-I",
+                           os.path.join(ROOT, "multiviewstitch_amd", "csrc"), os.path.join(ROOT, "tests", "frontend_rules.cpp"), "-o", exe])
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert run.returncode == 0 and "frontend rules ok" in run.stdout, run.stdout + run.stderr

@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define MVS_ABI_VERSION 4   /* 3: tracing hook, mvs_comm_set_exchange, view-sharded RemoveGround / LocalAlignmentCore; 4: mvs_deform_group_*, mvs_align_dev, mvs_retain_connect_region_dev / mvs_remove_ground_dev / mvs_part_recog_dev, mvs_trim (additive); mvs_local_alignment_core_sharded takes the rank; still 4, additive: mvs_visibility_cull(_dev), mvs_mesh_vertex_normals(_dev), mvs_processor_stitch_points / _cull_model (mvs_io.h), mvs_render_depth_views(_dev), mvs_processor_render (mvs_io.h), mvs_match_filter_pairs(_dev), mvs_sequence_pair_srt */
+#define MVS_ABI_VERSION 4   /* 3: tracing hook, mvs_comm_set_exchange, view-sharded RemoveGround / LocalAlignmentCore; 4: mvs_deform_group_*, mvs_align_dev, mvs_retain_connect_region_dev / mvs_remove_ground_dev / mvs_part_recog_dev, mvs_trim (additive); mvs_local_alignment_core_sharded takes the rank; still 4, additive: mvs_visibility_cull(_dev), mvs_mesh_vertex_normals(_dev), mvs_processor_stitch_points / _cull_model (mvs_io.h), mvs_render_depth_views(_dev), mvs_processor_render (mvs_io.h), mvs_match_filter_pairs(_dev), mvs_sequence_pair_srt, mvs_gen_new_views(_dev), mvs_keypoint_cull(_dev), mvs_sift_match, mvs_sift_match_lists(_dev) */
 
 enum mvs_status {
     MVS_OK            =  0,
@@ -361,6 +361,55 @@ int mvs_keypoint_cull_dev(int32_t n_frames, int32_t view_count, const mvs_camera
                           const float* descs_dev, const int32_t* tex_dev, const float* depths_dev, double min_dsp, double max_dsp,
                           const uint8_t* mask_dev, uint8_t* keep_dev, int64_t* out_offsets, float* out_keys_dev, float* out_descs_dev,
                           void* hip_stream);
+
+/* FeatureProc::MatchFeature (R/FeatureProc/FeatureProc.cpp:77-130, call site R/Processor/Processor.cpp:634): SiftMatchGPU's descriptor
+ * matching for ALL list pairs of two adjacent sequences in one launch set.  The input is what mvs_keypoint_cull(_dev) writes — list
+ * l = frame * view_count + view owns the keys [key_offsets[l], key_offsets[l+1]) of keys[total][4] float32 {x, y, s, o} and of
+ * descs[total][128] float32 — and the output is what mvs_match_filter_pairs and mvs_sequence_pair_srt read: raw_offsets (n1*n2 + 1) and
+ * raw[total][6] = (view1,u1,v1,view2,u2,v2), bucketed by frame pair.
+ * SiftGPU's source is not part of the reference tree.  The rules below are RECALLED from SiftMatchGPU (its GLSL matcher) and NOT
+ * VERIFIED against it; they are this library's definition:
+ *   1. quantise    : q = (int)(512*d + 0.5) in float32, truncating; d <= 0 or NaN gives 0.  Deviation: a value above 255 saturates to
+ *                    255; SiftGPU's narrowing to unsigned char is believed to wrap.  (A unit-norm descriptor clamped at 0.2 stays
+ *                    below 0.498.)
+ *   2. cap         : only the first max_sift descriptors of a list take part (the reference constructs SiftMatchGPU(4096),
+ *                    FeatureProc.cpp:83);
+ *   3. score       : s(i,j) = sum_c q1[i][c]*q2[j][c], an exact integer (at most 128*255^2);
+ *   4. one direction (list A against list B), for every descriptor i of A: best = the largest score, bestidx = the LOWEST j that
+ *                    attains it; second = the largest score over j != bestidx, 0 when there is no other j; best == 0 gives no match;
+ *                    in double, dist = acos(min(best/262144.0, 1)) and dist2 likewise from second; m(i) = bestidx when
+ *                    dist < distmax and dist < ratiomax*dist2, else -1.  A tie for best never matches when ratiomax <= 1;
+ *   5. mutual best : for ascending i, (i,j) is a match when m12(i) = j >= 0 and m21(j) = i (SiftGPU's default);
+ *   6. raw row     : for list l1 of sequence 1 and l2 of sequence 2, (l1 % view_count, int(x1+0.5), int(y1+0.5), l2 % view_count,
+ *                    int(x2+0.5), int(y2+0.5)); the sum in double (FeatureProc.cpp:96 adds a double constant to the float), the
+ *                    conversion is the double->int rule of mvs_gen_new_views (NaN and out of range give INT_MIN);
+ *   7. buckets     : bucket k = (l1 / view_count)*n_frames2 + (l2 / view_count); inside a bucket l1 ascending, then l2 ascending,
+ *                    then i ascending, the reference's loop order (Processor.cpp:652-664).
+ * Every score is exact, so nothing here has a tolerance but the two acos of rule 4.
+ * mvs_sift_match is GetSiftMatch for ONE list pair in index form: match_buf (capacity min(n1,n2) x 2) receives (i,j), n_match their
+ * number; view_count is not read.  It runs the batched kernels as their 1 x 1 case.
+ * mvs_sift_match_lists: raw == NULL writes only raw_offsets and pair_counts (optional, [L1*L2], the matches of list pair l1*L2 + l2 with
+ * L = n_frames*view_count), so that the caller can size raw; a raw_capacity (rows) below the total gives MVS_E_INVALID_ARG after
+ * raw_offsets and pair_counts are written.
+ * MVS_E_INVALID_ARG, before a device is needed: offsets that do not ascend from 0, view_count < 1, max_sift < 1, a frame count < 1, a
+ * required pointer NULL, n_frames1*n_frames2 > 1000000. */
+typedef struct mvs_sift_match_params {
+    int32_t view_count;        /* ParamParser::view_count                                  */
+    int32_t max_sift;          /* 4096, FeatureProc.cpp:83                                 */
+    double  distmax, ratiomax; /* ParamParser::distmax / ratiomax                          */
+} mvs_sift_match_params;
+int mvs_sift_match(int64_t n1, const float* descs1 /*n1 x 128*/, int64_t n2, const float* descs2 /*n2 x 128*/,
+                   const mvs_sift_match_params* p, int32_t* match_buf /*capacity min(n1,n2) x 2*/, int64_t* n_match);
+int mvs_sift_match_lists(int32_t n_frames1, int32_t n_frames2, const mvs_sift_match_params* p, const int64_t* key_offsets1 /*L1+1*/,
+                         const float* keys1, const float* descs1, const int64_t* key_offsets2 /*L2+1*/, const float* keys2,
+                         const float* descs2, int64_t* raw_offsets /*n1*n2+1*/, int32_t* raw /*raw_capacity x 6, or NULL*/,
+                         int64_t raw_capacity, int64_t* pair_counts /*L1*L2 or NULL*/);
+/* keys and descriptors in HBM (16-byte aligned), exactly the out_keys_dev / out_descs_dev of mvs_keypoint_cull_dev, read in the order of
+ * hip_stream (may be NULL); the offsets and every output stay host arrays; returns with the work complete */
+int mvs_sift_match_lists_dev(int32_t n_frames1, int32_t n_frames2, const mvs_sift_match_params* p, const int64_t* key_offsets1,
+                             const float* keys1_dev, const float* descs1_dev, const int64_t* key_offsets2, const float* keys2_dev,
+                             const float* descs2_dev, int64_t* raw_offsets, int32_t* raw, int64_t raw_capacity, int64_t* pair_counts,
+                             void* hip_stream);
 
 /* Chain composition, Processor.cpp:819-823: (s0,R0,t0) <- (sk,Rk,tk) o (s0,R0,t0). */
 int mvs_srt_compose(double sk, const double* Rk, const double* tk,

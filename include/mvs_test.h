@@ -46,6 +46,12 @@ int mvs_test_heavy_count(mvs_deform_t h, int* n, int* flagged);
  * 8 pown, 9 pnh, 10 l2g, 11 hl2g, 12 lcol (int16), 13 gent, 14 gcol.  out == NULL: only *bytes. */
 int mvs_test_mesh_table(mvs_deform_t h, int what, void* out, int64_t* bytes);
 
+/* mvs_sift_match's scores for one list pair, apart from its thresholds (rules 3 and 4 of mvs_sift_match_lists): best, bestidx and
+ * second of every descriptor of list 1 against list 2 (the first min(n1, max_sift) entries of the *12 arrays) and of list 2 against
+ * list 1 (min(n2, max_sift) entries of the *21 arrays).  With an empty other list: best = 0, bestidx = -1, second = 0. */
+int mvs_test_sift_scores(int64_t n1, const float* descs1, int64_t n2, const float* descs2, int32_t max_sift, int32_t* best12, int32_t* idx12,
+                         int32_t* second12, int32_t* best21, int32_t* idx21, int32_t* second21);
+
 #ifdef __cplusplus
 }
 #endif

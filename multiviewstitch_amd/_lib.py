@@ -58,6 +58,11 @@ class CMatchFilterParams(C.Structure):
                 ("sample_interval", C.c_int32), ("reserved", C.c_int32)]
 
 
+class CSiftMatchParams(C.Structure):
+    """struct mvs_sift_match_params."""
+    _fields_ = [("view_count", C.c_int32), ("max_sift", C.c_int32), ("distmax", C.c_double), ("ratiomax", C.c_double)]
+
+
 class CSeqPairParams(C.Structure):
     """struct mvs_seq_pair_params."""
     _fields_ = [("filter", CMatchFilterParams), ("min_dsp", C.c_double), ("max_dsp", C.c_double), ("min_match_count", C.c_int32),
@@ -100,6 +105,9 @@ _SIGS = {
     "mvs_gen_new_views_dev": (C.c_int, [_I32, _VP, _VP, _I32, _I32, _D, _VP, _VP, _VP]),
     "mvs_keypoint_cull": (C.c_int, [_I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _D, _D, _VP, _VP, _VP, _VP, _VP]),
     "mvs_keypoint_cull_dev": (C.c_int, [_I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _D, _D, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "mvs_sift_match": (C.c_int, [_I64, _VP, _I64, _VP, _VP, _VP, _VP]),
+    "mvs_sift_match_lists": (C.c_int, [_I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP]),
+    "mvs_sift_match_lists_dev": (C.c_int, [_I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP]),
     "mvs_render_depth": (C.c_int, [_VP, _I64, _VP, _I64, _VP, C.c_float, C.c_float, _VP]),
     "mvs_render_depth_dev": (C.c_int, [_VP, _I64, _VP, _I64, _VP, C.c_float, C.c_float, _VP, _VP]),
     "mvs_render_depth_views": (C.c_int, [_VP, _I64, _VP, _I64, _I32, _VP, _VP, _VP, _VP, _VP, C.c_float, C.c_float, _VP]),
@@ -200,6 +208,7 @@ _SIGS = {
     "mvs_test_sweep_steps": (C.c_int, [_VP, _I32, _VP]),
     "mvs_test_heavy_count": (C.c_int, [_VP, _VP, _VP]),
     "mvs_test_mesh_table": (C.c_int, [_VP, _I32, _VP, _VP]),
+    "mvs_test_sift_scores": (C.c_int, [_I64, _VP, _I64, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP]),
 }
 EXPORTS = tuple(_SIGS)
 

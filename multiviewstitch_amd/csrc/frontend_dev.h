@@ -1,6 +1,7 @@
 // frontend_dev.h — the small pieces the units of the `main -a 1` front end share (stitch.hip, matchpairs.hip, views.hip): CheckRange,
 // the 8-bit grey conversion, the segment look-up of back-to-back lists, the stage-1 rule of the match filter (one body for the
-// kernel and for host code) and the workgroup ranking of an ordered compaction.
+// kernel and for host code), the workgroup ranking of an ordered compaction and the two scan steps that turn per-workgroup survivor
+// counts into places (views.hip's key-point cull, siftmatch.hip's pairing).
 #ifndef MVS_FRONTEND_DEV_H_
 #define MVS_FRONTEND_DEV_H_
 #include <hip/hip_runtime.h>
@@ -67,6 +68,47 @@ __device__ inline WgRank wg_rank(bool flag, int* s_wsum) {
 #pragma unroll
     for (int q = 0; q < WAVES; ++q) { if (q < wv) r.rank += s_wsum[q]; r.total += s_wsum[q]; }
     return r;
+}
+
+// The scan over the survivor counts of nb workgroups, run by ONE workgroup of WAVES waves: base[b] = survivors in the workgroups
+// before b, base[nb] = all survivors.
+template <int WAVES>
+__device__ inline void wg_scan_counts(const int32_t* __restrict__ cnt, int nb, int32_t* __restrict__ base) {
+    __shared__ int s_wsum[WAVES], s_carry;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    if (tid == 0) s_carry = 0;
+    __syncthreads();
+    for (int c0 = 0; c0 < nb; c0 += WAVES * 64) {
+        const int i = c0 + tid, v = i < nb ? cnt[i] : 0;
+        int x = v;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int t = __shfl_up(x, o, 64);
+            if (lane >= o) x += t;
+        }
+        if (lane == 63) s_wsum[wv] = x;
+        __syncthreads();
+        int woff = 0, tot = 0;
+#pragma unroll
+        for (int q = 0; q < WAVES; ++q) { if (q < wv) woff += s_wsum[q]; tot += s_wsum[q]; }
+        const int carry = s_carry;
+        if (i < nb) base[i] = carry + woff + x - v;
+        __syncthreads();
+        if (tid == 0) s_carry = carry + tot;
+        __syncthreads();
+    }
+    if (tid == 0) base[nb] = s_carry;
+}
+
+// The survivors in front of item r (of `total`, flagged in keep, counted per workgroup of tpb items into base[nb + 1] by the scan
+// above): where the compacted segment that starts at r begins
+__device__ inline int64_t survivors_before(int64_t r, int64_t total, const uint8_t* __restrict__ keep, const int32_t* __restrict__ base,
+                                           int nb, int tpb) {
+    if (r >= total) return base[nb];
+    const int64_t b = r / tpb;
+    int64_t acc = base[b];
+    for (int64_t q = b * tpb; q < r; ++q) acc += keep[q];
+    return acc;
 }
 #endif  // __HIPCC__
 

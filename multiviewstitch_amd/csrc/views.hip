@@ -265,42 +265,14 @@ __global__ __launch_bounds__(VW_TPB) void k_kc_decide(const float* __restrict__ 
 
 // base[b] = survivors in the blocks before b, base[nb] = all survivors; one workgroup
 __global__ __launch_bounds__(VW_TPB) void k_kc_scan(const int32_t* __restrict__ cnt, int nb, int32_t* __restrict__ base) {
-    __shared__ int s_wsum[VW_WAVES], s_carry;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    if (tid == 0) s_carry = 0;
-    __syncthreads();
-    for (int c0 = 0; c0 < nb; c0 += VW_TPB) {
-        const int i = c0 + tid, v = i < nb ? cnt[i] : 0;
-        int x = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int t = __shfl_up(x, o, 64);
-            if (lane >= o) x += t;
-        }
-        if (lane == 63) s_wsum[wv] = x;
-        __syncthreads();
-        int woff = 0, tot = 0;
-#pragma unroll
-        for (int q = 0; q < VW_WAVES; ++q) { if (q < wv) woff += s_wsum[q]; tot += s_wsum[q]; }
-        const int carry = s_carry;
-        if (i < nb) base[i] = carry + woff + x - v;
-        __syncthreads();
-        if (tid == 0) s_carry = carry + tot;
-        __syncthreads();
-    }
-    if (tid == 0) base[nb] = s_carry;
+    wg_scan_counts<VW_WAVES>(cnt, nb, base);
 }
 
 __global__ void k_kc_offsets(const int64_t* __restrict__ off, int nlists, int64_t total, const uint8_t* __restrict__ keep,
                              const int32_t* __restrict__ base, int nb, int64_t* __restrict__ out_off) {
     const int l = blockIdx.x * blockDim.x + threadIdx.x;
     if (l > nlists) return;
-    const int64_t r = off[l];
-    if (r >= total) { out_off[l] = base[nb]; return; }
-    const int64_t b = r / VW_TPB;
-    int acc = base[b];
-    for (int64_t q = b * VW_TPB; q < r; ++q) acc += keep[q];
-    out_off[l] = acc;
+    out_off[l] = survivors_before(off[l], total, keep, base, nb, VW_TPB);
 }
 
 __global__ __launch_bounds__(VW_TPB) void k_kc_scatter(const float* __restrict__ keys, const float* __restrict__ descs, int64_t total,

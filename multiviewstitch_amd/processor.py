@@ -2,7 +2,8 @@
 ``Processor::AlignmentSeq`` (:952-1105) through ``mvs_processor_stitch_points`` / ``mvs_processor_cull_model``;
 ``Processor::Render`` (:1140-1192) through ``mvs_processor_render`` and its batched render ``mvs_render_depth_views``; the loop
 over adjacent sequences of ``Processor::CalcSimilarityTransformationSeq`` (:629-826) through ``mvs_sequence_pair_srt``; its head (:524-600)
-through ``mvs_gen_new_views`` (Image3D::GenNewViews) and ``mvs_keypoint_cull`` (the background cull of the key points)."""
+through ``mvs_gen_new_views`` (Image3D::GenNewViews) and ``mvs_keypoint_cull`` (the background cull of the key points); the descriptor
+matching between them, FeatureProc::MatchFeature (R/FeatureProc/FeatureProc.cpp:77-130), through ``mvs_sift_match_lists``."""
 from __future__ import annotations
 
 import ctypes as C
@@ -281,6 +282,72 @@ def MatchFilter(raw, tex1, valid1, tex2, valid2, img1, img2, ssd_win: int, ssd_e
     return out[:n_out.value].copy(), cnt
 
 
+def MatchFeatureSingleView(descs1, descs2, distmax: float = 0.7, ratiomax: float = 0.8, max_sift: int = 4096) -> np.ndarray:
+    """SiftMatchGPU::GetSiftMatch for one list pair (R/FeatureProc/FeatureProc.cpp:77-101, in index form): descs [n, 128] float32.
+    -> [m, 2] int32 (i, j), the mutual best matches for ascending i (the rules: include/mvs.h, mvs_sift_match_lists)."""
+    d1, d2 = L.arr(descs1, np.float32).reshape(-1, 128), L.arr(descs2, np.float32).reshape(-1, 128)
+    prm = L.CSiftMatchParams(1, int(max_sift), float(distmax), float(ratiomax))
+    buf = np.empty((max(1, min(len(d1), len(d2))), 2), np.int32)
+    n = C.c_int64()
+    L.check(L.lib().mvs_sift_match(len(d1), L.ptr(d1), len(d2), L.ptr(d2), C.byref(prm), L.ptr(buf), C.byref(n)))
+    return buf[:n.value].copy()
+
+
+def _key_lists(keys, descs, offsets, what):
+    """per-list arrays -> (offsets, flat keys, flat descs, device form?); flat device tensors with their offsets pass through"""
+    if offsets is not None:
+        off = L.arr(offsets, np.int64).reshape(-1)
+        if _is_dev(keys) != _is_dev(descs):
+            raise L.MvsError(-1, f"{what}: keys and descs must both be tensors on the GPU or both arrays")
+        if not _is_dev(keys):
+            keys, descs = L.arr(keys, np.float32).reshape(-1, 4), L.arr(descs, np.float32).reshape(-1, 128)
+        if len(off) < 1 or len(keys) < off[-1] or len(descs) < off[-1]:
+            raise L.MvsError(-1, f"{what}: keys / descs must hold key_offsets[-1] rows")
+        return off, keys, descs, _is_dev(keys)
+    if len(keys) != len(descs):
+        raise L.MvsError(-1, f"{what}: one descriptor list per key list")
+    kl = [L.arr(k, np.float32).reshape(-1, 4) for k in keys]
+    dl = [L.arr(d, np.float32).reshape(-1, 128) for d in descs]
+    if any(len(k) != len(d) for k, d in zip(kl, dl)):
+        raise L.MvsError(-1, f"{what}: a key list and its descriptor list differ in length")
+    off = np.zeros(len(kl) + 1, np.int64)
+    off[1:] = np.cumsum([len(k) for k in kl])
+    flat_k = np.concatenate(kl) if len(kl) else np.zeros((0, 4), np.float32)
+    flat_d = np.concatenate(dl) if len(dl) else np.zeros((0, 128), np.float32)
+    return off, np.ascontiguousarray(flat_k), np.ascontiguousarray(flat_d), False
+
+
+def MatchFeature(keys1, descs1, keys2, descs2, view_count: int, distmax: float = 0.7, ratiomax: float = 0.8, max_sift: int = 4096,
+                 stream: int | None = None, key_offsets1=None, key_offsets2=None):
+    """FeatureProc::MatchFeature for two adjacent sequences (R/FeatureProc/FeatureProc.cpp:114-130, call site Processor.cpp:634): every
+    list of the first sequence against every list of the second in one call.  keys[l] = [k_l, 4] float32 {x, y, s, o} and descs[l] =
+    [k_l, 128] float32 of list l = frame * view_count + view, as ``CullKeypoints`` returns them — or, with ``key_offsets1`` /
+    ``key_offsets2`` (int64 [lists + 1]), the flat arrays of ``KeypointCull``: numpy arrays, or contiguous float32 torch tensors on
+    the GPU (the device form; ``stream`` is then the HIP stream that produced them).
+    -> raw[i][j] = (n_ij, 6) int32 (view1, u1, v1, view2, u2, v2) between frame i of the first and frame j of the second sequence:
+    the ``raw`` of ``MatchFilterPairs`` and ``SequencePairSRT``."""
+    vc = int(view_count)
+    off1, k1, d1, dev1 = _key_lists(keys1, descs1, key_offsets1, "sequence 1")
+    off2, k2, d2, dev2 = _key_lists(keys2, descs2, key_offsets2, "sequence 2")
+    if dev1 != dev2:
+        raise L.MvsError(-1, "both sequences must be in the same form")
+    if vc < 1 or (len(off1) - 1) % vc or (len(off2) - 1) % vc:
+        raise L.MvsError(-1, "need view_count >= 1 and view_count lists per frame")
+    n1, n2 = (len(off1) - 1) // vc, (len(off2) - 1) // vc
+    prm = L.CSiftMatchParams(vc, int(max_sift), float(distmax), float(ratiomax))
+    if dev1:
+        ptrs = [_dev_ptr(a, "float32", w) for a, w in ((k1, "keys"), (d1, "descs"), (k2, "keys"), (d2, "descs"))]
+        fn, tail = L.lib().mvs_sift_match_lists_dev, (L.ptr(stream),)
+    else:
+        ptrs = [L.ptr(a) for a in (k1, d1, k2, d2)]
+        fn, tail = L.lib().mvs_sift_match_lists, ()
+    roff = np.zeros(max(1, n1 * n2) + 1, np.int64)
+    cap = int(min(np.minimum(np.diff(off1), int(max_sift)).sum() * (len(off2) - 1), np.minimum(np.diff(off2), int(max_sift)).sum() * (len(off1) - 1)))
+    raw = np.empty((max(1, cap), 6), np.int32)                           # a list pair cannot hold more matches than its shorter list
+    L.check(fn(n1, n2, C.byref(prm), L.ptr(off1), ptrs[0], ptrs[1], L.ptr(off2), ptrs[2], ptrs[3], L.ptr(roff), L.ptr(raw), len(raw), None, *tail))
+    return [[raw[roff[i * n2 + j]:roff[i * n2 + j + 1]].copy() for j in range(n2)] for i in range(n1)]
+
+
 def _raw_table(raw, n1, n2):
     """raw[i][j] = (n_ij, 6) int32 -> (offsets int64[n1*n2 + 1], all rows back to back), pair k = i*n2 + j."""
     flat = [L.arr(raw[i][j], np.int32).reshape(-1, 6) for i in range(n1) for j in range(n2)]
@@ -361,16 +428,21 @@ def CalcSimilarityTransformationSeq(sequences, params: dict, state, srt_txt=None
     """The loop over adjacent sequences of Processor::CalcSimilarityTransformationSeq (R/Processor/Processor.cpp:629-826) and the chain
     AlignmentSeq makes of it (:851-871).  ``sequences[k]`` = dict(cameras, depths, tex, imgs) of sequence k, plus ``raw`` (raw[i][j],
     the matches towards sequence k + 1) for every sequence but the last; ``params`` = the keyword arguments of ``SequencePairSRT``
-    (ssd_win, ssd_err, sample_interval, min_dsp, max_dsp, ...).  One ``SequencePairSRT`` per adjacent pair with ONE rand() stream
+    (ssd_win, ssd_err, sample_interval, min_dsp, max_dsp, ...).  A sequence without ``raw`` but with ``keys`` and ``descs`` (per-list
+    arrays, as ``CullKeypoints`` returns them; the next sequence must have them too) gets its ``raw`` from ``MatchFeature``, whose
+    ``distmax``, ``ratiomax`` and ``max_sift`` are then taken out of ``params`` (:634).  One ``SequencePairSRT`` per adjacent pair with ONE rand() stream
     through all of them: ``state`` is the srand seed — an int, or a one-element uint32 numpy array that receives the advanced state.
     After pair k every earlier entry is composed with it (:819-823); identity is appended for the last sequence (:851-853);
     ``srt_txt`` (a path) writes the chain as SRT.txt (:855-871).
     -> (scales [n], Rs [n, 3, 3], ts [n, 3], select_frames [(frm_idx1, frm_idx2)] per pair): the input of ``StitchPointSets``."""
     st = int(np.asarray(state).reshape(-1)[0])
+    params = dict(params)
+    match = {k: params.pop(k) for k in ("distmax", "ratiomax", "max_sift") if k in params}
     scales, Rs, ts, select = [], [], [], []
     for k in range(len(sequences) - 1):
         a, b = sequences[k], sequences[k + 1]
-        r = SequencePairSRT(a["cameras"], b["cameras"], a["depths"], b["depths"], a["raw"], a["tex"], b["tex"], a["imgs"], b["imgs"],
+        raw = a["raw"] if "raw" in a else MatchFeature(a["keys"], a["descs"], b["keys"], b["descs"], int(np.asarray(a["tex"]).shape[1]), **match)
+        r = SequencePairSRT(a["cameras"], b["cameras"], a["depths"], b["depths"], raw, a["tex"], b["tex"], a["imgs"], b["imgs"],
                             state=st, **params)
         st = r["state"]
         select.append((r["frm_idx1"], r["frm_idx2"]))

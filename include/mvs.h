@@ -411,6 +411,87 @@ int mvs_sift_match_lists_dev(int32_t n_frames1, int32_t n_frames2, const mvs_sif
                              const float* descs2_dev, int64_t* raw_offsets, int32_t* raw, int64_t raw_capacity, int64_t* pair_counts,
                              void* hip_stream);
 
+/* FeatureProc::DetectFeature (R/FeatureProc/FeatureProc.cpp:14-75,103-112, call site R/Processor/Processor.cpp:562): SIFT keys and
+ * descriptors of ALL lists of a call in one launch set.  List l = frame * view_count + view is raster l of imgs (n_lists x h x w x 3
+ * bytes, exactly the `views` of mvs_gen_new_views), the order mvs_keypoint_cull expects; the outputs are its inputs: key_offsets
+ * (n_lists + 1, ascending from 0), keys[total][4] float32 {x, y, s, o} and descs[total][128] float32.
+ * SiftGPU's source is not part of the reference tree.  The rules below are RECALLED from SiftGPU and Lowe's method and NOT VERIFIED
+ * against SiftGPU; they are this library's definition.  Rules 1-6 use float32 + - * / only, each in the stated order (the library is
+ * built with -ffp-contract=off); the transcendentals they need (the taps) are evaluated on the host in double.
+ *   1. grey      : a pixel in the margin (x < int(w*hl), x >= w - int(w*hr), y < int(h*vl), y >= h - int(h*vr); the double -> int
+ *                  rule of mvs_gen_new_views; FeatureProc.cpp:28-43) is black; I = (float)g / 255.0f with g = the 8-bit grey of
+ *                  mvs_match_filter (4899, 9617, 1868 on the channels in memory order, + 8192, >> 14).
+ *   2. base      : first_octave 0: U = I (W0 = w, H0 = h).  first_octave -1: U is 2w x 2h; U[2y][2x] = I[y][x]; an odd column of an
+ *                  even row is 0.5f * (a + b), a its left neighbour and b the sample right of that, clamped to the last one; an odd
+ *                  row is 0.5f * (a + b) of the even rows above and below (the one below clamped to the last even row).
+ *   3. Gaussian  : for sigma (double): r = (int)ceil(4 sigma); taps k[i] = exp(-i^2 / (2 sigma^2)), i = -r..r, in double, divided by
+ *                  their sum taken over ascending i, rounded to float32.  Rows first, then the columns of the row result; a pass is
+ *                  acc = k[-r] * p[-r], then acc = acc + k[i] * p[i] for ascending i; samples outside replicate the border.
+ *   4. pyramid   : n_oct = max(1, floor(log2(min(W0, H0))) - 3) octaves; octave o is W0 >> o by H0 >> o.  S + 3 Gaussian levels each
+ *                  (S = dog_levels), sigma_l = sigma0 * 2^(l/S) in double.  Level 0 of the first octave is U blurred by
+ *                  sqrt(sigma0^2 - (sigma_in * 2^-first_octave)^2); level l is level l - 1 blurred by sqrt(sigma_l^2 - sigma_(l-1)^2);
+ *                  level 0 of the next octave is level S at the even pixels (x, y) <- (2x, 2y).
+ *   5. extremum  : d[l] = g[l+1] - g[l], never stored.  For levels l = 1..S and pixels 1 <= xi <= W - 2, 1 <= yi <= H - 2: v = d[l][yi][xi]
+ *                  is a candidate when |v| > T, T = dog_threshold / (float)S, and v is strictly above or strictly below all 26
+ *                  neighbours in d[l-1..l+1].  A tie gives no key.
+ *   6. refinement: on the 27 values D[s][y][x] around the candidate, central differences: g = 0.5f * (D+ - D-); dxx = (D+ + D-) - 2v;
+ *                  dxy = 0.25f * ((D++ - D-+) - (D+- - D--)) (likewise xs, ys).  Kept when det2 = dxx*dyy - dxy*dxy > 0 and
+ *                  (tr*tr)*e < ((e+1)*(e+1))*det2 with tr = dxx + dyy, e = edge_threshold.  ONE solve of H delta = -g by Cramer's rule
+ *                  (the order of operations is that of sift_refine, csrc/sift_rules.h, the one body host and device share); dropped
+ *                  when the determinant is 0 or any |delta| >= 1, and when |v + 0.5f * ((gx*dx + gy*dy) + gs*ds)| <= T.
+ *                  x = ((xi + dx) + 0.5f) * step, y likewise, step = 2^octave (0.5 for the doubled octave): the top-left pixel centre
+ *                  is (0.5, 0.5), SiftGPU's default.  sigma_oct = sigma0 * exp2f((l + ds) / S), s = sigma_oct * step.  Then the filter
+ *                  of FeatureProc.cpp:53-57 drops x < left || x > right || y < top || y > bottom (left = int(w*hl), right =
+ *                  w - int(w*hr), ...).
+ *   7. orientation: on g[l] of the key's octave, the pixels (xi + dx, yi + dy), |dx|, |dy| <= R = (int)(3 * sw + 0.5f), sw = 1.5f *
+ *                  sigma_oct, that have all four neighbours.  gx = g[x+1] - g[x-1], gy likewise; vote = exp(-((dx - delta_x)^2 +
+ *                  (dy - delta_y)^2) / (2 sw^2)) * sqrt(gx^2 + gy^2); fb = atan2(gy, gx) (in [0, 2pi)) * 36 / 2pi - 0.5; the vote is
+ *                  split linearly between bins floor(fb) and floor(fb) + 1 (mod 36).  EVERY vote of rules 7 and 8 is quantised to
+ *                  (uint64)(vote * 2^24 + 0.5f) and the bins are integer sums: a histogram does not depend on the order of the
+ *                  votes.  h = (float)sum / 2^24, then 6 passes of h[b] = ((h[b-1] + h[b]) + h[b+1]) / 3.0f (circular).  A peak is a
+ *                  bin strictly above both neighbours and >= 0.8f * max; its angle is ((b + 0.5f * (hm - hp) / ((hm - 2 h) + hp)) +
+ *                  0.5f) * (2pi / 36), wrapped into [0, 2pi).  The max_orient largest peaks are kept (equal peaks: the lower bin
+ *                  first); a candidate without a peak gives no key.
+ *   8. descriptor: 4 x 4 cells of 8 bins on g[l]; cell width m = 3 * sigma_oct.  For the pixels with |dx|, |dy| <= (int)(m * 3.5355339f)
+ *                  + 2 that have all four neighbours: (nx, ny) = the offset from the key rotated by -o and divided by m; fx = nx +
+ *                  1.5, fy = ny + 1.5 (samples outside (-1, 4) are skipped); gradient g = 0.5f * central difference; vote = |g| *
+ *                  exp(-(nx^2 + ny^2) / 8) (a Gaussian of 2 cells); ft = ((atan2(gy, gx) - o) mod 2pi) * 8 / 2pi; the vote is split
+ *                  trilinearly between the cells floor(fx), floor(fx) + 1 (those in 0..3), likewise y, and the bins floor(ft),
+ *                  floor(ft) + 1 (mod 8); entry ((cell_y * 4 + cell_x) * 8 + bin).  d = (float)sum / 2^24; d /= (float)sqrt(sum of d^2
+ *                  in double over ascending index) when that is positive; d = min(d, 0.2f); normalised once more the same way.
+ *   9. order     : within a list octave ascending, level ascending, yi ascending, xi ascending, then a candidate's orientations by
+ *                  descending peak, then ascending bin.  The first max_features keys of a list are kept.  No list depends on another.
+ * A total above `capacity` (rows) gives MVS_E_INVALID_ARG after key_offsets is written, so that the caller can size the outputs.
+ * Scratch comes from the stream-ordered pool; lists are processed in chunks so that the pyramids, base images and candidate flags of a
+ * chunk, with the per-workgroup counts and places of its compaction (8 bytes per 256 items), stay below max(512 MiB, what ONE list
+ * needs: 4 * (W0*H0 + sum over octaves of (S+3)*W*H) + (1 + 8/256) * S * sum of W*H bytes, rounded up), whatever n_lists is.  On top
+ * come the tap table (at most 4 * (S+3) * 103 bytes), 4 bytes per list of a chunk, and the candidate tables (64 bytes per candidate
+ * and 8 bytes per key of a chunk).
+ * MVS_E_INVALID_ARG, before a device is needed: a NULL pointer, n_lists < 1, w or h below 8 or above 65535, first_octave outside
+ * {-1, 0}, dog_levels outside 1..5, max_orient outside 1..4, max_features < 1, a margin ratio outside [0, 1), hl + hr >= 1, vl + vr
+ * >= 1, a float parameter that is not finite, dog_threshold < 0, edge_threshold <= 0, sigma0 <= 0, sigma_in < 0, sigma0 not above
+ * sigma_in * 2^-first_octave, a blur radius above 51 (sigma0 too large for dog_levels), capacity < 0, an image whose pyramid has
+ * 2^31 - 1 or more (octave, level, pixel) items, S * sum over octaves of W*H ("image too large": w = h = 65535 doubled is one), and
+ * for mvs_sift_detect_dev a keys_dev or descs_dev that is not 16-byte aligned. */
+typedef struct mvs_sift_params {
+    int32_t first_octave;    /* -1: FeatureProc.cpp:20 "-fo -1"; 0 also accepted            */
+    int32_t dog_levels;      /* S = 3                                                        */
+    int32_t max_orient;      /* 2 orientations per extremum at most                          */
+    int32_t max_features;    /* per list, the first ones in output order; >= 1               */
+    float   dog_threshold;   /* 0.02 (compared as dog_threshold / S)                         */
+    float   edge_threshold;  /* 10                                                           */
+    float   sigma0, sigma_in;/* 1.6, 0.5                                                     */
+    double  hl, hr, vl, vr;  /* ParamParser::*_margin_ratio; 0 = no margin                   */
+} mvs_sift_params;
+/* the values in the comments above, max_features = INT32_MAX, no margins */
+void mvs_sift_default_params(mvs_sift_params* p);
+int mvs_sift_detect(int32_t n_lists, int32_t w, int32_t h, const uint8_t* imgs /*n_lists x h x w x 3*/, const mvs_sift_params* p,
+                    int64_t* key_offsets /*n_lists+1*/, float* keys /*capacity x 4*/, float* descs /*capacity x 128*/, int64_t capacity);
+/* images, keys and descriptors in HBM (keys and descs 16-byte aligned), in the order of hip_stream (may be NULL); key_offsets stays a
+ * host array; returns with the work complete */
+int mvs_sift_detect_dev(int32_t n_lists, int32_t w, int32_t h, const uint8_t* imgs_dev, const mvs_sift_params* p, int64_t* key_offsets,
+                        float* keys_dev, float* descs_dev, int64_t capacity, void* hip_stream);
+
 /* Chain composition, Processor.cpp:819-823: (s0,R0,t0) <- (sk,Rk,tk) o (s0,R0,t0). */
 int mvs_srt_compose(double sk, const double* Rk, const double* tk,
                     double* s0, double* R0, double* t0);

@@ -52,6 +52,17 @@ int mvs_test_mesh_table(mvs_deform_t h, int what, void* out, int64_t* bytes);
 int mvs_test_sift_scores(int64_t n1, const float* descs1, int64_t n2, const float* descs2, int32_t max_sift, int32_t* best12, int32_t* idx12,
                          int32_t* second12, int32_t* best21, int32_t* idx21, int32_t* second21);
 
+/* mvs_sift_detect's Gaussian level `level` (0..S+2) of octave `octave` for ONE image (rules 1-4): out receives ow x oh floats
+ * (out_floats = its capacity; too small gives MVS_E_INVALID_ARG with ow, oh set). */
+int mvs_test_sift_level(int32_t w, int32_t h, const uint8_t* img, const mvs_sift_params* p, int32_t octave, int32_t level, float* out,
+                        int64_t out_floats, int32_t* ow, int32_t* oh);
+
+/* mvs_sift_detect's candidates after rule 6 (the key filter included), before orientation, in the order of rule 9: cand_offsets
+ * (n_lists + 1), ci[total][4] = {octave, level, xi, yi}, cf[total][3] = {x, y, s}.  A total above capacity (rows) gives
+ * MVS_E_INVALID_ARG after cand_offsets is written. */
+int mvs_test_sift_candidates(int32_t n_lists, int32_t w, int32_t h, const uint8_t* imgs, const mvs_sift_params* p, int64_t* cand_offsets,
+                             int32_t* ci, float* cf, int64_t capacity);
+
 #ifdef __cplusplus
 }
 #endif

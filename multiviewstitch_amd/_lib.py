@@ -63,6 +63,13 @@ class CSiftMatchParams(C.Structure):
     _fields_ = [("view_count", C.c_int32), ("max_sift", C.c_int32), ("distmax", C.c_double), ("ratiomax", C.c_double)]
 
 
+class CSiftParams(C.Structure):
+    """struct mvs_sift_params."""
+    _fields_ = [("first_octave", C.c_int32), ("dog_levels", C.c_int32), ("max_orient", C.c_int32), ("max_features", C.c_int32),
+                ("dog_threshold", C.c_float), ("edge_threshold", C.c_float), ("sigma0", C.c_float), ("sigma_in", C.c_float),
+                ("hl", C.c_double), ("hr", C.c_double), ("vl", C.c_double), ("vr", C.c_double)]
+
+
 class CSeqPairParams(C.Structure):
     """struct mvs_seq_pair_params."""
     _fields_ = [("filter", CMatchFilterParams), ("min_dsp", C.c_double), ("max_dsp", C.c_double), ("min_match_count", C.c_int32),
@@ -108,6 +115,9 @@ _SIGS = {
     "mvs_sift_match": (C.c_int, [_I64, _VP, _I64, _VP, _VP, _VP, _VP]),
     "mvs_sift_match_lists": (C.c_int, [_I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP]),
     "mvs_sift_match_lists_dev": (C.c_int, [_I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP]),
+    "mvs_sift_default_params": (None, [_VP]),
+    "mvs_sift_detect": (C.c_int, [_I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _I64]),
+    "mvs_sift_detect_dev": (C.c_int, [_I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _I64, _VP]),
     "mvs_render_depth": (C.c_int, [_VP, _I64, _VP, _I64, _VP, C.c_float, C.c_float, _VP]),
     "mvs_render_depth_dev": (C.c_int, [_VP, _I64, _VP, _I64, _VP, C.c_float, C.c_float, _VP, _VP]),
     "mvs_render_depth_views": (C.c_int, [_VP, _I64, _VP, _I64, _I32, _VP, _VP, _VP, _VP, _VP, C.c_float, C.c_float, _VP]),
@@ -209,6 +219,8 @@ _SIGS = {
     "mvs_test_heavy_count": (C.c_int, [_VP, _VP, _VP]),
     "mvs_test_mesh_table": (C.c_int, [_VP, _I32, _VP, _VP]),
     "mvs_test_sift_scores": (C.c_int, [_I64, _VP, _I64, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "mvs_test_sift_level": (C.c_int, [_I32, _I32, _VP, _VP, _I32, _I32, _VP, _I64, _VP, _VP]),
+    "mvs_test_sift_candidates": (C.c_int, [_I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _I64]),
 }
 EXPORTS = tuple(_SIGS)
 

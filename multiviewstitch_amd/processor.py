@@ -3,7 +3,8 @@
 ``Processor::Render`` (:1140-1192) through ``mvs_processor_render`` and its batched render ``mvs_render_depth_views``; the loop
 over adjacent sequences of ``Processor::CalcSimilarityTransformationSeq`` (:629-826) through ``mvs_sequence_pair_srt``; its head (:524-600)
 through ``mvs_gen_new_views`` (Image3D::GenNewViews) and ``mvs_keypoint_cull`` (the background cull of the key points); the descriptor
-matching between them, FeatureProc::MatchFeature (R/FeatureProc/FeatureProc.cpp:77-130), through ``mvs_sift_match_lists``."""
+matching between them, FeatureProc::MatchFeature (R/FeatureProc/FeatureProc.cpp:77-130), through ``mvs_sift_match_lists``; the SIFT
+detection in front of the cull, FeatureProc::DetectFeature (:14-75,103-112), through ``mvs_sift_detect``."""
 from __future__ import annotations
 
 import ctypes as C
@@ -252,16 +253,86 @@ def CullKeypoints(cameras, depths, tex, keys, descs, min_dsp: float, max_dsp: fl
     return out_keys, ([r["descs"][o[i]:o[i + 1]].copy() for i in range(len(lists))] if descs is not None else None)
 
 
-def LoadSequenceModels(cameras, imgs, depths, view_count: int, axis: int, rot_angle: float) -> dict:
+def sift_params(**kw) -> L.CSiftParams:
+    """``mvs_sift_default_params`` (first_octave -1, 3 DoG levels, 2 orientations, thresholds 0.02 / 10, sigma 1.6 / 0.5, no margins,
+    no feature cap) with the given fields replaced; hl, hr, vl, vr are ParamParser's margin ratios."""
+    prm = L.CSiftParams()
+    L.lib().mvs_sift_default_params(C.byref(prm))
+    for k, v in kw.items():
+        if k not in dict(L.CSiftParams._fields_):
+            raise L.MvsError(-1, f"mvs_sift_params has no field {k}")
+        setattr(prm, k, v)
+    return prm
+
+
+def DetectFeature(views, params: L.CSiftParams | None = None, stream: int | None = None, capacity: int | None = None):
+    """FeatureProc::DetectFeature (R/FeatureProc/FeatureProc.cpp:14-75,103-112) for every raster of ``views`` [..., h, w, 3] uint8 in one
+    call (``mvs_sift_detect``; the rules: include/mvs.h).  Every leading index is a list, in memory order: the views of ``GenNewViews``
+    give list frame * view_count + view, what ``CullKeypoints`` and ``KeypointCull`` expect.
+    A numpy array -> (keys[l] = [k_l, 4] float32 {x, y, s, o}, descs[l] = [k_l, 128] float32).  A contiguous torch tensor on the GPU (the
+    device form; ``stream`` is then the HIP stream that produced it) -> (key_offsets int64 [lists + 1], keys [total, 4], descs [total, 128])
+    with keys and descs tensors on the same device: the flat form of ``KeypointCull`` and ``MatchFeature``.  ``capacity`` (rows) sizes
+    the first attempt; a call that finds more keys is repeated once with the right size."""
+    prm = params if params is not None else sift_params()
+    if len(views.shape) < 3 or views.shape[-1] != 3:
+        raise L.MvsError(-1, "views must be [..., h, w, 3]")
+    h, w = int(views.shape[-3]), int(views.shape[-2])
+    n = int(np.prod(views.shape[:-3], dtype=np.int64))
+    off = np.zeros(n + 1, np.int64)
+    dev = _is_dev(views)
+    if not dev:
+        views = L.arr(views, np.uint8)
+    cap = max(1, int(capacity) if capacity is not None else n * min(int(prm.max_features), 2048))
+    for attempt in range(2):
+        off[:] = -1
+        if dev:
+            import torch
+            keys = torch.empty((cap, 4), dtype=torch.float32, device=views.device)
+            descs = torch.empty((cap, 128), dtype=torch.float32, device=views.device)
+            rc = L.lib().mvs_sift_detect_dev(n, w, h, _dev_ptr(views, "uint8", "views"), C.byref(prm), L.ptr(off), L.ptr(int(keys.data_ptr())),
+                                             L.ptr(int(descs.data_ptr())), cap, L.ptr(stream))
+        else:
+            keys, descs = np.empty((cap, 4), np.float32), np.empty((cap, 128), np.float32)
+            rc = L.lib().mvs_sift_detect(n, w, h, L.ptr(views), C.byref(prm), L.ptr(off), L.ptr(keys), L.ptr(descs), cap)
+        if rc == -1 and attempt == 0 and off[-1] > cap:           # key_offsets holds the need
+            cap = int(off[-1])
+            continue
+        L.check(rc)
+        break
+    total = int(off[-1])
+    if dev:
+        return off, keys[:total], descs[:total]
+    return [keys[off[i]:off[i + 1]].copy() for i in range(n)], [descs[off[i]:off[i + 1]].copy() for i in range(n)]
+
+
+def DetectFeatureSingleView(img, params: L.CSiftParams | None = None):
+    """FeatureProc::DetectFeatureSingleView for one raster [h, w, 3] uint8 -> (keys [k, 4], descs [k, 128])."""
+    keys, descs = DetectFeature(L.arr(img, np.uint8)[None], params)
+    return keys[0], descs[0]
+
+
+def LoadSequenceModels(cameras, imgs, depths, view_count: int, axis: int, rot_angle: float, sift: L.CSiftParams | None = None,
+                       min_dsp: float | None = None, max_dsp: float | None = None, masks=None) -> dict:
     """The model loop of Processor::CalcSimilarityTransformationSeq for one sequence (R/Processor/Processor.cpp:524-547, LoadModel's
-    GenNewViews): -> dict(cameras, depths, tex, imgs, views), the ``sequences[k]`` entry of ``CalcSimilarityTransformationSeq`` minus
-    ``raw``, which stays the caller's SIFT matching on ``views``."""
+    GenNewViews): -> dict(cameras, depths, tex, imgs, views).  With ``sift`` (``sift_params(...)``; then ``min_dsp`` / ``max_dsp`` are
+    required, ``masks`` optional) the head of the function runs to its end (:562-600): ``DetectFeature`` on the generated views and
+    ``CullKeypoints`` on its keys; the result also holds ``keys`` and ``descs`` (per list), a complete ``sequences[k]`` entry from which
+    ``CalcSimilarityTransformationSeq`` makes ``raw`` itself.  Without ``sift`` the entry lacks ``raw`` (or ``keys`` / ``descs``), which
+    the caller then supplies from a SIFT of their own on ``views``.
+    This array form passes views, keys and descriptors through host memory between the three calls; a caller that wants them to stay in
+    HBM chains ``mvs_gen_new_views_dev``, ``mvs_sift_detect_dev`` and ``mvs_keypoint_cull_dev`` on one stream."""
     img = L.arr(imgs, np.uint8)
     d = L.arr(depths, np.float32)
     if len(d) != len(cameras):
         raise L.MvsError(-1, "one raster per camera")
     views, tex = GenNewViews(cameras, img, view_count, axis, rot_angle)
-    return dict(cameras=list(cameras), depths=d, tex=tex, imgs=img, views=views)
+    out = dict(cameras=list(cameras), depths=d, tex=tex, imgs=img, views=views)
+    if sift is not None:
+        if min_dsp is None or max_dsp is None:
+            raise L.MvsError(-1, "sift needs min_dsp and max_dsp for the key-point cull")
+        keys, descs = DetectFeature(views, sift)
+        out["keys"], out["descs"] = CullKeypoints(cameras, d, tex, keys, descs, min_dsp, max_dsp, masks)
+    return out
 
 
 def MatchFilter(raw, tex1, valid1, tex2, valid2, img1, img2, ssd_win: int, ssd_err: float, sample_interval: int):

@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define MVS_ABI_VERSION 4   /* 3: tracing hook, mvs_comm_set_exchange, view-sharded RemoveGround / LocalAlignmentCore; 4: mvs_deform_group_*, mvs_align_dev, mvs_retain_connect_region_dev / mvs_remove_ground_dev / mvs_part_recog_dev, mvs_trim (additive); mvs_local_alignment_core_sharded takes the rank; still 4, additive: mvs_visibility_cull(_dev), mvs_mesh_vertex_normals(_dev), mvs_processor_stitch_points / _cull_model (mvs_io.h), mvs_render_depth_views(_dev), mvs_processor_render (mvs_io.h), mvs_match_filter_pairs(_dev), mvs_sequence_pair_srt, mvs_gen_new_views(_dev), mvs_keypoint_cull(_dev), mvs_sift_match, mvs_sift_match_lists(_dev) */
+#define MVS_ABI_VERSION 4   /* 3: tracing hook, mvs_comm_set_exchange, view-sharded RemoveGround / LocalAlignmentCore; 4: mvs_deform_group_*, mvs_align_dev, mvs_retain_connect_region_dev / mvs_remove_ground_dev / mvs_part_recog_dev, mvs_trim (additive); mvs_local_alignment_core_sharded takes the rank; still 4, additive: mvs_visibility_cull(_dev), mvs_mesh_vertex_normals(_dev), mvs_processor_stitch_points / _cull_model (mvs_io.h), mvs_render_depth_views(_dev), mvs_processor_render (mvs_io.h), mvs_match_filter_pairs(_dev), mvs_sequence_pair_srt, mvs_gen_new_views(_dev), mvs_keypoint_cull(_dev), mvs_sift_match, mvs_sift_match_lists(_dev), mvs_sift_detect(_dev), mvs_point_sample(_dev), mvs_processor_point_sample (mvs_io.h) */
 
 enum mvs_status {
     MVS_OK            =  0,
@@ -491,6 +491,74 @@ int mvs_sift_detect(int32_t n_lists, int32_t w, int32_t h, const uint8_t* imgs /
  * host array; returns with the work complete */
 int mvs_sift_detect_dev(int32_t n_lists, int32_t w, int32_t h, const uint8_t* imgs_dev, const mvs_sift_params* p, int64_t* key_offsets,
                         float* keys_dev, float* descs_dev, int64_t capacity, void* hip_stream);
+
+/* ------------------------------------------------- point sampling (GeometryRec::RunPointSample) -- */
+/* The step between Processor::CheckConsistency and the stitch tail (R/Processor/Processor.cpp:933-949): the checked inverse-depth
+ * rasters of every sequence to the oriented points `x y z nx ny nz` of Rec/<name>.npts that mvs_processor_stitch_points reads.  GeoRec is a
+ * closed binary; its source is not part of the reference tree.  The rules below are not verified against GeoRec; they are this
+ * library's definition, chosen to give a meaning to every parameter GeometryRec::Init receives from config.txt (PtSampRds, NbrFrmNum,
+ * NbrFrmStep, MaxDspErr, MinConf, EdgeSzThres, MinDsp, MaxDsp).  startFrmIdx / endFrmIdx are 0 / size - 1 at the call site and are
+ * not parameters; maxPsDep / minPsDep belong to Poisson.
+ * Input: n_seq sequences; sequence k owns cams[cam_off[k] .. cam_off[k+1]) (cam_off as mvs_visibility_cull).  The frames of one
+ * sequence share one raster size; sequences may differ.  depths holds the float32 inverse-depth rasters of all cameras back to back in
+ * camera order.  All arithmetic is fp64 + - * / sqrt in the stated order (the library is built with -ffp-contract=off); every
+ * double -> int conversion is the rule of mvs_gen_new_views (truncation toward zero, INT_MIN when not representable); the camera maps
+ * are Camera's (R/Camera/Camera.cpp:40-72) in their operation order: world_from_img(c, u, v, z) = R^T ((u - cx) z / fx - t0,
+ * (v - cy) z / fy - t1, z - t2), img_from_world(c, P): Xc = R P + t (row sums left to right, then + t), u' = int(fx Xc.x / Xc.z + cx +
+ * 0.5), v' likewise.  A length is sqrt((x*x + y*y) + z*z), a dot product (x*x' + y*y') + z*z'.
+ * For frame f of a sequence of n frames, r = pt_samp_rds:
+ *   1. valid      : a pixel is valid when d = (double)raster[v][u] lies in [dsp_min, dsp_max]; its point is P = world_from_img(cam_f, u,
+ *                   v, 1.0 / d).
+ *   2. neighbours : pixel (u, v) needs 1 <= u <= w - 2, 1 <= v <= h - 2 and four valid axial neighbours: Pl, Pr at u -+ 1, Pu, Pd at
+ *                   v -+ 1.
+ *   3. edge, normal: z0 = 1.0 / d.  Dropped when |Pl - P| or |Pr - P| exceeds edge_sz_thres * (z0 / fabs(fx)), or |Pu - P| or |Pd - P|
+ *                   exceeds edge_sz_thres * (z0 / fabs(fy)).  a = Pr - Pl, b = Pd - Pu, nrm = a x b = (a.y*b.z - a.z*b.y, a.z*b.x -
+ *                   a.x*b.z, a.x*b.y - a.y*b.x), len its length; dropped unless len > 0; nrm is divided by len component by
+ *                   component.  With C = world_from_img(cam_f, 0, 0, 0.0), the camera centre, nrm is negated when nrm . (P - C) > 0.
+ *   4. agreement  : P agrees with frame g when Xc = R_g P + t_g has Xc.z > 0, (u', v') = img_from_world's result is inside the raster,
+ *                   dg = (double)raster_g[v'][u'] is valid by rule 1 and fabs(dg - 1.0 / Xc.z) <= max_dsp_err.
+ *   5. confidence : N(f) = { f + j * nbr_frm_step : j = +-1 .. +-nbr_frm_num } within [0, n); count = |N(f)|, agree = the g of N(f)
+ *                   that agree with P; the pixel passes when count == 0 or (double)agree >= min_conf * (double)count.
+ *   6. cells      : the raster is cut into r x r cells (partial cells at the right and bottom); the cell of (u, v) is (u / r, v / r).
+ *                   A cell's candidate is its pixel of lowest row-major index that passes rules 1, 2, 3 and 5; a cell without one
+ *                   has no candidate.
+ *   7. coverage   : frames are taken in ascending f.  A cell of frame f emits its candidate unless the cell is covered.  Every emitted
+ *                   point P then covers, in every later frame g > f of the sequence that agrees with P (rule 4), the cell (u' / r,
+ *                   v' / r).  Nothing covers a cell of an earlier frame; a sequence does not see another sequence.
+ *   8. order      : sequence-major, then frame ascending, then pixel index ascending.  Per emitted point: points[3], normals[3]
+ *                   (doubles, the layout of mvs_npts_write), frame (its frame within the sequence) and pixel (v * w + u), int32 each,
+ *                   both optional.  seq_offsets[n_seq + 1] (int64, host) brackets each sequence.
+ * A sequence without a camera emits nothing.  A total above `capacity` (rows) gives MVS_E_INVALID_ARG after seq_offsets is written, so
+ * that the caller can size the outputs.  The work is one launch for the candidates of all frames of all sequences, one launch per frame
+ * step of the longest sequence for rule 7, and an ordered compaction without atomics: two runs give the same bytes.
+ * Scratch comes from the stream-ordered pool: 5 bytes per cell of the call (the int32 candidate and the coverage byte; sum over the
+ * cameras of ceil(w / r) * ceil(h / r)), 8 bytes per 256 items of the compaction (h * ceil(w / r) items per camera, every camera rounded
+ * up to the largest), 140 bytes per camera and 52 bytes per sequence; the host form adds the rasters and the emitted rows.
+ * MVS_E_INVALID_ARG, before a device is needed: a NULL pointer other than frame / pixel, n_seq < 1, cam_off not ascending from 0, a
+ * camera with w or h <= 0 or fx or fy == 0, two raster sizes inside one sequence, w * h of a frame above 2^31 - 1, a parameter that is
+ * not finite, dsp_min <= 0 or dsp_min > dsp_max, max_dsp_err < 0, min_conf outside [0, 1], edge_sz_thres <= 0, pt_samp_rds < 1,
+ * nbr_frm_num < 0, nbr_frm_step < 1, capacity < 0, and a call of 2^31 or more cells (or too many workgroups for one launch). */
+typedef struct mvs_point_sample_params {
+    double  dsp_min, dsp_max;   /* MinDsp 0.0025, MaxDsp 0.3                                     */
+    double  max_dsp_err;        /* MaxDspErr 0.01                                                */
+    double  min_conf;           /* MinConf 0.9                                                   */
+    double  edge_sz_thres;      /* EdgeSzThres 4.0, in pixels of the frame                       */
+    int32_t pt_samp_rds;        /* PtSampRds 2: the side of a cell                               */
+    int32_t nbr_frm_num;        /* NbrFrmNum 2: neighbour frames on each side                    */
+    int32_t nbr_frm_step;       /* NbrFrmStep 1                                                  */
+    int32_t reserved;           /* 0                                                             */
+} mvs_point_sample_params;
+/* the config.txt values in the comments above */
+void mvs_point_sample_default_params(mvs_point_sample_params* p);
+int mvs_point_sample(int32_t n_seq, const int32_t* cam_off /*n_seq+1*/, const mvs_camera* cams, const float* depths,
+                     const mvs_point_sample_params* p, int64_t* seq_offsets /*n_seq+1*/, double* points /*capacity x 3*/,
+                     double* normals /*capacity x 3*/, int32_t* frame /*capacity, or NULL*/, int32_t* pixel /*capacity, or NULL*/,
+                     int64_t capacity);
+/* rasters and outputs in HBM, in the order of hip_stream (may be NULL); cam_off, cams and seq_offsets stay host arrays; returns with
+ * the work complete */
+int mvs_point_sample_dev(int32_t n_seq, const int32_t* cam_off, const mvs_camera* cams, const float* depths_dev,
+                         const mvs_point_sample_params* p, int64_t* seq_offsets, double* points_dev, double* normals_dev,
+                         int32_t* frame_dev, int32_t* pixel_dev, int64_t capacity, void* hip_stream);
 
 /* Chain composition, Processor.cpp:819-823: (s0,R0,t0) <- (sk,Rk,tk) o (s0,R0,t0). */
 int mvs_srt_compose(double sk, const double* Rk, const double* tk,

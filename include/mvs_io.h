@@ -95,6 +95,15 @@ int mvs_processor_cull_model(const char* model_obj, int32_t n_seq, const double*
 int mvs_processor_render(const char* deform_obj, const char* srt_txt, int32_t n_seq, const int32_t* cam_off, const mvs_camera* cams,
                          const char* result_dir, const char* const* seq_dirs, float znear, float zfar, int64_t* n_views_out);
 
+/* GeometryRec::RunPointSample on files (R/Processor/Processor.cpp:919-949; the rules: mvs_point_sample, this library's definition):
+ * for each sequence k read seq_dirs[k]/DATA/CHECK/_depth<i>.raw for its cameras i (mvs_depth_raw_read: the checked rasters that the file
+ * shuffle of :919-931 puts in front of GeoRec), sample all sequences in one call, and write seq_dirs[k]/Rec/PointSample.npts
+ * (mvs_npts_write), creating Rec/ as CreateDir does (a '/' is inserted after seq_dirs[k] when it lacks one).  npts_paths (may be NULL, and
+ * so may an entry): the file sequence k writes instead.  params may be NULL (defaults).  A missing or short raster is reported before
+ * anything is written.  n_points (n_seq, may be NULL) receives the rows written. */
+int mvs_processor_point_sample(int32_t n_seq, const char* const* seq_dirs, const int32_t* cam_off, const mvs_camera* cams,
+                               const mvs_point_sample_params* params, const char* const* npts_paths, int64_t* n_points);
+
 #ifdef __cplusplus
 }
 #endif

@@ -63,6 +63,12 @@ int mvs_test_sift_level(int32_t w, int32_t h, const uint8_t* img, const mvs_sift
 int mvs_test_sift_candidates(int32_t n_lists, int32_t w, int32_t h, const uint8_t* imgs, const mvs_sift_params* p, int64_t* cand_offsets,
                              int32_t* ci, float* cf, int64_t capacity);
 
+/* mvs_point_sample's candidate table of rule 6, before coverage (rule 7): cell_offsets (cameras + 1: the cells in front of every
+ * camera's frame, camera order) and cand[total] = per cell, row-major over ceil(h / r) x ceil(w / r), the candidate's pixel index or -1.
+ * A total above capacity (entries) gives MVS_E_INVALID_ARG after cell_offsets is written. */
+int mvs_test_point_sample_candidates(int32_t n_seq, const int32_t* cam_off, const mvs_camera* cams, const float* depths,
+                                     const mvs_point_sample_params* p, int64_t* cell_offsets, int32_t* cand, int64_t capacity);
+
 #ifdef __cplusplus
 }
 #endif

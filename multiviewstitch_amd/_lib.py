@@ -70,6 +70,13 @@ class CSiftParams(C.Structure):
                 ("hl", C.c_double), ("hr", C.c_double), ("vl", C.c_double), ("vr", C.c_double)]
 
 
+class CPointSampleParams(C.Structure):
+    """struct mvs_point_sample_params."""
+    _fields_ = [("dsp_min", C.c_double), ("dsp_max", C.c_double), ("max_dsp_err", C.c_double), ("min_conf", C.c_double),
+                ("edge_sz_thres", C.c_double), ("pt_samp_rds", C.c_int32), ("nbr_frm_num", C.c_int32), ("nbr_frm_step", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class CSeqPairParams(C.Structure):
     """struct mvs_seq_pair_params."""
     _fields_ = [("filter", CMatchFilterParams), ("min_dsp", C.c_double), ("max_dsp", C.c_double), ("min_match_count", C.c_int32),
@@ -118,6 +125,9 @@ _SIGS = {
     "mvs_sift_default_params": (None, [_VP]),
     "mvs_sift_detect": (C.c_int, [_I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _I64]),
     "mvs_sift_detect_dev": (C.c_int, [_I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _I64, _VP]),
+    "mvs_point_sample_default_params": (None, [_VP]),
+    "mvs_point_sample": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64]),
+    "mvs_point_sample_dev": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP]),
     "mvs_render_depth": (C.c_int, [_VP, _I64, _VP, _I64, _VP, C.c_float, C.c_float, _VP]),
     "mvs_render_depth_dev": (C.c_int, [_VP, _I64, _VP, _I64, _VP, C.c_float, C.c_float, _VP, _VP]),
     "mvs_render_depth_views": (C.c_int, [_VP, _I64, _VP, _I64, _I32, _VP, _VP, _VP, _VP, _VP, C.c_float, C.c_float, _VP]),
@@ -209,6 +219,7 @@ _SIGS = {
     "mvs_processor_stitch_points": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP, _U32, C.c_char_p, _VP]),
     "mvs_processor_cull_model": (C.c_int, [C.c_char_p, _I32, _VP, _VP, _VP, _VP, _VP, _I32, C.c_char_p, _VP, _VP]),
     "mvs_processor_render": (C.c_int, [C.c_char_p, C.c_char_p, _I32, _VP, _VP, C.c_char_p, _VP, C.c_float, C.c_float, _VP]),
+    "mvs_processor_point_sample": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP]),
     # include/mvs_test.h (test hooks: per handle, not part of the drop-in ABI)
     "mvs_test_preload_wait": (C.c_int, []),
     "mvs_test_ctl": (C.c_int, [_VP, _VP, _I32]),
@@ -221,6 +232,7 @@ _SIGS = {
     "mvs_test_sift_scores": (C.c_int, [_I64, _VP, _I64, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mvs_test_sift_level": (C.c_int, [_I32, _I32, _VP, _VP, _I32, _I32, _VP, _I64, _VP, _VP]),
     "mvs_test_sift_candidates": (C.c_int, [_I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _I64]),
+    "mvs_test_point_sample_candidates": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP, _I64]),
 }
 EXPORTS = tuple(_SIGS)
 

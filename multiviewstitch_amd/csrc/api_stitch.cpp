@@ -1,8 +1,9 @@
 // api_stitch.cpp — C-ABI of the tail of Processor::AlignmentSeq (R/Processor/Processor.cpp:952-1105): mvs_visibility_cull(_dev),
 // mvs_mesh_vertex_normals(_dev) (include/mvs.h) and the two file-level steps mvs_processor_stitch_points / _cull_model
 // (include/mvs_io.h); and of Processor::Render (:1140-1192): mvs_render_depth_views(_dev) (include/mvs.h) and the file-level
-// mvs_processor_render (include/mvs_io.h).  The point work is stitch.hip / align.hip / render_views.hip; the host reads and writes
-// the files and builds the small tables.
+// mvs_processor_render (include/mvs_io.h); and the file form of GeometryRec::RunPointSample (:919-949), mvs_processor_point_sample.
+// The point work is stitch.hip / align.hip / render_views.hip / pointsample.hip; the host reads and writes the files and builds the
+// small tables.
 #include "engine.h"
 #include "trace.h"
 #include "stitch.h"
@@ -311,6 +312,45 @@ int mvs_processor_render(const char* deform_obj, const char* srt_txt, int32_t n_
         }
     }
     if (n_views_out) *n_views_out = n_views;
+    return MVS_OK;
+}
+
+int mvs_processor_point_sample(int32_t n_seq, const char* const* seq_dirs, const int32_t* cam_off, const mvs_camera* cams,
+                               const mvs_point_sample_params* params, const char* const* npts_paths, int64_t* n_points) {
+    MVS_TRACE();
+    if (n_seq < 1) return bad(__func__, "n_seq must be >= 1");
+    if (!seq_dirs || !cam_off || !cams) return bad(__func__, "seq_dirs, cam_off and cams must not be NULL");
+    for (int k = 0; k < n_seq; ++k)
+        if (!seq_dirs[k]) return bad(__func__, "a path of seq_dirs is NULL");
+    int rc = check_offsets(__func__, "cam_off", cam_off, n_seq);
+    if (rc) return rc;
+    size_t floats = 0;
+    for (int c = 0; c < cam_off[n_seq]; ++c) {
+        if (cams[c].w <= 0 || cams[c].h <= 0) return bad(__func__, "every camera needs w, h > 0");
+        floats += (size_t)cams[c].w * (size_t)cams[c].h;
+    }
+    mvs_point_sample_params prm;
+    if (params) prm = *params; else mvs_point_sample_default_params(&prm);
+    std::vector<float> ras(floats ? floats : 1);                                                   // the rasters of DATA/CHECK, :919-931
+    size_t at = 0;
+    for (int k = 0; k < n_seq; ++k)
+        for (int c = cam_off[k]; c < cam_off[k + 1]; ++c) {
+            char name[48];
+            std::snprintf(name, sizeof name, "DATA/CHECK/_depth%d.raw", c - cam_off[k]);
+            if ((rc = mvs_depth_raw_read(join(seq_dirs[k], name).c_str(), cams[c].w, cams[c].h, ras.data() + at))) return rc;
+            at += (size_t)cams[c].w * (size_t)cams[c].h;
+        }
+    std::vector<int64_t> off((size_t)n_seq + 1);
+    std::vector<double> pts, nrm;
+    if ((rc = point_sample_vectors(__func__, n_seq, cam_off, cams, ras.data(), &prm, off.data(), &pts, &nrm))) return rc;
+    for (int k = 0; k < n_seq; ++k) {                                                              // Rec/*.npts, :933-949
+        const bool own = npts_paths && npts_paths[k];
+        const std::string dir = join(seq_dirs[k], "Rec/");
+        if (!own && (rc = make_dirs(dir))) return rc;
+        const std::string path = own ? std::string(npts_paths[k]) : dir + "PointSample.npts";
+        if ((rc = mvs_npts_write(path.c_str(), off[k + 1] - off[k], pts.data() + 3 * off[k], nrm.data() + 3 * off[k]))) return rc;
+        if (n_points) n_points[k] = off[k + 1] - off[k];
+    }
     return MVS_OK;
 }
 

@@ -33,6 +33,22 @@ __device__ inline void img_from_world(const CamDev& c, d3 pw, int32_t* u, int32_
     *u = cvt_i32(c.fx * p.x / p.z + c.cx + 0.5);
     *v = cvt_i32(c.fy * p.y / p.z + c.cy + 0.5);
 }
+// The same maps for bodies that host code shares (pointsample_rules.h), operation for operation those above: GetCamCoordFromWorld
+// alone (the camera coordinates img_from_world divides by), GetImgCoordFromCam of a camera point, and world_from_img
+__host__ __device__ inline d3 cam_from_world(const CamDev& c, d3 pw) {
+    return mk3(((c.R[0] * pw.x + c.R[1] * pw.y) + c.R[2] * pw.z) + c.t[0],
+               ((c.R[3] * pw.x + c.R[4] * pw.y) + c.R[5] * pw.z) + c.t[1],
+               ((c.R[6] * pw.x + c.R[7] * pw.y) + c.R[8] * pw.z) + c.t[2]);
+}
+__host__ __device__ inline void img_from_cam(const CamDev& c, d3 p, int32_t* u, int32_t* v) {
+    *u = cvt_i32(c.fx * p.x / p.z + c.cx + 0.5);
+    *v = cvt_i32(c.fy * p.y / p.z + c.cy + 0.5);
+}
+__host__ __device__ inline d3 world_from_img_hd(const CamDev& c, int u, int v, double d) {
+    const d3 pc = mk3((u - c.cx) * d / c.fx, (v - c.cy) * d / c.fy, d);
+    const d3 tmp = mk3(pc.x - c.t[0], pc.y - c.t[1], pc.z - c.t[2]);
+    return mulMtv(c.R, tmp);
+}
 // the point half of the similarity map (geom.hip k_srt_apply, stitch.hip k_vis_cull)
 __device__ inline d3 map34_point(const Map34& m, d3 p) {
     const d3 tt = mk3(m.t[0], m.t[1], m.t[2]);

@@ -77,8 +77,6 @@ __global__ __launch_bounds__(TPB) void k_check_seq(const float* __restrict__ dsp
     out[o] = ok ? dpf : 0.0f;
 }
 
-bool cam_fine(const mvs_camera* c) { return c && c->w > 0 && c->h > 0 && c->fx != 0.0 && c->fy != 0.0; }
-
 }  // namespace
 
 extern "C" {

@@ -406,6 +406,8 @@ template <class T> int down(T* h, const Scratch& d, size_t n) {
 }
 // the argument checks of the host entries: every one reports through bad(); check_offsets is the test of the n + 1 offsets of n
 // back-to-back lists (int64_t or int32_t): off[0] == 0, ascending and, with a limit, off[n] below it
+// a camera a raster kernel can use: positive size and focal lengths it can divide by (consist.hip, pointsample.hip)
+inline bool cam_fine(const mvs_camera* c) { return c && c->w > 0 && c->h > 0 && c->fx != 0.0 && c->fy != 0.0; }
 inline int bad(const char* fn, const char* what) { mvs_set_error("%s: %s", fn, what); return MVS_E_INVALID_ARG; }
 template <class T> int check_offsets(const char* fn, const char* name, const T* off, int64_t n, int64_t limit = 0) {
     const char* what = nullptr;

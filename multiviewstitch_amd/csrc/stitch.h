@@ -23,4 +23,8 @@ int cull_retain_dev(double* pts, double* nrm, int64_t* V, int32_t* faces, int64_
 // rasters of cams[0].w x cams[0].h floats in camera order.  Views are rendered in chunks of mvs_render_chunk_views().  Synchronises s.
 int render_views_dev(const double* pts, int64_t V, const int32_t* faces, int64_t F, int n_seq, const double* scales, const double* R,
                      const double* t, const int32_t* cam_off, const mvs_camera* cams, float znear, float zfar, float* out, hipStream_t s);
+// mvs_point_sample's host form (pointsample.hip) with outputs that size themselves: points / normals receive seq_offsets[n_seq] rows.
+// Validates like mvs_point_sample, reporting under the name fn.
+int point_sample_vectors(const char* fn, int32_t n_seq, const int32_t* cam_off, const mvs_camera* cams, const float* depths,
+                         const mvs_point_sample_params* p, int64_t* seq_offsets, std::vector<double>* points, std::vector<double>* normals);
 #endif

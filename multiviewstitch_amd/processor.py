@@ -4,7 +4,8 @@
 over adjacent sequences of ``Processor::CalcSimilarityTransformationSeq`` (:629-826) through ``mvs_sequence_pair_srt``; its head (:524-600)
 through ``mvs_gen_new_views`` (Image3D::GenNewViews) and ``mvs_keypoint_cull`` (the background cull of the key points); the descriptor
 matching between them, FeatureProc::MatchFeature (R/FeatureProc/FeatureProc.cpp:77-130), through ``mvs_sift_match_lists``; the SIFT
-detection in front of the cull, FeatureProc::DetectFeature (:14-75,103-112), through ``mvs_sift_detect``."""
+detection in front of the cull, FeatureProc::DetectFeature (:14-75,103-112), through ``mvs_sift_detect``; the point sampling between
+``CheckConsistency`` and the stitch tail, GeometryRec::RunPointSample (R/Processor/Processor.cpp:933-949), through ``mvs_point_sample``."""
 from __future__ import annotations
 
 import ctypes as C
@@ -128,6 +129,106 @@ def CheckConsistency(cameras, depths, min_dsp: float, max_dsp: float, reproj_err
     out = np.empty_like(d)
     L.check(L.lib().mvs_check_consistency_seq(len(cameras), L.ptr(d), cams, float(min_dsp), float(max_dsp), int(reproj_err), L.ptr(out)))
     return out
+
+
+def point_sample_params(**kw) -> L.CPointSampleParams:
+    """``mvs_point_sample_default_params`` (config.txt: MinDsp 0.0025, MaxDsp 0.3, MaxDspErr 0.01, MinConf 0.9, EdgeSzThres 4, PtSampRds 2,
+    NbrFrmNum 2, NbrFrmStep 1) with the given fields replaced."""
+    prm = L.CPointSampleParams()
+    L.lib().mvs_point_sample_default_params(C.byref(prm))
+    for k, v in kw.items():
+        if k not in dict(L.CPointSampleParams._fields_):
+            raise L.MvsError(-1, f"mvs_point_sample_params has no field {k}")
+        setattr(prm, k, v)
+    return prm
+
+
+def _seq_cams(cameras):
+    """cam_off int32 [n_seq + 1] and the mvs_camera array of ``cameras[k]`` = sequence k's cameras"""
+    off = np.zeros(len(cameras) + 1, np.int32)
+    off[1:] = np.cumsum([len(c) for c in cameras])
+    flat = [L.CCamera.of(c) for seq in cameras for c in seq]
+    return off, (L.CCamera * max(1, len(flat)))(*flat)
+
+
+def RunPointSample(cameras, depths, params: L.CPointSampleParams | None = None, stream: int | None = None, capacity: int | None = None):
+    """GeometryRec::RunPointSample (R/Processor/Processor.cpp:933-949) for every sequence in one call (``mvs_point_sample``; the rules,
+    this library's definition: include/mvs.h).  ``cameras[k]`` lists sequence k's cameras; ``depths[k]`` is its checked rasters
+    [frames, h, w] float32 (``CheckConsistency``'s result) — numpy arrays, or contiguous torch tensors on the GPU (the device form: the
+    results are tensors on the same device).  In the device form ``depths`` may also be ONE contiguous float32 tensor that holds the
+    rasters of all cameras back to back in camera order: it is read in place, where a list of several tensors is first concatenated
+    (a copy of all rasters).  ``stream`` is the HIP stream that produced the rasters (None: the legacy default stream); the kernels, the
+    concatenation and the allocation of the results are all ordered on it, whatever torch's current stream is.
+    -> a list with, per sequence, (points [m, 3] float64, normals [m, 3] float64, frame [m] int32, pixel [m] int32) in the order of
+    rule 8: the rows ``io.write_npts`` takes.  ``capacity`` (rows) sizes the first attempt, by default two frames' worth of cells per
+    sequence (later frames are mostly covered); a call that finds more points is repeated once with the right size."""
+    import contextlib
+    prm = params if params is not None else point_sample_params()
+    n = len(cameras)
+    off, cams = _seq_cams(cameras)
+    need = sum(len(c) * int(c[0].w) * int(c[0].h) for c in cameras if len(c))
+    whole = _is_dev(depths)
+    if whole:
+        if depths.numel() != need:
+            raise L.MvsError(-1, f"depths must hold the {need} floats of all rasters")
+    else:
+        if len(depths) != n:
+            raise L.MvsError(-1, f"{len(depths)} raster stacks for {n} sequences")
+        for k in range(n):
+            want = (len(cameras[k]),) + ((int(cameras[k][0].h), int(cameras[k][0].w)) if len(cameras[k]) else tuple(depths[k].shape[1:]))
+            if tuple(depths[k].shape) != want:
+                raise L.MvsError(-1, f"depths[{k}] must be [frames, h, w] = {want}")
+    soff = np.zeros(n + 1, np.int64)
+    dev = whole or (n > 0 and all(_is_dev(d) for d in depths))
+    order = contextlib.nullcontext()
+    if dev:
+        import torch
+        if stream:
+            order = torch.cuda.stream(torch.cuda.ExternalStream(int(stream)))
+    r = max(1, int(prm.pt_samp_rds))
+    cap = int(capacity) if capacity is not None else sum(2 * (-(-int(c[0].w) // r)) * (-(-int(c[0].h) // r)) for c in cameras if len(c))
+    cap = max(1, cap)
+    with order:
+        if dev:
+            flat = depths if whole else (torch.cat([d.reshape(-1) for d in depths]) if n > 1 else depths[0].reshape(-1))
+            if flat.numel() == 0:
+                flat = torch.zeros(1, dtype=torch.float32, device=flat.device)
+            dptr = _dev_ptr(flat, "float32", "depths")
+        else:
+            flat = np.concatenate([L.arr(d, np.float32).reshape(-1) for d in depths]) if n else np.zeros(1, np.float32)
+            if flat.size == 0:
+                flat = np.zeros(1, np.float32)
+        for attempt in range(2):
+            soff[:] = -1
+            if dev:
+                pts, nrm = (torch.empty((cap, 3), dtype=torch.float64, device=flat.device) for _ in range(2))
+                frm, pix = (torch.empty(cap, dtype=torch.int32, device=flat.device) for _ in range(2))
+                rc = L.lib().mvs_point_sample_dev(n, L.ptr(off), cams, dptr, C.byref(prm), L.ptr(soff), L.ptr(int(pts.data_ptr())),
+                                                  L.ptr(int(nrm.data_ptr())), L.ptr(int(frm.data_ptr())), L.ptr(int(pix.data_ptr())), cap, L.ptr(stream))
+            else:
+                pts, nrm, frm, pix = np.empty((cap, 3)), np.empty((cap, 3)), np.empty(cap, np.int32), np.empty(cap, np.int32)
+                rc = L.lib().mvs_point_sample(n, L.ptr(off), cams, L.ptr(flat), C.byref(prm), L.ptr(soff), L.ptr(pts), L.ptr(nrm), L.ptr(frm), L.ptr(pix), cap)
+            if rc == -1 and attempt == 0 and soff[-1] > cap:                   # seq_offsets holds the need
+                cap = int(soff[-1])
+                continue
+            L.check(rc)
+            break
+    return [tuple(a[soff[k]:soff[k + 1]] for a in (pts, nrm, frm, pix)) for k in range(n)]
+
+
+def PointSampleFiles(seq_dirs, cameras, params: L.CPointSampleParams | None = None, npts_paths=None) -> np.ndarray:
+    """``mvs_processor_point_sample``: sequence k's checked rasters ``seq_dirs[k]``/DATA/CHECK/_depth<i>.raw -> ``seq_dirs[k]``/Rec/PointSample.npts
+    (or ``npts_paths[k]``), the file ``StitchPointSets`` reads.  ``cameras[k]`` lists sequence k's cameras.  -> rows written per sequence."""
+    n = len(cameras)
+    if len(seq_dirs) != n or (npts_paths is not None and len(npts_paths) != n):
+        raise L.MvsError(-1, f"{len(seq_dirs)} sequence dirs for {n} sequences")
+    off, cams = _seq_cams(cameras)
+    dirs = (C.c_char_p * max(1, n))(*[os.fsencode(d) for d in seq_dirs])
+    outs = (C.c_char_p * max(1, n))(*[os.fsencode(p) if p is not None else None for p in npts_paths]) if npts_paths is not None else None
+    prm = params if params is not None else point_sample_params()
+    cnt = np.zeros(n, np.int64)
+    L.check(L.lib().mvs_processor_point_sample(n, dirs, L.ptr(off), cams, C.byref(prm), outs, L.ptr(cnt)))
+    return cnt
 
 
 def RenderDepth(points, facets, camera, znear: float = 0.01, zfar: float = 2000.0, out_dev: int | None = None, stream: int | None = None):

@@ -272,6 +272,19 @@ CULL_SEQUENCES, CULL_ALL_SEQ = 0, 1          # enum mvs_cull_mode
 STITCH_TRUNCATE = 1                         # MVS_STITCH_TRUNCATE (include/mvs_io.h)
 
 
+def cam_array(cameras):
+    """``cameras`` as an mvs_camera array, at least one element long (the entries take a pointer, never an empty array)."""
+    flat = [CCamera.of(c) for c in cameras]
+    return (CCamera * max(1, len(flat)))(*flat)
+
+
+def seq_cams(cameras):
+    """cam_off int32 [n_seq + 1] and the mvs_camera array of all cameras, ``cameras[k]`` = sequence k's cameras."""
+    off = np.zeros(len(cameras) + 1, np.int32)
+    off[1:] = np.cumsum([len(c) for c in cameras])
+    return off, cam_array([c for seq in cameras for c in seq])
+
+
 def seq_tables(scales, Rs, ts, cameras):
     """The SRT chain and the per-sequence camera lists of AlignmentSeq as C arrays:
     (n_seq, scales[n], R[n,3,3] row-major, t[n,3], cam_off int32[n+1], mvs_camera[]).  ``cameras[k]`` lists sequence k's cameras."""
@@ -281,10 +294,7 @@ def seq_tables(scales, Rs, ts, cameras):
     t = arr(ts, np.float64).reshape(n, 3)
     if len(cameras) != n:
         raise MvsError(-1, f"{len(cameras)} camera lists for {n} sequences")
-    off = np.zeros(n + 1, np.int32)
-    off[1:] = np.cumsum([len(c) for c in cameras])
-    flat = [CCamera.of(c) for seq in cameras for c in seq]
-    cams = (CCamera * max(1, len(flat)))(*flat)
+    off, cams = seq_cams(cameras)
     return n, s, R, t, off, cams
 
 
@@ -297,9 +307,9 @@ def arr(a, dt):
 
 
 def ptr(a):
-    """Host numpy array -> void*; None -> NULL; int -> raw (device) address."""
+    """Host numpy array -> void*; None -> NULL; int -> raw (device) address; torch tensor -> its address."""
     if a is None:
         return None
-    if isinstance(a, (int, np.integer)):
-        return C.c_void_p(int(a))
-    return C.c_void_p(a.ctypes.data)
+    if isinstance(a, np.ndarray):
+        return C.c_void_p(a.ctypes.data)
+    return C.c_void_p(int(a) if isinstance(a, (int, np.integer)) else a.data_ptr())

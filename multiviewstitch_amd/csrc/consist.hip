@@ -92,11 +92,9 @@ int mvs_check_consistency_seq_dev(int32_t n_frames, const float* depths_dev, con
     int rc = need_device();
     if (rc) return rc;
     hipStream_t s = (hipStream_t)hip_stream;
-    std::vector<CamDev> hc((size_t)n_frames);
-    for (int f = 0; f < n_frames; ++f) hc[f] = make_camdev(cams + f);
+    std::vector<CamDev> hc;
     Scratch dc;
-    if ((rc = dc.alloc(sizeof(CamDev) * hc.size(), s))) return rc;
-    HIPCHK(hipMemcpyAsync(dc.p, hc.data(), sizeof(CamDev) * hc.size(), hipMemcpyHostToDevice, s));
+    if ((rc = up_cams(dc, hc, cams, (size_t)n_frames, s))) return rc;
     const int npx = cams[0].w * cams[0].h;
     k_check_seq<<<dim3((npx + TPB - 1) / TPB, n_frames), dim3(TPB), 0, s>>>(depths_dev, dc.as<CamDev>(), n_frames, min_dsp, max_dsp, reproj_err, out_dev);
     HIPCHK(hipGetLastError());

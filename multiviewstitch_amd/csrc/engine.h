@@ -401,6 +401,13 @@ template <class T> int up(Scratch& d, const T* h, size_t n, size_t cap = 0) {
     if (rc || !n) return rc;
     return mvs_check_hip(hipMemcpy(d.p, h, sizeof(T) * n, hipMemcpyHostToDevice), "upload");
 }
+// the stream form: a fresh block of n elements allocated for s and the copy enqueued on s; h must stay alive until s has been
+// synchronised
+template <class T> int up_async(Scratch& d, const T* h, size_t n, hipStream_t s) {
+    int rc = d.alloc(sizeof(T) * n, s);
+    if (rc || !n) return rc;
+    return mvs_check_hip(hipMemcpyAsync(d.p, h, sizeof(T) * n, hipMemcpyHostToDevice, s), "upload");
+}
 template <class T> int down(T* h, const Scratch& d, size_t n) {
     return n ? mvs_check_hip(hipMemcpy(h, d.p, sizeof(T) * n, hipMemcpyDeviceToHost), "download") : MVS_OK;
 }
@@ -419,6 +426,27 @@ template <class T> int check_offsets(const char* fn, const char* name, const T* 
     mvs_set_error("%s: %s %s", fn, name, what);
     return MVS_E_INVALID_ARG;
 }
+// the cameras of one sequence whose pixels become 16-bit key halves and int32 texIndex entries (views.hip): one size for all
+inline int check_cams(const char* fn, int32_t n_frames, const mvs_camera* cams) {
+    if (n_frames < 1) return bad(fn, "need n_frames >= 1");
+    if (!cams) return bad(fn, "cams is NULL");
+    const int w = cams[0].w, h = cams[0].h;
+    if (w <= 0 || h <= 0) return bad(fn, "need w, h > 0");
+    if (w > 65535 || h > 65535) return bad(fn, "w and h must not exceed 65535");
+    if ((int64_t)w * h > 0x7fffffffLL) return bad(fn, "w * h must fit the int32 of a texIndex entry");
+    for (int i = 1; i < n_frames; ++i)
+        if (cams[i].w != w || cams[i].h != h) return bad(fn, "every camera must have the same size");
+    return MVS_OK;
+}
+// The tail of an ordered compaction (compact.hip): alloc, the unit's count kernel fills cnt, then ONE of segments / strided scans cnt
+// into base and writes the n + 1 offsets of the compacted segments; the unit's scatter kernel reads base.
+constexpr int COMPACT_TPB = 256;             // items per workgroup of every unit's count and scatter kernel
+struct CompactTail {
+    Scratch cnt, base, off;                  // int32 [nb], int32 [nb + 1], int64 [n + 1]
+    int  alloc(size_t nb, size_t n, hipStream_t s);
+    void segments(int nb, const int64_t* seg_dev, int64_t n, int64_t total, const uint8_t* keep, hipStream_t s);
+    void strided(int nb, const int32_t* at_dev, int n, int stride, hipStream_t s);
+};
 // the rest of the process-wide state (runtime.cpp)
 int  mvs_current_device();
 int  need_device();                                   // MVS_E_NO_DEVICE without a HIP device, else selects mvs_current_device() on this thread

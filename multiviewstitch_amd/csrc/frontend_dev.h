@@ -1,7 +1,6 @@
-// frontend_dev.h — the small pieces the units of the `main -a 1` front end share (stitch.hip, matchpairs.hip, views.hip): CheckRange,
-// the 8-bit grey conversion, the segment look-up of back-to-back lists, the stage-1 rule of the match filter (one body for the
-// kernel and for host code), the workgroup ranking of an ordered compaction and the two scan steps that turn per-workgroup survivor
-// counts into places (views.hip's key-point cull, siftmatch.hip's pairing).
+// frontend_dev.h — the small pieces the units of the `main -a 1` front end share: CheckRange, the 8-bit grey conversion, the segment
+// look-up of back-to-back lists, the stage-1 rule of the match filter (one body for the kernel and for host code), the workgroup
+// ranking of an ordered compaction (every unit's count and scatter kernels) and the two scan steps behind it (compact.hip).
 #ifndef MVS_FRONTEND_DEV_H_
 #define MVS_FRONTEND_DEV_H_
 #include <hip/hip_runtime.h>

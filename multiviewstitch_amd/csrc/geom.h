@@ -10,6 +10,8 @@ struct CamDev {
     int32_t w, h;
 };
 CamDev make_camdev(const mvs_camera* c);
+// n cameras as CamDev into a fresh block, the copy enqueued on s; `host` is the copy's source and stays alive until s has been synchronised
+int up_cams(Scratch& d, std::vector<CamDev>& host, const mvs_camera* cams, size_t n, hipStream_t s);
 
 // the similarity point map of mvs_srt_apply (v = M p + t, or M (p - t) when inverse; normals n' = Rn n), built on the host:
 // forward M = s R (Processor.cpp:1025), inverse M = (1/s) R^T (:1183); applied by map34_point (camera_dev.h)

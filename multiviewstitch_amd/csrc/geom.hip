@@ -141,6 +141,12 @@ CamDev make_camdev(const mvs_camera* c) {
     return d;
 }
 
+int up_cams(Scratch& d, std::vector<CamDev>& host, const mvs_camera* cams, size_t n, hipStream_t s) {
+    host.resize(n);
+    for (size_t i = 0; i < n; ++i) host[i] = make_camdev(cams + i);
+    return up_async(d, host.data(), n, s);
+}
+
 int depth_to_model_dev(const float* dsp_dev, const mvs_camera* cam, double mn, double mx, double smooth,
                        int64_t* n_points, int64_t* n_faces, double* out_pts, double* out_nrm, int32_t* out_tex,
                        int32_t* out_faces, hipStream_t s) {

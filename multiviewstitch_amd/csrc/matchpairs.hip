@@ -225,9 +225,8 @@ struct PairsDev {
 // off uploaded, keys allocated, the stage sizes and the flag cleared (counts of empty pairs are never written by the cascade)
 int pairs_begin(PairsDev& d, int np, const int64_t* raw_off, hipStream_t s) {
     int rc;
-    if ((rc = d.off.alloc(sizeof(int64_t) * ((size_t)np + 1), s)) || (rc = d.keys.alloc(sizeof(unsigned long long) * (size_t)raw_off[np], s)) ||
+    if ((rc = up_async(d.off, raw_off, (size_t)np + 1, s)) || (rc = d.keys.alloc(sizeof(unsigned long long) * (size_t)raw_off[np], s)) ||
         (rc = d.cnt.alloc(sizeof(int32_t) * (3 * (size_t)np + 1), s))) return rc;
-    HIPCHK(hipMemcpyAsync(d.off.p, raw_off, sizeof(int64_t) * ((size_t)np + 1), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemsetAsync(d.cnt.p, 0, sizeof(int32_t) * (3 * (size_t)np + 1), s));
     return MVS_OK;
 }
@@ -239,8 +238,7 @@ int pairs_map(int n1, int n2, const int64_t* raw_off, const int32_t* raw, const 
     const int64_t total = raw_off[np];
     if (total == 0) return MVS_OK;
     int rc;
-    if ((rc = d.raw.alloc(sizeof(int32_t) * 6 * (size_t)total, s)) || (rc = pairs_begin(d, np, raw_off, s))) return rc;
-    HIPCHK(hipMemcpyAsync(d.raw.p, raw, sizeof(int32_t) * 6 * (size_t)total, hipMemcpyHostToDevice, s));
+    if ((rc = up_async(d.raw, raw, 6 * (size_t)total, s)) || (rc = pairs_begin(d, np, raw_off, s))) return rc;
     k_mp_map<<<dim3((unsigned)((total + MP_TPB - 1) / MP_TPB)), dim3(MP_TPB), 0, s>>>(d.raw.as<int32_t>(), total, d.off.as<int64_t>(), np, n2, tex1, valid1,
                                                                                      tex2, valid2, p->w, p->h, p->view_count,
                                                                                      d.keys.as<unsigned long long>(), d.cnt.as<int32_t>() + 3 * (size_t)np);
@@ -270,9 +268,8 @@ int pairs_cascade(int n1, int n2, const int64_t* raw_off, const PairsDev& d, con
     }
     Scratch dwsoff, dws, dout;
     int rc;
-    if ((rc = dwsoff.alloc(sizeof(int64_t) * (size_t)np, s)) || (rc = dws.alloc(sizeof(unsigned long long) * (size_t)ws_total, s)) ||
+    if ((rc = up_async(dwsoff, ws_off.data(), ws_off.size(), s)) || (rc = dws.alloc(sizeof(unsigned long long) * (size_t)ws_total, s)) ||
         (rc = dout.alloc(sizeof(int32_t) * 4 * (size_t)total, s))) return rc;
-    HIPCHK(hipMemcpyAsync(dwsoff.p, ws_off.data(), sizeof(int64_t) * (size_t)np, hipMemcpyHostToDevice, s));
     const double gap = (double)p->sample_interval * (double)p->sample_interval;         // :713
     k_mp_cascade<<<dim3((unsigned)np), dim3(MP_TPB), 0, s>>>(d.keys.as<unsigned long long>(), d.off.as<int64_t>(), n2, cap, dws.as<unsigned long long>(),
                                                             dwsoff.as<int64_t>(), imgs1, imgs2, p->w, p->h, p->ssd_win, p->ssd_err, gap,
@@ -288,8 +285,7 @@ int pairs_cascade(int n1, int n2, const int64_t* raw_off, const PairsDev& d, con
     const int64_t kept = o.off[np];
     if (kept == 0) return MVS_OK;
     Scratch dooff;
-    if ((rc = o.packed.alloc(sizeof(int32_t) * 4 * (size_t)kept, s)) || (rc = dooff.alloc(sizeof(int64_t) * ((size_t)np + 1), s))) return rc;
-    HIPCHK(hipMemcpyAsync(dooff.p, o.off.data(), sizeof(int64_t) * ((size_t)np + 1), hipMemcpyHostToDevice, s));
+    if ((rc = o.packed.alloc(sizeof(int32_t) * 4 * (size_t)kept, s)) || (rc = up_async(dooff, o.off.data(), o.off.size(), s))) return rc;
     k_mp_pack<<<dim3((unsigned)np), dim3(MP_TPB), 0, s>>>(dout.as<int32_t>(), d.off.as<int64_t>(), dooff.as<int64_t>(), o.packed.as<int32_t>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));

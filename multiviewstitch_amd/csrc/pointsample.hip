@@ -12,8 +12,8 @@
 //                    candidate and a clear coverage byte emits; its thread then marks, with plain byte stores of 1, the cell its
 //                    point lands on in every later frame that agrees with it.  A launch writes only bytes of frames above t and
 //                    the byte of its own cell, which from then on holds the emit flag: stream order is the only synchronisation.
-//   k_ps_count / k_ps_scan / k_ps_offsets / k_ps_scatter
-//                    the ordered compaction of views.hip's key-point cull.  Output order is pixel order, not cell order: a frame is
+//   k_ps_count / CompactTail / k_ps_scatter
+//                    the ordered compaction of views.hip's key-point cull (compact.hip).  Output order is pixel order, not cell order: a frame is
 //                    walked as h x cw slots (pixel row v, cell column cx); the slot is set when cell (v / r, cx) emits and its
 //                    candidate lies in row v.  Survivor counts per workgroup, one exclusive scan, then the scatter recomputes point
 //                    and normal and writes the rows.  No atomic anywhere: two runs are bit-identical.
@@ -30,6 +30,7 @@
 namespace {
 
 constexpr int PS_TPB = 256, PS_WAVES = PS_TPB / 64;
+static_assert(PS_TPB == COMPACT_TPB, "k_ps_count and k_ps_scatter count and place per workgroup of the shared tail");
 
 struct PsSeq {                        // one sequence: its cameras cams[cam0 .. cam0 + n), all w x h, cut into cw x ch cells
     int32_t cam0, n, w, h, cw, ch;
@@ -88,16 +89,6 @@ __global__ __launch_bounds__(PS_TPB) void k_ps_count(const PsSeq* __restrict__ s
     const bool f = slot < (int64_t)s.h * s.cw && ps_slot(s, cam - s.cam0, slot, r, cand, flag) >= 0;
     const WgRank k = wg_rank<PS_WAVES>(f, s_wsum);
     if (threadIdx.x == 0) cnt[blockIdx.x] = k.total;
-}
-
-__global__ __launch_bounds__(PS_TPB) void k_ps_scan(const int32_t* __restrict__ cnt, int nb, int32_t* __restrict__ base) {
-    wg_scan_counts<PS_WAVES>(cnt, nb, base);
-}
-
-// seq_offsets: a sequence starts where the workgroups of its first camera start
-__global__ void k_ps_offsets(const int32_t* __restrict__ cam_off, int n_seq, int maxblk, const int32_t* __restrict__ base, int64_t* __restrict__ out_off) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k <= n_seq) out_off[k] = base[(int64_t)cam_off[k] * maxblk];
 }
 
 __global__ __launch_bounds__(PS_TPB) void k_ps_scatter(const float* __restrict__ depths, const CamDev* __restrict__ cams,
@@ -184,20 +175,15 @@ struct PsRun {
     hipStream_t s;
     int n_seq, nb = 0;
     std::vector<CamDev> hc;
-    Scratch dcam, dseq, dsof, dcoff, dcand, dcover, dcnt, dbase, dooff;
+    Scratch dcam, dseq, dsof, dcoff, dcand, dcover;
+    CompactTail ct;
     PsRun(const PsPlan& plan, int n, const float* depths_dev, hipStream_t st) : pl(plan), depths(depths_dev), s(st), n_seq(n) {}
 
     int candidates(const mvs_camera* cams, const int32_t* cam_off) {
-        hc.resize((size_t)pl.ncam);
-        for (int i = 0; i < pl.ncam; ++i) hc[(size_t)i] = make_camdev(cams + i);
         int rc;
-        if ((rc = dcam.alloc(sizeof(CamDev) * hc.size(), s)) || (rc = dseq.alloc(sizeof(PsSeq) * pl.seqs.size(), s)) ||
-            (rc = dsof.alloc(sizeof(int32_t) * pl.seq_of.size(), s)) || (rc = dcoff.alloc(sizeof(int32_t) * ((size_t)n_seq + 1), s)) ||
+        if ((rc = up_cams(dcam, hc, cams, (size_t)pl.ncam, s)) || (rc = up_async(dseq, pl.seqs.data(), pl.seqs.size(), s)) ||
+            (rc = up_async(dsof, pl.seq_of.data(), pl.seq_of.size(), s)) || (rc = up_async(dcoff, cam_off, (size_t)n_seq + 1, s)) ||
             (rc = dcand.alloc(sizeof(int32_t) * (size_t)pl.cells, s)) || (rc = dcover.alloc((size_t)pl.cells, s))) return rc;
-        HIPCHK(hipMemcpyAsync(dcam.p, hc.data(), sizeof(CamDev) * hc.size(), hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(dseq.p, pl.seqs.data(), sizeof(PsSeq) * pl.seqs.size(), hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(dsof.p, pl.seq_of.data(), sizeof(int32_t) * pl.seq_of.size(), hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(dcoff.p, cam_off, sizeof(int32_t) * ((size_t)n_seq + 1), hipMemcpyHostToDevice, s));
         k_ps_candidates<<<dim3((unsigned)(pl.ncam * pl.blk_cells)), dim3(PS_TPB), 0, s>>>(depths, dcam.as<CamDev>(), dseq.as<PsSeq>(), dsof.as<int32_t>(),
                                                                                          pl.blk_cells, pl.q, dcand.as<int32_t>());
         HIPCHK(hipGetLastError());
@@ -207,25 +193,23 @@ struct PsRun {
     int emit_and_scan(int64_t* seq_offsets) {
         int rc;
         nb = pl.ncam * pl.blk_slots;
-        if ((rc = dcnt.alloc(sizeof(int32_t) * (size_t)nb, s)) || (rc = dbase.alloc(sizeof(int32_t) * ((size_t)nb + 1), s)) ||
-            (rc = dooff.alloc(sizeof(int64_t) * ((size_t)n_seq + 1), s))) return rc;
+        if ((rc = ct.alloc((size_t)nb, (size_t)n_seq, s))) return rc;
         HIPCHK(hipMemsetAsync(dcover.p, 0, (size_t)pl.cells, s));
         for (int t = 0; t < pl.max_frames; ++t)
             k_ps_emit<<<dim3((unsigned)(n_seq * pl.blk_cells)), dim3(PS_TPB), 0, s>>>(depths, dcam.as<CamDev>(), dseq.as<PsSeq>(), pl.blk_cells, t, pl.q,
                                                                                      dcand.as<int32_t>(), dcover.as<uint8_t>());
         k_ps_count<<<dim3((unsigned)nb), dim3(PS_TPB), 0, s>>>(dseq.as<PsSeq>(), dsof.as<int32_t>(), pl.blk_slots, pl.q.r, dcand.as<int32_t>(),
-                                                              dcover.as<uint8_t>(), dcnt.as<int32_t>());
-        k_ps_scan<<<dim3(1), dim3(PS_TPB), 0, s>>>(dcnt.as<int32_t>(), nb, dbase.as<int32_t>());
-        k_ps_offsets<<<dim3((unsigned)(n_seq / PS_TPB + 1)), dim3(PS_TPB), 0, s>>>(dcoff.as<int32_t>(), n_seq, pl.blk_slots, dbase.as<int32_t>(), dooff.as<int64_t>());
+                                                              dcover.as<uint8_t>(), ct.cnt.as<int32_t>());
+        ct.strided(nb, dcoff.as<int32_t>(), n_seq, pl.blk_slots, s);       // seq_offsets: a sequence starts where the workgroups of its first camera start
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(seq_offsets, dooff.p, sizeof(int64_t) * ((size_t)n_seq + 1), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(seq_offsets, ct.off.p, sizeof(int64_t) * ((size_t)n_seq + 1), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         return MVS_OK;
     }
 
     int scatter(double* points, double* normals, int32_t* frame, int32_t* pixel) {
         k_ps_scatter<<<dim3((unsigned)nb), dim3(PS_TPB), 0, s>>>(depths, dcam.as<CamDev>(), dseq.as<PsSeq>(), dsof.as<int32_t>(), pl.blk_slots, pl.q,
-                                                                dcand.as<int32_t>(), dcover.as<uint8_t>(), dbase.as<int32_t>(), points, normals, frame, pixel);
+                                                                dcand.as<int32_t>(), dcover.as<uint8_t>(), ct.base.as<int32_t>(), points, normals, frame, pixel);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(s));
         return MVS_OK;

@@ -164,12 +164,10 @@ int render_views_dev(const double* pts, int64_t V, const int32_t* faces, int64_t
     Scratch dv, dm, win, cnt, off, bsum, tot;
     const size_t nslot = (size_t)nv * n_tiles;
     int rc;
-    if ((rc = dv.alloc(sizeof(ViewDev) * N, s)) || (rc = dm.alloc(sizeof(Map34) * hm.size(), s)) ||
+    if ((rc = up_async(dv, hv.data(), hv.size(), s)) || (rc = up_async(dm, hm.data(), hm.size(), s)) ||
         (rc = win.alloc(sizeof(float4) * (size_t)nv * V, s)) || (rc = cnt.alloc(sizeof(int32_t) * nslot, s)) ||
         (rc = off.alloc(sizeof(int32_t) * (nslot + 1), s)) || (rc = bsum.alloc(sizeof(int32_t) * ((nslot + 1 + 1023) / 1024), s)) ||
         (rc = tot.alloc(sizeof(unsigned long long) * nv, s))) return rc;
-    HIPCHK(hipMemcpyAsync(dv.p, hv.data(), sizeof(ViewDev) * N, hipMemcpyHostToDevice, s));
-    if (!hm.empty()) HIPCHK(hipMemcpyAsync(dm.p, hm.data(), sizeof(Map34) * hm.size(), hipMemcpyHostToDevice, s));
     const Map34* maps = hm.empty() ? nullptr : dm.as<Map34>();
     const unsigned vb = (unsigned)((V + TPB - 1) / TPB), fb = (unsigned)((F + TPB - 1) / TPB);
     for (int v0 = 0; v0 < N;) {

@@ -10,7 +10,7 @@
 //   k_sift_down   : rule 4, level S at the even pixels -> level 0 of the next octave
 //   k_sift_detect : rules 5-6 over EVERY (octave, level, pixel) of a list, flattened in the output order of rule 9.  It reads four
 //                   Gaussian levels and stores no DoG.  First run: the keep flag of every item and the survivors per workgroup;
-//                   k_sift_scan (wg_scan_counts, list-major) turns the counts into places; second run: the survivors refine
+//                   CompactTail (compact.hip; the counts are list-major) turns them into places; second run: the survivors refine
 //                   again (the same sift_refine body) and write their record at base + wg_rank — no atomic counter anywhere.
 //   k_sift_orient : rule 7, a wave per candidate, the 36-bin histogram in LDS as 64-bit integers (a vote is quantised to 2^-24
 //                   first, so the sum does not depend on the order of the lanes), smoothing and peaks in registers
@@ -32,6 +32,7 @@ namespace {
 
 constexpr int SF_TPB = 256;
 constexpr int SF_WAVES = SF_TPB / 64;
+static_assert(SF_TPB == COMPACT_TPB, "k_sift_detect counts and places per workgroup of the shared tail");
 constexpr size_t SIFT_SCRATCH_BYTES = (size_t)512 << 20;      // pyramid, base, keep flags, workgroup counts of one chunk of lists (mvs.h states it)
 constexpr int SF_MAX_CHUNK = 32768;                           // lists per chunk: the list index is blockIdx.y
 constexpr float SF_Q = 16777216.0f;                           // votes are accumulated in units of 2^-24
@@ -193,16 +194,6 @@ __global__ __launch_bounds__(SF_TPB) void k_sift_detect(SiftDev d, int64_t n_ite
     I[0] = it.o; I[1] = it.l; I[2] = it.x; I[3] = it.y; I[4] = list; I[5] = 0; I[6] = 0; I[7] = 0;
     F[0] = (((float)it.x + rf.dx) + 0.5f) * step; F[1] = (((float)it.y + rf.dy) + 0.5f) * step; F[2] = so * step; F[3] = so;
     F[4] = rf.dx; F[5] = rf.dy; F[6] = 0.0f; F[7] = 0.0f;
-}
-
-__global__ __launch_bounds__(SF_TPB) void k_sift_scan(const int32_t* __restrict__ cnt, int nb, int32_t* __restrict__ base) {
-    wg_scan_counts<SF_WAVES>(cnt, nb, base);
-}
-
-// where every list's candidates start: out[l] = base[l * nb], out[nl] = all of them
-__global__ void k_sift_coff(const int32_t* __restrict__ base, int nb, int nl, int32_t* __restrict__ out) {
-    const int l = blockIdx.x * blockDim.x + threadIdx.x;
-    if (l <= nl) out[l] = base[(int64_t)l * nb];
 }
 
 __device__ inline unsigned long long sf_quant(float v) { return (unsigned long long)(v * SF_Q + 0.5f); }
@@ -454,13 +445,12 @@ int sift_core(const char* fn, int n_lists, int w, int h, const uint8_t* imgs, co
     const int64_t npx0 = (int64_t)pl.W0 * pl.H0, n_items = pl.n_items;
     const int nb = (int)((n_items + SF_TPB - 1) / SF_TPB);
     if ((int64_t)nb * chunk >= 0x7fffffffLL) return bad(fn, "too many workgroups in one chunk");
-    Scratch pyr, U, keep, cnt, base, taps, dcoff;
+    Scratch pyr, U, keep, taps;
+    CompactTail ct;
     int rc;
     if ((rc = pyr.alloc(sizeof(float) * (size_t)pl.pyr_floats_per_list * chunk, s)) || (rc = U.alloc(sizeof(float) * (size_t)npx0 * chunk, s)) ||
-        (rc = keep.alloc((size_t)n_items * chunk, s)) || (rc = cnt.alloc(sizeof(int32_t) * (size_t)nb * chunk, s)) ||
-        (rc = base.alloc(sizeof(int32_t) * ((size_t)nb * chunk + 1), s)) || (rc = taps.alloc(sizeof(float) * pl.taps.size(), s)) ||
-        (rc = dcoff.alloc(sizeof(int32_t) * ((size_t)chunk + 1), s))) return rc;
-    HIPCHK(hipMemcpyAsync(taps.p, pl.taps.data(), sizeof(float) * pl.taps.size(), hipMemcpyHostToDevice, s));
+        (rc = keep.alloc((size_t)n_items * chunk, s)) || (rc = ct.alloc((size_t)nb * chunk, (size_t)chunk, s)) ||
+        (rc = up_async(taps, pl.taps.data(), pl.taps.size(), s))) return rc;
     SiftDev d = pl.d;
     d.pyr = pyr.as<float>();
     int64_t off = 0;
@@ -495,20 +485,19 @@ int sift_core(const char* fn, int n_lists, int w, int h, const uint8_t* imgs, co
             HIPCHK(hipStreamSynchronize(s));
             return MVS_OK;
         }
-        k_sift_detect<false><<<dim3((unsigned)nb, (unsigned)nl), dim3(SF_TPB), 0, s>>>(d, n_items, keep.as<uint8_t>(), cnt.as<int32_t>(), nullptr, nullptr, nullptr);
-        k_sift_scan<<<dim3(1), dim3(SF_TPB), 0, s>>>(cnt.as<int32_t>(), nb * nl, base.as<int32_t>());
-        k_sift_coff<<<dim3((unsigned)(nl / SF_TPB + 1)), dim3(SF_TPB), 0, s>>>(base.as<int32_t>(), nb, nl, dcoff.as<int32_t>());
+        k_sift_detect<false><<<dim3((unsigned)nb, (unsigned)nl), dim3(SF_TPB), 0, s>>>(d, n_items, keep.as<uint8_t>(), ct.cnt.as<int32_t>(), nullptr, nullptr, nullptr);
+        ct.strided(nb * nl, nullptr, nl, nb, s);                  // where every list's candidates start: list l's workgroups start at l * nb
         HIPCHK(hipGetLastError());
-        std::vector<int32_t> coff((size_t)nl + 1);
-        HIPCHK(hipMemcpyAsync(coff.data(), dcoff.p, sizeof(int32_t) * ((size_t)nl + 1), hipMemcpyDeviceToHost, s));
+        std::vector<int64_t> coff((size_t)nl + 1);
+        HIPCHK(hipMemcpyAsync(coff.data(), ct.off.p, sizeof(int64_t) * ((size_t)nl + 1), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
-        const int n_cand = coff[(size_t)nl];
+        const int n_cand = (int)coff[(size_t)nl];
         std::vector<int32_t> n_or((size_t)n_cand);
         Scratch ci, cf, dn_or, dori, dkmap;
         if (n_cand > 0) {
             if ((rc = ci.alloc(sizeof(int32_t) * 8 * (size_t)n_cand, s)) || (rc = cf.alloc(sizeof(float) * 8 * (size_t)n_cand, s)) ||
                 (rc = dn_or.alloc(sizeof(int32_t) * (size_t)n_cand, s)) || (rc = dori.alloc(sizeof(float) * 4 * (size_t)n_cand, s))) return rc;
-            k_sift_detect<true><<<dim3((unsigned)nb, (unsigned)nl), dim3(SF_TPB), 0, s>>>(d, n_items, keep.as<uint8_t>(), nullptr, base.as<int32_t>(), ci.as<int32_t>(),
+            k_sift_detect<true><<<dim3((unsigned)nb, (unsigned)nl), dim3(SF_TPB), 0, s>>>(d, n_items, keep.as<uint8_t>(), nullptr, ct.base.as<int32_t>(), ci.as<int32_t>(),
                                                                                           cf.as<float>());
             HIPCHK(hipGetLastError());
         }
@@ -539,7 +528,7 @@ int sift_core(const char* fn, int n_lists, int w, int h, const uint8_t* imgs, co
         std::vector<int2> kmap;
         for (int l = 0; l < nl; ++l) {
             int64_t nk = 0;
-            for (int c = coff[(size_t)l]; c < coff[(size_t)l + 1] && nk < p->max_features; ++c)
+            for (int c = (int)coff[(size_t)l]; c < coff[(size_t)l + 1] && nk < p->max_features; ++c)
                 for (int j = 0; j < n_or[(size_t)c] && nk < p->max_features; ++j, ++nk) kmap.push_back(make_int2(c, j));
             key_offsets[l0 + l + 1] = key_offsets[l0 + l] + nk;
         }
@@ -547,8 +536,7 @@ int sift_core(const char* fn, int n_lists, int w, int h, const uint8_t* imgs, co
         if (nk >= 0x7fffffffLL) return bad(fn, "2^31 - 1 or more keys in one chunk");
         fits = fits && total + nk <= capacity;
         if (fits && nk > 0) {
-            if ((rc = dkmap.alloc(sizeof(int2) * (size_t)nk, s))) return rc;
-            HIPCHK(hipMemcpyAsync(dkmap.p, kmap.data(), sizeof(int2) * (size_t)nk, hipMemcpyHostToDevice, s));
+            if ((rc = up_async(dkmap, kmap.data(), (size_t)nk, s))) return rc;
             k_sift_desc<<<dim3((unsigned)((nk + SF_WAVES - 1) / SF_WAVES)), dim3(SF_TPB), 0, s>>>(d, (int)nk, dkmap.as<int2>(), ci.as<int32_t>(), cf.as<float>(),
                                                                                                  dori.as<float>(), keys + 4 * total, descs + 128 * total);
             HIPCHK(hipGetLastError());

@@ -14,7 +14,7 @@
 //                   are applied there: m(i) = bestidx or -1.  Integer scores: nothing depends on scheduling, no atomics.
 //                   A and B fragments are both "16 bytes at 64 * kstep + 16 * (lane >> 4) of row lane & 15": whatever order the
 //                   instruction gives the 64 k of a step, both operands meet it with the same bytes, and a dot product does not care.
-//   k_sm_pair / k_sm_scan / k_sm_offsets / k_sm_rows : the mutual-best rule per list pair and an order-preserving compaction (the
+//   k_sm_pair / CompactTail / k_sm_rows : the mutual-best rule per list pair and an order-preserving compaction (compact.hip, the
 //                   scheme of views.hip's cull).  List pairs are numbered p = ((f1 * n2 + f2) * view_count + v1) * view_count + v2, so
 //                   the compacted rows ARE the buckets of rule 7 back to back: bucket k owns pairs [k * view_count^2, (k+1) * view_count^2).
 //
@@ -34,6 +34,7 @@ namespace {
 
 constexpr int SM_TPB = 256;
 constexpr int SM_WAVES = SM_TPB / 64;
+static_assert(SM_TPB == COMPACT_TPB, "k_sm_pair and k_sm_rows count and place per workgroup of the shared tail");
 constexpr int SM_ROWS_WAVE = 32;                          // query rows of a wave: two 16-row MFMA tiles
 constexpr int SM_ROWS = SM_WAVES * SM_ROWS_WAVE;          // ... of a workgroup
 constexpr int SM_TILE = 64;                               // descriptors of the other list per LDS stage
@@ -249,17 +250,6 @@ __global__ __launch_bounds__(SM_TPB) void k_sm_pair(SmDev d, int64_t npairs, uin
     if (threadIdx.x == 0) cnt[blockIdx.x] = k.total;
 }
 
-__global__ __launch_bounds__(SM_TPB) void k_sm_scan(const int32_t* __restrict__ cnt, int nb, int32_t* __restrict__ base) {
-    wg_scan_counts<SM_WAVES>(cnt, nb, base);
-}
-
-__global__ void k_sm_offsets(const int64_t* __restrict__ roff12, int64_t npairs, int64_t total, const uint8_t* __restrict__ keep,
-                             const int32_t* __restrict__ base, int nb, int64_t* __restrict__ pair_off) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p > npairs) return;
-    pair_off[p] = survivors_before(roff12[p], total, keep, base, nb, SM_TPB);
-}
-
 // rule 6; without keys (mvs_sift_match, the index form) a row is (i, j)
 __global__ __launch_bounds__(SM_TPB) void k_sm_rows(SmDev d, int64_t npairs, const uint8_t* __restrict__ keep, const int32_t* __restrict__ base,
                                                     const float* __restrict__ keys1, const float* __restrict__ keys2, int32_t* __restrict__ out) {
@@ -325,22 +315,16 @@ int sm_core(int n1, int n2, const mvs_sift_match_params* prm, const int64_t* off
         return MVS_E_INVALID_ARG;
     }
     if (work.empty()) return MVS_OK;                                     // nothing can match
-    Scratch q1, q2, s1, s2, doff1, doff2, dr12, dr21, dwork, m12, m21, dbg12, dbg21, keep, cnt, base, dpo, drows;
+    Scratch q1, q2, s1, s2, doff1, doff2, dr12, dr21, dwork, m12, m21, dbg12, dbg21, keep, drows;
+    CompactTail ct;
     const int nb = (int)((T12 + SM_TPB - 1) / SM_TPB);
     int rc;
     if ((rc = q1.alloc(128 * (size_t)tot1, s)) || (rc = q2.alloc(128 * (size_t)tot2, s)) || (rc = s1.alloc(sizeof(int32_t) * (size_t)tot1, s)) ||
-        (rc = s2.alloc(sizeof(int32_t) * (size_t)tot2, s)) || (rc = doff1.alloc(sizeof(int64_t) * ((size_t)L1 + 1), s)) ||
-        (rc = doff2.alloc(sizeof(int64_t) * ((size_t)L2 + 1), s)) || (rc = dr12.alloc(sizeof(int64_t) * ((size_t)NP + 1), s)) ||
-        (rc = dr21.alloc(sizeof(int64_t) * ((size_t)NP + 1), s)) || (rc = dwork.alloc(sizeof(int2) * work.size(), s)) ||
-        (rc = m12.alloc(sizeof(int32_t) * (size_t)T12, s)) || (rc = m21.alloc(sizeof(int32_t) * (size_t)T21, s)) || (rc = keep.alloc((size_t)T12, s)) ||
-        (rc = cnt.alloc(sizeof(int32_t) * (size_t)nb, s)) || (rc = base.alloc(sizeof(int32_t) * ((size_t)nb + 1), s)) ||
-        (rc = dpo.alloc(sizeof(int64_t) * ((size_t)NP + 1), s)) ||
+        (rc = s2.alloc(sizeof(int32_t) * (size_t)tot2, s)) || (rc = up_async(doff1, off1, (size_t)L1 + 1, s)) || (rc = up_async(doff2, off2, (size_t)L2 + 1, s)) ||
+        (rc = up_async(dr12, roff12.data(), roff12.size(), s)) || (rc = up_async(dr21, roff21.data(), roff21.size(), s)) ||
+        (rc = up_async(dwork, work.data(), work.size(), s)) || (rc = m12.alloc(sizeof(int32_t) * (size_t)T12, s)) ||
+        (rc = m21.alloc(sizeof(int32_t) * (size_t)T21, s)) || (rc = keep.alloc((size_t)T12, s)) || (rc = ct.alloc((size_t)nb, (size_t)NP, s)) ||
         (hook && ((rc = dbg12.alloc(sizeof(int32_t) * 3 * (size_t)T12, s)) || (rc = dbg21.alloc(sizeof(int32_t) * 3 * (size_t)T21, s))))) return rc;
-    HIPCHK(hipMemcpyAsync(doff1.p, off1, sizeof(int64_t) * ((size_t)L1 + 1), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(doff2.p, off2, sizeof(int64_t) * ((size_t)L2 + 1), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(dr12.p, roff12.data(), sizeof(int64_t) * ((size_t)NP + 1), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(dr21.p, roff21.data(), sizeof(int64_t) * ((size_t)NP + 1), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(dwork.p, work.data(), sizeof(int2) * work.size(), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemsetAsync(m12.p, 0xff, sizeof(int32_t) * (size_t)T12, s));                    // -1: a query nobody ran (the other list is empty)
     HIPCHK(hipMemsetAsync(m21.p, 0xff, sizeof(int32_t) * (size_t)T21, s));
     if (hook) {
@@ -355,11 +339,10 @@ int sm_core(int n1, int n2, const mvs_sift_match_params* prm, const int64_t* off
     d.m12 = m12.as<int32_t>(); d.m21 = m21.as<int32_t>(); d.dbg12 = hook ? dbg12.as<int32_t>() : nullptr; d.dbg21 = hook ? dbg21.as<int32_t>() : nullptr;
     d.T12 = T12; d.T21 = T21; d.n2 = n2; d.vc = vc; d.max_sift = prm->max_sift; d.distmax = prm->distmax; d.ratiomax = prm->ratiomax;
     k_sm_direction<<<dim3((unsigned)work.size()), dim3(SM_TPB), 0, s>>>(dwork.as<int2>(), d);
-    k_sm_pair<<<dim3((unsigned)nb), dim3(SM_TPB), 0, s>>>(d, NP, keep.as<uint8_t>(), cnt.as<int32_t>());
-    k_sm_scan<<<dim3(1), dim3(SM_TPB), 0, s>>>(cnt.as<int32_t>(), nb, base.as<int32_t>());
-    k_sm_offsets<<<dim3((unsigned)(NP / SM_TPB + 1)), dim3(SM_TPB), 0, s>>>(d.roff12, NP, T12, keep.as<uint8_t>(), base.as<int32_t>(), nb, dpo.as<int64_t>());
+    k_sm_pair<<<dim3((unsigned)nb), dim3(SM_TPB), 0, s>>>(d, NP, keep.as<uint8_t>(), ct.cnt.as<int32_t>());
+    ct.segments(nb, d.roff12, NP, T12, keep.as<uint8_t>(), s);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(pair_off.data(), dpo.p, sizeof(int64_t) * ((size_t)NP + 1), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(pair_off.data(), ct.off.p, sizeof(int64_t) * ((size_t)NP + 1), hipMemcpyDeviceToHost, s));
     if (hook) {
         int32_t* h12[3] = {hook->best12, hook->idx12, hook->second12};
         int32_t* h21[3] = {hook->best21, hook->idx21, hook->second21};
@@ -372,7 +355,7 @@ int sm_core(int n1, int n2, const mvs_sift_match_params* prm, const int64_t* off
     const int64_t total = pair_off[(size_t)NP];
     if (!want_rows || total == 0 || total > row_capacity) return MVS_OK;      // (the caller reports a capacity that is too small)
     if ((rc = drows.alloc(sizeof(int32_t) * width * (size_t)total, s))) return rc;
-    k_sm_rows<<<dim3((unsigned)nb), dim3(SM_TPB), 0, s>>>(d, NP, keep.as<uint8_t>(), base.as<int32_t>(), keys1, keys2, drows.as<int32_t>());
+    k_sm_rows<<<dim3((unsigned)nb), dim3(SM_TPB), 0, s>>>(d, NP, keep.as<uint8_t>(), ct.base.as<int32_t>(), keys1, keys2, drows.as<int32_t>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(rows, drows.p, sizeof(int32_t) * width * (size_t)total, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));

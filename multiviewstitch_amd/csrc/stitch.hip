@@ -186,17 +186,12 @@ int vis_cull_dev(const double* pts_dev, const int64_t* seg_off, int n_seg, int n
                 m.m = make_map34(scales[k0], R + 9 * k0, t + 3 * k0, 1);                                   // :1069
             }
         }
-    std::vector<CamDev> cd((size_t)std::max(n_cams, 1));
-    for (int c = 0; c < n_cams; ++c) cd[c] = make_camdev(&cams[c]);
+    std::vector<CamDev> cd;
     Scratch dseg, dmaps, doff, dcams, dcnt;
     int rc;
-    if ((rc = dseg.alloc(sizeof(int64_t) * (n_seg + 1), s)) || (rc = dmaps.alloc(sizeof(CullMap) * maps.size(), s)) ||
-        (rc = doff.alloc(sizeof(int32_t) * (n_seq + 1), s)) || (rc = dcams.alloc(sizeof(CamDev) * cd.size(), s)) ||
+    if ((rc = up_async(dseg, seg_off, (size_t)n_seg + 1, s)) || (rc = up_async(dmaps, maps.data(), maps.size(), s)) ||
+        (rc = up_async(doff, cam_off, (size_t)n_seq + 1, s)) || (rc = up_cams(dcams, cd, cams, (size_t)n_cams, s)) ||
         (rc = dcnt.alloc(sizeof(unsigned long long) * n_seg, s))) return rc;
-    HIPCHK(hipMemcpyAsync(dseg.p, seg_off, sizeof(int64_t) * (n_seg + 1), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(dmaps.p, maps.data(), sizeof(CullMap) * maps.size(), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(doff.p, cam_off, sizeof(int32_t) * (n_seq + 1), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(dcams.p, cd.data(), sizeof(CamDev) * cd.size(), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemsetAsync(dcnt.p, 0, sizeof(unsigned long long) * n_seg, s));
     int64_t maxn = 0;
     for (int g = 0; g < n_seg; ++g) maxn = std::max(maxn, seg_off[g + 1] - seg_off[g]);

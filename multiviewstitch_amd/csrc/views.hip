@@ -9,7 +9,7 @@
 //                     a later i overwrites an earlier one, without racing stores and without the xy array
 //   the background cull of the key points (Processor.cpp:567-600) for all view_count * n_frames lists of a sequence
 //     k_kc_decide   : one thread per key point, the cameras staged in LDS once per workgroup
-//     k_kc_scan / k_kc_offsets / k_kc_scatter : order-preserving compaction.  The lists lie back to back and so do the compacted
+//     CompactTail / k_kc_scatter : order-preserving compaction (compact.hip).  The lists lie back to back and so do the compacted
 //                     lists, so ONE exclusive scan of `keep` over all keys gives every survivor's place, and out_offsets are that
 //                     scan read at key_offsets; a wave copies each surviving 512-byte descriptor row
 //
@@ -29,6 +29,7 @@ namespace {
 
 constexpr int VW_TPB = 256;
 constexpr int VW_WAVES = VW_TPB / 64;
+static_assert(VW_TPB == COMPACT_TPB, "k_kc_decide and k_kc_scatter count and place per workgroup of the shared tail");
 constexpr int32_t GV_NONE = 0x7f7f7f7f;                  // what hipMemset(0x7f) leaves: no source pixel was in range
 constexpr int KC_CAMS = 64;                               // cameras staged in LDS at a time
 static_assert(sizeof(CamDev) % 8 == 0, "the cameras are staged as 8-byte words");
@@ -164,18 +165,6 @@ void gv_homography(const mvs_camera& c, int axis, double angle_deg, double* H) {
     mul33(K, T, H);
 }
 
-int check_cams(const char* fn, int32_t n_frames, const mvs_camera* cams) {
-    if (n_frames < 1) return bad(fn, "need n_frames >= 1");
-    if (!cams) return bad(fn, "cams is NULL");
-    const int w = cams[0].w, h = cams[0].h;
-    if (w <= 0 || h <= 0) return bad(fn, "need w, h > 0");
-    if (w > 65535 || h > 65535) return bad(fn, "w and h must not exceed 65535");
-    if ((int64_t)w * h > 0x7fffffffLL) return bad(fn, "w * h must fit the int32 of a texIndex entry");
-    for (int i = 1; i < n_frames; ++i)
-        if (cams[i].w != w || cams[i].h != h) return bad(fn, "every camera must have the same size");
-    return MVS_OK;
-}
-
 int check_views(const char* fn, int32_t n_frames, const mvs_camera* cams, const void* imgs, int32_t view_count, int32_t axis, const void* views,
                 const void* tex) {
     if (view_count < 1) return bad(fn, "need view_count >= 1");
@@ -201,8 +190,7 @@ int views_core(int n, const mvs_camera* cams, const uint8_t* imgs, int view_coun
         for (int k = 0; k < view_count; ++k) gv_homography(cams[f], axis, angle[(size_t)k], &H[9 * ((size_t)f * view_count + k)]);
     Scratch dH, dbb;
     int rc;
-    if ((rc = dH.alloc(sizeof(double) * H.size(), s)) || (rc = dbb.alloc(sizeof(int32_t) * 4 * (size_t)nfv, s))) return rc;
-    HIPCHK(hipMemcpyAsync(dH.p, H.data(), sizeof(double) * H.size(), hipMemcpyHostToDevice, s));
+    if ((rc = up_async(dH, H.data(), H.size(), s)) || (rc = dbb.alloc(sizeof(int32_t) * 4 * (size_t)nfv, s))) return rc;
     HIPCHK(hipMemsetAsync(dbb.p, 0x7f, sizeof(int32_t) * 4 * (size_t)nfv, s));
     const int bpa = h2 < 512 ? h2 : 512;
     const int bpb = (int)(((int64_t)w * h + VW_TPB - 1) / VW_TPB);
@@ -263,18 +251,6 @@ __global__ __launch_bounds__(VW_TPB) void k_kc_decide(const float* __restrict__ 
     if (tid == 0) cnt[blockIdx.x] = k.total;
 }
 
-// base[b] = survivors in the blocks before b, base[nb] = all survivors; one workgroup
-__global__ __launch_bounds__(VW_TPB) void k_kc_scan(const int32_t* __restrict__ cnt, int nb, int32_t* __restrict__ base) {
-    wg_scan_counts<VW_WAVES>(cnt, nb, base);
-}
-
-__global__ void k_kc_offsets(const int64_t* __restrict__ off, int nlists, int64_t total, const uint8_t* __restrict__ keep,
-                             const int32_t* __restrict__ base, int nb, int64_t* __restrict__ out_off) {
-    const int l = blockIdx.x * blockDim.x + threadIdx.x;
-    if (l > nlists) return;
-    out_off[l] = survivors_before(off[l], total, keep, base, nb, VW_TPB);
-}
-
 __global__ __launch_bounds__(VW_TPB) void k_kc_scatter(const float* __restrict__ keys, const float* __restrict__ descs, int64_t total,
                                                        const uint8_t* __restrict__ keep, const int32_t* __restrict__ base,
                                                        float* __restrict__ out_keys, float* __restrict__ out_descs) {
@@ -324,23 +300,19 @@ int cull_core(int n, int view_count, const mvs_camera* cams, const int64_t* off,
     const int64_t total = off[nl];
     if (total == 0) { std::memset(out_off, 0, sizeof(int64_t) * ((size_t)nl + 1)); return MVS_OK; }
     const int nb = (int)((total + VW_TPB - 1) / VW_TPB);
-    std::vector<CamDev> hc((size_t)n);
-    for (int i = 0; i < n; ++i) hc[(size_t)i] = make_camdev(cams + i);
-    Scratch dcam, doff, dkeep, dcnt, dbase, dooff;
+    std::vector<CamDev> hc;
+    Scratch dcam, doff, dkeep;
+    CompactTail ct;
     int rc;
-    if ((rc = dcam.alloc(sizeof(CamDev) * hc.size(), s)) || (rc = doff.alloc(sizeof(int64_t) * ((size_t)nl + 1), s)) ||
-        (rc = dcnt.alloc(sizeof(int32_t) * (size_t)nb, s)) || (rc = dbase.alloc(sizeof(int32_t) * ((size_t)nb + 1), s)) ||
-        (rc = dooff.alloc(sizeof(int64_t) * ((size_t)nl + 1), s)) || (!keep && (rc = dkeep.alloc((size_t)total, s)))) return rc;
+    if ((rc = up_cams(dcam, hc, cams, (size_t)n, s)) || (rc = up_async(doff, off, (size_t)nl + 1, s)) || (rc = ct.alloc((size_t)nb, (size_t)nl, s)) ||
+        (!keep && (rc = dkeep.alloc((size_t)total, s)))) return rc;
     if (!keep) keep = dkeep.as<uint8_t>();
-    HIPCHK(hipMemcpyAsync(dcam.p, hc.data(), sizeof(CamDev) * hc.size(), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(doff.p, off, sizeof(int64_t) * ((size_t)nl + 1), hipMemcpyHostToDevice, s));
     k_kc_decide<<<dim3((unsigned)nb), dim3(VW_TPB), 0, s>>>(keys, total, doff.as<int64_t>(), nl, view_count, n, dcam.as<CamDev>(), tex, depths, mask, mn, mx,
-                                                           keep, dcnt.as<int32_t>());
-    k_kc_scan<<<dim3(1), dim3(VW_TPB), 0, s>>>(dcnt.as<int32_t>(), nb, dbase.as<int32_t>());
-    k_kc_offsets<<<dim3((unsigned)(nl / VW_TPB + 1)), dim3(VW_TPB), 0, s>>>(doff.as<int64_t>(), nl, total, keep, dbase.as<int32_t>(), nb, dooff.as<int64_t>());
-    k_kc_scatter<<<dim3((unsigned)nb), dim3(VW_TPB), 0, s>>>(keys, descs, total, keep, dbase.as<int32_t>(), out_keys, out_descs);
+                                                           keep, ct.cnt.as<int32_t>());
+    ct.segments(nb, doff.as<int64_t>(), nl, total, keep, s);
+    k_kc_scatter<<<dim3((unsigned)nb), dim3(VW_TPB), 0, s>>>(keys, descs, total, keep, ct.base.as<int32_t>(), out_keys, out_descs);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out_off, dooff.p, sizeof(int64_t) * ((size_t)nl + 1), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(out_off, ct.off.p, sizeof(int64_t) * ((size_t)nl + 1), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return MVS_OK;
 }

@@ -5,9 +5,11 @@ over adjacent sequences of ``Processor::CalcSimilarityTransformationSeq`` (:629-
 through ``mvs_gen_new_views`` (Image3D::GenNewViews) and ``mvs_keypoint_cull`` (the background cull of the key points); the descriptor
 matching between them, FeatureProc::MatchFeature (R/FeatureProc/FeatureProc.cpp:77-130), through ``mvs_sift_match_lists``; the SIFT
 detection in front of the cull, FeatureProc::DetectFeature (:14-75,103-112), through ``mvs_sift_detect``; the point sampling between
-``CheckConsistency`` and the stitch tail, GeometryRec::RunPointSample (R/Processor/Processor.cpp:933-949), through ``mvs_point_sample``."""
+``CheckConsistency`` and the stitch tail, GeometryRec::RunPointSample (R/Processor/Processor.cpp:933-949), through ``mvs_point_sample``.
+The functions stand in pipeline order."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 
@@ -19,97 +21,103 @@ from . import srt as _srt
 from .deformation import _stats, default_params
 
 
-def Deform(model_obj, template_obj, parts_path, cam_R, dist_thres: float, out_obj, params: L.CParams | None = None) -> dict:
-    """./Result/Model.obj + ./Template/meanbody.obj + ./Template/part/parts -> ./Result/deform.obj.
-    ``cam_R`` is the rotation of cameras[0][0]; the view ray is its third row (R^T.col(2))."""
-    R = L.arr(cam_R, np.float64).reshape(9)
-    prm = params if params is not None else default_params()
-    st = L.CStats()
-    rc = L.check(L.lib().mvs_processor_deform(os.fsencode(model_obj), os.fsencode(template_obj), os.fsencode(parts_path), L.ptr(R),
-                                              float(dist_thres), C.byref(prm), os.fsencode(out_obj), C.byref(st)))
-    return _stats(st, rc)
+# ------------------------------------------------------------------ helpers ----
+def _is_dev(a):
+    return hasattr(a, "data_ptr")
 
 
-def StitchPointSets(npts_paths, scales, Rs, ts, cameras, out_dir, truncate: bool = False) -> np.ndarray:
-    """The tail of Processor::AlignmentSeq before Poisson (R/Processor/Processor.cpp:952-1040): each sequence's ``.npts`` culled,
-    compacted and mapped forward, written to ``out_dir``/PSR%d.obj and ``out_dir``/PSR.npts.  ``cameras[k]`` lists sequence k's
-    cameras.  By default sequence k keeps the reference's P_k points (the kept ones, then the untouched tail); ``truncate`` writes
-    the kept points only.  -> kept counts per sequence."""
-    n, s, R, t, coff, cams = L.seq_tables(scales, Rs, ts, cameras)
-    if len(npts_paths) != n:
-        raise L.MvsError(-1, f"{len(npts_paths)} paths for {n} sequences")
-    paths = (C.c_char_p * n)(*[os.fsencode(p) for p in npts_paths])
-    nk = np.empty(n, np.int64)
-    L.check(L.lib().mvs_processor_stitch_points(n, paths, L.ptr(s), L.ptr(R), L.ptr(t), L.ptr(coff), cams,
-                                                L.STITCH_TRUNCATE if truncate else 0, os.fsencode(out_dir), L.ptr(nk)))
-    return nk
+def _dev_ptr(a, dtype, what):
+    """device address of a contiguous torch tensor of the given dtype; None -> NULL"""
+    if a is None:
+        return None
+    if not _is_dev(a) or not a.is_contiguous() or str(a.dtype).split(".")[-1] != dtype:
+        raise L.MvsError(-1, f"the device form takes {what} as a contiguous {dtype} tensor")
+    return L.ptr(a)
 
 
-def CullPoissonModel(model_obj, scales, Rs, ts, cameras, out_obj, all_seq_proj: bool = True):
-    """The trim of the Poisson model (R/Processor/Processor.cpp:1057-1105): ReadObj (normals computed when the file has no `vn`),
-    the AllSeqProj cull with its facet remap, RetainConnectRegion, WriteObj.  -> (V, F) written."""
-    n, s, R, t, coff, cams = L.seq_tables(scales, Rs, ts, cameras)
-    V, F = C.c_int64(), C.c_int64()
-    L.check(L.lib().mvs_processor_cull_model(os.fsencode(model_obj), n, L.ptr(s), L.ptr(R), L.ptr(t), L.ptr(coff), cams,
-                                             int(bool(all_seq_proj)), os.fsencode(out_obj), C.byref(V), C.byref(F)))
-    return V.value, F.value
+def _out_like(like, shape, dtype):
+    """an uninitialised output of dtype ``dtype`` (its name) where ``like`` lives: a torch tensor on its device, or a numpy array"""
+    if _is_dev(like):
+        import torch
+        return torch.empty(shape, dtype=getattr(torch, dtype), device=like.device)
+    return np.empty(shape, dtype)
+
+
+def _params(struct, default, kw):
+    """``struct`` filled by the library's ``default`` function (mvs_<name>_default_params for struct mvs_<name>_params), then the
+    fields of ``kw`` replaced"""
+    prm = struct()
+    default(C.byref(prm))
+    for k, v in kw.items():
+        if k not in dict(struct._fields_):
+            raise L.MvsError(-1, f"{default.__name__.replace('_default', '')} has no field {k}")
+        setattr(prm, k, v)
+    return prm
+
+
+def _call_with_capacity(call, cap, off):
+    """``call(cap)`` -> (status, outputs) allocates outputs of ``cap`` rows and fills the offsets ``off``, whose last entry is the
+    number of rows the call needs.  A call that reports -1 with a larger need is made exactly once more, with that need."""
+    off[:] = -1
+    rc, out = call(cap)
+    if rc == -1 and off[-1] > cap:
+        cap = int(off[-1])
+        off[:] = -1
+        rc, out = call(cap)
+    L.check(rc)
+    return out
 
 
 def _view_tables(cameras, scales, Rs, ts):
     """seq_tables for Render / RenderViews: the SRT may be absent (None for all three: the world frame, NULL pointers)."""
     n = len(cameras)
     if scales is None and Rs is None and ts is None:
-        _, _, _, _, coff, cams = L.seq_tables(np.ones(n), np.tile(np.eye(3), (n, 1, 1)), np.zeros((n, 3)), cameras)
-        return n, None, None, None, coff, cams
+        return (n, None, None, None) + L.seq_cams(cameras)
     if scales is None or Rs is None or ts is None:
         raise L.MvsError(-1, "scales, Rs and ts must all be given or all be None")
     return L.seq_tables(scales, Rs, ts, cameras)
 
 
-def Render(deform_obj, srt_txt, cameras, result_dir, seq_dirs, znear: float = 0.01, zfar: float = 2000.0) -> int:
-    """The second half of `main -a 0` (R/Processor/Processor.cpp:1140-1192): SRT.txt and deform.obj read through float32, the mesh
-    mapped into every sequence's frame and written to ``result_dir``/render%d.obj, then every camera i of sequence k rendered to
-    ``seq_dirs[k]``DATA/Render/_depth<i>.raw (cameras[0][0]'s size for every raster).  ``cameras[k]`` lists sequence k's cameras.
-    -> views rendered."""
-    n, _, _, _, coff, cams = _view_tables(cameras, None, None, None)
-    if len(seq_dirs) != n:
-        raise L.MvsError(-1, f"{len(seq_dirs)} sequence dirs for {n} sequences")
-    dirs = (C.c_char_p * n)(*[os.fsencode(d) for d in seq_dirs])
-    nv = C.c_int64()
-    L.check(L.lib().mvs_processor_render(os.fsencode(deform_obj), os.fsencode(srt_txt), n, L.ptr(coff), cams, os.fsencode(result_dir), dirs,
-                                         float(znear), float(zfar), C.byref(nv)))
-    return nv.value
+def _key_lists(keys, descs, offsets, what):
+    """per-list arrays -> (offsets, flat keys, flat descs, device form?); flat device tensors with their offsets pass through"""
+    if offsets is not None:
+        off = L.arr(offsets, np.int64).reshape(-1)
+        if _is_dev(keys) != _is_dev(descs):
+            raise L.MvsError(-1, f"{what}: keys and descs must both be tensors on the GPU or both arrays")
+        if not _is_dev(keys):
+            keys, descs = L.arr(keys, np.float32).reshape(-1, 4), L.arr(descs, np.float32).reshape(-1, 128)
+        if len(off) < 1 or len(keys) < off[-1] or len(descs) < off[-1]:
+            raise L.MvsError(-1, f"{what}: keys / descs must hold key_offsets[-1] rows")
+        return off, keys, descs, _is_dev(keys)
+    if len(keys) != len(descs):
+        raise L.MvsError(-1, f"{what}: one descriptor list per key list")
+    kl = [L.arr(k, np.float32).reshape(-1, 4) for k in keys]
+    dl = [L.arr(d, np.float32).reshape(-1, 128) for d in descs]
+    if any(len(k) != len(d) for k, d in zip(kl, dl)):
+        raise L.MvsError(-1, f"{what}: a key list and its descriptor list differ in length")
+    off = np.zeros(len(kl) + 1, np.int64)
+    off[1:] = np.cumsum([len(k) for k in kl])
+    flat_k = np.concatenate(kl) if len(kl) else np.zeros((0, 4), np.float32)
+    flat_d = np.concatenate(dl) if len(dl) else np.zeros((0, 128), np.float32)
+    return off, np.ascontiguousarray(flat_k), np.ascontiguousarray(flat_d), False
 
 
-def RenderViews(points, facets, cameras, scales=None, Rs=None, ts=None, znear: float = 0.01, zfar: float = 2000.0,
-                out_dev: int | None = None, stream: int | None = None):
-    """Model2Depth::SetInput + Run (R/Model2Depth/Model2Depth.cpp:58-190): every camera of every sequence in one call.  Sequence k
-    renders the points mapped by its inverse SRT (1/s_k R_k^T (p - t_k)); without an SRT the points as given.  ``cameras[k]`` lists
-    sequence k's cameras; cameras[0][0]'s size (w0, h0) is the viewport of every view.  -> float32 [N, h0, w0] of inverse depths in
-    camera order.  With ``out_dev`` (device address of N*h0*w0 floats) the mesh arguments are device addresses, (address, count)
-    tuples as for RenderDepth, and nothing is returned."""
-    n, s, R, t, coff, cams = _view_tables(cameras, scales, Rs, ts)
-    if out_dev is not None:
-        (pp, V), (fp, F) = points, facets
-        L.check(L.lib().mvs_render_depth_views_dev(L.ptr(int(pp)), int(V), L.ptr(int(fp)), int(F), n, L.ptr(s), L.ptr(R), L.ptr(t),
-                                                   L.ptr(coff), cams, float(znear), float(zfar), L.ptr(int(out_dev)), L.ptr(stream)))
-        return None
-    pts = L.arr(points, np.float64).reshape(-1, 3)
-    fac = L.arr(facets, np.int32).reshape(-1, 3)
-    N = int(coff[-1])
-    w0, h0 = (int(cameras[0][0].w), int(cameras[0][0].h)) if N and len(cameras[0]) else (0, 0)
-    out = np.empty((N, h0, w0), np.float32)
-    L.check(L.lib().mvs_render_depth_views(L.ptr(pts), len(pts), L.ptr(fac), len(fac), n, L.ptr(s), L.ptr(R), L.ptr(t), L.ptr(coff), cams,
-                                           float(znear), float(zfar), L.ptr(out)))
-    return out
+def _raw_table(raw, n1, n2):
+    """raw[i][j] = (n_ij, 6) int32 -> (offsets int64[n1*n2 + 1], all rows back to back), pair k = i*n2 + j."""
+    flat = [L.arr(raw[i][j], np.int32).reshape(-1, 6) for i in range(n1) for j in range(n2)]
+    off = np.zeros(n1 * n2 + 1, np.int64)
+    off[1:] = np.cumsum([len(m) for m in flat])
+    allr = np.ascontiguousarray(np.concatenate(flat)) if off[-1] else np.zeros((0, 6), np.int32)
+    return off, allr
 
 
+# ------------------------------------------------------------------ consistency ----
 def CheckConsistencyCore(curcam, refcams, depth, refdepths, min_dsp: float, max_dsp: float, reproj_err: int) -> np.ndarray:
     """R/Processor/Processor.cpp:72-126 — float32 raster in, filtered float32 raster out (what SaveDepth writes to DATA/CHECK)."""
     d = L.arr(depth, np.float32)
     refs = [L.arr(r, np.float32) for r in refdepths]
     ptrs = (C.c_void_p * max(1, len(refs)))(*[r.ctypes.data for r in refs])
-    cams = (L.CCamera * max(1, len(refs)))(*[L.CCamera.of(c) for c in refcams])
+    cams = L.cam_array(refcams)
     out = np.empty_like(d)
     cc = L.CCamera.of(curcam)
     L.check(L.lib().mvs_check_consistency(L.ptr(d), C.byref(cc), len(refs), ptrs, cams, float(min_dsp), float(max_dsp), int(reproj_err),
@@ -120,7 +128,7 @@ def CheckConsistencyCore(curcam, refcams, depth, refdepths, min_dsp: float, max_
 def CheckConsistency(cameras, depths, min_dsp: float, max_dsp: float, reproj_err: int, out_dev: int | None = None, stream: int | None = None):
     """R/Processor/Processor.cpp:29-70 for one sequence: every frame against its two neighbours.
     ``depths`` is a float32 array [n, h, w] — or a device address when ``out_dev`` (a device address) is given."""
-    cams = (L.CCamera * len(cameras))(*[L.CCamera.of(c) for c in cameras])
+    cams = L.cam_array(cameras)
     if out_dev is not None:
         L.check(L.lib().mvs_check_consistency_seq_dev(len(cameras), L.ptr(int(depths)), cams, float(min_dsp), float(max_dsp), int(reproj_err),
                                                       L.ptr(int(out_dev)), L.ptr(stream)))
@@ -131,24 +139,11 @@ def CheckConsistency(cameras, depths, min_dsp: float, max_dsp: float, reproj_err
     return out
 
 
+# ------------------------------------------------------------------ point sample ----
 def point_sample_params(**kw) -> L.CPointSampleParams:
     """``mvs_point_sample_default_params`` (config.txt: MinDsp 0.0025, MaxDsp 0.3, MaxDspErr 0.01, MinConf 0.9, EdgeSzThres 4, PtSampRds 2,
     NbrFrmNum 2, NbrFrmStep 1) with the given fields replaced."""
-    prm = L.CPointSampleParams()
-    L.lib().mvs_point_sample_default_params(C.byref(prm))
-    for k, v in kw.items():
-        if k not in dict(L.CPointSampleParams._fields_):
-            raise L.MvsError(-1, f"mvs_point_sample_params has no field {k}")
-        setattr(prm, k, v)
-    return prm
-
-
-def _seq_cams(cameras):
-    """cam_off int32 [n_seq + 1] and the mvs_camera array of ``cameras[k]`` = sequence k's cameras"""
-    off = np.zeros(len(cameras) + 1, np.int32)
-    off[1:] = np.cumsum([len(c) for c in cameras])
-    flat = [L.CCamera.of(c) for seq in cameras for c in seq]
-    return off, (L.CCamera * max(1, len(flat)))(*flat)
+    return _params(L.CPointSampleParams, L.lib().mvs_point_sample_default_params, kw)
 
 
 def RunPointSample(cameras, depths, params: L.CPointSampleParams | None = None, stream: int | None = None, capacity: int | None = None):
@@ -162,10 +157,9 @@ def RunPointSample(cameras, depths, params: L.CPointSampleParams | None = None, 
     -> a list with, per sequence, (points [m, 3] float64, normals [m, 3] float64, frame [m] int32, pixel [m] int32) in the order of
     rule 8: the rows ``io.write_npts`` takes.  ``capacity`` (rows) sizes the first attempt, by default two frames' worth of cells per
     sequence (later frames are mostly covered); a call that finds more points is repeated once with the right size."""
-    import contextlib
     prm = params if params is not None else point_sample_params()
     n = len(cameras)
-    off, cams = _seq_cams(cameras)
+    off, cams = L.seq_cams(cameras)
     need = sum(len(c) * int(c[0].w) * int(c[0].h) for c in cameras if len(c))
     whole = _is_dev(depths)
     if whole:
@@ -187,33 +181,24 @@ def RunPointSample(cameras, depths, params: L.CPointSampleParams | None = None, 
             order = torch.cuda.stream(torch.cuda.ExternalStream(int(stream)))
     r = max(1, int(prm.pt_samp_rds))
     cap = int(capacity) if capacity is not None else sum(2 * (-(-int(c[0].w) // r)) * (-(-int(c[0].h) // r)) for c in cameras if len(c))
-    cap = max(1, cap)
     with order:
         if dev:
             flat = depths if whole else (torch.cat([d.reshape(-1) for d in depths]) if n > 1 else depths[0].reshape(-1))
             if flat.numel() == 0:
                 flat = torch.zeros(1, dtype=torch.float32, device=flat.device)
-            dptr = _dev_ptr(flat, "float32", "depths")
+            dptr, fn, tail = _dev_ptr(flat, "float32", "depths"), L.lib().mvs_point_sample_dev, (L.ptr(stream),)
         else:
             flat = np.concatenate([L.arr(d, np.float32).reshape(-1) for d in depths]) if n else np.zeros(1, np.float32)
             if flat.size == 0:
                 flat = np.zeros(1, np.float32)
-        for attempt in range(2):
-            soff[:] = -1
-            if dev:
-                pts, nrm = (torch.empty((cap, 3), dtype=torch.float64, device=flat.device) for _ in range(2))
-                frm, pix = (torch.empty(cap, dtype=torch.int32, device=flat.device) for _ in range(2))
-                rc = L.lib().mvs_point_sample_dev(n, L.ptr(off), cams, dptr, C.byref(prm), L.ptr(soff), L.ptr(int(pts.data_ptr())),
-                                                  L.ptr(int(nrm.data_ptr())), L.ptr(int(frm.data_ptr())), L.ptr(int(pix.data_ptr())), cap, L.ptr(stream))
-            else:
-                pts, nrm, frm, pix = np.empty((cap, 3)), np.empty((cap, 3)), np.empty(cap, np.int32), np.empty(cap, np.int32)
-                rc = L.lib().mvs_point_sample(n, L.ptr(off), cams, L.ptr(flat), C.byref(prm), L.ptr(soff), L.ptr(pts), L.ptr(nrm), L.ptr(frm), L.ptr(pix), cap)
-            if rc == -1 and attempt == 0 and soff[-1] > cap:                   # seq_offsets holds the need
-                cap = int(soff[-1])
-                continue
-            L.check(rc)
-            break
-    return [tuple(a[soff[k]:soff[k + 1]] for a in (pts, nrm, frm, pix)) for k in range(n)]
+            dptr, fn, tail = L.ptr(flat), L.lib().mvs_point_sample, ()
+
+        def call(cap):
+            out = tuple(_out_like(flat, shape, dt) for shape, dt in (((cap, 3), "float64"), ((cap, 3), "float64"), (cap, "int32"), (cap, "int32")))
+            return fn(n, L.ptr(off), cams, dptr, C.byref(prm), L.ptr(soff), *[L.ptr(a) for a in out], cap, *tail), out
+
+        out = _call_with_capacity(call, max(1, cap), soff)
+    return [tuple(a[soff[k]:soff[k + 1]] for a in out) for k in range(n)]
 
 
 def PointSampleFiles(seq_dirs, cameras, params: L.CPointSampleParams | None = None, npts_paths=None) -> np.ndarray:
@@ -222,7 +207,7 @@ def PointSampleFiles(seq_dirs, cameras, params: L.CPointSampleParams | None = No
     n = len(cameras)
     if len(seq_dirs) != n or (npts_paths is not None and len(npts_paths) != n):
         raise L.MvsError(-1, f"{len(seq_dirs)} sequence dirs for {n} sequences")
-    off, cams = _seq_cams(cameras)
+    off, cams = L.seq_cams(cameras)
     dirs = (C.c_char_p * max(1, n))(*[os.fsencode(d) for d in seq_dirs])
     outs = (C.c_char_p * max(1, n))(*[os.fsencode(p) if p is not None else None for p in npts_paths]) if npts_paths is not None else None
     prm = params if params is not None else point_sample_params()
@@ -231,40 +216,7 @@ def PointSampleFiles(seq_dirs, cameras, params: L.CPointSampleParams | None = No
     return cnt
 
 
-def RenderDepth(points, facets, camera, znear: float = 0.01, zfar: float = 2000.0, out_dev: int | None = None, stream: int | None = None):
-    """Model2Depth::RenderDepth for one camera (R/Model2Depth/Model2Depth.cpp:58-156) without GLUT: float32 raster [h, w]
-    of inverse depths, 0 where no triangle covers the pixel.  With ``out_dev`` the mesh arguments are device addresses
-    (points: V*3 float64, facets: F*3 int32 — pass (address, count) tuples) and nothing is returned."""
-    cc = L.CCamera.of(camera)
-    if out_dev is not None:
-        (pp, V), (fp, F) = points, facets
-        L.check(L.lib().mvs_render_depth_dev(L.ptr(int(pp)), int(V), L.ptr(int(fp)), int(F), C.byref(cc), float(znear), float(zfar),
-                                             L.ptr(int(out_dev)), L.ptr(stream)))
-        return None
-    pts = L.arr(points, np.float64).reshape(-1, 3)
-    fac = L.arr(facets, np.int32).reshape(-1, 3)
-    out = np.empty((camera.h, camera.w), np.float32)
-    L.check(L.lib().mvs_render_depth(L.ptr(pts), len(pts), L.ptr(fac), len(fac), C.byref(cc), float(znear), float(zfar), L.ptr(out)))
-    return out
-
-
-def _cam_array(cameras):
-    return (L.CCamera * max(1, len(cameras)))(*[L.CCamera.of(c) for c in cameras])
-
-
-def _is_dev(a):
-    return hasattr(a, "data_ptr")
-
-
-def _dev_ptr(a, dtype, what):
-    """device address of a contiguous torch tensor of the given dtype; None -> NULL"""
-    if a is None:
-        return None
-    if not _is_dev(a) or not a.is_contiguous() or str(a.dtype).split(".")[-1] != dtype:
-        raise L.MvsError(-1, f"the device form takes {what} as a contiguous {dtype} tensor")
-    return L.ptr(int(a.data_ptr()))
-
-
+# ------------------------------------------------------------------ views and cull ----
 def GenNewViews(cameras, imgs, view_count: int, axis: int, rot_angle: float, stream: int | None = None):
     """Image3D::GenNewViews (R/Image3D/Image3D.cpp:109-222) for every frame of one sequence in one call: ``view_count`` rotated
     homography views of each base image (rotation about row ``axis`` of the camera's R, ``rot_angle`` degrees apart) and each view's
@@ -273,22 +225,19 @@ def GenNewViews(cameras, imgs, view_count: int, axis: int, rot_angle: float, str
     -> (views [frames, view_count, h, w, 3] uint8, tex [frames, view_count, h*w] int32: the ``tex`` of ``MatchFilterPairs``).
     A pixel nothing paints is (0, 0, 0) with tex = -1; the views are rasters, the reference's JPEG round trip is not reproduced."""
     n = len(cameras)
-    cams = _cam_array(cameras)
+    cams = L.cam_array(cameras)
     w, h = (int(cameras[0].w), int(cameras[0].h)) if n else (0, 0)
     vc = max(0, int(view_count))
     if tuple(imgs.shape) != (n, h, w, 3):
         raise L.MvsError(-1, f"imgs must be [frames = {n}, h = {h}, w = {w}, 3]")
     if _is_dev(imgs):
-        import torch
-        views = torch.empty((n, vc, h, w, 3), dtype=torch.uint8, device=imgs.device)
-        tex = torch.empty((n, vc, h * w), dtype=torch.int32, device=imgs.device)
-        L.check(L.lib().mvs_gen_new_views_dev(n, cams, _dev_ptr(imgs, "uint8", "imgs"), int(view_count), int(axis), float(rot_angle),
-                                              L.ptr(int(views.data_ptr())), L.ptr(int(tex.data_ptr())), L.ptr(stream)))
-        return views, tex
-    img = L.arr(imgs, np.uint8)
-    views = np.empty((n, vc, h, w, 3), np.uint8)
-    tex = np.empty((n, vc, h * w), np.int32)
-    L.check(L.lib().mvs_gen_new_views(n, cams, L.ptr(img), int(view_count), int(axis), float(rot_angle), L.ptr(views), L.ptr(tex)))
+        iptr, fn, tail = _dev_ptr(imgs, "uint8", "imgs"), L.lib().mvs_gen_new_views_dev, (L.ptr(stream),)
+    else:
+        imgs = L.arr(imgs, np.uint8)
+        iptr, fn, tail = L.ptr(imgs), L.lib().mvs_gen_new_views, ()
+    views = _out_like(imgs, (n, vc, h, w, 3), "uint8")
+    tex = _out_like(imgs, (n, vc, h * w), "int32")
+    L.check(fn(n, cams, iptr, int(view_count), int(axis), float(rot_angle), L.ptr(views), L.ptr(tex), *tail))
     return views, tex
 
 
@@ -300,21 +249,16 @@ def KeypointCull(cameras, view_count: int, key_offsets, keys, descs, tex, depths
     (the device form, ``stream`` = the HIP stream that produced them).
     -> dict(keep [total] uint8, out_offsets int64, keys [kept, 4], descs [kept, 128] or None), list i at out_offsets[i]:out_offsets[i+1]."""
     n = len(cameras)
-    cams = _cam_array(cameras)
+    cams = L.cam_array(cameras)
     off = L.arr(key_offsets, np.int64).reshape(-1)
     if len(off) != n * int(view_count) + 1:
         raise L.MvsError(-1, "key_offsets must hold frames * view_count + 1 entries")
     total = int(off[-1])
     ooff = np.zeros(len(off), np.int64)
     if _is_dev(keys):
-        import torch
-        keep = torch.empty(max(1, total), dtype=torch.uint8, device=keys.device)
-        ok = torch.empty((max(1, total), 4), dtype=torch.float32, device=keys.device)
-        od = torch.empty((max(1, total), 128), dtype=torch.float32, device=keys.device) if descs is not None else None
-        L.check(L.lib().mvs_keypoint_cull_dev(n, int(view_count), cams, L.ptr(off), _dev_ptr(keys, "float32", "keys"), _dev_ptr(descs, "float32", "descs"),
-                                              _dev_ptr(tex, "int32", "tex"), _dev_ptr(depths, "float32", "depths"), float(min_dsp), float(max_dsp),
-                                              _dev_ptr(masks, "uint8", "masks"), L.ptr(int(keep.data_ptr())), L.ptr(ooff), L.ptr(int(ok.data_ptr())),
-                                              L.ptr(int(od.data_ptr())) if od is not None else None, L.ptr(stream)))
+        ptrs = [_dev_ptr(a, dt, w) for a, dt, w in ((keys, "float32", "keys"), (descs, "float32", "descs"), (tex, "int32", "tex"),
+                                                  (depths, "float32", "depths"), (masks, "uint8", "masks"))]
+        fn, tail = L.lib().mvs_keypoint_cull_dev, (L.ptr(stream),)
     else:
         keys = L.arr(keys, np.float32).reshape(-1, 4)
         descs = L.arr(descs, np.float32).reshape(-1, 128) if descs is not None else None
@@ -324,11 +268,13 @@ def KeypointCull(cameras, view_count: int, key_offsets, keys, descs, tex, depths
         if len(keys) != total or (descs is not None and len(descs) != total) or tex.size != n * int(view_count) * npx or depths.size != n * npx or \
                 (masks is not None and masks.size != n * npx):
             raise L.MvsError(-1, "keys / descs must hold key_offsets[-1] rows; tex, depths and masks one raster per view / frame")
-        keep = np.zeros(max(1, total), np.uint8)
-        ok = np.empty((max(1, total), 4), np.float32)
-        od = np.empty((max(1, total), 128), np.float32) if descs is not None else None
-        L.check(L.lib().mvs_keypoint_cull(n, int(view_count), cams, L.ptr(off), L.ptr(keys), L.ptr(descs), L.ptr(tex), L.ptr(depths), float(min_dsp),
-                                          float(max_dsp), L.ptr(masks), L.ptr(keep), L.ptr(ooff), L.ptr(ok), L.ptr(od)))
+        ptrs = [L.ptr(a) for a in (keys, descs, tex, depths, masks)]
+        fn, tail = L.lib().mvs_keypoint_cull, ()
+    keep = _out_like(keys, max(1, total), "uint8")
+    ok = _out_like(keys, (max(1, total), 4), "float32")
+    od = _out_like(keys, (max(1, total), 128), "float32") if descs is not None else None
+    L.check(fn(n, int(view_count), cams, L.ptr(off), *ptrs[:4], float(min_dsp), float(max_dsp), ptrs[4], L.ptr(keep), L.ptr(ooff), L.ptr(ok),
+               L.ptr(od), *tail))
     kept = int(ooff[-1])
     return dict(keep=keep[:total], out_offsets=ooff, keys=ok[:kept], descs=od[:kept] if od is not None else None)
 
@@ -354,16 +300,11 @@ def CullKeypoints(cameras, depths, tex, keys, descs, min_dsp: float, max_dsp: fl
     return out_keys, ([r["descs"][o[i]:o[i + 1]].copy() for i in range(len(lists))] if descs is not None else None)
 
 
+# ------------------------------------------------------------------ SIFT ----
 def sift_params(**kw) -> L.CSiftParams:
     """``mvs_sift_default_params`` (first_octave -1, 3 DoG levels, 2 orientations, thresholds 0.02 / 10, sigma 1.6 / 0.5, no margins,
     no feature cap) with the given fields replaced; hl, hr, vl, vr are ParamParser's margin ratios."""
-    prm = L.CSiftParams()
-    L.lib().mvs_sift_default_params(C.byref(prm))
-    for k, v in kw.items():
-        if k not in dict(L.CSiftParams._fields_):
-            raise L.MvsError(-1, f"mvs_sift_params has no field {k}")
-        setattr(prm, k, v)
-    return prm
+    return _params(L.CSiftParams, L.lib().mvs_sift_default_params, kw)
 
 
 def DetectFeature(views, params: L.CSiftParams | None = None, stream: int | None = None, capacity: int | None = None):
@@ -383,23 +324,16 @@ def DetectFeature(views, params: L.CSiftParams | None = None, stream: int | None
     dev = _is_dev(views)
     if not dev:
         views = L.arr(views, np.uint8)
-    cap = max(1, int(capacity) if capacity is not None else n * min(int(prm.max_features), 2048))
-    for attempt in range(2):
-        off[:] = -1
+
+    def call(cap):
+        keys, descs = _out_like(views, (cap, 4), "float32"), _out_like(views, (cap, 128), "float32")
         if dev:
-            import torch
-            keys = torch.empty((cap, 4), dtype=torch.float32, device=views.device)
-            descs = torch.empty((cap, 128), dtype=torch.float32, device=views.device)
-            rc = L.lib().mvs_sift_detect_dev(n, w, h, _dev_ptr(views, "uint8", "views"), C.byref(prm), L.ptr(off), L.ptr(int(keys.data_ptr())),
-                                             L.ptr(int(descs.data_ptr())), cap, L.ptr(stream))
+            rc = L.lib().mvs_sift_detect_dev(n, w, h, _dev_ptr(views, "uint8", "views"), C.byref(prm), L.ptr(off), L.ptr(keys), L.ptr(descs), cap, L.ptr(stream))
         else:
-            keys, descs = np.empty((cap, 4), np.float32), np.empty((cap, 128), np.float32)
             rc = L.lib().mvs_sift_detect(n, w, h, L.ptr(views), C.byref(prm), L.ptr(off), L.ptr(keys), L.ptr(descs), cap)
-        if rc == -1 and attempt == 0 and off[-1] > cap:           # key_offsets holds the need
-            cap = int(off[-1])
-            continue
-        L.check(rc)
-        break
+        return rc, (keys, descs)
+
+    keys, descs = _call_with_capacity(call, max(1, int(capacity) if capacity is not None else n * min(int(prm.max_features), 2048)), off)
     total = int(off[-1])
     if dev:
         return off, keys[:total], descs[:total]
@@ -436,24 +370,7 @@ def LoadSequenceModels(cameras, imgs, depths, view_count: int, axis: int, rot_an
     return out
 
 
-def MatchFilter(raw, tex1, valid1, tex2, valid2, img1, img2, ssd_win: int, ssd_err: float, sample_interval: int):
-    """The duplicate / SSD / gap cascade in front of RemoveOutliers (R/Processor/Processor.cpp:644-735) for the matches
-    between the generated views of one frame pair.  raw [n, 6] = (view1, u1, v1, view2, u2, v2); tex [views, h*w] int32,
-    valid [h*w] uint8, img [h, w, 3] uint8.  -> (matches [m, 4] = (u1, v1, u2, v2), sizes after the three stages)."""
-    raw = L.arr(raw, np.int32).reshape(-1, 6)
-    tex1, tex2 = L.arr(tex1, np.int32), L.arr(tex2, np.int32)
-    valid1, valid2 = L.arr(valid1, np.uint8), L.arr(valid2, np.uint8)
-    img1, img2 = L.arr(img1, np.uint8), L.arr(img2, np.uint8)
-    h, w = img1.shape[:2]
-    prm = L.CMatchFilterParams(w, h, tex1.shape[0], int(ssd_win), float(ssd_err), int(sample_interval), 0)
-    out = np.empty((max(1, len(raw)), 4), np.int32)
-    n_out = C.c_int64()
-    cnt = np.zeros(3, np.int64)
-    L.check(L.lib().mvs_match_filter(L.ptr(raw), len(raw), L.ptr(tex1), L.ptr(valid1), L.ptr(tex2), L.ptr(valid2), L.ptr(img1), L.ptr(img2),
-                                     C.byref(prm), L.ptr(out), C.byref(n_out), L.ptr(cnt)))
-    return out[:n_out.value].copy(), cnt
-
-
+# ------------------------------------------------------------------ match ----
 def MatchFeatureSingleView(descs1, descs2, distmax: float = 0.7, ratiomax: float = 0.8, max_sift: int = 4096) -> np.ndarray:
     """SiftMatchGPU::GetSiftMatch for one list pair (R/FeatureProc/FeatureProc.cpp:77-101, in index form): descs [n, 128] float32.
     -> [m, 2] int32 (i, j), the mutual best matches for ascending i (the rules: include/mvs.h, mvs_sift_match_lists)."""
@@ -463,30 +380,6 @@ def MatchFeatureSingleView(descs1, descs2, distmax: float = 0.7, ratiomax: float
     n = C.c_int64()
     L.check(L.lib().mvs_sift_match(len(d1), L.ptr(d1), len(d2), L.ptr(d2), C.byref(prm), L.ptr(buf), C.byref(n)))
     return buf[:n.value].copy()
-
-
-def _key_lists(keys, descs, offsets, what):
-    """per-list arrays -> (offsets, flat keys, flat descs, device form?); flat device tensors with their offsets pass through"""
-    if offsets is not None:
-        off = L.arr(offsets, np.int64).reshape(-1)
-        if _is_dev(keys) != _is_dev(descs):
-            raise L.MvsError(-1, f"{what}: keys and descs must both be tensors on the GPU or both arrays")
-        if not _is_dev(keys):
-            keys, descs = L.arr(keys, np.float32).reshape(-1, 4), L.arr(descs, np.float32).reshape(-1, 128)
-        if len(off) < 1 or len(keys) < off[-1] or len(descs) < off[-1]:
-            raise L.MvsError(-1, f"{what}: keys / descs must hold key_offsets[-1] rows")
-        return off, keys, descs, _is_dev(keys)
-    if len(keys) != len(descs):
-        raise L.MvsError(-1, f"{what}: one descriptor list per key list")
-    kl = [L.arr(k, np.float32).reshape(-1, 4) for k in keys]
-    dl = [L.arr(d, np.float32).reshape(-1, 128) for d in descs]
-    if any(len(k) != len(d) for k, d in zip(kl, dl)):
-        raise L.MvsError(-1, f"{what}: a key list and its descriptor list differ in length")
-    off = np.zeros(len(kl) + 1, np.int64)
-    off[1:] = np.cumsum([len(k) for k in kl])
-    flat_k = np.concatenate(kl) if len(kl) else np.zeros((0, 4), np.float32)
-    flat_d = np.concatenate(dl) if len(dl) else np.zeros((0, 128), np.float32)
-    return off, np.ascontiguousarray(flat_k), np.ascontiguousarray(flat_d), False
 
 
 def MatchFeature(keys1, descs1, keys2, descs2, view_count: int, distmax: float = 0.7, ratiomax: float = 0.8, max_sift: int = 4096,
@@ -520,13 +413,23 @@ def MatchFeature(keys1, descs1, keys2, descs2, view_count: int, distmax: float =
     return [[raw[roff[i * n2 + j]:roff[i * n2 + j + 1]].copy() for j in range(n2)] for i in range(n1)]
 
 
-def _raw_table(raw, n1, n2):
-    """raw[i][j] = (n_ij, 6) int32 -> (offsets int64[n1*n2 + 1], all rows back to back), pair k = i*n2 + j."""
-    flat = [L.arr(raw[i][j], np.int32).reshape(-1, 6) for i in range(n1) for j in range(n2)]
-    off = np.zeros(n1 * n2 + 1, np.int64)
-    off[1:] = np.cumsum([len(m) for m in flat])
-    allr = np.ascontiguousarray(np.concatenate(flat)) if off[-1] else np.zeros((0, 6), np.int32)
-    return off, allr
+# ------------------------------------------------------------------ filter and SRT ----
+def MatchFilter(raw, tex1, valid1, tex2, valid2, img1, img2, ssd_win: int, ssd_err: float, sample_interval: int):
+    """The duplicate / SSD / gap cascade in front of RemoveOutliers (R/Processor/Processor.cpp:644-735) for the matches
+    between the generated views of one frame pair.  raw [n, 6] = (view1, u1, v1, view2, u2, v2); tex [views, h*w] int32,
+    valid [h*w] uint8, img [h, w, 3] uint8.  -> (matches [m, 4] = (u1, v1, u2, v2), sizes after the three stages)."""
+    raw = L.arr(raw, np.int32).reshape(-1, 6)
+    tex1, tex2 = L.arr(tex1, np.int32), L.arr(tex2, np.int32)
+    valid1, valid2 = L.arr(valid1, np.uint8), L.arr(valid2, np.uint8)
+    img1, img2 = L.arr(img1, np.uint8), L.arr(img2, np.uint8)
+    h, w = img1.shape[:2]
+    prm = L.CMatchFilterParams(w, h, tex1.shape[0], int(ssd_win), float(ssd_err), int(sample_interval), 0)
+    out = np.empty((max(1, len(raw)), 4), np.int32)
+    n_out = C.c_int64()
+    cnt = np.zeros(3, np.int64)
+    L.check(L.lib().mvs_match_filter(L.ptr(raw), len(raw), L.ptr(tex1), L.ptr(valid1), L.ptr(tex2), L.ptr(valid2), L.ptr(img1), L.ptr(img2),
+                                     C.byref(prm), L.ptr(out), C.byref(n_out), L.ptr(cnt)))
+    return out[:n_out.value].copy(), cnt
 
 
 def MatchFilterPairs(raw, tex1, valid1, tex2, valid2, imgs1, imgs2, ssd_win: int, ssd_err: float, sample_interval: int, stream: int | None = None):
@@ -535,18 +438,18 @@ def MatchFilterPairs(raw, tex1, valid1, tex2, valid2, imgs1, imgs2, ssd_win: int
     valid [frames, h*w] uint8, imgs [frames, h, w, 3] uint8 — numpy arrays, or all six contiguous torch tensors on the GPU (the device
     form; ``stream`` is then the HIP stream that produced them).  -> (matches[i][j] = (m_ij, 4) int32 (u1, v1, u2, v2),
     sizes after the three stages int64 [n1, n2, 3])."""
-    dev = hasattr(tex1, "data_ptr")
+    names = ("tex1", "valid1", "tex2", "valid2", "imgs1", "imgs2")
+    types = ("int32", "uint8", "int32", "uint8", "uint8", "uint8")
     stacks = (tex1, valid1, tex2, valid2, imgs1, imgs2)
-    if dev:
-        if not all(hasattr(a, "data_ptr") and a.is_contiguous() for a in stacks):
+    if _is_dev(tex1):
+        if any(a is None for a in stacks):
             raise L.MvsError(-1, "the device form takes six contiguous tensors")
-        want = ("int32", "uint8", "int32", "uint8", "uint8", "uint8")
-        if any(str(a.dtype).split(".")[-1] != d for a, d in zip(stacks, want)):
-            raise L.MvsError(-1, "tex must be int32, valid and imgs uint8")
-        ptrs = [L.ptr(int(a.data_ptr())) for a in stacks]
+        ptrs = [_dev_ptr(a, dt, w) for a, dt, w in zip(stacks, types, names)]
+        fn, tail = L.lib().mvs_match_filter_pairs_dev, (L.ptr(stream),)
     else:
-        stacks = tuple(L.arr(a, dt) for a, dt in zip(stacks, (np.int32, np.uint8, np.int32, np.uint8, np.uint8, np.uint8)))
+        stacks = tuple(L.arr(a, dt) for a, dt in zip(stacks, types))
         ptrs = [L.ptr(a) for a in stacks]
+        fn, tail = L.lib().mvs_match_filter_pairs, ()
     n1, n2 = int(stacks[4].shape[0]), int(stacks[5].shape[0])
     h, w = int(stacks[4].shape[1]), int(stacks[4].shape[2])
     off, allr = _raw_table(raw, n1, n2)
@@ -554,11 +457,7 @@ def MatchFilterPairs(raw, tex1, valid1, tex2, valid2, imgs1, imgs2, ssd_win: int
     out = np.empty((max(1, len(allr)), 4), np.int32)
     ooff = np.zeros(n1 * n2 + 1, np.int64)
     cnt = np.zeros((n1, n2, 3), np.int64)
-    if dev:
-        L.check(L.lib().mvs_match_filter_pairs_dev(n1, n2, L.ptr(off), L.ptr(allr), *ptrs, C.byref(prm), L.ptr(out), L.ptr(ooff), L.ptr(cnt),
-                                                   L.ptr(stream)))
-    else:
-        L.check(L.lib().mvs_match_filter_pairs(n1, n2, L.ptr(off), L.ptr(allr), *ptrs, C.byref(prm), L.ptr(out), L.ptr(ooff), L.ptr(cnt)))
+    L.check(fn(n1, n2, L.ptr(off), L.ptr(allr), *ptrs, C.byref(prm), L.ptr(out), L.ptr(ooff), L.ptr(cnt), *tail))
     return [[out[ooff[i * n2 + j]:ooff[i * n2 + j + 1]].copy() for j in range(n2)] for i in range(n1)], cnt
 
 
@@ -581,8 +480,7 @@ def SequencePairSRT(cams1, cams2, depths1, depths2, raw, tex1, tex2, imgs1, imgs
     off, allr = _raw_table(raw, n1, n2)
     prm = L.CSeqPairParams(L.CMatchFilterParams(w, h, tex1.shape[1], int(ssd_win), float(ssd_err), int(sample_interval), 0), float(min_dsp),
                            float(max_dsp), int(min_match_count), int(ransac_iters), float(pixel_err), float(adapt_ratio))
-    c1 = (L.CCamera * n1)(*[L.CCamera.of(c) for c in cams1])
-    c2 = (L.CCamera * n2)(*[L.CCamera.of(c) for c in cams2])
+    c1, c2 = L.cam_array(cams1), L.cam_array(cams2)
     st, f1, f2, s, res, ns = C.c_uint32(state), C.c_int32(), C.c_int32(), C.c_double(), C.c_double(), C.c_int64()
     R, t = np.empty((3, 3)), np.empty(3)
     cnt = np.zeros((n1, n2, 3), np.int64)
@@ -628,3 +526,97 @@ def CalcSimilarityTransformationSeq(sequences, params: dict, state, srt_txt=None
     if srt_txt is not None:
         _io.write_srt_txt(srt_txt, scales, Rs, ts)
     return scales, Rs, ts, select
+
+
+# ------------------------------------------------------------------ stitch tail ----
+def StitchPointSets(npts_paths, scales, Rs, ts, cameras, out_dir, truncate: bool = False) -> np.ndarray:
+    """The tail of Processor::AlignmentSeq before Poisson (R/Processor/Processor.cpp:952-1040): each sequence's ``.npts`` culled,
+    compacted and mapped forward, written to ``out_dir``/PSR%d.obj and ``out_dir``/PSR.npts.  ``cameras[k]`` lists sequence k's
+    cameras.  By default sequence k keeps the reference's P_k points (the kept ones, then the untouched tail); ``truncate`` writes
+    the kept points only.  -> kept counts per sequence."""
+    n, s, R, t, coff, cams = L.seq_tables(scales, Rs, ts, cameras)
+    if len(npts_paths) != n:
+        raise L.MvsError(-1, f"{len(npts_paths)} paths for {n} sequences")
+    paths = (C.c_char_p * n)(*[os.fsencode(p) for p in npts_paths])
+    nk = np.empty(n, np.int64)
+    L.check(L.lib().mvs_processor_stitch_points(n, paths, L.ptr(s), L.ptr(R), L.ptr(t), L.ptr(coff), cams,
+                                                L.STITCH_TRUNCATE if truncate else 0, os.fsencode(out_dir), L.ptr(nk)))
+    return nk
+
+
+def CullPoissonModel(model_obj, scales, Rs, ts, cameras, out_obj, all_seq_proj: bool = True):
+    """The trim of the Poisson model (R/Processor/Processor.cpp:1057-1105): ReadObj (normals computed when the file has no `vn`),
+    the AllSeqProj cull with its facet remap, RetainConnectRegion, WriteObj.  -> (V, F) written."""
+    n, s, R, t, coff, cams = L.seq_tables(scales, Rs, ts, cameras)
+    V, F = C.c_int64(), C.c_int64()
+    L.check(L.lib().mvs_processor_cull_model(os.fsencode(model_obj), n, L.ptr(s), L.ptr(R), L.ptr(t), L.ptr(coff), cams,
+                                             int(bool(all_seq_proj)), os.fsencode(out_obj), C.byref(V), C.byref(F)))
+    return V.value, F.value
+
+
+# ------------------------------------------------------------------ deform ----
+def Deform(model_obj, template_obj, parts_path, cam_R, dist_thres: float, out_obj, params: L.CParams | None = None) -> dict:
+    """./Result/Model.obj + ./Template/meanbody.obj + ./Template/part/parts -> ./Result/deform.obj.
+    ``cam_R`` is the rotation of cameras[0][0]; the view ray is its third row (R^T.col(2))."""
+    R = L.arr(cam_R, np.float64).reshape(9)
+    prm = params if params is not None else default_params()
+    st = L.CStats()
+    rc = L.check(L.lib().mvs_processor_deform(os.fsencode(model_obj), os.fsencode(template_obj), os.fsencode(parts_path), L.ptr(R),
+                                              float(dist_thres), C.byref(prm), os.fsencode(out_obj), C.byref(st)))
+    return _stats(st, rc)
+
+
+# ------------------------------------------------------------------ render ----
+def Render(deform_obj, srt_txt, cameras, result_dir, seq_dirs, znear: float = 0.01, zfar: float = 2000.0) -> int:
+    """The second half of `main -a 0` (R/Processor/Processor.cpp:1140-1192): SRT.txt and deform.obj read through float32, the mesh
+    mapped into every sequence's frame and written to ``result_dir``/render%d.obj, then every camera i of sequence k rendered to
+    ``seq_dirs[k]``DATA/Render/_depth<i>.raw (cameras[0][0]'s size for every raster).  ``cameras[k]`` lists sequence k's cameras.
+    -> views rendered."""
+    n, _, _, _, coff, cams = _view_tables(cameras, None, None, None)
+    if len(seq_dirs) != n:
+        raise L.MvsError(-1, f"{len(seq_dirs)} sequence dirs for {n} sequences")
+    dirs = (C.c_char_p * n)(*[os.fsencode(d) for d in seq_dirs])
+    nv = C.c_int64()
+    L.check(L.lib().mvs_processor_render(os.fsencode(deform_obj), os.fsencode(srt_txt), n, L.ptr(coff), cams, os.fsencode(result_dir), dirs,
+                                         float(znear), float(zfar), C.byref(nv)))
+    return nv.value
+
+
+def RenderViews(points, facets, cameras, scales=None, Rs=None, ts=None, znear: float = 0.01, zfar: float = 2000.0,
+                out_dev: int | None = None, stream: int | None = None):
+    """Model2Depth::SetInput + Run (R/Model2Depth/Model2Depth.cpp:58-190): every camera of every sequence in one call.  Sequence k
+    renders the points mapped by its inverse SRT (1/s_k R_k^T (p - t_k)); without an SRT the points as given.  ``cameras[k]`` lists
+    sequence k's cameras; cameras[0][0]'s size (w0, h0) is the viewport of every view.  -> float32 [N, h0, w0] of inverse depths in
+    camera order.  With ``out_dev`` (device address of N*h0*w0 floats) the mesh arguments are device addresses, (address, count)
+    tuples as for RenderDepth, and nothing is returned."""
+    n, s, R, t, coff, cams = _view_tables(cameras, scales, Rs, ts)
+    if out_dev is not None:
+        (pp, V), (fp, F) = points, facets
+        L.check(L.lib().mvs_render_depth_views_dev(L.ptr(int(pp)), int(V), L.ptr(int(fp)), int(F), n, L.ptr(s), L.ptr(R), L.ptr(t),
+                                                   L.ptr(coff), cams, float(znear), float(zfar), L.ptr(int(out_dev)), L.ptr(stream)))
+        return None
+    pts = L.arr(points, np.float64).reshape(-1, 3)
+    fac = L.arr(facets, np.int32).reshape(-1, 3)
+    N = int(coff[-1])
+    w0, h0 = (int(cameras[0][0].w), int(cameras[0][0].h)) if N and len(cameras[0]) else (0, 0)
+    out = np.empty((N, h0, w0), np.float32)
+    L.check(L.lib().mvs_render_depth_views(L.ptr(pts), len(pts), L.ptr(fac), len(fac), n, L.ptr(s), L.ptr(R), L.ptr(t), L.ptr(coff), cams,
+                                           float(znear), float(zfar), L.ptr(out)))
+    return out
+
+
+def RenderDepth(points, facets, camera, znear: float = 0.01, zfar: float = 2000.0, out_dev: int | None = None, stream: int | None = None):
+    """Model2Depth::RenderDepth for one camera (R/Model2Depth/Model2Depth.cpp:58-156) without GLUT: float32 raster [h, w]
+    of inverse depths, 0 where no triangle covers the pixel.  With ``out_dev`` the mesh arguments are device addresses
+    (points: V*3 float64, facets: F*3 int32 — pass (address, count) tuples) and nothing is returned."""
+    cc = L.CCamera.of(camera)
+    if out_dev is not None:
+        (pp, V), (fp, F) = points, facets
+        L.check(L.lib().mvs_render_depth_dev(L.ptr(int(pp)), int(V), L.ptr(int(fp)), int(F), C.byref(cc), float(znear), float(zfar),
+                                             L.ptr(int(out_dev)), L.ptr(stream)))
+        return None
+    pts = L.arr(points, np.float64).reshape(-1, 3)
+    fac = L.arr(facets, np.int32).reshape(-1, 3)
+    out = np.empty((camera.h, camera.w), np.float32)
+    L.check(L.lib().mvs_render_depth(L.ptr(pts), len(pts), L.ptr(fac), len(fac), C.byref(cc), float(znear), float(zfar), L.ptr(out)))
+    return out

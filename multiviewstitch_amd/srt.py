@@ -99,8 +99,7 @@ def select_keyframe_pair(cams1, cams2, matches, min_match_count: int = 7, iters:
     off = np.zeros(n1 * n2 + 1, np.int64)
     off[1:] = np.cumsum([len(m) for m in flat])
     allm = np.ascontiguousarray(np.concatenate(flat)) if off[-1] else np.zeros((0, 6))
-    c1 = (L.CCamera * n1)(*[L.CCamera.of(c) for c in cams1])
-    c2 = (L.CCamera * n2)(*[L.CCamera.of(c) for c in cams2])
+    c1, c2 = L.cam_array(cams1), L.cam_array(cams2)
     st, f1, f2, err = C.c_uint32(state), C.c_int32(), C.c_int32(), C.c_double()
     keep = np.zeros(int(off[-1]), np.uint8)
     nk, perr = np.zeros(n1 * n2, np.int64), np.zeros(n1 * n2)

@@ -16,7 +16,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-GROUPS = {"candidates": ("k_ps_candidates",), "emit": ("k_ps_emit",), "compaction": ("k_ps_count", "k_ps_scan", "k_ps_offsets", "k_ps_scatter"),
+GROUPS = {"candidates": ("k_ps_candidates",), "emit": ("k_ps_emit",), "compaction": ("k_ps_count", "k_ct_scan", "k_ct_strided", "k_ps_scatter"),
           "check_consistency": ("k_check_seq",)}
 
 

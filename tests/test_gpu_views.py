@@ -9,7 +9,7 @@ import pytest
 from multiviewstitch_amd import _lib
 from multiviewstitch_amd import scene as S
 from tests import ref_views as RV
-from tests.test_views_host import CVIEWS, SCENARIOS, cull_expected, cull_scenario, view_scenario
+from tests.test_views_host import ALL_REMOVED_LIST, CVIEWS, EMPTY_LIST, SCENARIOS, cull_expected, cull_scenario, view_scenario
 
 
 @pytest.fixture(scope="module")
@@ -135,6 +135,26 @@ def test_cull_device_form_equals_the_restatement(processor):
                                stream=torch.cuda.current_stream().cuda_stream)
     r = {k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in r.items()}
     assert_cull(r, what, keys_out, descs_out, True)
+
+
+@pytest.mark.gpu
+def test_cull_scan_carries_past_its_first_chunk(processor):
+    """The scan of the shared compaction tail takes 256 workgroup counts per turn and carries their sum into the next: more than
+    65 536 + 256 keys give more than 257 workgroups of 256 keys, so the carry loop runs.  Every list of the scenario r times over;
+    a key's fate does not depend on other keys, so the restatement's per-list results r times over are what is expected."""
+    q = cull_scenario()
+    what, keys_out, _ = cull_expected(True)
+    n_keys = sum(len(k) for k in q["keys"])
+    r = -(-(65536 + 256 + 1) // n_keys)
+    keys = [np.tile(k, (r, 1)) for k in q["keys"]]
+    total = sum(len(k) for k in keys)
+    assert total > 65536 + 256 and (r - 1) * n_keys <= 65536 + 256
+    (off, flat, _, tex, depths), masks = flat_cull_args(dict(q, keys=keys), False, True)
+    got = processor.KeypointCull(q["cameras"], CVIEWS, off, flat, None, tex, depths, S.MIN_DSP, S.MAX_DSP, masks)
+    assert_cull(got, [np.tile(w, r) for w in what], [np.tile(k, (r, 1)) for k in keys_out], None, False)
+    oo = got["out_offsets"]
+    assert off[EMPTY_LIST + 1] == off[EMPTY_LIST] and oo[EMPTY_LIST + 1] == oo[EMPTY_LIST]
+    assert off[ALL_REMOVED_LIST + 1] > off[ALL_REMOVED_LIST] and oo[ALL_REMOVED_LIST + 1] == oo[ALL_REMOVED_LIST]
 
 
 # --------------------------------------------------------------- 3. hand-over ----

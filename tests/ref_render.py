@@ -45,9 +45,15 @@ def project(pts, cam, vw, vh, znear=0.01, zfar=2000.0):
         return np.stack([(xn + one) * (half * F32(vw)), (yn + one) * (half * F32(vh)), (zn + one) * half, wc], axis=1)
 
 
-def raster(win, faces, vw, vh):
-    """The depth buffer [vh, vw] (float32, cleared to 1): every (triangle, pixel) test of k_rd_raster, minimum per pixel."""
+def raster(win, faces, vw, vh, stats=None):
+    """The depth buffer [vh, vw] (float32, cleared to 1): every (triangle, pixel) test of k_rd_raster, minimum per pixel.
+    ``stats`` (a dict) receives how often the top-left rule and the minimum had to decide: ``on_edge_drawn`` = pixel centres with an
+    edge function exactly 0.0 that the triangle draws (a top or left edge), ``on_edge_skipped`` = centres that only the rule keeps
+    out (inside or on every edge, an edge function 0.0 on an edge of the other kind), ``ties`` = pixels whose final depth two or
+    more triangles gave, bit for bit."""
     zbuf = np.ones(vw * vh, F32)
+    if stats is not None:
+        stats.update(on_edge_drawn=0, on_edge_skipped=0, ties=0)
     faces = np.asarray(faces, np.int64).reshape(-1, 3)
     if len(faces) == 0:
         return zbuf.reshape(vh, vw)
@@ -91,6 +97,12 @@ def raster(win, faces, vw, vh):
         z = (((e0 * g(za) + e1 * g(zb)) + e2 * g(zc)) / g(area)).astype(F32)
     keep = inside & (z > 0) & (z < 1)
     np.minimum.at(zbuf, (j * vw + i)[keep], z[keep])
+    if stats is not None:
+        zero = (e0 == 0) | (e1 == 0) | (e2 == 0)
+        stats["on_edge_drawn"] = int((keep & zero).sum())
+        stats["on_edge_skipped"] = int((~inside & (e0 >= 0) & (e1 >= 0) & (e2 >= 0)).sum())
+        px = (j * vw + i)[keep]
+        stats["ties"] = int((np.bincount(px[z[keep] == zbuf[px]], minlength=vw * vh) >= 2).sum())
     return zbuf.reshape(vh, vw)
 
 
@@ -105,9 +117,10 @@ def convert(zbuf, zn_d, zf_d):
     return np.where(drawn & (z_e > 1e-6), r, F32(0)).astype(F32)
 
 
-def render(pts, faces, cam, vw=None, vh=None, znear=0.01, zfar=2000.0):
-    """One view: the camera's own frustum into a vw x vh viewport (default: the camera's size).  float32 [vh, vw]."""
+def render(pts, faces, cam, vw=None, vh=None, znear=0.01, zfar=2000.0, stats=None):
+    """One view: the camera's own frustum into a vw x vh viewport (default: the camera's size).  float32 [vh, vw].
+    ``stats``: see raster."""
     vw = cam.w if vw is None else vw
     vh = cam.h if vh is None else vh
     _, _, zn_d, zf_d = glcam(cam, znear, zfar)
-    return convert(raster(project(pts, cam, vw, vh, znear, zfar), faces, vw, vh), zn_d, zf_d)
+    return convert(raster(project(pts, cam, vw, vh, znear, zfar), faces, vw, vh, stats), zn_d, zf_d)

@@ -1,5 +1,6 @@
 """Depth-consistency filter (SURVEY §8(f) row 2, R/Processor/Processor.cpp:29-126): oracle properties on CPU, bit-exact
-parity of the HIP kernel against the oracle on the GPU."""
+parity of the HIP kernel against the oracle on the GPU, on rendered scenes.  Raster edges, non-finite depths and the double -> int
+rule: tests/test_consist_host.py and tests/test_gpu_consist.py."""
 import numpy as np
 import pytest
 

@@ -61,6 +61,118 @@ def test_depth_edge_cases(srt, oracle):
     assert np.array_equal(v, rv) and np.abs(p - rp).max() < 1e-12
 
 
+# ---- raster edges and non-finite depths (the scenes: tests/consist_scenes.py's poison list on small rasters) ----
+# (w, h): one row, one column, one pixel, one quad; 1023, 1024 and 1025 pixels straddle the 1024-element block of scan_exclusive_i32
+# (out[n] is the last element of block 0, or opens a block of its own); 37 x 29 is 4 workgroups and 49 pixels
+EDGE_SIZES = ((1, 1), (1, 40), (40, 1), (2, 2), (31, 33), (32, 32), (41, 25), (37, 29))
+SCAN_SIZES = ((31, 33), (32, 32), (41, 25))
+
+
+def edge_cam(w, h):
+    f = 1.2 * max(w, h, 8)
+    return S.Camera(f, f, w / 2 - 0.5, h / 2 - 0.5, *S._look_at(np.array([2.5, 1.0, 0.7])), w, h)
+
+
+def edge_rasters(w, h):
+    """full, checkerboard, and a slowly varying surface with the poison list scattered on it (about every ninth pixel), so that
+    triangles exist around every poisoned pixel"""
+    from tests.consist_scenes import poison
+    y, x = np.mgrid[0:h, 0:w]
+    full = np.full((h, w), 0.2, np.float32)
+    checker = np.where((x + y) % 2 == 0, np.float32(0.2), np.float32(0)).astype(np.float32)
+    smooth = (0.15 + 0.01 * np.sin(x / 5.0) * np.cos(y / 7.0)).astype(np.float32)
+    p = poison()
+    at = np.flatnonzero(np.random.default_rng(w * 1000 + h).random(w * h) < 0.11)
+    if w * h >= 4:
+        at = np.union1d(at, [1])                                          # at least one, in every raster that has room for it
+    smooth.reshape(-1)[at] = p[np.arange(len(at)) % len(p)]
+    return dict(full=full, checker=checker, smooth=smooth)
+
+
+def close(got, ref):
+    """the file's gates: NaN in the same places, everything else within 1e-12"""
+    return got.shape == ref.shape and np.array_equal(np.isnan(got), np.isnan(ref)) and \
+        bool((np.abs(got - ref)[~np.isnan(ref)] < 1e-12).all())
+
+
+def check_depth_case(srt, oracle, d, cam, smooth=S.SMOOTH):
+    got = srt.depth_to_model(d, cam, S.MIN_DSP, S.MAX_DSP, smooth)
+    ref = oracle.depth_to_model(d, cam, S.MIN_DSP, S.MAX_DSP, smooth)
+    assert np.array_equal(got[2], ref[2]) and np.array_equal(got[3], ref[3])
+    assert close(got[0], ref[0]) and not np.isnan(ref[0]).any()
+    assert close(got[1], ref[1])
+    p, v = srt.depth_unproject(d, cam, S.MIN_DSP, S.MAX_DSP)
+    rp, rv = oracle.depth_unproject(d, cam, S.MIN_DSP, S.MAX_DSP)
+    assert np.array_equal(v, rv) and close(p, rp)
+    # Image3D::SolveUnProjectionD tests d < min || d > max, so a NaN is "valid" and gives a NaN point; Depth2Model tests d > 0
+    # first, so a NaN is no vertex.  The asymmetry is the reference's.
+    nan = np.flatnonzero(np.isnan(d.reshape(-1)))
+    assert (v[nan] == 1).all() and np.isnan(p[nan]).all() and not np.isin(nan, got[2]).any()
+    assert np.array_equal(np.flatnonzero(np.isnan(p).any(1)), nan)
+    return got, ref
+
+
+@pytest.mark.parametrize("size", EDGE_SIZES)
+def test_depth_kernels_on_small_and_block_straddling_rasters(srt, oracle, size):
+    w, h = size
+    cam = edge_cam(w, h)
+    cases = edge_rasters(w, h)
+    assert w * h < 4 or np.isnan(cases["smooth"]).any()
+    for name, d in cases.items():
+        got, ref = check_depth_case(srt, oracle, d, cam)
+        if name == "full":
+            assert len(got[0]) == w * h and len(got[3]) == 2 * (w - 1) * (h - 1)
+        if name == "checker":
+            assert len(got[0]) == (w * h + 1) // 2
+        if min(w, h) == 1:                                                # points without faces: every normal is 0 / 0
+            assert len(got[3]) == 0 and np.isnan(got[1]).all()
+        elif name == "smooth" and w * h > 1000:
+            assert len(got[3]) > w * h // 2 and np.isnan(got[1]).any() and not np.isnan(got[1]).all()
+
+
+@pytest.mark.parametrize("size", SCAN_SIZES)
+def test_depth_to_model_device_form_around_the_scan_block(srt, size):
+    import torch
+    w, h = size
+    assert w * h in (1023, 1024, 1025)
+    cam = edge_cam(w, h)
+    dev = torch.device("cuda", 0)
+    for name, d in edge_rasters(w, h).items():
+        pts, nrm, tex, faces = srt.depth_to_model(d, cam, S.MIN_DSP, S.MAX_DSP, S.SMOOTH)
+        P, F = len(pts), len(faces)
+        dd = torch.from_numpy(d).to(dev)
+        assert srt.depth_to_model_dev(dd.data_ptr(), cam, S.MIN_DSP, S.MAX_DSP, S.SMOOTH) == (P, F)          # counts only
+        tp = torch.full((P + 1, 3), -7.0, dtype=torch.float64, device=dev)                                   # one guard row each
+        tn = torch.full((P + 1, 3), -7.0, dtype=torch.float64, device=dev)
+        tt = torch.full((P + 1,), -7, dtype=torch.int32, device=dev)
+        tf = torch.full((F + 1, 3), -7, dtype=torch.int32, device=dev)
+        assert srt.depth_to_model_dev(dd.data_ptr(), cam, S.MIN_DSP, S.MAX_DSP, S.SMOOTH, tp.data_ptr(), tn.data_ptr(), tt.data_ptr(),
+                                      tf.data_ptr()) == (P, F)
+        torch.cuda.synchronize()
+        for t, a in ((tp, pts), (tn, nrm), (tt, tex), (tf, faces)):
+            got = t.cpu().numpy()
+            assert got[:len(a)].tobytes() == a.tobytes(), name
+            assert (got[len(a):] == -7).all(), name
+
+
+@pytest.mark.parametrize("sign", [1.0, -1.0])
+def test_smoothness_difference_equal_to_the_threshold(srt, oracle, sign):
+    """`<=` against `<`: a 2 x 2 block that differs from the flat raster by exactly the float32 threshold keeps all its triangles,
+    one float32 step further drops them"""
+    smooth = 2.0 ** -9 * 100 / (S.MAX_DSP - S.MIN_DSP)
+    assert np.float32(smooth * (S.MAX_DSP - S.MIN_DSP) / 100) == np.float32(2.0 ** -9)         # `float threshold`, Depth2Model.cpp:45
+    cam = edge_cam(8, 6)
+    on = np.float32(0.125 + sign * 2.0 ** -9)
+    assert float(on) == 0.125 + sign * 2.0 ** -9                                                # exact in float32
+    off = np.nextafter(on, np.float32(on + sign))
+    assert abs(float(off) - 0.125) > 2.0 ** -9
+    for value, n_faces in ((on, 70), (off, 56)):
+        d = np.full((6, 8), 0.125, np.float32)
+        d[2:4, 3:5] = value
+        got, ref = check_depth_case(srt, oracle, d, cam, smooth)
+        assert len(ref[3]) == n_faces and len(got[3]) == n_faces
+
+
 def test_srt_apply_matches_oracle(srt, oracle):
     rng = np.random.default_rng(5)
     p, n = rng.normal(size=(100003, 3)), rng.normal(size=(100003, 3))

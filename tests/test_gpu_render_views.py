@@ -12,6 +12,7 @@ from multiviewstitch_amd import io as mio
 from multiviewstitch_amd import scene as S
 from oracle import binding as O
 from tests import ref_render as RR
+from tests import render_meshes as RM
 from tests.util import body_scene
 
 pytestmark = pytest.mark.gpu
@@ -89,19 +90,8 @@ def test_device_form_and_chunks_give_the_same_bytes(proc, monkeypatch):
 
 
 def test_edge_cases(proc):
-    cam = S.Camera(120.0, 120.0, 49.5, 39.5, np.eye(3), np.zeros(3), 100, 80)
-    big = S.Camera(150.0, 150.0, 89.5, 69.5, np.eye(3), np.zeros(3), 180, 140)     # spans 6 x 5 tiles
-    tiny = S.Camera(30.0, 30.0, 9.5, 5.5, np.eye(3), np.zeros(3), 20, 12)          # one tile
-    tri = lambda *p: np.array(p, float)
-    pts = np.concatenate([
-        tri([-1, -1, 3.0], [1, -1, 3.0], [0, 1, -1.0]),                              # 0-2: crosses the eye plane
-        tri([-500, -500, 5.0], [500, -500, 5.0], [0, 500, 5.0]),                     # 3-5: covers the whole raster
-        tri([0, 0, 2.0], [0.1, 0.1, 2.0], [0.2, 0.2, 2.0]),                          # 6-8: zero area
-        tri([np.nan, 0, 2.0], [0.3, 0, 2.0], [0, 0.3, 2.0]),                         # 9-11: a NaN vertex
-        tri([-0.2, -0.2, 2.5], [0.3, -0.1, 2.5], [0.0, 0.4, 2.0]),                  # 12-14: a plain triangle in front
-        tri([7, 7, 7.0], [8, 8, 8.0]),                                               # 15-16: unused vertices
-    ])
-    faces = np.array([[0, 1, 2], [3, 4, 5], [6, 7, 8], [9, 10, 11], [12, 14, 13]], np.int32)
+    cam, big, tiny = RM.edge_case_cameras()
+    pts, faces = RM.edge_case_mesh()                  # eye-plane crossing, screen-covering, zero-area, NaN vertex, a plain triangle
     for c in (cam, big, tiny):
         views = [[c, c], [], [c]]                                                    # an empty middle sequence
         got = proc.RenderViews(pts, faces, views)

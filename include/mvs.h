@@ -560,6 +560,92 @@ int mvs_point_sample_dev(int32_t n_seq, const int32_t* cam_off, const mvs_camera
                          const mvs_point_sample_params* p, int64_t* seq_offsets, double* points_dev, double* normals_dev,
                          int32_t* frame_dev, int32_t* pixel_dev, int64_t capacity, void* hip_stream);
 
+/* ------------------------------------------------- surface reconstruction (GeometryRec::RunPoisson) -- */
+/* The one call between the stitch tail and the trim of the model (R/Processor/Processor.cpp:1042-1058): the oriented points of
+ * Result/PSR.npts to the triangle mesh of Result/Model.obj that mvs_processor_cull_model reads.  GeoRec is a closed binary; its source is
+ * not part of the reference tree.  The rules below are NOT VERIFIED against GeoRec; they are this library's definition: an unscreened
+ * Poisson reconstruction on a dense grid stands in for GeoRec's octree.  GeometryRec::Init receives maxPsDep / minPsDep from config.txt
+ * (PsnDptMax 10, PsnDptMin 7); here they are depth_max / depth_min: the grid has 2^D cells per axis, D is never below depth_min, never
+ * above min(depth_max, MVS_POISSON_MAX_DEPTH) and, in between, as fine as the sampling supports (rule 3).
+ * Input: n rows of points[3] and normals[3] (doubles, the layout of mvs_npts_read); the normals point out of the body and are unit
+ * vectors or shorter (a component of magnitude 2^26 or more overflows rule 5's quantisation; its result is unspecified).  All
+ * arithmetic is fp64 + - * / in the stated order (the library is built with -ffp-contract=off).
+ *   1. used points : a row is used when its six values are finite; N = the used rows.  N < 2, or a bounding box of zero extent, gives
+ *                    MVS_E_DEGENERATE; N > 2^26 gives MVS_E_INVALID_ARG (the sums of rule 5 stay inside int64).
+ *   2. cube        : lo, hi = the componentwise min and max of the used points; c = 0.5 * (lo + hi); side = scale * max(hi - lo);
+ *                    o = c - 0.5 * side.
+ *   3. depth       : Dmax = min(depth_max, MVS_POISSON_MAX_DEPTH).  At depth d the cell of a point is, per axis,
+ *                    clamp(floor((p - o) / (side / 2^d)), 0, 2^d - 1); occupied(d) = the distinct such cells.  D = the largest d in
+ *                    [depth_min, Dmax] with (double)N >= samples_per_node * (double)occupied(d), depth_min when no d qualifies.
+ *   4. grid        : G = 2^D, h = side / G; nodes (ix, iy, iz) in [0, G]^3 at o + h * i, node index (iz * (G + 1) + iy) * (G + 1) + ix.
+ *                    Boundary nodes carry chi = 0.
+ *   5. splat       : per used point g = (p - o) / h, i0 = clamp(floor(g), 0, G - 1), f = g - i0 per axis; corner (bx, by, bz) of the
+ *                    cube at i0 has the weight w = (wx * wy) * wz, each factor f (bit set) or 1 - f.  The contribution x = w * n_a to
+ *                    component a at that corner is quantised, q = llrint(x * 2^36) (round to nearest even), and summed in int64 per
+ *                    node and component; V_a = (double)sum * 2^-36.  Integer sums do not depend on their order.
+ *   6. right side  : at interior nodes b = (((Vx[ix+1] - Vx[ix-1]) + (Vy[iy+1] - Vy[iy-1])) + (Vz[iz+1] - Vz[iz-1])) * (0.5 * h).
+ *   7. system      : for every interior node (the sum of the six neighbours' chi) - 6 chi = b: the unscaled 7-point Laplacian with
+ *                    zero Dirichlet boundary.
+ *   8. solve       : multigrid V(2,2) cycles (Jacobi damped by 6/7, full weighting, trilinear prolongation, levels D .. 1) until the
+ *                    true residual, recomputed on the device after every cycle, satisfies |b - A chi|_2 <= solve_tol * |b|_2;
+ *                    max_cycles without that gives MVS_E_SOLVER (info holds the residual reached).  The norms are sums of
+ *                    per-workgroup partials in a fixed order: two runs agree to the bit.  b = 0 gives chi = 0 at once.
+ *   9. iso value   : iso = the mean over the used points of the trilinear chi (corners and weights of rule 5, added in corner order
+ *                    bx + 2 by + 4 bz), reduced in a fixed order: partials per workgroup, then one workgroup.
+ *  10. inside      : a node is inside when chi < iso (a value equal to iso is outside); with outward normals the mesh is wound
+ *                    outward.  Every cube (ix, iy, iz) in [0, G)^3 is cut into the six Kuhn tetrahedra along its (0,0,0)-(1,1,1)
+ *                    diagonal: tetrahedron (a, b, c) has the corners q0 = cube origin, q1 = q0 + e_a, q2 = q1 + e_b, q3 = q2 + e_c,
+ *                    taken in the order xyz, xzy, yxz, yzx, zxy, zyx.  Every edge of a tetrahedron leaves its lower node by one of
+ *                    seven types 0..6 = +x, +y, +z, +x+y, +x+z, +y+z, +x+y+z; neighbouring cubes agree on every shared face.
+ *  11. vertices    : an edge (node, type) with exactly one inside end carries one vertex: with a, pa at the inside end and b, pb at
+ *                    the outside end, t = (iso - a) / (b - a), p = pa + t * (pb - pa).  Vertices are numbered in ascending
+ *                    (node index, type); vertices that coincide in position keep distinct numbers.
+ *  12. triangles   : a tetrahedron with inside corners I and outside corners O (both non-empty) emits the polygon over its I-O
+ *                    edges: for |I| = 1 or 3 the triangle over the three edges, for I = {A, B}, O = {C, D} the quad AC, AD, BD, BC.
+ *                    The cycle is reversed when the polygon's normal — (p1 - p0) x (p2 - p0), for the quad plus (p2 - p0) x (p3 - p0)
+ *                    — has a negative dot product with mean(O corners) - mean(I corners), then rotated so that its smallest
+ *                    vertex number comes first.  A triangle is (v0, v1, v2), a quad (v0, v1, v2) then (v0, v2, v3).  Faces are
+ *                    ordered by cube index (iz * G + iy) * G + ix, then by tetrahedron, then as listed.
+ *  13. no crossing : V = F = 0 and MVS_OK.
+ * info is written by every call that gets as far as the device; counts above a capacity (rows) give MVS_E_INVALID_ARG after info is
+ * written, so that the caller can size the outputs.
+ * Scratch comes from the stream-ordered pool.  Per node of the finest level, (G + 1)^3 of them: 24 bytes for the three int64 sums —
+ * reused for chi and the smoother's second buffer — and 8 for b; 1 byte per cube; 7/8 byte for the edge flags (one bit each, 7 per
+ * node); 12 bytes per 256 edge flags and per 256 face slots (12 per cube) for the two compactions.  Per node of every level below,
+ * (2^l + 1)^3 for l < D: 24 bytes.  2^(3 d - 3) bytes per candidate depth d of rule 3 when depth_min < Dmax.  8 bytes per workgroup of
+ * the residual norm.  The host form adds the points, the normals and the mesh.  D = 9 takes about 5 GB.
+ * MVS_E_INVALID_ARG, before a device is needed: points, normals, params or info NULL, an output NULL with a capacity above 0, n < 0, a
+ * negative capacity, a non-finite or non-positive scale, samples_per_node or solve_tol, scale <= 1 + 4.0 / 2^depth_min (every point
+ * then lies at least a cell from the boundary), depth_min < 3, depth_min > depth_max, depth_min > MVS_POISSON_MAX_DEPTH, max_cycles < 1. */
+#define MVS_POISSON_MAX_DEPTH 9
+typedef struct mvs_poisson_params {
+    double  scale;              /* 1.1: the cube's side over the largest extent of the points    */
+    double  samples_per_node;   /* 1.5                                                           */
+    double  solve_tol;          /* 1e-8                                                          */
+    int32_t depth_max;          /* PsnDptMax 10; above MVS_POISSON_MAX_DEPTH means that depth    */
+    int32_t depth_min;          /* PsnDptMin 7                                                   */
+    int32_t max_cycles;         /* 64                                                            */
+    int32_t reserved;           /* 0                                                             */
+} mvs_poisson_params;
+typedef struct mvs_poisson_info {
+    double  origin[3], h;       /* o and h of rules 2 and 4                                      */
+    double  iso;                /* rule 9                                                        */
+    double  rel_residual;       /* |b - A chi|_2 / |b|_2 after the last cycle                    */
+    int64_t n_used;             /* N of rule 1                                                   */
+    int64_t n_vertices, n_faces;
+    int32_t depth, cycles;      /* D of rule 3; V-cycles run                                     */
+} mvs_poisson_info;
+/* the values in the comments above */
+void mvs_poisson_default_params(mvs_poisson_params* p);
+int mvs_poisson_reconstruct(int64_t n, const double* points, const double* normals, const mvs_poisson_params* p, mvs_poisson_info* info,
+                            double* vertices /*vertex_capacity x 3*/, int64_t vertex_capacity, int32_t* faces /*face_capacity x 3*/,
+                            int64_t face_capacity);
+/* points, normals and outputs in HBM, in the order of hip_stream (may be NULL); params and info stay host structs; returns with the work
+ * complete */
+int mvs_poisson_reconstruct_dev(int64_t n, const double* points_dev, const double* normals_dev, const mvs_poisson_params* p,
+                                mvs_poisson_info* info, double* vertices_dev, int64_t vertex_capacity, int32_t* faces_dev,
+                                int64_t face_capacity, void* hip_stream);
+
 /* Chain composition, Processor.cpp:819-823: (s0,R0,t0) <- (sk,Rk,tk) o (s0,R0,t0). */
 int mvs_srt_compose(double sk, const double* Rk, const double* tk,
                     double* s0, double* R0, double* t0);

@@ -104,6 +104,12 @@ int mvs_processor_render(const char* deform_obj, const char* srt_txt, int32_t n_
 int mvs_processor_point_sample(int32_t n_seq, const char* const* seq_dirs, const int32_t* cam_off, const mvs_camera* cams,
                                const mvs_point_sample_params* params, const char* const* npts_paths, int64_t* n_points);
 
+/* GeometryRec::RunPoisson on files (R/Processor/Processor.cpp:1042-1058; the rules: mvs_poisson_reconstruct, this library's definition):
+ * read psr_npts (mvs_npts_read: Result/PSR.npts, what mvs_processor_stitch_points wrote), reconstruct, compute the vertex normals
+ * (mvs_mesh_vertex_normals_dev) and write model_obj (mvs_obj_write: `v`, `vn` and `f` lines), the file mvs_processor_cull_model reads.
+ * params may be NULL (defaults).  Nothing is written when the reconstruction fails.  V / F (may be NULL) receive the sizes written. */
+int mvs_processor_poisson(const char* psr_npts, const mvs_poisson_params* params, const char* model_obj, int64_t* V, int64_t* F);
+
 #ifdef __cplusplus
 }
 #endif

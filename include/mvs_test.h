@@ -69,6 +69,12 @@ int mvs_test_sift_candidates(int32_t n_lists, int32_t w, int32_t h, const uint8_
 int mvs_test_point_sample_candidates(int32_t n_seq, const int32_t* cam_off, const mvs_camera* cams, const float* depths,
                                      const mvs_point_sample_params* p, int64_t* cell_offsets, int32_t* cand, int64_t capacity);
 
+/* mvs_poisson_reconstruct up to rule 9: info (n_vertices and n_faces stay 0), the right-hand side of rule 6 and chi, (2^depth + 1)^3
+ * doubles each in node order.  A node count above node_capacity gives MVS_E_INVALID_ARG after info's depth, origin and h are written.
+ * MVS_E_SOLVER still hands out the field the cycles reached. */
+int mvs_test_poisson_field(int64_t n, const double* points, const double* normals, const mvs_poisson_params* p, mvs_poisson_info* info,
+                           double* rhs, double* chi, int64_t node_capacity);
+
 #ifdef __cplusplus
 }
 #endif

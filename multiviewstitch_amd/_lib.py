@@ -77,6 +77,18 @@ class CPointSampleParams(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class CPoissonParams(C.Structure):
+    """struct mvs_poisson_params."""
+    _fields_ = [("scale", C.c_double), ("samples_per_node", C.c_double), ("solve_tol", C.c_double), ("depth_max", C.c_int32),
+                ("depth_min", C.c_int32), ("max_cycles", C.c_int32), ("reserved", C.c_int32)]
+
+
+class CPoissonInfo(C.Structure):
+    """struct mvs_poisson_info."""
+    _fields_ = [("origin", C.c_double * 3), ("h", C.c_double), ("iso", C.c_double), ("rel_residual", C.c_double), ("n_used", C.c_int64),
+                ("n_vertices", C.c_int64), ("n_faces", C.c_int64), ("depth", C.c_int32), ("cycles", C.c_int32)]
+
+
 class CSeqPairParams(C.Structure):
     """struct mvs_seq_pair_params."""
     _fields_ = [("filter", CMatchFilterParams), ("min_dsp", C.c_double), ("max_dsp", C.c_double), ("min_match_count", C.c_int32),
@@ -128,6 +140,9 @@ _SIGS = {
     "mvs_point_sample_default_params": (None, [_VP]),
     "mvs_point_sample": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64]),
     "mvs_point_sample_dev": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP]),
+    "mvs_poisson_default_params": (None, [_VP]),
+    "mvs_poisson_reconstruct": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _I64]),
+    "mvs_poisson_reconstruct_dev": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _I64, _VP]),
     "mvs_render_depth": (C.c_int, [_VP, _I64, _VP, _I64, _VP, C.c_float, C.c_float, _VP]),
     "mvs_render_depth_dev": (C.c_int, [_VP, _I64, _VP, _I64, _VP, C.c_float, C.c_float, _VP, _VP]),
     "mvs_render_depth_views": (C.c_int, [_VP, _I64, _VP, _I64, _I32, _VP, _VP, _VP, _VP, _VP, C.c_float, C.c_float, _VP]),
@@ -220,6 +235,7 @@ _SIGS = {
     "mvs_processor_cull_model": (C.c_int, [C.c_char_p, _I32, _VP, _VP, _VP, _VP, _VP, _I32, C.c_char_p, _VP, _VP]),
     "mvs_processor_render": (C.c_int, [C.c_char_p, C.c_char_p, _I32, _VP, _VP, C.c_char_p, _VP, C.c_float, C.c_float, _VP]),
     "mvs_processor_point_sample": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "mvs_processor_poisson": (C.c_int, [C.c_char_p, _VP, C.c_char_p, _VP, _VP]),
     # include/mvs_test.h (test hooks: per handle, not part of the drop-in ABI)
     "mvs_test_preload_wait": (C.c_int, []),
     "mvs_test_ctl": (C.c_int, [_VP, _VP, _I32]),
@@ -233,6 +249,7 @@ _SIGS = {
     "mvs_test_sift_level": (C.c_int, [_I32, _I32, _VP, _VP, _I32, _I32, _VP, _I64, _VP, _VP]),
     "mvs_test_sift_candidates": (C.c_int, [_I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _I64]),
     "mvs_test_point_sample_candidates": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP, _I64]),
+    "mvs_test_poisson_field": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _I64]),
 }
 EXPORTS = tuple(_SIGS)
 

@@ -1,8 +1,9 @@
 // api_stitch.cpp — C-ABI of the tail of Processor::AlignmentSeq (R/Processor/Processor.cpp:952-1105): mvs_visibility_cull(_dev),
 // mvs_mesh_vertex_normals(_dev) (include/mvs.h) and the two file-level steps mvs_processor_stitch_points / _cull_model
 // (include/mvs_io.h); and of Processor::Render (:1140-1192): mvs_render_depth_views(_dev) (include/mvs.h) and the file-level
-// mvs_processor_render (include/mvs_io.h); and the file form of GeometryRec::RunPointSample (:919-949), mvs_processor_point_sample.
-// The point work is stitch.hip / align.hip / render_views.hip / pointsample.hip; the host reads and writes the files and builds the
+// mvs_processor_render (include/mvs_io.h); and the file forms of GeometryRec::RunPointSample (:919-949), mvs_processor_point_sample, and of
+// GeometryRec::RunPoisson (:1042-1058), mvs_processor_poisson.
+// The point work is stitch.hip / align.hip / render_views.hip / pointsample.hip / poisson.hip; the host reads and writes the files and builds the
 // small tables.
 #include "engine.h"
 #include "trace.h"
@@ -351,6 +352,35 @@ int mvs_processor_point_sample(int32_t n_seq, const char* const* seq_dirs, const
         if ((rc = mvs_npts_write(path.c_str(), off[k + 1] - off[k], pts.data() + 3 * off[k], nrm.data() + 3 * off[k]))) return rc;
         if (n_points) n_points[k] = off[k + 1] - off[k];
     }
+    return MVS_OK;
+}
+
+int mvs_processor_poisson(const char* psr_npts, const mvs_poisson_params* params, const char* model_obj, int64_t* V_out, int64_t* F_out) {
+    MVS_TRACE();
+    if (!psr_npts || !model_obj) return bad(__func__, "psr_npts / model_obj is NULL");
+    mvs_poisson_params prm;
+    if (params) prm = *params; else mvs_poisson_default_params(&prm);
+    int rc = need_device();
+    if (rc) return rc;
+    int64_t n = 0;
+    if ((rc = mvs_npts_read(psr_npts, &n, nullptr, nullptr))) return rc;
+    std::vector<double> hp((size_t)n * 3 + 1), hn((size_t)n * 3 + 1);
+    int64_t m = n;
+    if ((rc = mvs_npts_read(psr_npts, &m, hp.data(), hn.data()))) return rc;
+    if (m != n) { mvs_set_error("%s changed while it was read", psr_npts); return MVS_E_IO; }
+    Scratch dp, dn, dv, df, dvn;
+    mvs_poisson_info info;
+    if ((rc = up(dp, hp.data(), (size_t)n * 3)) || (rc = up(dn, hn.data(), (size_t)n * 3))) return rc;
+    if ((rc = poisson_blocks(__func__, n, dp.as<double>(), dn.as<double>(), &prm, &info, &dv, &df))) return rc;
+    const int64_t V = info.n_vertices, F = info.n_faces;
+    if ((rc = dvn.alloc((size_t)V * 24))) return rc;
+    if (V > 0 && (rc = mesh_vertex_normals_dev(dv.as<double>(), V, df.as<int32_t>(), F, dvn.as<double>(), nullptr))) return rc;
+    std::vector<double> ov((size_t)V * 3 + 1), on((size_t)V * 3 + 1);
+    std::vector<int32_t> of((size_t)F * 3 + 1);
+    if ((rc = down(ov.data(), dv, (size_t)V * 3)) || (rc = down(on.data(), dvn, (size_t)V * 3)) || (rc = down(of.data(), df, (size_t)F * 3))) return rc;
+    if ((rc = mvs_obj_write(model_obj, V, ov.data(), on.data(), F, of.data()))) return rc;
+    if (V_out) *V_out = V;
+    if (F_out) *F_out = F;
     return MVS_OK;
 }
 

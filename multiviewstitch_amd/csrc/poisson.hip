@@ -1,0 +1,755 @@
+// poisson.hip — mvs_poisson_reconstruct (include/mvs.h): oriented points to a triangle mesh, the step GeometryRec::RunPoisson takes
+// between Result/PSR.npts and Result/Model.obj (R/Processor/Processor.cpp:1042-1058).  GeoRec is a closed binary: the rules are this
+// library's definition, stated in include/mvs.h — an unscreened Poisson reconstruction on a dense grid; their per-point and
+// per-tetrahedron part is poisson_rules.h, one body for these kernels and for host code.
+//
+//   k_pn_bbox          used rows, min and max per workgroup (order-free); the host finishes and derives cube, depth and grid (rules 1-4)
+//   k_pn_occupy / k_pn_popcount
+//                      rule 3 when depth_min < Dmax: one bitmap of cells per candidate depth, atomicOr, then a popcount
+//   k_pn_splat         rule 5: a thread per point, 24 int64 atomic adds into the three planar sum arrays
+//   k_pn_rhs           rule 6: a thread per node
+//   k_mg_smooth / k_mg_residual / k_mg_restrict / k_mg_prolong
+//                      rule 8, levels above 33^3: V(2,2) cycles, Jacobi damped by 6/7, full weighting (x 4: the stencil is unscaled),
+//                      trilinear prolongation.  Smoother and residual march along z with the column's three values in registers.
+//   k_mg_coarse        the levels of 33^3 and below, down to the single interior node of level 1 and back, in ONE workgroup
+//   k_mg_residual (out == NULL) / k_pn_fold
+//                      the true residual's squared norm: partials per workgroup, folded by one workgroup in a fixed order
+//   k_pn_iso           rule 9, the same two-step reduction
+//   k_pn_cubemask      rule 10: the inside bits of a cube's eight corners, one byte per cube
+//   k_pn_edge_count / k_pn_vertex_scatter, k_pn_face_count / k_pn_face_scatter
+//                      rules 11-12: two ordered compactions (wg_rank per workgroup of 256 items; k_pn_scan_rows / _totals / _add scan the
+//                      millions of counts in two levels).  The edge flags stay behind as a bitmap, 64 flags per word: a face finds the
+//                      number of a vertex as base[workgroup] + popcounts, no edge map is stored.
+// Nothing but the integer atomics of the splat and the bitmap is unordered: two runs give the same bytes.
+#include "engine.h"
+#include "trace.h"
+#include "frontend_dev.h"
+#include "poisson_rules.h"
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+namespace {
+
+constexpr int PN_TPB = 256, PN_WAVES = PN_TPB / 64;
+constexpr int PN_RED_NB = 1024;          // workgroups of a reduction over the points
+constexpr int PN_ZC = 16;                // planes a thread of the smoother marches through
+constexpr int PN_COARSE = 5;             // levels up to this one (33^3 nodes) run inside k_mg_coarse
+constexpr int PN_COARSE_TPB = 1024;
+constexpr int PN_MAX_D = MVS_POISSON_MAX_DEPTH;
+
+// the sum of v over the workgroup (tid: the thread's linear index), in a fixed order: shuffles inside a wave, then the waves in
+// ascending order; valid in thread 0
+template <int WAVES>
+__device__ inline double wg_sum(double v, double* s_part, int tid) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    if ((tid & 63) == 0) s_part[tid >> 6] = v;
+    __syncthreads();
+    double t = 0.0;
+    if (tid == 0)
+        for (int q = 0; q < WAVES; ++q) t += s_part[q];
+    return t;
+}
+
+// ------------------------------------------------------------------ rules 1-3 ----
+__global__ __launch_bounds__(PN_TPB) void k_pn_bbox(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm, double* __restrict__ part) {
+    __shared__ double s_red[PN_WAVES][7];
+    double lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL}, cnt = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * PN_TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * PN_TPB) {
+        if (!pn_used(pts + 3 * i, nrm + 3 * i)) continue;
+        cnt += 1.0;
+        for (int a = 0; a < 3; ++a) { lo[a] = fmin(lo[a], pts[3 * i + a]); hi[a] = fmax(hi[a], pts[3 * i + a]); }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        for (int a = 0; a < 3; ++a) { lo[a] = fmin(lo[a], __shfl_down(lo[a], o, 64)); hi[a] = fmax(hi[a], __shfl_down(hi[a], o, 64)); }
+        cnt += __shfl_down(cnt, o, 64);                                      // whole numbers below 2^53: exact in any order
+    }
+    if ((threadIdx.x & 63) == 0) {
+        double* r = s_red[threadIdx.x >> 6];
+        for (int a = 0; a < 3; ++a) { r[a] = lo[a]; r[3 + a] = hi[a]; }
+        r[6] = cnt;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int q = 1; q < PN_WAVES; ++q) {
+            for (int a = 0; a < 3; ++a) { s_red[0][a] = fmin(s_red[0][a], s_red[q][a]); s_red[0][3 + a] = fmax(s_red[0][3 + a], s_red[q][3 + a]); }
+            s_red[0][6] += s_red[q][6];
+        }
+        for (int a = 0; a < 7; ++a) part[7 * blockIdx.x + a] = s_red[0][a];
+    }
+}
+
+struct PnOcc {                           // the candidate depths dmin .. dmax of rule 3: cell size and the first bitmap word of each
+    int32_t dmin, dmax;
+    double o[3], cs[PN_MAX_D + 1];
+    int64_t word0[PN_MAX_D + 2];
+};
+
+__global__ __launch_bounds__(PN_TPB) void k_pn_occupy(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm, PnOcc q,
+                                                      unsigned* __restrict__ bits) {
+    const int64_t i = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
+    if (i >= n || !pn_used(pts + 3 * i, nrm + 3 * i)) return;
+    for (int d = q.dmin; d <= q.dmax; ++d) {
+        const int m = 1 << d;
+        const int64_t cell = ((int64_t)pn_cell(pts[3 * i + 2], q.o[2], q.cs[d], m) * m + pn_cell(pts[3 * i + 1], q.o[1], q.cs[d], m)) * m +
+                             pn_cell(pts[3 * i], q.o[0], q.cs[d], m);
+        atomicOr(bits + q.word0[d] + (cell >> 5), 1u << (cell & 31));
+    }
+}
+
+__global__ __launch_bounds__(PN_TPB) void k_pn_popcount(PnOcc q, const unsigned* __restrict__ bits, unsigned long long* __restrict__ occupied) {
+    const int64_t w = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
+    if (w >= q.word0[q.dmax + 1]) return;
+    const unsigned v = bits[w];
+    if (!v) return;
+    int d = q.dmin;
+    while (w >= q.word0[d + 1]) ++d;
+    atomicAdd(occupied + d, (unsigned long long)__popc(v));
+}
+
+// ------------------------------------------------------------------ rules 5-6 ----
+__global__ __launch_bounds__(PN_TPB) void k_pn_splat(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm, PnGrid g,
+                                                     unsigned long long* __restrict__ sums) {
+    const int64_t i = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
+    if (i >= n || !pn_used(pts + 3 * i, nrm + 3 * i)) return;
+    const int64_t nn = (int64_t)(g.G + 1) * (g.G + 1) * (g.G + 1);
+    int i0[3];
+    double w[8];
+    pn_corners_weights(pts + 3 * i, g, i0, w);
+    for (int c = 0; c < 8; ++c) {
+        const int64_t node = pn_node(g.G, i0[0] + (c & 1), i0[1] + (c >> 1 & 1), i0[2] + (c >> 2 & 1));
+        for (int a = 0; a < 3; ++a) atomicAdd(sums + a * nn + node, (unsigned long long)pn_quant(w[c] * nrm[3 * i + a]));
+    }
+}
+
+__global__ __launch_bounds__(PN_TPB) void k_pn_rhs(PnGrid g, const long long* __restrict__ sums, double* __restrict__ b) {
+    const int n1 = g.G + 1;
+    const int64_t nn = (int64_t)n1 * n1 * n1, at = (int64_t)blockIdx.x * PN_TPB + threadIdx.x, plane = (int64_t)n1 * n1;
+    if (at >= nn) return;
+    const int ix = (int)(at % n1), iy = (int)(at / n1 % n1), iz = (int)(at / plane);
+    double v = 0.0;
+    if (ix > 0 && ix < g.G && iy > 0 && iy < g.G && iz > 0 && iz < g.G) {
+        const long long *sx = sums, *sy = sums + nn, *sz = sums + 2 * nn;
+        v = (((pn_dequant(sx[at + 1]) - pn_dequant(sx[at - 1])) + (pn_dequant(sy[at + n1]) - pn_dequant(sy[at - n1]))) +
+             (pn_dequant(sz[at + plane]) - pn_dequant(sz[at - plane]))) * (0.5 * g.h);
+    }
+    b[at] = v;
+}
+
+// ------------------------------------------------------------------ rule 8 ----
+// One node of a level of G cells (interior nodes only; the boundary holds 0 in every array):
+//   smooth    y = (x + S - b) / 7, S the six neighbours of x: Jacobi damped by 6/7 for S - 6 x = b
+//   residual  r = b - (S - 6 x)
+__device__ inline double pn_nbr_sum(const double* x, int64_t at, int n1, int64_t plane) {
+    return ((x[at - 1] + x[at + 1]) + (x[at - n1] + x[at + n1])) + (x[at - plane] + x[at + plane]);
+}
+// full weighting of the fine residual r (level of 2 Gc cells) at coarse node (ix, iy, iz), times 4
+__device__ inline double pn_restrict_at(const double* r, int Gc, int ix, int iy, int iz) {
+    const int n1 = 2 * Gc + 1;
+    const int64_t plane = (int64_t)n1 * n1, at = ((int64_t)(2 * iz) * n1 + 2 * iy) * n1 + 2 * ix;
+    double acc = 0.0;
+    for (int dz = -1; dz <= 1; ++dz)
+        for (int dy = -1; dy <= 1; ++dy)
+            for (int dx = -1; dx <= 1; ++dx) {
+                const double w = (dz ? 0.5 : 1.0) * (dy ? 0.5 : 1.0) * (dx ? 0.5 : 1.0);
+                acc += w * r[at + dz * plane + dy * n1 + dx];
+            }
+    return 0.5 * acc;
+}
+// the trilinear interpolant of the coarse correction e (level of G / 2 cells) at fine node (ix, iy, iz)
+__device__ inline double pn_prolong_at(const double* e, int G, int ix, int iy, int iz) {
+    const int m1 = G / 2 + 1;
+    double acc = 0.0;
+    for (int c = 0; c < 8; ++c) {
+        const int jx = (ix + (c & 1)) >> 1, jy = (iy + (c >> 1 & 1)) >> 1, jz = (iz + (c >> 2 & 1)) >> 1;
+        acc += e[((int64_t)jz * m1 + jy) * m1 + jx];
+    }
+    return 0.125 * acc;
+}
+
+// the launches of the large levels: x fastest, 64 x 4 columns per workgroup, every thread marches through PN_ZC planes
+__device__ inline bool pn_column(int G, int* ix, int* iy, int* z0, int* z1) {
+    *ix = 1 + blockIdx.x * 64 + threadIdx.x;
+    *iy = 1 + blockIdx.y * 4 + threadIdx.y;
+    *z0 = 1 + blockIdx.z * PN_ZC;
+    *z1 = *z0 + PN_ZC < G ? *z0 + PN_ZC : G;
+    return *ix < G && *iy < G;
+}
+dim3 pn_column_grid(int G) { return dim3((unsigned)((G - 1 + 63) / 64), (unsigned)((G - 1 + 3) / 4), (unsigned)((G - 1 + PN_ZC - 1) / PN_ZC)); }
+
+__global__ __launch_bounds__(PN_TPB) void k_mg_smooth(int G, const double* __restrict__ x, const double* __restrict__ b, double* __restrict__ y) {
+    int ix, iy, z0, z1;
+    if (!pn_column(G, &ix, &iy, &z0, &z1)) return;
+    const int n1 = G + 1;
+    const int64_t plane = (int64_t)n1 * n1;
+    int64_t at = pn_node(G, ix, iy, z0);
+    double lo = x[at - plane], c = x[at];
+    for (int iz = z0; iz < z1; ++iz, at += plane) {
+        const double hi = x[at + plane];
+        const double S = ((x[at - 1] + x[at + 1]) + (x[at - n1] + x[at + n1])) + (lo + hi);
+        y[at] = ((c + S) - b[at]) * (1.0 / 7.0);
+        lo = c;
+        c = hi;
+    }
+}
+
+// r = b - A x; with out == NULL only the squared norm: one partial per workgroup, part[(z * gridDim.y + y) * gridDim.x + x]
+__global__ __launch_bounds__(PN_TPB) void k_mg_residual(int G, const double* __restrict__ x, const double* __restrict__ b, double* __restrict__ out,
+                                                        double* __restrict__ part) {
+    __shared__ double s_part[PN_WAVES];
+    int ix, iy, z0, z1;
+    double acc = 0.0;
+    if (pn_column(G, &ix, &iy, &z0, &z1)) {
+        const int n1 = G + 1;
+        const int64_t plane = (int64_t)n1 * n1;
+        int64_t at = pn_node(G, ix, iy, z0);
+        double lo = x[at - plane], c = x[at];
+        for (int iz = z0; iz < z1; ++iz, at += plane) {
+            const double hi = x[at + plane];
+            const double S = ((x[at - 1] + x[at + 1]) + (x[at - n1] + x[at + n1])) + (lo + hi);
+            const double r = b[at] - (S - 6.0 * c);
+            if (out) out[at] = r;
+            acc += r * r;
+            lo = c;
+            c = hi;
+        }
+    }
+    if (!part) return;
+    const double t = wg_sum<PN_WAVES>(acc, s_part, threadIdx.y * 64 + threadIdx.x);
+    if (threadIdx.x == 0 && threadIdx.y == 0) part[((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = t;
+}
+
+// the sum of n partials by ONE workgroup: thread t takes t, t + 256, ... in ascending order, then wg_sum
+__global__ __launch_bounds__(PN_TPB) void k_pn_fold(const double* __restrict__ part, int n, double* __restrict__ out) {
+    __shared__ double s_part[PN_WAVES];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < n; i += PN_TPB) acc += part[i];
+    const double t = wg_sum<PN_WAVES>(acc, s_part, threadIdx.x);
+    if (threadIdx.x == 0) *out = t;
+}
+
+__global__ __launch_bounds__(PN_TPB) void k_mg_restrict(int Gc, const double* __restrict__ r, double* __restrict__ bc) {
+    const int ix = 1 + blockIdx.x * 64 + threadIdx.x, iy = 1 + blockIdx.y * 4 + threadIdx.y, iz = 1 + blockIdx.z;
+    if (ix >= Gc || iy >= Gc || iz >= Gc) return;
+    bc[pn_node(Gc, ix, iy, iz)] = pn_restrict_at(r, Gc, ix, iy, iz);
+}
+
+__global__ __launch_bounds__(PN_TPB) void k_mg_prolong(int G, const double* __restrict__ e, double* __restrict__ x) {
+    const int ix = 1 + blockIdx.x * 64 + threadIdx.x, iy = 1 + blockIdx.y * 4 + threadIdx.y, iz = 1 + blockIdx.z;
+    if (ix >= G || iy >= G || iz >= G) return;
+    x[pn_node(G, ix, iy, iz)] += pn_prolong_at(e, G, ix, iy, iz);
+}
+
+struct PnLevels { double *x[PN_MAX_D + 1], *t[PN_MAX_D + 1], *b[PN_MAX_D + 1]; };     // level l has 2^l cells; t: second buffer of the smoother, residual
+
+// f(at, ix, iy, iz) for every interior node of a level of G cells, the workgroup's threads striding over them
+template <class F>
+__device__ inline void pn_each_interior(int G, F f) {
+    const int m = G - 1, tot = m * m * m;
+    for (int q = threadIdx.x; q < tot; q += blockDim.x) {
+        const int ix = 1 + q % m, iy = 1 + q / m % m, iz = 1 + q / (m * m);
+        f(pn_node(G, ix, iy, iz), ix, iy, iz);
+    }
+    __syncthreads();                                                        // the level's arrays are global memory of this one workgroup
+}
+
+__device__ inline void pn_coarse_smooth2(int G, double* x, double* t, const double* b) {
+    const int n1 = G + 1;
+    const int64_t plane = (int64_t)n1 * n1;
+    pn_each_interior(G, [&](int64_t at, int, int, int) { t[at] = ((x[at] + pn_nbr_sum(x, at, n1, plane)) - b[at]) * (1.0 / 7.0); });
+    pn_each_interior(G, [&](int64_t at, int, int, int) { x[at] = ((t[at] + pn_nbr_sum(t, at, n1, plane)) - b[at]) * (1.0 / 7.0); });
+}
+
+// One V(2,2) cycle over the levels top .. 1 (top <= PN_COARSE) by ONE workgroup.  x[top] is the iterate to improve; the levels
+// below start from zero.
+__global__ __launch_bounds__(PN_COARSE_TPB) void k_mg_coarse(PnLevels L, int top) {
+    for (int l = top; l >= 2; --l) {
+        const int G = 1 << l, n1 = G + 1;
+        const int64_t plane = (int64_t)n1 * n1;
+        double *x = L.x[l], *t = L.t[l], *bc = L.b[l - 1], *xc = L.x[l - 1];
+        const double* b = L.b[l];
+        pn_coarse_smooth2(G, x, t, b);
+        pn_each_interior(G, [&](int64_t at, int, int, int) { t[at] = b[at] - (pn_nbr_sum(x, at, n1, plane) - 6.0 * x[at]); });
+        pn_each_interior(G / 2, [&](int64_t at, int ix, int iy, int iz) { bc[at] = pn_restrict_at(t, G / 2, ix, iy, iz); xc[at] = 0.0; });
+    }
+    if (threadIdx.x == 0) L.x[1][pn_node(2, 1, 1, 1)] = L.b[1][pn_node(2, 1, 1, 1)] / -6.0;      // level 1: one unknown
+    __syncthreads();
+    for (int l = 2; l <= top; ++l) {
+        const int G = 1 << l;
+        double* x = L.x[l];
+        const double* e = L.x[l - 1];
+        pn_each_interior(G, [&](int64_t at, int ix, int iy, int iz) { x[at] += pn_prolong_at(e, G, ix, iy, iz); });
+        pn_coarse_smooth2(G, x, L.t[l], L.b[l]);
+    }
+}
+
+// ------------------------------------------------------------------ rule 9 ----
+__global__ __launch_bounds__(PN_TPB) void k_pn_iso(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm, PnGrid g,
+                                                   const double* __restrict__ chi, double* __restrict__ part) {
+    __shared__ double s_part[PN_WAVES];
+    double acc = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * PN_TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * PN_TPB) {
+        if (!pn_used(pts + 3 * i, nrm + 3 * i)) continue;
+        int i0[3];
+        double w[8], v = 0.0;
+        pn_corners_weights(pts + 3 * i, g, i0, w);
+        for (int c = 0; c < 8; ++c) v = v + w[c] * chi[pn_node(g.G, i0[0] + (c & 1), i0[1] + (c >> 1 & 1), i0[2] + (c >> 2 & 1))];
+        acc += v;
+    }
+    const double t = wg_sum<PN_WAVES>(acc, s_part, threadIdx.x);
+    if (threadIdx.x == 0) part[blockIdx.x] = t;
+}
+
+// ------------------------------------------------------------------ rules 10-12 ----
+__global__ __launch_bounds__(PN_TPB) void k_pn_cubemask(int G, const double* __restrict__ chi, double iso, uint8_t* __restrict__ mask) {
+    const int64_t cube = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
+    if (cube >= (int64_t)G * G * G) return;
+    const int ix = (int)(cube % G), iy = (int)(cube / G % G), iz = (int)(cube / ((int64_t)G * G));
+    int m = 0;
+    for (int c = 0; c < 8; ++c) m |= (chi[pn_node(G, ix + (c & 1), iy + (c >> 1 & 1), iz + (c >> 2 & 1))] < iso ? 1 : 0) << c;
+    mask[cube] = (uint8_t)m;
+}
+
+// The scan between a count and a scatter kernel, in two levels: the compactions here have millions of workgroups, too many for the one
+// workgroup of compact.hip's tail.  A workgroup scans PN_SCAN_CH counts into its own row of `local` (CH + 1 entries, the last one the
+// row's total), one workgroup scans the totals, and the third launch adds the two: base[b] = survivors in the workgroups before b,
+// base[nb] = all survivors.
+constexpr int PN_SCAN_CH = 4096;
+__global__ __launch_bounds__(PN_TPB) void k_pn_scan_rows(const int32_t* __restrict__ cnt, int nb, int32_t* __restrict__ local, int32_t* __restrict__ tot) {
+    const int c0 = blockIdx.x * PN_SCAN_CH, len = nb - c0 < PN_SCAN_CH ? nb - c0 : PN_SCAN_CH;
+    int32_t* row = local + (int64_t)blockIdx.x * (PN_SCAN_CH + 1);
+    wg_scan_counts<PN_WAVES>(cnt + c0, len, row);
+    if (threadIdx.x == 0) tot[blockIdx.x] = row[len];                        // written by this thread
+}
+__global__ __launch_bounds__(PN_TPB) void k_pn_scan_totals(const int32_t* __restrict__ tot, int rows, int32_t* __restrict__ rbase) {
+    wg_scan_counts<PN_WAVES>(tot, rows, rbase);
+}
+__global__ __launch_bounds__(PN_TPB) void k_pn_scan_add(const int32_t* __restrict__ local, const int32_t* __restrict__ rbase, int nb, int rows,
+                                                        int32_t* __restrict__ base) {
+    const int64_t i = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
+    if (i < nb) base[i] = local[(i / PN_SCAN_CH) * (PN_SCAN_CH + 1) + i % PN_SCAN_CH] + rbase[i / PN_SCAN_CH];
+    if (i == nb) base[nb] = rbase[rows];
+}
+
+// edge item r = node * 7 + type: is it a crossed edge of the grid?
+__device__ inline bool pn_edge_crossed(int G, const double* __restrict__ chi, double iso, int64_t r, int64_t items) {
+    if (r >= items) return false;
+    const int n1 = G + 1, type = (int)(r % 7);
+    const int64_t node = r / 7;
+    const int ix = (int)(node % n1), iy = (int)(node / n1 % n1), iz = (int)(node / ((int64_t)n1 * n1));
+    if (!pn_edge_in_grid(G, ix, iy, iz, type)) return false;
+    const int m = pn_type_mask(type);
+    return (chi[node] < iso) != (chi[pn_node(G, ix + (m & 1), iy + (m >> 1 & 1), iz + (m >> 2 & 1))] < iso);
+}
+
+__global__ __launch_bounds__(PN_TPB) void k_pn_edge_count(int G, const double* __restrict__ chi, double iso, int64_t items,
+                                                          unsigned long long* __restrict__ words, int32_t* __restrict__ cnt) {
+    __shared__ int s_wsum[PN_WAVES];
+    const int64_t r = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
+    const bool f = pn_edge_crossed(G, chi, iso, r, items);
+    const unsigned long long bal = __ballot(f);
+    if ((threadIdx.x & 63) == 0) words[r >> 6] = bal;
+    const WgRank k = wg_rank<PN_WAVES>(f, s_wsum);
+    if (threadIdx.x == 0) cnt[blockIdx.x] = k.total;
+}
+
+// the number of the vertex on edge item r (a set flag): the survivors of the workgroups before its own, then popcounts
+__device__ inline int32_t pn_vertex_index(const unsigned long long* __restrict__ words, const int32_t* __restrict__ base, int64_t r) {
+    const int64_t blk = r >> 8, w = r >> 6;
+    int32_t acc = base[blk];
+    for (int64_t q = blk * PN_WAVES; q < w; ++q) acc += __popcll(words[q]);
+    return acc + __popcll(words[w] & ((1ull << (r & 63)) - 1ull));
+}
+
+__device__ inline void pn_node_pos(const PnGrid& g, int ix, int iy, int iz, double* p) {
+    p[0] = g.o[0] + g.h * (double)ix; p[1] = g.o[1] + g.h * (double)iy; p[2] = g.o[2] + g.h * (double)iz;
+}
+
+__global__ __launch_bounds__(PN_TPB) void k_pn_vertex_scatter(PnGrid g, const double* __restrict__ chi, double iso, int64_t items,
+                                                              const unsigned long long* __restrict__ words, const int32_t* __restrict__ base,
+                                                              double* __restrict__ vertices) {
+    __shared__ int s_wsum[PN_WAVES];
+    const int64_t r = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
+    const bool f = (words[r >> 6] >> (r & 63)) & 1ull;                       // the bitmap covers whole workgroups
+    const int64_t pos = (int64_t)base[blockIdx.x] + wg_rank<PN_WAVES>(f, s_wsum).rank;
+    if (!f) return;
+    const int n1 = g.G + 1, m = pn_type_mask((int)(r % 7));
+    const int64_t node = r / 7;
+    const int ix = (int)(node % n1), iy = (int)(node / n1 % n1), iz = (int)(node / ((int64_t)n1 * n1));
+    const int jx = ix + (m & 1), jy = iy + (m >> 1 & 1), jz = iz + (m >> 2 & 1);
+    const double vl = chi[node], vh = chi[pn_node(g.G, jx, jy, jz)];
+    double pl[3], ph[3], out[3];
+    pn_node_pos(g, ix, iy, iz, pl);
+    pn_node_pos(g, jx, jy, jz, ph);
+    if (vl < iso) pn_vertex(vl, vh, pl, ph, iso, out); else pn_vertex(vh, vl, ph, pl, iso, out);
+    for (int a = 0; a < 3; ++a) vertices[3 * pos + a] = out[a];
+}
+
+// face item r = (cube * 6 + tetrahedron) * 2 + slot: the inside bits of the tetrahedron's corners, or -1 when the slot is empty
+__device__ inline int pn_face_item(const uint8_t* __restrict__ mask, int64_t r, int64_t items) {
+    if (r >= items) return -1;
+    const int cm = mask[r / 12];
+    if (cm == 0 || cm == 255) return -1;
+    const int k = (int)(r % 12) >> 1, slot = (int)(r & 1);
+    int in = 0;
+    for (int i = 0; i < 4; ++i) in |= (cm >> pn_tet_corner(k, i) & 1) << i;
+    const int ni = __popc(in);
+    return (slot == 0 ? ni >= 1 && ni <= 3 : ni == 2) ? in : -1;
+}
+
+__global__ __launch_bounds__(PN_TPB) void k_pn_face_count(const uint8_t* __restrict__ mask, int64_t items, int32_t* __restrict__ cnt) {
+    __shared__ int s_wsum[PN_WAVES];
+    const int64_t r = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
+    const WgRank k = wg_rank<PN_WAVES>(pn_face_item(mask, r, items) >= 0, s_wsum);
+    if (threadIdx.x == 0) cnt[blockIdx.x] = k.total;
+}
+
+__global__ __launch_bounds__(PN_TPB) void k_pn_face_scatter(int G, const uint8_t* __restrict__ mask, int64_t items,
+                                                            const unsigned long long* __restrict__ words, const int32_t* __restrict__ vbase,
+                                                            const double* __restrict__ vertices, const int32_t* __restrict__ fbase,
+                                                            int32_t* __restrict__ faces) {
+    __shared__ int s_wsum[PN_WAVES];
+    const int64_t r = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
+    const int in = pn_face_item(mask, r, items);
+    const int64_t pos = (int64_t)fbase[blockIdx.x] + wg_rank<PN_WAVES>(in >= 0, s_wsum).rank;
+    if (in < 0) return;
+    const int64_t cube = r / 12;
+    const int k = (int)(r % 12) >> 1, slot = (int)(r & 1);
+    const int ix = (int)(cube % G), iy = (int)(cube / G % G), iz = (int)(cube / ((int64_t)G * G));
+    int ci[4], co[4];
+    const int n = pn_tet_cycle(in, ci, co);
+    int32_t idx[4];
+    double pos3[4][3], d[3];
+    for (int q = 0; q < n; ++q) {
+        int nm, type;
+        pn_tet_edge(k, ci[q], co[q], &nm, &type);
+        idx[q] = pn_vertex_index(words, vbase, pn_node(G, ix + (nm & 1), iy + (nm >> 1 & 1), iz + (nm >> 2 & 1)) * 7 + type);
+        for (int a = 0; a < 3; ++a) pos3[q][a] = vertices[3 * (int64_t)idx[q] + a];
+    }
+    pn_tet_dir(k, in, d);
+    pn_polygon(n, idx, pos3, d);
+    faces[3 * pos] = idx[0];
+    faces[3 * pos + 1] = idx[slot ? 2 : 1];
+    faces[3 * pos + 2] = idx[slot ? 3 : 2];
+}
+
+// ------------------------------------------------------------------ host ----
+int check_pn(const char* fn, int64_t n, const void* points, const void* normals, const mvs_poisson_params* p, const void* info,
+             const void* out_a, int64_t cap_a, const void* out_b, int64_t cap_b) {
+    if (!points || !normals || !p || !info) return bad(fn, "points, normals, params or info is NULL");
+    if (n < 0) return bad(fn, "n is negative");
+    if (cap_a < 0 || cap_b < 0) return bad(fn, "a capacity is negative");
+    if ((cap_a > 0 && !out_a) || (cap_b > 0 && !out_b)) return bad(fn, "an output with a capacity above 0 is NULL");
+    if (!std::isfinite(p->scale) || !std::isfinite(p->samples_per_node) || !std::isfinite(p->solve_tol)) return bad(fn, "a parameter is not finite");
+    if (p->scale <= 0.0 || p->samples_per_node <= 0.0 || p->solve_tol <= 0.0) return bad(fn, "need scale, samples_per_node, solve_tol > 0");
+    if (p->depth_min < 3) return bad(fn, "need depth_min >= 3");
+    if (p->depth_min > p->depth_max) return bad(fn, "depth_min exceeds depth_max");
+    if (p->depth_min > PN_MAX_D) return bad(fn, "depth_min exceeds MVS_POISSON_MAX_DEPTH");
+    if (p->scale <= 1.0 + 4.0 / (double)(1 << p->depth_min)) return bad(fn, "need scale > 1 + 4 / 2^depth_min: every point a cell from the boundary");
+    if (p->max_cycles < 1) return bad(fn, "need max_cycles >= 1");
+    return MVS_OK;
+}
+
+// One call: the grid, the field and the counts; the scatter once the caller's capacities are known to suffice.
+struct PnRun {
+    const mvs_poisson_params& p;
+    mvs_poisson_info& info;
+    int64_t n;
+    const double *pts, *nrm;
+    hipStream_t s;
+    PnGrid g{};
+    int64_t nn = 0;                       // nodes of the finest level
+    Scratch part, sums, rhs, coarse, red, mask, words;
+    struct Scan {                         // counts, their scan and its two levels, for nb workgroups
+        Scratch cnt, base, local, tot, rbase;
+        int alloc(size_t nb, hipStream_t s) {
+            const size_t rows = (nb + PN_SCAN_CH - 1) / PN_SCAN_CH;
+            int rc;
+            if ((rc = cnt.alloc(4 * nb, s)) || (rc = base.alloc(4 * (nb + 1), s)) || (rc = local.alloc(4 * rows * (PN_SCAN_CH + 1), s)) ||
+                (rc = tot.alloc(4 * rows, s))) return rc;
+            return rbase.alloc(4 * (rows + 1), s);
+        }
+        void run(int nb, hipStream_t s) {
+            const int rows = (nb + PN_SCAN_CH - 1) / PN_SCAN_CH;
+            k_pn_scan_rows<<<dim3((unsigned)rows), dim3(PN_TPB), 0, s>>>(cnt.as<int32_t>(), nb, local.as<int32_t>(), tot.as<int32_t>());
+            k_pn_scan_totals<<<dim3(1), dim3(PN_TPB), 0, s>>>(tot.as<int32_t>(), rows, rbase.as<int32_t>());
+            k_pn_scan_add<<<dim3((unsigned)(nb / PN_TPB + 1)), dim3(PN_TPB), 0, s>>>(local.as<int32_t>(), rbase.as<int32_t>(), nb, rows, base.as<int32_t>());
+        }
+    } ve, fa;
+    PnLevels L{};
+    double iso = 0.0;
+    int64_t edge_items = 0, face_items = 0;
+    PnRun(const mvs_poisson_params& prm, mvs_poisson_info& inf, int64_t n_, const double* pd, const double* nd, hipStream_t st)
+        : p(prm), info(inf), n(n_), pts(pd), nrm(nd), s(st) { std::memset(&info, 0, sizeof info); }
+
+    int fetch(void* dst, const void* src, size_t bytes) {
+        HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return MVS_OK;
+    }
+
+    // rules 1-4
+    int grid(const char* fn) {
+        int rc;
+        if (n < 2) { mvs_set_error("%s: fewer than 2 points", fn); return MVS_E_DEGENERATE; }
+        const int nb = (int)std::min<int64_t>(PN_RED_NB, (n + PN_TPB - 1) / PN_TPB);
+        if ((rc = part.alloc(sizeof(double) * 7 * PN_RED_NB, s))) return rc;
+        k_pn_bbox<<<dim3((unsigned)nb), dim3(PN_TPB), 0, s>>>(n, pts, nrm, part.as<double>());
+        HIPCHK(hipGetLastError());
+        std::vector<double> hp((size_t)7 * nb);
+        if ((rc = fetch(hp.data(), part.p, sizeof(double) * hp.size()))) return rc;
+        double lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL}, cnt = 0.0;
+        for (int b = 0; b < nb; ++b) {
+            for (int a = 0; a < 3; ++a) { lo[a] = std::fmin(lo[a], hp[7 * b + a]); hi[a] = std::fmax(hi[a], hp[7 * b + 3 + a]); }
+            cnt += hp[7 * b + 6];
+        }
+        info.n_used = (int64_t)cnt;
+        if (info.n_used > (1ll << 26)) return bad(fn, "more than 2^26 used points");
+        double ext = 0.0;
+        for (int a = 0; a < 3; ++a) ext = std::fmax(ext, hi[a] - lo[a]);
+        if (info.n_used < 2 || !(ext > 0.0)) { mvs_set_error("%s: fewer than 2 used points, or a bounding box of zero extent", fn); return MVS_E_DEGENERATE; }
+        const double side = p.scale * ext;                                                       // rule 2
+        for (int a = 0; a < 3; ++a) g.o[a] = 0.5 * (lo[a] + hi[a]) - 0.5 * side;
+        const int dmax = p.depth_max < PN_MAX_D ? p.depth_max : PN_MAX_D;
+        int D = p.depth_min;
+        if (dmax > p.depth_min) {                                                                // rule 3
+            PnOcc q{};
+            q.dmin = p.depth_min; q.dmax = dmax;
+            int64_t w = 0;
+            for (int d = q.dmin; d <= dmax; ++d) { q.cs[d] = side / (double)(1 << d); q.word0[d] = w; w += ((int64_t)1 << (3 * d)) / 32; }
+            q.word0[dmax + 1] = w;
+            for (int a = 0; a < 3; ++a) q.o[a] = g.o[a];
+            Scratch bits, occ;
+            unsigned long long hocc[PN_MAX_D + 1];
+            if ((rc = bits.alloc(sizeof(unsigned) * (size_t)w, s)) || (rc = occ.alloc(sizeof hocc, s))) return rc;
+            HIPCHK(hipMemsetAsync(bits.p, 0, sizeof(unsigned) * (size_t)w, s));
+            HIPCHK(hipMemsetAsync(occ.p, 0, sizeof hocc, s));
+            k_pn_occupy<<<dim3((unsigned)((n + PN_TPB - 1) / PN_TPB)), dim3(PN_TPB), 0, s>>>(n, pts, nrm, q, bits.as<unsigned>());
+            k_pn_popcount<<<dim3((unsigned)((w + PN_TPB - 1) / PN_TPB)), dim3(PN_TPB), 0, s>>>(q, bits.as<unsigned>(), occ.as<unsigned long long>());
+            HIPCHK(hipGetLastError());
+            if ((rc = fetch(hocc, occ.p, sizeof hocc))) return rc;
+            for (int d = q.dmin; d <= dmax; ++d)
+                if ((double)info.n_used >= p.samples_per_node * (double)hocc[d]) D = d;
+        }
+        g.G = 1 << D;                                                                            // rule 4
+        g.h = side / (double)g.G;
+        nn = (int64_t)(g.G + 1) * (g.G + 1) * (g.G + 1);
+        info.depth = D;
+        info.h = g.h;
+        for (int a = 0; a < 3; ++a) info.origin[a] = g.o[a];
+        return MVS_OK;
+    }
+
+    int levels() {
+        // the finest level: three planar arrays of 8 bytes per node — the int64 sums of the splat, then x, t and a spare — and b;
+        // the levels below in one block, x | t | b each
+        int rc;
+        const int D = info.depth;
+        if ((rc = sums.alloc(24 * (size_t)nn, s)) || (rc = rhs.alloc(8 * (size_t)nn, s))) return rc;
+        size_t below = 0;
+        for (int l = 1; l < D; ++l) below += 3 * (size_t)((1 << l) + 1) * ((1 << l) + 1) * ((1 << l) + 1);
+        if ((rc = coarse.alloc(8 * below, s))) return rc;
+        HIPCHK(hipMemsetAsync(coarse.p, 0, 8 * below, s));                    // depth >= 3: there are levels below
+        double* at = coarse.as<double>();
+        for (int l = 1; l < D; ++l) {
+            const size_t m = (size_t)((1 << l) + 1) * ((1 << l) + 1) * ((1 << l) + 1);
+            L.x[l] = at; L.t[l] = at + m; L.b[l] = at + 2 * m;
+            at += 3 * m;
+        }
+        L.x[D] = sums.as<double>(); L.t[D] = sums.as<double>() + nn; L.b[D] = rhs.as<double>();
+        return MVS_OK;
+    }
+
+    int norm2(int l, double* out) {                                          // |b - A x|^2 of level l, on the host
+        const int G = 1 << l;
+        const dim3 gr = pn_column_grid(G);
+        const int np = (int)(gr.x * gr.y * gr.z);
+        k_mg_residual<<<gr, dim3(64, 4), 0, s>>>(G, L.x[l], L.b[l], nullptr, red.as<double>() + 1);
+        k_pn_fold<<<dim3(1), dim3(PN_TPB), 0, s>>>(red.as<double>() + 1, np, red.as<double>());
+        HIPCHK(hipGetLastError());
+        return fetch(out, red.p, sizeof(double));
+    }
+
+    void smooth2(int l) {
+        const int G = 1 << l;
+        k_mg_smooth<<<pn_column_grid(G), dim3(64, 4), 0, s>>>(G, L.x[l], L.b[l], L.t[l]);
+        k_mg_smooth<<<pn_column_grid(G), dim3(64, 4), 0, s>>>(G, L.t[l], L.b[l], L.x[l]);
+    }
+
+    int vcycle() {
+        const int D = info.depth;
+        for (int l = D; l > PN_COARSE; --l) {
+            const int G = 1 << l, Gc = G / 2;
+            smooth2(l);
+            k_mg_residual<<<pn_column_grid(G), dim3(64, 4), 0, s>>>(G, L.x[l], L.b[l], L.t[l], nullptr);
+            k_mg_restrict<<<dim3((unsigned)((Gc - 1 + 63) / 64), (unsigned)((Gc - 1 + 3) / 4), (unsigned)(Gc - 1)), dim3(64, 4), 0, s>>>(Gc, L.t[l], L.b[l - 1]);
+            HIPCHK(hipMemsetAsync(L.x[l - 1], 0, 8 * (size_t)(Gc + 1) * (Gc + 1) * (Gc + 1), s));
+        }
+        k_mg_coarse<<<dim3(1), dim3(PN_COARSE_TPB), 0, s>>>(L, D < PN_COARSE ? D : PN_COARSE);
+        for (int l = PN_COARSE + 1; l <= D; ++l) {
+            const int G = 1 << l;
+            k_mg_prolong<<<dim3((unsigned)((G - 1 + 63) / 64), (unsigned)((G - 1 + 3) / 4), (unsigned)(G - 1)), dim3(64, 4), 0, s>>>(G, L.x[l - 1], L.x[l]);
+            smooth2(l);
+        }
+        HIPCHK(hipGetLastError());
+        return MVS_OK;
+    }
+
+    // rules 5-8
+    int field(const char* fn) {
+        int rc;
+        if ((rc = levels())) return rc;
+        const int D = info.depth;
+        const unsigned nblk = (unsigned)((nn + PN_TPB - 1) / PN_TPB);
+        HIPCHK(hipMemsetAsync(sums.p, 0, 24 * (size_t)nn, s));
+        k_pn_splat<<<dim3((unsigned)((n + PN_TPB - 1) / PN_TPB)), dim3(PN_TPB), 0, s>>>(n, pts, nrm, g, sums.as<unsigned long long>());
+        k_pn_rhs<<<dim3(nblk), dim3(PN_TPB), 0, s>>>(g, sums.as<long long>(), rhs.as<double>());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemsetAsync(sums.p, 0, 16 * (size_t)nn, s));                // the sums are spent: x = 0 and the smoother's second buffer
+        const dim3 gr = pn_column_grid(g.G);
+        if ((rc = red.alloc(sizeof(double) * (1 + (size_t)gr.x * gr.y * gr.z), s))) return rc;
+        double b2 = 0.0, r2 = 0.0;
+        if ((rc = norm2(D, &b2))) return rc;                                  // x = 0: the residual is b
+        if (!(b2 > 0.0)) return MVS_OK;                                       // b = 0 (or not finite): chi = 0 solves it
+        for (int c = 1; c <= p.max_cycles; ++c) {
+            if ((rc = vcycle()) || (rc = norm2(D, &r2))) return rc;
+            info.cycles = c;
+            info.rel_residual = std::sqrt(r2) / std::sqrt(b2);
+            if (std::sqrt(r2) <= p.solve_tol * std::sqrt(b2)) return MVS_OK;
+        }
+        mvs_set_error("%s: relative residual %.3e after %d cycles, above solve_tol %.3e", fn, info.rel_residual, info.cycles, p.solve_tol);
+        return MVS_E_SOLVER;
+    }
+
+    // rule 9
+    int iso_value() {
+        const int nb = (int)std::min<int64_t>(PN_RED_NB, (n + PN_TPB - 1) / PN_TPB);
+        k_pn_iso<<<dim3((unsigned)nb), dim3(PN_TPB), 0, s>>>(n, pts, nrm, g, L.x[info.depth], part.as<double>() + 1);
+        k_pn_fold<<<dim3(1), dim3(PN_TPB), 0, s>>>(part.as<double>() + 1, nb, part.as<double>());
+        HIPCHK(hipGetLastError());
+        double sum = 0.0;
+        int rc = fetch(&sum, part.p, sizeof(double));
+        if (rc) return rc;
+        info.iso = iso = sum / (double)info.n_used;
+        return MVS_OK;
+    }
+
+    // rules 10-12 up to the counts
+    int count() {
+        int rc;
+        const int G = g.G;
+        const double* chi = L.x[info.depth];
+        const int64_t cubes = (int64_t)G * G * G;
+        edge_items = 7 * nn;
+        face_items = 12 * cubes;
+        const int64_t nbe = (edge_items + PN_TPB - 1) / PN_TPB, nbf = (face_items + PN_TPB - 1) / PN_TPB;
+        if ((rc = mask.alloc((size_t)cubes, s)) || (rc = words.alloc(sizeof(unsigned long long) * PN_WAVES * (size_t)nbe, s)) ||
+            (rc = ve.alloc((size_t)nbe, s)) || (rc = fa.alloc((size_t)nbf, s))) return rc;
+        k_pn_cubemask<<<dim3((unsigned)((cubes + PN_TPB - 1) / PN_TPB)), dim3(PN_TPB), 0, s>>>(G, chi, iso, mask.as<uint8_t>());
+        k_pn_edge_count<<<dim3((unsigned)nbe), dim3(PN_TPB), 0, s>>>(G, chi, iso, edge_items, words.as<unsigned long long>(), ve.cnt.as<int32_t>());
+        ve.run((int)nbe, s);
+        k_pn_face_count<<<dim3((unsigned)nbf), dim3(PN_TPB), 0, s>>>(mask.as<uint8_t>(), face_items, fa.cnt.as<int32_t>());
+        fa.run((int)nbf, s);
+        HIPCHK(hipGetLastError());
+        int32_t nv = 0, nf = 0;                                               // base[nb]: all survivors
+        HIPCHK(hipMemcpyAsync(&nv, ve.base.as<int32_t>() + nbe, 4, hipMemcpyDeviceToHost, s));
+        if ((rc = fetch(&nf, fa.base.as<int32_t>() + nbf, 4))) return rc;
+        info.n_vertices = nv;
+        info.n_faces = nf;
+        return MVS_OK;
+    }
+
+    int scatter(double* vertices, int32_t* faces) {
+        if (info.n_vertices == 0) return MVS_OK;
+        const int64_t nbe = (edge_items + PN_TPB - 1) / PN_TPB, nbf = (face_items + PN_TPB - 1) / PN_TPB;
+        k_pn_vertex_scatter<<<dim3((unsigned)nbe), dim3(PN_TPB), 0, s>>>(g, L.x[info.depth], iso, edge_items, words.as<unsigned long long>(),
+                                                                        ve.base.as<int32_t>(), vertices);
+        k_pn_face_scatter<<<dim3((unsigned)nbf), dim3(PN_TPB), 0, s>>>(g.G, mask.as<uint8_t>(), face_items, words.as<unsigned long long>(),
+                                                                      ve.base.as<int32_t>(), vertices, fa.base.as<int32_t>(), faces);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(s));
+        return MVS_OK;
+    }
+
+    int counts(const char* fn) {
+        int rc;
+        if ((rc = grid(fn)) || (rc = field(fn)) || (rc = iso_value())) return rc;
+        return count();
+    }
+};
+
+int too_small(const char* fn) { return bad(fn, "a capacity is below the count (info holds n_vertices and n_faces)"); }
+
+}  // namespace
+
+// the device form for a caller inside the library that cannot know the counts in advance (mvs_processor_poisson): the blocks are sized
+// once the counts are known
+int poisson_blocks(const char* fn, int64_t n, const double* points_dev, const double* normals_dev, const mvs_poisson_params* p,
+                   mvs_poisson_info* info, Scratch* vertices, Scratch* faces) {
+    int rc = check_pn(fn, n, points_dev, normals_dev, p, info, nullptr, 0, nullptr, 0);
+    if (rc) return rc;
+    PnRun run(*p, *info, n, points_dev, normals_dev, nullptr);
+    if ((rc = run.counts(fn))) return rc;
+    if ((rc = vertices->alloc(24 * (size_t)info->n_vertices)) || (rc = faces->alloc(12 * (size_t)info->n_faces))) return rc;
+    return run.scatter(vertices->as<double>(), faces->as<int32_t>());
+}
+
+extern "C" {
+
+void mvs_poisson_default_params(mvs_poisson_params* p) {
+    if (!p) return;
+    p->scale = 1.1; p->samples_per_node = 1.5; p->solve_tol = 1e-8;
+    p->depth_max = 10; p->depth_min = 7; p->max_cycles = 64; p->reserved = 0;
+}
+
+int mvs_poisson_reconstruct_dev(int64_t n, const double* points_dev, const double* normals_dev, const mvs_poisson_params* p, mvs_poisson_info* info,
+                                double* vertices_dev, int64_t vertex_capacity, int32_t* faces_dev, int64_t face_capacity, void* hip_stream) {
+    MVS_TRACE();
+    int rc = check_pn(__func__, n, points_dev, normals_dev, p, info, vertices_dev, vertex_capacity, faces_dev, face_capacity);
+    if (rc) return rc;
+    if ((rc = need_device())) return rc;
+    PnRun run(*p, *info, n, points_dev, normals_dev, (hipStream_t)hip_stream);
+    if ((rc = run.counts(__func__))) return rc;
+    if (info->n_vertices > vertex_capacity || info->n_faces > face_capacity) return too_small(__func__);
+    return run.scatter(vertices_dev, faces_dev);
+}
+
+int mvs_poisson_reconstruct(int64_t n, const double* points, const double* normals, const mvs_poisson_params* p, mvs_poisson_info* info,
+                            double* vertices, int64_t vertex_capacity, int32_t* faces, int64_t face_capacity) {
+    MVS_TRACE();
+    int rc = check_pn(__func__, n, points, normals, p, info, vertices, vertex_capacity, faces, face_capacity);
+    if (rc) return rc;
+    if ((rc = need_device())) return rc;
+    Scratch dp, dn, dv, df;
+    if ((rc = up(dp, points, 3 * (size_t)n)) || (rc = up(dn, normals, 3 * (size_t)n))) return rc;
+    PnRun run(*p, *info, n, dp.as<double>(), dn.as<double>(), nullptr);
+    if ((rc = run.counts(__func__))) return rc;
+    if (info->n_vertices > vertex_capacity || info->n_faces > face_capacity) return too_small(__func__);
+    const size_t V = (size_t)info->n_vertices, F = (size_t)info->n_faces;
+    if ((rc = dv.alloc(24 * V)) || (rc = df.alloc(12 * F)) || (rc = run.scatter(dv.as<double>(), df.as<int32_t>()))) return rc;
+    if ((rc = down(vertices, dv, 3 * V))) return rc;
+    return down(faces, df, 3 * F);
+}
+
+int mvs_test_poisson_field(int64_t n, const double* points, const double* normals, const mvs_poisson_params* p, mvs_poisson_info* info, double* rhs,
+                           double* chi, int64_t node_capacity) {
+    MVS_TRACE();
+    int rc = check_pn(__func__, n, points, normals, p, info, rhs, node_capacity, chi, node_capacity);
+    if (rc) return rc;
+    if ((rc = need_device())) return rc;
+    Scratch dp, dn;
+    if ((rc = up(dp, points, 3 * (size_t)n)) || (rc = up(dn, normals, 3 * (size_t)n))) return rc;
+    PnRun run(*p, *info, n, dp.as<double>(), dn.as<double>(), nullptr);
+    if ((rc = run.grid(__func__))) return rc;
+    if (run.nn > node_capacity) return bad(__func__, "node_capacity is below (2^depth + 1)^3 (info holds the depth)");
+    const int frc = run.field(__func__);                                      // MVS_E_SOLVER still hands out the field it reached
+    if (frc && frc != MVS_E_SOLVER) return frc;
+    if (!frc && (rc = run.iso_value())) return rc;
+    HIPCHK(hipMemcpy(rhs, run.rhs.p, 8 * (size_t)run.nn, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(chi, run.L.x[info->depth], 8 * (size_t)run.nn, hipMemcpyDeviceToHost));
+    return frc;
+}
+
+}  // extern "C"

@@ -27,4 +27,8 @@ int render_views_dev(const double* pts, int64_t V, const int32_t* faces, int64_t
 // Validates like mvs_point_sample, reporting under the name fn.
 int point_sample_vectors(const char* fn, int32_t n_seq, const int32_t* cam_off, const mvs_camera* cams, const float* depths,
                          const mvs_point_sample_params* p, int64_t* seq_offsets, std::vector<double>* points, std::vector<double>* normals);
+// mvs_poisson_reconstruct_dev (poisson.hip) with outputs that size themselves: vertices / faces are allocated once info holds the
+// counts.  Validates like mvs_poisson_reconstruct, reporting under the name fn; the caller has a device.  Default stream.
+int poisson_blocks(const char* fn, int64_t n, const double* points_dev, const double* normals_dev, const mvs_poisson_params* p,
+                   mvs_poisson_info* info, Scratch* vertices, Scratch* faces);
 #endif

@@ -5,8 +5,9 @@ over adjacent sequences of ``Processor::CalcSimilarityTransformationSeq`` (:629-
 through ``mvs_gen_new_views`` (Image3D::GenNewViews) and ``mvs_keypoint_cull`` (the background cull of the key points); the descriptor
 matching between them, FeatureProc::MatchFeature (R/FeatureProc/FeatureProc.cpp:77-130), through ``mvs_sift_match_lists``; the SIFT
 detection in front of the cull, FeatureProc::DetectFeature (:14-75,103-112), through ``mvs_sift_detect``; the point sampling between
-``CheckConsistency`` and the stitch tail, GeometryRec::RunPointSample (R/Processor/Processor.cpp:933-949), through ``mvs_point_sample``.
-The functions stand in pipeline order."""
+``CheckConsistency`` and the stitch tail, GeometryRec::RunPointSample (R/Processor/Processor.cpp:933-949), through ``mvs_point_sample``;
+the surface reconstruction between the stitch tail and the trim of the model, GeometryRec::RunPoisson (:1042-1058), through
+``mvs_poisson_reconstruct``.  The functions stand in pipeline order."""
 from __future__ import annotations
 
 import contextlib
@@ -542,6 +543,74 @@ def StitchPointSets(npts_paths, scales, Rs, ts, cameras, out_dir, truncate: bool
     L.check(L.lib().mvs_processor_stitch_points(n, paths, L.ptr(s), L.ptr(R), L.ptr(t), L.ptr(coff), cams,
                                                 L.STITCH_TRUNCATE if truncate else 0, os.fsencode(out_dir), L.ptr(nk)))
     return nk
+
+
+# ------------------------------------------------------------------ surface reconstruction ----
+def poisson_params(**kw) -> L.CPoissonParams:
+    """``mvs_poisson_default_params`` (scale 1.1, samples_per_node 1.5, solve_tol 1e-8, config.txt's PsnDptMax 10 and PsnDptMin 7,
+    max_cycles 64) with the given fields replaced."""
+    return _params(L.CPoissonParams, L.lib().mvs_poisson_default_params, kw)
+
+
+def _poisson_info(info: L.CPoissonInfo) -> dict:
+    return dict(origin=np.array(info.origin[:]), h=info.h, iso=info.iso, rel_residual=info.rel_residual, n_used=info.n_used,
+                n_vertices=info.n_vertices, n_faces=info.n_faces, depth=info.depth, cycles=info.cycles)
+
+
+def RunPoisson(points, normals, params: L.CPoissonParams | None = None, stream: int | None = None, capacity: tuple | None = None):
+    """GeometryRec::RunPoisson (R/Processor/Processor.cpp:1042-1058) through ``mvs_poisson_reconstruct`` (the rules, this library's
+    definition: include/mvs.h).  ``points`` and ``normals`` are [n, 3] float64 — numpy arrays, or contiguous torch tensors on the GPU
+    (the device form: the results are tensors on the same device, and the kernels and the allocation of the results are ordered on
+    ``stream``, the HIP stream that produced the points; None: the legacy default stream).
+    -> (vertices [V, 3] float64, faces [F, 3] int32, info dict: origin, h, iso, rel_residual, n_used, n_vertices, n_faces, depth, cycles).
+    ``capacity`` = (vertex rows, face rows) sizes the first attempt, by default 12 * 4^Dmax vertices and twice as many faces (a closed
+    surface of modest area at the finest depth the call can pick); a call that finds more is repeated once with the right sizes."""
+    prm = params if params is not None else poisson_params()
+    dev = _is_dev(points)
+    if dev != _is_dev(normals):
+        raise L.MvsError(-1, "points and normals must both be tensors on the GPU or both arrays")
+    order = contextlib.nullcontext()
+    if dev:
+        import torch
+        if stream:
+            order = torch.cuda.stream(torch.cuda.ExternalStream(int(stream)))
+        if tuple(points.shape) != tuple(normals.shape) or points.dim() != 2 or points.shape[1] != 3:
+            raise L.MvsError(-1, "points and normals must be [n, 3]")
+        pp, pn, n = _dev_ptr(points, "float64", "points"), _dev_ptr(normals, "float64", "normals"), int(points.shape[0])
+        fn, tail = L.lib().mvs_poisson_reconstruct_dev, (L.ptr(stream),)
+    else:
+        points, normals = L.arr(points, np.float64).reshape(-1, 3), L.arr(normals, np.float64).reshape(-1, 3)
+        if points.shape != normals.shape:
+            raise L.MvsError(-1, "points and normals must be [n, 3]")
+        pp, pn, n = L.ptr(points), L.ptr(normals), len(points)
+        fn, tail = L.lib().mvs_poisson_reconstruct, ()
+    if n == 0:                                                  # a pointer to nothing is still a pointer
+        pp = pn = L.ptr(np.zeros(3))
+    if capacity is None:
+        dmax = max(0, min(int(prm.depth_max), 9))
+        capacity = (12 * 4 ** dmax, 24 * 4 ** dmax)
+    info = L.CPoissonInfo()
+    with order:
+        def call(vcap, fcap):
+            v, f = _out_like(points, (max(1, vcap), 3), "float64"), _out_like(points, (max(1, fcap), 3), "int32")
+            return fn(n, pp, pn, C.byref(prm), C.byref(info), L.ptr(v), vcap, L.ptr(f), fcap, *tail), v, f
+
+        vcap, fcap = int(capacity[0]), int(capacity[1])
+        rc, v, f = call(vcap, fcap)
+        if rc == -1 and (info.n_vertices > vcap or info.n_faces > fcap):
+            vcap, fcap = int(info.n_vertices), int(info.n_faces)
+            rc, v, f = call(vcap, fcap)
+    L.check(rc)
+    return v[:info.n_vertices], f[:info.n_faces], _poisson_info(info)
+
+
+def PoissonFiles(psr_npts, model_obj, params: L.CPoissonParams | None = None):
+    """``mvs_processor_poisson``: ``psr_npts`` (Result/PSR.npts, what ``StitchPointSets`` wrote) -> ``model_obj`` (Result/Model.obj with
+    `v`, `vn` and `f` lines, what ``CullPoissonModel`` reads).  -> (V, F) written."""
+    prm = params if params is not None else poisson_params()
+    V, F = C.c_int64(), C.c_int64()
+    L.check(L.lib().mvs_processor_poisson(os.fsencode(psr_npts), C.byref(prm), os.fsencode(model_obj), C.byref(V), C.byref(F)))
+    return V.value, F.value
 
 
 def CullPoissonModel(model_obj, scales, Rs, ts, cameras, out_obj, all_seq_proj: bool = True):

@@ -646,6 +646,69 @@ int mvs_poisson_reconstruct_dev(int64_t n, const double* points_dev, const doubl
                                 mvs_poisson_info* info, double* vertices_dev, int64_t vertex_capacity, int32_t* faces_dev,
                                 int64_t face_capacity, void* hip_stream);
 
+/* Sampling density: weighting of the normals, a density per vertex, and a trim of the mesh by it.  PSR.npts concatenates every
+ * sequence's points, so the sampling density doubles where two sequences overlap; rule 5 splats every normal with unit mass, the jump of
+ * chi across the surface follows the local density and the one iso value of rule 9 cuts the surface at the wrong offset where the
+ * density differs from the mean.  Rules 14-18 continue the list above; like rules 1-13 they are this library's definition and are NOT
+ * VERIFIED against GeoRec.  By default the weighting is off and nothing is trimmed: the results are those of mvs_poisson_reconstruct.
+ *  14. density grid : Dd = max(D - density_drop, 2), Gd = 2^Dd, hd = side / Gd, the origin o of rule 2.  Every used point has the corners
+ *                    and weights of rule 5 on that grid; q = llrint(w * 2^36) is summed in int64 per node; W = (double)sum * 2^-36.
+ *  15. point density: rho_p = the trilinear W at p: corners and weights of rule 14, added in corner order bx + 2 by + 4 bz.  A point sees
+ *                    its own splat: rho_p >= 1/8 up to the quantisation.  rho_mean = ((double) sum_p llrint(rho_p * 2^16)) * 2^-16 /
+ *                    (double)N: an int64 sum, which does not depend on its order (it stays inside int64 while sum_p rho_p < 2^47,
+ *                    which every N <= 2^23 ensures; beyond that the result is unspecified).
+ *  16. weighted splat (flag MVS_POISSON_WEIGHT_NORMALS): s_p = min(rho_mean / rho_p, max_gain), and rule 5's contribution becomes
+ *                    x = w * (n_a * s_p).  With the flag a call of more than 2^22 rows, used or not, gives MVS_E_INVALID_ARG: with
+ *                    w <= 1, |n_a| <= 1 and s_p <= max_gain <= 16 = 2^4 a contribution is at most 2^36 * 2^4 = 2^40 units, and 2^22 of
+ *                    them stay at or below 2^62, inside int64 like the 2^26 unit contributions of rule 1.  Rules 6-13 are unchanged;
+ *                    the iso value of rule 9 is the unweighted mean over the points, as without the flag.
+ *  17. vertex density: d_v = the trilinear W, evaluated as in rule 15, at the vertex position p of rule 11 (clamped into the grid as
+ *                    rule 5 clamps).
+ *  18. trim         : given V vertices, F faces, values[V] and a threshold, a vertex passes when values[v] >= threshold (NaN does not
+ *                    pass); a face is kept when its three vertices pass; a vertex is kept when it passes and lies in a kept face.
+ *                    Kept vertices and kept faces keep their order, the faces are renumbered.  Nothing kept: V = F = 0 and MVS_OK.
+ * mvs_poisson_reconstruct_density takes the arguments of mvs_poisson_reconstruct, the density parameters, a second info and
+ * vertex_density (vertex_capacity doubles, d_v of rule 17 per vertex; may be NULL).  With flags = 0 vertices, faces and info hold the
+ * bytes mvs_poisson_reconstruct gives, with or without vertex_density.  dinfo is written by every call that gets as far as the device
+ * and past rule 4.  Scratch, beyond that of mvs_poisson_reconstruct and from the same pool: 8 bytes per node of the density grid,
+ * (Gd + 1)^3 of them — at most an eighth of the solve grid's nodes at density_drop = 1 —, 16 bytes per row (rho_p and s_p) and 24 bytes per
+ * workgroup of the reduction over the points.
+ * MVS_E_INVALID_ARG, before a device is needed: what mvs_poisson_reconstruct refuses, dparams or dinfo NULL, max_gain not finite or
+ * outside [1, 16], density_drop outside [0, 8], a flag other than MVS_POISSON_WEIGHT_NORMALS, n > 2^22 with that flag. */
+#define MVS_POISSON_WEIGHT_NORMALS 1
+typedef struct mvs_poisson_density_params {
+    double  max_gain;           /* 4: the largest s_p of rule 16                                 */
+    int32_t flags;              /* 0; MVS_POISSON_WEIGHT_NORMALS                                 */
+    int32_t density_drop;       /* 1: levels the density grid lies below the solve grid          */
+} mvs_poisson_density_params;
+typedef struct mvs_poisson_density_info {
+    double  mean_density;       /* rho_mean of rule 15                                           */
+    double  min_point_density, max_point_density;   /* over the used points                      */
+    int32_t density_depth;      /* Dd of rule 14                                                 */
+    int32_t n_clamped;          /* used points with rho_mean / rho_p > max_gain                  */
+} mvs_poisson_density_info;
+/* the values in the comments above */
+void mvs_poisson_density_default_params(mvs_poisson_density_params* p);
+int mvs_poisson_reconstruct_density(int64_t n, const double* points, const double* normals, const mvs_poisson_params* p,
+                                    const mvs_poisson_density_params* dparams, mvs_poisson_info* info, mvs_poisson_density_info* dinfo,
+                                    double* vertices, double* vertex_density, int64_t vertex_capacity, int32_t* faces, int64_t face_capacity);
+/* the device form, as mvs_poisson_reconstruct_dev */
+int mvs_poisson_reconstruct_density_dev(int64_t n, const double* points_dev, const double* normals_dev, const mvs_poisson_params* p,
+                                        const mvs_poisson_density_params* dparams, mvs_poisson_info* info, mvs_poisson_density_info* dinfo,
+                                        double* vertices_dev, double* vertex_density_dev, int64_t vertex_capacity, int32_t* faces_dev,
+                                        int64_t face_capacity, void* hip_stream);
+/* Rule 18 on any triangle mesh: vertices[V][3], normals[V][3] (may be NULL, then normals_out is not written), faces[F][3], values[V].
+ * The outputs hold V resp. F rows and do not overlap the inputs; V_out / F_out receive the rows kept.  An ordered compaction without
+ * atomics: two runs give the same bytes.  MVS_E_INVALID_ARG, before a device is needed: a NULL argument other than normals /
+ * normals_out (normals given without normals_out included), V or F negative or above 2^31 - 1, a NaN threshold.  MVS_E_BAD_MESH: a
+ * face index outside [0, V). */
+int mvs_mesh_trim_by_value(int64_t V, const double* vertices, const double* normals, int64_t F, const int32_t* faces, const double* values,
+                           double threshold, double* vertices_out, double* normals_out, int32_t* faces_out, int64_t* V_out, int64_t* F_out);
+/* arrays in HBM, in the order of hip_stream (may be NULL); V_out / F_out stay host pointers; returns with the work complete */
+int mvs_mesh_trim_by_value_dev(int64_t V, const double* vertices_dev, const double* normals_dev, int64_t F, const int32_t* faces_dev,
+                               const double* values_dev, double threshold, double* vertices_out_dev, double* normals_out_dev,
+                               int32_t* faces_out_dev, int64_t* V_out, int64_t* F_out, void* hip_stream);
+
 /* Chain composition, Processor.cpp:819-823: (s0,R0,t0) <- (sk,Rk,tk) o (s0,R0,t0). */
 int mvs_srt_compose(double sk, const double* Rk, const double* tk,
                     double* s0, double* R0, double* t0);

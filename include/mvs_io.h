@@ -110,6 +110,15 @@ int mvs_processor_point_sample(int32_t n_seq, const char* const* seq_dirs, const
  * params may be NULL (defaults).  Nothing is written when the reconstruction fails.  V / F (may be NULL) receive the sizes written. */
 int mvs_processor_poisson(const char* psr_npts, const mvs_poisson_params* params, const char* model_obj, int64_t* V, int64_t* F);
 
+/* mvs_processor_poisson with the sampling density (rules 14-18 of include/mvs.h: this library's definition, NOT VERIFIED against GeoRec):
+ * mvs_poisson_reconstruct_density with dparams (NULL: the defaults, flags = 0: no weighting; set MVS_POISSON_WEIGHT_NORMALS to weight),
+ * then, when trim_ratio > 0, mvs_mesh_trim_by_value of the mesh by its vertex density at the threshold trim_ratio * mean_density
+ * (trim_ratio <= 0: no trim; NaN: MVS_E_INVALID_ARG).  The vertex normals are computed after the trim, from the trimmed mesh.  With
+ * dparams = NULL and trim_ratio = 0 the file holds the bytes mvs_processor_poisson writes.  V / F (may be NULL) receive the sizes
+ * written. */
+int mvs_processor_poisson_density(const char* psr_npts, const mvs_poisson_params* params, const mvs_poisson_density_params* dparams,
+                                  double trim_ratio, const char* model_obj, int64_t* V, int64_t* F);
+
 #ifdef __cplusplus
 }
 #endif

@@ -75,6 +75,16 @@ int mvs_test_point_sample_candidates(int32_t n_seq, const int32_t* cam_off, cons
 int mvs_test_poisson_field(int64_t n, const double* points, const double* normals, const mvs_poisson_params* p, mvs_poisson_info* info,
                            double* rhs, double* chi, int64_t node_capacity);
 
+/* mvs_poisson_reconstruct_density up to rule 6: info (depth, origin, h, n_used), dinfo, the int64 node sums of rule 14 ((2^Dd + 1)^3 in
+ * node order), rho_p of rule 15 and s_p of rule 16 per row (n each; an unused row holds 0) and the right-hand side of rule 6 ((2^depth +
+ * 1)^3 doubles), weighted when dparams sets MVS_POISSON_WEIGHT_NORMALS.  chi (may be NULL: the call stops after rule 6) receives the
+ * field of that right-hand side as mvs_test_poisson_field hands it out, and info the iso value, the cycles and the residual.  Node
+ * counts above density_node_capacity or node_capacity give MVS_E_INVALID_ARG after info's depth and dinfo's density_depth are written. */
+int mvs_test_poisson_density(int64_t n, const double* points, const double* normals, const mvs_poisson_params* p,
+                             const mvs_poisson_density_params* dparams, mvs_poisson_info* info, mvs_poisson_density_info* dinfo,
+                             int64_t* node_sums, int64_t density_node_capacity, double* rho, double* gain, double* rhs, double* chi,
+                             int64_t node_capacity);
+
 #ifdef __cplusplus
 }
 #endif

@@ -89,6 +89,17 @@ class CPoissonInfo(C.Structure):
                 ("n_vertices", C.c_int64), ("n_faces", C.c_int64), ("depth", C.c_int32), ("cycles", C.c_int32)]
 
 
+class CPoissonDensityParams(C.Structure):
+    """struct mvs_poisson_density_params."""
+    _fields_ = [("max_gain", C.c_double), ("flags", C.c_int32), ("density_drop", C.c_int32)]
+
+
+class CPoissonDensityInfo(C.Structure):
+    """struct mvs_poisson_density_info."""
+    _fields_ = [("mean_density", C.c_double), ("min_point_density", C.c_double), ("max_point_density", C.c_double),
+                ("density_depth", C.c_int32), ("n_clamped", C.c_int32)]
+
+
 class CSeqPairParams(C.Structure):
     """struct mvs_seq_pair_params."""
     _fields_ = [("filter", CMatchFilterParams), ("min_dsp", C.c_double), ("max_dsp", C.c_double), ("min_match_count", C.c_int32),
@@ -143,6 +154,11 @@ _SIGS = {
     "mvs_poisson_default_params": (None, [_VP]),
     "mvs_poisson_reconstruct": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _I64]),
     "mvs_poisson_reconstruct_dev": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _I64, _VP]),
+    "mvs_poisson_density_default_params": (None, [_VP]),
+    "mvs_poisson_reconstruct_density": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _I64]),
+    "mvs_poisson_reconstruct_density_dev": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _I64, _VP]),
+    "mvs_mesh_trim_by_value": (C.c_int, [_I64, _VP, _VP, _I64, _VP, _VP, _D, _VP, _VP, _VP, _VP, _VP]),
+    "mvs_mesh_trim_by_value_dev": (C.c_int, [_I64, _VP, _VP, _I64, _VP, _VP, _D, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mvs_render_depth": (C.c_int, [_VP, _I64, _VP, _I64, _VP, C.c_float, C.c_float, _VP]),
     "mvs_render_depth_dev": (C.c_int, [_VP, _I64, _VP, _I64, _VP, C.c_float, C.c_float, _VP, _VP]),
     "mvs_render_depth_views": (C.c_int, [_VP, _I64, _VP, _I64, _I32, _VP, _VP, _VP, _VP, _VP, C.c_float, C.c_float, _VP]),
@@ -236,6 +252,7 @@ _SIGS = {
     "mvs_processor_render": (C.c_int, [C.c_char_p, C.c_char_p, _I32, _VP, _VP, C.c_char_p, _VP, C.c_float, C.c_float, _VP]),
     "mvs_processor_point_sample": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mvs_processor_poisson": (C.c_int, [C.c_char_p, _VP, C.c_char_p, _VP, _VP]),
+    "mvs_processor_poisson_density": (C.c_int, [C.c_char_p, _VP, _VP, _D, C.c_char_p, _VP, _VP]),
     # include/mvs_test.h (test hooks: per handle, not part of the drop-in ABI)
     "mvs_test_preload_wait": (C.c_int, []),
     "mvs_test_ctl": (C.c_int, [_VP, _VP, _I32]),
@@ -250,6 +267,7 @@ _SIGS = {
     "mvs_test_sift_candidates": (C.c_int, [_I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _I64]),
     "mvs_test_point_sample_candidates": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP, _I64]),
     "mvs_test_poisson_field": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _I64]),
+    "mvs_test_poisson_density": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _I64]),
 }
 EXPORTS = tuple(_SIGS)
 

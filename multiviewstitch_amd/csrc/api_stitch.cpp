@@ -355,11 +355,9 @@ int mvs_processor_point_sample(int32_t n_seq, const char* const* seq_dirs, const
     return MVS_OK;
 }
 
-int mvs_processor_poisson(const char* psr_npts, const mvs_poisson_params* params, const char* model_obj, int64_t* V_out, int64_t* F_out) {
-    MVS_TRACE();
-    if (!psr_npts || !model_obj) return bad(__func__, "psr_npts / model_obj is NULL");
-    mvs_poisson_params prm;
-    if (params) prm = *params; else mvs_poisson_default_params(&prm);
+// PSR.npts -> Model.obj; dprm != NULL: through rules 14-17, and trimmed by rule 18 when trim_ratio > 0
+static int poisson_files(const char* fn, const char* psr_npts, const mvs_poisson_params& prm, const mvs_poisson_density_params* dprm, double trim_ratio,
+                         const char* model_obj, int64_t* V_out, int64_t* F_out) {
     int rc = need_device();
     if (rc) return rc;
     int64_t n = 0;
@@ -368,20 +366,50 @@ int mvs_processor_poisson(const char* psr_npts, const mvs_poisson_params* params
     int64_t m = n;
     if ((rc = mvs_npts_read(psr_npts, &m, hp.data(), hn.data()))) return rc;
     if (m != n) { mvs_set_error("%s changed while it was read", psr_npts); return MVS_E_IO; }
-    Scratch dp, dn, dv, df, dvn;
+    Scratch dp, dn, dv, df, dvn, dd, tv, tf;
     mvs_poisson_info info;
+    mvs_poisson_density_info dinfo;
     if ((rc = up(dp, hp.data(), (size_t)n * 3)) || (rc = up(dn, hn.data(), (size_t)n * 3))) return rc;
-    if ((rc = poisson_blocks(__func__, n, dp.as<double>(), dn.as<double>(), &prm, &info, &dv, &df))) return rc;
-    const int64_t V = info.n_vertices, F = info.n_faces;
+    if (dprm) rc = poisson_density_blocks(fn, n, dp.as<double>(), dn.as<double>(), &prm, dprm, &info, &dinfo, &dv, &dd, &df);
+    else rc = poisson_blocks(fn, n, dp.as<double>(), dn.as<double>(), &prm, &info, &dv, &df);
+    if (rc) return rc;
+    int64_t V = info.n_vertices, F = info.n_faces;
+    const Scratch *mv = &dv, *mf = &df;
+    if (dprm && trim_ratio > 0.0) {
+        if ((rc = tv.alloc((size_t)V * 24)) || (rc = tf.alloc((size_t)F * 12)) ||
+            (rc = mesh_trim_dev(V, dv.as<double>(), nullptr, F, df.as<int32_t>(), dd.as<double>(), trim_ratio * dinfo.mean_density, tv.as<double>(), nullptr,
+                                tf.as<int32_t>(), &V, &F, nullptr))) return rc;
+        mv = &tv; mf = &tf;
+    }
     if ((rc = dvn.alloc((size_t)V * 24))) return rc;
-    if (V > 0 && (rc = mesh_vertex_normals_dev(dv.as<double>(), V, df.as<int32_t>(), F, dvn.as<double>(), nullptr))) return rc;
+    if (V > 0 && (rc = mesh_vertex_normals_dev(mv->as<double>(), V, mf->as<int32_t>(), F, dvn.as<double>(), nullptr))) return rc;
     std::vector<double> ov((size_t)V * 3 + 1), on((size_t)V * 3 + 1);
     std::vector<int32_t> of((size_t)F * 3 + 1);
-    if ((rc = down(ov.data(), dv, (size_t)V * 3)) || (rc = down(on.data(), dvn, (size_t)V * 3)) || (rc = down(of.data(), df, (size_t)F * 3))) return rc;
+    if ((rc = down(ov.data(), *mv, (size_t)V * 3)) || (rc = down(on.data(), dvn, (size_t)V * 3)) || (rc = down(of.data(), *mf, (size_t)F * 3))) return rc;
     if ((rc = mvs_obj_write(model_obj, V, ov.data(), on.data(), F, of.data()))) return rc;
     if (V_out) *V_out = V;
     if (F_out) *F_out = F;
     return MVS_OK;
+}
+
+int mvs_processor_poisson(const char* psr_npts, const mvs_poisson_params* params, const char* model_obj, int64_t* V_out, int64_t* F_out) {
+    MVS_TRACE();
+    if (!psr_npts || !model_obj) return bad(__func__, "psr_npts / model_obj is NULL");
+    mvs_poisson_params prm;
+    if (params) prm = *params; else mvs_poisson_default_params(&prm);
+    return poisson_files(__func__, psr_npts, prm, nullptr, 0.0, model_obj, V_out, F_out);
+}
+
+int mvs_processor_poisson_density(const char* psr_npts, const mvs_poisson_params* params, const mvs_poisson_density_params* dparams, double trim_ratio,
+                                  const char* model_obj, int64_t* V_out, int64_t* F_out) {
+    MVS_TRACE();
+    if (!psr_npts || !model_obj) return bad(__func__, "psr_npts / model_obj is NULL");
+    if (trim_ratio != trim_ratio) return bad(__func__, "trim_ratio is NaN");
+    mvs_poisson_params prm;
+    mvs_poisson_density_params dprm;
+    if (params) prm = *params; else mvs_poisson_default_params(&prm);
+    if (dparams) dprm = *dparams; else mvs_poisson_density_default_params(&dprm);
+    return poisson_files(__func__, psr_npts, prm, &dprm, trim_ratio, model_obj, V_out, F_out);
 }
 
 }  // extern "C"

@@ -20,7 +20,14 @@
 //                      rules 11-12: two ordered compactions (wg_rank per workgroup of 256 items; k_pn_scan_rows / _totals / _add scan the
 //                      millions of counts in two levels).  The edge flags stay behind as a bitmap, 64 flags per word: a face finds the
 //                      number of a vertex as base[workgroup] + popcounts, no edge map is stored.
-// Nothing but the integer atomics of the splat and the bitmap is unordered: two runs give the same bytes.
+// mvs_poisson_reconstruct_density adds the sampling density (rules 14-17), mvs_mesh_trim_by_value the trim (rule 18):
+//   k_pn_density_splat rule 14: a thread per point, 8 int64 atomic adds into the node sums of the coarser density grid
+//   k_pn_point_density rule 15: rho_p per row; min, max and the int64 sum of the quantised densities per workgroup (order-free)
+//   k_pn_gain          rule 16: s_p per row and the rows cut at max_gain; k_pn_splat<true> is the splat of the scaled normals
+//   k_pn_vertex_density rule 17, over the vertex list the scatter wrote
+//   k_tr_face_mark / k_tr_vertex_count / CompactTail / k_tr_vertex_scatter / k_tr_face_scatter
+//                      rule 18: flags and plain byte marks, compact.hip's scan, two ordered scatters
+// Nothing but the integer atomics of the splats and the bitmap is unordered: two runs give the same bytes.
 #include "engine.h"
 #include "trace.h"
 #include "frontend_dev.h"
@@ -110,18 +117,164 @@ __global__ __launch_bounds__(PN_TPB) void k_pn_popcount(PnOcc q, const unsigned*
 }
 
 // ------------------------------------------------------------------ rules 5-6 ----
+// WEIGHTED: rule 16, every normal scaled by the gain s_p of its point
+template <bool WEIGHTED>
 __global__ __launch_bounds__(PN_TPB) void k_pn_splat(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm, PnGrid g,
-                                                     unsigned long long* __restrict__ sums) {
+                                                     unsigned long long* __restrict__ sums, const double* __restrict__ gain) {
     const int64_t i = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
     if (i >= n || !pn_used(pts + 3 * i, nrm + 3 * i)) return;
     const int64_t nn = (int64_t)(g.G + 1) * (g.G + 1) * (g.G + 1);
     int i0[3];
-    double w[8];
+    double w[8], na[3];
     pn_corners_weights(pts + 3 * i, g, i0, w);
+    for (int a = 0; a < 3; ++a) na[a] = WEIGHTED ? nrm[3 * i + a] * gain[i] : nrm[3 * i + a];
     for (int c = 0; c < 8; ++c) {
         const int64_t node = pn_node(g.G, i0[0] + (c & 1), i0[1] + (c >> 1 & 1), i0[2] + (c >> 2 & 1));
-        for (int a = 0; a < 3; ++a) atomicAdd(sums + a * nn + node, (unsigned long long)pn_quant(w[c] * nrm[3 * i + a]));
+        for (int a = 0; a < 3; ++a) atomicAdd(sums + a * nn + node, (unsigned long long)pn_quant(w[c] * na[a]));
     }
+}
+
+// ------------------------------------------------------------------ rules 14-17 ----
+// rule 14: a thread per point, 8 int64 atomic adds into the node sums of the density grid
+__global__ __launch_bounds__(PN_TPB) void k_pn_density_splat(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm, PnGrid gd,
+                                                             unsigned long long* __restrict__ dsum) {
+    const int64_t i = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
+    if (i >= n || !pn_used(pts + 3 * i, nrm + 3 * i)) return;
+    int i0[3];
+    double w[8];
+    pn_corners_weights(pts + 3 * i, gd, i0, w);
+    for (int c = 0; c < 8; ++c)
+        atomicAdd(dsum + pn_node(gd.G, i0[0] + (c & 1), i0[1] + (c >> 1 & 1), i0[2] + (c >> 2 & 1)), (unsigned long long)pn_quant(w[c]));
+}
+
+// rule 15: rho_p of every row (0 for a row that is not used) and, per workgroup, the min, the max and the int64 sum of the quantised
+// densities of its used rows — all three order-free; the host finishes.  part_d[2 b] = min, [2 b + 1] = max, part_q[b] = the sum.
+__global__ __launch_bounds__(PN_TPB) void k_pn_point_density(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm, PnGrid gd,
+                                                             const long long* __restrict__ dsum, double* __restrict__ rho,
+                                                             double* __restrict__ part_d, long long* __restrict__ part_q) {
+    __shared__ double s_lo[PN_WAVES], s_hi[PN_WAVES];
+    __shared__ long long s_q[PN_WAVES];
+    double lo = HUGE_VAL, hi = -HUGE_VAL;
+    long long q = 0;
+    for (int64_t i = (int64_t)blockIdx.x * PN_TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * PN_TPB) {
+        double r = 0.0;
+        if (pn_used(pts + 3 * i, nrm + 3 * i)) {
+            r = pn_density_at(pts + 3 * i, gd, dsum);
+            lo = fmin(lo, r);
+            hi = fmax(hi, r);
+            q += pn_rho_quant(r);
+        }
+        rho[i] = r;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        lo = fmin(lo, __shfl_down(lo, o, 64));
+        hi = fmax(hi, __shfl_down(hi, o, 64));
+        q += __shfl_down(q, o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) { s_lo[threadIdx.x >> 6] = lo; s_hi[threadIdx.x >> 6] = hi; s_q[threadIdx.x >> 6] = q; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < PN_WAVES; ++k) { lo = fmin(lo, s_lo[k]); hi = fmax(hi, s_hi[k]); q += s_q[k]; }
+        part_d[2 * blockIdx.x] = lo;
+        part_d[2 * blockIdx.x + 1] = hi;
+        part_q[blockIdx.x] = q;
+    }
+}
+
+// rule 16: s_p of every row (0 for a row that is not used) and, per workgroup, the used rows whose gain was cut at max_gain
+__global__ __launch_bounds__(PN_TPB) void k_pn_gain(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm,
+                                                    const double* __restrict__ rho, double rho_mean, double max_gain, double* __restrict__ gain,
+                                                    int32_t* __restrict__ part_c) {
+    __shared__ int s_c[PN_WAVES];
+    int cut = 0;
+    for (int64_t i = (int64_t)blockIdx.x * PN_TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * PN_TPB) {
+        double s = 0.0;
+        if (pn_used(pts + 3 * i, nrm + 3 * i)) {
+            s = pn_gain(rho_mean, rho[i], max_gain);
+            cut += rho_mean / rho[i] > max_gain ? 1 : 0;
+        }
+        gain[i] = s;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cut += __shfl_down(cut, o, 64);
+    if ((threadIdx.x & 63) == 0) s_c[threadIdx.x >> 6] = cut;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < PN_WAVES; ++k) cut += s_c[k];
+        part_c[blockIdx.x] = cut;
+    }
+}
+
+// rule 17: over the vertex list the scatter wrote
+__global__ __launch_bounds__(PN_TPB) void k_pn_vertex_density(int64_t nv, const double* __restrict__ vertices, PnGrid gd,
+                                                              const long long* __restrict__ dsum, double* __restrict__ out) {
+    const int64_t v = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
+    if (v >= nv) return;
+    const double* p = vertices + 3 * v;
+    out[v] = isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]) ? pn_density_at(p, gd, dsum) : NAN;      // a cell needs a finite position
+}
+
+// ------------------------------------------------------------------ rule 18 ----
+// The trim: k_tr_face_mark flags the kept faces, counts them per workgroup and marks their vertices as referenced with plain byte stores
+// of 1 (ref was cleared; every store writes the same value); k_tr_vertex_count counts the referenced vertices per workgroup; compact.hip's
+// tail scans the two count arrays; the two scatters write the survivors in their order, the faces through the new numbers of their vertices.
+__device__ inline bool tr_face_kept(int64_t V, const int32_t* __restrict__ faces, const double* __restrict__ values, double thr, int64_t f, int64_t F,
+                                    uint8_t* bad) {
+    if (f >= F) return false;
+    bool keep = true;
+    for (int q = 0; q < 3; ++q) {
+        const int32_t v = faces[3 * f + q];
+        if (v < 0 || v >= V) { *bad = 1; return false; }
+        keep = keep && pn_trim_pass(values[v], thr);
+    }
+    return keep;
+}
+
+__global__ __launch_bounds__(COMPACT_TPB) void k_tr_face_mark(int64_t V, int64_t F, const int32_t* __restrict__ faces, const double* __restrict__ values,
+                                                              double thr, uint8_t* __restrict__ keepf, uint8_t* __restrict__ ref, uint8_t* __restrict__ bad,
+                                                              int32_t* __restrict__ cnt) {
+    __shared__ int s_wsum[COMPACT_TPB / 64];
+    const int64_t f = (int64_t)blockIdx.x * COMPACT_TPB + threadIdx.x;
+    const bool keep = tr_face_kept(V, faces, values, thr, f, F, bad);
+    if (f < F) keepf[f] = keep ? 1 : 0;
+    if (keep)
+        for (int q = 0; q < 3; ++q) ref[faces[3 * f + q]] = 1;
+    const WgRank k = wg_rank<COMPACT_TPB / 64>(keep, s_wsum);
+    if (threadIdx.x == 0) cnt[blockIdx.x] = k.total;
+}
+
+__global__ __launch_bounds__(COMPACT_TPB) void k_tr_vertex_count(int64_t V, const uint8_t* __restrict__ ref, int32_t* __restrict__ cnt) {
+    __shared__ int s_wsum[COMPACT_TPB / 64];
+    const int64_t v = (int64_t)blockIdx.x * COMPACT_TPB + threadIdx.x;
+    const WgRank k = wg_rank<COMPACT_TPB / 64>(v < V && ref[v], s_wsum);
+    if (threadIdx.x == 0) cnt[blockIdx.x] = k.total;
+}
+
+__global__ __launch_bounds__(COMPACT_TPB) void k_tr_vertex_scatter(int64_t V, const uint8_t* __restrict__ ref, const int32_t* __restrict__ base,
+                                                                   const double* __restrict__ vertices, const double* __restrict__ normals,
+                                                                   double* __restrict__ vertices_out, double* __restrict__ normals_out,
+                                                                   int32_t* __restrict__ renum) {
+    __shared__ int s_wsum[COMPACT_TPB / 64];
+    const int64_t v = (int64_t)blockIdx.x * COMPACT_TPB + threadIdx.x;
+    const bool keep = v < V && ref[v];
+    const int64_t pos = (int64_t)base[blockIdx.x] + wg_rank<COMPACT_TPB / 64>(keep, s_wsum).rank;
+    if (!keep) return;
+    renum[v] = (int32_t)pos;
+    for (int a = 0; a < 3; ++a) vertices_out[3 * pos + a] = vertices[3 * v + a];
+    if (normals)
+        for (int a = 0; a < 3; ++a) normals_out[3 * pos + a] = normals[3 * v + a];
+}
+
+__global__ __launch_bounds__(COMPACT_TPB) void k_tr_face_scatter(int64_t F, const uint8_t* __restrict__ keepf, const int32_t* __restrict__ base,
+                                                                 const int32_t* __restrict__ faces, const int32_t* __restrict__ renum,
+                                                                 int32_t* __restrict__ faces_out) {
+    __shared__ int s_wsum[COMPACT_TPB / 64];
+    const int64_t f = (int64_t)blockIdx.x * COMPACT_TPB + threadIdx.x;
+    const bool keep = f < F && keepf[f];
+    const int64_t pos = (int64_t)base[blockIdx.x] + wg_rank<COMPACT_TPB / 64>(keep, s_wsum).rank;
+    if (!keep) return;
+    for (int q = 0; q < 3; ++q) faces_out[3 * pos + q] = renum[faces[3 * f + q]];       // a kept face: its vertices are referenced, renum is set
 }
 
 __global__ __launch_bounds__(PN_TPB) void k_pn_rhs(PnGrid g, const long long* __restrict__ sums, double* __restrict__ b) {
@@ -461,7 +614,14 @@ struct PnRun {
     hipStream_t s;
     PnGrid g{};
     int64_t nn = 0;                       // nodes of the finest level
+    double side = 0.0;                    // rule 2
     Scratch part, sums, rhs, coarse, red, mask, words;
+    // rules 14-17 (mvs_poisson_reconstruct_density): absent for the plain call
+    const mvs_poisson_density_params* dp = nullptr;
+    mvs_poisson_density_info* dinfo = nullptr;
+    PnGrid gd{};
+    int64_t nnd = 0;                      // nodes of the density grid
+    Scratch dsum, rho, gain, dpart;
     struct Scan {                         // counts, their scan and its two levels, for nb workgroups
         Scratch cnt, base, local, tot, rbase;
         int alloc(size_t nb, hipStream_t s) {
@@ -510,7 +670,7 @@ struct PnRun {
         double ext = 0.0;
         for (int a = 0; a < 3; ++a) ext = std::fmax(ext, hi[a] - lo[a]);
         if (info.n_used < 2 || !(ext > 0.0)) { mvs_set_error("%s: fewer than 2 used points, or a bounding box of zero extent", fn); return MVS_E_DEGENERATE; }
-        const double side = p.scale * ext;                                                       // rule 2
+        side = p.scale * ext;                                                                    // rule 2
         for (int a = 0; a < 3; ++a) g.o[a] = 0.5 * (lo[a] + hi[a]) - 0.5 * side;
         const int dmax = p.depth_max < PN_MAX_D ? p.depth_max : PN_MAX_D;
         int D = p.depth_min;
@@ -597,16 +757,27 @@ struct PnRun {
         return MVS_OK;
     }
 
+    // rules 5-6 (with rule 16 when the call weights): the levels, then b
+    int right_side() {
+        int rc;
+        if ((rc = levels())) return rc;
+        const unsigned nblk = (unsigned)((nn + PN_TPB - 1) / PN_TPB);
+        HIPCHK(hipMemsetAsync(sums.p, 0, 24 * (size_t)nn, s));
+        const dim3 pgrid((unsigned)((n + PN_TPB - 1) / PN_TPB));
+        if (dp && (dp->flags & MVS_POISSON_WEIGHT_NORMALS))
+            k_pn_splat<true><<<pgrid, dim3(PN_TPB), 0, s>>>(n, pts, nrm, g, sums.as<unsigned long long>(), gain.as<double>());
+        else
+            k_pn_splat<false><<<pgrid, dim3(PN_TPB), 0, s>>>(n, pts, nrm, g, sums.as<unsigned long long>(), nullptr);
+        k_pn_rhs<<<dim3(nblk), dim3(PN_TPB), 0, s>>>(g, sums.as<long long>(), rhs.as<double>());
+        HIPCHK(hipGetLastError());
+        return MVS_OK;
+    }
+
     // rules 5-8
     int field(const char* fn) {
         int rc;
-        if ((rc = levels())) return rc;
+        if ((rc = right_side())) return rc;
         const int D = info.depth;
-        const unsigned nblk = (unsigned)((nn + PN_TPB - 1) / PN_TPB);
-        HIPCHK(hipMemsetAsync(sums.p, 0, 24 * (size_t)nn, s));
-        k_pn_splat<<<dim3((unsigned)((n + PN_TPB - 1) / PN_TPB)), dim3(PN_TPB), 0, s>>>(n, pts, nrm, g, sums.as<unsigned long long>());
-        k_pn_rhs<<<dim3(nblk), dim3(PN_TPB), 0, s>>>(g, sums.as<long long>(), rhs.as<double>());
-        HIPCHK(hipGetLastError());
         HIPCHK(hipMemsetAsync(sums.p, 0, 16 * (size_t)nn, s));                // the sums are spent: x = 0 and the smoother's second buffer
         const dim3 gr = pn_column_grid(g.G);
         if ((rc = red.alloc(sizeof(double) * (1 + (size_t)gr.x * gr.y * gr.z), s))) return rc;
@@ -621,6 +792,51 @@ struct PnRun {
         }
         mvs_set_error("%s: relative residual %.3e after %d cycles, above solve_tol %.3e", fn, info.rel_residual, info.cycles, p.solve_tol);
         return MVS_E_SOLVER;
+    }
+
+    // rules 14-16: the density grid, rho_p, rho_mean and s_p
+    int density() {
+        int rc, Dd = 0;
+        gd = pn_density_grid(g, side, info.depth, dp->density_drop, &Dd);
+        nnd = (int64_t)(gd.G + 1) * (gd.G + 1) * (gd.G + 1);
+        std::memset(dinfo, 0, sizeof *dinfo);
+        dinfo->density_depth = Dd;
+        const int nb = (int)std::min<int64_t>(PN_RED_NB, (n + PN_TPB - 1) / PN_TPB);
+        if ((rc = dsum.alloc(8 * (size_t)nnd, s)) || (rc = rho.alloc(8 * (size_t)n, s)) || (rc = gain.alloc(8 * (size_t)n, s)) ||
+            (rc = dpart.alloc(24 * (size_t)PN_RED_NB, s))) return rc;
+        double* part_d = dpart.as<double>();
+        long long* part_q = dpart.as<long long>() + 2 * PN_RED_NB;
+        HIPCHK(hipMemsetAsync(dsum.p, 0, 8 * (size_t)nnd, s));
+        k_pn_density_splat<<<dim3((unsigned)((n + PN_TPB - 1) / PN_TPB)), dim3(PN_TPB), 0, s>>>(n, pts, nrm, gd, dsum.as<unsigned long long>());
+        k_pn_point_density<<<dim3((unsigned)nb), dim3(PN_TPB), 0, s>>>(n, pts, nrm, gd, dsum.as<long long>(), rho.as<double>(), part_d, part_q);
+        HIPCHK(hipGetLastError());
+        std::vector<double> hd((size_t)2 * nb);
+        std::vector<long long> hq((size_t)nb);
+        HIPCHK(hipMemcpyAsync(hd.data(), part_d, 16 * (size_t)nb, hipMemcpyDeviceToHost, s));
+        if ((rc = fetch(hq.data(), part_q, 8 * (size_t)nb))) return rc;
+        double lo = HUGE_VAL, hi = -HUGE_VAL;
+        long long q = 0;
+        for (int b = 0; b < nb; ++b) { lo = std::fmin(lo, hd[2 * b]); hi = std::fmax(hi, hd[2 * b + 1]); q += hq[b]; }
+        dinfo->mean_density = pn_rho_mean(q, info.n_used);
+        dinfo->min_point_density = lo;
+        dinfo->max_point_density = hi;
+        int32_t* part_c = dpart.as<int32_t>();                                // the partials above are spent
+        k_pn_gain<<<dim3((unsigned)nb), dim3(PN_TPB), 0, s>>>(n, pts, nrm, rho.as<double>(), dinfo->mean_density, dp->max_gain, gain.as<double>(), part_c);
+        HIPCHK(hipGetLastError());
+        std::vector<int32_t> hc((size_t)nb);
+        if ((rc = fetch(hc.data(), part_c, 4 * (size_t)nb))) return rc;
+        for (int b = 0; b < nb; ++b) dinfo->n_clamped += hc[b];
+        return MVS_OK;
+    }
+
+    // rule 17, after scatter
+    int vertex_density(const double* vertices, double* out) {
+        if (!out || info.n_vertices == 0) return MVS_OK;
+        k_pn_vertex_density<<<dim3((unsigned)((info.n_vertices + PN_TPB - 1) / PN_TPB)), dim3(PN_TPB), 0, s>>>(info.n_vertices, vertices, gd,
+                                                                                                              dsum.as<long long>(), out);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(s));
+        return MVS_OK;
     }
 
     // rule 9
@@ -675,14 +891,87 @@ struct PnRun {
 
     int counts(const char* fn) {
         int rc;
-        if ((rc = grid(fn)) || (rc = field(fn)) || (rc = iso_value())) return rc;
+        if ((rc = grid(fn)) || (dp && (rc = density())) || (rc = field(fn)) || (rc = iso_value())) return rc;
         return count();
     }
 };
 
 int too_small(const char* fn) { return bad(fn, "a capacity is below the count (info holds n_vertices and n_faces)"); }
 
+int check_pn_density(const char* fn, int64_t n, const mvs_poisson_density_params* dp, const void* dinfo) {
+    if (!dp || !dinfo) return bad(fn, "dparams or dinfo is NULL");
+    if (!std::isfinite(dp->max_gain) || dp->max_gain < 1.0 || dp->max_gain > 16.0) return bad(fn, "need max_gain in [1, 16]");
+    if (dp->density_drop < 0 || dp->density_drop > 8) return bad(fn, "need density_drop in [0, 8]");
+    if (dp->flags & ~MVS_POISSON_WEIGHT_NORMALS) return bad(fn, "flags holds a bit other than MVS_POISSON_WEIGHT_NORMALS");
+    if ((dp->flags & MVS_POISSON_WEIGHT_NORMALS) && n > (1ll << 22)) return bad(fn, "more than 2^22 points with MVS_POISSON_WEIGHT_NORMALS");
+    return MVS_OK;
+}
+
+int check_trim(const char* fn, int64_t V, const void* vertices, const void* normals, int64_t F, const void* faces, const void* values, double thr,
+               const void* vertices_out, const void* normals_out, const void* faces_out, const void* V_out, const void* F_out) {
+    if (!vertices || !faces || !values || !vertices_out || !faces_out || !V_out || !F_out) return bad(fn, "an argument other than normals / normals_out is NULL");
+    if (normals && !normals_out) return bad(fn, "normals without normals_out");
+    if (V < 0 || F < 0) return bad(fn, "V or F is negative");
+    if (V > 0x7fffffffLL || F > 0x7fffffffLL) return bad(fn, "V or F exceeds 2^31 - 1");
+    if (std::isnan(thr)) return bad(fn, "threshold is NaN");
+    return MVS_OK;
+}
+
 }  // namespace
+
+// rule 18 on device arrays, arguments validated by the caller.  Synchronises s.
+int mesh_trim_dev(int64_t V, const double* vertices, const double* normals, int64_t F, const int32_t* faces, const double* values, double thr,
+                  double* vertices_out, double* normals_out, int32_t* faces_out, int64_t* V_out, int64_t* F_out, hipStream_t s) {
+    *V_out = *F_out = 0;
+    if (V == 0 || F == 0) return MVS_OK;
+    int rc;
+    const int64_t nbv = (V + COMPACT_TPB - 1) / COMPACT_TPB, nbf = (F + COMPACT_TPB - 1) / COMPACT_TPB;
+    Scratch keepf, ref, renum;                                               // ref: V bytes and the bad-mesh byte behind them
+    CompactTail tv, tf;
+    if ((rc = keepf.alloc((size_t)F, s)) || (rc = ref.alloc((size_t)V + 1, s)) || (rc = renum.alloc(4 * (size_t)V, s)) ||
+        (rc = tv.alloc((size_t)nbv, 1, s)) || (rc = tf.alloc((size_t)nbf, 1, s))) return rc;
+    HIPCHK(hipMemsetAsync(ref.p, 0, (size_t)V + 1, s));
+    k_tr_face_mark<<<dim3((unsigned)nbf), dim3(COMPACT_TPB), 0, s>>>(V, F, faces, values, thr, keepf.as<uint8_t>(), ref.as<uint8_t>(), ref.as<uint8_t>() + V,
+                                                                    tf.cnt.as<int32_t>());
+    k_tr_vertex_count<<<dim3((unsigned)nbv), dim3(COMPACT_TPB), 0, s>>>(V, ref.as<uint8_t>(), tv.cnt.as<int32_t>());
+    tf.strided((int)nbf, nullptr, 1, (int)nbf, s);                            // off = {0, all survivors}
+    tv.strided((int)nbv, nullptr, 1, (int)nbv, s);
+    HIPCHK(hipGetLastError());
+    uint8_t badmesh = 0;
+    int64_t offv[2] = {0, 0}, offf[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(&badmesh, ref.as<uint8_t>() + V, 1, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(offv, tv.off.p, 16, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(offf, tf.off.p, 16, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (badmesh) { mvs_set_error("mesh trim: a face index is outside [0, V)"); return MVS_E_BAD_MESH; }
+    if (offf[1] > 0) {
+        k_tr_vertex_scatter<<<dim3((unsigned)nbv), dim3(COMPACT_TPB), 0, s>>>(V, ref.as<uint8_t>(), tv.base.as<int32_t>(), vertices, normals, vertices_out,
+                                                                             normals_out, renum.as<int32_t>());
+        k_tr_face_scatter<<<dim3((unsigned)nbf), dim3(COMPACT_TPB), 0, s>>>(F, keepf.as<uint8_t>(), tf.base.as<int32_t>(), faces, renum.as<int32_t>(),
+                                                                           faces_out);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    *V_out = offv[1];
+    *F_out = offf[1];
+    return MVS_OK;
+}
+
+// mvs_poisson_reconstruct_density_dev with outputs that size themselves, for mvs_processor_poisson_density; as poisson_blocks
+int poisson_density_blocks(const char* fn, int64_t n, const double* points_dev, const double* normals_dev, const mvs_poisson_params* p,
+                           const mvs_poisson_density_params* dp, mvs_poisson_info* info, mvs_poisson_density_info* dinfo, Scratch* vertices,
+                           Scratch* density, Scratch* faces) {
+    int rc = check_pn(fn, n, points_dev, normals_dev, p, info, nullptr, 0, nullptr, 0);
+    if (rc || (rc = check_pn_density(fn, n, dp, dinfo))) return rc;
+    PnRun run(*p, *info, n, points_dev, normals_dev, nullptr);
+    run.dp = dp;
+    run.dinfo = dinfo;
+    if ((rc = run.counts(fn))) return rc;
+    if ((rc = vertices->alloc(24 * (size_t)info->n_vertices)) || (rc = density->alloc(8 * (size_t)info->n_vertices)) ||
+        (rc = faces->alloc(12 * (size_t)info->n_faces))) return rc;
+    if ((rc = run.scatter(vertices->as<double>(), faces->as<int32_t>()))) return rc;
+    return run.vertex_density(vertices->as<double>(), density->as<double>());
+}
 
 // the device form for a caller inside the library that cannot know the counts in advance (mvs_processor_poisson): the blocks are sized
 // once the counts are known
@@ -749,6 +1038,116 @@ int mvs_test_poisson_field(int64_t n, const double* points, const double* normal
     if (!frc && (rc = run.iso_value())) return rc;
     HIPCHK(hipMemcpy(rhs, run.rhs.p, 8 * (size_t)run.nn, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(chi, run.L.x[info->depth], 8 * (size_t)run.nn, hipMemcpyDeviceToHost));
+    return frc;
+}
+
+// ------------------------------------------------------------------ rules 14-18 ----
+void mvs_poisson_density_default_params(mvs_poisson_density_params* p) {
+    if (!p) return;
+    p->max_gain = 4.0; p->flags = 0; p->density_drop = 1;
+}
+
+int mvs_poisson_reconstruct_density_dev(int64_t n, const double* points_dev, const double* normals_dev, const mvs_poisson_params* p,
+                                        const mvs_poisson_density_params* dparams, mvs_poisson_info* info, mvs_poisson_density_info* dinfo,
+                                        double* vertices_dev, double* vertex_density_dev, int64_t vertex_capacity, int32_t* faces_dev,
+                                        int64_t face_capacity, void* hip_stream) {
+    MVS_TRACE();
+    int rc = check_pn(__func__, n, points_dev, normals_dev, p, info, vertices_dev, vertex_capacity, faces_dev, face_capacity);
+    if (rc || (rc = check_pn_density(__func__, n, dparams, dinfo))) return rc;
+    if ((rc = need_device())) return rc;
+    PnRun run(*p, *info, n, points_dev, normals_dev, (hipStream_t)hip_stream);
+    run.dp = dparams;
+    run.dinfo = dinfo;
+    std::memset(dinfo, 0, sizeof *dinfo);
+    if ((rc = run.counts(__func__))) return rc;
+    if (info->n_vertices > vertex_capacity || info->n_faces > face_capacity) return too_small(__func__);
+    if ((rc = run.scatter(vertices_dev, faces_dev))) return rc;
+    return run.vertex_density(vertices_dev, vertex_density_dev);
+}
+
+int mvs_poisson_reconstruct_density(int64_t n, const double* points, const double* normals, const mvs_poisson_params* p,
+                                    const mvs_poisson_density_params* dparams, mvs_poisson_info* info, mvs_poisson_density_info* dinfo,
+                                    double* vertices, double* vertex_density, int64_t vertex_capacity, int32_t* faces, int64_t face_capacity) {
+    MVS_TRACE();
+    int rc = check_pn(__func__, n, points, normals, p, info, vertices, vertex_capacity, faces, face_capacity);
+    if (rc || (rc = check_pn_density(__func__, n, dparams, dinfo))) return rc;
+    if ((rc = need_device())) return rc;
+    Scratch dp, dn, dv, dd, df;
+    if ((rc = up(dp, points, 3 * (size_t)n)) || (rc = up(dn, normals, 3 * (size_t)n))) return rc;
+    PnRun run(*p, *info, n, dp.as<double>(), dn.as<double>(), nullptr);
+    run.dp = dparams;
+    run.dinfo = dinfo;
+    std::memset(dinfo, 0, sizeof *dinfo);
+    if ((rc = run.counts(__func__))) return rc;
+    if (info->n_vertices > vertex_capacity || info->n_faces > face_capacity) return too_small(__func__);
+    const size_t V = (size_t)info->n_vertices, F = (size_t)info->n_faces;
+    if ((rc = dv.alloc(24 * V)) || (rc = df.alloc(12 * F)) || (rc = run.scatter(dv.as<double>(), df.as<int32_t>()))) return rc;
+    if (vertex_density) {
+        if ((rc = dd.alloc(8 * V)) || (rc = run.vertex_density(dv.as<double>(), dd.as<double>())) || (rc = down(vertex_density, dd, V))) return rc;
+    }
+    if ((rc = down(vertices, dv, 3 * V))) return rc;
+    return down(faces, df, 3 * F);
+}
+
+int mvs_mesh_trim_by_value_dev(int64_t V, const double* vertices_dev, const double* normals_dev, int64_t F, const int32_t* faces_dev,
+                               const double* values_dev, double threshold, double* vertices_out_dev, double* normals_out_dev,
+                               int32_t* faces_out_dev, int64_t* V_out, int64_t* F_out, void* hip_stream) {
+    MVS_TRACE();
+    int rc = check_trim(__func__, V, vertices_dev, normals_dev, F, faces_dev, values_dev, threshold, vertices_out_dev, normals_out_dev, faces_out_dev,
+                        V_out, F_out);
+    if (rc || (rc = need_device())) return rc;
+    return mesh_trim_dev(V, vertices_dev, normals_dev, F, faces_dev, values_dev, threshold, vertices_out_dev, normals_out_dev, faces_out_dev, V_out,
+                         F_out, (hipStream_t)hip_stream);
+}
+
+int mvs_mesh_trim_by_value(int64_t V, const double* vertices, const double* normals, int64_t F, const int32_t* faces, const double* values,
+                           double threshold, double* vertices_out, double* normals_out, int32_t* faces_out, int64_t* V_out, int64_t* F_out) {
+    MVS_TRACE();
+    int rc = check_trim(__func__, V, vertices, normals, F, faces, values, threshold, vertices_out, normals_out, faces_out, V_out, F_out);
+    if (rc || (rc = need_device())) return rc;
+    Scratch dv, dn, df, dval, ov, on, of;
+    if ((rc = up(dv, vertices, 3 * (size_t)V)) || (rc = up(df, faces, 3 * (size_t)F)) || (rc = up(dval, values, (size_t)V)) ||
+        (normals && (rc = up(dn, normals, 3 * (size_t)V))) || (rc = ov.alloc(24 * (size_t)V)) || (rc = of.alloc(12 * (size_t)F)) ||
+        (normals && (rc = on.alloc(24 * (size_t)V)))) return rc;
+    if ((rc = mesh_trim_dev(V, dv.as<double>(), normals ? dn.as<double>() : nullptr, F, df.as<int32_t>(), dval.as<double>(), threshold, ov.as<double>(),
+                            normals ? on.as<double>() : nullptr, of.as<int32_t>(), V_out, F_out, nullptr))) return rc;
+    if ((rc = down(vertices_out, ov, 3 * (size_t)*V_out)) || (normals && (rc = down(normals_out, on, 3 * (size_t)*V_out)))) return rc;
+    return down(faces_out, of, 3 * (size_t)*F_out);
+}
+
+int mvs_test_poisson_density(int64_t n, const double* points, const double* normals, const mvs_poisson_params* p,
+                             const mvs_poisson_density_params* dparams, mvs_poisson_info* info, mvs_poisson_density_info* dinfo,
+                             int64_t* node_sums, int64_t density_node_capacity, double* rho, double* gain, double* rhs, double* chi,
+                             int64_t node_capacity) {
+    MVS_TRACE();
+    int rc = check_pn(__func__, n, points, normals, p, info, node_sums, density_node_capacity, rhs, node_capacity);
+    if (rc || (rc = check_pn_density(__func__, n, dparams, dinfo))) return rc;
+    if (!rho || !gain) return bad(__func__, "rho or gain is NULL");
+    if ((rc = need_device())) return rc;
+    Scratch dp, dn;
+    if ((rc = up(dp, points, 3 * (size_t)n)) || (rc = up(dn, normals, 3 * (size_t)n))) return rc;
+    PnRun run(*p, *info, n, dp.as<double>(), dn.as<double>(), nullptr);
+    run.dp = dparams;
+    run.dinfo = dinfo;
+    std::memset(dinfo, 0, sizeof *dinfo);
+    if ((rc = run.grid(__func__))) return rc;
+    int Dd = 0;
+    const PnGrid gd = pn_density_grid(run.g, run.side, info->depth, dparams->density_drop, &Dd);
+    dinfo->density_depth = Dd;
+    if ((int64_t)(gd.G + 1) * (gd.G + 1) * (gd.G + 1) > density_node_capacity || run.nn > node_capacity)
+        return bad(__func__, "a node capacity is below (2^depth + 1)^3 (info and dinfo hold the depths)");
+    if ((rc = run.density())) return rc;
+    int frc = MVS_OK;
+    if (chi) {                                                                // as mvs_test_poisson_field: MVS_E_SOLVER still hands out the field
+        frc = run.field(__func__);
+        if (frc && frc != MVS_E_SOLVER) return frc;
+        if (!frc && (rc = run.iso_value())) return rc;
+        HIPCHK(hipMemcpy(chi, run.L.x[info->depth], 8 * (size_t)run.nn, hipMemcpyDeviceToHost));
+    } else if ((rc = run.right_side())) return rc;
+    HIPCHK(hipMemcpy(node_sums, run.dsum.p, 8 * (size_t)run.nnd, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(rho, run.rho.p, 8 * (size_t)n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(gain, run.gain.p, 8 * (size_t)n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(rhs, run.rhs.p, 8 * (size_t)run.nn, hipMemcpyDeviceToHost));
     return frc;
 }
 

@@ -1,7 +1,9 @@
 // poisson_rules.h — the per-point and per-tetrahedron rules of mvs_poisson_reconstruct (include/mvs.h): the cell of a point (3), its
 // corners, weights and quantised contributions (5), the seven edge types and the six Kuhn tetrahedra of a cube (10), the vertex of a
-// crossed edge (11) and the polygon of a tetrahedron (12).  One body for the kernels of poisson.hip and for host code:
-// tests/poisson_rules.cpp runs it as a program of its own, tests/ref_poisson.py restates it.  Every operation is an fp64 + - * / in
+// crossed edge (11) and the polygon of a tetrahedron (12); of mvs_poisson_reconstruct_density the density grid (14), the density at a
+// point or a vertex (15, 17), the gain (16) and the pass test of the trim (18).  One body for the kernels of poisson.hip and for host code:
+// tests/poisson_rules.cpp and tests/poisson_density_rules.cpp run it as programs of their own, tests/ref_poisson.py and
+// tests/ref_poisson_density.py restate it.  Every operation is an fp64 + - * / in
 // the order written; the library is built with -ffp-contract=off.
 #ifndef MVS_POISSON_RULES_H_
 #define MVS_POISSON_RULES_H_
@@ -44,6 +46,38 @@ __host__ __device__ inline void pn_corners_weights(const double* p, const PnGrid
 // rule 5: a contribution x = w * n_a in units of 2^-36, round to nearest even (the default rounding mode)
 __host__ __device__ inline long long pn_quant(double x) { return llrint(x * 68719476736.0); }
 __host__ __device__ inline double pn_dequant(long long s) { return (double)s * (1.0 / 68719476736.0); }
+
+// rule 14: the density grid of a cube of this side at depth D: Dd = max(D - drop, 2), the origin of rule 2
+__host__ __device__ inline PnGrid pn_density_grid(const PnGrid& g, double side, int D, int drop, int* Dd) {
+    PnGrid d = g;
+    *Dd = D - drop > 2 ? D - drop : 2;
+    d.G = 1 << *Dd;
+    d.h = side / (double)d.G;
+    return d;
+}
+
+// rule 15: the trilinear W at p over the int64 node sums of rule 14 (corners and weights of rule 5 on the density grid, added in corner
+// order); the same body is rule 17 at a vertex
+__host__ __device__ inline double pn_density_at(const double* p, const PnGrid& gd, const long long* sums) {
+    int i0[3];
+    double w[8], v = 0.0;
+    pn_corners_weights(p, gd, i0, w);
+    for (int c = 0; c < 8; ++c) v = v + w[c] * pn_dequant(sums[pn_node(gd.G, i0[0] + (c & 1), i0[1] + (c >> 1 & 1), i0[2] + (c >> 2 & 1))]);
+    return v;
+}
+
+// rule 15: a point density in units of 2^-16 for the order-free sum behind rho_mean, and the mean of N of them
+__host__ __device__ inline long long pn_rho_quant(double rho) { return llrint(rho * 65536.0); }
+__host__ __device__ inline double pn_rho_mean(long long sum, long long N) { return (double)sum * (1.0 / 65536.0) / (double)N; }
+
+// rule 16: the gain of a point of density rho (rho = 0 gives max_gain)
+__host__ __device__ inline double pn_gain(double rho_mean, double rho, double max_gain) {
+    const double s = rho_mean / rho;
+    return s > max_gain ? max_gain : s;
+}
+
+// rule 18: does a value pass the threshold?  NaN does not
+__host__ __device__ inline bool pn_trim_pass(double value, double threshold) { return value >= threshold; }
 
 // rule 10: an edge type's offset as a bit mask (x = 1, y = 2, z = 4), types 0..6 = +x, +y, +z, +x+y, +x+z, +y+z, +x+y+z; and back
 __host__ __device__ inline int pn_type_mask(int type) { return (0x7653421 >> (4 * type)) & 15; }

@@ -557,15 +557,10 @@ def _poisson_info(info: L.CPoissonInfo) -> dict:
                 n_vertices=info.n_vertices, n_faces=info.n_faces, depth=info.depth, cycles=info.cycles)
 
 
-def RunPoisson(points, normals, params: L.CPoissonParams | None = None, stream: int | None = None, capacity: tuple | None = None):
-    """GeometryRec::RunPoisson (R/Processor/Processor.cpp:1042-1058) through ``mvs_poisson_reconstruct`` (the rules, this library's
-    definition: include/mvs.h).  ``points`` and ``normals`` are [n, 3] float64 — numpy arrays, or contiguous torch tensors on the GPU
-    (the device form: the results are tensors on the same device, and the kernels and the allocation of the results are ordered on
-    ``stream``, the HIP stream that produced the points; None: the legacy default stream).
-    -> (vertices [V, 3] float64, faces [F, 3] int32, info dict: origin, h, iso, rel_residual, n_used, n_vertices, n_faces, depth, cycles).
-    ``capacity`` = (vertex rows, face rows) sizes the first attempt, by default 12 * 4^Dmax vertices and twice as many faces (a closed
-    surface of modest area at the finest depth the call can pick); a call that finds more is repeated once with the right sizes."""
-    prm = params if params is not None else poisson_params()
+def _run_poisson(points, normals, prm, dprm, stream, capacity):
+    """the call behind ``RunPoisson`` (``dprm`` None: mvs_poisson_reconstruct) and ``RunPoissonDensity`` (mvs_poisson_reconstruct_density),
+    host or device form -> (vertices, faces, vertex density or None, info struct, density info struct or None)"""
+    name = "mvs_poisson_reconstruct" if dprm is None else "mvs_poisson_reconstruct_density"
     dev = _is_dev(points)
     if dev != _is_dev(normals):
         raise L.MvsError(-1, "points and normals must both be tensors on the GPU or both arrays")
@@ -577,40 +572,124 @@ def RunPoisson(points, normals, params: L.CPoissonParams | None = None, stream: 
         if tuple(points.shape) != tuple(normals.shape) or points.dim() != 2 or points.shape[1] != 3:
             raise L.MvsError(-1, "points and normals must be [n, 3]")
         pp, pn, n = _dev_ptr(points, "float64", "points"), _dev_ptr(normals, "float64", "normals"), int(points.shape[0])
-        fn, tail = L.lib().mvs_poisson_reconstruct_dev, (L.ptr(stream),)
+        fn, tail = getattr(L.lib(), name + "_dev"), (L.ptr(stream),)
     else:
         points, normals = L.arr(points, np.float64).reshape(-1, 3), L.arr(normals, np.float64).reshape(-1, 3)
         if points.shape != normals.shape:
             raise L.MvsError(-1, "points and normals must be [n, 3]")
         pp, pn, n = L.ptr(points), L.ptr(normals), len(points)
-        fn, tail = L.lib().mvs_poisson_reconstruct, ()
+        fn, tail = getattr(L.lib(), name), ()
     if n == 0:                                                  # a pointer to nothing is still a pointer
         pp = pn = L.ptr(np.zeros(3))
     if capacity is None:
         dmax = max(0, min(int(prm.depth_max), 9))
         capacity = (12 * 4 ** dmax, 24 * 4 ** dmax)
-    info = L.CPoissonInfo()
+    info, dinfo = L.CPoissonInfo(), None if dprm is None else L.CPoissonDensityInfo()
     with order:
         def call(vcap, fcap):
             v, f = _out_like(points, (max(1, vcap), 3), "float64"), _out_like(points, (max(1, fcap), 3), "int32")
-            return fn(n, pp, pn, C.byref(prm), C.byref(info), L.ptr(v), vcap, L.ptr(f), fcap, *tail), v, f
+            if dprm is None:
+                return fn(n, pp, pn, C.byref(prm), C.byref(info), L.ptr(v), vcap, L.ptr(f), fcap, *tail), v, f, None
+            d = _out_like(points, (max(1, vcap),), "float64")
+            return fn(n, pp, pn, C.byref(prm), C.byref(dprm), C.byref(info), C.byref(dinfo), L.ptr(v), L.ptr(d), vcap, L.ptr(f), fcap, *tail), v, f, d
 
         vcap, fcap = int(capacity[0]), int(capacity[1])
-        rc, v, f = call(vcap, fcap)
+        rc, v, f, d = call(vcap, fcap)
         if rc == -1 and (info.n_vertices > vcap or info.n_faces > fcap):
             vcap, fcap = int(info.n_vertices), int(info.n_faces)
-            rc, v, f = call(vcap, fcap)
+            rc, v, f, d = call(vcap, fcap)
     L.check(rc)
-    return v[:info.n_vertices], f[:info.n_faces], _poisson_info(info)
+    return v[:info.n_vertices], f[:info.n_faces], None if d is None else d[:info.n_vertices], info, dinfo
 
 
-def PoissonFiles(psr_npts, model_obj, params: L.CPoissonParams | None = None):
+def RunPoisson(points, normals, params: L.CPoissonParams | None = None, stream: int | None = None, capacity: tuple | None = None):
+    """GeometryRec::RunPoisson (R/Processor/Processor.cpp:1042-1058) through ``mvs_poisson_reconstruct`` (the rules, this library's
+    definition: include/mvs.h).  ``points`` and ``normals`` are [n, 3] float64 — numpy arrays, or contiguous torch tensors on the GPU
+    (the device form: the results are tensors on the same device, and the kernels and the allocation of the results are ordered on
+    ``stream``, the HIP stream that produced the points; None: the legacy default stream).
+    -> (vertices [V, 3] float64, faces [F, 3] int32, info dict: origin, h, iso, rel_residual, n_used, n_vertices, n_faces, depth, cycles).
+    ``capacity`` = (vertex rows, face rows) sizes the first attempt, by default 12 * 4^Dmax vertices and twice as many faces (a closed
+    surface of modest area at the finest depth the call can pick); a call that finds more is repeated once with the right sizes."""
+    v, f, _, info, _ = _run_poisson(points, normals, params if params is not None else poisson_params(), None, stream, capacity)
+    return v, f, _poisson_info(info)
+
+
+def PoissonFiles(psr_npts, model_obj, params: L.CPoissonParams | None = None, dparams: L.CPoissonDensityParams | None = None,
+                 trim_ratio: float | None = None):
     """``mvs_processor_poisson``: ``psr_npts`` (Result/PSR.npts, what ``StitchPointSets`` wrote) -> ``model_obj`` (Result/Model.obj with
-    `v`, `vn` and `f` lines, what ``CullPoissonModel`` reads).  -> (V, F) written."""
+    `v`, `vn` and `f` lines, what ``CullPoissonModel`` reads).  -> (V, F) written.  With ``dparams`` (``poisson_density_params``) or
+    ``trim_ratio`` the call is ``mvs_processor_poisson_density``: the normals weighted by the sampling density when ``dparams`` sets
+    WEIGHT_NORMALS, the mesh trimmed where its vertex density lies below ``trim_ratio`` times the mean point density."""
     prm = params if params is not None else poisson_params()
     V, F = C.c_int64(), C.c_int64()
-    L.check(L.lib().mvs_processor_poisson(os.fsencode(psr_npts), C.byref(prm), os.fsencode(model_obj), C.byref(V), C.byref(F)))
+    if dparams is None and trim_ratio is None:
+        L.check(L.lib().mvs_processor_poisson(os.fsencode(psr_npts), C.byref(prm), os.fsencode(model_obj), C.byref(V), C.byref(F)))
+    else:
+        L.check(L.lib().mvs_processor_poisson_density(os.fsencode(psr_npts), C.byref(prm), C.byref(dparams) if dparams is not None else None,
+                                                      float(trim_ratio or 0.0), os.fsencode(model_obj), C.byref(V), C.byref(F)))
     return V.value, F.value
+
+
+WEIGHT_NORMALS = 1                          # MVS_POISSON_WEIGHT_NORMALS
+
+
+def poisson_density_params(**kw) -> L.CPoissonDensityParams:
+    """``mvs_poisson_density_default_params`` (max_gain 4, flags 0: no weighting, density_drop 1) with the given fields replaced."""
+    return _params(L.CPoissonDensityParams, L.lib().mvs_poisson_density_default_params, kw)
+
+
+def RunPoissonDensity(points, normals, params: L.CPoissonParams | None = None, dparams: L.CPoissonDensityParams | None = None,
+                      stream: int | None = None, capacity: tuple | None = None):
+    """``mvs_poisson_reconstruct_density`` (rules 14-17 of include/mvs.h, this library's definition): ``RunPoisson`` with the sampling
+    density — the normals weighted by mean density / local density when ``dparams.flags`` holds ``WEIGHT_NORMALS`` (off by default: the
+    mesh is then ``RunPoisson``'s) — and the density of every vertex.  Arguments as ``RunPoisson``.
+    -> (vertices [V, 3] float64, faces [F, 3] int32, density [V] float64, info dict: that of ``RunPoisson`` plus mean_density,
+    min_point_density, max_point_density, density_depth, n_clamped)."""
+    v, f, d, info, dinfo = _run_poisson(points, normals, params if params is not None else poisson_params(),
+                                        dparams if dparams is not None else poisson_density_params(), stream, capacity)
+    out = _poisson_info(info)
+    out.update(mean_density=dinfo.mean_density, min_point_density=dinfo.min_point_density, max_point_density=dinfo.max_point_density,
+               density_depth=dinfo.density_depth, n_clamped=dinfo.n_clamped)
+    return v, f, d, out
+
+
+def TrimByValue(vertices, faces, values, threshold: float, normals=None, stream: int | None = None):
+    """``mvs_mesh_trim_by_value`` (rule 18 of include/mvs.h): the faces whose three vertices have ``values[v] >= threshold`` and the
+    vertices those faces use, in their order, the faces renumbered.  Arrays, or contiguous torch tensors on the GPU (the device form,
+    ordered on ``stream``).  -> (vertices, faces), or (vertices, faces, normals) when ``normals`` is given."""
+    dev = _is_dev(vertices)
+    if any(_is_dev(a) != dev for a in (faces, values)) or (normals is not None and _is_dev(normals) != dev):
+        raise L.MvsError(-1, "vertices, faces, values and normals must all be tensors on the GPU or all arrays")
+    order = contextlib.nullcontext()
+    if dev:
+        import torch
+        if stream:
+            order = torch.cuda.stream(torch.cuda.ExternalStream(int(stream)))
+        ptrs = [_dev_ptr(vertices, "float64", "vertices"), _dev_ptr(normals, "float64", "normals"), _dev_ptr(faces, "int32", "faces"),
+                _dev_ptr(values, "float64", "values")]
+        V, F = int(vertices.shape[0]), int(faces.shape[0])
+        if vertices.dim() != 2 or vertices.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3 or values.numel() != V or \
+                (normals is not None and tuple(normals.shape) != tuple(vertices.shape)):
+            raise L.MvsError(-1, "vertices and normals must be [V, 3], faces [F, 3], values [V]")
+        fn, tail = L.lib().mvs_mesh_trim_by_value_dev, (L.ptr(stream),)
+    else:
+        vertices, faces, values = L.arr(vertices, np.float64).reshape(-1, 3), L.arr(faces, np.int32).reshape(-1, 3), L.arr(values, np.float64).reshape(-1)
+        normals = L.arr(normals, np.float64).reshape(-1, 3) if normals is not None else None
+        V, F = len(vertices), len(faces)
+        if len(values) != V or (normals is not None and len(normals) != V):
+            raise L.MvsError(-1, "vertices and normals must be [V, 3], faces [F, 3], values [V]")
+        ptrs = [L.ptr(vertices), L.ptr(normals), L.ptr(faces), L.ptr(values)]
+        fn, tail = L.lib().mvs_mesh_trim_by_value, ()
+    nV, nF = C.c_int64(), C.c_int64()
+    with order:
+        ov, of = _out_like(vertices, (max(1, V), 3), "float64"), _out_like(vertices, (max(1, F), 3), "int32")
+        on = _out_like(vertices, (max(1, V), 3), "float64") if normals is not None else None
+        if V == 0 or F == 0:                                    # a pointer to nothing is still a pointer: the outputs stand in
+            ptrs = [L.ptr(ov), L.ptr(on), L.ptr(of), L.ptr(ov)]
+        L.check(fn(V, ptrs[0], ptrs[1], F, ptrs[2], ptrs[3], float(threshold), L.ptr(ov), L.ptr(on), L.ptr(of), C.byref(nV), C.byref(nF), *tail))
+    if normals is not None:
+        return ov[:nV.value], of[:nF.value], on[:nV.value]
+    return ov[:nV.value], of[:nF.value]
 
 
 def CullPoissonModel(model_obj, scales, Rs, ts, cameras, out_obj, all_seq_proj: bool = True):

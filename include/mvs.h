@@ -697,6 +697,67 @@ int mvs_poisson_reconstruct_density_dev(int64_t n, const double* points_dev, con
                                         const mvs_poisson_density_params* dparams, mvs_poisson_info* info, mvs_poisson_density_info* dinfo,
                                         double* vertices_dev, double* vertex_density_dev, int64_t vertex_capacity, int32_t* faces_dev,
                                         int64_t face_capacity, void* hip_stream);
+/* Screening: the point-interpolation term of Kazhdan and Hoppe (Screened Poisson Surface Reconstruction, 2013).  Rules 1-9 cut one iso
+ * surface at the mean of chi over the points; where the local jump of chi differs from the mean the surface sits at the wrong offset.
+ * The screened call penalises (chi(p) - T)^2 at every used point p, T the iso value of the unscreened field: a second solve that starts
+ * from that field.  Rules 19-23 continue the list above; like rules 1-18 they are this library's definition and are NOT VERIFIED against
+ * GeoRec.  alpha = 0 does no second solve: vertices, faces, vertex_density, info and dinfo hold the bytes of
+ * mvs_poisson_reconstruct_density, and sinfo holds cycles = 0, lambda = 0, target = iso_unscreened = iso.
+ *  19. weight      : occ = occupied(D) of rule 3, computed also when depth_min == Dmax; m = max(1.0, (double)N / (double)occ);
+ *                    lambda = alpha / m, the same for every used point.  MVS_POISSON_WEIGHT_NORMALS keeps its meaning for both solves
+ *                    and does not change lambda.
+ *  20. stencil     : every used point has the eight corners and weights w_c of rule 5 (the scale check makes all eight interior nodes).
+ *                    For every unordered corner pair c1 <= c2 (corner order bx + 2 by + 4 bz) x = (lambda * w_c1) * w_c2 and
+ *                    q = llrint(x * 2^30); q is added in int64 to the entry (node of c1, offset c2 - c1) and, for c1 != c2, also to the
+ *                    entry (node of c2, offset c1 - c2): the stencil is exactly symmetric and does not depend on the order of the
+ *                    points.  S_{i,o} = (double)sum * 2^-30 for the 27 offsets o in {-1, 0, 1}^3, kept in the order
+ *                    (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1); rs_i = (double)(the int64 sum of node i's 27 sums) * 2^-30.
+ *                    The sums stay inside int64: the 64 entries a point adds to belong to eight rows, and what it adds to one row i is
+ *                    at most lambda * w_i * (the sum of its eight weights, 1 up to rounding) * 2^30 plus half a unit per entry; with
+ *                    alpha <= 64 = 2^6, w <= 1 and N <= 2^26 a row sum, and so every entry of it (all are >= 0), is at most
+ *                    2^6 * 2^30 * 2^26 * (1 + 2^-50) + 8 * 2^26 < 2^63.
+ *  21. system      : chi0 and T are the field and the iso value of rules 1-9 (with the flag the weighted ones).  At interior nodes
+ *                    (the sum of the six neighbours' chi - 6 chi_i) - sum_o S_{i,o} chi_{i+o} = f_i, f_i = b_i - T * rs_i; the
+ *                    sum over o runs in the order of rule 20 into one accumulator that starts at 0.  M names the operator on the left.
+ *                    The boundary stays zero Dirichlet.
+ *  22. solve       : from chi0, multigrid cycles until the TRUE residual, recomputed on the device after every cycle with partial sums
+ *                    in a fixed order, satisfies |f - M chi|_2 <= solve_tol * |f|_2.  max_cycles applies to this solve on its own;
+ *                    failing it gives MVS_E_SOLVER with the residual reached in sinfo.  |f| = 0 gives chi = chi0.  The cycle is not
+ *                    part of the definition (csrc/poisson.hip: the V(2,2) cycle of rule 8 on M_l = A_l - S_l, S_D = S and
+ *                    S_l = 1/2 P^T S_(l+1) P with the trilinear prolongation P, Jacobi damped by 6/7 over the diagonal 6 + rs_i / 2).
+ *  23. surface     : iso = rule 9 evaluated on the screened chi; rules 10-13 and 17 are unchanged.
+ * Scratch beyond the density call's: 2^(3 D - 3) bytes for rule 19; per level 4 bytes per node (the number of the node's stencil row)
+ * and 228 bytes per node that a point touches (27 entries, the row sum and the node), a few per occupied cell; 1 byte per node of the
+ * finest level for the flags.
+ * MVS_E_INVALID_ARG, before a device is needed: what mvs_poisson_reconstruct_density refuses, sparams or sinfo NULL, alpha not finite or
+ * outside [0, 64], reserved != 0. */
+typedef struct mvs_poisson_screen_params {
+    double  alpha;              /* 4: the screening weight per point before rule 19's division   */
+    int64_t reserved;           /* 0                                                             */
+} mvs_poisson_screen_params;
+typedef struct mvs_poisson_screen_info {
+    double  target;             /* T of rule 21                                                  */
+    double  lambda;             /* rule 19                                                       */
+    double  rel_residual;       /* |f - M chi|_2 / |f|_2 after the last cycle of rule 22         */
+    double  iso_unscreened;     /* rule 9 on chi0                                                */
+    int64_t occupied;           /* occ of rule 19                                                */
+    int64_t active_nodes;       /* nodes of the finest level with a stencil                      */
+    int32_t cycles;             /* cycles of rule 22                                             */
+    int32_t reserved;
+} mvs_poisson_screen_info;
+/* the values in the comments above */
+void mvs_poisson_screen_default_params(mvs_poisson_screen_params* p);
+int mvs_poisson_reconstruct_screened(int64_t n, const double* points, const double* normals, const mvs_poisson_params* p,
+                                     const mvs_poisson_density_params* dparams, const mvs_poisson_screen_params* sparams, mvs_poisson_info* info,
+                                     mvs_poisson_density_info* dinfo, mvs_poisson_screen_info* sinfo, double* vertices, double* vertex_density,
+                                     int64_t vertex_capacity, int32_t* faces, int64_t face_capacity);
+/* the device form, as mvs_poisson_reconstruct_dev */
+int mvs_poisson_reconstruct_screened_dev(int64_t n, const double* points_dev, const double* normals_dev, const mvs_poisson_params* p,
+                                         const mvs_poisson_density_params* dparams, const mvs_poisson_screen_params* sparams,
+                                         mvs_poisson_info* info, mvs_poisson_density_info* dinfo, mvs_poisson_screen_info* sinfo,
+                                         double* vertices_dev, double* vertex_density_dev, int64_t vertex_capacity, int32_t* faces_dev,
+                                         int64_t face_capacity, void* hip_stream);
+
 /* Rule 18 on any triangle mesh: vertices[V][3], normals[V][3] (may be NULL, then normals_out is not written), faces[F][3], values[V].
  * The outputs hold V resp. F rows and do not overlap the inputs; V_out / F_out receive the rows kept.  An ordered compaction without
  * atomics: two runs give the same bytes.  MVS_E_INVALID_ARG, before a device is needed: a NULL argument other than normals /

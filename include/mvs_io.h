@@ -119,6 +119,12 @@ int mvs_processor_poisson(const char* psr_npts, const mvs_poisson_params* params
 int mvs_processor_poisson_density(const char* psr_npts, const mvs_poisson_params* params, const mvs_poisson_density_params* dparams,
                                   double trim_ratio, const char* model_obj, int64_t* V, int64_t* F);
 
+/* mvs_processor_poisson_density through mvs_poisson_reconstruct_screened (rules 19-23 of include/mvs.h: this library's definition, NOT
+ * VERIFIED against GeoRec): sparams NULL means the defaults (alpha = 4).  With alpha = 0 the file holds the bytes
+ * mvs_processor_poisson_density writes for the same dparams and trim_ratio. */
+int mvs_processor_poisson_screened(const char* psr_npts, const mvs_poisson_params* params, const mvs_poisson_density_params* dparams,
+                                   const mvs_poisson_screen_params* sparams, double trim_ratio, const char* model_obj, int64_t* V, int64_t* F);
+
 #ifdef __cplusplus
 }
 #endif

@@ -85,6 +85,18 @@ int mvs_test_poisson_density(int64_t n, const double* points, const double* norm
                              int64_t* node_sums, int64_t density_node_capacity, double* rho, double* gain, double* rhs, double* chi,
                              int64_t node_capacity);
 
+/* mvs_poisson_reconstruct_screened up to rule 23's iso value: info, dinfo and sinfo as that call writes them (n_vertices and n_faces stay
+ * 0); stencil: the int64 sums of rule 20 on the finest level, dense, [(2^depth + 1)^3][27] in node order and the offset order of rule 20
+ * (zero where no point touches; all zero for alpha = 0); f of rule 21 (b for alpha = 0), chi0 and the screened chi (chi0 for alpha = 0),
+ * (2^depth + 1)^3 doubles each.  A node count above node_capacity gives MVS_E_INVALID_ARG after info's depth is written.  MVS_E_SOLVER
+ * of the screened solve still hands out the field it reached.  diagonal selects the diagonal of the cycle's Jacobi smoother: 0 the public
+ * call's 6 + rs_i / 2, 1 the plain 6 + S_{i,0}, 2 the row sum 6 + rs_i — the measurement behind the choice, not a mode of the public call;
+ * another value gives MVS_E_INVALID_ARG. */
+int mvs_test_poisson_screened(int64_t n, const double* points, const double* normals, const mvs_poisson_params* p,
+                              const mvs_poisson_density_params* dparams, const mvs_poisson_screen_params* sparams, mvs_poisson_info* info,
+                              mvs_poisson_density_info* dinfo, mvs_poisson_screen_info* sinfo, int64_t* stencil, double* f, double* chi0,
+                              double* chi, int64_t node_capacity, int32_t diagonal);
+
 #ifdef __cplusplus
 }
 #endif

@@ -100,6 +100,17 @@ class CPoissonDensityInfo(C.Structure):
                 ("density_depth", C.c_int32), ("n_clamped", C.c_int32)]
 
 
+class CPoissonScreenParams(C.Structure):
+    """struct mvs_poisson_screen_params."""
+    _fields_ = [("alpha", C.c_double), ("reserved", C.c_int64)]
+
+
+class CPoissonScreenInfo(C.Structure):
+    """struct mvs_poisson_screen_info."""
+    _fields_ = [("target", C.c_double), ("lambda_", C.c_double), ("rel_residual", C.c_double), ("iso_unscreened", C.c_double),
+                ("occupied", C.c_int64), ("active_nodes", C.c_int64), ("cycles", C.c_int32), ("reserved", C.c_int32)]
+
+
 class CSeqPairParams(C.Structure):
     """struct mvs_seq_pair_params."""
     _fields_ = [("filter", CMatchFilterParams), ("min_dsp", C.c_double), ("max_dsp", C.c_double), ("min_match_count", C.c_int32),
@@ -157,6 +168,9 @@ _SIGS = {
     "mvs_poisson_density_default_params": (None, [_VP]),
     "mvs_poisson_reconstruct_density": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _I64]),
     "mvs_poisson_reconstruct_density_dev": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _I64, _VP]),
+    "mvs_poisson_screen_default_params": (None, [_VP]),
+    "mvs_poisson_reconstruct_screened": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _I64]),
+    "mvs_poisson_reconstruct_screened_dev": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _I64, _VP]),
     "mvs_mesh_trim_by_value": (C.c_int, [_I64, _VP, _VP, _I64, _VP, _VP, _D, _VP, _VP, _VP, _VP, _VP]),
     "mvs_mesh_trim_by_value_dev": (C.c_int, [_I64, _VP, _VP, _I64, _VP, _VP, _D, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mvs_render_depth": (C.c_int, [_VP, _I64, _VP, _I64, _VP, C.c_float, C.c_float, _VP]),
@@ -253,6 +267,7 @@ _SIGS = {
     "mvs_processor_point_sample": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mvs_processor_poisson": (C.c_int, [C.c_char_p, _VP, C.c_char_p, _VP, _VP]),
     "mvs_processor_poisson_density": (C.c_int, [C.c_char_p, _VP, _VP, _D, C.c_char_p, _VP, _VP]),
+    "mvs_processor_poisson_screened": (C.c_int, [C.c_char_p, _VP, _VP, _VP, _D, C.c_char_p, _VP, _VP]),
     # include/mvs_test.h (test hooks: per handle, not part of the drop-in ABI)
     "mvs_test_preload_wait": (C.c_int, []),
     "mvs_test_ctl": (C.c_int, [_VP, _VP, _I32]),
@@ -268,6 +283,7 @@ _SIGS = {
     "mvs_test_point_sample_candidates": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP, _I64]),
     "mvs_test_poisson_field": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _I64]),
     "mvs_test_poisson_density": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _I64]),
+    "mvs_test_poisson_screened": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _I32]),
 }
 EXPORTS = tuple(_SIGS)
 

@@ -355,9 +355,9 @@ int mvs_processor_point_sample(int32_t n_seq, const char* const* seq_dirs, const
     return MVS_OK;
 }
 
-// PSR.npts -> Model.obj; dprm != NULL: through rules 14-17, and trimmed by rule 18 when trim_ratio > 0
+// PSR.npts -> Model.obj; dprm != NULL: through rules 14-17, and trimmed by rule 18 when trim_ratio > 0; sprm != NULL (with dprm): rules 19-23
 static int poisson_files(const char* fn, const char* psr_npts, const mvs_poisson_params& prm, const mvs_poisson_density_params* dprm, double trim_ratio,
-                         const char* model_obj, int64_t* V_out, int64_t* F_out) {
+                         const char* model_obj, int64_t* V_out, int64_t* F_out, const mvs_poisson_screen_params* sprm = nullptr) {
     int rc = need_device();
     if (rc) return rc;
     int64_t n = 0;
@@ -369,8 +369,9 @@ static int poisson_files(const char* fn, const char* psr_npts, const mvs_poisson
     Scratch dp, dn, dv, df, dvn, dd, tv, tf;
     mvs_poisson_info info;
     mvs_poisson_density_info dinfo;
+    mvs_poisson_screen_info sinfo;
     if ((rc = up(dp, hp.data(), (size_t)n * 3)) || (rc = up(dn, hn.data(), (size_t)n * 3))) return rc;
-    if (dprm) rc = poisson_density_blocks(fn, n, dp.as<double>(), dn.as<double>(), &prm, dprm, &info, &dinfo, &dv, &dd, &df);
+    if (dprm) rc = poisson_density_blocks(fn, n, dp.as<double>(), dn.as<double>(), &prm, dprm, &info, &dinfo, &dv, &dd, &df, sprm, sprm ? &sinfo : nullptr);
     else rc = poisson_blocks(fn, n, dp.as<double>(), dn.as<double>(), &prm, &info, &dv, &df);
     if (rc) return rc;
     int64_t V = info.n_vertices, F = info.n_faces;
@@ -410,6 +411,20 @@ int mvs_processor_poisson_density(const char* psr_npts, const mvs_poisson_params
     if (params) prm = *params; else mvs_poisson_default_params(&prm);
     if (dparams) dprm = *dparams; else mvs_poisson_density_default_params(&dprm);
     return poisson_files(__func__, psr_npts, prm, &dprm, trim_ratio, model_obj, V_out, F_out);
+}
+
+int mvs_processor_poisson_screened(const char* psr_npts, const mvs_poisson_params* params, const mvs_poisson_density_params* dparams,
+                                   const mvs_poisson_screen_params* sparams, double trim_ratio, const char* model_obj, int64_t* V_out, int64_t* F_out) {
+    MVS_TRACE();
+    if (!psr_npts || !model_obj) return bad(__func__, "psr_npts / model_obj is NULL");
+    if (trim_ratio != trim_ratio) return bad(__func__, "trim_ratio is NaN");
+    mvs_poisson_params prm;
+    mvs_poisson_density_params dprm;
+    mvs_poisson_screen_params sprm;
+    if (params) prm = *params; else mvs_poisson_default_params(&prm);
+    if (dparams) dprm = *dparams; else mvs_poisson_density_default_params(&dprm);
+    if (sparams) sprm = *sparams; else mvs_poisson_screen_default_params(&sprm);
+    return poisson_files(__func__, psr_npts, prm, &dprm, trim_ratio, model_obj, V_out, F_out, &sprm);
 }
 
 }  // extern "C"

@@ -27,11 +27,13 @@
 //   k_pn_vertex_density rule 17, over the vertex list the scatter wrote
 //   k_tr_face_mark / k_tr_vertex_count / CompactTail / k_tr_vertex_scatter / k_tr_face_scatter
 //                      rule 18: flags and plain byte marks, compact.hip's scan, two ordered scatters
+// mvs_poisson_reconstruct_screened adds the second, screened solve (rules 19-23): the k_sc_* and *_sc kernels, described where they stand.
 // Nothing but the integer atomics of the splats and the bitmap is unordered: two runs give the same bytes.
 #include "engine.h"
 #include "trace.h"
 #include "frontend_dev.h"
 #include "poisson_rules.h"
+#include "knobs.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -438,6 +440,305 @@ __global__ __launch_bounds__(PN_COARSE_TPB) void k_mg_coarse(PnLevels L, int top
     }
 }
 
+// ------------------------------------------------------------------ rules 19-22 ----
+// The screened operator of level l is M_l = A_l - S_l with S_l = 1/2 P^T S_(l+1) P, P the trilinear prolongation: pn_restrict_at is HALF
+// the transposed prolongation, and under it the Laplacian reproduces itself.  (The trilinear bases nest, so S_l is also the stencil of
+// rule 20 splatted with the weights of level l and lambda * 2^-(D - l).)  A level keeps the number of every node's stencil row (idx, -1: the node has none) and the rows of the
+// nodes that a point touches, SC_ROW doubles each: the 27 entries in the offset order of rule 20, then the row sum.
+//   k_sc_flag / k_sc_count / k_sc_number   plain byte stores of 1, then the ordered compaction of the edges and faces: no atomic counter
+//   k_sc_splat / k_sc_convert              rule 20 on the finest level: 64 int64 atomic adds per point; the sums become doubles in place
+//   k_sc_flag_coarse / k_sc_coarsen        the rows of a level below the finest, gathered from the level above
+//   k_sc_rhs                               rule 21: f = b - T rs
+//   k_sc_smooth_rows                       the smoother of the launched levels is k_mg_smooth, then this pass over the rows (measured
+//                                          against the fused k_mg_smooth_sc, which the diagnostics build can still select)
+//   k_mg_smooth_sc / k_mg_residual_sc / k_mg_coarse_sc
+//                                          k_mg_smooth, k_mg_residual and k_mg_coarse with the stencil term at the nodes that have a row:
+//                                          Jacobi damped by 6/7 over the diagonal d = 6 + rs / 2.  Every entry of S is >= 0, so the
+//                                          absolute row sum of M is at most 12 + rs, and the eigenvalues of the iteration's
+//                                          (7/6 d)^-1 M lie below (12 + rs) / (7 + 7/12 rs) < 2: it converges.  6 + rs converges too
+//                                          but smooths the S part half as fast; the plain diagonal 6 + S_{i,0} can diverge where the
+//                                          points are dense (S is then lambda rho times a mass matrix, whose Jacobi spectrum reaches
+//                                          27/8).  The diagonal is a template parameter: the public call instantiates this one only,
+//                                          mvs_test_poisson_screened the other two for the measurement behind the choice.
+constexpr int SC_ROW = 28;
+// the smoother of the launched levels: 0 the fused kernel k_mg_smooth_sc, 1 k_mg_smooth and then k_sc_smooth_rows over the rows.  A
+// compile-time constant in the product build; the diagnostics build reads MVS_SC_SMOOTH_BY_ROWS once (scripts/bench_poisson_screened.py)
+#define SC_SMOOTH_BY_ROWS (MVS_KNOB("MVS_SC_SMOOTH_BY_ROWS", 1, 0, 1) != 0.0)
+constexpr int SC_DIAG_HALF_ROW_SUM = 0, SC_DIAG_PLAIN = 1, SC_DIAG_ROW_SUM = 2;    // the Jacobi diagonal 6 + rs / 2 (kept), 6 + S_{i,0}, 6 + rs
+struct ScLevels { const int32_t* idx[PN_MAX_D + 1]; const double* tab[PN_MAX_D + 1]; };
+
+__global__ __launch_bounds__(PN_TPB) void k_sc_flag(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm, PnGrid g,
+                                                    uint8_t* __restrict__ flag) {
+    const int64_t i = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
+    if (i >= n || !pn_used(pts + 3 * i, nrm + 3 * i)) return;
+    int i0[3];
+    double w[8];
+    pn_corners_weights(pts + 3 * i, g, i0, w);
+    for (int c = 0; c < 8; ++c) flag[pn_node(g.G, i0[0] + (c & 1), i0[1] + (c >> 1 & 1), i0[2] + (c >> 2 & 1))] = 1;
+}
+
+__global__ __launch_bounds__(PN_TPB) void k_sc_count(int64_t nn, const uint8_t* __restrict__ flag, int32_t* __restrict__ cnt) {
+    __shared__ int s_wsum[PN_WAVES];
+    const int64_t at = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
+    const WgRank k = wg_rank<PN_WAVES>(at < nn && flag[at], s_wsum);
+    if (threadIdx.x == 0) cnt[blockIdx.x] = k.total;
+}
+
+// idx[node] = the number of the node's row or -1; node_of[row] = its node
+__global__ __launch_bounds__(PN_TPB) void k_sc_number(int64_t nn, const uint8_t* __restrict__ flag, const int32_t* __restrict__ base,
+                                                      int32_t* __restrict__ idx, int32_t* __restrict__ node_of) {
+    __shared__ int s_wsum[PN_WAVES];
+    const int64_t at = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
+    const bool f = at < nn && flag[at];
+    const int pos = base[blockIdx.x] + wg_rank<PN_WAVES>(f, s_wsum).rank;
+    if (at < nn) idx[at] = f ? pos : -1;
+    if (f) node_of[pos] = (int32_t)at;
+}
+
+__global__ __launch_bounds__(PN_TPB) void k_sc_splat(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm, PnGrid g, double lambda,
+                                                     const int32_t* __restrict__ idx, unsigned long long* __restrict__ tab) {
+    const int64_t i = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
+    if (i >= n || !pn_used(pts + 3 * i, nrm + 3 * i)) return;
+    int i0[3];
+    double w[8];
+    int64_t row[8];
+    pn_corners_weights(pts + 3 * i, g, i0, w);
+    for (int c = 0; c < 8; ++c) row[c] = (int64_t)SC_ROW * idx[pn_node(g.G, i0[0] + (c & 1), i0[1] + (c >> 1 & 1), i0[2] + (c >> 2 & 1))];   // flagged: >= 0
+    for (int c1 = 0; c1 < 8; ++c1)
+        for (int c2 = c1; c2 < 8; ++c2) {
+            int o12, o21;
+            const unsigned long long q = (unsigned long long)pn_screen_pair(lambda, w, c1, c2, &o12, &o21);
+            atomicAdd(tab + row[c1] + o12, q);
+            if (c1 != c2) atomicAdd(tab + row[c2] + o21, q);
+        }
+}
+
+// The levels below the finest take their rows from the level above, T_c = 1/2 P^T T_f P, gathered: a coarse node has a row when one of
+// the 27 fine nodes around its own fine node has one (the same nodes the points touch on the coarse level), and a thread per coarse
+// row adds, in a fixed order, the products it is made of.  Per axis the trilinear weight of fine offset e from a coarse node is
+// 1 - |e| / 2 for |e| <= 1.  No atomics: a splat of 2 M points into the few rows of a coarse level would queue on them.
+__global__ __launch_bounds__(PN_TPB) void k_sc_flag_coarse(int Gc, const int32_t* __restrict__ idx_f, uint8_t* __restrict__ flag) {
+    const int n1 = Gc + 1, m1 = 2 * Gc + 1;
+    const int64_t at = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
+    if (at >= (int64_t)n1 * n1 * n1) return;
+    const int ix = (int)(at % n1), iy = (int)(at / n1 % n1), iz = (int)(at / ((int64_t)n1 * n1));
+    bool any = false;
+    for (int dz = -1; dz <= 1; ++dz)
+        for (int dy = -1; dy <= 1; ++dy)
+            for (int dx = -1; dx <= 1; ++dx) {
+                const int fx = 2 * ix + dx, fy = 2 * iy + dy, fz = 2 * iz + dz;
+                if (fx < 0 || fx >= m1 || fy < 0 || fy >= m1 || fz < 0 || fz >= m1) continue;
+                any = any || idx_f[((int64_t)fz * m1 + fy) * m1 + fx] >= 0;
+            }
+    flag[at] = any ? 1 : 0;
+}
+
+__device__ inline double sc_hat(int e) { return e == 0 ? 1.0 : e == 1 || e == -1 ? 0.5 : 0.0; }
+
+__global__ __launch_bounds__(PN_TPB) void k_sc_coarsen(int64_t rows, const int32_t* __restrict__ node_c, int Gc, const int32_t* __restrict__ idx_f,
+                                                       const double* __restrict__ tab_f, double* __restrict__ tab_c) {
+    const int64_t a = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
+    if (a >= rows) return;
+    const int n1 = Gc + 1, m1 = 2 * Gc + 1;
+    const int64_t at = node_c[a];
+    const int ix = (int)(at % n1), iy = (int)(at / n1 % n1), iz = (int)(at / ((int64_t)n1 * n1));
+    double* out = tab_c + SC_ROW * a;
+    double acc[27];
+    for (int k = 0; k < 27; ++k) acc[k] = 0.0;
+    for (int dz = -1; dz <= 1; ++dz)
+        for (int dy = -1; dy <= 1; ++dy)
+            for (int dx = -1; dx <= 1; ++dx) {                                // the fine node 2 I + d and its weight in the coarse basis of I
+                const int fx = 2 * ix + dx, fy = 2 * iy + dy, fz = 2 * iz + dz;
+                if (fx < 0 || fx >= m1 || fy < 0 || fy >= m1 || fz < 0 || fz >= m1) continue;
+                const int fa = idx_f[((int64_t)fz * m1 + fy) * m1 + fx];
+                if (fa < 0) continue;
+                const double* row = tab_f + (int64_t)SC_ROW * fa;
+                const double wd = (sc_hat(dx) * sc_hat(dy)) * sc_hat(dz);
+                for (int oz = -1; oz <= 1; ++oz)
+                    for (int oy = -1; oy <= 1; ++oy)
+                        for (int ox = -1; ox <= 1; ++ox) {                    // its entry o lands on the coarse nodes I + O with |d + o - 2 O| <= 1
+                            const double v = wd * row[pn_screen_offset(ox, oy, oz)];
+                            if (v == 0.0) continue;
+                            for (int Oz = -1; Oz <= 1; ++Oz) {
+                                const double wz = sc_hat(dz + oz - 2 * Oz);
+                                if (wz == 0.0) continue;
+                                for (int Oy = -1; Oy <= 1; ++Oy) {
+                                    const double wy = sc_hat(dy + oy - 2 * Oy);
+                                    if (wy == 0.0) continue;
+                                    for (int Ox = -1; Ox <= 1; ++Ox) {
+                                        const double wx = sc_hat(dx + ox - 2 * Ox);
+                                        if (wx != 0.0) acc[pn_screen_offset(Ox, Oy, Oz)] += v * ((wx * wy) * wz);
+                                    }
+                                }
+                            }
+                        }
+            }
+    double rs = 0.0;
+    for (int k = 0; k < 27; ++k) { out[k] = 0.5 * acc[k]; rs += 0.5 * acc[k]; }
+    out[27] = rs;
+}
+
+// the hook's dense copy of the finest level's sums, before k_sc_convert: out[node][27]
+__global__ __launch_bounds__(PN_TPB) void k_sc_dense(int64_t nn, const int32_t* __restrict__ idx, const long long* __restrict__ tab,
+                                                     long long* __restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
+    if (e >= 27 * nn) return;
+    const int a = idx[e / 27];
+    out[e] = a < 0 ? 0 : tab[(int64_t)SC_ROW * a + e % 27];
+}
+
+// a thread per row: the 27 int64 sums and their int64 sum become doubles in place (the bits of a double stored as the int64 they were)
+__global__ __launch_bounds__(PN_TPB) void k_sc_convert(int64_t rows, long long* __restrict__ tab) {
+    const int64_t a = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
+    if (a >= rows) return;
+    long long* row = tab + SC_ROW * a;
+    long long rs = 0;
+    for (int k = 0; k < 27; ++k) {
+        const long long v = row[k];
+        rs += v;
+        row[k] = __double_as_longlong(pn_screen_dequant(v));
+    }
+    row[27] = __double_as_longlong(pn_screen_dequant(rs));
+}
+
+__global__ __launch_bounds__(PN_TPB) void k_sc_rhs(int64_t nn, const int32_t* __restrict__ idx, const double* __restrict__ tab, double T,
+                                                   double* __restrict__ b) {
+    const int64_t at = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
+    if (at >= nn) return;
+    const int a = idx[at];
+    if (a >= 0) b[at] = b[at] - T * tab[(int64_t)SC_ROW * a + 27];
+}
+
+// sum_o S_{i,o} x_{i+o} of an interior node with a row
+__device__ inline double sc_apply(const double* __restrict__ x, int64_t at, int n1, int64_t plane, const double* __restrict__ row) {
+    double acc = 0.0;
+    int k = 0;
+    for (int dz = -1; dz <= 1; ++dz)
+        for (int dy = -1; dy <= 1; ++dy)
+            for (int dx = -1; dx <= 1; ++dx) acc = acc + row[k++] * x[at + dz * plane + dy * n1 + dx];
+    return acc;
+}
+// one interior node of M x = b, c = x[at] and S6 the sum of its six neighbours: the residual, and the Jacobi weight (6/7) / diagonal
+__device__ inline double sc_residual_at(const double* __restrict__ x, int64_t at, int n1, int64_t plane, double c, double S6, double b,
+                                        const double* __restrict__ row) {
+    double m = S6 - 6.0 * c;
+    if (row) m = m - sc_apply(x, at, n1, plane, row);
+    return b - m;
+}
+template <int DIAG>
+__device__ inline double sc_weight(const double* __restrict__ row) {
+    if (!row) return 1.0 / 7.0;
+    return (6.0 / 7.0) / (6.0 + (DIAG == SC_DIAG_PLAIN ? row[13] : DIAG == SC_DIAG_ROW_SUM ? row[27] : 0.5 * row[27]));
+}
+__device__ inline const double* sc_row(const int32_t* __restrict__ idx, const double* __restrict__ tab, int64_t at) {
+    const int a = idx[at];
+    return a < 0 ? nullptr : tab + (int64_t)SC_ROW * a;
+}
+
+template <int DIAG>
+__global__ __launch_bounds__(PN_TPB) void k_mg_smooth_sc(int G, const double* __restrict__ x, const double* __restrict__ b, double* __restrict__ y,
+                                                         const int32_t* __restrict__ idx, const double* __restrict__ tab) {
+    int ix, iy, z0, z1;
+    if (!pn_column(G, &ix, &iy, &z0, &z1)) return;
+    const int n1 = G + 1;
+    const int64_t plane = (int64_t)n1 * n1;
+    int64_t at = pn_node(G, ix, iy, z0);
+    double lo = x[at - plane], c = x[at];
+    for (int iz = z0; iz < z1; ++iz, at += plane) {
+        const double hi = x[at + plane];
+        const double S = ((x[at - 1] + x[at + 1]) + (x[at - n1] + x[at + n1])) + (lo + hi);
+        const double* row = sc_row(idx, tab, at);
+        y[at] = c - sc_residual_at(x, at, n1, plane, c, S, b[at], row) * sc_weight<DIAG>(row);
+        lo = c;
+        c = hi;
+    }
+}
+
+// The other form of the smoother: k_mg_smooth writes every node of y as if S were zero, then this pass, a thread per row, writes the
+// nodes that have a row again, from the same old iterate x.  node_of[row] = the row's node; a row at a boundary node is skipped.
+template <int DIAG>
+__global__ __launch_bounds__(PN_TPB) void k_sc_smooth_rows(int64_t rows, const int32_t* __restrict__ node_of, int G, const double* __restrict__ x,
+                                                           const double* __restrict__ b, double* __restrict__ y, const double* __restrict__ tab) {
+    const int64_t a = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
+    if (a >= rows) return;
+    const int n1 = G + 1;
+    const int64_t plane = (int64_t)n1 * n1, at = node_of[a];
+    const int ix = (int)(at % n1), iy = (int)(at / n1 % n1), iz = (int)(at / plane);
+    if (ix < 1 || ix >= G || iy < 1 || iy >= G || iz < 1 || iz >= G) return;
+    const double* row = tab + SC_ROW * a;
+    const double c = x[at];
+    y[at] = c - sc_residual_at(x, at, n1, plane, c, pn_nbr_sum(x, at, n1, plane), b[at], row) * sc_weight<DIAG>(row);
+}
+
+// k_mg_residual for M: r = b - M x; with out == NULL only the squared norm, one partial per workgroup
+__global__ __launch_bounds__(PN_TPB) void k_mg_residual_sc(int G, const double* __restrict__ x, const double* __restrict__ b, double* __restrict__ out,
+                                                           double* __restrict__ part, const int32_t* __restrict__ idx, const double* __restrict__ tab) {
+    __shared__ double s_part[PN_WAVES];
+    int ix, iy, z0, z1;
+    double acc = 0.0;
+    if (pn_column(G, &ix, &iy, &z0, &z1)) {
+        const int n1 = G + 1;
+        const int64_t plane = (int64_t)n1 * n1;
+        int64_t at = pn_node(G, ix, iy, z0);
+        double lo = x[at - plane], c = x[at];
+        for (int iz = z0; iz < z1; ++iz, at += plane) {
+            const double hi = x[at + plane];
+            const double S = ((x[at - 1] + x[at + 1]) + (x[at - n1] + x[at + n1])) + (lo + hi);
+            const double r = sc_residual_at(x, at, n1, plane, c, S, b[at], sc_row(idx, tab, at));
+            if (out) out[at] = r;
+            acc += r * r;
+            lo = c;
+            c = hi;
+        }
+    }
+    if (!part) return;
+    const double t = wg_sum<PN_WAVES>(acc, s_part, threadIdx.y * 64 + threadIdx.x);
+    if (threadIdx.x == 0 && threadIdx.y == 0) part[((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = t;
+}
+
+template <int DIAG>
+__device__ inline void sc_coarse_smooth(int G, const double* x, double* y, const double* b, const int32_t* idx, const double* tab) {
+    const int n1 = G + 1;
+    const int64_t plane = (int64_t)n1 * n1;
+    pn_each_interior(G, [&](int64_t at, int, int, int) {
+        const double* row = sc_row(idx, tab, at);
+        y[at] = x[at] - sc_residual_at(x, at, n1, plane, x[at], pn_nbr_sum(x, at, n1, plane), b[at], row) * sc_weight<DIAG>(row);
+    });
+}
+
+// k_mg_coarse for M: one V(2,2) cycle over the levels top .. 1 by ONE workgroup
+template <int DIAG>
+__global__ __launch_bounds__(PN_COARSE_TPB) void k_mg_coarse_sc(PnLevels L, ScLevels Sc, int top) {
+    for (int l = top; l >= 2; --l) {
+        const int G = 1 << l, n1 = G + 1;
+        const int64_t plane = (int64_t)n1 * n1;
+        double *x = L.x[l], *t = L.t[l], *bc = L.b[l - 1], *xc = L.x[l - 1];
+        const double* b = L.b[l];
+        const int32_t* idx = Sc.idx[l];
+        const double* tab = Sc.tab[l];
+        sc_coarse_smooth<DIAG>(G, x, t, b, idx, tab);
+        sc_coarse_smooth<DIAG>(G, t, x, b, idx, tab);
+        pn_each_interior(G, [&](int64_t at, int, int, int) {
+            t[at] = sc_residual_at(x, at, n1, plane, x[at], pn_nbr_sum(x, at, n1, plane), b[at], sc_row(idx, tab, at));
+        });
+        pn_each_interior(G / 2, [&](int64_t at, int ix, int iy, int iz) { bc[at] = pn_restrict_at(t, G / 2, ix, iy, iz); xc[at] = 0.0; });
+    }
+    if (threadIdx.x == 0) {                                                 // level 1: one unknown, its neighbours are boundary nodes
+        const int64_t at = pn_node(2, 1, 1, 1);
+        const double* row = sc_row(Sc.idx[1], Sc.tab[1], at);
+        L.x[1][at] = L.b[1][at] / -(6.0 + (row ? row[13] : 0.0));
+    }
+    __syncthreads();
+    for (int l = 2; l <= top; ++l) {
+        const int G = 1 << l;
+        double* x = L.x[l];
+        const double* e = L.x[l - 1];
+        pn_each_interior(G, [&](int64_t at, int ix, int iy, int iz) { x[at] += pn_prolong_at(e, G, ix, iy, iz); });
+        sc_coarse_smooth<DIAG>(G, x, L.t[l], L.b[l], Sc.idx[l], Sc.tab[l]);
+        sc_coarse_smooth<DIAG>(G, L.t[l], x, L.b[l], Sc.idx[l], Sc.tab[l]);
+    }
+}
+
 // ------------------------------------------------------------------ rule 9 ----
 __global__ __launch_bounds__(PN_TPB) void k_pn_iso(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm, PnGrid g,
                                                    const double* __restrict__ chi, double* __restrict__ part) {
@@ -638,6 +939,14 @@ struct PnRun {
             k_pn_scan_add<<<dim3((unsigned)(nb / PN_TPB + 1)), dim3(PN_TPB), 0, s>>>(local.as<int32_t>(), rbase.as<int32_t>(), nb, rows, base.as<int32_t>());
         }
     } ve, fa;
+    // rules 19-23 (mvs_poisson_reconstruct_screened): absent for the other calls
+    const mvs_poisson_screen_params* sp = nullptr;
+    mvs_poisson_screen_info* sinfo = nullptr;
+    int diag = SC_DIAG_HALF_ROW_SUM;      // another one through mvs_test_poisson_screened only
+    Scratch sc_flag, sc_idx[PN_MAX_D + 1], sc_tab[PN_MAX_D + 1], sc_node[PN_MAX_D + 1];   // sc_node[l][row] = the row's node
+    ScLevels Sc{};
+    int64_t sc_rows[PN_MAX_D + 1] = {};   // nodes with a stencil row, per level
+    Scan sn;
     PnLevels L{};
     double iso = 0.0;
     int64_t edge_items = 0, face_items = 0;
@@ -889,9 +1198,161 @@ struct PnRun {
         return MVS_OK;
     }
 
+    // rule 19: occupied(D), whether or not rule 3 had a choice
+    int occupied_at(int D, int64_t* out) {
+        int rc;
+        PnOcc q{};
+        q.dmin = q.dmax = D;
+        q.cs[D] = side / (double)(1 << D);
+        const int64_t w = ((int64_t)1 << (3 * D)) / 32;
+        q.word0[D] = 0; q.word0[D + 1] = w;
+        for (int a = 0; a < 3; ++a) q.o[a] = g.o[a];
+        Scratch bits, occ;
+        unsigned long long hocc[PN_MAX_D + 1];
+        if ((rc = bits.alloc(sizeof(unsigned) * (size_t)w, s)) || (rc = occ.alloc(sizeof hocc, s))) return rc;
+        HIPCHK(hipMemsetAsync(bits.p, 0, sizeof(unsigned) * (size_t)w, s));
+        HIPCHK(hipMemsetAsync(occ.p, 0, sizeof hocc, s));
+        k_pn_occupy<<<dim3((unsigned)((n + PN_TPB - 1) / PN_TPB)), dim3(PN_TPB), 0, s>>>(n, pts, nrm, q, bits.as<unsigned>());
+        k_pn_popcount<<<dim3((unsigned)((w + PN_TPB - 1) / PN_TPB)), dim3(PN_TPB), 0, s>>>(q, bits.as<unsigned>(), occ.as<unsigned long long>());
+        HIPCHK(hipGetLastError());
+        if ((rc = fetch(hocc, occ.p, sizeof hocc))) return rc;
+        *out = (int64_t)hocc[D];
+        return MVS_OK;
+    }
+
+    // rule 20 on the finest level, and the rows of every level below from the level above; dense (may be NULL): [nn][27] int64 on the
+    // device, the sums of the finest level
+    int stencils(double lambda, long long* dense) {
+        int rc;
+        const int D = info.depth;
+        const dim3 pgrid((unsigned)((n + PN_TPB - 1) / PN_TPB));
+        if ((rc = sc_flag.alloc((size_t)nn, s)) || (rc = sn.alloc((size_t)((nn + PN_TPB - 1) / PN_TPB), s))) return rc;
+        for (int l = D; l >= 1; --l) {
+            const int G = 1 << l;
+            const int64_t nl = (int64_t)(G + 1) * (G + 1) * (G + 1), nb = (nl + PN_TPB - 1) / PN_TPB;
+            if ((rc = sc_idx[l].alloc(4 * (size_t)nl, s))) return rc;
+            if (l == D) {
+                HIPCHK(hipMemsetAsync(sc_flag.p, 0, (size_t)nl, s));
+                k_sc_flag<<<pgrid, dim3(PN_TPB), 0, s>>>(n, pts, nrm, g, sc_flag.as<uint8_t>());
+            } else {
+                k_sc_flag_coarse<<<dim3((unsigned)nb), dim3(PN_TPB), 0, s>>>(G, sc_idx[l + 1].as<int32_t>(), sc_flag.as<uint8_t>());
+            }
+            k_sc_count<<<dim3((unsigned)nb), dim3(PN_TPB), 0, s>>>(nl, sc_flag.as<uint8_t>(), sn.cnt.as<int32_t>());
+            sn.run((int)nb, s);
+            HIPCHK(hipGetLastError());
+            int32_t rows = 0;                                                 // base[nb]: all flagged nodes
+            if ((rc = fetch(&rows, sn.base.as<int32_t>() + nb, 4))) return rc;
+            sc_rows[l] = rows;
+            if ((rc = sc_tab[l].alloc(8 * (size_t)SC_ROW * (size_t)rows, s)) || (rc = sc_node[l].alloc(4 * (size_t)rows, s))) return rc;
+            k_sc_number<<<dim3((unsigned)nb), dim3(PN_TPB), 0, s>>>(nl, sc_flag.as<uint8_t>(), sn.base.as<int32_t>(), sc_idx[l].as<int32_t>(),
+                                                                   sc_node[l].as<int32_t>());
+            if (l == D) {
+                HIPCHK(hipMemsetAsync(sc_tab[l].p, 0, 8 * (size_t)SC_ROW * (size_t)rows, s));
+                k_sc_splat<<<pgrid, dim3(PN_TPB), 0, s>>>(n, pts, nrm, g, lambda, sc_idx[l].as<int32_t>(), sc_tab[l].as<unsigned long long>());
+                if (dense)
+                    k_sc_dense<<<dim3((unsigned)((27 * nl + PN_TPB - 1) / PN_TPB)), dim3(PN_TPB), 0, s>>>(nl, sc_idx[l].as<int32_t>(), sc_tab[l].as<long long>(), dense);
+                if (rows > 0) k_sc_convert<<<dim3((unsigned)((rows + PN_TPB - 1) / PN_TPB)), dim3(PN_TPB), 0, s>>>(rows, sc_tab[l].as<long long>());
+            } else if (rows > 0) {
+                k_sc_coarsen<<<dim3((unsigned)((rows + PN_TPB - 1) / PN_TPB)), dim3(PN_TPB), 0, s>>>(rows, sc_node[l].as<int32_t>(), G, sc_idx[l + 1].as<int32_t>(),
+                                                                                                    sc_tab[l + 1].as<double>(), sc_tab[l].as<double>());
+            }
+            HIPCHK(hipGetLastError());
+            Sc.idx[l] = sc_idx[l].as<int32_t>();
+            Sc.tab[l] = sc_tab[l].as<double>();
+        }
+        return MVS_OK;
+    }
+
+    // rules 19-21, after rule 9: sinfo, the stencils and f in the place of b.  alpha = 0 stops after rule 19.
+    int screen_setup(long long* dense) {
+        int rc;
+        std::memset(sinfo, 0, sizeof *sinfo);
+        sinfo->target = sinfo->iso_unscreened = iso;
+        if ((rc = occupied_at(info.depth, &sinfo->occupied))) return rc;
+        if (!(sp->alpha > 0.0)) return MVS_OK;
+        sinfo->lambda = pn_screen_lambda(sp->alpha, info.n_used, sinfo->occupied);
+        if ((rc = stencils(sinfo->lambda, dense))) return rc;
+        sinfo->active_nodes = sc_rows[info.depth];
+        k_sc_rhs<<<dim3((unsigned)((nn + PN_TPB - 1) / PN_TPB)), dim3(PN_TPB), 0, s>>>(nn, Sc.idx[info.depth], Sc.tab[info.depth], sinfo->target, rhs.as<double>());
+        HIPCHK(hipGetLastError());
+        return MVS_OK;
+    }
+
+    int norm2_sc(const double* x, double* out) {                             // |f - M x|^2 of the finest level, on the host
+        const int D = info.depth;
+        const dim3 gr = pn_column_grid(g.G);
+        const int np = (int)(gr.x * gr.y * gr.z);
+        k_mg_residual_sc<<<gr, dim3(64, 4), 0, s>>>(g.G, x, L.b[D], nullptr, red.as<double>() + 1, Sc.idx[D], Sc.tab[D]);
+        k_pn_fold<<<dim3(1), dim3(PN_TPB), 0, s>>>(red.as<double>() + 1, np, red.as<double>());
+        HIPCHK(hipGetLastError());
+        return fetch(out, red.p, sizeof(double));
+    }
+
+    template <int DIAG>
+    void smooth_sc(int l, const double* x, double* y) {
+        const int G = 1 << l;
+        if (SC_SMOOTH_BY_ROWS) {
+            k_mg_smooth<<<pn_column_grid(G), dim3(64, 4), 0, s>>>(G, x, L.b[l], y);
+            if (sc_rows[l] > 0)
+                k_sc_smooth_rows<DIAG><<<dim3((unsigned)((sc_rows[l] + PN_TPB - 1) / PN_TPB)), dim3(PN_TPB), 0, s>>>(sc_rows[l], sc_node[l].as<int32_t>(), G, x,
+                                                                                                                    L.b[l], y, Sc.tab[l]);
+        } else {
+            k_mg_smooth_sc<DIAG><<<pn_column_grid(G), dim3(64, 4), 0, s>>>(G, x, L.b[l], y, Sc.idx[l], Sc.tab[l]);
+        }
+    }
+    void smooth2_sc(int l) {
+        if (diag == SC_DIAG_PLAIN) { smooth_sc<SC_DIAG_PLAIN>(l, L.x[l], L.t[l]); smooth_sc<SC_DIAG_PLAIN>(l, L.t[l], L.x[l]); }
+        else if (diag == SC_DIAG_ROW_SUM) { smooth_sc<SC_DIAG_ROW_SUM>(l, L.x[l], L.t[l]); smooth_sc<SC_DIAG_ROW_SUM>(l, L.t[l], L.x[l]); }
+        else { smooth_sc<SC_DIAG_HALF_ROW_SUM>(l, L.x[l], L.t[l]); smooth_sc<SC_DIAG_HALF_ROW_SUM>(l, L.t[l], L.x[l]); }
+    }
+
+    int vcycle_sc() {                                                        // vcycle for M
+        const int D = info.depth;
+        for (int l = D; l > PN_COARSE; --l) {
+            const int G = 1 << l, Gc = G / 2;
+            smooth2_sc(l);
+            k_mg_residual_sc<<<pn_column_grid(G), dim3(64, 4), 0, s>>>(G, L.x[l], L.b[l], L.t[l], nullptr, Sc.idx[l], Sc.tab[l]);
+            k_mg_restrict<<<dim3((unsigned)((Gc - 1 + 63) / 64), (unsigned)((Gc - 1 + 3) / 4), (unsigned)(Gc - 1)), dim3(64, 4), 0, s>>>(Gc, L.t[l], L.b[l - 1]);
+            HIPCHK(hipMemsetAsync(L.x[l - 1], 0, 8 * (size_t)(Gc + 1) * (Gc + 1) * (Gc + 1), s));
+        }
+        const int top = D < PN_COARSE ? D : PN_COARSE;
+        if (diag == SC_DIAG_PLAIN) k_mg_coarse_sc<SC_DIAG_PLAIN><<<dim3(1), dim3(PN_COARSE_TPB), 0, s>>>(L, Sc, top);
+        else if (diag == SC_DIAG_ROW_SUM) k_mg_coarse_sc<SC_DIAG_ROW_SUM><<<dim3(1), dim3(PN_COARSE_TPB), 0, s>>>(L, Sc, top);
+        else k_mg_coarse_sc<SC_DIAG_HALF_ROW_SUM><<<dim3(1), dim3(PN_COARSE_TPB), 0, s>>>(L, Sc, top);
+        for (int l = PN_COARSE + 1; l <= D; ++l) {
+            const int G = 1 << l;
+            k_mg_prolong<<<dim3((unsigned)((G - 1 + 63) / 64), (unsigned)((G - 1 + 3) / 4), (unsigned)(G - 1)), dim3(64, 4), 0, s>>>(G, L.x[l - 1], L.x[l]);
+            smooth2_sc(l);
+        }
+        HIPCHK(hipGetLastError());
+        return MVS_OK;
+    }
+
+    // rule 22: from chi0 in L.x[D], with f in L.b[D]
+    int screen_solve(const char* fn) {
+        int rc;
+        const int D = info.depth;
+        double f2 = 0.0, r2 = 0.0;
+        HIPCHK(hipMemsetAsync(L.t[D], 0, 8 * (size_t)nn, s));                 // M 0 = 0: the residual of zero is f
+        if ((rc = norm2_sc(L.t[D], &f2))) return rc;
+        if (!(f2 > 0.0)) return MVS_OK;
+        for (int c = 1; c <= p.max_cycles; ++c) {
+            if ((rc = vcycle_sc()) || (rc = norm2_sc(L.x[D], &r2))) return rc;
+            sinfo->cycles = c;
+            sinfo->rel_residual = std::sqrt(r2) / std::sqrt(f2);
+            if (std::sqrt(r2) <= p.solve_tol * std::sqrt(f2)) return MVS_OK;
+        }
+        mvs_set_error("%s: screened solve: relative residual %.3e after %d cycles, above solve_tol %.3e", fn, sinfo->rel_residual, sinfo->cycles, p.solve_tol);
+        return MVS_E_SOLVER;
+    }
+
     int counts(const char* fn) {
         int rc;
         if ((rc = grid(fn)) || (dp && (rc = density())) || (rc = field(fn)) || (rc = iso_value())) return rc;
+        if (sp) {                                                             // rules 19-23
+            if ((rc = screen_setup(nullptr))) return rc;
+            if (sp->alpha > 0.0 && ((rc = screen_solve(fn)) || (rc = iso_value()))) return rc;
+        }
         return count();
     }
 };
@@ -904,6 +1365,13 @@ int check_pn_density(const char* fn, int64_t n, const mvs_poisson_density_params
     if (dp->density_drop < 0 || dp->density_drop > 8) return bad(fn, "need density_drop in [0, 8]");
     if (dp->flags & ~MVS_POISSON_WEIGHT_NORMALS) return bad(fn, "flags holds a bit other than MVS_POISSON_WEIGHT_NORMALS");
     if ((dp->flags & MVS_POISSON_WEIGHT_NORMALS) && n > (1ll << 22)) return bad(fn, "more than 2^22 points with MVS_POISSON_WEIGHT_NORMALS");
+    return MVS_OK;
+}
+
+int check_pn_screen(const char* fn, const mvs_poisson_screen_params* sp, const void* sinfo) {
+    if (!sp || !sinfo) return bad(fn, "sparams or sinfo is NULL");
+    if (!std::isfinite(sp->alpha) || sp->alpha < 0.0 || sp->alpha > 64.0) return bad(fn, "need alpha in [0, 64]");
+    if (sp->reserved != 0) return bad(fn, "sparams.reserved is not 0");
     return MVS_OK;
 }
 
@@ -957,15 +1425,18 @@ int mesh_trim_dev(int64_t V, const double* vertices, const double* normals, int6
     return MVS_OK;
 }
 
-// mvs_poisson_reconstruct_density_dev with outputs that size themselves, for mvs_processor_poisson_density; as poisson_blocks
+// mvs_poisson_reconstruct_density_dev, or with sp mvs_poisson_reconstruct_screened_dev, with outputs that size themselves, for
+// mvs_processor_poisson_density and mvs_processor_poisson_screened; as poisson_blocks
 int poisson_density_blocks(const char* fn, int64_t n, const double* points_dev, const double* normals_dev, const mvs_poisson_params* p,
                            const mvs_poisson_density_params* dp, mvs_poisson_info* info, mvs_poisson_density_info* dinfo, Scratch* vertices,
-                           Scratch* density, Scratch* faces) {
+                           Scratch* density, Scratch* faces, const mvs_poisson_screen_params* sp, mvs_poisson_screen_info* sinfo) {
     int rc = check_pn(fn, n, points_dev, normals_dev, p, info, nullptr, 0, nullptr, 0);
-    if (rc || (rc = check_pn_density(fn, n, dp, dinfo))) return rc;
+    if (rc || (rc = check_pn_density(fn, n, dp, dinfo)) || (sp && (rc = check_pn_screen(fn, sp, sinfo)))) return rc;
     PnRun run(*p, *info, n, points_dev, normals_dev, nullptr);
     run.dp = dp;
     run.dinfo = dinfo;
+    run.sp = sp;
+    run.sinfo = sinfo;
     if ((rc = run.counts(fn))) return rc;
     if ((rc = vertices->alloc(24 * (size_t)info->n_vertices)) || (rc = density->alloc(8 * (size_t)info->n_vertices)) ||
         (rc = faces->alloc(12 * (size_t)info->n_faces))) return rc;
@@ -1087,6 +1558,102 @@ int mvs_poisson_reconstruct_density(int64_t n, const double* points, const doubl
     }
     if ((rc = down(vertices, dv, 3 * V))) return rc;
     return down(faces, df, 3 * F);
+}
+
+// ------------------------------------------------------------------ rules 19-23 ----
+void mvs_poisson_screen_default_params(mvs_poisson_screen_params* p) {
+    if (!p) return;
+    p->alpha = 4.0; p->reserved = 0;
+}
+
+int mvs_poisson_reconstruct_screened_dev(int64_t n, const double* points_dev, const double* normals_dev, const mvs_poisson_params* p,
+                                         const mvs_poisson_density_params* dparams, const mvs_poisson_screen_params* sparams,
+                                         mvs_poisson_info* info, mvs_poisson_density_info* dinfo, mvs_poisson_screen_info* sinfo,
+                                         double* vertices_dev, double* vertex_density_dev, int64_t vertex_capacity, int32_t* faces_dev,
+                                         int64_t face_capacity, void* hip_stream) {
+    MVS_TRACE();
+    int rc = check_pn(__func__, n, points_dev, normals_dev, p, info, vertices_dev, vertex_capacity, faces_dev, face_capacity);
+    if (rc || (rc = check_pn_density(__func__, n, dparams, dinfo)) || (rc = check_pn_screen(__func__, sparams, sinfo))) return rc;
+    if ((rc = need_device())) return rc;
+    PnRun run(*p, *info, n, points_dev, normals_dev, (hipStream_t)hip_stream);
+    run.dp = dparams;
+    run.dinfo = dinfo;
+    run.sp = sparams;
+    run.sinfo = sinfo;
+    std::memset(dinfo, 0, sizeof *dinfo);
+    std::memset(sinfo, 0, sizeof *sinfo);
+    if ((rc = run.counts(__func__))) return rc;
+    if (info->n_vertices > vertex_capacity || info->n_faces > face_capacity) return too_small(__func__);
+    if ((rc = run.scatter(vertices_dev, faces_dev))) return rc;
+    return run.vertex_density(vertices_dev, vertex_density_dev);
+}
+
+int mvs_poisson_reconstruct_screened(int64_t n, const double* points, const double* normals, const mvs_poisson_params* p,
+                                     const mvs_poisson_density_params* dparams, const mvs_poisson_screen_params* sparams, mvs_poisson_info* info,
+                                     mvs_poisson_density_info* dinfo, mvs_poisson_screen_info* sinfo, double* vertices, double* vertex_density,
+                                     int64_t vertex_capacity, int32_t* faces, int64_t face_capacity) {
+    MVS_TRACE();
+    int rc = check_pn(__func__, n, points, normals, p, info, vertices, vertex_capacity, faces, face_capacity);
+    if (rc || (rc = check_pn_density(__func__, n, dparams, dinfo)) || (rc = check_pn_screen(__func__, sparams, sinfo))) return rc;
+    if ((rc = need_device())) return rc;
+    Scratch dp, dn, dv, dd, df;
+    if ((rc = up(dp, points, 3 * (size_t)n)) || (rc = up(dn, normals, 3 * (size_t)n))) return rc;
+    PnRun run(*p, *info, n, dp.as<double>(), dn.as<double>(), nullptr);
+    run.dp = dparams;
+    run.dinfo = dinfo;
+    run.sp = sparams;
+    run.sinfo = sinfo;
+    std::memset(dinfo, 0, sizeof *dinfo);
+    std::memset(sinfo, 0, sizeof *sinfo);
+    if ((rc = run.counts(__func__))) return rc;
+    if (info->n_vertices > vertex_capacity || info->n_faces > face_capacity) return too_small(__func__);
+    const size_t V = (size_t)info->n_vertices, F = (size_t)info->n_faces;
+    if ((rc = dv.alloc(24 * V)) || (rc = df.alloc(12 * F)) || (rc = run.scatter(dv.as<double>(), df.as<int32_t>()))) return rc;
+    if (vertex_density) {
+        if ((rc = dd.alloc(8 * V)) || (rc = run.vertex_density(dv.as<double>(), dd.as<double>())) || (rc = down(vertex_density, dd, V))) return rc;
+    }
+    if ((rc = down(vertices, dv, 3 * V))) return rc;
+    return down(faces, df, 3 * F);
+}
+
+int mvs_test_poisson_screened(int64_t n, const double* points, const double* normals, const mvs_poisson_params* p,
+                              const mvs_poisson_density_params* dparams, const mvs_poisson_screen_params* sparams, mvs_poisson_info* info,
+                              mvs_poisson_density_info* dinfo, mvs_poisson_screen_info* sinfo, int64_t* stencil, double* f, double* chi0, double* chi,
+                              int64_t node_capacity, int32_t diagonal) {
+    MVS_TRACE();
+    int rc = check_pn(__func__, n, points, normals, p, info, f, node_capacity, chi, node_capacity);
+    if (rc || (rc = check_pn_density(__func__, n, dparams, dinfo)) || (rc = check_pn_screen(__func__, sparams, sinfo))) return rc;
+    if (!stencil || !chi0) return bad(__func__, "stencil or chi0 is NULL");
+    if (diagonal < 0 || diagonal > 2) return bad(__func__, "diagonal is not 0, 1 or 2");
+    if ((rc = need_device())) return rc;
+    Scratch dp, dn, dense;
+    if ((rc = up(dp, points, 3 * (size_t)n)) || (rc = up(dn, normals, 3 * (size_t)n))) return rc;
+    PnRun run(*p, *info, n, dp.as<double>(), dn.as<double>(), nullptr);
+    run.dp = dparams;
+    run.dinfo = dinfo;
+    run.sp = sparams;
+    run.sinfo = sinfo;
+    run.diag = diagonal;
+    std::memset(dinfo, 0, sizeof *dinfo);
+    std::memset(sinfo, 0, sizeof *sinfo);
+    if ((rc = run.grid(__func__))) return rc;
+    if (run.nn > node_capacity) return bad(__func__, "node_capacity is below (2^depth + 1)^3 (info holds the depth)");
+    const size_t nn = (size_t)run.nn;
+    if ((rc = run.density()) || (rc = run.field(__func__)) || (rc = run.iso_value())) return rc;
+    HIPCHK(hipMemcpy(chi0, run.L.x[info->depth], 8 * nn, hipMemcpyDeviceToHost));
+    if ((rc = dense.alloc(8 * 27 * nn))) return rc;
+    HIPCHK(hipMemset(dense.p, 0, 8 * 27 * nn));                              // alpha = 0: no stencil
+    if ((rc = run.screen_setup(dense.as<long long>()))) return rc;
+    HIPCHK(hipMemcpy(stencil, dense.p, 8 * 27 * nn, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(f, run.rhs.p, 8 * nn, hipMemcpyDeviceToHost));
+    int src = MVS_OK;
+    if (sparams->alpha > 0.0) {                                              // MVS_E_SOLVER still hands out the field it reached
+        src = run.screen_solve(__func__);
+        if (src && src != MVS_E_SOLVER) return src;
+        if (!src && (rc = run.iso_value())) return rc;
+    }
+    HIPCHK(hipMemcpy(chi, run.L.x[info->depth], 8 * nn, hipMemcpyDeviceToHost));
+    return src;
 }
 
 int mvs_mesh_trim_by_value_dev(int64_t V, const double* vertices_dev, const double* normals_dev, int64_t F, const int32_t* faces_dev,

@@ -76,6 +76,25 @@ __host__ __device__ inline double pn_gain(double rho_mean, double rho, double ma
     return s > max_gain ? max_gain : s;
 }
 
+// rule 19: the screening weight of every used point: alpha over the mean number of used points per occupied cell, at least 1
+__host__ __device__ inline double pn_screen_lambda(double alpha, long long N, long long occ) {
+    const double r = (double)N / (double)occ;
+    return alpha / (r > 1.0 ? r : 1.0);
+}
+
+// rule 20: the 27 offsets {-1, 0, 1}^3 of a stencil in the order (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1)
+__host__ __device__ inline int pn_screen_offset(int dx, int dy, int dz) { return (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1); }
+
+// rule 20: the contribution of the corner pair c1 <= c2 (corner order bx + 2 by + 4 bz) of a point with the weights w of rule 5, in
+// units of 2^-30: it goes to the entry (node of c1, offset *o12 = c2 - c1) and, when c1 != c2, to (node of c2, offset *o21 = c1 - c2)
+__host__ __device__ inline long long pn_screen_pair(double lambda, const double w[8], int c1, int c2, int* o12, int* o21) {
+    const int dx = (c2 & 1) - (c1 & 1), dy = (c2 >> 1 & 1) - (c1 >> 1 & 1), dz = (c2 >> 2 & 1) - (c1 >> 2 & 1);
+    *o12 = pn_screen_offset(dx, dy, dz);
+    *o21 = pn_screen_offset(-dx, -dy, -dz);
+    return llrint(((lambda * w[c1]) * w[c2]) * 1073741824.0);
+}
+__host__ __device__ inline double pn_screen_dequant(long long s) { return (double)s * (1.0 / 1073741824.0); }
+
 // rule 18: does a value pass the threshold?  NaN does not
 __host__ __device__ inline bool pn_trim_pass(double value, double threshold) { return value >= threshold; }
 

@@ -31,10 +31,12 @@ int point_sample_vectors(const char* fn, int32_t n_seq, const int32_t* cam_off, 
 // counts.  Validates like mvs_poisson_reconstruct, reporting under the name fn; the caller has a device.  Default stream.
 int poisson_blocks(const char* fn, int64_t n, const double* points_dev, const double* normals_dev, const mvs_poisson_params* p,
                    mvs_poisson_info* info, Scratch* vertices, Scratch* faces);
-// the same for mvs_poisson_reconstruct_density_dev: density receives d_v of rule 17 per vertex
+// the same for mvs_poisson_reconstruct_density_dev: density receives d_v of rule 17 per vertex; with sp (and sinfo) for
+// mvs_poisson_reconstruct_screened_dev
 int poisson_density_blocks(const char* fn, int64_t n, const double* points_dev, const double* normals_dev, const mvs_poisson_params* p,
                            const mvs_poisson_density_params* dp, mvs_poisson_info* info, mvs_poisson_density_info* dinfo, Scratch* vertices,
-                           Scratch* density, Scratch* faces);
+                           Scratch* density, Scratch* faces, const mvs_poisson_screen_params* sp = nullptr,
+                           mvs_poisson_screen_info* sinfo = nullptr);
 // mvs_mesh_trim_by_value_dev (poisson.hip, rule 18) with arguments the caller has validated.  Synchronises s.
 int mesh_trim_dev(int64_t V, const double* vertices, const double* normals, int64_t F, const int32_t* faces, const double* values, double thr,
                   double* vertices_out, double* normals_out, int32_t* faces_out, int64_t* V_out, int64_t* F_out, hipStream_t s);

@@ -557,10 +557,11 @@ def _poisson_info(info: L.CPoissonInfo) -> dict:
                 n_vertices=info.n_vertices, n_faces=info.n_faces, depth=info.depth, cycles=info.cycles)
 
 
-def _run_poisson(points, normals, prm, dprm, stream, capacity):
-    """the call behind ``RunPoisson`` (``dprm`` None: mvs_poisson_reconstruct) and ``RunPoissonDensity`` (mvs_poisson_reconstruct_density),
-    host or device form -> (vertices, faces, vertex density or None, info struct, density info struct or None)"""
-    name = "mvs_poisson_reconstruct" if dprm is None else "mvs_poisson_reconstruct_density"
+def _run_poisson(points, normals, prm, dprm, stream, capacity, sprm=None):
+    """the call behind ``RunPoisson`` (``dprm`` None: mvs_poisson_reconstruct), ``RunPoissonDensity`` (mvs_poisson_reconstruct_density) and
+    ``RunPoissonScreened`` (``sprm`` given: mvs_poisson_reconstruct_screened), host or device form
+    -> (vertices, faces, vertex density or None, info struct, density info struct or None[, screen info struct])"""
+    name = "mvs_poisson_reconstruct" if dprm is None else "mvs_poisson_reconstruct_density" if sprm is None else "mvs_poisson_reconstruct_screened"
     dev = _is_dev(points)
     if dev != _is_dev(normals):
         raise L.MvsError(-1, "points and normals must both be tensors on the GPU or both arrays")
@@ -585,12 +586,16 @@ def _run_poisson(points, normals, prm, dprm, stream, capacity):
         dmax = max(0, min(int(prm.depth_max), 9))
         capacity = (12 * 4 ** dmax, 24 * 4 ** dmax)
     info, dinfo = L.CPoissonInfo(), None if dprm is None else L.CPoissonDensityInfo()
+    sinfo = None if sprm is None else L.CPoissonScreenInfo()
     with order:
         def call(vcap, fcap):
             v, f = _out_like(points, (max(1, vcap), 3), "float64"), _out_like(points, (max(1, fcap), 3), "int32")
             if dprm is None:
                 return fn(n, pp, pn, C.byref(prm), C.byref(info), L.ptr(v), vcap, L.ptr(f), fcap, *tail), v, f, None
             d = _out_like(points, (max(1, vcap),), "float64")
+            if sprm is not None:
+                return fn(n, pp, pn, C.byref(prm), C.byref(dprm), C.byref(sprm), C.byref(info), C.byref(dinfo), C.byref(sinfo), L.ptr(v), L.ptr(d), vcap,
+                          L.ptr(f), fcap, *tail), v, f, d
             return fn(n, pp, pn, C.byref(prm), C.byref(dprm), C.byref(info), C.byref(dinfo), L.ptr(v), L.ptr(d), vcap, L.ptr(f), fcap, *tail), v, f, d
 
         vcap, fcap = int(capacity[0]), int(capacity[1])
@@ -599,7 +604,8 @@ def _run_poisson(points, normals, prm, dprm, stream, capacity):
             vcap, fcap = int(info.n_vertices), int(info.n_faces)
             rc, v, f, d = call(vcap, fcap)
     L.check(rc)
-    return v[:info.n_vertices], f[:info.n_faces], None if d is None else d[:info.n_vertices], info, dinfo
+    out = v[:info.n_vertices], f[:info.n_faces], None if d is None else d[:info.n_vertices], info, dinfo
+    return out if sprm is None else out + (sinfo,)
 
 
 def RunPoisson(points, normals, params: L.CPoissonParams | None = None, stream: int | None = None, capacity: tuple | None = None):
@@ -615,14 +621,18 @@ def RunPoisson(points, normals, params: L.CPoissonParams | None = None, stream: 
 
 
 def PoissonFiles(psr_npts, model_obj, params: L.CPoissonParams | None = None, dparams: L.CPoissonDensityParams | None = None,
-                 trim_ratio: float | None = None):
+                 trim_ratio: float | None = None, sparams: "L.CPoissonScreenParams | None" = None):
     """``mvs_processor_poisson``: ``psr_npts`` (Result/PSR.npts, what ``StitchPointSets`` wrote) -> ``model_obj`` (Result/Model.obj with
     `v`, `vn` and `f` lines, what ``CullPoissonModel`` reads).  -> (V, F) written.  With ``dparams`` (``poisson_density_params``) or
     ``trim_ratio`` the call is ``mvs_processor_poisson_density``: the normals weighted by the sampling density when ``dparams`` sets
-    WEIGHT_NORMALS, the mesh trimmed where its vertex density lies below ``trim_ratio`` times the mean point density."""
+    WEIGHT_NORMALS, the mesh trimmed where its vertex density lies below ``trim_ratio`` times the mean point density.  With ``sparams``
+    (``poisson_screen_params``) the call is ``mvs_processor_poisson_screened``: the field pulled to the iso value at every point."""
     prm = params if params is not None else poisson_params()
     V, F = C.c_int64(), C.c_int64()
-    if dparams is None and trim_ratio is None:
+    if sparams is not None:
+        L.check(L.lib().mvs_processor_poisson_screened(os.fsencode(psr_npts), C.byref(prm), C.byref(dparams) if dparams is not None else None,
+                                                       C.byref(sparams), float(trim_ratio or 0.0), os.fsencode(model_obj), C.byref(V), C.byref(F)))
+    elif dparams is None and trim_ratio is None:
         L.check(L.lib().mvs_processor_poisson(os.fsencode(psr_npts), C.byref(prm), os.fsencode(model_obj), C.byref(V), C.byref(F)))
     else:
         L.check(L.lib().mvs_processor_poisson_density(os.fsencode(psr_npts), C.byref(prm), C.byref(dparams) if dparams is not None else None,
@@ -650,6 +660,29 @@ def RunPoissonDensity(points, normals, params: L.CPoissonParams | None = None, d
     out = _poisson_info(info)
     out.update(mean_density=dinfo.mean_density, min_point_density=dinfo.min_point_density, max_point_density=dinfo.max_point_density,
                density_depth=dinfo.density_depth, n_clamped=dinfo.n_clamped)
+    return v, f, d, out
+
+
+def poisson_screen_params(**kw) -> L.CPoissonScreenParams:
+    """``mvs_poisson_screen_default_params`` (alpha 4) with the given fields replaced."""
+    return _params(L.CPoissonScreenParams, L.lib().mvs_poisson_screen_default_params, kw)
+
+
+def RunPoissonScreened(points, normals, params: L.CPoissonParams | None = None, dparams: L.CPoissonDensityParams | None = None,
+                       sparams: L.CPoissonScreenParams | None = None, stream: int | None = None, capacity: tuple | None = None):
+    """``mvs_poisson_reconstruct_screened`` (rules 19-23 of include/mvs.h, this library's definition): ``RunPoissonDensity`` followed by
+    a second solve that pulls the field to the iso value at every point with the weight ``sparams.alpha`` (4 by default; 0: the bytes of
+    ``RunPoissonDensity``).  Arguments as ``RunPoisson``.
+    -> (vertices [V, 3] float64, faces [F, 3] int32, density [V] float64, info dict: that of ``RunPoissonDensity`` plus target, lambda,
+    occupied, active_nodes, screen_cycles, screen_rel_residual, iso_unscreened)."""
+    v, f, d, info, dinfo, sinfo = _run_poisson(points, normals, params if params is not None else poisson_params(),
+                                               dparams if dparams is not None else poisson_density_params(), stream, capacity,
+                                               sparams if sparams is not None else poisson_screen_params())
+    out = _poisson_info(info)
+    out.update(mean_density=dinfo.mean_density, min_point_density=dinfo.min_point_density, max_point_density=dinfo.max_point_density,
+               density_depth=dinfo.density_depth, n_clamped=dinfo.n_clamped)
+    out.update({"target": sinfo.target, "lambda": sinfo.lambda_, "occupied": sinfo.occupied, "active_nodes": sinfo.active_nodes,
+                "screen_cycles": sinfo.cycles, "screen_rel_residual": sinfo.rel_residual, "iso_unscreened": sinfo.iso_unscreened})
     return v, f, d, out
 
 

@@ -357,7 +357,7 @@ int mvs_processor_point_sample(int32_t n_seq, const char* const* seq_dirs, const
 
 // PSR.npts -> Model.obj; dprm != NULL: through rules 14-17, and trimmed by rule 18 when trim_ratio > 0; sprm != NULL (with dprm): rules 19-23
 static int poisson_files(const char* fn, const char* psr_npts, const mvs_poisson_params& prm, const mvs_poisson_density_params* dprm, double trim_ratio,
-                         const char* model_obj, int64_t* V_out, int64_t* F_out, const mvs_poisson_screen_params* sprm = nullptr) {
+                         const char* model_obj, int64_t* V_out, int64_t* F_out, const mvs_poisson_screen_params* sprm) {
     int rc = need_device();
     if (rc) return rc;
     int64_t n = 0;
@@ -371,9 +371,9 @@ static int poisson_files(const char* fn, const char* psr_npts, const mvs_poisson
     mvs_poisson_density_info dinfo;
     mvs_poisson_screen_info sinfo;
     if ((rc = up(dp, hp.data(), (size_t)n * 3)) || (rc = up(dn, hn.data(), (size_t)n * 3))) return rc;
-    if (dprm) rc = poisson_density_blocks(fn, n, dp.as<double>(), dn.as<double>(), &prm, dprm, &info, &dinfo, &dv, &dd, &df, sprm, sprm ? &sinfo : nullptr);
-    else rc = poisson_blocks(fn, n, dp.as<double>(), dn.as<double>(), &prm, &info, &dv, &df);
-    if (rc) return rc;
+    const PnCall call{fn, sprm ? PN_SCREENED : dprm ? PN_DENSITY : PN_PLAIN, n, dp.as<double>(), dn.as<double>(), &prm, &info, dprm, dprm ? &dinfo : nullptr,
+                      sprm, sprm ? &sinfo : nullptr};
+    if ((rc = poisson_blocks(call, &dv, &dd, &df))) return rc;
     int64_t V = info.n_vertices, F = info.n_faces;
     const Scratch *mv = &dv, *mf = &df;
     if (dprm && trim_ratio > 0.0) {
@@ -398,7 +398,7 @@ int mvs_processor_poisson(const char* psr_npts, const mvs_poisson_params* params
     if (!psr_npts || !model_obj) return bad(__func__, "psr_npts / model_obj is NULL");
     mvs_poisson_params prm;
     if (params) prm = *params; else mvs_poisson_default_params(&prm);
-    return poisson_files(__func__, psr_npts, prm, nullptr, 0.0, model_obj, V_out, F_out);
+    return poisson_files(__func__, psr_npts, prm, nullptr, 0.0, model_obj, V_out, F_out, nullptr);
 }
 
 int mvs_processor_poisson_density(const char* psr_npts, const mvs_poisson_params* params, const mvs_poisson_density_params* dparams, double trim_ratio,
@@ -410,7 +410,7 @@ int mvs_processor_poisson_density(const char* psr_npts, const mvs_poisson_params
     mvs_poisson_density_params dprm;
     if (params) prm = *params; else mvs_poisson_default_params(&prm);
     if (dparams) dprm = *dparams; else mvs_poisson_density_default_params(&dprm);
-    return poisson_files(__func__, psr_npts, prm, &dprm, trim_ratio, model_obj, V_out, F_out);
+    return poisson_files(__func__, psr_npts, prm, &dprm, trim_ratio, model_obj, V_out, F_out, nullptr);
 }
 
 int mvs_processor_poisson_screened(const char* psr_npts, const mvs_poisson_params* params, const mvs_poisson_density_params* dparams,

@@ -8,11 +8,12 @@
 //                      rule 3 when depth_min < Dmax: one bitmap of cells per candidate depth, atomicOr, then a popcount
 //   k_pn_splat         rule 5: a thread per point, 24 int64 atomic adds into the three planar sum arrays
 //   k_pn_rhs           rule 6: a thread per node
-//   k_mg_smooth / k_mg_residual / k_mg_restrict / k_mg_prolong
+//   k_mg_smooth<Op> / k_mg_residual<Op> / k_mg_restrict / k_mg_prolong
 //                      rule 8, levels above 33^3: V(2,2) cycles, Jacobi damped by 6/7, full weighting (x 4: the stencil is unscaled),
 //                      trilinear prolongation.  Smoother and residual march along z with the column's three values in registers.
-//   k_mg_coarse        the levels of 33^3 and below, down to the single interior node of level 1 and back, in ONE workgroup
-//   k_mg_residual (out == NULL) / k_pn_fold
+//                      Op: the operator, MgPlain here (S - 6 x) or MgScreened<diagonal> for the second solve of the screened call
+//   k_mg_coarse<Op>    the levels of 33^3 and below, down to the single interior node of level 1 and back, in ONE workgroup
+//   k_mg_residual<Op> (out == NULL) / k_pn_fold
 //                      the true residual's squared norm: partials per workgroup, folded by one workgroup in a fixed order
 //   k_pn_iso           rule 9, the same two-step reduction
 //   k_pn_cubemask      rule 10: the inside bits of a cube's eight corners, one byte per cube
@@ -20,20 +21,24 @@
 //                      rules 11-12: two ordered compactions (wg_rank per workgroup of 256 items; k_pn_scan_rows / _totals / _add scan the
 //                      millions of counts in two levels).  The edge flags stay behind as a bitmap, 64 flags per word: a face finds the
 //                      number of a vertex as base[workgroup] + popcounts, no edge map is stored.
-// mvs_poisson_reconstruct_density adds the sampling density (rules 14-17), mvs_mesh_trim_by_value the trim (rule 18):
+// mvs_poisson_reconstruct_density adds the sampling density (rules 14-17; the trim of rule 18 is mesh_trim.hip):
 //   k_pn_density_splat rule 14: a thread per point, 8 int64 atomic adds into the node sums of the coarser density grid
 //   k_pn_point_density rule 15: rho_p per row; min, max and the int64 sum of the quantised densities per workgroup (order-free)
 //   k_pn_gain          rule 16: s_p per row and the rows cut at max_gain; k_pn_splat<true> is the splat of the scaled normals
 //   k_pn_vertex_density rule 17, over the vertex list the scatter wrote
-//   k_tr_face_mark / k_tr_vertex_count / CompactTail / k_tr_vertex_scatter / k_tr_face_scatter
-//                      rule 18: flags and plain byte marks, compact.hip's scan, two ordered scatters
-// mvs_poisson_reconstruct_screened adds the second, screened solve (rules 19-23): the k_sc_* and *_sc kernels, described where they stand.
-// Nothing but the integer atomics of the splats and the bitmap is unordered: two runs give the same bytes.
+// mvs_poisson_reconstruct_screened adds the second, screened solve (rules 19-23): the k_sc_* kernels build the stencil rows and the right
+// side, described where they stand; the solve is the multigrid above with MgScreened, its smoother on the launched levels
+// k_mg_smooth<MgPlain> followed by k_sc_smooth_rows over the rows.
+// The reductions fold through wg_fold (shuffles, then the waves in order).  Nothing but the integer atomics of the splats and the bitmap
+// is unordered: two runs give the same bytes (tests/test_gpu_poisson_bits.py holds a build to recorded ones).
+// The host side: PnCall (stitch.h) is the record of a call, whichever entry made it; PnRun its state on the device; reconstruct the device
+// form of every entry and reconstruct_host the host form; the test hooks of include/mvs_test.h drive PnRun step by step.
 #include "engine.h"
 #include "trace.h"
 #include "frontend_dev.h"
 #include "poisson_rules.h"
 #include "knobs.h"
+#include "stitch.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -47,46 +52,43 @@ constexpr int PN_COARSE = 5;             // levels up to this one (33^3 nodes) r
 constexpr int PN_COARSE_TPB = 1024;
 constexpr int PN_MAX_D = MVS_POISSON_MAX_DEPTH;
 
-// the sum of v over the workgroup (tid: the thread's linear index), in a fixed order: shuffles inside a wave, then the waves in
-// ascending order; valid in thread 0
-template <int WAVES>
-__device__ inline double wg_sum(double v, double* s_part, int tid) {
+// v folded over the workgroup by op (tid: the thread's linear index; s_part: WAVES entries of LDS that nothing else uses), in a fixed
+// order: shuffles inside a wave, then zero op wave 0 op wave 1 ... in thread 0, the only thread the result is valid in
+template <int WAVES, class T, class Op>
+__device__ inline T wg_fold(T v, T zero, T* s_part, int tid, Op op) {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_down(v, o, 64));
     if ((tid & 63) == 0) s_part[tid >> 6] = v;
     __syncthreads();
-    double t = 0.0;
+    T t = zero;
     if (tid == 0)
-        for (int q = 0; q < WAVES; ++q) t += s_part[q];
+        for (int q = 0; q < WAVES; ++q) t = op(t, s_part[q]);
     return t;
 }
+struct FoldAdd { template <class T> __device__ T operator()(T a, T b) const { return a + b; } };
+struct FoldMin { __device__ double operator()(double a, double b) const { return fmin(a, b); } };
+struct FoldMax { __device__ double operator()(double a, double b) const { return fmax(a, b); } };
+// the sum of a double: its order is part of the result's bytes
+template <int WAVES>
+__device__ inline double wg_sum(double v, double* s_part, int tid) { return wg_fold<WAVES>(v, 0.0, s_part, tid, FoldAdd()); }
 
 // ------------------------------------------------------------------ rules 1-3 ----
 __global__ __launch_bounds__(PN_TPB) void k_pn_bbox(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm, double* __restrict__ part) {
-    __shared__ double s_red[PN_WAVES][7];
+    __shared__ double s_red[7][PN_WAVES];
     double lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL}, cnt = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * PN_TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * PN_TPB) {
         if (!pn_used(pts + 3 * i, nrm + 3 * i)) continue;
         cnt += 1.0;
         for (int a = 0; a < 3; ++a) { lo[a] = fmin(lo[a], pts[3 * i + a]); hi[a] = fmax(hi[a], pts[3 * i + a]); }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        for (int a = 0; a < 3; ++a) { lo[a] = fmin(lo[a], __shfl_down(lo[a], o, 64)); hi[a] = fmax(hi[a], __shfl_down(hi[a], o, 64)); }
-        cnt += __shfl_down(cnt, o, 64);                                      // whole numbers below 2^53: exact in any order
+    for (int a = 0; a < 3; ++a) {
+        lo[a] = wg_fold<PN_WAVES>(lo[a], HUGE_VAL, s_red[a], threadIdx.x, FoldMin());
+        hi[a] = wg_fold<PN_WAVES>(hi[a], -HUGE_VAL, s_red[3 + a], threadIdx.x, FoldMax());
     }
-    if ((threadIdx.x & 63) == 0) {
-        double* r = s_red[threadIdx.x >> 6];
-        for (int a = 0; a < 3; ++a) { r[a] = lo[a]; r[3 + a] = hi[a]; }
-        r[6] = cnt;
-    }
-    __syncthreads();
+    cnt = wg_fold<PN_WAVES>(cnt, 0.0, s_red[6], threadIdx.x, FoldAdd());     // whole numbers below 2^53: exact in any order
     if (threadIdx.x == 0) {
-        for (int q = 1; q < PN_WAVES; ++q) {
-            for (int a = 0; a < 3; ++a) { s_red[0][a] = fmin(s_red[0][a], s_red[q][a]); s_red[0][3 + a] = fmax(s_red[0][3 + a], s_red[q][3 + a]); }
-            s_red[0][6] += s_red[q][6];
-        }
-        for (int a = 0; a < 7; ++a) part[7 * blockIdx.x + a] = s_red[0][a];
+        for (int a = 0; a < 3; ++a) { part[7 * blockIdx.x + a] = lo[a]; part[7 * blockIdx.x + 3 + a] = hi[a]; }
+        part[7 * blockIdx.x + 6] = cnt;
     }
 }
 
@@ -131,7 +133,7 @@ __global__ __launch_bounds__(PN_TPB) void k_pn_splat(int64_t n, const double* __
     pn_corners_weights(pts + 3 * i, g, i0, w);
     for (int a = 0; a < 3; ++a) na[a] = WEIGHTED ? nrm[3 * i + a] * gain[i] : nrm[3 * i + a];
     for (int c = 0; c < 8; ++c) {
-        const int64_t node = pn_node(g.G, i0[0] + (c & 1), i0[1] + (c >> 1 & 1), i0[2] + (c >> 2 & 1));
+        const int64_t node = pn_corner_node(g.G, i0, c);
         for (int a = 0; a < 3; ++a) atomicAdd(sums + a * nn + node, (unsigned long long)pn_quant(w[c] * na[a]));
     }
 }
@@ -146,7 +148,7 @@ __global__ __launch_bounds__(PN_TPB) void k_pn_density_splat(int64_t n, const do
     double w[8];
     pn_corners_weights(pts + 3 * i, gd, i0, w);
     for (int c = 0; c < 8; ++c)
-        atomicAdd(dsum + pn_node(gd.G, i0[0] + (c & 1), i0[1] + (c >> 1 & 1), i0[2] + (c >> 2 & 1)), (unsigned long long)pn_quant(w[c]));
+        atomicAdd(dsum + pn_corner_node(gd.G, i0, c), (unsigned long long)pn_quant(w[c]));
 }
 
 // rule 15: rho_p of every row (0 for a row that is not used) and, per workgroup, the min, the max and the int64 sum of the quantised
@@ -168,16 +170,10 @@ __global__ __launch_bounds__(PN_TPB) void k_pn_point_density(int64_t n, const do
         }
         rho[i] = r;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        lo = fmin(lo, __shfl_down(lo, o, 64));
-        hi = fmax(hi, __shfl_down(hi, o, 64));
-        q += __shfl_down(q, o, 64);
-    }
-    if ((threadIdx.x & 63) == 0) { s_lo[threadIdx.x >> 6] = lo; s_hi[threadIdx.x >> 6] = hi; s_q[threadIdx.x >> 6] = q; }
-    __syncthreads();
+    lo = wg_fold<PN_WAVES>(lo, HUGE_VAL, s_lo, threadIdx.x, FoldMin());
+    hi = wg_fold<PN_WAVES>(hi, -HUGE_VAL, s_hi, threadIdx.x, FoldMax());
+    q = wg_fold<PN_WAVES>(q, 0ll, s_q, threadIdx.x, FoldAdd());
     if (threadIdx.x == 0) {
-        for (int k = 1; k < PN_WAVES; ++k) { lo = fmin(lo, s_lo[k]); hi = fmax(hi, s_hi[k]); q += s_q[k]; }
         part_d[2 * blockIdx.x] = lo;
         part_d[2 * blockIdx.x + 1] = hi;
         part_q[blockIdx.x] = q;
@@ -198,14 +194,8 @@ __global__ __launch_bounds__(PN_TPB) void k_pn_gain(int64_t n, const double* __r
         }
         gain[i] = s;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) cut += __shfl_down(cut, o, 64);
-    if ((threadIdx.x & 63) == 0) s_c[threadIdx.x >> 6] = cut;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < PN_WAVES; ++k) cut += s_c[k];
-        part_c[blockIdx.x] = cut;
-    }
+    cut = wg_fold<PN_WAVES>(cut, 0, s_c, threadIdx.x, FoldAdd());
+    if (threadIdx.x == 0) part_c[blockIdx.x] = cut;
 }
 
 // rule 17: over the vertex list the scatter wrote
@@ -215,68 +205,6 @@ __global__ __launch_bounds__(PN_TPB) void k_pn_vertex_density(int64_t nv, const 
     if (v >= nv) return;
     const double* p = vertices + 3 * v;
     out[v] = isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]) ? pn_density_at(p, gd, dsum) : NAN;      // a cell needs a finite position
-}
-
-// ------------------------------------------------------------------ rule 18 ----
-// The trim: k_tr_face_mark flags the kept faces, counts them per workgroup and marks their vertices as referenced with plain byte stores
-// of 1 (ref was cleared; every store writes the same value); k_tr_vertex_count counts the referenced vertices per workgroup; compact.hip's
-// tail scans the two count arrays; the two scatters write the survivors in their order, the faces through the new numbers of their vertices.
-__device__ inline bool tr_face_kept(int64_t V, const int32_t* __restrict__ faces, const double* __restrict__ values, double thr, int64_t f, int64_t F,
-                                    uint8_t* bad) {
-    if (f >= F) return false;
-    bool keep = true;
-    for (int q = 0; q < 3; ++q) {
-        const int32_t v = faces[3 * f + q];
-        if (v < 0 || v >= V) { *bad = 1; return false; }
-        keep = keep && pn_trim_pass(values[v], thr);
-    }
-    return keep;
-}
-
-__global__ __launch_bounds__(COMPACT_TPB) void k_tr_face_mark(int64_t V, int64_t F, const int32_t* __restrict__ faces, const double* __restrict__ values,
-                                                              double thr, uint8_t* __restrict__ keepf, uint8_t* __restrict__ ref, uint8_t* __restrict__ bad,
-                                                              int32_t* __restrict__ cnt) {
-    __shared__ int s_wsum[COMPACT_TPB / 64];
-    const int64_t f = (int64_t)blockIdx.x * COMPACT_TPB + threadIdx.x;
-    const bool keep = tr_face_kept(V, faces, values, thr, f, F, bad);
-    if (f < F) keepf[f] = keep ? 1 : 0;
-    if (keep)
-        for (int q = 0; q < 3; ++q) ref[faces[3 * f + q]] = 1;
-    const WgRank k = wg_rank<COMPACT_TPB / 64>(keep, s_wsum);
-    if (threadIdx.x == 0) cnt[blockIdx.x] = k.total;
-}
-
-__global__ __launch_bounds__(COMPACT_TPB) void k_tr_vertex_count(int64_t V, const uint8_t* __restrict__ ref, int32_t* __restrict__ cnt) {
-    __shared__ int s_wsum[COMPACT_TPB / 64];
-    const int64_t v = (int64_t)blockIdx.x * COMPACT_TPB + threadIdx.x;
-    const WgRank k = wg_rank<COMPACT_TPB / 64>(v < V && ref[v], s_wsum);
-    if (threadIdx.x == 0) cnt[blockIdx.x] = k.total;
-}
-
-__global__ __launch_bounds__(COMPACT_TPB) void k_tr_vertex_scatter(int64_t V, const uint8_t* __restrict__ ref, const int32_t* __restrict__ base,
-                                                                   const double* __restrict__ vertices, const double* __restrict__ normals,
-                                                                   double* __restrict__ vertices_out, double* __restrict__ normals_out,
-                                                                   int32_t* __restrict__ renum) {
-    __shared__ int s_wsum[COMPACT_TPB / 64];
-    const int64_t v = (int64_t)blockIdx.x * COMPACT_TPB + threadIdx.x;
-    const bool keep = v < V && ref[v];
-    const int64_t pos = (int64_t)base[blockIdx.x] + wg_rank<COMPACT_TPB / 64>(keep, s_wsum).rank;
-    if (!keep) return;
-    renum[v] = (int32_t)pos;
-    for (int a = 0; a < 3; ++a) vertices_out[3 * pos + a] = vertices[3 * v + a];
-    if (normals)
-        for (int a = 0; a < 3; ++a) normals_out[3 * pos + a] = normals[3 * v + a];
-}
-
-__global__ __launch_bounds__(COMPACT_TPB) void k_tr_face_scatter(int64_t F, const uint8_t* __restrict__ keepf, const int32_t* __restrict__ base,
-                                                                 const int32_t* __restrict__ faces, const int32_t* __restrict__ renum,
-                                                                 int32_t* __restrict__ faces_out) {
-    __shared__ int s_wsum[COMPACT_TPB / 64];
-    const int64_t f = (int64_t)blockIdx.x * COMPACT_TPB + threadIdx.x;
-    const bool keep = f < F && keepf[f];
-    const int64_t pos = (int64_t)base[blockIdx.x] + wg_rank<COMPACT_TPB / 64>(keep, s_wsum).rank;
-    if (!keep) return;
-    for (int q = 0; q < 3; ++q) faces_out[3 * pos + q] = renum[faces[3 * f + q]];       // a kept face: its vertices are referenced, renum is set
 }
 
 __global__ __launch_bounds__(PN_TPB) void k_pn_rhs(PnGrid g, const long long* __restrict__ sums, double* __restrict__ b) {
@@ -293,10 +221,11 @@ __global__ __launch_bounds__(PN_TPB) void k_pn_rhs(PnGrid g, const long long* __
     b[at] = v;
 }
 
-// ------------------------------------------------------------------ rule 8 ----
-// One node of a level of G cells (interior nodes only; the boundary holds 0 in every array):
-//   smooth    y = (x + S - b) / 7, S the six neighbours of x: Jacobi damped by 6/7 for S - 6 x = b
-//   residual  r = b - (S - 6 x)
+// ------------------------------------------------------------------ rules 8 and 22 ----
+// One multigrid for the two operators, MgPlain (rule 8) and MgScreened (rule 22).  One node of a level of G cells (interior nodes only;
+// the boundary holds 0 in every array), S the six neighbours of x:
+//   smooth    MgPlain: y = (x + S - b) / 7, Jacobi damped by 6/7 for S - 6 x = b; MgScreened: y = x - r w, w = (6/7) / diagonal
+//   residual  r = b - (S - 6 x), for MgScreened less the stencil term of a node that has a row
 __device__ inline double pn_nbr_sum(const double* x, int64_t at, int n1, int64_t plane) {
     return ((x[at - 1] + x[at + 1]) + (x[at - n1] + x[at + n1])) + (x[at - plane] + x[at + plane]);
 }
@@ -334,7 +263,86 @@ __device__ inline bool pn_column(int G, int* ix, int* iy, int* z0, int* z1) {
 }
 dim3 pn_column_grid(int G) { return dim3((unsigned)((G - 1 + 63) / 64), (unsigned)((G - 1 + 3) / 4), (unsigned)((G - 1 + PN_ZC - 1) / PN_ZC)); }
 
-__global__ __launch_bounds__(PN_TPB) void k_mg_smooth(int G, const double* __restrict__ x, const double* __restrict__ b, double* __restrict__ y) {
+// The stencil rows of the screened operator (rules 19-22, below): a level keeps the number of every node's row (idx, -1: the node has
+// none) and the rows, SC_ROW doubles each: the 27 entries in the offset order of rule 20, then the row sum.
+constexpr int SC_ROW = 28;
+// the smoother of the launched levels of M: 0 the fused kernel k_mg_smooth<MgScreened>, 1 k_mg_smooth<MgPlain> and then k_sc_smooth_rows
+// over the rows.  A compile-time constant in the product build; the diagnostics build reads MVS_SC_SMOOTH_BY_ROWS once (scripts/bench_poisson_screened.py)
+#define SC_SMOOTH_BY_ROWS (MVS_KNOB("MVS_SC_SMOOTH_BY_ROWS", 1, 0, 1) != 0.0)
+constexpr int SC_DIAG_HALF_ROW_SUM = 0, SC_DIAG_PLAIN = 1, SC_DIAG_ROW_SUM = 2;    // the Jacobi diagonal 6 + rs / 2 (kept), 6 + S_{i,0}, 6 + rs
+struct ScLevels { const int32_t* idx[PN_MAX_D + 1]; const double* tab[PN_MAX_D + 1]; };
+
+// sum_o S_{i,o} x_{i+o} of an interior node with a row
+__device__ inline double sc_apply(const double* __restrict__ x, int64_t at, int n1, int64_t plane, const double* __restrict__ row) {
+    double acc = 0.0;
+    int k = 0;
+    for (int dz = -1; dz <= 1; ++dz)
+        for (int dy = -1; dy <= 1; ++dy)
+            for (int dx = -1; dx <= 1; ++dx) acc = acc + row[k++] * x[at + dz * plane + dy * n1 + dx];
+    return acc;
+}
+// one interior node of M x = b, c = x[at] and S6 the sum of its six neighbours: the residual, and the Jacobi weight (6/7) / diagonal
+__device__ inline double sc_residual_at(const double* __restrict__ x, int64_t at, int n1, int64_t plane, double c, double S6, double b,
+                                        const double* __restrict__ row) {
+    double m = S6 - 6.0 * c;
+    if (row) m = m - sc_apply(x, at, n1, plane, row);
+    return b - m;
+}
+template <int DIAG>
+__device__ inline double sc_weight(const double* __restrict__ row) {
+    if (!row) return 1.0 / 7.0;
+    return (6.0 / 7.0) / (6.0 + (DIAG == SC_DIAG_PLAIN ? row[13] : DIAG == SC_DIAG_ROW_SUM ? row[27] : 0.5 * row[27]));
+}
+__device__ inline const double* sc_row(const int32_t* __restrict__ idx, const double* __restrict__ tab, int64_t at) {
+    const int a = idx[at];
+    return a < 0 ? nullptr : tab + (int64_t)SC_ROW * a;
+}
+
+// The operator of a level, the parameter of the multigrid kernels and of the solver on the host.  Of one interior node `at` of the
+// system Op x = b, c = x[at] and S the sum of its six neighbours: relax, the damped Jacobi step; residual; solve1, the level of one
+// unknown.  A kernel builds its Op from its trailing arguments — none for MgPlain, so those instantiations take and load nothing more.
+// The two relax steps round differently at a node without a row: each operator keeps its own.
+struct MgPlain {                         // A x = S - 6 x
+    static constexpr bool screened = false;
+    __device__ static MgPlain level(int) { return {}; }
+    __device__ double relax(const double*, int64_t, int, int64_t, double c, double S, double b) const { return ((c + S) - b) * (1.0 / 7.0); }
+    __device__ double residual(const double*, int64_t, int, int64_t, double c, double S, double b) const { return b - (S - 6.0 * c); }
+    __device__ double solve1(int64_t, double b) const { return b / -6.0; }
+    template <class F> static void level_args(const ScLevels&, int, F f) { f(); }
+    template <class F> static void all_args(const ScLevels&, F f) { f(); }
+};
+template <int DIAG>
+struct MgScreened {                      // M x = A x - sum_o S_{i,o} x_{i+o} at the nodes that have a row (rules 19-22, below); DIAG: the Jacobi diagonal
+    static constexpr bool screened = true;
+    static constexpr int diag = DIAG;
+    const int32_t* idx;                  // of this level
+    const double* tab;
+    __device__ static MgScreened level(int l, const ScLevels& Sc) { return {Sc.idx[l], Sc.tab[l]}; }
+    __device__ double relax(const double* __restrict__ x, int64_t at, int n1, int64_t plane, double c, double S, double b) const {
+        const double* row = sc_row(idx, tab, at);
+        return c - sc_residual_at(x, at, n1, plane, c, S, b, row) * sc_weight<DIAG>(row);
+    }
+    __device__ double residual(const double* __restrict__ x, int64_t at, int n1, int64_t plane, double c, double S, double b) const {
+        return sc_residual_at(x, at, n1, plane, c, S, b, sc_row(idx, tab, at));
+    }
+    __device__ double solve1(int64_t at, double b) const {                   // its neighbours are boundary nodes
+        const double* row = sc_row(idx, tab, at);
+        return b / -(6.0 + (row ? row[13] : 0.0));
+    }
+    template <class F> static void level_args(const ScLevels& Sc, int l, F f) { f(Sc.idx[l], Sc.tab[l]); }
+    template <class F> static void all_args(const ScLevels& Sc, F f) { f(Sc); }
+};
+// the diagonal chosen at run time as the template argument: f(MgScreened<diag>()), the value only names the type
+template <class F>
+int with_diagonal(int diag, F f) {
+    if (diag == SC_DIAG_PLAIN) return f(MgScreened<SC_DIAG_PLAIN>());
+    if (diag == SC_DIAG_ROW_SUM) return f(MgScreened<SC_DIAG_ROW_SUM>());
+    return f(MgScreened<SC_DIAG_HALF_ROW_SUM>());
+}
+
+template <class Op, class... A>
+__global__ __launch_bounds__(PN_TPB) void k_mg_smooth(int G, const double* __restrict__ x, const double* __restrict__ b, double* __restrict__ y, A... a) {
+    const Op op{a...};
     int ix, iy, z0, z1;
     if (!pn_column(G, &ix, &iy, &z0, &z1)) return;
     const int n1 = G + 1;
@@ -344,16 +352,18 @@ __global__ __launch_bounds__(PN_TPB) void k_mg_smooth(int G, const double* __res
     for (int iz = z0; iz < z1; ++iz, at += plane) {
         const double hi = x[at + plane];
         const double S = ((x[at - 1] + x[at + 1]) + (x[at - n1] + x[at + n1])) + (lo + hi);
-        y[at] = ((c + S) - b[at]) * (1.0 / 7.0);
+        y[at] = op.relax(x, at, n1, plane, c, S, b[at]);
         lo = c;
         c = hi;
     }
 }
 
-// r = b - A x; with out == NULL only the squared norm: one partial per workgroup, part[(z * gridDim.y + y) * gridDim.x + x]
+// r = b - Op x; with out == NULL only the squared norm: one partial per workgroup, part[(z * gridDim.y + y) * gridDim.x + x]
+template <class Op, class... A>
 __global__ __launch_bounds__(PN_TPB) void k_mg_residual(int G, const double* __restrict__ x, const double* __restrict__ b, double* __restrict__ out,
-                                                        double* __restrict__ part) {
+                                                        double* __restrict__ part, A... a) {
     __shared__ double s_part[PN_WAVES];
+    const Op op{a...};
     int ix, iy, z0, z1;
     double acc = 0.0;
     if (pn_column(G, &ix, &iy, &z0, &z1)) {
@@ -364,7 +374,7 @@ __global__ __launch_bounds__(PN_TPB) void k_mg_residual(int G, const double* __r
         for (int iz = z0; iz < z1; ++iz, at += plane) {
             const double hi = x[at + plane];
             const double S = ((x[at - 1] + x[at + 1]) + (x[at - n1] + x[at + n1])) + (lo + hi);
-            const double r = b[at] - (S - 6.0 * c);
+            const double r = op.residual(x, at, n1, plane, c, S, b[at]);
             if (out) out[at] = r;
             acc += r * r;
             lo = c;
@@ -410,38 +420,45 @@ __device__ inline void pn_each_interior(int G, F f) {
     __syncthreads();                                                        // the level's arrays are global memory of this one workgroup
 }
 
-__device__ inline void pn_coarse_smooth2(int G, double* x, double* t, const double* b) {
+// two sweeps of the smoother inside the one workgroup: x -> t -> x
+template <class Op>
+__device__ inline void mg_coarse_smooth2(const Op& op, int G, double* x, double* t, const double* b) {
     const int n1 = G + 1;
     const int64_t plane = (int64_t)n1 * n1;
-    pn_each_interior(G, [&](int64_t at, int, int, int) { t[at] = ((x[at] + pn_nbr_sum(x, at, n1, plane)) - b[at]) * (1.0 / 7.0); });
-    pn_each_interior(G, [&](int64_t at, int, int, int) { x[at] = ((t[at] + pn_nbr_sum(t, at, n1, plane)) - b[at]) * (1.0 / 7.0); });
+    pn_each_interior(G, [&](int64_t at, int, int, int) { t[at] = op.relax(x, at, n1, plane, x[at], pn_nbr_sum(x, at, n1, plane), b[at]); });
+    pn_each_interior(G, [&](int64_t at, int, int, int) { x[at] = op.relax(t, at, n1, plane, t[at], pn_nbr_sum(t, at, n1, plane), b[at]); });
 }
 
 // One V(2,2) cycle over the levels top .. 1 (top <= PN_COARSE) by ONE workgroup.  x[top] is the iterate to improve; the levels
-// below start from zero.
-__global__ __launch_bounds__(PN_COARSE_TPB) void k_mg_coarse(PnLevels L, int top) {
+// below start from zero.  a: nothing, or the ScLevels of the screened operator.
+template <class Op, class... A>
+__global__ __launch_bounds__(PN_COARSE_TPB) void k_mg_coarse(PnLevels L, int top, A... a) {
     for (int l = top; l >= 2; --l) {
         const int G = 1 << l, n1 = G + 1;
         const int64_t plane = (int64_t)n1 * n1;
         double *x = L.x[l], *t = L.t[l], *bc = L.b[l - 1], *xc = L.x[l - 1];
         const double* b = L.b[l];
-        pn_coarse_smooth2(G, x, t, b);
-        pn_each_interior(G, [&](int64_t at, int, int, int) { t[at] = b[at] - (pn_nbr_sum(x, at, n1, plane) - 6.0 * x[at]); });
+        const Op op = Op::level(l, a...);
+        mg_coarse_smooth2(op, G, x, t, b);
+        pn_each_interior(G, [&](int64_t at, int, int, int) { t[at] = op.residual(x, at, n1, plane, x[at], pn_nbr_sum(x, at, n1, plane), b[at]); });
         pn_each_interior(G / 2, [&](int64_t at, int ix, int iy, int iz) { bc[at] = pn_restrict_at(t, G / 2, ix, iy, iz); xc[at] = 0.0; });
     }
-    if (threadIdx.x == 0) L.x[1][pn_node(2, 1, 1, 1)] = L.b[1][pn_node(2, 1, 1, 1)] / -6.0;      // level 1: one unknown
+    if (threadIdx.x == 0) {                                                 // level 1: one unknown
+        const int64_t at = pn_node(2, 1, 1, 1);
+        L.x[1][at] = Op::level(1, a...).solve1(at, L.b[1][at]);
+    }
     __syncthreads();
     for (int l = 2; l <= top; ++l) {
         const int G = 1 << l;
         double* x = L.x[l];
         const double* e = L.x[l - 1];
         pn_each_interior(G, [&](int64_t at, int ix, int iy, int iz) { x[at] += pn_prolong_at(e, G, ix, iy, iz); });
-        pn_coarse_smooth2(G, x, L.t[l], L.b[l]);
+        mg_coarse_smooth2(Op::level(l, a...), G, x, L.t[l], L.b[l]);
     }
 }
 
-// ------------------------------------------------------------------ rules 19-22 ----
-// The screened operator of level l is M_l = A_l - S_l with S_l = 1/2 P^T S_(l+1) P, P the trilinear prolongation: pn_restrict_at is HALF
+// ------------------------------------------------------------------ rules 19-21 ----
+// The stencils of MgScreened and the right side of rule 21.  The screened operator of level l is M_l = A_l - S_l with S_l = 1/2 P^T S_(l+1) P, P the trilinear prolongation: pn_restrict_at is HALF
 // the transposed prolongation, and under it the Laplacian reproduces itself.  (The trilinear bases nest, so S_l is also the stencil of
 // rule 20 splatted with the weights of level l and lambda * 2^-(D - l).)  A level keeps the number of every node's stencil row (idx, -1: the node has none) and the rows of the
 // nodes that a point touches, SC_ROW doubles each: the 27 entries in the offset order of rule 20, then the row sum.
@@ -449,10 +466,9 @@ __global__ __launch_bounds__(PN_COARSE_TPB) void k_mg_coarse(PnLevels L, int top
 //   k_sc_splat / k_sc_convert              rule 20 on the finest level: 64 int64 atomic adds per point; the sums become doubles in place
 //   k_sc_flag_coarse / k_sc_coarsen        the rows of a level below the finest, gathered from the level above
 //   k_sc_rhs                               rule 21: f = b - T rs
-//   k_sc_smooth_rows                       the smoother of the launched levels is k_mg_smooth, then this pass over the rows (measured
-//                                          against the fused k_mg_smooth_sc, which the diagnostics build can still select)
-//   k_mg_smooth_sc / k_mg_residual_sc / k_mg_coarse_sc
-//                                          k_mg_smooth, k_mg_residual and k_mg_coarse with the stencil term at the nodes that have a row:
+//   k_sc_smooth_rows                       the smoother of the launched levels is k_mg_smooth<MgPlain>, then this pass over the rows
+//                                          (measured against the fused k_mg_smooth<MgScreened>, which the diagnostics build can still select)
+//   the solve                              the multigrid kernels above with MgScreened, the stencil term at the nodes that have a row:
 //                                          Jacobi damped by 6/7 over the diagonal d = 6 + rs / 2.  Every entry of S is >= 0, so the
 //                                          absolute row sum of M is at most 12 + rs, and the eigenvalues of the iteration's
 //                                          (7/6 d)^-1 M lie below (12 + rs) / (7 + 7/12 rs) < 2: it converges.  6 + rs converges too
@@ -460,13 +476,6 @@ __global__ __launch_bounds__(PN_COARSE_TPB) void k_mg_coarse(PnLevels L, int top
 //                                          points are dense (S is then lambda rho times a mass matrix, whose Jacobi spectrum reaches
 //                                          27/8).  The diagonal is a template parameter: the public call instantiates this one only,
 //                                          mvs_test_poisson_screened the other two for the measurement behind the choice.
-constexpr int SC_ROW = 28;
-// the smoother of the launched levels: 0 the fused kernel k_mg_smooth_sc, 1 k_mg_smooth and then k_sc_smooth_rows over the rows.  A
-// compile-time constant in the product build; the diagnostics build reads MVS_SC_SMOOTH_BY_ROWS once (scripts/bench_poisson_screened.py)
-#define SC_SMOOTH_BY_ROWS (MVS_KNOB("MVS_SC_SMOOTH_BY_ROWS", 1, 0, 1) != 0.0)
-constexpr int SC_DIAG_HALF_ROW_SUM = 0, SC_DIAG_PLAIN = 1, SC_DIAG_ROW_SUM = 2;    // the Jacobi diagonal 6 + rs / 2 (kept), 6 + S_{i,0}, 6 + rs
-struct ScLevels { const int32_t* idx[PN_MAX_D + 1]; const double* tab[PN_MAX_D + 1]; };
-
 __global__ __launch_bounds__(PN_TPB) void k_sc_flag(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm, PnGrid g,
                                                     uint8_t* __restrict__ flag) {
     const int64_t i = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
@@ -474,7 +483,7 @@ __global__ __launch_bounds__(PN_TPB) void k_sc_flag(int64_t n, const double* __r
     int i0[3];
     double w[8];
     pn_corners_weights(pts + 3 * i, g, i0, w);
-    for (int c = 0; c < 8; ++c) flag[pn_node(g.G, i0[0] + (c & 1), i0[1] + (c >> 1 & 1), i0[2] + (c >> 2 & 1))] = 1;
+    for (int c = 0; c < 8; ++c) flag[pn_corner_node(g.G, i0, c)] = 1;
 }
 
 __global__ __launch_bounds__(PN_TPB) void k_sc_count(int64_t nn, const uint8_t* __restrict__ flag, int32_t* __restrict__ cnt) {
@@ -503,7 +512,7 @@ __global__ __launch_bounds__(PN_TPB) void k_sc_splat(int64_t n, const double* __
     double w[8];
     int64_t row[8];
     pn_corners_weights(pts + 3 * i, g, i0, w);
-    for (int c = 0; c < 8; ++c) row[c] = (int64_t)SC_ROW * idx[pn_node(g.G, i0[0] + (c & 1), i0[1] + (c >> 1 & 1), i0[2] + (c >> 2 & 1))];   // flagged: >= 0
+    for (int c = 0; c < 8; ++c) row[c] = (int64_t)SC_ROW * idx[pn_corner_node(g.G, i0, c)];   // flagged: >= 0
     for (int c1 = 0; c1 < 8; ++c1)
         for (int c2 = c1; c2 < 8; ++c2) {
             int o12, o21;
@@ -609,52 +618,7 @@ __global__ __launch_bounds__(PN_TPB) void k_sc_rhs(int64_t nn, const int32_t* __
     if (a >= 0) b[at] = b[at] - T * tab[(int64_t)SC_ROW * a + 27];
 }
 
-// sum_o S_{i,o} x_{i+o} of an interior node with a row
-__device__ inline double sc_apply(const double* __restrict__ x, int64_t at, int n1, int64_t plane, const double* __restrict__ row) {
-    double acc = 0.0;
-    int k = 0;
-    for (int dz = -1; dz <= 1; ++dz)
-        for (int dy = -1; dy <= 1; ++dy)
-            for (int dx = -1; dx <= 1; ++dx) acc = acc + row[k++] * x[at + dz * plane + dy * n1 + dx];
-    return acc;
-}
-// one interior node of M x = b, c = x[at] and S6 the sum of its six neighbours: the residual, and the Jacobi weight (6/7) / diagonal
-__device__ inline double sc_residual_at(const double* __restrict__ x, int64_t at, int n1, int64_t plane, double c, double S6, double b,
-                                        const double* __restrict__ row) {
-    double m = S6 - 6.0 * c;
-    if (row) m = m - sc_apply(x, at, n1, plane, row);
-    return b - m;
-}
-template <int DIAG>
-__device__ inline double sc_weight(const double* __restrict__ row) {
-    if (!row) return 1.0 / 7.0;
-    return (6.0 / 7.0) / (6.0 + (DIAG == SC_DIAG_PLAIN ? row[13] : DIAG == SC_DIAG_ROW_SUM ? row[27] : 0.5 * row[27]));
-}
-__device__ inline const double* sc_row(const int32_t* __restrict__ idx, const double* __restrict__ tab, int64_t at) {
-    const int a = idx[at];
-    return a < 0 ? nullptr : tab + (int64_t)SC_ROW * a;
-}
-
-template <int DIAG>
-__global__ __launch_bounds__(PN_TPB) void k_mg_smooth_sc(int G, const double* __restrict__ x, const double* __restrict__ b, double* __restrict__ y,
-                                                         const int32_t* __restrict__ idx, const double* __restrict__ tab) {
-    int ix, iy, z0, z1;
-    if (!pn_column(G, &ix, &iy, &z0, &z1)) return;
-    const int n1 = G + 1;
-    const int64_t plane = (int64_t)n1 * n1;
-    int64_t at = pn_node(G, ix, iy, z0);
-    double lo = x[at - plane], c = x[at];
-    for (int iz = z0; iz < z1; ++iz, at += plane) {
-        const double hi = x[at + plane];
-        const double S = ((x[at - 1] + x[at + 1]) + (x[at - n1] + x[at + n1])) + (lo + hi);
-        const double* row = sc_row(idx, tab, at);
-        y[at] = c - sc_residual_at(x, at, n1, plane, c, S, b[at], row) * sc_weight<DIAG>(row);
-        lo = c;
-        c = hi;
-    }
-}
-
-// The other form of the smoother: k_mg_smooth writes every node of y as if S were zero, then this pass, a thread per row, writes the
+// The chosen form of the smoother of M: k_mg_smooth<MgPlain> writes every node of y as if S were zero, then this pass, a thread per row, writes the
 // nodes that have a row again, from the same old iterate x.  node_of[row] = the row's node; a row at a boundary node is skipped.
 template <int DIAG>
 __global__ __launch_bounds__(PN_TPB) void k_sc_smooth_rows(int64_t rows, const int32_t* __restrict__ node_of, int G, const double* __restrict__ x,
@@ -670,75 +634,6 @@ __global__ __launch_bounds__(PN_TPB) void k_sc_smooth_rows(int64_t rows, const i
     y[at] = c - sc_residual_at(x, at, n1, plane, c, pn_nbr_sum(x, at, n1, plane), b[at], row) * sc_weight<DIAG>(row);
 }
 
-// k_mg_residual for M: r = b - M x; with out == NULL only the squared norm, one partial per workgroup
-__global__ __launch_bounds__(PN_TPB) void k_mg_residual_sc(int G, const double* __restrict__ x, const double* __restrict__ b, double* __restrict__ out,
-                                                           double* __restrict__ part, const int32_t* __restrict__ idx, const double* __restrict__ tab) {
-    __shared__ double s_part[PN_WAVES];
-    int ix, iy, z0, z1;
-    double acc = 0.0;
-    if (pn_column(G, &ix, &iy, &z0, &z1)) {
-        const int n1 = G + 1;
-        const int64_t plane = (int64_t)n1 * n1;
-        int64_t at = pn_node(G, ix, iy, z0);
-        double lo = x[at - plane], c = x[at];
-        for (int iz = z0; iz < z1; ++iz, at += plane) {
-            const double hi = x[at + plane];
-            const double S = ((x[at - 1] + x[at + 1]) + (x[at - n1] + x[at + n1])) + (lo + hi);
-            const double r = sc_residual_at(x, at, n1, plane, c, S, b[at], sc_row(idx, tab, at));
-            if (out) out[at] = r;
-            acc += r * r;
-            lo = c;
-            c = hi;
-        }
-    }
-    if (!part) return;
-    const double t = wg_sum<PN_WAVES>(acc, s_part, threadIdx.y * 64 + threadIdx.x);
-    if (threadIdx.x == 0 && threadIdx.y == 0) part[((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = t;
-}
-
-template <int DIAG>
-__device__ inline void sc_coarse_smooth(int G, const double* x, double* y, const double* b, const int32_t* idx, const double* tab) {
-    const int n1 = G + 1;
-    const int64_t plane = (int64_t)n1 * n1;
-    pn_each_interior(G, [&](int64_t at, int, int, int) {
-        const double* row = sc_row(idx, tab, at);
-        y[at] = x[at] - sc_residual_at(x, at, n1, plane, x[at], pn_nbr_sum(x, at, n1, plane), b[at], row) * sc_weight<DIAG>(row);
-    });
-}
-
-// k_mg_coarse for M: one V(2,2) cycle over the levels top .. 1 by ONE workgroup
-template <int DIAG>
-__global__ __launch_bounds__(PN_COARSE_TPB) void k_mg_coarse_sc(PnLevels L, ScLevels Sc, int top) {
-    for (int l = top; l >= 2; --l) {
-        const int G = 1 << l, n1 = G + 1;
-        const int64_t plane = (int64_t)n1 * n1;
-        double *x = L.x[l], *t = L.t[l], *bc = L.b[l - 1], *xc = L.x[l - 1];
-        const double* b = L.b[l];
-        const int32_t* idx = Sc.idx[l];
-        const double* tab = Sc.tab[l];
-        sc_coarse_smooth<DIAG>(G, x, t, b, idx, tab);
-        sc_coarse_smooth<DIAG>(G, t, x, b, idx, tab);
-        pn_each_interior(G, [&](int64_t at, int, int, int) {
-            t[at] = sc_residual_at(x, at, n1, plane, x[at], pn_nbr_sum(x, at, n1, plane), b[at], sc_row(idx, tab, at));
-        });
-        pn_each_interior(G / 2, [&](int64_t at, int ix, int iy, int iz) { bc[at] = pn_restrict_at(t, G / 2, ix, iy, iz); xc[at] = 0.0; });
-    }
-    if (threadIdx.x == 0) {                                                 // level 1: one unknown, its neighbours are boundary nodes
-        const int64_t at = pn_node(2, 1, 1, 1);
-        const double* row = sc_row(Sc.idx[1], Sc.tab[1], at);
-        L.x[1][at] = L.b[1][at] / -(6.0 + (row ? row[13] : 0.0));
-    }
-    __syncthreads();
-    for (int l = 2; l <= top; ++l) {
-        const int G = 1 << l;
-        double* x = L.x[l];
-        const double* e = L.x[l - 1];
-        pn_each_interior(G, [&](int64_t at, int ix, int iy, int iz) { x[at] += pn_prolong_at(e, G, ix, iy, iz); });
-        sc_coarse_smooth<DIAG>(G, x, L.t[l], L.b[l], Sc.idx[l], Sc.tab[l]);
-        sc_coarse_smooth<DIAG>(G, L.t[l], x, L.b[l], Sc.idx[l], Sc.tab[l]);
-    }
-}
-
 // ------------------------------------------------------------------ rule 9 ----
 __global__ __launch_bounds__(PN_TPB) void k_pn_iso(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm, PnGrid g,
                                                    const double* __restrict__ chi, double* __restrict__ part) {
@@ -749,7 +644,7 @@ __global__ __launch_bounds__(PN_TPB) void k_pn_iso(int64_t n, const double* __re
         int i0[3];
         double w[8], v = 0.0;
         pn_corners_weights(pts + 3 * i, g, i0, w);
-        for (int c = 0; c < 8; ++c) v = v + w[c] * chi[pn_node(g.G, i0[0] + (c & 1), i0[1] + (c >> 1 & 1), i0[2] + (c >> 2 & 1))];
+        for (int c = 0; c < 8; ++c) v = v + w[c] * chi[pn_corner_node(g.G, i0, c)];
         acc += v;
     }
     const double t = wg_sum<PN_WAVES>(acc, s_part, threadIdx.x);
@@ -760,9 +655,9 @@ __global__ __launch_bounds__(PN_TPB) void k_pn_iso(int64_t n, const double* __re
 __global__ __launch_bounds__(PN_TPB) void k_pn_cubemask(int G, const double* __restrict__ chi, double iso, uint8_t* __restrict__ mask) {
     const int64_t cube = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
     if (cube >= (int64_t)G * G * G) return;
-    const int ix = (int)(cube % G), iy = (int)(cube / G % G), iz = (int)(cube / ((int64_t)G * G));
+    const int i0[3] = {(int)(cube % G), (int)(cube / G % G), (int)(cube / ((int64_t)G * G))};
     int m = 0;
-    for (int c = 0; c < 8; ++c) m |= (chi[pn_node(G, ix + (c & 1), iy + (c >> 1 & 1), iz + (c >> 2 & 1))] < iso ? 1 : 0) << c;
+    for (int c = 0; c < 8; ++c) m |= (chi[pn_corner_node(G, i0, c)] < iso ? 1 : 0) << c;
     mask[cube] = (uint8_t)m;
 }
 
@@ -792,10 +687,9 @@ __device__ inline bool pn_edge_crossed(int G, const double* __restrict__ chi, do
     if (r >= items) return false;
     const int n1 = G + 1, type = (int)(r % 7);
     const int64_t node = r / 7;
-    const int ix = (int)(node % n1), iy = (int)(node / n1 % n1), iz = (int)(node / ((int64_t)n1 * n1));
-    if (!pn_edge_in_grid(G, ix, iy, iz, type)) return false;
-    const int m = pn_type_mask(type);
-    return (chi[node] < iso) != (chi[pn_node(G, ix + (m & 1), iy + (m >> 1 & 1), iz + (m >> 2 & 1))] < iso);
+    const int i0[3] = {(int)(node % n1), (int)(node / n1 % n1), (int)(node / ((int64_t)n1 * n1))};
+    if (!pn_edge_in_grid(G, i0[0], i0[1], i0[2], type)) return false;
+    return (chi[node] < iso) != (chi[pn_corner_node(G, i0, pn_type_mask(type))] < iso);
 }
 
 __global__ __launch_bounds__(PN_TPB) void k_pn_edge_count(int G, const double* __restrict__ chi, double iso, int64_t items,
@@ -871,7 +765,7 @@ __global__ __launch_bounds__(PN_TPB) void k_pn_face_scatter(int G, const uint8_t
     if (in < 0) return;
     const int64_t cube = r / 12;
     const int k = (int)(r % 12) >> 1, slot = (int)(r & 1);
-    const int ix = (int)(cube % G), iy = (int)(cube / G % G), iz = (int)(cube / ((int64_t)G * G));
+    const int i0[3] = {(int)(cube % G), (int)(cube / G % G), (int)(cube / ((int64_t)G * G))};
     int ci[4], co[4];
     const int n = pn_tet_cycle(in, ci, co);
     int32_t idx[4];
@@ -879,7 +773,7 @@ __global__ __launch_bounds__(PN_TPB) void k_pn_face_scatter(int G, const uint8_t
     for (int q = 0; q < n; ++q) {
         int nm, type;
         pn_tet_edge(k, ci[q], co[q], &nm, &type);
-        idx[q] = pn_vertex_index(words, vbase, pn_node(G, ix + (nm & 1), iy + (nm >> 1 & 1), iz + (nm >> 2 & 1)) * 7 + type);
+        idx[q] = pn_vertex_index(words, vbase, pn_corner_node(G, i0, nm) * 7 + type);
         for (int a = 0; a < 3; ++a) pos3[q][a] = vertices[3 * (int64_t)idx[q] + a];
     }
     pn_tet_dir(k, in, d);
@@ -906,12 +800,36 @@ int check_pn(const char* fn, int64_t n, const void* points, const void* normals,
     return MVS_OK;
 }
 
+int check_pn_density(const char* fn, int64_t n, const mvs_poisson_density_params* dp, const void* dinfo) {
+    if (!dp || !dinfo) return bad(fn, "dparams or dinfo is NULL");
+    if (!std::isfinite(dp->max_gain) || dp->max_gain < 1.0 || dp->max_gain > 16.0) return bad(fn, "need max_gain in [1, 16]");
+    if (dp->density_drop < 0 || dp->density_drop > 8) return bad(fn, "need density_drop in [0, 8]");
+    if (dp->flags & ~MVS_POISSON_WEIGHT_NORMALS) return bad(fn, "flags holds a bit other than MVS_POISSON_WEIGHT_NORMALS");
+    if ((dp->flags & MVS_POISSON_WEIGHT_NORMALS) && n > (1ll << 22)) return bad(fn, "more than 2^22 points with MVS_POISSON_WEIGHT_NORMALS");
+    return MVS_OK;
+}
+
+int check_pn_screen(const char* fn, const mvs_poisson_screen_params* sp, const void* sinfo) {
+    if (!sp || !sinfo) return bad(fn, "sparams or sinfo is NULL");
+    if (!std::isfinite(sp->alpha) || sp->alpha < 0.0 || sp->alpha > 64.0) return bad(fn, "need alpha in [0, 64]");
+    if (sp->reserved != 0) return bad(fn, "sparams.reserved is not 0");
+    return MVS_OK;
+}
+
+// the arguments of a call and two of its outputs with their capacities (an entry names its own pair), before need_device
+int check_call(const PnCall& c, const void* out_a, int64_t cap_a, const void* out_b, int64_t cap_b) {
+    int rc = check_pn(c.fn, c.n, c.points, c.normals, c.p, c.info, out_a, cap_a, out_b, cap_b);
+    if (!rc && c.rules >= PN_DENSITY) rc = check_pn_density(c.fn, c.n, c.dp, c.dinfo);
+    if (!rc && c.rules >= PN_SCREENED) rc = check_pn_screen(c.fn, c.sp, c.sinfo);
+    return rc;
+}
+
 // One call: the grid, the field and the counts; the scatter once the caller's capacities are known to suffice.
 struct PnRun {
     const mvs_poisson_params& p;
     mvs_poisson_info& info;
     int64_t n;
-    const double *pts, *nrm;
+    const double *pts, *nrm;              // on the device
     hipStream_t s;
     PnGrid g{};
     int64_t nn = 0;                       // nodes of the finest level
@@ -950,13 +868,38 @@ struct PnRun {
     PnLevels L{};
     double iso = 0.0;
     int64_t edge_items = 0, face_items = 0;
-    PnRun(const mvs_poisson_params& prm, mvs_poisson_info& inf, int64_t n_, const double* pd, const double* nd, hipStream_t st)
-        : p(prm), info(inf), n(n_), pts(pd), nrm(nd), s(st) { std::memset(&info, 0, sizeof info); }
+    // a checked call and its points on the device; every info struct of the call starts from zero
+    PnRun(const PnCall& c, const double* pd, const double* nd, hipStream_t st)
+        : p(*c.p), info(*c.info), n(c.n), pts(pd), nrm(nd), s(st), dp(c.dp), dinfo(c.dinfo), sp(c.sp), sinfo(c.sinfo) {
+        std::memset(&info, 0, sizeof info);
+        if (dinfo) std::memset(dinfo, 0, sizeof *dinfo);
+        if (sinfo) std::memset(sinfo, 0, sizeof *sinfo);
+    }
 
     int fetch(void* dst, const void* src, size_t bytes) {
         HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         return MVS_OK;
+    }
+
+    // hocc[d] = the occupied cells of the cube (side and g.o of rule 2) at every depth d = dmin .. dmax: rule 3, and occupied(D) of rule 19
+    int occupancy(int dmin, int dmax, unsigned long long hocc[PN_MAX_D + 1]) {
+        int rc;
+        PnOcc q{};
+        q.dmin = dmin; q.dmax = dmax;
+        int64_t w = 0;
+        for (int d = dmin; d <= dmax; ++d) { q.cs[d] = side / (double)(1 << d); q.word0[d] = w; w += ((int64_t)1 << (3 * d)) / 32; }
+        q.word0[dmax + 1] = w;
+        for (int a = 0; a < 3; ++a) q.o[a] = g.o[a];
+        Scratch bits, occ;
+        const size_t occ_bytes = sizeof(unsigned long long) * (PN_MAX_D + 1);
+        if ((rc = bits.alloc(sizeof(unsigned) * (size_t)w, s)) || (rc = occ.alloc(occ_bytes, s))) return rc;
+        HIPCHK(hipMemsetAsync(bits.p, 0, sizeof(unsigned) * (size_t)w, s));
+        HIPCHK(hipMemsetAsync(occ.p, 0, occ_bytes, s));
+        k_pn_occupy<<<dim3((unsigned)((n + PN_TPB - 1) / PN_TPB)), dim3(PN_TPB), 0, s>>>(n, pts, nrm, q, bits.as<unsigned>());
+        k_pn_popcount<<<dim3((unsigned)((w + PN_TPB - 1) / PN_TPB)), dim3(PN_TPB), 0, s>>>(q, bits.as<unsigned>(), occ.as<unsigned long long>());
+        HIPCHK(hipGetLastError());
+        return fetch(hocc, occ.p, occ_bytes);
     }
 
     // rules 1-4
@@ -984,22 +927,9 @@ struct PnRun {
         const int dmax = p.depth_max < PN_MAX_D ? p.depth_max : PN_MAX_D;
         int D = p.depth_min;
         if (dmax > p.depth_min) {                                                                // rule 3
-            PnOcc q{};
-            q.dmin = p.depth_min; q.dmax = dmax;
-            int64_t w = 0;
-            for (int d = q.dmin; d <= dmax; ++d) { q.cs[d] = side / (double)(1 << d); q.word0[d] = w; w += ((int64_t)1 << (3 * d)) / 32; }
-            q.word0[dmax + 1] = w;
-            for (int a = 0; a < 3; ++a) q.o[a] = g.o[a];
-            Scratch bits, occ;
             unsigned long long hocc[PN_MAX_D + 1];
-            if ((rc = bits.alloc(sizeof(unsigned) * (size_t)w, s)) || (rc = occ.alloc(sizeof hocc, s))) return rc;
-            HIPCHK(hipMemsetAsync(bits.p, 0, sizeof(unsigned) * (size_t)w, s));
-            HIPCHK(hipMemsetAsync(occ.p, 0, sizeof hocc, s));
-            k_pn_occupy<<<dim3((unsigned)((n + PN_TPB - 1) / PN_TPB)), dim3(PN_TPB), 0, s>>>(n, pts, nrm, q, bits.as<unsigned>());
-            k_pn_popcount<<<dim3((unsigned)((w + PN_TPB - 1) / PN_TPB)), dim3(PN_TPB), 0, s>>>(q, bits.as<unsigned>(), occ.as<unsigned long long>());
-            HIPCHK(hipGetLastError());
-            if ((rc = fetch(hocc, occ.p, sizeof hocc))) return rc;
-            for (int d = q.dmin; d <= dmax; ++d)
+            if ((rc = occupancy(p.depth_min, dmax, hocc))) return rc;
+            for (int d = p.depth_min; d <= dmax; ++d)
                 if ((double)info.n_used >= p.samples_per_node * (double)hocc[d]) D = d;
         }
         g.G = 1 << D;                                                                            // rule 4
@@ -1031,39 +961,73 @@ struct PnRun {
         return MVS_OK;
     }
 
-    int norm2(int l, double* out) {                                          // |b - A x|^2 of level l, on the host
-        const int G = 1 << l;
-        const dim3 gr = pn_column_grid(G);
+    // The solver, for Op = MgPlain or MgScreened<the diagonal>: Op x = L.b[l] on every level l.
+    template <class Op>
+    int norm2(const double* x, double* out) {                                // |b - Op x|^2 of the finest level, on the host
+        const int D = info.depth;
+        const dim3 gr = pn_column_grid(g.G);
         const int np = (int)(gr.x * gr.y * gr.z);
-        k_mg_residual<<<gr, dim3(64, 4), 0, s>>>(G, L.x[l], L.b[l], nullptr, red.as<double>() + 1);
+        Op::level_args(Sc, D, [&](auto... lv) { k_mg_residual<Op><<<gr, dim3(64, 4), 0, s>>>(g.G, x, L.b[D], nullptr, red.as<double>() + 1, lv...); });
         k_pn_fold<<<dim3(1), dim3(PN_TPB), 0, s>>>(red.as<double>() + 1, np, red.as<double>());
         HIPCHK(hipGetLastError());
         return fetch(out, red.p, sizeof(double));
     }
 
-    void smooth2(int l) {
+    template <class Op>
+    void smooth(int l, const double* x, double* y) {                         // one sweep of a launched level
         const int G = 1 << l;
-        k_mg_smooth<<<pn_column_grid(G), dim3(64, 4), 0, s>>>(G, L.x[l], L.b[l], L.t[l]);
-        k_mg_smooth<<<pn_column_grid(G), dim3(64, 4), 0, s>>>(G, L.t[l], L.b[l], L.x[l]);
+        if constexpr (Op::screened)
+            if (SC_SMOOTH_BY_ROWS) {
+                k_mg_smooth<MgPlain><<<pn_column_grid(G), dim3(64, 4), 0, s>>>(G, x, L.b[l], y);
+                if (sc_rows[l] > 0)
+                    k_sc_smooth_rows<Op::diag><<<dim3((unsigned)((sc_rows[l] + PN_TPB - 1) / PN_TPB)), dim3(PN_TPB), 0, s>>>(sc_rows[l], sc_node[l].as<int32_t>(), G, x,
+                                                                                                                        L.b[l], y, Sc.tab[l]);
+                return;
+            }
+        Op::level_args(Sc, l, [&](auto... lv) { k_mg_smooth<Op><<<pn_column_grid(G), dim3(64, 4), 0, s>>>(G, x, L.b[l], y, lv...); });
+    }
+    template <class Op>
+    void smooth2(int l) {
+        smooth<Op>(l, L.x[l], L.t[l]);
+        smooth<Op>(l, L.t[l], L.x[l]);
     }
 
+    template <class Op>
     int vcycle() {
         const int D = info.depth;
         for (int l = D; l > PN_COARSE; --l) {
             const int G = 1 << l, Gc = G / 2;
-            smooth2(l);
-            k_mg_residual<<<pn_column_grid(G), dim3(64, 4), 0, s>>>(G, L.x[l], L.b[l], L.t[l], nullptr);
+            smooth2<Op>(l);
+            Op::level_args(Sc, l, [&](auto... lv) { k_mg_residual<Op><<<pn_column_grid(G), dim3(64, 4), 0, s>>>(G, L.x[l], L.b[l], L.t[l], nullptr, lv...); });
             k_mg_restrict<<<dim3((unsigned)((Gc - 1 + 63) / 64), (unsigned)((Gc - 1 + 3) / 4), (unsigned)(Gc - 1)), dim3(64, 4), 0, s>>>(Gc, L.t[l], L.b[l - 1]);
             HIPCHK(hipMemsetAsync(L.x[l - 1], 0, 8 * (size_t)(Gc + 1) * (Gc + 1) * (Gc + 1), s));
         }
-        k_mg_coarse<<<dim3(1), dim3(PN_COARSE_TPB), 0, s>>>(L, D < PN_COARSE ? D : PN_COARSE);
+        Op::all_args(Sc, [&](auto... a) { k_mg_coarse<Op><<<dim3(1), dim3(PN_COARSE_TPB), 0, s>>>(L, D < PN_COARSE ? D : PN_COARSE, a...); });
         for (int l = PN_COARSE + 1; l <= D; ++l) {
             const int G = 1 << l;
             k_mg_prolong<<<dim3((unsigned)((G - 1 + 63) / 64), (unsigned)((G - 1 + 3) / 4), (unsigned)(G - 1)), dim3(64, 4), 0, s>>>(G, L.x[l - 1], L.x[l]);
-            smooth2(l);
+            smooth2<Op>(l);
         }
         HIPCHK(hipGetLastError());
         return MVS_OK;
+    }
+
+    // V cycles from the iterate in L.x[D] until the residual is at most solve_tol times the norm of the right side, which is the
+    // residual of `zero`, a buffer that holds 0.  MVS_E_SOLVER comes without an error text: the caller has the words for its solve.
+    template <class Op>
+    int solve(const double* zero, int32_t* cycles, double* rel_residual) {
+        int rc;
+        const int D = info.depth;
+        double b2 = 0.0, r2 = 0.0;
+        if ((rc = norm2<Op>(zero, &b2))) return rc;
+        if (!(b2 > 0.0)) return MVS_OK;                                       // b = 0 (or not finite): 0 solves it
+        for (int c = 1; c <= p.max_cycles; ++c) {
+            if ((rc = vcycle<Op>()) || (rc = norm2<Op>(L.x[D], &r2))) return rc;
+            *cycles = c;
+            *rel_residual = std::sqrt(r2) / std::sqrt(b2);
+            if (std::sqrt(r2) <= p.solve_tol * std::sqrt(b2)) return MVS_OK;
+        }
+        return MVS_E_SOLVER;
     }
 
     // rules 5-6 (with rule 16 when the call weights): the levels, then b
@@ -1090,17 +1054,10 @@ struct PnRun {
         HIPCHK(hipMemsetAsync(sums.p, 0, 16 * (size_t)nn, s));                // the sums are spent: x = 0 and the smoother's second buffer
         const dim3 gr = pn_column_grid(g.G);
         if ((rc = red.alloc(sizeof(double) * (1 + (size_t)gr.x * gr.y * gr.z), s))) return rc;
-        double b2 = 0.0, r2 = 0.0;
-        if ((rc = norm2(D, &b2))) return rc;                                  // x = 0: the residual is b
-        if (!(b2 > 0.0)) return MVS_OK;                                       // b = 0 (or not finite): chi = 0 solves it
-        for (int c = 1; c <= p.max_cycles; ++c) {
-            if ((rc = vcycle()) || (rc = norm2(D, &r2))) return rc;
-            info.cycles = c;
-            info.rel_residual = std::sqrt(r2) / std::sqrt(b2);
-            if (std::sqrt(r2) <= p.solve_tol * std::sqrt(b2)) return MVS_OK;
-        }
-        mvs_set_error("%s: relative residual %.3e after %d cycles, above solve_tol %.3e", fn, info.rel_residual, info.cycles, p.solve_tol);
-        return MVS_E_SOLVER;
+        rc = solve<MgPlain>(L.x[D], &info.cycles, &info.rel_residual);        // x = 0 is the start and the zero
+        if (rc == MVS_E_SOLVER)
+            mvs_set_error("%s: relative residual %.3e after %d cycles, above solve_tol %.3e", fn, info.rel_residual, info.cycles, p.solve_tol);
+        return rc;
     }
 
     // rules 14-16: the density grid, rho_p, rho_mean and s_p
@@ -1108,7 +1065,6 @@ struct PnRun {
         int rc, Dd = 0;
         gd = pn_density_grid(g, side, info.depth, dp->density_drop, &Dd);
         nnd = (int64_t)(gd.G + 1) * (gd.G + 1) * (gd.G + 1);
-        std::memset(dinfo, 0, sizeof *dinfo);
         dinfo->density_depth = Dd;
         const int nb = (int)std::min<int64_t>(PN_RED_NB, (n + PN_TPB - 1) / PN_TPB);
         if ((rc = dsum.alloc(8 * (size_t)nnd, s)) || (rc = rho.alloc(8 * (size_t)n, s)) || (rc = gain.alloc(8 * (size_t)n, s)) ||
@@ -1198,28 +1154,6 @@ struct PnRun {
         return MVS_OK;
     }
 
-    // rule 19: occupied(D), whether or not rule 3 had a choice
-    int occupied_at(int D, int64_t* out) {
-        int rc;
-        PnOcc q{};
-        q.dmin = q.dmax = D;
-        q.cs[D] = side / (double)(1 << D);
-        const int64_t w = ((int64_t)1 << (3 * D)) / 32;
-        q.word0[D] = 0; q.word0[D + 1] = w;
-        for (int a = 0; a < 3; ++a) q.o[a] = g.o[a];
-        Scratch bits, occ;
-        unsigned long long hocc[PN_MAX_D + 1];
-        if ((rc = bits.alloc(sizeof(unsigned) * (size_t)w, s)) || (rc = occ.alloc(sizeof hocc, s))) return rc;
-        HIPCHK(hipMemsetAsync(bits.p, 0, sizeof(unsigned) * (size_t)w, s));
-        HIPCHK(hipMemsetAsync(occ.p, 0, sizeof hocc, s));
-        k_pn_occupy<<<dim3((unsigned)((n + PN_TPB - 1) / PN_TPB)), dim3(PN_TPB), 0, s>>>(n, pts, nrm, q, bits.as<unsigned>());
-        k_pn_popcount<<<dim3((unsigned)((w + PN_TPB - 1) / PN_TPB)), dim3(PN_TPB), 0, s>>>(q, bits.as<unsigned>(), occ.as<unsigned long long>());
-        HIPCHK(hipGetLastError());
-        if ((rc = fetch(hocc, occ.p, sizeof hocc))) return rc;
-        *out = (int64_t)hocc[D];
-        return MVS_OK;
-    }
-
     // rule 20 on the finest level, and the rows of every level below from the level above; dense (may be NULL): [nn][27] int64 on the
     // device, the sums of the finest level
     int stencils(double lambda, long long* dense) {
@@ -1266,9 +1200,10 @@ struct PnRun {
     // rules 19-21, after rule 9: sinfo, the stencils and f in the place of b.  alpha = 0 stops after rule 19.
     int screen_setup(long long* dense) {
         int rc;
-        std::memset(sinfo, 0, sizeof *sinfo);
+        unsigned long long hocc[PN_MAX_D + 1];
         sinfo->target = sinfo->iso_unscreened = iso;
-        if ((rc = occupied_at(info.depth, &sinfo->occupied))) return rc;
+        if ((rc = occupancy(info.depth, info.depth, hocc))) return rc;         // occupied(D), whether or not rule 3 had a choice
+        sinfo->occupied = (int64_t)hocc[info.depth];
         if (!(sp->alpha > 0.0)) return MVS_OK;
         sinfo->lambda = pn_screen_lambda(sp->alpha, info.n_used, sinfo->occupied);
         if ((rc = stencils(sinfo->lambda, dense))) return rc;
@@ -1278,72 +1213,14 @@ struct PnRun {
         return MVS_OK;
     }
 
-    int norm2_sc(const double* x, double* out) {                             // |f - M x|^2 of the finest level, on the host
-        const int D = info.depth;
-        const dim3 gr = pn_column_grid(g.G);
-        const int np = (int)(gr.x * gr.y * gr.z);
-        k_mg_residual_sc<<<gr, dim3(64, 4), 0, s>>>(g.G, x, L.b[D], nullptr, red.as<double>() + 1, Sc.idx[D], Sc.tab[D]);
-        k_pn_fold<<<dim3(1), dim3(PN_TPB), 0, s>>>(red.as<double>() + 1, np, red.as<double>());
-        HIPCHK(hipGetLastError());
-        return fetch(out, red.p, sizeof(double));
-    }
-
-    template <int DIAG>
-    void smooth_sc(int l, const double* x, double* y) {
-        const int G = 1 << l;
-        if (SC_SMOOTH_BY_ROWS) {
-            k_mg_smooth<<<pn_column_grid(G), dim3(64, 4), 0, s>>>(G, x, L.b[l], y);
-            if (sc_rows[l] > 0)
-                k_sc_smooth_rows<DIAG><<<dim3((unsigned)((sc_rows[l] + PN_TPB - 1) / PN_TPB)), dim3(PN_TPB), 0, s>>>(sc_rows[l], sc_node[l].as<int32_t>(), G, x,
-                                                                                                                    L.b[l], y, Sc.tab[l]);
-        } else {
-            k_mg_smooth_sc<DIAG><<<pn_column_grid(G), dim3(64, 4), 0, s>>>(G, x, L.b[l], y, Sc.idx[l], Sc.tab[l]);
-        }
-    }
-    void smooth2_sc(int l) {
-        if (diag == SC_DIAG_PLAIN) { smooth_sc<SC_DIAG_PLAIN>(l, L.x[l], L.t[l]); smooth_sc<SC_DIAG_PLAIN>(l, L.t[l], L.x[l]); }
-        else if (diag == SC_DIAG_ROW_SUM) { smooth_sc<SC_DIAG_ROW_SUM>(l, L.x[l], L.t[l]); smooth_sc<SC_DIAG_ROW_SUM>(l, L.t[l], L.x[l]); }
-        else { smooth_sc<SC_DIAG_HALF_ROW_SUM>(l, L.x[l], L.t[l]); smooth_sc<SC_DIAG_HALF_ROW_SUM>(l, L.t[l], L.x[l]); }
-    }
-
-    int vcycle_sc() {                                                        // vcycle for M
-        const int D = info.depth;
-        for (int l = D; l > PN_COARSE; --l) {
-            const int G = 1 << l, Gc = G / 2;
-            smooth2_sc(l);
-            k_mg_residual_sc<<<pn_column_grid(G), dim3(64, 4), 0, s>>>(G, L.x[l], L.b[l], L.t[l], nullptr, Sc.idx[l], Sc.tab[l]);
-            k_mg_restrict<<<dim3((unsigned)((Gc - 1 + 63) / 64), (unsigned)((Gc - 1 + 3) / 4), (unsigned)(Gc - 1)), dim3(64, 4), 0, s>>>(Gc, L.t[l], L.b[l - 1]);
-            HIPCHK(hipMemsetAsync(L.x[l - 1], 0, 8 * (size_t)(Gc + 1) * (Gc + 1) * (Gc + 1), s));
-        }
-        const int top = D < PN_COARSE ? D : PN_COARSE;
-        if (diag == SC_DIAG_PLAIN) k_mg_coarse_sc<SC_DIAG_PLAIN><<<dim3(1), dim3(PN_COARSE_TPB), 0, s>>>(L, Sc, top);
-        else if (diag == SC_DIAG_ROW_SUM) k_mg_coarse_sc<SC_DIAG_ROW_SUM><<<dim3(1), dim3(PN_COARSE_TPB), 0, s>>>(L, Sc, top);
-        else k_mg_coarse_sc<SC_DIAG_HALF_ROW_SUM><<<dim3(1), dim3(PN_COARSE_TPB), 0, s>>>(L, Sc, top);
-        for (int l = PN_COARSE + 1; l <= D; ++l) {
-            const int G = 1 << l;
-            k_mg_prolong<<<dim3((unsigned)((G - 1 + 63) / 64), (unsigned)((G - 1 + 3) / 4), (unsigned)(G - 1)), dim3(64, 4), 0, s>>>(G, L.x[l - 1], L.x[l]);
-            smooth2_sc(l);
-        }
-        HIPCHK(hipGetLastError());
-        return MVS_OK;
-    }
-
     // rule 22: from chi0 in L.x[D], with f in L.b[D]
     int screen_solve(const char* fn) {
-        int rc;
         const int D = info.depth;
-        double f2 = 0.0, r2 = 0.0;
         HIPCHK(hipMemsetAsync(L.t[D], 0, 8 * (size_t)nn, s));                 // M 0 = 0: the residual of zero is f
-        if ((rc = norm2_sc(L.t[D], &f2))) return rc;
-        if (!(f2 > 0.0)) return MVS_OK;
-        for (int c = 1; c <= p.max_cycles; ++c) {
-            if ((rc = vcycle_sc()) || (rc = norm2_sc(L.x[D], &r2))) return rc;
-            sinfo->cycles = c;
-            sinfo->rel_residual = std::sqrt(r2) / std::sqrt(f2);
-            if (std::sqrt(r2) <= p.solve_tol * std::sqrt(f2)) return MVS_OK;
-        }
-        mvs_set_error("%s: screened solve: relative residual %.3e after %d cycles, above solve_tol %.3e", fn, sinfo->rel_residual, sinfo->cycles, p.solve_tol);
-        return MVS_E_SOLVER;
+        const int rc = with_diagonal(diag, [&](auto op) { return solve<decltype(op)>(L.t[D], &sinfo->cycles, &sinfo->rel_residual); });
+        if (rc == MVS_E_SOLVER)
+            mvs_set_error("%s: screened solve: relative residual %.3e after %d cycles, above solve_tol %.3e", fn, sinfo->rel_residual, sinfo->cycles, p.solve_tol);
+        return rc;
     }
 
     int counts(const char* fn) {
@@ -1357,103 +1234,62 @@ struct PnRun {
     }
 };
 
-int too_small(const char* fn) { return bad(fn, "a capacity is below the count (info holds n_vertices and n_faces)"); }
+// Where a call writes, on the device: the caller's arrays of vcap and fcap rows (density NULL: not wanted), or — bv set — blocks that
+// are sized once the counts are known (bd NULL: no density).
+struct PnOut {
+    double *vertices, *density;
+    int32_t* faces;
+    int64_t vcap, fcap;
+    Scratch *bv, *bd, *bf;
+};
 
-int check_pn_density(const char* fn, int64_t n, const mvs_poisson_density_params* dp, const void* dinfo) {
-    if (!dp || !dinfo) return bad(fn, "dparams or dinfo is NULL");
-    if (!std::isfinite(dp->max_gain) || dp->max_gain < 1.0 || dp->max_gain > 16.0) return bad(fn, "need max_gain in [1, 16]");
-    if (dp->density_drop < 0 || dp->density_drop > 8) return bad(fn, "need density_drop in [0, 8]");
-    if (dp->flags & ~MVS_POISSON_WEIGHT_NORMALS) return bad(fn, "flags holds a bit other than MVS_POISSON_WEIGHT_NORMALS");
-    if ((dp->flags & MVS_POISSON_WEIGHT_NORMALS) && n > (1ll << 22)) return bad(fn, "more than 2^22 points with MVS_POISSON_WEIGHT_NORMALS");
-    return MVS_OK;
+// The device form of every entry, after its checks: the counts, the capacity test, the scatter and the vertex densities.
+int reconstruct(const PnCall& c, const double* pts_dev, const double* nrm_dev, PnOut o, hipStream_t s) {
+    int rc;
+    PnRun run(c, pts_dev, nrm_dev, s);
+    if ((rc = run.counts(c.fn))) return rc;
+    const int64_t V = c.info->n_vertices, F = c.info->n_faces;
+    if (V > o.vcap || F > o.fcap) return bad(c.fn, "a capacity is below the count (info holds n_vertices and n_faces)");
+    if (o.bv) {
+        if ((rc = o.bv->alloc(24 * (size_t)V)) || (rc = o.bf->alloc(12 * (size_t)F)) || (o.bd && (rc = o.bd->alloc(8 * (size_t)V)))) return rc;
+        o.vertices = o.bv->as<double>();
+        o.faces = o.bf->as<int32_t>();
+        o.density = o.bd ? o.bd->as<double>() : nullptr;
+    }
+    if ((rc = run.scatter(o.vertices, o.faces))) return rc;
+    return run.vertex_density(o.vertices, o.density);
 }
 
-int check_pn_screen(const char* fn, const mvs_poisson_screen_params* sp, const void* sinfo) {
-    if (!sp || !sinfo) return bad(fn, "sparams or sinfo is NULL");
-    if (!std::isfinite(sp->alpha) || sp->alpha < 0.0 || sp->alpha > 64.0) return bad(fn, "need alpha in [0, 64]");
-    if (sp->reserved != 0) return bad(fn, "sparams.reserved is not 0");
-    return MVS_OK;
+// what every entry opens with
+int open_call(const PnCall& c, const void* out_a, int64_t cap_a, const void* out_b, int64_t cap_b) {
+    const int rc = check_call(c, out_a, cap_a, out_b, cap_b);
+    return rc ? rc : need_device();
+}
+int up_points(const PnCall& c, Scratch& dp, Scratch& dn) {
+    const int rc = up(dp, c.points, 3 * (size_t)c.n);
+    return rc ? rc : up(dn, c.normals, 3 * (size_t)c.n);
 }
 
-int check_trim(const char* fn, int64_t V, const void* vertices, const void* normals, int64_t F, const void* faces, const void* values, double thr,
-               const void* vertices_out, const void* normals_out, const void* faces_out, const void* V_out, const void* F_out) {
-    if (!vertices || !faces || !values || !vertices_out || !faces_out || !V_out || !F_out) return bad(fn, "an argument other than normals / normals_out is NULL");
-    if (normals && !normals_out) return bad(fn, "normals without normals_out");
-    if (V < 0 || F < 0) return bad(fn, "V or F is negative");
-    if (V > 0x7fffffffLL || F > 0x7fffffffLL) return bad(fn, "V or F exceeds 2^31 - 1");
-    if (std::isnan(thr)) return bad(fn, "threshold is NaN");
-    return MVS_OK;
+// The host form of every entry: the points go up, the device form fills blocks, the blocks come down.
+int reconstruct_host(const PnCall& c, double* vertices, double* density, int64_t vcap, int32_t* faces, int64_t fcap) {
+    int rc;
+    Scratch dp, dn, dv, dd, df;
+    if ((rc = open_call(c, vertices, vcap, faces, fcap)) || (rc = up_points(c, dp, dn)) ||
+        (rc = reconstruct(c, dp.as<double>(), dn.as<double>(), PnOut{nullptr, nullptr, nullptr, vcap, fcap, &dv, density ? &dd : nullptr, &df}, nullptr)))
+        return rc;
+    const size_t V = (size_t)c.info->n_vertices, F = (size_t)c.info->n_faces;
+    if ((density && (rc = down(density, dd, V))) || (rc = down(vertices, dv, 3 * V))) return rc;
+    return down(faces, df, 3 * F);
 }
 
 }  // namespace
 
-// rule 18 on device arrays, arguments validated by the caller.  Synchronises s.
-int mesh_trim_dev(int64_t V, const double* vertices, const double* normals, int64_t F, const int32_t* faces, const double* values, double thr,
-                  double* vertices_out, double* normals_out, int32_t* faces_out, int64_t* V_out, int64_t* F_out, hipStream_t s) {
-    *V_out = *F_out = 0;
-    if (V == 0 || F == 0) return MVS_OK;
-    int rc;
-    const int64_t nbv = (V + COMPACT_TPB - 1) / COMPACT_TPB, nbf = (F + COMPACT_TPB - 1) / COMPACT_TPB;
-    Scratch keepf, ref, renum;                                               // ref: V bytes and the bad-mesh byte behind them
-    CompactTail tv, tf;
-    if ((rc = keepf.alloc((size_t)F, s)) || (rc = ref.alloc((size_t)V + 1, s)) || (rc = renum.alloc(4 * (size_t)V, s)) ||
-        (rc = tv.alloc((size_t)nbv, 1, s)) || (rc = tf.alloc((size_t)nbf, 1, s))) return rc;
-    HIPCHK(hipMemsetAsync(ref.p, 0, (size_t)V + 1, s));
-    k_tr_face_mark<<<dim3((unsigned)nbf), dim3(COMPACT_TPB), 0, s>>>(V, F, faces, values, thr, keepf.as<uint8_t>(), ref.as<uint8_t>(), ref.as<uint8_t>() + V,
-                                                                    tf.cnt.as<int32_t>());
-    k_tr_vertex_count<<<dim3((unsigned)nbv), dim3(COMPACT_TPB), 0, s>>>(V, ref.as<uint8_t>(), tv.cnt.as<int32_t>());
-    tf.strided((int)nbf, nullptr, 1, (int)nbf, s);                            // off = {0, all survivors}
-    tv.strided((int)nbv, nullptr, 1, (int)nbv, s);
-    HIPCHK(hipGetLastError());
-    uint8_t badmesh = 0;
-    int64_t offv[2] = {0, 0}, offf[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(&badmesh, ref.as<uint8_t>() + V, 1, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(offv, tv.off.p, 16, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(offf, tf.off.p, 16, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (badmesh) { mvs_set_error("mesh trim: a face index is outside [0, V)"); return MVS_E_BAD_MESH; }
-    if (offf[1] > 0) {
-        k_tr_vertex_scatter<<<dim3((unsigned)nbv), dim3(COMPACT_TPB), 0, s>>>(V, ref.as<uint8_t>(), tv.base.as<int32_t>(), vertices, normals, vertices_out,
-                                                                             normals_out, renum.as<int32_t>());
-        k_tr_face_scatter<<<dim3((unsigned)nbf), dim3(COMPACT_TPB), 0, s>>>(F, keepf.as<uint8_t>(), tf.base.as<int32_t>(), faces, renum.as<int32_t>(),
-                                                                           faces_out);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(s));
-    }
-    *V_out = offv[1];
-    *F_out = offf[1];
-    return MVS_OK;
-}
-
-// mvs_poisson_reconstruct_density_dev, or with sp mvs_poisson_reconstruct_screened_dev, with outputs that size themselves, for
-// mvs_processor_poisson_density and mvs_processor_poisson_screened; as poisson_blocks
-int poisson_density_blocks(const char* fn, int64_t n, const double* points_dev, const double* normals_dev, const mvs_poisson_params* p,
-                           const mvs_poisson_density_params* dp, mvs_poisson_info* info, mvs_poisson_density_info* dinfo, Scratch* vertices,
-                           Scratch* density, Scratch* faces, const mvs_poisson_screen_params* sp, mvs_poisson_screen_info* sinfo) {
-    int rc = check_pn(fn, n, points_dev, normals_dev, p, info, nullptr, 0, nullptr, 0);
-    if (rc || (rc = check_pn_density(fn, n, dp, dinfo)) || (sp && (rc = check_pn_screen(fn, sp, sinfo)))) return rc;
-    PnRun run(*p, *info, n, points_dev, normals_dev, nullptr);
-    run.dp = dp;
-    run.dinfo = dinfo;
-    run.sp = sp;
-    run.sinfo = sinfo;
-    if ((rc = run.counts(fn))) return rc;
-    if ((rc = vertices->alloc(24 * (size_t)info->n_vertices)) || (rc = density->alloc(8 * (size_t)info->n_vertices)) ||
-        (rc = faces->alloc(12 * (size_t)info->n_faces))) return rc;
-    if ((rc = run.scatter(vertices->as<double>(), faces->as<int32_t>()))) return rc;
-    return run.vertex_density(vertices->as<double>(), density->as<double>());
-}
-
-// the device form for a caller inside the library that cannot know the counts in advance (mvs_processor_poisson): the blocks are sized
-// once the counts are known
-int poisson_blocks(const char* fn, int64_t n, const double* points_dev, const double* normals_dev, const mvs_poisson_params* p,
-                   mvs_poisson_info* info, Scratch* vertices, Scratch* faces) {
-    int rc = check_pn(fn, n, points_dev, normals_dev, p, info, nullptr, 0, nullptr, 0);
+// the device form for a caller inside the library that cannot know the counts in advance (mvs_processor_poisson and its kin)
+int poisson_blocks(const PnCall& c, Scratch* vertices, Scratch* density, Scratch* faces) {
+    const int rc = check_call(c, nullptr, 0, nullptr, 0);
     if (rc) return rc;
-    PnRun run(*p, *info, n, points_dev, normals_dev, nullptr);
-    if ((rc = run.counts(fn))) return rc;
-    if ((rc = vertices->alloc(24 * (size_t)info->n_vertices)) || (rc = faces->alloc(12 * (size_t)info->n_faces))) return rc;
-    return run.scatter(vertices->as<double>(), faces->as<int32_t>());
+    return reconstruct(c, c.points, c.normals, PnOut{nullptr, nullptr, nullptr, INT64_MAX, INT64_MAX, vertices, c.rules >= PN_DENSITY ? density : nullptr, faces},
+                       nullptr);
 }
 
 extern "C" {
@@ -1467,44 +1303,30 @@ void mvs_poisson_default_params(mvs_poisson_params* p) {
 int mvs_poisson_reconstruct_dev(int64_t n, const double* points_dev, const double* normals_dev, const mvs_poisson_params* p, mvs_poisson_info* info,
                                 double* vertices_dev, int64_t vertex_capacity, int32_t* faces_dev, int64_t face_capacity, void* hip_stream) {
     MVS_TRACE();
-    int rc = check_pn(__func__, n, points_dev, normals_dev, p, info, vertices_dev, vertex_capacity, faces_dev, face_capacity);
-    if (rc) return rc;
-    if ((rc = need_device())) return rc;
-    PnRun run(*p, *info, n, points_dev, normals_dev, (hipStream_t)hip_stream);
-    if ((rc = run.counts(__func__))) return rc;
-    if (info->n_vertices > vertex_capacity || info->n_faces > face_capacity) return too_small(__func__);
-    return run.scatter(vertices_dev, faces_dev);
+    const PnCall c{__func__, PN_PLAIN, n, points_dev, normals_dev, p, info, nullptr, nullptr, nullptr, nullptr};
+    const int rc = open_call(c, vertices_dev, vertex_capacity, faces_dev, face_capacity);
+    return rc ? rc : reconstruct(c, points_dev, normals_dev, PnOut{vertices_dev, nullptr, faces_dev, vertex_capacity, face_capacity}, (hipStream_t)hip_stream);
 }
 
 int mvs_poisson_reconstruct(int64_t n, const double* points, const double* normals, const mvs_poisson_params* p, mvs_poisson_info* info,
                             double* vertices, int64_t vertex_capacity, int32_t* faces, int64_t face_capacity) {
     MVS_TRACE();
-    int rc = check_pn(__func__, n, points, normals, p, info, vertices, vertex_capacity, faces, face_capacity);
-    if (rc) return rc;
-    if ((rc = need_device())) return rc;
-    Scratch dp, dn, dv, df;
-    if ((rc = up(dp, points, 3 * (size_t)n)) || (rc = up(dn, normals, 3 * (size_t)n))) return rc;
-    PnRun run(*p, *info, n, dp.as<double>(), dn.as<double>(), nullptr);
-    if ((rc = run.counts(__func__))) return rc;
-    if (info->n_vertices > vertex_capacity || info->n_faces > face_capacity) return too_small(__func__);
-    const size_t V = (size_t)info->n_vertices, F = (size_t)info->n_faces;
-    if ((rc = dv.alloc(24 * V)) || (rc = df.alloc(12 * F)) || (rc = run.scatter(dv.as<double>(), df.as<int32_t>()))) return rc;
-    if ((rc = down(vertices, dv, 3 * V))) return rc;
-    return down(faces, df, 3 * F);
+    return reconstruct_host(PnCall{__func__, PN_PLAIN, n, points, normals, p, info, nullptr, nullptr, nullptr, nullptr}, vertices, nullptr, vertex_capacity,
+                            faces, face_capacity);
 }
 
+// MVS_E_SOLVER still hands out the field the solve reached: the hooks go on after it
 int mvs_test_poisson_field(int64_t n, const double* points, const double* normals, const mvs_poisson_params* p, mvs_poisson_info* info, double* rhs,
                            double* chi, int64_t node_capacity) {
     MVS_TRACE();
-    int rc = check_pn(__func__, n, points, normals, p, info, rhs, node_capacity, chi, node_capacity);
-    if (rc) return rc;
-    if ((rc = need_device())) return rc;
+    const PnCall c{__func__, PN_PLAIN, n, points, normals, p, info, nullptr, nullptr, nullptr, nullptr};
     Scratch dp, dn;
-    if ((rc = up(dp, points, 3 * (size_t)n)) || (rc = up(dn, normals, 3 * (size_t)n))) return rc;
-    PnRun run(*p, *info, n, dp.as<double>(), dn.as<double>(), nullptr);
+    int rc = open_call(c, rhs, node_capacity, chi, node_capacity);
+    if (rc || (rc = up_points(c, dp, dn))) return rc;
+    PnRun run(c, dp.as<double>(), dn.as<double>(), nullptr);
     if ((rc = run.grid(__func__))) return rc;
     if (run.nn > node_capacity) return bad(__func__, "node_capacity is below (2^depth + 1)^3 (info holds the depth)");
-    const int frc = run.field(__func__);                                      // MVS_E_SOLVER still hands out the field it reached
+    const int frc = run.field(__func__);
     if (frc && frc != MVS_E_SOLVER) return frc;
     if (!frc && (rc = run.iso_value())) return rc;
     HIPCHK(hipMemcpy(rhs, run.rhs.p, 8 * (size_t)run.nn, hipMemcpyDeviceToHost));
@@ -1512,7 +1334,7 @@ int mvs_test_poisson_field(int64_t n, const double* points, const double* normal
     return frc;
 }
 
-// ------------------------------------------------------------------ rules 14-18 ----
+// ------------------------------------------------------------------ rules 14-17 ----
 void mvs_poisson_density_default_params(mvs_poisson_density_params* p) {
     if (!p) return;
     p->max_gain = 4.0; p->flags = 0; p->density_drop = 1;
@@ -1523,41 +1345,51 @@ int mvs_poisson_reconstruct_density_dev(int64_t n, const double* points_dev, con
                                         double* vertices_dev, double* vertex_density_dev, int64_t vertex_capacity, int32_t* faces_dev,
                                         int64_t face_capacity, void* hip_stream) {
     MVS_TRACE();
-    int rc = check_pn(__func__, n, points_dev, normals_dev, p, info, vertices_dev, vertex_capacity, faces_dev, face_capacity);
-    if (rc || (rc = check_pn_density(__func__, n, dparams, dinfo))) return rc;
-    if ((rc = need_device())) return rc;
-    PnRun run(*p, *info, n, points_dev, normals_dev, (hipStream_t)hip_stream);
-    run.dp = dparams;
-    run.dinfo = dinfo;
-    std::memset(dinfo, 0, sizeof *dinfo);
-    if ((rc = run.counts(__func__))) return rc;
-    if (info->n_vertices > vertex_capacity || info->n_faces > face_capacity) return too_small(__func__);
-    if ((rc = run.scatter(vertices_dev, faces_dev))) return rc;
-    return run.vertex_density(vertices_dev, vertex_density_dev);
+    const PnCall c{__func__, PN_DENSITY, n, points_dev, normals_dev, p, info, dparams, dinfo, nullptr, nullptr};
+    const int rc = open_call(c, vertices_dev, vertex_capacity, faces_dev, face_capacity);
+    return rc ? rc : reconstruct(c, points_dev, normals_dev, PnOut{vertices_dev, vertex_density_dev, faces_dev, vertex_capacity, face_capacity},
+                                 (hipStream_t)hip_stream);
 }
 
 int mvs_poisson_reconstruct_density(int64_t n, const double* points, const double* normals, const mvs_poisson_params* p,
                                     const mvs_poisson_density_params* dparams, mvs_poisson_info* info, mvs_poisson_density_info* dinfo,
                                     double* vertices, double* vertex_density, int64_t vertex_capacity, int32_t* faces, int64_t face_capacity) {
     MVS_TRACE();
-    int rc = check_pn(__func__, n, points, normals, p, info, vertices, vertex_capacity, faces, face_capacity);
-    if (rc || (rc = check_pn_density(__func__, n, dparams, dinfo))) return rc;
-    if ((rc = need_device())) return rc;
-    Scratch dp, dn, dv, dd, df;
-    if ((rc = up(dp, points, 3 * (size_t)n)) || (rc = up(dn, normals, 3 * (size_t)n))) return rc;
-    PnRun run(*p, *info, n, dp.as<double>(), dn.as<double>(), nullptr);
-    run.dp = dparams;
-    run.dinfo = dinfo;
-    std::memset(dinfo, 0, sizeof *dinfo);
-    if ((rc = run.counts(__func__))) return rc;
-    if (info->n_vertices > vertex_capacity || info->n_faces > face_capacity) return too_small(__func__);
-    const size_t V = (size_t)info->n_vertices, F = (size_t)info->n_faces;
-    if ((rc = dv.alloc(24 * V)) || (rc = df.alloc(12 * F)) || (rc = run.scatter(dv.as<double>(), df.as<int32_t>()))) return rc;
-    if (vertex_density) {
-        if ((rc = dd.alloc(8 * V)) || (rc = run.vertex_density(dv.as<double>(), dd.as<double>())) || (rc = down(vertex_density, dd, V))) return rc;
-    }
-    if ((rc = down(vertices, dv, 3 * V))) return rc;
-    return down(faces, df, 3 * F);
+    return reconstruct_host(PnCall{__func__, PN_DENSITY, n, points, normals, p, info, dparams, dinfo, nullptr, nullptr}, vertices, vertex_density,
+                            vertex_capacity, faces, face_capacity);
+}
+
+int mvs_test_poisson_density(int64_t n, const double* points, const double* normals, const mvs_poisson_params* p,
+                             const mvs_poisson_density_params* dparams, mvs_poisson_info* info, mvs_poisson_density_info* dinfo,
+                             int64_t* node_sums, int64_t density_node_capacity, double* rho, double* gain, double* rhs, double* chi,
+                             int64_t node_capacity) {
+    MVS_TRACE();
+    const PnCall c{__func__, PN_DENSITY, n, points, normals, p, info, dparams, dinfo, nullptr, nullptr};
+    Scratch dp, dn;
+    int rc = check_call(c, node_sums, density_node_capacity, rhs, node_capacity);
+    if (rc) return rc;
+    if (!rho || !gain) return bad(__func__, "rho or gain is NULL");
+    if ((rc = need_device()) || (rc = up_points(c, dp, dn))) return rc;
+    PnRun run(c, dp.as<double>(), dn.as<double>(), nullptr);
+    if ((rc = run.grid(__func__))) return rc;
+    int Dd = 0;
+    const PnGrid gd = pn_density_grid(run.g, run.side, info->depth, dparams->density_drop, &Dd);
+    dinfo->density_depth = Dd;
+    if ((int64_t)(gd.G + 1) * (gd.G + 1) * (gd.G + 1) > density_node_capacity || run.nn > node_capacity)
+        return bad(__func__, "a node capacity is below (2^depth + 1)^3 (info and dinfo hold the depths)");
+    if ((rc = run.density())) return rc;
+    int frc = MVS_OK;
+    if (chi) {
+        frc = run.field(__func__);
+        if (frc && frc != MVS_E_SOLVER) return frc;
+        if (!frc && (rc = run.iso_value())) return rc;
+        HIPCHK(hipMemcpy(chi, run.L.x[info->depth], 8 * (size_t)run.nn, hipMemcpyDeviceToHost));
+    } else if ((rc = run.right_side())) return rc;
+    HIPCHK(hipMemcpy(node_sums, run.dsum.p, 8 * (size_t)run.nnd, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(rho, run.rho.p, 8 * (size_t)n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(gain, run.gain.p, 8 * (size_t)n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(rhs, run.rhs.p, 8 * (size_t)run.nn, hipMemcpyDeviceToHost));
+    return frc;
 }
 
 // ------------------------------------------------------------------ rules 19-23 ----
@@ -1572,20 +1404,10 @@ int mvs_poisson_reconstruct_screened_dev(int64_t n, const double* points_dev, co
                                          double* vertices_dev, double* vertex_density_dev, int64_t vertex_capacity, int32_t* faces_dev,
                                          int64_t face_capacity, void* hip_stream) {
     MVS_TRACE();
-    int rc = check_pn(__func__, n, points_dev, normals_dev, p, info, vertices_dev, vertex_capacity, faces_dev, face_capacity);
-    if (rc || (rc = check_pn_density(__func__, n, dparams, dinfo)) || (rc = check_pn_screen(__func__, sparams, sinfo))) return rc;
-    if ((rc = need_device())) return rc;
-    PnRun run(*p, *info, n, points_dev, normals_dev, (hipStream_t)hip_stream);
-    run.dp = dparams;
-    run.dinfo = dinfo;
-    run.sp = sparams;
-    run.sinfo = sinfo;
-    std::memset(dinfo, 0, sizeof *dinfo);
-    std::memset(sinfo, 0, sizeof *sinfo);
-    if ((rc = run.counts(__func__))) return rc;
-    if (info->n_vertices > vertex_capacity || info->n_faces > face_capacity) return too_small(__func__);
-    if ((rc = run.scatter(vertices_dev, faces_dev))) return rc;
-    return run.vertex_density(vertices_dev, vertex_density_dev);
+    const PnCall c{__func__, PN_SCREENED, n, points_dev, normals_dev, p, info, dparams, dinfo, sparams, sinfo};
+    const int rc = open_call(c, vertices_dev, vertex_capacity, faces_dev, face_capacity);
+    return rc ? rc : reconstruct(c, points_dev, normals_dev, PnOut{vertices_dev, vertex_density_dev, faces_dev, vertex_capacity, face_capacity},
+                                 (hipStream_t)hip_stream);
 }
 
 int mvs_poisson_reconstruct_screened(int64_t n, const double* points, const double* normals, const mvs_poisson_params* p,
@@ -1593,27 +1415,8 @@ int mvs_poisson_reconstruct_screened(int64_t n, const double* points, const doub
                                      mvs_poisson_density_info* dinfo, mvs_poisson_screen_info* sinfo, double* vertices, double* vertex_density,
                                      int64_t vertex_capacity, int32_t* faces, int64_t face_capacity) {
     MVS_TRACE();
-    int rc = check_pn(__func__, n, points, normals, p, info, vertices, vertex_capacity, faces, face_capacity);
-    if (rc || (rc = check_pn_density(__func__, n, dparams, dinfo)) || (rc = check_pn_screen(__func__, sparams, sinfo))) return rc;
-    if ((rc = need_device())) return rc;
-    Scratch dp, dn, dv, dd, df;
-    if ((rc = up(dp, points, 3 * (size_t)n)) || (rc = up(dn, normals, 3 * (size_t)n))) return rc;
-    PnRun run(*p, *info, n, dp.as<double>(), dn.as<double>(), nullptr);
-    run.dp = dparams;
-    run.dinfo = dinfo;
-    run.sp = sparams;
-    run.sinfo = sinfo;
-    std::memset(dinfo, 0, sizeof *dinfo);
-    std::memset(sinfo, 0, sizeof *sinfo);
-    if ((rc = run.counts(__func__))) return rc;
-    if (info->n_vertices > vertex_capacity || info->n_faces > face_capacity) return too_small(__func__);
-    const size_t V = (size_t)info->n_vertices, F = (size_t)info->n_faces;
-    if ((rc = dv.alloc(24 * V)) || (rc = df.alloc(12 * F)) || (rc = run.scatter(dv.as<double>(), df.as<int32_t>()))) return rc;
-    if (vertex_density) {
-        if ((rc = dd.alloc(8 * V)) || (rc = run.vertex_density(dv.as<double>(), dd.as<double>())) || (rc = down(vertex_density, dd, V))) return rc;
-    }
-    if ((rc = down(vertices, dv, 3 * V))) return rc;
-    return down(faces, df, 3 * F);
+    return reconstruct_host(PnCall{__func__, PN_SCREENED, n, points, normals, p, info, dparams, dinfo, sparams, sinfo}, vertices, vertex_density,
+                            vertex_capacity, faces, face_capacity);
 }
 
 int mvs_test_poisson_screened(int64_t n, const double* points, const double* normals, const mvs_poisson_params* p,
@@ -1621,21 +1424,15 @@ int mvs_test_poisson_screened(int64_t n, const double* points, const double* nor
                               mvs_poisson_density_info* dinfo, mvs_poisson_screen_info* sinfo, int64_t* stencil, double* f, double* chi0, double* chi,
                               int64_t node_capacity, int32_t diagonal) {
     MVS_TRACE();
-    int rc = check_pn(__func__, n, points, normals, p, info, f, node_capacity, chi, node_capacity);
-    if (rc || (rc = check_pn_density(__func__, n, dparams, dinfo)) || (rc = check_pn_screen(__func__, sparams, sinfo))) return rc;
+    const PnCall c{__func__, PN_SCREENED, n, points, normals, p, info, dparams, dinfo, sparams, sinfo};
+    Scratch dp, dn, dense;
+    int rc = check_call(c, f, node_capacity, chi, node_capacity);
+    if (rc) return rc;
     if (!stencil || !chi0) return bad(__func__, "stencil or chi0 is NULL");
     if (diagonal < 0 || diagonal > 2) return bad(__func__, "diagonal is not 0, 1 or 2");
-    if ((rc = need_device())) return rc;
-    Scratch dp, dn, dense;
-    if ((rc = up(dp, points, 3 * (size_t)n)) || (rc = up(dn, normals, 3 * (size_t)n))) return rc;
-    PnRun run(*p, *info, n, dp.as<double>(), dn.as<double>(), nullptr);
-    run.dp = dparams;
-    run.dinfo = dinfo;
-    run.sp = sparams;
-    run.sinfo = sinfo;
+    if ((rc = need_device()) || (rc = up_points(c, dp, dn))) return rc;
+    PnRun run(c, dp.as<double>(), dn.as<double>(), nullptr);
     run.diag = diagonal;
-    std::memset(dinfo, 0, sizeof *dinfo);
-    std::memset(sinfo, 0, sizeof *sinfo);
     if ((rc = run.grid(__func__))) return rc;
     if (run.nn > node_capacity) return bad(__func__, "node_capacity is below (2^depth + 1)^3 (info holds the depth)");
     const size_t nn = (size_t)run.nn;
@@ -1647,7 +1444,7 @@ int mvs_test_poisson_screened(int64_t n, const double* points, const double* nor
     HIPCHK(hipMemcpy(stencil, dense.p, 8 * 27 * nn, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(f, run.rhs.p, 8 * nn, hipMemcpyDeviceToHost));
     int src = MVS_OK;
-    if (sparams->alpha > 0.0) {                                              // MVS_E_SOLVER still hands out the field it reached
+    if (sparams->alpha > 0.0) {
         src = run.screen_solve(__func__);
         if (src && src != MVS_E_SOLVER) return src;
         if (!src && (rc = run.iso_value())) return rc;
@@ -1656,66 +1453,5 @@ int mvs_test_poisson_screened(int64_t n, const double* points, const double* nor
     return src;
 }
 
-int mvs_mesh_trim_by_value_dev(int64_t V, const double* vertices_dev, const double* normals_dev, int64_t F, const int32_t* faces_dev,
-                               const double* values_dev, double threshold, double* vertices_out_dev, double* normals_out_dev,
-                               int32_t* faces_out_dev, int64_t* V_out, int64_t* F_out, void* hip_stream) {
-    MVS_TRACE();
-    int rc = check_trim(__func__, V, vertices_dev, normals_dev, F, faces_dev, values_dev, threshold, vertices_out_dev, normals_out_dev, faces_out_dev,
-                        V_out, F_out);
-    if (rc || (rc = need_device())) return rc;
-    return mesh_trim_dev(V, vertices_dev, normals_dev, F, faces_dev, values_dev, threshold, vertices_out_dev, normals_out_dev, faces_out_dev, V_out,
-                         F_out, (hipStream_t)hip_stream);
-}
-
-int mvs_mesh_trim_by_value(int64_t V, const double* vertices, const double* normals, int64_t F, const int32_t* faces, const double* values,
-                           double threshold, double* vertices_out, double* normals_out, int32_t* faces_out, int64_t* V_out, int64_t* F_out) {
-    MVS_TRACE();
-    int rc = check_trim(__func__, V, vertices, normals, F, faces, values, threshold, vertices_out, normals_out, faces_out, V_out, F_out);
-    if (rc || (rc = need_device())) return rc;
-    Scratch dv, dn, df, dval, ov, on, of;
-    if ((rc = up(dv, vertices, 3 * (size_t)V)) || (rc = up(df, faces, 3 * (size_t)F)) || (rc = up(dval, values, (size_t)V)) ||
-        (normals && (rc = up(dn, normals, 3 * (size_t)V))) || (rc = ov.alloc(24 * (size_t)V)) || (rc = of.alloc(12 * (size_t)F)) ||
-        (normals && (rc = on.alloc(24 * (size_t)V)))) return rc;
-    if ((rc = mesh_trim_dev(V, dv.as<double>(), normals ? dn.as<double>() : nullptr, F, df.as<int32_t>(), dval.as<double>(), threshold, ov.as<double>(),
-                            normals ? on.as<double>() : nullptr, of.as<int32_t>(), V_out, F_out, nullptr))) return rc;
-    if ((rc = down(vertices_out, ov, 3 * (size_t)*V_out)) || (normals && (rc = down(normals_out, on, 3 * (size_t)*V_out)))) return rc;
-    return down(faces_out, of, 3 * (size_t)*F_out);
-}
-
-int mvs_test_poisson_density(int64_t n, const double* points, const double* normals, const mvs_poisson_params* p,
-                             const mvs_poisson_density_params* dparams, mvs_poisson_info* info, mvs_poisson_density_info* dinfo,
-                             int64_t* node_sums, int64_t density_node_capacity, double* rho, double* gain, double* rhs, double* chi,
-                             int64_t node_capacity) {
-    MVS_TRACE();
-    int rc = check_pn(__func__, n, points, normals, p, info, node_sums, density_node_capacity, rhs, node_capacity);
-    if (rc || (rc = check_pn_density(__func__, n, dparams, dinfo))) return rc;
-    if (!rho || !gain) return bad(__func__, "rho or gain is NULL");
-    if ((rc = need_device())) return rc;
-    Scratch dp, dn;
-    if ((rc = up(dp, points, 3 * (size_t)n)) || (rc = up(dn, normals, 3 * (size_t)n))) return rc;
-    PnRun run(*p, *info, n, dp.as<double>(), dn.as<double>(), nullptr);
-    run.dp = dparams;
-    run.dinfo = dinfo;
-    std::memset(dinfo, 0, sizeof *dinfo);
-    if ((rc = run.grid(__func__))) return rc;
-    int Dd = 0;
-    const PnGrid gd = pn_density_grid(run.g, run.side, info->depth, dparams->density_drop, &Dd);
-    dinfo->density_depth = Dd;
-    if ((int64_t)(gd.G + 1) * (gd.G + 1) * (gd.G + 1) > density_node_capacity || run.nn > node_capacity)
-        return bad(__func__, "a node capacity is below (2^depth + 1)^3 (info and dinfo hold the depths)");
-    if ((rc = run.density())) return rc;
-    int frc = MVS_OK;
-    if (chi) {                                                                // as mvs_test_poisson_field: MVS_E_SOLVER still hands out the field
-        frc = run.field(__func__);
-        if (frc && frc != MVS_E_SOLVER) return frc;
-        if (!frc && (rc = run.iso_value())) return rc;
-        HIPCHK(hipMemcpy(chi, run.L.x[info->depth], 8 * (size_t)run.nn, hipMemcpyDeviceToHost));
-    } else if ((rc = run.right_side())) return rc;
-    HIPCHK(hipMemcpy(node_sums, run.dsum.p, 8 * (size_t)run.nnd, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(rho, run.rho.p, 8 * (size_t)n, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(gain, run.gain.p, 8 * (size_t)n, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(rhs, run.rhs.p, 8 * (size_t)run.nn, hipMemcpyDeviceToHost));
-    return frc;
-}
-
 }  // extern "C"
+

@@ -17,6 +17,10 @@ struct PnGrid {                         // rule 4: nodes (ix, iy, iz) in [0, G]^
 };
 
 __host__ __device__ inline int64_t pn_node(int32_t G, int ix, int iy, int iz) { return ((int64_t)iz * (G + 1) + iy) * (G + 1) + ix; }
+// corner c = bx + 2 by + 4 bz of the cube whose lower corner is node i0
+__host__ __device__ inline int64_t pn_corner_node(int32_t G, const int i0[3], int c) {
+    return pn_node(G, i0[0] + (c & 1), i0[1] + (c >> 1 & 1), i0[2] + (c >> 2 & 1));
+}
 
 // rule 1
 __host__ __device__ inline bool pn_used(const double* p, const double* n) {
@@ -62,7 +66,7 @@ __host__ __device__ inline double pn_density_at(const double* p, const PnGrid& g
     int i0[3];
     double w[8], v = 0.0;
     pn_corners_weights(p, gd, i0, w);
-    for (int c = 0; c < 8; ++c) v = v + w[c] * pn_dequant(sums[pn_node(gd.G, i0[0] + (c & 1), i0[1] + (c >> 1 & 1), i0[2] + (c >> 2 & 1))]);
+    for (int c = 0; c < 8; ++c) v = v + w[c] * pn_dequant(sums[pn_corner_node(gd.G, i0, c)]);
     return v;
 }
 

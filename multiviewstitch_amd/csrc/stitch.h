@@ -27,17 +27,27 @@ int render_views_dev(const double* pts, int64_t V, const int32_t* faces, int64_t
 // Validates like mvs_point_sample, reporting under the name fn.
 int point_sample_vectors(const char* fn, int32_t n_seq, const int32_t* cam_off, const mvs_camera* cams, const float* depths,
                          const mvs_point_sample_params* p, int64_t* seq_offsets, std::vector<double>* points, std::vector<double>* normals);
-// mvs_poisson_reconstruct_dev (poisson.hip) with outputs that size themselves: vertices / faces are allocated once info holds the
-// counts.  Validates like mvs_poisson_reconstruct, reporting under the name fn; the caller has a device.  Default stream.
-int poisson_blocks(const char* fn, int64_t n, const double* points_dev, const double* normals_dev, const mvs_poisson_params* p,
-                   mvs_poisson_info* info, Scratch* vertices, Scratch* faces);
-// the same for mvs_poisson_reconstruct_density_dev: density receives d_v of rule 17 per vertex; with sp (and sinfo) for
-// mvs_poisson_reconstruct_screened_dev
-int poisson_density_blocks(const char* fn, int64_t n, const double* points_dev, const double* normals_dev, const mvs_poisson_params* p,
-                           const mvs_poisson_density_params* dp, mvs_poisson_info* info, mvs_poisson_density_info* dinfo, Scratch* vertices,
-                           Scratch* density, Scratch* faces, const mvs_poisson_screen_params* sp = nullptr,
-                           mvs_poisson_screen_info* sinfo = nullptr);
-// mvs_mesh_trim_by_value_dev (poisson.hip, rule 18) with arguments the caller has validated.  Synchronises s.
+// One call of the Poisson stage (poisson.hip), whichever entry made it: `rules` says which of mvs_poisson_reconstruct (PN_PLAIN),
+// _density (PN_DENSITY: dp and dinfo) and _screened (PN_SCREENED: sp and sinfo too) it is; the parts it does not have are NULL.  The
+// points are the entry's own, host or device.
+enum { PN_PLAIN, PN_DENSITY, PN_SCREENED };
+struct PnCall {
+    const char* fn;                       // the name errors are reported under
+    int rules;
+    int64_t n;
+    const double *points, *normals;
+    const mvs_poisson_params* p;
+    mvs_poisson_info* info;
+    const mvs_poisson_density_params* dp;
+    mvs_poisson_density_info* dinfo;
+    const mvs_poisson_screen_params* sp;
+    mvs_poisson_screen_info* sinfo;
+};
+// the device form of the call (points on the device) with outputs that size themselves: vertices / faces and, with rules above
+// PN_PLAIN, density (d_v of rule 17 per vertex) are allocated once info holds the counts.  Validates like the public entry; the caller
+// has a device.  Default stream.
+int poisson_blocks(const PnCall& c, Scratch* vertices, Scratch* density, Scratch* faces);
+// mvs_mesh_trim_by_value_dev (mesh_trim.hip, rule 18) with arguments the caller has validated.  Synchronises s.
 int mesh_trim_dev(int64_t V, const double* vertices, const double* normals, int64_t F, const int32_t* faces, const double* values, double thr,
                   double* vertices_out, double* normals_out, int32_t* faces_out, int64_t* V_out, int64_t* F_out, hipStream_t s);
 #endif

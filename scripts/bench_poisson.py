@@ -18,8 +18,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 GROUPS = {"cube_depth": ("k_pn_bbox", "k_pn_occupy", "k_pn_popcount"), "splat": ("k_pn_splat<false>", "k_pn_splat<true>"), "rhs": ("k_pn_rhs",),
-          "smooth": ("k_mg_smooth",), "residual": ("k_mg_residual",), "restrict": ("k_mg_restrict",), "prolong": ("k_mg_prolong",),
-          "coarse_levels": ("k_mg_coarse",), "fold": ("k_pn_fold",), "iso": ("k_pn_iso",), "cube_mask": ("k_pn_cubemask",),
+          "smooth": ("k_mg_smooth<(anonymous namespace)::MgPlain>",), "residual": ("k_mg_residual<(anonymous namespace)::MgPlain>",),
+          "restrict": ("k_mg_restrict",), "prolong": ("k_mg_prolong",), "coarse_levels": ("k_mg_coarse<(anonymous namespace)::MgPlain>",), "fold": ("k_pn_fold",), "iso": ("k_pn_iso",), "cube_mask": ("k_pn_cubemask",),
           "edge_count": ("k_pn_edge_count",), "vertex_scatter": ("k_pn_vertex_scatter",), "face_count": ("k_pn_face_count",),
           "face_scatter": ("k_pn_face_scatter",), "scan": ("k_ct_scan", "k_ct_strided")}
 

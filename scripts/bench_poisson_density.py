@@ -1,4 +1,4 @@
-"""Timing of the sampling-density rules of the Poisson stage (csrc/poisson.hip, rules 14-18 of include/mvs.h) with the set-up of
+"""Timing of the sampling-density rules of the Poisson stage (csrc/poisson.hip and, the trim, csrc/mesh_trim.hip; rules 14-18 of include/mvs.h) with the set-up of
 scripts/bench_poisson.py: 2 M oriented points on a rotated ellipsoid (semi-axes 1, 0.7, 0.5), resident in HBM, depth 8 and depth 9
 (depth_min = depth_max).  Per depth, from HIP events on the call's stream, three calls after a warm-up each: the plain call
 (mvs_poisson_reconstruct_dev) and, in the same run, the call with the weighting and the vertex density

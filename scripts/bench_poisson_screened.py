@@ -23,8 +23,10 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-GROUPS = {"smooth_plain": ("k_mg_smooth(",), "smooth_screened": ("k_mg_smooth_sc",), "smooth_rows": ("k_sc_smooth_rows",), "residual_plain": ("k_mg_residual(",),
-          "residual_screened": ("k_mg_residual_sc",), "coarse_plain": ("k_mg_coarse(",), "coarse_screened": ("k_mg_coarse_sc",),
+PLAIN, SCREENED = "<(anonymous namespace)::MgPlain", "<(anonymous namespace)::MgScreened"      # the operator, first template argument of a multigrid kernel
+GROUPS = {"smooth_plain": ("k_mg_smooth" + PLAIN,), "smooth_screened": ("k_mg_smooth" + SCREENED,), "smooth_rows": ("k_sc_smooth_rows",),
+          "residual_plain": ("k_mg_residual" + PLAIN,), "residual_screened": ("k_mg_residual" + SCREENED,), "coarse_plain": ("k_mg_coarse" + PLAIN,),
+          "coarse_screened": ("k_mg_coarse" + SCREENED,),
           "restrict": ("k_mg_restrict",), "prolong": ("k_mg_prolong",), "stencil_flag": ("k_sc_flag(",), "stencil_number": ("k_sc_count", "k_sc_number"),
           "stencil_splat": ("k_sc_splat",), "stencil_coarsen": ("k_sc_flag_coarse", "k_sc_coarsen"), "stencil_convert": ("k_sc_convert",), "screen_rhs": ("k_sc_rhs",), "occupy": ("k_pn_occupy", "k_pn_popcount")}
 

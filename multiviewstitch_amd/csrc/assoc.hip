@@ -1,12 +1,22 @@
 // assoc.hip — node -> target correspondence search, the "HOT LOOP 1" of
-// Deformation::Deform (R/Deformation/Deformation.cpp:266-357), as three kernels
-// split at the exchange points of a view-sharded run:
+// Deformation::Deform (R/Deformation/Deformation.cpp:266-357).  Per node: the exact 1-NN squared distance d2min (float32, FLANN's
+// L2 order, :283-284), the ball d2 <= 2 * d2min (:288), the normal filter (:304-315), projLen / projDist (:330-335), the best
+// <= top_k members by the total order (projDist, |projLen|, index), their means (:338-349) and the rejection
+// tests (:350-353).  Three generations of searches compute this, all of them live:
 //
-//   k_assoc_dmin   : exact 1-NN squared distance (float32, FLANN's L2 order)     :283-284
-//   k_assoc_select : ball d2 <= 2*d2min (:288), normal filter (:304-315),
-//                    projLen/projDist (:330-335), best <= top_k by the total
-//                    order (projDist, |projLen|, index)  
-//   k_assoc_merge  : merge rank lists, means (:338-349), rejection tests (:350-353)
+//   sharded (deform_iterate.cpp, mvs_deform_assoc_*): three kernels split at the exchange points of a view-sharded run (SURVEY.md
+//       §8e) — k_assoc_dmin | all-reduce(MIN) | k_assoc_select (+ k_assoc_select_heavy or k_assoc_heavy_knn) | all-gather |
+//       k_assoc_merge (k_install_targets when every rank merges a block of the nodes only)
+//   fused (deform_pass.cpp, the first two associations of a fit): k_assoc_local = dmin + select + node target by one wave, the
+//       nodes with wide balls deferred to a workgroup each in k_assoc_select_heavy or — beside the node graph and the cotangent
+//       weights — k_assoc_heavy_knn
+//   bounded (deform_pass.cpp, from the third association of a fit on): k_assoc_prep (bound and class of every node) + k_assoc_all
+//       (heavy nodes: heavy_bounded, a workgroup each | mid: the fused code with the bound as its limit | near: near_nodes, 16
+//       lanes each | graph queries | weights); deform_group.cpp launches them once for all parts of a group (k_assoc_prep_multi,
+//       k_assoc_all_multi)
+//
+// The generations differ in how they FIND a ball's members.  What is done with them — the projection keys, the sorted top-k list,
+// the merge slots of a workgroup and their rank merge, the record write, the node verdict — is stated once, in assoc_dev.h.
 //
 // One wave64 per node.  Points are counting-sorted into a dense grid stored TILED (coarse cell = 8x8x8 fine cells,
 // grid_dev.h), so a run of x-adjacent fine cells or a whole coarse cell is one contiguous, coalesced range of float4
@@ -26,51 +36,11 @@
 #include "grid_dev.h"
 #include "knn_dev.h"
 #include "arap_dev.h"
+#include "assoc_dev.h"
 #include <algorithm>
 #include <mutex>
 
 namespace {
-
-#ifdef MVS_STAMPS
-__device__ unsigned long long g_wave_stamps[8 * 20000];       // k_assoc_local: start / end of every one-wave workgroup
-__device__ unsigned long long g_assoc_cycles[2 * 16384];      // per node: cycles of k_assoc_dmin, k_assoc_select
-__device__ unsigned long long g_dmin_shell[16384 * 8];          // per node: cycles at the end of coarse shells 0..5, cycles at the start of the coarse walk
-#define ASTAMP_BEGIN unsigned long long t0_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t0_) :: "memory")
-#define ASTAMP_END(slot) do { unsigned long long t1_; asm volatile("s_waitcnt vmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t1_) :: "memory"); \
-        if ((threadIdx.x & 63) == 0 && node < 16384) g_assoc_cycles[2 * node + (slot)] = t1_ - t0_; } while (0)
-#else
-#define ASTAMP_BEGIN
-#define ASTAMP_END(slot)
-#endif
-
-__device__ inline int rl_i(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
-__device__ inline double rl_d(double v, int l) {
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffLL), l);
-    const int hi = __builtin_amdgcn_readlane((int)(b >> 32), l);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-__device__ inline long long rl_ll(long long b, int l) {
-    const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffLL), l);
-    const int hi = __builtin_amdgcn_readlane((int)(b >> 32), l);
-    return ((long long)hi << 32) | (unsigned int)lo;
-}
-// value of the lane below (lane 0 of a 16-lane row keeps its own): DPP row_shr:1, one VALU move per 32 bits.  The
-// candidate lists live in lanes 0..7 (top_k <= 8), so the row-local shift is all an insertion needs (__shfl_up would
-// go through the LDS crossbar: ~12 ds_bpermute per insertion).
-__device__ inline int shr1_i(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x111, 0xf, 0xf, false); }
-__device__ inline long long shfl_up_ll(long long b) {
-    const int lo = shr1_i((int)(b & 0xffffffffLL));
-    const int hi = shr1_i((int)(b >> 32));
-    return ((long long)hi << 32) | (unsigned int)lo;
-}
-__device__ inline double shfl_up_d(double v) { return __longlong_as_double(shfl_up_ll(__double_as_longlong(v))); }
-
-__device__ inline bool key_less(double pd_a, double apl_a, long long i_a, double pd_b, double apl_b, long long i_b) {
-    if (pd_a != pd_b) return pd_a < pd_b;
-    if (apl_a != apl_b) return apl_a < apl_b;
-    return i_a < i_b;
-}
 
 struct QCell {
     float fx, fy, fz;      // query in fine-cell units
@@ -201,10 +171,7 @@ __device__ inline float dmin_node(const GridDev& g, const double* __restrict__ n
         }
         // ---- stage B: coarse occupancy grid, expanding shells with pruning; a coarse cell is ONE range
         if (!found) {
-#ifdef MVS_STAMPS
-            { unsigned long long t1_; asm volatile("s_waitcnt vmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t1_) :: "memory");
-              if (lane == 0 && node < 16384) g_dmin_shell[8 * node + 6] = t1_ - t0_; }
-#endif
+            ASTAMP_LAP(lane == 0 && node < 16384, g_dmin_shell[8 * node + 6]);
             const int CX = c.cx >> 3, CY = c.cy >> 3, CZ = c.cz >> 3;
             const float ih2 = g.inv_h * g.inv_h;
             float Mc = fminf(fminf(fminf(c.fx - 8.f * CX, 8.f * CX + 8.f - c.fx), fminf(c.fy - 8.f * CY, 8.f * CY + 8.f - c.fy)),
@@ -264,10 +231,7 @@ __device__ inline float dmin_node(const GridDev& g, const double* __restrict__ n
                         }
                     }
                 }
-#ifdef MVS_STAMPS
-                if (S < 6) { unsigned long long t1_; asm volatile("s_waitcnt vmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t1_) :: "memory");
-                             if (lane == 0 && node < 16384) g_dmin_shell[8 * node + S] = t1_ - t0_; }
-#endif
+                if (S < 6) ASTAMP_LAP(lane == 0 && node < 16384, g_dmin_shell[8 * node + S]);
                 const float bound = (((float)S) * 8.f + Mc - 0.08f) * g.h;
                 if (bound > 0.0f && (best <= bound * bound || bound * bound > limit2)) break;
             }
@@ -307,25 +271,7 @@ __global__ __launch_bounds__(256) void k_assoc_dmin(GridDev g, const double* __r
 // One node by one wave (PARTS == 1) or by the PARTS waves of a workgroup (heavy nodes: each wave takes every
 // PARTS-th occupied coarse cell of the ball, the per-wave lists are merged through LDS by wave 0).
 // A PARTS == 1 caller that passes a `heavy` list defers nodes whose ball spans more than 64 grid rows to it.
-#ifndef MVS_HEAVY_WAVES
-#define MVS_HEAVY_WAVES 16
-#endif
-constexpr int HEAVY_WAVES = MVS_HEAVY_WAVES;                // waves of a workgroup that takes a heavy node (16, or 8: two such workgroups to a CU)
-constexpr int HEAVY_RANGES = 2048;
-constexpr int HEAVY_CAND = 10240;                           // members of a ball the workgroup list holds (>= params.max_result = 10000)
-constexpr int HEAVY_PIECE = 256;                            // a listed cell is dealt out in pieces of this many points
-constexpr int HEAVY_ROWS = 25;                              // rows of the ball's bounding box above which a node is deferred
-struct HeavyLds { double pd[HEAVY_WAVES][8], pl[HEAVY_WAVES][8], x[HEAVY_WAVES][8], y[HEAVY_WAVES][8], z[HEAVY_WAVES][8];
-                  long long idx[HEAVY_WAVES][8]; int nb[HEAVY_WAVES], np[HEAVY_WAVES];
-                  int nr, ra[HEAVY_RANGES], rb[HEAVY_RANGES];         // occupied coarse cells of the ball, found by all waves
-                  float fmin[HEAVY_WAVES];                            // per-wave nearest distances of dmin_coarse_wg
-                  int next;                                           // next piece of the range list nobody has taken yet
-                  int hist[256], sel_bin, sel_before, nwin, npass;    // radix select of the 8th smallest (float) projection distance
-                  int cand[HEAVY_CAND];                               // ball members (sorted-order indices) found by phase 1 of the listed pieces
-                  int len[HEAVY_WAVES];                               // live entries of each wave's list (rank merge)
-                  double r_pd[8], r_pl[8], r_x[8], r_y[8], r_z[8]; long long r_idx[8];   // the merged list, best first
-                  int ball;                                           // ball members counted so far by all waves (full-result cut-off)
-                  unsigned w8[HEAVY_WAVES][8], T; int ovf; };         // bounded pass (heavy_bounded): the waves' smallest keys, the threshold, "does not fit"
+// (HEAVY_* and the workgroup's LDS, HeavyLds: assoc_dev.h)
 constexpr int HEAVY_DMIN_FLAG = 0x40000000;                 // heavy-list entry: the node's nearest distance is still open (coarse walk deferred)
 
 // The coarse-shell walk of dmin_node (stage B) by ALL waves of a workgroup: a far node (it faces a hole of the scan, its
@@ -406,18 +352,16 @@ __device__ inline void select_node(const GridDev& g, const double* __restrict__ 
                                    int32_t* __restrict__ counts, int32_t* __restrict__ heavy, int heavy_cap, HeavyLds* lds,
                                    const LocalMerge& lm) {
     ASTAMP_BEGIN;
-    const int64_t out = node;
     const int lane = threadIdx.x & 63, part = PARTS > 1 ? (int)(threadIdx.x >> 6) : 0;
     const int nparts = PARTS;                                // shares the node's ranges are dealt into
     int k_occ = 0;                                           // running index of the occupied rows (PARTS > 1)
     const d3 orig = ld3(node_pts + 3 * node), nn = ld3(node_nrm + 3 * node);
     const float qx = (float)orig.x, qy = (float)orig.y, qz = (float)orig.z;
 
-    // wave-resident sorted list: lane i (< len) holds the i-th best candidate
-    double L_pd = 0, L_pl = 0, L_x = 0, L_y = 0, L_z = 0;
-    long long L_idx = -1;
-    int len = 0;
-    double t_pd = 0, t_apl = 0; long long t_idx = 0;       // key of the current top_k-th element
+    TopK list;                                               // the wave's sorted list of the node's best candidates
+#ifdef MVS_STAMP_INSERT
+    if (PARTS == 1) list.stamp_node = node;
+#endif
     int n_ball = 0, n_pass = 0;
     bool slots_ready = false;          // PARTS > 1: the workgroup selection below has already put the node's candidates into the merge slots
 
@@ -433,53 +377,12 @@ __device__ inline void select_node(const GridDev& g, const double* __restrict__ 
         const QCell c = query_cell(g, qx, qy, qz);
         const int32_t* __restrict__ cs = g.cell_start;
 
-        // top-k insertion of the lanes' candidates (has: this lane holds one) into the wave-resident sorted list
-#ifdef MVS_STAMP_INSERT
-        unsigned long long ins_cycles = 0, ins_count = 0;
-#endif
-        auto insert = [&](bool has, double pd, double pl, d3 tp, long long gi) {
-#ifdef MVS_STAMP_INSERT
-            unsigned long long ti0_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ti0_) :: "memory");
-#endif
-            const double apl = fabs(pl);
-            unsigned long long pend = __ballot(has && (len < top_k || key_less(pd, apl, gi, t_pd, t_apl, t_idx)));
-            while (pend) {
-                const int src = __ffsll((long long)pend) - 1;
-                const double c_pd = rl_d(pd, src), c_pl = rl_d(pl, src);
-                const double c_x = rl_d(tp.x, src), c_y = rl_d(tp.y, src), c_z = rl_d(tp.z, src);
-                const long long c_i = rl_ll(gi, src);
-                const bool less = lane < len && key_less(L_pd, fabs(L_pl), L_idx, c_pd, fabs(c_pl), c_i);
-                const int pos = __popcll(__ballot(less));
-                const double u_pd = shfl_up_d(L_pd), u_pl = shfl_up_d(L_pl);
-                const double u_x = shfl_up_d(L_x), u_y = shfl_up_d(L_y), u_z = shfl_up_d(L_z);
-                const long long u_i = shfl_up_ll(L_idx);
-                if (lane > pos && lane <= len && lane < top_k) {
-                    L_pd = u_pd; L_pl = u_pl; L_x = u_x; L_y = u_y; L_z = u_z; L_idx = u_i;
-                } else if (lane == pos) {
-                    L_pd = c_pd; L_pl = c_pl; L_x = c_x; L_y = c_y; L_z = c_z; L_idx = c_i;
-                }
-                len = min(len + 1, top_k);
-                if (len == top_k) {
-                    t_pd = rl_d(L_pd, top_k - 1); t_apl = fabs(rl_d(L_pl, top_k - 1)); t_idx = rl_ll(L_idx, top_k - 1);
-                }
-                if (lane == src) has = false;
-                pend = __ballot(has && (len < top_k || key_less(pd, apl, gi, t_pd, t_apl, t_idx)));
-#ifdef MVS_STAMP_INSERT
-                ++ins_count;
-#endif
-            }
-#ifdef MVS_STAMP_INSERT
-            unsigned long long ti1_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ti1_) :: "memory");
-            ins_cycles += ti1_ - ti0_;
-            if (PARTS == 1 && lane == 0 && node < 16384) g_assoc_cycles[2 * node] = ins_cycles | (ins_count << 32);
-#endif
-        };
         // all points of the sorted range [A, B): ball test, normal filter, keys, top-k insertion
         auto scan = [&](int A, int B) {
             for (int cb = A; cb < B; cb += 64) {             // wave-uniform trip count
                 const int i = cb + lane;
                 bool has = false;
-                double pd = 0, pl = 0; d3 tp = mk3(0, 0, 0); long long gi = 0;
+                ProjKeys key{0, 0}; d3 tp = mk3(0, 0, 0); long long gi = 0;
                 if (i < B) {
                     const float4 p = g.spos[i];
                     if (d2f(qx, qy, qz, p.x, p.y, p.z) <= r2) {
@@ -488,16 +391,13 @@ __device__ inline void select_node(const GridDev& g, const double* __restrict__ 
                         if (dot3(nn, tn) > 0) {                       // :307
                             ++n_pass;
                             tp = ld3(g.tpos + 3 * (int64_t)i);
-                            const d3 dir = tp - orig;                 // :331
-                            pl = dot3(dir, nn) / nlen;                // :332
-                            const double x = sqn3(dir) - pl * pl;
-                            pd = sqrt((0.0 < x) ? x : 0.0);           // :334, clamped (Appendix A.2)
+                            key = proj_keys(orig, nn, nlen, tp);
                             gi = g.index_base + (long long)__float_as_int(p.w);
                             has = true;
                         }
                     }
                 }
-                insert(has, pd, pl, tp, gi);
+                list.insert(top_k, has, key.pd, key.pl, tp, gi);
             }
         };
 
@@ -577,9 +477,7 @@ __device__ inline void select_node(const GridDev& g, const double* __restrict__ 
                 }
                 if (PARTS > 1) {
                     __syncthreads();
-#ifdef MVS_STAMPS
-                    unsigned long long tA_; asm volatile("s_waitcnt vmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tA_) :: "memory");
-#endif
+                    ASTAMP_AT(tA_);
                     const int nr = min(lds->nr, HEAVY_RANGES);
                     // Phase 1 — ball test only: the waves take pieces as they become free, stream their positions (four 64-point
                     // groups in flight) and append the members of the ball to ONE workgroup list of sorted-order indices.  A far
@@ -645,12 +543,7 @@ __device__ inline void select_node(const GridDev& g, const double* __restrict__ 
                                     if (dot3(nn, tn) > 0) {                       // :307
                                         ++n_pass;
                                         const d3 tp = ld3(g.tpos + 3 * (int64_t)i);
-                                        const d3 dir = tp - orig;                 // :331
-                                        const double pl = dot3(dir, nn) / nlen;   // :332
-                                        const double x = sqn3(dir) - pl * pl;
-                                        const double pd = sqrt((0.0 < x) ? x : 0.0);
-                                        const float f = (float)pd;
-                                        ukey[k] = (f == f) ? __float_as_uint(f) : 0x7f800000u;      // (pd >= +0: the bit patterns order like the values)
+                                        ukey[k] = proj_dist_key(proj_keys(orig, nn, nlen, tp).pd);
                                     }
                                 }
                             }
@@ -692,23 +585,7 @@ __device__ inline void select_node(const GridDev& g, const double* __restrict__ 
                                 T = prefix;
                             }
                             // the members at or below T, exactly: into the merge slots
-#pragma unroll
-                            for (int k = 0; k < KMAX; ++k) {
-                                if (ukey[k] <= T && ukey[k] != 0xffffffffu) {
-                                    const int slot = atomicAdd(&lds->nwin, 1);
-                                    if (slot < PARTS * 8) {
-                                        const int i = lds->cand[k * 64 * PARTS + tid];
-                                        const d3 tp = ld3(g.tpos + 3 * (int64_t)i);
-                                        const d3 dir = tp - orig;                 // :331
-                                        const double pl = dot3(dir, nn) / nlen;   // :332
-                                        const double x = sqn3(dir) - pl * pl;
-                                        lds->pd[slot >> 3][slot & 7] = sqrt((0.0 < x) ? x : 0.0);     // :334, clamped (Appendix A.2)
-                                        lds->pl[slot >> 3][slot & 7] = pl;
-                                        lds->x[slot >> 3][slot & 7] = tp.x; lds->y[slot >> 3][slot & 7] = tp.y; lds->z[slot >> 3][slot & 7] = tp.z;
-                                        lds->idx[slot >> 3][slot & 7] = g.index_base + (long long)__float_as_int(g.spos[i].w);
-                                    }
-                                }
-                            }
+                            slots_fill<PARTS, KMAX>(g, lds, ukey, T, tid, orig, nn, nlen);
                             __syncthreads();
                             if (lds->nwin <= PARTS * 8) slots_ready = true;
                             else {
@@ -718,33 +595,27 @@ __device__ inline void select_node(const GridDev& g, const double* __restrict__ 
                                 for (int cb = 64 * lpart; cb < nc; cb += 64 * PARTS) {
                                     const int q = cb + lane;
                                     bool has = false;
-                                    double pd = 0, pl = 0; d3 tp = mk3(0, 0, 0); long long gi = 0;
+                                    ProjKeys key{0, 0}; d3 tp = mk3(0, 0, 0); long long gi = 0;
                                     if (q < nc) {
                                         const int i = lds->cand[q];
                                         const d3 tn = ld3(g.tnrm + 3 * (int64_t)i);
                                         if (dot3(nn, tn) > 0) {                       // :307
                                             ++n_pass;
                                             tp = ld3(g.tpos + 3 * (int64_t)i);
-                                            const d3 dir = tp - orig;                 // :331
-                                            pl = dot3(dir, nn) / nlen;                // :332
-                                            const double x = sqn3(dir) - pl * pl;
-                                            pd = sqrt((0.0 < x) ? x : 0.0);           // :334, clamped (Appendix A.2)
+                                            key = proj_keys(orig, nn, nlen, tp);
                                             gi = g.index_base + (long long)__float_as_int(g.spos[i].w);
                                             has = true;
                                         }
                                     }
-                                    insert(has, pd, pl, tp, gi);
+                                    list.insert(top_k, has, key.pd, key.pl, tp, gi);
                                 }
                             }
                         }
                     }
-#ifdef MVS_STAMPS   // (scripts/heavy_stats.py: list built / this wave done scanning / all waves done, in 16-cycle units, + ranges)
-                    unsigned long long tB_; asm volatile("s_waitcnt vmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tB_) :: "memory");
-                    __syncthreads();
-                    unsigned long long tC_; asm volatile("s_waitcnt vmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tC_) :: "memory");
-                    if (threadIdx.x == 0 && node < 16384)
-                        g_assoc_cycles[2 * node] = (((tA_ - t0_) >> 4) & 0xffff) | ((((tB_ - t0_) >> 4) & 0xffff) << 16) | ((((tC_ - t0_) >> 4) & 0xffff) << 32) | ((unsigned long long)nr << 48);
-#endif
+                    // (scripts/heavy_stats.py: list built / this wave done scanning / all waves done, in 16-cycle units, + ranges)
+                    ASTAMP_AT(tB_); ASTAMP_ONLY(__syncthreads();) ASTAMP_AT(tC_);
+                    ASTAMP_PUT(threadIdx.x == 0 && node < 16384, g_assoc_cycles[2 * node],
+                               (((tA_ - t0_) >> 4) & 0xffff) | ((((tB_ - t0_) >> 4) & 0xffff) << 16) | ((((tC_ - t0_) >> 4) & 0xffff) << 32) | ((unsigned long long)nr << 48));
                 }
             }
         }
@@ -752,44 +623,17 @@ __device__ inline void select_node(const GridDev& g, const double* __restrict__ 
     n_ball = wave_sum_i(n_ball);
     n_pass = wave_sum_i(n_pass);
     if (PARTS > 1) {
-        // merge the waves' lists by RANK: the <= PARTS * 8 survivors are published, every candidate counts how many others
-        // precede it in the total order (8 lanes per candidate, PARTS * 8 / 8 comparisons each) and the ones with fewer than
-        // top_k predecessors ARE the node's list, at the position their count says.  (One wave re-inserting all candidates took
-        // 20-30 K cycles at the end of every heavy node's chain; a tree of pairwise insertions still 33 K: an insertion is a
-        // ballot, twelve lane reads and six fp64 shifts.)
+        // the waves' lists (or the slots the workgroup selection has filled) merged by rank: wave 0 goes on with the node's list
         const int part = (int)(threadIdx.x >> 6);            // (local wave index from here on)
-        if (lane == 0) { lds->nb[part] = n_ball; lds->np[part] = n_pass; lds->len[part] = slots_ready ? 0 : len; }
-        if (lane < 8 && !slots_ready) {
-            const bool live = lane < len;
-            lds->pd[part][lane] = L_pd; lds->pl[part][lane] = L_pl; lds->x[part][lane] = L_x; lds->y[part][lane] = L_y; lds->z[part][lane] = L_z;
-            lds->idx[part][lane] = live ? L_idx : -1;
-        }
+        if (lane == 0) { lds->nb[part] = n_ball; lds->np[part] = n_pass; lds->len[part] = slots_ready ? 0 : list.len; }
+        if (lane < 8 && !slots_ready) list.to_slots(lds, part, lane);
         __syncthreads();
-        {
-            const int cand = (int)(threadIdx.x >> 3), chunk = (int)(threadIdx.x & 7);      // PARTS * 64 threads: PARTS * 8 candidates x 8 lanes
-            const int cw = cand >> 3, cl = cand & 7;
-            const long long my_i = lds->idx[cw][cl];
-            const double my_pd = lds->pd[cw][cl], my_apl = fabs(lds->pl[cw][cl]);
-            int before = 0;
-            constexpr int PER = PARTS;                                                       // PARTS * 8 candidates / 8 lanes
-            for (int k = 0; k < PER; ++k) {
-                const int j = chunk * PER + k, jw = j >> 3, jl = j & 7;
-                const long long o_i = lds->idx[jw][jl];
-                if (o_i >= 0 && key_less(lds->pd[jw][jl], fabs(lds->pl[jw][jl]), o_i, my_pd, my_apl, my_i)) ++before;
-            }
-            before += __shfl_xor(before, 1, 64); before += __shfl_xor(before, 2, 64); before += __shfl_xor(before, 4, 64);
-            if (chunk == 0 && my_i >= 0 && before < top_k) {
-                lds->r_pd[before] = my_pd; lds->r_pl[before] = lds->pl[cw][cl];
-                lds->r_x[before] = lds->x[cw][cl]; lds->r_y[before] = lds->y[cw][cl]; lds->r_z[before] = lds->z[cw][cl];
-                lds->r_idx[before] = my_i;
-            }
-        }
+        slots_rank<PARTS>(lds, top_k);
         __syncthreads();
         if (part == 0) {
             int tot = slots_ready ? lds->nwin : 0;
             for (int w = 0; w < PARTS; ++w) tot += lds->len[w];
-            len = min(tot, top_k);
-            if (lane < len) { L_pd = lds->r_pd[lane]; L_pl = lds->r_pl[lane]; L_x = lds->r_x[lane]; L_y = lds->r_y[lane]; L_z = lds->r_z[lane]; L_idx = lds->r_idx[lane]; }
+            list.from_ranked(lds, min(tot, top_k), lane);
         }
         if (part == 0) {
             n_ball = 0; n_pass = 0;
@@ -797,39 +641,8 @@ __device__ inline void select_node(const GridDev& g, const double* __restrict__ 
         }
         if (part != 0) return;
     }
-    if (lane < 8) {
-        mvs_cand* o = rec + out * 8 + lane;
-        const bool live = lane < len;
-        o->proj_dist = live ? L_pd : 0.0;
-        o->proj_len = live ? L_pl : 0.0;
-        o->pos[0] = live ? L_x : 0.0; o->pos[1] = live ? L_y : 0.0; o->pos[2] = live ? L_z : 0.0;
-        o->index = live ? L_idx : -1;
-    }
-    if (lane == 0) { counts[2 * out] = n_ball; counts[2 * out + 1] = n_pass; }
-    if (lm.controls) {
-        // means over the list, best first (Deformation.cpp:338-349), and the rejection tests (:286-297, :350-353) —
-        // the same operations in the same order as k_assoc_merge with one rank
-        bool ok = n_ball < lm.max_result && len > 0;
-        d3 mp = orig;
-        double m_pl = 0, m_pd = 0;
-        d3 acc = mk3(0, 0, 0);
-        for (int sidx = 0; sidx < len; ++sidx) {
-            m_pl += rl_d(L_pl, sidx); m_pd += rl_d(L_pd, sidx);
-            acc = acc + mk3(rl_d(L_x, sidx), rl_d(L_y, sidx), rl_d(L_z, sidx));
-        }
-        if (ok) {
-            const double dn = (double)len;
-            m_pl /= dn; m_pd /= dn; acc = acc / dn;
-            if (m_pl >= lm.proj_len_err || m_pd >= lm.proj_dist_err) ok = false;
-            if (ok) {
-                const d3 dir = acc - orig;
-                if (fabs(dot3(dir, nn) / (norm3(dir) * norm3(nn))) < lm.min_cos) ok = false;
-            }
-            if (ok) mp = acc;
-        }
-        if (lm.top_idx && lane < 8) lm.top_idx[(int64_t)node * 8 + lane] = (n_ball < lm.max_result && len > 0 && lane < len) ? L_idx : -1;
-        if (lane == 0) { lm.valid[node] = ok ? 1 : 0; st3(lm.controls + 3 * node, mp); }
-    }
+    write_records(rec, counts, node, lane, list, list.len, n_ball, n_pass);
+    if (lm.controls) node_verdict(lm, orig, nn, n_ball, list, list.len, lane, node, lm.controls, lm.valid, lm.top_idx);
     ASTAMP_END(1);
 }
 
@@ -859,8 +672,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) voi
                                                      int32_t* __restrict__ heavy_next, int assoc_blocks, int nn, const NgGeom* __restrict__ geo,
                                                      const int* __restrict__ ng_cs, const float4* __restrict__ ng_sorted, int32_t* __restrict__ nbr) {
 #ifdef MVS_STAMPS
-    unsigned long long tw0_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tw0_) :: "memory");
-    struct WaveStamp { unsigned long long t0; int b; __device__ ~WaveStamp() { unsigned long long t1_; asm volatile("s_waitcnt vmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t1_) :: "memory");
+    ASTAMP_AT_ISSUE(tw0_);
+    struct WaveStamp { unsigned long long t0; int b; __device__ ~WaveStamp() { ASTAMP_AT(t1_);
                                                                                  /* one 64-byte line per workgroup (entries of several XCDs on one line overwrite each other at write-back); the XCD's id travels along: every XCD has its own clock */
                                                                                  unsigned xcc_; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc_));
                                                                                  if ((threadIdx.x & 63) == 0 && b < 20000) { g_wave_stamps[8 * b] = t0; g_wave_stamps[8 * b + 1] = t1_; g_wave_stamps[8 * b + 2] = xcc_ & 0xf; unsigned hw_; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw_)); g_wave_stamps[8 * b + 3] = hw_; } } } ws_{tw0_, (int)blockIdx.x};
@@ -904,14 +717,10 @@ __device__ inline void heavy_entry(const GridDev& g, const double* __restrict__ 
     int s_first = 3;
     if (bound2 && dm < INFINITY) s_first = (int)fminf(1.0e6f, ceilf(sqrtf(dm) * g.inv_h * 0.125f)) + 1;
     if (entry & HEAVY_DMIN_FLAG) {
-#ifdef MVS_STAMPS
-        unsigned long long tc0_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tc0_) :: "memory");
-#endif
+        ASTAMP_AT_ISSUE(tc0_);
         dm = dmin_coarse_wg(g, node_pts, node, dm, lds, s_first);
-#ifdef MVS_STAMPS
-        { unsigned long long tc1_; asm volatile("s_waitcnt vmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tc1_) :: "memory");
-          if (threadIdx.x == 0 && node < 16384) g_dmin_shell[8 * node + 7] = tc1_ - tc0_; }
-#endif
+        ASTAMP_AT(tc1_);
+        ASTAMP_PUT(threadIdx.x == 0 && node < 16384, g_dmin_shell[8 * node + 7], tc1_ - tc0_);
         __syncthreads();                                     // (every wave has read d2min[node] before it is replaced)
         if (threadIdx.x == 0) d2min[node] = dm;
     }
@@ -1080,6 +889,9 @@ __device__ inline void wave_lds_fence() {
 struct NearSlots {            // one per 16-lane group
     double pd[16], pl[16], x[16], y[16], z[16]; long long idx[16];            // candidates (ball members that face the node)
     double s_pd[8], s_pl[8], s_x[8], s_y[8], s_z[8]; long long s_idx[8];      // the node's list, best first
+    // (the list as write_records / node_verdict of assoc_dev.h read it: element i is slot i)
+    __device__ __forceinline__ Cand own(int l) const { return {s_pd[l], s_pl[l], s_x[l], s_y[l], s_z[l], s_idx[l]}; }
+    __device__ __forceinline__ Cand at(int sidx) const { return own(sidx); }
 };
 
 // the item (point) numbers l, l+16, l+32, l+48 of a round of 64 over the concatenated ranges of a group: range of each item by
@@ -1207,22 +1019,19 @@ __device__ inline void near_nodes(const GridDev& g, const double* __restrict__ n
             const bool member = sel && V[k] && d2f(qx, qy, qz, P[k].x, P[k].y, P[k].z) <= r2;
             if (!__ballot(member)) continue;                                          // (wave-uniform)
             bool has = false;
-            double pd = 0, pl = 0; d3 tp = mk3(0, 0, 0); long long gi = 0;
+            ProjKeys key{0, 0}; d3 tp = mk3(0, 0, 0); long long gi = 0;
             if (member) {
                 ++n_ball;
                 const d3 tn = ld3(g.tnrm + 3 * (int64_t)I[k]);
                 tp = ld3(g.tpos + 3 * (int64_t)I[k]);                                 // (issued with the normal: one round trip)
                 if (dot3(nn, tn) > 0) {                                               // :307
                     ++n_pass;
-                    const d3 dir = tp - orig;                                         // :331
-                    pl = dot3(dir, nn) / nlen;                                        // :332
-                    const double x = sqn3(dir) - pl * pl;
-                    pd = sqrt((0.0 < x) ? x : 0.0);                                   // :334, clamped (Appendix A.2)
+                    key = proj_keys(orig, nn, nlen, tp);
                     gi = g.index_base + (long long)__float_as_int(P[k].w);
                     has = true;
                 }
             }
-            push(has, pd, pl, tp, gi);
+            push(has, key.pd, key.pl, tp, gi);
         }
     }
     n_ball = row_sum_i(n_ball);
@@ -1230,38 +1039,10 @@ __device__ inline void near_nodes(const GridDev& g, const double* __restrict__ n
     rank_slots();
     const int len = min(cnt, min(top_k, 8));
     if (!act) return;
-    // ---- what select_node writes for a single-rank run, same operations in the same order
-    if (l < 8) {
-        mvs_cand* o = rec + (int64_t)node * 8 + l;
-        const bool live = l < len;
-        o->proj_dist = live ? S->s_pd[l] : 0.0;
-        o->proj_len = live ? S->s_pl[l] : 0.0;
-        o->pos[0] = live ? S->s_x[l] : 0.0; o->pos[1] = live ? S->s_y[l] : 0.0; o->pos[2] = live ? S->s_z[l] : 0.0;
-        o->index = live ? S->s_idx[l] : -1;
-    }
-    if (l == 0) { counts[2 * (int64_t)node] = n_ball; counts[2 * (int64_t)node + 1] = n_pass; d2min[node] = dm; }
-    if (lm.controls) {
-        bool ok = n_ball < lm.max_result && len > 0;
-        d3 mp = orig;
-        double m_pl = 0, m_pd = 0;
-        d3 acc = mk3(0, 0, 0);
-        for (int sidx = 0; sidx < len; ++sidx) {                                      // :341-346, best first
-            m_pl += S->s_pl[sidx]; m_pd += S->s_pd[sidx];
-            acc = acc + mk3(S->s_x[sidx], S->s_y[sidx], S->s_z[sidx]);
-        }
-        if (ok) {
-            const double dn = (double)len;
-            m_pl /= dn; m_pd /= dn; acc = acc / dn;
-            if (m_pl >= lm.proj_len_err || m_pd >= lm.proj_dist_err) ok = false;
-            if (ok) {
-                const d3 dir = acc - orig;
-                if (fabs(dot3(dir, nn) / (norm3(dir) * norm3(nn))) < lm.min_cos) ok = false;
-            }
-            if (ok) mp = acc;
-        }
-        if (lm.top_idx && l < 8) lm.top_idx[(int64_t)node * 8 + l] = (n_ball < lm.max_result && len > 0 && l < len) ? S->s_idx[l] : -1;
-        if (l == 0) { lm.valid[node] = ok ? 1 : 0; st3(lm.controls + 3 * (int64_t)node, mp); }
-    }
+    // ---- the node's records, nearest distance and target, from the list in the group's slots
+    write_records(rec, counts, node, l, *S, len, n_ball, n_pass);
+    if (l == 0) d2min[node] = dm;
+    if (lm.controls) node_verdict(lm, orig, nn, n_ball, *S, len, l, node, lm.controls, lm.valid, lm.top_idx);
 }
 
 // Four graph queries by one wave, 16 lanes each, bounded by the PREVIOUS pass's neighbour list: the k nodes of that list are k
@@ -1546,11 +1327,7 @@ __device__ inline bool heavy_bounded(const GridDev& g, const double* __restrict_
                 ++n_ball;
                 if (dot3(nn, tn) > 0) {                       // :307
                     ++n_pass;
-                    const d3 dir = tp - orig;                 // :331
-                    const double pl = dot3(dir, nn) / nlen;   // :332
-                    const double x = sqn3(dir) - pl * pl;
-                    const float f = (float)sqrt((0.0 < x) ? x : 0.0);
-                    ukey[k] = (f == f) ? __float_as_uint(f) : 0x7f800000u;
+                    ukey[k] = proj_dist_key(proj_keys(orig, nn, nlen, tp).pd);
                 }
             }
         }
@@ -1583,89 +1360,23 @@ __device__ inline bool heavy_bounded(const GridDev& g, const double* __restrict_
     const unsigned T = lds->T;
     n_ball = lds->ball; n_pass = lds->npass;
     // ---- the survivors at or below the threshold, exactly, into the merge slots
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k) {
-        if (ukey[k] <= T && ukey[k] != 0xffffffffu) {
-            const int slot = atomicAdd(&lds->nwin, 1);
-            if (slot < PARTS * 8) {
-                const int i = lds->cand[k * 64 * PARTS + tid];
-                const d3 tp = ld3(g.tpos + 3 * (int64_t)i);
-                const d3 dir = tp - orig;                     // :331
-                const double pl = dot3(dir, nn) / nlen;       // :332
-                const double x = sqn3(dir) - pl * pl;
-                lds->pd[slot >> 3][slot & 7] = sqrt((0.0 < x) ? x : 0.0);     // :334, clamped (Appendix A.2)
-                lds->pl[slot >> 3][slot & 7] = pl;
-                lds->x[slot >> 3][slot & 7] = tp.x; lds->y[slot >> 3][slot & 7] = tp.y; lds->z[slot >> 3][slot & 7] = tp.z;
-                lds->idx[slot >> 3][slot & 7] = g.index_base + (long long)__float_as_int(g.spos[i].w);
-            }
-        }
-    }
+    slots_fill<PARTS, KMAX>(g, lds, ukey, T, tid, orig, nn, nlen);
     __syncthreads();
     const int nwin = lds->nwin;
     if (nwin > PARTS * 8) { __syncthreads(); return false; }      // more float ties than merge slots (degenerate input)
-    // ---- exact ranks among the slots (8 lanes per slot), the first top_k are the list
-    {
-        const int cd = tid >> 3, chunk = tid & 7;                 // PARTS * 64 threads: PARTS * 8 slots x 8 lanes
-        const int cw = cd >> 3, cl = cd & 7;
-        const long long my_i = lds->idx[cw][cl];
-        const double my_pd = lds->pd[cw][cl], my_apl = fabs(lds->pl[cw][cl]);
-        int before = 0;
-        for (int k = 0; k < PARTS; ++k) {
-            const int j = chunk * PARTS + k, jw = j >> 3, jl = j & 7;
-            const long long o_i = lds->idx[jw][jl];
-            if (o_i >= 0 && key_less(lds->pd[jw][jl], fabs(lds->pl[jw][jl]), o_i, my_pd, my_apl, my_i)) ++before;
-        }
-        before += __shfl_xor(before, 1, 64); before += __shfl_xor(before, 2, 64); before += __shfl_xor(before, 4, 64);
-        if (chunk == 0 && my_i >= 0 && before < top_k) {
-            lds->r_pd[before] = my_pd; lds->r_pl[before] = lds->pl[cw][cl];
-            lds->r_x[before] = lds->x[cw][cl]; lds->r_y[before] = lds->y[cw][cl]; lds->r_z[before] = lds->z[cw][cl];
-            lds->r_idx[before] = my_i;
-        }
-    }
+    // ---- exact ranks among the slots, the first top_k are the list
+    slots_rank<PARTS>(lds, top_k);
     __syncthreads();
     if (part != 0) return true;
-    // ---- what select_node writes (wave 0), same operations in the same order
-    const int len = min(nwin, top_k);
-    double L_pd = 0, L_pl = 0, L_x = 0, L_y = 0, L_z = 0;
-    long long L_idx = -1;
-    if (lane < len) { L_pd = lds->r_pd[lane]; L_pl = lds->r_pl[lane]; L_x = lds->r_x[lane]; L_y = lds->r_y[lane]; L_z = lds->r_z[lane]; L_idx = lds->r_idx[lane]; }
-    if (lane < 8) {
-        mvs_cand* o = rec + (int64_t)node * 8 + lane;
-        const bool live = lane < len;
-        o->proj_dist = live ? L_pd : 0.0;
-        o->proj_len = live ? L_pl : 0.0;
-        o->pos[0] = live ? L_x : 0.0; o->pos[1] = live ? L_y : 0.0; o->pos[2] = live ? L_z : 0.0;
-        o->index = live ? L_idx : -1;
-    }
-    if (lane == 0) { counts[2 * (int64_t)node] = n_ball; counts[2 * (int64_t)node + 1] = n_pass; d2min[node] = dm; }
-    if (lm.controls) {
-        bool ok = n_ball < lm.max_result && len > 0;
-        d3 mp = orig;
-        double m_pl = 0, m_pd = 0;
-        d3 acc = mk3(0, 0, 0);
-        for (int sidx = 0; sidx < len; ++sidx) {
-            m_pl += rl_d(L_pl, sidx); m_pd += rl_d(L_pd, sidx);
-            acc = acc + mk3(rl_d(L_x, sidx), rl_d(L_y, sidx), rl_d(L_z, sidx));
-        }
-        if (ok) {
-            const double dn = (double)len;
-            m_pl /= dn; m_pd /= dn; acc = acc / dn;
-            if (m_pl >= lm.proj_len_err || m_pd >= lm.proj_dist_err) ok = false;
-            if (ok) {
-                const d3 dir = acc - orig;
-                if (fabs(dot3(dir, nn) / (norm3(dir) * norm3(nn))) < lm.min_cos) ok = false;
-            }
-            if (ok) mp = acc;
-        }
-        if (lm.top_idx && lane < 8) lm.top_idx[(int64_t)node * 8 + lane] = (n_ball < lm.max_result && len > 0 && lane < len) ? L_idx : -1;
-        if (lane == 0) { lm.valid[node] = ok ? 1 : 0; st3(lm.controls + 3 * (int64_t)node, mp); }
-    }
+    // ---- the node's records, nearest distance and target (wave 0)
+    TopK list;
+    list.from_ranked(lds, min(nwin, top_k), lane);
+    write_records(rec, counts, node, lane, list, list.len, n_ball, n_pass);
+    if (lane == 0) d2min[node] = dm;
+    if (lm.controls) node_verdict(lm, orig, nn, n_ball, list, list.len, lane, node, lm.controls, lm.valid, lm.top_idx);
     return true;
 }
 
-#ifdef MVS_STAMPS
-__device__ unsigned long long g_all_stamps[4 * 4096];         // k_assoc_all: per workgroup {start, end (100 MHz constant clock), section, work items}
-#endif
 __device__ inline int assoc_all_sections(const GridDev& g, const double* __restrict__ node_pts, const double* __restrict__ node_nrm,
                                                                 int K, int top_k, const float* __restrict__ lim, float* __restrict__ d2min,
                                                                 mvs_cand* __restrict__ rec, int32_t* __restrict__ counts,
@@ -1737,16 +1448,12 @@ __device__ __forceinline__ void assoc_all_body(const GridDev& g, const double* _
     extern __shared__ __attribute__((aligned(16))) unsigned char all_dyn[];      // AllLds, or the cell counters of the node grid's builder
     AllLds& lds = *reinterpret_cast<AllLds*>(all_dyn);
     int items = 0;
-#ifdef MVS_STAMPS
-    unsigned long long t0_; asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t0_) :: "memory");
-#endif
+    ASTAMP_ONLY(const unsigned long long t0_ = stamp_issue<true>();)
     const int section = assoc_all_sections(g, node_pts, node_nrm, K, top_k, lim, d2min, rec, counts, heavy, mid, lm, heavy_next, mid_next, HB, MB, NB, GB, nn,
                                            graph_bounded, geo, cs, sorted, nbr, m, mesh_pts, &items, lds, nb, vb, vg);
     (void)section;
-#ifdef MVS_STAMPS
-    unsigned long long t1_; asm volatile("s_waitcnt vmcnt(0)\n\ts_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t1_) :: "memory");
-    if (threadIdx.x == 0 && blockIdx.x < 4096) { g_all_stamps[4 * blockIdx.x] = t0_; g_all_stamps[4 * blockIdx.x + 1] = t1_; g_all_stamps[4 * blockIdx.x + 2] = (unsigned long long)section; g_all_stamps[4 * blockIdx.x + 3] = (unsigned long long)items; }
-#endif
+    ASTAMP_ONLY(const unsigned long long t1_ = stamp_drained<true>();
+                if (threadIdx.x == 0 && blockIdx.x < 4096) { g_all_stamps[4 * blockIdx.x] = t0_; g_all_stamps[4 * blockIdx.x + 1] = t1_; g_all_stamps[4 * blockIdx.x + 2] = (unsigned long long)section; g_all_stamps[4 * blockIdx.x + 3] = (unsigned long long)items; })
 }
 __global__ __launch_bounds__(64 * HEAVY_WAVES, 4) void k_assoc_all(GridDev g, const double* __restrict__ node_pts, const double* __restrict__ node_nrm,
                                                                 int K, int top_k, const float* __restrict__ lim, float* __restrict__ d2min,
@@ -1779,9 +1486,9 @@ __global__ __launch_bounds__(64 * HEAVY_WAVES, 4) void k_assoc_all_multi(const P
 
 // ----------------------------------------------------------------- merge ----
 // One wave per node: the ranks' records of the node (8 per rank, 64 per pass of the wave) are loaded one per lane —
-// 384 contiguous bytes per rank — and inserted into the wave-resident sorted list exactly as select_node does; the node
-// target is then formed as in the single-rank path (same operations, same order).  (The first version, a thread per
-// node with its list in scratch memory, took 187 us per step at 8 ranks against 15 us at one: scripts/shard_steady.py.)
+// 384 contiguous bytes per rank — and inserted into the wave-resident sorted list (TopK); the node target is the verdict of
+// every path (node_verdict).  (The first version, a thread per node with its list in scratch memory, took 187 us per step
+// at 8 ranks against 15 us at one: scripts/shard_steady.py.)
 __global__ __launch_bounds__(256) void k_assoc_merge(const double* __restrict__ node_pts, const double* __restrict__ node_nrm, int K,
                               mvs_deform_params p, const mvs_cand* __restrict__ rec_all,
                               const int32_t* __restrict__ counts_all, int nranks, double* __restrict__ controls,
@@ -1796,10 +1503,7 @@ __global__ __launch_bounds__(256) void k_assoc_merge(const double* __restrict__ 
     const d3 orig = ld3(node_pts + 3 * (int64_t)(node0 + q)), nn = ld3(node_nrm + 3 * (int64_t)(node0 + q));
     const int node = q;                                       // (index into the record / count / output arrays)
     const int top_k = p.top_k;
-    double L_pd = 0, L_pl = 0, L_x = 0, L_y = 0, L_z = 0;
-    long long L_idx = -1;
-    int len = 0;
-    double t_pd = 0, t_apl = 0; long long t_idx = 0;
+    TopK list;
     long long ball = 0;
     for (int base = 0; base < nranks * 8; base += 64) {
         const int q = base + lane, r = q >> 3, sl = q & 7;
@@ -1813,53 +1517,11 @@ __global__ __launch_bounds__(256) void k_assoc_merge(const double* __restrict__ 
                 if (c.index >= 0) { has = true; pd = c.proj_dist; pl = c.proj_len; tp = mk3(c.pos[0], c.pos[1], c.pos[2]); gi = c.index; }
             }
         }
-        const double apl = fabs(pl);
-        unsigned long long pend = __ballot(has && (len < top_k || key_less(pd, apl, gi, t_pd, t_apl, t_idx)));
-        while (pend) {
-            const int src = __ffsll((long long)pend) - 1;
-            const double c_pd = rl_d(pd, src), c_pl = rl_d(pl, src);
-            const double c_x = rl_d(tp.x, src), c_y = rl_d(tp.y, src), c_z = rl_d(tp.z, src);
-            const long long c_i = rl_ll(gi, src);
-            const bool less = lane < len && key_less(L_pd, fabs(L_pl), L_idx, c_pd, fabs(c_pl), c_i);
-            const int pos = __popcll(__ballot(less));
-            const double u_pd = shfl_up_d(L_pd), u_pl = shfl_up_d(L_pl);
-            const double u_x = shfl_up_d(L_x), u_y = shfl_up_d(L_y), u_z = shfl_up_d(L_z);
-            const long long u_i = shfl_up_ll(L_idx);
-            if (lane > pos && lane <= len && lane < top_k) {
-                L_pd = u_pd; L_pl = u_pl; L_x = u_x; L_y = u_y; L_z = u_z; L_idx = u_i;
-            } else if (lane == pos) {
-                L_pd = c_pd; L_pl = c_pl; L_x = c_x; L_y = c_y; L_z = c_z; L_idx = c_i;
-            }
-            len = min(len + 1, top_k);
-            if (len == top_k) {
-                t_pd = rl_d(L_pd, top_k - 1); t_apl = fabs(rl_d(L_pl, top_k - 1)); t_idx = rl_ll(L_idx, top_k - 1);
-            }
-            if (lane == src) has = false;
-            pend = __ballot(has && (len < top_k || key_less(pd, apl, gi, t_pd, t_apl, t_idx)));
-        }
+        list.insert(top_k, has, pd, pl, tp, gi);
     }
     // total ball count over the ranks (lanes with sl == 0 hold one rank's count each)
     for (int o = 32; o > 0; o >>= 1) ball += __shfl_xor(ball, o, 64);
-    bool ok = ball < (long long)p.max_result && len > 0;     // :286-297 (full result dropped), :315
-    d3 mp = orig;
-    double m_pl = 0, m_pd = 0;
-    d3 acc = mk3(0, 0, 0);
-    for (int sidx = 0; sidx < len; ++sidx) {                  // :341-346, best first
-        m_pl += rl_d(L_pl, sidx); m_pd += rl_d(L_pd, sidx);
-        acc = acc + mk3(rl_d(L_x, sidx), rl_d(L_y, sidx), rl_d(L_z, sidx));
-    }
-    if (top_idx && lane < 8) top_idx[(int64_t)node * 8 + lane] = (ok && lane < len) ? L_idx : -1;
-    if (ok) {
-        const double dn = (double)len;
-        m_pl /= dn; m_pd /= dn; acc = acc / dn;               // :347-349
-        if (m_pl >= p.proj_len_err || m_pd >= p.proj_dist_err) ok = false;            // :350
-        if (ok) {
-            const d3 dir = acc - orig;                        // :352-353
-            if (fabs(dot3(dir, nn) / (norm3(dir) * norm3(nn))) < p.min_cos) ok = false;
-        }
-        if (ok) mp = acc;
-    }
-    if (lane == 0) { valid[node] = ok ? 1 : 0; st3(controls + 3 * node, mp); }   // :355-356 (controls stay at orig otherwise, :271-272)
+    node_verdict(p, orig, nn, ball, list, list.len, lane, node, controls, valid, top_idx);
 }
 
 }  // namespace

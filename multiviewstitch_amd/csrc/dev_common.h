@@ -62,6 +62,20 @@ __host__ __device__ inline float d2f(float qx, float qy, float qz, float px, flo
 // ------------------------------------------------------------- wave ops ----
 __device__ inline int lane_id() { return threadIdx.x & 63; }
 
+// the readlane family: the value of lane `l` (wave-uniform) in every lane — v_readlane per 32 bits, no LDS crossbar as __shfl would use
+__device__ inline int rl_i(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
+__device__ inline long long rl_ll(long long b, int l) {
+    const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffLL), l);
+    const int hi = __builtin_amdgcn_readlane((int)(b >> 32), l);
+    return ((long long)hi << 32) | (unsigned int)lo;
+}
+__device__ inline double rl_d(double v, int l) {
+    const long long b = __double_as_longlong(v);
+    const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffLL), l);
+    const int hi = __builtin_amdgcn_readlane((int)(b >> 32), l);
+    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+}
+
 __device__ inline float wave_min_f(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));

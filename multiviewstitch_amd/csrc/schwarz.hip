@@ -60,12 +60,8 @@ __device__ __forceinline__ unsigned pk_bf16(float lo, float hi) {
     return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
 }
 
-// uniform double from lane `l` of the wave (two v_readlane: no LDS crossbar as __shfl would use)
-__device__ inline double lane_bcast(double v, int l) {
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffLL), l), hi = __builtin_amdgcn_readlane((int)(b >> 32), l);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
+// uniform double from lane `l` of the wave: rl_d of the readlane family (dev_common.h)
+__device__ inline double lane_bcast(double v, int l) { return rl_d(v, l); }
 // sum over each 16-lane row (every lane of the row gets it): 4 DPP steps
 __device__ inline double row16_sum(double v) {
     v += dpp_d<0xB1>(v); v += dpp_d<0x4E>(v); v += dpp_d<0x141>(v); v += dpp_d<0x140>(v);

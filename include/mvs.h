@@ -362,6 +362,98 @@ int mvs_keypoint_cull_dev(int32_t n_frames, int32_t view_count, const mvs_camera
                           const uint8_t* mask_dev, uint8_t* keep_dev, int64_t* out_offsets, float* out_keys_dev, float* out_descs_dev,
                           void* hip_stream);
 
+/* ------------------------------------------------- foreground masks (Image3D::LoadModel, Segment 1) -- */
+/* A minimum cut on n 8-connected grids of gw x gh nodes, the cut of mvs_grabcut_masks as an entry of its own.  Node i = y * gw + x.
+ *   excess [n][gh*gw] int32 : the folded terminal link of a node: above 0 capacity from the source, below 0 capacity to the sink.
+ *   cap [n][8][gh*gw] int32 : cap[g][d][i] >= 0, the capacity from node i to its neighbour in direction d, direction-major.  The
+ *                             directions (dx, dy), y downwards: 0 (-1, 0) left, 1 (-1, -1) up-left, 2 (0, -1) up, 3 (+1, -1) up-right,
+ *                             4 (+1, 0) right, 5 (+1, +1) down-right, 6 (0, +1) down, 7 (-1, +1) down-left; d and d ^ 4 are opposite.  An
+ *                             entry that points outside the grid is ignored.  cap(i -> j) and cap(j -> i) may differ.
+ *   source_side [n][gh*gw] uint8 : 1 / 0.
+ * Rule G1: a node is on the source side iff the sink cannot be reached from it in the residual graph of a maximum preflow.  That set is
+ * the maximal minimum-cut source set and does not depend on the preflow found: let T be the nodes that reach the sink in the residual
+ * graph of a maximum preflow f.  No residual arc leaves V \ T for T, so the cut (V \ T, T) is saturated, carries nothing back and holds
+ * no excess in T: it is a minimum cut.  For ANY minimum cut (S', T') the value of f equals cap(S', T'), which forces f to saturate
+ * it and to send nothing back; no residual arc then leaves S', S' cannot reach the sink and S' is inside V \ T.  V \ T is therefore the
+ * union of all minimum-cut source sets, a property of the capacities alone: no schedule, tile size or order of atomics can change a
+ * byte of source_side, and two runs give the same bytes.
+ * The solver is push-relabel, phase 1 only: per node an int32 excess, an int32 height and eight residual capacities; lock-free pushes
+ * and relabels (Hong and He) on 16 x 16 tiles held in LDS, with integer atomics on LDS inside a tile and on global memory across tile
+ * borders; a global relabelling that is the exact backward breadth-first distance from the nodes of negative excess, computed by
+ * monotone min-relaxations to a fixed point, after which a node it did not reach has height INF and is inactive.  The cut is done when a
+ * converged relabelling leaves no node with excess > 0 and a finite height; source_side = (height == INF).  Heights only steer the
+ * pushes: whatever they are, excess and residual capacities stay a preflow, and the answer is read off an exact relabelling.
+ * Every kernel does a bounded amount of work and no workgroup waits on another.  Convergence is decided by the host, which reads one
+ * small counter record per round (a round: a batch of push launches when nodes are active, then a batch of relabel launches).
+ * max_rounds (>= 1) caps the rounds: reaching it gives MVS_E_SOLVER with a mvs_last_error() text, source_side is then not written.
+ * rounds (optional) receives the rounds used.
+ * Headroom: with |excess| <= E and every capacity <= C a node's excess stays within E + 8 C; inputs where that exceeds 2^31 - 1 give
+ * MVS_E_INVALID_ARG (the device form finds it in its first launch).  MVS_E_INVALID_ARG, before a device is needed: a NULL pointer other
+ * than rounds, n, gw or gh < 1, gw * gh above 2^26 or n * gw * gh above 2^31 - 1, max_rounds < 1; the host form also finds a negative
+ * capacity and the headroom there.  Scratch from the stream-ordered pool: 40 bytes per node. */
+int mvs_grid_mincut(int32_t n, int32_t gw, int32_t gh, const int32_t* excess, const int32_t* cap, int32_t max_rounds, uint8_t* source_side,
+                    int32_t* rounds /*or NULL*/);
+/* excess, cap and source_side in HBM, in the order of hip_stream (may be NULL); returns with the work complete */
+int mvs_grid_mincut_dev(int32_t n, int32_t gw, int32_t gh, const int32_t* excess_dev, const int32_t* cap_dev, int32_t max_rounds,
+                        uint8_t* source_side_dev, int32_t* rounds, void* hip_stream);
+
+/* Image3D::LoadModel with Segment 1 (R/Image3D/Image3D.cpp:23-51): a foreground mask per frame by cv::grabCut on the half-size image,
+ * started from the margin rectangle, 3 iterations, GC_PR_FGD kept, the mask resized back — for all frames of a sequence in one launch
+ * set.  OpenCV is not part of the reference tree: the rules below are recalled from OpenCV's grabcut.cpp, are NOT VERIFIED against it and
+ * are this library's definition.  imgs [n][h][w][3] uint8; mask [n][h*w] uint8, 255 / 0, what mvs_keypoint_cull reads; half_mask
+ * (optional) [n][hh*hw] uint8, 1 / 0.  A colour c is its three bytes (c0, c1, c2) in memory order.
+ *   1. half image : hw = w / 2, hh = h / 2; half pixel (x, y), per channel, = (a + b + c + d + 2) >> 2 over the full pixels (2x, 2y),
+ *                   (2x+1, 2y), (2x, 2y+1), (2x+1, 2y+1).  An odd last row or column is unused.
+ *   2. rectangle  : rowL = (int)(hh * vl), colL = (int)(hw * hl), rowR = (int)(hh * vr), colR = (int)(hw * hr) (double products,
+ *                   truncated); the rectangle is [colL, hw - colR) x [rowL, hh - rowR).
+ *   3. start      : inside the rectangle a pixel is probable foreground; outside it is background and stays so.
+ *   4. components : each of the two models (foreground, background) has 5 components.  Per frame and model: the histogram of the luma
+ *                   c0 + c1 + c2 (0..765) over the model's m pixels; t_k, k = 1..4, = the smallest luma whose cumulative count reaches
+ *                   (k * m + 4) / 5 (integer division); a pixel's component = the number of t_k strictly below its luma.  (OpenCV
+ *                   draws k-means++ seeds at random; this start is deterministic.)
+ *   5. learn      : per (frame, model, component) the count c, the sums s_a = sum c_a and the product sums p_ab = sum c_a c_b (a <= b),
+ *                   exact int64, accumulated in any order.  With m the model's pixels: mean_a = (double)s_a / c; cov_ab = (double)p_ab
+ *                   / c - mean_a * mean_b; det = c00 * (c11 * c22 - c12 * c21) - c01 * (c10 * c22 - c12 * c20) + c02 * (c10 * c21 -
+ *                   c11 * c20); when det <= DBL_EPSILON, 0.01 is added to c00, c11 and c22 and det is recomputed; the inverse is by
+ *                   cofactors, i00 = (c11 * c22 - c12 * c21) / det, i10 = -(c10 * c22 - c12 * c20) / det, i20 = (c10 * c21 - c11 * c20) /
+ *                   det, i01 = -(c01 * c22 - c02 * c21) / det, i11 = (c00 * c22 - c02 * c20) / det, i21 = -(c00 * c21 - c01 * c20) / det,
+ *                   i02 = (c01 * c12 - c02 * c11) / det, i12 = -(c00 * c12 - c02 * c10) / det, i22 = (c00 * c11 - c01 * c10) / det;
+ *                   weight = (double)c / m; lw = log(weight) - 0.5 * log(det).  A component with c = 0 is skipped everywhere.
+ *   6. assign     : with d = c - mean (doubles) and q = d0 * (d0 * i00 + d1 * i10 + d2 * i20) + d1 * (d0 * i01 + d1 * i11 + d2 * i21) +
+ *                   d2 * (d0 * i02 + d1 * i12 + d2 * i22), a_k = lw_k - 0.5 * q_k; the pixel's component is the k of largest a_k in its
+ *                   own model, the lowest k on ties.
+ *   7. beta       : S = the exact integer sum over all pixels and their left, up-left, up and up-right neighbours inside the image of
+ *                   the squared colour difference; beta = 1 / (2 * ((double)S / (4*hw*hh - 3*hw - 3*hh + 2))); S == 0: beta = 0.
+ *   8. n-links    : cap(i -> j) = llrint(1024 * g * exp(-beta * d2)), d2 the squared colour difference of i and j, g = gamma for
+ *                   directions 0, 2, 4, 6 and gamma / sqrt(2) for the diagonals; symmetric, computed once per call.
+ *   9. t-links    : L(model) = -(M + log(sum_k exp(a_k - M))), M = max_k a_k, over the model's non-empty components; L = 9 * gamma for a
+ *                   model without one.  Inside the rectangle excess = llrint(1024 * (L(background) - L(foreground))), clamped to +-K,
+ *                   K = llrint(1024 * 9 * gamma); outside excess = -K.  Only the difference of the two links enters a cut.
+ *  10. cut        : rule G1 (mvs_grid_mincut) on excess and the n-links; inside the rectangle foreground := source side.
+ *  11. iterations : learn (5) on the components of 4; then `iters` times: assign (6), learn (5), t-links (9), cut (10).
+ *  12. full size  : mask(x, y) = 255 iff any half pixel of its footprint is foreground: columns x0, x0 + 1 with x0 = x / 2 - 1 for even x
+ *                   and (x - 1) / 2 for odd x, clamped to [0, hw - 1]; rows alike.  That is where OpenCV's linear resize at exactly 2x
+ *                   is non-zero, the test of Image3D::InMask.  Deviation: the interpolated grey values are not produced.
+ * exp and log are the device's; everything else is integer or an IEEE double operation in the order written.
+ * MVS_E_INVALID_ARG, before a device is needed: a NULL pointer other than half_mask, n < 1, w or h below 2 or w * h above 2^26 or
+ * n * w * h above 2^31 - 1, a margin outside [0, 1] (a NaN included), an empty rectangle, iters < 1, gamma not finite, <= 0 or above
+ * 100000 (the headroom of the cut), max_rounds < 1.  MVS_E_SOLVER: a cut reached max_rounds.  Scratch from the stream-ordered pool: 78
+ * bytes per half pixel (colour, mask, component, n-links and the cut's 40) and 8248 bytes of tables per frame; the host form adds the
+ * images and the masks. */
+typedef struct mvs_grabcut_params {
+    double  hl, hr, vl, vr;     /* margin ratios left / right / top / bottom (ParamParser), 0.1 each by default   */
+    double  gamma;              /* 50                                                                             */
+    int32_t iters;              /* 3                                                                              */
+    int32_t max_rounds;         /* 4096: rounds of one cut                                                        */
+    int64_t reserved;           /* 0                                                                              */
+} mvs_grabcut_params;
+void mvs_grabcut_default_params(mvs_grabcut_params* p);
+int mvs_grabcut_masks(int32_t n, int32_t w, int32_t h, const uint8_t* imgs, const mvs_grabcut_params* p, uint8_t* mask,
+                      uint8_t* half_mask /*or NULL*/);
+/* imgs, mask and half_mask in HBM, in the order of hip_stream (may be NULL); returns with the work complete */
+int mvs_grabcut_masks_dev(int32_t n, int32_t w, int32_t h, const uint8_t* imgs_dev, const mvs_grabcut_params* p, uint8_t* mask_dev,
+                          uint8_t* half_mask_dev, void* hip_stream);
+
 /* FeatureProc::MatchFeature (R/FeatureProc/FeatureProc.cpp:77-130, call site R/Processor/Processor.cpp:634): SiftMatchGPU's descriptor
  * matching for ALL list pairs of two adjacent sequences in one launch set.  The input is what mvs_keypoint_cull(_dev) writes — list
  * l = frame * view_count + view owns the keys [key_offsets[l], key_offsets[l+1]) of keys[total][4] float32 {x, y, s, o} and of

@@ -97,6 +97,15 @@ int mvs_test_poisson_screened(int64_t n, const double* points, const double* nor
                               mvs_poisson_density_info* dinfo, mvs_poisson_screen_info* sinfo, int64_t* stencil, double* f, double* chi0,
                               double* chi, int64_t node_capacity, int32_t diagonal);
 
+/* mvs_grabcut_masks (host form) with its steps handed out, N = (w / 2) * (h / 2); every array but mask may be NULL:
+ *   S [n] int64 (rule 7) and ncap [n][8][N] int32 (rule 8, the layout of mvs_grid_mincut's cap), once per call;
+ *   labels [iters + 1][n][N] uint8 and sums [iters + 1][n][2][5][10] int64 (model 0 = foreground; per component c | s0 s1 s2 | p00 p01
+ *   p02 p11 p12 p22): entry 0 the components of rule 4 and their learn, entry i the assign and learn of iteration i;
+ *   excess [iters][n][N] int32, half_mask [iters][n][N] uint8 (1 / 0) and rounds [iters] int32 (rounds of the cut): iteration i at i - 1.
+ * MVS_E_SOLVER still hands out what the steps before the failed cut produced. */
+int mvs_test_grabcut_trace(int32_t n, int32_t w, int32_t h, const uint8_t* imgs, const mvs_grabcut_params* p, uint8_t* mask, int64_t* S,
+                           int32_t* ncap, uint8_t* labels, int64_t* sums, int32_t* excess, uint8_t* half_mask, int32_t* rounds);
+
 #ifdef __cplusplus
 }
 #endif

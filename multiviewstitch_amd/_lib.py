@@ -77,6 +77,12 @@ class CPointSampleParams(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class CGrabCutParams(C.Structure):
+    """struct mvs_grabcut_params."""
+    _fields_ = [("hl", C.c_double), ("hr", C.c_double), ("vl", C.c_double), ("vr", C.c_double), ("gamma", C.c_double),
+                ("iters", C.c_int32), ("max_rounds", C.c_int32), ("reserved", C.c_int64)]
+
+
 class CPoissonParams(C.Structure):
     """struct mvs_poisson_params."""
     _fields_ = [("scale", C.c_double), ("samples_per_node", C.c_double), ("solve_tol", C.c_double), ("depth_max", C.c_int32),
@@ -153,6 +159,11 @@ _SIGS = {
     "mvs_gen_new_views_dev": (C.c_int, [_I32, _VP, _VP, _I32, _I32, _D, _VP, _VP, _VP]),
     "mvs_keypoint_cull": (C.c_int, [_I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _D, _D, _VP, _VP, _VP, _VP, _VP]),
     "mvs_keypoint_cull_dev": (C.c_int, [_I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _D, _D, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "mvs_grid_mincut": (C.c_int, [_I32, _I32, _I32, _VP, _VP, _I32, _VP, _VP]),
+    "mvs_grid_mincut_dev": (C.c_int, [_I32, _I32, _I32, _VP, _VP, _I32, _VP, _VP, _VP]),
+    "mvs_grabcut_default_params": (None, [_VP]),
+    "mvs_grabcut_masks": (C.c_int, [_I32, _I32, _I32, _VP, _VP, _VP, _VP]),
+    "mvs_grabcut_masks_dev": (C.c_int, [_I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP]),
     "mvs_sift_match": (C.c_int, [_I64, _VP, _I64, _VP, _VP, _VP, _VP]),
     "mvs_sift_match_lists": (C.c_int, [_I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP]),
     "mvs_sift_match_lists_dev": (C.c_int, [_I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP]),
@@ -281,6 +292,7 @@ _SIGS = {
     "mvs_test_sift_level": (C.c_int, [_I32, _I32, _VP, _VP, _I32, _I32, _VP, _I64, _VP, _VP]),
     "mvs_test_sift_candidates": (C.c_int, [_I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _I64]),
     "mvs_test_point_sample_candidates": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP, _I64]),
+    "mvs_test_grabcut_trace": (C.c_int, [_I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mvs_test_poisson_field": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _I64]),
     "mvs_test_poisson_density": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _I64]),
     "mvs_test_poisson_screened": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _I32]),

@@ -52,6 +52,7 @@ const void* const* mvs_tu_kernels_geom(int*);
 const void* mvs_tu_probe_srt(); const void* mvs_tu_probe_align(); const void* mvs_tu_probe_consist(); const void* mvs_tu_probe_render();
 const void* mvs_tu_probe_stitch(); const void* mvs_tu_probe_render_views(); const void* mvs_tu_probe_matchpairs(); const void* mvs_tu_probe_views();
 const void* mvs_tu_probe_siftmatch(); const void* mvs_tu_probe_sift(); const void* mvs_tu_probe_pointsample(); const void* mvs_tu_probe_compact();
+const void* mvs_tu_probe_grabcut();
 // (never destroyed: the helper thread is detached and may outlive the static destructors of an exiting process)
 static std::mutex& g_preload_mu = *new std::mutex;
 static std::condition_variable& g_preload_cv = *new std::condition_variable;
@@ -77,7 +78,7 @@ void mvs_preload(int device) {
             }
             for (const void* k : {mvs_tu_probe_srt(), mvs_tu_probe_align(), mvs_tu_probe_consist(), mvs_tu_probe_render(),
                                   mvs_tu_probe_stitch(), mvs_tu_probe_render_views(), mvs_tu_probe_matchpairs(), mvs_tu_probe_views(),
-                                  mvs_tu_probe_siftmatch(), mvs_tu_probe_sift(), mvs_tu_probe_pointsample(), mvs_tu_probe_compact()}) {
+                                  mvs_tu_probe_siftmatch(), mvs_tu_probe_sift(), mvs_tu_probe_pointsample(), mvs_tu_probe_compact(), mvs_tu_probe_grabcut()}) {
                 hipFuncAttributes a;
                 if (hipFuncGetAttributes(&a, k) != hipSuccess) (void)hipGetLastError();
             }

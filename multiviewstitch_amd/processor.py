@@ -301,6 +301,54 @@ def CullKeypoints(cameras, depths, tex, keys, descs, min_dsp: float, max_dsp: fl
     return out_keys, ([r["descs"][o[i]:o[i + 1]].copy() for i in range(len(lists))] if descs is not None else None)
 
 
+# ------------------------------------------------------------------ foreground masks ----
+def grabcut_params(**kw) -> L.CGrabCutParams:
+    """``mvs_grabcut_default_params`` (margins 0.1 each, gamma 50, 3 iterations, 4096 rounds per cut) with the given fields replaced;
+    hl, hr, vl, vr are ParamParser's margin ratios."""
+    return _params(L.CGrabCutParams, L.lib().mvs_grabcut_default_params, kw)
+
+
+def GridMinCut(excess, cap, max_rounds: int = 4096, stream: int | None = None, with_rounds: bool = False):
+    """``mvs_grid_mincut``: the maximal minimum-cut source set (rule G1, include/mvs.h) of every grid.  excess [n, gh, gw] int32 (above 0:
+    capacity from the source, below 0: to the sink), cap [n, 8, gh, gw] int32 >= 0 in the direction order of the header — numpy arrays,
+    or contiguous int32 torch tensors on the GPU (the device form; ``stream`` is then the HIP stream that produced them).
+    -> source_side [n, gh, gw] uint8 (1 / 0) where the inputs live; with ``with_rounds`` also the rounds the solver took."""
+    if len(excess.shape) != 3 or tuple(cap.shape) != (excess.shape[0], 8) + tuple(excess.shape[1:]):
+        raise L.MvsError(-1, "excess must be [n, gh, gw] and cap [n, 8, gh, gw]")
+    n, gh, gw = (int(v) for v in excess.shape)
+    rounds = C.c_int32(0)
+    if _is_dev(excess):
+        eptr, cptr = _dev_ptr(excess, "int32", "excess"), _dev_ptr(cap, "int32", "cap")
+        fn, tail = L.lib().mvs_grid_mincut_dev, (L.ptr(stream),)
+    else:
+        excess, cap = L.arr(excess, np.int32), L.arr(cap, np.int32)
+        eptr, cptr, fn, tail = L.ptr(excess), L.ptr(cap), L.lib().mvs_grid_mincut, ()
+    side = _out_like(excess, (n, gh, gw), "uint8")
+    L.check(fn(n, gw, gh, eptr, cptr, int(max_rounds), L.ptr(side), C.byref(rounds), *tail))
+    return (side, rounds.value) if with_rounds else side
+
+
+def GrabCutMasks(imgs, params: L.CGrabCutParams | None = None, stream: int | None = None, with_half: bool = False):
+    """Image3D::LoadModel's foreground masks with Segment 1 (R/Image3D/Image3D.cpp:23-51) for every frame in one call
+    (``mvs_grabcut_masks``; the rules, this library's definition: include/mvs.h).  imgs [frames, h, w, 3] uint8 — a numpy array, or a
+    contiguous torch tensor on the GPU (the device form; ``stream`` is then the HIP stream that produced it).
+    -> masks [frames, h, w] uint8, 255 / 0: the ``masks`` of ``CullKeypoints``; with ``with_half`` also the half-size masks
+    [frames, h // 2, w // 2] (1 / 0)."""
+    prm = params if params is not None else grabcut_params()
+    if len(imgs.shape) != 4 or imgs.shape[-1] != 3:
+        raise L.MvsError(-1, "imgs must be [frames, h, w, 3]")
+    n, h, w = (int(v) for v in imgs.shape[:3])
+    if _is_dev(imgs):
+        iptr, fn, tail = _dev_ptr(imgs, "uint8", "imgs"), L.lib().mvs_grabcut_masks_dev, (L.ptr(stream),)
+    else:
+        imgs = L.arr(imgs, np.uint8)
+        iptr, fn, tail = L.ptr(imgs), L.lib().mvs_grabcut_masks, ()
+    mask = _out_like(imgs, (n, h, w), "uint8")
+    half = _out_like(imgs, (n, max(1, h // 2), max(1, w // 2)), "uint8") if with_half else None
+    L.check(fn(n, w, h, iptr, C.byref(prm), L.ptr(mask), L.ptr(half), *tail))
+    return (mask, half) if with_half else mask
+
+
 # ------------------------------------------------------------------ SIFT ----
 def sift_params(**kw) -> L.CSiftParams:
     """``mvs_sift_default_params`` (first_octave -1, 3 DoG levels, 2 orientations, thresholds 0.02 / 10, sigma 1.6 / 0.5, no margins,
@@ -348,21 +396,27 @@ def DetectFeatureSingleView(img, params: L.CSiftParams | None = None):
 
 
 def LoadSequenceModels(cameras, imgs, depths, view_count: int, axis: int, rot_angle: float, sift: L.CSiftParams | None = None,
-                       min_dsp: float | None = None, max_dsp: float | None = None, masks=None) -> dict:
+                       min_dsp: float | None = None, max_dsp: float | None = None, masks=None, segment: L.CGrabCutParams | None = None) -> dict:
     """The model loop of Processor::CalcSimilarityTransformationSeq for one sequence (R/Processor/Processor.cpp:524-547, LoadModel's
     GenNewViews): -> dict(cameras, depths, tex, imgs, views).  With ``sift`` (``sift_params(...)``; then ``min_dsp`` / ``max_dsp`` are
     required, ``masks`` optional) the head of the function runs to its end (:562-600): ``DetectFeature`` on the generated views and
     ``CullKeypoints`` on its keys; the result also holds ``keys`` and ``descs`` (per list), a complete ``sequences[k]`` entry from which
     ``CalcSimilarityTransformationSeq`` makes ``raw`` itself.  Without ``sift`` the entry lacks ``raw`` (or ``keys`` / ``descs``), which
-    the caller then supplies from a SIFT of their own on ``views``.
+    the caller then supplies from a SIFT of their own on ``views``.  With ``segment`` (``grabcut_params(...)``: ParamParser's Segment 1;
+    not together with ``masks``) the masks are made here, by ``GrabCutMasks`` on ``imgs``; they go to ``CullKeypoints`` and into the result
+    as ``masks``.
     This array form passes views, keys and descriptors through host memory between the three calls; a caller that wants them to stay in
     HBM chains ``mvs_gen_new_views_dev``, ``mvs_sift_detect_dev`` and ``mvs_keypoint_cull_dev`` on one stream."""
+    if segment is not None and masks is not None:
+        raise L.MvsError(-1, "give masks or segment, not both")
     img = L.arr(imgs, np.uint8)
     d = L.arr(depths, np.float32)
     if len(d) != len(cameras):
         raise L.MvsError(-1, "one raster per camera")
     views, tex = GenNewViews(cameras, img, view_count, axis, rot_angle)
     out = dict(cameras=list(cameras), depths=d, tex=tex, imgs=img, views=views)
+    if segment is not None:
+        masks = out["masks"] = GrabCutMasks(img, segment)
     if sift is not None:
         if min_dsp is None or max_dsp is None:
             raise L.MvsError(-1, "sift needs min_dsp and max_dsp for the key-point cull")

@@ -106,6 +106,10 @@ int mvs_test_poisson_screened(int64_t n, const double* points, const double* nor
 int mvs_test_grabcut_trace(int32_t n, int32_t w, int32_t h, const uint8_t* imgs, const mvs_grabcut_params* p, uint8_t* mask, int64_t* S,
                            int32_t* ncap, uint8_t* labels, int64_t* sums, int32_t* excess, uint8_t* half_mask, int32_t* rounds);
 
+/* closest_rotation (rule 0) or kabsch_rotation (rule 1) of svd3_dev.h for n row-major 3x3 matrices, one thread each:
+ * R [n][9]; U, Vm [n][9] as svd3_dev hands them out (may be NULL).  n == 0 launches nothing. */
+int mvs_test_rotations(int64_t n, const double* a, int32_t rule, double* R, double* U, double* Vm);
+
 #ifdef __cplusplus
 }
 #endif

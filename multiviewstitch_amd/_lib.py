@@ -296,6 +296,7 @@ _SIGS = {
     "mvs_test_poisson_field": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _I64]),
     "mvs_test_poisson_density": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _I64]),
     "mvs_test_poisson_screened": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _I32]),
+    "mvs_test_rotations": (C.c_int, [_I64, _VP, _I32, _VP, _VP, _VP]),
 }
 EXPORTS = tuple(_SIGS)
 

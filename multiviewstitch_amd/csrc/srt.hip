@@ -14,6 +14,7 @@
 #include "svd3_dev.h"
 #include "geom.h"
 #include "camera_dev.h"
+#include "../../include/mvs_test.h"
 
 namespace {
 
@@ -275,7 +276,42 @@ __global__ void k_srt_residual_b(const double* __restrict__ m_all, int64_t total
     match_err(c1[k], c2[k], x, m_all + 6 * i, &per_match[2 * i], &per_match[2 * i + 1]);
 }
 
+// test hook (include/mvs_test.h): the rotations of svd3_dev.h on their own, one thread per matrix
+__global__ __launch_bounds__(64) void k_test_rotations(int64_t n, const double* __restrict__ a, int rule, double* __restrict__ R,
+                                                       double* __restrict__ U, double* __restrict__ Vm) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double A[9], r[9];
+    for (int k = 0; k < 9; ++k) A[k] = a[9 * i + k];
+    if (rule == 0) closest_rotation(A, r); else kabsch_rotation(A, r);
+    for (int k = 0; k < 9; ++k) R[9 * i + k] = r[k];
+    if (U || Vm) {
+        double u[9], v[9];
+        svd3_dev(A, u, v);
+        for (int k = 0; k < 9; ++k) {
+            if (U) U[9 * i + k] = u[k];
+            if (Vm) Vm[9 * i + k] = v[k];
+        }
+    }
+}
+
 }  // namespace
+
+int mvs_test_rotations(int64_t n, const double* a, int32_t rule, double* R, double* U, double* Vm) {
+    if (!a || !R || n < 0 || n > 0x7fffffffLL || (rule != 0 && rule != 1)) { mvs_set_error("bad arguments"); return MVS_E_INVALID_ARG; }
+    if (n == 0) return MVS_OK;
+    int rc = need_device();
+    if (rc) return rc;
+    const size_t m = (size_t)n * 9;
+    Scratch da, dR, dU, dV;
+    if ((rc = up(da, a, m)) || (rc = dR.alloc(m * 8)) || (U && (rc = dU.alloc(m * 8))) || (Vm && (rc = dV.alloc(m * 8)))) return rc;
+    k_test_rotations<<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, nullptr>>>(n, da.as<double>(), rule, dR.as<double>(),
+                                                                                  U ? dU.as<double>() : nullptr, Vm ? dV.as<double>() : nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    if ((rc = down(R, dR, m)) || (U && (rc = down(U, dU, m))) || (Vm && (rc = down(Vm, dV, m)))) return rc;
+    return MVS_OK;
+}
 
 // One RemoveOutliers round for `sets` independent match sets (device buffers; sets with fewer than 3 matches are skipped):
 // stats -> every hypothesis of every set in ONE launch -> pick -> per-match pixel errors of the picked transforms.

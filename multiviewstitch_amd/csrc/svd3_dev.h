@@ -3,6 +3,9 @@
 //                      singular direction), used by the ARAP local step
 //   kabsch_rotation  : SRTSolver's rule, R = V U^T, flipped when |det + 1| <= 1e-9
 //                      (R/Solver/SRTSolver.cpp:109-119,165-175)
+// Supported scale: entries of magnitude 1e-60 .. 1e60 (tested at both ends, tests/test_gpu_rotations.py), and 0.  The products of
+// squared column norms in jacobi_pair (al * be, d * d + g2 * g2) overflow or underflow at entries around 1e+-77; no input is
+// rescaled.  A matrix with a NaN gives NaN throughout after the 64 sweeps of the cap.
 #ifndef MVS_SVD3_DEV_H_
 #define MVS_SVD3_DEV_H_
 #include "dev_common.h"

@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
-from tests import mesh_valence as MV, ref_numpy
+from tests import mesh_sheets as MS, mesh_valence as MV, ref_numpy
 
 
 def _edge_weights(oracle, m):
@@ -94,3 +94,44 @@ def test_cpu_references_agree(oracle, name, hubs_in):
     be, bv, br = MV.CPU_DISAGREEMENT[(name, hubs_in)]
     assert e <= be and dv <= bv and dr <= br, (e, dv, dr)
     assert MV.tolerances(name, hubs_in) == (MV.E_RTOL, MV.RMS_TOL, MV.RMS_TOL)        # (ten times the disagreement is far below the project figures)
+
+
+# ---- flat sheets (tests/mesh_sheets.py): every 1-ring covariance has rank 2 ----
+@pytest.mark.parametrize("name", MS.CASES)
+def test_sheet_is_what_it_says(oracle, name):
+    m = MS.case(name)
+    V = len(m.pts)
+    size = name.split("_")[0]
+    assert oracle.mesh_check(V, m.faces) == 0
+    assert (V >= 2048) == (size == "large") and V <= 2300
+    deg = MV.degrees(V, m.faces)
+    assert deg.max() == 8 and len(MV.boundary_vertices(m.faces)) == 2 * sum(MS.SIZES[size]) - 4
+    assert np.array_equal(m.nodes, np.arange(0, V, 13)) and len(m.nodes) >= 3
+    off = m.pts @ m.n
+    if name.endswith("_flat"):
+        assert (m.pts[:, 2] == 0).all() and (m.targets[:, 2] == 0).all() and np.array_equal(m.n, [0, 0, 1])
+    else:
+        assert np.abs(off).max() <= 1e-15 and (off != 0).any() and np.abs(m.n).min() > 0.05      # off the plane by rounding only
+    assert np.abs(m.targets @ m.n).max() <= 1e-15                                                 # the deformation stays in the plane
+    W, A = _edge_weights(oracle, m)
+    Wd, Ad = W.toarray(), A.toarray()
+    assert (np.asarray(W.sum(1)).ravel() > 0.5).all() and (Wd >= 0).all()
+    zero = int(((Wd == 0) & (Ad > 0)).sum())
+    print(f"[measured] {name}: {zero} of {int(Ad.sum())} real edge weights are exactly 0.0")
+    assert zero == MS.ZERO_WEIGHT_EDGES[size] and zero > Ad.sum() // 20                            # the kernels' padding sentinel
+
+
+@pytest.mark.parametrize("name", MS.CASES)
+def test_cpu_references_agree_on_sheets(oracle, name):
+    """as test_cpu_references_agree; and the oracle's own rotations keep the plane's normal: the case is well posed"""
+    m = MS.case(name)
+    a = oracle.arap(m.pts, m.faces, m.nodes, m.targets, 5, 1e-4)
+    b = ref_numpy.arap(m.pts, m.faces, m.nodes, m.targets, 5, 1e-4)
+    assert a["iters"] == b["iters"] == 5
+    e, dv, dr = MV.cpu_disagreement(m, a, b)
+    rn = float(np.abs(a["rot"] @ m.n - m.n).max())
+    print(f"[measured] {name}: CPU references differ by energy {e:.2e} vertex RMS/extent {dv:.2e} rotation RMS {dr:.2e}; oracle |R n - n| {rn:.2e}")
+    be, bv, br = MS.CPU_DISAGREEMENT[name]
+    assert e <= be and dv <= bv and dr <= br, (e, dv, dr)
+    assert rn <= 1e-12
+    assert (max(MV.E_RTOL, 10 * be), max(MV.RMS_TOL, 10 * bv), max(MV.RMS_TOL, 10 * br)) == (MV.E_RTOL, MV.RMS_TOL, MV.RMS_TOL)

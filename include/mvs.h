@@ -652,6 +652,75 @@ int mvs_point_sample_dev(int32_t n_seq, const int32_t* cam_off, const mvs_camera
                          const mvs_point_sample_params* p, int64_t* seq_offsets, double* points_dev, double* normals_dev,
                          int32_t* frame_dev, int32_t* pixel_dev, int64_t capacity, void* hip_stream);
 
+/* ------------------------------------------------- depth refinement (DepthRecovery/DepthOptimizer) -- */
+/* The stage behind Processor::Render in the reference's data flow: the rendered inverse-depth rasters DATA/Render/_depth<i>.raw of every
+ * sequence, taken back to the images, become DATA/Refine/_depth<i>.raw (DepthOptimizer::RefineAllDepthMaps, DepthOptimizer.cpp:20-43).
+ * The reference defines the files and the frame window (RefineDepthMap, :45-63: refFrmCount = 5 frames around the current one, without
+ * it) and stops there: DepthRefineCore is declared and never defined.  The rules below are this library's definition, NOT VERIFIED
+ * against any ZJU code: a plane sweep of 2 * steps + 1 disparity hypotheses around the rendered value, scored by the 8-bit grey SSD of
+ * the match filter (R/Common/Utils.h:221-241) against the reference frames.
+ * Input: n_seq sequences; sequence k owns cams[cam_off[k] .. cam_off[k+1]) (cam_off and cams as mvs_point_sample: the frames of one
+ * sequence share one raster size; sequences may differ).  imgs holds the RGB base images of all cameras back to back in camera order,
+ * each h x w x 3 bytes in the byte order the grey conversion of mvs_match_filter assumes; depths and out are float32 inverse-depth
+ * rasters in camera order; out must not alias depths.  All floating-point arithmetic is fp64 + - * / sqrt in the order written (the
+ * library is built with -ffp-contract=off); the camera maps and the double -> int rule are those of mvs_point_sample.
+ * For frame f of a sequence of n frames, with N = ssd_win, len = 2 N + 1, K = steps:
+ *   1. grey       : G_f[v][u] = (4899 * p0 + 9617 * p1 + 1868 * p2 + 8192) >> 14 of the pixel's three bytes in memory order, the
+ *                   integer conversion of mvs_match_filter.
+ *   2. references : g = f - ref_frm_count / 2 + i for i = 0 .. ref_frm_count - 1, kept when 0 <= g < n and g != f, in ascending order.
+ *   3. candidates : pixel (u, v) is a candidate when d0 = (double)depths_f[v][u] lies in [dsp_min, dsp_max] (a NaN does not) and
+ *                   N <= u < w - N, N <= v < h - N.  Any other pixel copies its input float bit for bit to out and reports k = -128,
+ *                   sum = -1, cnt = 0.
+ *   4. hypotheses : step = rel_range / (double)K and d_k = d0 * (1.0 + (double)k * step) for k = -K .. K, so d_0 == d0 exactly.  A
+ *                   hypothesis is live when d_k lies in [dsp_min, dsp_max].
+ *   5. cost       : for a live k and a reference g: P = world_from_img(cam_f, u, v, 1.0 / d_k), Xc = R_g P + t_g.  The reference
+ *                   counts when Xc.z > 0 and (u', v') = (int(fx Xc.x / Xc.z + cx + 0.5), v' likewise) has N <= u' < w - N,
+ *                   N <= v' < h - N.  It then contributes ssd_g = the sum over a, b in [-N, N] of (G_f[v+a][u+b] - G_g[v'+a][u'+b])^2,
+ *                   an exact integer.  sum_k is the sum of the ssd_g that count, cnt_k how many did.
+ *   6. choice     : only k with cnt_k > 0 are eligible.  k beats j when sum_k * cnt_j < sum_j * cnt_k in int64; on equality the smaller
+ *                   |k| wins, then k < 0.  Without an eligible k the pixel is treated as in rule 3.
+ *   7. acceptance : with m = (double)sum / (double)cnt of the winner k*, the pixel is accepted when sqrt(m / (double)(len * len)) <=
+ *                   ssd_err.  Accepted: k_out = k* and out = (float)d, d = d_k* when MVS_REFINE_SUBSTEP is off.  Not accepted: out is
+ *                   the input float bit for bit and k_out = -128; sum_out and cnt_out still report the winner.
+ *   8. substep    : (MVS_REFINE_SUBSTEP) when k* - 1 and k* + 1 both lie in [-K, K] and are eligible, c-, c0, c+ are their m values
+ *                   and den = (c- - 2.0 * c0) + c+.  If den > 0: o = 0.5 * ((c- - c+) / den) and d = d0 * (1.0 + ((double)k* + o) *
+ *                   step).  If that d is not in [dsp_min, dsp_max], or den <= 0, d = d_k*.
+ *   9. inputs     : every frame reads the original rasters and images; a sequence does not see another sequence.
+ * It follows that a sequence of one frame, or ref_frm_count = 1, returns its input bytes; that on images of one colour every sum is 0,
+ * so that k* is the eligible k of smallest |k| and a pixel returns its input bytes wherever k = 0 is eligible (it is not where d_0
+ * lands outside the interior of every reference while another d_k lands inside one); and that NaN, +-inf, negative values, -0.0 and
+ * zeros pass through unchanged.
+ * The result is defined by integers and by fp64 operations in a stated order: no schedule can change a byte, and two runs give the same
+ * bytes.  The work is three launches without atomics: the grey rasters of all images, the sum of squares over the window of every
+ * pixel, and the refinement of all frames of all sequences (rule 5's sum as sum a^2 + sum b^2 - 2 sum a b, exact in uint32).
+ * k_out (int8), sum_out (int32) and cnt_out (uint8), one entry per pixel in raster order, are optional.  With the ranges below a sum is
+ * at most 961 * 255^2 * 8 < 2^31.  Scratch comes from the stream-ordered pool: 5 bytes per pixel of the call (the grey byte and the
+ * uint32 sum of squares), 140 bytes per camera and 32 bytes per sequence; the host form adds the images, the rasters and the outputs.
+ * MVS_E_INVALID_ARG, before a device is needed: a NULL pointer other than the optional outputs, n_seq < 1, cam_off not ascending from
+ * 0, a camera with w or h <= 0 or fx or fy == 0, two raster sizes inside one sequence, w * h of a frame above 2^31 - 1, a parameter
+ * that is not finite, dsp_min <= 0 or dsp_min > dsp_max, rel_range <= 0 or >= 1, ssd_err < 0, ssd_win outside [0, 15], ref_frm_count
+ * outside [1, 9] or even, steps outside [1, 63], unknown flag bits, out == depths, and too many workgroups for one launch. */
+#define MVS_REFINE_SUBSTEP 1
+typedef struct mvs_depth_refine_params {   /* 48 bytes */
+    double  dsp_min, dsp_max;   /* MinDsp 0.0025, MaxDsp 0.3                                     */
+    double  rel_range;          /* 0.04: half-width of the search, relative to the rendered disparity */
+    double  ssd_err;            /* SSDError 40.0                                                 */
+    int32_t ssd_win;            /* SSDWin 7: N, the window is (2N+1)^2; 0..15                    */
+    int32_t ref_frm_count;      /* refFrmCount 5 (DepthOptimizer.cpp:45); odd, 1..9              */
+    int32_t steps;              /* 8: K hypotheses on each side; 1..63                           */
+    int32_t flags;              /* MVS_REFINE_SUBSTEP = 1                                        */
+} mvs_depth_refine_params;
+/* the values in the comments above; flags = MVS_REFINE_SUBSTEP */
+void mvs_depth_refine_default_params(mvs_depth_refine_params* p);
+int mvs_refine_depth_maps(int32_t n_seq, const int32_t* cam_off /*n_seq+1*/, const mvs_camera* cams, const uint8_t* imgs,
+                          const float* depths, const mvs_depth_refine_params* p, float* out, int8_t* k_out /*or NULL*/,
+                          int32_t* sum_out /*or NULL*/, uint8_t* cnt_out /*or NULL*/);
+/* images, rasters and outputs in HBM, in the order of hip_stream (may be NULL); cam_off and cams stay host arrays; returns with the
+ * work complete */
+int mvs_refine_depth_maps_dev(int32_t n_seq, const int32_t* cam_off, const mvs_camera* cams, const uint8_t* imgs_dev,
+                              const float* depths_dev, const mvs_depth_refine_params* p, float* out_dev, int8_t* k_out_dev,
+                              int32_t* sum_out_dev, uint8_t* cnt_out_dev, void* hip_stream);
+
 /* ------------------------------------------------- surface reconstruction (GeometryRec::RunPoisson) -- */
 /* The one call between the stitch tail and the trim of the model (R/Processor/Processor.cpp:1042-1058): the oriented points of
  * Result/PSR.npts to the triangle mesh of Result/Model.obj that mvs_processor_cull_model reads.  GeoRec is a closed binary; its source is

@@ -95,6 +95,16 @@ int mvs_processor_cull_model(const char* model_obj, int32_t n_seq, const double*
 int mvs_processor_render(const char* deform_obj, const char* srt_txt, int32_t n_seq, const int32_t* cam_off, const mvs_camera* cams,
                          const char* result_dir, const char* const* seq_dirs, float znear, float zfar, int64_t* n_views_out);
 
+/* DepthOptimizer::RefineAllDepthMaps on files (DepthRecovery/DepthOptimizer.cpp:20-43; the rules: mvs_refine_depth_maps, this library's
+ * definition): for each sequence k read seq_dirs[k]/DATA/Render/_depth<i>.raw for its cameras i (mvs_depth_raw_read: what
+ * mvs_processor_render wrote), refine all sequences in one call, and write seq_dirs[k]/DATA/Refine/_depth<i>.raw, creating the directory
+ * as CreateDir does (a '/' is inserted after seq_dirs[k] when it lacks one).  imgs holds the RGB base images of all cameras back to back
+ * in camera order, each h x w x 3 bytes: they are passed in memory because this library has no JPEG decoder, the stance
+ * mvs_gen_new_views takes.  params may be NULL (defaults).  A missing or short raster is reported before anything is written.  Not
+ * written: the _depth<i>.jpg previews (an image encode), as in mvs_processor_render. */
+int mvs_processor_refine_depths(int32_t n_seq, const char* const* seq_dirs, const int32_t* cam_off, const mvs_camera* cams,
+                                const uint8_t* imgs, const mvs_depth_refine_params* params);
+
 /* GeometryRec::RunPointSample on files (R/Processor/Processor.cpp:919-949; the rules: mvs_point_sample, this library's definition):
  * for each sequence k read seq_dirs[k]/DATA/CHECK/_depth<i>.raw for its cameras i (mvs_depth_raw_read: the checked rasters that the file
  * shuffle of :919-931 puts in front of GeoRec), sample all sequences in one call, and write seq_dirs[k]/Rec/PointSample.npts

@@ -77,6 +77,12 @@ class CPointSampleParams(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class CDepthRefineParams(C.Structure):
+    """struct mvs_depth_refine_params."""
+    _fields_ = [("dsp_min", C.c_double), ("dsp_max", C.c_double), ("rel_range", C.c_double), ("ssd_err", C.c_double),
+                ("ssd_win", C.c_int32), ("ref_frm_count", C.c_int32), ("steps", C.c_int32), ("flags", C.c_int32)]
+
+
 class CGrabCutParams(C.Structure):
     """struct mvs_grabcut_params."""
     _fields_ = [("hl", C.c_double), ("hr", C.c_double), ("vl", C.c_double), ("vr", C.c_double), ("gamma", C.c_double),
@@ -173,6 +179,9 @@ _SIGS = {
     "mvs_point_sample_default_params": (None, [_VP]),
     "mvs_point_sample": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64]),
     "mvs_point_sample_dev": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP]),
+    "mvs_depth_refine_default_params": (None, [_VP]),
+    "mvs_refine_depth_maps": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "mvs_refine_depth_maps_dev": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mvs_poisson_default_params": (None, [_VP]),
     "mvs_poisson_reconstruct": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _I64]),
     "mvs_poisson_reconstruct_dev": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _I64, _VP]),
@@ -275,6 +284,7 @@ _SIGS = {
     "mvs_processor_stitch_points": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP, _U32, C.c_char_p, _VP]),
     "mvs_processor_cull_model": (C.c_int, [C.c_char_p, _I32, _VP, _VP, _VP, _VP, _VP, _I32, C.c_char_p, _VP, _VP]),
     "mvs_processor_render": (C.c_int, [C.c_char_p, C.c_char_p, _I32, _VP, _VP, C.c_char_p, _VP, C.c_float, C.c_float, _VP]),
+    "mvs_processor_refine_depths": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP]),
     "mvs_processor_point_sample": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mvs_processor_poisson": (C.c_int, [C.c_char_p, _VP, C.c_char_p, _VP, _VP]),
     "mvs_processor_poisson_density": (C.c_int, [C.c_char_p, _VP, _VP, _D, C.c_char_p, _VP, _VP]),
@@ -334,6 +344,7 @@ def check(rc):
 
 CULL_SEQUENCES, CULL_ALL_SEQ = 0, 1          # enum mvs_cull_mode
 STITCH_TRUNCATE = 1                         # MVS_STITCH_TRUNCATE (include/mvs_io.h)
+REFINE_SUBSTEP = 1                          # MVS_REFINE_SUBSTEP (include/mvs.h)
 
 
 def cam_array(cameras):

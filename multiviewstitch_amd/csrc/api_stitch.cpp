@@ -316,6 +316,50 @@ int mvs_processor_render(const char* deform_obj, const char* srt_txt, int32_t n_
     return MVS_OK;
 }
 
+int mvs_processor_refine_depths(int32_t n_seq, const char* const* seq_dirs, const int32_t* cam_off, const mvs_camera* cams, const uint8_t* imgs,
+                                const mvs_depth_refine_params* params) {
+    MVS_TRACE();
+    if (n_seq < 1) return bad(__func__, "n_seq must be >= 1");
+    if (!seq_dirs || !cam_off || !cams || !imgs) return bad(__func__, "seq_dirs, cam_off, cams and imgs must not be NULL");
+    for (int k = 0; k < n_seq; ++k)
+        if (!seq_dirs[k]) return bad(__func__, "a path of seq_dirs is NULL");
+    int rc = check_offsets(__func__, "cam_off", cam_off, n_seq);
+    if (rc) return rc;
+    size_t floats = 0;
+    for (int c = 0; c < cam_off[n_seq]; ++c) {
+        if (cams[c].w <= 0 || cams[c].h <= 0) return bad(__func__, "every camera needs w, h > 0");
+        floats += (size_t)cams[c].w * (size_t)cams[c].h;
+    }
+    mvs_depth_refine_params prm;
+    if (params) prm = *params; else mvs_depth_refine_default_params(&prm);
+    std::vector<float> ras(floats ? floats : 1), out(floats ? floats : 1);                        // the rasters of DATA/Render, DepthOptimizer.cpp:28-31
+    size_t at = 0;
+    for (int k = 0; k < n_seq; ++k)
+        for (int c = cam_off[k]; c < cam_off[k + 1]; ++c) {
+            char name[48];
+            std::snprintf(name, sizeof name, "DATA/Render/_depth%d.raw", c - cam_off[k]);
+            if ((rc = mvs_depth_raw_read(join(seq_dirs[k], name).c_str(), cams[c].w, cams[c].h, ras.data() + at))) return rc;
+            at += (size_t)cams[c].w * (size_t)cams[c].h;
+        }
+    if ((rc = refine_depth_maps_host(__func__, n_seq, cam_off, cams, imgs, ras.data(), &prm, out.data(), nullptr, nullptr, nullptr))) return rc;
+    std::vector<double> raw;
+    at = 0;
+    for (int k = 0; k < n_seq; ++k) {                                                             // DATA/Refine, :36-40
+        if (cam_off[k + 1] == cam_off[k]) continue;
+        const std::string dir = join(seq_dirs[k], "DATA/Refine/");
+        if ((rc = make_dirs(dir))) return rc;
+        for (int c = cam_off[k]; c < cam_off[k + 1]; ++c) {
+            const size_t npx = (size_t)cams[c].w * (size_t)cams[c].h;
+            raw.assign(out.begin() + (std::ptrdiff_t)at, out.begin() + (std::ptrdiff_t)(at + npx));
+            char name[32];
+            std::snprintf(name, sizeof name, "_depth%d.raw", c - cam_off[k]);
+            if ((rc = mvs_depth_raw_write((dir + name).c_str(), (int64_t)npx, raw.data()))) return rc;
+            at += npx;
+        }
+    }
+    return MVS_OK;
+}
+
 int mvs_processor_point_sample(int32_t n_seq, const char* const* seq_dirs, const int32_t* cam_off, const mvs_camera* cams,
                                const mvs_point_sample_params* params, const char* const* npts_paths, int64_t* n_points) {
     MVS_TRACE();

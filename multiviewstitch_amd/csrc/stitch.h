@@ -27,6 +27,9 @@ int render_views_dev(const double* pts, int64_t V, const int32_t* faces, int64_t
 // Validates like mvs_point_sample, reporting under the name fn.
 int point_sample_vectors(const char* fn, int32_t n_seq, const int32_t* cam_off, const mvs_camera* cams, const float* depths,
                          const mvs_point_sample_params* p, int64_t* seq_offsets, std::vector<double>* points, std::vector<double>* normals);
+// mvs_refine_depth_maps's host form (depth_refine.hip), validating and reporting under the name fn
+int refine_depth_maps_host(const char* fn, int32_t n_seq, const int32_t* cam_off, const mvs_camera* cams, const uint8_t* imgs, const float* depths,
+                           const mvs_depth_refine_params* p, float* out, int8_t* k_out, int32_t* sum_out, uint8_t* cnt_out);
 // One call of the Poisson stage (poisson.hip), whichever entry made it: `rules` says which of mvs_poisson_reconstruct (PN_PLAIN),
 // _density (PN_DENSITY: dp and dinfo) and _screened (PN_SCREENED: sp and sinfo too) it is; the parts it does not have are NULL.  The
 // points are the entry's own, host or device.

@@ -1,6 +1,8 @@
 """``Processor::Deform`` (R/Processor/Processor.cpp:1111-1138) on files, through ``mvs_processor_deform``; the tail of
 ``Processor::AlignmentSeq`` (:952-1105) through ``mvs_processor_stitch_points`` / ``mvs_processor_cull_model``;
-``Processor::Render`` (:1140-1192) through ``mvs_processor_render`` and its batched render ``mvs_render_depth_views``; the loop
+``Processor::Render`` (:1140-1192) through ``mvs_processor_render`` and its batched render ``mvs_render_depth_views``; the refinement of
+those renders against the images, DepthOptimizer::RefineAllDepthMaps (DepthRecovery/DepthOptimizer.cpp:20-43), through
+``mvs_refine_depth_maps``; the loop
 over adjacent sequences of ``Processor::CalcSimilarityTransformationSeq`` (:629-826) through ``mvs_sequence_pair_srt``; its head (:524-600)
 through ``mvs_gen_new_views`` (Image3D::GenNewViews) and ``mvs_keypoint_cull`` (the background cull of the key points); the descriptor
 matching between them, FeatureProc::MatchFeature (R/FeatureProc/FeatureProc.cpp:77-130), through ``mvs_sift_match_lists``; the SIFT
@@ -855,3 +857,87 @@ def RenderDepth(points, facets, camera, znear: float = 0.01, zfar: float = 2000.
     out = np.empty((camera.h, camera.w), np.float32)
     L.check(L.lib().mvs_render_depth(L.ptr(pts), len(pts), L.ptr(fac), len(fac), C.byref(cc), float(znear), float(zfar), L.ptr(out)))
     return out
+
+
+# ------------------------------------------------------------------ depth refinement ----
+def depth_refine_params(**kw) -> L.CDepthRefineParams:
+    """``mvs_depth_refine_default_params`` (config.txt: MinDsp 0.0025, MaxDsp 0.3, SSDError 40, SSDWin 7; refFrmCount 5 of
+    DepthOptimizer.cpp:45; rel_range 0.04, steps 8, flags ``REFINE_SUBSTEP``) with the given fields replaced."""
+    return _params(L.CDepthRefineParams, L.lib().mvs_depth_refine_default_params, kw)
+
+
+def _flat_stack(stacks, n, dev, dtype, what):
+    """the per-sequence stacks of a call as one flat array where they live (``dev``: torch, on the current stream); never empty"""
+    if dev:
+        import torch
+        flat = torch.cat([a.reshape(-1) for a in stacks]) if n > 1 else stacks[0].reshape(-1)
+        if flat.numel() == 0:
+            flat = torch.zeros(1, dtype=getattr(torch, dtype), device=flat.device)
+        return flat, _dev_ptr(flat, dtype, what)
+    flat = np.concatenate([L.arr(a, dtype).reshape(-1) for a in stacks]) if n else np.zeros(1, dtype)
+    if flat.size == 0:
+        flat = np.zeros(1, dtype)
+    return flat, L.ptr(flat)
+
+
+def RefineAllDepthMaps(cameras, imgs, depths, params: L.CDepthRefineParams | None = None, stream: int | None = None, with_detail: bool = False):
+    """DepthOptimizer::RefineAllDepthMaps (DepthRecovery/DepthOptimizer.cpp:20-43) for every sequence in one call
+    (``mvs_refine_depth_maps``; the rules, this library's definition: include/mvs.h).  ``cameras[k]`` lists sequence k's cameras;
+    ``imgs[k]`` is its RGB base images [frames, h, w, 3] uint8 and ``depths[k]`` its rendered rasters [frames, h, w] float32
+    (``RenderViews``' result) — numpy arrays, or contiguous torch tensors on the GPU (the device form: the results are tensors on the
+    same device).  ``stream`` is the HIP stream that produced them (None: the legacy default stream); the kernels, the concatenation
+    of the sequences and the allocation of the results are all ordered on it, whatever torch's current stream is.
+    -> a list with, per sequence, the refined rasters [frames, h, w] float32: what ``CheckConsistency`` and ``RunPointSample`` read.
+    With ``with_detail`` each entry is (refined, k [frames, h, w] int8, sum int32, cnt uint8): the winning hypothesis of every pixel
+    (-128 where the pixel kept its input), its sum of squared grey differences and the reference frames that took part."""
+    prm = params if params is not None else depth_refine_params()
+    n = len(cameras)
+    off, cams = L.seq_cams(cameras)
+    if len(imgs) != n or len(depths) != n:
+        raise L.MvsError(-1, f"{len(imgs)} image stacks and {len(depths)} raster stacks for {n} sequences")
+    shapes = []
+    for k in range(n):
+        want = (len(cameras[k]),) + ((int(cameras[k][0].h), int(cameras[k][0].w)) if len(cameras[k]) else tuple(depths[k].shape[1:]))
+        if tuple(depths[k].shape) != want or tuple(imgs[k].shape) != want + (3,):
+            raise L.MvsError(-1, f"depths[{k}] must be [frames, h, w] = {want} and imgs[{k}] [frames, h, w, 3]")
+        shapes.append(want)
+    dev = n > 0 and all(_is_dev(a) for a in depths) and all(_is_dev(a) for a in imgs)
+    if not dev and (any(_is_dev(a) for a in depths) or any(_is_dev(a) for a in imgs)):
+        raise L.MvsError(-1, "imgs and depths must all be tensors on the GPU or all arrays")
+    order = contextlib.nullcontext()
+    if dev and stream:
+        import torch
+        order = torch.cuda.stream(torch.cuda.ExternalStream(int(stream)))
+    with order:
+        fimg, iptr = _flat_stack(imgs, n, dev, "uint8", "imgs")
+        fdep, dptr = _flat_stack(depths, n, dev, "float32", "depths")
+        size = int(fdep.numel()) if dev else fdep.size
+        out = _out_like(fdep, size, "float32")
+        det = tuple(_out_like(fdep, size, dt) for dt in ("int8", "int32", "uint8")) if with_detail else (None, None, None)
+        fn, tail = (L.lib().mvs_refine_depth_maps_dev, (L.ptr(stream),)) if dev else (L.lib().mvs_refine_depth_maps, ())
+        L.check(fn(n, L.ptr(off), cams, iptr, dptr, C.byref(prm), L.ptr(out), *[L.ptr(a) for a in det], *tail))
+    res, at = [], 0
+    for shape in shapes:
+        m = int(np.prod(shape, dtype=np.int64))
+        cut = tuple(a[at:at + m].reshape(shape) for a in ((out,) + det if with_detail else (out,)))
+        res.append(cut if with_detail else cut[0])
+        at += m
+    return res
+
+
+def RefineDepthFiles(seq_dirs, cameras, imgs, params: L.CDepthRefineParams | None = None) -> None:
+    """``mvs_processor_refine_depths``: sequence k's rendered rasters ``seq_dirs[k]``/DATA/Render/_depth<i>.raw (what ``Render`` wrote) ->
+    ``seq_dirs[k]``/DATA/Refine/_depth<i>.raw.  ``cameras[k]`` lists sequence k's cameras, ``imgs[k]`` is its RGB base images
+    [frames, h, w, 3] uint8 (the library has no JPEG decoder: the caller decodes them)."""
+    n = len(cameras)
+    if len(seq_dirs) != n or len(imgs) != n:
+        raise L.MvsError(-1, f"{len(seq_dirs)} sequence dirs and {len(imgs)} image stacks for {n} sequences")
+    for k in range(n):
+        want = (len(cameras[k]),) + ((int(cameras[k][0].h), int(cameras[k][0].w), 3) if len(cameras[k]) else tuple(imgs[k].shape[1:]))
+        if tuple(imgs[k].shape) != want:
+            raise L.MvsError(-1, f"imgs[{k}] must be [frames, h, w, 3] = {want}")
+    off, cams = L.seq_cams(cameras)
+    dirs = (C.c_char_p * max(1, n))(*[os.fsencode(d) for d in seq_dirs])
+    flat, iptr = _flat_stack(imgs, n, False, "uint8", "imgs")
+    prm = params if params is not None else depth_refine_params()
+    L.check(L.lib().mvs_processor_refine_depths(n, dirs, L.ptr(off), cams, iptr, C.byref(prm)))

@@ -991,7 +991,9 @@ int mvs_mesh_vertex_normals_dev(int64_t V, const double* points_dev, int64_t F, 
  * LocalAlignmentCore) are listed in DESIGN.md §3. */
 
 /* PointSetUtils::SetInput + CalcPivots (R/SetUtils/PointSetUtils.cpp:3-61): barycentre, bounding box
- * {min xyz, max xyz}, the three pivots (row i of axes = i-th pivot, largest eigenvalue first), eigenvalues. */
+ * {min xyz, max xyz}, the three pivots (row i of axes = i-th pivot, largest eigenvalue first), eigenvalues.
+ * Fewer than 2 selected points (n of 0 or 1 included): MVS_E_DEGENERATE, nothing is written; mvs_remove_ground[_dev], whose
+ * first step this is, answer a scan of 0 or 1 vertices the same way and leave counts and arrays alone. */
 int mvs_pca(const double* pts, int64_t n, const int32_t* labels, uint32_t mask,
             double* barycentre /*3*/, double* bbox /*6*/, double* axes /*9*/, double* eigenvalues /*3*/);
 

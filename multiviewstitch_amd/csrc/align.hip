@@ -915,7 +915,8 @@ extern "C" {
 
 int mvs_pca(const double* pts, int64_t n, const int32_t* labels, uint32_t mask, double* bary, double* bbox, double* axes, double* evals) {
     MVS_TRACE();
-    if (!pts || n < 2 || !bary || !bbox || !axes || !evals) { mvs_set_error("bad arguments"); return MVS_E_INVALID_ARG; }
+    if (n < 0 || (n > 0 && !pts) || !bary || !bbox || !axes || !evals) { mvs_set_error("bad arguments"); return MVS_E_INVALID_ARG; }
+    if (n < 2) { mvs_set_error("PCA needs at least 2 points (got %lld)", (long long)n); return MVS_E_DEGENERATE; }   // (as a selection of 0 or 1)
     int rc = need_device();
     if (rc) return rc;
     Scratch dp, dl; Work w; Pca p;
@@ -942,7 +943,8 @@ int mvs_retain_connect_region(int64_t* V, double* pts, double* normals, int64_t*
 
 int mvs_remove_ground(int64_t* V, double* pts, double* normals, int64_t* F, int32_t* faces, double dist_thres, double* ground_ray) {
     MVS_TRACE();
-    if (!V || !F || !pts || !ground_ray || *V < 2 || *F < 0 || (*F > 0 && !faces)) { mvs_set_error("bad arguments"); return MVS_E_INVALID_ARG; }
+    if (!V || !F || !ground_ray || *V < 0 || (*V > 0 && !pts) || *F < 0 || (*F > 0 && !faces)) { mvs_set_error("bad arguments"); return MVS_E_INVALID_ARG; }
+    if (*V < 2) { mvs_set_error("PCA needs at least 2 points (got %lld)", (long long)*V); return MVS_E_DEGENERATE; }   // (its first step: nothing is touched)
     int rc = need_device();
     if (rc) return rc;
     Scratch dp, dn, df; Work w;
@@ -971,7 +973,8 @@ int mvs_retain_connect_region_dev(int64_t* V, double* pts_dev, double* normals_d
 }
 int mvs_remove_ground_dev(int64_t* V, double* pts_dev, double* normals_dev, int64_t* F, int32_t* faces_dev, double dist_thres, double* ground_ray) {
     MVS_TRACE();
-    if (!V || !F || !pts_dev || !ground_ray || *V < 2 || *F < 0 || (*F > 0 && !faces_dev)) { mvs_set_error("bad arguments"); return MVS_E_INVALID_ARG; }
+    if (!V || !F || !ground_ray || *V < 0 || (*V > 0 && !pts_dev) || *F < 0 || (*F > 0 && !faces_dev)) { mvs_set_error("bad arguments"); return MVS_E_INVALID_ARG; }
+    if (*V < 2) { mvs_set_error("PCA needs at least 2 points (got %lld)", (long long)*V); return MVS_E_DEGENERATE; }
     int rc = need_device();
     if (rc) return rc;
     HIPCHK(hipDeviceSynchronize());

@@ -919,6 +919,88 @@ int mvs_poisson_reconstruct_screened_dev(int64_t n, const double* points_dev, co
                                          double* vertices_dev, double* vertex_density_dev, int64_t vertex_capacity, int32_t* faces_dev,
                                          int64_t face_capacity, void* hip_stream);
 
+/* Band-refined levels over the dense grid: the way to config.txt's PsnDptMax 10.  The surface occupies O(G^2) of the G^3 cells of a
+ * level; mvs_poisson_reconstruct pays for the empty volume and stops at MVS_POISSON_MAX_DEPTH.  mvs_poisson_reconstruct_band solves a
+ * dense base level (base_depth, 3 .. 9) and refines it level by level on the blocks of MVS_POISSON_BAND_BLOCK^3 cells within `band`
+ * blocks (1 .. 64, Chebyshev) of the points only, each level taking its boundary values from the level below: still fp64, integer splats
+ * that do not depend on their order, a stop criterion on the true residual, two runs the same bytes.  It is unscreened and unweighted;
+ * density and screening over the band are not offered.  Like rules 1-23 this is this library's definition, NOT VERIFIED against GeoRec.
+ *  24. depth       : D = rule 3 with Dmax = min(depth_max, MVS_POISSON_BAND_MAX_DEPTH).  At depth 10 the node index and the cube
+ *                    index still fit in int32; a (node index, type) key needs int64.  B = min(D, base_depth).  With D <= base_depth
+ *                    the result is that of mvs_poisson_reconstruct at depth_min = depth_max = D.
+ *  25. base        : rules 4-8 at depth B give chi_B on the dense grid of that depth.  Every solve of the call has the budget of rule
+ *                    28, max_cycles * 64 iterations; a V-cycle of the base solve counts as one.  The base solve runs one cycle past
+ *                    its criterion (info.cycles counts it, info.rel_residual is the residual after it): every finer level takes
+ *                    chi_B in its fixed values and its right side and cannot reduce the error it carries.
+ *  26. blocks      : for every level l = B + 1 .. D: G_l = 2^l, h_l = side / G_l, and the cells form blocks of MVS_POISSON_BAND_BLOCK
+ *                    cells per axis, G_l / 4 blocks per axis.  The block of a used point is the block of its level-l cell (rule 3's
+ *                    formula at d = l).  A block is active when some used point's block lies at Chebyshev distance <= band blocks
+ *                    from it.  A cell is active when its block is; cells outside the grid are not active.  A node is FREE when all
+ *                    eight cells that touch it are active, FIXED when at least one but not all of them are, and has no value
+ *                    otherwise.  The active set of level l - 1 covers that of level l (the same points, the same band, blocks twice
+ *                    as wide).
+ *  27. start       : every node of level l that has a value starts as 0.125 * the trilinear prolongation of chi_(l-1): a node that
+ *                    coincides with a coarse node copies its value, an edge midpoint is 0.5 * (a + b), and face and cube centres
+ *                    follow by the same halving applied axis after axis in the order x, y, z (first along x on the coarse rows,
+ *                    then along y on those results, then along z).  The factor is a power of two: no rounding.  Fixed nodes keep
+ *                    this value.  (Between two dense levels the field shrinks by 1/8 per level: the splat carries unit mass, b
+ *                    carries 0.5 h, the stencil is unscaled.)
+ *  28. system      : rules 5-6 at level l define b at the free nodes (V is needed one node beyond them; every such node has a
+ *                    value).  The free nodes satisfy rule 7, the terms of fixed neighbours moved to the right side: A_ff chi_f = b',
+ *                    b' = b - A_fc chi_c.  The solve runs until the true residual, recomputed on the device, satisfies
+ *                    |b' - A_ff chi|_2 <= solve_tol * |b'|_2; the norms are sums of per-workgroup partials in a fixed order, as in
+ *                    rule 8.  max_cycles * 64 iterations without that give MVS_E_SOLVER, with the level and the residual reported.
+ *                    b' = 0 gives chi_f = 0 at once.  The solver is not part of the definition (csrc/poisson_band.hip: conjugate
+ *                    gradients from the start values); the stop criterion and the identity of two runs are.
+ *  29. iso value   : rule 9 on level D.  The cube of every used point is active, so its eight corners have values.  The sum runs
+ *                    over the used points in their order, whatever rows that are not used stand between them.
+ *  30. surface     : rules 10-12 over the active cubes of level D only.  An edge (node, type) exists when an active cube contains
+ *                    it.  Vertices are numbered in ascending (node index, type) and faces ordered by ascending cube index, then
+ *                    tetrahedron, then as listed, over what exists: the numbers of the dense call when every block is active.
+ *  31. open edges  : a crossed edge of an active cube that lies on a face shared with an inactive cell, or on the boundary of the
+ *                    grid, is counted in n_open_edges (once, whatever the number of such faces).  The mesh is returned as it is,
+ *                    open there.  Where the solve closes a scan far from every sample, level D has no field and the surface ends;
+ *                    mvs_processor_cull_model removes such closure anyway.
+ * The per-point, per-block, per-node and per-edge decisions are csrc/poisson_band_rules.h.
+ * info keeps its meaning: depth, h and iso are those of level D, cycles and rel_residual those of the base solve.  binfo's arrays are
+ * indexed by the level l and zero outside B + 1 .. D.  info and binfo are written first; then a capacity below a count gives
+ * MVS_E_INVALID_ARG and nothing is written to the outputs, as in mvs_poisson_reconstruct.  With D <= base_depth the call IS
+ * mvs_poisson_reconstruct at depth_min = depth_max = D — its bytes — and binfo is zero apart from base_depth.
+ * MVS_E_SOLVER: the base solve (failed_level = B) or a band level (failed_level = l, rel_residual[l] and iterations[l] what it reached).
+ * Scratch, from the same pool: the base stage as mvs_poisson_reconstruct at depth B (given back after level B + 1 has started), 2^(3 d
+ * - 3) bytes for one candidate depth d of rule 3 at a time, and per level (T = 2^l / 4 + 1) 7 T^3 bytes of block tables and 49.5
+ * bytes per stored node (64 per stored block), two levels at most alive at once; on level D about 4 more bytes per stored node for
+ * the surface (csrc/poisson_band_plan.h).  binfo.scratch_bytes is the peak of it all for the call made.  A level that needs more than
+ * the device has gives MVS_E_OOM with the level named, before its arrays are asked for.
+ * MVS_E_INVALID_ARG, before a device is needed: what mvs_poisson_reconstruct refuses, except that depth_min may reach
+ * MVS_POISSON_BAND_MAX_DEPTH; bparams or binfo NULL; base_depth outside [3, MVS_POISSON_MAX_DEPTH]; band outside [1, 64]; a non-zero
+ * reserved field.  After the blocks of a level are counted: a level whose stored nodes would not fit an int32 index (the level is
+ * named in mvs_last_error). */
+#define MVS_POISSON_BAND_MAX_DEPTH 10
+#define MVS_POISSON_BAND_BLOCK 4
+typedef struct mvs_poisson_band_params {
+    int32_t base_depth;         /* 8: the depth of the dense base level                           */
+    int32_t band;               /* 2: blocks around the block of a point that are active          */
+    int32_t reserved[2];        /* 0                                                              */
+} mvs_poisson_band_params;
+typedef struct mvs_poisson_band_info {           /* arrays indexed by level l, entries outside B+1..D zero */
+    int64_t n_active_blocks[MVS_POISSON_BAND_MAX_DEPTH + 1], n_free[MVS_POISSON_BAND_MAX_DEPTH + 1];
+    double  rel_residual[MVS_POISSON_BAND_MAX_DEPTH + 1], bnorm[MVS_POISSON_BAND_MAX_DEPTH + 1];   /* |b' - A_ff chi| / |b'|, |b'| */
+    int32_t iterations[MVS_POISSON_BAND_MAX_DEPTH + 1];
+    int64_t n_open_edges, scratch_bytes;          /* rule 31; peak bytes taken from the pool by the call */
+    int32_t base_depth, failed_level;             /* B of rule 24; the level of MVS_E_SOLVER, else 0    */
+} mvs_poisson_band_info;
+/* the values in the comments above */
+void mvs_poisson_band_default_params(mvs_poisson_band_params* p);
+int mvs_poisson_reconstruct_band(int64_t n, const double* points, const double* normals, const mvs_poisson_params* p,
+                                 const mvs_poisson_band_params* bparams, mvs_poisson_info* info, mvs_poisson_band_info* binfo,
+                                 double* vertices, int64_t vertex_capacity, int32_t* faces, int64_t face_capacity);
+/* the device form, as mvs_poisson_reconstruct_dev */
+int mvs_poisson_reconstruct_band_dev(int64_t n, const double* points_dev, const double* normals_dev, const mvs_poisson_params* p,
+                                     const mvs_poisson_band_params* bparams, mvs_poisson_info* info, mvs_poisson_band_info* binfo,
+                                     double* vertices_dev, int64_t vertex_capacity, int32_t* faces_dev, int64_t face_capacity,
+                                     void* hip_stream);
+
 /* Rule 18 on any triangle mesh: vertices[V][3], normals[V][3] (may be NULL, then normals_out is not written), faces[F][3], values[V].
  * The outputs hold V resp. F rows and do not overlap the inputs; V_out / F_out receive the rows kept.  An ordered compaction without
  * atomics: two runs give the same bytes.  MVS_E_INVALID_ARG, before a device is needed: a NULL argument other than normals /

@@ -135,6 +135,13 @@ int mvs_processor_poisson_density(const char* psr_npts, const mvs_poisson_params
 int mvs_processor_poisson_screened(const char* psr_npts, const mvs_poisson_params* params, const mvs_poisson_density_params* dparams,
                                    const mvs_poisson_screen_params* sparams, double trim_ratio, const char* model_obj, int64_t* V, int64_t* F);
 
+/* mvs_processor_poisson through mvs_poisson_reconstruct_band (rules 24-31 of include/mvs.h: this library's definition, NOT VERIFIED
+ * against GeoRec): the way to PsnDptMax 10.  bparams NULL: the defaults (base_depth 8, band 2).  Model.obj carries `vn` lines as that of
+ * mvs_processor_poisson does; where the depth stays at or below base_depth the file holds the bytes mvs_processor_poisson writes at that
+ * depth.  n_open_edges (may be NULL) receives rule 31's count. */
+int mvs_processor_poisson_band(const char* psr_npts, const mvs_poisson_params* params, const mvs_poisson_band_params* bparams,
+                               const char* model_obj, int64_t* V, int64_t* F, int64_t* n_open_edges);
+
 #ifdef __cplusplus
 }
 #endif

@@ -97,6 +97,16 @@ int mvs_test_poisson_screened(int64_t n, const double* points, const double* nor
                               mvs_poisson_density_info* dinfo, mvs_poisson_screen_info* sinfo, int64_t* stencil, double* f, double* chi0,
                               double* chi, int64_t node_capacity, int32_t diagonal);
 
+/* mvs_poisson_reconstruct_band up to rule 29 (info with the iso value, binfo; n_vertices, n_faces and n_open_edges stay 0), with band
+ * level `level` expanded to the dense layout of its grid, node order [iz][iy][ix], n1 = 2^level + 1: active [(2^level / 4)^3] (1: the
+ * block is active), cls [n1^3] (0 no value, 1 fixed, 2 free), b [n1^3] (rule 6 at the free nodes, 0 at the fixed ones) and chi [n1^3];
+ * b and chi hold NaN where a node has no value.  For small levels: the expansion runs on the host.  MVS_E_INVALID_ARG: what the call
+ * refuses, a NULL array, a level outside base_depth + 1 .. D (after info's depth and binfo's base_depth are written), n1^3 above
+ * node_capacity.  MVS_E_SOLVER of that level still hands out what the iterations reached; of a level below it, nothing. */
+int mvs_test_poisson_band_level(int64_t n, const double* points, const double* normals, const mvs_poisson_params* p,
+                                const mvs_poisson_band_params* bparams, mvs_poisson_info* info, mvs_poisson_band_info* binfo, int32_t level,
+                                uint8_t* active, uint8_t* cls, double* b, double* chi, int64_t node_capacity);
+
 /* mvs_grabcut_masks (host form) with its steps handed out, N = (w / 2) * (h / 2); every array but mask may be NULL:
  *   S [n] int64 (rule 7) and ncap [n][8][N] int32 (rule 8, the layout of mvs_grid_mincut's cap), once per call;
  *   labels [iters + 1][n][N] uint8 and sums [iters + 1][n][2][5][10] int64 (model 0 = foreground; per component c | s0 s1 s2 | p00 p01

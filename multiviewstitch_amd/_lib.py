@@ -117,6 +117,22 @@ class CPoissonScreenParams(C.Structure):
     _fields_ = [("alpha", C.c_double), ("reserved", C.c_int64)]
 
 
+class CPoissonBandParams(C.Structure):
+    """struct mvs_poisson_band_params."""
+    _fields_ = [("base_depth", C.c_int32), ("band", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+POISSON_BAND_MAX_DEPTH = 10                 # MVS_POISSON_BAND_MAX_DEPTH
+
+
+class CPoissonBandInfo(C.Structure):
+    """struct mvs_poisson_band_info: the arrays are indexed by the level."""
+    _fields_ = [("n_active_blocks", C.c_int64 * (POISSON_BAND_MAX_DEPTH + 1)), ("n_free", C.c_int64 * (POISSON_BAND_MAX_DEPTH + 1)),
+                ("rel_residual", C.c_double * (POISSON_BAND_MAX_DEPTH + 1)), ("bnorm", C.c_double * (POISSON_BAND_MAX_DEPTH + 1)),
+                ("iterations", C.c_int32 * (POISSON_BAND_MAX_DEPTH + 1)), ("n_open_edges", C.c_int64), ("scratch_bytes", C.c_int64),
+                ("base_depth", C.c_int32), ("failed_level", C.c_int32)]
+
+
 class CPoissonScreenInfo(C.Structure):
     """struct mvs_poisson_screen_info."""
     _fields_ = [("target", C.c_double), ("lambda_", C.c_double), ("rel_residual", C.c_double), ("iso_unscreened", C.c_double),
@@ -191,6 +207,9 @@ _SIGS = {
     "mvs_poisson_screen_default_params": (None, [_VP]),
     "mvs_poisson_reconstruct_screened": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _I64]),
     "mvs_poisson_reconstruct_screened_dev": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _I64, _VP]),
+    "mvs_poisson_band_default_params": (None, [_VP]),
+    "mvs_poisson_reconstruct_band": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _I64]),
+    "mvs_poisson_reconstruct_band_dev": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _I64, _VP]),
     "mvs_mesh_trim_by_value": (C.c_int, [_I64, _VP, _VP, _I64, _VP, _VP, _D, _VP, _VP, _VP, _VP, _VP]),
     "mvs_mesh_trim_by_value_dev": (C.c_int, [_I64, _VP, _VP, _I64, _VP, _VP, _D, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mvs_render_depth": (C.c_int, [_VP, _I64, _VP, _I64, _VP, C.c_float, C.c_float, _VP]),
@@ -289,6 +308,7 @@ _SIGS = {
     "mvs_processor_poisson": (C.c_int, [C.c_char_p, _VP, C.c_char_p, _VP, _VP]),
     "mvs_processor_poisson_density": (C.c_int, [C.c_char_p, _VP, _VP, _D, C.c_char_p, _VP, _VP]),
     "mvs_processor_poisson_screened": (C.c_int, [C.c_char_p, _VP, _VP, _VP, _D, C.c_char_p, _VP, _VP]),
+    "mvs_processor_poisson_band": (C.c_int, [C.c_char_p, _VP, _VP, C.c_char_p, _VP, _VP, _VP]),
     # include/mvs_test.h (test hooks: per handle, not part of the drop-in ABI)
     "mvs_test_preload_wait": (C.c_int, []),
     "mvs_test_ctl": (C.c_int, [_VP, _VP, _I32]),
@@ -306,6 +326,7 @@ _SIGS = {
     "mvs_test_poisson_field": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _I64]),
     "mvs_test_poisson_density": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _I64]),
     "mvs_test_poisson_screened": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _I32]),
+    "mvs_test_poisson_band_level": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _I64]),
     "mvs_test_rotations": (C.c_int, [_I64, _VP, _I32, _VP, _VP, _VP]),
 }
 EXPORTS = tuple(_SIGS)

@@ -401,7 +401,8 @@ int mvs_processor_point_sample(int32_t n_seq, const char* const* seq_dirs, const
 
 // PSR.npts -> Model.obj; dprm != NULL: through rules 14-17, and trimmed by rule 18 when trim_ratio > 0; sprm != NULL (with dprm): rules 19-23
 static int poisson_files(const char* fn, const char* psr_npts, const mvs_poisson_params& prm, const mvs_poisson_density_params* dprm, double trim_ratio,
-                         const char* model_obj, int64_t* V_out, int64_t* F_out, const mvs_poisson_screen_params* sprm) {
+                         const char* model_obj, int64_t* V_out, int64_t* F_out, const mvs_poisson_screen_params* sprm,
+                         const mvs_poisson_band_params* bprm = nullptr /*alone: rules 24-31*/, int64_t* open_out = nullptr) {
     int rc = need_device();
     if (rc) return rc;
     int64_t n = 0;
@@ -417,7 +418,11 @@ static int poisson_files(const char* fn, const char* psr_npts, const mvs_poisson
     if ((rc = up(dp, hp.data(), (size_t)n * 3)) || (rc = up(dn, hn.data(), (size_t)n * 3))) return rc;
     const PnCall call{fn, sprm ? PN_SCREENED : dprm ? PN_DENSITY : PN_PLAIN, n, dp.as<double>(), dn.as<double>(), &prm, &info, dprm, dprm ? &dinfo : nullptr,
                       sprm, sprm ? &sinfo : nullptr};
-    if ((rc = poisson_blocks(call, &dv, &dd, &df))) return rc;
+    mvs_poisson_band_info binfo;
+    if (bprm) {
+        if ((rc = poisson_band_blocks(fn, n, dp.as<double>(), dn.as<double>(), &prm, bprm, &info, &binfo, &dv, &df))) return rc;
+        if (open_out) *open_out = binfo.n_open_edges;
+    } else if ((rc = poisson_blocks(call, &dv, &dd, &df))) return rc;
     int64_t V = info.n_vertices, F = info.n_faces;
     const Scratch *mv = &dv, *mf = &df;
     if (dprm && trim_ratio > 0.0) {
@@ -469,6 +474,17 @@ int mvs_processor_poisson_screened(const char* psr_npts, const mvs_poisson_param
     if (dparams) dprm = *dparams; else mvs_poisson_density_default_params(&dprm);
     if (sparams) sprm = *sparams; else mvs_poisson_screen_default_params(&sprm);
     return poisson_files(__func__, psr_npts, prm, &dprm, trim_ratio, model_obj, V_out, F_out, &sprm);
+}
+
+int mvs_processor_poisson_band(const char* psr_npts, const mvs_poisson_params* params, const mvs_poisson_band_params* bparams, const char* model_obj,
+                               int64_t* V_out, int64_t* F_out, int64_t* n_open_edges) {
+    MVS_TRACE();
+    if (!psr_npts || !model_obj) return bad(__func__, "psr_npts / model_obj is NULL");
+    mvs_poisson_params prm;
+    mvs_poisson_band_params bprm;
+    if (params) prm = *params; else mvs_poisson_default_params(&prm);
+    if (bparams) bprm = *bparams; else mvs_poisson_band_default_params(&bprm);
+    return poisson_files(__func__, psr_npts, prm, nullptr, 0.0, model_obj, V_out, F_out, nullptr, &bprm, n_open_edges);
 }
 
 }  // extern "C"

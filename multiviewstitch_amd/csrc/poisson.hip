@@ -39,6 +39,7 @@
 #include "poisson_rules.h"
 #include "knobs.h"
 #include "stitch.h"
+#include "poisson_base.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -785,7 +786,7 @@ __global__ __launch_bounds__(PN_TPB) void k_pn_face_scatter(int G, const uint8_t
 
 // ------------------------------------------------------------------ host ----
 int check_pn(const char* fn, int64_t n, const void* points, const void* normals, const mvs_poisson_params* p, const void* info,
-             const void* out_a, int64_t cap_a, const void* out_b, int64_t cap_b) {
+             const void* out_a, int64_t cap_a, const void* out_b, int64_t cap_b, int max_depth = PN_MAX_D) {
     if (!points || !normals || !p || !info) return bad(fn, "points, normals, params or info is NULL");
     if (n < 0) return bad(fn, "n is negative");
     if (cap_a < 0 || cap_b < 0) return bad(fn, "a capacity is negative");
@@ -794,7 +795,7 @@ int check_pn(const char* fn, int64_t n, const void* points, const void* normals,
     if (p->scale <= 0.0 || p->samples_per_node <= 0.0 || p->solve_tol <= 0.0) return bad(fn, "need scale, samples_per_node, solve_tol > 0");
     if (p->depth_min < 3) return bad(fn, "need depth_min >= 3");
     if (p->depth_min > p->depth_max) return bad(fn, "depth_min exceeds depth_max");
-    if (p->depth_min > PN_MAX_D) return bad(fn, "depth_min exceeds MVS_POISSON_MAX_DEPTH");
+    if (p->depth_min > max_depth) return bad(fn, max_depth == PN_MAX_D ? "depth_min exceeds MVS_POISSON_MAX_DEPTH" : "depth_min exceeds the call's largest depth");
     if (p->scale <= 1.0 + 4.0 / (double)(1 << p->depth_min)) return bad(fn, "need scale > 1 + 4 / 2^depth_min: every point a cell from the boundary");
     if (p->max_cycles < 1) return bad(fn, "need max_cycles >= 1");
     return MVS_OK;
@@ -1290,6 +1291,56 @@ int poisson_blocks(const PnCall& c, Scratch* vertices, Scratch* density, Scratch
     if (rc) return rc;
     return reconstruct(c, c.points, c.normals, PnOut{nullptr, nullptr, nullptr, INT64_MAX, INT64_MAX, vertices, c.rules >= PN_DENSITY ? density : nullptr, faces},
                        nullptr);
+}
+
+// ------------------------------------------------------------------ for poisson_band.hip (poisson_base.h) ----
+int poisson_check_plain(const PnCall& c, int max_depth, const void* out_a, int64_t cap_a, const void* out_b, int64_t cap_b) {
+    return check_pn(c.fn, c.n, c.points, c.normals, c.p, c.info, out_a, cap_a, out_b, cap_b, max_depth);
+}
+
+int poisson_cube(const PnCall& c, const double* pts_dev, const double* nrm_dev, hipStream_t s, double origin[3], double* side) {
+    mvs_poisson_params p3 = *c.p;
+    p3.depth_min = p3.depth_max = 3;      // rule 3 has no choice to make: no occupancy pass
+    PnCall c3 = c;
+    c3.p = &p3;
+    PnRun run(c3, pts_dev, nrm_dev, s);
+    const int rc = run.grid(c.fn);
+    if (rc) return rc;
+    for (int a = 0; a < 3; ++a) origin[a] = run.g.o[a];
+    *side = run.side;
+    return MVS_OK;
+}
+
+PnBaseField::~PnBaseField() { delete (PnRun*)run; }
+
+int PnBaseField::solve(const PnCall& c, const double* pts_dev, const double* nrm_dev, hipStream_t s) {
+    int rc;
+    PnRun* r = new PnRun(c, pts_dev, nrm_dev, s);
+    run = r;
+    if ((rc = r->grid(c.fn)) || (rc = r->field(c.fn))) return rc;
+    if (c.info->cycles > 0) {
+        // One cycle past the criterion.  The finer levels take this field as their fixed values and in their right sides and cannot
+        // reduce its error; a cycle costs a thirteenth of this solve and takes the error down by the cycle's contraction.
+        double before = 0.0, after = 0.0;
+        double* x = r->L.x[c.info->depth];
+        if ((rc = r->norm2<MgPlain>(x, &before))) return rc;
+        if (before > 0.0) {
+            if ((rc = r->vcycle<MgPlain>()) || (rc = r->norm2<MgPlain>(x, &after))) return rc;
+            c.info->cycles += 1;
+            c.info->rel_residual *= std::sqrt(after) / std::sqrt(before);
+        }
+    }
+    g = r->g;
+    chi = r->L.x[c.info->depth];
+    size_t below = 0;
+    for (int l = 1; l < c.info->depth; ++l) below += 3 * (size_t)((1 << l) + 1) * ((1 << l) + 1) * ((1 << l) + 1);
+    bytes = (int64_t)(32 * (size_t)r->nn + 8 * below);
+    return MVS_OK;
+}
+
+int poisson_plain_dev(const PnCall& c, const double* pts_dev, const double* nrm_dev, double* vertices_dev, int64_t vcap, int32_t* faces_dev,
+                      int64_t fcap, Scratch* bv, Scratch* bf, hipStream_t s) {
+    return reconstruct(c, pts_dev, nrm_dev, PnOut{vertices_dev, nullptr, faces_dev, vcap, fcap, bv, nullptr, bf}, s);
 }
 
 extern "C" {

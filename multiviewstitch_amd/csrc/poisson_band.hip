@@ -1,0 +1,1115 @@
+// poisson_band.hip — mvs_poisson_reconstruct_band (include/mvs.h, rules 24-31): a dense base level from poisson.hip (poisson_base.h),
+// then every level l = B + 1 .. D on the blocks of 4^3 cells near the points only.  poisson_band_rules.h makes every decision — the
+// block of a point, the dilation, the class of a node, its start value, the state of an edge, the place of a row in rule 30's order —;
+// poisson_band_plan.h does the host's sizing; this file stores and moves.
+//
+// A level keeps a table of T = G / 4 + 1 entries per axis (the node plane ix = G belongs to block index G / 4) and, for every STORED
+// block — an active one, or one that holds a node with a value: a block whose neighbour at offset -1 along any subset of axes is
+// active —, 64 nodes (the lower corners of its 4^3 cells) in planar arrays: node 64 s + lx + 4 ly + 16 lz.  One wave owns one block, so a
+// wave's loads and stores are one contiguous 512-byte run per array; the in-block neighbours come by wave shuffle, the 16 lanes of
+// each face read the face neighbour's run (its number is in the block's six-entry neighbour list).
+//
+//   k_bd_occupy / k_bd_popcount           rule 24: rule 3's occupied cells, one candidate depth at a time (depth 10 included)
+//   k_bd_mark / k_bd_dilate / k_bd_stored rule 26: the blocks of the points (plain byte stores of 1), three bd_dilate_at passes, the stored blocks
+//   k_bd_row_count / k_bd_number          the stored blocks numbered in (bz, by, bx) order: a wave per table row counts and ranks by
+//                                         ballot, the host scans the T^2 row counts (bd_row_firsts; it needs the total anyway).  No atomic counter
+//   k_bd_neighbours / k_bd_rows           the six face neighbours of every block; on level D the block and row behind every place of bd_segment
+//   k_bd_class_start<Coarse>              rules 26-27: the class byte and the start value, from the dense chi_B or the level below's blocks
+//   k_bd_splat / k_bd_rhs                 rules 5-6 into block storage: int64 atomic adds, then b at the free nodes
+//   k_bd_bnorm                            |b'|^2, b' = b - A_fc chi_c: the stencil over the vector of the fixed values and zeros
+//   k_bd_residual<WRITE>                  the TRUE residual of the free nodes from chi and b (fixed neighbours included: the same number
+//                                         as b' - A_ff chi_f); WRITE: it becomes r of the solve
+//   k_bd_apply / k_bd_update              rule 28's solve, conjugate gradients on 6 x - S = -b' from the start values: p = r + beta p
+//                                         and A p fused with the p . A p partials; x, r updated fused with the r . r partials.  Every
+//                                         workgroup folds the (at most BD_NPART) partials of the launch before in a fixed order: the
+//                                         step lengths never leave the device, the host reads one number per 64 iterations
+//   k_bd_fold                             the sum of partials by one workgroup, as k_pn_fold
+//   k_bd_used_count / k_bd_used_scatter / k_bd_iso
+//                                         rule 29: the reduction of k_pn_iso through the block table, over the used rows listed in
+//                                         their order by an ordered compaction, so rows that are not used move no bit of the iso value
+//   k_bd_cubemask / k_bd_edge_count / k_bd_vertex_scatter / k_bd_face_count / k_bd_face_scatter
+//                                         rules 30-31 over the stored nodes in the order bd_segment gives them: the two ordered
+//                                         compactions of poisson.hip, items = (place of the node) * 7 + type resp. * 12 + slot (int64)
+// Nothing but integer atomics (the splat, the bitmap, the count of open edges) is unordered: two runs give the same bytes.
+#include "engine.h"
+#include "trace.h"
+#include "frontend_dev.h"
+#include "poisson_band_rules.h"
+#include "poisson_band_plan.h"
+#include "poisson_base.h"
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <limits>
+#include <memory>
+#include <vector>
+
+static_assert(BP_MAX_DEPTH == MVS_POISSON_BAND_MAX_DEPTH && BP_BLOCK == MVS_POISSON_BAND_BLOCK && BD_BLOCK == MVS_POISSON_BAND_BLOCK, "one block size, one depth limit");
+
+namespace {
+
+constexpr int BD_TPB = 256, BD_WAVES = BD_TPB / 64;
+constexpr int BD_RED_NB = 1024;          // workgroups of a reduction over the points
+constexpr int BD_NPART = 1024;           // workgroups of a solver launch at most: the partials every workgroup folds
+constexpr int BD_MAX_D = MVS_POISSON_BAND_MAX_DEPTH;
+constexpr int BD_SCAN_CH = 4096;
+
+// the sum of v over the workgroup in a fixed order (shuffles inside a wave, then the waves in order), valid in thread 0: wg_sum of poisson.hip
+__device__ inline double bd_wg_sum(double v, double* s_part, int tid) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = v + __shfl_down(v, o, 64);
+    if ((tid & 63) == 0) s_part[tid >> 6] = v;
+    __syncthreads();
+    double t = 0.0;
+    if (tid == 0)
+        for (int q = 0; q < BD_WAVES; ++q) t = t + s_part[q];
+    return t;
+}
+// the sum of n partials, the same number in every thread of every workgroup: thread t takes t, t + 256, ... ascending, then bd_wg_sum
+__device__ inline double bd_fold_all(const double* __restrict__ part, int n, double* s_part, double* s_out) {
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < n; i += BD_TPB) acc += part[i];
+    const double t = bd_wg_sum(acc, s_part, threadIdx.x);
+    if (threadIdx.x == 0) *s_out = t;
+    __syncthreads();
+    return *s_out;
+}
+
+__global__ __launch_bounds__(BD_TPB) void k_bd_fold(const double* __restrict__ part, int n, double* __restrict__ out) {
+    __shared__ double s_part[BD_WAVES];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < n; i += BD_TPB) acc += part[i];
+    const double t = bd_wg_sum(acc, s_part, threadIdx.x);
+    if (threadIdx.x == 0) *out = t;
+}
+
+// ------------------------------------------------------------------ rule 24 ----
+__global__ __launch_bounds__(BD_TPB) void k_bd_occupy(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm, PnGrid g,
+                                                      unsigned* __restrict__ bits) {
+    const int64_t i = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
+    if (i >= n || !pn_used(pts + 3 * i, nrm + 3 * i)) return;
+    const int m = g.G;
+    const int64_t cell = ((int64_t)pn_cell(pts[3 * i + 2], g.o[2], g.h, m) * m + pn_cell(pts[3 * i + 1], g.o[1], g.h, m)) * m + pn_cell(pts[3 * i], g.o[0], g.h, m);
+    atomicOr(bits + (cell >> 5), 1u << (cell & 31));
+}
+__global__ __launch_bounds__(BD_TPB) void k_bd_popcount(int64_t words, const unsigned* __restrict__ bits, unsigned long long* __restrict__ occupied) {
+    const int64_t w = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
+    const unsigned v = w < words ? bits[w] : 0u;
+    if (v) atomicAdd(occupied, (unsigned long long)__popc(v));
+}
+
+// ------------------------------------------------------------------ the level as the kernels see it ----
+struct BdView {
+    int32_t G, T, Gb;
+    const uint8_t* act;                   // T^3: is the block active?
+    const int32_t* num;                   // T^3: the stored number of the block, -1: not stored
+    const int32_t* first;                 // T^2 + 1: the row firsts (bd_row_firsts)
+};
+__device__ inline int64_t bd_tab(const BdView& v, int bx, int by, int bz) { return ((int64_t)bz * v.T + by) * v.T + bx; }
+struct BdActive {
+    BdView v;
+    __device__ bool operator()(int cx, int cy, int cz) const { return v.act[bd_tab(v, cx >> 2, cy >> 2, cz >> 2)] != 0; }
+};
+// node (ix, iy, iz) in [0, G]^3 -> its place 64 s + lane in the node arrays, -1 when its block is not stored
+__device__ inline int64_t bd_slot(const BdView& v, int ix, int iy, int iz) {
+    const int s = v.num[bd_tab(v, ix >> 2, iy >> 2, iz >> 2)];
+    return s < 0 ? -1 : (int64_t)s * 64 + ((iz & 3) << 4 | (iy & 3) << 2 | (ix & 3));
+}
+__device__ inline void bd_unpack(int32_t c, int* bx, int* by, int* bz) { *bx = c & 1023; *by = c >> 10 & 1023; *bz = c >> 20 & 1023; }
+
+// ------------------------------------------------------------------ rule 26 ----
+__global__ __launch_bounds__(BD_TPB) void k_bd_mark(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm, PnGrid g, int T,
+                                                    uint8_t* __restrict__ tab) {
+    const int64_t i = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
+    if (i >= n || !pn_used(pts + 3 * i, nrm + 3 * i)) return;
+    int b[3];
+    bd_point_block(pts + 3 * i, g.o, g.h, g.G, b);
+    tab[((int64_t)b[2] * T + b[1]) * T + b[0]] = 1;
+}
+
+__global__ __launch_bounds__(BD_TPB) void k_bd_dilate(int T, int Gb, const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int axis, int band) {
+    const int64_t at = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
+    if (at >= (int64_t)T * T * T) return;
+    const int bx = (int)(at % T), by = (int)(at / T % T), bz = (int)(at / ((int64_t)T * T));
+    out[at] = bx < Gb && by < Gb && bz < Gb && bd_dilate_at(in, T, Gb, bx, by, bz, axis, band) ? 1 : 0;
+}
+
+__global__ __launch_bounds__(BD_TPB) void k_bd_stored(int T, const uint8_t* __restrict__ act, uint8_t* __restrict__ stored) {
+    const int64_t at = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
+    if (at >= (int64_t)T * T * T) return;
+    const int bx = (int)(at % T), by = (int)(at / T % T), bz = (int)(at / ((int64_t)T * T));
+    bool any = false;
+    for (int c = 0; c < 8; ++c) {
+        const int qx = bx - (c & 1), qy = by - (c >> 1 & 1), qz = bz - (c >> 2 & 1);
+        if (qx < 0 || qy < 0 || qz < 0) continue;
+        any = any || act[((int64_t)qz * T + qy) * T + qx];
+    }
+    stored[at] = any ? 1 : 0;
+}
+
+// a wave per row (bz, by) of the table: how many of its T blocks are stored
+__global__ __launch_bounds__(BD_TPB) void k_bd_row_count(int T, const uint8_t* __restrict__ stored, int32_t* __restrict__ cnt) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * BD_WAVES + (threadIdx.x >> 6);
+    if (row >= (int64_t)T * T) return;                                       // the whole wave
+    int acc = 0;
+    for (int c0 = 0; c0 < T; c0 += 64) {
+        const bool f = c0 + lane < T && stored[row * T + c0 + lane];
+        acc += __popcll(__ballot(f));
+    }
+    if (lane == 0) cnt[row] = acc;
+}
+
+// ... and their numbers, ascending along the row from the row's first; coord[s] = bx | by << 10 | bz << 20
+__global__ __launch_bounds__(BD_TPB) void k_bd_number(int T, const uint8_t* __restrict__ stored, const int32_t* __restrict__ first,
+                                                      int32_t* __restrict__ num, int32_t* __restrict__ coord) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * BD_WAVES + (threadIdx.x >> 6);
+    if (row >= (int64_t)T * T) return;
+    int acc = first[row];
+    for (int c0 = 0; c0 < T; c0 += 64) {
+        const int bx = c0 + lane;
+        const bool f = bx < T && stored[row * T + bx];
+        const unsigned long long bal = __ballot(f);
+        const int s = acc + __popcll(bal & ((1ull << lane) - 1ull));
+        if (bx < T) num[row * T + bx] = f ? s : -1;
+        if (f) coord[s] = bx | (int)(row % T) << 10 | (int)(row / T) << 20;
+        acc += __popcll(bal);
+    }
+}
+
+// nbr[6 s + f]: the stored number of the neighbour of block s across face f = -x, +x, -y, +y, -z, +z; -1: none
+__global__ __launch_bounds__(BD_TPB) void k_bd_neighbours(int64_t ns, const int32_t* __restrict__ coord, BdView v, int32_t* __restrict__ nbr) {
+    const int64_t i = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
+    if (i >= 6 * ns) return;
+    const int f = (int)(i % 6);
+    int b[3];
+    bd_unpack(coord[i / 6], &b[0], &b[1], &b[2]);
+    b[f >> 1] += f & 1 ? 1 : -1;
+    nbr[i] = b[f >> 1] < 0 || b[f >> 1] >= v.T ? -1 : v.num[bd_tab(v, b[0], b[1], b[2])];
+}
+
+// rows[place] = 16 s + 4 lz + ly for the row of four nodes at (ly, lz) of block s, place = bd_segment: the stored rows in (iz, iy, ix) order
+__global__ __launch_bounds__(BD_TPB) void k_bd_rows(int64_t ns, const int32_t* __restrict__ coord, BdView v, int32_t* __restrict__ rows) {
+    const int64_t i = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
+    if (i >= 16 * ns) return;
+    const int s = (int)(i >> 4), ly = (int)(i & 3), lz = (int)(i >> 2 & 3);
+    int bx, by, bz;
+    bd_unpack(coord[s], &bx, &by, &bz);
+    const BdRowSlab q = bd_row_slab(v.first, v.T, by, bz);
+    rows[bd_segment(s, ly, lz, q.rfirst, q.rcnt, q.sfirst, q.scnt)] = (int32_t)i;
+}
+
+// ------------------------------------------------------------------ rules 26-27 ----
+struct BdDenseCoarse {                   // chi_B on the dense grid of Gc cells
+    const double* chi;
+    int Gc;
+    __device__ double operator()(int jx, int jy, int jz) const { return chi[pn_node(Gc, jx, jy, jz)]; }
+};
+struct BdBlockCoarse {                   // chi of the level below in its blocks; rule 26's nesting: the node is stored
+    BdView v;
+    const double* chi;
+    __device__ double operator()(int jx, int jy, int jz) const {
+        const int64_t at = bd_slot(v, jx, jy, jz);
+        return at < 0 ? NAN : chi[at];
+    }
+};
+
+template <class Coarse>
+__global__ __launch_bounds__(BD_TPB) void k_bd_class_start(int64_t ns, const int32_t* __restrict__ coord, BdView v, Coarse coarse,
+                                                           uint8_t* __restrict__ cls, double* __restrict__ x) {
+    const int64_t at = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
+    if (at >= 64 * ns) return;
+    const int lane = (int)(at & 63);
+    int bx, by, bz;
+    bd_unpack(coord[at >> 6], &bx, &by, &bz);
+    const int ix = 4 * bx + (lane & 3), iy = 4 * by + (lane >> 2 & 3), iz = 4 * bz + (lane >> 4);
+    int c = BD_NONE;
+    if (ix <= v.G && iy <= v.G && iz <= v.G) c = bd_node_class(v.G, ix, iy, iz, BdActive{v});
+    cls[at] = (uint8_t)c;
+    x[at] = c == BD_NONE ? 0.0 : bd_start_value(ix, iy, iz, coarse);
+}
+
+// ------------------------------------------------------------------ rules 5-6 in block storage ----
+__global__ __launch_bounds__(BD_TPB) void k_bd_splat(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm, PnGrid g, BdView v,
+                                                     int64_t nodes, unsigned long long* __restrict__ sums) {
+    const int64_t i = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
+    if (i >= n || !pn_used(pts + 3 * i, nrm + 3 * i)) return;
+    int i0[3];
+    double w[8];
+    pn_corners_weights(pts + 3 * i, g, i0, w);
+    for (int c = 0; c < 8; ++c) {
+        const int64_t at = bd_slot(v, i0[0] + (c & 1), i0[1] + (c >> 1 & 1), i0[2] + (c >> 2 & 1));
+        if (at < 0) continue;                                                // rule 29: cannot be, the cube of a used point is active
+        for (int a = 0; a < 3; ++a) atomicAdd(sums + a * nodes + at, (unsigned long long)pn_quant(w[c] * nrm[3 * i + a]));
+    }
+}
+
+// the places of the six neighbours of node `lane` of block s, in the order of nbr; -1: in a block that is not stored
+__device__ inline void bd_nb_slots(const int32_t* __restrict__ nb, int64_t s, int lane, int64_t at[6]) {
+    const int l[3] = {lane & 3, lane >> 2 & 3, lane >> 4};
+    for (int a = 0; a < 3; ++a) {
+        const int st = 1 << (2 * a);
+        at[2 * a] = l[a] > 0 ? s * 64 + lane - st : nb[2 * a] >= 0 ? (int64_t)nb[2 * a] * 64 + lane + 3 * st : -1;
+        at[2 * a + 1] = l[a] < 3 ? s * 64 + lane + st : nb[2 * a + 1] >= 0 ? (int64_t)nb[2 * a + 1] * 64 + lane - 3 * st : -1;
+    }
+}
+
+// rule 6 at the free nodes (k_pn_rhs's expression); 0 elsewhere
+__global__ __launch_bounds__(BD_TPB) void k_bd_rhs(int64_t ns, const int32_t* __restrict__ nbr, const uint8_t* __restrict__ cls, int64_t nodes,
+                                                   const long long* __restrict__ sums, double h, double* __restrict__ b) {
+    const int64_t at = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
+    if (at >= 64 * ns) return;
+    double val = 0.0;
+    if (cls[at] == BD_FREE) {
+        int64_t q[6];
+        bd_nb_slots(nbr + 6 * (at >> 6), at >> 6, (int)(at & 63), q);
+        const long long *sx = sums, *sy = sums + nodes, *sz = sums + 2 * nodes;
+        // every neighbour of a free node has a value, so its block is stored and no q is -1; a table that broke that must not read outside
+        const auto V = [](const long long* a, int64_t i) { return i < 0 ? 0.0 : pn_dequant(a[i]); };
+        val = (((V(sx, q[1]) - V(sx, q[0])) + (V(sy, q[3]) - V(sy, q[2]))) + (V(sz, q[5]) - V(sz, q[4]))) * (0.5 * h);
+    }
+    b[at] = val;
+}
+
+// ------------------------------------------------------------------ rule 28 ----
+// The six-neighbour sum of a planar quantity at node `lane` of the wave's block (every lane of the wave calls it): own the lane's value,
+// load(place) the same quantity anywhere; the neighbours inside the block come by shuffle, those across a face from the neighbour's
+// run, 0 where that block is not stored (only beside nodes that are not free).  The order of pn_nbr_sum.
+template <class F>
+__device__ inline double bd_sum6(double own, const int32_t* __restrict__ nb, int lane, F load) {
+    const int lx = lane & 3, ly = lane >> 2 & 3, lz = lane >> 4;
+    double xm = __shfl(own, (lane + 63) & 63, 64), xp = __shfl(own, (lane + 1) & 63, 64);
+    double ym = __shfl(own, (lane + 60) & 63, 64), yp = __shfl(own, (lane + 4) & 63, 64);
+    double zm = __shfl(own, (lane + 48) & 63, 64), zp = __shfl(own, (lane + 16) & 63, 64);
+    if (lx == 0) xm = nb[0] >= 0 ? load((int64_t)nb[0] * 64 + lane + 3) : 0.0;
+    if (lx == 3) xp = nb[1] >= 0 ? load((int64_t)nb[1] * 64 + lane - 3) : 0.0;
+    if (ly == 0) ym = nb[2] >= 0 ? load((int64_t)nb[2] * 64 + lane + 12) : 0.0;
+    if (ly == 3) yp = nb[3] >= 0 ? load((int64_t)nb[3] * 64 + lane - 12) : 0.0;
+    if (lz == 0) zm = nb[4] >= 0 ? load((int64_t)nb[4] * 64 + lane + 48) : 0.0;
+    if (lz == 3) zp = nb[5] >= 0 ? load((int64_t)nb[5] * 64 + lane - 48) : 0.0;
+    return ((xm + xp) + (ym + yp)) + (zm + zp);
+}
+
+// The launches of the solve: wave w of the launch takes the blocks w, w + waves, ...; a workgroup leaves one partial.
+#define BD_EACH_BLOCK(s) for (int64_t s = (int64_t)blockIdx.x * BD_WAVES + (threadIdx.x >> 6); s < ns; s += (int64_t)gridDim.x * BD_WAVES)
+
+// |b'|^2 over the free nodes, b' = b - (the stencil over the fixed values and zeros)
+__global__ __launch_bounds__(BD_TPB) void k_bd_bnorm(int64_t ns, const int32_t* __restrict__ nbr, const uint8_t* __restrict__ cls,
+                                                     const double* __restrict__ x, const double* __restrict__ b, double* __restrict__ part) {
+    __shared__ double s_part[BD_WAVES];
+    const int lane = threadIdx.x & 63;
+    double acc = 0.0;
+    BD_EACH_BLOCK(s) {
+        const int64_t at = s * 64 + lane;
+        const int c = cls[at];
+        const double fx = c == BD_FIXED ? x[at] : 0.0;
+        const double S = bd_sum6(fx, nbr + 6 * s, lane, [&](int64_t q) { return cls[q] == BD_FIXED ? x[q] : 0.0; });
+        const double bp = c == BD_FREE ? b[at] - S : 0.0;
+        acc += bp * bp;
+    }
+    const double t = bd_wg_sum(acc, s_part, threadIdx.x);
+    if (threadIdx.x == 0) part[blockIdx.x] = t;
+}
+
+// the residual of 6 x - S = -b at the free nodes, x with the fixed values in place: (S - 6 x) - b, 0 at the other nodes.  Its squared norm
+// per workgroup; WRITE: r, the start of the solve.
+template <bool WRITE>
+__global__ __launch_bounds__(BD_TPB) void k_bd_residual(int64_t ns, const int32_t* __restrict__ nbr, const uint8_t* __restrict__ cls,
+                                                        const double* __restrict__ x, const double* __restrict__ b, double* __restrict__ r,
+                                                        double* __restrict__ part) {
+    __shared__ double s_part[BD_WAVES];
+    const int lane = threadIdx.x & 63;
+    double acc = 0.0;
+    BD_EACH_BLOCK(s) {
+        const int64_t at = s * 64 + lane;
+        const double xv = x[at];
+        const double S = bd_sum6(xv, nbr + 6 * s, lane, [&](int64_t q) { return x[q]; });
+        const double rv = cls[at] == BD_FREE ? (S - 6.0 * xv) - b[at] : 0.0;
+        if (WRITE) r[at] = rv;
+        acc += rv * rv;
+    }
+    const double t = bd_wg_sum(acc, s_part, threadIdx.x);
+    if (threadIdx.x == 0) part[blockIdx.x] = t;
+}
+
+// p = r + beta p_old (beta = rr / rr_before, 0 in the first iteration), A p = 6 p - S(p) at the free nodes, and the partials of p . A p.
+// r and p are 0 at the nodes that are not free, so the neighbour's new p is r + beta p_old there too.
+__global__ __launch_bounds__(BD_TPB) void k_bd_apply(int64_t ns, const int32_t* __restrict__ nbr, const uint8_t* __restrict__ cls, int first, int np,
+                                                     const double* __restrict__ rr, const double* __restrict__ rr_before,
+                                                     const double* __restrict__ r, const double* __restrict__ p_old, double* __restrict__ p,
+                                                     double* __restrict__ ap, double* __restrict__ part) {
+    __shared__ double s_a[BD_WAVES], s_b[BD_WAVES], s_part[BD_WAVES], s_o[2];
+    double beta = 0.0;
+    if (!first) {
+        const double n = bd_fold_all(rr, np, s_a, s_o), d = bd_fold_all(rr_before, np, s_b, s_o + 1);
+        beta = d > 0.0 ? n / d : 0.0;
+    }
+    const int lane = threadIdx.x & 63;
+    double acc = 0.0;
+    BD_EACH_BLOCK(s) {
+        const int64_t at = s * 64 + lane;
+        const double pv = r[at] + beta * p_old[at];
+        const double S = bd_sum6(pv, nbr + 6 * s, lane, [&](int64_t q) { return r[q] + beta * p_old[q]; });
+        const double av = cls[at] == BD_FREE ? 6.0 * pv - S : 0.0;
+        p[at] = pv;
+        ap[at] = av;
+        acc += pv * av;
+    }
+    const double t = bd_wg_sum(acc, s_part, threadIdx.x);
+    if (threadIdx.x == 0) part[blockIdx.x] = t;
+}
+
+// alpha = rr / (p . A p); x += alpha p, r -= alpha A p, and the partials of the new r . r
+__global__ __launch_bounds__(BD_TPB) void k_bd_update(int64_t ns, int np, const double* __restrict__ rr, const double* __restrict__ pap,
+                                                      const double* __restrict__ p, const double* __restrict__ ap, double* __restrict__ x,
+                                                      double* __restrict__ r, double* __restrict__ part) {
+    __shared__ double s_a[BD_WAVES], s_b[BD_WAVES], s_part[BD_WAVES], s_o[2];
+    const double n = bd_fold_all(rr, np, s_a, s_o), d = bd_fold_all(pap, np, s_b, s_o + 1);
+    const double alpha = d > 0.0 ? n / d : 0.0;
+    const int lane = threadIdx.x & 63;
+    double acc = 0.0;
+    BD_EACH_BLOCK(s) {
+        const int64_t at = s * 64 + lane;
+        x[at] = x[at] + alpha * p[at];
+        const double rv = r[at] - alpha * ap[at];
+        r[at] = rv;
+        acc += rv * rv;
+    }
+    const double t = bd_wg_sum(acc, s_part, threadIdx.x);
+    if (threadIdx.x == 0) part[blockIdx.x] = t;
+}
+
+__global__ __launch_bounds__(BD_TPB) void k_bd_zero_free(int64_t nodes, const uint8_t* __restrict__ cls, double* __restrict__ x) {
+    const int64_t at = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
+    if (at < nodes && cls[at] == BD_FREE) x[at] = 0.0;
+}
+
+// how many nodes are free: integers
+__global__ __launch_bounds__(BD_TPB) void k_bd_count_free(int64_t nodes, const uint8_t* __restrict__ cls, unsigned long long* __restrict__ out) {
+    const int64_t at = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
+    const unsigned long long bal = __ballot(at < nodes && cls[at] == BD_FREE);
+    if ((threadIdx.x & 63) == 0 && bal) atomicAdd(out, (unsigned long long)__popcll(bal));
+}
+__global__ __launch_bounds__(BD_TPB) void k_bd_count_set(int64_t n, const uint8_t* __restrict__ flag, unsigned long long* __restrict__ out) {
+    const int64_t at = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
+    const unsigned long long bal = __ballot(at < n && flag[at]);
+    if ((threadIdx.x & 63) == 0 && bal) atomicAdd(out, (unsigned long long)__popcll(bal));
+}
+
+// ------------------------------------------------------------------ rule 29 ----
+// The used rows in their order, by ordered compaction: the sum of rule 29 then runs over used[0 .. N), so a row that is not used moves
+// no used row to another thread and the iso value, an fp64 sum in a fixed order, does not depend on such rows.
+__global__ __launch_bounds__(BD_TPB) void k_bd_used_count(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm, int32_t* __restrict__ cnt) {
+    __shared__ int s_wsum[BD_WAVES];
+    const int64_t i = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
+    const WgRank k = wg_rank<BD_WAVES>(i < n && pn_used(pts + 3 * i, nrm + 3 * i), s_wsum);
+    if (threadIdx.x == 0) cnt[blockIdx.x] = k.total;
+}
+__global__ __launch_bounds__(BD_TPB) void k_bd_used_scatter(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm,
+                                                            const int32_t* __restrict__ base, int64_t* __restrict__ used) {
+    __shared__ int s_wsum[BD_WAVES];
+    const int64_t i = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
+    const bool f = i < n && pn_used(pts + 3 * i, nrm + 3 * i);
+    const int64_t pos = (int64_t)base[blockIdx.x] + wg_rank<BD_WAVES>(f, s_wsum).rank;
+    if (f) used[pos] = i;
+}
+
+__global__ __launch_bounds__(BD_TPB) void k_bd_iso(int64_t m, const int64_t* __restrict__ used, const double* __restrict__ pts, PnGrid g, BdView v,
+                                                   const double* __restrict__ chi, double* __restrict__ part) {
+    __shared__ double s_part[BD_WAVES];
+    double acc = 0.0;
+    for (int64_t k = (int64_t)blockIdx.x * BD_TPB + threadIdx.x; k < m; k += (int64_t)gridDim.x * BD_TPB) {
+        const int64_t i = used[k];
+        int i0[3];
+        double w[8], val = 0.0;
+        pn_corners_weights(pts + 3 * i, g, i0, w);
+        for (int c = 0; c < 8; ++c) {
+            const int64_t at = bd_slot(v, i0[0] + (c & 1), i0[1] + (c >> 1 & 1), i0[2] + (c >> 2 & 1));
+            val = val + w[c] * (at < 0 ? NAN : chi[at]);
+        }
+        acc += val;
+    }
+    const double t = bd_wg_sum(acc, s_part, threadIdx.x);
+    if (threadIdx.x == 0) part[blockIdx.x] = t;
+}
+
+// ------------------------------------------------------------------ rules 30-31 ----
+// the scan between a count and a scatter kernel, in two levels (k_pn_scan_* of poisson.hip)
+__global__ __launch_bounds__(BD_TPB) void k_bd_scan_rows(const int32_t* __restrict__ cnt, int nb, int32_t* __restrict__ local, int32_t* __restrict__ tot) {
+    const int c0 = blockIdx.x * BD_SCAN_CH, len = nb - c0 < BD_SCAN_CH ? nb - c0 : BD_SCAN_CH;
+    int32_t* row = local + (int64_t)blockIdx.x * (BD_SCAN_CH + 1);
+    wg_scan_counts<BD_WAVES>(cnt + c0, len, row);
+    if (threadIdx.x == 0) tot[blockIdx.x] = row[len];                        // written by this thread
+}
+__global__ __launch_bounds__(BD_TPB) void k_bd_scan_totals(const int32_t* __restrict__ tot, int rows, int32_t* __restrict__ rbase) {
+    wg_scan_counts<BD_WAVES>(tot, rows, rbase);
+}
+__global__ __launch_bounds__(BD_TPB) void k_bd_scan_add(const int32_t* __restrict__ local, const int32_t* __restrict__ rbase, int nb, int rows,
+                                                        int32_t* __restrict__ base) {
+    const int64_t i = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
+    if (i < nb) base[i] = local[(i / BD_SCAN_CH) * (BD_SCAN_CH + 1) + i % BD_SCAN_CH] + rbase[i / BD_SCAN_CH];
+    if (i == nb) base[nb] = rbase[rows];
+}
+
+struct BdSurf {                          // level D for the surface kernels
+    BdView v;
+    PnGrid g;
+    const int32_t *coord, *rows;          // per stored block; per place of bd_segment
+    const double* chi;
+    double iso;
+    int64_t nodes;                        // 64 * stored blocks: the places q = 4 * place of the row + lx, in (iz, iy, ix) order
+};
+// place q of rule 30's order -> the node and where its value lies
+__device__ inline int64_t bd_place_node(const BdSurf& q, int64_t place, int* ix, int* iy, int* iz) {
+    const int32_t ri = q.rows[place >> 2];
+    const int s = ri >> 4, lx = (int)(place & 3), ly = ri & 3, lz = ri >> 2 & 3;
+    int bx, by, bz;
+    bd_unpack(q.coord[s], &bx, &by, &bz);
+    *ix = 4 * bx + lx; *iy = 4 * by + ly; *iz = 4 * bz + lz;
+    return (int64_t)s * 64 + (lz << 4 | ly << 2 | lx);
+}
+// node -> its place in rule 30's order (the node's block is stored)
+__device__ inline int64_t bd_node_place(const BdView& v, int ix, int iy, int iz) {
+    const int by = iy >> 2, bz = iz >> 2;
+    const int s = v.num[bd_tab(v, ix >> 2, by, bz)];
+    const BdRowSlab q = bd_row_slab(v.first, v.T, by, bz);
+    return bd_segment(s, iy & 3, iz & 3, q.rfirst, q.rcnt, q.sfirst, q.scnt) * 4 + (ix & 3);
+}
+
+// the inside bits of the eight corners of the cube at place q; 0 (no face) for a cube that is not active
+__global__ __launch_bounds__(BD_TPB) void k_bd_cubemask(BdSurf q, uint8_t* __restrict__ mask) {
+    const int64_t place = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
+    if (place >= q.nodes) return;
+    int ix, iy, iz, m = 0;
+    bd_place_node(q, place, &ix, &iy, &iz);
+    if (ix < q.v.G && iy < q.v.G && iz < q.v.G && BdActive{q.v}(ix, iy, iz))
+        for (int c = 0; c < 8; ++c) {
+            const int64_t at = bd_slot(q.v, ix + (c & 1), iy + (c >> 1 & 1), iz + (c >> 2 & 1));
+            m |= (at >= 0 && q.chi[at] < q.iso ? 1 : 0) << c;
+        }
+    mask[place] = (uint8_t)m;
+}
+
+// edge item r = place * 7 + type: a crossed edge that exists?  *open: rule 31
+__device__ inline bool bd_edge_crossed(const BdSurf& q, int64_t r, int64_t items, bool* open) {
+    *open = false;
+    if (r >= items) return false;
+    const int type = (int)(r % 7);
+    int ix, iy, iz;
+    const int64_t at = bd_place_node(q, r / 7, &ix, &iy, &iz);
+    if (ix > q.v.G || iy > q.v.G || iz > q.v.G) return false;
+    bool exists;
+    bd_edge_state(q.v.G, ix, iy, iz, type, BdActive{q.v}, &exists, open);
+    if (!exists) { *open = false; return false; }
+    const int m = pn_type_mask(type);
+    const int64_t hi = bd_slot(q.v, ix + (m & 1), iy + (m >> 1 & 1), iz + (m >> 2 & 1));      // a corner of an active cube: stored
+    const bool f = hi >= 0 && (q.chi[at] < q.iso) != (q.chi[hi] < q.iso);
+    *open = *open && f;
+    return f;
+}
+
+__global__ __launch_bounds__(BD_TPB) void k_bd_edge_count(BdSurf q, int64_t items, unsigned long long* __restrict__ words, int32_t* __restrict__ cnt,
+                                                          unsigned long long* __restrict__ n_open) {
+    __shared__ int s_wsum[BD_WAVES];
+    const int64_t r = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
+    bool open;
+    const bool f = bd_edge_crossed(q, r, items, &open);
+    const unsigned long long bal = __ballot(f), obal = __ballot(open);
+    if ((threadIdx.x & 63) == 0) {
+        words[r >> 6] = bal;
+        if (obal) atomicAdd(n_open, (unsigned long long)__popcll(obal));     // integers: any order
+    }
+    const WgRank k = wg_rank<BD_WAVES>(f, s_wsum);
+    if (threadIdx.x == 0) cnt[blockIdx.x] = k.total;
+}
+
+__device__ inline int32_t bd_vertex_index(const unsigned long long* __restrict__ words, const int32_t* __restrict__ base, int64_t r) {
+    const int64_t blk = r >> 8, w = r >> 6;
+    int32_t acc = base[blk];
+    for (int64_t k = blk * BD_WAVES; k < w; ++k) acc += __popcll(words[k]);
+    return acc + __popcll(words[w] & ((1ull << (r & 63)) - 1ull));
+}
+
+__global__ __launch_bounds__(BD_TPB) void k_bd_vertex_scatter(BdSurf q, int64_t items, const unsigned long long* __restrict__ words,
+                                                              const int32_t* __restrict__ base, double* __restrict__ vertices) {
+    __shared__ int s_wsum[BD_WAVES];
+    const int64_t r = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
+    const bool f = (words[r >> 6] >> (r & 63)) & 1ull;                       // the bitmap covers whole workgroups
+    const int64_t pos = (int64_t)base[blockIdx.x] + wg_rank<BD_WAVES>(f, s_wsum).rank;
+    if (!f) return;
+    const int m = pn_type_mask((int)(r % 7));
+    int ix, iy, iz;
+    const int64_t at = bd_place_node(q, r / 7, &ix, &iy, &iz);
+    const int jx = ix + (m & 1), jy = iy + (m >> 1 & 1), jz = iz + (m >> 2 & 1);
+    const double vl = q.chi[at], vh = q.chi[bd_slot(q.v, jx, jy, jz)];
+    const double pl[3] = {q.g.o[0] + q.g.h * (double)ix, q.g.o[1] + q.g.h * (double)iy, q.g.o[2] + q.g.h * (double)iz};
+    const double ph[3] = {q.g.o[0] + q.g.h * (double)jx, q.g.o[1] + q.g.h * (double)jy, q.g.o[2] + q.g.h * (double)jz};
+    double out[3];
+    if (vl < q.iso) pn_vertex(vl, vh, pl, ph, q.iso, out); else pn_vertex(vh, vl, ph, pl, q.iso, out);
+    for (int a = 0; a < 3; ++a) vertices[3 * pos + a] = out[a];
+}
+
+// face item r = (place * 6 + tetrahedron) * 2 + slot: pn_face_item of poisson.hip
+__device__ inline int bd_face_item(const uint8_t* __restrict__ mask, int64_t r, int64_t items) {
+    if (r >= items) return -1;
+    const int cm = mask[r / 12];
+    if (cm == 0 || cm == 255) return -1;
+    const int k = (int)(r % 12) >> 1, slot = (int)(r & 1);
+    int in = 0;
+    for (int i = 0; i < 4; ++i) in |= (cm >> pn_tet_corner(k, i) & 1) << i;
+    const int ni = __popc(in);
+    return (slot == 0 ? ni >= 1 && ni <= 3 : ni == 2) ? in : -1;
+}
+
+__global__ __launch_bounds__(BD_TPB) void k_bd_face_count(const uint8_t* __restrict__ mask, int64_t items, int32_t* __restrict__ cnt) {
+    __shared__ int s_wsum[BD_WAVES];
+    const int64_t r = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
+    const WgRank k = wg_rank<BD_WAVES>(bd_face_item(mask, r, items) >= 0, s_wsum);
+    if (threadIdx.x == 0) cnt[blockIdx.x] = k.total;
+}
+
+__global__ __launch_bounds__(BD_TPB) void k_bd_face_scatter(BdSurf q, const uint8_t* __restrict__ mask, int64_t items,
+                                                            const unsigned long long* __restrict__ words, const int32_t* __restrict__ vbase,
+                                                            const double* __restrict__ vertices, const int32_t* __restrict__ fbase,
+                                                            int32_t* __restrict__ faces) {
+    __shared__ int s_wsum[BD_WAVES];
+    const int64_t r = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
+    const int in = bd_face_item(mask, r, items);
+    const int64_t pos = (int64_t)fbase[blockIdx.x] + wg_rank<BD_WAVES>(in >= 0, s_wsum).rank;
+    if (in < 0) return;
+    const int k = (int)(r % 12) >> 1, slot = (int)(r & 1);
+    int ix, iy, iz;
+    bd_place_node(q, r / 12, &ix, &iy, &iz);
+    int ci[4], co[4];
+    const int n = pn_tet_cycle(in, ci, co);
+    int32_t idx[4];
+    double pos3[4][3], d[3];
+    for (int e = 0; e < n; ++e) {
+        int nm, type;
+        pn_tet_edge(k, ci[e], co[e], &nm, &type);
+        idx[e] = bd_vertex_index(words, vbase, bd_node_place(q.v, ix + (nm & 1), iy + (nm >> 1 & 1), iz + (nm >> 2 & 1)) * 7 + type);
+        for (int a = 0; a < 3; ++a) pos3[e][a] = vertices[3 * (int64_t)idx[e] + a];
+    }
+    pn_tet_dir(k, in, d);
+    pn_polygon(n, idx, pos3, d);
+    faces[3 * pos] = idx[0];
+    faces[3 * pos + 1] = idx[slot ? 2 : 1];
+    faces[3 * pos + 2] = idx[slot ? 3 : 2];
+}
+
+// ------------------------------------------------------------------ host ----
+inline unsigned bd_grid(int64_t items) { return (unsigned)((items + BD_TPB - 1) / BD_TPB); }
+
+int check_band(const char* fn, const mvs_poisson_band_params* bp, const void* binfo) {
+    if (!bp || !binfo) return bad(fn, "bparams or binfo is NULL");
+    if (bp->base_depth < 3 || bp->base_depth > MVS_POISSON_MAX_DEPTH) return bad(fn, "need base_depth in [3, MVS_POISSON_MAX_DEPTH]");
+    if (bp->band < 1 || bp->band > 64) return bad(fn, "need band in [1, 64]");
+    if (bp->reserved[0] != 0 || bp->reserved[1] != 0) return bad(fn, "bparams.reserved is not 0");
+    return MVS_OK;
+}
+
+// one level of the band on the device
+struct BdLevel {
+    BdExtent e{};
+    PnGrid g{};
+    int64_t ns = 0, nodes = 0, held = 0;  // stored blocks, 64 * ns, bytes taken from the pool
+    Scratch act, num, first, coord, nbr, cls, sums, b, x, ap;
+    BdView view() const { return BdView{e.G, e.T, e.Gb, act.as<uint8_t>(), num.as<int32_t>(), first.as<int32_t>()}; }
+};
+
+// what the test hook wants of one level, dense and in node order
+struct BdDump {
+    int level;
+    uint8_t *active, *cls;
+    double *b, *chi;
+    int64_t node_capacity;
+};
+
+struct BdScan {                          // counts, their scan and its two levels, for nb workgroups (PnRun::Scan of poisson.hip)
+    Scratch cnt, base, local, tot, rbase;
+    int64_t bytes = 0;
+    int alloc(size_t nb, hipStream_t s) {
+        const size_t rows = (nb + BD_SCAN_CH - 1) / BD_SCAN_CH;
+        int rc;
+        bytes = (int64_t)(4 * nb + 4 * (nb + 1) + 4 * rows * (BD_SCAN_CH + 1) + 4 * rows + 4 * (rows + 1));
+        if ((rc = cnt.alloc(4 * nb, s)) || (rc = base.alloc(4 * (nb + 1), s)) || (rc = local.alloc(4 * rows * (BD_SCAN_CH + 1), s)) ||
+            (rc = tot.alloc(4 * rows, s))) return rc;
+        return rbase.alloc(4 * (rows + 1), s);
+    }
+    void run(int nb, hipStream_t s) {
+        const int rows = (nb + BD_SCAN_CH - 1) / BD_SCAN_CH;
+        k_bd_scan_rows<<<dim3((unsigned)rows), dim3(BD_TPB), 0, s>>>(cnt.as<int32_t>(), nb, local.as<int32_t>(), tot.as<int32_t>());
+        k_bd_scan_totals<<<dim3(1), dim3(BD_TPB), 0, s>>>(tot.as<int32_t>(), rows, rbase.as<int32_t>());
+        k_bd_scan_add<<<dim3((unsigned)(nb / BD_TPB + 1)), dim3(BD_TPB), 0, s>>>(local.as<int32_t>(), rbase.as<int32_t>(), nb, rows, base.as<int32_t>());
+    }
+};
+
+// One call past its checks, the points on the device.
+struct BdRun {
+    const char* fn;
+    const mvs_poisson_params& p;
+    const mvs_poisson_band_params& bp;
+    mvs_poisson_info& info;
+    mvs_poisson_band_info& binfo;
+    int64_t n;
+    const double *pts, *nrm;
+    hipStream_t s;
+    double origin[3] = {0.0, 0.0, 0.0}, side = 0.0, iso = 0.0;
+    int D = 0, B = 0;
+    BdBytes bytes;
+    Scratch red, cnt8;                    // the partials of the reductions and their sum; one integer counter
+    std::unique_ptr<BdLevel> top;         // level D after levels()
+    // the surface
+    Scratch rows, mask, words;
+    BdScan ve, fa;
+    int64_t edge_items = 0, face_items = 0;
+
+    BdRun(const char* f, const mvs_poisson_params& pp, const mvs_poisson_band_params& b, mvs_poisson_info& i, mvs_poisson_band_info& bi, int64_t nn,
+          const double* pd, const double* nd, hipStream_t st)
+        : fn(f), p(pp), bp(b), info(i), binfo(bi), n(nn), pts(pd), nrm(nd), s(st) {
+        std::memset(&info, 0, sizeof info);
+        std::memset(&binfo, 0, sizeof binfo);
+    }
+
+    int take(Scratch& sc, int64_t b, int64_t* held = nullptr) {
+        const int rc = sc.alloc((size_t)b, s);
+        if (rc) return rc;
+        bytes.take(b);
+        if (held) *held += b;
+        return MVS_OK;
+    }
+    int fetch(void* dst, const void* src, size_t b) {
+        HIPCHK(hipMemcpyAsync(dst, src, b, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return MVS_OK;
+    }
+    PnGrid grid_of(int l) const {
+        PnGrid g{};
+        for (int a = 0; a < 3; ++a) g.o[a] = origin[a];
+        g.G = 1 << l;
+        g.h = side / (double)g.G;
+        return g;
+    }
+    // the number behind the flags of a byte array, or the free nodes of a class array
+    int count(const uint8_t* flag, int64_t m, bool free_nodes, int64_t* out) {
+        HIPCHK(hipMemsetAsync(cnt8.p, 0, 8, s));
+        if (free_nodes) k_bd_count_free<<<dim3(bd_grid(m)), dim3(BD_TPB), 0, s>>>(m, flag, cnt8.as<unsigned long long>());
+        else k_bd_count_set<<<dim3(bd_grid(m)), dim3(BD_TPB), 0, s>>>(m, flag, cnt8.as<unsigned long long>());
+        HIPCHK(hipGetLastError());
+        unsigned long long v = 0;
+        const int rc = fetch(&v, cnt8.p, 8);
+        *out = (int64_t)v;
+        return rc;
+    }
+
+    // rules 1-2 and 24: the cube, N, D and B
+    int depth() {
+        int rc;
+        mvs_poisson_info i0;
+        const PnCall c{fn, PN_PLAIN, n, pts, nrm, &p, &i0, nullptr, nullptr, nullptr, nullptr};
+        if ((rc = poisson_cube(c, pts, nrm, s, origin, &side))) return rc;
+        info.n_used = i0.n_used;
+        for (int a = 0; a < 3; ++a) info.origin[a] = origin[a];
+        if ((rc = take(red, 8 * (1 + 4 * (int64_t)BD_NPART))) || (rc = take(cnt8, 8))) return rc;
+        const int dmax = p.depth_max < BD_MAX_D ? p.depth_max : BD_MAX_D;
+        D = p.depth_min;
+        for (int d = p.depth_min + 1; d <= dmax; ++d) {                       // depth_min is the answer when nothing finer qualifies
+            const PnGrid g = grid_of(d);
+            const int64_t words = ((int64_t)1 << (3 * d)) / 32;
+            Scratch bits;
+            if ((rc = take(bits, 4 * words))) return rc;
+            HIPCHK(hipMemsetAsync(bits.p, 0, (size_t)(4 * words), s));
+            HIPCHK(hipMemsetAsync(cnt8.p, 0, 8, s));
+            k_bd_occupy<<<dim3(bd_grid(n)), dim3(BD_TPB), 0, s>>>(n, pts, nrm, g, bits.as<unsigned>());
+            k_bd_popcount<<<dim3(bd_grid(words)), dim3(BD_TPB), 0, s>>>(words, bits.as<unsigned>(), cnt8.as<unsigned long long>());
+            HIPCHK(hipGetLastError());
+            unsigned long long occ = 0;
+            if ((rc = fetch(&occ, cnt8.p, 8))) return rc;                     // synchronises: bits may go
+            bytes.give(4 * words);
+            if ((double)info.n_used >= p.samples_per_node * (double)occ) D = d;
+        }
+        B = D < bp.base_depth ? D : bp.base_depth;
+        binfo.base_depth = B;
+        return MVS_OK;
+    }
+
+    // rule 26 and the numbering: the tables and the per-block arrays of level l
+    int blocks(BdLevel& L, int l) {
+        int rc;
+        L.e = bd_extent(l);
+        L.g = grid_of(l);
+        const BdExtent& e = L.e;
+        const unsigned tgrid = bd_grid(e.table), rgrid = (unsigned)((e.rows + BD_WAVES - 1) / BD_WAVES);
+        Scratch ta, tb, rcnt;
+        if ((rc = take(ta, e.table)) || (rc = take(tb, e.table)) || (rc = take(rcnt, 4 * e.rows)) || (rc = take(L.act, e.table, &L.held)) ||
+            (rc = take(L.num, 4 * e.table, &L.held)) || (rc = take(L.first, 4 * (e.rows + 1), &L.held))) return rc;
+        HIPCHK(hipMemsetAsync(ta.p, 0, (size_t)e.table, s));
+        k_bd_mark<<<dim3(bd_grid(n)), dim3(BD_TPB), 0, s>>>(n, pts, nrm, L.g, e.T, ta.as<uint8_t>());
+        k_bd_dilate<<<dim3(tgrid), dim3(BD_TPB), 0, s>>>(e.T, e.Gb, ta.as<uint8_t>(), tb.as<uint8_t>(), 0, bp.band);
+        k_bd_dilate<<<dim3(tgrid), dim3(BD_TPB), 0, s>>>(e.T, e.Gb, tb.as<uint8_t>(), ta.as<uint8_t>(), 1, bp.band);
+        k_bd_dilate<<<dim3(tgrid), dim3(BD_TPB), 0, s>>>(e.T, e.Gb, ta.as<uint8_t>(), L.act.as<uint8_t>(), 2, bp.band);
+        k_bd_stored<<<dim3(tgrid), dim3(BD_TPB), 0, s>>>(e.T, L.act.as<uint8_t>(), tb.as<uint8_t>());
+        k_bd_row_count<<<dim3(rgrid), dim3(BD_TPB), 0, s>>>(e.T, tb.as<uint8_t>(), rcnt.as<int32_t>());
+        HIPCHK(hipGetLastError());
+        std::vector<int32_t> hc((size_t)e.rows), hf((size_t)e.rows + 1);
+        if ((rc = fetch(hc.data(), rcnt.p, 4 * (size_t)e.rows))) return rc;
+        L.ns = bd_row_firsts(e, hc.data(), hf.data());
+        if (L.ns < 0) { mvs_set_error("%s: the row counts of level %d are not counts", fn, l); return MVS_E_HIP; }
+        if ((rc = count(L.act.as<uint8_t>(), e.table, false, &binfo.n_active_blocks[l]))) return rc;
+        if (!bd_fits_int32(L.ns)) {
+            mvs_set_error("%s: level %d stores %lld blocks of 64 nodes: more than an int32 index reaches", fn, l, (long long)L.ns);
+            return MVS_E_INVALID_ARG;
+        }
+        L.nodes = L.ns * 64;
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(hipMemGetInfo(&free_b, &total_b));
+        const int64_t need = bd_level_bytes(e, L.ns, l == D);
+        if (need > (int64_t)total_b) {
+            mvs_set_error("%s: level %d stores %lld blocks and needs %lld bytes: more than the device has", fn, l, (long long)L.ns, (long long)need);
+            return MVS_E_OOM;
+        }
+        if ((rc = take(L.coord, 4 * L.ns, &L.held)) || (rc = take(L.nbr, 24 * L.ns, &L.held))) return rc;
+        HIPCHK(hipMemcpy(L.first.p, hf.data(), 4 * hf.size(), hipMemcpyHostToDevice));       // the stream is idle: fetch synchronised it
+        k_bd_number<<<dim3(rgrid), dim3(BD_TPB), 0, s>>>(e.T, tb.as<uint8_t>(), L.first.as<int32_t>(), L.num.as<int32_t>(), L.coord.as<int32_t>());
+        if (L.ns > 0) k_bd_neighbours<<<dim3(bd_grid(6 * L.ns)), dim3(BD_TPB), 0, s>>>(L.ns, L.coord.as<int32_t>(), L.view(), L.nbr.as<int32_t>());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(s));                                      // ta, tb and rcnt go
+        bytes.give(2 * e.table + 4 * e.rows);
+        return MVS_OK;
+    }
+
+    // rules 26-28 on level l; coarse: the level below
+    template <class Coarse>
+    int fill(BdLevel& L, int l, Coarse coarse) {
+        int rc;
+        if ((rc = take(L.cls, L.nodes, &L.held)) || (rc = take(L.sums, 24 * L.nodes, &L.held)) || (rc = take(L.b, 8 * L.nodes, &L.held)) ||
+            (rc = take(L.x, 8 * L.nodes, &L.held)) || (rc = take(L.ap, 8 * L.nodes, &L.held))) return rc;
+        if (L.ns == 0) return MVS_OK;
+        const BdView v = L.view();
+        const unsigned ngrid = bd_grid(L.nodes);
+        k_bd_class_start<Coarse><<<dim3(ngrid), dim3(BD_TPB), 0, s>>>(L.ns, L.coord.as<int32_t>(), v, coarse, L.cls.as<uint8_t>(), L.x.as<double>());
+        HIPCHK(hipMemsetAsync(L.sums.p, 0, (size_t)(24 * L.nodes), s));
+        k_bd_splat<<<dim3(bd_grid(n)), dim3(BD_TPB), 0, s>>>(n, pts, nrm, L.g, v, L.nodes, L.sums.as<unsigned long long>());
+        k_bd_rhs<<<dim3(ngrid), dim3(BD_TPB), 0, s>>>(L.ns, L.nbr.as<int32_t>(), L.cls.as<uint8_t>(), L.nodes, L.sums.as<long long>(), L.g.h, L.b.as<double>());
+        HIPCHK(hipGetLastError());
+        return count(L.cls.as<uint8_t>(), L.nodes, true, &binfo.n_free[l]);
+    }
+
+    int folded(int np, double* part, double* out) {
+        k_bd_fold<<<dim3(1), dim3(BD_TPB), 0, s>>>(part, np, red.as<double>());
+        HIPCHK(hipGetLastError());
+        return fetch(out, red.p, 8);
+    }
+
+    // rule 28: conjugate gradients from the start values until the true residual meets solve_tol
+    int solve(BdLevel& L, int l) {
+        int rc;
+        if (L.ns == 0) return MVS_OK;
+        const int np = (int)std::min<int64_t>((L.ns + BD_WAVES - 1) / BD_WAVES, BD_NPART);
+        const dim3 gr((unsigned)np), tb(BD_TPB);
+        double* part[4];                                                     // r . r twice (this iteration's and the one before), p . A p, the true residual
+        for (int q = 0; q < 4; ++q) part[q] = red.as<double>() + 1 + q * BD_NPART;
+        const int32_t* nbr = L.nbr.as<int32_t>();
+        const uint8_t* cls = L.cls.as<uint8_t>();
+        double *x = L.x.as<double>(), *b = L.b.as<double>(), *ap = L.ap.as<double>();
+        double *r = L.sums.as<double>(), *pa = r + L.nodes, *pb = r + 2 * L.nodes;      // the sums are spent
+        double b2 = 0.0, r2 = 0.0;
+        k_bd_bnorm<<<gr, tb, 0, s>>>(L.ns, nbr, cls, x, b, part[3]);
+        if ((rc = folded(np, part[3], &b2))) return rc;
+        binfo.bnorm[l] = std::sqrt(b2);
+        if (!(b2 > 0.0)) {                                                    // b' = 0 (or not finite): chi_f = 0
+            k_bd_zero_free<<<dim3(bd_grid(L.nodes)), tb, 0, s>>>(L.nodes, cls, x);
+            HIPCHK(hipGetLastError());
+            return MVS_OK;
+        }
+        HIPCHK(hipMemsetAsync(L.sums.p, 0, (size_t)(24 * L.nodes), s));
+        k_bd_residual<true><<<gr, tb, 0, s>>>(L.ns, nbr, cls, x, b, r, part[0]);
+        if ((rc = folded(np, part[0], &r2))) return rc;
+        binfo.rel_residual[l] = std::sqrt(r2) / std::sqrt(b2);
+        if (std::sqrt(r2) <= p.solve_tol * std::sqrt(b2)) return MVS_OK;
+        int cur = 0, it = 0;
+        for (int c = 1; c <= p.max_cycles; ++c) {
+            for (int k = 0; k < 64; ++k, ++it) {
+                k_bd_apply<<<gr, tb, 0, s>>>(L.ns, nbr, cls, it == 0 ? 1 : 0, np, part[cur], part[cur ^ 1], r, pa, pb, ap, part[2]);
+                k_bd_update<<<gr, tb, 0, s>>>(L.ns, np, part[cur], part[2], pb, ap, x, r, part[cur ^ 1]);
+                cur ^= 1;
+                std::swap(pa, pb);
+            }
+            k_bd_residual<false><<<gr, tb, 0, s>>>(L.ns, nbr, cls, x, b, nullptr, part[3]);
+            if ((rc = folded(np, part[3], &r2))) return rc;
+            binfo.iterations[l] = it;
+            binfo.rel_residual[l] = std::sqrt(r2) / std::sqrt(b2);
+            if (std::sqrt(r2) <= p.solve_tol * std::sqrt(b2)) return MVS_OK;
+        }
+        binfo.failed_level = l;
+        mvs_set_error("%s: level %d: relative residual %.3e after %d iterations, above solve_tol %.3e", fn, l, binfo.rel_residual[l], it, p.solve_tol);
+        return MVS_E_SOLVER;
+    }
+
+    // level l of the hook, dense: active [Gb^3], cls, b, chi [n1^3] in node order; NaN where a node has no value, b 0 at fixed nodes
+    int dump(const BdLevel& L, const double* b_dev, const BdDump& d) {
+        const BdExtent& e = L.e;
+        const int64_t nn = (int64_t)e.n1 * e.n1 * e.n1;
+        std::vector<uint8_t> act((size_t)e.table), cls((size_t)L.nodes + 1);
+        std::vector<double> hb((size_t)L.nodes + 1), hx((size_t)L.nodes + 1);
+        std::vector<int32_t> coord((size_t)L.ns + 1);
+        HIPCHK(hipStreamSynchronize(s));
+        HIPCHK(hipMemcpy(act.data(), L.act.p, (size_t)e.table, hipMemcpyDeviceToHost));
+        if (L.ns > 0) {
+            HIPCHK(hipMemcpy(cls.data(), L.cls.p, (size_t)L.nodes, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(hb.data(), b_dev, 8 * (size_t)L.nodes, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(hx.data(), L.x.p, 8 * (size_t)L.nodes, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(coord.data(), L.coord.p, 4 * (size_t)L.ns, hipMemcpyDeviceToHost));
+        }
+        for (int bz = 0; bz < e.Gb; ++bz)
+            for (int by = 0; by < e.Gb; ++by)
+                for (int bx = 0; bx < e.Gb; ++bx) d.active[((int64_t)bz * e.Gb + by) * e.Gb + bx] = act[(size_t)bd_table_at(e, bx, by, bz)];
+        const double nan = std::numeric_limits<double>::quiet_NaN();
+        for (int64_t i = 0; i < nn; ++i) { d.cls[i] = BD_NONE; d.b[i] = nan; d.chi[i] = nan; }
+        for (int64_t sb = 0; sb < L.ns; ++sb) {
+            const int bx = coord[(size_t)sb] & 1023, by = coord[(size_t)sb] >> 10 & 1023, bz = coord[(size_t)sb] >> 20 & 1023;
+            for (int lane = 0; lane < 64; ++lane) {
+                const int ix = 4 * bx + (lane & 3), iy = 4 * by + (lane >> 2 & 3), iz = 4 * bz + (lane >> 4);
+                const size_t at = (size_t)(sb * 64 + lane);
+                if (ix > e.G || iy > e.G || iz > e.G || cls[at] == BD_NONE) continue;
+                const int64_t node = ((int64_t)iz * e.n1 + iy) * e.n1 + ix;
+                d.cls[node] = cls[at];
+                d.b[node] = cls[at] == BD_FREE ? hb[at] : 0.0;
+                d.chi[node] = hx[at];
+            }
+        }
+        return MVS_OK;
+    }
+
+    // rules 25-28: the base, then the levels B + 1 .. D; level D stays in `top`.  dump (may be NULL): the hook's level.
+    int levels(const BdDump* d) {
+        int rc;
+        mvs_poisson_params pb = p;
+        pb.depth_min = pb.depth_max = B;
+        pb.max_cycles = (int32_t)std::min<int64_t>((int64_t)p.max_cycles * 64, INT32_MAX);   // rule 25: one budget for every solve of the call
+        mvs_poisson_info ib;
+        const PnCall cb{fn, PN_PLAIN, n, pts, nrm, &pb, &ib, nullptr, nullptr, nullptr, nullptr};
+        std::unique_ptr<PnBaseField> base(new PnBaseField);
+        rc = base->solve(cb, pts, nrm, s);
+        info.cycles = ib.cycles;
+        info.rel_residual = ib.rel_residual;
+        if (rc == MVS_E_SOLVER) binfo.failed_level = B;
+        if (rc) return rc;
+        bytes.take(base->bytes);
+        std::unique_ptr<BdLevel> below;
+        for (int l = B + 1; l <= D; ++l) {
+            std::unique_ptr<BdLevel> L(new BdLevel);
+            if ((rc = blocks(*L, l))) return rc;
+            if (d && d->level == l && (int64_t)L->e.n1 * L->e.n1 * L->e.n1 > d->node_capacity)
+                return bad(fn, "node_capacity is below (2^level + 1)^3");
+            if (below) rc = fill(*L, l, BdBlockCoarse{below->view(), below->x.as<double>()});
+            else rc = fill(*L, l, BdDenseCoarse{base->chi, 1 << B});
+            if (rc) return rc;
+            HIPCHK(hipStreamSynchronize(s));                                  // the level below has been read: it goes back to the pool
+            if (below) { bytes.give(below->held); below.reset(); }
+            if (base) { bytes.give(base->bytes); base.reset(); }
+            const int src = solve(*L, l);
+            if (src && src != MVS_E_SOLVER) return src;
+            if (d && d->level == l && (rc = dump(*L, L->b.as<double>(), *d))) return rc;   // the solve leaves b as it is
+            if (src) return src;
+            below = std::move(L);
+        }
+        top = std::move(below);
+        return MVS_OK;
+    }
+
+    // rule 29
+    int iso_value() {
+        int rc;
+        const BdLevel& L = *top;
+        const int64_t m = info.n_used, nbu = (n + BD_TPB - 1) / BD_TPB;
+        BdScan us;
+        Scratch used;
+        if ((rc = us.alloc((size_t)nbu, s)) || (rc = take(used, 8 * m))) return rc;
+        bytes.take(us.bytes);
+        k_bd_used_count<<<dim3((unsigned)nbu), dim3(BD_TPB), 0, s>>>(n, pts, nrm, us.cnt.as<int32_t>());
+        us.run((int)nbu, s);
+        k_bd_used_scatter<<<dim3((unsigned)nbu), dim3(BD_TPB), 0, s>>>(n, pts, nrm, us.base.as<int32_t>(), used.as<int64_t>());
+        const int nb = (int)std::min<int64_t>(BD_RED_NB, (m + BD_TPB - 1) / BD_TPB);
+        double* part = red.as<double>() + 1;
+        k_bd_iso<<<dim3((unsigned)nb), dim3(BD_TPB), 0, s>>>(m, used.as<int64_t>(), pts, L.g, L.view(), L.x.as<double>(), part);
+        double sum = 0.0;
+        rc = folded(nb, part, &sum);                                          // synchronises: used and the scan may go
+        bytes.give(us.bytes + 8 * m);
+        if (rc) return rc;
+        info.iso = iso = sum / (double)info.n_used;
+        return MVS_OK;
+    }
+
+    BdSurf surf() const {
+        const BdLevel& L = *top;
+        return BdSurf{L.view(), L.g, L.coord.as<int32_t>(), rows.as<int32_t>(), L.x.as<double>(), iso, L.nodes};
+    }
+
+    // rules 30-31 up to the counts
+    int count_mesh() {
+        int rc;
+        BdLevel& L = *top;
+        if (L.ns == 0) return MVS_OK;
+        edge_items = 7 * L.nodes;
+        face_items = 12 * L.nodes;
+        const int64_t nbe = (edge_items + BD_TPB - 1) / BD_TPB, nbf = (face_items + BD_TPB - 1) / BD_TPB;
+        if ((rc = take(rows, 64 * L.ns)) || (rc = take(mask, L.nodes)) || (rc = take(words, 8 * BD_WAVES * nbe)) || (rc = ve.alloc((size_t)nbe, s)) ||
+            (rc = fa.alloc((size_t)nbf, s))) return rc;
+        bytes.take(ve.bytes + fa.bytes);
+        k_bd_rows<<<dim3(bd_grid(16 * L.ns)), dim3(BD_TPB), 0, s>>>(L.ns, L.coord.as<int32_t>(), L.view(), rows.as<int32_t>());
+        const BdSurf q = surf();
+        HIPCHK(hipMemsetAsync(cnt8.p, 0, 8, s));
+        k_bd_cubemask<<<dim3(bd_grid(L.nodes)), dim3(BD_TPB), 0, s>>>(q, mask.as<uint8_t>());
+        k_bd_edge_count<<<dim3((unsigned)nbe), dim3(BD_TPB), 0, s>>>(q, edge_items, words.as<unsigned long long>(), ve.cnt.as<int32_t>(), cnt8.as<unsigned long long>());
+        ve.run((int)nbe, s);
+        k_bd_face_count<<<dim3((unsigned)nbf), dim3(BD_TPB), 0, s>>>(mask.as<uint8_t>(), face_items, fa.cnt.as<int32_t>());
+        fa.run((int)nbf, s);
+        HIPCHK(hipGetLastError());
+        int32_t nv = 0, nf = 0;
+        unsigned long long nopen = 0;
+        HIPCHK(hipMemcpyAsync(&nv, ve.base.as<int32_t>() + nbe, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&nopen, cnt8.p, 8, hipMemcpyDeviceToHost, s));
+        if ((rc = fetch(&nf, fa.base.as<int32_t>() + nbf, 4))) return rc;
+        info.n_vertices = nv;
+        info.n_faces = nf;
+        binfo.n_open_edges = (int64_t)nopen;
+        return MVS_OK;
+    }
+
+    int scatter(double* vertices, int32_t* faces) {
+        if (info.n_vertices == 0) return MVS_OK;
+        const int64_t nbe = (edge_items + BD_TPB - 1) / BD_TPB, nbf = (face_items + BD_TPB - 1) / BD_TPB;
+        const BdSurf q = surf();
+        k_bd_vertex_scatter<<<dim3((unsigned)nbe), dim3(BD_TPB), 0, s>>>(q, edge_items, words.as<unsigned long long>(), ve.base.as<int32_t>(), vertices);
+        k_bd_face_scatter<<<dim3((unsigned)nbf), dim3(BD_TPB), 0, s>>>(q, mask.as<uint8_t>(), face_items, words.as<unsigned long long>(), ve.base.as<int32_t>(),
+                                                                      vertices, fa.base.as<int32_t>(), faces);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(s));
+        return MVS_OK;
+    }
+
+    void finish_info() {
+        info.depth = D;
+        info.h = side / (double)(1 << D);
+        binfo.scratch_bytes = bytes.peak;
+    }
+};
+
+// where the call writes, on the device: the caller's arrays, or — bv set — blocks sized once the counts are known (PnOut of poisson.hip)
+struct BdOut {
+    double* vertices;
+    int32_t* faces;
+    int64_t vcap, fcap;
+    Scratch *bv, *bf;
+};
+
+struct BdCall {
+    const char* fn;
+    int64_t n;
+    const double *points, *normals;
+    const mvs_poisson_params* p;
+    const mvs_poisson_band_params* bp;
+    mvs_poisson_info* info;
+    mvs_poisson_band_info* binfo;
+};
+
+int check_band_call(const BdCall& c, const void* out_a, int64_t cap_a, const void* out_b, int64_t cap_b) {
+    const PnCall pc{c.fn, PN_PLAIN, c.n, c.points, c.normals, c.p, c.info, nullptr, nullptr, nullptr, nullptr};
+    const int rc = poisson_check_plain(pc, BD_MAX_D, out_a, cap_a, out_b, cap_b);
+    return rc ? rc : check_band(c.fn, c.bp, c.binfo);
+}
+
+// the device form of the entry, after its checks
+int band_reconstruct(const BdCall& c, const double* pts, const double* nrm, BdOut o, hipStream_t s) {
+    int rc;
+    BdRun run(c.fn, *c.p, *c.bp, *c.info, *c.binfo, c.n, pts, nrm, s);
+    if ((rc = run.depth())) return rc;
+    if (run.D <= run.B) {                                                     // rule 24: the plain call at depth D, its bytes
+        mvs_poisson_params pd = *c.p;
+        pd.depth_min = pd.depth_max = run.D;
+        const PnCall pc{c.fn, PN_PLAIN, c.n, pts, nrm, &pd, c.info, nullptr, nullptr, nullptr, nullptr};
+        return poisson_plain_dev(pc, pts, nrm, o.vertices, o.vcap, o.faces, o.fcap, o.bv, o.bf, s);
+    }
+    rc = run.levels(nullptr);
+    run.finish_info();
+    if (rc || (rc = run.iso_value()) || (rc = run.count_mesh())) { run.finish_info(); return rc; }
+    run.finish_info();
+    const int64_t V = c.info->n_vertices, F = c.info->n_faces;
+    if (!bd_capacity_ok(V, F, o.vcap, o.fcap)) return bad(c.fn, "a capacity is below the count (info holds n_vertices and n_faces)");
+    if (o.bv) {
+        if ((rc = o.bv->alloc(24 * (size_t)V)) || (rc = o.bf->alloc(12 * (size_t)F))) return rc;
+        o.vertices = o.bv->as<double>();
+        o.faces = o.bf->as<int32_t>();
+    }
+    return run.scatter(o.vertices, o.faces);
+}
+
+}  // namespace
+
+// the device form for a caller inside the library that cannot know the counts in advance (mvs_processor_poisson_band)
+int poisson_band_blocks(const char* fn, int64_t n, const double* pts_dev, const double* nrm_dev, const mvs_poisson_params* p,
+                        const mvs_poisson_band_params* bp, mvs_poisson_info* info, mvs_poisson_band_info* binfo, Scratch* vertices, Scratch* faces) {
+    const BdCall c{fn, n, pts_dev, nrm_dev, p, bp, info, binfo};
+    const int rc = check_band_call(c, nullptr, 0, nullptr, 0);
+    return rc ? rc : band_reconstruct(c, pts_dev, nrm_dev, BdOut{nullptr, nullptr, INT64_MAX, INT64_MAX, vertices, faces}, nullptr);
+}
+
+extern "C" {
+
+void mvs_poisson_band_default_params(mvs_poisson_band_params* p) {
+    if (!p) return;
+    p->base_depth = 8; p->band = 2; p->reserved[0] = p->reserved[1] = 0;
+}
+
+int mvs_poisson_reconstruct_band_dev(int64_t n, const double* points_dev, const double* normals_dev, const mvs_poisson_params* p,
+                                     const mvs_poisson_band_params* bparams, mvs_poisson_info* info, mvs_poisson_band_info* binfo,
+                                     double* vertices_dev, int64_t vertex_capacity, int32_t* faces_dev, int64_t face_capacity, void* hip_stream) {
+    MVS_TRACE();
+    const BdCall c{__func__, n, points_dev, normals_dev, p, bparams, info, binfo};
+    int rc = check_band_call(c, vertices_dev, vertex_capacity, faces_dev, face_capacity);
+    if (rc || (rc = need_device())) return rc;
+    return band_reconstruct(c, points_dev, normals_dev, BdOut{vertices_dev, faces_dev, vertex_capacity, face_capacity, nullptr, nullptr}, (hipStream_t)hip_stream);
+}
+
+int mvs_poisson_reconstruct_band(int64_t n, const double* points, const double* normals, const mvs_poisson_params* p,
+                                 const mvs_poisson_band_params* bparams, mvs_poisson_info* info, mvs_poisson_band_info* binfo, double* vertices,
+                                 int64_t vertex_capacity, int32_t* faces, int64_t face_capacity) {
+    MVS_TRACE();
+    const BdCall c{__func__, n, points, normals, p, bparams, info, binfo};
+    Scratch dp, dn, dv, df;
+    int rc = check_band_call(c, vertices, vertex_capacity, faces, face_capacity);
+    if (rc || (rc = need_device()) || (rc = up(dp, points, 3 * (size_t)n)) || (rc = up(dn, normals, 3 * (size_t)n)) ||
+        (rc = band_reconstruct(c, dp.as<double>(), dn.as<double>(), BdOut{nullptr, nullptr, vertex_capacity, face_capacity, &dv, &df}, nullptr)))
+        return rc;
+    const size_t V = (size_t)info->n_vertices, F = (size_t)info->n_faces;
+    if ((rc = down(vertices, dv, 3 * V))) return rc;
+    return down(faces, df, 3 * F);
+}
+
+// The call up to rule 29, level `level` handed out dense (include/mvs_test.h).  MVS_E_SOLVER of that level still hands out what it reached.
+int mvs_test_poisson_band_level(int64_t n, const double* points, const double* normals, const mvs_poisson_params* p,
+                                const mvs_poisson_band_params* bparams, mvs_poisson_info* info, mvs_poisson_band_info* binfo, int32_t level,
+                                uint8_t* active, uint8_t* cls, double* b, double* chi, int64_t node_capacity) {
+    MVS_TRACE();
+    const BdCall c{__func__, n, points, normals, p, bparams, info, binfo};
+    Scratch dp, dn;
+    int rc = check_band_call(c, b, node_capacity, chi, node_capacity);
+    if (rc) return rc;
+    if (!active || !cls || !b || !chi) return bad(__func__, "active, cls, b or chi is NULL");
+    if ((rc = need_device()) || (rc = up(dp, points, 3 * (size_t)n)) || (rc = up(dn, normals, 3 * (size_t)n))) return rc;
+    BdRun run(__func__, *p, *bparams, *info, *binfo, n, dp.as<double>(), dn.as<double>(), nullptr);
+    if ((rc = run.depth())) return rc;
+    run.finish_info();
+    if (level <= run.B || level > run.D) return bad(__func__, "level is outside base_depth + 1 .. depth (info and binfo hold them)");
+    const BdDump d{level, active, cls, b, chi, node_capacity};
+    rc = run.levels(&d);
+    run.finish_info();
+    if (rc) return rc;
+    rc = run.iso_value();
+    run.finish_info();
+    return rc;
+}
+
+}  // extern "C"

@@ -1,0 +1,95 @@
+// poisson_band_plan.h — the sizes and index arithmetic the host does for the band levels of the Poisson stage (rules 24-31,
+// poisson_band_rules.h): the extents of a level's block table, the bytes a level takes, the test that its stored nodes fit an int32
+// index, the row and slab tables bd_segment reads, and the bookkeeping of the bytes a call holds.  Plain C++ without a HIP call:
+// poisson_band.hip uses it, and tests/poisson_band_plan.cpp runs it as a program of its own under the address and undefined-behaviour
+// sanitizers, on block sets of its own and at the extents of depth 10, before anything runs on a device.
+#ifndef MVS_POISSON_BAND_PLAN_H_
+#define MVS_POISSON_BAND_PLAN_H_
+#include <stddef.h>
+#include <stdint.h>
+
+#define BP_MAX_DEPTH 10                  /* MVS_POISSON_BAND_MAX_DEPTH */
+#define BP_BLOCK 4                       /* MVS_POISSON_BAND_BLOCK */
+#define BP_BLOCK_NODES 64                /* nodes a stored block holds: the lower corners of its 4^3 cells */
+#define BP_NODE_BYTES 49                 /* per stored node: the class byte, three 8-byte planes (the sums of the splat, then r and the two p), b, chi, A p */
+
+// The extents of level l (B + 1 <= l <= BP_MAX_DEPTH, so G >= 16): G cells, n1 = G + 1 nodes and Gb = G / 4 blocks per axis; the
+// block table has T = Gb + 1 entries per axis, the node plane ix = G belonging to block index Gb, which holds no cell.
+struct BdExtent {
+    int32_t l, G, n1, Gb, T;
+    int64_t table;                       // T^3 entries
+    int64_t rows;                        // T^2 rows (bz, by) of the table
+};
+inline BdExtent bd_extent(int l) {
+    BdExtent e;
+    e.l = l;
+    e.G = 1 << l;
+    e.n1 = e.G + 1;
+    e.Gb = e.G / BP_BLOCK;
+    e.T = e.Gb + 1;
+    e.rows = (int64_t)e.T * e.T;
+    e.table = e.rows * e.T;
+    return e;
+}
+inline int64_t bd_table_at(const BdExtent& e, int bx, int by, int bz) { return ((int64_t)bz * e.T + by) * e.T + bx; }
+
+// Do `stored` blocks fit?  Node 64 * s + lane and the row 16 * s + (lz, ly) are int32 on the device.
+inline bool bd_fits_int32(int64_t stored) { return stored >= 0 && stored * BP_BLOCK_NODES <= (int64_t)INT32_MAX; }
+
+// What the stored blocks of a level take (poisson_band.hip's BdLevel): the node arrays, the packed coordinates and the six face
+// neighbours of every block; and what the level's tables take whatever is stored: two bytes of work (points, dilation, stored) and
+// the active byte, the int32 number of every block, the row counts and the row firsts.
+inline int64_t bd_block_bytes(int64_t stored) { return stored * ((int64_t)BP_BLOCK_NODES * BP_NODE_BYTES + 4 + 24); }
+inline int64_t bd_table_bytes(const BdExtent& e) { return e.table * (3 + 4) + (2 * e.rows + 1) * 4; }
+// rules 10-12 over the stored nodes of level D (7 edge items and 12 face items per node, 256 items per workgroup): the sixteen row
+// records of every block, the cube masks, the edge bitmap, and the counts, their scan's rows and the bases of the two compactions
+inline int64_t bd_surface_bytes(int64_t stored) {
+    const int64_t nodes = stored * BP_BLOCK_NODES, nbe = (7 * nodes + 255) / 256, nbf = (12 * nodes + 255) / 256;
+    return 64 * stored + nodes + 32 * nbe + 13 * (nbe + nbf + 2);
+}
+// Can level l with `stored` blocks be held at all by a device of `device_bytes`?  (What the pool has free is not known to the caller;
+// a level that exceeds the device is refused before its arrays are asked for, with the level named.)
+inline int64_t bd_level_bytes(const BdExtent& e, int64_t stored, bool finest) {
+    return bd_table_bytes(e) + bd_block_bytes(stored) + (finest ? bd_surface_bytes(stored) : 0);
+}
+
+// The row firsts of a level from its row counts: first[r] = the stored blocks in the rows before r (rows in (bz, by) order), first[rows]
+// = all stored blocks.  -> that total, or -1 when a count is negative or exceeds T (the table cannot be right).
+inline int64_t bd_row_firsts(const BdExtent& e, const int32_t* count, int32_t* first) {
+    int64_t acc = 0;
+    for (int64_t r = 0; r < e.rows; ++r) {
+        if (count[r] < 0 || count[r] > e.T) return -1;
+        first[r] = (int32_t)(acc > INT32_MAX ? INT32_MAX : acc);
+        acc += count[r];
+    }
+    first[e.rows] = (int32_t)(acc > INT32_MAX ? INT32_MAX : acc);
+    return acc;
+}
+// what bd_segment takes for a block of row (bz, by), read from the row firsts (host and device alike)
+struct BdRowSlab { int32_t rfirst, rcnt, sfirst, scnt; };
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+inline BdRowSlab bd_row_slab(const int32_t* first, int T, int by, int bz) {
+    const int64_t r = (int64_t)bz * T + by, s0 = (int64_t)bz * T, s1 = s0 + T;
+    BdRowSlab q;
+    q.rfirst = first[r];
+    q.rcnt = first[r + 1] - first[r];
+    q.sfirst = first[s0];
+    q.scnt = first[s1] - first[s0];
+    return q;
+}
+
+// The bytes a call holds from the pool: take() and give() as blocks come and go, peak is mvs_poisson_band_info.scratch_bytes.
+struct BdBytes {
+    int64_t now = 0, peak = 0;
+    void take(int64_t b) { now += b; if (now > peak) peak = now; }
+    void give(int64_t b) { now -= b; }
+};
+
+// The capacity test of the outputs, as the plain call makes it: the counts are known, nothing has been written.
+inline bool bd_capacity_ok(int64_t n_vertices, int64_t n_faces, int64_t vertex_capacity, int64_t face_capacity) {
+    return n_vertices <= vertex_capacity && n_faces <= face_capacity;
+}
+
+#endif

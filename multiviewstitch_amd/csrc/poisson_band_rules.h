@@ -1,50 +1,12 @@
-// poisson_band_rules.h — band-refined levels over the dense grid of the Poisson stage: the definition (rules 24-31, continuing rules
-// 1-23 of include/mvs.h) and its per-point, per-block, per-node and per-edge decisions as one __host__ __device__ body.
-//
-// The surface occupies O(G^2) of the G^3 cells of a level; the dense grid of mvs_poisson_reconstruct pays for the empty volume and
-// stops at MVS_POISSON_MAX_DEPTH = 9, while config.txt asks for PsnDptMax 10.  The band scheme solves a dense base level and refines it
-// level by level on the blocks of cells near the points only, each level taking its boundary values from the level below: still fp64,
-// integer splats that do not depend on their order, a stop criterion on the true residual.  It is unscreened and unweighted.  Like rules
-// 1-23 these are this library's definition and are NOT VERIFIED against GeoRec.  base_depth (3 .. 9, by default 8) and band (1 .. 64
-// blocks, by default 2) are its two parameters; MVS_POISSON_BAND_MAX_DEPTH is 10, MVS_POISSON_BAND_BLOCK is 4.
-//  24. depth       : D = rule 3 with Dmax = min(depth_max, MVS_POISSON_BAND_MAX_DEPTH).  At depth 10 the node index and the cube
-//                    index still fit in int32; a (node index, type) key needs int64.  B = min(D, base_depth).  With D <= base_depth
-//                    the result is that of mvs_poisson_reconstruct at depth_min = depth_max = D.
-//  25. base        : rules 4-8 at depth B give chi_B on the dense grid of that depth.
-//  26. blocks      : for every level l = B + 1 .. D: G_l = 2^l, h_l = side / G_l, and the cells form blocks of MVS_POISSON_BAND_BLOCK
-//                    cells per axis, G_l / 4 blocks per axis.  The block of a used point is the block of its level-l cell (rule 3's
-//                    formula at d = l).  A block is active when some used point's block lies at Chebyshev distance <= band blocks
-//                    from it.  A cell is active when its block is; cells outside the grid are not active.  A node is FREE when all
-//                    eight cells that touch it are active, FIXED when at least one but not all of them are, and has no value
-//                    otherwise.  The active set of level l - 1 covers that of level l (the same points, the same band, blocks twice
-//                    as wide).
-//  27. start       : every node of level l that has a value starts as 0.125 * the trilinear prolongation of chi_(l-1): a node that
-//                    coincides with a coarse node copies its value, an edge midpoint is 0.5 * (a + b), and face and cube centres
-//                    follow by the same halving applied axis after axis in the order x, y, z (first along x on the coarse rows,
-//                    then along y on those results, then along z).  The factor is a power of two: no rounding.  Fixed nodes keep
-//                    this value.  (Between two dense levels the field shrinks by 1/8 per level: the splat carries unit mass, b
-//                    carries 0.5 h, the stencil is unscaled.)
-//  28. system      : rules 5-6 at level l define b at the free nodes (V is needed one node beyond them; every such node has a
-//                    value).  The free nodes satisfy rule 7, the terms of fixed neighbours moved to the right side: A_ff chi_f = b',
-//                    b' = b - A_fc chi_c.  The solve runs until the true residual, recomputed on the device, satisfies
-//                    |b' - A_ff chi|_2 <= solve_tol * |b'|_2; the norms are sums of per-workgroup partials in a fixed order, as in
-//                    rule 8.  max_cycles * 64 iterations without that give MVS_E_SOLVER, with the level and the residual reported.
-//                    b' = 0 gives chi_f = 0 at once.  The solver is not part of the definition; the stop criterion and the identity
-//                    of two runs are.
-//  29. iso value   : rule 9 on level D.  The cube of every used point is active, so its eight corners have values.
-//  30. surface     : rules 10-12 over the active cubes of level D only.  An edge (node, type) exists when an active cube contains
-//                    it.  Vertices are numbered in ascending (node index, type) and faces ordered by ascending cube index, then
-//                    tetrahedron, then as listed, over what exists: the numbers of the dense call when every block is active.
-//  31. open edges  : a crossed edge of an active cube that lies on a face shared with an inactive cell, or on the boundary of the
-//                    grid, is counted in n_open_edges (once, whatever the number of such faces).  The mesh is returned as it is,
-//                    open there.  Where the solve closes a scan far from every sample, level D has no field and the surface ends;
-//                    mvs_processor_cull_model removes such closure anyway.
+// poisson_band_rules.h — band-refined levels over the dense grid of the Poisson stage (mvs_poisson_reconstruct_band): the per-point,
+// per-block, per-node and per-edge decisions of rules 24-31 as one __host__ __device__ body.  The rules themselves are stated in
+// include/mvs.h, behind mvs_poisson_reconstruct_screened, as rules 1-23 are.
 //
 // This header holds the decisions of rules 26, 27, 30 and 31: the block of a point, the dilation that makes a block active, the class
 // of a node, the start value of a node, whether an edge exists and is open, and the place of a row of nodes in rule 30's order.
-// tests/poisson_band_rules.cpp runs it as a program of its own against tests/ref_poisson_band.py, the numpy / scipy restatement of the
-// whole scheme.  No entry of the library runs the scheme yet.  A function that needs to know whether a cell is active,
-// or the value of a coarse node, takes that as a callable: storage is not a rule.
+// poisson_band.hip runs it on the device; tests/poisson_band_rules.cpp runs it as a program of its own against
+// tests/ref_poisson_band.py, the numpy / scipy restatement of the whole scheme.  A function that needs to know whether a cell is
+// active, or the value of a coarse node, takes that as a callable: storage is not a rule.
 #ifndef MVS_POISSON_BAND_RULES_H_
 #define MVS_POISSON_BAND_RULES_H_
 #include "poisson_rules.h"

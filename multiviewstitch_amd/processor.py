@@ -677,15 +677,22 @@ def RunPoisson(points, normals, params: L.CPoissonParams | None = None, stream: 
 
 
 def PoissonFiles(psr_npts, model_obj, params: L.CPoissonParams | None = None, dparams: L.CPoissonDensityParams | None = None,
-                 trim_ratio: float | None = None, sparams: "L.CPoissonScreenParams | None" = None):
+                 trim_ratio: float | None = None, sparams: "L.CPoissonScreenParams | None" = None,
+                 bparams: "L.CPoissonBandParams | None" = None):
     """``mvs_processor_poisson``: ``psr_npts`` (Result/PSR.npts, what ``StitchPointSets`` wrote) -> ``model_obj`` (Result/Model.obj with
     `v`, `vn` and `f` lines, what ``CullPoissonModel`` reads).  -> (V, F) written.  With ``dparams`` (``poisson_density_params``) or
     ``trim_ratio`` the call is ``mvs_processor_poisson_density``: the normals weighted by the sampling density when ``dparams`` sets
     WEIGHT_NORMALS, the mesh trimmed where its vertex density lies below ``trim_ratio`` times the mean point density.  With ``sparams``
-    (``poisson_screen_params``) the call is ``mvs_processor_poisson_screened``: the field pulled to the iso value at every point."""
+    (``poisson_screen_params``) the call is ``mvs_processor_poisson_screened``: the field pulled to the iso value at every point.
+    With ``bparams`` (``poisson_band_params``) the call is ``mvs_processor_poisson_band``, the band-refined levels up to depth 10; it is
+    unscreened and unweighted, so ``bparams`` together with ``dparams``, ``sparams`` or ``trim_ratio`` raises."""
     prm = params if params is not None else poisson_params()
     V, F = C.c_int64(), C.c_int64()
-    if sparams is not None:
+    if bparams is not None:
+        if dparams is not None or sparams is not None or trim_ratio is not None:
+            raise L.MvsError(-1, "PoissonFiles: bparams cannot be combined with dparams, sparams or trim_ratio (the band levels are unscreened and unweighted)")
+        L.check(L.lib().mvs_processor_poisson_band(os.fsencode(psr_npts), C.byref(prm), C.byref(bparams), os.fsencode(model_obj), C.byref(V), C.byref(F), None))
+    elif sparams is not None:
         L.check(L.lib().mvs_processor_poisson_screened(os.fsencode(psr_npts), C.byref(prm), C.byref(dparams) if dparams is not None else None,
                                                        C.byref(sparams), float(trim_ratio or 0.0), os.fsencode(model_obj), C.byref(V), C.byref(F)))
     elif dparams is None and trim_ratio is None:
@@ -694,6 +701,72 @@ def PoissonFiles(psr_npts, model_obj, params: L.CPoissonParams | None = None, dp
         L.check(L.lib().mvs_processor_poisson_density(os.fsencode(psr_npts), C.byref(prm), C.byref(dparams) if dparams is not None else None,
                                                       float(trim_ratio or 0.0), os.fsencode(model_obj), C.byref(V), C.byref(F)))
     return V.value, F.value
+
+
+def poisson_band_params(**kw) -> L.CPoissonBandParams:
+    """``mvs_poisson_band_default_params`` (base_depth 8, band 2) with the given fields replaced."""
+    return _params(L.CPoissonBandParams, L.lib().mvs_poisson_band_default_params, kw)
+
+
+def _poisson_band_info(binfo: L.CPoissonBandInfo) -> dict:
+    return dict(n_active_blocks=list(binfo.n_active_blocks), n_free=list(binfo.n_free), rel_residual=list(binfo.rel_residual),
+                bnorm=list(binfo.bnorm), iterations=list(binfo.iterations), n_open_edges=binfo.n_open_edges,
+                scratch_bytes=binfo.scratch_bytes, base_depth=binfo.base_depth, failed_level=binfo.failed_level)
+
+
+def RunPoissonBand(points, normals, params: L.CPoissonParams | None = None, bparams: L.CPoissonBandParams | None = None,
+                   stream: int | None = None, capacity: tuple | None = None):
+    """``mvs_poisson_reconstruct_band`` (rules 24-31 of include/mvs.h, this library's definition): a dense base level of depth
+    ``bparams.base_depth`` refined level by level on the blocks within ``bparams.band`` blocks of the points, up to depth 10.  Arguments
+    as ``RunPoisson``.  -> (vertices [V, 3] float64, faces [F, 3] int32, info dict as ``RunPoisson``'s — depth, h and iso those of the
+    finest level, cycles and rel_residual those of the base solve —, band info dict: per level (lists indexed by the level)
+    n_active_blocks, n_free, rel_residual, bnorm, iterations; n_open_edges, scratch_bytes, base_depth, failed_level).  When the call
+    fails, the exception carries ``info`` and ``band_info`` as far as they were written."""
+    prm = params if params is not None else poisson_params()
+    bprm = bparams if bparams is not None else poisson_band_params()
+    dev = _is_dev(points)
+    if dev != _is_dev(normals):
+        raise L.MvsError(-1, "points and normals must both be tensors on the GPU or both arrays")
+    order = contextlib.nullcontext()
+    if dev:
+        import torch
+        if stream:
+            order = torch.cuda.stream(torch.cuda.ExternalStream(int(stream)))
+        if tuple(points.shape) != tuple(normals.shape) or points.dim() != 2 or points.shape[1] != 3:
+            raise L.MvsError(-1, "points and normals must be [n, 3]")
+        pp, pn, n = _dev_ptr(points, "float64", "points"), _dev_ptr(normals, "float64", "normals"), int(points.shape[0])
+        fn, tail = L.lib().mvs_poisson_reconstruct_band_dev, (L.ptr(stream),)
+    else:
+        points, normals = L.arr(points, np.float64).reshape(-1, 3), L.arr(normals, np.float64).reshape(-1, 3)
+        if points.shape != normals.shape:
+            raise L.MvsError(-1, "points and normals must be [n, 3]")
+        pp, pn, n = L.ptr(points), L.ptr(normals), len(points)
+        fn, tail = L.lib().mvs_poisson_reconstruct_band, ()
+    nothing = np.zeros(3)                                       # a pointer to nothing is still a pointer; the name keeps it alive
+    if n == 0:
+        pp = pn = L.ptr(nothing)
+    if capacity is None:
+        dmax = max(0, min(int(prm.depth_max), L.POISSON_BAND_MAX_DEPTH))
+        capacity = (12 * 4 ** dmax, 24 * 4 ** dmax)
+    info, binfo = L.CPoissonInfo(), L.CPoissonBandInfo()
+    with order:
+        def call(vcap, fcap):
+            # v and f are named here and returned: the addresses handed to the library stay those of live arrays
+            v, f = _out_like(points, (max(1, vcap), 3), "float64"), _out_like(points, (max(1, fcap), 3), "int32")
+            rc = fn(n, pp, pn, C.byref(prm), C.byref(bprm), C.byref(info), C.byref(binfo), L.ptr(v), vcap, L.ptr(f), fcap, *tail)
+            return rc, v, f
+
+        vcap, fcap = int(capacity[0]), int(capacity[1])
+        rc, v, f = call(vcap, fcap)
+        if rc == -1 and (info.n_vertices > vcap or info.n_faces > fcap):
+            vcap, fcap = int(info.n_vertices), int(info.n_faces)
+            rc, v, f = call(vcap, fcap)
+    try:
+        L.check(rc)
+    except L.MvsError as e:
+        e.info, e.band_info = _poisson_info(info), _poisson_band_info(binfo)
+        raise
+    return v[:info.n_vertices], f[:info.n_faces], _poisson_info(info), _poisson_band_info(binfo)
 
 
 WEIGHT_NORMALS = 1                          # MVS_POISSON_WEIGHT_NORMALS

@@ -924,7 +924,8 @@ int mvs_poisson_reconstruct_screened_dev(int64_t n, const double* points_dev, co
  * dense base level (base_depth, 3 .. 9) and refines it level by level on the blocks of MVS_POISSON_BAND_BLOCK^3 cells within `band`
  * blocks (1 .. 64, Chebyshev) of the points only, each level taking its boundary values from the level below: still fp64, integer splats
  * that do not depend on their order, a stop criterion on the true residual, two runs the same bytes.  It is unscreened and unweighted;
- * density and screening over the band are not offered.  Like rules 1-23 this is this library's definition, NOT VERIFIED against GeoRec.
+ * mvs_poisson_reconstruct_band_density, below, carries the sampling density of rules 14-17 over every level (rules 32-35); screening
+ * over the band is not offered.  Like rules 1-23 this is this library's definition, NOT VERIFIED against GeoRec.
  *  24. depth       : D = rule 3 with Dmax = min(depth_max, MVS_POISSON_BAND_MAX_DEPTH).  At depth 10 the node index and the cube
  *                    index still fit in int32; a (node index, type) key needs int64.  B = min(D, base_depth).  With D <= base_depth
  *                    the result is that of mvs_poisson_reconstruct at depth_min = depth_max = D.
@@ -1000,6 +1001,50 @@ int mvs_poisson_reconstruct_band_dev(int64_t n, const double* points_dev, const 
                                      const mvs_poisson_band_params* bparams, mvs_poisson_info* info, mvs_poisson_band_info* binfo,
                                      double* vertices_dev, int64_t vertex_capacity, int32_t* faces_dev, int64_t face_capacity,
                                      void* hip_stream);
+
+/* The band call with the sampling density: rules 14-17 carried over every level, so that the depth config.txt asks for weights the
+ * normals where sequences overlap and its mesh, the one that ends in open edges and base-level closure, has a density per vertex for
+ * mvs_mesh_trim_by_value.  Rules 32-35 continue the list; like rules 1-31 they are this library's definition, NOT VERIFIED against GeoRec.
+ *  32. density grid: D and B are those of rule 24.  With D <= B the call IS mvs_poisson_reconstruct_density at depth_min = depth_max
+ *                    = D: its bytes, dinfo included, and binfo zero apart from base_depth.  Otherwise rule 14 applies with this D:
+ *                    Dd = max(D - density_drop, 2), and rule 15 (rho_p, rho_mean, the minimum and maximum, density_depth) is
+ *                    unchanged, with the same integer sums.  W is the function rule 14 defines on the full grid of depth Dd.
+ *                    Storage is not part of the definition, but a memory condition is: for Dd > B no array over all (2^Dd + 1)^3
+ *                    nodes is allocated.  The sums then live on stored blocks of level Dd (MVS_POISSON_BAND_BLOCK^3 cells; stored: a
+ *                    block that holds a node of a cell of the block of some used point, rule 26's block without the dilation),
+ *                    found through a table of the blocks, and a node without storage reads as 0.  That zero is exact: a point
+ *                    adds only to the corners of its own cell, that cell's block is marked, every node that touches a marked
+ *                    cell is stored, so every node with a non-zero sum is stored.  For Dd <= B the sums are a dense array, at most
+ *                    the base grid's size.  The structure lives from before the base splat until rule 34.
+ *  33. weighted levels (flag MVS_POISSON_WEIGHT_NORMALS): s_p of rule 16 is computed once, and the splat of rule 5 uses
+ *                    x = w * (n_a * s_p) at the base level (rule 25) and at every band level (rule 28).  Rule 26's blocks depend on
+ *                    the positions only and are unchanged; rule 29's iso value stays the unweighted mean over the used points.  The
+ *                    limit n <= 2^22 of rule 16 applies, by the same int64 argument on every level.
+ *  34. vertex density: rule 17 at the vertices of rule 30, W read as rule 32 says: 0 at a node that is not stored.  vertex_density
+ *                    may be NULL.
+ *  35. flags = 0   : vertices, faces, info and binfo hold the bytes of mvs_poisson_reconstruct_band, with or without vertex_density —
+ *                    but for binfo.scratch_bytes, which counts the density structure.
+ * The read of rule 32 is csrc/poisson_band_rules.h (bd_density_at).  dinfo is written by every call that gets past rule 24 and, with
+ * D > B, past rule 32.  Capacities, MVS_E_SOLVER and MVS_E_OOM as in mvs_poisson_reconstruct_band; vertex_density holds vertex_capacity
+ * doubles.  Scratch beyond the band call's, counted in binfo.scratch_bytes (csrc/poisson_band_plan.h, bd_density_bytes): 16 bytes per
+ * row for rho_p and s_p, 24 bytes for each of 1024 workgroups of the reduction over the points, and the node sums — 8 (2^Dd + 1)^3
+ * bytes for Dd <= B; for Dd > B 8 bytes per stored node (64 per stored block, plus 4 for its coordinates) and 4 bytes per entry of the
+ * table, (2^Dd / 4 + 1)^3 of them, with 2 more bytes per entry and 8 per table row while the blocks are numbered.
+ * MVS_E_INVALID_ARG, before a device is needed: what mvs_poisson_reconstruct_band refuses and what mvs_poisson_reconstruct_density
+ * refuses of dparams and dinfo: either NULL, max_gain not finite or outside [1, 16], density_drop outside [0, 8], a flag other than
+ * MVS_POISSON_WEIGHT_NORMALS, n > 2^22 with that flag.  Default parameters: mvs_poisson_band_default_params and
+ * mvs_poisson_density_default_params. */
+int mvs_poisson_reconstruct_band_density(int64_t n, const double* points, const double* normals, const mvs_poisson_params* p,
+                                         const mvs_poisson_band_params* bparams, const mvs_poisson_density_params* dparams,
+                                         mvs_poisson_info* info, mvs_poisson_band_info* binfo, mvs_poisson_density_info* dinfo,
+                                         double* vertices, double* vertex_density, int64_t vertex_capacity, int32_t* faces,
+                                         int64_t face_capacity);
+/* the device form, as mvs_poisson_reconstruct_dev */
+int mvs_poisson_reconstruct_band_density_dev(int64_t n, const double* points_dev, const double* normals_dev, const mvs_poisson_params* p,
+                                             const mvs_poisson_band_params* bparams, const mvs_poisson_density_params* dparams,
+                                             mvs_poisson_info* info, mvs_poisson_band_info* binfo, mvs_poisson_density_info* dinfo,
+                                             double* vertices_dev, double* vertex_density_dev, int64_t vertex_capacity, int32_t* faces_dev,
+                                             int64_t face_capacity, void* hip_stream);
 
 /* Rule 18 on any triangle mesh: vertices[V][3], normals[V][3] (may be NULL, then normals_out is not written), faces[F][3], values[V].
  * The outputs hold V resp. F rows and do not overlap the inputs; V_out / F_out receive the rows kept.  An ordered compaction without

@@ -142,6 +142,16 @@ int mvs_processor_poisson_screened(const char* psr_npts, const mvs_poisson_param
 int mvs_processor_poisson_band(const char* psr_npts, const mvs_poisson_params* params, const mvs_poisson_band_params* bparams,
                                const char* model_obj, int64_t* V, int64_t* F, int64_t* n_open_edges);
 
+/* mvs_processor_poisson_band through mvs_poisson_reconstruct_band_density (rules 32-35 of include/mvs.h: this library's definition, NOT
+ * VERIFIED against GeoRec): the band levels with the sampling density.  bparams and dparams NULL: their defaults (flags = 0: no
+ * weighting).  It reconstructs, then, when trim_ratio > 0, trims the mesh by its vertex density at the threshold trim_ratio *
+ * mean_density (mvs_mesh_trim_by_value_dev; trim_ratio <= 0: no trim; NaN: MVS_E_INVALID_ARG), then computes the vertex normals of
+ * the trimmed mesh, then writes.  n_open_edges (may be NULL) receives rule 31's count on the untrimmed mesh.  With dparams = NULL and
+ * trim_ratio = 0 the file holds the bytes mvs_processor_poisson_band writes. */
+int mvs_processor_poisson_band_density(const char* psr_npts, const mvs_poisson_params* params, const mvs_poisson_band_params* bparams,
+                                       const mvs_poisson_density_params* dparams, double trim_ratio, const char* model_obj, int64_t* V,
+                                       int64_t* F, int64_t* n_open_edges);
+
 #ifdef __cplusplus
 }
 #endif

@@ -107,6 +107,17 @@ int mvs_test_poisson_band_level(int64_t n, const double* points, const double* n
                                 const mvs_poisson_band_params* bparams, mvs_poisson_info* info, mvs_poisson_band_info* binfo, int32_t level,
                                 uint8_t* active, uint8_t* cls, double* b, double* chi, int64_t node_capacity);
 
+/* mvs_poisson_reconstruct_band_density up to rule 29: what mvs_test_poisson_band_level takes and hands out — the level's b weighted
+ * when dparams sets MVS_POISSON_WEIGHT_NORMALS (rule 33) —, plus dparams and dinfo, and of rule 32 node_sums, the int64 sums of the
+ * density grid expanded on the host to the dense layout (2^Dd + 1)^3 in node order (0 at a node without storage), and rho_p and s_p per
+ * row (n each; an unused row holds 0) as mvs_test_poisson_density hands them out.  MVS_E_INVALID_ARG as that hook and the call; a
+ * node count of the density grid above density_node_capacity after dinfo's density_depth is written. */
+int mvs_test_poisson_band_density_level(int64_t n, const double* points, const double* normals, const mvs_poisson_params* p,
+                                        const mvs_poisson_band_params* bparams, const mvs_poisson_density_params* dparams,
+                                        mvs_poisson_info* info, mvs_poisson_band_info* binfo, mvs_poisson_density_info* dinfo, int32_t level,
+                                        uint8_t* active, uint8_t* cls, double* b, double* chi, int64_t node_capacity, int64_t* node_sums,
+                                        int64_t density_node_capacity, double* rho, double* gain);
+
 /* mvs_grabcut_masks (host form) with its steps handed out, N = (w / 2) * (h / 2); every array but mask may be NULL:
  *   S [n] int64 (rule 7) and ncap [n][8][N] int32 (rule 8, the layout of mvs_grid_mincut's cap), once per call;
  *   labels [iters + 1][n][N] uint8 and sums [iters + 1][n][2][5][10] int64 (model 0 = foreground; per component c | s0 s1 s2 | p00 p01

@@ -210,6 +210,8 @@ _SIGS = {
     "mvs_poisson_band_default_params": (None, [_VP]),
     "mvs_poisson_reconstruct_band": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _I64]),
     "mvs_poisson_reconstruct_band_dev": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _I64, _VP]),
+    "mvs_poisson_reconstruct_band_density": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _I64]),
+    "mvs_poisson_reconstruct_band_density_dev": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _I64, _VP]),
     "mvs_mesh_trim_by_value": (C.c_int, [_I64, _VP, _VP, _I64, _VP, _VP, _D, _VP, _VP, _VP, _VP, _VP]),
     "mvs_mesh_trim_by_value_dev": (C.c_int, [_I64, _VP, _VP, _I64, _VP, _VP, _D, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mvs_render_depth": (C.c_int, [_VP, _I64, _VP, _I64, _VP, C.c_float, C.c_float, _VP]),
@@ -309,6 +311,7 @@ _SIGS = {
     "mvs_processor_poisson_density": (C.c_int, [C.c_char_p, _VP, _VP, _D, C.c_char_p, _VP, _VP]),
     "mvs_processor_poisson_screened": (C.c_int, [C.c_char_p, _VP, _VP, _VP, _D, C.c_char_p, _VP, _VP]),
     "mvs_processor_poisson_band": (C.c_int, [C.c_char_p, _VP, _VP, C.c_char_p, _VP, _VP, _VP]),
+    "mvs_processor_poisson_band_density": (C.c_int, [C.c_char_p, _VP, _VP, _VP, _D, C.c_char_p, _VP, _VP, _VP]),
     # include/mvs_test.h (test hooks: per handle, not part of the drop-in ABI)
     "mvs_test_preload_wait": (C.c_int, []),
     "mvs_test_ctl": (C.c_int, [_VP, _VP, _I32]),
@@ -327,6 +330,8 @@ _SIGS = {
     "mvs_test_poisson_density": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _I64]),
     "mvs_test_poisson_screened": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _I32]),
     "mvs_test_poisson_band_level": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _I64]),
+    "mvs_test_poisson_band_density_level": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _I64, _VP, _I64, _VP,
+                                                      _VP]),
     "mvs_test_rotations": (C.c_int, [_I64, _VP, _I32, _VP, _VP, _VP]),
 }
 EXPORTS = tuple(_SIGS)

@@ -842,6 +842,7 @@ struct PnRun {
     PnGrid gd{};
     int64_t nnd = 0;                      // nodes of the density grid
     Scratch dsum, rho, gain, dpart;
+    const double* row_gain = nullptr;     // s_p per row from outside (PnBaseField::solve for the band levels): rule 16's splat without dp
     struct Scan {                         // counts, their scan and its two levels, for nb workgroups
         Scratch cnt, base, local, tot, rbase;
         int alloc(size_t nb, hipStream_t s) {
@@ -1038,8 +1039,8 @@ struct PnRun {
         const unsigned nblk = (unsigned)((nn + PN_TPB - 1) / PN_TPB);
         HIPCHK(hipMemsetAsync(sums.p, 0, 24 * (size_t)nn, s));
         const dim3 pgrid((unsigned)((n + PN_TPB - 1) / PN_TPB));
-        if (dp && (dp->flags & MVS_POISSON_WEIGHT_NORMALS))
-            k_pn_splat<true><<<pgrid, dim3(PN_TPB), 0, s>>>(n, pts, nrm, g, sums.as<unsigned long long>(), gain.as<double>());
+        if (row_gain || (dp && (dp->flags & MVS_POISSON_WEIGHT_NORMALS)))
+            k_pn_splat<true><<<pgrid, dim3(PN_TPB), 0, s>>>(n, pts, nrm, g, sums.as<unsigned long long>(), row_gain ? row_gain : gain.as<double>());
         else
             k_pn_splat<false><<<pgrid, dim3(PN_TPB), 0, s>>>(n, pts, nrm, g, sums.as<unsigned long long>(), nullptr);
         k_pn_rhs<<<dim3(nblk), dim3(PN_TPB), 0, s>>>(g, sums.as<long long>(), rhs.as<double>());
@@ -1086,12 +1087,20 @@ struct PnRun {
         dinfo->mean_density = pn_rho_mean(q, info.n_used);
         dinfo->min_point_density = lo;
         dinfo->max_point_density = hi;
-        int32_t* part_c = dpart.as<int32_t>();                                // the partials above are spent
-        k_pn_gain<<<dim3((unsigned)nb), dim3(PN_TPB), 0, s>>>(n, pts, nrm, rho.as<double>(), dinfo->mean_density, dp->max_gain, gain.as<double>(), part_c);
+        return gains(n, pts, nrm, rho.as<double>(), dinfo->mean_density, dp->max_gain, gain.as<double>(), dpart.as<int32_t>(), &dinfo->n_clamped, s);
+    }
+
+    // rule 16: s_p of every row and the count of the used rows cut at max_gain; part_c: PN_RED_NB int32 on the device
+    static int gains(int64_t n, const double* pts, const double* nrm, const double* rho, double rho_mean, double max_gain, double* gain,
+                     int32_t* part_c, int32_t* n_clamped, hipStream_t s) {
+        const int nb = (int)std::min<int64_t>(PN_RED_NB, (n + PN_TPB - 1) / PN_TPB);
+        k_pn_gain<<<dim3((unsigned)nb), dim3(PN_TPB), 0, s>>>(n, pts, nrm, rho, rho_mean, max_gain, gain, part_c);
         HIPCHK(hipGetLastError());
         std::vector<int32_t> hc((size_t)nb);
-        if ((rc = fetch(hc.data(), part_c, 4 * (size_t)nb))) return rc;
-        for (int b = 0; b < nb; ++b) dinfo->n_clamped += hc[b];
+        HIPCHK(hipMemcpyAsync(hc.data(), part_c, 4 * (size_t)nb, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        *n_clamped = 0;
+        for (int b = 0; b < nb; ++b) *n_clamped += hc[b];
         return MVS_OK;
     }
 
@@ -1298,6 +1307,15 @@ int poisson_check_plain(const PnCall& c, int max_depth, const void* out_a, int64
     return check_pn(c.fn, c.n, c.points, c.normals, c.p, c.info, out_a, cap_a, out_b, cap_b, max_depth);
 }
 
+int poisson_check_density(const char* fn, int64_t n, const mvs_poisson_density_params* dp, const void* dinfo) { return check_pn_density(fn, n, dp, dinfo); }
+
+int poisson_gains(int64_t n, const double* pts_dev, const double* nrm_dev, const double* rho_dev, double rho_mean, double max_gain, double* gain_dev,
+                  int32_t* n_clamped, hipStream_t s) {
+    Scratch part_c;
+    const int rc = part_c.alloc(4 * (size_t)PN_RED_NB, s);
+    return rc ? rc : PnRun::gains(n, pts_dev, nrm_dev, rho_dev, rho_mean, max_gain, gain_dev, part_c.as<int32_t>(), n_clamped, s);
+}
+
 int poisson_cube(const PnCall& c, const double* pts_dev, const double* nrm_dev, hipStream_t s, double origin[3], double* side) {
     mvs_poisson_params p3 = *c.p;
     p3.depth_min = p3.depth_max = 3;      // rule 3 has no choice to make: no occupancy pass
@@ -1313,10 +1331,11 @@ int poisson_cube(const PnCall& c, const double* pts_dev, const double* nrm_dev, 
 
 PnBaseField::~PnBaseField() { delete (PnRun*)run; }
 
-int PnBaseField::solve(const PnCall& c, const double* pts_dev, const double* nrm_dev, hipStream_t s) {
+int PnBaseField::solve(const PnCall& c, const double* pts_dev, const double* nrm_dev, hipStream_t s, const double* gain_dev) {
     int rc;
     PnRun* r = new PnRun(c, pts_dev, nrm_dev, s);
     run = r;
+    r->row_gain = gain_dev;
     if ((rc = r->grid(c.fn)) || (rc = r->field(c.fn))) return rc;
     if (c.info->cycles > 0) {
         // One cycle past the criterion.  The finer levels take this field as their fixed values and in their right sides and cannot
@@ -1341,6 +1360,11 @@ int PnBaseField::solve(const PnCall& c, const double* pts_dev, const double* nrm
 int poisson_plain_dev(const PnCall& c, const double* pts_dev, const double* nrm_dev, double* vertices_dev, int64_t vcap, int32_t* faces_dev,
                       int64_t fcap, Scratch* bv, Scratch* bf, hipStream_t s) {
     return reconstruct(c, pts_dev, nrm_dev, PnOut{vertices_dev, nullptr, faces_dev, vcap, fcap, bv, nullptr, bf}, s);
+}
+
+int poisson_density_dev(const PnCall& c, const double* pts_dev, const double* nrm_dev, double* vertices_dev, double* density_dev, int64_t vcap,
+                        int32_t* faces_dev, int64_t fcap, Scratch* bv, Scratch* bd, Scratch* bf, hipStream_t s) {
+    return reconstruct(c, pts_dev, nrm_dev, PnOut{vertices_dev, density_dev, faces_dev, vcap, fcap, bv, bd, bf}, s);
 }
 
 extern "C" {

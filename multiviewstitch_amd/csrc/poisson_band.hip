@@ -15,7 +15,7 @@
 //                                         ballot, the host scans the T^2 row counts (bd_row_firsts; it needs the total anyway).  No atomic counter
 //   k_bd_neighbours / k_bd_rows           the six face neighbours of every block; on level D the block and row behind every place of bd_segment
 //   k_bd_class_start<Coarse>              rules 26-27: the class byte and the start value, from the dense chi_B or the level below's blocks
-//   k_bd_splat / k_bd_rhs                 rules 5-6 into block storage: int64 atomic adds, then b at the free nodes
+//   k_bd_splat<WEIGHTED> / k_bd_rhs       rules 5-6 into block storage: int64 atomic adds (WEIGHTED: rule 33, the normals times s_p), then b at the free nodes
 //   k_bd_bnorm                            |b'|^2, b' = b - A_fc chi_c: the stencil over the vector of the fixed values and zeros
 //   k_bd_residual<WRITE>                  the TRUE residual of the free nodes from chi and b (fixed neighbours included: the same number
 //                                         as b' - A_ff chi_f); WRITE: it becomes r of the solve
@@ -30,7 +30,16 @@
 //   k_bd_cubemask / k_bd_edge_count / k_bd_vertex_scatter / k_bd_face_count / k_bd_face_scatter
 //                                         rules 30-31 over the stored nodes in the order bd_segment gives them: the two ordered
 //                                         compactions of poisson.hip, items = (place of the node) * 7 + type resp. * 12 + slot (int64)
-// Nothing but integer atomics (the splat, the bitmap, the count of open edges) is unordered: two runs give the same bytes.
+// mvs_poisson_reconstruct_band_density (rules 32-35) carries the sampling density of rules 14-17 over every level.  The int64 sums of
+// the density grid of depth Dd lie dense when Dd <= B and else in the blocks of level Dd that a cell of a used point touches
+// (k_bd_mark without the dilation, k_bd_stored, k_bd_row_count, k_bd_number: the table of a level, 8 bytes per stored node); a node
+// without storage reads as 0 (bd_density_at of poisson_band_rules.h).
+//   k_bd_density_splat                    rule 14 through that storage: a thread per point, 8 int64 atomic adds
+//   k_bd_point_density                    rule 15: rho_p per row; min, max and the int64 sum of the quantised densities per workgroup
+//                                         (order-free, k_pn_point_density's partials); the gains of rule 16 are poisson.hip's k_pn_gain
+//   k_bd_vertex_density                   rule 34 over the vertex list the scatter wrote
+// BdRun runs the stages in the order depth, density, base, levels, iso, mesh, vertex density.
+// Nothing but integer atomics (the splats, the bitmap, the count of open edges) is unordered: two runs give the same bytes.
 #include "engine.h"
 #include "trace.h"
 #include "frontend_dev.h"
@@ -111,10 +120,7 @@ struct BdActive {
     __device__ bool operator()(int cx, int cy, int cz) const { return v.act[bd_tab(v, cx >> 2, cy >> 2, cz >> 2)] != 0; }
 };
 // node (ix, iy, iz) in [0, G]^3 -> its place 64 s + lane in the node arrays, -1 when its block is not stored
-__device__ inline int64_t bd_slot(const BdView& v, int ix, int iy, int iz) {
-    const int s = v.num[bd_tab(v, ix >> 2, iy >> 2, iz >> 2)];
-    return s < 0 ? -1 : (int64_t)s * 64 + ((iz & 3) << 4 | (iy & 3) << 2 | (ix & 3));
-}
+__device__ inline int64_t bd_slot(const BdView& v, int ix, int iy, int iz) { return bd_node_slot(v.num, v.T, ix, iy, iz); }
 __device__ inline void bd_unpack(int32_t c, int* bx, int* by, int* bz) { *bx = c & 1023; *by = c >> 10 & 1023; *bz = c >> 20 & 1023; }
 
 // ------------------------------------------------------------------ rule 26 ----
@@ -231,18 +237,97 @@ __global__ __launch_bounds__(BD_TPB) void k_bd_class_start(int64_t ns, const int
 }
 
 // ------------------------------------------------------------------ rules 5-6 in block storage ----
+// WEIGHTED: rule 33, every normal scaled by the gain s_p of its point (k_pn_splat<true>'s expression)
+template <bool WEIGHTED>
 __global__ __launch_bounds__(BD_TPB) void k_bd_splat(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm, PnGrid g, BdView v,
-                                                     int64_t nodes, unsigned long long* __restrict__ sums) {
+                                                     int64_t nodes, unsigned long long* __restrict__ sums, const double* __restrict__ gain) {
+    const int64_t i = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
+    if (i >= n || !pn_used(pts + 3 * i, nrm + 3 * i)) return;
+    int i0[3];
+    double w[8], na[3];
+    pn_corners_weights(pts + 3 * i, g, i0, w);
+    for (int a = 0; a < 3; ++a) na[a] = WEIGHTED ? nrm[3 * i + a] * gain[i] : nrm[3 * i + a];
+    for (int c = 0; c < 8; ++c) {
+        const int64_t at = bd_slot(v, i0[0] + (c & 1), i0[1] + (c >> 1 & 1), i0[2] + (c >> 2 & 1));
+        if (at < 0) continue;                                                // rule 29: cannot be, the cube of a used point is active
+        for (int a = 0; a < 3; ++a) atomicAdd(sums + a * nodes + at, (unsigned long long)pn_quant(w[c] * na[a]));
+    }
+}
+
+// ------------------------------------------------------------------ rules 32-34 ----
+// The int64 sums of the density grid as the kernels see them: dense in node order (num == NULL: Dd <= B) or 64 per stored block of
+// level Dd behind the block table (rule 32); operator() is the sum() of bd_density_at
+struct BdDensity {
+    PnGrid g;
+    const int32_t* num;
+    int32_t T;
+    const long long* sums;
+    __device__ int64_t slot(int ix, int iy, int iz) const { return num ? bd_node_slot(num, T, ix, iy, iz) : pn_node(g.G, ix, iy, iz); }
+    __device__ long long operator()(int ix, int iy, int iz) const { return num ? BdBlockSums{num, T, sums}(ix, iy, iz) : BdDenseSums{g.G, sums}(ix, iy, iz); }
+};
+
+// rule 14 into that storage: a thread per point, 8 int64 atomic adds
+__global__ __launch_bounds__(BD_TPB) void k_bd_density_splat(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm, BdDensity d,
+                                                             unsigned long long* __restrict__ dsum) {
     const int64_t i = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
     if (i >= n || !pn_used(pts + 3 * i, nrm + 3 * i)) return;
     int i0[3];
     double w[8];
-    pn_corners_weights(pts + 3 * i, g, i0, w);
+    pn_corners_weights(pts + 3 * i, d.g, i0, w);
     for (int c = 0; c < 8; ++c) {
-        const int64_t at = bd_slot(v, i0[0] + (c & 1), i0[1] + (c >> 1 & 1), i0[2] + (c >> 2 & 1));
-        if (at < 0) continue;                                                // rule 29: cannot be, the cube of a used point is active
-        for (int a = 0; a < 3; ++a) atomicAdd(sums + a * nodes + at, (unsigned long long)pn_quant(w[c] * nrm[3 * i + a]));
+        const int64_t at = d.slot(i0[0] + (c & 1), i0[1] + (c >> 1 & 1), i0[2] + (c >> 2 & 1));
+        if (at < 0) continue;                                                // rule 32: cannot be, the block of the point's cell is marked
+        atomicAdd(dsum + at, (unsigned long long)pn_quant(w[c]));
     }
+}
+
+// v folded over the workgroup by op in a fixed order, valid in thread 0: wg_fold of poisson.hip
+template <class T, class Op>
+__device__ inline T bd_wg_fold(T v, T zero, T* s_part, int tid, Op op) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_down(v, o, 64));
+    if ((tid & 63) == 0) s_part[tid >> 6] = v;
+    __syncthreads();
+    T t = zero;
+    if (tid == 0)
+        for (int q = 0; q < BD_WAVES; ++q) t = op(t, s_part[q]);
+    return t;
+}
+
+// rule 15 through rule 32's read: rho_p of every row (0 for a row that is not used) and, per workgroup, the min, the max and the int64
+// sum of the quantised densities of its used rows, all three order-free (k_pn_point_density's partials); the host finishes
+__global__ __launch_bounds__(BD_TPB) void k_bd_point_density(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm, BdDensity d,
+                                                             double* __restrict__ rho, double* __restrict__ part_d, long long* __restrict__ part_q) {
+    __shared__ double s_lo[BD_WAVES], s_hi[BD_WAVES];
+    __shared__ long long s_q[BD_WAVES];
+    double lo = HUGE_VAL, hi = -HUGE_VAL;
+    long long q = 0;
+    for (int64_t i = (int64_t)blockIdx.x * BD_TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * BD_TPB) {
+        double r = 0.0;
+        if (pn_used(pts + 3 * i, nrm + 3 * i)) {
+            r = bd_density_at(pts + 3 * i, d.g, d);
+            lo = fmin(lo, r);
+            hi = fmax(hi, r);
+            q += pn_rho_quant(r);
+        }
+        rho[i] = r;
+    }
+    lo = bd_wg_fold(lo, HUGE_VAL, s_lo, threadIdx.x, [](double a, double b) { return fmin(a, b); });
+    hi = bd_wg_fold(hi, -HUGE_VAL, s_hi, threadIdx.x, [](double a, double b) { return fmax(a, b); });
+    q = bd_wg_fold(q, 0ll, s_q, threadIdx.x, [](long long a, long long b) { return a + b; });
+    if (threadIdx.x == 0) {
+        part_d[2 * blockIdx.x] = lo;
+        part_d[2 * blockIdx.x + 1] = hi;
+        part_q[blockIdx.x] = q;
+    }
+}
+
+// rule 34: a thread per vertex of the scattered list; a cell needs a finite position
+__global__ __launch_bounds__(BD_TPB) void k_bd_vertex_density(int64_t nv, const double* __restrict__ vertices, BdDensity d, double* __restrict__ out) {
+    const int64_t v = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
+    if (v >= nv) return;
+    const double* p = vertices + 3 * v;
+    out[v] = isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]) ? bd_density_at(p, d.g, d) : NAN;
 }
 
 // the places of the six neighbours of node `lane` of block s, in the order of nbr; -1: in a block that is not stored
@@ -659,6 +744,14 @@ struct BdRun {
     int D = 0, B = 0;
     BdBytes bytes;
     Scratch red, cnt8;                    // the partials of the reductions and their sum; one integer counter
+    // rules 32-34 (mvs_poisson_reconstruct_band_density): absent for the band call
+    const mvs_poisson_density_params* dp = nullptr;
+    mvs_poisson_density_info* dinfo = nullptr;
+    PnGrid gd{};
+    int Dd = 0;
+    BdExtent de{};                        // the block table of level Dd, when the sums live in blocks
+    int64_t dns = 0, dslots = 0;          // stored blocks of the density grid; int64 sums held (64 dns, or every node of a dense grid)
+    Scratch dnum, dcoord, dsum, rho, gain, dpart;
     std::unique_ptr<BdLevel> top;         // level D after levels()
     // the surface
     Scratch rows, mask, words;
@@ -666,11 +759,14 @@ struct BdRun {
     int64_t edge_items = 0, face_items = 0;
 
     BdRun(const char* f, const mvs_poisson_params& pp, const mvs_poisson_band_params& b, mvs_poisson_info& i, mvs_poisson_band_info& bi, int64_t nn,
-          const double* pd, const double* nd, hipStream_t st)
-        : fn(f), p(pp), bp(b), info(i), binfo(bi), n(nn), pts(pd), nrm(nd), s(st) {
+          const double* pd, const double* nd, hipStream_t st, const mvs_poisson_density_params* dpar = nullptr, mvs_poisson_density_info* di = nullptr)
+        : fn(f), p(pp), bp(b), info(i), binfo(bi), n(nn), pts(pd), nrm(nd), s(st), dp(dpar), dinfo(di) {
         std::memset(&info, 0, sizeof info);
         std::memset(&binfo, 0, sizeof binfo);
+        if (dinfo) std::memset(dinfo, 0, sizeof *dinfo);
     }
+    bool weighted() const { return dp && (dp->flags & MVS_POISSON_WEIGHT_NORMALS); }
+    BdDensity density_view() const { return BdDensity{gd, bd_density_in_blocks(Dd, B) ? dnum.as<int32_t>() : nullptr, de.T, dsum.as<long long>()}; }
 
     int take(Scratch& sc, int64_t b, int64_t* held = nullptr) {
         const int rc = sc.alloc((size_t)b, s);
@@ -734,6 +830,99 @@ struct BdRun {
         return MVS_OK;
     }
 
+    // rules 32-33 up to the gains: where the sums of the density grid live, rule 14 into it, rho_p, rho_mean and s_p
+    int density() {
+        int rc;
+        gd = pn_density_grid(grid_of(D), side, D, dp->density_drop, &Dd);
+        dinfo->density_depth = Dd;
+        if (bd_density_in_blocks(Dd, B)) {                                   // the blocks a cell of a used point touches: rule 26's marks, not dilated
+            de = bd_extent(Dd);
+            const unsigned tgrid = bd_grid(de.table), rgrid = (unsigned)((de.rows + BD_WAVES - 1) / BD_WAVES);
+            Scratch ta, tb, rcnt, first;
+            if ((rc = take(ta, de.table)) || (rc = take(tb, de.table)) || (rc = take(rcnt, 4 * de.rows)) || (rc = take(first, 4 * (de.rows + 1))) ||
+                (rc = dnum.alloc((size_t)(4 * de.table), s))) return rc;
+            HIPCHK(hipMemsetAsync(ta.p, 0, (size_t)de.table, s));
+            k_bd_mark<<<dim3(bd_grid(n)), dim3(BD_TPB), 0, s>>>(n, pts, nrm, gd, de.T, ta.as<uint8_t>());
+            k_bd_stored<<<dim3(tgrid), dim3(BD_TPB), 0, s>>>(de.T, ta.as<uint8_t>(), tb.as<uint8_t>());
+            k_bd_row_count<<<dim3(rgrid), dim3(BD_TPB), 0, s>>>(de.T, tb.as<uint8_t>(), rcnt.as<int32_t>());
+            HIPCHK(hipGetLastError());
+            std::vector<int32_t> hc((size_t)de.rows), hf((size_t)de.rows + 1);
+            if ((rc = fetch(hc.data(), rcnt.p, 4 * (size_t)de.rows))) return rc;
+            dns = bd_row_firsts(de, hc.data(), hf.data());
+            if (dns < 0) { mvs_set_error("%s: the row counts of the density grid are not counts", fn); return MVS_E_HIP; }
+            if (!bd_fits_int32(dns)) {
+                mvs_set_error("%s: the density grid of depth %d stores %lld blocks of 64 nodes: more than an int32 index reaches", fn, Dd, (long long)dns);
+                return MVS_E_INVALID_ARG;
+            }
+            if ((rc = dcoord.alloc((size_t)(4 * dns), s))) return rc;
+            HIPCHK(hipMemcpy(first.p, hf.data(), 4 * hf.size(), hipMemcpyHostToDevice));     // the stream is idle: fetch synchronised it
+            k_bd_number<<<dim3(rgrid), dim3(BD_TPB), 0, s>>>(de.T, tb.as<uint8_t>(), first.as<int32_t>(), dnum.as<int32_t>(), dcoord.as<int32_t>());
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipStreamSynchronize(s));                                  // ta, tb, rcnt and first go
+            bytes.give(bd_density_work_bytes(Dd, B));
+            dslots = dns * 64;
+        } else
+            dslots = (int64_t)(gd.G + 1) * (gd.G + 1) * (gd.G + 1);
+        if ((rc = dsum.alloc((size_t)(8 * dslots), s)) || (rc = rho.alloc(8 * (size_t)n, s)) || (rc = gain.alloc(8 * (size_t)n, s)) ||
+            (rc = dpart.alloc(24 * (size_t)BD_RED_NB, s))) return rc;
+        bytes.take(bd_density_bytes(Dd, B, dns, n));
+        const BdDensity dv = density_view();
+        const int nb = (int)std::min<int64_t>(BD_RED_NB, (n + BD_TPB - 1) / BD_TPB);
+        double* part_d = dpart.as<double>();
+        long long* part_q = dpart.as<long long>() + 2 * BD_RED_NB;
+        HIPCHK(hipMemsetAsync(dsum.p, 0, (size_t)(8 * dslots), s));
+        k_bd_density_splat<<<dim3(bd_grid(n)), dim3(BD_TPB), 0, s>>>(n, pts, nrm, dv, dsum.as<unsigned long long>());
+        k_bd_point_density<<<dim3((unsigned)nb), dim3(BD_TPB), 0, s>>>(n, pts, nrm, dv, rho.as<double>(), part_d, part_q);
+        HIPCHK(hipGetLastError());
+        std::vector<double> hd((size_t)2 * nb);
+        std::vector<long long> hq((size_t)nb);
+        HIPCHK(hipMemcpyAsync(hd.data(), part_d, 16 * (size_t)nb, hipMemcpyDeviceToHost, s));
+        if ((rc = fetch(hq.data(), part_q, 8 * (size_t)nb))) return rc;
+        double lo = HUGE_VAL, hi = -HUGE_VAL;
+        long long q = 0;
+        for (int b = 0; b < nb; ++b) { lo = std::fmin(lo, hd[2 * b]); hi = std::fmax(hi, hd[2 * b + 1]); q += hq[b]; }
+        dinfo->mean_density = pn_rho_mean(q, info.n_used);
+        dinfo->min_point_density = lo;
+        dinfo->max_point_density = hi;
+        return poisson_gains(n, pts, nrm, rho.as<double>(), dinfo->mean_density, dp->max_gain, gain.as<double>(), &dinfo->n_clamped, s);
+    }
+
+    // rule 34, after scatter
+    int vertex_density(const double* vertices, double* out) {
+        if (!out || info.n_vertices == 0) return MVS_OK;
+        k_bd_vertex_density<<<dim3(bd_grid(info.n_vertices)), dim3(BD_TPB), 0, s>>>(info.n_vertices, vertices, density_view(), out);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(s));
+        return MVS_OK;
+    }
+
+    // the hook's part of rules 32-33: the node sums expanded to the dense layout of the density grid, rho_p and s_p per row
+    int dump_density(int64_t* node_sums, int64_t capacity, double* rho_out, double* gain_out) {
+        const int n1 = gd.G + 1;
+        const int64_t nn = (int64_t)n1 * n1 * n1;
+        if (nn > capacity) return bad(fn, "density_node_capacity is below (2^density_depth + 1)^3 (dinfo holds the depth)");
+        HIPCHK(hipStreamSynchronize(s));
+        HIPCHK(hipMemcpy(rho_out, rho.p, 8 * (size_t)n, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(gain_out, gain.p, 8 * (size_t)n, hipMemcpyDeviceToHost));
+        if (!bd_density_in_blocks(Dd, B)) {
+            HIPCHK(hipMemcpy(node_sums, dsum.p, 8 * (size_t)nn, hipMemcpyDeviceToHost));
+            return MVS_OK;
+        }
+        std::vector<long long> hs((size_t)dslots + 1);
+        std::vector<int32_t> coord((size_t)dns + 1);
+        HIPCHK(hipMemcpy(hs.data(), dsum.p, 8 * (size_t)dslots, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(coord.data(), dcoord.p, 4 * (size_t)dns, hipMemcpyDeviceToHost));
+        for (int64_t i = 0; i < nn; ++i) node_sums[i] = 0;
+        for (int64_t sb = 0; sb < dns; ++sb) {
+            const int bx = coord[(size_t)sb] & 1023, by = coord[(size_t)sb] >> 10 & 1023, bz = coord[(size_t)sb] >> 20 & 1023;
+            for (int lane = 0; lane < 64; ++lane) {
+                const int ix = 4 * bx + (lane & 3), iy = 4 * by + (lane >> 2 & 3), iz = 4 * bz + (lane >> 4);
+                if (ix <= gd.G && iy <= gd.G && iz <= gd.G) node_sums[((int64_t)iz * n1 + iy) * n1 + ix] = hs[(size_t)(sb * 64 + lane)];
+            }
+        }
+        return MVS_OK;
+    }
+
     // rule 26 and the numbering: the tables and the per-block arrays of level l
     int blocks(BdLevel& L, int l) {
         int rc;
@@ -790,7 +979,8 @@ struct BdRun {
         const unsigned ngrid = bd_grid(L.nodes);
         k_bd_class_start<Coarse><<<dim3(ngrid), dim3(BD_TPB), 0, s>>>(L.ns, L.coord.as<int32_t>(), v, coarse, L.cls.as<uint8_t>(), L.x.as<double>());
         HIPCHK(hipMemsetAsync(L.sums.p, 0, (size_t)(24 * L.nodes), s));
-        k_bd_splat<<<dim3(bd_grid(n)), dim3(BD_TPB), 0, s>>>(n, pts, nrm, L.g, v, L.nodes, L.sums.as<unsigned long long>());
+        if (weighted()) k_bd_splat<true><<<dim3(bd_grid(n)), dim3(BD_TPB), 0, s>>>(n, pts, nrm, L.g, v, L.nodes, L.sums.as<unsigned long long>(), gain.as<double>());
+        else k_bd_splat<false><<<dim3(bd_grid(n)), dim3(BD_TPB), 0, s>>>(n, pts, nrm, L.g, v, L.nodes, L.sums.as<unsigned long long>(), nullptr);
         k_bd_rhs<<<dim3(ngrid), dim3(BD_TPB), 0, s>>>(L.ns, L.nbr.as<int32_t>(), L.cls.as<uint8_t>(), L.nodes, L.sums.as<long long>(), L.g.h, L.b.as<double>());
         HIPCHK(hipGetLastError());
         return count(L.cls.as<uint8_t>(), L.nodes, true, &binfo.n_free[l]);
@@ -891,7 +1081,7 @@ struct BdRun {
         mvs_poisson_info ib;
         const PnCall cb{fn, PN_PLAIN, n, pts, nrm, &pb, &ib, nullptr, nullptr, nullptr, nullptr};
         std::unique_ptr<PnBaseField> base(new PnBaseField);
-        rc = base->solve(cb, pts, nrm, s);
+        rc = base->solve(cb, pts, nrm, s, weighted() ? gain.as<double>() : nullptr);
         info.cycles = ib.cycles;
         info.rel_residual = ib.rel_residual;
         if (rc == MVS_E_SOLVER) binfo.failed_level = B;
@@ -1003,6 +1193,8 @@ struct BdOut {
     int32_t* faces;
     int64_t vcap, fcap;
     Scratch *bv, *bf;
+    double* density = nullptr;            // rule 34 per vertex; NULL (and bd NULL): not wanted
+    Scratch* bd = nullptr;
 };
 
 struct BdCall {
@@ -1013,25 +1205,31 @@ struct BdCall {
     const mvs_poisson_band_params* bp;
     mvs_poisson_info* info;
     mvs_poisson_band_info* binfo;
+    const mvs_poisson_density_params* dp = nullptr;      // mvs_poisson_reconstruct_band_density: rules 32-35; the band call has neither
+    mvs_poisson_density_info* dinfo = nullptr;
+    bool density = false;
 };
 
 int check_band_call(const BdCall& c, const void* out_a, int64_t cap_a, const void* out_b, int64_t cap_b) {
     const PnCall pc{c.fn, PN_PLAIN, c.n, c.points, c.normals, c.p, c.info, nullptr, nullptr, nullptr, nullptr};
-    const int rc = poisson_check_plain(pc, BD_MAX_D, out_a, cap_a, out_b, cap_b);
-    return rc ? rc : check_band(c.fn, c.bp, c.binfo);
+    int rc = poisson_check_plain(pc, BD_MAX_D, out_a, cap_a, out_b, cap_b);
+    if (!rc) rc = check_band(c.fn, c.bp, c.binfo);
+    return !rc && c.density ? poisson_check_density(c.fn, c.n, c.dp, c.dinfo) : rc;
 }
 
 // the device form of the entry, after its checks
 int band_reconstruct(const BdCall& c, const double* pts, const double* nrm, BdOut o, hipStream_t s) {
     int rc;
-    BdRun run(c.fn, *c.p, *c.bp, *c.info, *c.binfo, c.n, pts, nrm, s);
+    BdRun run(c.fn, *c.p, *c.bp, *c.info, *c.binfo, c.n, pts, nrm, s, c.dp, c.dinfo);
     if ((rc = run.depth())) return rc;
-    if (run.D <= run.B) {                                                     // rule 24: the plain call at depth D, its bytes
+    if (run.D <= run.B) {                                                     // rules 24 and 32: the plain or the density call at depth D, its bytes
         mvs_poisson_params pd = *c.p;
         pd.depth_min = pd.depth_max = run.D;
-        const PnCall pc{c.fn, PN_PLAIN, c.n, pts, nrm, &pd, c.info, nullptr, nullptr, nullptr, nullptr};
+        const PnCall pc{c.fn, c.density ? PN_DENSITY : PN_PLAIN, c.n, pts, nrm, &pd, c.info, c.dp, c.dinfo, nullptr, nullptr};
+        if (c.density) return poisson_density_dev(pc, pts, nrm, o.vertices, o.density, o.vcap, o.faces, o.fcap, o.bv, o.bd, o.bf, s);
         return poisson_plain_dev(pc, pts, nrm, o.vertices, o.vcap, o.faces, o.fcap, o.bv, o.bf, s);
     }
+    if (c.density && (rc = run.density())) { run.finish_info(); return rc; }
     rc = run.levels(nullptr);
     run.finish_info();
     if (rc || (rc = run.iso_value()) || (rc = run.count_mesh())) { run.finish_info(); return rc; }
@@ -1039,11 +1237,13 @@ int band_reconstruct(const BdCall& c, const double* pts, const double* nrm, BdOu
     const int64_t V = c.info->n_vertices, F = c.info->n_faces;
     if (!bd_capacity_ok(V, F, o.vcap, o.fcap)) return bad(c.fn, "a capacity is below the count (info holds n_vertices and n_faces)");
     if (o.bv) {
-        if ((rc = o.bv->alloc(24 * (size_t)V)) || (rc = o.bf->alloc(12 * (size_t)F))) return rc;
+        if ((rc = o.bv->alloc(24 * (size_t)V)) || (rc = o.bf->alloc(12 * (size_t)F)) || (o.bd && (rc = o.bd->alloc(8 * (size_t)V)))) return rc;
         o.vertices = o.bv->as<double>();
         o.faces = o.bf->as<int32_t>();
+        o.density = o.bd ? o.bd->as<double>() : nullptr;
     }
-    return run.scatter(o.vertices, o.faces);
+    if ((rc = run.scatter(o.vertices, o.faces))) return rc;
+    return c.density ? run.vertex_density(o.vertices, o.density) : MVS_OK;
 }
 
 }  // namespace
@@ -1054,6 +1254,15 @@ int poisson_band_blocks(const char* fn, int64_t n, const double* pts_dev, const 
     const BdCall c{fn, n, pts_dev, nrm_dev, p, bp, info, binfo};
     const int rc = check_band_call(c, nullptr, 0, nullptr, 0);
     return rc ? rc : band_reconstruct(c, pts_dev, nrm_dev, BdOut{nullptr, nullptr, INT64_MAX, INT64_MAX, vertices, faces}, nullptr);
+}
+
+// ... and for mvs_poisson_reconstruct_band_density (mvs_processor_poisson_band_density); density receives d_v of rule 34 per vertex
+int poisson_band_density_blocks(const char* fn, int64_t n, const double* pts_dev, const double* nrm_dev, const mvs_poisson_params* p,
+                                const mvs_poisson_band_params* bp, const mvs_poisson_density_params* dp, mvs_poisson_info* info,
+                                mvs_poisson_band_info* binfo, mvs_poisson_density_info* dinfo, Scratch* vertices, Scratch* density, Scratch* faces) {
+    const BdCall c{fn, n, pts_dev, nrm_dev, p, bp, info, binfo, dp, dinfo, true};
+    const int rc = check_band_call(c, nullptr, 0, nullptr, 0);
+    return rc ? rc : band_reconstruct(c, pts_dev, nrm_dev, BdOut{nullptr, nullptr, INT64_MAX, INT64_MAX, vertices, faces, nullptr, density}, nullptr);
 }
 
 extern "C" {
@@ -1103,6 +1312,66 @@ int mvs_test_poisson_band_level(int64_t n, const double* points, const double* n
     if ((rc = run.depth())) return rc;
     run.finish_info();
     if (level <= run.B || level > run.D) return bad(__func__, "level is outside base_depth + 1 .. depth (info and binfo hold them)");
+    const BdDump d{level, active, cls, b, chi, node_capacity};
+    rc = run.levels(&d);
+    run.finish_info();
+    if (rc) return rc;
+    rc = run.iso_value();
+    run.finish_info();
+    return rc;
+}
+
+// ------------------------------------------------------------------ rules 32-35 ----
+int mvs_poisson_reconstruct_band_density_dev(int64_t n, const double* points_dev, const double* normals_dev, const mvs_poisson_params* p,
+                                             const mvs_poisson_band_params* bparams, const mvs_poisson_density_params* dparams,
+                                             mvs_poisson_info* info, mvs_poisson_band_info* binfo, mvs_poisson_density_info* dinfo,
+                                             double* vertices_dev, double* vertex_density_dev, int64_t vertex_capacity, int32_t* faces_dev,
+                                             int64_t face_capacity, void* hip_stream) {
+    MVS_TRACE();
+    const BdCall c{__func__, n, points_dev, normals_dev, p, bparams, info, binfo, dparams, dinfo, true};
+    int rc = check_band_call(c, vertices_dev, vertex_capacity, faces_dev, face_capacity);
+    if (rc || (rc = need_device())) return rc;
+    return band_reconstruct(c, points_dev, normals_dev, BdOut{vertices_dev, faces_dev, vertex_capacity, face_capacity, nullptr, nullptr, vertex_density_dev, nullptr},
+                            (hipStream_t)hip_stream);
+}
+
+int mvs_poisson_reconstruct_band_density(int64_t n, const double* points, const double* normals, const mvs_poisson_params* p,
+                                         const mvs_poisson_band_params* bparams, const mvs_poisson_density_params* dparams, mvs_poisson_info* info,
+                                         mvs_poisson_band_info* binfo, mvs_poisson_density_info* dinfo, double* vertices, double* vertex_density,
+                                         int64_t vertex_capacity, int32_t* faces, int64_t face_capacity) {
+    MVS_TRACE();
+    const BdCall c{__func__, n, points, normals, p, bparams, info, binfo, dparams, dinfo, true};
+    Scratch dp, dn, dv, dd, df;
+    int rc = check_band_call(c, vertices, vertex_capacity, faces, face_capacity);
+    if (rc || (rc = need_device()) || (rc = up(dp, points, 3 * (size_t)n)) || (rc = up(dn, normals, 3 * (size_t)n)) ||
+        (rc = band_reconstruct(c, dp.as<double>(), dn.as<double>(),
+                               BdOut{nullptr, nullptr, vertex_capacity, face_capacity, &dv, &df, nullptr, vertex_density ? &dd : nullptr}, nullptr)))
+        return rc;
+    const size_t V = (size_t)info->n_vertices, F = (size_t)info->n_faces;
+    if ((vertex_density && (rc = down(vertex_density, dd, V))) || (rc = down(vertices, dv, 3 * V))) return rc;
+    return down(faces, df, 3 * F);
+}
+
+// The call up to rule 29 with rules 32-33, level `level` and the density handed out dense (include/mvs_test.h)
+int mvs_test_poisson_band_density_level(int64_t n, const double* points, const double* normals, const mvs_poisson_params* p,
+                                        const mvs_poisson_band_params* bparams, const mvs_poisson_density_params* dparams, mvs_poisson_info* info,
+                                        mvs_poisson_band_info* binfo, mvs_poisson_density_info* dinfo, int32_t level, uint8_t* active, uint8_t* cls,
+                                        double* b, double* chi, int64_t node_capacity, int64_t* node_sums, int64_t density_node_capacity, double* rho,
+                                        double* gain) {
+    MVS_TRACE();
+    const BdCall c{__func__, n, points, normals, p, bparams, info, binfo, dparams, dinfo, true};
+    Scratch dp, dn;
+    int rc = check_band_call(c, b, node_capacity, node_sums, density_node_capacity);
+    if (rc) return rc;
+    if (!active || !cls || !b || !chi || !node_sums || !rho || !gain) return bad(__func__, "active, cls, b, chi, node_sums, rho or gain is NULL");
+    if ((rc = need_device()) || (rc = up(dp, points, 3 * (size_t)n)) || (rc = up(dn, normals, 3 * (size_t)n))) return rc;
+    BdRun run(__func__, *p, *bparams, *info, *binfo, n, dp.as<double>(), dn.as<double>(), nullptr, dparams, dinfo);
+    if ((rc = run.depth())) return rc;
+    run.finish_info();
+    if (level <= run.B || level > run.D) return bad(__func__, "level is outside base_depth + 1 .. depth (info and binfo hold them)");
+    rc = run.density();
+    run.finish_info();
+    if (rc || (rc = run.dump_density(node_sums, density_node_capacity, rho, gain))) return rc;
     const BdDump d{level, active, cls, b, chi, node_capacity};
     rc = run.levels(&d);
     run.finish_info();

@@ -1,6 +1,7 @@
 // poisson_band_plan.h — the sizes and index arithmetic the host does for the band levels of the Poisson stage (rules 24-31,
 // poisson_band_rules.h): the extents of a level's block table, the bytes a level takes, the test that its stored nodes fit an int32
-// index, the row and slab tables bd_segment reads, and the bookkeeping of the bytes a call holds.  Plain C++ without a HIP call:
+// index, the row and slab tables bd_segment reads, the bytes of the density structure of rules 32-34 (16 bytes per row for rho_p and
+// s_p, and the node sums dense or in blocks), and the bookkeeping of the bytes a call holds.  Plain C++ without a HIP call:
 // poisson_band.hip uses it, and tests/poisson_band_plan.cpp runs it as a program of its own under the address and undefined-behaviour
 // sanitizers, on block sets of its own and at the extents of depth 10, before anything runs on a device.
 #ifndef MVS_POISSON_BAND_PLAN_H_
@@ -51,6 +52,23 @@ inline int64_t bd_surface_bytes(int64_t stored) {
 // a level that exceeds the device is refused before its arrays are asked for, with the level named.)
 inline int64_t bd_level_bytes(const BdExtent& e, int64_t stored, bool finest) {
     return bd_table_bytes(e) + bd_block_bytes(stored) + (finest ? bd_surface_bytes(stored) : 0);
+}
+
+// Rules 32-34, what the density structure of mvs_poisson_reconstruct_band_density holds from before the base splat until the vertex
+// densities are written, for n rows: 16 bytes per row (rho_p and s_p), the partials of the reduction over the points (24 bytes for
+// each of 1024 workgroups), and the int64 node sums of the density grid of depth Dd — dense, 8 (2^Dd + 1)^3 bytes, when Dd <= B; else
+// in the `stored` blocks of level Dd that a cell of a used point touches: 512 bytes and the packed coordinate per block, and the int32
+// number of every block of the table.  While the blocks are numbered the two work bytes per table entry, the row counts and the row
+// firsts of bd_table_bytes are held too and given back (bd_density_work_bytes).
+inline int64_t bd_density_bytes(int Dd, int B, int64_t stored, int64_t n) {
+    const int64_t rows = 16 * n + 24 * 1024;
+    if (Dd <= B) { const int64_t n1 = ((int64_t)1 << Dd) + 1; return rows + 8 * n1 * n1 * n1; }
+    return rows + 4 * bd_extent(Dd).table + stored * (8 * BP_BLOCK_NODES + 4);
+}
+inline int64_t bd_density_work_bytes(int Dd, int B) {
+    if (Dd <= B) return 0;
+    const BdExtent e = bd_extent(Dd);
+    return 2 * e.table + (2 * e.rows + 1) * 4;
 }
 
 // The row firsts of a level from its row counts: first[r] = the stored blocks in the rows before r (rows in (bz, by) order), first[rows]

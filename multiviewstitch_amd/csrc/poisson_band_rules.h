@@ -7,6 +7,8 @@
 // poisson_band.hip runs it on the device; tests/poisson_band_rules.cpp runs it as a program of its own against
 // tests/ref_poisson_band.py, the numpy / scipy restatement of the whole scheme.  A function that needs to know whether a cell is
 // active, or the value of a coarse node, takes that as a callable: storage is not a rule.
+// For mvs_poisson_reconstruct_band_density it holds rule 32's read: the trilinear density over a lookup that returns 0 where a node of
+// the density grid is not stored (tests/poisson_band_density_rules.cpp against tests/ref_poisson_band_density.py).
 #ifndef MVS_POISSON_BAND_RULES_H_
 #define MVS_POISSON_BAND_RULES_H_
 #include "poisson_rules.h"
@@ -89,5 +91,44 @@ __host__ __device__ inline void bd_edge_state(int G, int ix, int iy, int iz, int
 __host__ __device__ inline int64_t bd_segment(int s, int ly, int lz, int rfirst, int rcnt, int sfirst, int scnt) {
     return (int64_t)16 * sfirst + (int64_t)lz * 4 * scnt + (int64_t)4 * (rfirst - sfirst) + (int64_t)ly * rcnt + (s - rfirst);
 }
+
+// ------------------------------------------------------------------ rules 32-34: the sampling density over the band ----
+// Node (ix, iy, iz) of a level kept in blocks: num[(bz * T + by) * T + bx] is the stored number of block (bx, by, bz) of a table of T
+// entries per axis, -1 for a block that is not stored.  -> the node's place 64 s + lx + 4 ly + 16 lz, or -1
+__host__ __device__ inline int64_t bd_node_slot(const int32_t* num, int T, int ix, int iy, int iz) {
+    const int s = num[((int64_t)(iz >> 2) * T + (iy >> 2)) * T + (ix >> 2)];
+    return s < 0 ? -1 : (int64_t)s * 64 + ((iz & 3) << 4 | (iy & 3) << 2 | (ix & 3));
+}
+
+// rule 32: does the density grid of depth Dd live in blocks (no array over all its nodes), or dense like the base grid of depth B?
+__host__ __device__ inline bool bd_density_in_blocks(int Dd, int B) { return Dd > B; }
+
+// rule 32: the trilinear W of rules 15 and 17 at p over the density grid gd — pn_density_at's corners, weights and order of addition.
+// sum(ix, iy, iz) is the int64 node sum of rule 14, 0 at a node without storage: no used point lies in a cell around such a node, so
+// its sum is 0 and the zero read is exact.
+template <class F>
+__host__ __device__ inline double bd_density_at(const double* p, const PnGrid& gd, F sum) {
+    int i0[3];
+    double w[8], v = 0.0;
+    pn_corners_weights(p, gd, i0, w);
+    for (int c = 0; c < 8; ++c) v = v + w[c] * pn_dequant(sum(i0[0] + (c & 1), i0[1] + (c >> 1 & 1), i0[2] + (c >> 2 & 1)));
+    return v;
+}
+// sum() of bd_density_at over block storage: 64 sums per stored block behind the table of bd_node_slot
+struct BdBlockSums {
+    const int32_t* num;
+    int32_t T;
+    const long long* sums;
+    __host__ __device__ long long operator()(int ix, int iy, int iz) const {
+        const int64_t at = bd_node_slot(num, T, ix, iy, iz);
+        return at < 0 ? 0 : sums[at];
+    }
+};
+// ... and over a dense array in node order
+struct BdDenseSums {
+    int32_t G;
+    const long long* sums;
+    __host__ __device__ long long operator()(int ix, int iy, int iz) const { return sums[pn_node(G, ix, iy, iz)]; }
+};
 
 #endif

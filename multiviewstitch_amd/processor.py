@@ -684,14 +684,22 @@ def PoissonFiles(psr_npts, model_obj, params: L.CPoissonParams | None = None, dp
     ``trim_ratio`` the call is ``mvs_processor_poisson_density``: the normals weighted by the sampling density when ``dparams`` sets
     WEIGHT_NORMALS, the mesh trimmed where its vertex density lies below ``trim_ratio`` times the mean point density.  With ``sparams``
     (``poisson_screen_params``) the call is ``mvs_processor_poisson_screened``: the field pulled to the iso value at every point.
-    With ``bparams`` (``poisson_band_params``) the call is ``mvs_processor_poisson_band``, the band-refined levels up to depth 10; it is
-    unscreened and unweighted, so ``bparams`` together with ``dparams``, ``sparams`` or ``trim_ratio`` raises."""
+    With ``bparams`` (``poisson_band_params``) the call is ``mvs_processor_poisson_band``, the band-refined levels up to depth 10;
+    ``bparams`` with ``dparams`` AND ``trim_ratio`` (0.0: no trim) is ``mvs_processor_poisson_band_density``, those levels weighted and
+    trimmed by the sampling density as above; ``bparams`` with only one of the two raises, as it did before that call existed.  The
+    band levels are unscreened, so ``bparams`` together with ``sparams`` raises."""
     prm = params if params is not None else poisson_params()
     V, F = C.c_int64(), C.c_int64()
     if bparams is not None:
-        if dparams is not None or sparams is not None or trim_ratio is not None:
-            raise L.MvsError(-1, "PoissonFiles: bparams cannot be combined with dparams, sparams or trim_ratio (the band levels are unscreened and unweighted)")
-        L.check(L.lib().mvs_processor_poisson_band(os.fsencode(psr_npts), C.byref(prm), C.byref(bparams), os.fsencode(model_obj), C.byref(V), C.byref(F), None))
+        if sparams is not None:
+            raise L.MvsError(-1, "PoissonFiles: bparams cannot be combined with sparams (the band levels are unscreened)")
+        if (dparams is None) != (trim_ratio is None):
+            raise L.MvsError(-1, "PoissonFiles: bparams with the sampling density needs dparams and trim_ratio together (trim_ratio 0.0: no trim)")
+        if dparams is not None:
+            L.check(L.lib().mvs_processor_poisson_band_density(os.fsencode(psr_npts), C.byref(prm), C.byref(bparams), C.byref(dparams), float(trim_ratio),
+                                                               os.fsencode(model_obj), C.byref(V), C.byref(F), None))
+        else:
+            L.check(L.lib().mvs_processor_poisson_band(os.fsencode(psr_npts), C.byref(prm), C.byref(bparams), os.fsencode(model_obj), C.byref(V), C.byref(F), None))
     elif sparams is not None:
         L.check(L.lib().mvs_processor_poisson_screened(os.fsencode(psr_npts), C.byref(prm), C.byref(dparams) if dparams is not None else None,
                                                        C.byref(sparams), float(trim_ratio or 0.0), os.fsencode(model_obj), C.byref(V), C.byref(F)))
@@ -714,16 +722,11 @@ def _poisson_band_info(binfo: L.CPoissonBandInfo) -> dict:
                 scratch_bytes=binfo.scratch_bytes, base_depth=binfo.base_depth, failed_level=binfo.failed_level)
 
 
-def RunPoissonBand(points, normals, params: L.CPoissonParams | None = None, bparams: L.CPoissonBandParams | None = None,
-                   stream: int | None = None, capacity: tuple | None = None):
-    """``mvs_poisson_reconstruct_band`` (rules 24-31 of include/mvs.h, this library's definition): a dense base level of depth
-    ``bparams.base_depth`` refined level by level on the blocks within ``bparams.band`` blocks of the points, up to depth 10.  Arguments
-    as ``RunPoisson``.  -> (vertices [V, 3] float64, faces [F, 3] int32, info dict as ``RunPoisson``'s — depth, h and iso those of the
-    finest level, cycles and rel_residual those of the base solve —, band info dict: per level (lists indexed by the level)
-    n_active_blocks, n_free, rel_residual, bnorm, iterations; n_open_edges, scratch_bytes, base_depth, failed_level).  When the call
-    fails, the exception carries ``info`` and ``band_info`` as far as they were written."""
-    prm = params if params is not None else poisson_params()
-    bprm = bparams if bparams is not None else poisson_band_params()
+def _run_poisson_band(points, normals, prm, bprm, dprm, stream, capacity):
+    """the call behind ``RunPoissonBand`` (``dprm`` None: mvs_poisson_reconstruct_band) and ``RunPoissonBandDensity``
+    (mvs_poisson_reconstruct_band_density), host or device form
+    -> (vertices, faces, vertex density or None, info struct, band info struct, density info struct or None)"""
+    name = "mvs_poisson_reconstruct_band" if dprm is None else "mvs_poisson_reconstruct_band_density"
     dev = _is_dev(points)
     if dev != _is_dev(normals):
         raise L.MvsError(-1, "points and normals must both be tensors on the GPU or both arrays")
@@ -735,38 +738,55 @@ def RunPoissonBand(points, normals, params: L.CPoissonParams | None = None, bpar
         if tuple(points.shape) != tuple(normals.shape) or points.dim() != 2 or points.shape[1] != 3:
             raise L.MvsError(-1, "points and normals must be [n, 3]")
         pp, pn, n = _dev_ptr(points, "float64", "points"), _dev_ptr(normals, "float64", "normals"), int(points.shape[0])
-        fn, tail = L.lib().mvs_poisson_reconstruct_band_dev, (L.ptr(stream),)
+        fn, tail = getattr(L.lib(), name + "_dev"), (L.ptr(stream),)
     else:
         points, normals = L.arr(points, np.float64).reshape(-1, 3), L.arr(normals, np.float64).reshape(-1, 3)
         if points.shape != normals.shape:
             raise L.MvsError(-1, "points and normals must be [n, 3]")
         pp, pn, n = L.ptr(points), L.ptr(normals), len(points)
-        fn, tail = L.lib().mvs_poisson_reconstruct_band, ()
+        fn, tail = getattr(L.lib(), name), ()
     nothing = np.zeros(3)                                       # a pointer to nothing is still a pointer; the name keeps it alive
     if n == 0:
         pp = pn = L.ptr(nothing)
     if capacity is None:
         dmax = max(0, min(int(prm.depth_max), L.POISSON_BAND_MAX_DEPTH))
         capacity = (12 * 4 ** dmax, 24 * 4 ** dmax)
-    info, binfo = L.CPoissonInfo(), L.CPoissonBandInfo()
+    info, binfo, dinfo = L.CPoissonInfo(), L.CPoissonBandInfo(), None if dprm is None else L.CPoissonDensityInfo()
     with order:
         def call(vcap, fcap):
-            # v and f are named here and returned: the addresses handed to the library stay those of live arrays
+            # v, f and d are named here and returned: the addresses handed to the library stay those of live arrays
             v, f = _out_like(points, (max(1, vcap), 3), "float64"), _out_like(points, (max(1, fcap), 3), "int32")
-            rc = fn(n, pp, pn, C.byref(prm), C.byref(bprm), C.byref(info), C.byref(binfo), L.ptr(v), vcap, L.ptr(f), fcap, *tail)
-            return rc, v, f
+            if dprm is None:
+                return fn(n, pp, pn, C.byref(prm), C.byref(bprm), C.byref(info), C.byref(binfo), L.ptr(v), vcap, L.ptr(f), fcap, *tail), v, f, None
+            d = _out_like(points, (max(1, vcap),), "float64")
+            rc = fn(n, pp, pn, C.byref(prm), C.byref(bprm), C.byref(dprm), C.byref(info), C.byref(binfo), C.byref(dinfo), L.ptr(v), L.ptr(d), vcap,
+                    L.ptr(f), fcap, *tail)
+            return rc, v, f, d
 
         vcap, fcap = int(capacity[0]), int(capacity[1])
-        rc, v, f = call(vcap, fcap)
+        rc, v, f, d = call(vcap, fcap)
         if rc == -1 and (info.n_vertices > vcap or info.n_faces > fcap):
             vcap, fcap = int(info.n_vertices), int(info.n_faces)
-            rc, v, f = call(vcap, fcap)
+            rc, v, f, d = call(vcap, fcap)
     try:
         L.check(rc)
     except L.MvsError as e:
         e.info, e.band_info = _poisson_info(info), _poisson_band_info(binfo)
         raise
-    return v[:info.n_vertices], f[:info.n_faces], _poisson_info(info), _poisson_band_info(binfo)
+    return v[:info.n_vertices], f[:info.n_faces], None if d is None else d[:info.n_vertices], info, binfo, dinfo
+
+
+def RunPoissonBand(points, normals, params: L.CPoissonParams | None = None, bparams: L.CPoissonBandParams | None = None,
+                   stream: int | None = None, capacity: tuple | None = None):
+    """``mvs_poisson_reconstruct_band`` (rules 24-31 of include/mvs.h, this library's definition): a dense base level of depth
+    ``bparams.base_depth`` refined level by level on the blocks within ``bparams.band`` blocks of the points, up to depth 10.  Arguments
+    as ``RunPoisson``.  -> (vertices [V, 3] float64, faces [F, 3] int32, info dict as ``RunPoisson``'s — depth, h and iso those of the
+    finest level, cycles and rel_residual those of the base solve —, band info dict: per level (lists indexed by the level)
+    n_active_blocks, n_free, rel_residual, bnorm, iterations; n_open_edges, scratch_bytes, base_depth, failed_level).  When the call
+    fails, the exception carries ``info`` and ``band_info`` as far as they were written."""
+    v, f, _, info, binfo, _ = _run_poisson_band(points, normals, params if params is not None else poisson_params(),
+                                                bparams if bparams is not None else poisson_band_params(), None, stream, capacity)
+    return v, f, _poisson_info(info), _poisson_band_info(binfo)
 
 
 WEIGHT_NORMALS = 1                          # MVS_POISSON_WEIGHT_NORMALS
@@ -790,6 +810,26 @@ def RunPoissonDensity(points, normals, params: L.CPoissonParams | None = None, d
     out.update(mean_density=dinfo.mean_density, min_point_density=dinfo.min_point_density, max_point_density=dinfo.max_point_density,
                density_depth=dinfo.density_depth, n_clamped=dinfo.n_clamped)
     return v, f, d, out
+
+
+def _poisson_density_info(dinfo: L.CPoissonDensityInfo) -> dict:
+    return dict(mean_density=dinfo.mean_density, min_point_density=dinfo.min_point_density, max_point_density=dinfo.max_point_density,
+                density_depth=dinfo.density_depth, n_clamped=dinfo.n_clamped)
+
+
+def RunPoissonBandDensity(points, normals, params: L.CPoissonParams | None = None, bparams: L.CPoissonBandParams | None = None,
+                          dparams: L.CPoissonDensityParams | None = None, stream: int | None = None, capacity: tuple | None = None):
+    """``mvs_poisson_reconstruct_band_density`` (rules 32-35 of include/mvs.h, this library's definition): ``RunPoissonBand`` with the
+    sampling density carried over every level — the normals of the base level and of every band level weighted by mean density / local
+    density when ``dparams.flags`` holds ``WEIGHT_NORMALS`` (off by default: the mesh is then ``RunPoissonBand``'s) — and the density of
+    every vertex, the values ``TrimByValue`` trims by.  Arguments as ``RunPoisson``.
+    -> (vertices [V, 3] float64, faces [F, 3] int32, vertex_density [V] float64, info dict and band info dict as ``RunPoissonBand``'s,
+    density info dict: mean_density, min_point_density, max_point_density, density_depth, n_clamped).  When the call fails, the
+    exception carries ``info`` and ``band_info`` as far as they were written."""
+    v, f, d, info, binfo, dinfo = _run_poisson_band(points, normals, params if params is not None else poisson_params(),
+                                                    bparams if bparams is not None else poisson_band_params(),
+                                                    dparams if dparams is not None else poisson_density_params(), stream, capacity)
+    return v, f, d, _poisson_info(info), _poisson_band_info(binfo), _poisson_density_info(dinfo)
 
 
 def poisson_screen_params(**kw) -> L.CPoissonScreenParams:

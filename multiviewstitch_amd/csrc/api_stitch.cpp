@@ -420,9 +420,8 @@ static int poisson_files(const char* fn, const char* psr_npts, const mvs_poisson
                       sprm, sprm ? &sinfo : nullptr};
     mvs_poisson_band_info binfo;
     if (bprm) {
-        if (dprm) rc = poisson_band_density_blocks(fn, n, dp.as<double>(), dn.as<double>(), &prm, bprm, dprm, &info, &binfo, &dinfo, &dv, &dd, &df);
-        else rc = poisson_band_blocks(fn, n, dp.as<double>(), dn.as<double>(), &prm, bprm, &info, &binfo, &dv, &df);
-        if (rc) return rc;
+        const BdCall band{fn, n, dp.as<double>(), dn.as<double>(), &prm, bprm, &info, &binfo, dprm, dprm ? &dinfo : nullptr, dprm != nullptr};
+        if ((rc = poisson_band_blocks(band, &dv, &dd, &df))) return rc;
         if (open_out) *open_out = binfo.n_open_edges;
     } else if ((rc = poisson_blocks(call, &dv, &dd, &df))) return rc;
     int64_t V = info.n_vertices, F = info.n_faces;

@@ -16,27 +16,29 @@
 //   k_mg_residual<Op> (out == NULL) / k_pn_fold
 //                      the true residual's squared norm: partials per workgroup, folded by one workgroup in a fixed order
 //   k_pn_iso           rule 9, the same two-step reduction
-//   k_pn_cubemask      rule 10: the inside bits of a cube's eight corners, one byte per cube
-//   k_pn_edge_count / k_pn_vertex_scatter, k_pn_face_count / k_pn_face_scatter
-//                      rules 11-12: two ordered compactions (wg_rank per workgroup of 256 items; k_pn_scan_rows / _totals / _add scan the
-//                      millions of counts in two levels).  The edge flags stay behind as a bitmap, 64 flags per word: a face finds the
-//                      number of a vertex as base[workgroup] + popcounts, no edge map is stored.
+//   k_pn_cubemask<S> / k_pn_edge_count<S> / k_pn_vertex_scatter<S> / k_pn_face_scatter<S> (poisson_surface.h), k_pn_face_count
+//                      rules 10-12 over a surface view, here PnDenseSurf: the cube masks and two ordered compactions, described there.
+//                      k_pn_scan_rows / _totals / _add (PnScan) scan the millions of counts in two levels.
 // mvs_poisson_reconstruct_density adds the sampling density (rules 14-17; the trim of rule 18 is mesh_trim.hip):
-//   k_pn_density_splat rule 14: a thread per point, 8 int64 atomic adds into the node sums of the coarser density grid
-//   k_pn_point_density rule 15: rho_p per row; min, max and the int64 sum of the quantised densities per workgroup (order-free)
+//   k_pn_density_splat<Sums> rule 14: a thread per point, 8 int64 atomic adds into the node sums of the coarser density grid
+//   k_pn_point_density<Sums> rule 15: rho_p per row; min, max and the int64 sum of the quantised densities per workgroup (order-free)
 //   k_pn_gain          rule 16: s_p per row and the rows cut at max_gain; k_pn_splat<true> is the splat of the scaled normals
-//   k_pn_vertex_density rule 17, over the vertex list the scatter wrote
+//   k_pn_vertex_density<Sums> rule 17, over the vertex list the scatter wrote
+//                      Sums: how the node sums are stored, BdDenseSums here; the band levels (poisson_band.hip) run the same three
+//                      kernels over BdBlockSums too, through poisson_density_rows and poisson_vertex_density
 // mvs_poisson_reconstruct_screened adds the second, screened solve (rules 19-23): the k_sc_* kernels build the stencil rows and the right
 // side, described where they stand; the solve is the multigrid above with MgScreened, its smoother on the launched levels
 // k_mg_smooth<MgPlain> followed by k_sc_smooth_rows over the rows.
-// The reductions fold through wg_fold (shuffles, then the waves in order).  Nothing but the integer atomics of the splats and the bitmap
+// The reductions fold through wg_fold of poisson_dev.h (shuffles, then the waves in order).  Nothing but the integer atomics of the splats and the bitmap
 // is unordered: two runs give the same bytes (tests/test_gpu_poisson_bits.py holds a build to recorded ones).
 // The host side: PnCall (stitch.h) is the record of a call, whichever entry made it; PnRun its state on the device; reconstruct the device
-// form of every entry and reconstruct_host the host form; the test hooks of include/mvs_test.h drive PnRun step by step.
+// form of every entry and reconstruct_host the host form; the test hooks of include/mvs_test.h drive PnRun step by step.  What
+// poisson_band.hip shares — the scan, the fold, the face count, the density of rules 14-17, the tail of a call — is declared in poisson_base.h.
 #include "engine.h"
 #include "trace.h"
 #include "frontend_dev.h"
-#include "poisson_rules.h"
+#include "poisson_dev.h"
+#include "poisson_surface.h"
 #include "knobs.h"
 #include "stitch.h"
 #include "poisson_base.h"
@@ -46,32 +48,11 @@
 
 namespace {
 
-constexpr int PN_TPB = 256, PN_WAVES = PN_TPB / 64;
 constexpr int PN_RED_NB = 1024;          // workgroups of a reduction over the points
 constexpr int PN_ZC = 16;                // planes a thread of the smoother marches through
 constexpr int PN_COARSE = 5;             // levels up to this one (33^3 nodes) run inside k_mg_coarse
 constexpr int PN_COARSE_TPB = 1024;
 constexpr int PN_MAX_D = MVS_POISSON_MAX_DEPTH;
-
-// v folded over the workgroup by op (tid: the thread's linear index; s_part: WAVES entries of LDS that nothing else uses), in a fixed
-// order: shuffles inside a wave, then zero op wave 0 op wave 1 ... in thread 0, the only thread the result is valid in
-template <int WAVES, class T, class Op>
-__device__ inline T wg_fold(T v, T zero, T* s_part, int tid, Op op) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_down(v, o, 64));
-    if ((tid & 63) == 0) s_part[tid >> 6] = v;
-    __syncthreads();
-    T t = zero;
-    if (tid == 0)
-        for (int q = 0; q < WAVES; ++q) t = op(t, s_part[q]);
-    return t;
-}
-struct FoldAdd { template <class T> __device__ T operator()(T a, T b) const { return a + b; } };
-struct FoldMin { __device__ double operator()(double a, double b) const { return fmin(a, b); } };
-struct FoldMax { __device__ double operator()(double a, double b) const { return fmax(a, b); } };
-// the sum of a double: its order is part of the result's bytes
-template <int WAVES>
-__device__ inline double wg_sum(double v, double* s_part, int tid) { return wg_fold<WAVES>(v, 0.0, s_part, tid, FoldAdd()); }
 
 // ------------------------------------------------------------------ rules 1-3 ----
 __global__ __launch_bounds__(PN_TPB) void k_pn_bbox(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm, double* __restrict__ part) {
@@ -140,23 +121,29 @@ __global__ __launch_bounds__(PN_TPB) void k_pn_splat(int64_t n, const double* __
 }
 
 // ------------------------------------------------------------------ rules 14-17 ----
+// The node sums of the density grid are read and written through Sums, BdDenseSums (node order) or BdBlockSums (the stored blocks of a
+// band level, rule 32; a node without storage reads as 0) of poisson_band_rules.h: the dense call instantiates the first only.
 // rule 14: a thread per point, 8 int64 atomic adds into the node sums of the density grid
-__global__ __launch_bounds__(PN_TPB) void k_pn_density_splat(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm, PnGrid gd,
+template <class Sums>
+__global__ __launch_bounds__(PN_TPB) void k_pn_density_splat(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm, PnGrid gd, Sums d,
                                                              unsigned long long* __restrict__ dsum) {
     const int64_t i = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
     if (i >= n || !pn_used(pts + 3 * i, nrm + 3 * i)) return;
     int i0[3];
     double w[8];
     pn_corners_weights(pts + 3 * i, gd, i0, w);
-    for (int c = 0; c < 8; ++c)
-        atomicAdd(dsum + pn_corner_node(gd.G, i0, c), (unsigned long long)pn_quant(w[c]));
+    for (int c = 0; c < 8; ++c) {
+        const int64_t at = d.slot(i0[0] + (c & 1), i0[1] + (c >> 1 & 1), i0[2] + (c >> 2 & 1));
+        if (!Sums::dense && at < 0) continue;                                // rule 32: cannot be, the block of the point's cell is marked
+        atomicAdd(dsum + at, (unsigned long long)pn_quant(w[c]));
+    }
 }
 
 // rule 15: rho_p of every row (0 for a row that is not used) and, per workgroup, the min, the max and the int64 sum of the quantised
 // densities of its used rows — all three order-free; the host finishes.  part_d[2 b] = min, [2 b + 1] = max, part_q[b] = the sum.
-__global__ __launch_bounds__(PN_TPB) void k_pn_point_density(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm, PnGrid gd,
-                                                             const long long* __restrict__ dsum, double* __restrict__ rho,
-                                                             double* __restrict__ part_d, long long* __restrict__ part_q) {
+template <class Sums>
+__global__ __launch_bounds__(PN_TPB) void k_pn_point_density(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm, PnGrid gd, Sums d,
+                                                             double* __restrict__ rho, double* __restrict__ part_d, long long* __restrict__ part_q) {
     __shared__ double s_lo[PN_WAVES], s_hi[PN_WAVES];
     __shared__ long long s_q[PN_WAVES];
     double lo = HUGE_VAL, hi = -HUGE_VAL;
@@ -164,7 +151,7 @@ __global__ __launch_bounds__(PN_TPB) void k_pn_point_density(int64_t n, const do
     for (int64_t i = (int64_t)blockIdx.x * PN_TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * PN_TPB) {
         double r = 0.0;
         if (pn_used(pts + 3 * i, nrm + 3 * i)) {
-            r = pn_density_at(pts + 3 * i, gd, dsum);
+            r = bd_density_at(pts + 3 * i, gd, d);
             lo = fmin(lo, r);
             hi = fmax(hi, r);
             q += pn_rho_quant(r);
@@ -200,12 +187,12 @@ __global__ __launch_bounds__(PN_TPB) void k_pn_gain(int64_t n, const double* __r
 }
 
 // rule 17: over the vertex list the scatter wrote
-__global__ __launch_bounds__(PN_TPB) void k_pn_vertex_density(int64_t nv, const double* __restrict__ vertices, PnGrid gd,
-                                                              const long long* __restrict__ dsum, double* __restrict__ out) {
+template <class Sums>
+__global__ __launch_bounds__(PN_TPB) void k_pn_vertex_density(int64_t nv, const double* __restrict__ vertices, PnGrid gd, Sums d, double* __restrict__ out) {
     const int64_t v = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
     if (v >= nv) return;
     const double* p = vertices + 3 * v;
-    out[v] = isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]) ? pn_density_at(p, gd, dsum) : NAN;      // a cell needs a finite position
+    out[v] = isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]) ? bd_density_at(p, gd, d) : NAN;      // a cell needs a finite position
 }
 
 __global__ __launch_bounds__(PN_TPB) void k_pn_rhs(PnGrid g, const long long* __restrict__ sums, double* __restrict__ b) {
@@ -387,12 +374,10 @@ __global__ __launch_bounds__(PN_TPB) void k_mg_residual(int G, const double* __r
     if (threadIdx.x == 0 && threadIdx.y == 0) part[((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = t;
 }
 
-// the sum of n partials by ONE workgroup: thread t takes t, t + 256, ... in ascending order, then wg_sum
+// the sum of n partials by ONE workgroup, in the order of wg_sum_partials
 __global__ __launch_bounds__(PN_TPB) void k_pn_fold(const double* __restrict__ part, int n, double* __restrict__ out) {
     __shared__ double s_part[PN_WAVES];
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < n; i += PN_TPB) acc += part[i];
-    const double t = wg_sum<PN_WAVES>(acc, s_part, threadIdx.x);
+    const double t = wg_sum_partials(part, n, s_part);
     if (threadIdx.x == 0) *out = t;
 }
 
@@ -653,15 +638,7 @@ __global__ __launch_bounds__(PN_TPB) void k_pn_iso(int64_t n, const double* __re
 }
 
 // ------------------------------------------------------------------ rules 10-12 ----
-__global__ __launch_bounds__(PN_TPB) void k_pn_cubemask(int G, const double* __restrict__ chi, double iso, uint8_t* __restrict__ mask) {
-    const int64_t cube = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
-    if (cube >= (int64_t)G * G * G) return;
-    const int i0[3] = {(int)(cube % G), (int)(cube / G % G), (int)(cube / ((int64_t)G * G))};
-    int m = 0;
-    for (int c = 0; c < 8; ++c) m |= (chi[pn_corner_node(G, i0, c)] < iso ? 1 : 0) << c;
-    mask[cube] = (uint8_t)m;
-}
-
+// The kernels are poisson_surface.h's over PnDenseSurf; what stays here serves the band levels too (PnScan, poisson_face_count).
 // The scan between a count and a scatter kernel, in two levels: the compactions here have millions of workgroups, too many for the one
 // workgroup of compact.hip's tail.  A workgroup scans PN_SCAN_CH counts into its own row of `local` (CH + 1 entries, the last one the
 // row's total), one workgroup scans the totals, and the third launch adds the two: base[b] = survivors in the workgroups before b,
@@ -683,105 +660,11 @@ __global__ __launch_bounds__(PN_TPB) void k_pn_scan_add(const int32_t* __restric
     if (i == nb) base[nb] = rbase[rows];
 }
 
-// edge item r = node * 7 + type: is it a crossed edge of the grid?
-__device__ inline bool pn_edge_crossed(int G, const double* __restrict__ chi, double iso, int64_t r, int64_t items) {
-    if (r >= items) return false;
-    const int n1 = G + 1, type = (int)(r % 7);
-    const int64_t node = r / 7;
-    const int i0[3] = {(int)(node % n1), (int)(node / n1 % n1), (int)(node / ((int64_t)n1 * n1))};
-    if (!pn_edge_in_grid(G, i0[0], i0[1], i0[2], type)) return false;
-    return (chi[node] < iso) != (chi[pn_corner_node(G, i0, pn_type_mask(type))] < iso);
-}
-
-__global__ __launch_bounds__(PN_TPB) void k_pn_edge_count(int G, const double* __restrict__ chi, double iso, int64_t items,
-                                                          unsigned long long* __restrict__ words, int32_t* __restrict__ cnt) {
-    __shared__ int s_wsum[PN_WAVES];
-    const int64_t r = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
-    const bool f = pn_edge_crossed(G, chi, iso, r, items);
-    const unsigned long long bal = __ballot(f);
-    if ((threadIdx.x & 63) == 0) words[r >> 6] = bal;
-    const WgRank k = wg_rank<PN_WAVES>(f, s_wsum);
-    if (threadIdx.x == 0) cnt[blockIdx.x] = k.total;
-}
-
-// the number of the vertex on edge item r (a set flag): the survivors of the workgroups before its own, then popcounts
-__device__ inline int32_t pn_vertex_index(const unsigned long long* __restrict__ words, const int32_t* __restrict__ base, int64_t r) {
-    const int64_t blk = r >> 8, w = r >> 6;
-    int32_t acc = base[blk];
-    for (int64_t q = blk * PN_WAVES; q < w; ++q) acc += __popcll(words[q]);
-    return acc + __popcll(words[w] & ((1ull << (r & 63)) - 1ull));
-}
-
-__device__ inline void pn_node_pos(const PnGrid& g, int ix, int iy, int iz, double* p) {
-    p[0] = g.o[0] + g.h * (double)ix; p[1] = g.o[1] + g.h * (double)iy; p[2] = g.o[2] + g.h * (double)iz;
-}
-
-__global__ __launch_bounds__(PN_TPB) void k_pn_vertex_scatter(PnGrid g, const double* __restrict__ chi, double iso, int64_t items,
-                                                              const unsigned long long* __restrict__ words, const int32_t* __restrict__ base,
-                                                              double* __restrict__ vertices) {
-    __shared__ int s_wsum[PN_WAVES];
-    const int64_t r = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
-    const bool f = (words[r >> 6] >> (r & 63)) & 1ull;                       // the bitmap covers whole workgroups
-    const int64_t pos = (int64_t)base[blockIdx.x] + wg_rank<PN_WAVES>(f, s_wsum).rank;
-    if (!f) return;
-    const int n1 = g.G + 1, m = pn_type_mask((int)(r % 7));
-    const int64_t node = r / 7;
-    const int ix = (int)(node % n1), iy = (int)(node / n1 % n1), iz = (int)(node / ((int64_t)n1 * n1));
-    const int jx = ix + (m & 1), jy = iy + (m >> 1 & 1), jz = iz + (m >> 2 & 1);
-    const double vl = chi[node], vh = chi[pn_node(g.G, jx, jy, jz)];
-    double pl[3], ph[3], out[3];
-    pn_node_pos(g, ix, iy, iz, pl);
-    pn_node_pos(g, jx, jy, jz, ph);
-    if (vl < iso) pn_vertex(vl, vh, pl, ph, iso, out); else pn_vertex(vh, vl, ph, pl, iso, out);
-    for (int a = 0; a < 3; ++a) vertices[3 * pos + a] = out[a];
-}
-
-// face item r = (cube * 6 + tetrahedron) * 2 + slot: the inside bits of the tetrahedron's corners, or -1 when the slot is empty
-__device__ inline int pn_face_item(const uint8_t* __restrict__ mask, int64_t r, int64_t items) {
-    if (r >= items) return -1;
-    const int cm = mask[r / 12];
-    if (cm == 0 || cm == 255) return -1;
-    const int k = (int)(r % 12) >> 1, slot = (int)(r & 1);
-    int in = 0;
-    for (int i = 0; i < 4; ++i) in |= (cm >> pn_tet_corner(k, i) & 1) << i;
-    const int ni = __popc(in);
-    return (slot == 0 ? ni >= 1 && ni <= 3 : ni == 2) ? in : -1;
-}
-
 __global__ __launch_bounds__(PN_TPB) void k_pn_face_count(const uint8_t* __restrict__ mask, int64_t items, int32_t* __restrict__ cnt) {
     __shared__ int s_wsum[PN_WAVES];
     const int64_t r = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
     const WgRank k = wg_rank<PN_WAVES>(pn_face_item(mask, r, items) >= 0, s_wsum);
     if (threadIdx.x == 0) cnt[blockIdx.x] = k.total;
-}
-
-__global__ __launch_bounds__(PN_TPB) void k_pn_face_scatter(int G, const uint8_t* __restrict__ mask, int64_t items,
-                                                            const unsigned long long* __restrict__ words, const int32_t* __restrict__ vbase,
-                                                            const double* __restrict__ vertices, const int32_t* __restrict__ fbase,
-                                                            int32_t* __restrict__ faces) {
-    __shared__ int s_wsum[PN_WAVES];
-    const int64_t r = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
-    const int in = pn_face_item(mask, r, items);
-    const int64_t pos = (int64_t)fbase[blockIdx.x] + wg_rank<PN_WAVES>(in >= 0, s_wsum).rank;
-    if (in < 0) return;
-    const int64_t cube = r / 12;
-    const int k = (int)(r % 12) >> 1, slot = (int)(r & 1);
-    const int i0[3] = {(int)(cube % G), (int)(cube / G % G), (int)(cube / ((int64_t)G * G))};
-    int ci[4], co[4];
-    const int n = pn_tet_cycle(in, ci, co);
-    int32_t idx[4];
-    double pos3[4][3], d[3];
-    for (int q = 0; q < n; ++q) {
-        int nm, type;
-        pn_tet_edge(k, ci[q], co[q], &nm, &type);
-        idx[q] = pn_vertex_index(words, vbase, pn_corner_node(G, i0, nm) * 7 + type);
-        for (int a = 0; a < 3; ++a) pos3[q][a] = vertices[3 * (int64_t)idx[q] + a];
-    }
-    pn_tet_dir(k, in, d);
-    pn_polygon(n, idx, pos3, d);
-    faces[3 * pos] = idx[0];
-    faces[3 * pos + 1] = idx[slot ? 2 : 1];
-    faces[3 * pos + 2] = idx[slot ? 3 : 2];
 }
 
 // ------------------------------------------------------------------ host ----
@@ -843,22 +726,7 @@ struct PnRun {
     int64_t nnd = 0;                      // nodes of the density grid
     Scratch dsum, rho, gain, dpart;
     const double* row_gain = nullptr;     // s_p per row from outside (PnBaseField::solve for the band levels): rule 16's splat without dp
-    struct Scan {                         // counts, their scan and its two levels, for nb workgroups
-        Scratch cnt, base, local, tot, rbase;
-        int alloc(size_t nb, hipStream_t s) {
-            const size_t rows = (nb + PN_SCAN_CH - 1) / PN_SCAN_CH;
-            int rc;
-            if ((rc = cnt.alloc(4 * nb, s)) || (rc = base.alloc(4 * (nb + 1), s)) || (rc = local.alloc(4 * rows * (PN_SCAN_CH + 1), s)) ||
-                (rc = tot.alloc(4 * rows, s))) return rc;
-            return rbase.alloc(4 * (rows + 1), s);
-        }
-        void run(int nb, hipStream_t s) {
-            const int rows = (nb + PN_SCAN_CH - 1) / PN_SCAN_CH;
-            k_pn_scan_rows<<<dim3((unsigned)rows), dim3(PN_TPB), 0, s>>>(cnt.as<int32_t>(), nb, local.as<int32_t>(), tot.as<int32_t>());
-            k_pn_scan_totals<<<dim3(1), dim3(PN_TPB), 0, s>>>(tot.as<int32_t>(), rows, rbase.as<int32_t>());
-            k_pn_scan_add<<<dim3((unsigned)(nb / PN_TPB + 1)), dim3(PN_TPB), 0, s>>>(local.as<int32_t>(), rbase.as<int32_t>(), nb, rows, base.as<int32_t>());
-        }
-    } ve, fa;
+    PnScan ve, fa;
     // rules 19-23 (mvs_poisson_reconstruct_screened): absent for the other calls
     const mvs_poisson_screen_params* sp = nullptr;
     mvs_poisson_screen_info* sinfo = nullptr;
@@ -866,7 +734,7 @@ struct PnRun {
     Scratch sc_flag, sc_idx[PN_MAX_D + 1], sc_tab[PN_MAX_D + 1], sc_node[PN_MAX_D + 1];   // sc_node[l][row] = the row's node
     ScLevels Sc{};
     int64_t sc_rows[PN_MAX_D + 1] = {};   // nodes with a stencil row, per level
-    Scan sn;
+    PnScan sn;
     PnLevels L{};
     double iso = 0.0;
     int64_t edge_items = 0, face_items = 0;
@@ -1068,50 +936,16 @@ struct PnRun {
         gd = pn_density_grid(g, side, info.depth, dp->density_drop, &Dd);
         nnd = (int64_t)(gd.G + 1) * (gd.G + 1) * (gd.G + 1);
         dinfo->density_depth = Dd;
-        const int nb = (int)std::min<int64_t>(PN_RED_NB, (n + PN_TPB - 1) / PN_TPB);
         if ((rc = dsum.alloc(8 * (size_t)nnd, s)) || (rc = rho.alloc(8 * (size_t)n, s)) || (rc = gain.alloc(8 * (size_t)n, s)) ||
             (rc = dpart.alloc(24 * (size_t)PN_RED_NB, s))) return rc;
-        double* part_d = dpart.as<double>();
-        long long* part_q = dpart.as<long long>() + 2 * PN_RED_NB;
         HIPCHK(hipMemsetAsync(dsum.p, 0, 8 * (size_t)nnd, s));
-        k_pn_density_splat<<<dim3((unsigned)((n + PN_TPB - 1) / PN_TPB)), dim3(PN_TPB), 0, s>>>(n, pts, nrm, gd, dsum.as<unsigned long long>());
-        k_pn_point_density<<<dim3((unsigned)nb), dim3(PN_TPB), 0, s>>>(n, pts, nrm, gd, dsum.as<long long>(), rho.as<double>(), part_d, part_q);
-        HIPCHK(hipGetLastError());
-        std::vector<double> hd((size_t)2 * nb);
-        std::vector<long long> hq((size_t)nb);
-        HIPCHK(hipMemcpyAsync(hd.data(), part_d, 16 * (size_t)nb, hipMemcpyDeviceToHost, s));
-        if ((rc = fetch(hq.data(), part_q, 8 * (size_t)nb))) return rc;
-        double lo = HUGE_VAL, hi = -HUGE_VAL;
-        long long q = 0;
-        for (int b = 0; b < nb; ++b) { lo = std::fmin(lo, hd[2 * b]); hi = std::fmax(hi, hd[2 * b + 1]); q += hq[b]; }
-        dinfo->mean_density = pn_rho_mean(q, info.n_used);
-        dinfo->min_point_density = lo;
-        dinfo->max_point_density = hi;
-        return gains(n, pts, nrm, rho.as<double>(), dinfo->mean_density, dp->max_gain, gain.as<double>(), dpart.as<int32_t>(), &dinfo->n_clamped, s);
+        return poisson_density_rows(n, pts, nrm, density_sums(), info.n_used, dp->max_gain, rho.as<double>(), gain.as<double>(), dpart, dinfo, s);
     }
-
-    // rule 16: s_p of every row and the count of the used rows cut at max_gain; part_c: PN_RED_NB int32 on the device
-    static int gains(int64_t n, const double* pts, const double* nrm, const double* rho, double rho_mean, double max_gain, double* gain,
-                     int32_t* part_c, int32_t* n_clamped, hipStream_t s) {
-        const int nb = (int)std::min<int64_t>(PN_RED_NB, (n + PN_TPB - 1) / PN_TPB);
-        k_pn_gain<<<dim3((unsigned)nb), dim3(PN_TPB), 0, s>>>(n, pts, nrm, rho, rho_mean, max_gain, gain, part_c);
-        HIPCHK(hipGetLastError());
-        std::vector<int32_t> hc((size_t)nb);
-        HIPCHK(hipMemcpyAsync(hc.data(), part_c, 4 * (size_t)nb, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        *n_clamped = 0;
-        for (int b = 0; b < nb; ++b) *n_clamped += hc[b];
-        return MVS_OK;
-    }
+    PnDensitySums density_sums() const { return PnDensitySums{gd, nullptr, 0, dsum.as<long long>()}; }
 
     // rule 17, after scatter
     int vertex_density(const double* vertices, double* out) {
-        if (!out || info.n_vertices == 0) return MVS_OK;
-        k_pn_vertex_density<<<dim3((unsigned)((info.n_vertices + PN_TPB - 1) / PN_TPB)), dim3(PN_TPB), 0, s>>>(info.n_vertices, vertices, gd,
-                                                                                                              dsum.as<long long>(), out);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(s));
-        return MVS_OK;
+        return out && info.n_vertices > 0 ? poisson_vertex_density(info.n_vertices, vertices, density_sums(), out, s) : MVS_OK;
     }
 
     // rule 9
@@ -1127,19 +961,20 @@ struct PnRun {
         return MVS_OK;
     }
 
+    PnDenseSurf surf() const { return PnDenseSurf{g, L.x[info.depth], iso}; }
+
     // rules 10-12 up to the counts
     int count() {
         int rc;
-        const int G = g.G;
-        const double* chi = L.x[info.depth];
-        const int64_t cubes = (int64_t)G * G * G;
-        edge_items = 7 * nn;
+        const PnDenseSurf q = surf();
+        const int64_t cubes = q.cube_items();
+        edge_items = 7 * q.node_items();
         face_items = 12 * cubes;
         const int64_t nbe = (edge_items + PN_TPB - 1) / PN_TPB, nbf = (face_items + PN_TPB - 1) / PN_TPB;
         if ((rc = mask.alloc((size_t)cubes, s)) || (rc = words.alloc(sizeof(unsigned long long) * PN_WAVES * (size_t)nbe, s)) ||
             (rc = ve.alloc((size_t)nbe, s)) || (rc = fa.alloc((size_t)nbf, s))) return rc;
-        k_pn_cubemask<<<dim3((unsigned)((cubes + PN_TPB - 1) / PN_TPB)), dim3(PN_TPB), 0, s>>>(G, chi, iso, mask.as<uint8_t>());
-        k_pn_edge_count<<<dim3((unsigned)nbe), dim3(PN_TPB), 0, s>>>(G, chi, iso, edge_items, words.as<unsigned long long>(), ve.cnt.as<int32_t>());
+        k_pn_cubemask<<<dim3((unsigned)((cubes + PN_TPB - 1) / PN_TPB)), dim3(PN_TPB), 0, s>>>(q, mask.as<uint8_t>());
+        k_pn_edge_count<<<dim3((unsigned)nbe), dim3(PN_TPB), 0, s>>>(q, edge_items, words.as<unsigned long long>(), ve.cnt.as<int32_t>());
         ve.run((int)nbe, s);
         k_pn_face_count<<<dim3((unsigned)nbf), dim3(PN_TPB), 0, s>>>(mask.as<uint8_t>(), face_items, fa.cnt.as<int32_t>());
         fa.run((int)nbf, s);
@@ -1155,9 +990,9 @@ struct PnRun {
     int scatter(double* vertices, int32_t* faces) {
         if (info.n_vertices == 0) return MVS_OK;
         const int64_t nbe = (edge_items + PN_TPB - 1) / PN_TPB, nbf = (face_items + PN_TPB - 1) / PN_TPB;
-        k_pn_vertex_scatter<<<dim3((unsigned)nbe), dim3(PN_TPB), 0, s>>>(g, L.x[info.depth], iso, edge_items, words.as<unsigned long long>(),
-                                                                        ve.base.as<int32_t>(), vertices);
-        k_pn_face_scatter<<<dim3((unsigned)nbf), dim3(PN_TPB), 0, s>>>(g.G, mask.as<uint8_t>(), face_items, words.as<unsigned long long>(),
+        const PnDenseSurf q = surf();
+        k_pn_vertex_scatter<<<dim3((unsigned)nbe), dim3(PN_TPB), 0, s>>>(q, edge_items, words.as<unsigned long long>(), ve.base.as<int32_t>(), vertices);
+        k_pn_face_scatter<<<dim3((unsigned)nbf), dim3(PN_TPB), 0, s>>>(q, mask.as<uint8_t>(), face_items, words.as<unsigned long long>(),
                                                                       ve.base.as<int32_t>(), vertices, fa.base.as<int32_t>(), faces);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(s));
@@ -1244,30 +1079,12 @@ struct PnRun {
     }
 };
 
-// Where a call writes, on the device: the caller's arrays of vcap and fcap rows (density NULL: not wanted), or — bv set — blocks that
-// are sized once the counts are known (bd NULL: no density).
-struct PnOut {
-    double *vertices, *density;
-    int32_t* faces;
-    int64_t vcap, fcap;
-    Scratch *bv, *bd, *bf;
-};
-
 // The device form of every entry, after its checks: the counts, the capacity test, the scatter and the vertex densities.
 int reconstruct(const PnCall& c, const double* pts_dev, const double* nrm_dev, PnOut o, hipStream_t s) {
     int rc;
     PnRun run(c, pts_dev, nrm_dev, s);
     if ((rc = run.counts(c.fn))) return rc;
-    const int64_t V = c.info->n_vertices, F = c.info->n_faces;
-    if (V > o.vcap || F > o.fcap) return bad(c.fn, "a capacity is below the count (info holds n_vertices and n_faces)");
-    if (o.bv) {
-        if ((rc = o.bv->alloc(24 * (size_t)V)) || (rc = o.bf->alloc(12 * (size_t)F)) || (o.bd && (rc = o.bd->alloc(8 * (size_t)V)))) return rc;
-        o.vertices = o.bv->as<double>();
-        o.faces = o.bf->as<int32_t>();
-        o.density = o.bd ? o.bd->as<double>() : nullptr;
-    }
-    if ((rc = run.scatter(o.vertices, o.faces))) return rc;
-    return run.vertex_density(o.vertices, o.density);
+    return poisson_finish(c.fn, run, *c.info, o);
 }
 
 // what every entry opens with
@@ -1309,11 +1126,73 @@ int poisson_check_plain(const PnCall& c, int max_depth, const void* out_a, int64
 
 int poisson_check_density(const char* fn, int64_t n, const mvs_poisson_density_params* dp, const void* dinfo) { return check_pn_density(fn, n, dp, dinfo); }
 
-int poisson_gains(int64_t n, const double* pts_dev, const double* nrm_dev, const double* rho_dev, double rho_mean, double max_gain, double* gain_dev,
-                  int32_t* n_clamped, hipStream_t s) {
-    Scratch part_c;
-    const int rc = part_c.alloc(4 * (size_t)PN_RED_NB, s);
-    return rc ? rc : PnRun::gains(n, pts_dev, nrm_dev, rho_dev, rho_mean, max_gain, gain_dev, part_c.as<int32_t>(), n_clamped, s);
+// PnScan: counts, their scan and its two levels
+int PnScan::alloc(size_t nb, hipStream_t s) {
+    const size_t rows = (nb + PN_SCAN_CH - 1) / PN_SCAN_CH;
+    int rc;
+    bytes = (int64_t)(4 * nb + 4 * (nb + 1) + 4 * rows * (PN_SCAN_CH + 1) + 4 * rows + 4 * (rows + 1));
+    if ((rc = cnt.alloc(4 * nb, s)) || (rc = base.alloc(4 * (nb + 1), s)) || (rc = local.alloc(4 * rows * (PN_SCAN_CH + 1), s)) ||
+        (rc = tot.alloc(4 * rows, s))) return rc;
+    return rbase.alloc(4 * (rows + 1), s);
+}
+void PnScan::run(int nb, hipStream_t s) {
+    const int rows = (nb + PN_SCAN_CH - 1) / PN_SCAN_CH;
+    k_pn_scan_rows<<<dim3((unsigned)rows), dim3(PN_TPB), 0, s>>>(cnt.as<int32_t>(), nb, local.as<int32_t>(), tot.as<int32_t>());
+    k_pn_scan_totals<<<dim3(1), dim3(PN_TPB), 0, s>>>(tot.as<int32_t>(), rows, rbase.as<int32_t>());
+    k_pn_scan_add<<<dim3((unsigned)(nb / PN_TPB + 1)), dim3(PN_TPB), 0, s>>>(local.as<int32_t>(), rbase.as<int32_t>(), nb, rows, base.as<int32_t>());
+}
+
+void poisson_fold(const double* part_dev, int n, double* out_dev, hipStream_t s) { k_pn_fold<<<dim3(1), dim3(PN_TPB), 0, s>>>(part_dev, n, out_dev); }
+
+void poisson_face_count(const uint8_t* mask_dev, int64_t items, int32_t* cnt_dev, hipStream_t s) {
+    k_pn_face_count<<<dim3((unsigned)((items + PN_TPB - 1) / PN_TPB)), dim3(PN_TPB), 0, s>>>(mask_dev, items, cnt_dev);
+}
+
+// f(the accessor of d's storage): the one run-time choice between the two instantiations of the density kernels
+template <class F>
+static void with_sums(const PnDensitySums& d, F f) {
+    if (d.num) f(BdBlockSums{d.num, d.T, d.sums});
+    else f(BdDenseSums{d.g.G, d.sums});
+}
+
+int poisson_density_rows(int64_t n, const double* pts, const double* nrm, const PnDensitySums& d, int64_t n_used, double max_gain, double* rho,
+                         double* gain, Scratch& part, mvs_poisson_density_info* dinfo, hipStream_t s) {
+    const int nb = (int)std::min<int64_t>(PN_RED_NB, (n + PN_TPB - 1) / PN_TPB);
+    double* part_d = part.as<double>();
+    long long* part_q = part.as<long long>() + 2 * PN_RED_NB;
+    with_sums(d, [&](auto sums) {
+        k_pn_density_splat<<<dim3((unsigned)((n + PN_TPB - 1) / PN_TPB)), dim3(PN_TPB), 0, s>>>(n, pts, nrm, d.g, sums, (unsigned long long*)d.sums);
+        k_pn_point_density<<<dim3((unsigned)nb), dim3(PN_TPB), 0, s>>>(n, pts, nrm, d.g, sums, rho, part_d, part_q);
+    });
+    HIPCHK(hipGetLastError());
+    std::vector<double> hd((size_t)2 * nb);
+    std::vector<long long> hq((size_t)nb);
+    HIPCHK(hipMemcpyAsync(hd.data(), part_d, 16 * (size_t)nb, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(hq.data(), part_q, 8 * (size_t)nb, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    double lo = HUGE_VAL, hi = -HUGE_VAL;
+    long long q = 0;
+    for (int b = 0; b < nb; ++b) { lo = std::fmin(lo, hd[2 * b]); hi = std::fmax(hi, hd[2 * b + 1]); q += hq[b]; }
+    dinfo->mean_density = pn_rho_mean(q, n_used);
+    dinfo->min_point_density = lo;
+    dinfo->max_point_density = hi;
+    // rule 16: s_p of every row and the count of the used rows cut at max_gain; the partials above are spent
+    int32_t* part_c = part.as<int32_t>();
+    k_pn_gain<<<dim3((unsigned)nb), dim3(PN_TPB), 0, s>>>(n, pts, nrm, rho, dinfo->mean_density, max_gain, gain, part_c);
+    HIPCHK(hipGetLastError());
+    std::vector<int32_t> hc((size_t)nb);
+    HIPCHK(hipMemcpyAsync(hc.data(), part_c, 4 * (size_t)nb, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    dinfo->n_clamped = 0;
+    for (int b = 0; b < nb; ++b) dinfo->n_clamped += hc[b];
+    return MVS_OK;
+}
+
+int poisson_vertex_density(int64_t nv, const double* vertices, const PnDensitySums& d, double* out, hipStream_t s) {
+    with_sums(d, [&](auto sums) { k_pn_vertex_density<<<dim3((unsigned)((nv + PN_TPB - 1) / PN_TPB)), dim3(PN_TPB), 0, s>>>(nv, vertices, d.g, sums, out); });
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+    return MVS_OK;
 }
 
 int poisson_cube(const PnCall& c, const double* pts_dev, const double* nrm_dev, hipStream_t s, double origin[3], double* side) {
@@ -1357,15 +1236,7 @@ int PnBaseField::solve(const PnCall& c, const double* pts_dev, const double* nrm
     return MVS_OK;
 }
 
-int poisson_plain_dev(const PnCall& c, const double* pts_dev, const double* nrm_dev, double* vertices_dev, int64_t vcap, int32_t* faces_dev,
-                      int64_t fcap, Scratch* bv, Scratch* bf, hipStream_t s) {
-    return reconstruct(c, pts_dev, nrm_dev, PnOut{vertices_dev, nullptr, faces_dev, vcap, fcap, bv, nullptr, bf}, s);
-}
-
-int poisson_density_dev(const PnCall& c, const double* pts_dev, const double* nrm_dev, double* vertices_dev, double* density_dev, int64_t vcap,
-                        int32_t* faces_dev, int64_t fcap, Scratch* bv, Scratch* bd, Scratch* bf, hipStream_t s) {
-    return reconstruct(c, pts_dev, nrm_dev, PnOut{vertices_dev, density_dev, faces_dev, vcap, fcap, bv, bd, bf}, s);
-}
+int poisson_dense_dev(const PnCall& c, const double* pts_dev, const double* nrm_dev, PnOut o, hipStream_t s) { return reconstruct(c, pts_dev, nrm_dev, o, s); }
 
 extern "C" {
 

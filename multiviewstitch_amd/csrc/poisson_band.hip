@@ -23,26 +23,26 @@
 //                                         and A p fused with the p . A p partials; x, r updated fused with the r . r partials.  Every
 //                                         workgroup folds the (at most BD_NPART) partials of the launch before in a fixed order: the
 //                                         step lengths never leave the device, the host reads one number per 64 iterations
-//   k_bd_fold                             the sum of partials by one workgroup, as k_pn_fold
 //   k_bd_used_count / k_bd_used_scatter / k_bd_iso
 //                                         rule 29: the reduction of k_pn_iso through the block table, over the used rows listed in
 //                                         their order by an ordered compaction, so rows that are not used move no bit of the iso value
-//   k_bd_cubemask / k_bd_edge_count / k_bd_vertex_scatter / k_bd_face_count / k_bd_face_scatter
-//                                         rules 30-31 over the stored nodes in the order bd_segment gives them: the two ordered
-//                                         compactions of poisson.hip, items = (place of the node) * 7 + type resp. * 12 + slot (int64)
+//   BdSurf                                rules 30-31: the view through which the extraction of poisson_surface.h (k_pn_cubemask,
+//                                         k_pn_edge_count, k_pn_vertex_scatter, k_pn_face_scatter) sees the stored nodes in the order
+//                                         bd_segment gives them, items = (place of the node) * 7 + type resp. * 12 + slot (int64)
+// What the dense stage has already, it lends (poisson_base.h): the folds and the vertex numbering (poisson_dev.h), the scan between a
+// count and a scatter kernel (PnScan), the sum of partials by one workgroup (poisson_fold), the face count and the tail of a call.
 // mvs_poisson_reconstruct_band_density (rules 32-35) carries the sampling density of rules 14-17 over every level.  The int64 sums of
 // the density grid of depth Dd lie dense when Dd <= B and else in the blocks of level Dd that a cell of a used point touches
 // (k_bd_mark without the dilation, k_bd_stored, k_bd_row_count, k_bd_number: the table of a level, 8 bytes per stored node); a node
-// without storage reads as 0 (bd_density_at of poisson_band_rules.h).
-//   k_bd_density_splat                    rule 14 through that storage: a thread per point, 8 int64 atomic adds
-//   k_bd_point_density                    rule 15: rho_p per row; min, max and the int64 sum of the quantised densities per workgroup
-//                                         (order-free, k_pn_point_density's partials); the gains of rule 16 are poisson.hip's k_pn_gain
-//   k_bd_vertex_density                   rule 34 over the vertex list the scatter wrote
+// without storage reads as 0 (bd_density_at of poisson_band_rules.h).  The kernels of rules 14-17 are poisson.hip's, instantiated for
+// either storage (PnDensitySums, poisson_density_rows, poisson_vertex_density of poisson_base.h).
 // BdRun runs the stages in the order depth, density, base, levels, iso, mesh, vertex density.
 // Nothing but integer atomics (the splats, the bitmap, the count of open edges) is unordered: two runs give the same bytes.
 #include "engine.h"
 #include "trace.h"
 #include "frontend_dev.h"
+#include "poisson_dev.h"
+#include "poisson_surface.h"
 #include "poisson_band_rules.h"
 #include "poisson_band_plan.h"
 #include "poisson_base.h"
@@ -57,52 +57,21 @@ static_assert(BP_MAX_DEPTH == MVS_POISSON_BAND_MAX_DEPTH && BP_BLOCK == MVS_POIS
 
 namespace {
 
-constexpr int BD_TPB = 256, BD_WAVES = BD_TPB / 64;
 constexpr int BD_RED_NB = 1024;          // workgroups of a reduction over the points
 constexpr int BD_NPART = 1024;           // workgroups of a solver launch at most: the partials every workgroup folds
 constexpr int BD_MAX_D = MVS_POISSON_BAND_MAX_DEPTH;
-constexpr int BD_SCAN_CH = 4096;
-
-// the sum of v over the workgroup in a fixed order (shuffles inside a wave, then the waves in order), valid in thread 0: wg_sum of poisson.hip
-__device__ inline double bd_wg_sum(double v, double* s_part, int tid) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = v + __shfl_down(v, o, 64);
-    if ((tid & 63) == 0) s_part[tid >> 6] = v;
-    __syncthreads();
-    double t = 0.0;
-    if (tid == 0)
-        for (int q = 0; q < BD_WAVES; ++q) t = t + s_part[q];
-    return t;
-}
-// the sum of n partials, the same number in every thread of every workgroup: thread t takes t, t + 256, ... ascending, then bd_wg_sum
-__device__ inline double bd_fold_all(const double* __restrict__ part, int n, double* s_part, double* s_out) {
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < n; i += BD_TPB) acc += part[i];
-    const double t = bd_wg_sum(acc, s_part, threadIdx.x);
-    if (threadIdx.x == 0) *s_out = t;
-    __syncthreads();
-    return *s_out;
-}
-
-__global__ __launch_bounds__(BD_TPB) void k_bd_fold(const double* __restrict__ part, int n, double* __restrict__ out) {
-    __shared__ double s_part[BD_WAVES];
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < n; i += BD_TPB) acc += part[i];
-    const double t = bd_wg_sum(acc, s_part, threadIdx.x);
-    if (threadIdx.x == 0) *out = t;
-}
 
 // ------------------------------------------------------------------ rule 24 ----
-__global__ __launch_bounds__(BD_TPB) void k_bd_occupy(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm, PnGrid g,
+__global__ __launch_bounds__(PN_TPB) void k_bd_occupy(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm, PnGrid g,
                                                       unsigned* __restrict__ bits) {
-    const int64_t i = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
     if (i >= n || !pn_used(pts + 3 * i, nrm + 3 * i)) return;
     const int m = g.G;
     const int64_t cell = ((int64_t)pn_cell(pts[3 * i + 2], g.o[2], g.h, m) * m + pn_cell(pts[3 * i + 1], g.o[1], g.h, m)) * m + pn_cell(pts[3 * i], g.o[0], g.h, m);
     atomicOr(bits + (cell >> 5), 1u << (cell & 31));
 }
-__global__ __launch_bounds__(BD_TPB) void k_bd_popcount(int64_t words, const unsigned* __restrict__ bits, unsigned long long* __restrict__ occupied) {
-    const int64_t w = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
+__global__ __launch_bounds__(PN_TPB) void k_bd_popcount(int64_t words, const unsigned* __restrict__ bits, unsigned long long* __restrict__ occupied) {
+    const int64_t w = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
     const unsigned v = w < words ? bits[w] : 0u;
     if (v) atomicAdd(occupied, (unsigned long long)__popc(v));
 }
@@ -121,27 +90,27 @@ struct BdActive {
 };
 // node (ix, iy, iz) in [0, G]^3 -> its place 64 s + lane in the node arrays, -1 when its block is not stored
 __device__ inline int64_t bd_slot(const BdView& v, int ix, int iy, int iz) { return bd_node_slot(v.num, v.T, ix, iy, iz); }
-__device__ inline void bd_unpack(int32_t c, int* bx, int* by, int* bz) { *bx = c & 1023; *by = c >> 10 & 1023; *bz = c >> 20 & 1023; }
+__host__ __device__ inline void bd_unpack(int32_t c, int* bx, int* by, int* bz) { *bx = c & 1023; *by = c >> 10 & 1023; *bz = c >> 20 & 1023; }
 
 // ------------------------------------------------------------------ rule 26 ----
-__global__ __launch_bounds__(BD_TPB) void k_bd_mark(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm, PnGrid g, int T,
+__global__ __launch_bounds__(PN_TPB) void k_bd_mark(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm, PnGrid g, int T,
                                                     uint8_t* __restrict__ tab) {
-    const int64_t i = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
     if (i >= n || !pn_used(pts + 3 * i, nrm + 3 * i)) return;
     int b[3];
     bd_point_block(pts + 3 * i, g.o, g.h, g.G, b);
     tab[((int64_t)b[2] * T + b[1]) * T + b[0]] = 1;
 }
 
-__global__ __launch_bounds__(BD_TPB) void k_bd_dilate(int T, int Gb, const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int axis, int band) {
-    const int64_t at = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
+__global__ __launch_bounds__(PN_TPB) void k_bd_dilate(int T, int Gb, const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int axis, int band) {
+    const int64_t at = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
     if (at >= (int64_t)T * T * T) return;
     const int bx = (int)(at % T), by = (int)(at / T % T), bz = (int)(at / ((int64_t)T * T));
     out[at] = bx < Gb && by < Gb && bz < Gb && bd_dilate_at(in, T, Gb, bx, by, bz, axis, band) ? 1 : 0;
 }
 
-__global__ __launch_bounds__(BD_TPB) void k_bd_stored(int T, const uint8_t* __restrict__ act, uint8_t* __restrict__ stored) {
-    const int64_t at = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
+__global__ __launch_bounds__(PN_TPB) void k_bd_stored(int T, const uint8_t* __restrict__ act, uint8_t* __restrict__ stored) {
+    const int64_t at = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
     if (at >= (int64_t)T * T * T) return;
     const int bx = (int)(at % T), by = (int)(at / T % T), bz = (int)(at / ((int64_t)T * T));
     bool any = false;
@@ -154,9 +123,9 @@ __global__ __launch_bounds__(BD_TPB) void k_bd_stored(int T, const uint8_t* __re
 }
 
 // a wave per row (bz, by) of the table: how many of its T blocks are stored
-__global__ __launch_bounds__(BD_TPB) void k_bd_row_count(int T, const uint8_t* __restrict__ stored, int32_t* __restrict__ cnt) {
+__global__ __launch_bounds__(PN_TPB) void k_bd_row_count(int T, const uint8_t* __restrict__ stored, int32_t* __restrict__ cnt) {
     const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * BD_WAVES + (threadIdx.x >> 6);
+    const int64_t row = (int64_t)blockIdx.x * PN_WAVES + (threadIdx.x >> 6);
     if (row >= (int64_t)T * T) return;                                       // the whole wave
     int acc = 0;
     for (int c0 = 0; c0 < T; c0 += 64) {
@@ -167,10 +136,10 @@ __global__ __launch_bounds__(BD_TPB) void k_bd_row_count(int T, const uint8_t* _
 }
 
 // ... and their numbers, ascending along the row from the row's first; coord[s] = bx | by << 10 | bz << 20
-__global__ __launch_bounds__(BD_TPB) void k_bd_number(int T, const uint8_t* __restrict__ stored, const int32_t* __restrict__ first,
+__global__ __launch_bounds__(PN_TPB) void k_bd_number(int T, const uint8_t* __restrict__ stored, const int32_t* __restrict__ first,
                                                       int32_t* __restrict__ num, int32_t* __restrict__ coord) {
     const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * BD_WAVES + (threadIdx.x >> 6);
+    const int64_t row = (int64_t)blockIdx.x * PN_WAVES + (threadIdx.x >> 6);
     if (row >= (int64_t)T * T) return;
     int acc = first[row];
     for (int c0 = 0; c0 < T; c0 += 64) {
@@ -185,8 +154,8 @@ __global__ __launch_bounds__(BD_TPB) void k_bd_number(int T, const uint8_t* __re
 }
 
 // nbr[6 s + f]: the stored number of the neighbour of block s across face f = -x, +x, -y, +y, -z, +z; -1: none
-__global__ __launch_bounds__(BD_TPB) void k_bd_neighbours(int64_t ns, const int32_t* __restrict__ coord, BdView v, int32_t* __restrict__ nbr) {
-    const int64_t i = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
+__global__ __launch_bounds__(PN_TPB) void k_bd_neighbours(int64_t ns, const int32_t* __restrict__ coord, BdView v, int32_t* __restrict__ nbr) {
+    const int64_t i = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
     if (i >= 6 * ns) return;
     const int f = (int)(i % 6);
     int b[3];
@@ -196,8 +165,8 @@ __global__ __launch_bounds__(BD_TPB) void k_bd_neighbours(int64_t ns, const int3
 }
 
 // rows[place] = 16 s + 4 lz + ly for the row of four nodes at (ly, lz) of block s, place = bd_segment: the stored rows in (iz, iy, ix) order
-__global__ __launch_bounds__(BD_TPB) void k_bd_rows(int64_t ns, const int32_t* __restrict__ coord, BdView v, int32_t* __restrict__ rows) {
-    const int64_t i = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
+__global__ __launch_bounds__(PN_TPB) void k_bd_rows(int64_t ns, const int32_t* __restrict__ coord, BdView v, int32_t* __restrict__ rows) {
+    const int64_t i = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
     if (i >= 16 * ns) return;
     const int s = (int)(i >> 4), ly = (int)(i & 3), lz = (int)(i >> 2 & 3);
     int bx, by, bz;
@@ -222,9 +191,9 @@ struct BdBlockCoarse {                   // chi of the level below in its blocks
 };
 
 template <class Coarse>
-__global__ __launch_bounds__(BD_TPB) void k_bd_class_start(int64_t ns, const int32_t* __restrict__ coord, BdView v, Coarse coarse,
+__global__ __launch_bounds__(PN_TPB) void k_bd_class_start(int64_t ns, const int32_t* __restrict__ coord, BdView v, Coarse coarse,
                                                            uint8_t* __restrict__ cls, double* __restrict__ x) {
-    const int64_t at = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
+    const int64_t at = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
     if (at >= 64 * ns) return;
     const int lane = (int)(at & 63);
     int bx, by, bz;
@@ -239,9 +208,9 @@ __global__ __launch_bounds__(BD_TPB) void k_bd_class_start(int64_t ns, const int
 // ------------------------------------------------------------------ rules 5-6 in block storage ----
 // WEIGHTED: rule 33, every normal scaled by the gain s_p of its point (k_pn_splat<true>'s expression)
 template <bool WEIGHTED>
-__global__ __launch_bounds__(BD_TPB) void k_bd_splat(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm, PnGrid g, BdView v,
+__global__ __launch_bounds__(PN_TPB) void k_bd_splat(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm, PnGrid g, BdView v,
                                                      int64_t nodes, unsigned long long* __restrict__ sums, const double* __restrict__ gain) {
-    const int64_t i = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
     if (i >= n || !pn_used(pts + 3 * i, nrm + 3 * i)) return;
     int i0[3];
     double w[8], na[3];
@@ -252,82 +221,6 @@ __global__ __launch_bounds__(BD_TPB) void k_bd_splat(int64_t n, const double* __
         if (at < 0) continue;                                                // rule 29: cannot be, the cube of a used point is active
         for (int a = 0; a < 3; ++a) atomicAdd(sums + a * nodes + at, (unsigned long long)pn_quant(w[c] * na[a]));
     }
-}
-
-// ------------------------------------------------------------------ rules 32-34 ----
-// The int64 sums of the density grid as the kernels see them: dense in node order (num == NULL: Dd <= B) or 64 per stored block of
-// level Dd behind the block table (rule 32); operator() is the sum() of bd_density_at
-struct BdDensity {
-    PnGrid g;
-    const int32_t* num;
-    int32_t T;
-    const long long* sums;
-    __device__ int64_t slot(int ix, int iy, int iz) const { return num ? bd_node_slot(num, T, ix, iy, iz) : pn_node(g.G, ix, iy, iz); }
-    __device__ long long operator()(int ix, int iy, int iz) const { return num ? BdBlockSums{num, T, sums}(ix, iy, iz) : BdDenseSums{g.G, sums}(ix, iy, iz); }
-};
-
-// rule 14 into that storage: a thread per point, 8 int64 atomic adds
-__global__ __launch_bounds__(BD_TPB) void k_bd_density_splat(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm, BdDensity d,
-                                                             unsigned long long* __restrict__ dsum) {
-    const int64_t i = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
-    if (i >= n || !pn_used(pts + 3 * i, nrm + 3 * i)) return;
-    int i0[3];
-    double w[8];
-    pn_corners_weights(pts + 3 * i, d.g, i0, w);
-    for (int c = 0; c < 8; ++c) {
-        const int64_t at = d.slot(i0[0] + (c & 1), i0[1] + (c >> 1 & 1), i0[2] + (c >> 2 & 1));
-        if (at < 0) continue;                                                // rule 32: cannot be, the block of the point's cell is marked
-        atomicAdd(dsum + at, (unsigned long long)pn_quant(w[c]));
-    }
-}
-
-// v folded over the workgroup by op in a fixed order, valid in thread 0: wg_fold of poisson.hip
-template <class T, class Op>
-__device__ inline T bd_wg_fold(T v, T zero, T* s_part, int tid, Op op) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_down(v, o, 64));
-    if ((tid & 63) == 0) s_part[tid >> 6] = v;
-    __syncthreads();
-    T t = zero;
-    if (tid == 0)
-        for (int q = 0; q < BD_WAVES; ++q) t = op(t, s_part[q]);
-    return t;
-}
-
-// rule 15 through rule 32's read: rho_p of every row (0 for a row that is not used) and, per workgroup, the min, the max and the int64
-// sum of the quantised densities of its used rows, all three order-free (k_pn_point_density's partials); the host finishes
-__global__ __launch_bounds__(BD_TPB) void k_bd_point_density(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm, BdDensity d,
-                                                             double* __restrict__ rho, double* __restrict__ part_d, long long* __restrict__ part_q) {
-    __shared__ double s_lo[BD_WAVES], s_hi[BD_WAVES];
-    __shared__ long long s_q[BD_WAVES];
-    double lo = HUGE_VAL, hi = -HUGE_VAL;
-    long long q = 0;
-    for (int64_t i = (int64_t)blockIdx.x * BD_TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * BD_TPB) {
-        double r = 0.0;
-        if (pn_used(pts + 3 * i, nrm + 3 * i)) {
-            r = bd_density_at(pts + 3 * i, d.g, d);
-            lo = fmin(lo, r);
-            hi = fmax(hi, r);
-            q += pn_rho_quant(r);
-        }
-        rho[i] = r;
-    }
-    lo = bd_wg_fold(lo, HUGE_VAL, s_lo, threadIdx.x, [](double a, double b) { return fmin(a, b); });
-    hi = bd_wg_fold(hi, -HUGE_VAL, s_hi, threadIdx.x, [](double a, double b) { return fmax(a, b); });
-    q = bd_wg_fold(q, 0ll, s_q, threadIdx.x, [](long long a, long long b) { return a + b; });
-    if (threadIdx.x == 0) {
-        part_d[2 * blockIdx.x] = lo;
-        part_d[2 * blockIdx.x + 1] = hi;
-        part_q[blockIdx.x] = q;
-    }
-}
-
-// rule 34: a thread per vertex of the scattered list; a cell needs a finite position
-__global__ __launch_bounds__(BD_TPB) void k_bd_vertex_density(int64_t nv, const double* __restrict__ vertices, BdDensity d, double* __restrict__ out) {
-    const int64_t v = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
-    if (v >= nv) return;
-    const double* p = vertices + 3 * v;
-    out[v] = isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]) ? bd_density_at(p, d.g, d) : NAN;
 }
 
 // the places of the six neighbours of node `lane` of block s, in the order of nbr; -1: in a block that is not stored
@@ -341,9 +234,9 @@ __device__ inline void bd_nb_slots(const int32_t* __restrict__ nb, int64_t s, in
 }
 
 // rule 6 at the free nodes (k_pn_rhs's expression); 0 elsewhere
-__global__ __launch_bounds__(BD_TPB) void k_bd_rhs(int64_t ns, const int32_t* __restrict__ nbr, const uint8_t* __restrict__ cls, int64_t nodes,
+__global__ __launch_bounds__(PN_TPB) void k_bd_rhs(int64_t ns, const int32_t* __restrict__ nbr, const uint8_t* __restrict__ cls, int64_t nodes,
                                                    const long long* __restrict__ sums, double h, double* __restrict__ b) {
-    const int64_t at = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
+    const int64_t at = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
     if (at >= 64 * ns) return;
     double val = 0.0;
     if (cls[at] == BD_FREE) {
@@ -377,12 +270,12 @@ __device__ inline double bd_sum6(double own, const int32_t* __restrict__ nb, int
 }
 
 // The launches of the solve: wave w of the launch takes the blocks w, w + waves, ...; a workgroup leaves one partial.
-#define BD_EACH_BLOCK(s) for (int64_t s = (int64_t)blockIdx.x * BD_WAVES + (threadIdx.x >> 6); s < ns; s += (int64_t)gridDim.x * BD_WAVES)
+#define BD_EACH_BLOCK(s) for (int64_t s = (int64_t)blockIdx.x * PN_WAVES + (threadIdx.x >> 6); s < ns; s += (int64_t)gridDim.x * PN_WAVES)
 
 // |b'|^2 over the free nodes, b' = b - (the stencil over the fixed values and zeros)
-__global__ __launch_bounds__(BD_TPB) void k_bd_bnorm(int64_t ns, const int32_t* __restrict__ nbr, const uint8_t* __restrict__ cls,
+__global__ __launch_bounds__(PN_TPB) void k_bd_bnorm(int64_t ns, const int32_t* __restrict__ nbr, const uint8_t* __restrict__ cls,
                                                      const double* __restrict__ x, const double* __restrict__ b, double* __restrict__ part) {
-    __shared__ double s_part[BD_WAVES];
+    __shared__ double s_part[PN_WAVES];
     const int lane = threadIdx.x & 63;
     double acc = 0.0;
     BD_EACH_BLOCK(s) {
@@ -393,17 +286,17 @@ __global__ __launch_bounds__(BD_TPB) void k_bd_bnorm(int64_t ns, const int32_t* 
         const double bp = c == BD_FREE ? b[at] - S : 0.0;
         acc += bp * bp;
     }
-    const double t = bd_wg_sum(acc, s_part, threadIdx.x);
+    const double t = wg_sum<PN_WAVES>(acc, s_part, threadIdx.x);
     if (threadIdx.x == 0) part[blockIdx.x] = t;
 }
 
 // the residual of 6 x - S = -b at the free nodes, x with the fixed values in place: (S - 6 x) - b, 0 at the other nodes.  Its squared norm
 // per workgroup; WRITE: r, the start of the solve.
 template <bool WRITE>
-__global__ __launch_bounds__(BD_TPB) void k_bd_residual(int64_t ns, const int32_t* __restrict__ nbr, const uint8_t* __restrict__ cls,
+__global__ __launch_bounds__(PN_TPB) void k_bd_residual(int64_t ns, const int32_t* __restrict__ nbr, const uint8_t* __restrict__ cls,
                                                         const double* __restrict__ x, const double* __restrict__ b, double* __restrict__ r,
                                                         double* __restrict__ part) {
-    __shared__ double s_part[BD_WAVES];
+    __shared__ double s_part[PN_WAVES];
     const int lane = threadIdx.x & 63;
     double acc = 0.0;
     BD_EACH_BLOCK(s) {
@@ -414,20 +307,20 @@ __global__ __launch_bounds__(BD_TPB) void k_bd_residual(int64_t ns, const int32_
         if (WRITE) r[at] = rv;
         acc += rv * rv;
     }
-    const double t = bd_wg_sum(acc, s_part, threadIdx.x);
+    const double t = wg_sum<PN_WAVES>(acc, s_part, threadIdx.x);
     if (threadIdx.x == 0) part[blockIdx.x] = t;
 }
 
 // p = r + beta p_old (beta = rr / rr_before, 0 in the first iteration), A p = 6 p - S(p) at the free nodes, and the partials of p . A p.
 // r and p are 0 at the nodes that are not free, so the neighbour's new p is r + beta p_old there too.
-__global__ __launch_bounds__(BD_TPB) void k_bd_apply(int64_t ns, const int32_t* __restrict__ nbr, const uint8_t* __restrict__ cls, int first, int np,
+__global__ __launch_bounds__(PN_TPB) void k_bd_apply(int64_t ns, const int32_t* __restrict__ nbr, const uint8_t* __restrict__ cls, int first, int np,
                                                      const double* __restrict__ rr, const double* __restrict__ rr_before,
                                                      const double* __restrict__ r, const double* __restrict__ p_old, double* __restrict__ p,
                                                      double* __restrict__ ap, double* __restrict__ part) {
-    __shared__ double s_a[BD_WAVES], s_b[BD_WAVES], s_part[BD_WAVES], s_o[2];
+    __shared__ double s_a[PN_WAVES], s_b[PN_WAVES], s_part[PN_WAVES], s_o[2];
     double beta = 0.0;
     if (!first) {
-        const double n = bd_fold_all(rr, np, s_a, s_o), d = bd_fold_all(rr_before, np, s_b, s_o + 1);
+        const double n = wg_sum_partials_all(rr, np, s_a, s_o), d = wg_sum_partials_all(rr_before, np, s_b, s_o + 1);
         beta = d > 0.0 ? n / d : 0.0;
     }
     const int lane = threadIdx.x & 63;
@@ -441,16 +334,16 @@ __global__ __launch_bounds__(BD_TPB) void k_bd_apply(int64_t ns, const int32_t* 
         ap[at] = av;
         acc += pv * av;
     }
-    const double t = bd_wg_sum(acc, s_part, threadIdx.x);
+    const double t = wg_sum<PN_WAVES>(acc, s_part, threadIdx.x);
     if (threadIdx.x == 0) part[blockIdx.x] = t;
 }
 
 // alpha = rr / (p . A p); x += alpha p, r -= alpha A p, and the partials of the new r . r
-__global__ __launch_bounds__(BD_TPB) void k_bd_update(int64_t ns, int np, const double* __restrict__ rr, const double* __restrict__ pap,
+__global__ __launch_bounds__(PN_TPB) void k_bd_update(int64_t ns, int np, const double* __restrict__ rr, const double* __restrict__ pap,
                                                       const double* __restrict__ p, const double* __restrict__ ap, double* __restrict__ x,
                                                       double* __restrict__ r, double* __restrict__ part) {
-    __shared__ double s_a[BD_WAVES], s_b[BD_WAVES], s_part[BD_WAVES], s_o[2];
-    const double n = bd_fold_all(rr, np, s_a, s_o), d = bd_fold_all(pap, np, s_b, s_o + 1);
+    __shared__ double s_a[PN_WAVES], s_b[PN_WAVES], s_part[PN_WAVES], s_o[2];
+    const double n = wg_sum_partials_all(rr, np, s_a, s_o), d = wg_sum_partials_all(pap, np, s_b, s_o + 1);
     const double alpha = d > 0.0 ? n / d : 0.0;
     const int lane = threadIdx.x & 63;
     double acc = 0.0;
@@ -461,23 +354,23 @@ __global__ __launch_bounds__(BD_TPB) void k_bd_update(int64_t ns, int np, const 
         r[at] = rv;
         acc += rv * rv;
     }
-    const double t = bd_wg_sum(acc, s_part, threadIdx.x);
+    const double t = wg_sum<PN_WAVES>(acc, s_part, threadIdx.x);
     if (threadIdx.x == 0) part[blockIdx.x] = t;
 }
 
-__global__ __launch_bounds__(BD_TPB) void k_bd_zero_free(int64_t nodes, const uint8_t* __restrict__ cls, double* __restrict__ x) {
-    const int64_t at = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
+__global__ __launch_bounds__(PN_TPB) void k_bd_zero_free(int64_t nodes, const uint8_t* __restrict__ cls, double* __restrict__ x) {
+    const int64_t at = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
     if (at < nodes && cls[at] == BD_FREE) x[at] = 0.0;
 }
 
 // how many nodes are free: integers
-__global__ __launch_bounds__(BD_TPB) void k_bd_count_free(int64_t nodes, const uint8_t* __restrict__ cls, unsigned long long* __restrict__ out) {
-    const int64_t at = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
+__global__ __launch_bounds__(PN_TPB) void k_bd_count_free(int64_t nodes, const uint8_t* __restrict__ cls, unsigned long long* __restrict__ out) {
+    const int64_t at = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
     const unsigned long long bal = __ballot(at < nodes && cls[at] == BD_FREE);
     if ((threadIdx.x & 63) == 0 && bal) atomicAdd(out, (unsigned long long)__popcll(bal));
 }
-__global__ __launch_bounds__(BD_TPB) void k_bd_count_set(int64_t n, const uint8_t* __restrict__ flag, unsigned long long* __restrict__ out) {
-    const int64_t at = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
+__global__ __launch_bounds__(PN_TPB) void k_bd_count_set(int64_t n, const uint8_t* __restrict__ flag, unsigned long long* __restrict__ out) {
+    const int64_t at = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
     const unsigned long long bal = __ballot(at < n && flag[at]);
     if ((threadIdx.x & 63) == 0 && bal) atomicAdd(out, (unsigned long long)__popcll(bal));
 }
@@ -485,26 +378,26 @@ __global__ __launch_bounds__(BD_TPB) void k_bd_count_set(int64_t n, const uint8_
 // ------------------------------------------------------------------ rule 29 ----
 // The used rows in their order, by ordered compaction: the sum of rule 29 then runs over used[0 .. N), so a row that is not used moves
 // no used row to another thread and the iso value, an fp64 sum in a fixed order, does not depend on such rows.
-__global__ __launch_bounds__(BD_TPB) void k_bd_used_count(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm, int32_t* __restrict__ cnt) {
-    __shared__ int s_wsum[BD_WAVES];
-    const int64_t i = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
-    const WgRank k = wg_rank<BD_WAVES>(i < n && pn_used(pts + 3 * i, nrm + 3 * i), s_wsum);
+__global__ __launch_bounds__(PN_TPB) void k_bd_used_count(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm, int32_t* __restrict__ cnt) {
+    __shared__ int s_wsum[PN_WAVES];
+    const int64_t i = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
+    const WgRank k = wg_rank<PN_WAVES>(i < n && pn_used(pts + 3 * i, nrm + 3 * i), s_wsum);
     if (threadIdx.x == 0) cnt[blockIdx.x] = k.total;
 }
-__global__ __launch_bounds__(BD_TPB) void k_bd_used_scatter(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm,
+__global__ __launch_bounds__(PN_TPB) void k_bd_used_scatter(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm,
                                                             const int32_t* __restrict__ base, int64_t* __restrict__ used) {
-    __shared__ int s_wsum[BD_WAVES];
-    const int64_t i = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
+    __shared__ int s_wsum[PN_WAVES];
+    const int64_t i = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
     const bool f = i < n && pn_used(pts + 3 * i, nrm + 3 * i);
-    const int64_t pos = (int64_t)base[blockIdx.x] + wg_rank<BD_WAVES>(f, s_wsum).rank;
+    const int64_t pos = (int64_t)base[blockIdx.x] + wg_rank<PN_WAVES>(f, s_wsum).rank;
     if (f) used[pos] = i;
 }
 
-__global__ __launch_bounds__(BD_TPB) void k_bd_iso(int64_t m, const int64_t* __restrict__ used, const double* __restrict__ pts, PnGrid g, BdView v,
+__global__ __launch_bounds__(PN_TPB) void k_bd_iso(int64_t m, const int64_t* __restrict__ used, const double* __restrict__ pts, PnGrid g, BdView v,
                                                    const double* __restrict__ chi, double* __restrict__ part) {
-    __shared__ double s_part[BD_WAVES];
+    __shared__ double s_part[PN_WAVES];
     double acc = 0.0;
-    for (int64_t k = (int64_t)blockIdx.x * BD_TPB + threadIdx.x; k < m; k += (int64_t)gridDim.x * BD_TPB) {
+    for (int64_t k = (int64_t)blockIdx.x * PN_TPB + threadIdx.x; k < m; k += (int64_t)gridDim.x * PN_TPB) {
         const int64_t i = used[k];
         int i0[3];
         double w[8], val = 0.0;
@@ -515,176 +408,52 @@ __global__ __launch_bounds__(BD_TPB) void k_bd_iso(int64_t m, const int64_t* __r
         }
         acc += val;
     }
-    const double t = bd_wg_sum(acc, s_part, threadIdx.x);
+    const double t = wg_sum<PN_WAVES>(acc, s_part, threadIdx.x);
     if (threadIdx.x == 0) part[blockIdx.x] = t;
 }
 
 // ------------------------------------------------------------------ rules 30-31 ----
-// the scan between a count and a scatter kernel, in two levels (k_pn_scan_* of poisson.hip)
-__global__ __launch_bounds__(BD_TPB) void k_bd_scan_rows(const int32_t* __restrict__ cnt, int nb, int32_t* __restrict__ local, int32_t* __restrict__ tot) {
-    const int c0 = blockIdx.x * BD_SCAN_CH, len = nb - c0 < BD_SCAN_CH ? nb - c0 : BD_SCAN_CH;
-    int32_t* row = local + (int64_t)blockIdx.x * (BD_SCAN_CH + 1);
-    wg_scan_counts<BD_WAVES>(cnt + c0, len, row);
-    if (threadIdx.x == 0) tot[blockIdx.x] = row[len];                        // written by this thread
-}
-__global__ __launch_bounds__(BD_TPB) void k_bd_scan_totals(const int32_t* __restrict__ tot, int rows, int32_t* __restrict__ rbase) {
-    wg_scan_counts<BD_WAVES>(tot, rows, rbase);
-}
-__global__ __launch_bounds__(BD_TPB) void k_bd_scan_add(const int32_t* __restrict__ local, const int32_t* __restrict__ rbase, int nb, int rows,
-                                                        int32_t* __restrict__ base) {
-    const int64_t i = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
-    if (i < nb) base[i] = local[(i / BD_SCAN_CH) * (BD_SCAN_CH + 1) + i % BD_SCAN_CH] + rbase[i / BD_SCAN_CH];
-    if (i == nb) base[nb] = rbase[rows];
-}
-
-struct BdSurf {                          // level D for the surface kernels
+// Level D as poisson_surface.h's kernels see it: node and cube items are the places q = 4 * place of the row + lx of the stored nodes,
+// in (iz, iy, ix) order
+struct BdSurf {
+    static constexpr bool counts_open = true;
     BdView v;
     PnGrid g;
     const int32_t *coord, *rows;          // per stored block; per place of bd_segment
     const double* chi;
     double iso;
-    int64_t nodes;                        // 64 * stored blocks: the places q = 4 * place of the row + lx, in (iz, iy, ix) order
+    int64_t nodes;                        // 64 * stored blocks
+    unsigned long long* n_open;           // rule 31's count
+    __host__ __device__ int64_t node_items() const { return nodes; }
+    __host__ __device__ int64_t cube_items() const { return nodes; }
+    __device__ int64_t node(int64_t place, int i[3]) const {
+        const int32_t ri = rows[place >> 2];
+        const int s = ri >> 4, lx = (int)(place & 3), ly = ri & 3, lz = ri >> 2 & 3;
+        int bx, by, bz;
+        bd_unpack(coord[s], &bx, &by, &bz);
+        i[0] = 4 * bx + lx; i[1] = 4 * by + ly; i[2] = 4 * bz + lz;
+        return (int64_t)s * 64 + (lz << 4 | ly << 2 | lx);
+    }
+    __device__ void cube(int64_t place, int i[3]) const { node(place, i); }
+    __device__ bool takes_part(const int i[3]) const { return i[0] < v.G && i[1] < v.G && i[2] < v.G && BdActive{v}(i[0], i[1], i[2]); }
+    __device__ int64_t slot(int ix, int iy, int iz) const { return bd_slot(v, ix, iy, iz); }
+    __device__ bool has(int64_t at) const { return at >= 0; }
+    __device__ int64_t place(int ix, int iy, int iz) const {                // the node's block is stored
+        const int by = iy >> 2, bz = iz >> 2;
+        const int s = v.num[bd_tab(v, ix >> 2, by, bz)];
+        const BdRowSlab q = bd_row_slab(v.first, v.T, by, bz);
+        return bd_segment(s, iy & 3, iz & 3, q.rfirst, q.rcnt, q.sfirst, q.scnt) * 4 + (ix & 3);
+    }
+    __device__ bool edge(const int i[3], int type, bool* open) const {
+        bool exists = false;
+        *open = false;
+        if (i[0] <= v.G && i[1] <= v.G && i[2] <= v.G) bd_edge_state(v.G, i[0], i[1], i[2], type, BdActive{v}, &exists, open);
+        return exists;
+    }
 };
-// place q of rule 30's order -> the node and where its value lies
-__device__ inline int64_t bd_place_node(const BdSurf& q, int64_t place, int* ix, int* iy, int* iz) {
-    const int32_t ri = q.rows[place >> 2];
-    const int s = ri >> 4, lx = (int)(place & 3), ly = ri & 3, lz = ri >> 2 & 3;
-    int bx, by, bz;
-    bd_unpack(q.coord[s], &bx, &by, &bz);
-    *ix = 4 * bx + lx; *iy = 4 * by + ly; *iz = 4 * bz + lz;
-    return (int64_t)s * 64 + (lz << 4 | ly << 2 | lx);
-}
-// node -> its place in rule 30's order (the node's block is stored)
-__device__ inline int64_t bd_node_place(const BdView& v, int ix, int iy, int iz) {
-    const int by = iy >> 2, bz = iz >> 2;
-    const int s = v.num[bd_tab(v, ix >> 2, by, bz)];
-    const BdRowSlab q = bd_row_slab(v.first, v.T, by, bz);
-    return bd_segment(s, iy & 3, iz & 3, q.rfirst, q.rcnt, q.sfirst, q.scnt) * 4 + (ix & 3);
-}
-
-// the inside bits of the eight corners of the cube at place q; 0 (no face) for a cube that is not active
-__global__ __launch_bounds__(BD_TPB) void k_bd_cubemask(BdSurf q, uint8_t* __restrict__ mask) {
-    const int64_t place = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
-    if (place >= q.nodes) return;
-    int ix, iy, iz, m = 0;
-    bd_place_node(q, place, &ix, &iy, &iz);
-    if (ix < q.v.G && iy < q.v.G && iz < q.v.G && BdActive{q.v}(ix, iy, iz))
-        for (int c = 0; c < 8; ++c) {
-            const int64_t at = bd_slot(q.v, ix + (c & 1), iy + (c >> 1 & 1), iz + (c >> 2 & 1));
-            m |= (at >= 0 && q.chi[at] < q.iso ? 1 : 0) << c;
-        }
-    mask[place] = (uint8_t)m;
-}
-
-// edge item r = place * 7 + type: a crossed edge that exists?  *open: rule 31
-__device__ inline bool bd_edge_crossed(const BdSurf& q, int64_t r, int64_t items, bool* open) {
-    *open = false;
-    if (r >= items) return false;
-    const int type = (int)(r % 7);
-    int ix, iy, iz;
-    const int64_t at = bd_place_node(q, r / 7, &ix, &iy, &iz);
-    if (ix > q.v.G || iy > q.v.G || iz > q.v.G) return false;
-    bool exists;
-    bd_edge_state(q.v.G, ix, iy, iz, type, BdActive{q.v}, &exists, open);
-    if (!exists) { *open = false; return false; }
-    const int m = pn_type_mask(type);
-    const int64_t hi = bd_slot(q.v, ix + (m & 1), iy + (m >> 1 & 1), iz + (m >> 2 & 1));      // a corner of an active cube: stored
-    const bool f = hi >= 0 && (q.chi[at] < q.iso) != (q.chi[hi] < q.iso);
-    *open = *open && f;
-    return f;
-}
-
-__global__ __launch_bounds__(BD_TPB) void k_bd_edge_count(BdSurf q, int64_t items, unsigned long long* __restrict__ words, int32_t* __restrict__ cnt,
-                                                          unsigned long long* __restrict__ n_open) {
-    __shared__ int s_wsum[BD_WAVES];
-    const int64_t r = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
-    bool open;
-    const bool f = bd_edge_crossed(q, r, items, &open);
-    const unsigned long long bal = __ballot(f), obal = __ballot(open);
-    if ((threadIdx.x & 63) == 0) {
-        words[r >> 6] = bal;
-        if (obal) atomicAdd(n_open, (unsigned long long)__popcll(obal));     // integers: any order
-    }
-    const WgRank k = wg_rank<BD_WAVES>(f, s_wsum);
-    if (threadIdx.x == 0) cnt[blockIdx.x] = k.total;
-}
-
-__device__ inline int32_t bd_vertex_index(const unsigned long long* __restrict__ words, const int32_t* __restrict__ base, int64_t r) {
-    const int64_t blk = r >> 8, w = r >> 6;
-    int32_t acc = base[blk];
-    for (int64_t k = blk * BD_WAVES; k < w; ++k) acc += __popcll(words[k]);
-    return acc + __popcll(words[w] & ((1ull << (r & 63)) - 1ull));
-}
-
-__global__ __launch_bounds__(BD_TPB) void k_bd_vertex_scatter(BdSurf q, int64_t items, const unsigned long long* __restrict__ words,
-                                                              const int32_t* __restrict__ base, double* __restrict__ vertices) {
-    __shared__ int s_wsum[BD_WAVES];
-    const int64_t r = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
-    const bool f = (words[r >> 6] >> (r & 63)) & 1ull;                       // the bitmap covers whole workgroups
-    const int64_t pos = (int64_t)base[blockIdx.x] + wg_rank<BD_WAVES>(f, s_wsum).rank;
-    if (!f) return;
-    const int m = pn_type_mask((int)(r % 7));
-    int ix, iy, iz;
-    const int64_t at = bd_place_node(q, r / 7, &ix, &iy, &iz);
-    const int jx = ix + (m & 1), jy = iy + (m >> 1 & 1), jz = iz + (m >> 2 & 1);
-    const double vl = q.chi[at], vh = q.chi[bd_slot(q.v, jx, jy, jz)];
-    const double pl[3] = {q.g.o[0] + q.g.h * (double)ix, q.g.o[1] + q.g.h * (double)iy, q.g.o[2] + q.g.h * (double)iz};
-    const double ph[3] = {q.g.o[0] + q.g.h * (double)jx, q.g.o[1] + q.g.h * (double)jy, q.g.o[2] + q.g.h * (double)jz};
-    double out[3];
-    if (vl < q.iso) pn_vertex(vl, vh, pl, ph, q.iso, out); else pn_vertex(vh, vl, ph, pl, q.iso, out);
-    for (int a = 0; a < 3; ++a) vertices[3 * pos + a] = out[a];
-}
-
-// face item r = (place * 6 + tetrahedron) * 2 + slot: pn_face_item of poisson.hip
-__device__ inline int bd_face_item(const uint8_t* __restrict__ mask, int64_t r, int64_t items) {
-    if (r >= items) return -1;
-    const int cm = mask[r / 12];
-    if (cm == 0 || cm == 255) return -1;
-    const int k = (int)(r % 12) >> 1, slot = (int)(r & 1);
-    int in = 0;
-    for (int i = 0; i < 4; ++i) in |= (cm >> pn_tet_corner(k, i) & 1) << i;
-    const int ni = __popc(in);
-    return (slot == 0 ? ni >= 1 && ni <= 3 : ni == 2) ? in : -1;
-}
-
-__global__ __launch_bounds__(BD_TPB) void k_bd_face_count(const uint8_t* __restrict__ mask, int64_t items, int32_t* __restrict__ cnt) {
-    __shared__ int s_wsum[BD_WAVES];
-    const int64_t r = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
-    const WgRank k = wg_rank<BD_WAVES>(bd_face_item(mask, r, items) >= 0, s_wsum);
-    if (threadIdx.x == 0) cnt[blockIdx.x] = k.total;
-}
-
-__global__ __launch_bounds__(BD_TPB) void k_bd_face_scatter(BdSurf q, const uint8_t* __restrict__ mask, int64_t items,
-                                                            const unsigned long long* __restrict__ words, const int32_t* __restrict__ vbase,
-                                                            const double* __restrict__ vertices, const int32_t* __restrict__ fbase,
-                                                            int32_t* __restrict__ faces) {
-    __shared__ int s_wsum[BD_WAVES];
-    const int64_t r = (int64_t)blockIdx.x * BD_TPB + threadIdx.x;
-    const int in = bd_face_item(mask, r, items);
-    const int64_t pos = (int64_t)fbase[blockIdx.x] + wg_rank<BD_WAVES>(in >= 0, s_wsum).rank;
-    if (in < 0) return;
-    const int k = (int)(r % 12) >> 1, slot = (int)(r & 1);
-    int ix, iy, iz;
-    bd_place_node(q, r / 12, &ix, &iy, &iz);
-    int ci[4], co[4];
-    const int n = pn_tet_cycle(in, ci, co);
-    int32_t idx[4];
-    double pos3[4][3], d[3];
-    for (int e = 0; e < n; ++e) {
-        int nm, type;
-        pn_tet_edge(k, ci[e], co[e], &nm, &type);
-        idx[e] = bd_vertex_index(words, vbase, bd_node_place(q.v, ix + (nm & 1), iy + (nm >> 1 & 1), iz + (nm >> 2 & 1)) * 7 + type);
-        for (int a = 0; a < 3; ++a) pos3[e][a] = vertices[3 * (int64_t)idx[e] + a];
-    }
-    pn_tet_dir(k, in, d);
-    pn_polygon(n, idx, pos3, d);
-    faces[3 * pos] = idx[0];
-    faces[3 * pos + 1] = idx[slot ? 2 : 1];
-    faces[3 * pos + 2] = idx[slot ? 3 : 2];
-}
 
 // ------------------------------------------------------------------ host ----
-inline unsigned bd_grid(int64_t items) { return (unsigned)((items + BD_TPB - 1) / BD_TPB); }
+inline unsigned bd_grid(int64_t items) { return (unsigned)((items + PN_TPB - 1) / PN_TPB); }
 
 int check_band(const char* fn, const mvs_poisson_band_params* bp, const void* binfo) {
     if (!bp || !binfo) return bad(fn, "bparams or binfo is NULL");
@@ -709,25 +478,6 @@ struct BdDump {
     uint8_t *active, *cls;
     double *b, *chi;
     int64_t node_capacity;
-};
-
-struct BdScan {                          // counts, their scan and its two levels, for nb workgroups (PnRun::Scan of poisson.hip)
-    Scratch cnt, base, local, tot, rbase;
-    int64_t bytes = 0;
-    int alloc(size_t nb, hipStream_t s) {
-        const size_t rows = (nb + BD_SCAN_CH - 1) / BD_SCAN_CH;
-        int rc;
-        bytes = (int64_t)(4 * nb + 4 * (nb + 1) + 4 * rows * (BD_SCAN_CH + 1) + 4 * rows + 4 * (rows + 1));
-        if ((rc = cnt.alloc(4 * nb, s)) || (rc = base.alloc(4 * (nb + 1), s)) || (rc = local.alloc(4 * rows * (BD_SCAN_CH + 1), s)) ||
-            (rc = tot.alloc(4 * rows, s))) return rc;
-        return rbase.alloc(4 * (rows + 1), s);
-    }
-    void run(int nb, hipStream_t s) {
-        const int rows = (nb + BD_SCAN_CH - 1) / BD_SCAN_CH;
-        k_bd_scan_rows<<<dim3((unsigned)rows), dim3(BD_TPB), 0, s>>>(cnt.as<int32_t>(), nb, local.as<int32_t>(), tot.as<int32_t>());
-        k_bd_scan_totals<<<dim3(1), dim3(BD_TPB), 0, s>>>(tot.as<int32_t>(), rows, rbase.as<int32_t>());
-        k_bd_scan_add<<<dim3((unsigned)(nb / BD_TPB + 1)), dim3(BD_TPB), 0, s>>>(local.as<int32_t>(), rbase.as<int32_t>(), nb, rows, base.as<int32_t>());
-    }
 };
 
 // One call past its checks, the points on the device.
@@ -755,18 +505,17 @@ struct BdRun {
     std::unique_ptr<BdLevel> top;         // level D after levels()
     // the surface
     Scratch rows, mask, words;
-    BdScan ve, fa;
+    PnScan ve, fa;
     int64_t edge_items = 0, face_items = 0;
 
-    BdRun(const char* f, const mvs_poisson_params& pp, const mvs_poisson_band_params& b, mvs_poisson_info& i, mvs_poisson_band_info& bi, int64_t nn,
-          const double* pd, const double* nd, hipStream_t st, const mvs_poisson_density_params* dpar = nullptr, mvs_poisson_density_info* di = nullptr)
-        : fn(f), p(pp), bp(b), info(i), binfo(bi), n(nn), pts(pd), nrm(nd), s(st), dp(dpar), dinfo(di) {
+    BdRun(const BdCall& c, const double* pd, const double* nd, hipStream_t st)
+        : fn(c.fn), p(*c.p), bp(*c.bp), info(*c.info), binfo(*c.binfo), n(c.n), pts(pd), nrm(nd), s(st), dp(c.dp), dinfo(c.dinfo) {
         std::memset(&info, 0, sizeof info);
         std::memset(&binfo, 0, sizeof binfo);
         if (dinfo) std::memset(dinfo, 0, sizeof *dinfo);
     }
     bool weighted() const { return dp && (dp->flags & MVS_POISSON_WEIGHT_NORMALS); }
-    BdDensity density_view() const { return BdDensity{gd, bd_density_in_blocks(Dd, B) ? dnum.as<int32_t>() : nullptr, de.T, dsum.as<long long>()}; }
+    PnDensitySums density_sums() const { return PnDensitySums{gd, bd_density_in_blocks(Dd, B) ? dnum.as<int32_t>() : nullptr, de.T, dsum.as<long long>()}; }
 
     int take(Scratch& sc, int64_t b, int64_t* held = nullptr) {
         const int rc = sc.alloc((size_t)b, s);
@@ -790,8 +539,8 @@ struct BdRun {
     // the number behind the flags of a byte array, or the free nodes of a class array
     int count(const uint8_t* flag, int64_t m, bool free_nodes, int64_t* out) {
         HIPCHK(hipMemsetAsync(cnt8.p, 0, 8, s));
-        if (free_nodes) k_bd_count_free<<<dim3(bd_grid(m)), dim3(BD_TPB), 0, s>>>(m, flag, cnt8.as<unsigned long long>());
-        else k_bd_count_set<<<dim3(bd_grid(m)), dim3(BD_TPB), 0, s>>>(m, flag, cnt8.as<unsigned long long>());
+        if (free_nodes) k_bd_count_free<<<dim3(bd_grid(m)), dim3(PN_TPB), 0, s>>>(m, flag, cnt8.as<unsigned long long>());
+        else k_bd_count_set<<<dim3(bd_grid(m)), dim3(PN_TPB), 0, s>>>(m, flag, cnt8.as<unsigned long long>());
         HIPCHK(hipGetLastError());
         unsigned long long v = 0;
         const int rc = fetch(&v, cnt8.p, 8);
@@ -817,8 +566,8 @@ struct BdRun {
             if ((rc = take(bits, 4 * words))) return rc;
             HIPCHK(hipMemsetAsync(bits.p, 0, (size_t)(4 * words), s));
             HIPCHK(hipMemsetAsync(cnt8.p, 0, 8, s));
-            k_bd_occupy<<<dim3(bd_grid(n)), dim3(BD_TPB), 0, s>>>(n, pts, nrm, g, bits.as<unsigned>());
-            k_bd_popcount<<<dim3(bd_grid(words)), dim3(BD_TPB), 0, s>>>(words, bits.as<unsigned>(), cnt8.as<unsigned long long>());
+            k_bd_occupy<<<dim3(bd_grid(n)), dim3(PN_TPB), 0, s>>>(n, pts, nrm, g, bits.as<unsigned>());
+            k_bd_popcount<<<dim3(bd_grid(words)), dim3(PN_TPB), 0, s>>>(words, bits.as<unsigned>(), cnt8.as<unsigned long long>());
             HIPCHK(hipGetLastError());
             unsigned long long occ = 0;
             if ((rc = fetch(&occ, cnt8.p, 8))) return rc;                     // synchronises: bits may go
@@ -837,14 +586,14 @@ struct BdRun {
         dinfo->density_depth = Dd;
         if (bd_density_in_blocks(Dd, B)) {                                   // the blocks a cell of a used point touches: rule 26's marks, not dilated
             de = bd_extent(Dd);
-            const unsigned tgrid = bd_grid(de.table), rgrid = (unsigned)((de.rows + BD_WAVES - 1) / BD_WAVES);
+            const unsigned tgrid = bd_grid(de.table), rgrid = (unsigned)((de.rows + PN_WAVES - 1) / PN_WAVES);
             Scratch ta, tb, rcnt, first;
             if ((rc = take(ta, de.table)) || (rc = take(tb, de.table)) || (rc = take(rcnt, 4 * de.rows)) || (rc = take(first, 4 * (de.rows + 1))) ||
                 (rc = dnum.alloc((size_t)(4 * de.table), s))) return rc;
             HIPCHK(hipMemsetAsync(ta.p, 0, (size_t)de.table, s));
-            k_bd_mark<<<dim3(bd_grid(n)), dim3(BD_TPB), 0, s>>>(n, pts, nrm, gd, de.T, ta.as<uint8_t>());
-            k_bd_stored<<<dim3(tgrid), dim3(BD_TPB), 0, s>>>(de.T, ta.as<uint8_t>(), tb.as<uint8_t>());
-            k_bd_row_count<<<dim3(rgrid), dim3(BD_TPB), 0, s>>>(de.T, tb.as<uint8_t>(), rcnt.as<int32_t>());
+            k_bd_mark<<<dim3(bd_grid(n)), dim3(PN_TPB), 0, s>>>(n, pts, nrm, gd, de.T, ta.as<uint8_t>());
+            k_bd_stored<<<dim3(tgrid), dim3(PN_TPB), 0, s>>>(de.T, ta.as<uint8_t>(), tb.as<uint8_t>());
+            k_bd_row_count<<<dim3(rgrid), dim3(PN_TPB), 0, s>>>(de.T, tb.as<uint8_t>(), rcnt.as<int32_t>());
             HIPCHK(hipGetLastError());
             std::vector<int32_t> hc((size_t)de.rows), hf((size_t)de.rows + 1);
             if ((rc = fetch(hc.data(), rcnt.p, 4 * (size_t)de.rows))) return rc;
@@ -856,7 +605,7 @@ struct BdRun {
             }
             if ((rc = dcoord.alloc((size_t)(4 * dns), s))) return rc;
             HIPCHK(hipMemcpy(first.p, hf.data(), 4 * hf.size(), hipMemcpyHostToDevice));     // the stream is idle: fetch synchronised it
-            k_bd_number<<<dim3(rgrid), dim3(BD_TPB), 0, s>>>(de.T, tb.as<uint8_t>(), first.as<int32_t>(), dnum.as<int32_t>(), dcoord.as<int32_t>());
+            k_bd_number<<<dim3(rgrid), dim3(PN_TPB), 0, s>>>(de.T, tb.as<uint8_t>(), first.as<int32_t>(), dnum.as<int32_t>(), dcoord.as<int32_t>());
             HIPCHK(hipGetLastError());
             HIPCHK(hipStreamSynchronize(s));                                  // ta, tb, rcnt and first go
             bytes.give(bd_density_work_bytes(Dd, B));
@@ -866,34 +615,13 @@ struct BdRun {
         if ((rc = dsum.alloc((size_t)(8 * dslots), s)) || (rc = rho.alloc(8 * (size_t)n, s)) || (rc = gain.alloc(8 * (size_t)n, s)) ||
             (rc = dpart.alloc(24 * (size_t)BD_RED_NB, s))) return rc;
         bytes.take(bd_density_bytes(Dd, B, dns, n));
-        const BdDensity dv = density_view();
-        const int nb = (int)std::min<int64_t>(BD_RED_NB, (n + BD_TPB - 1) / BD_TPB);
-        double* part_d = dpart.as<double>();
-        long long* part_q = dpart.as<long long>() + 2 * BD_RED_NB;
         HIPCHK(hipMemsetAsync(dsum.p, 0, (size_t)(8 * dslots), s));
-        k_bd_density_splat<<<dim3(bd_grid(n)), dim3(BD_TPB), 0, s>>>(n, pts, nrm, dv, dsum.as<unsigned long long>());
-        k_bd_point_density<<<dim3((unsigned)nb), dim3(BD_TPB), 0, s>>>(n, pts, nrm, dv, rho.as<double>(), part_d, part_q);
-        HIPCHK(hipGetLastError());
-        std::vector<double> hd((size_t)2 * nb);
-        std::vector<long long> hq((size_t)nb);
-        HIPCHK(hipMemcpyAsync(hd.data(), part_d, 16 * (size_t)nb, hipMemcpyDeviceToHost, s));
-        if ((rc = fetch(hq.data(), part_q, 8 * (size_t)nb))) return rc;
-        double lo = HUGE_VAL, hi = -HUGE_VAL;
-        long long q = 0;
-        for (int b = 0; b < nb; ++b) { lo = std::fmin(lo, hd[2 * b]); hi = std::fmax(hi, hd[2 * b + 1]); q += hq[b]; }
-        dinfo->mean_density = pn_rho_mean(q, info.n_used);
-        dinfo->min_point_density = lo;
-        dinfo->max_point_density = hi;
-        return poisson_gains(n, pts, nrm, rho.as<double>(), dinfo->mean_density, dp->max_gain, gain.as<double>(), &dinfo->n_clamped, s);
+        return poisson_density_rows(n, pts, nrm, density_sums(), info.n_used, dp->max_gain, rho.as<double>(), gain.as<double>(), dpart, dinfo, s);
     }
 
     // rule 34, after scatter
     int vertex_density(const double* vertices, double* out) {
-        if (!out || info.n_vertices == 0) return MVS_OK;
-        k_bd_vertex_density<<<dim3(bd_grid(info.n_vertices)), dim3(BD_TPB), 0, s>>>(info.n_vertices, vertices, density_view(), out);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(s));
-        return MVS_OK;
+        return out && info.n_vertices > 0 ? poisson_vertex_density(info.n_vertices, vertices, density_sums(), out, s) : MVS_OK;
     }
 
     // the hook's part of rules 32-33: the node sums expanded to the dense layout of the density grid, rho_p and s_p per row
@@ -914,7 +642,8 @@ struct BdRun {
         HIPCHK(hipMemcpy(coord.data(), dcoord.p, 4 * (size_t)dns, hipMemcpyDeviceToHost));
         for (int64_t i = 0; i < nn; ++i) node_sums[i] = 0;
         for (int64_t sb = 0; sb < dns; ++sb) {
-            const int bx = coord[(size_t)sb] & 1023, by = coord[(size_t)sb] >> 10 & 1023, bz = coord[(size_t)sb] >> 20 & 1023;
+            int bx, by, bz;
+            bd_unpack(coord[(size_t)sb], &bx, &by, &bz);
             for (int lane = 0; lane < 64; ++lane) {
                 const int ix = 4 * bx + (lane & 3), iy = 4 * by + (lane >> 2 & 3), iz = 4 * bz + (lane >> 4);
                 if (ix <= gd.G && iy <= gd.G && iz <= gd.G) node_sums[((int64_t)iz * n1 + iy) * n1 + ix] = hs[(size_t)(sb * 64 + lane)];
@@ -929,17 +658,17 @@ struct BdRun {
         L.e = bd_extent(l);
         L.g = grid_of(l);
         const BdExtent& e = L.e;
-        const unsigned tgrid = bd_grid(e.table), rgrid = (unsigned)((e.rows + BD_WAVES - 1) / BD_WAVES);
+        const unsigned tgrid = bd_grid(e.table), rgrid = (unsigned)((e.rows + PN_WAVES - 1) / PN_WAVES);
         Scratch ta, tb, rcnt;
         if ((rc = take(ta, e.table)) || (rc = take(tb, e.table)) || (rc = take(rcnt, 4 * e.rows)) || (rc = take(L.act, e.table, &L.held)) ||
             (rc = take(L.num, 4 * e.table, &L.held)) || (rc = take(L.first, 4 * (e.rows + 1), &L.held))) return rc;
         HIPCHK(hipMemsetAsync(ta.p, 0, (size_t)e.table, s));
-        k_bd_mark<<<dim3(bd_grid(n)), dim3(BD_TPB), 0, s>>>(n, pts, nrm, L.g, e.T, ta.as<uint8_t>());
-        k_bd_dilate<<<dim3(tgrid), dim3(BD_TPB), 0, s>>>(e.T, e.Gb, ta.as<uint8_t>(), tb.as<uint8_t>(), 0, bp.band);
-        k_bd_dilate<<<dim3(tgrid), dim3(BD_TPB), 0, s>>>(e.T, e.Gb, tb.as<uint8_t>(), ta.as<uint8_t>(), 1, bp.band);
-        k_bd_dilate<<<dim3(tgrid), dim3(BD_TPB), 0, s>>>(e.T, e.Gb, ta.as<uint8_t>(), L.act.as<uint8_t>(), 2, bp.band);
-        k_bd_stored<<<dim3(tgrid), dim3(BD_TPB), 0, s>>>(e.T, L.act.as<uint8_t>(), tb.as<uint8_t>());
-        k_bd_row_count<<<dim3(rgrid), dim3(BD_TPB), 0, s>>>(e.T, tb.as<uint8_t>(), rcnt.as<int32_t>());
+        k_bd_mark<<<dim3(bd_grid(n)), dim3(PN_TPB), 0, s>>>(n, pts, nrm, L.g, e.T, ta.as<uint8_t>());
+        k_bd_dilate<<<dim3(tgrid), dim3(PN_TPB), 0, s>>>(e.T, e.Gb, ta.as<uint8_t>(), tb.as<uint8_t>(), 0, bp.band);
+        k_bd_dilate<<<dim3(tgrid), dim3(PN_TPB), 0, s>>>(e.T, e.Gb, tb.as<uint8_t>(), ta.as<uint8_t>(), 1, bp.band);
+        k_bd_dilate<<<dim3(tgrid), dim3(PN_TPB), 0, s>>>(e.T, e.Gb, ta.as<uint8_t>(), L.act.as<uint8_t>(), 2, bp.band);
+        k_bd_stored<<<dim3(tgrid), dim3(PN_TPB), 0, s>>>(e.T, L.act.as<uint8_t>(), tb.as<uint8_t>());
+        k_bd_row_count<<<dim3(rgrid), dim3(PN_TPB), 0, s>>>(e.T, tb.as<uint8_t>(), rcnt.as<int32_t>());
         HIPCHK(hipGetLastError());
         std::vector<int32_t> hc((size_t)e.rows), hf((size_t)e.rows + 1);
         if ((rc = fetch(hc.data(), rcnt.p, 4 * (size_t)e.rows))) return rc;
@@ -960,8 +689,8 @@ struct BdRun {
         }
         if ((rc = take(L.coord, 4 * L.ns, &L.held)) || (rc = take(L.nbr, 24 * L.ns, &L.held))) return rc;
         HIPCHK(hipMemcpy(L.first.p, hf.data(), 4 * hf.size(), hipMemcpyHostToDevice));       // the stream is idle: fetch synchronised it
-        k_bd_number<<<dim3(rgrid), dim3(BD_TPB), 0, s>>>(e.T, tb.as<uint8_t>(), L.first.as<int32_t>(), L.num.as<int32_t>(), L.coord.as<int32_t>());
-        if (L.ns > 0) k_bd_neighbours<<<dim3(bd_grid(6 * L.ns)), dim3(BD_TPB), 0, s>>>(L.ns, L.coord.as<int32_t>(), L.view(), L.nbr.as<int32_t>());
+        k_bd_number<<<dim3(rgrid), dim3(PN_TPB), 0, s>>>(e.T, tb.as<uint8_t>(), L.first.as<int32_t>(), L.num.as<int32_t>(), L.coord.as<int32_t>());
+        if (L.ns > 0) k_bd_neighbours<<<dim3(bd_grid(6 * L.ns)), dim3(PN_TPB), 0, s>>>(L.ns, L.coord.as<int32_t>(), L.view(), L.nbr.as<int32_t>());
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(s));                                      // ta, tb and rcnt go
         bytes.give(2 * e.table + 4 * e.rows);
@@ -977,17 +706,17 @@ struct BdRun {
         if (L.ns == 0) return MVS_OK;
         const BdView v = L.view();
         const unsigned ngrid = bd_grid(L.nodes);
-        k_bd_class_start<Coarse><<<dim3(ngrid), dim3(BD_TPB), 0, s>>>(L.ns, L.coord.as<int32_t>(), v, coarse, L.cls.as<uint8_t>(), L.x.as<double>());
+        k_bd_class_start<Coarse><<<dim3(ngrid), dim3(PN_TPB), 0, s>>>(L.ns, L.coord.as<int32_t>(), v, coarse, L.cls.as<uint8_t>(), L.x.as<double>());
         HIPCHK(hipMemsetAsync(L.sums.p, 0, (size_t)(24 * L.nodes), s));
-        if (weighted()) k_bd_splat<true><<<dim3(bd_grid(n)), dim3(BD_TPB), 0, s>>>(n, pts, nrm, L.g, v, L.nodes, L.sums.as<unsigned long long>(), gain.as<double>());
-        else k_bd_splat<false><<<dim3(bd_grid(n)), dim3(BD_TPB), 0, s>>>(n, pts, nrm, L.g, v, L.nodes, L.sums.as<unsigned long long>(), nullptr);
-        k_bd_rhs<<<dim3(ngrid), dim3(BD_TPB), 0, s>>>(L.ns, L.nbr.as<int32_t>(), L.cls.as<uint8_t>(), L.nodes, L.sums.as<long long>(), L.g.h, L.b.as<double>());
+        if (weighted()) k_bd_splat<true><<<dim3(bd_grid(n)), dim3(PN_TPB), 0, s>>>(n, pts, nrm, L.g, v, L.nodes, L.sums.as<unsigned long long>(), gain.as<double>());
+        else k_bd_splat<false><<<dim3(bd_grid(n)), dim3(PN_TPB), 0, s>>>(n, pts, nrm, L.g, v, L.nodes, L.sums.as<unsigned long long>(), nullptr);
+        k_bd_rhs<<<dim3(ngrid), dim3(PN_TPB), 0, s>>>(L.ns, L.nbr.as<int32_t>(), L.cls.as<uint8_t>(), L.nodes, L.sums.as<long long>(), L.g.h, L.b.as<double>());
         HIPCHK(hipGetLastError());
         return count(L.cls.as<uint8_t>(), L.nodes, true, &binfo.n_free[l]);
     }
 
     int folded(int np, double* part, double* out) {
-        k_bd_fold<<<dim3(1), dim3(BD_TPB), 0, s>>>(part, np, red.as<double>());
+        poisson_fold(part, np, red.as<double>(), s);
         HIPCHK(hipGetLastError());
         return fetch(out, red.p, 8);
     }
@@ -996,8 +725,8 @@ struct BdRun {
     int solve(BdLevel& L, int l) {
         int rc;
         if (L.ns == 0) return MVS_OK;
-        const int np = (int)std::min<int64_t>((L.ns + BD_WAVES - 1) / BD_WAVES, BD_NPART);
-        const dim3 gr((unsigned)np), tb(BD_TPB);
+        const int np = (int)std::min<int64_t>((L.ns + PN_WAVES - 1) / PN_WAVES, BD_NPART);
+        const dim3 gr((unsigned)np), tb(PN_TPB);
         double* part[4];                                                     // r . r twice (this iteration's and the one before), p . A p, the true residual
         for (int q = 0; q < 4; ++q) part[q] = red.as<double>() + 1 + q * BD_NPART;
         const int32_t* nbr = L.nbr.as<int32_t>();
@@ -1058,7 +787,8 @@ struct BdRun {
         const double nan = std::numeric_limits<double>::quiet_NaN();
         for (int64_t i = 0; i < nn; ++i) { d.cls[i] = BD_NONE; d.b[i] = nan; d.chi[i] = nan; }
         for (int64_t sb = 0; sb < L.ns; ++sb) {
-            const int bx = coord[(size_t)sb] & 1023, by = coord[(size_t)sb] >> 10 & 1023, bz = coord[(size_t)sb] >> 20 & 1023;
+            int bx, by, bz;
+            bd_unpack(coord[(size_t)sb], &bx, &by, &bz);
             for (int lane = 0; lane < 64; ++lane) {
                 const int ix = 4 * bx + (lane & 3), iy = 4 * by + (lane >> 2 & 3), iz = 4 * bz + (lane >> 4);
                 const size_t at = (size_t)(sb * 64 + lane);
@@ -1113,17 +843,17 @@ struct BdRun {
     int iso_value() {
         int rc;
         const BdLevel& L = *top;
-        const int64_t m = info.n_used, nbu = (n + BD_TPB - 1) / BD_TPB;
-        BdScan us;
+        const int64_t m = info.n_used, nbu = (n + PN_TPB - 1) / PN_TPB;
+        PnScan us;
         Scratch used;
         if ((rc = us.alloc((size_t)nbu, s)) || (rc = take(used, 8 * m))) return rc;
         bytes.take(us.bytes);
-        k_bd_used_count<<<dim3((unsigned)nbu), dim3(BD_TPB), 0, s>>>(n, pts, nrm, us.cnt.as<int32_t>());
+        k_bd_used_count<<<dim3((unsigned)nbu), dim3(PN_TPB), 0, s>>>(n, pts, nrm, us.cnt.as<int32_t>());
         us.run((int)nbu, s);
-        k_bd_used_scatter<<<dim3((unsigned)nbu), dim3(BD_TPB), 0, s>>>(n, pts, nrm, us.base.as<int32_t>(), used.as<int64_t>());
-        const int nb = (int)std::min<int64_t>(BD_RED_NB, (m + BD_TPB - 1) / BD_TPB);
+        k_bd_used_scatter<<<dim3((unsigned)nbu), dim3(PN_TPB), 0, s>>>(n, pts, nrm, us.base.as<int32_t>(), used.as<int64_t>());
+        const int nb = (int)std::min<int64_t>(BD_RED_NB, (m + PN_TPB - 1) / PN_TPB);
         double* part = red.as<double>() + 1;
-        k_bd_iso<<<dim3((unsigned)nb), dim3(BD_TPB), 0, s>>>(m, used.as<int64_t>(), pts, L.g, L.view(), L.x.as<double>(), part);
+        k_bd_iso<<<dim3((unsigned)nb), dim3(PN_TPB), 0, s>>>(m, used.as<int64_t>(), pts, L.g, L.view(), L.x.as<double>(), part);
         double sum = 0.0;
         rc = folded(nb, part, &sum);                                          // synchronises: used and the scan may go
         bytes.give(us.bytes + 8 * m);
@@ -1134,7 +864,7 @@ struct BdRun {
 
     BdSurf surf() const {
         const BdLevel& L = *top;
-        return BdSurf{L.view(), L.g, L.coord.as<int32_t>(), rows.as<int32_t>(), L.x.as<double>(), iso, L.nodes};
+        return BdSurf{L.view(), L.g, L.coord.as<int32_t>(), rows.as<int32_t>(), L.x.as<double>(), iso, L.nodes, cnt8.as<unsigned long long>()};
     }
 
     // rules 30-31 up to the counts
@@ -1144,17 +874,17 @@ struct BdRun {
         if (L.ns == 0) return MVS_OK;
         edge_items = 7 * L.nodes;
         face_items = 12 * L.nodes;
-        const int64_t nbe = (edge_items + BD_TPB - 1) / BD_TPB, nbf = (face_items + BD_TPB - 1) / BD_TPB;
-        if ((rc = take(rows, 64 * L.ns)) || (rc = take(mask, L.nodes)) || (rc = take(words, 8 * BD_WAVES * nbe)) || (rc = ve.alloc((size_t)nbe, s)) ||
+        const int64_t nbe = (edge_items + PN_TPB - 1) / PN_TPB, nbf = (face_items + PN_TPB - 1) / PN_TPB;
+        if ((rc = take(rows, 64 * L.ns)) || (rc = take(mask, L.nodes)) || (rc = take(words, 8 * PN_WAVES * nbe)) || (rc = ve.alloc((size_t)nbe, s)) ||
             (rc = fa.alloc((size_t)nbf, s))) return rc;
         bytes.take(ve.bytes + fa.bytes);
-        k_bd_rows<<<dim3(bd_grid(16 * L.ns)), dim3(BD_TPB), 0, s>>>(L.ns, L.coord.as<int32_t>(), L.view(), rows.as<int32_t>());
+        k_bd_rows<<<dim3(bd_grid(16 * L.ns)), dim3(PN_TPB), 0, s>>>(L.ns, L.coord.as<int32_t>(), L.view(), rows.as<int32_t>());
         const BdSurf q = surf();
         HIPCHK(hipMemsetAsync(cnt8.p, 0, 8, s));
-        k_bd_cubemask<<<dim3(bd_grid(L.nodes)), dim3(BD_TPB), 0, s>>>(q, mask.as<uint8_t>());
-        k_bd_edge_count<<<dim3((unsigned)nbe), dim3(BD_TPB), 0, s>>>(q, edge_items, words.as<unsigned long long>(), ve.cnt.as<int32_t>(), cnt8.as<unsigned long long>());
+        k_pn_cubemask<<<dim3(bd_grid(L.nodes)), dim3(PN_TPB), 0, s>>>(q, mask.as<uint8_t>());
+        k_pn_edge_count<<<dim3((unsigned)nbe), dim3(PN_TPB), 0, s>>>(q, edge_items, words.as<unsigned long long>(), ve.cnt.as<int32_t>());
         ve.run((int)nbe, s);
-        k_bd_face_count<<<dim3((unsigned)nbf), dim3(BD_TPB), 0, s>>>(mask.as<uint8_t>(), face_items, fa.cnt.as<int32_t>());
+        poisson_face_count(mask.as<uint8_t>(), face_items, fa.cnt.as<int32_t>(), s);
         fa.run((int)nbf, s);
         HIPCHK(hipGetLastError());
         int32_t nv = 0, nf = 0;
@@ -1170,10 +900,10 @@ struct BdRun {
 
     int scatter(double* vertices, int32_t* faces) {
         if (info.n_vertices == 0) return MVS_OK;
-        const int64_t nbe = (edge_items + BD_TPB - 1) / BD_TPB, nbf = (face_items + BD_TPB - 1) / BD_TPB;
+        const int64_t nbe = (edge_items + PN_TPB - 1) / PN_TPB, nbf = (face_items + PN_TPB - 1) / PN_TPB;
         const BdSurf q = surf();
-        k_bd_vertex_scatter<<<dim3((unsigned)nbe), dim3(BD_TPB), 0, s>>>(q, edge_items, words.as<unsigned long long>(), ve.base.as<int32_t>(), vertices);
-        k_bd_face_scatter<<<dim3((unsigned)nbf), dim3(BD_TPB), 0, s>>>(q, mask.as<uint8_t>(), face_items, words.as<unsigned long long>(), ve.base.as<int32_t>(),
+        k_pn_vertex_scatter<<<dim3((unsigned)nbe), dim3(PN_TPB), 0, s>>>(q, edge_items, words.as<unsigned long long>(), ve.base.as<int32_t>(), vertices);
+        k_pn_face_scatter<<<dim3((unsigned)nbf), dim3(PN_TPB), 0, s>>>(q, mask.as<uint8_t>(), face_items, words.as<unsigned long long>(), ve.base.as<int32_t>(),
                                                                       vertices, fa.base.as<int32_t>(), faces);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(s));
@@ -1187,29 +917,6 @@ struct BdRun {
     }
 };
 
-// where the call writes, on the device: the caller's arrays, or — bv set — blocks sized once the counts are known (PnOut of poisson.hip)
-struct BdOut {
-    double* vertices;
-    int32_t* faces;
-    int64_t vcap, fcap;
-    Scratch *bv, *bf;
-    double* density = nullptr;            // rule 34 per vertex; NULL (and bd NULL): not wanted
-    Scratch* bd = nullptr;
-};
-
-struct BdCall {
-    const char* fn;
-    int64_t n;
-    const double *points, *normals;
-    const mvs_poisson_params* p;
-    const mvs_poisson_band_params* bp;
-    mvs_poisson_info* info;
-    mvs_poisson_band_info* binfo;
-    const mvs_poisson_density_params* dp = nullptr;      // mvs_poisson_reconstruct_band_density: rules 32-35; the band call has neither
-    mvs_poisson_density_info* dinfo = nullptr;
-    bool density = false;
-};
-
 int check_band_call(const BdCall& c, const void* out_a, int64_t cap_a, const void* out_b, int64_t cap_b) {
     const PnCall pc{c.fn, PN_PLAIN, c.n, c.points, c.normals, c.p, c.info, nullptr, nullptr, nullptr, nullptr};
     int rc = poisson_check_plain(pc, BD_MAX_D, out_a, cap_a, out_b, cap_b);
@@ -1218,51 +925,66 @@ int check_band_call(const BdCall& c, const void* out_a, int64_t cap_a, const voi
 }
 
 // the device form of the entry, after its checks
-int band_reconstruct(const BdCall& c, const double* pts, const double* nrm, BdOut o, hipStream_t s) {
+int band_reconstruct(const BdCall& c, const double* pts, const double* nrm, PnOut o, hipStream_t s) {
     int rc;
-    BdRun run(c.fn, *c.p, *c.bp, *c.info, *c.binfo, c.n, pts, nrm, s, c.dp, c.dinfo);
+    BdRun run(c, pts, nrm, s);
     if ((rc = run.depth())) return rc;
     if (run.D <= run.B) {                                                     // rules 24 and 32: the plain or the density call at depth D, its bytes
         mvs_poisson_params pd = *c.p;
         pd.depth_min = pd.depth_max = run.D;
-        const PnCall pc{c.fn, c.density ? PN_DENSITY : PN_PLAIN, c.n, pts, nrm, &pd, c.info, c.dp, c.dinfo, nullptr, nullptr};
-        if (c.density) return poisson_density_dev(pc, pts, nrm, o.vertices, o.density, o.vcap, o.faces, o.fcap, o.bv, o.bd, o.bf, s);
-        return poisson_plain_dev(pc, pts, nrm, o.vertices, o.vcap, o.faces, o.fcap, o.bv, o.bf, s);
+        return poisson_dense_dev(PnCall{c.fn, c.density ? PN_DENSITY : PN_PLAIN, c.n, pts, nrm, &pd, c.info, c.dp, c.dinfo, nullptr, nullptr}, pts, nrm, o, s);
     }
     if (c.density && (rc = run.density())) { run.finish_info(); return rc; }
     rc = run.levels(nullptr);
     run.finish_info();
     if (rc || (rc = run.iso_value()) || (rc = run.count_mesh())) { run.finish_info(); return rc; }
     run.finish_info();
-    const int64_t V = c.info->n_vertices, F = c.info->n_faces;
-    if (!bd_capacity_ok(V, F, o.vcap, o.fcap)) return bad(c.fn, "a capacity is below the count (info holds n_vertices and n_faces)");
-    if (o.bv) {
-        if ((rc = o.bv->alloc(24 * (size_t)V)) || (rc = o.bf->alloc(12 * (size_t)F)) || (o.bd && (rc = o.bd->alloc(8 * (size_t)V)))) return rc;
-        o.vertices = o.bv->as<double>();
-        o.faces = o.bf->as<int32_t>();
-        o.density = o.bd ? o.bd->as<double>() : nullptr;
+    return poisson_finish(c.fn, run, *c.info, o);
+}
+
+// the host form of the two entries: the points go up, the device form fills blocks, the blocks come down
+int band_reconstruct_host(const BdCall& c, double* vertices, double* density, int64_t vcap, int32_t* faces, int64_t fcap) {
+    Scratch dp, dn, dv, dd, df;
+    int rc = check_band_call(c, vertices, vcap, faces, fcap);
+    if (rc || (rc = need_device()) || (rc = up(dp, c.points, 3 * (size_t)c.n)) || (rc = up(dn, c.normals, 3 * (size_t)c.n)) ||
+        (rc = band_reconstruct(c, dp.as<double>(), dn.as<double>(), PnOut{nullptr, nullptr, nullptr, vcap, fcap, &dv, density ? &dd : nullptr, &df}, nullptr)))
+        return rc;
+    const size_t V = (size_t)c.info->n_vertices, F = (size_t)c.info->n_faces;
+    if ((density && (rc = down(density, dd, V))) || (rc = down(vertices, dv, 3 * V))) return rc;
+    return down(faces, df, 3 * F);
+}
+
+// The two hooks after their checks: the call up to rule 29, level d.level handed out dense; with rules 32-33 (c.density) the density too.
+// MVS_E_SOLVER of that level still hands out what it reached.
+int band_level(const BdCall& c, const BdDump& d, int64_t* node_sums, int64_t density_node_capacity, double* rho, double* gain) {
+    Scratch dp, dn;
+    int rc;
+    if ((rc = need_device()) || (rc = up(dp, c.points, 3 * (size_t)c.n)) || (rc = up(dn, c.normals, 3 * (size_t)c.n))) return rc;
+    BdRun run(c, dp.as<double>(), dn.as<double>(), nullptr);
+    if ((rc = run.depth())) return rc;
+    run.finish_info();
+    if (d.level <= run.B || d.level > run.D) return bad(c.fn, "level is outside base_depth + 1 .. depth (info and binfo hold them)");
+    if (c.density) {
+        rc = run.density();
+        run.finish_info();
+        if (rc || (rc = run.dump_density(node_sums, density_node_capacity, rho, gain))) return rc;
     }
-    if ((rc = run.scatter(o.vertices, o.faces))) return rc;
-    return c.density ? run.vertex_density(o.vertices, o.density) : MVS_OK;
+    rc = run.levels(&d);
+    run.finish_info();
+    if (rc) return rc;
+    rc = run.iso_value();
+    run.finish_info();
+    return rc;
 }
 
 }  // namespace
 
-// the device form for a caller inside the library that cannot know the counts in advance (mvs_processor_poisson_band)
-int poisson_band_blocks(const char* fn, int64_t n, const double* pts_dev, const double* nrm_dev, const mvs_poisson_params* p,
-                        const mvs_poisson_band_params* bp, mvs_poisson_info* info, mvs_poisson_band_info* binfo, Scratch* vertices, Scratch* faces) {
-    const BdCall c{fn, n, pts_dev, nrm_dev, p, bp, info, binfo};
+// the device form for a caller inside the library that cannot know the counts in advance (mvs_processor_poisson_band and
+// mvs_processor_poisson_band_density); c.density: density receives d_v of rule 34 per vertex
+int poisson_band_blocks(const BdCall& c, Scratch* vertices, Scratch* density, Scratch* faces) {
     const int rc = check_band_call(c, nullptr, 0, nullptr, 0);
-    return rc ? rc : band_reconstruct(c, pts_dev, nrm_dev, BdOut{nullptr, nullptr, INT64_MAX, INT64_MAX, vertices, faces}, nullptr);
-}
-
-// ... and for mvs_poisson_reconstruct_band_density (mvs_processor_poisson_band_density); density receives d_v of rule 34 per vertex
-int poisson_band_density_blocks(const char* fn, int64_t n, const double* pts_dev, const double* nrm_dev, const mvs_poisson_params* p,
-                                const mvs_poisson_band_params* bp, const mvs_poisson_density_params* dp, mvs_poisson_info* info,
-                                mvs_poisson_band_info* binfo, mvs_poisson_density_info* dinfo, Scratch* vertices, Scratch* density, Scratch* faces) {
-    const BdCall c{fn, n, pts_dev, nrm_dev, p, bp, info, binfo, dp, dinfo, true};
-    const int rc = check_band_call(c, nullptr, 0, nullptr, 0);
-    return rc ? rc : band_reconstruct(c, pts_dev, nrm_dev, BdOut{nullptr, nullptr, INT64_MAX, INT64_MAX, vertices, faces, nullptr, density}, nullptr);
+    if (rc) return rc;
+    return band_reconstruct(c, c.points, c.normals, PnOut{nullptr, nullptr, nullptr, INT64_MAX, INT64_MAX, vertices, c.density ? density : nullptr, faces}, nullptr);
 }
 
 extern "C" {
@@ -1279,22 +1001,14 @@ int mvs_poisson_reconstruct_band_dev(int64_t n, const double* points_dev, const 
     const BdCall c{__func__, n, points_dev, normals_dev, p, bparams, info, binfo};
     int rc = check_band_call(c, vertices_dev, vertex_capacity, faces_dev, face_capacity);
     if (rc || (rc = need_device())) return rc;
-    return band_reconstruct(c, points_dev, normals_dev, BdOut{vertices_dev, faces_dev, vertex_capacity, face_capacity, nullptr, nullptr}, (hipStream_t)hip_stream);
+    return band_reconstruct(c, points_dev, normals_dev, PnOut{vertices_dev, nullptr, faces_dev, vertex_capacity, face_capacity}, (hipStream_t)hip_stream);
 }
 
 int mvs_poisson_reconstruct_band(int64_t n, const double* points, const double* normals, const mvs_poisson_params* p,
                                  const mvs_poisson_band_params* bparams, mvs_poisson_info* info, mvs_poisson_band_info* binfo, double* vertices,
                                  int64_t vertex_capacity, int32_t* faces, int64_t face_capacity) {
     MVS_TRACE();
-    const BdCall c{__func__, n, points, normals, p, bparams, info, binfo};
-    Scratch dp, dn, dv, df;
-    int rc = check_band_call(c, vertices, vertex_capacity, faces, face_capacity);
-    if (rc || (rc = need_device()) || (rc = up(dp, points, 3 * (size_t)n)) || (rc = up(dn, normals, 3 * (size_t)n)) ||
-        (rc = band_reconstruct(c, dp.as<double>(), dn.as<double>(), BdOut{nullptr, nullptr, vertex_capacity, face_capacity, &dv, &df}, nullptr)))
-        return rc;
-    const size_t V = (size_t)info->n_vertices, F = (size_t)info->n_faces;
-    if ((rc = down(vertices, dv, 3 * V))) return rc;
-    return down(faces, df, 3 * F);
+    return band_reconstruct_host(BdCall{__func__, n, points, normals, p, bparams, info, binfo}, vertices, nullptr, vertex_capacity, faces, face_capacity);
 }
 
 // The call up to rule 29, level `level` handed out dense (include/mvs_test.h).  MVS_E_SOLVER of that level still hands out what it reached.
@@ -1303,22 +1017,10 @@ int mvs_test_poisson_band_level(int64_t n, const double* points, const double* n
                                 uint8_t* active, uint8_t* cls, double* b, double* chi, int64_t node_capacity) {
     MVS_TRACE();
     const BdCall c{__func__, n, points, normals, p, bparams, info, binfo};
-    Scratch dp, dn;
-    int rc = check_band_call(c, b, node_capacity, chi, node_capacity);
+    const int rc = check_band_call(c, b, node_capacity, chi, node_capacity);
     if (rc) return rc;
     if (!active || !cls || !b || !chi) return bad(__func__, "active, cls, b or chi is NULL");
-    if ((rc = need_device()) || (rc = up(dp, points, 3 * (size_t)n)) || (rc = up(dn, normals, 3 * (size_t)n))) return rc;
-    BdRun run(__func__, *p, *bparams, *info, *binfo, n, dp.as<double>(), dn.as<double>(), nullptr);
-    if ((rc = run.depth())) return rc;
-    run.finish_info();
-    if (level <= run.B || level > run.D) return bad(__func__, "level is outside base_depth + 1 .. depth (info and binfo hold them)");
-    const BdDump d{level, active, cls, b, chi, node_capacity};
-    rc = run.levels(&d);
-    run.finish_info();
-    if (rc) return rc;
-    rc = run.iso_value();
-    run.finish_info();
-    return rc;
+    return band_level(c, BdDump{level, active, cls, b, chi, node_capacity}, nullptr, 0, nullptr, nullptr);
 }
 
 // ------------------------------------------------------------------ rules 32-35 ----
@@ -1331,8 +1033,7 @@ int mvs_poisson_reconstruct_band_density_dev(int64_t n, const double* points_dev
     const BdCall c{__func__, n, points_dev, normals_dev, p, bparams, info, binfo, dparams, dinfo, true};
     int rc = check_band_call(c, vertices_dev, vertex_capacity, faces_dev, face_capacity);
     if (rc || (rc = need_device())) return rc;
-    return band_reconstruct(c, points_dev, normals_dev, BdOut{vertices_dev, faces_dev, vertex_capacity, face_capacity, nullptr, nullptr, vertex_density_dev, nullptr},
-                            (hipStream_t)hip_stream);
+    return band_reconstruct(c, points_dev, normals_dev, PnOut{vertices_dev, vertex_density_dev, faces_dev, vertex_capacity, face_capacity}, (hipStream_t)hip_stream);
 }
 
 int mvs_poisson_reconstruct_band_density(int64_t n, const double* points, const double* normals, const mvs_poisson_params* p,
@@ -1340,16 +1041,8 @@ int mvs_poisson_reconstruct_band_density(int64_t n, const double* points, const 
                                          mvs_poisson_band_info* binfo, mvs_poisson_density_info* dinfo, double* vertices, double* vertex_density,
                                          int64_t vertex_capacity, int32_t* faces, int64_t face_capacity) {
     MVS_TRACE();
-    const BdCall c{__func__, n, points, normals, p, bparams, info, binfo, dparams, dinfo, true};
-    Scratch dp, dn, dv, dd, df;
-    int rc = check_band_call(c, vertices, vertex_capacity, faces, face_capacity);
-    if (rc || (rc = need_device()) || (rc = up(dp, points, 3 * (size_t)n)) || (rc = up(dn, normals, 3 * (size_t)n)) ||
-        (rc = band_reconstruct(c, dp.as<double>(), dn.as<double>(),
-                               BdOut{nullptr, nullptr, vertex_capacity, face_capacity, &dv, &df, nullptr, vertex_density ? &dd : nullptr}, nullptr)))
-        return rc;
-    const size_t V = (size_t)info->n_vertices, F = (size_t)info->n_faces;
-    if ((vertex_density && (rc = down(vertex_density, dd, V))) || (rc = down(vertices, dv, 3 * V))) return rc;
-    return down(faces, df, 3 * F);
+    return band_reconstruct_host(BdCall{__func__, n, points, normals, p, bparams, info, binfo, dparams, dinfo, true}, vertices, vertex_density,
+                                 vertex_capacity, faces, face_capacity);
 }
 
 // The call up to rule 29 with rules 32-33, level `level` and the density handed out dense (include/mvs_test.h)
@@ -1360,25 +1053,10 @@ int mvs_test_poisson_band_density_level(int64_t n, const double* points, const d
                                         double* gain) {
     MVS_TRACE();
     const BdCall c{__func__, n, points, normals, p, bparams, info, binfo, dparams, dinfo, true};
-    Scratch dp, dn;
-    int rc = check_band_call(c, b, node_capacity, node_sums, density_node_capacity);
+    const int rc = check_band_call(c, b, node_capacity, node_sums, density_node_capacity);
     if (rc) return rc;
     if (!active || !cls || !b || !chi || !node_sums || !rho || !gain) return bad(__func__, "active, cls, b, chi, node_sums, rho or gain is NULL");
-    if ((rc = need_device()) || (rc = up(dp, points, 3 * (size_t)n)) || (rc = up(dn, normals, 3 * (size_t)n))) return rc;
-    BdRun run(__func__, *p, *bparams, *info, *binfo, n, dp.as<double>(), dn.as<double>(), nullptr, dparams, dinfo);
-    if ((rc = run.depth())) return rc;
-    run.finish_info();
-    if (level <= run.B || level > run.D) return bad(__func__, "level is outside base_depth + 1 .. depth (info and binfo hold them)");
-    rc = run.density();
-    run.finish_info();
-    if (rc || (rc = run.dump_density(node_sums, density_node_capacity, rho, gain))) return rc;
-    const BdDump d{level, active, cls, b, chi, node_capacity};
-    rc = run.levels(&d);
-    run.finish_info();
-    if (rc) return rc;
-    rc = run.iso_value();
-    run.finish_info();
-    return rc;
+    return band_level(c, BdDump{level, active, cls, b, chi, node_capacity}, node_sums, density_node_capacity, rho, gain);
 }
 
 }  // extern "C"

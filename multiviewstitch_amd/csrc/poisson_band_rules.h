@@ -114,21 +114,26 @@ __host__ __device__ inline double bd_density_at(const double* p, const PnGrid& g
     for (int c = 0; c < 8; ++c) v = v + w[c] * pn_dequant(sum(i0[0] + (c & 1), i0[1] + (c >> 1 & 1), i0[2] + (c >> 2 & 1)));
     return v;
 }
-// sum() of bd_density_at over block storage: 64 sums per stored block behind the table of bd_node_slot
+// sum() of bd_density_at over block storage: 64 sums per stored block behind the table of bd_node_slot.  slot: where the sum of a node
+// lies, -1 for a node without storage; dense: every node has storage, known when the code is compiled
 struct BdBlockSums {
+    static constexpr bool dense = false;
     const int32_t* num;
     int32_t T;
     const long long* sums;
+    __host__ __device__ int64_t slot(int ix, int iy, int iz) const { return bd_node_slot(num, T, ix, iy, iz); }
     __host__ __device__ long long operator()(int ix, int iy, int iz) const {
-        const int64_t at = bd_node_slot(num, T, ix, iy, iz);
+        const int64_t at = slot(ix, iy, iz);
         return at < 0 ? 0 : sums[at];
     }
 };
 // ... and over a dense array in node order
 struct BdDenseSums {
+    static constexpr bool dense = true;
     int32_t G;
     const long long* sums;
-    __host__ __device__ long long operator()(int ix, int iy, int iz) const { return sums[pn_node(G, ix, iy, iz)]; }
+    __host__ __device__ int64_t slot(int ix, int iy, int iz) const { return pn_node(G, ix, iy, iz); }
+    __host__ __device__ long long operator()(int ix, int iy, int iz) const { return sums[slot(ix, iy, iz)]; }
 };
 
 #endif

@@ -50,13 +50,21 @@ struct PnCall {
 // PN_PLAIN, density (d_v of rule 17 per vertex) are allocated once info holds the counts.  Validates like the public entry; the caller
 // has a device.  Default stream.
 int poisson_blocks(const PnCall& c, Scratch* vertices, Scratch* density, Scratch* faces);
-// the same for mvs_poisson_reconstruct_band (poisson_band.hip)
-int poisson_band_blocks(const char* fn, int64_t n, const double* pts_dev, const double* nrm_dev, const mvs_poisson_params* p,
-                        const mvs_poisson_band_params* bp, mvs_poisson_info* info, mvs_poisson_band_info* binfo, Scratch* vertices, Scratch* faces);
-// ... and for mvs_poisson_reconstruct_band_density: density receives d_v of rule 34 per vertex
-int poisson_band_density_blocks(const char* fn, int64_t n, const double* pts_dev, const double* nrm_dev, const mvs_poisson_params* p,
-                                const mvs_poisson_band_params* bp, const mvs_poisson_density_params* dp, mvs_poisson_info* info,
-                                mvs_poisson_band_info* binfo, mvs_poisson_density_info* dinfo, Scratch* vertices, Scratch* density, Scratch* faces);
+// A call of mvs_poisson_reconstruct_band or — density set — mvs_poisson_reconstruct_band_density (poisson_band.hip), whichever entry made it
+struct BdCall {
+    const char* fn;
+    int64_t n;
+    const double *points, *normals;
+    const mvs_poisson_params* p;
+    const mvs_poisson_band_params* bp;
+    mvs_poisson_info* info;
+    mvs_poisson_band_info* binfo;
+    const mvs_poisson_density_params* dp = nullptr;      // rules 32-35; the band call has neither
+    mvs_poisson_density_info* dinfo = nullptr;
+    bool density = false;
+};
+// poisson_blocks for the two band calls, the points on the device; density (used when c.density) receives d_v of rule 34 per vertex
+int poisson_band_blocks(const BdCall& c, Scratch* vertices, Scratch* density, Scratch* faces);
 // mvs_mesh_trim_by_value_dev (mesh_trim.hip, rule 18) with arguments the caller has validated.  Synchronises s.
 int mesh_trim_dev(int64_t V, const double* vertices, const double* normals, int64_t F, const int32_t* faces, const double* values, double thr,
                   double* vertices_out, double* normals_out, int32_t* faces_out, int64_t* V_out, int64_t* F_out, hipStream_t s);

@@ -1,4 +1,4 @@
-"""The bytes of the Poisson stage (csrc/poisson.hip, csrc/mesh_trim.hip), recorded: for every case below the sha256 of the raw bytes of
+"""The bytes of the Poisson stage (csrc/poisson.hip, csrc/poisson_band.hip, csrc/mesh_trim.hip), recorded: for every case below the sha256 of the raw bytes of
 every output array, the integer and floating fields of the info structs (floats as float.hex()) and the return code.  The library is built
 with -ffp-contract=off and nothing in the stage but integer atomics is unordered, so these digests are a function of the written fp64
 operations and their order; tests/test_gpu_poisson_bits.py holds every build to the recording in tests/golden/poisson_bits.json.  The
@@ -13,6 +13,18 @@ The cases are the smallest that reach each path of the solver, at solve_tol = 1e
                        diagonals 1 and 2 on `d4` and `d6`
   depth7/<call>        the three public host calls on poisson_scenes.big_sphere() at depth 7: two launched levels above the coarse kernel
   trim/open            mvs_mesh_trim_by_value on the mesh of `open` at TRIM_RATIO
+and for the band levels (rules 24-35), whose conjugate gradients, iso sum and extraction the restatements hold to a bound only:
+  band/<scene>         RunPoissonBand on `two_levels`, `clipped`, `hemisphere`, `cap`, `all_active` of tests/poisson_band_scenes.py: both
+                       forms of the level below, the grid boundary, base depth 3, open edges, the band that is the whole grid; the mesh,
+                       info and the band info (scratch_bytes of rule 35 included)
+  band_level/two_levels/<l>
+                       mvs_test_poisson_band_level on levels 5 and 6: active, cls, b, chi
+  band_density/<scene>[/unweighted]
+                       RunPoissonBandDensity with MVS_POISSON_WEIGHT_NORMALS on `uneven6` (the sums in blocks), `uneven6_drop2` (dense
+                       sums) and `open6` of tests/poisson_band_density_scenes.py, and on `uneven6` without the flag: the mesh, the vertex
+                       densities and the three info structs
+  band_density_level/uneven6/6
+                       mvs_test_poisson_band_density_level with the flag: node_sums, rho, gain, active, cls, b, chi
 
 A deliberate change of the solver's arithmetic re-records: build the library, then on a GPU
   python scripts/record_poisson_bits.py --parent $(git rev-parse HEAD) --out tests/golden/poisson_bits.json
@@ -34,7 +46,11 @@ TOL = 1e-12
 CASES = (("field/hemisphere", "field/picked", "field/ellipsoid", "density/clamped", "density/drop_floor") +
          tuple(f"screened/{name}/0" for name in ("d3", "d4_alpha64", "d4_weighted", "d6")) +
          tuple(f"screened/{name}/{diag}" for diag in (1, 2) for name in ("d4", "d6")) +
-         ("depth7/plain", "depth7/density", "depth7/screened", "trim/open"))
+         ("depth7/plain", "depth7/density", "depth7/screened", "trim/open") +
+         tuple(f"band/{name}" for name in ("two_levels", "clipped", "hemisphere", "cap", "all_active")) +
+         ("band_level/two_levels/5", "band_level/two_levels/6") +
+         ("band_density/uneven6", "band_density/uneven6_drop2", "band_density/open6", "band_density/uneven6/unweighted") +
+         ("band_density_level/uneven6/6",))
 
 
 def digest(a) -> str:
@@ -116,9 +132,63 @@ def _trim(scene):
     return dict(rc=0, arrays=dict(vertices=digest(tv), faces=digest(tf), normals=digest(tn)), info=dict(V=len(tv), F=len(tf)))
 
 
+def _band(scene):
+    from multiviewstitch_amd import processor as P
+    from tests import poisson_band_scenes as BS
+    pts, nrm, prm, bprm = BS.scene(scene)
+    v, f, info, binfo = P.RunPoissonBand(pts, nrm, P.poisson_params(**dict(prm, solve_tol=TOL)), P.poisson_band_params(**bprm))
+    return dict(rc=0, arrays=dict(vertices=digest(v), faces=digest(f)), info=fields(info), binfo=fields(binfo))
+
+
+def _band_level(scene, level):
+    from multiviewstitch_amd import _lib as L, processor as P
+    from tests import poisson_band_scenes as BS
+    pts, nrm, prm, bprm = BS.scene(scene)
+    prm, bp = P.poisson_params(**dict(prm, solve_tol=TOL)), P.poisson_band_params(**bprm)
+    nn, nb = (2 ** int(level) + 1) ** 3, (2 ** int(level) // 4) ** 3
+    active, cls, b, chi = np.full(nb, 7, np.uint8), np.full(nn, 7, np.uint8), np.full(nn, -1.0), np.full(nn, -1.0)
+    hp, hn = L.arr(pts, np.float64), L.arr(nrm, np.float64)
+    info, binfo = L.CPoissonInfo(), L.CPoissonBandInfo()
+    rc = L.lib().mvs_test_poisson_band_level(len(hp), L.ptr(hp), L.ptr(hn), C.byref(prm), C.byref(bp), C.byref(info), C.byref(binfo), int(level),
+                                             L.ptr(active), L.ptr(cls), L.ptr(b), L.ptr(chi), nn)
+    return dict(rc=rc, arrays=dict(active=digest(active), cls=digest(cls), b=digest(b), chi=digest(chi)), info=fields(info), binfo=fields(binfo))
+
+
+def _band_density_params(scene, weight):
+    from multiviewstitch_amd import processor as P
+    from tests import poisson_band_density_scenes as S
+    pts, nrm, prm, bprm, dprm = S.scene(scene)
+    return (pts, nrm, P.poisson_params(**dict(prm, solve_tol=TOL)), P.poisson_band_params(**bprm),
+            P.poisson_density_params(flags=P.WEIGHT_NORMALS if weight else 0, **dprm))
+
+
+def _band_density(scene, weight="weighted"):
+    from multiviewstitch_amd import processor as P
+    v, f, d, info, binfo, dinfo = P.RunPoissonBandDensity(*_band_density_params(scene, weight == "weighted"))
+    return dict(rc=0, arrays=dict(vertices=digest(v), faces=digest(f), vertex_density=digest(d)), info=fields(info), binfo=fields(binfo),
+                dinfo=fields(dinfo))
+
+
+def _band_density_level(scene, level):
+    from multiviewstitch_amd import _lib as L
+    from tests import poisson_band_density_scenes as S
+    pts, nrm, prm, bp, dp = _band_density_params(scene, True)
+    n, nn, nb, nd = len(pts), (2 ** int(level) + 1) ** 3, (2 ** int(level) // 4) ** 3, (2 ** S.DENSITY_DEPTHS[scene] + 1) ** 3
+    active, cls, b, chi = np.full(nb, 7, np.uint8), np.full(nn, 7, np.uint8), np.full(nn, -1.0), np.full(nn, -1.0)
+    sums, rho, gain = np.full(nd, -1, np.int64), np.full(n, np.nan), np.full(n, np.nan)
+    hp, hn = L.arr(pts, np.float64), L.arr(nrm, np.float64)
+    info, binfo, dinfo = L.CPoissonInfo(), L.CPoissonBandInfo(), L.CPoissonDensityInfo()
+    rc = L.lib().mvs_test_poisson_band_density_level(n, L.ptr(hp), L.ptr(hn), C.byref(prm), C.byref(bp), C.byref(dp), C.byref(info), C.byref(binfo),
+                                                     C.byref(dinfo), int(level), L.ptr(active), L.ptr(cls), L.ptr(b), L.ptr(chi), nn, L.ptr(sums), nd,
+                                                     L.ptr(rho), L.ptr(gain))
+    return dict(rc=rc, arrays=dict(node_sums=digest(sums), rho=digest(rho), gain=digest(gain), active=digest(active), cls=digest(cls), b=digest(b),
+                                   chi=digest(chi)), info=fields(info), binfo=fields(binfo), dinfo=fields(dinfo))
+
+
 def record(case) -> dict:
     kind, *rest = case.split("/")
-    return dict(field=_field, density=_density, screened=_screened, depth7=_depth7, trim=_trim)[kind](*rest)
+    return dict(field=_field, density=_density, screened=_screened, depth7=_depth7, trim=_trim, band=_band, band_level=_band_level,
+                band_density=_band_density, band_density_level=_band_density_level)[kind](*rest)
 
 
 def main():

@@ -925,7 +925,8 @@ int mvs_poisson_reconstruct_screened_dev(int64_t n, const double* points_dev, co
  * blocks (1 .. 64, Chebyshev) of the points only, each level taking its boundary values from the level below: still fp64, integer splats
  * that do not depend on their order, a stop criterion on the true residual, two runs the same bytes.  It is unscreened and unweighted;
  * mvs_poisson_reconstruct_band_density, below, carries the sampling density of rules 14-17 over every level (rules 32-35); screening
- * over the band is not offered.  Like rules 1-23 this is this library's definition, NOT VERIFIED against GeoRec.
+ * over the band is mvs_poisson_reconstruct_band_screened, further below (rules 36-41).  Like rules 1-23 this is this library's
+ * definition, NOT VERIFIED against GeoRec.
  *  24. depth       : D = rule 3 with Dmax = min(depth_max, MVS_POISSON_BAND_MAX_DEPTH).  At depth 10 the node index and the cube
  *                    index still fit in int32; a (node index, type) key needs int64.  B = min(D, base_depth).  With D <= base_depth
  *                    the result is that of mvs_poisson_reconstruct at depth_min = depth_max = D.
@@ -1045,6 +1046,66 @@ int mvs_poisson_reconstruct_band_density_dev(int64_t n, const double* points_dev
                                              mvs_poisson_info* info, mvs_poisson_band_info* binfo, mvs_poisson_density_info* dinfo,
                                              double* vertices_dev, double* vertex_density_dev, int64_t vertex_capacity, int32_t* faces_dev,
                                              int64_t face_capacity, void* hip_stream);
+
+/* The band-density call with screening on the base level and on every band level: the depth config.txt asks for and the point-
+ * interpolation term of rules 19-23 in one call.  Every level pulls its field to a target at the samples before the next level starts
+ * from it: one field and one solve per band level.  Rules 36-41 continue the list; like rules 1-35 they are this library's definition,
+ * NOT VERIFIED against GeoRec.
+ *  36. cases       : D and B are those of rule 24.  With D <= B the call IS mvs_poisson_reconstruct_screened at depth_min = depth_max
+ *                    = D: its bytes, sinfo included; binfo is zero apart from base_depth and bsinfo is zero.  Otherwise, with alpha =
+ *                    0, vertices, faces, vertex_density, info, binfo and dinfo hold the bytes of mvs_poisson_reconstruct_band_density
+ *                    with the same dparams, and sinfo and bsinfo are zero.  MVS_POISSON_WEIGHT_NORMALS keeps rule 33's meaning on
+ *                    every level and does not change any lambda.
+ *  37. base        : rules 19-23 at depth B give the screened chi_B: chi0 and T are rule 25's field (with the flag the weighted one)
+ *                    and rule 9 on it, occ = occupied(B), computed even when rule 3 does not need it.  Both solves of the base run one
+ *                    cycle past their criterion, for rule 25's reason, and each has rule 25's budget.  sinfo describes this level
+ *                    (cycles and rel_residual count and follow the extra cycle).
+ *  38. weight and stencil of level l (B < l <= D): lambda_l = alpha / max(1.0, (double)N / (double)occupied(l)).  The stencil S_l is
+ *                    rule 20's at level l with lambda_l: the same quantisation, the same symmetric int64 sums, the same offset order
+ *                    and the same int64 bound.  Every node that a used point touches is FREE: the eight cells around a corner of the
+ *                    point's cell lie within one cell of that cell, hence in blocks at Chebyshev distance <= 1 <= band from the
+ *                    point's block, which are active (the scale check keeps them inside the grid), and a node whose eight cells are
+ *                    active is FREE.  So S_l has no entry at a FIXED node: a row belongs to a FREE node and each of its 27 offsets
+ *                    points at a node that is touched too or carries a zero entry, and every one of the 26 neighbours of a node with
+ *                    a row has a value and is stored.  Storage is not part of the definition, but a memory condition is: no array
+ *                    over all nodes of a level is allocated, and rows exist only for touched nodes.
+ *  39. target      : T_l is rule 29's mean (the used points in their order) evaluated on the START values of level l, which are rule
+ *                    27 applied to the screened chi of level l - 1.  No unscreened solve is made on a band level.
+ *  40. system      : the free nodes satisfy rule 21's equation with lambda_l, S_l and T_l, the terms of fixed neighbours moved to
+ *                    the right: M_ff chi_f = f', f' = f - A_fc chi_c, f = b - T_l rs (b of rule 28).  The solve runs from the start
+ *                    values until |f' - M_ff chi|_2 <= solve_tol * |f'|_2 on the true residual, recomputed on the device with
+ *                    partials in a fixed order.  The budget is rule 28's; past it the call returns MVS_E_SOLVER with the level
+ *                    named.  f' = 0 gives chi_f = 0.  binfo.rel_residual, bnorm (|f'|) and iterations of level l describe this
+ *                    solve.  The solver is not part of the definition (csrc/poisson_band.hip: conjugate gradients on the positive
+ *                    definite -M_ff, preconditioned by its diagonal 6 + S_{i,0}); the stop criterion and the identity of two runs are.
+ *  41. surface     : rule 29 on the screened chi_D; rules 30, 31 and 34 are unchanged.
+ * bsinfo's arrays are indexed by the level l and zero outside B + 1 .. D.  info, binfo and dinfo keep the meaning they have in
+ * mvs_poisson_reconstruct_band_density.  Capacities, MVS_E_SOLVER (failed_level = B for either solve of the base) and MVS_E_OOM as
+ * there.  Scratch beyond the band-density call's, counted in binfo.scratch_bytes (csrc/poisson_band_plan.h, bd_screen_block_bytes and
+ * bd_screen_row_bytes): the base as rule 23's scratch says; 8 bytes per used point for their list; per level 2^(3 l - 3) bytes for
+ * occupied(l) while it is counted, per stored block 109 bytes (its 27 neighbours and a flag) and per stored node 12 bytes (the number
+ * of its row, the preconditioner) plus 1 byte and the scan while the rows are numbered, and 228 bytes per touched node (27 entries, the
+ * row sum and the node).  A level whose rows need more than the device has gives MVS_E_OOM with the level named, before they are asked for.
+ * MVS_E_INVALID_ARG, before a device is needed: what mvs_poisson_reconstruct_band_density refuses, what
+ * mvs_poisson_reconstruct_screened refuses of sparams and sinfo (either NULL, alpha not finite or outside [0, 64], reserved != 0), and
+ * bsinfo NULL. */
+typedef struct mvs_poisson_band_screen_info {    /* arrays indexed by level l, entries outside B+1..D zero */
+    double  lambda[MVS_POISSON_BAND_MAX_DEPTH + 1], target[MVS_POISSON_BAND_MAX_DEPTH + 1];        /* rules 38 and 39      */
+    int64_t occupied[MVS_POISSON_BAND_MAX_DEPTH + 1], active_nodes[MVS_POISSON_BAND_MAX_DEPTH + 1]; /* occupied(l); the rows */
+} mvs_poisson_band_screen_info;
+int mvs_poisson_reconstruct_band_screened(int64_t n, const double* points, const double* normals, const mvs_poisson_params* p,
+                                          const mvs_poisson_band_params* bparams, const mvs_poisson_density_params* dparams,
+                                          mvs_poisson_info* info, mvs_poisson_band_info* binfo, mvs_poisson_density_info* dinfo,
+                                          double* vertices, double* vertex_density, int64_t vertex_capacity, int32_t* faces,
+                                          int64_t face_capacity, const mvs_poisson_screen_params* sparams, mvs_poisson_screen_info* sinfo,
+                                          mvs_poisson_band_screen_info* bsinfo);
+/* the device form, as mvs_poisson_reconstruct_dev */
+int mvs_poisson_reconstruct_band_screened_dev(int64_t n, const double* points_dev, const double* normals_dev, const mvs_poisson_params* p,
+                                              const mvs_poisson_band_params* bparams, const mvs_poisson_density_params* dparams,
+                                              mvs_poisson_info* info, mvs_poisson_band_info* binfo, mvs_poisson_density_info* dinfo,
+                                              double* vertices_dev, double* vertex_density_dev, int64_t vertex_capacity, int32_t* faces_dev,
+                                              int64_t face_capacity, void* hip_stream, const mvs_poisson_screen_params* sparams,
+                                              mvs_poisson_screen_info* sinfo, mvs_poisson_band_screen_info* bsinfo);
 
 /* Rule 18 on any triangle mesh: vertices[V][3], normals[V][3] (may be NULL, then normals_out is not written), faces[F][3], values[V].
  * The outputs hold V resp. F rows and do not overlap the inputs; V_out / F_out receive the rows kept.  An ordered compaction without

@@ -152,6 +152,14 @@ int mvs_processor_poisson_band_density(const char* psr_npts, const mvs_poisson_p
                                        const mvs_poisson_density_params* dparams, double trim_ratio, const char* model_obj, int64_t* V,
                                        int64_t* F, int64_t* n_open_edges);
 
+/* mvs_processor_poisson_band_density through mvs_poisson_reconstruct_band_screened (rules 36-41 of include/mvs.h: this library's
+ * definition, NOT VERIFIED against GeoRec): the band levels with the sampling density and screening on every level.  bparams, dparams
+ * and sparams NULL: their defaults (alpha = 4).  Reconstruct, trim by trim_ratio, normals, write, as that call does; with alpha = 0 the
+ * file holds the bytes it writes. */
+int mvs_processor_poisson_band_screened(const char* psr_npts, const mvs_poisson_params* params, const mvs_poisson_band_params* bparams,
+                                        const mvs_poisson_density_params* dparams, const mvs_poisson_screen_params* sparams, double trim_ratio,
+                                        const char* model_obj, int64_t* V, int64_t* F, int64_t* n_open_edges);
+
 #ifdef __cplusplus
 }
 #endif

@@ -118,6 +118,20 @@ int mvs_test_poisson_band_density_level(int64_t n, const double* points, const d
                                         uint8_t* active, uint8_t* cls, double* b, double* chi, int64_t node_capacity, int64_t* node_sums,
                                         int64_t density_node_capacity, double* rho, double* gain);
 
+/* mvs_poisson_reconstruct_band_screened up to rule 41's iso value: what mvs_test_poisson_band_density_level takes and hands out (b is
+ * rule 28's, before T_l rs is taken off; chi the screened field of the level), plus sparams, sinfo and bsinfo and, of rules 38-40 on
+ * that level, all expanded on the host to the dense layout n1^3 in node order: stencil [n1^3][27], the int64 sums of rule 38 (0 at a
+ * node without a row); f, rule 40's b - T_l rs (NaN at a node without a value, 0 at a fixed node); start, the start values of rule 39
+ * (NaN at a node without a value).  With alpha = 0 the stencil is zero, f is b and start what the solve began from.
+ * MVS_E_INVALID_ARG as that hook and the call, or a NULL array. */
+int mvs_test_poisson_band_screened_level(int64_t n, const double* points, const double* normals, const mvs_poisson_params* p,
+                                         const mvs_poisson_band_params* bparams, const mvs_poisson_density_params* dparams,
+                                         mvs_poisson_info* info, mvs_poisson_band_info* binfo, mvs_poisson_density_info* dinfo, int32_t level,
+                                         uint8_t* active, uint8_t* cls, double* b, double* chi, int64_t node_capacity, int64_t* node_sums,
+                                         int64_t density_node_capacity, double* rho, double* gain, const mvs_poisson_screen_params* sparams,
+                                         mvs_poisson_screen_info* sinfo, mvs_poisson_band_screen_info* bsinfo, int64_t* stencil, double* f,
+                                         double* start);
+
 /* mvs_grabcut_masks (host form) with its steps handed out, N = (w / 2) * (h / 2); every array but mask may be NULL:
  *   S [n] int64 (rule 7) and ncap [n][8][N] int32 (rule 8, the layout of mvs_grid_mincut's cap), once per call;
  *   labels [iters + 1][n][N] uint8 and sums [iters + 1][n][2][5][10] int64 (model 0 = foreground; per component c | s0 s1 s2 | p00 p01

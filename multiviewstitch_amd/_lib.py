@@ -139,6 +139,12 @@ class CPoissonScreenInfo(C.Structure):
                 ("occupied", C.c_int64), ("active_nodes", C.c_int64), ("cycles", C.c_int32), ("reserved", C.c_int32)]
 
 
+class CPoissonBandScreenInfo(C.Structure):
+    """struct mvs_poisson_band_screen_info: the arrays are indexed by the level."""
+    _fields_ = [("lambda_", C.c_double * (POISSON_BAND_MAX_DEPTH + 1)), ("target", C.c_double * (POISSON_BAND_MAX_DEPTH + 1)),
+                ("occupied", C.c_int64 * (POISSON_BAND_MAX_DEPTH + 1)), ("active_nodes", C.c_int64 * (POISSON_BAND_MAX_DEPTH + 1))]
+
+
 class CSeqPairParams(C.Structure):
     """struct mvs_seq_pair_params."""
     _fields_ = [("filter", CMatchFilterParams), ("min_dsp", C.c_double), ("max_dsp", C.c_double), ("min_match_count", C.c_int32),
@@ -212,6 +218,8 @@ _SIGS = {
     "mvs_poisson_reconstruct_band_dev": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _I64, _VP]),
     "mvs_poisson_reconstruct_band_density": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _I64]),
     "mvs_poisson_reconstruct_band_density_dev": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _I64, _VP]),
+    "mvs_poisson_reconstruct_band_screened": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _I64, _VP, _VP, _VP]),
+    "mvs_poisson_reconstruct_band_screened_dev": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _I64, _VP, _VP, _VP, _VP]),
     "mvs_mesh_trim_by_value": (C.c_int, [_I64, _VP, _VP, _I64, _VP, _VP, _D, _VP, _VP, _VP, _VP, _VP]),
     "mvs_mesh_trim_by_value_dev": (C.c_int, [_I64, _VP, _VP, _I64, _VP, _VP, _D, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mvs_render_depth": (C.c_int, [_VP, _I64, _VP, _I64, _VP, C.c_float, C.c_float, _VP]),
@@ -312,6 +320,7 @@ _SIGS = {
     "mvs_processor_poisson_screened": (C.c_int, [C.c_char_p, _VP, _VP, _VP, _D, C.c_char_p, _VP, _VP]),
     "mvs_processor_poisson_band": (C.c_int, [C.c_char_p, _VP, _VP, C.c_char_p, _VP, _VP, _VP]),
     "mvs_processor_poisson_band_density": (C.c_int, [C.c_char_p, _VP, _VP, _VP, _D, C.c_char_p, _VP, _VP, _VP]),
+    "mvs_processor_poisson_band_screened": (C.c_int, [C.c_char_p, _VP, _VP, _VP, _VP, _D, C.c_char_p, _VP, _VP, _VP]),
     # include/mvs_test.h (test hooks: per handle, not part of the drop-in ABI)
     "mvs_test_preload_wait": (C.c_int, []),
     "mvs_test_ctl": (C.c_int, [_VP, _VP, _I32]),
@@ -332,6 +341,8 @@ _SIGS = {
     "mvs_test_poisson_band_level": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _I64]),
     "mvs_test_poisson_band_density_level": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _I64, _VP, _I64, _VP,
                                                       _VP]),
+    "mvs_test_poisson_band_screened_level": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _I64, _VP, _I64, _VP,
+                                                       _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mvs_test_rotations": (C.c_int, [_I64, _VP, _I32, _VP, _VP, _VP]),
 }
 EXPORTS = tuple(_SIGS)

@@ -402,7 +402,8 @@ int mvs_processor_point_sample(int32_t n_seq, const char* const* seq_dirs, const
 // PSR.npts -> Model.obj; dprm != NULL: through rules 14-17, and trimmed by rule 18 when trim_ratio > 0; sprm != NULL (with dprm): rules 19-23
 static int poisson_files(const char* fn, const char* psr_npts, const mvs_poisson_params& prm, const mvs_poisson_density_params* dprm, double trim_ratio,
                          const char* model_obj, int64_t* V_out, int64_t* F_out, const mvs_poisson_screen_params* sprm,
-                         const mvs_poisson_band_params* bprm = nullptr /*alone: rules 24-31; with dprm: rules 32-35*/, int64_t* open_out = nullptr) {
+                         const mvs_poisson_band_params* bprm = nullptr /*alone: rules 24-31; with dprm: rules 32-35; with sprm too: rules 36-41*/,
+                         int64_t* open_out = nullptr) {
     int rc = need_device();
     if (rc) return rc;
     int64_t n = 0;
@@ -420,7 +421,10 @@ static int poisson_files(const char* fn, const char* psr_npts, const mvs_poisson
                       sprm, sprm ? &sinfo : nullptr};
     mvs_poisson_band_info binfo;
     if (bprm) {
-        const BdCall band{fn, n, dp.as<double>(), dn.as<double>(), &prm, bprm, &info, &binfo, dprm, dprm ? &dinfo : nullptr, dprm != nullptr};
+        mvs_poisson_band_screen_info bsinfo;
+        const bool screen = dprm && sprm;
+        const BdCall band{fn, n, dp.as<double>(), dn.as<double>(), &prm, bprm, &info, &binfo, dprm, dprm ? &dinfo : nullptr, dprm != nullptr,
+                          screen ? sprm : nullptr, screen ? &sinfo : nullptr, screen ? &bsinfo : nullptr, screen};
         if ((rc = poisson_band_blocks(band, &dv, &dd, &df))) return rc;
         if (open_out) *open_out = binfo.n_open_edges;
     } else if ((rc = poisson_blocks(call, &dv, &dd, &df))) return rc;
@@ -501,6 +505,23 @@ int mvs_processor_poisson_band_density(const char* psr_npts, const mvs_poisson_p
     if (bparams) bprm = *bparams; else mvs_poisson_band_default_params(&bprm);
     if (dparams) dprm = *dparams; else mvs_poisson_density_default_params(&dprm);
     return poisson_files(__func__, psr_npts, prm, &dprm, trim_ratio, model_obj, V_out, F_out, nullptr, &bprm, n_open_edges);
+}
+
+int mvs_processor_poisson_band_screened(const char* psr_npts, const mvs_poisson_params* params, const mvs_poisson_band_params* bparams,
+                                        const mvs_poisson_density_params* dparams, const mvs_poisson_screen_params* sparams, double trim_ratio,
+                                        const char* model_obj, int64_t* V_out, int64_t* F_out, int64_t* n_open_edges) {
+    MVS_TRACE();
+    if (!psr_npts || !model_obj) return bad(__func__, "psr_npts / model_obj is NULL");
+    if (trim_ratio != trim_ratio) return bad(__func__, "trim_ratio is NaN");
+    mvs_poisson_params prm;
+    mvs_poisson_band_params bprm;
+    mvs_poisson_density_params dprm;
+    mvs_poisson_screen_params sprm;
+    if (params) prm = *params; else mvs_poisson_default_params(&prm);
+    if (bparams) bprm = *bparams; else mvs_poisson_band_default_params(&bprm);
+    if (dparams) dprm = *dparams; else mvs_poisson_density_default_params(&dprm);
+    if (sparams) sprm = *sparams; else mvs_poisson_screen_default_params(&sprm);
+    return poisson_files(__func__, psr_npts, prm, &dprm, trim_ratio, model_obj, V_out, F_out, &sprm, &bprm, n_open_edges);
 }
 
 }  // extern "C"

@@ -1126,6 +1126,8 @@ int poisson_check_plain(const PnCall& c, int max_depth, const void* out_a, int64
 
 int poisson_check_density(const char* fn, int64_t n, const mvs_poisson_density_params* dp, const void* dinfo) { return check_pn_density(fn, n, dp, dinfo); }
 
+int poisson_check_screen(const char* fn, const mvs_poisson_screen_params* sp, const void* sinfo) { return check_pn_screen(fn, sp, sinfo); }
+
 // PnScan: counts, their scan and its two levels
 int PnScan::alloc(size_t nb, hipStream_t s) {
     const size_t rows = (nb + PN_SCAN_CH - 1) / PN_SCAN_CH;
@@ -1143,6 +1145,11 @@ void PnScan::run(int nb, hipStream_t s) {
 }
 
 void poisson_fold(const double* part_dev, int n, double* out_dev, hipStream_t s) { k_pn_fold<<<dim3(1), dim3(PN_TPB), 0, s>>>(part_dev, n, out_dev); }
+
+static_assert(PN_SC_ROW == SC_ROW, "one row layout");
+void poisson_screen_convert(int64_t rows, long long* tab_dev, hipStream_t s) {
+    if (rows > 0) k_sc_convert<<<dim3((unsigned)((rows + PN_TPB - 1) / PN_TPB)), dim3(PN_TPB), 0, s>>>(rows, tab_dev);
+}
 
 void poisson_face_count(const uint8_t* mask_dev, int64_t items, int32_t* cnt_dev, hipStream_t s) {
     k_pn_face_count<<<dim3((unsigned)((items + PN_TPB - 1) / PN_TPB)), dim3(PN_TPB), 0, s>>>(mask_dev, items, cnt_dev);
@@ -1233,6 +1240,28 @@ int PnBaseField::solve(const PnCall& c, const double* pts_dev, const double* nrm
     size_t below = 0;
     for (int l = 1; l < c.info->depth; ++l) below += 3 * (size_t)((1 << l) + 1) * ((1 << l) + 1) * ((1 << l) + 1);
     bytes = (int64_t)(32 * (size_t)r->nn + 8 * below);
+    if (c.sp && c.sinfo) {                                                    // rule 37: rules 19-22 on this field, from it
+        if ((rc = r->iso_value()) || (rc = r->screen_setup(nullptr))) return rc;
+        bytes += (int64_t)r->nn + r->sn.bytes;
+        for (int l = 1; l <= c.info->depth; ++l) bytes += 4 * (int64_t)((1 << l) + 1) * ((1 << l) + 1) * ((1 << l) + 1) + (8 * SC_ROW + 4) * r->sc_rows[l];
+        if (c.sp->alpha > 0.0) {
+            if ((rc = r->screen_solve(c.fn))) return rc;
+            if (c.sinfo->cycles > 0) {
+                double before = 0.0, after = 0.0;
+                double* x = r->L.x[c.info->depth];
+                rc = with_diagonal(r->diag, [&](auto op) -> int {
+                    using Op = decltype(op);
+                    int q = r->template norm2<Op>(x, &before);
+                    if (q || !(before > 0.0)) return q;
+                    if ((q = r->template vcycle<Op>()) || (q = r->template norm2<Op>(x, &after))) return q;
+                    c.sinfo->cycles += 1;
+                    c.sinfo->rel_residual *= std::sqrt(after) / std::sqrt(before);
+                    return MVS_OK;
+                });
+                if (rc) return rc;
+            }
+        }
+    }
     return MVS_OK;
 }
 

@@ -36,6 +36,8 @@
 // (k_bd_mark without the dilation, k_bd_stored, k_bd_row_count, k_bd_number: the table of a level, 8 bytes per stored node); a node
 // without storage reads as 0 (bd_density_at of poisson_band_rules.h).  The kernels of rules 14-17 are poisson.hip's, instantiated for
 // either storage (PnDensitySums, poisson_density_rows, poisson_vertex_density of poisson_base.h).
+// mvs_poisson_reconstruct_band_screened (rules 36-41) screens the base (PnBaseField with sparams) and every level: the k_bd_sc_* kernels
+// below number the rows over the stored node places, splat rule 38's stencil and solve M_ff chi_f = f' in the place of rule 28's system.
 // BdRun runs the stages in the order depth, density, base, levels, iso, mesh, vertex density.
 // Nothing but integer atomics (the splats, the bitmap, the count of open edges) is unordered: two runs give the same bytes.
 #include "engine.h"
@@ -46,6 +48,7 @@
 #include "poisson_band_rules.h"
 #include "poisson_band_plan.h"
 #include "poisson_base.h"
+#include "knobs.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -375,6 +378,222 @@ __global__ __launch_bounds__(PN_TPB) void k_bd_count_set(int64_t n, const uint8_
     if ((threadIdx.x & 63) == 0 && bal) atomicAdd(out, (unsigned long long)__popcll(bal));
 }
 
+// ------------------------------------------------------------------ rules 38-40 ----
+// mvs_poisson_reconstruct_band_screened: the stencil rows of level l over the stored node places, and the solve of M_ff chi_f = f'.
+//   k_bd_sc_flag / k_bd_sc_count / k_bd_sc_number   plain byte stores of 1 at the places the points touch (and at their blocks), then an
+//                                                   ordered compaction over the places: ridx[place] = the number of its row or -1,
+//                                                   rnode[row] = its place.  No atomic counter
+//   k_bd_nb27                                       the 27 blocks around every stored block, in the offset order of rule 20
+//   k_bd_sc_splat                                   rule 38 through the block table: pn_screen_pair and int64 atomic adds (order-free);
+//                                                   poisson_screen_convert makes the sums doubles in place
+//   k_bd_sc_rhs / k_bd_sc_dinv                      f = b - T_l rs at the rows; the inverse diagonal 1 / (6 + S_{i,0}) of every place
+//   k_bd_sc_residual / k_bd_sc_apply / k_bd_sc_update   k_bd_residual / apply / update with the stencil term and the preconditioner.
+//                                                   A wave whose block has a row stages its 64 values and the one-node halo around
+//                                                   them, 6^3 doubles, in its own part of LDS, and the lanes with a row read their 27
+//                                                   operands there; a wave whose block has none takes the plain path: the branch is
+//                                                   uniform over the wave, and most stored blocks lie in the band, not on the surface
+// Rule 38: every neighbour of a node with a row is stored, so no operand of a row is missing; a table that broke that reads 0.
+constexpr int BD_HALO = 6 * 6 * 6;
+struct BdScreen {
+    const int32_t* nb27;                  // 27 per stored block, -1: not stored
+    const uint8_t* has;                   // per stored block: does a node of it have a row?
+    const int32_t* ridx;                  // per place: the number of its row, -1: none
+    const double* tab;                    // PN_SC_ROW doubles per row
+};
+
+__global__ __launch_bounds__(PN_TPB) void k_bd_sc_flag(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm, PnGrid g, BdView v,
+                                                       uint8_t* __restrict__ flag, uint8_t* __restrict__ has) {
+    const int64_t i = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
+    if (i >= n || !pn_used(pts + 3 * i, nrm + 3 * i)) return;
+    int i0[3];
+    double w[8];
+    pn_corners_weights(pts + 3 * i, g, i0, w);
+    for (int c = 0; c < 8; ++c) {
+        const int64_t at = bd_slot(v, i0[0] + (c & 1), i0[1] + (c >> 1 & 1), i0[2] + (c >> 2 & 1));
+        if (at < 0) continue;                                                // rule 29: cannot be
+        flag[at] = 1;
+        has[at >> 6] = 1;
+    }
+}
+__global__ __launch_bounds__(PN_TPB) void k_bd_sc_count(int64_t nodes, const uint8_t* __restrict__ flag, int32_t* __restrict__ cnt) {
+    __shared__ int s_wsum[PN_WAVES];
+    const int64_t at = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
+    const WgRank k = wg_rank<PN_WAVES>(at < nodes && flag[at], s_wsum);
+    if (threadIdx.x == 0) cnt[blockIdx.x] = k.total;
+}
+__global__ __launch_bounds__(PN_TPB) void k_bd_sc_number(int64_t nodes, const uint8_t* __restrict__ flag, const int32_t* __restrict__ base,
+                                                         int32_t* __restrict__ ridx, int32_t* __restrict__ rnode) {
+    __shared__ int s_wsum[PN_WAVES];
+    const int64_t at = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
+    const bool f = at < nodes && flag[at];
+    const int pos = base[blockIdx.x] + wg_rank<PN_WAVES>(f, s_wsum).rank;
+    if (at < nodes) ridx[at] = f ? pos : -1;
+    if (f) rnode[pos] = (int32_t)at;
+}
+
+// nb27[27 s + o]: the stored number of the block at offset o = (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1) from block s (o = 13: s); -1: none
+__global__ __launch_bounds__(PN_TPB) void k_bd_nb27(int64_t ns, const int32_t* __restrict__ coord, BdView v, int32_t* __restrict__ nb27) {
+    const int64_t i = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
+    if (i >= 27 * ns) return;
+    const int o = (int)(i % 27);
+    int bx, by, bz;
+    bd_unpack(coord[i / 27], &bx, &by, &bz);
+    bx += o % 3 - 1; by += o / 3 % 3 - 1; bz += o / 9 - 1;
+    nb27[i] = bx < 0 || bx >= v.T || by < 0 || by >= v.T || bz < 0 || bz >= v.T ? -1 : v.num[bd_tab(v, bx, by, bz)];
+}
+
+__global__ __launch_bounds__(PN_TPB) void k_bd_sc_splat(int64_t n, const double* __restrict__ pts, const double* __restrict__ nrm, PnGrid g, BdView v,
+                                                        double lambda, const int32_t* __restrict__ ridx, unsigned long long* __restrict__ tab) {
+    const int64_t i = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
+    if (i >= n || !pn_used(pts + 3 * i, nrm + 3 * i)) return;
+    int i0[3];
+    double w[8];
+    int64_t row[8];
+    pn_corners_weights(pts + 3 * i, g, i0, w);
+    bool ok = true;
+    for (int c = 0; c < 8; ++c) {
+        const int64_t at = bd_slot(v, i0[0] + (c & 1), i0[1] + (c >> 1 & 1), i0[2] + (c >> 2 & 1));
+        const int a = at < 0 ? -1 : ridx[at];
+        ok = ok && a >= 0;                                                   // flagged by k_bd_sc_flag: >= 0
+        row[c] = (int64_t)PN_SC_ROW * a;
+    }
+    if (!ok) return;
+    for (int c1 = 0; c1 < 8; ++c1)
+        for (int c2 = c1; c2 < 8; ++c2) {
+            int o12, o21;
+            const unsigned long long q = (unsigned long long)pn_screen_pair(lambda, w, c1, c2, &o12, &o21);
+            atomicAdd(tab + row[c1] + o12, q);
+            if (c1 != c2) atomicAdd(tab + row[c2] + o21, q);
+        }
+}
+
+// rule 40's f = b - T rs at the rows (all at free nodes: rule 38)
+__global__ __launch_bounds__(PN_TPB) void k_bd_sc_rhs(int64_t rows, const int32_t* __restrict__ rnode, const uint8_t* __restrict__ cls,
+                                                      const double* __restrict__ tab, double T, double* __restrict__ b) {
+    const int64_t a = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
+    if (a >= rows) return;
+    const int64_t at = rnode[a];
+    if (cls[at] == BD_FREE) b[at] = b[at] - T * tab[(int64_t)PN_SC_ROW * a + 27];
+}
+
+// the preconditioner: 1 / (6 + S_{i,0}) with a row, 1 / 6 without; JACOBI = false: 1, plain conjugate gradients
+template <bool JACOBI>
+__global__ __launch_bounds__(PN_TPB) void k_bd_sc_dinv(int64_t nodes, const int32_t* __restrict__ ridx, const double* __restrict__ tab,
+                                                       double* __restrict__ dinv) {
+    const int64_t at = (int64_t)blockIdx.x * PN_TPB + threadIdx.x;
+    if (at >= nodes) return;
+    const int a = ridx[at];
+    dinv[at] = !JACOBI ? 1.0 : 1.0 / (6.0 + (a < 0 ? 0.0 : tab[(int64_t)PN_SC_ROW * a + 13]));
+}
+
+// sum_o S_{i,o} x_{i+o} at node `lane` of block s, 0 at a lane without a row; every lane of the wave calls it, and only when q.has[s].
+// own: the lane's x; load(place): x anywhere; halo: the wave's BD_HALO doubles of LDS.
+template <class F>
+__device__ inline double bd_sc_term(const BdScreen& q, int64_t s, int lane, double own, double* halo, F load) {
+    const int lx = lane & 3, ly = lane >> 2 & 3, lz = lane >> 4;
+    const int32_t* nb = q.nb27 + 27 * s;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                   // the reads of the block before are done
+    __builtin_amdgcn_wave_barrier();
+    halo[(lz + 1) * 36 + (ly + 1) * 6 + (lx + 1)] = own;
+    for (int h = lane; h < BD_HALO; h += 64) {
+        const int hx = h % 6, hy = h / 6 % 6, hz = h / 36;
+        const int ox = hx == 0 ? 0 : hx == 5 ? 2 : 1, oy = hy == 0 ? 0 : hy == 5 ? 2 : 1, oz = hz == 0 ? 0 : hz == 5 ? 2 : 1;
+        if (ox == 1 && oy == 1 && oz == 1) continue;                          // inside the block: written above
+        const int32_t b = nb[oz * 9 + oy * 3 + ox];
+        halo[h] = b >= 0 ? load((int64_t)b * 64 + (((hz - 1) & 3) << 4 | ((hy - 1) & 3) << 2 | ((hx - 1) & 3))) : 0.0;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const int a = q.ridx[s * 64 + lane];
+    double acc = 0.0;
+    if (a >= 0) {
+        const double* __restrict__ row = q.tab + (int64_t)PN_SC_ROW * a;
+        const double* c = halo + lz * 36 + ly * 6 + lx;                      // the node at offset (-1, -1, -1)
+#pragma unroll
+        for (int k = 0; k < 27; ++k) acc = acc + row[k] * c[(k / 9) * 36 + (k / 3 % 3) * 6 + k % 3];
+    }
+    return acc;
+}
+
+// k_bd_residual with the stencil term: (S6 - 6 x) - sum_o S_o x_o - f at the free nodes.  WRITE: r, and the partials of r . (r dinv) too
+template <bool WRITE>
+__global__ __launch_bounds__(PN_TPB) void k_bd_sc_residual(int64_t ns, const int32_t* __restrict__ nbr, const uint8_t* __restrict__ cls, BdScreen q,
+                                                           const double* __restrict__ x, const double* __restrict__ b,
+                                                           const double* __restrict__ dinv, double* __restrict__ r, double* __restrict__ part,
+                                                           double* __restrict__ part_z) {
+    __shared__ double s_part[PN_WAVES], s_z[PN_WAVES], s_halo[PN_WAVES][BD_HALO];
+    const int lane = threadIdx.x & 63;
+    double acc = 0.0, accz = 0.0;
+    BD_EACH_BLOCK(s) {
+        const int64_t at = s * 64 + lane;
+        const double xv = x[at];
+        const double S = bd_sum6(xv, nbr + 6 * s, lane, [&](int64_t p) { return x[p]; });
+        double rv = (S - 6.0 * xv) - b[at];
+        if (q.has[s]) rv = rv - bd_sc_term(q, s, lane, xv, s_halo[threadIdx.x >> 6], [&](int64_t p) { return x[p]; });
+        if (cls[at] != BD_FREE) rv = 0.0;
+        if (WRITE) { r[at] = rv; accz += rv * (rv * dinv[at]); }
+        acc += rv * rv;
+    }
+    const double t = wg_sum<PN_WAVES>(acc, s_part, threadIdx.x);
+    if (threadIdx.x == 0) part[blockIdx.x] = t;
+    if (WRITE) {
+        const double tz = wg_sum<PN_WAVES>(accz, s_z, threadIdx.x);
+        if (threadIdx.x == 0) part_z[blockIdx.x] = tz;
+    }
+}
+
+// k_bd_apply on -M_ff with the preconditioner: p = r dinv + beta p_old (beta = rz / rz_before), A p = (6 p - S6(p)) + sum_o S_o p_o
+__global__ __launch_bounds__(PN_TPB) void k_bd_sc_apply(int64_t ns, const int32_t* __restrict__ nbr, const uint8_t* __restrict__ cls, BdScreen q, int first,
+                                                        int np, const double* __restrict__ rz, const double* __restrict__ rz_before,
+                                                        const double* __restrict__ r, const double* __restrict__ dinv,
+                                                        const double* __restrict__ p_old, double* __restrict__ p, double* __restrict__ ap,
+                                                        double* __restrict__ part) {
+    __shared__ double s_a[PN_WAVES], s_b[PN_WAVES], s_part[PN_WAVES], s_o[2], s_halo[PN_WAVES][BD_HALO];
+    double beta = 0.0;
+    if (!first) {
+        const double n = wg_sum_partials_all(rz, np, s_a, s_o), d = wg_sum_partials_all(rz_before, np, s_b, s_o + 1);
+        beta = d > 0.0 ? n / d : 0.0;
+    }
+    const int lane = threadIdx.x & 63;
+    double acc = 0.0;
+    BD_EACH_BLOCK(s) {
+        const int64_t at = s * 64 + lane;
+        const auto P = [&](int64_t k) { return r[k] * dinv[k] + beta * p_old[k]; };
+        const double pv = P(at);
+        const double S = bd_sum6(pv, nbr + 6 * s, lane, P);
+        double av = 6.0 * pv - S;
+        if (q.has[s]) av = av + bd_sc_term(q, s, lane, pv, s_halo[threadIdx.x >> 6], P);
+        if (cls[at] != BD_FREE) av = 0.0;
+        p[at] = pv;
+        ap[at] = av;
+        acc += pv * av;
+    }
+    const double t = wg_sum<PN_WAVES>(acc, s_part, threadIdx.x);
+    if (threadIdx.x == 0) part[blockIdx.x] = t;
+}
+
+// k_bd_update with the partials of the new r . (r dinv)
+__global__ __launch_bounds__(PN_TPB) void k_bd_sc_update(int64_t ns, int np, const double* __restrict__ rz, const double* __restrict__ pap,
+                                                         const double* __restrict__ p, const double* __restrict__ ap,
+                                                         const double* __restrict__ dinv, double* __restrict__ x, double* __restrict__ r,
+                                                         double* __restrict__ part) {
+    __shared__ double s_a[PN_WAVES], s_b[PN_WAVES], s_part[PN_WAVES], s_o[2];
+    const double n = wg_sum_partials_all(rz, np, s_a, s_o), d = wg_sum_partials_all(pap, np, s_b, s_o + 1);
+    const double alpha = d > 0.0 ? n / d : 0.0;
+    const int lane = threadIdx.x & 63;
+    double acc = 0.0;
+    BD_EACH_BLOCK(s) {
+        const int64_t at = s * 64 + lane;
+        x[at] = x[at] + alpha * p[at];
+        const double rv = r[at] - alpha * ap[at];
+        r[at] = rv;
+        acc += rv * (rv * dinv[at]);
+    }
+    const double t = wg_sum<PN_WAVES>(acc, s_part, threadIdx.x);
+    if (threadIdx.x == 0) part[blockIdx.x] = t;
+}
+
 // ------------------------------------------------------------------ rule 29 ----
 // The used rows in their order, by ordered compaction: the sum of rule 29 then runs over used[0 .. N), so a row that is not used moves
 // no used row to another thread and the iso value, an fp64 sum in a fixed order, does not depend on such rows.
@@ -469,6 +688,9 @@ struct BdLevel {
     PnGrid g{};
     int64_t ns = 0, nodes = 0, held = 0;  // stored blocks, 64 * ns, bytes taken from the pool
     Scratch act, num, first, coord, nbr, cls, sums, b, x, ap;
+    int64_t rows = 0;                     // rules 38-40: the nodes with a stencil row, and what the screened solve needs
+    Scratch nb27, has, ridx, rnode, tab, dinv;
+    BdScreen screen() const { return BdScreen{nb27.as<int32_t>(), has.as<uint8_t>(), ridx.as<int32_t>(), tab.as<double>()}; }
     BdView view() const { return BdView{e.G, e.T, e.Gb, act.as<uint8_t>(), num.as<int32_t>(), first.as<int32_t>()}; }
 };
 
@@ -478,6 +700,8 @@ struct BdDump {
     uint8_t *active, *cls;
     double *b, *chi;
     int64_t node_capacity;
+    int64_t* stencil = nullptr;           // mvs_test_poisson_band_screened_level only: [n1^3][27], f and the start values
+    double *f = nullptr, *start = nullptr;
 };
 
 // One call past its checks, the points on the device.
@@ -502,6 +726,12 @@ struct BdRun {
     BdExtent de{};                        // the block table of level Dd, when the sums live in blocks
     int64_t dns = 0, dslots = 0;          // stored blocks of the density grid; int64 sums held (64 dns, or every node of a dense grid)
     Scratch dnum, dcoord, dsum, rho, gain, dpart;
+    // rules 36-41 (mvs_poisson_reconstruct_band_screened): absent for the other calls, and for alpha = 0
+    const mvs_poisson_screen_params* sp = nullptr;
+    mvs_poisson_screen_info* sinfo = nullptr;
+    mvs_poisson_band_screen_info* bsinfo = nullptr;
+    Scratch used;                         // the used rows in their order, kept over the levels
+    std::vector<double> kept_b, kept_start;   // the hook's level: rule 28's b and the start values, before rules 39-40 change them
     std::unique_ptr<BdLevel> top;         // level D after levels()
     // the surface
     Scratch rows, mask, words;
@@ -513,6 +743,11 @@ struct BdRun {
         std::memset(&info, 0, sizeof info);
         std::memset(&binfo, 0, sizeof binfo);
         if (dinfo) std::memset(dinfo, 0, sizeof *dinfo);
+        if (c.screen) {
+            std::memset(c.sinfo, 0, sizeof *c.sinfo);
+            std::memset(c.bsinfo, 0, sizeof *c.bsinfo);
+            if (c.sp->alpha > 0.0) { sp = c.sp; sinfo = c.sinfo; bsinfo = c.bsinfo; }
+        }
     }
     bool weighted() const { return dp && (dp->flags & MVS_POISSON_WEIGHT_NORMALS); }
     PnDensitySums density_sums() const { return PnDensitySums{gd, bd_density_in_blocks(Dd, B) ? dnum.as<int32_t>() : nullptr, de.T, dsum.as<long long>()}; }
@@ -682,7 +917,7 @@ struct BdRun {
         L.nodes = L.ns * 64;
         size_t free_b = 0, total_b = 0;
         HIPCHK(hipMemGetInfo(&free_b, &total_b));
-        const int64_t need = bd_level_bytes(e, L.ns, l == D);
+        const int64_t need = bd_level_bytes(e, L.ns, l == D) + (sp ? bd_screen_block_bytes(L.ns) + bd_screen_work_bytes(L.ns) : 0);
         if (need > (int64_t)total_b) {
             mvs_set_error("%s: level %d stores %lld blocks and needs %lld bytes: more than the device has", fn, l, (long long)L.ns, (long long)need);
             return MVS_E_OOM;
@@ -715,6 +950,139 @@ struct BdRun {
         return count(L.cls.as<uint8_t>(), L.nodes, true, &binfo.n_free[l]);
     }
 
+    // occupied(l) of rule 38
+    int occupied_at(int l, int64_t* out) {
+        int rc;
+        const PnGrid g = grid_of(l);
+        const int64_t words = bd_occupancy_bytes(l) / 4;
+        Scratch bits;
+        if ((rc = take(bits, bd_occupancy_bytes(l)))) return rc;
+        HIPCHK(hipMemsetAsync(bits.p, 0, (size_t)bd_occupancy_bytes(l), s));
+        HIPCHK(hipMemsetAsync(cnt8.p, 0, 8, s));
+        k_bd_occupy<<<dim3(bd_grid(n)), dim3(PN_TPB), 0, s>>>(n, pts, nrm, g, bits.as<unsigned>());
+        k_bd_popcount<<<dim3(bd_grid(words)), dim3(PN_TPB), 0, s>>>(words, bits.as<unsigned>(), cnt8.as<unsigned long long>());
+        HIPCHK(hipGetLastError());
+        unsigned long long occ = 0;
+        rc = fetch(&occ, cnt8.p, 8);                                          // synchronises: bits may go
+        bytes.give(bd_occupancy_bytes(l));
+        *out = (int64_t)occ;
+        return rc;
+    }
+
+    // the used rows in their order (rule 29's list), once per call
+    int used_list() {
+        int rc;
+        const int64_t m = info.n_used, nbu = (n + PN_TPB - 1) / PN_TPB;
+        PnScan us;
+        if ((rc = us.alloc((size_t)nbu, s)) || (rc = take(used, bd_used_bytes(m)))) return rc;
+        if (us.bytes != bd_scan_bytes(n)) { mvs_set_error("%s: the scan over the points holds %lld bytes where the plan says %lld", fn, (long long)us.bytes, (long long)bd_scan_bytes(n)); return MVS_E_HIP; }
+        bytes.take(bd_scan_bytes(n));
+        k_bd_used_count<<<dim3((unsigned)nbu), dim3(PN_TPB), 0, s>>>(n, pts, nrm, us.cnt.as<int32_t>());
+        us.run((int)nbu, s);
+        k_bd_used_scatter<<<dim3((unsigned)nbu), dim3(PN_TPB), 0, s>>>(n, pts, nrm, us.base.as<int32_t>(), used.as<int64_t>());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(s));                                      // the scan may go
+        bytes.give(bd_scan_bytes(n));
+        return MVS_OK;
+    }
+    // rule 29's mean of x over the used points of the list
+    int mean_at_points(const BdLevel& L, const double* x, double* out) {
+        const int64_t m = info.n_used;
+        const int nb = (int)std::min<int64_t>(BD_RED_NB, (m + PN_TPB - 1) / PN_TPB);
+        double* part = red.as<double>() + 1;
+        k_bd_iso<<<dim3((unsigned)nb), dim3(PN_TPB), 0, s>>>(m, used.as<int64_t>(), pts, L.g, L.view(), x, part);
+        double sum = 0.0;
+        const int rc = folded(nb, part, &sum);
+        *out = sum / (double)info.n_used;
+        return rc;
+    }
+
+    // rules 38-40 on level l after fill(): occupied(l), lambda_l, the rows and their stencils, T_l on the start values, f in the place
+    // of b.  d (may be NULL): the hook's level, which takes the int64 sums, f and the start values here.
+    int screen_fill(BdLevel& L, int l, const BdDump* d) {
+        int rc;
+        if (L.ns == 0) return MVS_OK;
+        if ((rc = occupied_at(l, &bsinfo->occupied[l]))) return rc;
+        bsinfo->lambda[l] = pn_screen_lambda(sp->alpha, info.n_used, bsinfo->occupied[l]);
+        const BdView v = L.view();
+        const dim3 pgrid(bd_grid(n)), tb(PN_TPB);
+        const int64_t nb = (L.nodes + PN_TPB - 1) / PN_TPB;
+        {
+            Scratch flag;
+            PnScan sn;
+            // the arrays one by one, the bytes by the plan (bd_screen_block_bytes, bd_screen_work_bytes): the plan's tests hold for what is asked for here
+            if ((rc = L.nb27.alloc((size_t)(27 * 4 * L.ns), s)) || (rc = L.has.alloc((size_t)L.ns, s)) || (rc = L.ridx.alloc((size_t)(4 * L.nodes), s)) ||
+                (rc = L.dinv.alloc((size_t)(8 * L.nodes), s)) || (rc = flag.alloc((size_t)L.nodes, s)) || (rc = sn.alloc((size_t)nb, s))) return rc;
+            if (27 * 4 * L.ns + L.ns + 4 * L.nodes + 8 * L.nodes != bd_screen_block_bytes(L.ns) || L.nodes + sn.bytes != bd_screen_work_bytes(L.ns)) {
+                mvs_set_error("%s: level %d: the arrays of the screened solve are not what the plan counts", fn, l);
+                return MVS_E_HIP;
+            }
+            bytes.take(bd_screen_block_bytes(L.ns) + bd_screen_work_bytes(L.ns));
+            L.held += bd_screen_block_bytes(L.ns);
+            HIPCHK(hipMemsetAsync(flag.p, 0, (size_t)L.nodes, s));
+            HIPCHK(hipMemsetAsync(L.has.p, 0, (size_t)L.ns, s));
+            k_bd_nb27<<<dim3(bd_grid(27 * L.ns)), tb, 0, s>>>(L.ns, L.coord.as<int32_t>(), v, L.nb27.as<int32_t>());
+            k_bd_sc_flag<<<pgrid, tb, 0, s>>>(n, pts, nrm, L.g, v, flag.as<uint8_t>(), L.has.as<uint8_t>());
+            k_bd_sc_count<<<dim3((unsigned)nb), tb, 0, s>>>(L.nodes, flag.as<uint8_t>(), sn.cnt.as<int32_t>());
+            sn.run((int)nb, s);
+            HIPCHK(hipGetLastError());
+            int32_t rows = 0;                                                 // base[nb]: all flagged places
+            if ((rc = fetch(&rows, sn.base.as<int32_t>() + nb, 4))) return rc;
+            L.rows = bsinfo->active_nodes[l] = rows;
+            size_t free_b = 0, total_b = 0;
+            HIPCHK(hipMemGetInfo(&free_b, &total_b));
+            if (bd_level_bytes(L.e, L.ns, l == D) + bd_screen_block_bytes(L.ns) + bd_screen_row_bytes(L.rows) > (int64_t)total_b) {
+                mvs_set_error("%s: level %d has %lld stencil rows and needs %lld bytes for them: more than the device has", fn, l, (long long)L.rows,
+                              (long long)bd_screen_row_bytes(L.rows));
+                return MVS_E_OOM;
+            }
+            static_assert(BP_SC_ROW == PN_SC_ROW, "one row layout");
+            if ((rc = L.tab.alloc((size_t)(8 * PN_SC_ROW * L.rows), s)) || (rc = L.rnode.alloc((size_t)(4 * L.rows), s))) return rc;
+            bytes.take(bd_screen_row_bytes(L.rows));                          // 8 * BP_SC_ROW + 4 per row: the two arrays above
+            L.held += bd_screen_row_bytes(L.rows);
+            k_bd_sc_number<<<dim3((unsigned)nb), tb, 0, s>>>(L.nodes, flag.as<uint8_t>(), sn.base.as<int32_t>(), L.ridx.as<int32_t>(), L.rnode.as<int32_t>());
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipStreamSynchronize(s));                                  // flag and the scan go
+            bytes.give(bd_screen_work_bytes(L.ns));
+        }
+        HIPCHK(hipMemsetAsync(L.tab.p, 0, (size_t)(8 * PN_SC_ROW * L.rows), s));
+        k_bd_sc_splat<<<pgrid, tb, 0, s>>>(n, pts, nrm, L.g, v, bsinfo->lambda[l], L.ridx.as<int32_t>(), L.tab.as<unsigned long long>());
+        HIPCHK(hipGetLastError());
+        if (d && (rc = dump_stencil(L, *d))) return rc;
+        poisson_screen_convert(L.rows, L.tab.as<long long>(), s);
+        if (MVS_KNOB("MVS_BD_SC_JACOBI", 1, 0, 1) != 0.0)
+            k_bd_sc_dinv<true><<<dim3(bd_grid(L.nodes)), tb, 0, s>>>(L.nodes, L.ridx.as<int32_t>(), L.tab.as<double>(), L.dinv.as<double>());
+        else
+            k_bd_sc_dinv<false><<<dim3(bd_grid(L.nodes)), tb, 0, s>>>(L.nodes, L.ridx.as<int32_t>(), L.tab.as<double>(), L.dinv.as<double>());
+        HIPCHK(hipGetLastError());
+        if ((rc = mean_at_points(L, L.x.as<double>(), &bsinfo->target[l]))) return rc;
+        if (L.rows > 0) k_bd_sc_rhs<<<dim3(bd_grid(L.rows)), tb, 0, s>>>(L.rows, L.rnode.as<int32_t>(), L.cls.as<uint8_t>(), L.tab.as<double>(), bsinfo->target[l], L.b.as<double>());
+        HIPCHK(hipGetLastError());
+        return MVS_OK;
+    }
+
+    // the hook's int64 sums of level l, dense [n1^3][27], before they become doubles
+    int dump_stencil(const BdLevel& L, const BdDump& d) {
+        const BdExtent& e = L.e;
+        std::vector<long long> tab((size_t)(PN_SC_ROW * L.rows) + 1);
+        std::vector<int32_t> rnode((size_t)L.rows + 1), coord((size_t)L.ns + 1);
+        HIPCHK(hipStreamSynchronize(s));
+        HIPCHK(hipMemcpy(tab.data(), L.tab.p, 8 * (size_t)(PN_SC_ROW * L.rows), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(rnode.data(), L.rnode.p, 4 * (size_t)L.rows, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(coord.data(), L.coord.p, 4 * (size_t)L.ns, hipMemcpyDeviceToHost));
+        for (int64_t a = 0; a < L.rows; ++a) {
+            const int64_t at = rnode[(size_t)a];
+            const int lane = (int)(at & 63);
+            int bx, by, bz;
+            bd_unpack(coord[(size_t)(at >> 6)], &bx, &by, &bz);
+            const int ix = 4 * bx + (lane & 3), iy = 4 * by + (lane >> 2 & 3), iz = 4 * bz + (lane >> 4);
+            if (ix > e.G || iy > e.G || iz > e.G) continue;
+            const int64_t node = ((int64_t)iz * e.n1 + iy) * e.n1 + ix;
+            for (int k = 0; k < 27; ++k) d.stencil[27 * node + k] = tab[(size_t)(PN_SC_ROW * a + k)];
+        }
+        return MVS_OK;
+    }
+
     int folded(int np, double* part, double* out) {
         poisson_fold(part, np, red.as<double>(), s);
         HIPCHK(hipGetLastError());
@@ -734,6 +1102,9 @@ struct BdRun {
         double *x = L.x.as<double>(), *b = L.b.as<double>(), *ap = L.ap.as<double>();
         double *r = L.sums.as<double>(), *pa = r + L.nodes, *pb = r + 2 * L.nodes;      // the sums are spent
         double b2 = 0.0, r2 = 0.0;
+        const bool sc = sp != nullptr;                                        // rule 40: M_ff and f' in the place of A_ff and b'
+        const BdScreen q = L.screen();
+        const double* dinv = L.dinv.as<double>();
         k_bd_bnorm<<<gr, tb, 0, s>>>(L.ns, nbr, cls, x, b, part[3]);
         if ((rc = folded(np, part[3], &b2))) return rc;
         binfo.bnorm[l] = std::sqrt(b2);
@@ -743,19 +1114,26 @@ struct BdRun {
             return MVS_OK;
         }
         HIPCHK(hipMemsetAsync(L.sums.p, 0, (size_t)(24 * L.nodes), s));
-        k_bd_residual<true><<<gr, tb, 0, s>>>(L.ns, nbr, cls, x, b, r, part[0]);
-        if ((rc = folded(np, part[0], &r2))) return rc;
+        if (sc) k_bd_sc_residual<true><<<gr, tb, 0, s>>>(L.ns, nbr, cls, q, x, b, dinv, r, part[3], part[0]);
+        else k_bd_residual<true><<<gr, tb, 0, s>>>(L.ns, nbr, cls, x, b, r, part[0]);
+        if ((rc = folded(np, part[sc ? 3 : 0], &r2))) return rc;
         binfo.rel_residual[l] = std::sqrt(r2) / std::sqrt(b2);
         if (std::sqrt(r2) <= p.solve_tol * std::sqrt(b2)) return MVS_OK;
         int cur = 0, it = 0;
         for (int c = 1; c <= p.max_cycles; ++c) {
             for (int k = 0; k < 64; ++k, ++it) {
-                k_bd_apply<<<gr, tb, 0, s>>>(L.ns, nbr, cls, it == 0 ? 1 : 0, np, part[cur], part[cur ^ 1], r, pa, pb, ap, part[2]);
-                k_bd_update<<<gr, tb, 0, s>>>(L.ns, np, part[cur], part[2], pb, ap, x, r, part[cur ^ 1]);
+                if (sc) {
+                    k_bd_sc_apply<<<gr, tb, 0, s>>>(L.ns, nbr, cls, q, it == 0 ? 1 : 0, np, part[cur], part[cur ^ 1], r, dinv, pa, pb, ap, part[2]);
+                    k_bd_sc_update<<<gr, tb, 0, s>>>(L.ns, np, part[cur], part[2], pb, ap, dinv, x, r, part[cur ^ 1]);
+                } else {
+                    k_bd_apply<<<gr, tb, 0, s>>>(L.ns, nbr, cls, it == 0 ? 1 : 0, np, part[cur], part[cur ^ 1], r, pa, pb, ap, part[2]);
+                    k_bd_update<<<gr, tb, 0, s>>>(L.ns, np, part[cur], part[2], pb, ap, x, r, part[cur ^ 1]);
+                }
                 cur ^= 1;
                 std::swap(pa, pb);
             }
-            k_bd_residual<false><<<gr, tb, 0, s>>>(L.ns, nbr, cls, x, b, nullptr, part[3]);
+            if (sc) k_bd_sc_residual<false><<<gr, tb, 0, s>>>(L.ns, nbr, cls, q, x, b, nullptr, nullptr, part[3], nullptr);
+            else k_bd_residual<false><<<gr, tb, 0, s>>>(L.ns, nbr, cls, x, b, nullptr, part[3]);
             if ((rc = folded(np, part[3], &r2))) return rc;
             binfo.iterations[l] = it;
             binfo.rel_residual[l] = std::sqrt(r2) / std::sqrt(b2);
@@ -786,6 +1164,7 @@ struct BdRun {
                 for (int bx = 0; bx < e.Gb; ++bx) d.active[((int64_t)bz * e.Gb + by) * e.Gb + bx] = act[(size_t)bd_table_at(e, bx, by, bz)];
         const double nan = std::numeric_limits<double>::quiet_NaN();
         for (int64_t i = 0; i < nn; ++i) { d.cls[i] = BD_NONE; d.b[i] = nan; d.chi[i] = nan; }
+        if (d.f) for (int64_t i = 0; i < nn; ++i) d.f[i] = d.start[i] = nan;
         for (int64_t sb = 0; sb < L.ns; ++sb) {
             int bx, by, bz;
             bd_unpack(coord[(size_t)sb], &bx, &by, &bz);
@@ -797,6 +1176,11 @@ struct BdRun {
                 d.cls[node] = cls[at];
                 d.b[node] = cls[at] == BD_FREE ? hb[at] : 0.0;
                 d.chi[node] = hx[at];
+                if (d.f) {                                                   // b_dev holds f; rule 28's b and the start values were kept
+                    d.f[node] = d.b[node];
+                    d.b[node] = cls[at] == BD_FREE ? kept_b[at] : 0.0;
+                    d.start[node] = kept_start[at];
+                }
             }
         }
         return MVS_OK;
@@ -809,7 +1193,7 @@ struct BdRun {
         pb.depth_min = pb.depth_max = B;
         pb.max_cycles = (int32_t)std::min<int64_t>((int64_t)p.max_cycles * 64, INT32_MAX);   // rule 25: one budget for every solve of the call
         mvs_poisson_info ib;
-        const PnCall cb{fn, PN_PLAIN, n, pts, nrm, &pb, &ib, nullptr, nullptr, nullptr, nullptr};
+        const PnCall cb{fn, PN_PLAIN, n, pts, nrm, &pb, &ib, nullptr, nullptr, sp, sinfo};    // sp: rule 37, the screened chi_B
         std::unique_ptr<PnBaseField> base(new PnBaseField);
         rc = base->solve(cb, pts, nrm, s, weighted() ? gain.as<double>() : nullptr);
         info.cycles = ib.cycles;
@@ -817,6 +1201,7 @@ struct BdRun {
         if (rc == MVS_E_SOLVER) binfo.failed_level = B;
         if (rc) return rc;
         bytes.take(base->bytes);
+        if (sp && (rc = used_list())) return rc;
         std::unique_ptr<BdLevel> below;
         for (int l = B + 1; l <= D; ++l) {
             std::unique_ptr<BdLevel> L(new BdLevel);
@@ -826,6 +1211,15 @@ struct BdRun {
             if (below) rc = fill(*L, l, BdBlockCoarse{below->view(), below->x.as<double>()});
             else rc = fill(*L, l, BdDenseCoarse{base->chi, 1 << B});
             if (rc) return rc;
+            if (d && d->level == l && d->stencil) std::memset(d->stencil, 0, 27 * 8 * (size_t)L->e.n1 * L->e.n1 * L->e.n1);   // rows are written over it
+            if (d && d->level == l && d->f && L->ns > 0) {
+                kept_b.resize((size_t)L->nodes);
+                kept_start.resize((size_t)L->nodes);
+                HIPCHK(hipStreamSynchronize(s));
+                HIPCHK(hipMemcpy(kept_b.data(), L->b.p, 8 * (size_t)L->nodes, hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(kept_start.data(), L->x.p, 8 * (size_t)L->nodes, hipMemcpyDeviceToHost));
+            }
+            if (sp && (rc = screen_fill(*L, l, d && d->level == l && d->stencil ? d : nullptr))) return rc;
             HIPCHK(hipStreamSynchronize(s));                                  // the level below has been read: it goes back to the pool
             if (below) { bytes.give(below->held); below.reset(); }
             if (base) { bytes.give(base->bytes); base.reset(); }
@@ -843,9 +1237,14 @@ struct BdRun {
     int iso_value() {
         int rc;
         const BdLevel& L = *top;
+        if (sp) {                                                             // rule 41: the list of the call
+            rc = mean_at_points(L, L.x.as<double>(), &iso);
+            info.iso = iso;
+            return rc;
+        }
         const int64_t m = info.n_used, nbu = (n + PN_TPB - 1) / PN_TPB;
         PnScan us;
-        Scratch used;
+        Scratch used;                                                         // of this stage only
         if ((rc = us.alloc((size_t)nbu, s)) || (rc = take(used, 8 * m))) return rc;
         bytes.take(us.bytes);
         k_bd_used_count<<<dim3((unsigned)nbu), dim3(PN_TPB), 0, s>>>(n, pts, nrm, us.cnt.as<int32_t>());
@@ -921,7 +1320,10 @@ int check_band_call(const BdCall& c, const void* out_a, int64_t cap_a, const voi
     const PnCall pc{c.fn, PN_PLAIN, c.n, c.points, c.normals, c.p, c.info, nullptr, nullptr, nullptr, nullptr};
     int rc = poisson_check_plain(pc, BD_MAX_D, out_a, cap_a, out_b, cap_b);
     if (!rc) rc = check_band(c.fn, c.bp, c.binfo);
-    return !rc && c.density ? poisson_check_density(c.fn, c.n, c.dp, c.dinfo) : rc;
+    if (!rc && c.density) rc = poisson_check_density(c.fn, c.n, c.dp, c.dinfo);
+    if (!rc && c.screen) rc = poisson_check_screen(c.fn, c.sp, c.sinfo);
+    if (!rc && c.screen && !c.bsinfo) rc = bad(c.fn, "bsinfo is NULL");
+    return rc;
 }
 
 // the device form of the entry, after its checks
@@ -929,9 +1331,10 @@ int band_reconstruct(const BdCall& c, const double* pts, const double* nrm, PnOu
     int rc;
     BdRun run(c, pts, nrm, s);
     if ((rc = run.depth())) return rc;
-    if (run.D <= run.B) {                                                     // rules 24 and 32: the plain or the density call at depth D, its bytes
+    if (run.D <= run.B) {                                                     // rules 24, 32 and 36: the plain, the density or the screened call at depth D, its bytes
         mvs_poisson_params pd = *c.p;
         pd.depth_min = pd.depth_max = run.D;
+        if (c.screen) return poisson_dense_dev(PnCall{c.fn, PN_SCREENED, c.n, pts, nrm, &pd, c.info, c.dp, c.dinfo, c.sp, c.sinfo}, pts, nrm, o, s);
         return poisson_dense_dev(PnCall{c.fn, c.density ? PN_DENSITY : PN_PLAIN, c.n, pts, nrm, &pd, c.info, c.dp, c.dinfo, nullptr, nullptr}, pts, nrm, o, s);
     }
     if (c.density && (rc = run.density())) { run.finish_info(); return rc; }
@@ -1057,6 +1460,48 @@ int mvs_test_poisson_band_density_level(int64_t n, const double* points, const d
     if (rc) return rc;
     if (!active || !cls || !b || !chi || !node_sums || !rho || !gain) return bad(__func__, "active, cls, b, chi, node_sums, rho or gain is NULL");
     return band_level(c, BdDump{level, active, cls, b, chi, node_capacity}, node_sums, density_node_capacity, rho, gain);
+}
+
+// ------------------------------------------------------------------ rules 36-41 ----
+int mvs_poisson_reconstruct_band_screened_dev(int64_t n, const double* points_dev, const double* normals_dev, const mvs_poisson_params* p,
+                                              const mvs_poisson_band_params* bparams, const mvs_poisson_density_params* dparams,
+                                              mvs_poisson_info* info, mvs_poisson_band_info* binfo, mvs_poisson_density_info* dinfo,
+                                              double* vertices_dev, double* vertex_density_dev, int64_t vertex_capacity, int32_t* faces_dev,
+                                              int64_t face_capacity, void* hip_stream, const mvs_poisson_screen_params* sparams,
+                                              mvs_poisson_screen_info* sinfo, mvs_poisson_band_screen_info* bsinfo) {
+    MVS_TRACE();
+    const BdCall c{__func__, n, points_dev, normals_dev, p, bparams, info, binfo, dparams, dinfo, true, sparams, sinfo, bsinfo, true};
+    int rc = check_band_call(c, vertices_dev, vertex_capacity, faces_dev, face_capacity);
+    if (rc || (rc = need_device())) return rc;
+    return band_reconstruct(c, points_dev, normals_dev, PnOut{vertices_dev, vertex_density_dev, faces_dev, vertex_capacity, face_capacity}, (hipStream_t)hip_stream);
+}
+
+int mvs_poisson_reconstruct_band_screened(int64_t n, const double* points, const double* normals, const mvs_poisson_params* p,
+                                          const mvs_poisson_band_params* bparams, const mvs_poisson_density_params* dparams, mvs_poisson_info* info,
+                                          mvs_poisson_band_info* binfo, mvs_poisson_density_info* dinfo, double* vertices, double* vertex_density,
+                                          int64_t vertex_capacity, int32_t* faces, int64_t face_capacity, const mvs_poisson_screen_params* sparams,
+                                          mvs_poisson_screen_info* sinfo, mvs_poisson_band_screen_info* bsinfo) {
+    MVS_TRACE();
+    return band_reconstruct_host(BdCall{__func__, n, points, normals, p, bparams, info, binfo, dparams, dinfo, true, sparams, sinfo, bsinfo, true}, vertices,
+                                 vertex_density, vertex_capacity, faces, face_capacity);
+}
+
+// The call up to rule 41's iso value, level `level` with its stencil sums, f and start values handed out dense (include/mvs_test.h)
+int mvs_test_poisson_band_screened_level(int64_t n, const double* points, const double* normals, const mvs_poisson_params* p,
+                                         const mvs_poisson_band_params* bparams, const mvs_poisson_density_params* dparams, mvs_poisson_info* info,
+                                         mvs_poisson_band_info* binfo, mvs_poisson_density_info* dinfo, int32_t level, uint8_t* active, uint8_t* cls,
+                                         double* b, double* chi, int64_t node_capacity, int64_t* node_sums, int64_t density_node_capacity, double* rho,
+                                         double* gain, const mvs_poisson_screen_params* sparams, mvs_poisson_screen_info* sinfo,
+                                         mvs_poisson_band_screen_info* bsinfo, int64_t* stencil, double* f, double* start) {
+    MVS_TRACE();
+    const BdCall c{__func__, n, points, normals, p, bparams, info, binfo, dparams, dinfo, true, sparams, sinfo, bsinfo, true};
+    const int rc = check_band_call(c, b, node_capacity, node_sums, density_node_capacity);
+    if (rc) return rc;
+    if (!active || !cls || !b || !chi || !node_sums || !rho || !gain || !stencil || !f || !start)
+        return bad(__func__, "active, cls, b, chi, node_sums, rho, gain, stencil, f or start is NULL");
+    BdDump d{level, active, cls, b, chi, node_capacity};
+    d.stencil = stencil; d.f = f; d.start = start;
+    return band_level(c, d, node_sums, density_node_capacity, rho, gain);
 }
 
 }  // extern "C"

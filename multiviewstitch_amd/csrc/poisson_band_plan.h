@@ -1,9 +1,11 @@
 // poisson_band_plan.h — the sizes and index arithmetic the host does for the band levels of the Poisson stage (rules 24-31,
 // poisson_band_rules.h): the extents of a level's block table, the bytes a level takes, the test that its stored nodes fit an int32
 // index, the row and slab tables bd_segment reads, the bytes of the density structure of rules 32-34 (16 bytes per row for rho_p and
-// s_p, and the node sums dense or in blocks), and the bookkeeping of the bytes a call holds.  Plain C++ without a HIP call:
+// s_p, and the node sums dense or in blocks), the bytes of the stencil rows and block tables of rules 38-40, and the bookkeeping of
+// the bytes a call holds.  Plain C++ without a HIP call:
 // poisson_band.hip uses it, and tests/poisson_band_plan.cpp runs it as a program of its own under the address and undefined-behaviour
-// sanitizers, on block sets of its own and at the extents of depth 10, before anything runs on a device.
+// sanitizers, on block sets of its own and at the extents of depth 10, before anything runs on a device
+// (tests/poisson_band_screened_plan.cpp does the same for the screened call's part).
 #ifndef MVS_POISSON_BAND_PLAN_H_
 #define MVS_POISSON_BAND_PLAN_H_
 #include <stddef.h>
@@ -70,6 +72,25 @@ inline int64_t bd_density_work_bytes(int Dd, int B) {
     const BdExtent e = bd_extent(Dd);
     return 2 * e.table + (2 * e.rows + 1) * 4;
 }
+
+// Rules 38-40, what a level of mvs_poisson_reconstruct_band_screened holds beyond bd_level_bytes while it lives.  Per stored block the
+// 27 neighbours of the block (int32, offset order of rule 20) and the byte that says whether a node of it has a row; per stored node
+// the int32 number of its row and the double of the preconditioner.  Per row (a node that a used point touches) BP_SC_ROW doubles —
+// the 27 entries and the row sum — and the int32 place of its node.
+#define BP_SC_ROW 28
+inline int64_t bd_screen_block_bytes(int64_t stored) { return stored * (27 * 4 + 1 + (int64_t)BP_BLOCK_NODES * (4 + 8)); }
+inline int64_t bd_screen_row_bytes(int64_t rows) { return rows * (8 * BP_SC_ROW + 4); }
+// ... and while its rows are numbered: a flag byte per stored node and the counts, the scan's rows and the bases of the compaction
+// (256 nodes per workgroup, 4096 workgroups per row of the scan: poisson_base.h's PnScan)
+inline int64_t bd_scan_bytes(int64_t items) {
+    const int64_t nb = (items + 255) / 256, rows = (nb + 4095) / 4096;
+    return 4 * nb + 4 * (nb + 1) + 4 * rows * 4097 + 4 * rows + 4 * (rows + 1);
+}
+inline int64_t bd_screen_work_bytes(int64_t stored) { return stored * BP_BLOCK_NODES + bd_scan_bytes(stored * BP_BLOCK_NODES); }
+// occupied(l) of rule 38: one bit per cell of level l while it is counted
+inline int64_t bd_occupancy_bytes(int l) { return ((int64_t)1 << (3 * l)) / 8; }
+// the list of the used points, kept over the levels for rules 39 and 41, and its scan while it is made (n rows, N used)
+inline int64_t bd_used_bytes(int64_t n_used) { return 8 * n_used; }
 
 // The row firsts of a level from its row counts: first[r] = the stored blocks in the rows before r (rows in (bz, by) order), first[rows]
 // = all stored blocks.  -> that total, or -1 when a count is negative or exceeds T (the table cannot be right).

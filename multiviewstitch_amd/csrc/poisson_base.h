@@ -13,6 +13,8 @@
 int poisson_check_plain(const PnCall& c, int max_depth, const void* out_a, int64_t cap_a, const void* out_b, int64_t cap_b);
 // check_call's part for dparams and dinfo (rules 14-16); before a device is needed
 int poisson_check_density(const char* fn, int64_t n, const mvs_poisson_density_params* dp, const void* dinfo);
+// check_call's part for sparams and sinfo (rule 19); before a device is needed
+int poisson_check_screen(const char* fn, const mvs_poisson_screen_params* sp, const void* sinfo);
 // rules 1-2: the origin and side of the cube and N.  c.info is zeroed and receives n_used and origin.  MVS_E_DEGENERATE as the plain call.
 int poisson_cube(const PnCall& c, const double* pts_dev, const double* nrm_dev, hipStream_t s, double origin[3], double* side);
 // The base stage: rules 1-8 at depth c.p->depth_min (the caller sets depth_min = depth_max), and one V-cycle past rule 8's criterion.  c.p and c.info outlive the object;
@@ -26,7 +28,8 @@ struct PnBaseField {
     PnBaseField(const PnBaseField&) = delete;
     PnBaseField& operator=(const PnBaseField&) = delete;
     ~PnBaseField();
-    // gain_dev (may be NULL): s_p per row, rule 16's splat x = w * (n_a * s_p) instead of rule 5's
+    // gain_dev (may be NULL): s_p per row, rule 16's splat x = w * (n_a * s_p) instead of rule 5's.  With c.sp and c.sinfo (rule 37)
+    // chi is the screened field of rules 19-22, its solve too run one cycle past its criterion; c.sinfo describes it.
     int solve(const PnCall& c, const double* pts_dev, const double* nrm_dev, hipStream_t s, const double* gain_dev = nullptr);
 };
 // The scan between a count and a scatter kernel, for nb workgroups: the count kernel writes cnt, run() leaves base[b] = the survivors in
@@ -39,6 +42,10 @@ struct PnScan {
 };
 // *out_dev = the sum of n partials, by one workgroup in a fixed order (k_pn_fold)
 void poisson_fold(const double* part_dev, int n, double* out_dev, hipStream_t s);
+// A stencil row of rules 20 and 38 as the kernels keep it: the 27 entries in the offset order of rule 20, then the row sum.
+constexpr int PN_SC_ROW = 28;
+// k_sc_convert over `rows` rows: the 27 int64 sums of every row and their int64 sum become doubles in place
+void poisson_screen_convert(int64_t rows, long long* tab_dev, hipStream_t s);
 // rule 12's count: cnt_dev[workgroup] = the face items (of `items`, 12 per cube item of mask_dev) that hold a triangle
 void poisson_face_count(const uint8_t* mask_dev, int64_t items, int32_t* cnt_dev, hipStream_t s);
 

@@ -62,8 +62,12 @@ struct BdCall {
     const mvs_poisson_density_params* dp = nullptr;      // rules 32-35; the band call has neither
     mvs_poisson_density_info* dinfo = nullptr;
     bool density = false;
+    const mvs_poisson_screen_params* sp = nullptr;        // rules 36-41 (mvs_poisson_reconstruct_band_screened); the other two calls have none
+    mvs_poisson_screen_info* sinfo = nullptr;
+    mvs_poisson_band_screen_info* bsinfo = nullptr;
+    bool screen = false;
 };
-// poisson_blocks for the two band calls, the points on the device; density (used when c.density) receives d_v of rule 34 per vertex
+// poisson_blocks for the band calls, the points on the device; density (used when c.density) receives d_v of rule 34 per vertex
 int poisson_band_blocks(const BdCall& c, Scratch* vertices, Scratch* density, Scratch* faces);
 // mvs_mesh_trim_by_value_dev (mesh_trim.hip, rule 18) with arguments the caller has validated.  Synchronises s.
 int mesh_trim_dev(int64_t V, const double* vertices, const double* normals, int64_t F, const int32_t* faces, const double* values, double thr,

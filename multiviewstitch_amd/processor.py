@@ -686,8 +686,8 @@ def PoissonFiles(psr_npts, model_obj, params: L.CPoissonParams | None = None, dp
     (``poisson_screen_params``) the call is ``mvs_processor_poisson_screened``: the field pulled to the iso value at every point.
     With ``bparams`` (``poisson_band_params``) the call is ``mvs_processor_poisson_band``, the band-refined levels up to depth 10;
     ``bparams`` with ``dparams`` AND ``trim_ratio`` (0.0: no trim) is ``mvs_processor_poisson_band_density``, those levels weighted and
-    trimmed by the sampling density as above; ``bparams`` with only one of the two raises, as it did before that call existed.  The
-    band levels are unscreened, so ``bparams`` together with ``sparams`` raises."""
+    trimmed by the sampling density as above; ``bparams`` with only one of the two raises, as it did before that call existed.
+    ``bparams`` together with ``sparams`` raises here: the band levels with screening are ``PoissonBandScreenedFiles``."""
     prm = params if params is not None else poisson_params()
     V, F = C.c_int64(), C.c_int64()
     if bparams is not None:
@@ -722,11 +722,14 @@ def _poisson_band_info(binfo: L.CPoissonBandInfo) -> dict:
                 scratch_bytes=binfo.scratch_bytes, base_depth=binfo.base_depth, failed_level=binfo.failed_level)
 
 
-def _run_poisson_band(points, normals, prm, bprm, dprm, stream, capacity):
-    """the call behind ``RunPoissonBand`` (``dprm`` None: mvs_poisson_reconstruct_band) and ``RunPoissonBandDensity``
-    (mvs_poisson_reconstruct_band_density), host or device form
-    -> (vertices, faces, vertex density or None, info struct, band info struct, density info struct or None)"""
-    name = "mvs_poisson_reconstruct_band" if dprm is None else "mvs_poisson_reconstruct_band_density"
+def _run_poisson_band(points, normals, prm, bprm, dprm, stream, capacity, sprm=None):
+    """the call behind ``RunPoissonBand`` (``dprm`` None: mvs_poisson_reconstruct_band), ``RunPoissonBandDensity``
+    (mvs_poisson_reconstruct_band_density) and ``RunPoissonBandScreened`` (``sprm`` given: mvs_poisson_reconstruct_band_screened), host or
+    device form
+    -> (vertices, faces, vertex density or None, info struct, band info struct, density info struct or None[, screen info struct, band
+    screen info struct])"""
+    name = "mvs_poisson_reconstruct_band" if dprm is None else "mvs_poisson_reconstruct_band_density" if sprm is None else \
+        "mvs_poisson_reconstruct_band_screened"
     dev = _is_dev(points)
     if dev != _is_dev(normals):
         raise L.MvsError(-1, "points and normals must both be tensors on the GPU or both arrays")
@@ -752,6 +755,8 @@ def _run_poisson_band(points, normals, prm, bprm, dprm, stream, capacity):
         dmax = max(0, min(int(prm.depth_max), L.POISSON_BAND_MAX_DEPTH))
         capacity = (12 * 4 ** dmax, 24 * 4 ** dmax)
     info, binfo, dinfo = L.CPoissonInfo(), L.CPoissonBandInfo(), None if dprm is None else L.CPoissonDensityInfo()
+    sinfo, bsinfo = L.CPoissonScreenInfo(), L.CPoissonBandScreenInfo()
+    screen = () if sprm is None else (C.byref(sprm), C.byref(sinfo), C.byref(bsinfo))
     with order:
         def call(vcap, fcap):
             # v, f and d are named here and returned: the addresses handed to the library stay those of live arrays
@@ -760,7 +765,7 @@ def _run_poisson_band(points, normals, prm, bprm, dprm, stream, capacity):
                 return fn(n, pp, pn, C.byref(prm), C.byref(bprm), C.byref(info), C.byref(binfo), L.ptr(v), vcap, L.ptr(f), fcap, *tail), v, f, None
             d = _out_like(points, (max(1, vcap),), "float64")
             rc = fn(n, pp, pn, C.byref(prm), C.byref(bprm), C.byref(dprm), C.byref(info), C.byref(binfo), C.byref(dinfo), L.ptr(v), L.ptr(d), vcap,
-                    L.ptr(f), fcap, *tail)
+                    L.ptr(f), fcap, *tail, *screen)
             return rc, v, f, d
 
         vcap, fcap = int(capacity[0]), int(capacity[1])
@@ -773,7 +778,8 @@ def _run_poisson_band(points, normals, prm, bprm, dprm, stream, capacity):
     except L.MvsError as e:
         e.info, e.band_info = _poisson_info(info), _poisson_band_info(binfo)
         raise
-    return v[:info.n_vertices], f[:info.n_faces], None if d is None else d[:info.n_vertices], info, binfo, dinfo
+    out = v[:info.n_vertices], f[:info.n_faces], None if d is None else d[:info.n_vertices], info, binfo, dinfo
+    return out if sprm is None else out + (sinfo, bsinfo)
 
 
 def RunPoissonBand(points, normals, params: L.CPoissonParams | None = None, bparams: L.CPoissonBandParams | None = None,
@@ -853,6 +859,48 @@ def RunPoissonScreened(points, normals, params: L.CPoissonParams | None = None, 
     out.update({"target": sinfo.target, "lambda": sinfo.lambda_, "occupied": sinfo.occupied, "active_nodes": sinfo.active_nodes,
                 "screen_cycles": sinfo.cycles, "screen_rel_residual": sinfo.rel_residual, "iso_unscreened": sinfo.iso_unscreened})
     return v, f, d, out
+
+
+def _poisson_screen_info(sinfo: L.CPoissonScreenInfo) -> dict:
+    return {"target": sinfo.target, "lambda": sinfo.lambda_, "occupied": sinfo.occupied, "active_nodes": sinfo.active_nodes,
+            "screen_cycles": sinfo.cycles, "screen_rel_residual": sinfo.rel_residual, "iso_unscreened": sinfo.iso_unscreened}
+
+
+def _poisson_band_screen_info(bsinfo: L.CPoissonBandScreenInfo) -> dict:
+    return {"lambda": list(bsinfo.lambda_), "target": list(bsinfo.target), "occupied": list(bsinfo.occupied),
+            "active_nodes": list(bsinfo.active_nodes)}
+
+
+def RunPoissonBandScreened(points, normals, params: L.CPoissonParams | None = None, bparams: L.CPoissonBandParams | None = None,
+                           dparams: L.CPoissonDensityParams | None = None, sparams: L.CPoissonScreenParams | None = None,
+                           stream: int | None = None, capacity: tuple | None = None):
+    """``mvs_poisson_reconstruct_band_screened`` (rules 36-41 of include/mvs.h, this library's definition): ``RunPoissonBandDensity``
+    with a screened solve on the base level and on every band level, the field pulled to the level's target at every point with the
+    weight ``sparams.alpha`` (4 by default; 0: the bytes of ``RunPoissonBandDensity``).  Arguments as ``RunPoisson``.
+    -> (vertices [V, 3] float64, faces [F, 3] int32, vertex_density [V] float64, info dict, band info dict and density info dict as
+    ``RunPoissonBandDensity``'s, screen info dict of the base level: target, lambda, occupied, active_nodes, screen_cycles,
+    screen_rel_residual, iso_unscreened; band screen info dict: per level (lists indexed by the level) lambda, target, occupied,
+    active_nodes).  When the call fails, the exception carries ``info`` and ``band_info`` as far as they were written."""
+    v, f, d, info, binfo, dinfo, sinfo, bsinfo = _run_poisson_band(points, normals, params if params is not None else poisson_params(),
+                                                                   bparams if bparams is not None else poisson_band_params(),
+                                                                   dparams if dparams is not None else poisson_density_params(), stream, capacity,
+                                                                   sparams if sparams is not None else poisson_screen_params())
+    return (v, f, d, _poisson_info(info), _poisson_band_info(binfo), _poisson_density_info(dinfo), _poisson_screen_info(sinfo),
+            _poisson_band_screen_info(bsinfo))
+
+
+def PoissonBandScreenedFiles(psr_npts, model_obj, params: L.CPoissonParams | None = None, bparams: L.CPoissonBandParams | None = None,
+                             dparams: L.CPoissonDensityParams | None = None, sparams: L.CPoissonScreenParams | None = None,
+                             trim_ratio: float = 0.0):
+    """``mvs_processor_poisson_band_screened``: ``PoissonFiles`` through ``mvs_poisson_reconstruct_band_screened`` — reconstruct, trim
+    where the vertex density lies below ``trim_ratio`` times the mean point density (0.0: no trim), vertex normals, write.  A parameter
+    struct left None takes its defaults.  -> (V, F, n_open_edges), the open edges counted on the untrimmed mesh."""
+    V, F, opened = C.c_int64(), C.c_int64(), C.c_int64()
+    L.check(L.lib().mvs_processor_poisson_band_screened(os.fsencode(psr_npts), None if params is None else C.byref(params),
+                                                        None if bparams is None else C.byref(bparams), None if dparams is None else C.byref(dparams),
+                                                        None if sparams is None else C.byref(sparams), float(trim_ratio), os.fsencode(model_obj),
+                                                        C.byref(V), C.byref(F), C.byref(opened)))
+    return V.value, F.value, opened.value
 
 
 def TrimByValue(vertices, faces, values, threshold: float, normals=None, stream: int | None = None):

@@ -324,8 +324,8 @@ int mvs_sequence_pair_srt(int32_t n1, int32_t n2, const mvs_camera* cams1, const
  *   colour      : the four branches of :179-211 (both equal, u11 == u22, v11 == v22, bilinear) with the reference's expressions and
  *                 summation order, (uchar) of the double; tex = v11*w + u11 for the both-equal branch, else int(vf+0.5)*w + int(uf+0.5).
  * Deviations: a destination pixel nothing paints is uninitialised cv::Mat memory in the reference; here it is (0,0,0), tex = -1.  The
- * reference writes the views as JPEG and SIFT reads them back; this library has no image codec: the entry returns the rasters, and
- * what SIFT sees after the JPEG round trip is not pinned.
+ * reference writes the views as JPEG and SIFT reads them back; this library has a JPEG decoder (mvs_jpeg_decode) and no encoder: the
+ * entry returns the rasters, and what SIFT sees after the JPEG round trip is not pinned.
  * MVS_E_INVALID_ARG: view_count < 1, axis outside 0..2, n_frames < 1, cameras of differing sizes, a NULL pointer, w or h > 65535. */
 int mvs_gen_new_views(int32_t n_frames, const mvs_camera* cams, const uint8_t* imgs /*n x h x w x 3*/, int32_t view_count, int32_t axis,
                       double rot_angle, uint8_t* views /*n x views x h x w x 3*/, int32_t* tex /*n x views x w*h*/);
@@ -720,6 +720,62 @@ int mvs_refine_depth_maps(int32_t n_seq, const int32_t* cam_off /*n_seq+1*/, con
 int mvs_refine_depth_maps_dev(int32_t n_seq, const int32_t* cam_off, const mvs_camera* cams, const uint8_t* imgs_dev,
                               const float* depths_dev, const mvs_depth_refine_params* p, float* out_dev, int8_t* k_out_dev,
                               int32_t* sum_out_dev, uint8_t* cnt_out_dev, void* hip_stream);
+
+/* ------------------------------------------------- base images (cv::imread of <imgdir>%05d.jpg) -- */
+/* The batched baseline JPEG decoder: the frames the reference opens with cv::imread (R/Image3D/Image3D.cpp:21, R/Processor/Processor.cpp:
+ * 532,545, R/FeatureProc/FeatureProc.cpp:26, R/DepthRecovery/DepthOptimizer.cpp:13-14), all images of a call through each kernel in one
+ * launch.  The rules below are this library's definition.  They are pinned byte for byte against the default decompressor of
+ * libjpeg-turbo (API 6.2, as Pillow 12.2.0 runs it: np.asarray(Image.open(f))) on the streams of tests/golden/jpeg.  They are NOT VERIFIED
+ * against the libjpeg that OpenCV 3.0 bundles in the reference's build: an IJG 9 build upsamples the chroma of subsampled files
+ * differently.
+ *   J1 accepted  : SOF0 and SOF1 (8-bit, Huffman); 1 component, or 3 components taken as Y Cb Cr; one interleaved scan; sampling factors
+ *                  luma 1x1, 2x1 or 2x2 with chroma 1x1 (a single component counts as 1x1 whatever it states); DQT with 8- or 16-bit
+ *                  entries; up to 4 + 4 Huffman tables; DRI / RSTn; APPn and COM skipped, the EXIF orientation ignored as cv::imread of
+ *                  OpenCV 3.0 does.  Everything else is MVS_E_IO with the image index and the feature in mvs_last_error():
+ *                  "progressive", "arithmetic coding", "lossless or hierarchical", "12-bit samples", "<n> components", "Adobe transform
+ *                  0", "non-interleaved or multi-scan", "sampling factors";
+ *   J2 walk      : host code.  It reads the sizes, the tables and the segment table: one entry per restart interval, or one for the whole
+ *                  scan when DRI = 0, each with image, first byte, end byte, first MCU and MCU count.  A marker is FF followed by a byte
+ *                  that is neither 00 nor FF; a segment ends at the FF of the next marker or at the end of the data.  The scan must hold
+ *                  exactly ceil(MCUs / interval) segments and end with EOI or with the data.  The walk reads nothing past len;
+ *   J3 entropy   : canonical Huffman codes of 1-16 bits from BITS / HUFFVAL; receive / extend as T.81 F.2.2; the DC predictor of every
+ *                  component is 0 at the start of every segment; FF 00 is one FF byte, an FF followed by anything else ends the
+ *                  segment's bits; size categories up to 15; the predictor is int32 (wrapping), a coefficient is stored as int16,
+ *                  truncating.  A segment that runs out of bits, or meets a code that is not in its table, a run past coefficient 63 (a
+ *                  ZRL that ends past 64 included) or a DC size category above 15 makes the call fail with MVS_E_IO naming the image.
+ *                  The decoder never reads a byte outside its segment and never writes outside its MCU range; every loop is bounded by
+ *                  the segment's byte count and by MCUs x blocks x 64;
+ *   J4 IDCT      : libjpeg's jidctint (Loeffler-Ligtenberg-Moshovitz, CONST_BITS 13, PASS1_BITS 2): columns first, the quantiser
+ *                  multiplied in, descaled by 11; then rows, descaled by 18, + 128, clamped to 0..255.  Constants 2446, 3196, 4433, 6270,
+ *                  7373, 9633, 12299, 15137, 16069, 16819, 20995, 25172.  All arithmetic is 32-bit two's-complement wrapping; libjpeg's
+ *                  zero-AC short cuts give the general path's values, so there is no branch;
+ *   J5 upsample  : "fancy" upsampling.  A chroma plane has cw = ceil(W h_c / h_max) by ch = ceil(H v_c / v_max) real samples; edges use
+ *                  those, never the MCU padding.  Horizontal 2:1: out[2i] = (3 p[i] + p[i-1] + 1) >> 2, out[2i+1] = (3 p[i] + p[i+1] +
+ *                  2) >> 2, first = p[0], last = p[cw-1].  2:1 both ways: s = 3 near + far, far the row above for even output rows and
+ *                  the row below for odd ones, first and last row replicated; out[2i] = (3 s[i] + s[i-1] + 8) >> 4, out[2i+1] = (3 s[i]
+ *                  + s[i+1] + 7) >> 4, first = (4 s[0] + 8) >> 4, last = (4 s[cw-1] + 7) >> 4.  A plane of cw <= 2 is replicated in both
+ *                  directions instead (out[x][y] = p[y / 2][x / 2]), as libjpeg-turbo does for planes that narrow.  Cropped to W x H;
+ *   J6 colour    : cb, cr minus 128; r = y + ((91881 cr + 32768) >> 16), g = y + ((-22554 cb - 46802 cr + 32768) >> 16), b = y +
+ *                  ((116130 cb + 32768) >> 16); arithmetic shifts; clamped to 0..255.  A 1-component file writes its sample to all three
+ *                  channels, as cv::imread does;
+ *   J7 order     : flags bit 0: MVS_JPEG_BGR (0) is cv::imread's layout, what mvs_gen_new_views and the match filter take; MVS_JPEG_RGB
+ *                  (1) is what mvs_refine_depth_maps documents;
+ *   J8 batch     : all images of a call have one size W x H (W, H <= 65535 by the format), as the cameras of a sequence do; n <= 65535;
+ *                  else MVS_E_INVALID_ARG before anything is launched.  A rejected stream (J1, J2) is reported first.
+ * What stays absent is an encoder: the proj%d_%d.jpg round trip in front of SIFT and the _depth<i>.jpg previews. */
+#define MVS_JPEG_BGR 0u
+#define MVS_JPEG_RGB 1u
+typedef struct {
+    int32_t w, h, components, h_samp, v_samp, restart_interval, n_segments, sof;   /* h_samp, v_samp: the luma's, as J1 counts them */
+} mvs_jpeg_info_t;
+/* J1, J2 on one stream: host only, no device needed */
+int mvs_jpeg_info(const uint8_t* data, int64_t len, mvs_jpeg_info_t* out);
+/* stream i is data[offsets[i] .. offsets[i+1]); imgs receives n x h x w x 3 bytes (mvs_jpeg_info of a stream gives w and h) */
+int mvs_jpeg_decode(int32_t n, const int64_t* offsets /*n+1, ascending from 0*/, const uint8_t* data, uint32_t flags,
+                    uint8_t* imgs /*n x h x w x 3*/);
+/* the streams stay a host array, the pixels are written in HBM, in the order of hip_stream (may be NULL); returns with the work complete */
+int mvs_jpeg_decode_dev(int32_t n, const int64_t* offsets, const uint8_t* data /*host*/, uint32_t flags, uint8_t* imgs_dev,
+                        void* hip_stream);
 
 /* ------------------------------------------------- surface reconstruction (GeometryRec::RunPoisson) -- */
 /* The one call between the stitch tail and the trim of the model (R/Processor/Processor.cpp:1042-1058): the oriented points of

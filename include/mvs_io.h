@@ -99,11 +99,22 @@ int mvs_processor_render(const char* deform_obj, const char* srt_txt, int32_t n_
  * definition): for each sequence k read seq_dirs[k]/DATA/Render/_depth<i>.raw for its cameras i (mvs_depth_raw_read: what
  * mvs_processor_render wrote), refine all sequences in one call, and write seq_dirs[k]/DATA/Refine/_depth<i>.raw, creating the directory
  * as CreateDir does (a '/' is inserted after seq_dirs[k] when it lacks one).  imgs holds the RGB base images of all cameras back to back
- * in camera order, each h x w x 3 bytes: they are passed in memory because this library has no JPEG decoder, the stance
- * mvs_gen_new_views takes.  params may be NULL (defaults).  A missing or short raster is reported before anything is written.  Not
+ * in camera order, each h x w x 3 bytes, in memory; mvs_processor_refine_depths_files reads them from the sequence directories.  params may be NULL (defaults).  A missing or short raster is reported before anything is written.  Not
  * written: the _depth<i>.jpg previews (an image encode), as in mvs_processor_render. */
 int mvs_processor_refine_depths(int32_t n_seq, const char* const* seq_dirs, const int32_t* cam_off, const mvs_camera* cams,
                                 const uint8_t* imgs, const mvs_depth_refine_params* params);
+
+/* The base images of every sequence from where the reference takes them (R/Processor/Processor.cpp:532): camera i = 0.. of sequence k is
+ * seq_dirs[k]%05d.jpg (a '/' is inserted after seq_dirs[k] when it lacks one).  The files are read on up to 16 host threads and decoded by
+ * mvs_jpeg_decode (rules J1-J8 of include/mvs.h: this library's definition), all sequences that share a size in one call; flags as there
+ * (MVS_JPEG_BGR / MVS_JPEG_RGB).  The decoded size must be the cameras' w x h (MVS_E_INVALID_ARG).  imgs receives all cameras back to
+ * back in camera order, each h x w x 3 bytes.  A missing or rejected file is reported before anything is written to imgs. */
+int mvs_processor_load_images(int32_t n_seq, const char* const* seq_dirs, const int32_t* cam_off, const mvs_camera* cams, uint32_t flags,
+                              uint8_t* imgs /*all cameras back to back, host*/);
+
+/* mvs_processor_refine_depths with the RGB frames read by mvs_processor_load_images from the same seq_dirs. */
+int mvs_processor_refine_depths_files(int32_t n_seq, const char* const* seq_dirs, const int32_t* cam_off, const mvs_camera* cams,
+                                      const mvs_depth_refine_params* params);
 
 /* GeometryRec::RunPointSample on files (R/Processor/Processor.cpp:919-949; the rules: mvs_point_sample, this library's definition):
  * for each sequence k read seq_dirs[k]/DATA/CHECK/_depth<i>.raw for its cameras i (mvs_depth_raw_read: the checked rasters that the file

@@ -145,6 +145,11 @@ int mvs_test_grabcut_trace(int32_t n, int32_t w, int32_t h, const uint8_t* imgs,
  * R [n][9]; U, Vm [n][9] as svd3_dev hands them out (may be NULL).  n == 0 launches nothing. */
 int mvs_test_rotations(int64_t n, const double* a, int32_t rule, double* R, double* U, double* Vm);
 
+/* mvs_jpeg_decode_dev with its parts timed (scripts/bench_jpeg.py): ms [5] receives the milliseconds of the header walk (host), of the
+ * allocation and upload (host clock, synchronised), and of the three launch sets (HIP events): entropy, inverse DCT, pixels. */
+int mvs_test_jpeg_decode_timed(int32_t n, const int64_t* offsets, const uint8_t* data, uint32_t flags, uint8_t* imgs_dev, void* hip_stream,
+                               double* ms);
+
 #ifdef __cplusplus
 }
 #endif

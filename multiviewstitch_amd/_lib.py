@@ -83,6 +83,11 @@ class CDepthRefineParams(C.Structure):
                 ("ssd_win", C.c_int32), ("ref_frm_count", C.c_int32), ("steps", C.c_int32), ("flags", C.c_int32)]
 
 
+class CJpegInfo(C.Structure):
+    """struct mvs_jpeg_info_t."""
+    _fields_ = [(k, C.c_int32) for k in ("w", "h", "components", "h_samp", "v_samp", "restart_interval", "n_segments", "sof")]
+
+
 class CGrabCutParams(C.Structure):
     """struct mvs_grabcut_params."""
     _fields_ = [("hl", C.c_double), ("hr", C.c_double), ("vl", C.c_double), ("vr", C.c_double), ("gamma", C.c_double),
@@ -204,6 +209,9 @@ _SIGS = {
     "mvs_depth_refine_default_params": (None, [_VP]),
     "mvs_refine_depth_maps": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mvs_refine_depth_maps_dev": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "mvs_jpeg_info": (C.c_int, [_VP, _I64, _VP]),
+    "mvs_jpeg_decode": (C.c_int, [_I32, _VP, _VP, _U32, _VP]),
+    "mvs_jpeg_decode_dev": (C.c_int, [_I32, _VP, _VP, _U32, _VP, _VP]),
     "mvs_poisson_default_params": (None, [_VP]),
     "mvs_poisson_reconstruct": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _I64]),
     "mvs_poisson_reconstruct_dev": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _I64, _VP]),
@@ -314,6 +322,8 @@ _SIGS = {
     "mvs_processor_cull_model": (C.c_int, [C.c_char_p, _I32, _VP, _VP, _VP, _VP, _VP, _I32, C.c_char_p, _VP, _VP]),
     "mvs_processor_render": (C.c_int, [C.c_char_p, C.c_char_p, _I32, _VP, _VP, C.c_char_p, _VP, C.c_float, C.c_float, _VP]),
     "mvs_processor_refine_depths": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP]),
+    "mvs_processor_load_images": (C.c_int, [_I32, _VP, _VP, _VP, _U32, _VP]),
+    "mvs_processor_refine_depths_files": (C.c_int, [_I32, _VP, _VP, _VP, _VP]),
     "mvs_processor_point_sample": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mvs_processor_poisson": (C.c_int, [C.c_char_p, _VP, C.c_char_p, _VP, _VP]),
     "mvs_processor_poisson_density": (C.c_int, [C.c_char_p, _VP, _VP, _D, C.c_char_p, _VP, _VP]),
@@ -343,6 +353,7 @@ _SIGS = {
                                                       _VP]),
     "mvs_test_poisson_band_screened_level": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _I64, _VP, _I64, _VP,
                                                        _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "mvs_test_jpeg_decode_timed": (C.c_int, [_I32, _VP, _VP, _U32, _VP, _VP, _VP]),
     "mvs_test_rotations": (C.c_int, [_I64, _VP, _I32, _VP, _VP, _VP]),
 }
 EXPORTS = tuple(_SIGS)
@@ -381,6 +392,7 @@ def check(rc):
 
 CULL_SEQUENCES, CULL_ALL_SEQ = 0, 1          # enum mvs_cull_mode
 STITCH_TRUNCATE = 1                         # MVS_STITCH_TRUNCATE (include/mvs_io.h)
+JPEG_BGR, JPEG_RGB = 0, 1                   # MVS_JPEG_BGR, MVS_JPEG_RGB (include/mvs.h)
 REFINE_SUBSTEP = 1                          # MVS_REFINE_SUBSTEP (include/mvs.h)
 
 

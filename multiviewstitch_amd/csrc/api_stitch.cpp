@@ -2,7 +2,8 @@
 // mvs_mesh_vertex_normals(_dev) (include/mvs.h) and the two file-level steps mvs_processor_stitch_points / _cull_model
 // (include/mvs_io.h); and of Processor::Render (:1140-1192): mvs_render_depth_views(_dev) (include/mvs.h) and the file-level
 // mvs_processor_render (include/mvs_io.h); and the file forms of GeometryRec::RunPointSample (:919-949), mvs_processor_point_sample, and of
-// GeometryRec::RunPoisson (:1042-1058), mvs_processor_poisson.
+// GeometryRec::RunPoisson (:1042-1058), mvs_processor_poisson; and the base images of the sequence directories (:532), mvs_processor_load_images,
+// with the file form of the depth refinement that reads them, mvs_processor_refine_depths_files.
 // The point work is stitch.hip / align.hip / render_views.hip / pointsample.hip / poisson.hip; the host reads and writes the files and builds the
 // small tables.
 #include "engine.h"
@@ -14,7 +15,9 @@
 #include <cstdio>
 #include <cstring>
 #include <sys/stat.h>
+#include <algorithm>
 #include <string>
+#include <thread>
 #include <vector>
 
 namespace {
@@ -316,20 +319,26 @@ int mvs_processor_render(const char* deform_obj, const char* srt_txt, int32_t n_
     return MVS_OK;
 }
 
-int mvs_processor_refine_depths(int32_t n_seq, const char* const* seq_dirs, const int32_t* cam_off, const mvs_camera* cams, const uint8_t* imgs,
-                                const mvs_depth_refine_params* params) {
-    MVS_TRACE();
-    if (n_seq < 1) return bad(__func__, "n_seq must be >= 1");
-    if (!seq_dirs || !cam_off || !cams || !imgs) return bad(__func__, "seq_dirs, cam_off, cams and imgs must not be NULL");
+// the checks the file forms of the depth refinement share
+static int check_seq_dirs(const char* fn, int32_t n_seq, const char* const* seq_dirs, const int32_t* cam_off, const mvs_camera* cams, size_t* px) {
+    if (n_seq < 1) return bad(fn, "n_seq must be >= 1");
+    if (!seq_dirs || !cam_off || !cams) return bad(fn, "seq_dirs, cam_off and cams must not be NULL");
     for (int k = 0; k < n_seq; ++k)
-        if (!seq_dirs[k]) return bad(__func__, "a path of seq_dirs is NULL");
-    int rc = check_offsets(__func__, "cam_off", cam_off, n_seq);
+        if (!seq_dirs[k]) return bad(fn, "a path of seq_dirs is NULL");
+    int rc = check_offsets(fn, "cam_off", cam_off, n_seq);
     if (rc) return rc;
-    size_t floats = 0;
+    *px = 0;
     for (int c = 0; c < cam_off[n_seq]; ++c) {
-        if (cams[c].w <= 0 || cams[c].h <= 0) return bad(__func__, "every camera needs w, h > 0");
-        floats += (size_t)cams[c].w * (size_t)cams[c].h;
+        if (cams[c].w <= 0 || cams[c].h <= 0) return bad(fn, "every camera needs w, h > 0");
+        *px += (size_t)cams[c].w * (size_t)cams[c].h;
     }
+    return MVS_OK;
+}
+
+// DATA/Render -> mvs_refine_depth_maps -> DATA/Refine for checked arguments, under the name fn
+static int refine_depths_body(const char* fn, int32_t n_seq, const char* const* seq_dirs, const int32_t* cam_off, const mvs_camera* cams,
+                              const uint8_t* imgs, const mvs_depth_refine_params* params, size_t floats) {
+    int rc;
     mvs_depth_refine_params prm;
     if (params) prm = *params; else mvs_depth_refine_default_params(&prm);
     std::vector<float> ras(floats ? floats : 1), out(floats ? floats : 1);                        // the rasters of DATA/Render, DepthOptimizer.cpp:28-31
@@ -341,7 +350,7 @@ int mvs_processor_refine_depths(int32_t n_seq, const char* const* seq_dirs, cons
             if ((rc = mvs_depth_raw_read(join(seq_dirs[k], name).c_str(), cams[c].w, cams[c].h, ras.data() + at))) return rc;
             at += (size_t)cams[c].w * (size_t)cams[c].h;
         }
-    if ((rc = refine_depth_maps_host(__func__, n_seq, cam_off, cams, imgs, ras.data(), &prm, out.data(), nullptr, nullptr, nullptr))) return rc;
+    if ((rc = refine_depth_maps_host(fn, n_seq, cam_off, cams, imgs, ras.data(), &prm, out.data(), nullptr, nullptr, nullptr))) return rc;
     std::vector<double> raw;
     at = 0;
     for (int k = 0; k < n_seq; ++k) {                                                             // DATA/Refine, :36-40
@@ -358,6 +367,114 @@ int mvs_processor_refine_depths(int32_t n_seq, const char* const* seq_dirs, cons
         }
     }
     return MVS_OK;
+}
+
+int mvs_processor_refine_depths(int32_t n_seq, const char* const* seq_dirs, const int32_t* cam_off, const mvs_camera* cams, const uint8_t* imgs,
+                                const mvs_depth_refine_params* params) {
+    MVS_TRACE();
+    if (n_seq < 1) return bad(__func__, "n_seq must be >= 1");
+    if (!seq_dirs || !cam_off || !cams || !imgs) return bad(__func__, "seq_dirs, cam_off, cams and imgs must not be NULL");
+    size_t floats = 0;
+    int rc = check_seq_dirs(__func__, n_seq, seq_dirs, cam_off, cams, &floats);
+    if (rc) return rc;
+    return refine_depths_body(__func__, n_seq, seq_dirs, cam_off, cams, imgs, params, floats);
+}
+
+// <seq_dirs[k]>%05d.jpg of every camera into `out` (all cameras back to back), under the name fn: the files read on host threads, then one
+// mvs_jpeg_decode per size; nothing is written to `out` before every file has been read and every stream walked
+static int load_images_body(const char* fn, int32_t n_seq, const char* const* seq_dirs, const int32_t* cam_off, const mvs_camera* cams,
+                            uint32_t flags, uint8_t* out) {
+    const int ncam = cam_off[n_seq];
+    if (ncam == 0) return MVS_OK;
+    std::vector<std::string> path((size_t)ncam), blob((size_t)ncam);
+    std::vector<int> err((size_t)ncam, 0);
+    for (int k = 0; k < n_seq; ++k)
+        for (int c = cam_off[k]; c < cam_off[k + 1]; ++c) {
+            char name[24];
+            std::snprintf(name, sizeof name, "%05d.jpg", c - cam_off[k]);                          // Processor.cpp:532
+            path[(size_t)c] = join(seq_dirs[k], name);
+        }
+    const int nt = (int)std::max(1u, std::min({16u, (unsigned)ncam, std::max(1u, std::thread::hardware_concurrency())}));
+    auto part = [&](int t) {
+        for (int c = t; c < ncam; c += nt) {
+            FILE* f = std::fopen(path[(size_t)c].c_str(), "rb");
+            if (!f) { err[(size_t)c] = errno ? errno : EIO; continue; }
+            char buf[1 << 16];
+            size_t got;
+            while ((got = std::fread(buf, 1, sizeof buf, f)) > 0) blob[(size_t)c].append(buf, got);
+            if (std::ferror(f)) err[(size_t)c] = EIO;
+            std::fclose(f);
+        }
+    };
+    std::vector<std::thread> th;
+    for (int t = 1; t < nt; ++t) th.emplace_back(part, t);
+    part(0);
+    for (auto& x : th) x.join();
+    for (int c = 0; c < ncam; ++c)
+        if (err[(size_t)c]) { mvs_set_error("%s: %s: %s", fn, path[(size_t)c].c_str(), std::strerror(err[(size_t)c])); return MVS_E_IO; }
+    // the cameras by size, in the order of their first camera; pass 0 walks the streams and checks the sizes, pass 1 decodes
+    std::vector<char> done((size_t)ncam, 0);
+    std::vector<int64_t> px0((size_t)ncam + 1, 0);
+    for (int c = 0; c < ncam; ++c) px0[(size_t)c + 1] = px0[(size_t)c] + (int64_t)cams[c].w * cams[c].h;
+    for (int pass = 0; pass < 2; ++pass) {
+        std::fill(done.begin(), done.end(), 0);
+        for (int c0 = 0; c0 < ncam; ++c0) {
+            if (done[(size_t)c0]) continue;
+            std::vector<int> grp;
+            std::vector<int64_t> off(1, 0);
+            std::string data;
+            for (int c = c0; c < ncam; ++c)
+                if (cams[c].w == cams[c0].w && cams[c].h == cams[c0].h) {
+                    done[(size_t)c] = 1;
+                    grp.push_back(c);
+                    data += blob[(size_t)c];
+                    off.push_back((int64_t)data.size());
+                }
+            const size_t npx = (size_t)cams[c0].w * (size_t)cams[c0].h;
+            std::vector<uint8_t> px(pass ? grp.size() * npx * 3 : 0);
+            int32_t w = 0, h = 0;
+            int rc = jpeg_decode_host(fn, (int32_t)grp.size(), off.data(), (const uint8_t*)data.data(), flags, pass ? px.data() : nullptr, &w, &h);
+            if (rc) {                                                                              // the index of a group -> the file
+                const std::string why = mvs_last_error();
+                const size_t at = why.find("image ");
+                if (at != std::string::npos) {
+                    const int i = std::atoi(why.c_str() + at + 6);
+                    if (i >= 0 && i < (int)grp.size()) mvs_set_error("%s (%s)", why.c_str(), path[(size_t)grp[(size_t)i]].c_str());
+                }
+                return rc;
+            }
+            if (w != cams[c0].w || h != cams[c0].h) {
+                mvs_set_error("%s: %s is %d x %d, its camera %d x %d", fn, path[(size_t)c0].c_str(), w, h, cams[c0].w, cams[c0].h);
+                return MVS_E_INVALID_ARG;
+            }
+            for (size_t i = 0; pass && i < grp.size(); ++i) std::memcpy(out + 3 * px0[(size_t)grp[i]], px.data() + i * npx * 3, npx * 3);
+        }
+        if (pass == 0)
+            if (int rc = need_device()) return rc;
+    }
+    return MVS_OK;
+}
+
+int mvs_processor_load_images(int32_t n_seq, const char* const* seq_dirs, const int32_t* cam_off, const mvs_camera* cams, uint32_t flags,
+                              uint8_t* imgs) {
+    MVS_TRACE();
+    size_t px = 0;
+    int rc = check_seq_dirs(__func__, n_seq, seq_dirs, cam_off, cams, &px);
+    if (rc) return rc;
+    if (!imgs) return bad(__func__, "imgs is NULL");
+    if (flags & ~(uint32_t)MVS_JPEG_RGB) return bad(__func__, "unknown flag bits");
+    return load_images_body(__func__, n_seq, seq_dirs, cam_off, cams, flags, imgs);
+}
+
+int mvs_processor_refine_depths_files(int32_t n_seq, const char* const* seq_dirs, const int32_t* cam_off, const mvs_camera* cams,
+                                      const mvs_depth_refine_params* params) {
+    MVS_TRACE();
+    size_t px = 0;
+    int rc = check_seq_dirs(__func__, n_seq, seq_dirs, cam_off, cams, &px);
+    if (rc) return rc;
+    std::vector<uint8_t> imgs(px ? 3 * px : 1);
+    if ((rc = load_images_body(__func__, n_seq, seq_dirs, cam_off, cams, MVS_JPEG_RGB, imgs.data()))) return rc;
+    return refine_depths_body(__func__, n_seq, seq_dirs, cam_off, cams, imgs.data(), params, px);
 }
 
 int mvs_processor_point_sample(int32_t n_seq, const char* const* seq_dirs, const int32_t* cam_off, const mvs_camera* cams,

@@ -30,6 +30,9 @@ int point_sample_vectors(const char* fn, int32_t n_seq, const int32_t* cam_off, 
 // mvs_refine_depth_maps's host form (depth_refine.hip), validating and reporting under the name fn
 int refine_depth_maps_host(const char* fn, int32_t n_seq, const int32_t* cam_off, const mvs_camera* cams, const uint8_t* imgs, const float* depths,
                            const mvs_depth_refine_params* p, float* out, int8_t* k_out, int32_t* sum_out, uint8_t* cnt_out);
+// mvs_jpeg_decode's host form (jpeg.hip) under the name fn; w / h (may be NULL) receive the size; imgs == NULL: the header walk and the
+// checks only, no device needed
+int jpeg_decode_host(const char* fn, int32_t n, const int64_t* offsets, const uint8_t* data, uint32_t flags, uint8_t* imgs, int32_t* w, int32_t* h);
 // One call of the Poisson stage (poisson.hip), whichever entry made it: `rules` says which of mvs_poisson_reconstruct (PN_PLAIN),
 // _density (PN_DENSITY: dp and dinfo) and _screened (PN_SCREENED: sp and sinfo too) it is; the parts it does not have are NULL.  The
 // points are the entry's own, host or device.

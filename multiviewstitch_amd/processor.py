@@ -1089,7 +1089,7 @@ def RefineAllDepthMaps(cameras, imgs, depths, params: L.CDepthRefineParams | Non
 def RefineDepthFiles(seq_dirs, cameras, imgs, params: L.CDepthRefineParams | None = None) -> None:
     """``mvs_processor_refine_depths``: sequence k's rendered rasters ``seq_dirs[k]``/DATA/Render/_depth<i>.raw (what ``Render`` wrote) ->
     ``seq_dirs[k]``/DATA/Refine/_depth<i>.raw.  ``cameras[k]`` lists sequence k's cameras, ``imgs[k]`` is its RGB base images
-    [frames, h, w, 3] uint8 (the library has no JPEG decoder: the caller decodes them)."""
+    [frames, h, w, 3] uint8 in memory (``RefineDepthFilesFromJpeg`` reads them from the sequence directories)."""
     n = len(cameras)
     if len(seq_dirs) != n or len(imgs) != n:
         raise L.MvsError(-1, f"{len(seq_dirs)} sequence dirs and {len(imgs)} image stacks for {n} sequences")
@@ -1102,3 +1102,93 @@ def RefineDepthFiles(seq_dirs, cameras, imgs, params: L.CDepthRefineParams | Non
     flat, iptr = _flat_stack(imgs, n, False, "uint8", "imgs")
     prm = params if params is not None else depth_refine_params()
     L.check(L.lib().mvs_processor_refine_depths(n, dirs, L.ptr(off), cams, iptr, C.byref(prm)))
+
+
+# ------------------------------------------------------------------ base images ----
+def _jpeg_order(order):
+    if order not in ("BGR", "RGB"):
+        raise L.MvsError(-1, "order must be 'BGR' or 'RGB'")
+    return L.JPEG_RGB if order == "RGB" else L.JPEG_BGR
+
+
+def JpegInfo(data) -> dict:
+    """``mvs_jpeg_info``: the header walk of one JPEG stream (rules J1, J2 of include/mvs.h; host code, no device needed) ->
+    dict(w, h, components, h_samp, v_samp, restart_interval, n_segments, sof).  A stream the decoder rejects raises MVS_E_IO naming the
+    feature."""
+    buf = np.frombuffer(bytes(data) or b"\0", np.uint8)
+    info = L.CJpegInfo()
+    L.check(L.lib().mvs_jpeg_info(L.ptr(buf), len(bytes(data)), C.byref(info)))
+    return {k: int(getattr(info, k)) for k, _ in L.CJpegInfo._fields_}
+
+
+def DecodeJpegs(datas, order: str = "BGR", device=None, stream: int | None = None):
+    """``mvs_jpeg_decode``: the baseline JPEG streams ``datas`` (bytes each, all of one size) -> [n, h, w, 3] uint8, every image through
+    each kernel in one launch (rules J1-J8 of include/mvs.h: this library's definition, pinned byte for byte against libjpeg-turbo's
+    default decompressor).  ``order`` "BGR" is ``cv::imread``'s layout (what ``GenNewViews`` and the match filter take), "RGB" what
+    ``RefineAllDepthMaps`` documents.  With ``device`` (a torch device) the result is a tensor there and the pixels never visit the host
+    (``mvs_jpeg_decode_dev`` in the order of ``stream``, a HIP stream handle; None: the legacy default stream); otherwise a numpy
+    array."""
+    flags = _jpeg_order(order)
+    datas = [bytes(d) for d in datas]
+    n = len(datas)
+    if n < 1:
+        raise L.MvsError(-1, "need at least one stream")
+    off = np.zeros(n + 1, np.int64)
+    off[1:] = np.cumsum([len(d) for d in datas])
+    blob = np.frombuffer(b"".join(datas) or b"\0", np.uint8)
+    info = JpegInfo(datas[0])
+    shape = (n, info["h"], info["w"], 3)
+    if device is None:
+        out = np.empty(shape, np.uint8)
+        L.check(L.lib().mvs_jpeg_decode(n, L.ptr(off), L.ptr(blob), flags, L.ptr(out)))
+        return out
+    import torch
+    order_ctx = torch.cuda.stream(torch.cuda.ExternalStream(int(stream))) if stream else contextlib.nullcontext()
+    with order_ctx:
+        out = torch.empty(shape, dtype=torch.uint8, device=device)
+        L.check(L.lib().mvs_jpeg_decode_dev(n, L.ptr(off), L.ptr(blob), flags, L.ptr(out), L.ptr(stream)))
+    return out
+
+
+def LoadImages(seq_dirs, cameras, order: str = "BGR") -> list:
+    """``mvs_processor_load_images``: camera i of sequence k from ``seq_dirs[k]``%05d.jpg (R/Processor/Processor.cpp:532) -> per sequence
+    [frames, h, w, 3] uint8; the files are read on host threads and all sequences of one size are decoded in one call."""
+    n = len(cameras)
+    if len(seq_dirs) != n:
+        raise L.MvsError(-1, f"{len(seq_dirs)} sequence dirs for {n} sequences")
+    off, cams = L.seq_cams(cameras)
+    dirs = (C.c_char_p * max(1, n))(*[os.fsencode(d) for d in seq_dirs])
+    sizes = [sum(int(c.w) * int(c.h) * 3 for c in seq) for seq in cameras]
+    flat = np.zeros(max(1, sum(sizes)), np.uint8)
+    L.check(L.lib().mvs_processor_load_images(n, dirs, L.ptr(off), cams, _jpeg_order(order), L.ptr(flat)))
+    res, at = [], 0
+    for k, seq in enumerate(cameras):
+        if len(seq) and any((int(c.w), int(c.h)) != (int(seq[0].w), int(seq[0].h)) for c in seq):
+            raise L.MvsError(-1, f"the cameras of sequence {k} differ in size")
+        shape = (len(seq), int(seq[0].h), int(seq[0].w), 3) if len(seq) else (0, 0, 0, 3)
+        res.append(flat[at:at + sizes[k]].reshape(shape))
+        at += sizes[k]
+    return res
+
+
+def LoadSequenceFiles(seq_dir, cameras, view_count: int, axis: int, rot_angle: float, **kw) -> dict:
+    """``LoadSequenceModels`` from a sequence directory: the frames ``seq_dir``%05d.jpg (``LoadImages``, BGR as ``cv::imread``) and the
+    checked rasters ``seq_dir``/DATA/CHECK/_depth<i>.raw (``mvs_depth_raw_read``) -> the ``sequences[k]`` entry of
+    ``CalcSimilarityTransformationSeq``.  ``kw`` goes to ``LoadSequenceModels`` (sift, min_dsp, max_dsp, masks, segment)."""
+    (imgs,) = LoadImages([seq_dir], [cameras], "BGR")
+    depths = np.empty((len(cameras),) + tuple(imgs.shape[1:3]), np.float32)
+    for i, cam in enumerate(cameras):
+        path = os.path.join(os.fspath(seq_dir), "DATA", "CHECK", f"_depth{i}.raw")
+        L.check(L.lib().mvs_depth_raw_read(os.fsencode(path), int(cam.w), int(cam.h), L.ptr(depths[i])))
+    return LoadSequenceModels(cameras, imgs, depths, view_count, axis, rot_angle, **kw)
+
+
+def RefineDepthFilesFromJpeg(seq_dirs, cameras, params: L.CDepthRefineParams | None = None) -> None:
+    """``mvs_processor_refine_depths_files``: ``RefineDepthFiles`` with the RGB frames read from ``seq_dirs[k]``%05d.jpg."""
+    n = len(cameras)
+    if len(seq_dirs) != n:
+        raise L.MvsError(-1, f"{len(seq_dirs)} sequence dirs for {n} sequences")
+    off, cams = L.seq_cams(cameras)
+    dirs = (C.c_char_p * max(1, n))(*[os.fsencode(d) for d in seq_dirs])
+    prm = params if params is not None else depth_refine_params()
+    L.check(L.lib().mvs_processor_refine_depths_files(n, dirs, L.ptr(off), cams, C.byref(prm)))

@@ -324,8 +324,9 @@ int mvs_sequence_pair_srt(int32_t n1, int32_t n2, const mvs_camera* cams1, const
  *   colour      : the four branches of :179-211 (both equal, u11 == u22, v11 == v22, bilinear) with the reference's expressions and
  *                 summation order, (uchar) of the double; tex = v11*w + u11 for the both-equal branch, else int(vf+0.5)*w + int(uf+0.5).
  * Deviations: a destination pixel nothing paints is uninitialised cv::Mat memory in the reference; here it is (0,0,0), tex = -1.  The
- * reference writes the views as JPEG and SIFT reads them back; this library has a JPEG decoder (mvs_jpeg_decode) and no encoder: the
- * entry returns the rasters, and what SIFT sees after the JPEG round trip is not pinned.
+ * reference writes the views as JPEG and SIFT reads them back: the entry returns the rasters, mvs_jpeg_roundtrip turns them into the
+ * pixels that come back from the file (rules E1-E9 below, pinned against libjpeg-turbo, not against the reference's libjpeg), and
+ * mvs_processor_save_views (mvs_io.h) writes the files.
  * MVS_E_INVALID_ARG: view_count < 1, axis outside 0..2, n_frames < 1, cameras of differing sizes, a NULL pointer, w or h > 65535. */
 int mvs_gen_new_views(int32_t n_frames, const mvs_camera* cams, const uint8_t* imgs /*n x h x w x 3*/, int32_t view_count, int32_t axis,
                       double rot_angle, uint8_t* views /*n x views x h x w x 3*/, int32_t* tex /*n x views x w*h*/);
@@ -762,7 +763,7 @@ int mvs_refine_depth_maps_dev(int32_t n_seq, const int32_t* cam_off, const mvs_c
  *                  (1) is what mvs_refine_depth_maps documents;
  *   J8 batch     : all images of a call have one size W x H (W, H <= 65535 by the format), as the cameras of a sequence do; n <= 65535;
  *                  else MVS_E_INVALID_ARG before anything is launched.  A rejected stream (J1, J2) is reported first.
- * What stays absent is an encoder: the proj%d_%d.jpg round trip in front of SIFT and the _depth<i>.jpg previews. */
+ * The encoder (mvs_jpeg_encode, rules E1-E9) follows the decoder's entries below. */
 #define MVS_JPEG_BGR 0u
 #define MVS_JPEG_RGB 1u
 typedef struct {
@@ -776,6 +777,84 @@ int mvs_jpeg_decode(int32_t n, const int64_t* offsets /*n+1, ascending from 0*/,
 /* the streams stay a host array, the pixels are written in HBM, in the order of hip_stream (may be NULL); returns with the work complete */
 int mvs_jpeg_decode_dev(int32_t n, const int64_t* offsets, const uint8_t* data /*host*/, uint32_t flags, uint8_t* imgs_dev,
                         void* hip_stream);
+
+/* The batched baseline JPEG encoder: cv::imwrite of the generated views (R/Image3D/Image3D.cpp:218-219) and of the depth previews
+ * (R/Common/Utils.h:189-217), all images of a call through each kernel in one launch.  The rules below are this library's definition.
+ * They are pinned byte for byte against the default compressor of libjpeg-turbo (API 6.2, as Pillow 12.2.0 runs it:
+ * Image.fromarray(a).save(f, "JPEG", quality=q, subsampling=s, restart_marker_blocks=r), optimize off, no dpi / exif / icc) on the inputs
+ * of tests/golden/jpeg_enc.  They are NOT VERIFIED against the libjpeg that OpenCV 3.0 bundles in the reference's build.
+ *   E1 input     : n images of one size W x H (1 .. 65535 each, n <= 65535), uint8: [n, h, w, 3] in B G R (MVS_JPEG_BGR) or R G B
+ *                  (MVS_JPEG_RGB) order, or [n, h, w] grey (MVS_JPEG_GREY: one component).  mvs_jpeg_encode_params: quality 1 .. 100
+ *                  (default 95, cv::imwrite's); sampling 444 / 422 / 420 (default 420: what jpeg_set_defaults leaves and cv::imwrite does
+ *                  not change; checked but not used for grey); restart_interval in MCUs, 0 .. 65535 (default 0, as OpenCV writes) or
+ *                  MVS_JPEG_RESTART_ROW: one MCU row per interval; reserved = 0 is not checked.  params == NULL: the defaults.  Anything
+ *                  else is MVS_E_INVALID_ARG before a launch and before a device is looked for;
+ *   E2 colour    : int32, arithmetic shift: Y = (19595 R + 38470 G + 7471 B + 32768) >> 16, Cb = (-11059 R - 21709 G + 32768 B + 8388608 +
+ *                  32767) >> 16, Cr = (32768 R - 27439 G - 5329 B + 8388608 + 32767) >> 16;
+ *   E3 planes    : in this order: a full-resolution plane is extended to the right to whole MCUs by repeating its last column, and
+ *                  downward only to a multiple of v_max rows by repeating its last row.  Then it is downsampled: 2:1 horizontally
+ *                  (a + b + bias) >> 1 with bias 0, 1, 0, 1, ... by output column; 2:1 both ways (a + b + c + d + bias) >> 2 with bias 1,
+ *                  2, 1, 2, ...; 1:1 a copy.  Then every downsampled plane, luma included, is extended downward to whole MCUs by repeating
+ *                  its last downsampled row.  (Repeating input rows to the MCU height instead gives other chroma bytes whenever H mod 16
+ *                  is in 1 .. 8 at 4:2:0.);
+ *   E4 FDCT      : libjpeg's jfdctint (CONST_BITS 13, PASS1_BITS 2) on samples minus 128, the forward twin of J4 with the same twelve
+ *                  constants.  descale(x, n) = (x + (1 << (n - 1))) >> n.  On eight values d0 .. d7: tmp0 = d0 + d7, tmp7 = d0 - d7, tmp1
+ *                  = d1 + d6, tmp6 = d1 - d6, tmp2 = d2 + d5, tmp5 = d2 - d5, tmp3 = d3 + d4, tmp4 = d3 - d4; tmp10 = tmp0 + tmp3, tmp13 =
+ *                  tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2; z1 = (tmp12 + tmp13) 4433; out2 = descale(z1 + 6270 tmp13, s),
+ *                  out6 = descale(z1 - 15137 tmp12, s); z1 = tmp4 + tmp7, z2 = tmp5 + tmp6, z3 = tmp4 + tmp6, z4 = tmp5 + tmp7, z5 = (z3 +
+ *                  z4) 9633; tmp4 *= 2446, tmp5 *= 16819, tmp6 *= 25172, tmp7 *= 12299; z1 *= -7373, z2 *= -20995, z3 = -16069 z3 + z5,
+ *                  z4 = -3196 z4 + z5; out7 = descale(tmp4 + z1 + z3, s), out5 = descale(tmp5 + z2 + z4, s), out3 = descale(tmp6 + z2 +
+ *                  z3, s), out1 = descale(tmp7 + z1 + z4, s).  Rows first: out0, out4 = (tmp10 +- tmp11) << 2 and s = 11; then columns:
+ *                  out0, out4 = descale(tmp10 +- tmp11, 2) and s = 15.  The result is 8 times the DCT; int32 cannot overflow on 8-bit
+ *                  input;
+ *   E5 quantise  : base tables T.81 K.1 (luma) and K.2 (chroma); scale = 5000 / q for q < 50 (integer division), else 200 - 2 q; entry =
+ *                  clamp((base * scale + 50) / 100, 1, 255).  A coefficient c with entry e becomes sign(c) * ((|c| + 4 e) / (8 e)),
+ *                  integer division: half away from zero;
+ *   E6 blocks    : one interleaved scan, MCUs in row-major order; inside an MCU luma's v x h blocks row-major, then Cb, then Cr.  A
+ *                  component has ceil(cw / 8) x ceil(ch / 8) real blocks, cw = ceil(W h_c / h_max), ch = ceil(H v_c / v_max).  An MCU
+ *                  position outside them is a dummy block: it codes as DC difference 0 followed by EOB and leaves the predictor
+ *                  unchanged;
+ *   E7 entropy   : the four tables of T.81 K.3-K.6.  DC: the size category of the difference and its bits, d - 1 for a negative d.  AC,
+ *                  in zigzag order: run / size symbols, ZRL (F0) for every 16 zeros in front of a non-zero coefficient, EOB (00) when the
+ *                  block ends in zeros.  Bits go MSB first; a produced FF byte is followed by 00.  At the end of every restart interval
+ *                  and of the scan the last byte is filled with 1 bits; then FF D0+k follows, k counting the intervals mod 8, and the
+ *                  predictors return to 0;
+ *   E8 stream    : FF D8; APP0 FF E0 00 10 'JFIF' 00 01 01 00 00 01 00 01 00 00; one DQT segment per table (8-bit entries in zigzag
+ *                  order: table 0, and table 1 unless grey); SOF0 (precision 8, H, W, ids 1 2 3, sampling bytes, tables 0 1 1); DHT as
+ *                  separate segments in the order DC0, AC0, DC1, AC1 (grey: DC0, AC0); DRI only when the interval is above 0; SOS
+ *                  (table selectors 00 11 11, then 00 3F 00); the scan; FF D9.  Nothing else;
+ *   E9 batch     : offsets[n + 1] is always written; a total above capacity is MVS_E_INVALID_ARG after that (the rule of
+ *                  mvs_point_sample: the caller can size the output and call again).  mvs_jpeg_encode_bound is an upper bound of one
+ *                  stream.  Stream positions come from scans, never from an atomic counter: two runs give the same bytes. */
+#define MVS_JPEG_GREY 2u
+#define MVS_JPEG_RESTART_ROW 65536
+typedef struct mvs_jpeg_encode_params {   /* 16 bytes */
+    int32_t quality, sampling, restart_interval, reserved;
+} mvs_jpeg_encode_params;
+void mvs_jpeg_encode_default_params(mvs_jpeg_encode_params* p);
+/* bytes that hold any stream of E1-E8 for one w x h image with these flags and params (NULL: the defaults): 640 for the header, then
+ * every scan block at 23 + 63 * 26 bits, every interval's last byte, all of it doubled as if every byte were an FF, and two bytes of
+ * marker per interval.  Not tight.  A negative value is the error code (MVS_E_INVALID_ARG).  Host code, no device needed */
+int64_t mvs_jpeg_encode_bound(int32_t w, int32_t h, uint32_t flags, const mvs_jpeg_encode_params* p);
+/* image i's stream is data[offsets[i] .. offsets[i+1]); capacity: the bytes data can take */
+int mvs_jpeg_encode(int32_t n, int32_t w, int32_t h, const uint8_t* imgs, uint32_t flags, const mvs_jpeg_encode_params* p,
+                    int64_t* offsets /*n+1*/, uint8_t* data, int64_t capacity);
+/* pixels and streams in HBM, offsets a host array; in the order of hip_stream (may be NULL); returns with the work complete */
+int mvs_jpeg_encode_dev(int32_t n, int32_t w, int32_t h, const uint8_t* imgs_dev, uint32_t flags, const mvs_jpeg_encode_params* p,
+                        int64_t* offsets /*n+1, host*/, uint8_t* data_dev, int64_t capacity, void* hip_stream);
+/* The pixels mvs_jpeg_decode returns (same order flag; n x h x w x 3, a grey input in all three channels) for mvs_jpeg_encode of the
+ * input, without producing a stream: entropy coding is lossless, so the call runs E2-E5 and then J4-J7 on those coefficients.  What
+ * SIFT sees after proj%d_%d.jpg. */
+int mvs_jpeg_roundtrip(int32_t n, int32_t w, int32_t h, const uint8_t* imgs, uint32_t flags, const mvs_jpeg_encode_params* p,
+                       uint8_t* out /*n x h x w x 3*/);
+int mvs_jpeg_roundtrip_dev(int32_t n, int32_t w, int32_t h, const uint8_t* imgs_dev, uint32_t flags, const mvs_jpeg_encode_params* p,
+                           uint8_t* out_dev, void* hip_stream);
+/* RenderDepthMap's grey image (R/Common/Utils.h:189-217) for n rasters of w x h floats: per raster d_min / d_max over the valid values
+ * (d >= 0 and finite: an order-free min / max; NaN is not >= 0; +inf is left out here because the reference's expression is undefined
+ * on it); a valid pixel is (uint8)(255 * ((double)d - d_min) / (d_max - d_min)), truncating; 255 where the pixel is not valid; 0 for
+ * every valid pixel when d_max == d_min (undefined in the reference: a division by zero); a raster without a valid pixel is all 255. */
+int mvs_depth_preview(int32_t n, int32_t w, int32_t h, const float* depths, uint8_t* out /*n x h x w*/);
+int mvs_depth_preview_dev(int32_t n, int32_t w, int32_t h, const float* depths_dev, uint8_t* out_dev, void* hip_stream);
 
 /* ------------------------------------------------- surface reconstruction (GeometryRec::RunPoisson) -- */
 /* The one call between the stitch tail and the trim of the model (R/Processor/Processor.cpp:1042-1058): the oriented points of

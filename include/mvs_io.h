@@ -100,7 +100,7 @@ int mvs_processor_render(const char* deform_obj, const char* srt_txt, int32_t n_
  * mvs_processor_render wrote), refine all sequences in one call, and write seq_dirs[k]/DATA/Refine/_depth<i>.raw, creating the directory
  * as CreateDir does (a '/' is inserted after seq_dirs[k] when it lacks one).  imgs holds the RGB base images of all cameras back to back
  * in camera order, each h x w x 3 bytes, in memory; mvs_processor_refine_depths_files reads them from the sequence directories.  params may be NULL (defaults).  A missing or short raster is reported before anything is written.  Not
- * written: the _depth<i>.jpg previews (an image encode), as in mvs_processor_render. */
+ * written: the _depth<i>.jpg previews; mvs_processor_depth_previews writes them. */
 int mvs_processor_refine_depths(int32_t n_seq, const char* const* seq_dirs, const int32_t* cam_off, const mvs_camera* cams,
                                 const uint8_t* imgs, const mvs_depth_refine_params* params);
 
@@ -115,6 +115,20 @@ int mvs_processor_load_images(int32_t n_seq, const char* const* seq_dirs, const 
 /* mvs_processor_refine_depths with the RGB frames read by mvs_processor_load_images from the same seq_dirs. */
 int mvs_processor_refine_depths_files(int32_t n_seq, const char* const* seq_dirs, const int32_t* cam_off, const mvs_camera* cams,
                                       const mvs_depth_refine_params* params);
+
+/* cv::imwrite of the generated views (R/Image3D/Image3D.cpp:218-219): view j of frame i of `views` (what mvs_gen_new_views returned:
+ * n_frames x view_count x h x w x 3 bytes, host; flags MVS_JPEG_BGR or MVS_JPEG_RGB say their order) goes to <seq_dir>Views/proj<i>_<j>.jpg
+ * (a '/' is inserted after seq_dir when it lacks one; the directory is created).  All views are encoded in one mvs_jpeg_encode (rules
+ * E1-E9 of include/mvs.h: this library's definition; params NULL: quality 95, 4:2:0, as cv::imwrite), the files written on up to 16 host
+ * threads.  Nothing is written when the encode fails. */
+int mvs_processor_save_views(const char* seq_dir, int32_t n_frames, int32_t view_count, int32_t w, int32_t h, const uint8_t* views, uint32_t flags,
+                             const mvs_jpeg_encode_params* params);
+
+/* RenderDepthMap on files (R/Common/Utils.h:189-217; call sites Processor.cpp:60, Model2Depth.cpp:146, DepthOptimizer.cpp:33): read
+ * <seq_dir>DATA/<sub>/_depth<i>.raw for i = 0 .. n - 1 (mvs_depth_raw_read; sub is "CHECK", "Render" or "Refine"), make the grey images
+ * (mvs_depth_preview), encode them in one mvs_jpeg_encode (MVS_JPEG_GREY; params NULL: the defaults) and write _depth<i>.jpg beside each
+ * raster.  A missing or short raster is reported before anything is written. */
+int mvs_processor_depth_previews(const char* seq_dir, const char* sub, int32_t n, int32_t w, int32_t h, const mvs_jpeg_encode_params* params);
 
 /* GeometryRec::RunPointSample on files (R/Processor/Processor.cpp:919-949; the rules: mvs_point_sample, this library's definition):
  * for each sequence k read seq_dirs[k]/DATA/CHECK/_depth<i>.raw for its cameras i (mvs_depth_raw_read: the checked rasters that the file

@@ -150,6 +150,12 @@ int mvs_test_rotations(int64_t n, const double* a, int32_t rule, double* R, doub
 int mvs_test_jpeg_decode_timed(int32_t n, const int64_t* offsets, const uint8_t* data, uint32_t flags, uint8_t* imgs_dev, void* hip_stream,
                                double* ms);
 
+/* mvs_jpeg_encode_dev with its parts timed (scripts/bench_jpeg_encode.py): ms [4] receives the milliseconds of the plan and the header
+ * (host) and of the three launch sets (HIP events; the host reads two totals in between and those waits are inside): transform, entropy
+ * up to the unstuffed bytes, stuffing and headers. */
+int mvs_test_jpeg_encode_timed(int32_t n, int32_t w, int32_t h, const uint8_t* imgs_dev, uint32_t flags, const mvs_jpeg_encode_params* p,
+                               int64_t* offsets, uint8_t* data_dev, int64_t capacity, void* hip_stream, double* ms);
+
 #ifdef __cplusplus
 }
 #endif

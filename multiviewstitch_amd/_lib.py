@@ -88,6 +88,11 @@ class CJpegInfo(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("w", "h", "components", "h_samp", "v_samp", "restart_interval", "n_segments", "sof")]
 
 
+class CJpegEncodeParams(C.Structure):
+    """struct mvs_jpeg_encode_params."""
+    _fields_ = [(k, C.c_int32) for k in ("quality", "sampling", "restart_interval", "reserved")]
+
+
 class CGrabCutParams(C.Structure):
     """struct mvs_grabcut_params."""
     _fields_ = [("hl", C.c_double), ("hr", C.c_double), ("vl", C.c_double), ("vr", C.c_double), ("gamma", C.c_double),
@@ -314,6 +319,16 @@ _SIGS = {
     "mvs_npts_write": (C.c_int, [C.c_char_p, _I64, _VP, _VP]),
     "mvs_srt_txt_read": (C.c_int, [C.c_char_p, _I64, _VP, _VP, _VP]),
     "mvs_srt_txt_write": (C.c_int, [C.c_char_p, _I64, _VP, _VP, _VP]),
+    "mvs_jpeg_encode_default_params": (None, [_VP]),
+    "mvs_jpeg_encode_bound": (C.c_int64, [_I32, _I32, _U32, _VP]),
+    "mvs_jpeg_encode": (C.c_int, [_I32, _I32, _I32, _VP, _U32, _VP, _VP, _VP, _I64]),
+    "mvs_jpeg_encode_dev": (C.c_int, [_I32, _I32, _I32, _VP, _U32, _VP, _VP, _VP, _I64, _VP]),
+    "mvs_jpeg_roundtrip": (C.c_int, [_I32, _I32, _I32, _VP, _U32, _VP, _VP]),
+    "mvs_jpeg_roundtrip_dev": (C.c_int, [_I32, _I32, _I32, _VP, _U32, _VP, _VP, _VP]),
+    "mvs_depth_preview": (C.c_int, [_I32, _I32, _I32, _VP, _VP]),
+    "mvs_depth_preview_dev": (C.c_int, [_I32, _I32, _I32, _VP, _VP, _VP]),
+    "mvs_processor_save_views": (C.c_int, [C.c_char_p, _I32, _I32, _I32, _I32, _VP, _U32, _VP]),
+    "mvs_processor_depth_previews": (C.c_int, [C.c_char_p, C.c_char_p, _I32, _I32, _I32, _VP]),
     "mvs_depth_raw_read": (C.c_int, [C.c_char_p, _I32, _I32, _VP]),
     "mvs_depth_raw_write": (C.c_int, [C.c_char_p, _I64, _VP]),
     "mvs_parts_read": (C.c_int, [C.c_char_p, _I64, _VP]),
@@ -354,6 +369,7 @@ _SIGS = {
     "mvs_test_poisson_band_screened_level": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _I64, _VP, _I64, _VP,
                                                        _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mvs_test_jpeg_decode_timed": (C.c_int, [_I32, _VP, _VP, _U32, _VP, _VP, _VP]),
+    "mvs_test_jpeg_encode_timed": (C.c_int, [_I32, _I32, _I32, _VP, _U32, _VP, _VP, _VP, _I64, _VP, _VP]),
     "mvs_test_rotations": (C.c_int, [_I64, _VP, _I32, _VP, _VP, _VP]),
 }
 EXPORTS = tuple(_SIGS)
@@ -393,6 +409,7 @@ def check(rc):
 CULL_SEQUENCES, CULL_ALL_SEQ = 0, 1          # enum mvs_cull_mode
 STITCH_TRUNCATE = 1                         # MVS_STITCH_TRUNCATE (include/mvs_io.h)
 JPEG_BGR, JPEG_RGB = 0, 1                   # MVS_JPEG_BGR, MVS_JPEG_RGB (include/mvs.h)
+JPEG_GREY, JPEG_RESTART_ROW = 2, 65536      # MVS_JPEG_GREY, MVS_JPEG_RESTART_ROW
 REFINE_SUBSTEP = 1                          # MVS_REFINE_SUBSTEP (include/mvs.h)
 
 

@@ -477,6 +477,76 @@ int mvs_processor_refine_depths_files(int32_t n_seq, const char* const* seq_dirs
     return refine_depths_body(__func__, n_seq, seq_dirs, cam_off, cams, imgs.data(), params, px);
 }
 
+// stream i = data[off[i] .. off[i + 1]) to path[i], on up to 16 host threads; the first file that fails is reported
+static int write_streams(const char* fn, const std::vector<std::string>& path, const int64_t* off, const uint8_t* data) {
+    const int n = (int)path.size();
+    std::vector<int> err((size_t)n, 0);
+    const int nt = (int)std::max(1u, std::min({16u, (unsigned)n, std::max(1u, std::thread::hardware_concurrency())}));
+    auto part = [&](int t) {
+        for (int i = t; i < n; i += nt) {
+            FILE* f = std::fopen(path[(size_t)i].c_str(), "wb");
+            if (!f) { err[(size_t)i] = errno ? errno : EIO; continue; }
+            const size_t len = (size_t)(off[i + 1] - off[i]);
+            if (std::fwrite(data + off[i], 1, len, f) != len) err[(size_t)i] = EIO;
+            if (std::fclose(f)) err[(size_t)i] = EIO;
+        }
+    };
+    std::vector<std::thread> th;
+    for (int t = 1; t < nt; ++t) th.emplace_back(part, t);
+    part(0);
+    for (auto& x : th) x.join();
+    for (int i = 0; i < n; ++i)
+        if (err[(size_t)i]) { mvs_set_error("%s: %s: %s", fn, path[(size_t)i].c_str(), std::strerror(err[(size_t)i])); return MVS_E_IO; }
+    return MVS_OK;
+}
+
+int mvs_processor_save_views(const char* seq_dir, int32_t n_frames, int32_t view_count, int32_t w, int32_t h, const uint8_t* views, uint32_t flags,
+                             const mvs_jpeg_encode_params* params) {
+    MVS_TRACE();
+    if (!seq_dir || !views) return bad(__func__, "seq_dir or views is NULL");
+    if (n_frames < 1 || view_count < 1 || (int64_t)n_frames * view_count > 65535) return bad(__func__, "need n_frames, view_count >= 1 and at most 65535 views");
+    if (flags & ~(uint32_t)MVS_JPEG_RGB) return bad(__func__, "unknown flag bits");
+    const int n = n_frames * view_count;
+    std::vector<int64_t> off((size_t)n + 1);
+    std::vector<uint8_t> data;
+    int rc = jpeg_encode_host(__func__, n, w, h, views, flags, params, off.data(), &data);
+    if (rc) return rc;
+    const std::string dir = join(seq_dir, "Views/");
+    if ((rc = make_dirs(dir))) return rc;
+    std::vector<std::string> path;
+    for (int i = 0; i < n_frames; ++i)
+        for (int j = 0; j < view_count; ++j) {
+            char name[48];
+            std::snprintf(name, sizeof name, "proj%d_%d.jpg", i, j);                               // Image3D.cpp:218
+            path.push_back(dir + name);
+        }
+    return write_streams(__func__, path, off.data(), data.data());
+}
+
+int mvs_processor_depth_previews(const char* seq_dir, const char* sub, int32_t n, int32_t w, int32_t h, const mvs_jpeg_encode_params* params) {
+    MVS_TRACE();
+    if (!seq_dir || !sub) return bad(__func__, "seq_dir or sub is NULL");
+    if (std::strcmp(sub, "CHECK") && std::strcmp(sub, "Render") && std::strcmp(sub, "Refine")) return bad(__func__, "sub must be CHECK, Render or Refine");
+    if (n < 1 || n > 65535) return bad(__func__, "need n in 1 .. 65535");
+    if (w < 1 || h < 1 || w > 65535 || h > 65535) return bad(__func__, "w and h must be in 1 .. 65535");
+    const size_t npx = (size_t)w * (size_t)h;
+    const std::string dir = join(seq_dir, (std::string("DATA/") + sub + "/").c_str());
+    std::vector<float> ras((size_t)n * npx);
+    std::vector<std::string> path;
+    int rc;
+    for (int i = 0; i < n; ++i) {
+        char name[32];
+        std::snprintf(name, sizeof name, "_depth%d", i);
+        if ((rc = mvs_depth_raw_read((dir + name + ".raw").c_str(), w, h, ras.data() + (size_t)i * npx))) return rc;
+        path.push_back(dir + name + ".jpg");
+    }
+    std::vector<uint8_t> grey((size_t)n * npx), data;
+    std::vector<int64_t> off((size_t)n + 1);
+    if ((rc = depth_preview_host(__func__, n, w, h, ras.data(), grey.data())) ||
+        (rc = jpeg_encode_host(__func__, n, w, h, grey.data(), MVS_JPEG_GREY, params, off.data(), &data))) return rc;
+    return write_streams(__func__, path, off.data(), data.data());
+}
+
 int mvs_processor_point_sample(int32_t n_seq, const char* const* seq_dirs, const int32_t* cam_off, const mvs_camera* cams,
                                const mvs_point_sample_params* params, const char* const* npts_paths, int64_t* n_points) {
     MVS_TRACE();

@@ -281,6 +281,31 @@ int jpeg_decode_host(const char* fn, int32_t n, const int64_t* offsets, const ui
     return down(imgs, dout, nb);
 }
 
+// the dequantise / IDCT launch and the pixel launch on coefficient blocks that are in HBM already (mvs_jpeg_roundtrip, jpeg_enc.hip): n
+// images of layout L (blocks and planes from 0), image i's blocks at i * n_coef.  Synchronises s
+int jpeg_coef_to_pixels_dev(int32_t n, const JpegLayout& L, int64_t n_coef, const uint16_t* q_luma, const uint16_t* q_chroma, const int16_t* coef_dev,
+                            int rgb, uint8_t* imgs_dev, hipStream_t s) {
+    std::vector<JpegImg> imgs((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        JpegImg& im = imgs[(size_t)i];
+        memset(&im, 0, sizeof im);
+        im.L = L;
+        for (int c = 0; c < 3; ++c) { im.L.coef[c] += i * n_coef; im.L.plane[c] += i * n_coef; im.q[c] = c ? 1 : 0; }
+    }
+    std::vector<uint16_t> quant(q_luma, q_luma + 64);
+    quant.insert(quant.end(), q_chroma, q_chroma + 64);
+    Scratch dimg, dquant, dplane;
+    int rc;
+    if ((rc = up_async(dimg, imgs.data(), imgs.size(), s)) || (rc = up_async(dquant, quant.data(), quant.size(), s)) ||
+        (rc = dplane.alloc((size_t)n_coef * (size_t)n, s))) return rc;
+    k_jpeg_idct<<<dim3((unsigned)((n_coef / 64 + 63) / 64), (unsigned)n), dim3(64), 0, s>>>(dimg.as<JpegImg>(), dquant.as<uint16_t>(), coef_dev,
+                                                                                           dplane.as<uint8_t>());
+    k_jpeg_pixels<<<dim3((unsigned)(((int64_t)L.w * L.h + 255) / 256), (unsigned)n), dim3(256), 0, s>>>(dimg.as<JpegImg>(), dplane.as<uint8_t>(), rgb,
+                                                                                                        imgs_dev);
+    HIPCHK(hipGetLastError());
+    return mvs_check_hip(hipStreamSynchronize(s), "jpeg_coef_to_pixels_dev");
+}
+
 extern "C" {
 
 int mvs_jpeg_info(const uint8_t* data, int64_t len, mvs_jpeg_info_t* out) {

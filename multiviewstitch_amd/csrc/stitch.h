@@ -33,6 +33,16 @@ int refine_depth_maps_host(const char* fn, int32_t n_seq, const int32_t* cam_off
 // mvs_jpeg_decode's host form (jpeg.hip) under the name fn; w / h (may be NULL) receive the size; imgs == NULL: the header walk and the
 // checks only, no device needed
 int jpeg_decode_host(const char* fn, int32_t n, const int64_t* offsets, const uint8_t* data, uint32_t flags, uint8_t* imgs, int32_t* w, int32_t* h);
+// the decoder's dequantise / IDCT and pixel launches on coefficient blocks in HBM (jpeg.hip; mvs_jpeg_roundtrip): n images of layout L,
+// image i's blocks at i * n_coef, the quantisers in natural order.  Synchronises s
+struct JpegLayout;
+int jpeg_coef_to_pixels_dev(int32_t n, const JpegLayout& L, int64_t n_coef, const uint16_t* q_luma, const uint16_t* q_chroma, const int16_t* coef_dev,
+                            int rgb, uint8_t* imgs_dev, hipStream_t s);
+// mvs_jpeg_encode's host form (jpeg_enc.hip) under the name fn with an output that sizes itself: data receives offsets[n] bytes
+int jpeg_encode_host(const char* fn, int32_t n, int32_t w, int32_t h, const uint8_t* imgs, uint32_t flags, const mvs_jpeg_encode_params* p,
+                     int64_t* offsets, std::vector<uint8_t>* data);
+// mvs_depth_preview's host form (jpeg_enc.hip) under the name fn
+int depth_preview_host(const char* fn, int32_t n, int32_t w, int32_t h, const float* depths, uint8_t* out);
 // One call of the Poisson stage (poisson.hip), whichever entry made it: `rules` says which of mvs_poisson_reconstruct (PN_PLAIN),
 // _density (PN_DENSITY: dp and dinfo) and _screened (PN_SCREENED: sp and sinfo too) it is; the parts it does not have are NULL.  The
 // points are the entry's own, host or device.

@@ -226,7 +226,8 @@ def GenNewViews(cameras, imgs, view_count: int, axis: int, rot_angle: float, str
     texIndex table.  imgs [frames, h, w, 3] uint8 — a numpy array, or a contiguous torch tensor on the GPU (the device form;
     ``stream`` is then the HIP stream that produced it, and the results are tensors on the same device).
     -> (views [frames, view_count, h, w, 3] uint8, tex [frames, view_count, h*w] int32: the ``tex`` of ``MatchFilterPairs``).
-    A pixel nothing paints is (0, 0, 0) with tex = -1; the views are rasters, the reference's JPEG round trip is not reproduced."""
+    A pixel nothing paints is (0, 0, 0) with tex = -1; the views are rasters: ``JpegRoundTrip`` gives what the reference reads back from
+    ``proj%d_%d.jpg``, ``SaveViews`` writes those files."""
     n = len(cameras)
     cams = L.cam_array(cameras)
     w, h = (int(cameras[0].w), int(cameras[0].h)) if n else (0, 0)
@@ -398,7 +399,8 @@ def DetectFeatureSingleView(img, params: L.CSiftParams | None = None):
 
 
 def LoadSequenceModels(cameras, imgs, depths, view_count: int, axis: int, rot_angle: float, sift: L.CSiftParams | None = None,
-                       min_dsp: float | None = None, max_dsp: float | None = None, masks=None, segment: L.CGrabCutParams | None = None) -> dict:
+                       min_dsp: float | None = None, max_dsp: float | None = None, masks=None, segment: L.CGrabCutParams | None = None,
+                       jpeg_quality: int | None = None) -> dict:
     """The model loop of Processor::CalcSimilarityTransformationSeq for one sequence (R/Processor/Processor.cpp:524-547, LoadModel's
     GenNewViews): -> dict(cameras, depths, tex, imgs, views).  With ``sift`` (``sift_params(...)``; then ``min_dsp`` / ``max_dsp`` are
     required, ``masks`` optional) the head of the function runs to its end (:562-600): ``DetectFeature`` on the generated views and
@@ -407,6 +409,9 @@ def LoadSequenceModels(cameras, imgs, depths, view_count: int, axis: int, rot_an
     the caller then supplies from a SIFT of their own on ``views``.  With ``segment`` (``grabcut_params(...)``: ParamParser's Segment 1;
     not together with ``masks``) the masks are made here, by ``GrabCutMasks`` on ``imgs``; they go to ``CullKeypoints`` and into the result
     as ``masks``.
+    With ``jpeg_quality`` the views pass through ``JpegRoundTrip`` (4:2:0, no restart markers: ``cv::imwrite``'s stream at that quality)
+    before ``DetectFeature`` and are returned that way: the pixels SiftGPU reads from ``proj%d_%d.jpg`` (R/FeatureProc/FeatureProc.cpp:26).
+    With None nothing changes.
     This array form passes views, keys and descriptors through host memory between the three calls; a caller that wants them to stay in
     HBM chains ``mvs_gen_new_views_dev``, ``mvs_sift_detect_dev`` and ``mvs_keypoint_cull_dev`` on one stream."""
     if segment is not None and masks is not None:
@@ -416,6 +421,8 @@ def LoadSequenceModels(cameras, imgs, depths, view_count: int, axis: int, rot_an
     if len(d) != len(cameras):
         raise L.MvsError(-1, "one raster per camera")
     views, tex = GenNewViews(cameras, img, view_count, axis, rot_angle)
+    if jpeg_quality is not None:
+        views = JpegRoundTrip(views.reshape((-1,) + views.shape[2:]), quality=jpeg_quality).reshape(views.shape)
     out = dict(cameras=list(cameras), depths=d, tex=tex, imgs=img, views=views)
     if segment is not None:
         masks = out["masks"] = GrabCutMasks(img, segment)
@@ -1150,6 +1157,132 @@ def DecodeJpegs(datas, order: str = "BGR", device=None, stream: int | None = Non
     return out
 
 
+# ------------------------------------------------------------------ JPEG encode ----
+_SAMPLING = {"444": 444, "422": 422, "420": 420, 444: 444, 422: 422, 420: 420}
+
+
+def jpeg_encode_params(**kw) -> L.CJpegEncodeParams:
+    """``mvs_jpeg_encode_default_params`` (quality 95, sampling 420, restart_interval 0: what ``cv::imwrite`` writes) with the given fields
+    replaced; ``restart_interval=L.JPEG_RESTART_ROW`` is one MCU row per interval."""
+    return _params(L.CJpegEncodeParams, L.lib().mvs_jpeg_encode_default_params, kw)
+
+
+def _jpeg_enc_call(imgs, quality, sampling, restart_interval, order):
+    """-> (n, h, w, flags, params) of an encoder call on ``imgs`` [n, h, w, 3] or, with ``order`` "GREY", [n, h, w]"""
+    if order not in ("BGR", "RGB", "GREY"):
+        raise L.MvsError(-1, "order must be 'BGR', 'RGB' or 'GREY'")
+    if sampling not in _SAMPLING:
+        raise L.MvsError(-1, "sampling must be '444', '422' or '420'")
+    shape = tuple(int(x) for x in imgs.shape)
+    if (len(shape) != 3 if order == "GREY" else len(shape) != 4 or shape[3] != 3) or shape[0] < 1:
+        raise L.MvsError(-1, "imgs must be [n, h, w, 3] uint8, or [n, h, w] with order 'GREY', n >= 1")
+    flags = L.JPEG_GREY if order == "GREY" else L.JPEG_RGB if order == "RGB" else L.JPEG_BGR
+    prm = jpeg_encode_params(quality=int(quality), sampling=_SAMPLING[sampling], restart_interval=int(restart_interval))
+    return shape[0], shape[1], shape[2], flags, prm
+
+
+def JpegEncodeBound(w: int, h: int, quality: int = 95, sampling="420", restart_interval: int = 0, order: str = "BGR") -> int:
+    """``mvs_jpeg_encode_bound``: bytes that hold any stream of one w x h image with these parameters (host code, no device needed)."""
+    _, _, _, flags, prm = _jpeg_enc_call(np.empty((1, 1, 1) if order == "GREY" else (1, 1, 1, 3), np.uint8), quality, sampling, restart_interval, order)
+    return int(L.check(L.lib().mvs_jpeg_encode_bound(int(w), int(h), flags, C.byref(prm))))
+
+
+def EncodeJpegs(imgs, quality: int = 95, sampling="420", restart_interval: int = 0, order: str = "BGR", device=None, stream: int | None = None,
+                capacity: int | None = None):
+    """``mvs_jpeg_encode``: ``imgs`` [n, h, w, 3] uint8 in ``order`` "BGR" (``cv::imwrite``'s layout) or "RGB", or [n, h, w] with ``order``
+    "GREY" -> the baseline JPEG stream of every image, all images through each kernel in one launch (rules E1-E9 of include/mvs.h: this
+    library's definition, pinned byte for byte against libjpeg-turbo's default compressor).  A numpy array -> list[bytes].  With
+    ``device`` (a torch device; ``imgs`` may already be a tensor there) -> (data uint8 tensor [total], offsets int64 numpy [n + 1]):
+    ``mvs_jpeg_encode_dev`` in the order of ``stream`` (a HIP stream handle; None: the legacy default stream); pixels and streams never
+    visit the host.  ``capacity`` (bytes; default n x ``mvs_jpeg_encode_bound``) sizes the output; a call that needs more raises
+    MVS_E_INVALID_ARG, and the error carries ``offsets`` as the call wrote them."""
+    dev = device is not None or _is_dev(imgs)
+    if not dev:
+        imgs = L.arr(imgs, np.uint8)
+    n, h, w, flags, prm = _jpeg_enc_call(imgs, quality, sampling, restart_interval, order)
+    cap = int(capacity) if capacity is not None else n * int(L.check(L.lib().mvs_jpeg_encode_bound(w, h, flags, C.byref(prm))))
+    off = np.zeros(n + 1, np.int64)
+
+    def finish(rc):
+        try:
+            L.check(rc)
+        except L.MvsError as e:
+            e.offsets = off
+            raise
+
+    if not dev:
+        out = np.empty(max(1, cap), np.uint8)
+        finish(L.lib().mvs_jpeg_encode(n, w, h, L.ptr(imgs), flags, C.byref(prm), L.ptr(off), L.ptr(out), cap))
+        return [out[off[i]:off[i + 1]].tobytes() for i in range(n)]
+    import torch
+    order_ctx = torch.cuda.stream(torch.cuda.ExternalStream(int(stream))) if stream else contextlib.nullcontext()
+    with order_ctx:
+        src = imgs if _is_dev(imgs) else torch.as_tensor(L.arr(imgs, np.uint8)).to(device)
+        out = torch.empty(max(1, cap), dtype=torch.uint8, device=src.device)
+        finish(L.lib().mvs_jpeg_encode_dev(n, w, h, _dev_ptr(src, "uint8", "imgs"), flags, C.byref(prm), L.ptr(off), L.ptr(out), cap, L.ptr(stream)))
+    return out[:int(off[n])], off
+
+
+def JpegRoundTrip(imgs, quality: int = 95, sampling="420", restart_interval: int = 0, order: str = "BGR", stream: int | None = None):
+    """``mvs_jpeg_roundtrip``: the pixels ``DecodeJpegs(EncodeJpegs(imgs, ...), order)`` returns, [n, h, w, 3] uint8, without a stream in
+    between (the transform launch of the encoder, then the decoder's inverse DCT and pixel launches): what SIFT sees after the reference
+    wrote a view to ``proj%d_%d.jpg`` and read it back.  A numpy array -> a numpy array; a contiguous torch tensor on the GPU -> a tensor
+    there (``mvs_jpeg_roundtrip_dev`` in the order of ``stream``)."""
+    dev = _is_dev(imgs)
+    if not dev:
+        imgs = L.arr(imgs, np.uint8)
+    n, h, w, flags, prm = _jpeg_enc_call(imgs, quality, sampling, restart_interval, order)
+    if not dev:
+        out = np.empty((n, h, w, 3), np.uint8)
+        L.check(L.lib().mvs_jpeg_roundtrip(n, w, h, L.ptr(imgs), flags, C.byref(prm), L.ptr(out)))
+        return out
+    import torch
+    order_ctx = torch.cuda.stream(torch.cuda.ExternalStream(int(stream))) if stream else contextlib.nullcontext()
+    with order_ctx:
+        out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=imgs.device)
+        L.check(L.lib().mvs_jpeg_roundtrip_dev(n, w, h, _dev_ptr(imgs, "uint8", "imgs"), flags, C.byref(prm), L.ptr(out), L.ptr(stream)))
+    return out
+
+
+def DepthPreview(depths, stream: int | None = None):
+    """``mvs_depth_preview``: RenderDepthMap's grey image (R/Common/Utils.h:189-217) of every raster of ``depths`` [n, h, w] float32 ->
+    [n, h, w] uint8: 255 * (d - d_min) / (d_max - d_min) truncated over the valid (d >= 0, finite) pixels of the raster, 255 elsewhere;
+    0 where d_max == d_min.  A numpy array, or a contiguous torch tensor on the GPU (the device form, in the order of ``stream``)."""
+    dev = _is_dev(depths)
+    if not dev:
+        depths = L.arr(depths, np.float32)
+    if len(depths.shape) != 3 or depths.shape[0] < 1:
+        raise L.MvsError(-1, "depths must be [n, h, w] float32, n >= 1")
+    n, h, w = (int(x) for x in depths.shape)
+    if not dev:
+        out = np.empty((n, h, w), np.uint8)
+        L.check(L.lib().mvs_depth_preview(n, w, h, L.ptr(depths), L.ptr(out)))
+        return out
+    import torch
+    order_ctx = torch.cuda.stream(torch.cuda.ExternalStream(int(stream))) if stream else contextlib.nullcontext()
+    with order_ctx:
+        out = torch.empty((n, h, w), dtype=torch.uint8, device=depths.device)
+        L.check(L.lib().mvs_depth_preview_dev(n, w, h, _dev_ptr(depths, "float32", "depths"), L.ptr(out), L.ptr(stream)))
+    return out
+
+
+def SaveViews(seq_dir, views, quality: int = 95, sampling="420", restart_interval: int = 0, order: str = "BGR") -> None:
+    """``mvs_processor_save_views``: the views of ``GenNewViews`` [frames, view_count, h, w, 3] uint8 -> ``seq_dir``Views/proj<frame>_<view>.jpg
+    (R/Image3D/Image3D.cpp:218-219), the bytes ``EncodeJpegs`` returns for them."""
+    v = L.arr(views, np.uint8)
+    if v.ndim != 5 or v.shape[4] != 3 or order not in ("BGR", "RGB"):
+        raise L.MvsError(-1, "views must be [frames, view_count, h, w, 3] in order 'BGR' or 'RGB'")
+    _, h, w, flags, prm = _jpeg_enc_call(v.reshape((-1,) + v.shape[2:]), quality, sampling, restart_interval, order)
+    L.check(L.lib().mvs_processor_save_views(os.fsencode(seq_dir), int(v.shape[0]), int(v.shape[1]), w, h, L.ptr(v), flags, C.byref(prm)))
+
+
+def DepthPreviewFiles(seq_dir, sub: str, n: int, w: int, h: int, quality: int = 95, restart_interval: int = 0) -> None:
+    """``mvs_processor_depth_previews``: ``seq_dir``DATA/``sub``/_depth<i>.raw, i < n, each w x h -> _depth<i>.jpg beside it: ``EncodeJpegs``
+    (grey) of ``DepthPreview`` of the rasters.  ``sub`` is "CHECK", "Render" or "Refine"."""
+    prm = jpeg_encode_params(quality=int(quality), restart_interval=int(restart_interval))
+    L.check(L.lib().mvs_processor_depth_previews(os.fsencode(seq_dir), os.fsencode(sub), int(n), int(w), int(h), C.byref(prm)))
+
+
 def LoadImages(seq_dirs, cameras, order: str = "BGR") -> list:
     """``mvs_processor_load_images``: camera i of sequence k from ``seq_dirs[k]``%05d.jpg (R/Processor/Processor.cpp:532) -> per sequence
     [frames, h, w, 3] uint8; the files are read on host threads and all sequences of one size are decoded in one call."""
@@ -1174,7 +1307,7 @@ def LoadImages(seq_dirs, cameras, order: str = "BGR") -> list:
 def LoadSequenceFiles(seq_dir, cameras, view_count: int, axis: int, rot_angle: float, **kw) -> dict:
     """``LoadSequenceModels`` from a sequence directory: the frames ``seq_dir``%05d.jpg (``LoadImages``, BGR as ``cv::imread``) and the
     checked rasters ``seq_dir``/DATA/CHECK/_depth<i>.raw (``mvs_depth_raw_read``) -> the ``sequences[k]`` entry of
-    ``CalcSimilarityTransformationSeq``.  ``kw`` goes to ``LoadSequenceModels`` (sift, min_dsp, max_dsp, masks, segment)."""
+    ``CalcSimilarityTransformationSeq``.  ``kw`` goes to ``LoadSequenceModels`` (sift, min_dsp, max_dsp, masks, segment, jpeg_quality)."""
     (imgs,) = LoadImages([seq_dir], [cameras], "BGR")
     depths = np.empty((len(cameras),) + tuple(imgs.shape[1:3]), np.float32)
     for i, cam in enumerate(cameras):

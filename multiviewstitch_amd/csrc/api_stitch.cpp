@@ -17,7 +17,6 @@
 #include <sys/stat.h>
 #include <algorithm>
 #include <string>
-#include <thread>
 #include <vector>
 
 namespace {
@@ -394,8 +393,8 @@ static int load_images_body(const char* fn, int32_t n_seq, const char* const* se
             std::snprintf(name, sizeof name, "%05d.jpg", c - cam_off[k]);                          // Processor.cpp:532
             path[(size_t)c] = join(seq_dirs[k], name);
         }
-    const int nt = (int)std::max(1u, std::min({16u, (unsigned)ncam, std::max(1u, std::thread::hardware_concurrency())}));
-    auto part = [&](int t) {
+    const int nt = io_threads(ncam, IO_UNKNOWN);
+    parallel_parts(nt, [&](int t) {
         for (int c = t; c < ncam; c += nt) {
             FILE* f = std::fopen(path[(size_t)c].c_str(), "rb");
             if (!f) { err[(size_t)c] = errno ? errno : EIO; continue; }
@@ -405,11 +404,7 @@ static int load_images_body(const char* fn, int32_t n_seq, const char* const* se
             if (std::ferror(f)) err[(size_t)c] = EIO;
             std::fclose(f);
         }
-    };
-    std::vector<std::thread> th;
-    for (int t = 1; t < nt; ++t) th.emplace_back(part, t);
-    part(0);
-    for (auto& x : th) x.join();
+    });
     for (int c = 0; c < ncam; ++c)
         if (err[(size_t)c]) { mvs_set_error("%s: %s: %s", fn, path[(size_t)c].c_str(), std::strerror(err[(size_t)c])); return MVS_E_IO; }
     // the cameras by size, in the order of their first camera; pass 0 walks the streams and checks the sizes, pass 1 decodes
@@ -481,8 +476,8 @@ int mvs_processor_refine_depths_files(int32_t n_seq, const char* const* seq_dirs
 static int write_streams(const char* fn, const std::vector<std::string>& path, const int64_t* off, const uint8_t* data) {
     const int n = (int)path.size();
     std::vector<int> err((size_t)n, 0);
-    const int nt = (int)std::max(1u, std::min({16u, (unsigned)n, std::max(1u, std::thread::hardware_concurrency())}));
-    auto part = [&](int t) {
+    const int nt = io_threads(n, IO_UNKNOWN);
+    parallel_parts(nt, [&](int t) {
         for (int i = t; i < n; i += nt) {
             FILE* f = std::fopen(path[(size_t)i].c_str(), "wb");
             if (!f) { err[(size_t)i] = errno ? errno : EIO; continue; }
@@ -490,11 +485,7 @@ static int write_streams(const char* fn, const std::vector<std::string>& path, c
             if (std::fwrite(data + off[i], 1, len, f) != len) err[(size_t)i] = EIO;
             if (std::fclose(f)) err[(size_t)i] = EIO;
         }
-    };
-    std::vector<std::thread> th;
-    for (int t = 1; t < nt; ++t) th.emplace_back(part, t);
-    part(0);
-    for (auto& x : th) x.join();
+    });
     for (int i = 0; i < n; ++i)
         if (err[(size_t)i]) { mvs_set_error("%s: %s: %s", fn, path[(size_t)i].c_str(), std::strerror(err[(size_t)i])); return MVS_E_IO; }
     return MVS_OK;

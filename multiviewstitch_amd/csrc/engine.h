@@ -4,10 +4,12 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <chrono>
 #include <string>
 #include <vector>
 #include <map>
 #include "../../include/mvs.h"
+#include "host_parts.h"   // io_threads, parallel_parts: the host thread fan-out
 
 void mvs_set_error(const char* fmt, ...);
 int  mvs_check_hip(hipError_t e, const char* what);
@@ -411,6 +413,33 @@ template <class T> int up_async(Scratch& d, const T* h, size_t n, hipStream_t s)
 template <class T> int down(T* h, const Scratch& d, size_t n) {
     return n ? mvs_check_hip(hipMemcpy(h, d.p, sizeof(T) * n, hipMemcpyDeviceToHost), "download") : MVS_OK;
 }
+// The stage clock of the timed test hooks (include/mvs_test.h): constructed enabled or disabled; mark(s) records an event on s when
+// enabled; read(ms), after the caller has synchronised s, writes the milliseconds between consecutive marks (marks - 1 values).  The
+// destructor destroys every event that was created, on whichever path the caller returns.
+inline double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+struct StageClock {
+    const bool on;
+    std::vector<hipEvent_t> ev;
+    explicit StageClock(bool enabled) : on(enabled) {}
+    StageClock(const StageClock&) = delete;
+    StageClock& operator=(const StageClock&) = delete;
+    ~StageClock() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
+    int mark(hipStream_t s) {
+        if (!on) return MVS_OK;
+        hipEvent_t e = nullptr;
+        HIPCHK(hipEventCreate(&e));
+        ev.push_back(e);
+        return mvs_check_hip(hipEventRecord(e, s), "hipEventRecord");
+    }
+    int read(double* ms) const {
+        for (size_t k = 0; k + 1 < ev.size(); ++k) {
+            float f = 0.f;
+            HIPCHK(hipEventElapsedTime(&f, ev[k], ev[k + 1]));
+            ms[k] = f;
+        }
+        return MVS_OK;
+    }
+};
 // the argument checks of the host entries: every one reports through bad(); check_offsets is the test of the n + 1 offsets of n
 // back-to-back lists (int64_t or int32_t): off[0] == 0, ascending and, with a limit, off[n] below it
 // a camera a raster kernel can use: positive size and focal lengths it can divide by (consist.hip, pointsample.hip)

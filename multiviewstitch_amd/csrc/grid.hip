@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include "dev_common.h"
 #include "grid_dev.h"
+#include "scan_dev.h"
 #include "knobs.h"
 #include <algorithm>
 #include <cmath>
@@ -79,58 +80,6 @@ __global__ __launch_bounds__(TPB) void k_count_nonzero(const int32_t* __restrict
     }
 }
 
-// ---- exclusive scan of int32 counts (3 phases, 1024 elements per block) ----
-constexpr int SCAN_ELEMS = 1024;
-
-__global__ void k_scan_block_sums(const int32_t* __restrict__ in, int64_t n, int32_t* __restrict__ bsum) {
-    const int64_t base = (int64_t)blockIdx.x * SCAN_ELEMS;
-    int s = 0;
-    for (int k = threadIdx.x; k < SCAN_ELEMS; k += blockDim.x)
-        if (base + k < n) s += in[base + k];
-    s = wave_sum_i(s);
-    __shared__ int sm[TPB / 64];
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) { int t = 0; for (int w = 0; w < TPB / 64; ++w) t += sm[w]; bsum[blockIdx.x] = t; }
-}
-
-// exclusive scan of the nb block sums in place, ONE workgroup of 1024 threads: a thread owns a contiguous run of ceil(nb / 1024)
-// sums (a wave walking 64 at a time took 13-43 us for the 2-64 K block sums of a target grid or a 2 M-vertex compaction)
-__global__ __launch_bounds__(1024) void k_scan_sums_serial(int32_t* bsum, int64_t nb) {
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    const int64_t per = (nb + 1023) / 1024, lo = (int64_t)t * per, hi = lo + per < nb ? lo + per : nb;
-    int sum = 0;
-    for (int64_t i = lo; i < hi; ++i) sum += bsum[i];
-    int x = sum;
-    for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(x, o, 64); if (lane >= o) x += y; }
-    __shared__ int sm[16];
-    if (lane == 63) sm[wv] = x;
-    __syncthreads();
-    int off = 0;
-    for (int w = 0; w < wv; ++w) off += sm[w];
-    int run = off + x - sum;
-    for (int64_t i = lo; i < hi; ++i) { const int v = bsum[i]; bsum[i] = run; run += v; }
-}
-
-__global__ void k_scan_apply(const int32_t* __restrict__ in, int64_t n, const int32_t* __restrict__ bsum,
-                             int32_t* __restrict__ out) {
-    // each thread owns 4 consecutive elements of the block's 1024
-    const int64_t base = (int64_t)blockIdx.x * SCAN_ELEMS + threadIdx.x * 4;
-    int v[4], t = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { v[k] = (base + k < n) ? in[base + k] : 0; t += v[k]; }
-    int x = t;
-    for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(x, o, 64); if ((int)(threadIdx.x & 63) >= o) x += y; }
-    __shared__ int sm[TPB / 64];
-    if ((threadIdx.x & 63) == 63) sm[threadIdx.x >> 6] = x;
-    __syncthreads();
-    int off = bsum[blockIdx.x];
-    for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) off += sm[w];
-    int run = off + x - t;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { if (base + k <= n) out[base + k] = run; run += v[k]; }   // out has n+1 entries
-}
-
 __global__ void k_scatter(const double* __restrict__ pts, const double* __restrict__ nrm, int64_t P,
                           const int32_t* __restrict__ cell_of_pt, const int32_t* __restrict__ cell_start,
                           int32_t* __restrict__ cursor, float4* __restrict__ spos, double* __restrict__ tpos,
@@ -160,12 +109,10 @@ __global__ void k_coarse_start(const int32_t* __restrict__ cs, int64_t ncoarse, 
 
 }  // namespace
 
-// in: n entries; out: n+1 entries, out[n] = total; bsum: (n + 1 + 1023) / 1024 ints of workspace.  No allocation, no host sync.
+// the <int32_t, int32_t> instantiation of scan_dev.h.  in: n entries; out: n+1 entries, out[n] = total; bsum: (n + 1 + 1023) / 1024 ints
+// of workspace.  No allocation, no host sync.
 void scan_exclusive_i32_async(const int32_t* in, int64_t n, int32_t* out, int32_t* bsum, hipStream_t s) {
-    const int64_t nb = (n + 1 + SCAN_ELEMS - 1) / SCAN_ELEMS;
-    k_scan_block_sums<<<dim3((unsigned)nb), dim3(TPB), 0, s>>>(in, n, bsum);
-    k_scan_sums_serial<<<dim3(1), dim3(1024), 0, s>>>(bsum, nb);
-    k_scan_apply<<<dim3((unsigned)nb), dim3(TPB), 0, s>>>(in, n, bsum, out);
+    scan_exclusive_async<int32_t, int32_t>(in, n, out, bsum, s);
 }
 
 // allocating, synchronising form (set-up paths of geom.hip / align.hip)
@@ -311,9 +258,9 @@ const void* const* mvs_tu_kernels_grid(int* n) {
         (const void*)k_bbox,
         (const void*)k_cell_count,
         (const void*)k_count_nonzero,
-        (const void*)k_scan_block_sums,
-        (const void*)k_scan_sums_serial,
-        (const void*)k_scan_apply,
+        (const void*)k_scan_block_sums<int32_t, int32_t>,
+        (const void*)k_scan_sums_serial<int32_t>,
+        (const void*)k_scan_apply<int32_t, int32_t>,
         (const void*)k_scatter,
         (const void*)k_coarse_start};
     *n = (int)(sizeof ks / sizeof ks[0]);

@@ -9,7 +9,6 @@
 #include <cstdint>
 #include <functional>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/mvs_io.h"
@@ -170,19 +169,6 @@ inline bool next_int(const char*& p, const char* end, int* out) {
     return true;
 }
 
-// fn(part, begin, end) on `parts` ranges of [0, n) — threads for the large files only
-int io_threads(size_t bytes) {
-    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-    return (int)std::max<size_t>(1, std::min<size_t>(std::min<unsigned>(hw, 16u), bytes >> 20));
-}
-void parallel_parts(int parts, const std::function<void(int)>& fn) {
-    if (parts <= 1) { fn(0); return; }
-    std::vector<std::thread> th;
-    for (int t = 1; t < parts; ++t) th.emplace_back(fn, t);
-    fn(0);
-    for (auto& x : th) x.join();
-}
-
 bool read_whole(const char* path, std::string* s) {
     File fp(path, "rb");
     if (!fp.f) return false;
@@ -277,7 +263,7 @@ static int obj_parse(const std::string& text, const char* path, int64_t* n_verti
     // getline(line, 512) fails there and the reference's loop ends, PlyObj.cpp:40-41), pass 2 parses every part at its offsets
     const char* T = text.data();
     const size_t N = text.size();
-    const int parts = io_threads(N);
+    const int parts = io_threads(IO_UNKNOWN, (int64_t)N);
     std::vector<size_t> cut((size_t)parts + 1, N);
     cut[0] = 0;
     for (int t = 1; t < parts; ++t) {
@@ -383,7 +369,7 @@ int mvs_obj_write(const char* path, int64_t n_vertices, const double* points, co
     head += "\n#\n# Vertices: " + std::to_string(n_vertices) + "\n# Faces: " + std::to_string(n_faces) + "\n#\n####\n";
     // the vertex block, then the facet block: rounds of `parts` slices of BLOCK items formatted side by side into buffers that are
     // reused, each round written in order (a buffer per part for the WHOLE file was 324 MB of first-touched memory: 2 s)
-    const int parts = io_threads((size_t)n_vertices * (normals ? 60 : 30) + (size_t)n_faces * 30);
+    const int parts = io_threads(IO_UNKNOWN, (int64_t)n_vertices * (normals ? 60 : 30) + (int64_t)n_faces * 30);
     const int64_t BLOCK = 1 << 16;
     std::vector<std::string> txt((size_t)parts);
     errno = 0;
@@ -471,7 +457,7 @@ int mvs_npts_read(const char* path, int64_t* n, double* points, double* normals)
     // pass 2 parses them into their places; the first token that is no number ends the file there (as `stream >> float` does)
     const char* T = text.data();
     const size_t N = text.size();
-    const int parts = io_threads(N);
+    const int parts = io_threads(IO_UNKNOWN, (int64_t)N);
     std::vector<size_t> cut((size_t)parts + 1, N);
     cut[0] = 0;
     for (int t = 1; t < parts; ++t) {
@@ -525,7 +511,7 @@ int mvs_npts_read(const char* path, int64_t* n, double* points, double* normals)
 int mvs_npts_write(const char* path, int64_t n, const double* points, const double* normals) {
     MVS_TRACE();
     if (!path || n < 0 || (n && (!points || !normals))) { mvs_set_error("mvs_npts_write: bad arguments"); return MVS_E_INVALID_ARG; }
-    const int parts = io_threads((size_t)n * 60);
+    const int parts = io_threads(IO_UNKNOWN, (int64_t)n * 60);
     std::vector<std::string> txt((size_t)parts);
     parallel_parts(parts, [&](int t) {
         std::string& o = txt[t];

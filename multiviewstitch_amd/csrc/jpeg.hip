@@ -1,5 +1,7 @@
 // jpeg.hip — mvs_jpeg_info, mvs_jpeg_decode(_dev) (include/mvs.h): the batched baseline JPEG decoder, rules J1-J8.  The header walk is
-// host code (jpeg_rules.h: jpeg_parse); the rest is three launch sets, each over all images of the call:
+// host code (jpeg_rules.h: jpeg_parse) on the fan-out of host_parts.h; the rest is three launch sets, each over all images of the call.
+// Which block a wave or a lane is at comes from the walks of jpeg_rules.h, which the encoder shares; the last two launch sets are
+// jpeg_pixels_tail, which the encoder's round trip runs too; the timed hook's stage times come from the StageClock of engine.h.
 //
 //   k_jpeg_entropy ONE launch, a workgroup of one wave per entry of the segment table (a restart interval, or a whole scan).  The wave
 //                  copies the Huffman tables of its image into LDS and stages the segment's bytes through a ring of 2048 bytes in LDS,
@@ -19,8 +21,6 @@
 #include "../../include/mvs_test.h"
 #include "stitch.h"
 #include <algorithm>
-#include <chrono>
-#include <thread>
 
 namespace {
 
@@ -68,12 +68,11 @@ __global__ __launch_bounds__(64) void k_jpeg_entropy(const JpegSeg* __restrict__
     __syncthreads();
     JpegBits<RingBytes> bits{RingBytes{(const uint8_t*)s_ring}, sg.first, sg.end, 0u, 0};     // lane 0's
     int err = 0;
-    const int b0 = L.hs[0] * L.vs[0], bpm = L.ncomp == 1 ? 1 : b0 + 2;
-    const int nblk = sg.nmcu * bpm;
+    const int bpm = jpeg_blocks_per_mcu(L), nblk = sg.nmcu * bpm;
     for (int blk = 0; blk < nblk; ++blk) {
-        const int m = sg.mcu0 + blk / bpm, k = blk % bpm;
-        const int c = k < b0 ? 0 : k - b0 + 1, kk = k < b0 ? k : 0;
-        const int64_t at = L.coef[c] + 64 * jpeg_block_of(L, c, m, kk % L.hs[c], kk / L.hs[c]);
+        int c, bx, by, m;
+        jpeg_scan_block(L, sg.mcu0 * bpm + blk, &c, &bx, &by, &m);
+        const int64_t at = jpeg_block_at(L, c, bx, by);
         s_blk[lane] = 0;
         __syncthreads();
         if (lane == 0 && !err) {
@@ -102,21 +101,16 @@ __global__ __launch_bounds__(64) void k_jpeg_idct(const JpegImg* __restrict__ im
                                                   const int16_t* __restrict__ coef, uint8_t* __restrict__ planes) {
     const JpegImg* im = imgs + blockIdx.y;
     const JpegLayout& L = im->L;
-    int64_t b = (int64_t)blockIdx.x * 64 + threadIdx.x;
-    int c = 0;
-    for (; c < L.ncomp; ++c) {
-        const int64_t nb = (int64_t)L.bw[c] * L.bh[c];
-        if (b < nb) break;
-        b -= nb;
-    }
-    if (c >= L.ncomp) return;
+    int c, bx, by;
+    int64_t k;
+    if (!jpeg_plane_find(L, (int64_t)blockIdx.x * 64 + threadIdx.x, &c, &k)) return;
     uint32_t ws[8][8];
     for (int x = 0; x < 8; ++x) {
         uint32_t col[8];
-        jpeg_idct_column(coef + L.coef[c] + 64 * b, quant + 64 * im->q[c], x, col);
+        jpeg_idct_column(coef + L.coef[c] + 64 * k, quant + 64 * im->q[c], x, col);
         for (int v = 0; v < 8; ++v) ws[v][x] = col[v];
     }
-    const int by = (int)(b / L.bw[c]), bx = (int)(b % L.bw[c]);
+    jpeg_plane_place(L, c, k, &bx, &by);
     for (int y = 0; y < 8; ++y) {
         union { uint8_t b8[8]; uint2 u; } px;
         jpeg_idct_row(ws[y], px.b8);
@@ -145,8 +139,6 @@ struct JpegPlan {
     int w = 0, h = 0;
 };
 
-double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
 // J1, J2, J8 for the n streams of a call
 int jpeg_plan(const char* fn, int32_t n, const int64_t* offsets, const uint8_t* data, uint32_t flags, JpegPlan* pl) {
     if (n < 1) return bad(fn, "need n >= 1");
@@ -156,16 +148,10 @@ int jpeg_plan(const char* fn, int32_t n, const int64_t* offsets, const uint8_t* 
     if (rc) return rc;
     std::vector<JpegHeader> hd((size_t)n);
     std::vector<char> ok((size_t)n, 0);
-    const int64_t bytes = offsets[n];
-    const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(16, std::max(1u, std::thread::hardware_concurrency())),
-                                                               std::min<int64_t>(n, bytes >> 20)));
-    auto part = [&](int t) {
+    const int nt = io_threads(n, offsets[n]);
+    parallel_parts(nt, [&](int t) {
         for (int i = t; i < n; i += nt) ok[(size_t)i] = jpeg_parse(data + offsets[i], offsets[i + 1] - offsets[i], &hd[(size_t)i]);
-    };
-    std::vector<std::thread> th;
-    for (int t = 1; t < nt; ++t) th.emplace_back(part, t);
-    part(0);
-    for (auto& x : th) x.join();
+    });
     for (int i = 0; i < n; ++i)
         if (!ok[(size_t)i]) { mvs_set_error("%s: image %d: %s", fn, i, hd[(size_t)i].why.c_str()); return MVS_E_IO; }
     pl->w = hd[0].w; pl->h = hd[0].h;
@@ -211,11 +197,24 @@ int jpeg_plan(const char* fn, int32_t n, const int64_t* offsets, const uint8_t* 
     return MVS_OK;
 }
 
+// J4-J7, the one coefficients-to-pixels tail (jpeg_run; the round trip through jpeg_coef_to_pixels_dev): the dequantise / IDCT launch and
+// the pixel launch on n images of w x h, max_blocks the largest block count of one.  planes: a byte per padded sample, allocated by the
+// caller in front of its first launch (allocating here put the pool's fence on s between the entropy launch and these two: 0.041 ->
+// 0.046 ms on the IDCT stage of the timed hook).  clk gets a mark behind each launch
+int jpeg_pixels_tail(const JpegImg* imgs, const uint16_t* quant, const int16_t* coef, int32_t n, int64_t max_blocks, int w, int h, int rgb,
+                     uint8_t* planes, uint8_t* out, StageClock& clk, hipStream_t s) {
+    k_jpeg_idct<<<dim3((unsigned)((max_blocks + 63) / 64), (unsigned)n), dim3(64), 0, s>>>(imgs, quant, coef, planes);
+    if (int rc = clk.mark(s)) return rc;
+    k_jpeg_pixels<<<dim3((unsigned)(((int64_t)w * h + 255) / 256), (unsigned)n), dim3(256), 0, s>>>(imgs, planes, rgb, out);
+    return clk.mark(s);
+}
+
 // upload, the three launch sets and the error words, complete on return; ms (may be NULL): upload, entropy, idct, pixels in milliseconds
 int jpeg_run(const char* fn, const JpegPlan& pl, int32_t n, const int64_t* offsets, const uint8_t* data, uint32_t flags, uint8_t* imgs_dev,
              hipStream_t s, double* ms) {
     const size_t bytes = (size_t)offsets[n], padded = (bytes + 3) / 4 * 4 + 4;
     Scratch ddata, dimg, dhuff, dquant, dseg, dcoef, dplane, derr;
+    StageClock clk(ms != nullptr);
     int rc;
     const double t0 = now_ms();
     if ((rc = ddata.alloc(padded, s))) return rc;
@@ -226,34 +225,20 @@ int jpeg_run(const char* fn, const JpegPlan& pl, int32_t n, const int64_t* offse
         (rc = dcoef.alloc(sizeof(int16_t) * (size_t)pl.n_coef, s)) || (rc = dplane.alloc((size_t)pl.n_plane, s)) ||
         (rc = derr.alloc(sizeof(int32_t) * (size_t)n, s))) return rc;
     HIPCHK(hipMemsetAsync(derr.p, 0, sizeof(int32_t) * (size_t)n, s));
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     if (ms) {
         HIPCHK(hipStreamSynchronize(s));
         ms[0] = now_ms() - t0;
-        for (auto& e : ev) HIPCHK(hipEventCreate(&e));
-        HIPCHK(hipEventRecord(ev[0], s));
     }
+    if ((rc = clk.mark(s))) return rc;
     k_jpeg_entropy<<<dim3((unsigned)pl.segs.size()), dim3(64), 0, s>>>(dseg.as<JpegSeg>(), dimg.as<JpegImg>(), dhuff.as<JpegHuff>(),
                                                                         ddata.as<uint32_t>(), dcoef.as<int16_t>(), derr.as<int32_t>());
-    if (ms) HIPCHK(hipEventRecord(ev[1], s));
-    k_jpeg_idct<<<dim3((unsigned)((pl.max_blocks + 63) / 64), (unsigned)n), dim3(64), 0, s>>>(dimg.as<JpegImg>(), dquant.as<uint16_t>(),
-                                                                                             dcoef.as<int16_t>(), dplane.as<uint8_t>());
-    if (ms) HIPCHK(hipEventRecord(ev[2], s));
-    k_jpeg_pixels<<<dim3((unsigned)(((int64_t)pl.w * pl.h + 255) / 256), (unsigned)n), dim3(256), 0, s>>>(
-        dimg.as<JpegImg>(), dplane.as<uint8_t>(), (int)(flags & MVS_JPEG_RGB), imgs_dev);
-    if (ms) HIPCHK(hipEventRecord(ev[3], s));
+    if ((rc = clk.mark(s)) || (rc = jpeg_pixels_tail(dimg.as<JpegImg>(), dquant.as<uint16_t>(), dcoef.as<int16_t>(), n, pl.max_blocks, pl.w, pl.h,
+                                                     (int)(flags & MVS_JPEG_RGB), dplane.as<uint8_t>(), imgs_dev, clk, s))) return rc;
     HIPCHK(hipGetLastError());
     std::vector<int32_t> err((size_t)n);
     HIPCHK(hipMemcpyAsync(err.data(), derr.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    if (ms) {
-        for (int k = 0; k < 3; ++k) {
-            float f = 0.f;
-            HIPCHK(hipEventElapsedTime(&f, ev[k], ev[k + 1]));
-            ms[1 + k] = f;
-        }
-        for (auto& e : ev) (void)hipEventDestroy(e);
-    }
+    if (ms && (rc = clk.read(ms + 1))) return rc;
     for (int i = 0; i < n; ++i)
         if (err[(size_t)i]) {
             int e = 1;
@@ -281,8 +266,8 @@ int jpeg_decode_host(const char* fn, int32_t n, const int64_t* offsets, const ui
     return down(imgs, dout, nb);
 }
 
-// the dequantise / IDCT launch and the pixel launch on coefficient blocks that are in HBM already (mvs_jpeg_roundtrip, jpeg_enc.hip): n
-// images of layout L (blocks and planes from 0), image i's blocks at i * n_coef.  Synchronises s
+// the round trip of jpeg_enc.hip: the table of n images of layout L (blocks and planes from 0), image i's blocks at i * n_coef, then
+// jpeg_pixels_tail.  Synchronises s
 int jpeg_coef_to_pixels_dev(int32_t n, const JpegLayout& L, int64_t n_coef, const uint16_t* q_luma, const uint16_t* q_chroma, const int16_t* coef_dev,
                             int rgb, uint8_t* imgs_dev, hipStream_t s) {
     std::vector<JpegImg> imgs((size_t)n);
@@ -295,15 +280,24 @@ int jpeg_coef_to_pixels_dev(int32_t n, const JpegLayout& L, int64_t n_coef, cons
     std::vector<uint16_t> quant(q_luma, q_luma + 64);
     quant.insert(quant.end(), q_chroma, q_chroma + 64);
     Scratch dimg, dquant, dplane;
+    StageClock off(false);
     int rc;
     if ((rc = up_async(dimg, imgs.data(), imgs.size(), s)) || (rc = up_async(dquant, quant.data(), quant.size(), s)) ||
-        (rc = dplane.alloc((size_t)n_coef * (size_t)n, s))) return rc;
-    k_jpeg_idct<<<dim3((unsigned)((n_coef / 64 + 63) / 64), (unsigned)n), dim3(64), 0, s>>>(dimg.as<JpegImg>(), dquant.as<uint16_t>(), coef_dev,
-                                                                                           dplane.as<uint8_t>());
-    k_jpeg_pixels<<<dim3((unsigned)(((int64_t)L.w * L.h + 255) / 256), (unsigned)n), dim3(256), 0, s>>>(dimg.as<JpegImg>(), dplane.as<uint8_t>(), rgb,
-                                                                                                        imgs_dev);
+        (rc = dplane.alloc((size_t)n_coef * (size_t)n, s)) ||
+        (rc = jpeg_pixels_tail(dimg.as<JpegImg>(), dquant.as<uint16_t>(), coef_dev, n, n_coef / 64, L.w, L.h, rgb, dplane.as<uint8_t>(), imgs_dev, off, s))) return rc;
     HIPCHK(hipGetLastError());
     return mvs_check_hip(hipStreamSynchronize(s), "jpeg_coef_to_pixels_dev");
+}
+
+// mvs_jpeg_decode_dev under the name fn; ms (NULL: not timed): the header walk, then jpeg_run's four, in milliseconds
+static int jpeg_decode_dev(const char* fn, int32_t n, const int64_t* offsets, const uint8_t* data, uint32_t flags, uint8_t* imgs_dev, void* hip_stream,
+                           double* ms) {
+    JpegPlan pl;
+    const double t0 = now_ms();
+    int rc = jpeg_plan(fn, n, offsets, data, flags, &pl);
+    if (ms) ms[0] = now_ms() - t0;
+    if (rc || (rc = need_device())) return rc;
+    return jpeg_run(fn, pl, n, offsets, data, flags, imgs_dev, (hipStream_t)hip_stream, ms ? ms + 1 : nullptr);
 }
 
 extern "C" {
@@ -326,21 +320,13 @@ int mvs_jpeg_decode(int32_t n, const int64_t* offsets, const uint8_t* data, uint
 int mvs_jpeg_decode_dev(int32_t n, const int64_t* offsets, const uint8_t* data, uint32_t flags, uint8_t* imgs_dev, void* hip_stream) {
     MVS_TRACE();
     if (!imgs_dev) return bad(__func__, "imgs_dev is NULL");
-    JpegPlan pl;
-    int rc = jpeg_plan(__func__, n, offsets, data, flags, &pl);
-    if (rc || (rc = need_device())) return rc;
-    return jpeg_run(__func__, pl, n, offsets, data, flags, imgs_dev, (hipStream_t)hip_stream, nullptr);
+    return jpeg_decode_dev(__func__, n, offsets, data, flags, imgs_dev, hip_stream, nullptr);
 }
 
 int mvs_test_jpeg_decode_timed(int32_t n, const int64_t* offsets, const uint8_t* data, uint32_t flags, uint8_t* imgs_dev, void* hip_stream,
                                double* ms) {
     if (!ms || !imgs_dev) return bad(__func__, "ms or imgs_dev is NULL");
-    JpegPlan pl;
-    const double t0 = now_ms();
-    int rc = jpeg_plan(__func__, n, offsets, data, flags, &pl);
-    ms[0] = now_ms() - t0;
-    if (rc || (rc = need_device())) return rc;
-    return jpeg_run(__func__, pl, n, offsets, data, flags, imgs_dev, (hipStream_t)hip_stream, ms + 1);
+    return jpeg_decode_dev(__func__, n, offsets, data, flags, imgs_dev, hip_stream, ms);
 }
 
 }  // extern "C"

@@ -4,31 +4,32 @@
 //   k_je_transform ONE launch, a lane per coefficient block of the padded planes (JpegLayout, as the decoder's): E2-E5.  The lane
 //                  gathers its 64 samples (colour, edge repeat and downsampling on the way), runs the row and the column pass of E4 with
 //                  the workspace in registers and writes the quantised block as eight 16-byte stores.  Dummy blocks (E6) are zeros.
-//   entropy        k_je_bits: a lane per scan block, its bit count; the DC predecessor is read from the coefficient array.  scan_u64 over
-//                  all blocks of the call.  k_je_intervals: bytes per restart interval (or whole scan); scan_u64 over the intervals gives
+//   entropy        k_je_bits: a lane per scan block, its bit count; the DC predecessor is read from the coefficient array.  A scan over
+//                  all blocks of the call.  k_je_intervals: bytes per restart interval (or whole scan); a scan over the intervals gives
 //                  each one a byte-aligned start in the unstuffed buffer.  k_je_write: a lane per scan block puts its bits at their bit
 //                  offset, whole 32-bit words with atomicOr into the zeroed buffer (an OR commutes: the bytes do not depend on the
 //                  order), the interval's last lane fills the last byte with 1 bits.  A scan without restart markers is one interval and
 //                  goes through the same lanes: nothing is serial in it.
-//   stuffing       k_je_ffcount: FF bytes per chunk of 1024 unstuffed bytes; scan_u64; k_je_offsets: a wave per image, the stream
+//   stuffing       k_je_ffcount: FF bytes per chunk of 1024 unstuffed bytes; a scan; k_je_offsets: a wave per image, the stream
 //                  offsets (E9) — the host reads them and checks the capacity before anything is written to the output;
 //                  k_je_stuff: a lane per four unstuffed bytes writes them at their final place, FF followed by 00; the lane that holds
 //                  an interval's last byte writes RSTn or EOI behind it.  k_je_headers copies the header in front of every scan.
 //   k_dp_range / k_dp_write: mvs_depth_preview, min / max of the valid depths by atomicMin / atomicMax on the bits of the non-negative
 //                  floats (order-free), then a lane per pixel.
 //
-// Stream positions come from scans only; two runs give the same bytes.
+// Stream positions come from scans only; two runs give the same bytes.  The scans are scan_dev.h's, as grid.hip's; which block a lane
+// is at comes from the walks of jpeg_rules.h, as in the decoder; the round trip ends in the decoder's jpeg_pixels_tail (jpeg.hip).
 #include "engine.h"
 #include "trace.h"
 #include "jpeg_enc_rules.h"
 #include "frontend_dev.h"
+#include "scan_dev.h"
 #include "../../include/mvs_test.h"
 #include "stitch.h"
-#include <chrono>
 
 namespace {
 
-constexpr int JE_TPB = 256, JE_ITEMS = 4, JE_TILE = JE_TPB * JE_ITEMS;   // scan tile; also the stuffing chunk in bytes
+constexpr int JE_TPB = 256, JE_TILE = JE_TPB * 4;   // the stuffing chunk in bytes: four per lane
 
 struct JeCall {                        // what every kernel of a call reads
     JpegLayout L;                      // of one image; image i's blocks start at i * n_coef
@@ -37,7 +38,8 @@ struct JeCall {                        // what every kernel of a call reads
     int32_t n, per, nint, hdr;         // images, MCUs per interval, intervals per image, header bytes
 };
 
-// exclusive scan of 256 values, one per thread; *total: their sum
+// exclusive scan of 256 values, one per thread; *total: their sum.  Not scan_dev.h's: k_je_ffcount and k_je_stuff scan the FF counts of
+// one chunk inside the workgroup that holds the chunk and never leave it
 __device__ inline uint64_t wg_excl_scan(uint64_t v, uint64_t* s_buf /*[JE_TPB]*/, uint64_t* total) {
     const int t = threadIdx.x;
     s_buf[t] = v;
@@ -54,64 +56,13 @@ __device__ inline uint64_t wg_excl_scan(uint64_t v, uint64_t* s_buf /*[JE_TPB]*/
     return incl - v;
 }
 
-__global__ __launch_bounds__(JE_TPB) void k_scan_tiles(const uint32_t* __restrict__ in, int64_t n, uint64_t* __restrict__ part) {
-    __shared__ uint64_t s_buf[JE_TPB];
-    const int64_t i0 = ((int64_t)blockIdx.x * JE_TPB + threadIdx.x) * JE_ITEMS;
-    uint64_t v = 0;
-    for (int k = 0; k < JE_ITEMS; ++k) v += i0 + k < n ? in[i0 + k] : 0u;
-    uint64_t total;
-    wg_excl_scan(v, s_buf, &total);
-    if (threadIdx.x == 0) part[blockIdx.x] = total;
-}
-// ONE workgroup: part[0 .. nb) -> its exclusive scan, part[nb] = the sum
-__global__ __launch_bounds__(JE_TPB) void k_scan_top(uint64_t* __restrict__ part, int64_t nb) {
-    __shared__ uint64_t s_buf[JE_TPB];
-    uint64_t carry = 0;
-    for (int64_t c0 = 0; c0 < nb; c0 += JE_TPB) {
-        const int64_t i = c0 + threadIdx.x;
-        const uint64_t v = i < nb ? part[i] : 0;
-        uint64_t total;
-        const uint64_t ex = wg_excl_scan(v, s_buf, &total);
-        if (i < nb) part[i] = carry + ex;
-        carry += total;
-    }
-    if (threadIdx.x == 0) part[nb] = carry;
-}
-__global__ __launch_bounds__(JE_TPB) void k_scan_apply(const uint32_t* __restrict__ in, int64_t n, const uint64_t* __restrict__ part, int64_t nb,
-                                                       uint64_t* __restrict__ out) {
-    __shared__ uint64_t s_buf[JE_TPB];
-    const int64_t i0 = ((int64_t)blockIdx.x * JE_TPB + threadIdx.x) * JE_ITEMS;
-    uint32_t x[JE_ITEMS];
-    uint64_t v = 0;
-    for (int k = 0; k < JE_ITEMS; ++k) { x[k] = i0 + k < n ? in[i0 + k] : 0u; v += x[k]; }
-    uint64_t total;
-    uint64_t at = part[blockIdx.x] + wg_excl_scan(v, s_buf, &total);
-    for (int k = 0; k < JE_ITEMS; ++k) {
-        if (i0 + k < n) out[i0 + k] = at;
-        at += x[k];
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) out[n] = part[nb];
-}
-// out[0 .. n] = the exclusive scan of in[0 .. n), out[n] the sum; part: (n + JE_TILE - 1) / JE_TILE + 1 words of workspace
-void scan_u64(const uint32_t* in, int64_t n, uint64_t* out, uint64_t* part, hipStream_t s) {
-    const int64_t nb = (n + JE_TILE - 1) / JE_TILE;
-    k_scan_tiles<<<dim3((unsigned)nb), dim3(JE_TPB), 0, s>>>(in, n, part);
-    k_scan_top<<<dim3(1), dim3(JE_TPB), 0, s>>>(part, nb);
-    k_scan_apply<<<dim3((unsigned)nb), dim3(JE_TPB), 0, s>>>(in, n, part, nb, out);
-}
 
 // ------------------------------------------------------------------ transform ----
 __global__ __launch_bounds__(64) void k_je_transform(JeCall cl, const uint16_t* __restrict__ quant /*[2][64]*/, int16_t* __restrict__ coef) {
     const JpegLayout& L = cl.L;
-    int64_t b = (int64_t)blockIdx.x * 64 + threadIdx.x;
-    int c = 0;
-    for (; c < L.ncomp; ++c) {
-        const int64_t nb = (int64_t)L.bw[c] * L.bh[c];
-        if (b < nb) break;
-        b -= nb;
-    }
-    if (c >= L.ncomp) return;
-    const int by = (int)(b / L.bw[c]), bx = (int)(b % L.bw[c]);
+    int c, bx, by;
+    int64_t k;
+    if (!jpeg_plane_block(L, (int64_t)blockIdx.x * 64 + threadIdx.x, &c, &bx, &by, &k)) return;
     union { int16_t v[64]; uint4 q[8]; } blk;
     if (jpeg_enc_dummy(L, c, bx, by)) {
         for (int k = 0; k < 8; ++k) blk.q[k] = make_uint4(0u, 0u, 0u, 0u);
@@ -120,20 +71,21 @@ __global__ __launch_bounds__(64) void k_je_transform(JeCall cl, const uint16_t* 
         px.px += (int64_t)blockIdx.y * cl.img_bytes;
         jpeg_enc_block(L, px, c, bx, by, quant + (c ? 64 : 0), blk.v);
     }
-    uint4* o = (uint4*)(coef + (int64_t)blockIdx.y * cl.n_coef + L.coef[c] + 64 * b);
+    uint4* o = (uint4*)(coef + (int64_t)blockIdx.y * cl.n_coef + L.coef[c] + 64 * k);
     for (int k = 0; k < 8; ++k) o[k] = blk.q[k];
 }
 
 // ------------------------------------------------------------------ entropy ----
 // scan block j of the call -> its image, and through blk / pred / c what jpeg_enc_block_bits takes
-struct JeBlock { const int16_t* blk; int32_t pred; int c; int64_t jj; };
+struct JeBlock { const int16_t* blk; int32_t pred; int c; int jj; };
 __device__ inline JeBlock je_block(const JeCall& cl, const int16_t* __restrict__ coef, int64_t j) {
-    const int64_t img = j / cl.nblk, jj = j % cl.nblk;
+    const int64_t img = j / cl.nblk;
+    const int jj = (int)(j % cl.nblk);
     const int16_t* ic = coef + img * cl.n_coef;
     int c, bx, by, m;
-    jpeg_enc_scan_block(cl.L, jj, &c, &bx, &by, &m);
+    jpeg_scan_block(cl.L, jj, &c, &bx, &by, &m);
     if (jpeg_enc_dummy(cl.L, c, bx, by)) return JeBlock{nullptr, 0, c, jj};
-    return JeBlock{ic + cl.L.coef[c] + 64 * ((int64_t)by * cl.L.bw[c] + bx), jpeg_enc_pred(cl.L, ic, jj, c, cl.per), c, jj};
+    return JeBlock{ic + jpeg_block_at(cl.L, c, bx, by), jpeg_enc_pred(cl.L, ic, jj, c, cl.per), c, jj};
 }
 
 __global__ __launch_bounds__(JE_TPB) void k_je_bits(JeCall cl, const JpegEncTables* __restrict__ T, const int16_t* __restrict__ coef,
@@ -149,7 +101,7 @@ __global__ __launch_bounds__(JE_TPB) void k_je_bits(JeCall cl, const JpegEncTabl
 // first and one-past-last scan block (of the call) of interval t (of the call)
 __device__ inline void je_interval(const JeCall& cl, int64_t t, int64_t* a, int64_t* b) {
     const int64_t img = t / cl.nint, tl = t % cl.nint;
-    const int64_t bpm = cl.nblk / ((int64_t)cl.L.mcux * cl.L.mcuy);
+    const int64_t bpm = jpeg_blocks_per_mcu(cl.L);
     const int64_t first = tl * cl.per * bpm, end = first + (int64_t)cl.per * bpm;
     *a = img * cl.nblk + first;
     *b = img * cl.nblk + (end < cl.nblk ? end : cl.nblk);
@@ -189,8 +141,7 @@ __global__ __launch_bounds__(JE_TPB) void k_je_write(JeCall cl, const JpegEncTab
     const int64_t j = (int64_t)blockIdx.x * JE_TPB + threadIdx.x;
     if (j >= cl.nblk * cl.n) return;
     const JeBlock B = je_block(cl, coef, j);
-    const int64_t bpm = cl.nblk / ((int64_t)cl.L.mcux * cl.L.mcuy);
-    const int64_t t = j / cl.nblk * cl.nint + B.jj / ((int64_t)cl.per * bpm);
+    const int64_t t = j / cl.nblk * cl.nint + B.jj / ((int64_t)cl.per * jpeg_blocks_per_mcu(cl.L));
     int64_t a, b;
     je_interval(cl, t, &a, &b);
     JeBitWriter w{raw, 8u * ibyte_at[t] + (bit_at[j] - bit_at[a]), 0u};
@@ -297,8 +248,6 @@ __global__ __launch_bounds__(JE_TPB) void k_dp_write(const float* __restrict__ d
 }
 
 // ------------------------------------------------------------------ host ----
-double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
 struct JePlan {
     JpegEncShape S;
     JpegEncTables T;
@@ -331,6 +280,13 @@ int je_plan(const char* fn, int32_t n, int32_t w, int32_t h, uint32_t flags, con
     return MVS_OK;
 }
 
+// E9: the streams of a call against the caller's capacity
+int je_fits(const char* fn, int64_t total, int64_t capacity) {
+    if (total <= capacity) return MVS_OK;
+    mvs_set_error("%s: the streams take %lld bytes, capacity is %lld (offsets is written)", fn, (long long)total, (long long)capacity);
+    return MVS_E_INVALID_ARG;
+}
+
 struct JeCoef { Scratch tab, coef; };
 // the transform launch on the pixels at imgs_dev
 int je_transform(JePlan& pl, const uint8_t* imgs_dev, JeCoef* c, hipStream_t s) {
@@ -352,24 +308,19 @@ int je_run(const char* fn, JePlan& pl, const uint8_t* imgs_dev, int64_t* offsets
     const int64_t N = cl0.nblk * cl0.n, NI = cl0.n_int;
     JeCoef c;
     Scratch dbits, dbit_at, dpart, dpart2, dibytes, dibyte_at, draw, dcnt, dff_at, doff, dhdr;
+    StageClock clk(ms != nullptr);
     int rc;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    if (ms) {
-        for (auto& e : ev) HIPCHK(hipEventCreate(&e));
-        HIPCHK(hipEventRecord(ev[0], s));
-    }
-    if ((rc = je_transform(pl, imgs_dev, &c, s))) return rc;
+    if ((rc = clk.mark(s)) || (rc = je_transform(pl, imgs_dev, &c, s)) || (rc = clk.mark(s))) return rc;
     const JeCall& cl = pl.cl;
-    if (ms) HIPCHK(hipEventRecord(ev[1], s));
     if ((rc = dbits.alloc(4 * (size_t)N, s)) || (rc = dbit_at.alloc(8 * (size_t)(N + 1), s)) ||
         (rc = dpart.alloc(8 * (size_t)((N + JE_TILE - 1) / JE_TILE + 2), s)) || (rc = dibytes.alloc(4 * (size_t)NI, s)) ||
         (rc = dibyte_at.alloc(8 * (size_t)(NI + 1), s)) || (rc = doff.alloc(8 * (size_t)(cl.n + 1), s)) ||
         (rc = up_async(dhdr, pl.hdr.data(), pl.hdr.size(), s))) return rc;
     const JpegEncTables* T = c.tab.as<JpegEncTables>();
     k_je_bits<<<dim3((unsigned)((N + JE_TPB - 1) / JE_TPB)), dim3(JE_TPB), 0, s>>>(cl, T, c.coef.as<int16_t>(), dbits.as<uint32_t>());
-    scan_u64(dbits.as<uint32_t>(), N, dbit_at.as<uint64_t>(), dpart.as<uint64_t>(), s);
+    scan_exclusive_async(dbits.as<uint32_t>(), N, dbit_at.as<uint64_t>(), dpart.as<uint64_t>(), s);
     k_je_intervals<<<dim3((unsigned)((NI + JE_TPB - 1) / JE_TPB)), dim3(JE_TPB), 0, s>>>(cl, dbit_at.as<uint64_t>(), dibytes.as<uint32_t>());
-    scan_u64(dibytes.as<uint32_t>(), NI, dibyte_at.as<uint64_t>(), dpart.as<uint64_t>(), s);
+    scan_exclusive_async(dibytes.as<uint32_t>(), NI, dibyte_at.as<uint64_t>(), dpart.as<uint64_t>(), s);
     uint64_t raw_bytes = 0;                                           // the unstuffed bytes of the call: the buffer is sized from them
     HIPCHK(hipMemcpyAsync(&raw_bytes, dibyte_at.as<uint64_t>() + NI, 8, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
@@ -380,36 +331,25 @@ int je_run(const char* fn, JePlan& pl, const uint8_t* imgs_dev, int64_t* offsets
     HIPCHK(hipMemsetAsync(draw.p, 0, raw_alloc, s));
     k_je_write<<<dim3((unsigned)((N + JE_TPB - 1) / JE_TPB)), dim3(JE_TPB), 0, s>>>(cl, T, c.coef.as<int16_t>(), dbit_at.as<uint64_t>(),
                                                                                      dibyte_at.as<uint64_t>(), draw.as<uint32_t>());
-    if (ms) HIPCHK(hipEventRecord(ev[2], s));
+    if ((rc = clk.mark(s))) return rc;
     k_je_ffcount<<<dim3((unsigned)nchunk), dim3(JE_TPB), 0, s>>>(draw.as<uint32_t>(), dibyte_at.as<uint64_t>(), NI, dcnt.as<uint32_t>());
-    scan_u64(dcnt.as<uint32_t>(), nchunk, dff_at.as<uint64_t>(), dpart2.as<uint64_t>(), s);
+    scan_exclusive_async(dcnt.as<uint32_t>(), nchunk, dff_at.as<uint64_t>(), dpart2.as<uint64_t>(), s);
     k_je_offsets<<<dim3((unsigned)cl.n), dim3(64), 0, s>>>(cl, draw.as<uint8_t>(), dibyte_at.as<uint64_t>(), dff_at.as<uint64_t>(), doff.as<int64_t>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(offsets, doff.p, 8 * (size_t)(cl.n + 1), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     const int64_t total = offsets[cl.n];
-    if (data_dev && total > capacity) {
-        mvs_set_error("%s: the streams take %lld bytes, capacity is %lld (offsets is written)", fn, (long long)total, (long long)capacity);
-        return MVS_E_INVALID_ARG;
-    }
+    if (data_dev && (rc = je_fits(fn, total, capacity))) return rc;
     if (!data_dev) {
         if ((rc = own->alloc((size_t)total, s))) return rc;
         data_dev = own->as<uint8_t>();
     }
     k_je_stuff<<<dim3((unsigned)nchunk), dim3(JE_TPB), 0, s>>>(cl, draw.as<uint32_t>(), dibyte_at.as<uint64_t>(), dff_at.as<uint64_t>(), data_dev);
     k_je_headers<<<dim3((unsigned)cl.n), dim3(JE_TPB), 0, s>>>(dhdr.as<uint8_t>(), cl.hdr, doff.as<int64_t>(), data_dev);
-    if (ms) HIPCHK(hipEventRecord(ev[3], s));
+    if ((rc = clk.mark(s))) return rc;
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
-    if (ms) {
-        for (int k = 0; k < 3; ++k) {
-            float f = 0.f;
-            HIPCHK(hipEventElapsedTime(&f, ev[k], ev[k + 1]));
-            ms[k] = f;
-        }
-        for (auto& e : ev) (void)hipEventDestroy(e);
-    }
-    return MVS_OK;
+    return ms ? clk.read(ms) : MVS_OK;
 }
 
 int je_check_ptrs(const char* fn, const void* imgs, const void* out) {
@@ -447,19 +387,41 @@ int dp_check(const char* fn, int32_t n, int32_t w, int32_t h, const void* depths
     return MVS_OK;
 }
 
+// the host forms under the name fn: E1, the entry's own pointer check (ptrs: NULL, or what it found wrong), the call on an upload of
+// imgs; the streams end in `dout`, a device block of offsets[n] bytes
+int je_host(const char* fn, int32_t n, int32_t w, int32_t h, const uint8_t* imgs, uint32_t flags, const mvs_jpeg_encode_params* p, const char* ptrs,
+            int64_t* offsets, Scratch* dout) {
+    JePlan pl;
+    int rc = je_plan(fn, n, w, h, flags, p, &pl);
+    if (rc) return rc;
+    if (ptrs) return bad(fn, ptrs);
+    if ((rc = need_device())) return rc;
+    Scratch dimg;                                                     // the device block is sized from the streams, not from a capacity
+    if ((rc = up(dimg, imgs, (size_t)pl.cl.img_bytes * (size_t)n))) return rc;
+    return je_run(fn, pl, dimg.as<uint8_t>(), offsets, nullptr, 0, dout, nullptr, nullptr);
+}
+
+// mvs_jpeg_encode_dev under the name fn; ms (NULL: not timed): E1, then je_run's three, in milliseconds
+int je_dev(const char* fn, int32_t n, int32_t w, int32_t h, const uint8_t* imgs_dev, uint32_t flags, const mvs_jpeg_encode_params* p, int64_t* offsets,
+           uint8_t* data_dev, int64_t capacity, void* hip_stream, double* ms) {
+    JePlan pl;
+    const double t0 = now_ms();
+    int rc = je_plan(fn, n, w, h, flags, p, &pl);
+    if (ms) ms[0] = now_ms() - t0;
+    if (rc) return rc;
+    if (!imgs_dev || !offsets || !data_dev || capacity < 0) return bad(fn, "imgs_dev, offsets or data_dev is NULL, or capacity is negative");
+    if ((rc = need_device())) return rc;
+    return je_run(fn, pl, imgs_dev, offsets, data_dev, capacity, nullptr, (hipStream_t)hip_stream, ms ? ms + 1 : nullptr);
+}
+
 }  // namespace
 
 // mvs_jpeg_encode's host form under the name fn with an output that sizes itself: data receives offsets[n] bytes
 int jpeg_encode_host(const char* fn, int32_t n, int32_t w, int32_t h, const uint8_t* imgs, uint32_t flags, const mvs_jpeg_encode_params* p,
                      int64_t* offsets, std::vector<uint8_t>* data) {
-    JePlan pl;
-    int rc = je_plan(fn, n, w, h, flags, p, &pl);
+    Scratch dout;
+    int rc = je_host(fn, n, w, h, imgs, flags, p, !imgs || !offsets ? "imgs or offsets is NULL" : nullptr, offsets, &dout);
     if (rc) return rc;
-    if (!imgs || !offsets) return bad(fn, "imgs or offsets is NULL");
-    if ((rc = need_device())) return rc;
-    Scratch dimg, dout;
-    if ((rc = up(dimg, imgs, (size_t)pl.cl.img_bytes * (size_t)n)) || (rc = je_run(fn, pl, dimg.as<uint8_t>(), offsets, nullptr, 0, &dout, nullptr, nullptr)))
-        return rc;
     data->resize((size_t)offsets[n]);
     return down(data->data(), dout, data->size());
 }
@@ -488,43 +450,23 @@ int64_t mvs_jpeg_encode_bound(int32_t w, int32_t h, uint32_t flags, const mvs_jp
 int mvs_jpeg_encode(int32_t n, int32_t w, int32_t h, const uint8_t* imgs, uint32_t flags, const mvs_jpeg_encode_params* p, int64_t* offsets,
                     uint8_t* data, int64_t capacity) {
     MVS_TRACE();
-    JePlan pl;
-    int rc = je_plan(__func__, n, w, h, flags, p, &pl);
-    if (rc) return rc;
-    if (!imgs || !offsets || (!data && capacity > 0) || capacity < 0) return bad(__func__, "imgs, offsets or data is NULL, or capacity is negative");
-    if ((rc = need_device())) return rc;
-    Scratch dimg, dout;                                               // the device block is sized from the streams, not from capacity
-    if ((rc = up(dimg, imgs, (size_t)pl.cl.img_bytes * (size_t)n)) ||
-        (rc = je_run(__func__, pl, dimg.as<uint8_t>(), offsets, nullptr, 0, &dout, nullptr, nullptr))) return rc;
-    if (offsets[n] > capacity) {
-        mvs_set_error("%s: the streams take %lld bytes, capacity is %lld (offsets is written)", __func__, (long long)offsets[n], (long long)capacity);
-        return MVS_E_INVALID_ARG;
-    }
+    const bool ptrs = !imgs || !offsets || (!data && capacity > 0) || capacity < 0;
+    Scratch dout;
+    int rc = je_host(__func__, n, w, h, imgs, flags, p, ptrs ? "imgs, offsets or data is NULL, or capacity is negative" : nullptr, offsets, &dout);
+    if (rc || (rc = je_fits(__func__, offsets[n], capacity))) return rc;
     return down(data, dout, (size_t)offsets[n]);
 }
 
 int mvs_jpeg_encode_dev(int32_t n, int32_t w, int32_t h, const uint8_t* imgs_dev, uint32_t flags, const mvs_jpeg_encode_params* p,
                         int64_t* offsets, uint8_t* data_dev, int64_t capacity, void* hip_stream) {
     MVS_TRACE();
-    JePlan pl;
-    int rc = je_plan(__func__, n, w, h, flags, p, &pl);
-    if (rc) return rc;
-    if (!imgs_dev || !offsets || !data_dev || capacity < 0) return bad(__func__, "imgs_dev, offsets or data_dev is NULL, or capacity is negative");
-    if ((rc = need_device())) return rc;
-    return je_run(__func__, pl, imgs_dev, offsets, data_dev, capacity, nullptr, (hipStream_t)hip_stream, nullptr);
+    return je_dev(__func__, n, w, h, imgs_dev, flags, p, offsets, data_dev, capacity, hip_stream, nullptr);
 }
 
 int mvs_test_jpeg_encode_timed(int32_t n, int32_t w, int32_t h, const uint8_t* imgs_dev, uint32_t flags, const mvs_jpeg_encode_params* p,
                                int64_t* offsets, uint8_t* data_dev, int64_t capacity, void* hip_stream, double* ms) {
     if (!ms) return bad(__func__, "ms is NULL");
-    JePlan pl;
-    const double t0 = now_ms();
-    int rc = je_plan(__func__, n, w, h, flags, p, &pl);
-    ms[0] = now_ms() - t0;
-    if (rc) return rc;
-    if (!imgs_dev || !offsets || !data_dev || capacity < 0) return bad(__func__, "imgs_dev, offsets or data_dev is NULL, or capacity is negative");
-    if ((rc = need_device())) return rc;
-    return je_run(__func__, pl, imgs_dev, offsets, data_dev, capacity, nullptr, (hipStream_t)hip_stream, ms + 1);
+    return je_dev(__func__, n, w, h, imgs_dev, flags, p, offsets, data_dev, capacity, hip_stream, ms);
 }
 
 int mvs_jpeg_roundtrip(int32_t n, int32_t w, int32_t h, const uint8_t* imgs, uint32_t flags, const mvs_jpeg_encode_params* p, uint8_t* out) {

@@ -1,6 +1,7 @@
 // jpeg_enc_rules.h — rules E1-E9 of include/mvs.h (the baseline JPEG encoder): the per-sample and per-symbol rules as one
-// __host__ __device__ body — the colour of E2, the sample of E3, the two passes of E4, the quantiser of E5, the scan order and the dummy
-// blocks of E6, one block of E7 into a bit sink — and the host parts: the tables of E5 / E7, the header of E8, the bound of E9.  The
+// __host__ __device__ body — the colour of E2, the sample of E3, the two passes of E4, the quantiser of E5, the dummy blocks and the DC
+// predecessor of E6, one block of E7 into a bit sink — and the host parts: the tables of E5 / E7, the header of E8, the bound of E9.
+// The scan order of E6 (jpeg_scan_block), the plane order and jpeg_enc_layout are in jpeg_rules.h, stated once for both directions.  The
 // kernels of jpeg_enc.hip run this body; tests/jpeg_enc_rules.cpp runs it as a host program of its own, tests/ref_jpeg_enc.py restates it
 // operation for operation.  All arithmetic is int32_t; a right shift of a signed value is the arithmetic one.
 #ifndef MVS_JPEG_ENC_RULES_H_
@@ -108,24 +109,14 @@ __host__ __device__ inline void jpeg_enc_block(const JpegLayout& L, const JpegEn
 __host__ __device__ inline bool jpeg_enc_dummy(const JpegLayout& L, int c, int bx, int by) {
     return bx >= (L.cw[c] + 7) / 8 || by >= (L.ch[c] + 7) / 8;
 }
-// block j of an image's scan (MCUs row-major; luma v x h blocks row-major, then Cb, then Cr) -> component and block position
-__host__ __device__ inline void jpeg_enc_scan_block(const JpegLayout& L, int64_t j, int* c, int* bx, int* by, int* mcu) {
-    const int b0 = L.hs[0] * L.vs[0], bpm = L.ncomp == 1 ? 1 : b0 + 2;
-    const int m = (int)(j / bpm), k = (int)(j % bpm);
-    const int cc = k < b0 ? 0 : k - b0 + 1, kk = k < b0 ? k : 0;
-    *c = cc; *mcu = m;
-    *bx = m % L.mcux * L.hs[cc] + kk % L.hs[cc];
-    *by = m / L.mcux * L.vs[cc] + kk / L.hs[cc];
-}
 // the DC predictor of scan block j (component c): the DC of the last real block of c in front of it inside its restart interval of
 // `per` MCUs, 0 without one.  coef: the image's blocks as JpegLayout places them
-__host__ __device__ inline int32_t jpeg_enc_pred(const JpegLayout& L, const int16_t* coef, int64_t j, int c, int per) {
-    const int b0 = L.hs[0] * L.vs[0], bpm = L.ncomp == 1 ? 1 : b0 + 2;
-    const int64_t first = j / bpm / per * per * bpm;                 // the interval's first block
-    for (int64_t q = j - 1; q >= first; --q) {
+__host__ __device__ inline int32_t jpeg_enc_pred(const JpegLayout& L, const int16_t* coef, int j, int c, int per) {
+    const int bpm = jpeg_blocks_per_mcu(L), first = j / bpm / per * per * bpm;   // the interval's first block
+    for (int q = j - 1; q >= first; --q) {
         int cc, bx, by, m;
-        jpeg_enc_scan_block(L, q, &cc, &bx, &by, &m);
-        if (cc == c && !jpeg_enc_dummy(L, c, bx, by)) return coef[L.coef[c] + 64 * ((int64_t)by * L.bw[c] + bx)];
+        jpeg_scan_block(L, q, &cc, &bx, &by, &m);
+        if (cc == c && !jpeg_enc_dummy(L, c, bx, by)) return coef[jpeg_block_at(L, c, bx, by)];
     }
     return 0;
 }
@@ -214,15 +205,6 @@ inline void jpeg_enc_make_tables(int quality, JpegEncTables* T) {
     }
     jpeg_enc_quant_table(K1, quality, T->quant[0]);
     jpeg_enc_quant_table(K2, quality, T->quant[1]);
-}
-
-// the layout of a W x H image of ncomp components with luma sampling hmax x vmax, blocks and planes from 0
-inline JpegLayout jpeg_enc_layout(int w, int h, int ncomp, int hmax, int vmax, int64_t* n_coef) {
-    JpegHeader H;
-    H.w = w; H.h = h; H.ncomp = ncomp;
-    if (ncomp == 3) { H.hs[0] = hmax; H.vs[0] = vmax; }
-    int64_t np = 0;
-    return jpeg_layout(H, 0, 0, n_coef, &np);
 }
 
 // E8: everything in front of the scan; restart: the interval in MCUs as DRI states it (0: no DRI)

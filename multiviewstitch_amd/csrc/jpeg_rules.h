@@ -1,8 +1,9 @@
 // jpeg_rules.h — rules J1-J8 of include/mvs.h (the baseline JPEG decoder): the header walk and the segment table (J1, J2: host code), and
 // the per-symbol and per-sample rules as one __host__ __device__ body: the bit reader, the Huffman symbol and one block of J3, the two
-// passes of J4, the chroma sample of J5 and the colour of J6, J7.  The kernels of jpeg.hip run this body; tests/jpeg_rules.cpp runs it
-// as a host program of its own, tests/ref_jpeg.py restates it operation for operation.  All arithmetic of J4 is uint32_t (32-bit
-// two's-complement wrapping); a right shift of a signed value is the arithmetic one.
+// passes of J4, the chroma sample of J5 and the colour of J6, J7, and the two walks over an image's blocks (scan order, plane order),
+// which the encoder shares.  The kernels of jpeg.hip run this body; tests/jpeg_rules.cpp runs it as a host program of its own,
+// tests/ref_jpeg.py restates it operation for operation.  All arithmetic of J4 is uint32_t (32-bit two's-complement wrapping); a right
+// shift of a signed value is the arithmetic one.
 #ifndef MVS_JPEG_RULES_H_
 #define MVS_JPEG_RULES_H_
 #include <stdint.h>
@@ -138,10 +139,46 @@ __host__ __device__ inline int jpeg_decode_block(JpegBits<Bytes>& b, const JpegH
     return 0;
 }
 
-// the block of component c that MCU m holds at (i, j) of its hs x vs blocks
-__host__ __device__ inline int64_t jpeg_block_of(const JpegLayout& L, int c, int m, int i, int j) {
-    const int my = m / L.mcux, mx = m % L.mcux;
-    return (int64_t)(my * L.vs[c] + j) * L.bw[c] + mx * L.hs[c] + i;
+// ---------------------------------------------------------------- the two walks over an image's blocks ----
+// Scan order (J3, E6): MCUs row-major; inside an MCU the luma blocks vs x hs row-major, then Cb, then Cr.  An image has at most
+// 3 * 8192 * 8192 blocks (w, h <= 65535), so a block of its scan is an int.
+__host__ __device__ inline int jpeg_blocks_per_mcu(const JpegLayout& L) {
+    const int b0 = L.hs[0] * L.vs[0];
+    return L.ncomp == 1 ? 1 : b0 + 2;
+}
+// block j of the scan -> its MCU, its component and its place (bx, by) among the component's bw x bh blocks
+__host__ __device__ inline void jpeg_scan_block(const JpegLayout& L, int j, int* c, int* bx, int* by, int* mcu) {
+    const int bpm = jpeg_blocks_per_mcu(L), b0 = L.hs[0] * L.vs[0];
+    const int m = j / bpm, k = j % bpm;
+    const int cc = k < b0 ? 0 : k - b0 + 1, kk = k < b0 ? k : 0;
+    *c = cc; *mcu = m;
+    *bx = m % L.mcux * L.hs[cc] + kk % L.hs[cc];
+    *by = m / L.mcux * L.vs[cc] + kk / L.hs[cc];
+}
+// Plane order (J4, E4): component by component, a component's blocks row-major.  Block b of the padded planes -> its component and
+// k = by * bw + bx (false behind the last block); k -> its place.  Two steps: k_jpeg_idct addresses its block through k and takes the
+// place, a 64-bit division, behind pass 1, whose loads then do not wait for it
+__host__ __device__ inline bool jpeg_plane_find(const JpegLayout& L, int64_t b, int* c, int64_t* k) {
+    int cc = 0;
+    for (; cc < L.ncomp; ++cc) {
+        const int64_t nb = (int64_t)L.bw[cc] * L.bh[cc];
+        if (b < nb) break;
+        b -= nb;
+    }
+    *c = cc; *k = b;
+    return cc < L.ncomp;
+}
+__host__ __device__ inline void jpeg_plane_place(const JpegLayout& L, int c, int64_t k, int* bx, int* by) {
+    *by = (int)(k / L.bw[c]); *bx = (int)(k % L.bw[c]);
+}
+__host__ __device__ inline bool jpeg_plane_block(const JpegLayout& L, int64_t b, int* c, int* bx, int* by, int64_t* k) {
+    if (!jpeg_plane_find(L, b, c, k)) return false;
+    jpeg_plane_place(L, *c, *k, bx, by);
+    return true;
+}
+// first int16 of block (bx, by) of component c in the coefficient array
+__host__ __device__ inline int64_t jpeg_block_at(const JpegLayout& L, int c, int bx, int by) {
+    return L.coef[c] + 64 * ((int64_t)by * L.bw[c] + bx);
 }
 
 // ---------------------------------------------------------------- J4 ----
@@ -280,6 +317,15 @@ inline JpegLayout jpeg_layout(const JpegHeader& H, int64_t coef0, int64_t plane0
     }
     *n_coef = nc; *n_plane = np;
     return L;
+}
+
+// the layout of a W x H image of ncomp components with luma sampling hmax x vmax (what the encoder makes), blocks and planes from 0
+inline JpegLayout jpeg_enc_layout(int w, int h, int ncomp, int hmax, int vmax, int64_t* n_coef) {
+    JpegHeader H;
+    H.w = w; H.h = h; H.ncomp = ncomp;
+    if (ncomp == 3) { H.hs[0] = hmax; H.vs[0] = vmax; }
+    int64_t np = 0;
+    return jpeg_layout(H, 0, 0, n_coef, &np);
 }
 
 // J1, J2: reads nothing past len; false with H->why set

@@ -25,6 +25,14 @@ from .deformation import _stats, default_params
 
 
 # ------------------------------------------------------------------ helpers ----
+def _stream_order(stream):
+    """the context in which torch allocates and frees in the order of the caller's HIP stream (0 or None: torch's current stream)"""
+    if not stream:
+        return contextlib.nullcontext()
+    import torch
+    return torch.cuda.stream(torch.cuda.ExternalStream(int(stream)))
+
+
 def _is_dev(a):
     return hasattr(a, "data_ptr")
 
@@ -177,11 +185,9 @@ def RunPointSample(cameras, depths, params: L.CPointSampleParams | None = None, 
                 raise L.MvsError(-1, f"depths[{k}] must be [frames, h, w] = {want}")
     soff = np.zeros(n + 1, np.int64)
     dev = whole or (n > 0 and all(_is_dev(d) for d in depths))
-    order = contextlib.nullcontext()
+    order = _stream_order(stream) if dev else contextlib.nullcontext()
     if dev:
         import torch
-        if stream:
-            order = torch.cuda.stream(torch.cuda.ExternalStream(int(stream)))
     r = max(1, int(prm.pt_samp_rds))
     cap = int(capacity) if capacity is not None else sum(2 * (-(-int(c[0].w) // r)) * (-(-int(c[0].h) // r)) for c in cameras if len(c))
     with order:
@@ -628,11 +634,9 @@ def _run_poisson(points, normals, prm, dprm, stream, capacity, sprm=None):
     dev = _is_dev(points)
     if dev != _is_dev(normals):
         raise L.MvsError(-1, "points and normals must both be tensors on the GPU or both arrays")
-    order = contextlib.nullcontext()
+    order = _stream_order(stream) if dev else contextlib.nullcontext()
     if dev:
         import torch
-        if stream:
-            order = torch.cuda.stream(torch.cuda.ExternalStream(int(stream)))
         if tuple(points.shape) != tuple(normals.shape) or points.dim() != 2 or points.shape[1] != 3:
             raise L.MvsError(-1, "points and normals must be [n, 3]")
         pp, pn, n = _dev_ptr(points, "float64", "points"), _dev_ptr(normals, "float64", "normals"), int(points.shape[0])
@@ -740,11 +744,9 @@ def _run_poisson_band(points, normals, prm, bprm, dprm, stream, capacity, sprm=N
     dev = _is_dev(points)
     if dev != _is_dev(normals):
         raise L.MvsError(-1, "points and normals must both be tensors on the GPU or both arrays")
-    order = contextlib.nullcontext()
+    order = _stream_order(stream) if dev else contextlib.nullcontext()
     if dev:
         import torch
-        if stream:
-            order = torch.cuda.stream(torch.cuda.ExternalStream(int(stream)))
         if tuple(points.shape) != tuple(normals.shape) or points.dim() != 2 or points.shape[1] != 3:
             raise L.MvsError(-1, "points and normals must be [n, 3]")
         pp, pn, n = _dev_ptr(points, "float64", "points"), _dev_ptr(normals, "float64", "normals"), int(points.shape[0])
@@ -917,11 +919,9 @@ def TrimByValue(vertices, faces, values, threshold: float, normals=None, stream:
     dev = _is_dev(vertices)
     if any(_is_dev(a) != dev for a in (faces, values)) or (normals is not None and _is_dev(normals) != dev):
         raise L.MvsError(-1, "vertices, faces, values and normals must all be tensors on the GPU or all arrays")
-    order = contextlib.nullcontext()
+    order = _stream_order(stream) if dev else contextlib.nullcontext()
     if dev:
         import torch
-        if stream:
-            order = torch.cuda.stream(torch.cuda.ExternalStream(int(stream)))
         ptrs = [_dev_ptr(vertices, "float64", "vertices"), _dev_ptr(normals, "float64", "normals"), _dev_ptr(faces, "int32", "faces"),
                 _dev_ptr(values, "float64", "values")]
         V, F = int(vertices.shape[0]), int(faces.shape[0])
@@ -1072,10 +1072,7 @@ def RefineAllDepthMaps(cameras, imgs, depths, params: L.CDepthRefineParams | Non
     dev = n > 0 and all(_is_dev(a) for a in depths) and all(_is_dev(a) for a in imgs)
     if not dev and (any(_is_dev(a) for a in depths) or any(_is_dev(a) for a in imgs)):
         raise L.MvsError(-1, "imgs and depths must all be tensors on the GPU or all arrays")
-    order = contextlib.nullcontext()
-    if dev and stream:
-        import torch
-        order = torch.cuda.stream(torch.cuda.ExternalStream(int(stream)))
+    order = _stream_order(stream) if dev else contextlib.nullcontext()
     with order:
         fimg, iptr = _flat_stack(imgs, n, dev, "uint8", "imgs")
         fdep, dptr = _flat_stack(depths, n, dev, "float32", "depths")
@@ -1150,7 +1147,7 @@ def DecodeJpegs(datas, order: str = "BGR", device=None, stream: int | None = Non
         L.check(L.lib().mvs_jpeg_decode(n, L.ptr(off), L.ptr(blob), flags, L.ptr(out)))
         return out
     import torch
-    order_ctx = torch.cuda.stream(torch.cuda.ExternalStream(int(stream))) if stream else contextlib.nullcontext()
+    order_ctx = _stream_order(stream)
     with order_ctx:
         out = torch.empty(shape, dtype=torch.uint8, device=device)
         L.check(L.lib().mvs_jpeg_decode_dev(n, L.ptr(off), L.ptr(blob), flags, L.ptr(out), L.ptr(stream)))
@@ -1215,7 +1212,7 @@ def EncodeJpegs(imgs, quality: int = 95, sampling="420", restart_interval: int =
         finish(L.lib().mvs_jpeg_encode(n, w, h, L.ptr(imgs), flags, C.byref(prm), L.ptr(off), L.ptr(out), cap))
         return [out[off[i]:off[i + 1]].tobytes() for i in range(n)]
     import torch
-    order_ctx = torch.cuda.stream(torch.cuda.ExternalStream(int(stream))) if stream else contextlib.nullcontext()
+    order_ctx = _stream_order(stream)
     with order_ctx:
         src = imgs if _is_dev(imgs) else torch.as_tensor(L.arr(imgs, np.uint8)).to(device)
         out = torch.empty(max(1, cap), dtype=torch.uint8, device=src.device)
@@ -1237,7 +1234,7 @@ def JpegRoundTrip(imgs, quality: int = 95, sampling="420", restart_interval: int
         L.check(L.lib().mvs_jpeg_roundtrip(n, w, h, L.ptr(imgs), flags, C.byref(prm), L.ptr(out)))
         return out
     import torch
-    order_ctx = torch.cuda.stream(torch.cuda.ExternalStream(int(stream))) if stream else contextlib.nullcontext()
+    order_ctx = _stream_order(stream)
     with order_ctx:
         out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=imgs.device)
         L.check(L.lib().mvs_jpeg_roundtrip_dev(n, w, h, _dev_ptr(imgs, "uint8", "imgs"), flags, C.byref(prm), L.ptr(out), L.ptr(stream)))
@@ -1259,7 +1256,7 @@ def DepthPreview(depths, stream: int | None = None):
         L.check(L.lib().mvs_depth_preview(n, w, h, L.ptr(depths), L.ptr(out)))
         return out
     import torch
-    order_ctx = torch.cuda.stream(torch.cuda.ExternalStream(int(stream))) if stream else contextlib.nullcontext()
+    order_ctx = _stream_order(stream)
     with order_ctx:
         out = torch.empty((n, h, w), dtype=torch.uint8, device=depths.device)
         L.check(L.lib().mvs_depth_preview_dev(n, w, h, _dev_ptr(depths, "float32", "depths"), L.ptr(out), L.ptr(stream)))

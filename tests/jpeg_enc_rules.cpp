@@ -44,16 +44,16 @@ static int encode(const uint8_t* px, int w, int h, int chan, int rgb, int qualit
             for (int bx = 0; bx < L.bw[c]; ++bx)
                 if (!jpeg_enc_dummy(L, c, bx, by)) jpeg_enc_block(L, P, c, bx, by, T.quant[c ? 1 : 0], coef->data() + L.coef[c] + 64 * ((int64_t)by * L.bw[c] + bx));
     *out = jpeg_enc_header(w, h, S.ncomp, S.hmax, S.vmax, T, S.restart);
-    const int64_t bpm = S.nblk / S.nmcu;
+    const int64_t bpm = jpeg_blocks_per_mcu(L);
     for (int t = 0; t < S.nint; ++t) {
         ByteSink sink{out};
         const int64_t first = (int64_t)t * S.per * bpm, end = first + (int64_t)S.per * bpm < S.nblk ? first + (int64_t)S.per * bpm : S.nblk;
-        for (int64_t j = first; j < end; ++j) {
+        for (int j = (int)first; j < end; ++j) {
             int c, bx, by, m;
-            jpeg_enc_scan_block(L, j, &c, &bx, &by, &m);
+            jpeg_scan_block(L, j, &c, &bx, &by, &m);
             if (c < 0 || c >= L.ncomp || bx < 0 || bx >= L.bw[c] || by < 0 || by >= L.bh[c]) std::abort();
             const bool dummy = jpeg_enc_dummy(L, c, bx, by);
-            const int16_t* blk = dummy ? nullptr : coef->data() + L.coef[c] + 64 * ((int64_t)by * L.bw[c] + bx);
+            const int16_t* blk = dummy ? nullptr : coef->data() + jpeg_block_at(L, c, bx, by);
             JpegEncCount cnt;
             const int32_t pred = dummy ? 0 : jpeg_enc_pred(L, coef->data(), j, c, S.per);
             jpeg_enc_block_bits(blk, pred, T.dc[c ? 1 : 0], T.ac[c ? 1 : 0], cnt);

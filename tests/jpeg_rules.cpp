@@ -7,7 +7,10 @@
 // its exact length before it is walked, so a read past the stream is a sanitizer report.
 // out, per stream: int32 status (0 = MVS_OK, -10 = MVS_E_IO), int32 w, h, int64 n_coef, n_plane, then (status 0 only) w * h * 3 bytes R G B,
 // n_coef int16 (component by component, [block][64]) and n_plane bytes (component by component, padded planes).
+// Before that, the header walk of all streams runs on the host fan-out (csrc/host_parts.h, as jpeg_plan of jpeg.hip runs it) with 1 part
+// and with 4 parts; the two sets of headers must be identical.
 #include "jpeg_rules.h"
+#include "host_parts.h"
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -28,15 +31,15 @@ static int decode(const uint8_t* d, int64_t n, JpegHeader* H, std::vector<uint8_
     coef->assign((size_t)nc, 0);
     planes->assign((size_t)np, 0);
     int error = 0;
-    const int b0 = L.hs[0] * L.vs[0], bpm = L.ncomp == 1 ? 1 : b0 + 2;
+    const int bpm = jpeg_blocks_per_mcu(L);
     for (const JpegSeg& sg : H->segs) {
         JpegBits<HostBytes> bits{HostBytes{d, sg.first, sg.end}, sg.first, sg.end, 0u, 0};
         int32_t pred[3] = {0, 0, 0};
         int err = 0;
         for (int blk = 0; blk < sg.nmcu * bpm && !err; ++blk) {
-            const int m = sg.mcu0 + blk / bpm, k = blk % bpm;
-            const int c = k < b0 ? 0 : k - b0 + 1, kk = k < b0 ? k : 0;
-            int16_t* out = coef->data() + L.coef[c] + 64 * jpeg_block_of(L, c, m, kk % L.hs[c], kk / L.hs[c]);
+            int c, bx, by, m;
+            jpeg_scan_block(L, sg.mcu0 * bpm + blk, &c, &bx, &by, &m);
+            int16_t* out = coef->data() + jpeg_block_at(L, c, bx, by);
             if (out < coef->data() || out + 64 > coef->data() + nc) std::abort();
             err = jpeg_decode_block(bits, H->dc[c], H->ac[c], &pred[c], out);
             if (err) for (int i = 0; i < 64; ++i) out[i] = 0;
@@ -61,6 +64,28 @@ static int decode(const uint8_t* d, int64_t n, JpegHeader* H, std::vector<uint8_
     return 0;
 }
 
+static bool same_header(bool oka, const JpegHeader& a, bool okb, const JpegHeader& b) {
+    if (oka != okb || a.why != b.why) return false;
+    if (!oka) return true;
+    bool same = a.w == b.w && a.h == b.h && a.ncomp == b.ncomp && a.sof == b.sof && a.restart == b.restart && a.segs.size() == b.segs.size();
+    for (int c = 0; same && c < a.ncomp; ++c)
+        same = a.hs[c] == b.hs[c] && a.vs[c] == b.vs[c] && a.dc_id[c] == b.dc_id[c] && a.ac_id[c] == b.ac_id[c] &&
+               !memcmp(a.quant[c], b.quant[c], sizeof a.quant[c]) && !memcmp(&a.dc[c], &b.dc[c], sizeof(JpegHuff)) &&
+               !memcmp(&a.ac[c], &b.ac[c], sizeof(JpegHuff));
+    for (size_t k = 0; same && k < a.segs.size(); ++k) same = !memcmp(&a.segs[k], &b.segs[k], sizeof(JpegSeg));
+    return same;
+}
+
+// the header walk of every stream on `parts` threads, strided as jpeg_plan strides it
+static void walk_all(int parts, const std::vector<uint8_t*>& d, const std::vector<int64_t>& off, std::vector<JpegHeader>* hd, std::vector<char>* ok) {
+    const int n = (int)d.size();
+    hd->assign((size_t)n, JpegHeader());
+    ok->assign((size_t)n, 0);
+    parallel_parts(parts, [&](int t) {
+        for (int i = t; i < n; i += parts) (*ok)[(size_t)i] = jpeg_parse(d[(size_t)i], off[(size_t)i + 1] - off[(size_t)i], &(*hd)[(size_t)i]);
+    });
+}
+
 int main(int argc, char** argv) {
     if (argc != 3) { std::fprintf(stderr, "usage: jpeg_rules <pack> <out>\n"); return 2; }
     FILE* f = std::fopen(argv[1], "rb");
@@ -71,11 +96,25 @@ int main(int argc, char** argv) {
     if (std::fread(off.data(), 8, off.size(), f) != off.size()) return 2;
     FILE* o = std::fopen(argv[2], "wb");
     if (!o) return 2;
+    std::vector<uint8_t*> blk((size_t)n);
     for (int64_t i = 0; i < n; ++i) {
         const int64_t len = off[(size_t)i + 1] - off[(size_t)i];
         if (len < 0) return 2;
-        uint8_t* d = (uint8_t*)std::malloc(len ? (size_t)len : 1);       // exact size: the walk reads nothing past len
-        if (len && std::fread(d, 1, (size_t)len, f) != (size_t)len) return 2;
+        blk[(size_t)i] = (uint8_t*)std::malloc(len ? (size_t)len : 1);   // exact size: the walk reads nothing past len
+        if (len && std::fread(blk[(size_t)i], 1, (size_t)len, f) != (size_t)len) return 2;
+    }
+    std::vector<JpegHeader> h1, h4;
+    std::vector<char> ok1, ok4;
+    walk_all(1, blk, off, &h1, &ok1);
+    walk_all(4, blk, off, &h4, &ok4);
+    for (int64_t i = 0; i < n; ++i)
+        if (!same_header(ok1[(size_t)i], h1[(size_t)i], ok4[(size_t)i], h4[(size_t)i])) {
+            std::fprintf(stderr, "stream %lld: the header walk on 4 parts differs from the walk on 1 part\n", (long long)i);
+            return 4;
+        }
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t len = off[(size_t)i + 1] - off[(size_t)i];
+        uint8_t* d = blk[(size_t)i];
         JpegHeader H;
         std::vector<uint8_t> px, planes;
         std::vector<int16_t> coef;
@@ -93,6 +132,6 @@ int main(int argc, char** argv) {
     }
     std::fclose(o);
     std::fclose(f);
-    std::printf("jpeg rules ok %lld\n", (long long)n);
+    std::printf("jpeg rules ok %lld, headers equal on 1 and 4 parts\n", (long long)n);
     return 0;
 }

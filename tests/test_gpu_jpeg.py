@@ -63,6 +63,35 @@ def test_the_device_form_on_a_stream_writes_the_same_bytes():
     assert torch.equal(t, t0)
 
 
+def test_the_timed_hook_writes_the_bytes_of_the_plain_entry():
+    """mvs_test_jpeg_decode_timed on the sixteen 33x50 streams against mvs_jpeg_decode_dev, and the plain entry once more after it"""
+    import ctypes as C
+    import torch
+    lib = L.lib()
+    datas = [FIX[k][0] for k in MIXED + MIXED[:2]]
+
+    def call(datas, ms):
+        off = np.zeros(len(datas) + 1, np.int64)
+        off[1:] = np.cumsum([len(d) for d in datas])
+        blob = np.frombuffer(b"".join(datas), np.uint8)
+        out = torch.zeros((len(datas), 33, 50, 3), dtype=torch.uint8, device="cuda")
+        if ms is None:
+            rc = lib.mvs_jpeg_decode_dev(len(datas), L.ptr(off), L.ptr(blob), L.JPEG_RGB, L.ptr(out), None)
+        else:
+            rc = lib.mvs_test_jpeg_decode_timed(len(datas), L.ptr(off), L.ptr(blob), L.JPEG_RGB, L.ptr(out), None, ms)
+        return rc, out.cpu().numpy()
+
+    rc, want = call(datas, None)
+    assert rc == 0
+    ms = (C.c_double * 5)(-1.0, -1.0, -1.0, -1.0, -1.0)
+    rc, got = call(datas, ms)
+    print("ms", list(ms))
+    assert rc == 0 and np.array_equal(got, want)
+    assert all(np.isfinite(m) and m >= 0 for m in ms)
+    rc, again = call(datas, None)
+    assert rc == 0 and np.array_equal(again, want)
+
+
 def test_errors():
     with pytest.raises(L.MvsError) as e:
         P.DecodeJpegs([FIX["33x50_420_q50"][0], FIX["17x23_420_q50"][0], FIX["33x50_444_q50"][0]])

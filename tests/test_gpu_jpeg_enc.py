@@ -93,6 +93,54 @@ def test_the_device_form_on_a_stream_equals_the_host_form():
     assert torch.equal(data, data0) and np.array_equal(off, off0)
 
 
+@pytest.mark.parametrize("restart", [0, 1])
+def test_more_than_1024_scan_tiles_in_one_call(restart):
+    """65535 copies of one 40 x 32 grey image, 20 blocks each: 1 310 700 scan blocks, 1280 tiles of the device-wide scan (csrc/scan_dev.h),
+    the smallest call in which a thread of the scan's second level owns more than one tile sum; with an interval of one MCU the
+    interval scan has 1 310 700 items as well.  Every stream is the stream of the image alone, which is the restatement's"""
+    import torch
+    n, img = 65535, image(40, 32, 7)[..., 1].copy()
+    (one,) = P.EncodeJpegs(img[None], order="GREY", restart_interval=restart)
+    assert one == E.encode(img, "grey", 95, restart)
+    imgs = torch.as_tensor(img).to("cuda").expand(n, 40, 32).contiguous()
+    data, off = P.EncodeJpegs(imgs, order="GREY", restart_interval=restart, device="cuda", capacity=n * len(one))
+    print("restart", restart, len(one), "bytes per stream,", n * 20, "scan blocks,", -(-(n * 20 + 1) // 1024), "tiles")
+    assert np.array_equal(off, np.arange(n + 1, dtype=np.int64) * len(one))
+    row = torch.as_tensor(np.frombuffer(one, np.uint8).copy()).to("cuda")
+    assert bool((data.view(n, len(one)) == row).all())
+
+
+def test_the_timed_hook_writes_the_bytes_of_the_plain_entry():
+    """mvs_test_jpeg_encode_timed on five 33x50 images against mvs_jpeg_encode_dev; then a capacity one byte short, which returns between
+    the marks of the stage clock, and the plain entry after it"""
+    import ctypes as C
+    import torch
+    lib = L.lib()
+    imgs = torch.as_tensor(np.stack([image(33, 50, seed) for seed in range(5)])).to("cuda")
+    prm = P.jpeg_encode_params(quality=75, sampling=420, restart_interval=2)
+    cap = 5 * int(lib.mvs_jpeg_encode_bound(50, 33, L.JPEG_RGB, C.byref(prm)))
+
+    def plain():
+        off, data = np.zeros(6, np.int64), torch.zeros(cap, dtype=torch.uint8, device="cuda")
+        L.check(lib.mvs_jpeg_encode_dev(5, 50, 33, L.ptr(imgs), L.JPEG_RGB, C.byref(prm), L.ptr(off), L.ptr(data), cap, None))
+        return off, data[:int(off[5])].cpu().numpy()
+
+    def timed(capacity):
+        off, data, ms = np.zeros(6, np.int64), torch.zeros(cap, dtype=torch.uint8, device="cuda"), (C.c_double * 4)(-1.0, -1.0, -1.0, -1.0)
+        rc = lib.mvs_test_jpeg_encode_timed(5, 50, 33, L.ptr(imgs), L.JPEG_RGB, C.byref(prm), L.ptr(off), L.ptr(data), capacity, None, ms)
+        return rc, off, data[:int(off[5])].cpu().numpy(), list(ms)
+
+    off0, want = plain()
+    rc, off, got, ms = timed(cap)
+    print("ms", ms)
+    assert rc == 0 and np.array_equal(off, off0) and np.array_equal(got, want)
+    assert all(np.isfinite(m) and m >= 0 for m in ms)
+    rc, off, _, _ = timed(int(off0[5]) - 1)
+    assert rc == E_INVALID and np.array_equal(off, off0)
+    off1, again = plain()
+    assert np.array_equal(off1, off0) and np.array_equal(again, want)
+
+
 @pytest.mark.parametrize("size", ["33x50", "8x9"])
 @pytest.mark.parametrize("mode", ["grey", "444", "422", "420"])
 def test_the_round_trip_equals_decode_of_encode(size, mode):

@@ -81,7 +81,7 @@ def _run(exe, tmp_path, streams):
     with open(pack, "wb") as fh:
         fh.write(struct.pack("<q", len(streams)) + off.tobytes() + b"".join(streams))
     run = subprocess.run([exe, pack, out], capture_output=True, text=True, timeout=120)
-    assert run.returncode == 0 and f"jpeg rules ok {len(streams)}" in run.stdout, run.stdout + run.stderr
+    assert run.returncode == 0 and f"jpeg rules ok {len(streams)}, headers equal on 1 and 4 parts" in run.stdout, run.stdout + run.stderr
     assert "runtime error" not in run.stderr and "Sanitizer" not in run.stderr, run.stderr
     raw = open(out, "rb").read()
     res, p = [], 0

@@ -156,6 +156,16 @@ int mvs_test_jpeg_decode_timed(int32_t n, const int64_t* offsets, const uint8_t*
 int mvs_test_jpeg_encode_timed(int32_t n, int32_t w, int32_t h, const uint8_t* imgs_dev, uint32_t flags, const mvs_jpeg_encode_params* p,
                                int64_t* offsets, uint8_t* data_dev, int64_t capacity, void* hip_stream, double* ms);
 
+/* mvs_jpeg_encode from quantised coefficients in place of pixels: E1 as that entry, then coef (host, [n][n_coef] int16: component by
+ * component, the blocks row-major over the padded plane of whole MCUs, natural order inside a block) is uploaded in place of the
+ * transform's output and the rest of the call runs unchanged: bit counts, scans, restart intervals, the bit writer, FF count, offsets,
+ * stuffing, markers, headers.  For the entropy coder on contents no pixels produce (tests/jpeg_coef_cases.py).  What stands at a dummy
+ * block (E6) is never read.  Of flags only MVS_JPEG_GREY matters.  MVS_E_INVALID_ARG before any upload, with the index in the message: a
+ * DC of a real block outside -1024 .. 1023 (so that every difference fits category 11) or an AC outside -1023 .. 1023; E7 has no code for
+ * more.  offsets, data and capacity as mvs_jpeg_encode. */
+int mvs_test_jpeg_encode_coef(int32_t n, int32_t w, int32_t h, const int16_t* coef, uint32_t flags, const mvs_jpeg_encode_params* p,
+                              int64_t* offsets, uint8_t* data, int64_t capacity);
+
 #ifdef __cplusplus
 }
 #endif

@@ -370,6 +370,7 @@ _SIGS = {
                                                        _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mvs_test_jpeg_decode_timed": (C.c_int, [_I32, _VP, _VP, _U32, _VP, _VP, _VP]),
     "mvs_test_jpeg_encode_timed": (C.c_int, [_I32, _I32, _I32, _VP, _U32, _VP, _VP, _VP, _I64, _VP, _VP]),
+    "mvs_test_jpeg_encode_coef": (C.c_int, [_I32, _I32, _I32, _VP, _U32, _VP, _VP, _VP, _I64]),
     "mvs_test_rotations": (C.c_int, [_I64, _VP, _I32, _VP, _VP, _VP]),
 }
 EXPORTS = tuple(_SIGS)

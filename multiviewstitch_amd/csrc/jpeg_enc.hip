@@ -17,6 +17,9 @@
 //   k_dp_range / k_dp_write: mvs_depth_preview, min / max of the valid depths by atomicMin / atomicMax on the bits of the non-negative
 //                  floats (order-free), then a lane per pixel.
 //
+// mvs_test_jpeg_encode_coef (include/mvs_test.h) uploads coefficient blocks of its caller's choice in place of k_je_transform's output and
+// runs everything behind it (je_entropy), which the production entries run after their transform launch.
+//
 // Stream positions come from scans only; two runs give the same bytes.  The scans are scan_dev.h's, as grid.hip's; which block a lane
 // is at comes from the walks of jpeg_rules.h, as in the decoder; the round trip ends in the decoder's jpeg_pixels_tail (jpeg.hip).
 #include "engine.h"
@@ -288,10 +291,15 @@ int je_fits(const char* fn, int64_t total, int64_t capacity) {
 }
 
 struct JeCoef { Scratch tab, coef; };
+// the tables of the call in HBM and room for its coefficient blocks
+int je_coef_alloc(JePlan& pl, JeCoef* c, hipStream_t s) {
+    int rc = up_async(c->tab, &pl.T, 1, s);
+    return rc ? rc : c->coef.alloc(sizeof(int16_t) * (size_t)pl.cl.n_coef * (size_t)pl.cl.n, s);
+}
 // the transform launch on the pixels at imgs_dev
 int je_transform(JePlan& pl, const uint8_t* imgs_dev, JeCoef* c, hipStream_t s) {
     int rc;
-    if ((rc = up_async(c->tab, &pl.T, 1, s)) || (rc = c->coef.alloc(sizeof(int16_t) * (size_t)pl.cl.n_coef * (size_t)pl.cl.n, s))) return rc;
+    if ((rc = je_coef_alloc(pl, c, s))) return rc;
     pl.cl.px.px = imgs_dev;
     const int64_t nb = pl.cl.n_coef / 64;
     k_je_transform<<<dim3((unsigned)((nb + 63) / 64), (unsigned)pl.cl.n), dim3(64), 0, s>>>(pl.cl, &c->tab.as<JpegEncTables>()->quant[0][0],
@@ -299,19 +307,15 @@ int je_transform(JePlan& pl, const uint8_t* imgs_dev, JeCoef* c, hipStream_t s) 
     return mvs_check_hip(hipGetLastError(), "k_je_transform");
 }
 
-// The call on pixels in HBM.  offsets: host, written before the capacity is checked.  data_dev != NULL: the streams go there (capacity
-// bytes); else `own` receives a block of offsets[n] bytes that holds them.  ms (may be NULL): transform, entropy, stuffing in milliseconds.
-// Complete on return
-int je_run(const char* fn, JePlan& pl, const uint8_t* imgs_dev, int64_t* offsets, uint8_t* data_dev, int64_t capacity, Scratch* own, hipStream_t s,
-           double* ms) {
-    const JeCall& cl0 = pl.cl;
-    const int64_t N = cl0.nblk * cl0.n, NI = cl0.n_int;
-    JeCoef c;
-    Scratch dbits, dbit_at, dpart, dpart2, dibytes, dibyte_at, draw, dcnt, dff_at, doff, dhdr;
-    StageClock clk(ms != nullptr);
-    int rc;
-    if ((rc = clk.mark(s)) || (rc = je_transform(pl, imgs_dev, &c, s)) || (rc = clk.mark(s))) return rc;
+// Everything behind the transform, on the coefficient blocks c its caller made (k_je_transform's, or mvs_test_jpeg_encode_coef's upload):
+// bits, scans, intervals, write, FF count, offsets, stuffing, headers.  clk: the caller's clock with the marks around the transform set;
+// the other arguments are je_run's.  Complete on return
+int je_entropy(const char* fn, const JePlan& pl, const JeCoef& c, StageClock& clk, int64_t* offsets, uint8_t* data_dev, int64_t capacity, Scratch* own,
+               hipStream_t s, double* ms) {
     const JeCall& cl = pl.cl;
+    const int64_t N = cl.nblk * cl.n, NI = cl.n_int;
+    Scratch dbits, dbit_at, dpart, dpart2, dibytes, dibyte_at, draw, dcnt, dff_at, doff, dhdr;
+    int rc;
     if ((rc = dbits.alloc(4 * (size_t)N, s)) || (rc = dbit_at.alloc(8 * (size_t)(N + 1), s)) ||
         (rc = dpart.alloc(8 * (size_t)((N + JE_TILE - 1) / JE_TILE + 2), s)) || (rc = dibytes.alloc(4 * (size_t)NI, s)) ||
         (rc = dibyte_at.alloc(8 * (size_t)(NI + 1), s)) || (rc = doff.alloc(8 * (size_t)(cl.n + 1), s)) ||
@@ -350,6 +354,36 @@ int je_run(const char* fn, JePlan& pl, const uint8_t* imgs_dev, int64_t* offsets
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
     return ms ? clk.read(ms) : MVS_OK;
+}
+
+// The call on pixels in HBM.  offsets: host, written before the capacity is checked.  data_dev != NULL: the streams go there (capacity
+// bytes); else `own` receives a block of offsets[n] bytes that holds them.  ms (may be NULL): transform, entropy, stuffing in milliseconds.
+// Complete on return
+int je_run(const char* fn, JePlan& pl, const uint8_t* imgs_dev, int64_t* offsets, uint8_t* data_dev, int64_t capacity, Scratch* own, hipStream_t s,
+           double* ms) {
+    JeCoef c;
+    StageClock clk(ms != nullptr);
+    int rc;
+    if ((rc = clk.mark(s)) || (rc = je_transform(pl, imgs_dev, &c, s)) || (rc = clk.mark(s))) return rc;
+    return je_entropy(fn, pl, c, clk, offsets, data_dev, capacity, own, s, ms);
+}
+
+// E7's symbols end at size 11 for a DC difference and at size 10 for an AC value: NULL, or the first value of the real blocks of n
+// images (coef as JpegLayout places them) that jpeg_enc_block_bits has no code for, with its place in *at
+const int16_t* je_coef_range(const JeCall& cl, const int16_t* coef, int64_t* at) {
+    const JpegLayout& L = cl.L;
+    for (int64_t img = 0; img < cl.n; ++img)
+        for (int c = 0; c < L.ncomp; ++c)
+            for (int by = 0; by < L.bh[c]; ++by)
+                for (int bx = 0; bx < L.bw[c]; ++bx) {
+                    if (jpeg_enc_dummy(L, c, bx, by)) continue;                 // E6: nothing reads them
+                    const int64_t b = img * cl.n_coef + jpeg_block_at(L, c, bx, by);
+                    for (int k = 0; k < 64; ++k) {
+                        const int v = coef[b + k];
+                        if (v > 1023 || v < (k ? -1023 : -1024)) { *at = b + k; return coef + b + k; }
+                    }
+                }
+    return nullptr;
 }
 
 int je_check_ptrs(const char* fn, const void* imgs, const void* out) {
@@ -467,6 +501,29 @@ int mvs_test_jpeg_encode_timed(int32_t n, int32_t w, int32_t h, const uint8_t* i
                                int64_t* offsets, uint8_t* data_dev, int64_t capacity, void* hip_stream, double* ms) {
     if (!ms) return bad(__func__, "ms is NULL");
     return je_dev(__func__, n, w, h, imgs_dev, flags, p, offsets, data_dev, capacity, hip_stream, ms);
+}
+
+int mvs_test_jpeg_encode_coef(int32_t n, int32_t w, int32_t h, const int16_t* coef, uint32_t flags, const mvs_jpeg_encode_params* p,
+                              int64_t* offsets, uint8_t* data, int64_t capacity) {
+    JePlan pl;
+    int rc = je_plan(__func__, n, w, h, flags, p, &pl);
+    if (rc) return rc;
+    if (!coef || !offsets || (!data && capacity > 0) || capacity < 0) return bad(__func__, "coef, offsets or data is NULL, or capacity is negative");
+    int64_t at = 0;
+    if (const int16_t* v = je_coef_range(pl.cl, coef, &at)) {
+        mvs_set_error("%s: coef[%lld] = %d (image %lld, value %lld of the image, position %d of its block) is outside %s", __func__, (long long)at,
+                      (int)*v, (long long)(at / pl.cl.n_coef), (long long)(at % pl.cl.n_coef), (int)(at % 64),
+                      at % 64 ? "-1023 .. 1023 of an AC coefficient" : "-1024 .. 1023 of a DC coefficient");
+        return MVS_E_INVALID_ARG;
+    }
+    if ((rc = need_device())) return rc;
+    JeCoef c;
+    Scratch dout;
+    StageClock clk(false);
+    if ((rc = je_coef_alloc(pl, &c, nullptr))) return rc;
+    HIPCHK(hipMemcpy(c.coef.p, coef, sizeof(int16_t) * (size_t)pl.cl.n_coef * (size_t)n, hipMemcpyHostToDevice));
+    if ((rc = je_entropy(__func__, pl, c, clk, offsets, nullptr, 0, &dout, nullptr, nullptr)) || (rc = je_fits(__func__, offsets[n], capacity))) return rc;
+    return down(data, dout, (size_t)offsets[n]);
 }
 
 int mvs_jpeg_roundtrip(int32_t n, int32_t w, int32_t h, const uint8_t* imgs, uint32_t flags, const mvs_jpeg_encode_params* p, uint8_t* out) {

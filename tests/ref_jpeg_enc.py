@@ -1,6 +1,7 @@
 """Rules E1-E9 of include/mvs.h (the baseline JPEG encoder) restated in numpy and plain Python, operation for operation, and the
 restatement of ``mvs_depth_preview``.  ``encode`` returns the stream; ``encode_all`` also the quantised coefficient blocks and the counters
-the fixture-set test reads (stuffed FF bytes, ZRL symbols, dummy blocks, padded and byte-aligned interval ends).  The round trip of
+the fixture-set test reads (stuffed FF bytes, ZRL symbols, dummy blocks, padded and byte-aligned interval ends); ``encode_coef`` is E6-E9
+alone, on coefficients its caller chose, and also returns the bytes of every interval before stuffing.  The round trip of
 ``mvs_jpeg_roundtrip`` is ``ref_jpeg.decode(encode(x))``."""
 import numpy as np
 
@@ -122,11 +123,12 @@ class Writer:
     """E7: bits MSB first, FF followed by 00"""
 
     def __init__(self):
-        self.out, self.acc, self.n, self.stuffed = bytearray(), 0, 0, 0
+        self.out, self.raw, self.acc, self.n, self.stuffed, self.bits = bytearray(), bytearray(), 0, 0, 0, 0   # raw: the bytes before stuffing
 
     def put(self, code, length):
         self.acc = (self.acc << length) | code
         self.n += length
+        self.bits += length
         while self.n >= 8:
             self.n -= 8
             self._byte((self.acc >> self.n) & 255)
@@ -134,6 +136,7 @@ class Writer:
 
     def _byte(self, b):
         self.out.append(b)
+        self.raw.append(b)
         if b == 255:
             self.out.append(0)
             self.stuffed += 1
@@ -150,17 +153,21 @@ def _size(v):
     return int(abs(int(v))).bit_length()
 
 
-def encode_block(w, blk, pred, dc, ac, count):
-    """E7: one block of 64 coefficients in natural order (None: a dummy block) -> the new predictor"""
+def encode_block(w, blk, pred, dc, ac, count, seen=None):
+    """E7: one block of 64 coefficients in natural order (None: a dummy block) -> the new predictor.  seen (optional): dict(dc, ac: sets
+    that receive (symbol, value > 0) of every symbol of a real block, (symbol, None) where no value follows; bits: the longest real block)"""
     if blk is None:
         w.put(*dc[0])
         w.put(*ac[0])
         return pred
+    start = w.bits
     d = int(blk[0]) - pred
     s = _size(d)
     w.put(*dc[s])
     if s:
         w.put((d if d >= 0 else d - 1) & ((1 << s) - 1), s)
+    if seen is not None:
+        seen["dc"].add((s, d > 0 if s else None))
     run = 0
     for k in range(1, 64):
         v = int(blk[ZIGZAG[k]])
@@ -171,12 +178,20 @@ def encode_block(w, blk, pred, dc, ac, count):
             w.put(*ac[0xF0])
             count["zrl"] += 1
             run -= 16
+            if seen is not None:
+                seen["ac"].add((0xF0, None))
         s = _size(v)
         w.put(*ac[(run << 4) | s])
         w.put((v if v >= 0 else v - 1) & ((1 << s) - 1), s)
+        if seen is not None:
+            seen["ac"].add(((run << 4) | s, v > 0))
         run = 0
     if run:
         w.put(*ac[0])
+    if seen is not None:
+        if run:
+            seen["ac"].add((0, None))
+        seen["bits"] = max(seen["bits"], w.bits - start)
     return int(blk[0])
 
 
@@ -228,16 +243,34 @@ def encode_all(img, mode="420", quality=95, restart_interval=0, order="RGB"):
         c[:, rb[1]:] = 0
         coef.append(c)
         real.append(rb)
+    stream, _, count = encode_coef(coef, W, H, mode, quality, restart_interval)
+    return stream, coef, count
+
+
+def encode_coef(coef, W, H, mode, quality, restart_interval, seen=None):
+    """E6-E9 on given coefficients: per component an int16 array [bh, bw, 64] over the padded plane, natural order inside a block; what
+    stands at a dummy block is ignored -> (stream, the unstuffed bytes of every restart interval, counters).  seen (optional): per table
+    (0 luma, 1 chroma) what ``encode_block`` records"""
+    grey = mode == "grey"
+    hmax, vmax = SAMPLING[mode]
+    mcux, mcuy = -(-W // (8 * hmax)), -(-H // (8 * vmax))
+    comps = [(1, 1, 0)] if grey else [(1, 1, 0), (hmax, vmax, 1), (hmax, vmax, 1)]
+    assert len(coef) == len(comps)
+    real = []
+    for c, (hr, vr, _) in zip(coef, comps):
+        assert c.shape == (mcuy * vmax // vr, mcux * hmax // hr, 64) and c.dtype == np.int16
+        real.append((-(-(-(-H // vr)) // 8), -(-(-(-W // hr)) // 8)))   # E6: the real blocks
     restart = mcux if restart_interval == ROW else restart_interval
     per = restart if restart else mcux * mcuy
     count = dict(stuffed=0, zrl=0, dummy_col=0, dummy_row=0, padded_end=0, aligned_end=0)
     out = bytearray(header(W, H, mode, quality, restart))
+    raws = []
     n_int = -(-mcux * mcuy // per)
     for t in range(n_int):
         w, pred = Writer(), [0, 0, 0]
         for m in range(t * per, min((t + 1) * per, mcux * mcuy)):
             my, mx = divmod(m, mcux)
-            for ci, (_, hr, vr, tab) in enumerate(comps):
+            for ci, (hr, vr, tab) in enumerate(comps):
                 hs, vs = (hmax // hr, vmax // vr) if not grey else (1, 1)
                 for j in range(vs):
                     for i in range(hs):
@@ -245,13 +278,15 @@ def encode_all(img, mode="420", quality=95, restart_interval=0, order="RGB"):
                         dummy = by >= real[ci][0] or bx >= real[ci][1]
                         if dummy:
                             count["dummy_row" if by >= real[ci][0] else "dummy_col"] += 1
-                        pred[ci] = encode_block(w, None if dummy else coef[ci][by, bx], pred[ci], DC_CODES[tab], AC_CODES[tab], count)
+                        pred[ci] = encode_block(w, None if dummy else coef[ci][by, bx], pred[ci], DC_CODES[tab], AC_CODES[tab], count,
+                                                 None if seen is None else seen[tab])
         count["padded_end" if w.flush() else "aligned_end"] += 1
         count["stuffed"] += w.stuffed
         out += w.out
+        raws.append(bytes(w.raw))
         if t + 1 < n_int:
             out += bytes([0xFF, 0xD0 + (t & 7)])
-    return bytes(out + b"\xff\xd9"), coef, count
+    return bytes(out + b"\xff\xd9"), raws, count
 
 
 def encode(img, mode="420", quality=95, restart_interval=0, order="RGB"):

@@ -110,12 +110,19 @@ def _cases():
 
 
 def _run(exe, tmp_path, cases):
+    return run_records(exe, tmp_path, [((a.shape[1], a.shape[0], 1 if mode == "grey" else 3, int(order == "RGB"), q, 420 if mode == "grey" else int(mode), r),
+                                        np.ascontiguousarray(a).tobytes()) for _, a, mode, q, r, order in cases])
+
+
+def run_records(exe, tmp_path, cases):
+    """cases: [((w, h, chan, rgb, quality, sampling, restart_interval), the bytes behind them)], the records of the program's pack format
+    (chan -1 or -3: a coefficient record, tests/test_jpeg_coef_host.py) -> [(stream, coefficients)]"""
     pack, out = str(tmp_path / "pack.bin"), str(tmp_path / "out.bin")
     with open(pack, "wb") as fh:
         fh.write(struct.pack("<q", len(cases)))
-        for _, a, mode, q, r, order in cases:
-            fh.write(struct.pack("<7i", a.shape[1], a.shape[0], 1 if mode == "grey" else 3, int(order == "RGB"), q, 420 if mode == "grey" else int(mode), r))
-            fh.write(np.ascontiguousarray(a).tobytes())
+        for head, body in cases:
+            fh.write(struct.pack("<7i", *head))
+            fh.write(body)
     run = subprocess.run([exe, pack, out], capture_output=True, text=True, timeout=300)
     assert run.returncode == 0 and f"jpeg enc rules ok {len(cases)}" in run.stdout, run.stdout + run.stderr
     assert "runtime error" not in run.stderr and "Sanitizer" not in run.stderr, run.stderr

@@ -277,7 +277,8 @@ int mvs_match_filter_pairs_dev(int32_t n1, int32_t n2, const int64_t* raw_offset
                                int64_t* out_offsets, int64_t* stage_counts, void* hip_stream);
 
 /* One turn of the loop over adjacent sequences of Processor::CalcSimilarityTransformationSeq (R/Processor/Processor.cpp:629-826,
- * without the match JPEGs of :767-793; SIFT matching, :634, is the caller's: its output is `raw`):
+ * without the match JPEGs of :767-793, which mvs_match_overlays draws and mvs_processor_match_overlays (mvs_io.h) writes from the lists
+ * of mvs_match_filter_pairs; SIFT matching, :634, is the caller's: its output is `raw`):
  *   the valid masks of both sequences from their float32 inverse-depth rasters (valid iff inside [min_dsp, max_dsp], Image3D.cpp:98-101),
  *   the cascade of mvs_match_filter_pairs (:645-735), every survivor lifted to {GetPoint(u1,v1) of frame i, GetPoint(u2,v2) of frame j}
  *   with the arithmetic of mvs_depth_unproject ((0,0,0) for a pixel outside [min_dsp, max_dsp]), mvs_select_keyframe_pair on the lifted
@@ -855,6 +856,78 @@ int mvs_jpeg_roundtrip_dev(int32_t n, int32_t w, int32_t h, const uint8_t* imgs_
  * every valid pixel when d_max == d_min (undefined in the reference: a division by zero); a raster without a valid pixel is all 255. */
 int mvs_depth_preview(int32_t n, int32_t w, int32_t h, const float* depths, uint8_t* out /*n x h x w*/);
 int mvs_depth_preview_dev(int32_t n, int32_t w, int32_t h, const float* depths_dev, uint8_t* out_dev, void* hip_stream);
+
+/* The match and SIFT overlay pictures: the drawing of R/Processor/Processor.cpp:767-793 (every frame pair of two adjacent sequences:
+ * cv::vconcat of the two base images, per match two radius-1 rings in (255,255,0) and a thickness-2 line in a cv::RNG colour; :486-505
+ * is the same code) and of R/FeatureProc/FeatureProc.cpp:67-73 and Processor.cpp:604-615 (a filled radius-1 mark in (0,255,0) at every
+ * key point of a generated view), all canvases of a call in ONE launch.  The rules below are this library's definition, chosen to give
+ * the reference's pixels for what the reference draws.  They are RECALLED from OpenCV 3.0's drawing.cpp and cv::RNG and NOT VERIFIED
+ * against it: OpenCV is neither on the machines this was written on nor in the reference tree.  csrc/overlay_rules.h holds every
+ * decision as one body for host and device.
+ *   O1 canvas    : n canvases (1 .. 65535) of h x w x 3 bytes, 1 <= w, h <= 16384.  A colour is three bytes in the canvas's own channel
+ *                  order;
+ *   O2 primitive : mvs_draw_prim, 24 bytes.  kind is MVS_DRAW_DISC, MVS_DRAW_RING or MVS_DRAW_SEGMENT; (x0, y0) is the centre of a disc
+ *                  or ring and one end A of a segment, (x1, y1) the segment's other end B (not read for a disc or ring); size is the
+ *                  radius r (0 .. 255) of a disc or ring, or the thickness T (1 .. 255) of a segment; c the colour; pad is not read.
+ *                  Canvas i owns prims[prim_offsets[i] .. prim_offsets[i+1]), prim_offsets ascending from 0;
+ *   O3 coverage  : exact in int64.  Pixel p = (x, y), dx = x - x0, dy = y - y0.  DISC: dx^2 + dy^2 <= r^2 (r = 1: the 5-pixel plus of
+ *                  cv::circle(.., 1, .., -1)).  RING: (r-1)^2 < dx^2 + dy^2 <= r^2; r = 0: the centre pixel; r = 1: the 4 pixels of
+ *                  cv::circle(.., 1, colour).  SEGMENT: the capsule 4 dist(p, AB)^2 <= T^2; with e = p - A, d = B - A, L2 = d.d, s = e.d:
+ *                  s <= 0: 4 |e|^2 <= T^2; s >= L2: 4 |p - B|^2 <= T^2; otherwise 4 (e.x d.y - e.y d.x)^2 <= T^2 L2.  A == B is a disc
+ *                  of diameter T.  Deviation: for the reference's T = 2 OpenCV fills a polygon around the line and round caps at its
+ *                  ends in 16.16 fixed point; the capsule is that shape up to the pixels on the fixed-point rim;
+ *   O4 order     : a pixel takes the colour of the covering primitive with the HIGHEST index in its canvas's list; a pixel nothing
+ *                  covers keeps the source pixel.  This is sequential painting stated as a gather, as mvs_gen_new_views states the
+ *                  reference's scatter: every pixel is written once, nothing races, out == in is allowed;
+ *   O5 range     : disc and ring centres may lie anywhere with |coordinate| <= 2^20 and are clipped; segment ends must lie inside the
+ *                  canvas.  Anything else is MVS_E_INVALID_ARG naming canvas and primitive, before a device is looked for.  With O1
+ *                  every product of O3 stays below 2^62 (the bounds stand next to the arithmetic in overlay_rules.h);
+ *   O6 colours   : cv::RNG as recalled: the state is uint64, 0xffffffff by default; next() is state = (uint32)state * 4164903690 +
+ *                  (state >> 32), returning the low 32 bits; a double is ((uint64)next() << 32 | next()) * 5.4210108624275221700372640043497e-20
+ *                  with the high word drawn first.  Per match, in this order, r, g, b = (uint8)(double * 255); the line colour is
+ *                  (b, g, r) in a B G R canvas.  The generator is sequential and cheap and runs on the host; one generator runs through
+ *                  all (i, j) of a sequence pair in row-major order, as :768 has it.
+ * A cv::Point2f becomes a pixel by cvRound, round half to even (the SIFT keys are floats): one helper, which gives INT_MIN for NaN and
+ * for values outside int32 as the double -> int helper of mvs_gen_new_views does; such a mark is clipped away. */
+#define MVS_DRAW_DISC 0
+#define MVS_DRAW_RING 1
+#define MVS_DRAW_SEGMENT 2
+typedef struct mvs_draw_prim {            /* 24 bytes */
+    int32_t x0, y0, x1, y1;
+    uint8_t kind, size, c[3], pad[3];
+} mvs_draw_prim;
+/* out [n][h][w][3] = imgs [n][h][w][3] with every canvas's list painted (O1-O5) */
+int mvs_draw_overlays(int32_t n, int32_t w, int32_t h, const uint8_t* imgs, const int64_t* prim_offsets /*n+1*/, const mvs_draw_prim* prims,
+                      uint8_t* out);
+/* the pixels in HBM (out_dev may be imgs_dev), the lists host arrays that are uploaded; in the order of hip_stream (may be NULL);
+ * returns with the work complete */
+int mvs_draw_overlays_dev(int32_t n, int32_t w, int32_t h, const uint8_t* imgs_dev, const int64_t* prim_offsets, const mvs_draw_prim* prims,
+                          uint8_t* out_dev, void* hip_stream);
+/* O6: n line colours from the generator at *state (in / out), bgr [n][3] = (b, g, r) each.  Host code, no device needed; a NULL
+ * pointer or n < 1 does nothing */
+void mvs_cv_rng_colours(uint64_t* state, int64_t n, uint8_t* bgr /*n x 3*/);
+/* Processor.cpp:767-793 for all n1 x n2 frame pairs: canvas i*n2 + j of out [n1*n2][2h][w][3] is imgs1[i] over imgs2[j] (rows 0 .. h-1
+ * and h .. 2h-1; the stack is never materialised as an input) with, per match (u1, v1, u2, v2) of pair i*n2 + j in list order, a ring
+ * (r = 1, (255,255,0)) at (u1, v1), one at (u2, h + v2) and a segment (T = 2) between them in the next colour of O6.  matches
+ * [total][4] with match_offsets (n1*n2 + 1) is the `out` / `out_offsets` of mvs_match_filter_pairs; the images are B G R.  rng_state
+ * (in / out; NULL: a fresh default generator) runs through the pairs in order: 6 draws per match.  n1*n2 <= 65535, 2h <= 16384; a
+ * match with an end outside its image is MVS_E_INVALID_ARG naming pair and match. */
+int mvs_match_overlays(int32_t n1, int32_t n2, int32_t w, int32_t h, const uint8_t* imgs1 /*n1 x h x w x 3*/, const uint8_t* imgs2 /*n2 x h x w x 3*/,
+                       const int64_t* match_offsets /*n1*n2+1*/, const int32_t* matches /*total x 4*/, uint64_t* rng_state,
+                       uint8_t* out /*n1*n2 x 2h x w x 3*/);
+/* images and canvases in HBM; the match lists host arrays; one launch does the stack and the drawing, in the order of hip_stream (may be
+ * NULL); returns with the work complete */
+int mvs_match_overlays_dev(int32_t n1, int32_t n2, int32_t w, int32_t h, const uint8_t* imgs1_dev, const uint8_t* imgs2_dev,
+                           const int64_t* match_offsets, const int32_t* matches, uint64_t* rng_state, uint8_t* out_dev, void* hip_stream);
+/* FeatureProc.cpp:67-69 / Processor.cpp:607-609 for n_lists views: out = views with a filled r = 1 disc in (0,255,0) at cvRound of the
+ * (x, y) of every key of the view's list, keys [total][4] = (x, y, s, o) floats with key_offsets (n_lists + 1) as mvs_sift_detect and
+ * mvs_keypoint_cull return them. */
+int mvs_sift_overlays(int32_t n_lists, int32_t w, int32_t h, const uint8_t* views /*n_lists x h x w x 3*/, const int64_t* key_offsets,
+                      const float* keys, uint8_t* out);
+/* views and out in HBM (out_dev may be views_dev), the key lists host arrays; in the order of hip_stream (may be NULL); returns with the
+ * work complete */
+int mvs_sift_overlays_dev(int32_t n_lists, int32_t w, int32_t h, const uint8_t* views_dev, const int64_t* key_offsets, const float* keys,
+                          uint8_t* out_dev, void* hip_stream);
 
 /* ------------------------------------------------- surface reconstruction (GeometryRec::RunPoisson) -- */
 /* The one call between the stitch tail and the trim of the model (R/Processor/Processor.cpp:1042-1058): the oriented points of

@@ -130,6 +130,29 @@ int mvs_processor_save_views(const char* seq_dir, int32_t n_frames, int32_t view
  * raster.  A missing or short raster is reported before anything is written. */
 int mvs_processor_depth_previews(const char* seq_dir, const char* sub, int32_t n, int32_t w, int32_t h, const mvs_jpeg_encode_params* params);
 
+/* The match pictures of one sequence pair k (R/Processor/Processor.cpp:767-793): the canvases of mvs_match_overlays (rules O1-O6 of
+ * include/mvs.h: this library's definition; arguments as there, host arrays) encoded by mvs_jpeg_encode (rules E1-E9; params NULL:
+ * quality 95, 4:2:0, as cv::imwrite) and written to <match_dir>match<k>_<i>_<j>.jpg (a '/' is inserted after match_dir when it lacks
+ * one; the directory is created; the reference's is "./Match/").  flags: MVS_JPEG_BGR or MVS_JPEG_RGB, the order of the images; with
+ * MVS_JPEG_RGB the colours are written the other way round, so the picture is the same.  The base images are uploaded once; the
+ * canvases are worked off in batches under a byte budget (MVS_OVERLAY_BATCH_BYTES in the environment, read at every call; default
+ * 512 MiB of canvases: the 256 canvases of 640 x 960 of a 16 x 16 sequence pair are one batch), each batch one draw launch into HBM and
+ * one encoder call; only the streams are downloaded, and written on up to 16 host threads.  The generator (rng_state in / out; NULL: a
+ * fresh default one, as :768) runs on across the batches: the files do not depend on the budget.  Every argument is checked before a
+ * device is looked for and before anything is created; nothing of a batch is written when its encode fails. */
+int mvs_processor_match_overlays(const char* match_dir, int32_t k, int32_t n1, int32_t n2, int32_t w, int32_t h, const uint8_t* imgs1,
+                                 const uint8_t* imgs2, const int64_t* match_offsets, const int32_t* matches, uint32_t flags, uint64_t* rng_state,
+                                 const mvs_jpeg_encode_params* params);
+
+/* The SIFT pictures of one sequence (R/FeatureProc/FeatureProc.cpp:67-73 with sub = "Sift"; after the background cull,
+ * Processor.cpp:604-615, with sub = "Sift1"): view j of frame i of `views` (n_frames x view_count x h x w x 3 bytes, host; what
+ * mvs_gen_new_views returned, or those pixels after mvs_jpeg_roundtrip as the reference reads them back) with the marks of
+ * mvs_sift_overlays for list i * view_count + j goes to <seq_dir>Views/<sub>/proj<i>_<j>.jpg.  Batches, budget, params, flags and the
+ * order of checks as mvs_processor_match_overlays (the marks are (0,255,0) in either order). */
+int mvs_processor_sift_overlays(const char* seq_dir, const char* sub, int32_t n_frames, int32_t view_count, int32_t w, int32_t h,
+                                const uint8_t* views, const int64_t* key_offsets, const float* keys, uint32_t flags,
+                                const mvs_jpeg_encode_params* params);
+
 /* GeometryRec::RunPointSample on files (R/Processor/Processor.cpp:919-949; the rules: mvs_point_sample, this library's definition):
  * for each sequence k read seq_dirs[k]/DATA/CHECK/_depth<i>.raw for its cameras i (mvs_depth_raw_read: the checked rasters that the file
  * shuffle of :919-931 puts in front of GeoRec), sample all sequences in one call, and write seq_dirs[k]/Rec/PointSample.npts

@@ -166,6 +166,12 @@ int mvs_test_jpeg_encode_timed(int32_t n, int32_t w, int32_t h, const uint8_t* i
 int mvs_test_jpeg_encode_coef(int32_t n, int32_t w, int32_t h, const int16_t* coef, uint32_t flags, const mvs_jpeg_encode_params* p,
                               int64_t* offsets, uint8_t* data, int64_t capacity);
 
+/* mvs_match_overlays_dev with its parts timed (scripts/bench_overlay.py): ms [2] receives the milliseconds of building the lists (host)
+ * and of the draw launch alone (HIP events around it; the upload of the lists is in front of the first). */
+int mvs_test_match_overlays_timed(int32_t n1, int32_t n2, int32_t w, int32_t h, const uint8_t* imgs1_dev, const uint8_t* imgs2_dev,
+                                  const int64_t* match_offsets, const int32_t* matches, uint64_t* rng_state, uint8_t* out_dev, void* hip_stream,
+                                  double* ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -93,6 +93,17 @@ class CJpegEncodeParams(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("quality", "sampling", "restart_interval", "reserved")]
 
 
+class CDrawPrim(C.Structure):
+    """struct mvs_draw_prim (24 bytes)."""
+    _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32), ("kind", C.c_uint8), ("size", C.c_uint8),
+                ("c", C.c_uint8 * 3), ("pad", C.c_uint8 * 3)]
+
+
+DRAW_PRIM_DTYPE = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("kind", "u1"), ("size", "u1"), ("c", "u1", (3,)),
+                            ("pad", "u1", (3,))])
+DRAW_DISC, DRAW_RING, DRAW_SEGMENT = 0, 1, 2          # MVS_DRAW_DISC, MVS_DRAW_RING, MVS_DRAW_SEGMENT (include/mvs.h)
+
+
 class CGrabCutParams(C.Structure):
     """struct mvs_grabcut_params."""
     _fields_ = [("hl", C.c_double), ("hr", C.c_double), ("vl", C.c_double), ("vr", C.c_double), ("gamma", C.c_double),
@@ -327,6 +338,15 @@ _SIGS = {
     "mvs_jpeg_roundtrip_dev": (C.c_int, [_I32, _I32, _I32, _VP, _U32, _VP, _VP, _VP]),
     "mvs_depth_preview": (C.c_int, [_I32, _I32, _I32, _VP, _VP]),
     "mvs_depth_preview_dev": (C.c_int, [_I32, _I32, _I32, _VP, _VP, _VP]),
+    "mvs_draw_overlays": (C.c_int, [_I32, _I32, _I32, _VP, _VP, _VP, _VP]),
+    "mvs_draw_overlays_dev": (C.c_int, [_I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP]),
+    "mvs_cv_rng_colours": (None, [_VP, _I64, _VP]),
+    "mvs_match_overlays": (C.c_int, [_I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "mvs_match_overlays_dev": (C.c_int, [_I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "mvs_sift_overlays": (C.c_int, [_I32, _I32, _I32, _VP, _VP, _VP, _VP]),
+    "mvs_sift_overlays_dev": (C.c_int, [_I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP]),
+    "mvs_processor_match_overlays": (C.c_int, [C.c_char_p, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _U32, _VP, _VP]),
+    "mvs_processor_sift_overlays": (C.c_int, [C.c_char_p, C.c_char_p, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _U32, _VP]),
     "mvs_processor_save_views": (C.c_int, [C.c_char_p, _I32, _I32, _I32, _I32, _VP, _U32, _VP]),
     "mvs_processor_depth_previews": (C.c_int, [C.c_char_p, C.c_char_p, _I32, _I32, _I32, _VP]),
     "mvs_depth_raw_read": (C.c_int, [C.c_char_p, _I32, _I32, _VP]),
@@ -372,6 +392,7 @@ _SIGS = {
     "mvs_test_jpeg_encode_timed": (C.c_int, [_I32, _I32, _I32, _VP, _U32, _VP, _VP, _VP, _I64, _VP, _VP]),
     "mvs_test_jpeg_encode_coef": (C.c_int, [_I32, _I32, _I32, _VP, _U32, _VP, _VP, _VP, _I64]),
     "mvs_test_rotations": (C.c_int, [_I64, _VP, _I32, _VP, _VP, _VP]),
+    "mvs_test_match_overlays_timed": (C.c_int, [_I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
 }
 EXPORTS = tuple(_SIGS)
 

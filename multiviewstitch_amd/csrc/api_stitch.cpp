@@ -538,6 +538,49 @@ int mvs_processor_depth_previews(const char* seq_dir, const char* sub, int32_t n
     return write_streams(__func__, path, off.data(), data.data());
 }
 
+// the sink of the overlay producers (stitch.h): canvas c goes to dir + name(c); the directory is created in front of the first batch
+static OverlaySink overlay_files(const char* fn, const std::string& dir, std::function<std::string(int32_t)> name) {
+    return [fn, dir, name](int32_t first, int32_t count, const int64_t* off, const uint8_t* data) {
+        if (first == 0)
+            if (int rc = make_dirs(dir)) return rc;
+        std::vector<std::string> path;
+        for (int32_t c = first; c < first + count; ++c) path.push_back(dir + name(c));
+        return write_streams(fn, path, off, data);
+    };
+}
+
+int mvs_processor_match_overlays(const char* match_dir, int32_t k, int32_t n1, int32_t n2, int32_t w, int32_t h, const uint8_t* imgs1,
+                                 const uint8_t* imgs2, const int64_t* match_offsets, const int32_t* matches, uint32_t flags, uint64_t* rng_state,
+                                 const mvs_jpeg_encode_params* params) {
+    MVS_TRACE();
+    if (!match_dir) return bad(__func__, "match_dir is NULL");
+    if (k < 0) return bad(__func__, "k must be >= 0");
+    const auto name = [k, n2](int32_t c) {
+        char s[64];
+        std::snprintf(s, sizeof s, "match%d_%d_%d.jpg", k, c / n2, c % n2);                         // Processor.cpp:787
+        return std::string(s);
+    };
+    return match_overlay_streams(__func__, n1, n2, w, h, imgs1, imgs2, match_offsets, matches, flags, rng_state, params,
+                                 overlay_files(__func__, join(match_dir, ""), name));
+}
+
+int mvs_processor_sift_overlays(const char* seq_dir, const char* sub, int32_t n_frames, int32_t view_count, int32_t w, int32_t h,
+                                const uint8_t* views, const int64_t* key_offsets, const float* keys, uint32_t flags,
+                                const mvs_jpeg_encode_params* params) {
+    MVS_TRACE();
+    if (!seq_dir || !sub) return bad(__func__, "seq_dir or sub is NULL");
+    if (std::strcmp(sub, "Sift") && std::strcmp(sub, "Sift1")) return bad(__func__, "sub must be Sift or Sift1");
+    if (n_frames < 1 || view_count < 1 || (int64_t)n_frames * view_count > 65535)
+        return bad(__func__, "need n_frames, view_count >= 1 and at most 65535 views");
+    const auto name = [view_count](int32_t c) {
+        char s[48];
+        std::snprintf(s, sizeof s, "proj%d_%d.jpg", c / view_count, c % view_count);                // FeatureProc.cpp:71, Processor.cpp:612
+        return std::string(s);
+    };
+    return sift_overlay_streams(__func__, n_frames * view_count, w, h, views, key_offsets, keys, flags, params,
+                                overlay_files(__func__, join(seq_dir, (std::string("Views/") + sub + "/").c_str()), name));
+}
+
 int mvs_processor_point_sample(int32_t n_seq, const char* const* seq_dirs, const int32_t* cam_off, const mvs_camera* cams,
                                const mvs_point_sample_params* params, const char* const* npts_paths, int64_t* n_points) {
     MVS_TRACE();

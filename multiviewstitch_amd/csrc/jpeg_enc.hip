@@ -459,6 +459,20 @@ int jpeg_encode_host(const char* fn, int32_t n, int32_t w, int32_t h, const uint
     data->resize((size_t)offsets[n]);
     return down(data->data(), dout, data->size());
 }
+int jpeg_encode_check(const char* fn, int32_t w, int32_t h, uint32_t flags, const mvs_jpeg_encode_params* p) {
+    JePlan pl;
+    return je_plan(fn, 1, w, h, flags, p, &pl);
+}
+// mvs_jpeg_encode_dev under the name fn with an output that sizes itself: dout receives offsets[n] bytes
+int jpeg_encode_dev_own(const char* fn, int32_t n, int32_t w, int32_t h, const uint8_t* imgs_dev, uint32_t flags, const mvs_jpeg_encode_params* p,
+                        int64_t* offsets, Scratch* dout, hipStream_t s) {
+    JePlan pl;
+    int rc = je_plan(fn, n, w, h, flags, p, &pl);
+    if (rc) return rc;
+    if (!imgs_dev || !offsets || !dout) return bad(fn, "imgs_dev, offsets or the output block is NULL");
+    if ((rc = need_device())) return rc;
+    return je_run(fn, pl, imgs_dev, offsets, nullptr, 0, dout, s, nullptr);
+}
 // mvs_depth_preview's host form
 int depth_preview_host(const char* fn, int32_t n, int32_t w, int32_t h, const float* depths, uint8_t* out) {
     int rc = dp_check(fn, n, w, h, depths, out);

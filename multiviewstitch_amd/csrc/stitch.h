@@ -2,6 +2,7 @@
 #ifndef MVS_STITCH_H_
 #define MVS_STITCH_H_
 #include "engine.h"
+#include <functional>
 
 // visibility cull of the points of n_seg segments (seg_off: host, n_seg + 1, from 0); mode = enum mvs_cull_mode; the keep mask goes
 // to keep_u8 or, when it is not NULL, keep_i32 (device, P entries); n_keep (host, n_seg) receives the kept counts.  Synchronises s.
@@ -43,6 +44,22 @@ int jpeg_encode_host(const char* fn, int32_t n, int32_t w, int32_t h, const uint
                      int64_t* offsets, std::vector<uint8_t>* data);
 // mvs_depth_preview's host form (jpeg_enc.hip) under the name fn
 int depth_preview_host(const char* fn, int32_t n, int32_t w, int32_t h, const float* depths, uint8_t* out);
+// E1 of mvs_jpeg_encode for images of w x h under the name fn, nothing else (jpeg_enc.hip): no device needed
+int jpeg_encode_check(const char* fn, int32_t w, int32_t h, uint32_t flags, const mvs_jpeg_encode_params* p);
+// mvs_jpeg_encode_dev under the name fn with an output that sizes itself (jpeg_enc.hip): dout receives a device block of offsets[n] bytes
+// that holds the streams.  Complete on return
+int jpeg_encode_dev_own(const char* fn, int32_t n, int32_t w, int32_t h, const uint8_t* imgs_dev, uint32_t flags, const mvs_jpeg_encode_params* p,
+                        int64_t* offsets, Scratch* dout, hipStream_t s);
+// The overlay pictures as JPEG streams (overlay.hip), validating and reporting under the name fn: the canvases are drawn and encoded in
+// batches under the byte budget MVS_OVERLAY_BATCH_BYTES, each batch one draw launch into HBM and one encoder call; sink(first, count, off,
+// data) receives the streams of canvases first .. first + count - 1 (host: canvas first + i at data[off[i] .. off[i + 1])) and returns a
+// status that ends the call when it is not MVS_OK.  Nothing of a batch reaches the sink when its encode fails.  Arguments as
+// mvs_processor_match_overlays / mvs_processor_sift_overlays (n = n_frames * view_count)
+using OverlaySink = std::function<int(int32_t first, int32_t count, const int64_t* off, const uint8_t* data)>;
+int match_overlay_streams(const char* fn, int32_t n1, int32_t n2, int32_t w, int32_t h, const uint8_t* imgs1, const uint8_t* imgs2, const int64_t* moff,
+                          const int32_t* matches, uint32_t flags, uint64_t* rng_state, const mvs_jpeg_encode_params* params, const OverlaySink& sink);
+int sift_overlay_streams(const char* fn, int32_t n, int32_t w, int32_t h, const uint8_t* views, const int64_t* koff, const float* keys, uint32_t flags,
+                         const mvs_jpeg_encode_params* params, const OverlaySink& sink);
 // One call of the Poisson stage (poisson.hip), whichever entry made it: `rules` says which of mvs_poisson_reconstruct (PN_PLAIN),
 // _density (PN_DENSITY: dp and dinfo) and _screened (PN_SCREENED: sp and sinfo too) it is; the parts it does not have are NULL.  The
 // points are the entry's own, host or device.

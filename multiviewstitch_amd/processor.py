@@ -9,7 +9,8 @@ matching between them, FeatureProc::MatchFeature (R/FeatureProc/FeatureProc.cpp:
 detection in front of the cull, FeatureProc::DetectFeature (:14-75,103-112), through ``mvs_sift_detect``; the point sampling between
 ``CheckConsistency`` and the stitch tail, GeometryRec::RunPointSample (R/Processor/Processor.cpp:933-949), through ``mvs_point_sample``;
 the surface reconstruction between the stitch tail and the trim of the model, GeometryRec::RunPoisson (:1042-1058), through
-``mvs_poisson_reconstruct``.  The functions stand in pipeline order."""
+``mvs_poisson_reconstruct``; the match and SIFT overlay pictures (:767-793, :604-615, FeatureProc.cpp:67-73) through
+``mvs_match_overlays`` / ``mvs_sift_overlays`` and their file forms.  The functions stand in pipeline order."""
 from __future__ import annotations
 
 import contextlib
@@ -564,7 +565,21 @@ def SequencePairSRT(cams1, cams2, depths1, depths2, raw, tex1, tex2, imgs1, imgs
                 scale=s.value, R=R, t=t, residual=res.value, stage_counts=cnt, matches=sel[:ns.value].copy())
 
 
-def CalcSimilarityTransformationSeq(sequences, params: dict, state, srt_txt=None):
+def _pair_match_pictures(match_dir, k, a, b, raw, params):
+    """``match_dir``match<k>_<i>_<j>.jpg of sequence pair k (R/Processor/Processor.cpp:767-793) from the lists ``MatchFilterPairs`` returns for
+    the pair's inputs: the valid masks as ``mvs_sequence_pair_srt`` forms them (inside [min_dsp, max_dsp], compared in double), so the
+    lists are the bits the chain used; one fresh ``cv::RNG`` per sequence pair (:768)."""
+    mn, mx = float(params["min_dsp"]), float(params["max_dsp"])
+    valid = []
+    for s in (a, b):
+        d = L.arr(s["depths"], np.float32).astype(np.float64)
+        valid.append((~((d < mn) | (d > mx))).astype(np.uint8).reshape(len(d), -1))
+    matches, _ = MatchFilterPairs(raw, a["tex"], valid[0], b["tex"], valid[1], a["imgs"], b["imgs"], params["ssd_win"], params["ssd_err"],
+                                  params["sample_interval"])
+    MatchOverlayFiles(match_dir, k, a["imgs"], b["imgs"], matches)
+
+
+def CalcSimilarityTransformationSeq(sequences, params: dict, state, srt_txt=None, match_dir=None):
     """The loop over adjacent sequences of Processor::CalcSimilarityTransformationSeq (R/Processor/Processor.cpp:629-826) and the chain
     AlignmentSeq makes of it (:851-871).  ``sequences[k]`` = dict(cameras, depths, tex, imgs) of sequence k, plus ``raw`` (raw[i][j],
     the matches towards sequence k + 1) for every sequence but the last; ``params`` = the keyword arguments of ``SequencePairSRT``
@@ -573,7 +588,11 @@ def CalcSimilarityTransformationSeq(sequences, params: dict, state, srt_txt=None
     ``distmax``, ``ratiomax`` and ``max_sift`` are then taken out of ``params`` (:634).  One ``SequencePairSRT`` per adjacent pair with ONE rand() stream
     through all of them: ``state`` is the srand seed — an int, or a one-element uint32 numpy array that receives the advanced state.
     After pair k every earlier entry is composed with it (:819-823); identity is appended for the last sequence (:851-853);
-    ``srt_txt`` (a path) writes the chain as SRT.txt (:855-871).
+    ``srt_txt`` (a path) writes the chain as SRT.txt (:855-871).  ``match_dir`` (a path; the reference's is ./Match/) writes pair k's
+    match pictures match<k>_<i>_<j>.jpg (:767-793, ``MatchOverlayFiles``) in front of pair k's fit, so they exist when the fit raises, as
+    in the reference.  One deviation: the reference draws the lists after ``RemoveOutliers`` for the pairs that reached it;
+    ``mvs_sequence_pair_srt`` does not hand out those masks, so the pictures show every pair's list as the match filter left it.  With
+    the default None nothing is drawn and nothing changes.
     -> (scales [n], Rs [n, 3, 3], ts [n, 3], select_frames [(frm_idx1, frm_idx2)] per pair): the input of ``StitchPointSets``."""
     st = int(np.asarray(state).reshape(-1)[0])
     params = dict(params)
@@ -582,6 +601,8 @@ def CalcSimilarityTransformationSeq(sequences, params: dict, state, srt_txt=None
     for k in range(len(sequences) - 1):
         a, b = sequences[k], sequences[k + 1]
         raw = a["raw"] if "raw" in a else MatchFeature(a["keys"], a["descs"], b["keys"], b["descs"], int(np.asarray(a["tex"]).shape[1]), **match)
+        if match_dir is not None:
+            _pair_match_pictures(match_dir, k, a, b, raw, params)
         r = SequencePairSRT(a["cameras"], b["cameras"], a["depths"], b["depths"], raw, a["tex"], b["tex"], a["imgs"], b["imgs"],
                             state=st, **params)
         st = r["state"]
@@ -1278,6 +1299,154 @@ def DepthPreviewFiles(seq_dir, sub: str, n: int, w: int, h: int, quality: int = 
     (grey) of ``DepthPreview`` of the rasters.  ``sub`` is "CHECK", "Render" or "Refine"."""
     prm = jpeg_encode_params(quality=int(quality), restart_interval=int(restart_interval))
     L.check(L.lib().mvs_processor_depth_previews(os.fsencode(seq_dir), os.fsencode(sub), int(n), int(w), int(h), C.byref(prm)))
+
+
+# ------------------------------------------------------------------ overlay pictures ----
+def draw_prim(kind: int, x0: int, y0: int, x1: int = 0, y1: int = 0, size: int = 1, colour=(0, 0, 0)):
+    """one ``mvs_draw_prim`` as a record of ``L.DRAW_PRIM_DTYPE``: ``kind`` is ``L.DRAW_DISC`` / ``L.DRAW_RING`` (centre (x0, y0), radius
+    ``size``) or ``L.DRAW_SEGMENT`` ((x0, y0) - (x1, y1), thickness ``size``); ``colour`` in the canvas's channel order"""
+    return (int(x0), int(y0), int(x1), int(y1), int(kind), int(size), tuple(int(c) for c in colour), (0, 0, 0))
+
+
+def cv_rng_colours(n: int, state: int = 0xFFFFFFFF):
+    """``mvs_cv_rng_colours`` (rule O6 of include/mvs.h; host code): the next ``n`` line colours of the ``cv::RNG`` at ``state`` (default: a
+    fresh generator) -> (bgr uint8 [n, 3], the advanced state)."""
+    st = C.c_uint64(int(state))
+    out = np.zeros((max(1, int(n)), 3), np.uint8)
+    L.lib().mvs_cv_rng_colours(C.byref(st), int(n), L.ptr(out))
+    return out[:max(0, int(n))].copy(), int(st.value)
+
+
+def _lists(lists, n, dtype, cols, what):
+    """``lists[i]`` = the rows of list i -> (offsets int64 [n + 1], all rows back to back)"""
+    if len(lists) != n:
+        raise L.MvsError(-1, f"{what}: {len(lists)} lists for {n} canvases")
+    flat = [np.asarray(p, dtype=dtype).reshape((-1,) + cols) for p in lists]
+    off = np.zeros(n + 1, np.int64)
+    off[1:] = np.cumsum([len(p) for p in flat])
+    allr = np.ascontiguousarray(np.concatenate(flat)) if off[-1] else np.zeros((0,) + cols, dtype)
+    return off, allr
+
+
+def _canvas_io(imgs, device, stream, in_place, out_shape=None):
+    """the pixels of an overlay call where they are to be worked on -> (source, output, device form?): numpy arrays, or torch tensors on
+    the GPU allocated in the order of ``stream``; ``in_place`` makes the output the source (``out == in``)"""
+    if device is None and not _is_dev(imgs):
+        src = L.arr(imgs, np.uint8)
+        return src, np.empty(out_shape or src.shape, np.uint8), False
+    import torch
+    with _stream_order(stream):
+        src = imgs if _is_dev(imgs) else torch.as_tensor(L.arr(imgs, np.uint8)).to(device)
+        out = src if in_place and out_shape is None else torch.empty(out_shape or tuple(src.shape), dtype=torch.uint8, device=src.device)
+    return src, out, True
+
+
+def DrawOverlays(imgs, prims, device=None, stream: int | None = None, in_place: bool = False):
+    """``mvs_draw_overlays``: ``imgs`` [n, h, w, 3] uint8 with ``prims[i]`` (records of ``draw_prim``) painted on canvas i in list order
+    (rules O1-O5 of include/mvs.h: discs, rings and thick segments, exact integer coverage, a later primitive over an earlier one), all
+    canvases in one launch.  A numpy array -> a numpy array; with ``device`` (a torch device), or ``imgs`` a contiguous tensor there, ->
+    a tensor (``mvs_draw_overlays_dev`` in the order of ``stream``; ``in_place`` paints into ``imgs`` itself)."""
+    src, out, dev = _canvas_io(imgs, device, stream, in_place)
+    if len(src.shape) != 4 or src.shape[3] != 3:
+        raise L.MvsError(-1, "imgs must be [n, h, w, 3] uint8")
+    n, h, w = (int(x) for x in src.shape[:3])
+    off, flat = _lists(prims, n, L.DRAW_PRIM_DTYPE, (), "DrawOverlays")
+    if not dev:
+        L.check(L.lib().mvs_draw_overlays(n, w, h, L.ptr(src), L.ptr(off), L.ptr(flat), L.ptr(out)))
+        return out
+    with _stream_order(stream):
+        L.check(L.lib().mvs_draw_overlays_dev(n, w, h, _dev_ptr(src, "uint8", "imgs"), L.ptr(off), L.ptr(flat), L.ptr(out), L.ptr(stream)))
+    return out
+
+
+def _match_lists(imgs1, imgs2, matches):
+    n1, n2 = int(imgs1.shape[0]), int(imgs2.shape[0])
+    if len(imgs1.shape) != 4 or imgs1.shape[3] != 3 or tuple(imgs1.shape[1:]) != tuple(imgs2.shape[1:]):
+        raise L.MvsError(-1, "imgs1 and imgs2 must be [frames, h, w, 3] uint8 of one size")
+    if len(matches) != n1 or any(len(row) != n2 for row in matches):
+        raise L.MvsError(-1, "matches must be matches[i][j], one list per frame pair")
+    off, flat = _lists([matches[i][j] for i in range(n1) for j in range(n2)], n1 * n2, np.int32, (4,), "matches")
+    return n1, n2, int(imgs1.shape[1]), int(imgs1.shape[2]), off, flat
+
+
+def _rng_state(rng_state):
+    """None (a fresh default generator, NULL) or a one-element uint64 numpy array that the call advances"""
+    if rng_state is None:
+        return None
+    if not isinstance(rng_state, np.ndarray) or rng_state.dtype != np.uint64 or rng_state.size != 1 or not rng_state.flags.c_contiguous:
+        raise L.MvsError(-1, "rng_state must be None or a one-element uint64 numpy array (it receives the advanced state)")
+    return rng_state
+
+
+def MatchOverlays(imgs1, imgs2, matches, rng_state=None, device=None, stream: int | None = None):
+    """``mvs_match_overlays``: the match pictures of R/Processor/Processor.cpp:767-793 for every frame pair of two adjacent sequences ->
+    [n1 * n2, 2 h, w, 3] uint8, canvas i * n2 + j = ``imgs1[i]`` over ``imgs2[j]`` (BGR, [frames, h, w, 3]) with two rings and a line
+    per match of ``matches[i][j]`` ((m, 4) int32 (u1, v1, u2, v2): what ``MatchFilterPairs`` returns), the line colours from one
+    ``cv::RNG`` through all pairs (``rng_state``: None for a fresh one, or a one-element uint64 array that is advanced by 6 draws per
+    match).  numpy in -> numpy out; with ``device``, or image tensors on the GPU, -> a tensor there (one launch stacks and draws)."""
+    if _is_dev(imgs1) != _is_dev(imgs2):
+        raise L.MvsError(-1, "imgs1 and imgs2 must both be tensors on the GPU or both arrays")
+    dev = device is not None or _is_dev(imgs1)
+    if not _is_dev(imgs1):
+        imgs1, imgs2 = L.arr(imgs1, np.uint8), L.arr(imgs2, np.uint8)
+    n1, n2, h, w, off, flat = _match_lists(imgs1, imgs2, matches)
+    st = _rng_state(rng_state)
+    if not dev:
+        out = np.empty((n1 * n2, 2 * h, w, 3), np.uint8)
+        L.check(L.lib().mvs_match_overlays(n1, n2, w, h, L.ptr(imgs1), L.ptr(imgs2), L.ptr(off), L.ptr(flat), L.ptr(st), L.ptr(out)))
+        return out
+    import torch
+    with _stream_order(stream):
+        a = imgs1 if _is_dev(imgs1) else torch.as_tensor(imgs1).to(device)
+        b = imgs2 if _is_dev(imgs2) else torch.as_tensor(imgs2).to(device)
+        out = torch.empty((n1 * n2, 2 * h, w, 3), dtype=torch.uint8, device=a.device)
+        L.check(L.lib().mvs_match_overlays_dev(n1, n2, w, h, _dev_ptr(a, "uint8", "imgs1"), _dev_ptr(b, "uint8", "imgs2"), L.ptr(off), L.ptr(flat),
+                                               L.ptr(st), L.ptr(out), L.ptr(stream)))
+    return out
+
+
+def SiftOverlays(views, keys, device=None, stream: int | None = None, in_place: bool = False):
+    """``mvs_sift_overlays``: the SIFT pictures of R/FeatureProc/FeatureProc.cpp:67-69: ``views`` [n, h, w, 3] uint8 with a filled
+    radius-1 mark in (0, 255, 0) at ``cvRound`` of the (x, y) of every key of ``keys[i]`` ((k, 4) float32 as ``DetectFeature`` returns
+    them).  numpy, or torch tensors with ``device`` as ``DrawOverlays``."""
+    src, out, dev = _canvas_io(views, device, stream, in_place)
+    if len(src.shape) != 4 or src.shape[3] != 3:
+        raise L.MvsError(-1, "views must be [n, h, w, 3] uint8")
+    n, h, w = (int(x) for x in src.shape[:3])
+    off, flat = _lists(keys, n, np.float32, (4,), "SiftOverlays")
+    if not dev:
+        L.check(L.lib().mvs_sift_overlays(n, w, h, L.ptr(src), L.ptr(off), L.ptr(flat), L.ptr(out)))
+        return out
+    with _stream_order(stream):
+        L.check(L.lib().mvs_sift_overlays_dev(n, w, h, _dev_ptr(src, "uint8", "views"), L.ptr(off), L.ptr(flat), L.ptr(out), L.ptr(stream)))
+    return out
+
+
+def MatchOverlayFiles(match_dir, k: int, imgs1, imgs2, matches, rng_state=None, quality: int = 95, sampling="420", restart_interval: int = 0,
+                      order: str = "BGR") -> None:
+    """``mvs_processor_match_overlays``: the pictures of ``MatchOverlays`` for sequence pair ``k`` -> ``match_dir``match<k>_<i>_<j>.jpg
+    (R/Processor/Processor.cpp:787; the reference's directory is ./Match/), the bytes ``EncodeJpegs`` returns for the canvases.  Drawn and
+    encoded on the GPU in batches under MVS_OVERLAY_BATCH_BYTES; only the streams come back.  With ``order`` "RGB" the colours are
+    written the other way round: the picture is the same."""
+    imgs1, imgs2 = L.arr(imgs1, np.uint8), L.arr(imgs2, np.uint8)
+    n1, n2, h, w, off, flat = _match_lists(imgs1, imgs2, matches)
+    prm = jpeg_encode_params(quality=int(quality), sampling=_SAMPLING.get(sampling, -1), restart_interval=int(restart_interval))
+    L.check(L.lib().mvs_processor_match_overlays(os.fsencode(match_dir), int(k), n1, n2, w, h, L.ptr(imgs1), L.ptr(imgs2), L.ptr(off), L.ptr(flat),
+                                                 _jpeg_order(order), L.ptr(_rng_state(rng_state)), C.byref(prm)))
+
+
+def SiftOverlayFiles(seq_dir, sub: str, views, keys, quality: int = 95, sampling="420", restart_interval: int = 0, order: str = "BGR") -> None:
+    """``mvs_processor_sift_overlays``: ``views`` [frames, view_count, h, w, 3] with the marks of ``SiftOverlays`` for ``keys[i * view_count
+    + j]`` -> ``seq_dir``Views/``sub``/proj<i>_<j>.jpg; ``sub`` is "Sift" (FeatureProc.cpp:67-73) or "Sift1" (after the background
+    cull, Processor.cpp:604-615)."""
+    v = L.arr(views, np.uint8)
+    if v.ndim != 5 or v.shape[4] != 3:
+        raise L.MvsError(-1, "views must be [frames, view_count, h, w, 3] uint8")
+    f, vc, h, w = (int(x) for x in v.shape[:4])
+    off, flat = _lists(keys, f * vc, np.float32, (4,), "SiftOverlayFiles")
+    prm = jpeg_encode_params(quality=int(quality), sampling=_SAMPLING.get(sampling, -1), restart_interval=int(restart_interval))
+    L.check(L.lib().mvs_processor_sift_overlays(os.fsencode(seq_dir), os.fsencode(sub), f, vc, w, h, L.ptr(v), L.ptr(off), L.ptr(flat),
+                                                _jpeg_order(order), C.byref(prm)))
 
 
 def LoadImages(seq_dirs, cameras, order: str = "BGR") -> list:

@@ -723,6 +723,77 @@ int mvs_refine_depth_maps_dev(int32_t n_seq, const int32_t* cam_off, const mvs_c
                               const float* depths_dev, const mvs_depth_refine_params* p, float* out_dev, int8_t* k_out_dev,
                               int32_t* sum_out_dev, uint8_t* cnt_out_dev, void* hip_stream);
 
+/* ------------------------------------------------- depth recovery (DATA/_depth<i>.raw from the images) -- */
+/* The one input of the reference's `-a 1` run that no program of the reference writes: the first inverse-depth rasters
+ * DATA/_depth<i>.raw of every sequence, which Processor::CheckConsistency reads (Processor.cpp:37-38).  mvs_refine_depth_maps searches
+ * a few per cent around an existing value and cannot start a sequence; this call has no input raster: a plane sweep over `levels`
+ * disparities of [dsp_min, dsp_max], scored as the refinement scores its hypotheses.  The rules R1-R9 below are this library's
+ * definition, NOT VERIFIED against any ZJU code.  levels, peak and min_refs are choices: nobody has measured them on a real sequence.
+ * Input: n_seq, cam_off, cams and imgs as mvs_refine_depth_maps (the frames of one sequence share one raster size; sequences may
+ * differ; imgs holds the RGB base images of all cameras back to back in camera order).  out: float32 inverse-depth rasters in camera
+ * order.  All floating-point arithmetic is fp64 + - * / sqrt in the order written (the library is built with -ffp-contract=off); the
+ * camera maps and the double -> int rule are those of mvs_point_sample.  Every cost is an exact integer.
+ * For frame f of a sequence of n frames, with N = ssd_win, len = 2 N + 1, L = levels:
+ *   R1 grey       : G_f[v][u] = (4899 * p0 + 9617 * p1 + 1868 * p2 + 8192) >> 14 of the pixel's three bytes in memory order, the
+ *                   integer conversion of mvs_match_filter.
+ *   R2 references : g = f - ref_frm_count / 2 + i for i = 0 .. ref_frm_count - 1, kept when 0 <= g < n and g != f, in ascending order.
+ *   R3 candidates : every pixel with N <= u < w - N and N <= v < h - N is a candidate.  Any other pixel gets out = +0.0f, level = -1,
+ *                   sum = -1, cnt = 0.
+ *   R4 levels     : step = (dsp_max - dsp_min) / (double)(L - 1); d_l = dsp_min + (double)l * step for l < L - 1 and d_{L-1} = dsp_max
+ *                   exactly.  The levels are uniform in disparity, so a reference pixel moves by equal amounts per level.
+ *   R5 cost       : for a level l and a reference g: P = world_from_img(cam_f, u, v, 1.0 / d_l), Xc = R_g P + t_g.  The reference
+ *                   counts when Xc.z > 0 and (u', v') = (int(fx Xc.x / Xc.z + cx + 0.5), v' likewise) has N <= u' < w - N,
+ *                   N <= v' < h - N.  It then contributes ssd_g = the sum over a, b in [-N, N] of (G_f[v+a][u+b] - G_g[v'+a][u'+b])^2,
+ *                   an exact integer.  sum_l is the sum of the ssd_g that count, cnt_l how many did.
+ *   R6 choice     : level l is eligible when cnt_l >= min_refs.  l beats j when sum_l * cnt_j < sum_j * cnt_l in int64; on equality
+ *                   the lower l wins.  The worst eligible level W is found by the same comparison reversed; on equality the lower l
+ *                   is W.  A pixel without an eligible level is treated as in R3.
+ *   R7 acceptance : with m = (double)sum / (double)cnt of the winner l* and m_W of W, the pixel is accepted when both
+ *                   sqrt(m / (double)(len * len)) <= ssd_err and m < peak * m_W hold.  A flat cost curve says nothing: an image of
+ *                   one colour rejects every pixel, and so does a pixel with one eligible level.  A rejected pixel gets out = +0.0f
+ *                   and level = -1; its sum and cnt still report the winner.
+ *   R8 substep    : (MVS_RECOVER_SUBSTEP) when l* - 1 and l* + 1 both lie in [0, L - 1] and are eligible, c-, c0, c+ are their m
+ *                   values and den = (c- - 2.0 * c0) + c+.  If den > 0: o = 0.5 * ((c- - c+) / den) and d = dsp_min + ((double)l* + o)
+ *                   * step.  If that d is not in [dsp_min, dsp_max], or den <= 0, or the substep does not apply, d = d_l*.
+ *   R9 value      : out = (float)d.  If (double)out < dsp_min, out becomes the next float32 above; if (double)out > dsp_max, the next
+ *                   float32 below.  Every accepted pixel is therefore a valid value for mvs_check_consistency, the model loader and
+ *                   mvs_point_sample under the same range.
+ * Every frame reads only images; a sequence does not see another sequence.  It follows that a sequence of one frame, or
+ * ref_frm_count = 1, or min_refs above the references a frame has, rejects every pixel.
+ * The result is defined by integers and by fp64 operations in a stated order: no schedule can change a byte, and two runs give the same
+ * bytes.  The work is three launches without atomics: the grey rasters of all images, the sum of squares over the window of every
+ * pixel (both shared with the refinement), and the sweep of all frames of all sequences, a thread per pixel walking every level.
+ * level_out (int16), sum_out (int32) and cnt_out (uint8), one entry per pixel in raster order, are optional.  Scratch comes from the
+ * stream-ordered pool as for the refinement: 5 bytes per pixel, 140 bytes per camera and 32 bytes per sequence; the host form adds the
+ * images and the outputs.
+ * MVS_E_INVALID_ARG, before a device is needed: a NULL pointer other than the optional outputs, n_seq < 1, cam_off not ascending from
+ * 0, a camera with w or h <= 0 or fx or fy == 0, two raster sizes inside one sequence, w * h of a frame above 2^31 - 1, a parameter
+ * that is not finite, dsp_min <= 0 or dsp_min >= dsp_max, ssd_err < 0, peak outside (0, 1], ssd_win outside [0, 15], ref_frm_count
+ * outside [1, 9] or even, levels outside [2, 1024], min_refs outside [1, 8], unknown flag bits, reserved != 0, and too many workgroups
+ * for one launch. */
+#define MVS_RECOVER_SUBSTEP 1
+typedef struct mvs_depth_recover_params {  /* 56 bytes */
+    double  dsp_min, dsp_max;   /* MinDsp 0.0025, MaxDsp 0.3                                     */
+    double  ssd_err;            /* SSDError 40.0                                                 */
+    double  peak;               /* 0.9: the winner's mean cost must lie below peak * the worst; (0, 1].  A choice, not measured */
+    int32_t ssd_win;            /* SSDWin 7: N, the window is (2N+1)^2; 0..15                    */
+    int32_t ref_frm_count;      /* refFrmCount 5 (DepthOptimizer.cpp:45); odd, 1..9              */
+    int32_t levels;             /* 128: L disparity levels; 2..1024.  A choice, not measured     */
+    int32_t min_refs;           /* 2: references a level needs to be eligible; 1..8.  A choice, not measured */
+    int32_t flags;              /* MVS_RECOVER_SUBSTEP = 1                                       */
+    int32_t reserved;           /* 0                                                             */
+} mvs_depth_recover_params;
+/* the values in the comments above; flags = MVS_RECOVER_SUBSTEP */
+void mvs_depth_recover_default_params(mvs_depth_recover_params* p);
+int mvs_recover_depth_maps(int32_t n_seq, const int32_t* cam_off /*n_seq+1*/, const mvs_camera* cams, const uint8_t* imgs,
+                           const mvs_depth_recover_params* p, float* out, int16_t* level_out /*or NULL*/, int32_t* sum_out /*or NULL*/,
+                           uint8_t* cnt_out /*or NULL*/);
+/* images and outputs in HBM, in the order of hip_stream (may be NULL); cam_off and cams stay host arrays; returns with the work
+ * complete */
+int mvs_recover_depth_maps_dev(int32_t n_seq, const int32_t* cam_off, const mvs_camera* cams, const uint8_t* imgs_dev,
+                               const mvs_depth_recover_params* p, float* out_dev, int16_t* level_out_dev, int32_t* sum_out_dev,
+                               uint8_t* cnt_out_dev, void* hip_stream);
+
 /* ------------------------------------------------- base images (cv::imread of <imgdir>%05d.jpg) -- */
 /* The batched baseline JPEG decoder: the frames the reference opens with cv::imread (R/Image3D/Image3D.cpp:21, R/Processor/Processor.cpp:
  * 532,545, R/FeatureProc/FeatureProc.cpp:26, R/DepthRecovery/DepthOptimizer.cpp:13-14), all images of a call through each kernel in one

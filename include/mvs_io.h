@@ -116,6 +116,17 @@ int mvs_processor_load_images(int32_t n_seq, const char* const* seq_dirs, const 
 int mvs_processor_refine_depths_files(int32_t n_seq, const char* const* seq_dirs, const int32_t* cam_off, const mvs_camera* cams,
                                       const mvs_depth_refine_params* params);
 
+/* mvs_recover_depth_maps on files: the first rasters of every sequence, seq_dirs[k]/DATA/_depth<i>.raw for its cameras i — what
+ * Processor::CheckConsistency reads (Processor.cpp:37-38) and no program of the reference writes.  All sequences are recovered in one
+ * call and written with mvs_depth_raw_write; the directory is created as CreateDir does (a '/' is inserted after seq_dirs[k] when it
+ * lacks one).  imgs holds the RGB base images of all cameras back to back in camera order, each h x w x 3 bytes, in memory.  params may
+ * be NULL (defaults).  Nothing is written when the call fails.  Not written: the _depth<i>.jpg previews. */
+int mvs_processor_recover_depths(int32_t n_seq, const char* const* seq_dirs, const int32_t* cam_off, const mvs_camera* cams,
+                                 const uint8_t* imgs, const mvs_depth_recover_params* params);
+/* mvs_processor_recover_depths with the RGB frames read by mvs_processor_load_images from the same seq_dirs. */
+int mvs_processor_recover_depths_files(int32_t n_seq, const char* const* seq_dirs, const int32_t* cam_off, const mvs_camera* cams,
+                                       const mvs_depth_recover_params* params);
+
 /* cv::imwrite of the generated views (R/Image3D/Image3D.cpp:218-219): view j of frame i of `views` (what mvs_gen_new_views returned:
  * n_frames x view_count x h x w x 3 bytes, host; flags MVS_JPEG_BGR or MVS_JPEG_RGB say their order) goes to <seq_dir>Views/proj<i>_<j>.jpg
  * (a '/' is inserted after seq_dir when it lacks one; the directory is created).  All views are encoded in one mvs_jpeg_encode (rules

@@ -83,6 +83,13 @@ class CDepthRefineParams(C.Structure):
                 ("ssd_win", C.c_int32), ("ref_frm_count", C.c_int32), ("steps", C.c_int32), ("flags", C.c_int32)]
 
 
+class CDepthRecoverParams(C.Structure):
+    """struct mvs_depth_recover_params."""
+    _fields_ = [("dsp_min", C.c_double), ("dsp_max", C.c_double), ("ssd_err", C.c_double), ("peak", C.c_double),
+                ("ssd_win", C.c_int32), ("ref_frm_count", C.c_int32), ("levels", C.c_int32), ("min_refs", C.c_int32), ("flags", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class CJpegInfo(C.Structure):
     """struct mvs_jpeg_info_t."""
     _fields_ = [(k, C.c_int32) for k in ("w", "h", "components", "h_samp", "v_samp", "restart_interval", "n_segments", "sof")]
@@ -225,6 +232,9 @@ _SIGS = {
     "mvs_depth_refine_default_params": (None, [_VP]),
     "mvs_refine_depth_maps": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mvs_refine_depth_maps_dev": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "mvs_depth_recover_default_params": (None, [_VP]),
+    "mvs_recover_depth_maps": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "mvs_recover_depth_maps_dev": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mvs_jpeg_info": (C.c_int, [_VP, _I64, _VP]),
     "mvs_jpeg_decode": (C.c_int, [_I32, _VP, _VP, _U32, _VP]),
     "mvs_jpeg_decode_dev": (C.c_int, [_I32, _VP, _VP, _U32, _VP, _VP]),
@@ -359,6 +369,8 @@ _SIGS = {
     "mvs_processor_refine_depths": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP]),
     "mvs_processor_load_images": (C.c_int, [_I32, _VP, _VP, _VP, _U32, _VP]),
     "mvs_processor_refine_depths_files": (C.c_int, [_I32, _VP, _VP, _VP, _VP]),
+    "mvs_processor_recover_depths": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP]),
+    "mvs_processor_recover_depths_files": (C.c_int, [_I32, _VP, _VP, _VP, _VP]),
     "mvs_processor_point_sample": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mvs_processor_poisson": (C.c_int, [C.c_char_p, _VP, C.c_char_p, _VP, _VP]),
     "mvs_processor_poisson_density": (C.c_int, [C.c_char_p, _VP, _VP, _D, C.c_char_p, _VP, _VP]),
@@ -433,6 +445,7 @@ STITCH_TRUNCATE = 1                         # MVS_STITCH_TRUNCATE (include/mvs_i
 JPEG_BGR, JPEG_RGB = 0, 1                   # MVS_JPEG_BGR, MVS_JPEG_RGB (include/mvs.h)
 JPEG_GREY, JPEG_RESTART_ROW = 2, 65536      # MVS_JPEG_GREY, MVS_JPEG_RESTART_ROW
 REFINE_SUBSTEP = 1                          # MVS_REFINE_SUBSTEP (include/mvs.h)
+RECOVER_SUBSTEP = 1                         # MVS_RECOVER_SUBSTEP (include/mvs.h)
 
 
 def cam_array(cameras):

@@ -472,6 +472,54 @@ int mvs_processor_refine_depths_files(int32_t n_seq, const char* const* seq_dirs
     return refine_depths_body(__func__, n_seq, seq_dirs, cam_off, cams, imgs.data(), params, px);
 }
 
+// mvs_recover_depth_maps -> DATA/_depth<i>.raw for checked arguments, under the name fn; nothing is written when the call fails
+static int recover_depths_body(const char* fn, int32_t n_seq, const char* const* seq_dirs, const int32_t* cam_off, const mvs_camera* cams,
+                               const uint8_t* imgs, const mvs_depth_recover_params* params, size_t floats) {
+    int rc;
+    mvs_depth_recover_params prm;
+    if (params) prm = *params; else mvs_depth_recover_default_params(&prm);
+    std::vector<float> out(floats ? floats : 1);
+    if ((rc = recover_depth_maps_host(fn, n_seq, cam_off, cams, imgs, &prm, out.data(), nullptr, nullptr, nullptr))) return rc;
+    std::vector<double> raw;
+    size_t at = 0;
+    for (int k = 0; k < n_seq; ++k) {                                                             // what Processor.cpp:37-38 reads
+        if (cam_off[k + 1] == cam_off[k]) continue;
+        const std::string dir = join(seq_dirs[k], "DATA/");
+        if ((rc = make_dirs(dir))) return rc;
+        for (int c = cam_off[k]; c < cam_off[k + 1]; ++c) {
+            const size_t npx = (size_t)cams[c].w * (size_t)cams[c].h;
+            raw.assign(out.begin() + (std::ptrdiff_t)at, out.begin() + (std::ptrdiff_t)(at + npx));
+            char name[32];
+            std::snprintf(name, sizeof name, "_depth%d.raw", c - cam_off[k]);
+            if ((rc = mvs_depth_raw_write((dir + name).c_str(), (int64_t)npx, raw.data()))) return rc;
+            at += npx;
+        }
+    }
+    return MVS_OK;
+}
+
+int mvs_processor_recover_depths(int32_t n_seq, const char* const* seq_dirs, const int32_t* cam_off, const mvs_camera* cams, const uint8_t* imgs,
+                                 const mvs_depth_recover_params* params) {
+    MVS_TRACE();
+    if (n_seq < 1) return bad(__func__, "n_seq must be >= 1");
+    if (!seq_dirs || !cam_off || !cams || !imgs) return bad(__func__, "seq_dirs, cam_off, cams and imgs must not be NULL");
+    size_t floats = 0;
+    int rc = check_seq_dirs(__func__, n_seq, seq_dirs, cam_off, cams, &floats);
+    if (rc) return rc;
+    return recover_depths_body(__func__, n_seq, seq_dirs, cam_off, cams, imgs, params, floats);
+}
+
+int mvs_processor_recover_depths_files(int32_t n_seq, const char* const* seq_dirs, const int32_t* cam_off, const mvs_camera* cams,
+                                       const mvs_depth_recover_params* params) {
+    MVS_TRACE();
+    size_t px = 0;
+    int rc = check_seq_dirs(__func__, n_seq, seq_dirs, cam_off, cams, &px);
+    if (rc) return rc;
+    std::vector<uint8_t> imgs(px ? 3 * px : 1);
+    if ((rc = load_images_body(__func__, n_seq, seq_dirs, cam_off, cams, MVS_JPEG_RGB, imgs.data()))) return rc;
+    return recover_depths_body(__func__, n_seq, seq_dirs, cam_off, cams, imgs.data(), params, px);
+}
+
 // stream i = data[off[i] .. off[i + 1]) to path[i], on up to 16 host threads; the first file that fails is reported
 static int write_streams(const char* fn, const std::vector<std::string>& path, const int64_t* off, const uint8_t* data) {
     const int n = (int)path.size();

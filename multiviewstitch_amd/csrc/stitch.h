@@ -31,6 +31,9 @@ int point_sample_vectors(const char* fn, int32_t n_seq, const int32_t* cam_off, 
 // mvs_refine_depth_maps's host form (depth_refine.hip), validating and reporting under the name fn
 int refine_depth_maps_host(const char* fn, int32_t n_seq, const int32_t* cam_off, const mvs_camera* cams, const uint8_t* imgs, const float* depths,
                            const mvs_depth_refine_params* p, float* out, int8_t* k_out, int32_t* sum_out, uint8_t* cnt_out);
+// mvs_recover_depth_maps's host form (depth_recover.hip), validating and reporting under the name fn
+int recover_depth_maps_host(const char* fn, int32_t n_seq, const int32_t* cam_off, const mvs_camera* cams, const uint8_t* imgs,
+                            const mvs_depth_recover_params* p, float* out, int16_t* level_out, int32_t* sum_out, uint8_t* cnt_out);
 // mvs_jpeg_decode's host form (jpeg.hip) under the name fn; w / h (may be NULL) receive the size; imgs == NULL: the header walk and the
 // checks only, no device needed
 int jpeg_decode_host(const char* fn, int32_t n, const int64_t* offsets, const uint8_t* data, uint32_t flags, uint8_t* imgs, int32_t* w, int32_t* h);

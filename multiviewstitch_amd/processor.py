@@ -2,7 +2,8 @@
 ``Processor::AlignmentSeq`` (:952-1105) through ``mvs_processor_stitch_points`` / ``mvs_processor_cull_model``;
 ``Processor::Render`` (:1140-1192) through ``mvs_processor_render`` and its batched render ``mvs_render_depth_views``; the refinement of
 those renders against the images, DepthOptimizer::RefineAllDepthMaps (DepthRecovery/DepthOptimizer.cpp:20-43), through
-``mvs_refine_depth_maps``; the loop
+``mvs_refine_depth_maps``; the first rasters DATA/_depth<i>.raw, which the reference reads (:37-38) and never writes, through
+``mvs_recover_depth_maps``; the loop
 over adjacent sequences of ``Processor::CalcSimilarityTransformationSeq`` (:629-826) through ``mvs_sequence_pair_srt``; its head (:524-600)
 through ``mvs_gen_new_views`` (Image3D::GenNewViews) and ``mvs_keypoint_cull`` (the background cull of the key points); the descriptor
 matching between them, FeatureProc::MatchFeature (R/FeatureProc/FeatureProc.cpp:77-130), through ``mvs_sift_match_lists``; the SIFT
@@ -1127,6 +1128,86 @@ def RefineDepthFiles(seq_dirs, cameras, imgs, params: L.CDepthRefineParams | Non
     flat, iptr = _flat_stack(imgs, n, False, "uint8", "imgs")
     prm = params if params is not None else depth_refine_params()
     L.check(L.lib().mvs_processor_refine_depths(n, dirs, L.ptr(off), cams, iptr, C.byref(prm)))
+
+
+# ------------------------------------------------------------------ depth recovery ----
+def depth_recover_params(**kw) -> L.CDepthRecoverParams:
+    """``mvs_depth_recover_default_params`` (config.txt: MinDsp 0.0025, MaxDsp 0.3, SSDError 40, SSDWin 7; refFrmCount 5 of
+    DepthOptimizer.cpp:45; peak 0.9, levels 128, min_refs 2 — choices nobody has measured on a real sequence; flags
+    ``RECOVER_SUBSTEP``) with the given fields replaced."""
+    return _params(L.CDepthRecoverParams, L.lib().mvs_depth_recover_default_params, kw)
+
+
+def RecoverDepthMaps(cameras, imgs, params: L.CDepthRecoverParams | None = None, stream: int | None = None, with_detail: bool = False):
+    """The first inverse-depth rasters of every sequence from its images alone, in one call (``mvs_recover_depth_maps``; the rules
+    R1-R9, this library's definition: include/mvs.h): what the reference reads as DATA/_depth<i>.raw and never writes.  ``cameras[k]``
+    lists sequence k's cameras; ``imgs[k]`` is its RGB base images [frames, h, w, 3] uint8 — numpy arrays, or contiguous torch tensors
+    on the GPU (the device form: the results are tensors on the same device).  ``stream`` is the HIP stream that produced them (None:
+    the legacy default stream); the kernels, the concatenation of the sequences and the allocation of the results are all ordered on
+    it, whatever torch's current stream is.
+    -> a list with, per sequence, the rasters [frames, h, w] float32 (+0.0 where no level was accepted): what ``CheckConsistency``
+    reads.  With ``with_detail`` each entry is (rasters, level [frames, h, w] int16, sum int32, cnt uint8): the winning level of
+    every pixel (-1 where none was accepted), its sum of squared grey differences and the reference frames that took part."""
+    prm = params if params is not None else depth_recover_params()
+    n = len(cameras)
+    off, cams = L.seq_cams(cameras)
+    if len(imgs) != n:
+        raise L.MvsError(-1, f"{len(imgs)} image stacks for {n} sequences")
+    shapes = []
+    for k in range(n):
+        want = (len(cameras[k]),) + ((int(cameras[k][0].h), int(cameras[k][0].w)) if len(cameras[k]) else tuple(imgs[k].shape[1:3]))
+        if tuple(imgs[k].shape) != want + (3,):
+            raise L.MvsError(-1, f"imgs[{k}] must be [frames, h, w, 3] = {want + (3,)}")
+        shapes.append(want)
+    dev = n > 0 and all(_is_dev(a) for a in imgs)
+    if not dev and any(_is_dev(a) for a in imgs):
+        raise L.MvsError(-1, "imgs must all be tensors on the GPU or all arrays")
+    order = _stream_order(stream) if dev else contextlib.nullcontext()
+    with order:
+        fimg, iptr = _flat_stack(imgs, n, dev, "uint8", "imgs")
+        size = max(1, sum(int(np.prod(s, dtype=np.int64)) for s in shapes))
+        out = _out_like(fimg, size, "float32")
+        det = tuple(_out_like(fimg, size, dt) for dt in ("int16", "int32", "uint8")) if with_detail else (None, None, None)
+        fn, tail = (L.lib().mvs_recover_depth_maps_dev, (L.ptr(stream),)) if dev else (L.lib().mvs_recover_depth_maps, ())
+        L.check(fn(n, L.ptr(off), cams, iptr, C.byref(prm), L.ptr(out), *[L.ptr(a) for a in det], *tail))
+    res, at = [], 0
+    for shape in shapes:
+        m = int(np.prod(shape, dtype=np.int64))
+        cut = tuple(a[at:at + m].reshape(shape) for a in ((out,) + det if with_detail else (out,)))
+        res.append(cut if with_detail else cut[0])
+        at += m
+    return res
+
+
+def _recover_files_args(seq_dirs, cameras):
+    n = len(cameras)
+    if len(seq_dirs) != n:
+        raise L.MvsError(-1, f"{len(seq_dirs)} sequence dirs for {n} sequences")
+    off, cams = L.seq_cams(cameras)
+    return n, (C.c_char_p * max(1, n))(*[os.fsencode(d) for d in seq_dirs]), off, cams
+
+
+def RecoverDepthFiles(seq_dirs, cameras, imgs, params: L.CDepthRecoverParams | None = None) -> None:
+    """``mvs_processor_recover_depths``: ``RecoverDepthMaps`` of all sequences written to ``seq_dirs[k]``/DATA/_depth<i>.raw, the rasters
+    ``CheckConsistency`` on files reads.  ``cameras[k]`` lists sequence k's cameras, ``imgs[k]`` is its RGB base images
+    [frames, h, w, 3] uint8 in memory (``RecoverDepthFilesFromJpeg`` reads them from the sequence directories)."""
+    n, dirs, off, cams = _recover_files_args(seq_dirs, cameras)
+    if len(imgs) != n:
+        raise L.MvsError(-1, f"{len(imgs)} image stacks for {n} sequences")
+    for k in range(n):
+        want = (len(cameras[k]),) + ((int(cameras[k][0].h), int(cameras[k][0].w), 3) if len(cameras[k]) else tuple(imgs[k].shape[1:]))
+        if tuple(imgs[k].shape) != want:
+            raise L.MvsError(-1, f"imgs[{k}] must be [frames, h, w, 3] = {want}")
+    flat, iptr = _flat_stack(imgs, n, False, "uint8", "imgs")
+    prm = params if params is not None else depth_recover_params()
+    L.check(L.lib().mvs_processor_recover_depths(n, dirs, L.ptr(off), cams, iptr, C.byref(prm)))
+
+
+def RecoverDepthFilesFromJpeg(seq_dirs, cameras, params: L.CDepthRecoverParams | None = None) -> None:
+    """``mvs_processor_recover_depths_files``: ``RecoverDepthFiles`` with the RGB frames read from ``seq_dirs[k]``%05d.jpg."""
+    n, dirs, off, cams = _recover_files_args(seq_dirs, cameras)
+    prm = params if params is not None else depth_recover_params()
+    L.check(L.lib().mvs_processor_recover_depths_files(n, dirs, L.ptr(off), cams, C.byref(prm)))
 
 
 # ------------------------------------------------------------------ base images ----

@@ -794,6 +794,63 @@ int mvs_recover_depth_maps_dev(int32_t n_seq, const int32_t* cam_off, const mvs_
                                const mvs_depth_recover_params* p, float* out_dev, int16_t* level_out_dev, int32_t* sum_out_dev,
                                uint8_t* cnt_out_dev, void* hip_stream);
 
+/* ------------------------------------------------- vertex colours (the pictures back onto the stitched model) -- */
+/* The colour of every vertex of Model.obj / PSR%d.obj / deform.obj from the base images of all cameras of all sequences.  The reference
+ * has no such stage: the rules C1-C8 below are this library's definition, NOT VERIFIED against any ZJU code.  min_cos = 0.2, occ_tol =
+ * 0.01, the cos^2 weight and its 1/4096 quantum are choices: nobody has measured them on a real sequence.
+ * Input: V vertices and V normals (fp64) in the world frame; n_seq, the SRT chain (scales, R row-major, t; all NULL: the world frame),
+ * cam_off and cams as mvs_render_depth_views takes them; imgs[N][h][w][3] uint8 and depths[N][h][w] float32 inverse depth (or NULL) of
+ * all cameras back to back in camera order, N = cam_off[n_seq].  Every camera must have cams[0]'s size, w, h >= 2: the one viewport of
+ * mvs_render_depth_views, whose rasters are what depths is meant to hold.  All floating-point arithmetic is fp64 + - * / sqrt in the
+ * order written (the library is built with -ffp-contract=off); cvt_i32 is the double -> int rule of mvs_point_sample (truncation toward
+ * zero).  For vertex i (point p, normal n) and view (k, c), the views taken in camera order:
+ *   C1 map        : p' = (1 / s_k) R_k^T (p - t_k) and n' = R_k^T n, operation for operation as mvs_srt_apply(inverse = 1): M = (1.0 /
+ *                   s_k) * R_k^T element by element, p' = M (p - t_k), every row ((a x + b y) + c z).  Without a chain p and n as given.
+ *   C2 projection : q = R_c p' + t_c (the camera's map, rows as above, then + t).  The view is rejected unless q.z > 0.  x = fx * q.x /
+ *                   q.z + cx, y = fy * q.y / q.z + cy; rejected unless 0 <= x <= w - 1 and 0 <= y <= h - 1 (a NaN rejects).
+ *   C3 facing     : m = R_c n'; dot = -((m.x q.x + m.y q.y) + m.z q.z); cos = dot / sqrt(((m.x m.x + m.y m.y) + m.z m.z) * ((q.x q.x +
+ *                   q.y q.y) + q.z q.z)).  Rejected unless cos >= min_cos; a NaN normal rejects every view.
+ *   C4 occlusion  : only when depths is given.  u = cvt_i32(x + 0.5), v = cvt_i32(y + 0.5), d = (double)depths[view][v][u].  Rejected
+ *                   unless d > 0 and fabs(q.z * d - 1.0) <= occ_tol.  The nearest pixel alone is tested, no neighbourhood.
+ *   C5 sample     : bilinear, in integers.  x0 = min(cvt_i32(x), w - 2), ax = cvt_i32((x - x0) * 256.0 + 0.5), in [0, 256]; y0 and ay
+ *                   likewise.  Per channel S = (256 - ax)(256 - ay) I[y0][x0] + ax (256 - ay) I[y0][x0+1] + (256 - ax) ay I[y0+1][x0] +
+ *                   ax ay I[y0+1][x0+1]: an exact integer, at most 255 * 65536.
+ *   C6 weight     : Wq = max(1, cvt_i32(cos * cos * 4096.0 + 0.5)).
+ *   C7 accumulate : in int64, A_ch += Wq * S_ch and B += Wq.  The sums commute: no schedule can change a byte.  With MVS_COLOUR_BEST the
+ *                   one accepted view of greatest Wq replaces the blend; a tie goes to the lowest view index.
+ *   C8 result     : colour_ch = (A_ch + 32768 * B) / (65536 * B) by integer division, stored as uint8 in the channel order of the images.
+ *                   n_views[i] is the count of accepted views, also under MVS_COLOUR_BEST.  A vertex with no accepted view gets `fill`
+ *                   and the count 0.
+ * A facet index is never read: occlusion comes from the rasters alone.  The work is ONE launch for all vertices and all views, the camera
+ * and SRT tables staged once per workgroup, without atomics; below 262 144 vertices a row of 16 lanes shares the views of a vertex and
+ * reduces the integer sums over the row, above it a thread walks all views of its vertex (MVS_COLOUR_MAPPING in the environment, read at
+ * every call: 1 or 16 fixes the mapping, for measurements and tests; the bytes are the same).  Two runs give the same bytes.  The tables must
+ * fit 64 KiB (144 bytes per camera, 168 per sequence): chunking the views is not built; the int64 sums would make it exact.
+ * V = 0 is MVS_OK and writes nothing.  MVS_E_INVALID_ARG, before a device is needed, naming the entry: min_cos outside (0, 1], occ_tol
+ * not finite or <= 0, an unknown flag bit, reserved != 0, V < 0 or V >= 2^31 - 1, a NULL points, normals (mvs_mesh_vertex_normals
+ * computes them), imgs, colours, cam_off or cams, n_seq < 1, cam_off not ascending from 0, no camera, a chain given in part, a camera
+ * whose size is not cams[0]'s, w or h < 2, w * h above 2^31 - 1, tables above 64 KiB.  prm == NULL: the defaults. */
+#define MVS_COLOUR_BEST 1
+typedef struct mvs_colour_params {  /* 24 bytes */
+    double  min_cos;            /* 0.2: C3; (0, 1].  A choice, not measured                      */
+    double  occ_tol;            /* 0.01: C4, relative to the vertex's depth; > 0.  A choice, not measured */
+    int32_t flags;              /* MVS_COLOUR_BEST = 1                                           */
+    uint8_t fill[3];            /* 128, 128, 128: the colour of a vertex no view accepts         */
+    uint8_t reserved;           /* 0                                                             */
+} mvs_colour_params;
+/* the values in the comments above; flags = 0 */
+void mvs_colour_default_params(mvs_colour_params* p);
+int mvs_colour_vertices(const double* points, const double* normals, int64_t V, int32_t n_seq, const double* scales, const double* R,
+                        const double* t, const int32_t* cam_off /*n_seq+1*/, const mvs_camera* cams, const uint8_t* imgs,
+                        const float* depths /*or NULL*/, const mvs_colour_params* prm /*NULL: defaults*/, uint8_t* colours /*V*3*/,
+                        int32_t* n_views /*V or NULL*/);
+/* points, normals, images, rasters and outputs in HBM, in the order of hip_stream (may be NULL); the tables stay host arrays; returns
+ * with the work complete */
+int mvs_colour_vertices_dev(const double* points_dev, const double* normals_dev, int64_t V, int32_t n_seq, const double* scales,
+                            const double* R, const double* t, const int32_t* cam_off, const mvs_camera* cams, const uint8_t* imgs_dev,
+                            const float* depths_dev, const mvs_colour_params* prm, uint8_t* colours_dev, int32_t* n_views_dev,
+                            void* hip_stream);
+
 /* ------------------------------------------------- base images (cv::imread of <imgdir>%05d.jpg) -- */
 /* The batched baseline JPEG decoder: the frames the reference opens with cv::imread (R/Image3D/Image3D.cpp:21, R/Processor/Processor.cpp:
  * 532,545, R/FeatureProc/FeatureProc.cpp:26, R/DepthRecovery/DepthOptimizer.cpp:13-14), all images of a call through each kernel in one

@@ -29,6 +29,19 @@ int mvs_obj_read(const char* path, int64_t* n_vertices, int64_t* n_normals, int6
 int mvs_obj_write(const char* path, int64_t n_vertices, const double* points, const double* normals,
                   int64_t n_faces, const int32_t* faces);
 
+/* mvs_obj_write with every `v` line extended to `v x y z r g b`: r, g, b are colour / 255 as float32, printed by the same %g writer —
+ * the convention MeshLab and CloudCompare read.  colours holds V * 3 bytes in the channel order `order` (MVS_JPEG_BGR or MVS_JPEG_RGB of
+ * include/mvs.h: what mvs_colour_vertices returned for images of that order).  mvs_obj_read ignores what follows the third number of a
+ * `v` line, so it reads the geometry of such a file unchanged.  This library's convention; the reference writes no colours. */
+int mvs_obj_write_coloured(const char* path, int64_t n_vertices, const double* points, const double* normals /*or NULL*/,
+                           const uint8_t* colours, uint32_t order, int64_t n_faces, const int32_t* faces);
+
+/* The colours of a file mvs_obj_write_coloured wrote, in the channel order `order`: colours (n_vertices * 3 bytes) receives, per `v`
+ * line and channel, (uint8)((double)c * 255.0 + 0.5) of the float32 c read, clamped to 0 .. 255 — every byte value survives the round
+ * trip.  n_vertices must be the file's count of `v` lines (mvs_obj_read gives it), else MVS_E_INVALID_ARG.  A `v` line with fewer than
+ * six numbers is MVS_E_IO, naming the line. */
+int mvs_obj_read_colours(const char* path, int64_t n_vertices, uint8_t* colours, uint32_t order);
+
 /* oriented point list `x y z nx ny nz` per line — written at R/Processor/Processor.cpp:1033-1040 (doubles, 6 significant
  * digits), read at :958-963 (`ifs >> float`). */
 int mvs_npts_read(const char* path, int64_t* n, double* points /*n*3 or NULL*/, double* normals /*n*3 or NULL*/);
@@ -126,6 +139,19 @@ int mvs_processor_recover_depths(int32_t n_seq, const char* const* seq_dirs, con
 /* mvs_processor_recover_depths with the RGB frames read by mvs_processor_load_images from the same seq_dirs. */
 int mvs_processor_recover_depths_files(int32_t n_seq, const char* const* seq_dirs, const int32_t* cam_off, const mvs_camera* cams,
                                        const mvs_depth_recover_params* params);
+
+/* mvs_colour_vertices on files (rules C1-C8 of include/mvs.h: this library's definition; the reference has no such stage): the coloured
+ * model of a run.  model_obj (Model.obj, PSR%d.obj, deform.obj) is read as ReadObj reads it, its normals from the `vn` lines or, when it
+ * has none, computed as mvs_mesh_vertex_normals; srt_txt is read through float32 as mvs_processor_render reads it; the frames
+ * seq_dirs[k]%05d.jpg are loaded and decoded as mvs_processor_load_images does (RGB); the mesh is rendered from every camera with
+ * mvs_render_depth_views_dev (znear, zfar as there; cams[0]'s size for every view) and those rasters are the occlusion test C4 — a file
+ * without facets (PSR%d.obj) has no rasters and C4 is skipped; then every vertex is coloured and out_obj written with
+ * mvs_obj_write_coloured in RGB (normals as read; computed ones are written when the file has facets).  Every camera must have cams[0]'s
+ * size.  params may be NULL (defaults).  Any bad input is reported before a file is written.  n_coloured (may be NULL) receives the number
+ * of vertices at least one view accepted. */
+int mvs_processor_colour_model(const char* model_obj, const char* srt_txt, int32_t n_seq, const int32_t* cam_off, const mvs_camera* cams,
+                               const char* const* seq_dirs, const mvs_colour_params* params, float znear, float zfar, const char* out_obj,
+                               int64_t* n_coloured);
 
 /* cv::imwrite of the generated views (R/Image3D/Image3D.cpp:218-219): view j of frame i of `views` (what mvs_gen_new_views returned:
  * n_frames x view_count x h x w x 3 bytes, host; flags MVS_JPEG_BGR or MVS_JPEG_RGB say their order) goes to <seq_dir>Views/proj<i>_<j>.jpg

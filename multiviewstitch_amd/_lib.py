@@ -90,6 +90,11 @@ class CDepthRecoverParams(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class CColourParams(C.Structure):
+    """struct mvs_colour_params."""
+    _fields_ = [("min_cos", C.c_double), ("occ_tol", C.c_double), ("flags", C.c_int32), ("fill", C.c_uint8 * 3), ("reserved", C.c_uint8)]
+
+
 class CJpegInfo(C.Structure):
     """struct mvs_jpeg_info_t."""
     _fields_ = [(k, C.c_int32) for k in ("w", "h", "components", "h_samp", "v_samp", "restart_interval", "n_segments", "sof")]
@@ -235,6 +240,9 @@ _SIGS = {
     "mvs_depth_recover_default_params": (None, [_VP]),
     "mvs_recover_depth_maps": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mvs_recover_depth_maps_dev": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "mvs_colour_default_params": (None, [_VP]),
+    "mvs_colour_vertices": (C.c_int, [_VP, _VP, _I64, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "mvs_colour_vertices_dev": (C.c_int, [_VP, _VP, _I64, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mvs_jpeg_info": (C.c_int, [_VP, _I64, _VP]),
     "mvs_jpeg_decode": (C.c_int, [_I32, _VP, _VP, _U32, _VP]),
     "mvs_jpeg_decode_dev": (C.c_int, [_I32, _VP, _VP, _U32, _VP, _VP]),
@@ -336,6 +344,8 @@ _SIGS = {
     # include/mvs_io.h
     "mvs_obj_read": (C.c_int, [C.c_char_p, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mvs_obj_write": (C.c_int, [C.c_char_p, _I64, _VP, _VP, _I64, _VP]),
+    "mvs_obj_write_coloured": (C.c_int, [C.c_char_p, _I64, _VP, _VP, _VP, _U32, _I64, _VP]),
+    "mvs_obj_read_colours": (C.c_int, [C.c_char_p, _I64, _VP, _U32]),
     "mvs_npts_read": (C.c_int, [C.c_char_p, _VP, _VP, _VP]),
     "mvs_npts_write": (C.c_int, [C.c_char_p, _I64, _VP, _VP]),
     "mvs_srt_txt_read": (C.c_int, [C.c_char_p, _I64, _VP, _VP, _VP]),
@@ -371,6 +381,7 @@ _SIGS = {
     "mvs_processor_refine_depths_files": (C.c_int, [_I32, _VP, _VP, _VP, _VP]),
     "mvs_processor_recover_depths": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP]),
     "mvs_processor_recover_depths_files": (C.c_int, [_I32, _VP, _VP, _VP, _VP]),
+    "mvs_processor_colour_model": (C.c_int, [C.c_char_p, C.c_char_p, _I32, _VP, _VP, _VP, _VP, C.c_float, C.c_float, C.c_char_p, _VP]),
     "mvs_processor_point_sample": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mvs_processor_poisson": (C.c_int, [C.c_char_p, _VP, C.c_char_p, _VP, _VP]),
     "mvs_processor_poisson_density": (C.c_int, [C.c_char_p, _VP, _VP, _D, C.c_char_p, _VP, _VP]),
@@ -446,6 +457,7 @@ JPEG_BGR, JPEG_RGB = 0, 1                   # MVS_JPEG_BGR, MVS_JPEG_RGB (includ
 JPEG_GREY, JPEG_RESTART_ROW = 2, 65536      # MVS_JPEG_GREY, MVS_JPEG_RESTART_ROW
 REFINE_SUBSTEP = 1                          # MVS_REFINE_SUBSTEP (include/mvs.h)
 RECOVER_SUBSTEP = 1                         # MVS_RECOVER_SUBSTEP (include/mvs.h)
+COLOUR_BEST = 1                             # MVS_COLOUR_BEST (include/mvs.h)
 
 
 def cam_array(cameras):

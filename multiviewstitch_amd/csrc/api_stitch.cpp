@@ -520,6 +520,61 @@ int mvs_processor_recover_depths_files(int32_t n_seq, const char* const* seq_dir
     return recover_depths_body(__func__, n_seq, seq_dirs, cam_off, cams, imgs.data(), params, px);
 }
 
+int mvs_processor_colour_model(const char* model_obj, const char* srt_txt, int32_t n_seq, const int32_t* cam_off, const mvs_camera* cams,
+                               const char* const* seq_dirs, const mvs_colour_params* params, float znear, float zfar, const char* out_obj,
+                               int64_t* n_coloured) {
+    MVS_TRACE();
+    int rc = check_views(__func__, n_seq, nullptr, nullptr, nullptr, cam_off, cams, znear, zfar);
+    if (rc || (rc = colour_check_views(__func__, n_seq, nullptr, nullptr, nullptr, cam_off, cams))) return rc;
+    mvs_colour_params prm;
+    if (params) prm = *params; else mvs_colour_default_params(&prm);
+    if ((rc = colour_check_params(__func__, &prm))) return rc;
+    if (!model_obj || !srt_txt || !seq_dirs || !out_obj) return bad(__func__, "model_obj, srt_txt, seq_dirs and out_obj must not be NULL");
+    for (int k = 0; k < n_seq; ++k)
+        if (!seq_dirs[k]) return bad(__func__, "a path of seq_dirs is NULL");
+    if ((rc = need_device())) return rc;
+    std::vector<double> sc(n_seq), R((size_t)n_seq * 9), t((size_t)n_seq * 3);
+    if ((rc = mvs_srt_txt_read(srt_txt, n_seq, sc.data(), R.data(), t.data()))) return rc;          // through float32, as mvs_processor_render
+    int64_t V = 0, N = 0, F = 0;
+    if ((rc = mvs_obj_read(model_obj, &V, &N, &F, nullptr, nullptr, nullptr))) return rc;
+    if (N != 0 && N != V) {
+        mvs_set_error("%s: %lld normals for %lld vertices (the reference indexes one per vertex)", model_obj, (long long)N, (long long)V);
+        return MVS_E_BAD_MESH;
+    }
+    if (V <= 0 || V >= 0x7fffffffLL || F >= 0x7fffffffLL / 3) { mvs_set_error("%s: no vertices, or mesh too large", model_obj); return MVS_E_BAD_MESH; }
+    std::vector<double> hp((size_t)V * 3), hn((size_t)V * 3);
+    std::vector<int32_t> hf((size_t)F * 3);
+    if ((rc = mvs_obj_read(model_obj, &V, &N, &F, hp.data(), hn.data(), hf.data()))) return rc;
+    for (int64_t i = 0; i < F * 3; ++i)
+        if (hf[i] < 0 || hf[i] >= V) { mvs_set_error("%s: facet index %d outside [1, %lld]", model_obj, hf[i] + 1, (long long)V); return MVS_E_BAD_MESH; }
+    const int n_views = cam_off[n_seq];
+    const size_t npx = (size_t)cams[0].w * (size_t)cams[0].h * (size_t)n_views;
+    std::vector<uint8_t> himg(3 * npx);
+    if ((rc = load_images_body(__func__, n_seq, seq_dirs, cam_off, cams, MVS_JPEG_RGB, himg.data()))) return rc;
+    Scratch dp, dn, df, di, dras, dc, dk;
+    if ((rc = up(dp, hp.data(), (size_t)V * 3)) || (rc = up(dn, hn.data(), N ? (size_t)V * 3 : 0, (size_t)V * 3)) ||
+        (rc = up(df, hf.data(), (size_t)F * 3)) || (rc = up(di, himg.data(), 3 * npx)) || (F && (rc = dras.alloc(sizeof(float) * npx))) ||
+        (rc = dc.alloc((size_t)V * 3)) || (rc = dk.alloc(sizeof(int32_t) * (size_t)V))) return rc;
+    // no `vn` lines: CalculateVertexNormals, PlyObj.cpp:11-14
+    if (N == 0 && (rc = mesh_vertex_normals_dev(dp.as<double>(), V, df.as<int32_t>(), F, dn.as<double>(), nullptr))) return rc;
+    if (F && (rc = render_views_dev(dp.as<double>(), V, df.as<int32_t>(), F, n_seq, sc.data(), R.data(), t.data(), cam_off, cams, znear, zfar,
+                                    dras.as<float>(), nullptr))) return rc;
+    if ((rc = colour_vertices_dev(__func__, dp.as<double>(), dn.as<double>(), V, n_seq, sc.data(), R.data(), t.data(), cam_off, cams, di.as<uint8_t>(),
+                                  F ? dras.as<float>() : nullptr, &prm, dc.as<uint8_t>(), dk.as<int32_t>(), nullptr))) return rc;
+    std::vector<uint8_t> hc((size_t)V * 3);
+    std::vector<int32_t> hk((size_t)V);
+    if ((rc = down(hc.data(), dc, hc.size())) || (rc = down(hk.data(), dk, hk.size()))) return rc;
+    const bool with_normals = N != 0 || F != 0;
+    if (N == 0 && F != 0 && (rc = down(hn.data(), dn, (size_t)V * 3))) return rc;
+    if ((rc = mvs_obj_write_coloured(out_obj, V, hp.data(), with_normals ? hn.data() : nullptr, hc.data(), MVS_JPEG_RGB, F, hf.data()))) return rc;
+    if (n_coloured) {
+        int64_t n = 0;
+        for (int32_t k : hk) n += k > 0;
+        *n_coloured = n;
+    }
+    return MVS_OK;
+}
+
 // stream i = data[off[i] .. off[i + 1]) to path[i], on up to 16 host threads; the first file that fails is reported
 static int write_streams(const char* fn, const std::vector<std::string>& path, const int64_t* off, const uint8_t* data) {
     const int n = (int)path.size();

@@ -357,11 +357,12 @@ int mvs_obj_read(const char* path, int64_t* n_vertices, int64_t* n_normals, int6
     return obj_parse(text, path, n_vertices, n_normals, n_faces, points, normals, faces);
 }
 
-int mvs_obj_write(const char* path, int64_t n_vertices, const double* points, const double* normals, int64_t n_faces,
-                  const int32_t* faces) {
-    MVS_TRACE();
+// WriteObjCore under the name fn; colours (V * 3 bytes, or NULL) extend every `v` line by r g b = byte / 255 as float32, the channels
+// taken in the order swap ? 2 1 0 : 0 1 2
+static int obj_write_core(const char* fn, const char* path, int64_t n_vertices, const double* points, const double* normals, const uint8_t* colours,
+                          bool swap, int64_t n_faces, const int32_t* faces) {
     if (!path || n_vertices < 0 || n_faces < 0 || (n_vertices && !points) || (n_faces && !faces)) {
-        mvs_set_error("mvs_obj_write: bad arguments"); return MVS_E_INVALID_ARG;
+        mvs_set_error("%s: bad arguments", fn); return MVS_E_INVALID_ARG;
     }
     std::string head;
     head += "####\n#\n# OBJ File Generated by MultiviewStitch Program\n#\n####\n# Object ";
@@ -396,7 +397,9 @@ int mvs_obj_write(const char* path, int64_t n_vertices, const double* points, co
                 for (int c = 0; c < 3; ++c) { n += fmt_g(ln + n, as_f32(normals[3 * i + c])); ln[n++] = c < 2 ? ' ' : '\n'; }
             }
             ln[n++] = 'v'; ln[n++] = ' ';
-            for (int c = 0; c < 3; ++c) { n += fmt_g(ln + n, as_f32(points[3 * i + c])); ln[n++] = c < 2 ? ' ' : '\n'; }
+            for (int c = 0; c < 3; ++c) { n += fmt_g(ln + n, as_f32(points[3 * i + c])); ln[n++] = c < 2 || colours ? ' ' : '\n'; }
+            if (colours)
+                for (int c = 0; c < 3; ++c) { n += fmt_g(ln + n, (double)((float)colours[3 * i + (swap ? 2 - c : c)] / 255.0f)); ln[n++] = c < 2 ? ' ' : '\n'; }
             o.append(ln, (size_t)n);
         }
     });
@@ -417,6 +420,59 @@ int mvs_obj_write(const char* path, int64_t n_vertices, const double* points, co
         }
     });
     if (!ok) return io_fail("cannot write", path);
+    return MVS_OK;
+}
+
+int mvs_obj_write(const char* path, int64_t n_vertices, const double* points, const double* normals, int64_t n_faces,
+                  const int32_t* faces) {
+    MVS_TRACE();
+    return obj_write_core(__func__, path, n_vertices, points, normals, nullptr, false, n_faces, faces);
+}
+
+int mvs_obj_write_coloured(const char* path, int64_t n_vertices, const double* points, const double* normals, const uint8_t* colours,
+                           uint32_t order, int64_t n_faces, const int32_t* faces) {
+    MVS_TRACE();
+    if (order != MVS_JPEG_BGR && order != MVS_JPEG_RGB) { mvs_set_error("%s: order must be MVS_JPEG_BGR or MVS_JPEG_RGB", __func__); return MVS_E_INVALID_ARG; }
+    if (n_vertices > 0 && !colours) { mvs_set_error("%s: colours is NULL", __func__); return MVS_E_INVALID_ARG; }
+    return obj_write_core(__func__, path, n_vertices, points, normals, n_vertices > 0 ? colours : nullptr, order == MVS_JPEG_BGR, n_faces, faces);
+}
+
+int mvs_obj_read_colours(const char* path, int64_t n_vertices, uint8_t* colours, uint32_t order) {
+    MVS_TRACE();
+    if (!path || n_vertices < 0 || (n_vertices && !colours)) { mvs_set_error("%s: bad arguments", __func__); return MVS_E_INVALID_ARG; }
+    if (order != MVS_JPEG_BGR && order != MVS_JPEG_RGB) { mvs_set_error("%s: order must be MVS_JPEG_BGR or MVS_JPEG_RGB", __func__); return MVS_E_INVALID_ARG; }
+    errno = 0;
+    std::string text;
+    if (!read_whole(path, &text)) return io_fail("cannot open", path);
+    // the lines mvs_obj_read takes as vertices (obj_line: `v` then a blank), up to the first line of more than 511 characters
+    const char* T = text.data();
+    const size_t N = text.size();
+    int64_t nv = 0, line_no = 0;
+    for (size_t pos = 0; pos < N;) {
+        const void* nl = std::memchr(T + pos, '\n', N - pos);
+        const size_t eol = nl ? (size_t)((const char*)nl - T) : N;
+        if (eol - pos > 511) break;
+        ++line_no;
+        const char* b = T + pos;
+        const char* e = T + eol;
+        pos = eol + 1;
+        if (e > b && e[-1] == '\r') --e;
+        if (e == b || *b != 'v' || (e - b > 1 && b[1] != ' ' && b[1] != '\t')) continue;
+        double v[6];
+        const char* p = b + 1;
+        for (int c = 0; c < 6; ++c)
+            if (!next_f32(p, e, v + c)) {
+                mvs_set_error("%s: %s: line %lld: a `v` line with fewer than six numbers", __func__, path, (long long)line_no);
+                return MVS_E_IO;
+            }
+        if (nv < n_vertices)
+            for (int c = 0; c < 3; ++c) {
+                const double x = v[3 + c] * 255.0 + 0.5;
+                colours[3 * nv + (order == MVS_JPEG_BGR ? 2 - c : c)] = (uint8_t)(x >= 255.0 ? 255 : x > 0.0 ? (int)x : 0);
+            }
+        ++nv;
+    }
+    if (nv != n_vertices) { mvs_set_error("%s: %s holds %lld `v` lines, not %lld", __func__, path, (long long)nv, (long long)n_vertices); return MVS_E_INVALID_ARG; }
     return MVS_OK;
 }
 

@@ -34,6 +34,14 @@ int refine_depth_maps_host(const char* fn, int32_t n_seq, const int32_t* cam_off
 // mvs_recover_depth_maps's host form (depth_recover.hip), validating and reporting under the name fn
 int recover_depth_maps_host(const char* fn, int32_t n_seq, const int32_t* cam_off, const mvs_camera* cams, const uint8_t* imgs,
                             const mvs_depth_recover_params* p, float* out, int16_t* level_out, int32_t* sum_out, uint8_t* cnt_out);
+// mvs_colour_vertices_dev (colour.hip) under the name fn: validates, needs a device, colours; complete on return.  The two checks it
+// starts with are there for the file form, which has to fail before it reads a frame
+int colour_check_params(const char* fn, const mvs_colour_params* p);
+int colour_check_views(const char* fn, int32_t n_seq, const double* scales, const double* R, const double* t, const int32_t* cam_off,
+                       const mvs_camera* cams);
+int colour_vertices_dev(const char* fn, const double* pts, const double* nrm, int64_t V, int32_t n_seq, const double* scales, const double* R,
+                        const double* t, const int32_t* cam_off, const mvs_camera* cams, const uint8_t* imgs, const float* depths,
+                        const mvs_colour_params* prm, uint8_t* colours, int32_t* n_views, hipStream_t s);
 // mvs_jpeg_decode's host form (jpeg.hip) under the name fn; w / h (may be NULL) receive the size; imgs == NULL: the header walk and the
 // checks only, no device needed
 int jpeg_decode_host(const char* fn, int32_t n, const int64_t* offsets, const uint8_t* data, uint32_t flags, uint8_t* imgs, int32_t* w, int32_t* h);

@@ -34,6 +34,34 @@ def WriteObj(path, points, normals=None, facets=None):
     L.check(L.lib().mvs_obj_write(_p(path), len(pts), L.ptr(pts), L.ptr(nrm), len(fac), L.ptr(fac)))
 
 
+def _order(order):
+    if order not in ("BGR", "RGB"):
+        raise L.MvsError(-1, f"order must be 'BGR' or 'RGB', not {order!r}")
+    return L.JPEG_RGB if order == "RGB" else L.JPEG_BGR
+
+
+def WriteObjColoured(path, points, colours, normals=None, facets=None, order: str = "RGB"):
+    """``mvs_obj_write_coloured``: ``WriteObj`` with every ``v`` line extended to ``v x y z r g b`` (colour / 255 as float32, %g).
+    ``colours`` [V, 3] uint8 in the channel order ``order`` (what ``processor.ColourVertices`` returned for images of that order)."""
+    pts = L.arr(points, np.float64).reshape(-1, 3)
+    col = L.arr(colours, np.uint8).reshape(-1, 3)
+    if len(col) != len(pts):
+        raise L.MvsError(-1, f"{len(col)} colours for {len(pts)} vertices")
+    nrm = None if normals is None or len(normals) != len(pts) else L.arr(normals, np.float64).reshape(-1, 3)
+    fac = np.empty((0, 3), np.int32) if facets is None else L.arr(facets, np.int32).reshape(-1, 3)
+    L.check(L.lib().mvs_obj_write_coloured(_p(path), len(pts), L.ptr(pts), L.ptr(nrm), L.ptr(col), _order(order), len(fac), L.ptr(fac)))
+
+
+def ReadObjColours(path, order: str = "RGB"):
+    """``mvs_obj_read_colours``: -> colours [V, 3] uint8 of a file ``WriteObjColoured`` wrote, in the channel order ``order``."""
+    flag = _order(order)
+    nv, nn, nf = C.c_int64(), C.c_int64(), C.c_int64()
+    L.check(L.lib().mvs_obj_read(_p(path), C.byref(nv), C.byref(nn), C.byref(nf), None, None, None))
+    col = np.empty((nv.value, 3), np.uint8)
+    L.check(L.lib().mvs_obj_read_colours(_p(path), nv.value, L.ptr(col), flag))
+    return col
+
+
 def read_npts(path):
     n = C.c_int64()
     L.check(L.lib().mvs_npts_read(_p(path), C.byref(n), None, None))

@@ -11,7 +11,8 @@ detection in front of the cull, FeatureProc::DetectFeature (:14-75,103-112), thr
 ``CheckConsistency`` and the stitch tail, GeometryRec::RunPointSample (R/Processor/Processor.cpp:933-949), through ``mvs_point_sample``;
 the surface reconstruction between the stitch tail and the trim of the model, GeometryRec::RunPoisson (:1042-1058), through
 ``mvs_poisson_reconstruct``; the match and SIFT overlay pictures (:767-793, :604-615, FeatureProc.cpp:67-73) through
-``mvs_match_overlays`` / ``mvs_sift_overlays`` and their file forms.  The functions stand in pipeline order."""
+``mvs_match_overlays`` / ``mvs_sift_overlays`` and their file forms; the colours of the stitched model from the base images, a stage the
+reference does not have, through ``mvs_colour_vertices`` and ``mvs_processor_colour_model``.  The functions stand in pipeline order."""
 from __future__ import annotations
 
 import contextlib
@@ -1208,6 +1209,76 @@ def RecoverDepthFilesFromJpeg(seq_dirs, cameras, params: L.CDepthRecoverParams |
     n, dirs, off, cams = _recover_files_args(seq_dirs, cameras)
     prm = params if params is not None else depth_recover_params()
     L.check(L.lib().mvs_processor_recover_depths_files(n, dirs, L.ptr(off), cams, C.byref(prm)))
+
+
+# ------------------------------------------------------------------ vertex colours ----
+def colour_params(**kw) -> L.CColourParams:
+    """``mvs_colour_default_params`` (min_cos 0.2, occ_tol 0.01, flags 0, fill 128 128 128 — choices nobody has measured on a real
+    sequence) with the given fields replaced; ``fill`` takes three byte values, ``flags`` may be ``COLOUR_BEST``."""
+    fill = kw.pop("fill", None)
+    prm = _params(L.CColourParams, L.lib().mvs_colour_default_params, kw)
+    if fill is not None:
+        prm.fill[:] = [int(v) for v in fill]
+    return prm
+
+
+def ColourVertices(points, normals, cameras, imgs, depths=None, scales=None, Rs=None, ts=None, params: L.CColourParams | None = None,
+                   stream: int | None = None, with_counts: bool = False):
+    """The colour of every vertex from the base images of all cameras of all sequences, in one call (``mvs_colour_vertices``; the rules
+    C1-C8, this library's definition: include/mvs.h).  ``points`` / ``normals`` [V, 3] float64 in the world frame; ``cameras[k]`` lists
+    sequence k's cameras, all of one size; ``imgs`` [N, h, w, 3] uint8 and ``depths`` [N, h, w] float32 (the rasters of ``RenderViews``,
+    or None: no occlusion test) hold all cameras in camera order; ``scales`` / ``Rs`` / ``ts`` are the SRT chain (None for all three: the
+    world frame).  The arrays are numpy arrays, or contiguous torch tensors on the GPU (the device form: the results are tensors on the
+    same device); ``stream`` is the HIP stream that produced them (None: the legacy default stream), and the allocation of the results
+    is ordered on it.  -> colours [V, 3] uint8 in the channel order of the images; with ``with_counts`` (colours, n_views [V] int32)."""
+    prm = params if params is not None else colour_params()
+    n, s, R, t, coff, cams = _view_tables(cameras, scales, Rs, ts)
+    N = int(coff[-1])
+    w0, h0 = (int(cameras[0][0].w), int(cameras[0][0].h)) if N and len(cameras[0]) else (0, 0)
+    arrays = [points, normals, imgs] + ([depths] if depths is not None else [])
+    dev = all(_is_dev(a) for a in arrays)
+    if not dev and any(_is_dev(a) for a in arrays):
+        raise L.MvsError(-1, "points, normals, imgs and depths must all be tensors on the GPU or all arrays")
+    if not dev:
+        points, normals = L.arr(points, np.float64), L.arr(normals, np.float64)
+        imgs = L.arr(imgs, np.uint8)
+        depths = None if depths is None else L.arr(depths, np.float32)
+    V = int(points.shape[0]) if len(points.shape) == 2 else -1
+    if tuple(points.shape) != (V, 3) or tuple(normals.shape) != (V, 3):
+        raise L.MvsError(-1, "points and normals must be [V, 3]")
+    if tuple(imgs.shape) != (N, h0, w0, 3):
+        raise L.MvsError(-1, f"imgs must be [N, h, w, 3] = {(N, h0, w0, 3)}")
+    if depths is not None and tuple(depths.shape) != (N, h0, w0):
+        raise L.MvsError(-1, f"depths must be [N, h, w] = {(N, h0, w0)}")
+    order = _stream_order(stream) if dev else contextlib.nullcontext()
+    with order:
+        col = _out_like(points, (V, 3), "uint8")
+        cnt = _out_like(points, (V,), "int32") if with_counts else None
+        if dev:
+            ptrs = (_dev_ptr(points, "float64", "points"), _dev_ptr(normals, "float64", "normals"))
+            iptr, dptr = _dev_ptr(imgs, "uint8", "imgs"), _dev_ptr(depths, "float32", "depths")
+            fn, tail = L.lib().mvs_colour_vertices_dev, (L.ptr(stream),)
+        else:
+            ptrs, iptr, dptr = (L.ptr(points), L.ptr(normals)), L.ptr(imgs), L.ptr(depths)
+            fn, tail = L.lib().mvs_colour_vertices, ()
+        L.check(fn(*ptrs, V, n, L.ptr(s), L.ptr(R), L.ptr(t), L.ptr(coff), cams, iptr, dptr, C.byref(prm), L.ptr(col), L.ptr(cnt), *tail))
+    return (col, cnt) if with_counts else col
+
+
+def ColourModelFiles(model_obj, srt_txt, seq_dirs, cameras, out_obj, params: L.CColourParams | None = None, znear: float = 0.01,
+                     zfar: float = 2000.0) -> int:
+    """``mvs_processor_colour_model``: ``model_obj`` (Model.obj, PSR%d.obj, deform.obj) coloured from the frames ``seq_dirs[k]``%05d.jpg
+    of every sequence and written to ``out_obj`` with ``v x y z r g b`` lines.  The chain comes from ``srt_txt``; the occlusion test uses
+    the mesh rendered from every camera (``RenderViews``), and is skipped for a file without facets.  -> vertices that received a colour."""
+    n, _, _, _, coff, cams = _view_tables(cameras, None, None, None)
+    if len(seq_dirs) != n:
+        raise L.MvsError(-1, f"{len(seq_dirs)} sequence dirs for {n} sequences")
+    dirs = (C.c_char_p * max(1, n))(*[os.fsencode(d) for d in seq_dirs])
+    prm = params if params is not None else colour_params()
+    nc = C.c_int64()
+    L.check(L.lib().mvs_processor_colour_model(os.fsencode(model_obj), os.fsencode(srt_txt), n, L.ptr(coff), cams, dirs, C.byref(prm),
+                                               float(znear), float(zfar), os.fsencode(out_obj), C.byref(nc)))
+    return nc.value
 
 
 # ------------------------------------------------------------------ base images ----

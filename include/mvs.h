@@ -794,6 +794,63 @@ int mvs_recover_depth_maps_dev(int32_t n_seq, const int32_t* cam_off, const mvs_
                                const mvs_depth_recover_params* p, float* out_dev, int16_t* level_out_dev, int32_t* sum_out_dev,
                                uint8_t* cnt_out_dev, void* hip_stream);
 
+/* ------------------------------------------------- depth recovery with semi-global aggregation of the cost volume -- */
+/* mvs_recover_depth_maps lets every pixel choose its level by itself (R6): a window with little texture picks whatever level happens to
+ * score lowest.  This call regularises the cost volume along 4 or 8 path directions (semi-global matching, Hirschmueller) before the
+ * winner is taken.  The rules S1-S6 below are this library's definition, NOT VERIFIED against any ZJU code; everything they do not
+ * mention is R1-R5 and R9 unchanged.  p1, p2 and cost_cap are choices: nobody has measured them on a real sequence (they were moved
+ * from 64, 1024, 4095 on the evidence of one synthetic scene, tests/depth_sgm_scenes.py).  mvs_recover_depth_maps is not changed by this
+ * entry.  With len = 2 N + 1 and the *rectangle* of a frame R3's candidate set [N, w - N) x [N, h - N):
+ *   S1 volume     : for every pixel p of the rectangle and level l, with sum_l and cnt_l of R5: C(p, l) = min(cost_cap, sum_l / (cnt_l *
+ *                   len * len)) by int64 division when cnt_l >= min_refs, and C(p, l) = cost_cap otherwise.  A pixel with no eligible
+ *                   level is a flat column of cost_cap and passes messages through.
+ *   S2 paths      : for each direction r of the set, over the pixels of the rectangle, with q = p - r: L_r(p, l) = C(p, l) when q is
+ *                   outside the rectangle; otherwise L_r(p, l) = C(p, l) + min(L_r(q, l), L_r(q, l - 1) + p1, L_r(q, l + 1) + p1,
+ *                   M_r(q) + p2) - M_r(q) with M_r(q) = min over k of L_r(q, k).  A neighbour level outside [0, L - 1] does not take
+ *                   part.  The directions are (+-1, 0), (0, +-1) for paths = 4; paths = 8 adds (+-1, +-1).  S(p, l) = the sum over r of
+ *                   L_r(p, l).  The argument checks guarantee L_r <= cost_cap + p2 <= 8190 and S <= 65520: both fit uint16.  All of
+ *                   it is integers: no schedule can change a byte.
+ *   S3 winner     : l* is the lowest l that minimises S(p, l).
+ *   S4 acceptance : with the raw (sum, cnt) of level l* and W the worst eligible raw level as R6 finds it, the pixel is accepted when
+ *                   l* is eligible and R7's two tests hold for m = sum / cnt of l* and m_W.  sum_out and cnt_out report level l*'s raw
+ *                   pair; they are -1 and 0 when l* is not eligible or the pixel is outside the rectangle.  agg_out = S(p, l*), and -1
+ *                   outside the rectangle.  level_out = l* when accepted, else -1; out = +0.0f when rejected.
+ *   S5 substep    : (MVS_RECOVER_SUBSTEP) R8 with c-, c0, c+ = (double)S(p, l* - 1), (double)S(p, l*), (double)S(p, l* + 1) when both
+ *                   neighbours lie in [0, L - 1].  Eligibility is not asked: S is defined at every level.
+ *   S6 value      : R9.
+ * With p1 = p2 = 0, S2 gives L_r = C: the call is then the winner-takes-all of the quantised, capped cost.
+ * The work: the grey rasters and the squares of the plain sweep; then, per group of frames, one launch that writes C as uint16 in the
+ * layout [frame][pixel of the rectangle][level] (level fastest) and the worst eligible raw pair of every pixel, one launch per line
+ * family (rows, columns, and for paths = 8 the two diagonals) in which one wave64 walks one line in both directions and adds L_r into the
+ * uint16 volume S, and one launch that takes the winner and writes the outputs.  No atomic; two runs give the same bytes.  Frames are
+ * processed in groups of as many whole frames as the budget holds (max_volume_mb; 0: MVS_SGM_VOLUME_MB of csrc/knobs.h, 4096); a
+ * frame's result depends on nothing outside its sequence's images, so the bytes do not depend on the grouping.  Scratch comes from the
+ * stream-ordered pool: what the plain sweep takes, and per group 4 bytes per (rectangle pixel, level) for the two volumes plus 8 bytes
+ * per rectangle pixel and 8 per camera.
+ * MVS_E_INVALID_ARG, before a device is needed: everything mvs_recover_depth_maps reports, and p1 < 0, p1 > p2, p2 > 4095, cost_cap
+ * outside [1, 4095], paths other than 4 or 8, max_volume_mb < 0, reserved != 0, and a frame whose volumes do not fit the budget (the
+ * message says how many megabytes one frame needs).  aggregate may be NULL (the defaults). */
+typedef struct mvs_depth_aggregate_params {  /* 24 bytes */
+    int32_t p1;             /* 8: penalty for a change of one level along a path; 0 .. p2.  A choice, not measured */
+    int32_t p2;             /* 128: penalty for any larger change; p1 .. 4095.  A choice, not measured */
+    int32_t cost_cap;       /* 255: 1 .. 4095: a level's cost is capped here; an ineligible level costs exactly this.  A choice, not measured */
+    int32_t paths;          /* 8: 4 or 8 */
+    int32_t max_volume_mb;  /* 0: the library's default budget; > 0: device memory the volumes of one group of frames may take */
+    int32_t reserved;       /* 0 */
+} mvs_depth_aggregate_params;
+/* the values in the comments above */
+void mvs_depth_aggregate_default_params(mvs_depth_aggregate_params* p);
+int mvs_recover_depth_maps_aggregated(int32_t n_seq, const int32_t* cam_off /*n_seq+1*/, const mvs_camera* cams, const uint8_t* imgs,
+                                      const mvs_depth_recover_params* p, const mvs_depth_aggregate_params* aggregate /*or NULL*/, float* out,
+                                      int16_t* level_out /*or NULL*/, int32_t* sum_out /*or NULL*/, uint8_t* cnt_out /*or NULL*/,
+                                      int32_t* agg_out /*or NULL*/);
+/* images and outputs in HBM, in the order of hip_stream (may be NULL); cam_off and cams stay host arrays; returns with the work
+ * complete */
+int mvs_recover_depth_maps_aggregated_dev(int32_t n_seq, const int32_t* cam_off, const mvs_camera* cams, const uint8_t* imgs_dev,
+                                          const mvs_depth_recover_params* p, const mvs_depth_aggregate_params* aggregate, float* out_dev,
+                                          int16_t* level_out_dev, int32_t* sum_out_dev, uint8_t* cnt_out_dev, int32_t* agg_out_dev,
+                                          void* hip_stream);
+
 /* ------------------------------------------------- vertex colours (the pictures back onto the stitched model) -- */
 /* The colour of every vertex of Model.obj / PSR%d.obj / deform.obj from the base images of all cameras of all sequences.  The reference
  * has no such stage: the rules C1-C8 below are this library's definition, NOT VERIFIED against any ZJU code.  min_cos = 0.2, occ_tol =

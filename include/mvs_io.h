@@ -139,6 +139,15 @@ int mvs_processor_recover_depths(int32_t n_seq, const char* const* seq_dirs, con
 /* mvs_processor_recover_depths with the RGB frames read by mvs_processor_load_images from the same seq_dirs. */
 int mvs_processor_recover_depths_files(int32_t n_seq, const char* const* seq_dirs, const int32_t* cam_off, const mvs_camera* cams,
                                        const mvs_depth_recover_params* params);
+/* The two entries above with mvs_recover_depth_maps_aggregated (rules S1-S6 of include/mvs.h) in place of the plain sweep: the same
+ * files DATA/_depth<i>.raw.  params and aggregate may each be NULL (defaults).  Nothing is written when the call fails.
+ * Every argument check of mvs_recover_depth_maps_aggregated, the budget included, is made before a device is needed and, in the _files
+ * form, before a frame is read: MVS_E_INVALID_ARG under the entry's name. */
+int mvs_processor_recover_depths_aggregated(int32_t n_seq, const char* const* seq_dirs, const int32_t* cam_off, const mvs_camera* cams,
+                                            const uint8_t* imgs, const mvs_depth_recover_params* params,
+                                            const mvs_depth_aggregate_params* aggregate);
+int mvs_processor_recover_depths_aggregated_files(int32_t n_seq, const char* const* seq_dirs, const int32_t* cam_off, const mvs_camera* cams,
+                                                  const mvs_depth_recover_params* params, const mvs_depth_aggregate_params* aggregate);
 
 /* mvs_colour_vertices on files (rules C1-C8 of include/mvs.h: this library's definition; the reference has no such stage): the coloured
  * model of a run.  model_obj (Model.obj, PSR%d.obj, deform.obj) is read as ReadObj reads it, its normals from the `vn` lines or, when it

@@ -90,6 +90,11 @@ class CDepthRecoverParams(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class CDepthAggregateParams(C.Structure):
+    """struct mvs_depth_aggregate_params."""
+    _fields_ = [(k, C.c_int32) for k in ("p1", "p2", "cost_cap", "paths", "max_volume_mb", "reserved")]
+
+
 class CColourParams(C.Structure):
     """struct mvs_colour_params."""
     _fields_ = [("min_cos", C.c_double), ("occ_tol", C.c_double), ("flags", C.c_int32), ("fill", C.c_uint8 * 3), ("reserved", C.c_uint8)]
@@ -240,6 +245,9 @@ _SIGS = {
     "mvs_depth_recover_default_params": (None, [_VP]),
     "mvs_recover_depth_maps": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mvs_recover_depth_maps_dev": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "mvs_depth_aggregate_default_params": (None, [_VP]),
+    "mvs_recover_depth_maps_aggregated": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "mvs_recover_depth_maps_aggregated_dev": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mvs_colour_default_params": (None, [_VP]),
     "mvs_colour_vertices": (C.c_int, [_VP, _VP, _I64, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mvs_colour_vertices_dev": (C.c_int, [_VP, _VP, _I64, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
@@ -381,6 +389,8 @@ _SIGS = {
     "mvs_processor_refine_depths_files": (C.c_int, [_I32, _VP, _VP, _VP, _VP]),
     "mvs_processor_recover_depths": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP]),
     "mvs_processor_recover_depths_files": (C.c_int, [_I32, _VP, _VP, _VP, _VP]),
+    "mvs_processor_recover_depths_aggregated": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "mvs_processor_recover_depths_aggregated_files": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP]),
     "mvs_processor_colour_model": (C.c_int, [C.c_char_p, C.c_char_p, _I32, _VP, _VP, _VP, _VP, C.c_float, C.c_float, C.c_char_p, _VP]),
     "mvs_processor_point_sample": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mvs_processor_poisson": (C.c_int, [C.c_char_p, _VP, C.c_char_p, _VP, _VP]),
@@ -457,6 +467,7 @@ JPEG_BGR, JPEG_RGB = 0, 1                   # MVS_JPEG_BGR, MVS_JPEG_RGB (includ
 JPEG_GREY, JPEG_RESTART_ROW = 2, 65536      # MVS_JPEG_GREY, MVS_JPEG_RESTART_ROW
 REFINE_SUBSTEP = 1                          # MVS_REFINE_SUBSTEP (include/mvs.h)
 RECOVER_SUBSTEP = 1                         # MVS_RECOVER_SUBSTEP (include/mvs.h)
+SGM_VOLUME_MB = 4096                        # MVS_SGM_VOLUME_MB (csrc/knobs.h): the budget behind max_volume_mb = 0; the host test pins it
 COLOUR_BEST = 1                             # MVS_COLOUR_BEST (include/mvs.h)
 
 

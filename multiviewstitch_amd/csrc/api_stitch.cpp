@@ -472,14 +472,18 @@ int mvs_processor_refine_depths_files(int32_t n_seq, const char* const* seq_dirs
     return refine_depths_body(__func__, n_seq, seq_dirs, cam_off, cams, imgs.data(), params, px);
 }
 
-// mvs_recover_depth_maps -> DATA/_depth<i>.raw for checked arguments, under the name fn; nothing is written when the call fails
+// mvs_recover_depth_maps (or, with `aggregated`, mvs_recover_depth_maps_aggregated under ap) -> DATA/_depth<i>.raw for checked
+// arguments, under the name fn; nothing is written when the call fails
 static int recover_depths_body(const char* fn, int32_t n_seq, const char* const* seq_dirs, const int32_t* cam_off, const mvs_camera* cams,
-                               const uint8_t* imgs, const mvs_depth_recover_params* params, size_t floats) {
+                               const uint8_t* imgs, const mvs_depth_recover_params* params, size_t floats, bool aggregated = false,
+                               const mvs_depth_aggregate_params* ap = nullptr) {
     int rc;
     mvs_depth_recover_params prm;
     if (params) prm = *params; else mvs_depth_recover_default_params(&prm);
     std::vector<float> out(floats ? floats : 1);
-    if ((rc = recover_depth_maps_host(fn, n_seq, cam_off, cams, imgs, &prm, out.data(), nullptr, nullptr, nullptr))) return rc;
+    rc = aggregated ? recover_depth_maps_aggregated_host(fn, n_seq, cam_off, cams, imgs, &prm, ap, out.data(), nullptr, nullptr, nullptr, nullptr)
+                    : recover_depth_maps_host(fn, n_seq, cam_off, cams, imgs, &prm, out.data(), nullptr, nullptr, nullptr);
+    if (rc) return rc;
     std::vector<double> raw;
     size_t at = 0;
     for (int k = 0; k < n_seq; ++k) {                                                             // what Processor.cpp:37-38 reads
@@ -518,6 +522,32 @@ int mvs_processor_recover_depths_files(int32_t n_seq, const char* const* seq_dir
     std::vector<uint8_t> imgs(px ? 3 * px : 1);
     if ((rc = load_images_body(__func__, n_seq, seq_dirs, cam_off, cams, MVS_JPEG_RGB, imgs.data()))) return rc;
     return recover_depths_body(__func__, n_seq, seq_dirs, cam_off, cams, imgs.data(), params, px);
+}
+
+int mvs_processor_recover_depths_aggregated(int32_t n_seq, const char* const* seq_dirs, const int32_t* cam_off, const mvs_camera* cams,
+                                            const uint8_t* imgs, const mvs_depth_recover_params* params,
+                                            const mvs_depth_aggregate_params* aggregate) {
+    MVS_TRACE();
+    if (n_seq < 1) return bad(__func__, "n_seq must be >= 1");
+    if (!seq_dirs || !cam_off || !cams || !imgs) return bad(__func__, "seq_dirs, cam_off, cams and imgs must not be NULL");
+    size_t floats = 0;
+    int rc = check_seq_dirs(__func__, n_seq, seq_dirs, cam_off, cams, &floats);
+    if (rc) return rc;
+    return recover_depths_body(__func__, n_seq, seq_dirs, cam_off, cams, imgs, params, floats, true, aggregate);
+}
+
+int mvs_processor_recover_depths_aggregated_files(int32_t n_seq, const char* const* seq_dirs, const int32_t* cam_off, const mvs_camera* cams,
+                                                  const mvs_depth_recover_params* params, const mvs_depth_aggregate_params* aggregate) {
+    MVS_TRACE();
+    size_t px = 0;
+    int rc = check_seq_dirs(__func__, n_seq, seq_dirs, cam_off, cams, &px);
+    if (rc) return rc;
+    mvs_depth_recover_params prm;                                                                // every parameter error before a frame is read
+    if (params) prm = *params; else mvs_depth_recover_default_params(&prm);
+    if ((rc = recover_depth_maps_aggregated_check(__func__, n_seq, cam_off, cams, &prm, aggregate))) return rc;
+    std::vector<uint8_t> imgs(px ? 3 * px : 1);
+    if ((rc = load_images_body(__func__, n_seq, seq_dirs, cam_off, cams, MVS_JPEG_RGB, imgs.data()))) return rc;
+    return recover_depths_body(__func__, n_seq, seq_dirs, cam_off, cams, imgs.data(), &prm, px, true, aggregate);
 }
 
 int mvs_processor_colour_model(const char* model_obj, const char* srt_txt, int32_t n_seq, const int32_t* cam_off, const mvs_camera* cams,

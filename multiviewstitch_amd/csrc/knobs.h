@@ -28,6 +28,11 @@ inline double mvs_knob_env(const char* name, double dflt, double lo, double hi) 
 // an experiment knob: MVS_MATCH_PAIRS_LDS_CAP (environment, read at every call) can only lower it and never changes a result.
 #define MVS_MATCH_PAIRS_LDS_KEYS 4096
 
+// depth_sgm.hip: megabytes of device memory that the two uint16 volumes (C and S, 4 bytes per pixel and level) of one group of frames
+// may take when mvs_depth_aggregate_params.max_volume_mb is 0.  A 640 x 480 frame at 128 levels and N = 7 needs 143 MB, so a group holds
+// 28 such frames: 13000 rows for the row family, more waves than the device has slots.  The grouping never changes a result.
+#define MVS_SGM_VOLUME_MB 4096
+
 // trace level of the host side: MVS_DEBUG_CG=1 (plans, verdicts, set-up laps) or 2 (+ residual histories) in the
 // environment when the library is loaded; read once (runtime.cpp), 0 otherwise.  It changes no result.
 int mvs_debug_level();

@@ -48,7 +48,7 @@ int mvs_debug_level() {
 // runtime and the stream pool (mutex).  mvs_preload_wait (mvs_test.h) joins the work, for measurements.
 const void* const* mvs_tu_kernels_grid(int*); const void* const* mvs_tu_kernels_assoc(int*); const void* const* mvs_tu_kernels_knn(int*);
 const void* const* mvs_tu_kernels_arap(int*); const void* const* mvs_tu_kernels_schwarz(int*); const void* const* mvs_tu_kernels_meshbuild(int*);
-const void* const* mvs_tu_kernels_geom(int*);
+const void* const* mvs_tu_kernels_geom(int*); const void* const* mvs_tu_kernels_depth_sgm(int*);
 const void* mvs_tu_probe_srt(); const void* mvs_tu_probe_align(); const void* mvs_tu_probe_consist(); const void* mvs_tu_probe_render();
 const void* mvs_tu_probe_stitch(); const void* mvs_tu_probe_render_views(); const void* mvs_tu_probe_matchpairs(); const void* mvs_tu_probe_views();
 const void* mvs_tu_probe_siftmatch(); const void* mvs_tu_probe_sift(); const void* mvs_tu_probe_pointsample(); const void* mvs_tu_probe_compact();
@@ -68,7 +68,9 @@ void mvs_preload(int device) {
         if (hipSetDevice(device) == hipSuccess) {
             // the deformation path first, every kernel of it (a kernel's first launch otherwise pays its own resolution: the first
             // outer iteration of a fresh process took 5.6-7.5 ms against 0.8 ms warm with only the code objects loaded), in the
-            // order a fit meets the units; then one kernel of each remaining unit
+            // order a fit meets the units; then one kernel of each remaining unit; last, behind everything a fit or an older
+            // stage waits for, the kernels of the aggregated depth recovery (depth_sgm.hip; what these nine resolutions cost the thread has
+            // not been measured)
             stream_pool_prime(device);
             for (auto unit : {mvs_tu_kernels_meshbuild, mvs_tu_kernels_knn, mvs_tu_kernels_grid, mvs_tu_kernels_assoc, mvs_tu_kernels_arap, mvs_tu_kernels_schwarz,
                               mvs_tu_kernels_geom}) {
@@ -82,6 +84,9 @@ void mvs_preload(int device) {
                 hipFuncAttributes a;
                 if (hipFuncGetAttributes(&a, k) != hipSuccess) (void)hipGetLastError();
             }
+            int n = 0;
+            const void* const* ks = mvs_tu_kernels_depth_sgm(&n);
+            for (int i = 0; i < n; ++i) { hipFuncAttributes a; if (hipFuncGetAttributes(&a, ks[i]) != hipSuccess) (void)hipGetLastError(); }
         }
         std::lock_guard<std::mutex> lk(g_preload_mu);
         g_preload_done.push_back(device);

@@ -34,6 +34,13 @@ int refine_depth_maps_host(const char* fn, int32_t n_seq, const int32_t* cam_off
 // mvs_recover_depth_maps's host form (depth_recover.hip), validating and reporting under the name fn
 int recover_depth_maps_host(const char* fn, int32_t n_seq, const int32_t* cam_off, const mvs_camera* cams, const uint8_t* imgs,
                             const mvs_depth_recover_params* p, float* out, int16_t* level_out, int32_t* sum_out, uint8_t* cnt_out);
+// mvs_recover_depth_maps_aggregated's host form (depth_sgm.hip), validating and reporting under the name fn; ap may be NULL (defaults)
+int recover_depth_maps_aggregated_host(const char* fn, int32_t n_seq, const int32_t* cam_off, const mvs_camera* cams, const uint8_t* imgs,
+                                       const mvs_depth_recover_params* p, const mvs_depth_aggregate_params* ap, float* out, int16_t* level_out,
+                                       int32_t* sum_out, uint8_t* cnt_out, int32_t* agg_out);
+// its argument checks alone, but for the NULL tests of imgs and out: no device, no image is needed
+int recover_depth_maps_aggregated_check(const char* fn, int32_t n_seq, const int32_t* cam_off, const mvs_camera* cams,
+                                        const mvs_depth_recover_params* p, const mvs_depth_aggregate_params* ap);
 // mvs_colour_vertices_dev (colour.hip) under the name fn: validates, needs a device, colours; complete on return.  The two checks it
 // starts with are there for the file form, which has to fail before it reads a frame
 int colour_check_params(const char* fn, const mvs_colour_params* p);

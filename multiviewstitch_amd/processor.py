@@ -1149,7 +1149,11 @@ def RecoverDepthMaps(cameras, imgs, params: L.CDepthRecoverParams | None = None,
     -> a list with, per sequence, the rasters [frames, h, w] float32 (+0.0 where no level was accepted): what ``CheckConsistency``
     reads.  With ``with_detail`` each entry is (rasters, level [frames, h, w] int16, sum int32, cnt uint8): the winning level of
     every pixel (-1 where none was accepted), its sum of squared grey differences and the reference frames that took part."""
-    prm = params if params is not None else depth_recover_params()
+    return _recover(cameras, imgs, params if params is not None else depth_recover_params(), None, stream, with_detail)
+
+
+def _recover(cameras, imgs, prm, aprm, stream, with_detail):
+    """the call behind ``RecoverDepthMaps`` (``aprm`` None) and ``RecoverDepthMapsAggregated``"""
     n = len(cameras)
     off, cams = L.seq_cams(cameras)
     if len(imgs) != n:
@@ -1168,9 +1172,11 @@ def RecoverDepthMaps(cameras, imgs, params: L.CDepthRecoverParams | None = None,
         fimg, iptr = _flat_stack(imgs, n, dev, "uint8", "imgs")
         size = max(1, sum(int(np.prod(s, dtype=np.int64)) for s in shapes))
         out = _out_like(fimg, size, "float32")
-        det = tuple(_out_like(fimg, size, dt) for dt in ("int16", "int32", "uint8")) if with_detail else (None, None, None)
-        fn, tail = (L.lib().mvs_recover_depth_maps_dev, (L.ptr(stream),)) if dev else (L.lib().mvs_recover_depth_maps, ())
-        L.check(fn(n, L.ptr(off), cams, iptr, C.byref(prm), L.ptr(out), *[L.ptr(a) for a in det], *tail))
+        kinds = ("int16", "int32", "uint8") + (("int32",) if aprm is not None else ())
+        det = tuple(_out_like(fimg, size, dt) for dt in kinds) if with_detail else (None,) * len(kinds)
+        name = "mvs_recover_depth_maps" + ("_aggregated" if aprm is not None else "") + ("_dev" if dev else "")
+        head = (C.byref(prm),) + ((C.byref(aprm),) if aprm is not None else ())
+        L.check(getattr(L.lib(), name)(n, L.ptr(off), cams, iptr, *head, L.ptr(out), *[L.ptr(a) for a in det], *((L.ptr(stream),) if dev else ())))
     res, at = [], 0
     for shape in shapes:
         m = int(np.prod(shape, dtype=np.int64))
@@ -1178,6 +1184,23 @@ def RecoverDepthMaps(cameras, imgs, params: L.CDepthRecoverParams | None = None,
         res.append(cut if with_detail else cut[0])
         at += m
     return res
+
+
+def depth_aggregate_params(**kw) -> L.CDepthAggregateParams:
+    """``mvs_depth_aggregate_default_params`` (p1 8, p2 128, cost_cap 255 — choices nobody has measured on a real sequence; paths 8;
+    max_volume_mb 0: the library's budget) with the given fields replaced."""
+    return _params(L.CDepthAggregateParams, L.lib().mvs_depth_aggregate_default_params, kw)
+
+
+def RecoverDepthMapsAggregated(cameras, imgs, params: L.CDepthRecoverParams | None = None, aparams: L.CDepthAggregateParams | None = None,
+                               stream: int | None = None, with_detail: bool = False):
+    """``RecoverDepthMaps`` with semi-global path aggregation of the cost volume before the winner is taken
+    (``mvs_recover_depth_maps_aggregated``; the rules S1-S6, this library's definition: include/mvs.h).  Arguments and results as
+    ``RecoverDepthMaps``; ``aparams`` holds the penalties, the cost cap, the number of paths and the memory budget.  With ``with_detail``
+    each entry is (rasters, level int16, sum int32, cnt uint8, agg int32): the winner's raw sum and count, and its aggregated cost S
+    (-1 outside the rectangle of candidates)."""
+    return _recover(cameras, imgs, params if params is not None else depth_recover_params(),
+                    aparams if aparams is not None else depth_aggregate_params(), stream, with_detail)
 
 
 def _recover_files_args(seq_dirs, cameras):
@@ -1209,6 +1232,32 @@ def RecoverDepthFilesFromJpeg(seq_dirs, cameras, params: L.CDepthRecoverParams |
     n, dirs, off, cams = _recover_files_args(seq_dirs, cameras)
     prm = params if params is not None else depth_recover_params()
     L.check(L.lib().mvs_processor_recover_depths_files(n, dirs, L.ptr(off), cams, C.byref(prm)))
+
+
+def RecoverDepthFilesAggregated(seq_dirs, cameras, imgs, params: L.CDepthRecoverParams | None = None,
+                                aparams: L.CDepthAggregateParams | None = None) -> None:
+    """``mvs_processor_recover_depths_aggregated``: ``RecoverDepthFiles`` with ``RecoverDepthMapsAggregated`` in place of the plain sweep."""
+    n, dirs, off, cams = _recover_files_args(seq_dirs, cameras)
+    if len(imgs) != n:
+        raise L.MvsError(-1, f"{len(imgs)} image stacks for {n} sequences")
+    for k in range(n):
+        want = (len(cameras[k]),) + ((int(cameras[k][0].h), int(cameras[k][0].w), 3) if len(cameras[k]) else tuple(imgs[k].shape[1:]))
+        if tuple(imgs[k].shape) != want:
+            raise L.MvsError(-1, f"imgs[{k}] must be [frames, h, w, 3] = {want}")
+    flat, iptr = _flat_stack(imgs, n, False, "uint8", "imgs")
+    prm = params if params is not None else depth_recover_params()
+    aprm = aparams if aparams is not None else depth_aggregate_params()
+    L.check(L.lib().mvs_processor_recover_depths_aggregated(n, dirs, L.ptr(off), cams, iptr, C.byref(prm), C.byref(aprm)))
+
+
+def RecoverDepthFilesAggregatedFromJpeg(seq_dirs, cameras, params: L.CDepthRecoverParams | None = None,
+                                        aparams: L.CDepthAggregateParams | None = None) -> None:
+    """``mvs_processor_recover_depths_aggregated_files``: ``RecoverDepthFilesAggregated`` with the RGB frames read from
+    ``seq_dirs[k]``%05d.jpg."""
+    n, dirs, off, cams = _recover_files_args(seq_dirs, cameras)
+    prm = params if params is not None else depth_recover_params()
+    aprm = aparams if aparams is not None else depth_aggregate_params()
+    L.check(L.lib().mvs_processor_recover_depths_aggregated_files(n, dirs, L.ptr(off), cams, C.byref(prm), C.byref(aprm)))
 
 
 # ------------------------------------------------------------------ vertex colours ----

@@ -1530,6 +1530,85 @@ int mvs_srt_apply_dev(const double* pts_dev, const double* normals_dev, int64_t 
                       double s, const double* R, const double* t, int inverse,
                       double* out_pts_dev, double* out_normals_dev, void* hip_stream);
 
+/* ------------------------------------------- chain refinement (joint ICP) -- */
+/* Refine the SRT chain on the sequences' oriented points: a joint point-to-plane similarity ICP over the overlaps of ALL sequences,
+ * between the pairwise feature fit that made the chain (Processor.cpp:813-823) and the fusion of the points
+ * (mvs_processor_stitch_points).  The reference has no such stage.  The rules I1-I9 are this library's definition, NOT VERIFIED against
+ * any ZJU code; rel_dist = 0.02, min_cos = 0.7 and min_pairs = 64 are choices measured on no real sequence.  The per-match part (I1,
+ * I3-I6) is one host/device body, csrc/srt_refine_rules.h; tests/ref_srt_refine.py restates all nine in numpy.
+ *
+ * points, normals: the rows of each sequence's .npts in that sequence's OWN frame, segment k = [seg_off[k], seg_off[k+1]) (host,
+ * n_seq + 1 offsets ascending from 0).  scales[n_seq], R[n_seq*9] (row-major), t[n_seq*3]: the chain as mvs_visibility_cull takes
+ * it, read and, when a step was made, overwritten.  iters_done: the steps made.  history (optional, iters*2 doubles): per step the
+ * accepted matches of all pairs and the rms residual before the step, D sqrt(sum r^2 / count), in common-frame units; rows
+ * [iters_done, iters) are not written.  pair_count (optional, n_seq*n_seq): the accepted matches of the last search, [a*n_seq+b] for
+ * the queries of a against the points of b.
+ *
+ *   I1 maps      : entry k maps y = s_k R_k p + t_k as mvs_srt_apply does (M = s_k R_k element by element, then M p + t).  A normal is
+ *                  used as n / |n| in fp64.  A point takes part iff its three coordinates are finite and no larger than FLT_MAX in
+ *                  magnitude (they stay finite as float32): any other point is never a query and never a nearest point.  A point
+ *                  whose normal is not finite or has |n|^2 zero or not finite is still searched, and its match is rejected.
+ *   I2 frame     : once per call, from the input chain: lo, hi = the bounding box of the mapped points that take part, c = (lo+hi)/2,
+ *                  D = |hi-lo|/2, normalised coordinates x = (y-c)/D, the cap is 2 rel_dist.  No such point, D == 0 or D not finite
+ *                  is MVS_E_DEGENERATE.  The frame stays while the chain moves.
+ *   I3 search    : for every ordered pair (a, b), a != b, and every query i of a (i % stride == 0): the point is mapped into b's OWN
+ *                  frame by mvs_srt_relative(b, a) and mvs_srt_apply's expression in fp64, rounded to float32 (a result that is not
+ *                  finite has no match), and its nearest point j of b is found by d2f (float32, FLANN's accumulation order) over
+ *                  b's float32-rounded coordinates, ties to the lower index: the arithmetic and the tie rule of mvs_part_recog.
+ *   I4 accept    : iff, in fp64, |x_a - x_b|^2 <= cap^2 and (R_a n_a) . (R_b n_b) >= min_cos.  The search stops early only where that
+ *                  cannot change an acceptance: once every point within cap D / s_b * (1 + 1/64) + 2^-18 (E_b + cap D / s_b) of
+ *                  the query has been seen (E_b: the largest coordinate magnitude of b's grid box) and none is proven nearest, there
+ *                  is no match.  The slack covers the float32 rounding of both points and of d2f, and an R_b whose singular values
+ *                  lie within 1 +- 2^-7.
+ *   I5 terms     : with n = R_b n_b: r = n . (x_a - x_b) and the 14-vector J = [x_a x n, n, n . x_a, -(x_b x n), -n, -(n . x_b)]:
+ *                  the derivative of r by (w, tau, sigma) of a, then of b (I8).  n is held fixed (point to plane).
+ *   I6 sums      : per ordered pair, int64: the count; q(J_i J_j) for i <= j, row by row (105); q(J_i r) (14); q(r r): 121 numbers,
+ *                  q(v) = llrint(v * 2^36), every product one fp64 multiply.  |entries| <= 1 by I2 (a little more once the chain has
+ *                  moved), so the 2^24 queries a sequence may have cannot overflow.  Integer adds commute: two runs give the same
+ *                  bytes.  These 121 numbers per pair are all that leaves the device per iteration.
+ *   I7 solve     : on the host.  The 7 n_seq square normal matrix H = sum J^T J and the gradient g = sum J r from the dequantised
+ *                  sums, pairs added in ascending (a, b) order.  The rows and columns of fixed_seq (-1: the last sequence, the
+ *                  chain's identity, Processor.cpp:851-853), of every HELD sequence — fewer than min_pairs accepted matches this
+ *                  iteration as query or target over all pairs, or none at all — and, with MVS_SRT_REFINE_FIX_SCALE, every scale
+ *                  column are dropped; damping * (the largest diagonal entry) is added to every diagonal entry; H step = -g by
+ *                  Cholesky factorisation in plain row order, no pivoting.  A pivot <= 0 is MVS_E_SOLVER.  An iteration in which no
+ *                  sequence is free ends the call without a step: when that is the first, the call returns MVS_OK with the
+ *                  chain's bytes unchanged and iters_done = 0.
+ *   I8 step      : (w, tau, sigma) of sequence k acts in the normalised frame, x' = e^sigma Exp(w) x + tau: dR = Exp(w) (Rodrigues:
+ *                  I + sin(th)/th K + (1 - cos th)/th^2 K^2, th = |w|; I for th == 0), g = e^sigma, s' = g s, R' = dR R,
+ *                  t' = g dR t + (c - g dR c + D tau).
+ *   I9 stop      : after the iteration whose largest |step entry| is below tol, or after `iters` iterations.
+ *
+ * Device side: the n_seq target grids are built once per call, in each sequence's own frame (knn.hip's grid); each iteration is ONE
+ * launch over all ordered pairs and one wait: the sums come down, the host solves, the 13 n_seq doubles of the chain go up.  Scratch
+ * from the stream-ordered pool: 24 bytes per point, a grid per sequence, 968 n_seq^2 bytes of sums.
+ * MVS_E_INVALID_ARG, before a device is needed, naming the entry: a NULL pointer other than params (NULL: the defaults), history or
+ * pair_count; n_seq < 2 or above 128; offsets that do not ascend from 0 or reach 2^31 - 1; more than 2^24 queries in one sequence;
+ * rel_dist outside (0, 1], min_cos outside [-1, 1], damping or tol negative or not finite, iters outside 1..64, stride < 1,
+ * fixed_seq outside -1..n_seq-1, min_pairs < 0, unknown flags, reserved != 0; a scale that is not finite and positive, an R or t
+ * that is not finite. */
+enum { MVS_SRT_REFINE_FIX_SCALE = 1 };           /* 6 instead of 7 unknowns per sequence */
+typedef struct mvs_srt_refine_params {
+    double  rel_dist;    /* 0.02  match cap, as a fraction of the bounding-box diagonal of all mapped points (I2) */
+    double  min_cos;     /* 0.7   least dot product of the two unit normals in the common frame */
+    double  damping;     /* 1e-9  times the largest diagonal entry, added to every diagonal entry (I7) */
+    double  tol;         /* 1e-9  stop when no entry of the step exceeds it (I9) */
+    int32_t iters;       /* 20    at most, 1..64 */
+    int32_t stride;      /* 1     point i of a sequence is a query iff i % stride == 0 */
+    int32_t fixed_seq;   /* -1    the sequence that does not move; -1 = the last (the chain's identity, Processor.cpp:851-853) */
+    int32_t min_pairs;   /* 64    a sequence with fewer accepted matches (as query or target, all pairs) is held this iteration */
+    int32_t flags, reserved;
+} mvs_srt_refine_params;
+void mvs_srt_refine_default_params(mvs_srt_refine_params* p);
+int mvs_srt_refine(const double* points, const double* normals, const int64_t* seg_off, int32_t n_seq,
+                   double* scales, double* R, double* t, const mvs_srt_refine_params* p,
+                   int32_t* iters_done, double* history, int64_t* pair_count);
+/* Same with the points and normals in HBM; the chain and the reports stay host arrays.  Everything is ordered on hip_stream (NULL =
+ * legacy default stream); returns with the work complete. */
+int mvs_srt_refine_dev(const double* points_dev, const double* normals_dev, const int64_t* seg_off, int32_t n_seq,
+                       double* scales, double* R, double* t, const mvs_srt_refine_params* p,
+                       int32_t* iters_done, double* history, int64_t* pair_count, void* hip_stream);
+
 /* ------------------------------------------------- stitch tail (f1) -- */
 /* The visibility cull of Processor::AlignmentSeq: a point stays iff, for every sequence k0 and every camera c of k0, the point
  * mapped into k0's frame projects inside c's image (Camera::GetImgCoordFromWorld, R/Camera/Camera.cpp:45-48,68-72, then

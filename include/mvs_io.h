@@ -86,6 +86,15 @@ int mvs_processor_stitch_points(int32_t n_seq, const char* const* npts_paths, co
                                 const double* t, const int32_t* cam_off, const mvs_camera* cams, uint32_t flags,
                                 const char* out_dir, int64_t* n_keep);
 
+/* mvs_srt_refine on files, between mvs_processor_point_sample and mvs_processor_stitch_points: read npts_paths[k] (mvs_npts_read) as
+ * sequence k's points and normals and the chain of n_seq entries from srt_in (mvs_srt_txt_read: float32, as the reference reads
+ * SRT.txt), refine, and write the chain to srt_out (mvs_srt_txt_write; srt_out may be srt_in) — also when no step was made.  The
+ * files are read before a device is needed: a missing or short file is MVS_E_IO naming it.  p may be NULL (the defaults); iters_done
+ * and history (optional, iters*2) as mvs_srt_refine.  MVS_E_INVALID_ARG under this entry's name: a NULL path, n_seq < 2, and what
+ * mvs_srt_refine refuses. */
+int mvs_processor_refine_srt(int32_t n_seq, const char* const* npts_paths, const char* srt_in, const mvs_srt_refine_params* p,
+                             const char* srt_out, int32_t* iters_done, double* history);
+
 /* The trim of the Poisson model after GeometryRec (R/Processor/Processor.cpp:1057-1105): ReadObj(model_obj) — normals from the
  * `vn` lines, computed as mvs_mesh_vertex_normals when the file has none (R/PlyObj/PlyObj.cpp:3-16) —, then with all_seq_proj
  * (ParamParser::isAllSeqProj) the cull MVS_CULL_ALL_SEQ and the facet remap (a facet stays iff its three vertices do,

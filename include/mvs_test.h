@@ -172,6 +172,19 @@ int mvs_test_match_overlays_timed(int32_t n1, int32_t n2, int32_t w, int32_t h, 
                                   const int64_t* match_offsets, const int32_t* matches, uint64_t* rng_state, uint8_t* out_dev, void* hip_stream,
                                   double* ms);
 
+/* ONE search-and-sum launch of mvs_srt_refine for the given chain, and nothing else: host arrays and argument checks as that entry
+ * (the chain is only read); sums [n_seq*n_seq*121] int64 receives the sums of I6, slot a*n_seq+b, in the order count | J_i J_j, i <= j,
+ * row by row | J_i r | r r; c_D [4] (may be NULL) the c and D of I2. */
+int mvs_test_srt_refine_sums(const double* points, const double* normals, const int64_t* seg_off, int32_t n_seq, const double* scales,
+                             const double* R, const double* t, const mvs_srt_refine_params* p, int64_t* sums, double* c_D);
+/* ... with the reduction of the 121 sums chosen (form 0: a butterfly per term over the wave, what the entry runs; 1: LDS atomics of
+ * every accepted lane) and, when ms is given, `reps` further launches of that form timed by HIP events around them: ms [3] receives
+ * the milliseconds of one launch, of one host solve of I7 on the sums (every sequence but the fixed one free; -1 when it fails) and of
+ * the set-up in front of the first search (I2 and the grids, host clock, synchronised) (scripts/bench_srt_refine.py). */
+int mvs_test_srt_refine_timed(const double* points, const double* normals, const int64_t* seg_off, int32_t n_seq, const double* scales,
+                              const double* R, const double* t, const mvs_srt_refine_params* p, int64_t* sums, double* c_D, int32_t form,
+                              int32_t reps, double* ms);
+
 #ifdef __cplusplus
 }
 #endif

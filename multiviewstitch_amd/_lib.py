@@ -100,6 +100,12 @@ class CColourParams(C.Structure):
     _fields_ = [("min_cos", C.c_double), ("occ_tol", C.c_double), ("flags", C.c_int32), ("fill", C.c_uint8 * 3), ("reserved", C.c_uint8)]
 
 
+class CSrtRefineParams(C.Structure):
+    """struct mvs_srt_refine_params."""
+    _fields_ = [("rel_dist", C.c_double), ("min_cos", C.c_double), ("damping", C.c_double), ("tol", C.c_double), ("iters", C.c_int32),
+                ("stride", C.c_int32), ("fixed_seq", C.c_int32), ("min_pairs", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
 class CJpegInfo(C.Structure):
     """struct mvs_jpeg_info_t."""
     _fields_ = [(k, C.c_int32) for k in ("w", "h", "components", "h_samp", "v_samp", "restart_interval", "n_segments", "sof")]
@@ -288,6 +294,9 @@ _SIGS = {
     "mvs_srt_relative": (C.c_int, [_D, _VP, _VP, _D, _VP, _VP, _VP, _VP, _VP]),
     "mvs_srt_apply": (C.c_int, [_VP, _VP, _I64, _D, _VP, _VP, _I32, _VP, _VP]),
     "mvs_srt_apply_dev": (C.c_int, [_VP, _VP, _I64, _D, _VP, _VP, _I32, _VP, _VP, _VP]),
+    "mvs_srt_refine_default_params": (None, [_VP]),
+    "mvs_srt_refine": (C.c_int, [_VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "mvs_srt_refine_dev": (C.c_int, [_VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mvs_visibility_cull": (C.c_int, [_VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _VP]),
     "mvs_visibility_cull_dev": (C.c_int, [_VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP]),
     "mvs_mesh_vertex_normals": (C.c_int, [_I64, _VP, _I64, _VP, _VP]),
@@ -382,6 +391,7 @@ _SIGS = {
     "mvs_parts_read": (C.c_int, [C.c_char_p, _I64, _VP]),
     "mvs_processor_deform": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, _VP, _D, _VP, C.c_char_p, _VP]),
     "mvs_processor_stitch_points": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP, _U32, C.c_char_p, _VP]),
+    "mvs_processor_refine_srt": (C.c_int, [_I32, _VP, C.c_char_p, _VP, C.c_char_p, _VP, _VP]),
     "mvs_processor_cull_model": (C.c_int, [C.c_char_p, _I32, _VP, _VP, _VP, _VP, _VP, _I32, C.c_char_p, _VP, _VP]),
     "mvs_processor_render": (C.c_int, [C.c_char_p, C.c_char_p, _I32, _VP, _VP, C.c_char_p, _VP, C.c_float, C.c_float, _VP]),
     "mvs_processor_refine_depths": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP]),
@@ -426,6 +436,8 @@ _SIGS = {
     "mvs_test_jpeg_encode_coef": (C.c_int, [_I32, _I32, _I32, _VP, _U32, _VP, _VP, _VP, _I64]),
     "mvs_test_rotations": (C.c_int, [_I64, _VP, _I32, _VP, _VP, _VP]),
     "mvs_test_match_overlays_timed": (C.c_int, [_I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "mvs_test_srt_refine_sums": (C.c_int, [_VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "mvs_test_srt_refine_timed": (C.c_int, [_VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _VP]),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -468,6 +480,8 @@ JPEG_GREY, JPEG_RESTART_ROW = 2, 65536      # MVS_JPEG_GREY, MVS_JPEG_RESTART_RO
 REFINE_SUBSTEP = 1                          # MVS_REFINE_SUBSTEP (include/mvs.h)
 RECOVER_SUBSTEP = 1                         # MVS_RECOVER_SUBSTEP (include/mvs.h)
 SGM_VOLUME_MB = 4096                        # MVS_SGM_VOLUME_MB (csrc/knobs.h): the budget behind max_volume_mb = 0; the host test pins it
+SRT_REFINE_FIX_SCALE = 1                    # MVS_SRT_REFINE_FIX_SCALE (include/mvs.h)
+SRT_REFINE_TERMS = 121                      # the int64 sums of one ordered pair (rule I6)
 COLOUR_BEST = 1                             # MVS_COLOUR_BEST (include/mvs.h)
 
 

@@ -12,7 +12,9 @@ detection in front of the cull, FeatureProc::DetectFeature (:14-75,103-112), thr
 the surface reconstruction between the stitch tail and the trim of the model, GeometryRec::RunPoisson (:1042-1058), through
 ``mvs_poisson_reconstruct``; the match and SIFT overlay pictures (:767-793, :604-615, FeatureProc.cpp:67-73) through
 ``mvs_match_overlays`` / ``mvs_sift_overlays`` and their file forms; the colours of the stitched model from the base images, a stage the
-reference does not have, through ``mvs_colour_vertices`` and ``mvs_processor_colour_model``.  The functions stand in pipeline order."""
+reference does not have, through ``mvs_colour_vertices`` and ``mvs_processor_colour_model``; the refinement of the SRT chain on the
+sampled points, another stage the reference does not have, through ``mvs_srt_refine`` and ``mvs_processor_refine_srt``.  The functions
+stand in pipeline order."""
 from __future__ import annotations
 
 import contextlib
@@ -619,6 +621,72 @@ def CalcSimilarityTransformationSeq(sequences, params: dict, state, srt_txt=None
     if srt_txt is not None:
         _io.write_srt_txt(srt_txt, scales, Rs, ts)
     return scales, Rs, ts, select
+
+
+# ------------------------------------------------------------------ chain refinement ----
+def srt_refine_params(**kw) -> L.CSrtRefineParams:
+    """``mvs_srt_refine_default_params`` (rel_dist 0.02, min_cos 0.7, damping 1e-9, tol 1e-9, iters 20, stride 1, fixed_seq -1: the last,
+    min_pairs 64, flags 0 — rel_dist, min_cos and min_pairs are choices nobody has measured on a real sequence) with the given fields
+    replaced."""
+    return _params(L.CSrtRefineParams, L.lib().mvs_srt_refine_default_params, kw)
+
+
+def RefineSRT(points, normals, scales, Rs, ts, params: L.CSrtRefineParams | None = None, stream: int | None = None):
+    """Joint similarity ICP of the SRT chain on the sequences' oriented points (``mvs_srt_refine``; the rules I1-I9, this library's
+    definition: include/mvs.h), between ``RunPointSample`` and the stitch tail.  ``points[k]``, ``normals[k]``: sequence k's rows
+    [m_k, 3] float64 in its own frame, as ``RunPointSample`` returns them — numpy arrays, or contiguous torch tensors on the GPU (the
+    device form: several tensors are first concatenated; ``stream`` is the HIP stream that produced them and everything is ordered on
+    it).  ``scales``, ``Rs``, ``ts``: the chain, not modified.
+    -> (scales [n], Rs [n, 3, 3], ts [n, 3], report): the refined chain and report = dict(iters_done, history [iters_done, 2]: accepted
+    matches and rms residual before each step in common-frame units, pair_count [n, n]: the accepted matches of the last search, queries
+    of row a against the points of column b)."""
+    prm = params if params is not None else srt_refine_params()
+    s = L.arr(scales, np.float64).reshape(-1).copy()
+    n = len(s)
+    if len(points) != n or len(normals) != n:
+        raise L.MvsError(-1, f"{len(points)} point sets and {len(normals)} normal sets for {n} sequences")
+    R = L.arr(Rs, np.float64).reshape(n, 3, 3).copy()
+    t = L.arr(ts, np.float64).reshape(n, 3).copy()
+    dev = n > 0 and all(_is_dev(a) for a in list(points) + list(normals))
+    if not dev and any(_is_dev(a) for a in list(points) + list(normals)):
+        raise L.MvsError(-1, "points and normals must all be tensors on the GPU or all arrays")
+    for k in range(n):
+        if len(points[k].shape) != 2 or points[k].shape[1] != 3 or tuple(normals[k].shape) != tuple(points[k].shape):
+            raise L.MvsError(-1, f"points[{k}] and normals[{k}] must both be [m, 3]")
+    off = np.zeros(n + 1, np.int64)
+    off[1:] = np.cumsum([int(p.shape[0]) for p in points])
+    done = C.c_int32(0)
+    hist = np.zeros((max(1, int(prm.iters)), 2), np.float64)
+    pc = np.zeros((n, n), np.int64)
+    with (_stream_order(stream) if dev else contextlib.nullcontext()):
+        if dev:
+            import torch
+            fp = torch.cat([p for p in points]) if n > 1 else points[0]
+            fn_ = torch.cat([q for q in normals]) if n > 1 else normals[0]
+            if fp.numel() == 0:
+                fp, fn_ = (torch.zeros((1, 3), dtype=torch.float64, device=fp.device) for _ in range(2))
+            pp, pn, fn, tail = _dev_ptr(fp, "float64", "points"), _dev_ptr(fn_, "float64", "normals"), L.lib().mvs_srt_refine_dev, (L.ptr(stream),)
+        else:
+            fp = np.ascontiguousarray(np.concatenate([L.arr(p, np.float64) for p in points])) if n else np.zeros((1, 3))
+            fn_ = np.ascontiguousarray(np.concatenate([L.arr(q, np.float64) for q in normals])) if n else np.zeros((1, 3))
+            if fp.size == 0:
+                fp, fn_ = np.zeros((1, 3)), np.zeros((1, 3))
+            pp, pn, fn, tail = L.ptr(fp), L.ptr(fn_), L.lib().mvs_srt_refine, ()
+        L.check(fn(pp, pn, L.ptr(off), n, L.ptr(s), L.ptr(R), L.ptr(t), C.byref(prm), C.byref(done), L.ptr(hist), L.ptr(pc), *tail))
+    return s, R, t, dict(iters_done=done.value, history=hist[:done.value].copy(), pair_count=pc)
+
+
+def RefineSRTFiles(npts_paths, srt_in, srt_out, params: L.CSrtRefineParams | None = None) -> dict:
+    """``mvs_processor_refine_srt``: sequence k's ``npts_paths[k]`` (what ``PointSampleFiles`` wrote) and the chain of ``srt_in`` (SRT.txt)
+    -> the refined chain in ``srt_out``, the file a caller passes on to ``StitchPointSets`` (through ``io.read_srt_txt``).
+    -> dict(iters_done, history) as ``RefineSRT``."""
+    prm = params if params is not None else srt_refine_params()
+    n = len(npts_paths)
+    paths = (C.c_char_p * max(1, n))(*[os.fsencode(p) for p in npts_paths])
+    done = C.c_int32(0)
+    hist = np.zeros((max(1, int(prm.iters)), 2), np.float64)
+    L.check(L.lib().mvs_processor_refine_srt(n, paths, os.fsencode(srt_in), C.byref(prm), os.fsencode(srt_out), C.byref(done), L.ptr(hist)))
+    return dict(iters_done=done.value, history=hist[:done.value].copy())
 
 
 # ------------------------------------------------------------------ stitch tail ----
